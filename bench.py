@@ -14,7 +14,11 @@ GPU keeps up to ~530 M paths in flight (min(spp, 256 x N) samples of its 1/N of 
 Rays = ray segments for which a closest-hit query ran, counted on the device.
 The scene, BVH and path state are resident in HBM before the timed region starts.
 
-The JSON line also carries:
+A plain run only sets up, warms up, times the steps and prints the line (`roofline`, `cpu_baseline` and `secondary` are
+null).  --dump-outputs DIR also writes what the last timed step handed its caller (rank 0's gathered film: rgb.npy and
+weight.npy, float32); the inputs are fixed by the arguments, so two builds can be compared output for output.
+
+With --full the JSON line also carries, each taking work of its own outside the timed steps:
   roofline      the dominant kernel (k_traverse8_persistent) against the roof that binds it: VECTOR-INSTRUCTION ISSUE.
                 achieved = wave-level VALU instructions the algorithm needs per launch (node-loop and triangle-loop trip
                 counts MEASURED by the instrumented instance on this input x the loops' static VALU counts from the
@@ -93,6 +97,37 @@ def isa_counts(instance):
     return dict(VALU_FALLBACK, source="bench.py VALU_FALLBACK", kernel_sha16=None)
 
 
+DUMP_MAX_PIXELS = 3_000_000  # 48 MB of rgb + weight; larger frames (C4 at 3840x2160) are written as a fixed pixel sample
+
+
+def dump_outputs(out_dir, rgb, weight, W, H):
+    """--dump-outputs: the (rgb, weight) tensors FilmGather returned for the last timed step, as rgb.npy (H, W, 3) and
+    weight.npy (H, W); above DUMP_MAX_PIXELS the same seeded pixel sample of both, as (n, 3) and (n,)."""
+    import numpy as np
+    a = rgb.cpu().numpy().reshape(H * W, 3)
+    w = weight.cpu().numpy().reshape(H * W)
+    if H * W > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(0).choice(H * W, DUMP_MAX_PIXELS, replace=False))
+        a, w = a[idx], w[idx]
+    else:
+        a, w = a.reshape(H, W, 3), w.reshape(H, W)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rgb.npy"), a.astype(np.float32))
+    np.save(os.path.join(out_dir, "weight.npy"), w.astype(np.float32))
+
+
+def build(load=True):
+    """__graft_entry__.build(), which takes its lock in the source tree.  A checkout built by another user that this one may
+    not write to is used as it was built; a library that was never built still fails the package import."""
+    import __graft_entry__ as g
+    try:
+        g.build(quiet=True, load=load)
+    except PermissionError as e:
+        print(f"bench.py: cannot write to the source tree ({e}); using the libraries built there", file=sys.stderr)
+        if load:
+            import parallelraytracing_amd  # noqa: F401
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -104,6 +139,10 @@ def parse():
     ap.add_argument("--jitter", type=int, default=0, help="1 = jittered primary rays (PrtSampling.jitter), an A/B / profiling option")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--wide", type=int, default=2, help="2 = compressed 8-wide tree (default), 1 = 4-wide tree (A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline (instrumented traversal batch, per-kernel timing of the timed steps), "
+                         "the CPU baseline and the secondary block; --no-kernel-timing, --no-cpu-baseline and "
+                         "--no-secondary leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary block (other configs, jittered C3, presets)")
@@ -111,7 +150,12 @@ def parse():
     ap.add_argument("--no-overlap", action="store_true", help="per-frame gather on the render stream instead of a side stream")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL over xGMI) | gloo (rehearsal on a box with fewer GPUs)")
     ap.add_argument("--dump", default="", help="write the final frame as PPM/PFM with this path prefix")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's gathered film as DIR/rgb.npy and DIR/weight.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def time_config(prt, torch, name, device, spp_step, steps, sampling=None, params=None):
@@ -207,8 +251,7 @@ def launch_ranks(args):
     import socket
     import subprocess
 
-    import __graft_entry__ as g
-    g.build(quiet=True, load=False)  # once, here: the ranks then find everything up to date
+    build(load=False)  # once, here: the ranks then find everything up to date
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
@@ -263,8 +306,7 @@ def main():
     import torch
     import torch.distributed as dist
 
-    import __graft_entry__ as g
-    g.build(quiet=True)
+    build()
     import parallelraytracing_amd as prt
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -318,26 +360,30 @@ def main():
     gather = prt.dist.FilmGather(r, device, overlap=not args.no_overlap)
     setup_s = time.time() - t_setup
 
-    # trip counts and algorithmic traffic of the dominant kernel, measured with the instrumented traversal on the first
-    # samples (a batch of up to 64 samples, like the timed batches: with compact primary rays a wave of bounce 0 holds 64
-    # samples of one pixel, which a one-sample batch cannot show in the active-lane fractions; counts are per sample below)
-    n_meas = max(1, min(64, sif))
-    r.set_param("measure_spp", n_meas)
-    trav = r.measure_traversal(sample=0)
-    rays_sample = int(trav.rays_total) // n_meas
-    rays_walked = int(trav.rays_traversed) // n_meas  # rays that enter the BVH root box; the others never reach this kernel
-    wide8 = int(bvh.n_nodes8) > 0 and args.wide == 2
-    node_bytes = NODE_BYTES if wide8 else NODE_BYTES4
-    kernel_name = "k_traverse8_persistent" if wide8 else "k_traverse4_persistent"
-    node_visits_sample = int(trav.bvh_node_visits) // n_meas
-    tri_tests_sample = int(trav.bvh_tri_tests) // n_meas
-    alg_bytes_sample = node_bytes * node_visits_sample + TRI_BYTES * tri_tests_sample + RAY_FIXED_BYTES * rays_walked
-    node_wave_steps_sample = int(trav.node_lane_slots) / 64.0 / n_meas   # trips of the node loop, summed over waves
-    tri_rounds_sample = int(trav.tri_lane_slots) / 64.0 / n_meas         # trips of the triangle loop
+    rays_sample = None
+    if args.full:
+        # trip counts and algorithmic traffic of the dominant kernel, measured with the instrumented traversal on the first
+        # samples (a batch of up to 64 samples, like the timed batches: with compact primary rays a wave of bounce 0 holds 64
+        # samples of one pixel, which a one-sample batch cannot show in the active-lane fractions; counts are per sample
+        # below).  The batch leaves the film and the sample index alone.
+        n_meas = max(1, min(64, sif))
+        r.set_param("measure_spp", n_meas)
+        trav = r.measure_traversal(sample=0)
+        rays_sample = int(trav.rays_total) // n_meas
+        rays_walked = int(trav.rays_traversed) // n_meas  # rays that enter the BVH root box; the others never reach this kernel
+        wide8 = int(bvh.n_nodes8) > 0 and args.wide == 2
+        node_bytes = NODE_BYTES if wide8 else NODE_BYTES4
+        kernel_name = "k_traverse8_persistent" if wide8 else "k_traverse4_persistent"
+        node_visits_sample = int(trav.bvh_node_visits) // n_meas
+        tri_tests_sample = int(trav.bvh_tri_tests) // n_meas
+        alg_bytes_sample = node_bytes * node_visits_sample + TRI_BYTES * tri_tests_sample + RAY_FIXED_BYTES * rays_walked
+        node_wave_steps_sample = int(trav.node_lane_slots) / 64.0 / n_meas   # trips of the node loop, summed over waves
+        tri_rounds_sample = int(trav.tri_lane_slots) / 64.0 / n_meas         # trips of the triangle loop
+    kernel_timing = args.full and not args.no_kernel_timing
 
     def step():
         r.render_async(spp_step)
-        gather()
+        return gather()
 
     def barrier():
         if world > 1:
@@ -349,11 +395,11 @@ def main():
     barrier()
     r.synchronize()  # a tripped traversal watchdog or a full overflow list is an error here, not a fast-looking number
     r.reset_stats()
-    r.enable_timing(not args.no_kernel_timing)
+    r.enable_timing(kernel_timing)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -376,9 +422,13 @@ def main():
 
     value = rays_total / dt / 1e6
 
+    if args.dump_outputs and rank == 0:
+        gather.wait()
+        dump_outputs(args.dump_outputs, *last, W, H)
+
     # ---- roofline of the dominant kernel, this rank ----
     roofline = None
-    if not args.no_kernel_timing and st.intersect_launches:
+    if kernel_timing and st.intersect_launches:
         avg_ms = st.intersect_ms / st.intersect_launches
         # measure_traversal ran on THIS rank's tiles, so the per-sample figures are already the local share; a launch is one
         # depth of one batch of `sif` samples: per launch = per sample x samples / launches
@@ -486,7 +536,7 @@ def main():
     cpu = None
     orc = None
     cores = 1
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as orc
         # the GPU box gives one GPU slot a share of 16 host cores; PRT_CPU_THREADS overrides
         try:
@@ -521,7 +571,7 @@ def main():
 
     # ---- secondary block (N = 1): the other single-GPU configs, jittered C3, the reference's default scene ----
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         secondary = {"note": "same pipeline, timed in this run with inputs resident; reduced sample counts (spp_per_step x steps; "
                              "C3_jitter: the headline's own 256 samples per step), spp_per_step samples in flight; the headline "
                              "stays C3 without jitter"}

@@ -42,7 +42,7 @@ def test_bench_two_ranks_sharing_the_gpu_over_gloo_matches_one_rank(tmp_path):
     for n in (1, 2, "self"):
         dump = str(tmp_path / f"f{n}")
         args = ["--gpus", "1" if n == 1 else "2", "--steps", "1", "--warmup", "0", "--config", "C2", "--spp-per-step", "2",
-                "--no-cpu-baseline", "--no-secondary", "--dump", dump]
+                "--full", "--no-cpu-baseline", "--no-secondary", "--dump", dump]
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PRT_BENCH_SAME_DEVICE="1")
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)

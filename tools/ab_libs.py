@@ -24,7 +24,7 @@ def main():
             env = dict(os.environ)
             if t != "base":
                 env["PRT_LIB_PATH"] = os.path.join(CSRC, "ab", f"libprt_{t}.so")
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary"] + bench_args,
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary"] + bench_args,
                                env=env, capture_output=True, text=True)
             line = [l for l in p.stdout.splitlines() if l.startswith("{")]
             if p.returncode != 0 or not line:

@@ -6,7 +6,7 @@ TAG=$1; shift
 OUT=$ROOT/gpurun_out/bt_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --no-cpu-baseline --no-secondary --steps 3 --warmup 1 "$@" > $OUT/run.log 2>&1 || { tail -5 $OUT/run.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-secondary --steps 3 --warmup 1 "$@" > $OUT/run.log 2>&1 || { tail -5 $OUT/run.log; exit 1; }
 python3 - "$OUT" <<'PY' | tee $ROOT/gpurun_out/${TAG}_bounce_times.txt
 import csv, glob, sys
 rows = []

@@ -8,7 +8,7 @@
 # Outputs land in gpurun_out/<tag>/ (scratch); the summaries to commit are copied into gpurun_out/<tag>/profiles/.
 TAG=${1:-r2_x}
 shift
-ARGS="--no-cpu-baseline --no-secondary $*"
+ARGS="--full --no-cpu-baseline --no-secondary $*"
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 READ_FACTOR=${READ_FACTOR:-2.0}
