@@ -286,6 +286,20 @@ int prt_film_display(PrtContext* ctx, float exposure, float gamma, uint8_t* rgba
 int prt_camera_rays(PrtContext* ctx, uint32_t n, const float* px, const float* py, float* origins, float* dirs);
 /* Scene::Intersect for n rays (src/core/scene.h:22-25).  Host in/out. */
 int prt_closest_hit(PrtContext* ctx, uint32_t n, const float* origins, const float* dirs, PrtHit* hits);
+/* The same from DEVICE arrays (n x 3 floats each; d_hits: n PrtHit records), enqueued on the context's stream with no
+ * host wait. */
+int prt_closest_hit_device(PrtContext* ctx, uint32_t n, const void* d_origins, const void* d_dirs, void* d_hits);
+/* Occlusion (shadow-ray) query: occluded[i] = 1 iff tmax[i] > 0 and the closest hit of ray i (exactly what
+ * prt_closest_hit returns) lies at d2 < fl32(tmax[i] * tmax[i]); else 0.  A blocker at exactly tmax does not occlude,
+ * tmax = +inf occludes on any hit, a NaN / zero / negative tmax or a zero direction never occludes.  The walk stops at
+ * the first blocker it accepts.  Host arrays; synchronous, like prt_closest_hit; a ray the walk had to give up
+ * (two-level stack overflow) is an error, never a silent 0. */
+int prt_occluded(PrtContext* ctx, uint32_t n, const float* origins, const float* dirs, const float* tmax,
+                 uint8_t* occluded);
+/* The same from DEVICE arrays (n x 3 floats, n floats, n bytes), enqueued on the context's stream with no host wait; a
+ * traversal error is reported by the next prt_synchronize. */
+int prt_occluded_device(PrtContext* ctx, uint32_t n, const void* d_origins, const void* d_dirs, const void* d_tmax,
+                        void* d_occluded);
 /* MaterialHandle::Scatter + Emit for n (ray, hit, rng state) tuples (src/core/material.h:139-161).
  * rng_state is advanced in place. scattered[i] = 0/1. */
 int prt_scatter(PrtContext* ctx, uint32_t n, const float* in_dirs, const PrtHit* hits, uint32_t* rng_state,

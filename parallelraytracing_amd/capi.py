@@ -142,6 +142,9 @@ SIGNATURES = {
     "prt_film_display": (C.c_int, [_vp, C.c_float, C.c_float, C.POINTER(C.c_uint8)]),
     "prt_camera_rays": (C.c_int, [_vp, C.c_uint32, _fp, _fp, _fp, _fp]),
     "prt_closest_hit": (C.c_int, [_vp, C.c_uint32, _fp, _fp, C.POINTER(PrtHit)]),
+    "prt_closest_hit_device": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp]),
+    "prt_occluded": (C.c_int, [_vp, C.c_uint32, _fp, _fp, _fp, C.POINTER(C.c_uint8)]),
+    "prt_occluded_device": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "prt_scatter": (C.c_int, [_vp, C.c_uint32, _fp, C.POINTER(PrtHit), _u32p, _u32p, _fp, _fp, _fp, _fp]),
     "prt_enable_timing": (C.c_int, [_vp, C.c_int]),
     "prt_get_stats": (C.c_int, [_vp, C.POINTER(PrtStats)]),

@@ -1540,14 +1540,52 @@ int prt_camera_rays(PrtContext* c, uint32_t n, const float* px, const float* py,
     return PRT_OK;
 }
 
+// The ray-query pipeline on the context's stream, from device arrays (n x 3 origins / directions): closest hit
+// (d_tmax == nullptr: PrtHit records into d_hits) or occlusion (one byte per ray into d_occ).  No host wait.
+static int enqueue_query(PrtContext* c, uint32_t n, const float* d_o, const float* d_d, const float* d_tmax, PrtHit* d_hits,
+                         uint8_t* d_occ) {
+    int rc;
+    if ((rc = ensure_path_state(c, n))) return rc;
+    if ((rc = ensure_counters(c))) return rc;
+    if ((rc = ensure_spill(c))) return rc;
+    uint32_t* cnt = c->d_counts + (size_t)(PRT_MAX_DEPTH + 1) * PRT_CNT_STRIDE;  // a counter slot the render loop never uses
+    const int stack_depth = c->bvh.max_depth <= 31 ? 31 : 63;
+    const bool walk8 = c->variant == 0 || c->dsc.n_insts || !c->dsc.nodes;
+    if (d_tmax) {
+        // occlusion: every ray seeded with "miss at d2 = tmax^2", the analytic scan from that bound, the any-hit walk
+        // (or, with another traversal variant forced, the closest hit, which k_occlusion_bytes compares with the bound)
+        prt_launch_pack_occlusion_rays(c->stream, n, d_o, d_d, d_tmax, c->rb[0], cnt);
+        prt_launch_scan_prims_bounded(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n);
+        if (c->dsc.n_nodes) {
+            if (walk8)
+                prt_launch_occluded(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->bvh.max_depth,
+                                    c->bvh.max_stack4, c->tune);
+            else
+                prt_launch_intersect(c->stream, c->dsc, c->rb[0], cnt, n, stack_depth, c->variant, nullptr);
+        }
+        prt_launch_occlusion_bytes(c->stream, c->dsc, n, c->rb[0], d_tmax, d_occ);
+    } else {
+        prt_launch_pack_rays(c->stream, n, d_o, d_d, c->rb[0], cnt);
+        prt_launch_scan_prims(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n, nullptr);
+        if (c->dsc.n_nodes) {
+            if (walk8)
+                prt_launch_traverse(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->bvh.max_depth,
+                                    c->bvh.max_stack4, c->tune, nullptr);
+            else
+                prt_launch_intersect(c->stream, c->dsc, c->rb[0], cnt, n, stack_depth, c->variant, nullptr);
+        }
+        prt_launch_hit_records(c->stream, c->dsc, n, c->rb[0], d_hits);
+    }
+    HIPCHECK(c, hipGetLastError());
+    return PRT_OK;
+}
+
 int prt_closest_hit(PrtContext* c, uint32_t n, const float* origins, const float* dirs, PrtHit* hits) {
     int rc = need_device(c);
     if (rc) return rc;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     if (n == 0) return PRT_OK;
     if (!origins || !dirs || !hits) return fail(c, PRT_ERR_INVALID, "null array");
-    if ((rc = ensure_path_state(c, n))) return rc;
-    if ((rc = ensure_counters(c))) return rc;
     const size_t b3 = (size_t)n * 12;
     const size_t bh = (size_t)n * sizeof(PrtHit);
     if ((rc = ensure_scratch(c, 2 * b3 + bh + 64))) return rc;
@@ -1557,23 +1595,53 @@ int prt_closest_hit(PrtContext* c, uint32_t n, const float* origins, const float
     PrtHit* d_h = (PrtHit*)(base + ((2 * b3 + 15) & ~(size_t)15));
     HIPCHECK(c, hipMemcpyAsync(d_o, origins, b3, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipMemcpyAsync(d_d, dirs, b3, hipMemcpyHostToDevice, c->stream));
-    uint32_t* cnt = c->d_counts + (size_t)(PRT_MAX_DEPTH + 1) * PRT_CNT_STRIDE;  // a counter slot the render loop never uses
-    prt_launch_pack_rays(c->stream, n, d_o, d_d, c->rb[0], cnt);
-    const int stack_depth = c->bvh.max_depth <= 31 ? 31 : 63;
-    if ((rc = ensure_spill(c))) return rc;
-    prt_launch_scan_prims(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n, nullptr);
-    if (c->dsc.n_nodes) {
-        if (c->variant == 0 || c->dsc.n_insts || !c->dsc.nodes)
-            prt_launch_traverse(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->bvh.max_depth,
-                                c->bvh.max_stack4, c->tune, nullptr);
-        else
-            prt_launch_intersect(c->stream, c->dsc, c->rb[0], cnt, n, stack_depth, c->variant, nullptr);
-    }
-    prt_launch_hit_records(c->stream, c->dsc, n, c->rb[0], d_h);
-    HIPCHECK(c, hipGetLastError());
+    if ((rc = enqueue_query(c, n, d_o, d_d, nullptr, d_h, nullptr))) return rc;
     HIPCHECK(c, hipMemcpyAsync(hits, d_h, bh, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
+}
+
+int prt_closest_hit_device(PrtContext* c, uint32_t n, const void* d_origins, const void* d_dirs, void* d_hits) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (n == 0) return PRT_OK;
+    if (!d_origins || !d_dirs || !d_hits) return fail(c, PRT_ERR_INVALID, "null array");
+    return enqueue_query(c, n, (const float*)d_origins, (const float*)d_dirs, nullptr, (PrtHit*)d_hits, nullptr);
+}
+
+int prt_occluded(PrtContext* c, uint32_t n, const float* origins, const float* dirs, const float* tmax, uint8_t* occluded) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (n == 0) return PRT_OK;
+    if (!origins || !dirs || !tmax || !occluded) return fail(c, PRT_ERR_INVALID, "null array");
+    const size_t b3 = (size_t)n * 12, b1 = (size_t)n * 4;
+    const size_t off_t = (2 * b3 + 15) & ~(size_t)15, off_b = (off_t + b1 + 15) & ~(size_t)15;
+    if ((rc = ensure_scratch(c, off_b + n + 64))) return rc;
+    char* base = (char*)c->d_scratch;
+    float* d_o = (float*)base;
+    float* d_d = (float*)(base + b3);
+    float* d_t = (float*)(base + off_t);
+    uint8_t* d_b = (uint8_t*)(base + off_b);
+    HIPCHECK(c, hipMemcpyAsync(d_o, origins, b3, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_d, dirs, b3, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_t, tmax, b1, hipMemcpyHostToDevice, c->stream));
+    if ((rc = enqueue_query(c, n, d_o, d_d, d_t, nullptr, d_b))) return rc;
+    HIPCHECK(c, hipMemcpyAsync(occluded, d_b, n, hipMemcpyDeviceToHost, c->stream));
+    // waits for the stream and reports a ray the walk had to give up (two-level stack overflow): never a silent "not occluded"
+    return prt_synchronize(c);
+}
+
+int prt_occluded_device(PrtContext* c, uint32_t n, const void* d_origins, const void* d_dirs, const void* d_tmax,
+                        void* d_occluded) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (n == 0) return PRT_OK;
+    if (!d_origins || !d_dirs || !d_tmax || !d_occluded) return fail(c, PRT_ERR_INVALID, "null array");
+    return enqueue_query(c, n, (const float*)d_origins, (const float*)d_dirs, (const float*)d_tmax, nullptr,
+                         (uint8_t*)d_occluded);
 }
 
 int prt_scatter(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* hits, uint32_t* rng_state,

@@ -191,6 +191,16 @@ void prt_launch_camera_rays(hipStream_t st, const DevCamera& cam, uint32_t n, co
 void prt_launch_pack_rays(hipStream_t st, uint32_t n, const float* o, const float* d, const PrtRayBuf& out,
                           uint32_t* counts);
 void prt_launch_hit_records(hipStream_t st, const DevScene& sc, uint32_t n, const PrtRayBuf& in, PrtHit* out);
+// occlusion queries (prt_occluded): pack + seed (hit = HIT_MISS at hd2 = tmax^2, or HIT_DEAD), the analytic scan from that
+// bound, the any-hit walk, one byte per ray
+void prt_launch_pack_occlusion_rays(hipStream_t st, uint32_t n, const float* o, const float* d, const float* tmax,
+                                    const PrtRayBuf& out, uint32_t* counts);
+void prt_launch_scan_prims_bounded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
+                                   uint32_t* work, uint32_t max_rays);
+void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr, uint32_t* work,
+                         uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune);
+void prt_launch_occlusion_bytes(hipStream_t st, const DevScene& sc, uint32_t n, const PrtRayBuf& in, const float* tmax,
+                                uint8_t* out);
 void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, const float* in_d, const PrtHit* hits,
                              uint32_t* rng_io, uint32_t* scattered, float* atten, float* emitted, float* o_out,
                              float* d_out);

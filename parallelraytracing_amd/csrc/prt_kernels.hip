@@ -1626,16 +1626,17 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse4_persistent(DevScene sc
     T8_HALF(w1.w, nxb, fxb, nyb, fyb, nzb, fzb)
 
 #define T8_SENTINEL 0xFFFFFFFFu
-template <int STACK_L, int WAVES, bool STATS, bool INST, bool LEAN = false, bool PRIM = false, bool PATH = false>
-__global__ void __launch_bounds__(256, WAVES) k_traverse8_persistent(DevScene sc, const float4* __restrict__ ro,
-                                                                    const float4* __restrict__ rd,
-                                                                    uint32_t* __restrict__ hit,
-                                                                    const float* __restrict__ hd2,
-                                                                    const uint32_t* __restrict__ count_ptr,
-                                                                    uint32_t* __restrict__ work,
-                                                                    uint32_t* __restrict__ ovf, PrtTravTuning tune,
-                                                                    unsigned long long* __restrict__ stats, PrtPrimary pr,
-                                                                    PrtPathArgs pa) {
+// The body of the 8-wide walk, shared by the closest-hit kernel (k_traverse8_persistent, ANY = false) and the occlusion
+// kernel (k_occluded8_persistent, ANY = true).  ANY: any-hit walk.  Every ray arrives seeded with the bound "miss at
+// d2 = tmax^2" (k_pack_occlusion_rays + k_scan_prims_bounded); a ray whose seeded hit is already a blocker is not walked,
+// and a lane whose ray has a triangle accepted below its bound in a triangle phase is done: its stack and pending group
+// are dropped (the phase has tested all queued items, the queue is empty after it) and its helpers end with it.
+template <int STACK_L, int WAVES, bool STATS, bool INST, bool LEAN, bool PRIM, bool PATH, bool ANY>
+__device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __restrict__ ro, const float4* __restrict__ rd,
+                                               uint32_t* __restrict__ hit, const float* __restrict__ hd2,
+                                               const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ work,
+                                               uint32_t* __restrict__ ovf, PrtTravTuning tune,
+                                               unsigned long long* __restrict__ stats, PrtPrimary pr, PrtPathArgs pa) {
     // PRIM: the rays are compact primary rays (PrtPrimary): origin and direction are rebuilt from the path id
     // PATH (PrtPathArgs, prt_kernels.h): the work items are whole PATHS, not rays.  A lane whose walk is over is not
     // released: it waits (need_shade) until refill_min lanes of the wave wait or are idle, then those lanes run the shade
@@ -1670,6 +1671,7 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse8_persistent(DevScene sc
     // wave-uniform 64-bit mask rebuilt from the helpers' k every outer iteration of a draining wave.)
     constexpr bool STEAL = LEAN && !INST;
     static_assert(!PATH || (!LEAN && !INST && !PRIM && !STATS), "the path instance is the plain one-level kernel");
+    static_assert(!ANY || (!PATH && !PRIM && !STATS), "the any-hit walk reads plain ray buffers");
     const uint32_t count = PATH ? pa.n_paths : *count_ptr;
     // PATH: the path a busy lane carries (k = its path id): direction as stored (the walk normalises it again, as the
     // reference's TransformNormal does), throughput, RNG state, segment index; need_shade: the walk of the current
@@ -2061,7 +2063,7 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse8_persistent(DevScene sc
                 if (idle && qi_seq < cur_end) {
                     const uint32_t qi = (!PRIM && tune.perm) ? tune.perm[qi_seq] : qi_seq;  // (sort_rays: a measurement aid)
                     uint32_t hid = PRIM ? HIT_MISS : ld_stream(&hit[qi]);
-                    if (hid != HIT_DEAD) {
+                    if (hid != HIT_DEAD && !(ANY && hid != HIT_MISS)) {  // (ANY: an analytic hit below tmax already blocks)
                         float4 O, D;
                         float hd2_0 = 0.0f;
                         if (PRIM) {
@@ -2294,8 +2296,12 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse8_persistent(DevScene sc
                                 }
                                 key = ((unsigned long long)__float_as_uint(d2) << 32) | prim;
                                 // NaN / inf d2 have bit patterns above FLT_MAX's: they can never win, as in the reference
-                                cand = true;
-                                atomicMin(&s_key[wbase + owner], key);
+                                if (ANY)  // only a key below the bound is a blocker: a candidate equal to the seed (prim 0, d2 == tmax^2) is not
+                                    cand = key < atomicMin(&s_key[wbase + owner], key);
+                                else {
+                                    cand = true;
+                                    atomicMin(&s_key[wbase + owner], key);
+                                }
                             }
                         }
                         if (STATS && lane == 0) ++s_iters[4 + wv];
@@ -2309,11 +2315,26 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse8_persistent(DevScene sc
                     ((volatile unsigned long long*)s_key)[(STEAL && k >= 0xFFFFFF00u && k != 0xFFFFFFFFu) ? wbase + (k & 63u) : tid];
                 if (LEAN) {
                     tlimit = limit_from_d2(__uint_as_float((uint32_t)(won >> 32)), pad);  // same value if nothing changed
+                    // ANY: the ray (of this lane, or of the root it helps) has a blocker once its slot names a triangle
+                    if (ANY && k != 0xFFFFFFFFu &&
+                        ((volatile uint32_t*)s_slot)[(STEAL && k >= 0xFFFFFF00u) ? wbase + (k & 63u) : tid] != HIT_MISS) {
+                        gy = 0u;
+                        sp = 0;
+                    }
                 } else if (won != key_best) {
                     best.d2 = __uint_as_float((uint32_t)(won >> 32));
                     best.prim = (uint32_t)won;
                     best.id = sc.n_prims + ((volatile uint32_t*)s_slot)[tid];
                     tlimit = INST ? (limit_from_d2(best.d2, 0.0f) + padw4) * lscale + 4.0f * pad : limit_from_d2(best.d2, pad);
+                    if (ANY && k != 0xFFFFFFFFu) {  // a blocker: drop the stack, the pending group and (INST) the level state
+                        gy = 0u;
+                        sp = 0;
+                        if (INST) {
+                            ipm = 0u;
+                            in_blas = false;
+                            stall = false;
+                        }
+                    }
                 }
                 pending = false;  // everything that was queued has been tested
             }
@@ -2361,6 +2382,36 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse8_persistent(DevScene sc
         if (threadIdx.x < 4) atomicAdd(&stats[3], 64ull * s_iters[threadIdx.x]);
         if (threadIdx.x < 4) atomicAdd(&stats[4], 64ull * s_iters[4 + threadIdx.x]);
     }
+}
+
+template <int STACK_L, int WAVES, bool STATS, bool INST, bool LEAN = false, bool PRIM = false, bool PATH = false>
+__global__ void __launch_bounds__(256, WAVES) k_traverse8_persistent(DevScene sc, const float4* __restrict__ ro,
+                                                                    const float4* __restrict__ rd,
+                                                                    uint32_t* __restrict__ hit,
+                                                                    const float* __restrict__ hd2,
+                                                                    const uint32_t* __restrict__ count_ptr,
+                                                                    uint32_t* __restrict__ work,
+                                                                    uint32_t* __restrict__ ovf, PrtTravTuning tune,
+                                                                    unsigned long long* __restrict__ stats, PrtPrimary pr,
+                                                                    PrtPathArgs pa) {
+    traverse8_body<STACK_L, WAVES, STATS, INST, LEAN, PRIM, PATH, false>(sc, ro, rd, hit, hd2, count_ptr, work, ovf, tune,
+                                                                         stats, pr, pa);
+}
+
+// Occlusion queries (prt_occluded): the any-hit walk of the 8-wide tree.  hit[] holds HIT_MISS for the rays to walk
+// (anything else is final: HIT_DEAD, or an analytic blocker), hd2[] their seeded bound tmax^2.  On return hit[] holds a
+// blocker's id or HIT_MISS; rays that overflowed the LDS stack are on the overflow list (one-level trees) as in
+// k_traverse8_persistent.
+template <int STACK_L, int WAVES, bool INST, bool LEAN = false>
+__global__ void __launch_bounds__(256, WAVES) k_occluded8_persistent(DevScene sc, const float4* __restrict__ ro,
+                                                                    const float4* __restrict__ rd,
+                                                                    uint32_t* __restrict__ hit,
+                                                                    const float* __restrict__ hd2,
+                                                                    const uint32_t* __restrict__ count_ptr,
+                                                                    uint32_t* __restrict__ work,
+                                                                    uint32_t* __restrict__ ovf, PrtTravTuning tune) {
+    traverse8_body<STACK_L, WAVES, false, INST, LEAN, false, false, true>(sc, ro, rd, hit, hd2, count_ptr, work, ovf, tune,
+                                                                          nullptr, PrtPrimary{}, PrtPathArgs{});
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2703,6 +2754,79 @@ __global__ void k_hit_records(DevScene sc, uint32_t n, const float4* __restrict_
     out[i] = h;
 }
 
+// ---- occlusion queries (prt_occluded): occluded[i] = 1 iff tmax[i] > 0 and closest_hit(ray i).d2 < fl32(tmax[i]^2) ----
+// The ray buffer as k_pack_rays writes it, plus the seed of every ray's bound: hit = HIT_MISS at hd2 = tmax^2, or
+// HIT_DEAD for a ray that can never be occluded (tmax <= 0 or NaN, zero direction).
+__global__ void k_pack_occlusion_rays(uint32_t n, const float* __restrict__ o, const float* __restrict__ d,
+                                      const float* __restrict__ tmax, float4* __restrict__ ro, float4* __restrict__ rd,
+                                      uint32_t* __restrict__ hit, float* __restrict__ hd2, uint32_t* __restrict__ counts) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i == 0) counts[0] = n;
+    if (i >= n) return;
+    const float dx = d[3 * i], dy = d[3 * i + 1], dz = d[3 * i + 2];
+    const float t = tmax[i];
+    ro[i] = make_float4(o[3 * i], o[3 * i + 1], o[3 * i + 2], __uint_as_float(i));
+    rd[i] = make_float4(dx, dy, dz, 0.f);
+    const bool dead = !(t > 0.0f) || (dx == 0.0f && dy == 0.0f && dz == 0.0f);
+    hit[i] = dead ? HIT_DEAD : HIT_MISS;
+    hd2[i] = t * t;
+}
+
+// k_scan_prims from the seeded bound instead of FLT_MAX: an analytic hit below tmax makes the ray's answer final before
+// traversal.  Strict < in the linear scan, and the primitive walk's tie rule lets an equal d2 win over a hit only, never
+// over the seeded miss: a primitive at exactly d2 == tmax^2 does not block.
+__global__ void __launch_bounds__(256) k_scan_prims_bounded(DevScene sc, const float4* __restrict__ ro,
+                                                            const float4* __restrict__ rd, uint32_t* __restrict__ hit,
+                                                            float* __restrict__ hd2, const uint32_t* __restrict__ count_ptr,
+                                                            uint32_t* __restrict__ work) {
+    const uint32_t count = *count_ptr;
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < 8u) work[32u * k] = 0u;  // chunk cursors of the traversal kernel that follows (as k_scan_prims)
+    if (k == 8u) work[512] = 0u;     // its overflow-list counter
+    if (k >= count) return;
+    if (hit[k] == HIT_DEAD) return;
+    const float4 O = ro[k];
+    const float4 D = rd[k];
+    const float t2 = hd2[k];
+    Closest best;
+    best.d2 = t2;
+    best.id = HIT_MISS;
+    best.prim = 0xFFFFFFFFu;
+    uint32_t n_ptests = 0;
+    if (sc.abvh_nodes)
+        scan_analytic<true, 256>(sc, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), best, n_ptests);
+    else
+        scan_analytic<false>(sc, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), best, n_ptests);
+    if (!(best.d2 < t2)) {  // (the primitive walk's stack fallback restarts from FLT_MAX: keep only blockers)
+        best.id = HIT_MISS;
+        best.d2 = t2;
+    }
+    hit[k] = best.id;
+    hd2[k] = best.d2;
+}
+
+// One byte per ray from the final hit id.  The blocker's world distance^2 is rebuilt by world_hit_from_id, the arithmetic
+// the walks accept on, and compared with tmax^2 again: exact whichever pipeline produced the id (any-hit walk, or the
+// closest-hit fallbacks, whose result is the closest hit below the bound, or the closest hit outright).
+__global__ void k_occlusion_bytes(DevScene sc, uint32_t n, const float4* __restrict__ ro, const float4* __restrict__ rd,
+                                  const uint32_t* __restrict__ hit, const float* __restrict__ tmax, uint8_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float t = tmax[i];
+    const uint32_t id = hit[i];
+    uint8_t occ = 0u;
+    if (t > 0.0f && id != HIT_MISS && id != HIT_DEAD) {
+        const float4 O = ro[i], D = rd[i];
+        WorldHit w;
+        if (sc.n_insts)
+            world_hit_from_id<true>(sc, id, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), w);
+        else
+            world_hit_from_id<false>(sc, id, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), w);
+        occ = (w.has && w.d2 < t * t) ? 1u : 0u;
+    }
+    out[i] = occ;
+}
+
 __global__ void k_scatter_test(DevScene sc, uint32_t n, const float* __restrict__ in_d, const PrtHit* __restrict__ hits,
                                uint32_t* __restrict__ rng_io, uint32_t* __restrict__ scattered,
                                float* __restrict__ atten_o, float* __restrict__ emit_o, float* __restrict__ o_out,
@@ -2930,6 +3054,53 @@ void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
 #undef PRT_LAUNCH_T
 }
 
+// The any-hit walk behind prt_occluded, on a buffer that k_pack_occlusion_rays + k_scan_prims_bounded prepared: the instance
+// t8_kind picks for the closest-hit walk, in its any-hit form, with the same tunables and the same overflow list (its rays
+// are re-walked by the 4-wide closest-hit instance from their seeded bound, which answers the query as well).  Scenes
+// without the 8-wide tree (or with another one forced): the closest-hit walk from the seeded bound.
+void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr, uint32_t* work,
+                         uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune_in) {
+    const PrtT8Kind kind = t8_kind(sc, tune_in);
+    if (kind == T8_NONE) {
+        prt_launch_traverse(st, sc, in, count_ptr, work, spill, max_rays, tree_depth, stack4, tune_in, nullptr);
+        return;
+    }
+    PrtTravTuning tune = tune_in;  // the "auto" values exactly as prt_launch_traverse resolves them
+    if (tune.exit_max == 0xFFFFFFFFu) tune.exit_max = kind == T8_INST12_4 ? 32u : 16u;
+    if (tune.tri_min == 0u) tune.tri_min = (kind != T8_INST12_4 && sc.node_stride == 8u) ? 12u : 24u;
+    tune.perm = nullptr;
+    uint32_t g = tune.grid_blocks;
+    const uint32_t need_blocks = blocks_for(max_rays);
+    if (g > need_blocks) g = need_blocks;
+    if (g == 0) g = 1;
+    const dim3 grid(g), block(256);
+    uint32_t* ovf = work + 512;
+#define PRT_LAUNCH_O(L, W, IN, LN, GRID, TUNE)                                                                       \
+    hipLaunchKernelGGL((k_occluded8_persistent<L, W, IN, LN>), GRID, block, 0, st, sc, in.o, in.d, in.hit, in.hd2,  \
+                       count_ptr, work, ovf, TUNE)
+    if (kind == T8_INST12_4) {  // a stack overflow is an error (prt_synchronize / the host form report it)
+        PRT_LAUNCH_O(12, 4, true, false, grid, tune);
+        return;
+    }
+    const uint32_t stack_l = kind == T8_WIDE11_5 ? 11u : kind == T8_LEAN8_5 ? 8u : 15u;
+    if (kind == T8_WIDE11_5) {
+        PRT_LAUNCH_O(11, 5, false, false, grid, tune);
+    } else if (kind == T8_LEAN8_5) {
+        const dim3 grid5(g == tune.grid_blocks ? g + g / 4u : g);
+        PrtTravTuning t5 = tune;
+        if (tune.stack_cap != 0u || sc.depth8 > stack_l + 1u) t5.steal = 0u;
+        PRT_LAUNCH_O(8, 5, false, true, grid5, t5);
+    } else {
+        PRT_LAUNCH_O(15, 4, false, false, grid, tune);
+    }
+#undef PRT_LAUNCH_O
+    if (sc.nodes4 && (tune.stack_cap != 0u || sc.depth8 > stack_l + 1u)) {
+        hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
+        hipLaunchKernelGGL((k_traverse4_persistent<27, 5, 1, false>), dim3(8), block, 0, st, sc, in.o, in.d, in.hit, in.hd2,
+                           ovf, work, spill, ovf + 1, ovf, tune, (unsigned long long*)nullptr);
+    }
+}
+
 // The PATH instance (PrtPathArgs): whole paths in one launch, for small batches.  One-level scenes with the 8-wide tree,
 // a tree its 15-entry stack holds, and no primitive BVH (classify_ray's walk keeps a per-thread LDS stack of its own).
 bool prt_path_kernel_applies(const DevScene& sc, const PrtTravTuning& tune) {
@@ -3055,6 +3226,23 @@ void prt_launch_pack_rays(hipStream_t st, uint32_t n, const float* o, const floa
 
 void prt_launch_hit_records(hipStream_t st, const DevScene& sc, uint32_t n, const PrtRayBuf& in, PrtHit* out) {
     hipLaunchKernelGGL(k_hit_records, dim3(blocks_for(n)), dim3(256), 0, st, sc, n, in.o, in.d, in.hit, out);
+}
+
+void prt_launch_pack_occlusion_rays(hipStream_t st, uint32_t n, const float* o, const float* d, const float* tmax,
+                                    const PrtRayBuf& out, uint32_t* counts) {
+    hipLaunchKernelGGL(k_pack_occlusion_rays, dim3(blocks_for(n)), dim3(256), 0, st, n, o, d, tmax, out.o, out.d, out.hit,
+                       out.hd2, counts);
+}
+
+void prt_launch_scan_prims_bounded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
+                                   uint32_t* work, uint32_t max_rays) {
+    hipLaunchKernelGGL(k_scan_prims_bounded, dim3(blocks_for(max_rays)), dim3(256), 0, st, sc, in.o, in.d, in.hit, in.hd2,
+                       count_ptr, work);
+}
+
+void prt_launch_occlusion_bytes(hipStream_t st, const DevScene& sc, uint32_t n, const PrtRayBuf& in, const float* tmax,
+                                uint8_t* out) {
+    hipLaunchKernelGGL(k_occlusion_bytes, dim3(blocks_for(n)), dim3(256), 0, st, sc, n, in.o, in.d, in.hit, tmax, out);
 }
 
 void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, const float* in_d, const PrtHit* hits,

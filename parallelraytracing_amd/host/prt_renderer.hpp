@@ -173,6 +173,12 @@ public:
     uint32_t DeviceCount() const { return prt_group_size(grp_); }
     const char* Transport() const { return prt_group_transport(grp_); }
     PrtContext* context(uint32_t rank = 0) { return prt_group_context(grp_, rank); }
+    // Occlusion (shadow-ray) query on the first GPU's context: occluded[i] = 1 iff something blocks ray i
+    // (origins / dirs: n x 3 floats, host memory) before distance tmax[i] (prt_occluded)
+    void Occluded(uint32_t n, const float* origins, const float* dirs, const float* tmax, uint8_t* occluded) {
+        PrtContext* c = prt_group_context(grp_, 0);
+        if (prt_occluded(c, n, origins, dirs, tmax, occluded)) throw Error(std::string("prt_occluded: ") + prt_last_error(c));
+    }
 
 private:
     void check(int rc) {

@@ -296,6 +296,12 @@ class Film:
         return np.where(self.weights[..., None] > 0, self.accum / w, 0.0).astype(np.float32)
 
 
+def hits_to_numpy(t) -> np.ndarray:
+    """The [n, 10] int32 tensor of HipWavefrontRenderer.closest_hit_device as PrtHit records (capi.HIT_DTYPE)."""
+    a = np.ascontiguousarray(t.cpu().numpy(), dtype=np.int32).reshape(-1, 10)
+    return a.view(np.dtype(capi.HIT_DTYPE)).reshape(-1)
+
+
 class HipWavefrontRenderer:
     """The MI355X backend behind the reference's Renderer interface (src/core/renderer.h:8-16)."""
 
@@ -413,6 +419,103 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_closest_hit(self._ctx, o.shape[0], o.ctypes.data_as(_fp), d.ctypes.data_as(_fp),
                                                hits.ctypes.data_as(C.POINTER(PrtHit))))
         return hits
+
+    # ---- ray queries on device-resident data (torch tensors) and occlusion -------------------------------------
+    def _torch_device(self):
+        import torch
+        dev = capi.lib().prt_get_device(self._ctx)
+        if dev < 0:
+            raise PrtError("no HIP device bound to this context: device tensors need one")
+        return torch.device("cuda", dev)
+
+    def _check_tensor(self, name: str, t, shape):
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch tensor on {self._torch_device()}, got {type(t).__name__}")
+        if t.device != self._torch_device():
+            raise ValueError(f"{name}: tensor is on {t.device}, the renderer's device is {self._torch_device()}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: dtype {t.dtype}, expected torch.float32")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {shape}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: tensor is not contiguous")
+
+    def _on_context_stream(self, fn):
+        """Runs fn() (which enqueues on the context's stream) ordered after torch's current stream, and makes that
+        stream wait for what fn enqueued: the results are then safe to use in ordinary torch code."""
+        import torch
+        dev = self._torch_device()
+        h = C.c_void_p()
+        self._check(capi.lib().prt_get_stream(self._ctx, C.byref(h)))
+        cur = torch.cuda.current_stream(dev)
+        if (h.value or 0) == cur.cuda_stream:
+            self._check(fn())
+            return
+        ext = torch.cuda.ExternalStream(h.value, device=dev)
+        before = torch.cuda.Event()
+        before.record(cur)
+        ext.wait_event(before)
+        self._check(fn())
+        after = torch.cuda.Event()
+        after.record(ext)
+        cur.wait_event(after)
+
+    def closest_hit_device(self, origins, dirs):
+        """prt_closest_hit_device on torch tensors ([n, 3] float32 on the renderer's device): the raw 40-byte PrtHit
+        records as an [n, 10] int32 tensor on that device (hits_to_numpy views them as capi.HIT_DTYPE)."""
+        import torch
+        n = int(origins.shape[0]) if getattr(origins, "dim", lambda: 0)() == 2 else -1
+        self._check_tensor("origins", origins, (n, 3))
+        self._check_tensor("dirs", dirs, (n, 3))
+        out = torch.empty((n, 10), dtype=torch.int32, device=origins.device)
+        if n:
+            self._on_context_stream(lambda: capi.lib().prt_closest_hit_device(
+                self._ctx, n, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
+    def occluded(self, origins, dirs, tmax):
+        """Occlusion (shadow-ray) query: True where something blocks the ray before distance tmax, i.e. where the
+        closest hit lies at d2 < fl32(tmax^2) (prt_occluded).  numpy inputs: the host form, a bool ndarray.  torch
+        tensors on the renderer's device: the device form, a torch.bool tensor on that device, ordered after torch's
+        current stream.  tmax: one value per ray, or a scalar for all of them."""
+        try:
+            import torch
+            is_t = isinstance(origins, torch.Tensor) or isinstance(dirs, torch.Tensor)
+        except ImportError:
+            is_t = False
+        if is_t:
+            n = int(origins.shape[0]) if isinstance(origins, torch.Tensor) and origins.dim() == 2 else -1
+            self._check_tensor("origins", origins, (n, 3))
+            self._check_tensor("dirs", dirs, (n, 3))
+            if isinstance(tmax, torch.Tensor):
+                if tmax.dim() == 0:
+                    tmax = tmax.to(device=origins.device).expand(n).contiguous()
+                self._check_tensor("tmax", tmax, (n,))
+            elif np.ndim(tmax) == 0:
+                tmax = torch.full((n,), float(tmax), dtype=torch.float32, device=origins.device)
+            else:
+                raise ValueError("tmax: expected a scalar or a torch tensor with the rays")
+            out = torch.empty(n, dtype=torch.uint8, device=origins.device)
+            if n:
+                self._on_context_stream(lambda: capi.lib().prt_occluded_device(
+                    self._ctx, n, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()), C.c_void_p(tmax.data_ptr()),
+                    C.c_void_p(out.data_ptr())))
+            return out.bool()
+        o, d = _f32(origins), _f32(dirs)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError(f"origins / dirs: expected two [n, 3] arrays, got {o.shape} and {d.shape}")
+        n = o.shape[0]
+        t = np.asarray(tmax, np.float32)
+        if t.ndim == 0:
+            t = np.full(n, t, np.float32)
+        elif t.shape != (n,):
+            raise ValueError(f"tmax: shape {t.shape}, expected a scalar or ({n},)")
+        t = np.ascontiguousarray(t)
+        out = np.zeros(n, np.uint8)
+        self._check(capi.lib().prt_occluded(self._ctx, n, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp),
+                                            t.ctypes.data_as(_fp), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out.astype(bool)
 
     def scatter(self, in_dirs, hits: np.ndarray, rng_state):
         d = _f32(in_dirs).reshape(-1, 3)
