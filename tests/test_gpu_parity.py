@@ -856,6 +856,87 @@ def test_tonemap_matches_oracle_within_one_lsb():
     assert (disp[..., 3] == 255).all()
 
 
+def _tonemap_f64(s, w, exposure, gamma):
+    """Film::UpdateDisplayGPU's formula in float64 on the fp32 inputs: mean, Reinhard, gamma, then IEEE fminf / fmaxf
+    (a NaN operand yields the other one: NaN -> fmin(1, NaN) = 1 -> byte 255) and byte = v * 255 + 0.5 truncated.
+    Returns the bytes and y = v * 255 + 0.5."""
+    s = s.astype(np.float64)
+    w = np.repeat(w.astype(np.float64), 3)
+    with np.errstate(all="ignore"):
+        x = (s / w) * exposure
+        x = x / (1.0 + x)
+        v = np.power(x, float(np.float32(1.0) / np.float32(gamma)))   # the kernel's exponent: 1.0f / gamma
+    v = np.where(w > 0, v, 0.0)
+    v = np.fmax(0.0, np.fmin(1.0, v))
+    y = v * 255.0 + 0.5
+    return np.floor(y).astype(np.int64), y
+
+
+def test_tonemap_device_matches_float64():
+    """prt_film_tonemap on device arrays over a dense sweep of sums and weights (w = 0, 1, 3, 2^24; denormal, huge,
+    negative, inf and NaN sums; means next to every byte boundary): every byte equals the float64 formula's, except where y = v * 255 + 0.5 lies
+    within 32 fp32 ulps of an integer (fp32 rounding of the mean, Reinhard, powf and the scale may land either side);
+    those are counted and may differ by one."""
+    import torch
+    Wt, Ht = 1024, 96
+    n = Wt * Ht
+    r = prt.HipWavefrontRenderer(device=0)
+    r.Init(prt.Film(Wt, Ht), prt.Scene("DEFAULT"), prt.Camera(width=Wt, height=Ht))
+    rng = np.random.default_rng(5)
+    total_band = 0
+    total_exc = 0
+    for exposure in (0.5, 1.0, 2.7):
+        for gamma in (1.0, 2.2, 2.4):
+            inv_g = np.float32(1.0) / np.float32(gamma)
+            # means whose bytes sit on a boundary: v = (b - 0.5) / 255 -> x = v^gamma -> mean = x / (1 - x) / exposure,
+            # each nudged by -4..+4 fp32 ulps
+            b = np.arange(1, 256, dtype=np.float64)
+            xv = ((b - 0.5) / 255.0) ** (1.0 / float(inv_g))
+            m = (xv / (1.0 - xv) / np.float32(exposure)).astype(np.float32)
+            bound = np.concatenate([m + (m * np.float32(k) * np.float32(2.0 ** -23)).astype(np.float32)
+                                    for k in range(-4, 5)])
+            special = np.array([0.0, 1e-45, 1e-40, 1.17e-38, 1e-30, 1e-7, 1.0, 3e37, 3.4e38, np.inf, -np.inf, np.nan,
+                                -0.0, -1e-3, -0.5, -2.0], np.float32)
+            means = np.concatenate([bound, special, (10.0 ** rng.uniform(-40, 38, 20000)).astype(np.float32),
+                                    rng.uniform(0, 4, 20000).astype(np.float32)])
+            weights = np.array([0.0, 1.0, 3.0, 2.0 ** 24, 7.0, 256.0], np.float32)   # (1 / a denormal is inf in fp32)
+            wsel = weights[rng.integers(0, len(weights), size=means.size)]
+            wsel[: bound.size] = rng.choice(np.array([1.0, 3.0, 2.0 ** 24, 64.0], np.float32), size=bound.size)
+            with np.errstate(over="ignore"):
+                sums = (means.astype(np.float64) * np.maximum(wsel, 1.0)).astype(np.float32)   # (huge: inf)
+            sums = np.where(wsel == 1.0, means, sums).astype(np.float32)
+            k = min(n, sums.size)
+            rgb = np.zeros((n, 3), np.float32)
+            wt = np.zeros(n, np.float32)
+            rgb[:k, 0] = sums[:k]
+            rgb[:k, 1] = np.roll(sums, 1)[:k]
+            rgb[:k, 2] = np.roll(sums, 2)[:k]
+            wt[:k] = wsel[:k]
+            d_rgb = torch.from_numpy(rgb.ravel()).to("cuda:0")
+            d_w = torch.from_numpy(wt).to("cuda:0")
+            d_out = torch.empty(4 * n, dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            r.film_tonemap(d_rgb.data_ptr(), d_w.data_ptr(), d_out.data_ptr(), exposure, gamma)
+            r.synchronize()
+            got = d_out.cpu().numpy().reshape(n, 4)
+            assert (got[:, 3] == 255).all()
+            want, y = _tonemap_f64(rgb.ravel(), wt, exposure, gamma)
+            got = got[:, :3].ravel().astype(np.int64)
+            band = np.abs(y - np.rint(y)) <= 32 * 2.0 ** -24 * np.maximum(y, 1.0)
+            diff = got != want
+            assert not (diff & ~band).any(), (exposure, gamma, np.nonzero(diff & ~band)[0][:8])
+            assert (np.abs(got - want)[diff] <= 1).all()
+            total_band += int(band.sum())
+            total_exc += int(diff.sum())
+            # IEEE fminf / fmaxf on the specials, as the reference's formula gives them (weight 1)
+            i_inf = np.nonzero((rgb[:, 0] == np.inf) & (wt > 0))[0]
+            i_nan = np.nonzero(np.isnan(rgb[:, 0]) & (wt > 0))[0]
+            assert (got.reshape(n, 3)[i_inf, 0] == 255).all() and (got.reshape(n, 3)[i_nan, 0] == 255).all()
+            assert (got.reshape(n, 3)[wt == 0] == 0).all()
+    # the sweep puts ~2,300 values per setting next to byte boundaries on purpose; few of them actually flip
+    assert total_exc <= total_band and total_exc <= 0.02 * 9 * 3 * n
+
+
 def test_error_paths():
     r = prt.HipWavefrontRenderer(device=0)
     with pytest.raises(prt.PrtError):
