@@ -141,6 +141,41 @@ typedef struct PrtSampling {
     float clamp;
 } PrtSampling;
 
+/* Next-event estimation toward analytic emitters (DESIGN.md §3 "Light sampling"); NULL / mode OFF = the reference's
+ * estimator, where direct light is found only by a scattered ray that hits an emitter.
+ *  Light set: analytic primitives with an Emissive material, positive mean emission and a rotation + uniform scale +
+ *    translation transform (with inv = inverse(mat)).  Quads are sampled uniformly by area (both faces emit); spheres
+ *    uniformly in the cone they subtend from the shading point (not at all from inside or within PRT_LIGHT_SPHERE_MARGIN
+ *    of their surface: pdf 0).  A light is picked with pmf proportional to emitting area x mean(rgb): quads 2 w h s^2,
+ *    spheres 4 pi r^2 s^2.  Emissive mesh triangles, placed copies and analytic emitters with any other transform are
+ *    never sampled; their emission counts on scattered hits at weight 1 (PrtLightStats.n_emitters_unsampled).
+ *  Where: one light sample at every Lambertian vertex that scatters (segment index k with k + 1 < max_depth); never at
+ *    metal, dielectric or emissive vertices.  It adds thr * (albedo / pi) * Le * max(0, n.w) * w_L / (pmf * pdf_w) if the
+ *    shadow ray (x, w) with tmax = t_light * (1 - PRT_LIGHT_SHADOW_EPS) is not occluded (prt_occluded's semantics), with
+ *    the throughput before that vertex's roulette, and clamped on its own (PrtSampling.clamp).
+ *  Weights: NEE_MIS: power heuristic, w_L = pL^2 / (pL^2 + pB^2), pL = pmf * pdf_w, pB = max(0, n.w) / pi; a scattered
+ *    segment from a Lambertian vertex that hits a light-set emitter counts its emission at w_B = 1 - w_L for that pair
+ *    of vertices.  NEE: w_L = 1, w_B = 0 except w_B = 1 where pL = 0.  Emission seen from the camera or after a metal /
+ *    dielectric vertex keeps weight 1; the sky is never sampled.
+ *  RNG: the light sample draws from pcg_hash(state at the vertex + a constant of its own) and never advances the path's
+ *    own state, so the scattered path, its segments and rays_per_depth are draw for draw those of lighting OFF. */
+enum { PRT_LIGHTING_OFF = 0, PRT_LIGHTING_NEE_MIS = 1, PRT_LIGHTING_NEE = 2 };
+/* relative: a blocker within the last 1e-3 of the shadow segment is missed (bias).  Not smaller: the reference's fp32 sphere
+ * test (Circle::Intersect's b^2 - 4ac) places a grazing hit up to ~3e-4 of t early, so a tighter bound lets a sphere light
+ * block its own samples near the rim of its cone. */
+#define PRT_LIGHT_SHADOW_EPS 1e-3f
+#define PRT_LIGHT_SPHERE_MARGIN 1e-3f  /* relative: no sphere sample from within (1 + margin) R of its centre */
+typedef struct PrtLighting {
+    uint32_t mode;
+} PrtLighting;
+/* Shadow rays cast / found occluded by the render calls since the last prt_reset_stats; the current scene's light set. */
+typedef struct PrtLightStats {
+    uint64_t shadow_rays;
+    uint64_t shadow_occluded;
+    uint32_t n_lights;
+    uint32_t n_emitters_unsampled; /* emissive primitives outside the light set (mesh / placed triangles, other transforms) */
+} PrtLightStats;
+
 /* Closest-hit record of one ray (what Scene::Intersect returns, src/core/surface_interaction.h:6-13,
  * plus the winning primitive index and the world distance^2 the reference minimises,
  * src/core/primitive.cpp:42-48).  prim < 0: miss. */
@@ -260,6 +295,23 @@ int prt_synchronize(PrtContext* ctx);
 int prt_set_sampling(PrtContext* ctx, const PrtSampling* sampling);
 /* Samples kept in flight together (paths = local pixels * n); default 1. */
 int prt_set_samples_in_flight(PrtContext* ctx, uint32_t n);
+/* Light sampling for the following prt_render calls (PrtLighting above; NULL = off).  A mode other than PRT_LIGHTING_*
+ * returns PRT_ERR_INVALID.  Works on host-only contexts too (it only records the mode). */
+int prt_set_lighting(PrtContext* ctx, const PrtLighting* l);
+int prt_get_light_stats(PrtContext* ctx, PrtLightStats* out);
+/* The light set of the current scene (host-only contexts too): n_lights, and for the first min(n_lights, capacity)
+ * lights the primitive index and the pmf (prim / pmf may be NULL). */
+int prt_light_info(PrtContext* ctx, uint32_t capacity, uint32_t* n_lights, uint32_t* prim, float* pmf);
+/* One light sample per (hit, in_dir, key) through the device code the render uses (keys = the path's RNG state at the
+ * vertex, not advanced).  Host arrays.  Per i: shadow_dirs (3 floats), tmax, light (0xFFFFFFFF: none: not Lambertian,
+ * no light, or pdf 0), contrib (3 floats: (albedo / pi) Le max(0, n.w) w_L / pdf_light, throughput 1, unclamped),
+ * pdf_light = pmf * pdf_w, pdf_bsdf = max(0, n.w) / pi, w_light under the context's lighting mode (OFF is taken as
+ * NEE_MIS), and w_bsdf: the weight a scattered segment from the same vertex along the same direction gets when it meets
+ * that light (the render's own evaluation; 1 - w_light up to rounding).  hits[i].normal is the shading normal as
+ * prt_closest_hit returns it (flipped to the incoming side). */
+int prt_sample_light(PrtContext* ctx, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,
+                     float* shadow_dirs, float* tmax, uint32_t* light, float* contrib, float* pdf_light, float* pdf_bsdf,
+                     float* w_light, float* w_bsdf);
 
 /* ---- Film read-back (Film::m_Accum / m_Weights; src/core/film.h:54-60) ------------------------ */
 /* Whole film to host, row-major, top-left origin; only pixels owned by this rank are non-zero. */
@@ -375,6 +427,9 @@ int prt_group_set_film(PrtGroup* g, uint32_t width, uint32_t height);
 int prt_group_film_clear(PrtGroup* g);
 int prt_group_set_sampling(PrtGroup* g, const PrtSampling* s);
 int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n);
+int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l);
+/* shadow-ray counts summed over the ranks; n_lights / n_emitters_unsampled as rank 0 has them */
+int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out);
 int prt_group_set_param(PrtGroup* g, const char* name, int value);
 /* Renderer::ProgressiveRender x spp on every rank's tiles, then the gather + un-tiling on rank 0's device. */
 int prt_group_render(PrtGroup* g, uint32_t spp, uint32_t max_depth, uint32_t seed, uint32_t first_sample);

@@ -81,6 +81,19 @@ class PrtSampling(C.Structure):
     _fields_ = [("jitter", C.c_uint32), ("rr_depth", C.c_uint32), ("clamp", C.c_float)]
 
 
+class PrtLighting(C.Structure):
+    _fields_ = [("mode", C.c_uint32)]
+
+
+class PrtLightStats(C.Structure):
+    _fields_ = [("shadow_rays", C.c_uint64), ("shadow_occluded", C.c_uint64), ("n_lights", C.c_uint32),
+                ("n_emitters_unsampled", C.c_uint32)]
+
+
+# PrtLighting.mode (include/prt.h)
+LIGHTING_MODES = {"off": 0, "mis": 1, "nee": 2}
+
+
 class PrtBvhInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_triangles", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32), ("sah_cost", C.c_float), ("pad_abs", C.c_float),
@@ -126,6 +139,12 @@ SIGNATURES = {
     "prt_group_film_read": (C.c_int, [_vp, _fp, _fp]),
     "prt_group_film_display": (C.c_int, [_vp, C.c_float, C.c_float, C.POINTER(C.c_uint8)]),
     "prt_group_get_stats": (C.c_int, [_vp, C.POINTER(PrtStats)]),
+    "prt_group_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),
+    "prt_group_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
+    "prt_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),
+    "prt_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
+    "prt_light_info": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _fp]),
+    "prt_sample_light": (C.c_int, [_vp, C.c_uint32, _fp, C.POINTER(PrtHit), _u32p, _fp, _fp, _u32p, _fp, _fp, _fp, _fp, _fp]),
     "prt_set_scene": (C.c_int, [_vp, C.POINTER(PrtSceneDesc)]),
     "prt_set_camera": (C.c_int, [_vp, C.POINTER(PrtCameraDesc)]),
     "prt_set_film": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),

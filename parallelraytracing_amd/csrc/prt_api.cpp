@@ -30,7 +30,8 @@ constexpr float kPadCoeff = 1.0f / 262144.0f;  // 2^-18, see traverse() in prt_k
 constexpr uint32_t kMaxLeaf = 3;  // the compressed 8-wide node encodes at most 3 triangles per leaf (bvh.h)
 constexpr size_t kRayStatWords = (size_t)PRT_RAY_STAT_SLOTS * PRT_MAX_DEPTH;
 constexpr uint32_t kTravStatsWords = 16 + PRT_TIMELINE_WORDS * (PRT_MAX_DEPTH + 1);  // counters + one launch timeline per bounce
-constexpr uint32_t kMaxStack = 63;  // LDS stack entries per lane: 31 (5 blocks/CU) or 63 (2 blocks/CU)
+constexpr uint32_t kMaxStack = 63;
+constexpr size_t kLightStatWords = 2 * (size_t)PRT_RAY_STAT_SLOTS;  // k_light_accum's [slot][shadow rays, occluded]  // LDS stack entries per lane: 31 (5 blocks/CU) or 63 (2 blocks/CU)
 
 struct EventPair {
     hipEvent_t a, b;
@@ -132,6 +133,17 @@ struct PrtContext {
     uint32_t pix_entries = 0;
     uint32_t* d_spill = nullptr;  // global part of the per-lane traversal stacks
     size_t spill_entries = 0;
+
+    // ---- light sampling (PrtLighting, include/prt.h) ----
+    uint32_t lighting = PRT_LIGHTING_OFF;
+    std::vector<float> lights;         // the light table: 4 * PRT_LIGHT_F4 floats per light (prt_kernels.h DevLights)
+    std::vector<uint32_t> prim_light;  // per analytic primitive: its light index, 0xFFFFFFFF if not in the light set
+    uint32_t n_emitters_unsampled = 0;
+    void* d_lights = nullptr;
+    void* d_prim_light = nullptr;
+    PrtLightBufs lb{};                 // shadow rays, pdf of the previous scatter, light radiance: cap_light paths each
+    uint64_t cap_light = 0;
+    unsigned long long* d_light_stats = nullptr;  // [slot][shadow rays, occluded], since prt_reset_stats
 };
 
 namespace {
@@ -208,6 +220,137 @@ int ensure_path_state(PrtContext* c, uint64_t n_paths) {
     return PRT_OK;
 }
 
+void free_light_state(PrtContext* c) {
+    free_dev(c->lb.sh.o);
+    free_dev(c->lb.sh.d);
+    free_dev(c->lb.sh.t);
+    free_dev(c->lb.sh.hit);
+    free_dev(c->lb.sh.hd2);
+    free_dev(c->lb.pdf_b);
+    free_dev(c->lb.lrad);
+    c->cap_light = 0;
+}
+
+// the lighting pipeline's per-path buffers (sized with the path state; the statistics words once)
+int ensure_light_state(PrtContext* c, uint64_t n_paths) {
+    if (!c->d_light_stats) {
+        HIPCHECK(c, hipMalloc((void**)&c->d_light_stats, kLightStatWords * sizeof(unsigned long long)));
+        HIPCHECK(c, hipMemset(c->d_light_stats, 0, kLightStatWords * sizeof(unsigned long long)));
+    }
+    c->lb.stats = c->d_light_stats;
+    if (n_paths <= c->cap_light) return PRT_OK;
+    free_light_state(c);
+    const uint64_t n = std::max<uint64_t>(n_paths, 256);
+    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.o, n * sizeof(float4)));
+    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.d, n * sizeof(float4)));
+    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.t, n * sizeof(float4)));
+    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.hit, n * sizeof(uint32_t)));
+    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.hd2, n * sizeof(float)));
+    HIPCHECK(c, hipMalloc((void**)&c->lb.pdf_b, n * sizeof(float)));
+    HIPCHECK(c, hipMalloc((void**)&c->lb.lrad, n * sizeof(float4)));
+    c->cap_light = n;
+    return PRT_OK;
+}
+
+DevLights dev_lights(const PrtContext* c) {
+    return DevLights{(const float4*)c->d_lights, (const uint32_t*)c->d_prim_light,
+                     (uint32_t)(c->lights.size() / (4 * PRT_LIGHT_F4)),
+                     c->lighting == PRT_LIGHTING_NEE ? (uint32_t)PRT_LIGHTING_NEE : (uint32_t)PRT_LIGHTING_NEE_MIS};
+}
+
+// Rotation + uniform scale + translation with inv = inverse(mat) (column-major mat4s): transpose(M3) * M3 = s^2 * I, bottom row
+// (0, 0, 0, 1), inv * mat = I.  Only for such transforms is the reference's local ray (primitive.cpp:29-30) a ray transform.
+// *s2_out = s^2.
+bool is_similarity(const float* M, const float* inv, double* s2_out) {
+    double g[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            g[a][b] = (double)M[4 * a] * M[4 * b] + (double)M[4 * a + 1] * M[4 * b + 1] + (double)M[4 * a + 2] * M[4 * b + 2];
+    const double s2 = g[0][0];
+    bool ok = s2 > 1e-20 && std::isfinite(s2);
+    for (int a = 0; a < 3 && ok; ++a)
+        for (int b = 0; b < 3; ++b)
+            if (std::fabs(g[a][b] - (a == b ? s2 : 0.0)) > 1e-4 * s2) ok = false;
+    for (int r = 0; r < 4 && ok; ++r)
+        for (int cc = 0; cc < 4; ++cc) {
+            double acc = 0.0;
+            for (int kk = 0; kk < 4; ++kk) acc += (double)inv[4 * kk + r] * (double)M[4 * cc + kk];
+            if (std::fabs(acc - (r == cc ? 1.0 : 0.0)) > 1e-3) ok = false;
+        }
+    *s2_out = s2;
+    return ok && M[3] == 0.0f && M[7] == 0.0f && M[11] == 0.0f && M[15] == 1.0f;
+}
+
+// The light set of a scene (include/prt.h PrtLighting): emissive analytic primitives with positive mean emission and a
+// rotation + uniform scale + translation transform with inv = inverse(mat) (the test prt_set_scene applies to placed copies:
+// only then is the surface the reference intersects, primitive.cpp:29-30, the one sampled here).  pmf ~ emitting area x
+// mean(rgb), computed in double.  Every other emissive primitive (mesh and placed triangles, other transforms) counts
+// in n_emitters_unsampled.
+void build_light_table(PrtContext* c, const PrtSceneDesc* s) {
+    c->lights.clear();
+    c->prim_light.assign(s->n_primitives, 0xFFFFFFFFu);
+    c->n_emitters_unsampled = 0;
+    auto emissive = [&](uint32_t m) { return m < s->n_materials && s->materials[m].type == PRT_MAT_EMISSIVE; };
+    std::vector<double> power;
+    for (uint32_t i = 0; i < s->n_primitives; ++i) {
+        const PrtPrimitive& p = s->primitives[i];
+        if (!emissive(p.material_id)) continue;
+        const float* M = p.mat;
+        double s2 = 0.0;
+        if (!is_similarity(p.mat, p.inv, &s2)) {
+            ++c->n_emitters_unsampled;
+            continue;
+        }
+        const float* rgb = s->materials[p.material_id].rgb;
+        const double mean = ((double)rgb[0] + (double)rgb[1] + (double)rgb[2]) / 3.0;
+        const bool quad = p.shape_type == PRT_SHAPE_QUAD;
+        const double w = p.shape_param[0], h = p.shape_param[1];
+        const double area = quad ? std::fabs(w * h) * s2 : 4.0 * M_PI * w * w * s2;
+        const double pw = (quad ? 2.0 * area : area) * mean;  // a quad emits from both faces
+        if (!(pw > 0.0) || !std::isfinite(pw)) continue;      // emits nothing: not a light, nothing unsampled either
+        float rec[4 * PRT_LIGHT_F4] = {};
+        rec[0] = M[12];
+        rec[1] = M[13];
+        rec[2] = M[14];
+        rec[3] = quad ? (float)area : (float)(std::fabs(w) * std::sqrt(s2));
+        const double nx = (double)M[1] * M[10] - (double)M[2] * M[9], ny = (double)M[2] * M[8] - (double)M[0] * M[10],
+                     nz = (double)M[0] * M[9] - (double)M[1] * M[8];
+        const double nl = std::sqrt(nx * nx + ny * ny + nz * nz);
+        for (int a = 0; a < 3; ++a) {
+            rec[4 + a] = quad ? (float)(w * M[a]) : 0.0f;
+            rec[8 + a] = quad ? (float)(h * M[8 + a]) : 0.0f;
+        }
+        if (quad) {
+            rec[12] = (float)(nx / nl);
+            rec[13] = (float)(ny / nl);
+            rec[14] = (float)(nz / nl);
+        }
+        const uint32_t kind = quad ? 1u : 0u;
+        memcpy(&rec[15], &kind, 4);
+        rec[16] = rgb[0];
+        rec[17] = rgb[1];
+        rec[18] = rgb[2];
+        memcpy(&rec[19], &i, 4);
+        c->prim_light[i] = (uint32_t)power.size();
+        power.push_back(pw);
+        c->lights.insert(c->lights.end(), rec, rec + 4 * PRT_LIGHT_F4);
+    }
+    double total = 0.0;
+    for (double pw : power) total += pw;
+    double acc = 0.0;
+    for (size_t l = 0; l < power.size(); ++l) {
+        acc += power[l];
+        c->lights[4 * PRT_LIGHT_F4 * l + 7] = (float)(power[l] / total);                                 // pmf
+        c->lights[4 * PRT_LIGHT_F4 * l + 11] = l + 1 == power.size() ? 1.0f : (float)(acc / total);  // cdf
+    }
+    for (uint32_t m = 0; m < s->n_meshes; ++m)
+        if (emissive(s->meshes[m].material_id)) c->n_emitters_unsampled += s->meshes[m].n_triangles;
+    for (uint32_t i = 0; i < s->n_instances; ++i) {
+        const PrtInstance& pi = s->instances[i];
+        if (emissive(pi.material_id) && pi.mesh < s->n_instanced_meshes) c->n_emitters_unsampled += s->instanced_meshes[pi.mesh].n_triangles;
+    }
+}
+
 int ensure_counters(PrtContext* c) {
     if (c->d_counts) return PRT_OK;
     HIPCHECK(c, hipMalloc((void**)&c->d_counts, (PRT_MAX_DEPTH + 2) * PRT_CNT_STRIDE * sizeof(uint32_t)));
@@ -256,6 +399,8 @@ void free_scene(PrtContext* c) {
     free_dev(c->d_abvh_order);
     free_dev(c->d_tris);
     free_dev(c->d_nrms);
+    free_dev(c->d_lights);
+    free_dev(c->d_prim_light);
     c->has_scene = false;
 }
 
@@ -335,7 +480,10 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // k_shade shades one analytic-only segment in place per call (never stored, never re-read: shade -24 % on C3) when
     // the scene has a BVH and few analytic primitives; with many of them (RANDOM_BALLS presets) compacting between
     // bounces is the better deal
-    const uint32_t fuse = (c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
+    // Lighting modes (PrtLighting) run k_shade_nee, which shades one segment per call: no fused segments, no compact primary
+    // rays, no path route (tunables: the frame does not depend on them)
+    const bool lit = c->lighting != PRT_LIGHTING_OFF;
+    const uint32_t fuse = (!lit && c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
     // The ray count of a bounce is only known on the device.  With big batches a k_shade grid sized for the worst case is
     // a million blocks, most of which find nothing to do (~0.5 ms per launch, 4 % of a C3 step).  The host therefore
     // reads the counts of bounce d back WHILE the traversal kernel of bounce d runs (the copy is enqueued right after
@@ -365,7 +513,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // bit-identical (tests run both routes).  OFF by default (prt_set_param("path_kernel", 1 | 2)): measured, it ties with
     // the pipeline up to ~250 k paths per call and loses above (profiles/r3_path_kernel.txt, TUNING.md): both are bound
     // by a path's chain of dependent node fetches, and the pipeline shades with full waves.
-    const bool path_route = c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
+    const bool path_route = !lit && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
                             !trav_stats && !c->d_shade_div && c->variant == 0 && fuse == 0u && c->sort_rays == 0u &&
                             prt_path_kernel_applies(c->dsc, c->tune);
     if (path_route) {
@@ -385,7 +533,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // front/back counters of every bounce start at zero (the producers add to them atomically)
     HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
     // compact primary rays (PrtPrimary): the default pipeline without jitter / roulette / clamp / fusion
-    const bool compact = c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
+    const bool compact = !lit && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
                          c->sampling.jitter == 0u && c->sampling.rr_depth == 0u && !(c->sampling.clamp > 0.0f) && fuse == 0u &&
                          prt_traverse_takes_primary(c->dsc, c->tune);
     if (compact && c->pix_entries < c->tm.n_pix_local) {
@@ -394,6 +542,11 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
         HIPCHECK(c, hipMalloc((void**)&c->d_pix, 4 * (size_t)c->tm.n_pix_local * sizeof(float4)));
         c->pix_entries = c->tm.n_pix_local;
         c->pix_records_blank = false;
+    }
+    const DevLights lt = dev_lights(c);
+    if (lit) {  // the paths' light radiance starts at zero (paths that end with their primary ray never get a light sample)
+        if ((rc = ensure_light_state(c, n_paths))) return rc;
+        HIPCHECK(c, hipMemsetAsync(c->lb.lrad, 0, (size_t)n_paths * sizeof(float4), c->stream));
     }
     const PrtPrimary primary{(const uint32_t*)c->rb[0].t, c->d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, c->tm.n_pix_local,
                              1.0f / (float)c->tm.n_pix_local, first_sample, seed};
@@ -465,16 +618,43 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
         }
         if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, c->d_counts, d, n_paths, c->d_shade_div, (compact && d == 0) ? &primary : nullptr);
         if ((rc = begin_event(c, 2, &ep))) return rc;
-        prt_launch_shade(c->stream, c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, fuse, c->sampling,
-                         n_rays_known, (compact && d == 0) ? &primary : nullptr);
+        if (lit) {
+            prt_launch_shade_nee(c->stream, c->dsc, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
+                                 c->sampling, n_rays_known);
+            if (lt.n_lights) {
+                // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
+                // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
+                const uint32_t* scount = c->d_counts + (size_t)d * PRT_CNT_STRIDE + 48u;
+                const uint32_t nmax = n_rays_known == 0xFFFFFFFFu ? n_paths : n_rays_known;
+                prt_launch_scan_prims_bounded(c->stream, c->dsc, c->lb.sh, scount, c->d_work, nmax);
+                if (c->dsc.n_nodes) {
+                    if (c->variant == 0 || c->dsc.n_insts || !c->dsc.nodes) {
+                        PrtTravTuning tune = c->tune;
+                        tune.perm = nullptr;
+                        prt_launch_occluded(c->stream, c->dsc, c->lb.sh, scount, c->d_work, c->d_spill, nmax, c->bvh.max_depth,
+                                            c->bvh.max_stack4, tune);
+                    } else {
+                        prt_launch_intersect(c->stream, c->dsc, c->lb.sh, scount, nmax, stack_depth, c->variant, nullptr);
+                    }
+                }
+                prt_launch_light_accum(c->stream, c->dsc, c->lb, scount, c->d_work, nmax);
+            }
+        } else {
+            prt_launch_shade(c->stream, c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, fuse, c->sampling,
+                             n_rays_known, (compact && d == 0) ? &primary : nullptr);
+        }
         if ((rc = end_event(c, &ep))) return rc;
         if (exact && d + 1 < max_depth) HIPCHECK(c, read_back(d + 1));
     }
     // film += the batch's samples (unless this is a measurement run) and per-depth ray counts from the paths' last
     // segment indices
     if ((rc = begin_event(c, 3, &ep))) return rc;
-    prt_launch_accumulate(c->stream, c->d_rad, c->d_film_local, c->tm, S_cur, max_depth, accumulate, c->ray_stats_target,
-                          compact ? c->d_pix + c->tm.n_pix_local : nullptr);
+    if (lit)
+        prt_launch_accumulate_lit(c->stream, c->d_rad, c->lb.lrad, c->d_film_local, c->tm, S_cur, max_depth, accumulate,
+                                  c->ray_stats_target);
+    else
+        prt_launch_accumulate(c->stream, c->d_rad, c->d_film_local, c->tm, S_cur, max_depth, accumulate, c->ray_stats_target,
+                              compact ? c->d_pix + c->tm.n_pix_local : nullptr);
     if ((rc = end_event(c, &ep))) return rc;
     if (accumulate) c->stats.samples += S_cur;
     HIPCHECK(c, hipGetLastError());
@@ -546,6 +726,8 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
         HIPCHECK(c, upload(&c->d_insts, c->dev_insts.data(), c->dev_insts.size() * sizeof(DevInstance)));
         HIPCHECK(c, upload(&c->d_tlas_inst, c->tlas_inst.data(), c->tlas_inst.size() * 4));
     }
+    HIPCHECK(c, upload(&c->d_lights, c->lights.data(), c->lights.size() * 4));
+    HIPCHECK(c, upload(&c->d_prim_light, c->prim_light.data(), c->prim_light.size() * 4));
     if (!gb) {
         HIPCHECK(c, upload(&c->d_tris, c->tri_records.data(), c->tri_records.size() * 4));
         HIPCHECK(c, upload(&c->d_nrms, c->nrm_records.data(), c->nrm_records.size() * 4));
@@ -673,6 +855,8 @@ void prt_destroy(PrtContext* c) {
         (void)hipStreamSynchronize(c->stream);
         free_scene(c);
         free_path_state(c);
+        free_light_state(c);
+        free_dev(c->d_light_stats);
         free_dev(c->d_film_local);
         free_dev(c->d_counts);
         free_dev(c->d_ray_stats);
@@ -748,6 +932,7 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
         to_dev_mat(p.inv, d.inv);
         c->prims.push_back(d);
     }
+    build_light_table(c, s);
     uint64_t n_tris = 0;
     for (uint32_t m = 0; m < s->n_meshes; ++m) {
         const PrtMesh& me = s->meshes[m];
@@ -1038,22 +1223,8 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
             if (pi.material_id >= s->n_materials) return fail(c, PRT_ERR_INVALID, "instance %u: material out of range", i);
             // rotation + uniform scale + translation only: transpose(M3) * M3 = s^2 * I, and inv * mat = I
             const float* M = pi.mat;
-            double g[3][3];
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b)
-                    g[a][b] = (double)M[4 * a] * M[4 * b] + (double)M[4 * a + 1] * M[4 * b + 1] + (double)M[4 * a + 2] * M[4 * b + 2];
-            const double s2 = g[0][0];
-            bool ok = s2 > 1e-20 && std::isfinite(s2);
-            for (int a = 0; a < 3 && ok; ++a)
-                for (int b = 0; b < 3; ++b)
-                    if (std::fabs(g[a][b] - (a == b ? s2 : 0.0)) > 1e-4 * s2) ok = false;
-            for (int r = 0; r < 4 && ok; ++r)
-                for (int cc = 0; cc < 4; ++cc) {
-                    double acc = 0.0;
-                    for (int kk = 0; kk < 4; ++kk) acc += (double)pi.inv[4 * kk + r] * (double)pi.mat[4 * cc + kk];
-                    if (std::fabs(acc - (r == cc ? 1.0 : 0.0)) > 1e-3) ok = false;
-                }
-            if (!ok || M[3] != 0.0f || M[7] != 0.0f || M[11] != 0.0f || M[15] != 1.0f)
+            double s2 = 0.0;
+            if (!is_similarity(pi.mat, pi.inv, &s2))
                 return fail(c, PRT_ERR_INVALID,
                             "instance %u: the transform must be rotation + uniform scale + translation with inv = inverse(mat) "
                             "(the reference's local ray, primitive.cpp:29-30, is only a ray transform for those)", i);
@@ -1195,6 +1366,9 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     dst->dsc = src->dsc;  // scalar fields; every device pointer is replaced by upload_scene
     dst->scene_device_built = src->scene_device_built;
     dst->mesh_sizes = src->mesh_sizes;
+    dst->lights = src->lights;
+    dst->prim_light = src->prim_light;
+    dst->n_emitters_unsampled = src->n_emitters_unsampled;
     if (!dst->has_device) {
         dst->has_scene = true;
         return PRT_OK;
@@ -1385,6 +1559,45 @@ int prt_set_sampling(PrtContext* c, const PrtSampling* sp) {
 int prt_set_samples_in_flight(PrtContext* c, uint32_t n) {
     if (!c || n == 0 || n > 1024) return fail(c, PRT_ERR_INVALID, "samples in flight must be 1..1024");
     c->S = n;
+    return PRT_OK;
+}
+
+int prt_set_lighting(PrtContext* c, const PrtLighting* l) {
+    if (!c) return PRT_ERR_INVALID;
+    if (l && l->mode != PRT_LIGHTING_OFF && l->mode != PRT_LIGHTING_NEE_MIS && l->mode != PRT_LIGHTING_NEE)
+        return fail(c, PRT_ERR_INVALID, "bad lighting mode %u", l->mode);
+    c->lighting = l ? l->mode : (uint32_t)PRT_LIGHTING_OFF;
+    return PRT_OK;
+}
+
+int prt_light_info(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint32_t* prim, float* pmf) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    const uint32_t n = (uint32_t)(c->lights.size() / (4 * PRT_LIGHT_F4));
+    if (n_lights) *n_lights = n;
+    for (uint32_t l = 0; l < n && l < capacity; ++l) {
+        const float* r = &c->lights[4 * PRT_LIGHT_F4 * l];
+        if (prim) memcpy(&prim[l], &r[19], 4);
+        if (pmf) pmf[l] = r[7];
+    }
+    return PRT_OK;
+}
+
+int prt_get_light_stats(PrtContext* c, PrtLightStats* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->n_lights = (uint32_t)(c->lights.size() / (4 * PRT_LIGHT_F4));
+    out->n_emitters_unsampled = c->n_emitters_unsampled;
+    if (!c->has_device || !c->d_light_stats) return PRT_OK;
+    int rc = need_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> h(kLightStatWords);
+    HIPCHECK(c, hipMemcpy(h.data(), c->d_light_stats, kLightStatWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t sl = 0; sl < PRT_RAY_STAT_SLOTS; ++sl) {
+        out->shadow_rays += h[2 * sl];
+        out->shadow_occluded += h[2 * sl + 1];
+    }
     return PRT_OK;
 }
 
@@ -1686,6 +1899,56 @@ int prt_scatter(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* h
     return PRT_OK;
 }
 
+int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,
+                     float* shadow_dirs, float* tmax, uint32_t* light, float* contrib, float* pdf_light, float* pdf_bsdf,
+                     float* w_light, float* w_bsdf) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (n == 0) return PRT_OK;
+    if (!in_dirs || !hits || !keys || !shadow_dirs || !tmax || !light || !contrib || !pdf_light || !pdf_bsdf || !w_light || !w_bsdf)
+        return fail(c, PRT_ERR_INVALID, "null array");
+    for (uint32_t i = 0; i < n; ++i)
+        if (hits[i].prim >= 0 && hits[i].material_id >= c->materials.size())
+            return fail(c, PRT_ERR_INVALID, "hit %u: material out of range", i);
+    const size_t b3 = (size_t)n * 12, b1 = (size_t)n * 4, bh = (size_t)n * sizeof(PrtHit), bf = (size_t)n * 44;
+    if ((rc = ensure_scratch(c, bh + b3 + 2 * b1 + bf + 64))) return rc;
+    char* base = (char*)c->d_scratch;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base + off;
+        off += (bytes + 15) & ~(size_t)15;
+        return p;
+    };
+    PrtHit* d_h = (PrtHit*)take(bh);
+    float* d_in = (float*)take(b3);
+    uint32_t* d_k = (uint32_t*)take(b1);
+    uint32_t* d_l = (uint32_t*)take(b1);
+    float* d_f = (float*)take(bf);
+    HIPCHECK(c, hipMemcpyAsync(d_h, hits, bh, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_in, in_dirs, b3, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_k, keys, b1, hipMemcpyHostToDevice, c->stream));
+    prt_launch_sample_light_test(c->stream, c->dsc, dev_lights(c), n, d_in, d_h, d_k, d_f, d_l);
+    HIPCHECK(c, hipGetLastError());
+    std::vector<float> f((size_t)n * 11);
+    HIPCHECK(c, hipMemcpyAsync(f.data(), d_f, bf, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(light, d_l, b1, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; ++i) {
+        const float* r = &f[11 * i];
+        for (int a = 0; a < 3; ++a) {
+            shadow_dirs[3 * i + a] = r[a];
+            contrib[3 * i + a] = r[4 + a];
+        }
+        tmax[i] = r[3];
+        pdf_light[i] = r[7];
+        pdf_bsdf[i] = r[8];
+        w_light[i] = r[9];
+        w_bsdf[i] = r[10];
+    }
+    return PRT_OK;
+}
+
 // ---- measurement -----------------------------------------------------------------------------------
 int prt_enable_timing(PrtContext* c, int on) {
     if (!c) return PRT_ERR_INVALID;
@@ -1721,6 +1984,7 @@ int prt_reset_stats(PrtContext* c) {
     memset(&c->stats, 0, sizeof(c->stats));
     c->dead_paths = 0;
     if (c->d_ray_stats) HIPCHECK(c, hipMemset(c->d_ray_stats, 0, kRayStatWords * sizeof(unsigned long long)));
+    if (c->d_light_stats) HIPCHECK(c, hipMemset(c->d_light_stats, 0, kLightStatWords * sizeof(unsigned long long)));
     return PRT_OK;
 }
 

@@ -307,6 +307,28 @@ int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n_samples) {
     return for_each_rank(g, [&](uint32_t r) { return prt_set_samples_in_flight(g->ctx[r], n_samples); }, false);
 }
 
+int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l) {
+    if (!g) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_lighting(g->ctx[r], l); }, false);
+}
+
+int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out) {
+    if (!g || !out || g->ctx.empty()) return PRT_ERR_INVALID;
+    memset(out, 0, sizeof(*out));
+    for (size_t r = 0; r < g->ctx.size(); ++r) {
+        PrtLightStats s;
+        const int rc = prt_get_light_stats(g->ctx[r], &s);
+        if (rc) return gfail(g, rc, "rank %zu: %s", r, prt_last_error(g->ctx[r]));
+        out->shadow_rays += s.shadow_rays;
+        out->shadow_occluded += s.shadow_occluded;
+        if (r == 0) {
+            out->n_lights = s.n_lights;
+            out->n_emitters_unsampled = s.n_emitters_unsampled;
+        }
+    }
+    return PRT_OK;
+}
+
 int prt_group_set_param(PrtGroup* g, const char* name, int value) {
     if (!g) return PRT_ERR_INVALID;
     return for_each_rank(g, [&](uint32_t r) { return prt_set_param(g->ctx[r], name, value); }, false);

@@ -149,7 +149,29 @@ struct PrtPathArgs {
     uint32_t first_sample, seed, max_depth, n_paths;
 };
 
-#define PRT_CNT_STRIDE 64u  // uint32 per bounce in the counter array: [0] front, [32] back, [16] finished-in-producer counts
+#define PRT_CNT_STRIDE 64u  // uint32 per bounce in the counter array: [0] front, [32] back, [16] finished-in-producer counts, [48] shadow rays (lighting modes)
+
+// Light table (PrtLighting, include/prt.h), read-only, 5 x float4 per light:
+//   [0] centre.xyz, R (sphere) | area w h s^2 (quad)   [1] edge u = w * column 0 of Mat, pmf   [2] edge v = h * column 2, cdf
+//   [3] unit normal of the quad plane, kind (0 sphere, 1 quad; bits)   [4] emission rgb, primitive index (bits)
+// prim_light[p]: light index of analytic primitive p, 0xFFFFFFFF if it is not in the light set.  Passed only to the
+// lighting kernels (DevScene stays as it is: the lighting-off instances keep their code).
+#define PRT_LIGHT_F4 5u
+struct DevLights {
+    const float4* lights;
+    const uint32_t* prim_light;
+    uint32_t n_lights;
+    uint32_t mode;  // PRT_LIGHTING_NEE_MIS / PRT_LIGHTING_NEE
+};
+// What the lighting shade step needs beyond k_shade's arguments: the shadow-ray buffer (o = x, path id; d = w, -;
+// t = clamped contribution rgb, tmax; hit / hd2 seeded as k_pack_occlusion_rays seeds them), the per-path pdf of the
+// previous scatter (pB, < 0: the previous vertex was not Lambertian) and the per-path light radiance.
+struct PrtLightBufs {
+    PrtRayBuf sh;
+    float* pdf_b;
+    float4* lrad;
+    unsigned long long* stats;  // [PRT_RAY_STAT_SLOTS][2]: shadow rays, occluded (block b adds to slot b mod SLOTS)
+};
 
 void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, uint32_t n_paths,
                        uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
@@ -204,3 +226,15 @@ void prt_launch_occlusion_bytes(hipStream_t st, const DevScene& sc, uint32_t n, 
 void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, const float* in_d, const PrtHit* hits,
                              uint32_t* rng_io, uint32_t* scattered, float* atten, float* emitted, float* o_out,
                              float* d_out);
+// lighting modes (PrtLighting): the shade step with a light sample per Lambertian vertex (shadow rays into lb.sh, counted
+// in counts[iter * stride + 48]); after the shadow walk, the unoccluded contributions into lb.lrad (and the traversal
+// cursors reset for the next bounce); the film accumulation of rad + lrad
+void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
+                          const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
+                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known);
+void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBufs& lb, const uint32_t* count_ptr,
+                            uint32_t* work, uint32_t max_rays);
+void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, const PrtTileMap& tm,
+                               uint32_t S, uint32_t max_depth, bool update_film, unsigned long long* ray_stats);
+void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
+                                  const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light);

@@ -2649,6 +2649,76 @@ __global__ void __launch_bounds__(256) k_accumulate(const float4* __restrict__ r
     }
 }
 
+// Lighting modes (PrtLighting): k_accumulate where a sample is rad[path] + lrad[path], the path's terminal radiance plus the
+// sum of its light samples (without a light sample lrad is +0 and the sum is rad bit for bit); no compact primary rays.
+// (A separate kernel, not a template parameter of k_accumulate: the lighting-off instance keeps its code.)
+__global__ void __launch_bounds__(256) k_accumulate_lit(const float4* __restrict__ rad, const float4* __restrict__ lrad,
+                                                        float4* __restrict__ film_local, PrtTileMap tm, uint32_t S,
+                                                        uint32_t max_depth, int update_film,
+                                                        unsigned long long* __restrict__ ray_stats) {
+    // rad[path] = {radiance, index of the path's last segment}.  Ray segments at depth d = paths whose last segment
+    // index is >= d: a per-block histogram of the last indices (wave ballots -> LDS) gives the per-depth counts.
+    // A block takes several groups of 256 pixels (grid-stride): its per-depth counts reach the global counters with ONE
+    // atomic per depth per block, and a counter word only executes ~87 atomics per microsecond (tools/atomic_rate.hip): with
+    // one block per 256 pixels a 1080p frame was 8,100 atomics per word = 93 us, most of a one-sample k_accumulate.
+    __shared__ uint32_t s_ends[PRT_MAX_DEPTH];
+    if (threadIdx.x < PRT_MAX_DEPTH) s_ends[threadIdx.x] = 0u;
+    __syncthreads();
+    for (uint32_t pl0 = blockIdx.x * 256u; pl0 < tm.n_pix_local; pl0 += gridDim.x * 256u) {  // block-uniform trip count
+    const uint32_t pl = pl0 + threadIdx.x;
+    uint32_t x, y;
+    const bool valid = pl < tm.n_pix_local && tile_pixel(tm, pl, x, y);
+    float4 f = valid ? film_local[pl] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 E = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xFFFFFFFFu));
+    const float weight = 1.0f;
+    const uint32_t lane = lane_id();
+    // Samples are added in sample order (that fixes the fp32 sum), but their loads do not depend on each other: eight
+    // at a time are in flight (a rank of an 8-GPU run has only four blocks per CU here, too few to hide the latency of
+    // one load per iteration)
+    for (uint32_t s0 = 0; s0 < S; s0 += 8u) {  // block-uniform trip counts
+        float4 r[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j)
+            r[j] = (valid && s0 + j < S) ? ld_stream(&rad[(size_t)(s0 + j) * tm.n_pix_local + pl]) : E;
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j) {
+            if (valid && s0 + j < S) {
+                const float4 l = ld_stream(&lrad[(size_t)(s0 + j) * tm.n_pix_local + pl]);
+                r[j].x = r[j].x + l.x;
+                r[j].y = r[j].y + l.y;
+                r[j].z = r[j].z + l.z;
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j) {
+            if (s0 + j >= S) break;
+            uint32_t e = 0xFFFFFFFFu;
+            if (valid) {
+                f.x += r[j].x * weight;
+                f.y += r[j].y * weight;
+                f.z += r[j].z * weight;
+                f.w += weight;
+                e = __float_as_uint(r[j].w);
+            }
+            for (uint32_t dd = 0; dd < max_depth; ++dd) {
+                const unsigned long long mk = __ballot(e == dd);
+                if (mk != 0ull && lane == 0) atomicAdd(&s_ends[dd], (uint32_t)__popcll(mk));
+            }
+        }
+    }
+    if (valid && update_film) film_local[pl] = f;
+    }
+    __syncthreads();
+    if (threadIdx.x < max_depth) {
+        unsigned long long n = 0;
+        for (uint32_t e = threadIdx.x; e < max_depth; ++e) n += s_ends[e];
+        // (PRT_RAY_STAT_SLOTS copies of the counters, summed by the host when it reads them: a single word would execute only
+        // ~87 of these atomics per microsecond, a floor of 23 us for 2,048 blocks, half of a one-sample k_accumulate)
+        if (n) atomicAdd(&ray_stats[(blockIdx.x & (PRT_RAY_STAT_SLOTS - 1u)) * PRT_MAX_DEPTH + threadIdx.x], n);
+    }
+}
+
+
 // Un-tile `world` gathered rank payloads (each `stride` float4) into the Film layout
 // (m_Accum[3*(y*W+x)+c], m_Weights[y*W+x]; src/core/film.h:54-60).
 __global__ void __launch_bounds__(256) k_resolve(const float4* __restrict__ gathered, uint32_t world, uint32_t stride,
@@ -2855,6 +2925,369 @@ __global__ void k_scatter_test(DevScene sc, uint32_t n, const float* __restrict_
     d_out[3 * i + 0] = sd.x;
     d_out[3 * i + 1] = sd.y;
     d_out[3 * i + 2] = sd.z;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Light sampling (PrtLighting, include/prt.h; DESIGN.md §3 "Light sampling"): next-event estimation toward the analytic
+// emitters of the light table (DevLights), combined with the scattered path by multiple importance sampling.  Per bounce:
+// k_shade_nee (k_shade's step plus one light sample per Lambertian vertex that scatters; the sample becomes a shadow ray)
+// -> k_scan_prims_bounded + the any-hit walk over the shadow rays (prt_occluded's pipeline) -> k_light_accum.
+// ---------------------------------------------------------------------------------------------------------
+#define PRT_LIGHT_RNG 0x68E31DA5u            // the light sample's own stream: pcg_hash(path state at the vertex + this)
+#define PRT_INV_PI 0.318309886183790672f
+#define PRT_TWO_PI 6.28318530717958648f
+
+// 1 - cos(theta_max) of the cone a sphere light (L0 = centre, R) subtends from x, as (R^2/D^2) / (1 + sqrt(1 - R^2/D^2))
+// (no cancellation for small R/D); 0 from inside the sphere or within PRT_LIGHT_SPHERE_MARGIN of its surface
+PRT_DEV float sphere_cone_omc(float4 L0, f3 x) {
+    const f3 cd = mk3(L0.x, L0.y, L0.z) - x;
+    const float D2 = dot3(cd, cd);
+    const float lim = L0.w * (1.0f + PRT_LIGHT_SPHERE_MARGIN);
+    if (!(D2 > lim * lim)) return 0.0f;
+    const float q = (L0.w * L0.w) / D2;
+    return q / (1.0f + __builtin_sqrtf(1.0f - q));
+}
+
+// Solid-angle pdf with which the light (records L0, L3) samples the unit direction w from x, whose point on the light lies
+// at distance^2 d2: quad d2 / (A |n_l.w|), sphere 1 / (2 pi (1 - cos theta_max)); 0 = the light cannot sample w.
+PRT_DEV float light_pdf_w(float4 L0, float4 L3, f3 x, f3 w, float d2) {
+    if (__float_as_uint(L3.w) == 1u) {
+        const float den = L0.w * __builtin_fabsf(dot3(mk3(L3.x, L3.y, L3.z), w));
+        return den > 0.0f ? d2 / den : 0.0f;
+    }
+    const float omc = sphere_cone_omc(L0, x);
+    return omc > 0.0f ? 1.0f / (PRT_TWO_PI * omc) : 0.0f;
+}
+
+struct LightSample {
+    f3 w;          // unit direction from x
+    float t_light; // distance to the sampled point (quad) / the near intersection (sphere)
+    float tmax;    // shadow-ray bound: t_light * (1 - PRT_LIGHT_SHADOW_EPS)
+    float pdf_l;   // pmf * pdf_w
+    f3 le;         // emission
+    uint32_t light;
+};
+
+// One light sample from x with the draws of key's own stream (the path's state is not advanced): the light by its CDF,
+// then a point uniform by area (quad) or a direction uniform in the cone (sphere).  false: no sample (pdf 0).
+PRT_DEV bool sample_light(const DevLights& lt, f3 x, uint32_t key, LightSample& s) {
+    uint32_t ls = pcg_hash(key + PRT_LIGHT_RNG);
+    const float u0 = rnd01(ls);
+    const float u1 = rnd01(ls);
+    const float u2 = rnd01(ls);
+    uint32_t lo = 0u, hi = lt.n_lights - 1u;  // smallest i with u0 < cdf[i] (cdf[n - 1] = 1)
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (u0 < lt.lights[PRT_LIGHT_F4 * mid + 2u].w) hi = mid; else lo = mid + 1u;
+    }
+    const float4* L = lt.lights + PRT_LIGHT_F4 * lo;
+    const float4 L0 = L[0], L1 = L[1], L2 = L[2], L3 = L[3], L4 = L[4];
+    s.light = lo;
+    s.le = mk3(L4.x, L4.y, L4.z);
+    const f3 c = mk3(L0.x, L0.y, L0.z);
+    float t_light, pdf_w;
+    if (__float_as_uint(L3.w) == 1u) {  // quad: p = c + (u1 - 1/2) u + (u2 - 1/2) v
+        const f3 p = c + mk3(L1.x, L1.y, L1.z) * (u1 - 0.5f) + mk3(L2.x, L2.y, L2.z) * (u2 - 0.5f);
+        const f3 dv = p - x;
+        const float d2 = dot3(dv, dv);
+        t_light = __builtin_sqrtf(d2);
+        s.w = dv * (1.0f / t_light);
+        pdf_w = light_pdf_w(L0, L3, x, s.w, d2);
+    } else {  // sphere: 1 - cos theta = u1 (1 - cos theta_max), phi = 2 pi u2 about the direction to the centre
+        const float omc = sphere_cone_omc(L0, x);
+        if (!(omc > 0.0f)) return false;
+        const f3 cd = c - x;
+        const float D2 = dot3(cd, cd);
+        const float D = __builtin_sqrtf(D2);
+        const f3 wc = cd * (1.0f / D);
+        const float a = u1 * omc;
+        const float cos_t = 1.0f - a;
+        const float sin2 = a * (2.0f - a);
+        const float sin_t = __builtin_sqrtf(sin2);
+        float sp, cp;
+        sincosf(PRT_TWO_PI * u2, &sp, &cp);
+        // orthonormal frame about wc (Duff et al. 2017)
+        const float sg = __builtin_copysignf(1.0f, wc.z);
+        const float ia = -1.0f / (sg + wc.z);
+        const float b = wc.x * wc.y * ia;
+        const f3 t1 = mk3(1.0f + sg * wc.x * wc.x * ia, sg * b, -sg * wc.x);
+        const f3 t2 = mk3(b, sg + wc.y * wc.y * ia, -wc.y);
+        s.w = (t1 * (sin_t * cp) + t2 * (sin_t * sp)) + wc * cos_t;
+        // near intersection along w, D cos - sqrt(R^2 - D^2 sin^2), in the form without cancellation (product of the roots)
+        const float h = L0.w * L0.w - D2 * sin2;
+        t_light = (D2 - L0.w * L0.w) / (D * cos_t + __builtin_sqrtf(h > 0.0f ? h : 0.0f));
+        pdf_w = 1.0f / (PRT_TWO_PI * omc);
+    }
+    s.t_light = t_light;
+    s.tmax = t_light * (1.0f - PRT_LIGHT_SHADOW_EPS);
+    s.pdf_l = L1.w * pdf_w;
+    return s.pdf_l > 0.0f && s.pdf_l < 3.0e38f && s.tmax > 0.0f;
+}
+
+// MIS weight of a light sample with pdfs (pl, pb) under the context's mode: power heuristic, or 1 (NEE)
+PRT_DEV float light_weight(uint32_t mode, float pl, float pb) {
+    if (mode == (uint32_t)PRT_LIGHTING_NEE) return 1.0f;
+    const float r = pb / pl;
+    return 1.0f / (1.0f + r * r);
+}
+
+// Weight of the emission of analytic primitive `prim` met by a segment scattered at x by a Lambertian vertex with pdf pb
+// (direction w, hit at distance^2 d2): 1 - w_L of the same pair; 1 for emitters outside the light set or where pL = 0.
+PRT_DEV float bsdf_hit_weight(const DevLights& lt, uint32_t prim, f3 x, f3 w, float d2, float pb) {
+    const uint32_t li = lt.prim_light[prim];
+    if (li == 0xFFFFFFFFu) return 1.0f;
+    const float4* L = lt.lights + PRT_LIGHT_F4 * li;
+    const float pl = L[1].w * light_pdf_w(L[0], L[3], x, w, d2);
+    if (!(pl > 0.0f)) return 1.0f;
+    if (lt.mode == (uint32_t)PRT_LIGHTING_NEE) return 0.0f;
+    const float r = pl / pb;  // pb = 0: r = inf, weight 0
+    return 1.0f / (1.0f + r * r);
+}
+
+// Light sample of a Lambertian vertex (position x, shading normal n, albedo, throughput thr before its roulette) with the
+// key of the path's state at the vertex.  false: no sample (pdf 0).  Otherwise s, pb = max(0, n.w) / pi, the weight wl and
+// `contrib`, the clamped term a shadow ray (x, s.w, s.tmax) delivers if unoccluded (zero, and no shadow ray, if n.w <= 0).
+PRT_DEV bool light_sample_term(const DevLights& lt, f3 x, f3 n, f3 albedo, f3 thr, uint32_t key, float clamp, LightSample& s,
+                               float& pb, float& wl, f3& contrib) {
+    if (!sample_light(lt, x, key, s)) return false;
+    const float c = dot3(n, s.w);
+    pb = (c > 0.0f ? c : 0.0f) * PRT_INV_PI;
+    wl = light_weight(lt.mode, s.pdf_l, pb);
+    contrib = mk3(0.0f, 0.0f, 0.0f);
+    if (c > 0.0f) {
+        contrib = ((thr * albedo) * s.le) * ((pb * wl) / s.pdf_l);
+        if (clamp > 0.0f) {  // each delivered term is clamped on its own (PrtSampling.clamp)
+            contrib.x = contrib.x > clamp ? clamp : contrib.x;
+            contrib.y = contrib.y > clamp ? clamp : contrib.y;
+            contrib.z = contrib.z > clamp ? clamp : contrib.z;
+        }
+    }
+    return true;
+}
+
+// advance_path<1, INST, ABVH, SHADE_BLOCK> (no fused segment) with light sampling: the same vertex, the same draws, the same
+// segments; in addition the light sample (`shadow`) of a Lambertian vertex that scatters, emission of light-set emitters
+// met after a Lambertian vertex weighted by bsdf_hit_weight, and pb_next = the pdf of the scatter (-1: not Lambertian).
+template <bool INST, bool ABVH>
+PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t id, f3& o, f3& d, f3& thr, uint32_t& rng,
+                             uint32_t& depth, uint32_t max_depth, const PrtSampling& sp, float4* __restrict__ rad_slot,
+                             uint32_t& id0, float& d2_0, float pb_prev, float& pb_next, bool& shadow, f3& sx, f3& sw,
+                             float& stmax, f3& scontrib) {
+    if (id == HIT_MISS) {
+        st_stream(rad_slot, path_result(thr * mk3(sc.sky[0], sc.sky[1], sc.sky[2]), sp.clamp, depth));
+        return 0;
+    }
+    WorldHit w;
+    world_hit_from_id<INST>(sc, id, o, d, w);
+    const uint32_t type = sc.mat_type[w.material];
+    const float4 rgbs = sc.mat_rgbs[w.material];
+    const uint32_t key = rng;  // the path's state at the vertex
+    f3 atten, emitted, so, sd;
+    bool scattered = false;
+    if (depth + 1u >= max_depth) {
+        emitted = (type == 4u) ? mk3(rgbs.x, rgbs.y, rgbs.z) : mk3(0.f, 0.f, 0.f);
+    } else {
+        scattered = material_scatter(type, rgbs, d, w.pos, w.normal, w.front, rng, atten, emitted, so, sd);
+    }
+    if (!scattered) {
+        f3 L = thr * emitted;
+        if (type == 4u && id < sc.n_prims && pb_prev >= 0.0f) {
+            const float wb = bsdf_hit_weight(lt, id, o, d, w.d2, pb_prev);
+            if (wb != 1.0f) L = L * wb;
+        }
+        st_stream(rad_slot, path_result(L, sp.clamp, depth));
+        return 0;
+    }
+    if (type == 1u && lt.n_lights) {  // (scattered: depth + 1 < max_depth)
+        LightSample ls;
+        float pb, wl;
+        if (light_sample_term(lt, w.pos, w.normal, mk3(rgbs.x, rgbs.y, rgbs.z), thr, key, sp.clamp, ls, pb, wl, scontrib) &&
+            pb > 0.0f) {
+            shadow = true;
+            sw = ls.w;
+            stmax = ls.tmax;
+        }
+    }
+    sx = w.pos;
+    thr = thr * atten;
+    o = so;
+    d = normalize3(sd);
+    if (type == 1u) {
+        const float c = dot3(w.normal, d);
+        pb_next = (c > 0.0f ? c : 0.0f) * PRT_INV_PI;
+    }
+    if (sp.rr_depth != 0u && depth + 1u >= sp.rr_depth) {
+        float p = thr.x > thr.y ? thr.x : thr.y;
+        p = p > thr.z ? p : thr.z;
+        p = p > 1.0f ? 1.0f : p;
+        p = p < 0.05f ? 0.05f : p;
+        if (!(rnd01(rng) < p)) {
+            st_stream(rad_slot, path_result(mk3(0.f, 0.f, 0.f), 0.0f, depth));
+            return 0;
+        }
+        thr = mk3(thr.x / p, thr.y / p, thr.z / p);
+    }
+    ++depth;
+    if (classify_ray<ABVH, SHADE_BLOCK>(sc, o, d, id0, d2_0)) return 1;
+    // the new segment cannot hit a triangle: its closest hit is the analytic scan's (advance_path's budget step)
+    if (id0 == HIT_MISS) {
+        st_stream(rad_slot, path_result(thr * mk3(sc.sky[0], sc.sky[1], sc.sky[2]), sp.clamp, depth));
+        return 0;
+    }
+    const uint32_t m = sc.prims[id0].material;
+    if (sc.mat_type[m] == 4u) {
+        const float4 e = sc.mat_rgbs[m];
+        f3 L = thr * mk3(e.x, e.y, e.z);
+        if (pb_next >= 0.0f) {
+            const float wb = bsdf_hit_weight(lt, id0, o, d, d2_0, pb_next);
+            if (wb != 1.0f) L = L * wb;
+        }
+        st_stream(rad_slot, path_result(L, sp.clamp, depth));
+        return 0;
+    }
+    return 2;
+}
+
+template <bool INST, bool ABVH>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee(DevScene sc, DevLights lt, const float4* __restrict__ ro,
+                                                          const float4* __restrict__ rd, const float4* __restrict__ rt,
+                                                          const uint32_t* __restrict__ hit, float4* __restrict__ no,
+                                                          float4* __restrict__ nd, float4* __restrict__ nt,
+                                                          uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
+                                                          PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                                                          uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
+                                                          uint32_t cap, PrtSampling sp) {
+    const uint32_t nA = CNT_A(counts, iter), nB = CNT_B(counts, iter);
+    const uint32_t count = nA + nB;
+    if (blockIdx.x * (uint32_t)SHADE_BLOCK >= count) return;  // whole block exits together
+    const uint32_t k = blockIdx.x * (uint32_t)SHADE_BLOCK + threadIdx.x;
+    if (k < 8u) work[32u * k] = 0u;  // chunk cursors of the shadow walk / the next bounce's traversal
+    if (k == 8u) work[512] = 0u;
+    bool front = false, back = false, shadow = false;
+    f3 o = mk3(0.f, 0.f, 0.f), d = mk3(0.f, 0.f, 1.f), thr = mk3(0.f, 0.f, 0.f);
+    f3 sx = o, sw = d, sc_rgb = o;
+    float stmax = 0.0f, pb_next = -1.0f;
+    uint32_t id0 = HIT_MISS, rng = 0, depth = 0, pid = 0;
+    float d2_0 = 3.402823466e+38f;
+    if (k < count) {
+        const uint32_t src = k < nA ? k : cap - 1u - (k - nA);
+        const uint32_t id = ld_stream(&hit[src]);
+        const float4 O = ld_stream(&ro[src]);
+        const float4 D = ld_stream(&rd[src]);
+        const float4 T = ld_stream(&rt[src]);
+        pid = __float_as_uint(O.w);
+        rng = __float_as_uint(D.w);
+        depth = __float_as_uint(T.w);
+        thr = mk3(T.x, T.y, T.z);
+        o = mk3(O.x, O.y, O.z);
+        d = mk3(D.x, D.y, D.z);
+        // pdf of the scatter that started this segment (segment 0 starts at the camera)
+        const float pb_prev = depth ? lb.pdf_b[pid] : -1.0f;
+        if (id != HIT_DEAD) {
+            const int r = advance_path_nee<INST, ABVH>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
+                                                       pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb);
+            front = r == 1;
+            back = r == 2;
+        }
+    }
+    const uint32_t slot = block_alloc2<SHADE_BLOCK>(front, back, false, &CNT_A(counts, iter + 1u), &CNT_B(counts, iter + 1u),
+                                                    &CNT_C(counts, iter + 1u), cap);
+    if (slot != 0xFFFFFFFFu) {
+        st_stream(&no[slot], make_float4(o.x, o.y, o.z, __uint_as_float(pid)));
+        st_stream(&nd[slot], make_float4(d.x, d.y, d.z, __uint_as_float(rng)));
+        st_stream(&nt[slot], make_float4(thr.x, thr.y, thr.z, __uint_as_float(depth)));
+        st_stream(&nhit[slot], id0);
+        st_stream(&nhd2[slot], d2_0);
+        lb.pdf_b[pid] = pb_next;  // (one writer per path; read by the path's next k_shade_nee)
+    }
+    __syncthreads();  // block_alloc2's LDS counts are reused below (see its contract)
+    uint32_t* cs = &counts[iter * CNT_STRIDE + 48u];
+    const uint32_t ss = block_alloc2<SHADE_BLOCK>(shadow, false, false, cs, cs, cs, cap);
+    if (ss != 0xFFFFFFFFu) {  // seeded as k_pack_occlusion_rays seeds a ray: a miss at hd2 = tmax^2
+        lb.sh.o[ss] = make_float4(sx.x, sx.y, sx.z, __uint_as_float(pid));
+        lb.sh.d[ss] = make_float4(sw.x, sw.y, sw.z, 0.0f);
+        lb.sh.t[ss] = make_float4(sc_rgb.x, sc_rgb.y, sc_rgb.z, stmax);
+        lb.sh.hit[ss] = HIT_MISS;
+        lb.sh.hd2[ss] = stmax * stmax;
+    }
+}
+
+// After the shadow walk: every unoccluded shadow ray adds its contribution to its path's light radiance (at most one shadow
+// ray per path per bounce: no atomics; the sum runs in vertex order).  The blocker test is k_occlusion_bytes': exact
+// whichever walk produced the id.  Also resets the traversal cursors for the next bounce and counts the rays.
+__global__ void __launch_bounds__(256) k_light_accum(DevScene sc, PrtLightBufs lb, const uint32_t* __restrict__ count_ptr,
+                                                     uint32_t* __restrict__ work) {
+    __shared__ uint32_t s_n[2];
+    const uint32_t count = *count_ptr;
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < 8u) work[32u * k] = 0u;
+    if (k == 8u) work[512] = 0u;
+    if (blockIdx.x * 256u >= count) return;  // whole block exits together
+    if (threadIdx.x < 2u) s_n[threadIdx.x] = 0u;
+    __syncthreads();
+    bool occ = false;
+    if (k < count) {
+        const uint32_t id = lb.sh.hit[k];
+        const float4 O = lb.sh.o[k];
+        const float4 T = lb.sh.t[k];
+        if (id != HIT_MISS && id != HIT_DEAD) {
+            const float4 D = lb.sh.d[k];
+            WorldHit w;
+            if (sc.n_insts)
+                world_hit_from_id<true>(sc, id, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), w);
+            else
+                world_hit_from_id<false>(sc, id, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), w);
+            occ = w.has && w.d2 < T.w * T.w;
+        }
+        if (!occ) {
+            float4* p = &lb.lrad[__float_as_uint(O.w)];
+            float4 a = *p;
+            a.x = a.x + T.x;
+            a.y = a.y + T.y;
+            a.z = a.z + T.z;
+            *p = a;
+        }
+    }
+    const unsigned long long mn = __ballot(k < count), mo = __ballot(occ);
+    if (lane_id() == 0u) {
+        atomicAdd(&s_n[0], (uint32_t)__popcll(mn));
+        atomicAdd(&s_n[1], (uint32_t)__popcll(mo));
+    }
+    __syncthreads();
+    // (PRT_RAY_STAT_SLOTS copies of the two counters, block b adds to copy b mod SLOTS, summed by the host: one word executes
+    // only ~87 atomics per microsecond, as for k_accumulate's ray counters)
+    if (threadIdx.x < 2u && s_n[threadIdx.x])
+        atomicAdd(&lb.stats[2u * (blockIdx.x & (PRT_RAY_STAT_SLOTS - 1u)) + threadIdx.x], (unsigned long long)s_n[threadIdx.x]);
+}
+
+// prt_sample_light: one light sample per (hit, key) through the render's own light_sample_term (throughput 1, no clamp) and,
+// for the same pair of vertices, the weight bsdf_hit_weight gives a scattered segment in direction w that meets the light;
+// out 11 floats per ray: w.xyz, tmax, contrib.rgb, pdf_light, pdf_bsdf, w_light, w_bsdf
+__global__ void k_sample_light_test(DevScene sc, DevLights lt, uint32_t n, const float* __restrict__ in_d,
+                                    const PrtHit* __restrict__ hits, const uint32_t* __restrict__ keys, float* __restrict__ out,
+                                    uint32_t* __restrict__ out_light) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const PrtHit h = hits[i];
+    float r[11] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    uint32_t light = 0xFFFFFFFFu;
+    if (h.prim >= 0 && sc.mat_type[h.material_id] == 1u && lt.n_lights) {
+        const float4 a = sc.mat_rgbs[h.material_id];
+        const f3 x = mk3(h.position[0], h.position[1], h.position[2]);
+        LightSample s;
+        float pb = 0.0f, wl = 0.0f;
+        f3 C;
+        if (light_sample_term(lt, x, mk3(h.normal[0], h.normal[1], h.normal[2]), mk3(a.x, a.y, a.z), mk3(1.f, 1.f, 1.f), keys[i],
+                              0.0f, s, pb, wl, C)) {
+            light = s.light;
+            const uint32_t prim = __float_as_uint(lt.lights[PRT_LIGHT_F4 * s.light + 4u].w);
+            const float vals[11] = {s.w.x, s.w.y, s.w.z, s.tmax, C.x, C.y, C.z, s.pdf_l, pb, wl,
+                                    bsdf_hit_weight(lt, prim, x, s.w, s.t_light * s.t_light, pb)};
+            for (int j = 0; j < 11; ++j) r[j] = vals[j];
+        }
+    }
+    for (int j = 0; j < 11; ++j) out[11 * (size_t)i + j] = r[j];
+    out_light[i] = light;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3250,4 +3683,37 @@ void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, con
                              float* d_out) {
     hipLaunchKernelGGL(k_scatter_test, dim3(blocks_for(n)), dim3(256), 0, st, sc, n, in_d, hits, rng_io, scattered,
                        atten, emitted, o_out, d_out);
+}
+
+void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
+                          const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
+                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known) {
+    const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
+    const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
+#define PRT_SHADE_NEE(IN, AB)                                                                                          \
+    hipLaunchKernelGGL((k_shade_nee<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, in.o, in.d, in.t, in.hit, out.o,  \
+                       out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+    if (sc.abvh_nodes) {
+        if (sc.n_insts) PRT_SHADE_NEE(true, true); else PRT_SHADE_NEE(false, true);
+    } else {
+        if (sc.n_insts) PRT_SHADE_NEE(true, false); else PRT_SHADE_NEE(false, false);
+    }
+#undef PRT_SHADE_NEE
+}
+
+void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBufs& lb, const uint32_t* count_ptr,
+                            uint32_t* work, uint32_t max_rays) {
+    hipLaunchKernelGGL(k_light_accum, dim3(blocks_for(max_rays ? max_rays : 1u)), dim3(256), 0, st, sc, lb, count_ptr, work);
+}
+
+void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, const PrtTileMap& tm,
+                               uint32_t S, uint32_t max_depth, bool update_film, unsigned long long* ray_stats) {
+    const uint32_t nb = blocks_for(tm.n_pix_local ? tm.n_pix_local : 1);
+    hipLaunchKernelGGL(k_accumulate_lit, dim3(nb < 8192u ? nb : 8192u), dim3(256), 0, st, rad, lrad, film_local, tm, S,
+                       max_depth, update_film ? 1 : 0, ray_stats);
+}
+
+void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
+                                  const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light) {
+    hipLaunchKernelGGL(k_sample_light_test, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, n, in_d, hits, keys, out_f, out_light);
 }

@@ -159,6 +159,16 @@ public:
     }
     void SetSamplesInFlight(uint32_t n) { check(prt_group_set_samples_in_flight(grp_, n)); }
     void SetParam(const char* name, int value) { check(prt_group_set_param(grp_, name, value)); }
+    // Light sampling toward the analytic emitters (PrtLighting): PRT_LIGHTING_OFF / _NEE_MIS / _NEE
+    void SetLighting(uint32_t mode) {
+        const PrtLighting l{mode};
+        check(prt_group_set_lighting(grp_, &l));
+    }
+    PrtLightStats LightStats() {
+        PrtLightStats s{};
+        check(prt_group_get_light_stats(grp_, &s));
+        return s;
+    }
     void Clear() {
         check(prt_group_film_clear(grp_));
         frame_ = 0;

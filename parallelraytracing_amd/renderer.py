@@ -371,6 +371,43 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_set_sampling(self._ctx, C.byref(sp)))
         return sp
 
+    def set_lighting(self, mode) -> int:
+        """Light sampling toward the analytic emitters (include/prt.h PrtLighting): "off" | "mis" | "nee" or 0 | 1 | 2."""
+        m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
+        self._check(capi.lib().prt_set_lighting(self._ctx, C.byref(capi.PrtLighting(m))))
+        return m
+
+    def light_info(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The light set of the current scene: (primitive index [n] uint32, pmf [n] float32).  Host-only contexts too."""
+        n = C.c_uint32(0)
+        self._check(capi.lib().prt_light_info(self._ctx, 0, C.byref(n), None, None))
+        prim = np.zeros(n.value, np.uint32)
+        pmf = np.zeros(n.value, np.float32)
+        self._check(capi.lib().prt_light_info(self._ctx, n.value, C.byref(n), prim.ctypes.data_as(_u32p), pmf.ctypes.data_as(_fp)))
+        return prim, pmf
+
+    def light_stats(self) -> "capi.PrtLightStats":
+        s = capi.PrtLightStats()
+        self._check(capi.lib().prt_get_light_stats(self._ctx, C.byref(s)))
+        return s
+
+    def sample_light(self, in_dirs, hits: np.ndarray, keys) -> dict:
+        """prt_sample_light: one light sample per (hit, key) through the render's device code."""
+        d = _f32(in_dirs).reshape(-1, 3)
+        n = d.shape[0]
+        hits = np.ascontiguousarray(hits)
+        k = np.ascontiguousarray(keys, dtype=np.uint32)
+        sd, contrib = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        tmax, pl, pb, wl, wb = (np.zeros(n, np.float32) for _ in range(5))
+        light = np.zeros(n, np.uint32)
+        self._check(capi.lib().prt_sample_light(self._ctx, n, d.ctypes.data_as(_fp), hits.ctypes.data_as(C.POINTER(PrtHit)),
+                                                k.ctypes.data_as(_u32p), sd.ctypes.data_as(_fp), tmax.ctypes.data_as(_fp),
+                                                light.ctypes.data_as(_u32p), contrib.ctypes.data_as(_fp),
+                                                pl.ctypes.data_as(_fp), pb.ctypes.data_as(_fp), wl.ctypes.data_as(_fp),
+                                                wb.ctypes.data_as(_fp)))
+        return {"dir": sd, "tmax": tmax, "light": light, "contrib": contrib, "pdf_light": pl, "pdf_bsdf": pb, "w_light": wl,
+                "w_bsdf": wb}
+
     def set_variant(self, v: int):
         self._check(capi.lib().prt_set_variant(self._ctx, v))
 
@@ -678,6 +715,29 @@ class HipWavefrontGroupRenderer:
         sp = PrtSampling(int(jitter), int(rr_depth), float(clamp))
         self._check(capi.lib().prt_group_set_sampling(self._grp, C.byref(sp)))
         return sp
+
+    def set_lighting(self, mode) -> int:
+        m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
+        self._check(capi.lib().prt_group_set_lighting(self._grp, C.byref(capi.PrtLighting(m))))
+        return m
+
+    def light_info(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The light set as rank 0 holds it (every rank holds the same)."""
+        L = capi.lib()
+        ctx = L.prt_group_context(self._grp, 0)
+        n = C.c_uint32(0)
+        if L.prt_light_info(ctx, 0, C.byref(n), None, None):
+            raise PrtError(L.prt_last_error(ctx).decode())
+        prim = np.zeros(n.value, np.uint32)
+        pmf = np.zeros(n.value, np.float32)
+        if L.prt_light_info(ctx, n.value, C.byref(n), prim.ctypes.data_as(_u32p), pmf.ctypes.data_as(_fp)):
+            raise PrtError(L.prt_last_error(ctx).decode())
+        return prim, pmf
+
+    def light_stats(self) -> "capi.PrtLightStats":
+        s = capi.PrtLightStats()
+        self._check(capi.lib().prt_group_get_light_stats(self._grp, C.byref(s)))
+        return s
 
     def download(self) -> Film:
         f = self.film
