@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomized parity: random scenes (analytic primitives of every material, refined meshes, placed copies), random cameras,
 builders, kernel tunables and sampling flags; every frame bit for bit against the oracle (throughput form) + ray counts.
+--lighting: the same generators with emissive analytic primitives and light sampling, every sample against the float64 replay.
   python tests/fuzz_parity.py --cases 200 --seed 1      (GPU box; ~0.3 s per case)
 Test infrastructure (it calls the oracle): a checker, not a product path; tests/test_gpu_fuzz.py runs a seeded subset."""
 import argparse
@@ -385,6 +386,100 @@ def run_graze_quads_case(case, seed, n=100_000, cos_lo=1e-5, cos_hi=0.08):
     return f"quad graze case {case}: {'ok ' if ok else 'MISMATCH'} {k} quads, {len(bad)} of {n} rays differ{extra}", ok, cosi[bad, 0]
 
 
+def lighting_draw(rng):
+    """A random scene, camera, frame and settings for a light-sampled render (run_lighting_case)."""
+    scene, desc, kind, _ = random_scene(rng)
+    # with random probability analytic primitives become emitters; sometimes one with a transform outside the light set
+    e2 = scene.AddEmissive(tuple(rng.uniform(1, 8, 3)))
+    turned = 0
+    for p in scene.primitives[1:]:
+        if rng.random() < 0.15:
+            p.material_id = e2
+            turned += 1
+    if rng.random() < 0.3:
+        scene.AddCircle(float(rng.uniform(0.3, 0.8)), e2, scale=(1.5, 1.0, 0.7), translation=tuple(float(v) for v in rng.uniform(-4, 4, 3)))
+        desc += ", a stretched emitter"
+    desc += f", {turned} turned emissive"
+    W, H = int(rng.choice([64, 96, 131])), int(rng.choice([48, 72]))
+    pos = rng.normal(size=3)
+    pos = pos / np.linalg.norm(pos) * rng.uniform(3, 14)
+    pos[1] = abs(pos[1]) + 0.3
+    front = -pos + rng.uniform(-1, 1, 3)
+    cam = prt.Camera(position=tuple(float(v) for v in pos), front=tuple(float(v) for v in front), width=W, height=H)
+    depth = int(rng.integers(2, 9))
+    rseed = int(rng.integers(0, 1 << 30))
+    mode = str(rng.choice(["mis", "nee"]))
+    smp = (0, 0, 0.0)
+    if rng.random() < 0.5:
+        smp = (int(rng.integers(0, 2)), int(rng.choice([0, 1, 3])), float(rng.choice([0.0, 1.5])))
+    params = {}
+    if kind != "none" and rng.random() < 0.5:
+        params["gpu_build"] = int(rng.choice([1, 2]))
+    if rng.random() < 0.3:
+        params["node_stride"] = 8
+    if rng.random() < 0.3:
+        params["prim_bvh"] = 0
+    if rng.random() < 0.2:
+        params["exact_grids"] = int(rng.integers(0, 3))
+    if rng.random() < 0.3:
+        params["steal"] = 0
+        params["tail"] = 0
+    if rng.random() < 0.25:
+        params["big"] = int(rng.choice([2, 3, 5]))
+        params["big_min"] = 1
+        params["big_keep"] = int(rng.choice([0, 1, 4]))
+        params["chunk"] = int(rng.choice([64, 128, 256]))
+    if rng.random() < 0.3:
+        params["static_small"] = int(rng.choice([0, 2, 64]))
+    samples = (0, int(rng.integers(1, 40)))
+    sif = int(rng.choice([1, 2, 16]))
+    return dict(scene=scene, desc=desc, cam=cam, W=W, H=H, depth=depth, seed=rseed, mode=mode, sampling=smp, params=params,
+                samples=samples, sif=sif)
+
+
+def run_lighting_case(case, seed, render=True):
+    """A random scene with emissive analytic primitives, rendered with light sampling (random mode, sampling flags, tunables
+    and batching), every sample of every pixel against the float64 per-path replay of tests/lighting_replay.py.  A draw whose
+    share of undecidable light samples exceeds the replay's cap is redrawn.  -> (message, ok, redraws).
+    render=False: the reference side alone (no GPU), to measure the redraw rate."""
+    import lighting_replay as lr
+    for attempt in range(5):
+        rng = np.random.default_rng([seed, case, 8086, attempt])
+        c = lighting_draw(rng)
+        osc = orc.OracleScene(c["scene"].desc())
+        rep = lr.replay(c["scene"], c["cam"], c["W"], c["H"], c["depth"], c["seed"], c["samples"], c["mode"], c["sampling"],
+                        use_bvh=c["scene"].n_triangles > 6000, osc=osc)
+        if lr.unstable_share(rep) <= lr.MAX_UNSTABLE:
+            break
+    else:
+        return f"lighting case {case}: no draw within the cap in 5 attempts", False, 5
+    head = (f"lighting case {case}: {c['W']}x{c['H']} depth {c['depth']} {c['mode']} [{c['desc']}] params {c['params']} sampling "
+            f"{c['sampling']} lights {rep.lights.n} light samples {rep.n_light_samples} occluded {rep.shadow_occluded} "
+            f"unstable {rep.n_unstable} redraws {attempt}")
+    if not render:
+        return head, True, attempt
+    r = prt.HipWavefrontRenderer(device=0, max_depth=c["depth"], seed=c["seed"])
+    for k, v in c["params"].items():
+        r.set_param(k, v)
+    film = prt.Film(c["W"], c["H"])
+    try:
+        r.Init(film, c["scene"], c["cam"])
+    except prt.PrtError as e:  # e.g. a tree too deep for the two-level kernel: must be a clean error
+        return f"lighting case {case}: Init refused ({str(e)[:80]}) [{c['desc']}]", True, attempt
+    r.set_samples_in_flight(c["sif"])
+    r.set_lighting(c["mode"])
+    if c["sampling"] != (0, 0, 0.0):
+        r.set_sampling(*c["sampling"])
+    r.reset_stats()
+    frames = lr.render_samples(r, film, c["samples"])
+    r.synchronize()
+    try:
+        rec = lr.check_against_gpu(rep, frames, r.light_stats(), r.light_info(), quiet=True)
+    except AssertionError as e:
+        return f"{head}: MISMATCH {str(e)[:400]}", False, attempt
+    return f"{head}: ok, worst error / tolerance {rec['worst_ratio']}", True, attempt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=100)
@@ -396,11 +491,14 @@ def main():
     ap.add_argument("--graze-quads", action="store_true", help="rays grazing quads along their edges (walk over the primitives' boxes)")
     ap.add_argument("--cos-lo", type=float, default=1e-5, help="--graze-quads: smallest cosine of incidence")
     ap.add_argument("--rays", action="store_true", help="closest-hit cases with awkward rays against the brute-force scan")
+    ap.add_argument("--lighting", action="store_true", help="light-sampled frames against the float64 per-path replay")
+    ap.add_argument("--no-render", action="store_true", help="--lighting: the reference side alone (no GPU): redraw rate")
     a = ap.parse_args()
     t0 = time.time()
     bad = 0
     for case in range(a.first, a.first + a.cases):
-        msg, ok = (run_ray_case(case, a.seed) if a.rays else run_sequence_case(case, a.seed) if a.sequences else
+        msg, ok = (run_lighting_case(case, a.seed, render=not a.no_render)[:2] if a.lighting else
+                   run_ray_case(case, a.seed) if a.rays else run_sequence_case(case, a.seed) if a.sequences else
                    run_graze_case(case, a.seed) if a.graze else
                    run_graze_quads_case(case, a.seed, cos_lo=a.cos_lo)[:2] if a.graze_quads else run_case(case, a.seed))
         if not ok:

@@ -5,7 +5,8 @@ combination), a camera, frame size, depth, sample count and batching, one of the
 tunables (incl. a stack so small that rays take the overflow list) and the sampling flags, renders through the C-ABI and
 compares EVERY pixel and the ray count with the oracle's throughput form (CPURenderer::TraceRay's iterative twin,
 backend/cuda_megakernel/renderer.cu:81-119; PrimitiveList::Intersect semantics, core/primitive.cpp:21-59).
-A longer run (6,300 cases, 0 mismatches) is recorded in DESIGN.md."""
+A longer run (6,300 cases, 0 mismatches) is recorded in DESIGN.md.
+48 further cases render with light sampling and are held, sample by sample, to the float64 replay (tests/lighting_replay.py)."""
 import importlib.util
 import os
 
@@ -28,6 +29,23 @@ def test_random_scenes_cameras_builders_and_tunables_bit_exact(first):
         if not ok:
             bad.append(msg)
     assert bad == []
+
+
+@pytest.mark.parametrize("first", [0, 24])
+def test_random_light_sampled_scenes_match_the_float64_replay(first):
+    """fuzz_parity.run_lighting_case: the generators above with analytic primitives turned emissive at random (and emitters
+    outside the light set), a random mode, sampling flags, batching and the tunables lighting honours; two sample indices per
+    case, every stable pixel sample within the tolerance of tests/lighting_replay.py, shadow-ray counts and light set as in
+    tests/test_gpu_lighting_replay.py.  A draw with too many undecidable light samples is redrawn; at most 10 % may be."""
+    bad, redraws = [], 0
+    for case in range(first, first + 24):
+        msg, ok, n = fuzz.run_lighting_case(case, seed=17)
+        print(msg, flush=True)
+        redraws += n
+        if not ok:
+            bad.append(msg)
+    assert bad == []
+    assert redraws <= 0.1 * 24, redraws
 
 
 @pytest.mark.parametrize("first", [0, 40])
