@@ -8,7 +8,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -17,21 +16,21 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/prt.h"
 #include "bvh.h"
 #include "bvh_gpu.h"
 #include "prt_kernels.h"
+#include "prt_scene.h"
 
 namespace {
 
 constexpr float kPadCoeff = 1.0f / 262144.0f;  // 2^-18, see traverse() in prt_kernels.hip
-constexpr uint32_t kMaxLeaf = 3;  // the compressed 8-wide node encodes at most 3 triangles per leaf (bvh.h)
 constexpr size_t kRayStatWords = (size_t)PRT_RAY_STAT_SLOTS * PRT_MAX_DEPTH;
 constexpr uint32_t kTravStatsWords = 16 + PRT_TIMELINE_WORDS * (PRT_MAX_DEPTH + 1);  // counters + one launch timeline per bounce
-constexpr uint32_t kMaxStack = 63;
-constexpr size_t kLightStatWords = 2 * (size_t)PRT_RAY_STAT_SLOTS;  // k_light_accum's [slot][shadow rays, occluded]  // LDS stack entries per lane: 31 (5 blocks/CU) or 63 (2 blocks/CU)
+constexpr size_t kLightStatWords = 2 * (size_t)PRT_RAY_STAT_SLOTS;  // k_light_accum's [slot][shadow rays, occluded]
 
 struct EventPair {
     hipEvent_t a, b;
@@ -49,20 +48,8 @@ struct PrtContext {
 
     // ---- scene ----
     bool has_scene = false;
-    std::vector<PrtMaterial> materials;
-    std::vector<DevPrim> prims;
-    BvhBuild bvh;
-    std::vector<float> tri_records;   // 12 floats per triangle, leaf order
-    std::vector<float> nrm_records;   // 12 floats per triangle, leaf order
-    double gpu_build_ms = 0.0;
-    bool scene_device_built = false;  // the scene's 8-wide tree came from the device-side builder (no binary / 4-wide tree)
-    std::vector<uint32_t> mesh_sizes;  // per world-space mesh of the scene: n_vertices, n_triangles (prt_refit_meshes checks them)
+    PrtHostScene hs;                   // the compiled scene (prt_scene.h): every host array the device copies come from
     double refit_ms = 0.0;             // device time of the last prt_refit_meshes (records + boxes + quantization)
-    std::vector<uint32_t> nodes8_all;  // scenes with placed mesh copies: top-level tree + every mesh's tree
-    std::vector<DevInstance> dev_insts;
-    std::vector<uint32_t> tlas_inst;   // top-level leaf slot -> instance
-    BvhBuild abvh;                     // BVH over the analytic primitives' world boxes (scenes with many of them)
-    PrtBvhInfo bvh_info{};
     DevScene dsc{};
     void* d_prims = nullptr;
     void* d_mat_rgbs = nullptr;
@@ -136,9 +123,6 @@ struct PrtContext {
 
     // ---- light sampling (PrtLighting, include/prt.h) ----
     uint32_t lighting = PRT_LIGHTING_OFF;
-    std::vector<float> lights;         // the light table: 4 * PRT_LIGHT_F4 floats per light (prt_kernels.h DevLights)
-    std::vector<uint32_t> prim_light;  // per analytic primitive: its light index, 0xFFFFFFFF if not in the light set
-    uint32_t n_emitters_unsampled = 0;
     void* d_lights = nullptr;
     void* d_prim_light = nullptr;
     PrtLightBufs lb{};                 // shadow rays, pdf of the previous scatter, light radiance: cap_light paths each
@@ -254,101 +238,8 @@ int ensure_light_state(PrtContext* c, uint64_t n_paths) {
 
 DevLights dev_lights(const PrtContext* c) {
     return DevLights{(const float4*)c->d_lights, (const uint32_t*)c->d_prim_light,
-                     (uint32_t)(c->lights.size() / (4 * PRT_LIGHT_F4)),
+                     (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4)),
                      c->lighting == PRT_LIGHTING_NEE ? (uint32_t)PRT_LIGHTING_NEE : (uint32_t)PRT_LIGHTING_NEE_MIS};
-}
-
-// Rotation + uniform scale + translation with inv = inverse(mat) (column-major mat4s): transpose(M3) * M3 = s^2 * I, bottom row
-// (0, 0, 0, 1), inv * mat = I.  Only for such transforms is the reference's local ray (primitive.cpp:29-30) a ray transform.
-// *s2_out = s^2.
-bool is_similarity(const float* M, const float* inv, double* s2_out) {
-    double g[3][3];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b)
-            g[a][b] = (double)M[4 * a] * M[4 * b] + (double)M[4 * a + 1] * M[4 * b + 1] + (double)M[4 * a + 2] * M[4 * b + 2];
-    const double s2 = g[0][0];
-    bool ok = s2 > 1e-20 && std::isfinite(s2);
-    for (int a = 0; a < 3 && ok; ++a)
-        for (int b = 0; b < 3; ++b)
-            if (std::fabs(g[a][b] - (a == b ? s2 : 0.0)) > 1e-4 * s2) ok = false;
-    for (int r = 0; r < 4 && ok; ++r)
-        for (int cc = 0; cc < 4; ++cc) {
-            double acc = 0.0;
-            for (int kk = 0; kk < 4; ++kk) acc += (double)inv[4 * kk + r] * (double)M[4 * cc + kk];
-            if (std::fabs(acc - (r == cc ? 1.0 : 0.0)) > 1e-3) ok = false;
-        }
-    *s2_out = s2;
-    return ok && M[3] == 0.0f && M[7] == 0.0f && M[11] == 0.0f && M[15] == 1.0f;
-}
-
-// The light set of a scene (include/prt.h PrtLighting): emissive analytic primitives with positive mean emission and a
-// rotation + uniform scale + translation transform with inv = inverse(mat) (the test prt_set_scene applies to placed copies:
-// only then is the surface the reference intersects, primitive.cpp:29-30, the one sampled here).  pmf ~ emitting area x
-// mean(rgb), computed in double.  Every other emissive primitive (mesh and placed triangles, other transforms) counts
-// in n_emitters_unsampled.
-void build_light_table(PrtContext* c, const PrtSceneDesc* s) {
-    c->lights.clear();
-    c->prim_light.assign(s->n_primitives, 0xFFFFFFFFu);
-    c->n_emitters_unsampled = 0;
-    auto emissive = [&](uint32_t m) { return m < s->n_materials && s->materials[m].type == PRT_MAT_EMISSIVE; };
-    std::vector<double> power;
-    for (uint32_t i = 0; i < s->n_primitives; ++i) {
-        const PrtPrimitive& p = s->primitives[i];
-        if (!emissive(p.material_id)) continue;
-        const float* M = p.mat;
-        double s2 = 0.0;
-        if (!is_similarity(p.mat, p.inv, &s2)) {
-            ++c->n_emitters_unsampled;
-            continue;
-        }
-        const float* rgb = s->materials[p.material_id].rgb;
-        const double mean = ((double)rgb[0] + (double)rgb[1] + (double)rgb[2]) / 3.0;
-        const bool quad = p.shape_type == PRT_SHAPE_QUAD;
-        const double w = p.shape_param[0], h = p.shape_param[1];
-        const double area = quad ? std::fabs(w * h) * s2 : 4.0 * M_PI * w * w * s2;
-        const double pw = (quad ? 2.0 * area : area) * mean;  // a quad emits from both faces
-        if (!(pw > 0.0) || !std::isfinite(pw)) continue;      // emits nothing: not a light, nothing unsampled either
-        float rec[4 * PRT_LIGHT_F4] = {};
-        rec[0] = M[12];
-        rec[1] = M[13];
-        rec[2] = M[14];
-        rec[3] = quad ? (float)area : (float)(std::fabs(w) * std::sqrt(s2));
-        const double nx = (double)M[1] * M[10] - (double)M[2] * M[9], ny = (double)M[2] * M[8] - (double)M[0] * M[10],
-                     nz = (double)M[0] * M[9] - (double)M[1] * M[8];
-        const double nl = std::sqrt(nx * nx + ny * ny + nz * nz);
-        for (int a = 0; a < 3; ++a) {
-            rec[4 + a] = quad ? (float)(w * M[a]) : 0.0f;
-            rec[8 + a] = quad ? (float)(h * M[8 + a]) : 0.0f;
-        }
-        if (quad) {
-            rec[12] = (float)(nx / nl);
-            rec[13] = (float)(ny / nl);
-            rec[14] = (float)(nz / nl);
-        }
-        const uint32_t kind = quad ? 1u : 0u;
-        memcpy(&rec[15], &kind, 4);
-        rec[16] = rgb[0];
-        rec[17] = rgb[1];
-        rec[18] = rgb[2];
-        memcpy(&rec[19], &i, 4);
-        c->prim_light[i] = (uint32_t)power.size();
-        power.push_back(pw);
-        c->lights.insert(c->lights.end(), rec, rec + 4 * PRT_LIGHT_F4);
-    }
-    double total = 0.0;
-    for (double pw : power) total += pw;
-    double acc = 0.0;
-    for (size_t l = 0; l < power.size(); ++l) {
-        acc += power[l];
-        c->lights[4 * PRT_LIGHT_F4 * l + 7] = (float)(power[l] / total);                                 // pmf
-        c->lights[4 * PRT_LIGHT_F4 * l + 11] = l + 1 == power.size() ? 1.0f : (float)(acc / total);  // cdf
-    }
-    for (uint32_t m = 0; m < s->n_meshes; ++m)
-        if (emissive(s->meshes[m].material_id)) c->n_emitters_unsampled += s->meshes[m].n_triangles;
-    for (uint32_t i = 0; i < s->n_instances; ++i) {
-        const PrtInstance& pi = s->instances[i];
-        if (emissive(pi.material_id) && pi.mesh < s->n_instanced_meshes) c->n_emitters_unsampled += s->instanced_meshes[pi.mesh].n_triangles;
-    }
 }
 
 int ensure_counters(PrtContext* c) {
@@ -453,11 +344,6 @@ int drain_events(PrtContext* c) {
     return PRT_OK;
 }
 
-void to_dev_mat(const float* m16, float* m12) {
-    for (int col = 0; col < 4; ++col)
-        for (int r = 0; r < 3; ++r) m12[col * 3 + r] = m16[col * 4 + r];
-}
-
 // glm-order helpers for the camera basis (Camera::Camera, src/core/camera.h:10-16)
 f3 h_normalize(f3 v) {
     const float d = (v.x * v.x + v.y * v.y) + v.z * v.z;
@@ -475,7 +361,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     const uint32_t n_paths = (uint32_t)n_paths64;
     int rc = ensure_path_state(c, n_paths);
     if (rc) return rc;
-    const int stack_depth = c->bvh.max_depth <= 31 ? 31 : 63;
+    const int stack_depth = c->hs.bvh.max_depth <= 31 ? 31 : 63;
     if ((rc = ensure_spill(c))) return rc;
     // k_shade shades one analytic-only segment in place per call (never stored, never re-read: shade -24 % on C3) when
     // the scene has a BVH and few analytic primitives; with many of them (RANDOM_BALLS presets) compacting between
@@ -590,8 +476,8 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                         tune.perm = q + 3 * (size_t)n_paths;
                     }
                 }
-                prt_launch_traverse(c->stream, c->dsc, in, front_count, c->d_work, c->d_spill, n_paths, c->bvh.max_depth,
-                                    c->bvh.max_stack4, tune, trav_stats, (compact && d == 0) ? &primary : nullptr);
+                prt_launch_traverse(c->stream, c->dsc, in, front_count, c->d_work, c->d_spill, n_paths, c->hs.bvh.max_depth,
+                                    c->hs.bvh.max_stack4, tune, trav_stats, (compact && d == 0) ? &primary : nullptr);
             }
             else
                 prt_launch_intersect(c->stream, c->dsc, in, front_count, n_paths, stack_depth, c->variant, trav_stats);
@@ -631,8 +517,8 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                     if (c->variant == 0 || c->dsc.n_insts || !c->dsc.nodes) {
                         PrtTravTuning tune = c->tune;
                         tune.perm = nullptr;
-                        prt_launch_occluded(c->stream, c->dsc, c->lb.sh, scount, c->d_work, c->d_spill, nmax, c->bvh.max_depth,
-                                            c->bvh.max_stack4, tune);
+                        prt_launch_occluded(c->stream, c->dsc, c->lb.sh, scount, c->d_work, c->d_spill, nmax, c->hs.bvh.max_depth,
+                                            c->hs.bvh.max_stack4, tune);
                     } else {
                         prt_launch_intersect(c->stream, c->dsc, c->lb.sh, scount, nmax, stack_depth, c->variant, nullptr);
                     }
@@ -661,6 +547,38 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     return PRT_OK;
 }
 
+// The one place that fills c->dsc: the compiled scene's scalars next to the context's device pointers (all null on a
+// host-only context, which has no node stride and no tree depth for the launchers either).
+void fill_dev_scene(PrtContext* c, uint32_t node_stride, uint32_t depth8) {
+    const PrtSceneScalars& k = c->hs.sc;
+    DevScene d{};
+    d.prims = (const DevPrim*)c->d_prims;
+    d.mat_rgbs = (const float4*)c->d_mat_rgbs;
+    d.mat_type = (const uint32_t*)c->d_mat_type;
+    d.nodes = (const float4*)c->d_nodes;
+    d.nodes4 = (const float4*)c->d_nodes4;
+    d.nodes8 = (const uint4*)c->d_nodes8;  // null when the tree has no compressed 8-wide form: the 4-wide kernel runs
+    d.tris = (const float4*)c->d_tris;
+    d.tri_normals = (const float4*)c->d_nrms;
+    d.abvh_nodes = (const float4*)c->d_abvh_nodes;
+    d.abvh_order = (const uint32_t*)c->d_abvh_order;
+    d.insts = (const DevInstance*)c->d_insts;
+    d.tlas_inst = (const uint32_t*)c->d_tlas_inst;
+    d.n_insts = k.n_insts;
+    d.node_stride = node_stride;
+    d.depth8 = depth8;
+    d.n_prims = k.n_prims;
+    d.n_nodes = k.n_nodes;
+    d.n_tris = k.n_tris;
+    d.pad = k.pad;
+    memcpy(d.abvh_q, k.abvh_q, sizeof(d.abvh_q));
+    d.extent = k.extent;
+    memcpy(d.root_min, k.root_min, sizeof(d.root_min));
+    memcpy(d.root_max, k.root_max, sizeof(d.root_max));
+    memcpy(d.sky, k.sky, sizeof(d.sky));
+    c->dsc = d;
+}
+
 // Second half of prt_set_scene / prt_clone_scene: the context's host copies -> its device.  `gb` (device-side build):
 // the builder's arrays on this device become the scene's arrays; otherwise trees and triangle records are uploaded from
 // the host copies (a scene built on ANOTHER device arrives that way too: its 8-wide tree and records were read back).
@@ -677,10 +595,10 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
     // misses the caches moves 1.5 lines = 192 B (tools/gather_calib.hip).  Trees far beyond the L2s (C5: 1.6 M nodes =
     // 131 MB, HBM-bound traversal) get one node per 128-B line instead: every miss is one line, at 1.6x the array size;
     // trees the caches hold (C3: 16 MB) stay packed, where the smaller footprint is worth more than the line count.
-    const std::vector<uint32_t>& n8 = c->nodes8_all.empty() ? c->bvh.nodes8 : c->nodes8_all;
+    const std::vector<uint32_t>& n8 = c->hs.nodes8_all.empty() ? c->hs.bvh.nodes8 : c->hs.nodes8_all;
     const size_t n_nodes8 = gb ? (size_t)gb->n_nodes : n8.size() / 20;
-    c->dsc.node_stride = c->node_stride ? (uint32_t)c->node_stride : (n_nodes8 * 80 > ((size_t)64 << 20) ? 8u : 5u);
-    if (c->dsc.node_stride == 8u && n_nodes8) {
+    const uint32_t node_stride = c->node_stride ? (uint32_t)c->node_stride : (n_nodes8 * 80 > ((size_t)64 << 20) ? 8u : 5u);
+    if (node_stride == 8u && n_nodes8) {
         void* wide = nullptr;
         HIPCHECK(c, hipMalloc(&wide, 128 * n_nodes8));
         hipError_t e = hipMemset(wide, 0, 128 * n_nodes8);
@@ -701,51 +619,38 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
         if (bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
         return e;
     };
-    std::vector<float> rgbs(4 * c->materials.size());
-    std::vector<uint32_t> mtype(c->materials.size());
-    for (size_t i = 0; i < c->materials.size(); ++i) {
-        rgbs[4 * i + 0] = c->materials[i].rgb[0];
-        rgbs[4 * i + 1] = c->materials[i].rgb[1];
-        rgbs[4 * i + 2] = c->materials[i].rgb[2];
-        rgbs[4 * i + 3] = c->materials[i].scalar;
-        mtype[i] = c->materials[i].type;
+    std::vector<float> rgbs(4 * c->hs.materials.size());
+    std::vector<uint32_t> mtype(c->hs.materials.size());
+    for (size_t i = 0; i < c->hs.materials.size(); ++i) {
+        rgbs[4 * i + 0] = c->hs.materials[i].rgb[0];
+        rgbs[4 * i + 1] = c->hs.materials[i].rgb[1];
+        rgbs[4 * i + 2] = c->hs.materials[i].rgb[2];
+        rgbs[4 * i + 3] = c->hs.materials[i].scalar;
+        mtype[i] = c->hs.materials[i].type;
     }
-    HIPCHECK(c, upload(&c->d_prims, c->prims.data(), c->prims.size() * sizeof(DevPrim)));
+    HIPCHECK(c, upload(&c->d_prims, c->hs.prims.data(), c->hs.prims.size() * sizeof(DevPrim)));
     HIPCHECK(c, upload(&c->d_mat_rgbs, rgbs.data(), rgbs.size() * 4));
     HIPCHECK(c, upload(&c->d_mat_type, mtype.data(), mtype.size() * 4));
-    if (!c->scene_device_built) {  // (device-built scenes have no binary / 4-wide tree: null pointers select the 8-wide kernel)
-        HIPCHECK(c, upload(&c->d_nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * 4));
-        HIPCHECK(c, upload(&c->d_nodes4, c->bvh.nodes4.data(), c->bvh.nodes4.size() * 4));
+    if (!c->hs.scene_device_built) {  // (device-built scenes have no binary / 4-wide tree: null pointers select the 8-wide kernel)
+        HIPCHECK(c, upload(&c->d_nodes, c->hs.bvh.nodes.data(), c->hs.bvh.nodes.size() * 4));
+        HIPCHECK(c, upload(&c->d_nodes4, c->hs.bvh.nodes4.data(), c->hs.bvh.nodes4.size() * 4));
     }
-    if (!gb && !n8.empty() && c->dsc.node_stride != 8u) HIPCHECK(c, upload(&c->d_nodes8, n8.data(), n8.size() * 4));
-    if (!c->abvh.nodes4.empty()) {
-        HIPCHECK(c, upload(&c->d_abvh_nodes, c->abvh.nodes4.data(), c->abvh.nodes4.size() * 4));
-        HIPCHECK(c, upload(&c->d_abvh_order, c->abvh.order.data(), c->abvh.order.size() * 4));
+    if (!gb && !n8.empty() && node_stride != 8u) HIPCHECK(c, upload(&c->d_nodes8, n8.data(), n8.size() * 4));
+    if (!c->hs.abvh.nodes4.empty()) {
+        HIPCHECK(c, upload(&c->d_abvh_nodes, c->hs.abvh.nodes4.data(), c->hs.abvh.nodes4.size() * 4));
+        HIPCHECK(c, upload(&c->d_abvh_order, c->hs.abvh.order.data(), c->hs.abvh.order.size() * 4));
     }
-    if (!c->dev_insts.empty()) {
-        HIPCHECK(c, upload(&c->d_insts, c->dev_insts.data(), c->dev_insts.size() * sizeof(DevInstance)));
-        HIPCHECK(c, upload(&c->d_tlas_inst, c->tlas_inst.data(), c->tlas_inst.size() * 4));
+    if (!c->hs.dev_insts.empty()) {
+        HIPCHECK(c, upload(&c->d_insts, c->hs.dev_insts.data(), c->hs.dev_insts.size() * sizeof(DevInstance)));
+        HIPCHECK(c, upload(&c->d_tlas_inst, c->hs.tlas_inst.data(), c->hs.tlas_inst.size() * 4));
     }
-    HIPCHECK(c, upload(&c->d_lights, c->lights.data(), c->lights.size() * 4));
-    HIPCHECK(c, upload(&c->d_prim_light, c->prim_light.data(), c->prim_light.size() * 4));
+    HIPCHECK(c, upload(&c->d_lights, c->hs.lights.data(), c->hs.lights.size() * 4));
+    HIPCHECK(c, upload(&c->d_prim_light, c->hs.prim_light.data(), c->hs.prim_light.size() * 4));
     if (!gb) {
-        HIPCHECK(c, upload(&c->d_tris, c->tri_records.data(), c->tri_records.size() * 4));
-        HIPCHECK(c, upload(&c->d_nrms, c->nrm_records.data(), c->nrm_records.size() * 4));
+        HIPCHECK(c, upload(&c->d_tris, c->hs.tri_records.data(), c->hs.tri_records.size() * 4));
+        HIPCHECK(c, upload(&c->d_nrms, c->hs.nrm_records.data(), c->hs.nrm_records.size() * 4));
     }
-    DevScene& d = c->dsc;
-    d.prims = (const DevPrim*)c->d_prims;
-    d.mat_rgbs = (const float4*)c->d_mat_rgbs;
-    d.mat_type = (const uint32_t*)c->d_mat_type;
-    d.nodes = (const float4*)c->d_nodes;
-    d.nodes4 = (const float4*)c->d_nodes4;
-    d.abvh_nodes = (const float4*)c->d_abvh_nodes;
-    d.abvh_order = (const uint32_t*)c->d_abvh_order;
-    d.depth8 = c->bvh_info.depth8;
-    d.insts = (const DevInstance*)c->d_insts;
-    d.tlas_inst = (const uint32_t*)c->d_tlas_inst;
-    d.nodes8 = (const uint4*)c->d_nodes8;  // null when the tree has no compressed 8-wide form: the 4-wide kernel runs
-    d.tris = (const float4*)c->d_tris;
-    d.tri_normals = (const float4*)c->d_nrms;
+    fill_dev_scene(c, node_stride, c->hs.bvh_info.depth8);
     const int rc_cnt = ensure_counters(c);
     if (rc_cnt) return rc_cnt;
     c->has_scene = true;
@@ -754,10 +659,10 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
 
 // Device-side build (csrc/bvh_gpu.hip) of the 8-wide tree over n triangles given as 9 floats each (+ normals, + a material
 // per triangle): nodes and the triangle / normal records in the tree's slot order come back to the host copies the
-// rest of prt_set_scene works with; with `keep` the device arrays stay allocated and are handed to the caller.
-constexpr int kDeviceBuildGaveUp = -1000;  // internal: not a PRT_ERR_* code
+// scene compiler works with (prt_scene.h PrtDeviceBuilder); with `keep` the device arrays stay allocated and are handed
+// to the caller.  The builder's time is added to *ms.
 int device_build(PrtContext* c, const float* verts, const float* norms, const uint32_t* tri_mat, uint32_t n, uint32_t n_prims,
-                 std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, PrtGpuBvh* keep, float leaf_cost = 0.0f) {
+                 std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, PrtGpuBvh* keep, float leaf_cost, double* ms) {
     float cmin[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, cmax[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (size_t t = 0; t < (size_t)n; ++t)
         for (int a = 0; a < 3; ++a) {
@@ -792,11 +697,11 @@ int device_build(PrtContext* c, const float* verts, const float* norms, const ui
     const int brc = c->gpu_build == 2
                         ? prt_gpu_bvh8_build(c->stream, (const float*)dv, (const float*)dn, (const uint32_t*)dm, n, n_prims, cmin, cmax, &gb)
                         : prt_gpu_bvh8_build_ploc(c->stream, (const float*)dv, (const float*)dn, (const uint32_t*)dm, n, n_prims, cmin, cmax, &gb, leaf_cost);
-    c->gpu_build_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     drop();
     if (brc < 0) {  // the builder itself gave up (too many passes / levels for this input): the caller may take the host builder
         (void)fail(c, PRT_ERR_INVALID, "device-side BVH build gave up (%d)", brc);
-        return kDeviceBuildGaveUp;
+        return kPrtDeviceBuildGaveUp;
     }
     if (brc) return fail(c, PRT_ERR_HIP, "device-side BVH build failed (%d)", brc);
     nodes8.resize(20 * (size_t)gb.n_nodes);
@@ -908,441 +813,40 @@ int prt_get_device(const PrtContext* c) { return c ? c->device : -1; }
 
 int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     if (!c || !s) return PRT_ERR_INVALID;
-    if ((s->n_materials && !s->materials) || (s->n_primitives && !s->primitives) || (s->n_meshes && !s->meshes) ||
-        (s->n_instanced_meshes && !s->instanced_meshes) || (s->n_instances && !s->instances))
-        return fail(c, PRT_ERR_INVALID, "null array in scene description");
-    // From here on the context's host copies and c->dsc are rewritten in place: a scene the context held before is gone
-    // whatever happens, so every failure below leaves the context WITHOUT a scene (the next render fails with
-    // PRT_ERR_INVALID instead of walking half-built arrays); has_scene is set again only after the last upload.
+    int rc = prt_check_scene_arrays(s, &c->err);
+    if (rc) return rc;
+    // A scene the context held before is gone whatever happens: a failure below leaves the context WITHOUT a scene (the
+    // next render fails with PRT_ERR_INVALID); has_scene is set again only after the last upload.
     c->has_scene = false;
-    // ---- validate + flatten (host) ----
-    c->materials.assign(s->materials, s->materials + s->n_materials);
-    c->prims.clear();
-    for (uint32_t i = 0; i < s->n_primitives; ++i) {
-        const PrtPrimitive& p = s->primitives[i];
-        if (p.shape_type != PRT_SHAPE_CIRCLE && p.shape_type != PRT_SHAPE_QUAD)
-            return fail(c, PRT_ERR_INVALID, "primitive %u: analytic shapes are CIRCLE or QUAD (triangles come as meshes)", i);
-        if (p.material_id >= s->n_materials) return fail(c, PRT_ERR_INVALID, "primitive %u: material out of range", i);
-        DevPrim d;
-        d.shape_type = p.shape_type;
-        d.p0 = p.shape_param[0];
-        d.p1 = p.shape_param[1];
-        d.material = p.material_id;
-        to_dev_mat(p.mat, d.mat);
-        to_dev_mat(p.inv, d.inv);
-        c->prims.push_back(d);
-    }
-    build_light_table(c, s);
-    uint64_t n_tris = 0;
-    for (uint32_t m = 0; m < s->n_meshes; ++m) {
-        const PrtMesh& me = s->meshes[m];
-        if (me.n_triangles && (!me.positions || !me.normals || !me.indices))
-            return fail(c, PRT_ERR_INVALID, "mesh %u: positions, normals and indices are required", m);
-        if (me.material_id >= s->n_materials) return fail(c, PRT_ERR_INVALID, "mesh %u: material out of range", m);
-        n_tris += me.n_triangles;
-    }
-    if (n_tris >= (1ull << 26)) return fail(c, PRT_ERR_INVALID, "too many triangles (limit 2^26 - 1)");
-    std::vector<float> verts(9 * (size_t)n_tris);
-    std::vector<float> norms(9 * (size_t)n_tris);
-    std::vector<uint32_t> tri_mat((size_t)n_tris);
-    float extent = 0.0f;
-    {
-        size_t t = 0;
-        for (uint32_t m = 0; m < s->n_meshes; ++m) {
-            const PrtMesh& me = s->meshes[m];
-            for (uint32_t k = 0; k < me.n_triangles; ++k, ++t) {
-                for (int v = 0; v < 3; ++v) {
-                    const uint32_t vi = me.indices[3 * (size_t)k + v];
-                    if (vi >= me.n_vertices) return fail(c, PRT_ERR_INVALID, "mesh %u: vertex index out of range", m);
-                    for (int a = 0; a < 3; ++a) {
-                        const float pv = me.positions[3 * (size_t)vi + a];
-                        if (!std::isfinite(pv)) return fail(c, PRT_ERR_INVALID, "mesh %u: non-finite vertex", m);
-                        verts[9 * t + 3 * v + a] = pv;
-                        norms[9 * t + 3 * v + a] = me.normals[3 * (size_t)vi + a];
-                        extent = std::max(extent, std::fabs(pv));
-                    }
-                }
-                tri_mat[t] = me.material_id;
-            }
-        }
-    }
-    c->mesh_sizes.clear();
-    for (uint32_t m = 0; m < s->n_meshes; ++m) {
-        c->mesh_sizes.push_back(s->meshes[m].n_vertices);
-        c->mesh_sizes.push_back(s->meshes[m].n_triangles);
-    }
-    const uint32_t n_prims = (uint32_t)c->prims.size();
-    // device-side build (prt_set_param("gpu_build", 1)): Morton-ordered 8-wide tree straight on the GPU (bvh_gpu.hip);
-    // only for world-space meshes on a context with a device; anything else takes the host builder below
-    const bool gpu_any = c->gpu_build && c->has_device;  // placed copies and the top-level tree take the device builder too
-    bool gpu_build = gpu_any && n_tris > 0;
+    PrtHostScene hs = std::move(c->hs);  // (the compiler recycles the record arrays' storage; everything else goes)
+    c->hs = PrtHostScene();
+    PrtSceneOptions opt{c->pad_coeff, c->abvh_enabled != 0, nullptr};
+    // device-side build (prt_set_param("gpu_build", 1 | 2)) on a context with a device: world meshes, placed copies and the
+    // top-level tree.  The world meshes' device arrays (`keep`) stay with this layer: they become the scene's arrays below,
+    // or go if the compiler did not take that tree after all (deeper than the kernels' stacks: the host builder's stands)
     PrtGpuBvh gb{};
-    c->gpu_build_ms = 0.0;
-    const auto t_build0 = std::chrono::steady_clock::now();
-    if (gpu_build) {
-        // host copies for the read-back entry points (prt_bvh_read / prt_bvh_read8) and for scenes whose node array is put
-        // together on the host (placed copies); the binary and 4-wide trees of the A/B kernels are not built in this mode
-        c->bvh = BvhBuild();
-        c->bvh.max_leaf = 3;
-        c->tri_records.assign(12 * (size_t)n_tris, 0.0f);
-        c->nrm_records.assign(12 * (size_t)n_tris, 0.0f);
-        const int brc = device_build(c, verts.data(), norms.data(), tri_mat.data(), (uint32_t)n_tris, n_prims, c->bvh.nodes8, c->bvh.depth8,
-                                     c->tri_records.data(), c->nrm_records.data(), s->n_instances == 0 ? &gb : nullptr);
-        if (brc && brc != kDeviceBuildGaveUp) return brc;
-        if (!brc && c->bvh.depth8 > 15u) {
-            (void)hipFree(gb.d_nodes8);
-            (void)hipFree(gb.d_tris);
-            (void)hipFree(gb.d_nrms);
-        }
-        // A valid mesh is never refused because the DEVICE builder could not cope with it (a tree deeper than the kernels'
-        // stacks, or more clustering passes than its guard allows: degenerate inputs such as thousands of coincident
-        // triangles): the host builder, with its forced median splits, takes over.
-        if (brc == kDeviceBuildGaveUp || c->bvh.depth8 > 15u) {
-            gb = PrtGpuBvh{};
-            gpu_build = false;
-            c->bvh = BvhBuild();
-        }
-    }
-    if (!gpu_build && !bvh_build(verts.data(), (uint32_t)n_tris, kMaxLeaf, 0, kMaxStack, &c->bvh)) {
-        return fail(c, PRT_ERR_INVALID, "BVH deeper than the traversal stack (%u > %u)", c->bvh.max_depth, kMaxStack);
-    }
-    const double build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
-    if (!gpu_build) {
-        c->tri_records.assign(12 * (size_t)n_tris, 0.0f);
-        c->nrm_records.assign(12 * (size_t)n_tris, 0.0f);
-    }
-    for (size_t slot = 0; !gpu_build && slot < (size_t)n_tris; ++slot) {
-        const uint32_t t = c->bvh.order[slot];
-        float* r = &c->tri_records[12 * slot];
-        float* q = &c->nrm_records[12 * slot];
-        for (int v = 0; v < 3; ++v)
-            for (int a = 0; a < 3; ++a) {
-                r[4 * v + a] = verts[9 * (size_t)t + 3 * v + a];
-                q[4 * v + a] = norms[9 * (size_t)t + 3 * v + a];
-            }
-        const uint32_t prim = n_prims + t;  // global primitive index: analytic first, then triangles in input order
-        memcpy(&r[3], &prim, 4);
-        memcpy(&r[7], &tri_mat[t], 4);
-    }
-    PrtBvhInfo& bi = c->bvh_info;
-    bi.n_nodes = (uint32_t)(c->bvh.nodes.size() / 16);
-    bi.n_triangles = (uint32_t)n_tris;
-    bi.max_depth = c->bvh.max_depth;
-    bi.max_leaf_size = c->bvh.max_leaf;
-    bi.sah_cost = c->bvh.sah_cost;
-    bi.pad_abs = c->pad_coeff;
-    bi.node_bytes = (uint64_t)c->bvh.nodes4.size() * 4;
-    bi.n_nodes4 = (uint32_t)(c->bvh.nodes4.size() / 32);
-    bi.max_stack4 = c->bvh.max_stack4;
-    bi.n_nodes8 = (uint32_t)(c->bvh.nodes8.size() / 20);
-    bi.depth8 = c->bvh.depth8;
-    bi.build_ms = (float)(gpu_build ? c->gpu_build_ms : build_ms);
-    bi.built_on_device = (gpu_build || (gpu_any && s->n_instances)) ? 1u : 0u;
-    bi.refit_ms = 0.0f;
-    bi.refits = 0u;
-    bi.tri_bytes = (uint64_t)c->tri_records.size() * 4;
-
-    DevScene& d = c->dsc;
-    memset(&d, 0, sizeof(d));
-    d.n_prims = n_prims;
-    d.n_nodes = gpu_build ? (uint32_t)(c->bvh.nodes8.size() / 20) : bi.n_nodes;  // "the scene has a BVH" for the producers' classification
-    d.n_tris = (uint32_t)n_tris;
-    d.pad = c->pad_coeff;
-    d.extent = extent;
-    memcpy(d.sky, s->sky, sizeof(d.sky));
-    for (int k = 0; k < 3; ++k) {
-        d.root_min[k] = FLT_MAX;
-        d.root_max[k] = -FLT_MAX;
-    }
-    for (size_t t = 0; t < (size_t)n_tris * 9; ++t) {
-        d.root_min[t % 3] = std::min(d.root_min[t % 3], verts[t]);
-        d.root_max[t % 3] = std::max(d.root_max[t % 3], verts[t]);
-    }
-    // ---- BVH over the analytic primitives (only when there are many: the reference scans all of them for every ray,
-    // primitive.cpp:26; its default scene RANDOM_BALLS_LARGE has 809).  World boxes are only valid bounds of the
-    // reference's hits when the primitive's transform is rotation + uniform scale + translation; one primitive that is
-    // not keeps the linear scan for the whole scene. ----
-    c->abvh = BvhBuild();
-    float extent_prims = 0.0f;
-    double quad_pad[3] = {0.0, 0.0, 0.0};
-    if (c->abvh_enabled && n_prims > 16u) {
-        std::vector<float> pv(9 * (size_t)n_prims);
-        bool ok = true;
-        for (uint32_t i = 0; i < n_prims && ok; ++i) {
-            const PrtPrimitive& p = s->primitives[i];
-            const float* M = p.mat;
-            double g[3][3];
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b)
-                    g[a][b] = (double)M[4 * a] * M[4 * b] + (double)M[4 * a + 1] * M[4 * b + 1] + (double)M[4 * a + 2] * M[4 * b + 2];
-            const double s2 = g[0][0];
-            ok = s2 > 1e-20 && std::isfinite(s2) && M[3] == 0.0f && M[7] == 0.0f && M[11] == 0.0f && M[15] == 1.0f;
-            for (int a = 0; a < 3 && ok; ++a)
-                for (int b = 0; b < 3; ++b)
-                    if (std::fabs(g[a][b] - (a == b ? s2 : 0.0)) > 1e-4 * s2) ok = false;
-            if (!ok) break;
-            float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-            if (p.shape_type == PRT_SHAPE_CIRCLE) {  // sphere of radius r around the local origin
-                const double R = std::fabs((double)p.shape_param[0]) * std::sqrt(s2);
-                for (int a = 0; a < 3; ++a) {
-                    mn[a] = (float)((double)M[12 + a] - R);
-                    mx[a] = (float)((double)M[12 + a] + R);
-                }
-                // phantom hits of the fp32 discriminant: up to K * dist^2 / R outside the sphere, dist <= |o|_1 + |c|_1
-                // (K = 1e-6: measured worst 2.0e-7 over 3.6e7 grazing rays at 3..1000 units, analytic bound 4.8e-7)
-                if (R > 0.0) {
-                    const double q = 1e-6 / R, c1 = std::fabs((double)M[12]) + std::fabs((double)M[13]) + std::fabs((double)M[14]);
-                    quad_pad[0] = std::max(quad_pad[0], q);
-                    quad_pad[1] = std::max(quad_pad[1], 2.0 * q * c1);
-                    quad_pad[2] = std::max(quad_pad[2], q * c1 * c1);
-                }
-            } else {  // quad in the local plane y = 0
-                for (int corner = 0; corner < 4; ++corner) {
-                    const float lx = ((corner & 1) ? 0.5f : -0.5f) * p.shape_param[0], lz = ((corner & 2) ? 0.5f : -0.5f) * p.shape_param[1];
-                    for (int a = 0; a < 3; ++a) {
-                        const float wv = (M[a] * lx + M[4 + a] * 0.0f) + (M[8 + a] * lz + M[12 + a]);
-                        mn[a] = std::min(mn[a], wv);
-                        mx[a] = std::max(mx[a], wv);
-                    }
-                }
-            }
-            float mag = 0.0f;
-            for (int a = 0; a < 3; ++a) mag = std::max(mag, std::max(std::fabs(mn[a]), std::fabs(mx[a])));
-            const float slack = 1e-5f * (mag + (float)std::sqrt(s2) * (std::fabs(p.shape_param[0]) + std::fabs(p.shape_param[1]))) + 1e-30f;
-            for (int a = 0; a < 3; ++a) {
-                mn[a] -= slack;
-                mx[a] += slack;
-                if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) ok = false;
-                extent_prims = std::max(extent_prims, std::max(std::fabs(mn[a]), std::fabs(mx[a])));
-            }
-            const float tri[9] = {mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], mn[0], mx[1], mn[2]};  // spans the box
-            memcpy(&pv[9 * (size_t)i], tri, sizeof(tri));
-        }
-        if (ok && (!bvh_build(pv.data(), n_prims, kMaxLeaf, 1, kMaxStack, &c->abvh) || c->abvh.nodes4.empty()))  // (a walk that would need more than ABVH_STACK entries falls back to the scan)
-            ok = false;
-        if (!ok) c->abvh = BvhBuild();
-    }
-    if (!c->abvh.nodes4.empty()) {
-        extent = std::max(extent, extent_prims);  // the culling pad of the primitive walk scales with the scene
-        d.extent = extent;
-        for (int k = 0; k < 3; ++k) d.abvh_q[k] = (float)(quad_pad[k] * 1.0000002);  // (rounded up)
-    }
-
-    // ---- placed mesh copies (PrtInstance): one tree per instanced mesh in its own space + a top-level tree over the
-    // copies' world boxes; the world-space meshes above become one identity instance ----
-    c->nodes8_all.clear();
-    c->dev_insts.clear();
-    c->tlas_inst.clear();
-    if (s->n_instances) {
-        const uint32_t n_world = (uint32_t)n_tris;
-        if (n_world && c->bvh.nodes8.empty()) return fail(c, PRT_ERR_INVALID, "instances need the 8-wide tree (leaves <= 3 triangles)");
-        struct Blas {
-            BvhBuild bvh;
-            uint32_t slot_base = 0, node_base = 0, n_tris = 0;
-            float mn[3], mx[3], extent = 0.0f;
+    if (c->gpu_build && c->has_device)
+        opt.device_build = [&](const float* verts, const float* norms, const uint32_t* tri_mat, uint32_t n, uint32_t n_prims, float leaf_cost,
+                               bool keep, std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, double* ms, std::string* err) {
+            const int brc = device_build(c, verts, norms, tri_mat, n, n_prims, nodes8, depth, tri_rec, nrm_rec, keep ? &gb : nullptr, leaf_cost, ms);
+            if (brc) *err = c->err;
+            return brc;
         };
-        std::vector<Blas> blas(s->n_instanced_meshes);
-        uint64_t slots = n_world;
-        for (uint32_t m = 0; m < s->n_instanced_meshes; ++m) {
-            const PrtMesh& me = s->instanced_meshes[m];
-            if (!me.n_triangles || !me.positions || !me.normals || !me.indices)
-                return fail(c, PRT_ERR_INVALID, "instanced mesh %u: positions, normals and indices are required", m);
-            Blas& B = blas[m];
-            B.n_tris = me.n_triangles;
-            std::vector<float> v(9 * (size_t)me.n_triangles), nn(9 * (size_t)me.n_triangles);
-            for (int a = 0; a < 3; ++a) {
-                B.mn[a] = FLT_MAX;
-                B.mx[a] = -FLT_MAX;
-            }
-            for (uint32_t k = 0; k < me.n_triangles; ++k)
-                for (int vv = 0; vv < 3; ++vv) {
-                    const uint32_t vi = me.indices[3 * (size_t)k + vv];
-                    if (vi >= me.n_vertices) return fail(c, PRT_ERR_INVALID, "instanced mesh %u: vertex index out of range", m);
-                    for (int a = 0; a < 3; ++a) {
-                        const float pv = me.positions[3 * (size_t)vi + a];
-                        if (!std::isfinite(pv)) return fail(c, PRT_ERR_INVALID, "instanced mesh %u: non-finite vertex", m);
-                        v[9 * (size_t)k + 3 * vv + a] = pv;
-                        nn[9 * (size_t)k + 3 * vv + a] = me.normals[3 * (size_t)vi + a];
-                        B.mn[a] = std::min(B.mn[a], pv);
-                        B.mx[a] = std::max(B.mx[a], pv);
-                        B.extent = std::max(B.extent, std::fabs(pv));
-                    }
-                }
-            B.slot_base = (uint32_t)slots;
-            slots += me.n_triangles;
-            if (slots >= (1ull << 26)) return fail(c, PRT_ERR_INVALID, "too many triangles (limit 2^26 - 1)");
-            // triangle / normal records in this mesh's leaf order: {P0, face index}, {P1, -}, {P2, -}
-            c->tri_records.resize(12 * (size_t)slots, 0.0f);
-            c->nrm_records.resize(12 * (size_t)slots, 0.0f);
-            if (gpu_any) {  // the mesh's tree in its own space on the device; the records come back in its slot order
-                const int brc = device_build(c, v.data(), nn.data(), nullptr, me.n_triangles, 0u, B.bvh.nodes8, B.bvh.depth8,
-                                             &c->tri_records[12 * (size_t)B.slot_base], &c->nrm_records[12 * (size_t)B.slot_base], nullptr);
-                if (brc && brc != kDeviceBuildGaveUp) return brc;
-                if (!brc) continue;
-                B.bvh = BvhBuild();  // the device builder gave up on this mesh: the host builder takes it
-            }
-            if (!bvh_build(v.data(), me.n_triangles, kMaxLeaf, 0, kMaxStack, &B.bvh) || B.bvh.nodes8.empty())
-                return fail(c, PRT_ERR_INVALID, "instanced mesh %u: BVH construction failed", m);
-            for (uint32_t sl = 0; sl < me.n_triangles; ++sl) {
-                const uint32_t t = B.bvh.order[sl];
-                float* r = &c->tri_records[12 * ((size_t)B.slot_base + sl)];
-                float* q = &c->nrm_records[12 * ((size_t)B.slot_base + sl)];
-                for (int vv = 0; vv < 3; ++vv)
-                    for (int a = 0; a < 3; ++a) {
-                        r[4 * vv + a] = v[9 * (size_t)t + 3 * vv + a];
-                        q[4 * vv + a] = nn[9 * (size_t)t + 3 * vv + a];
-                    }
-                memcpy(&r[3], &t, 4);
-            }
-        }
-        // the instance table: [identity instance of the world-space meshes] + the placed copies
-        auto identity12 = [](float* m12) {
-            for (int k = 0; k < 12; ++k) m12[k] = 0.0f;
-            m12[0] = m12[4] = m12[8] = 1.0f;
-        };
-        std::vector<std::array<float, 6>> boxes;
-        if (n_world) {
-            DevInstance I{};
-            identity12(I.mat);
-            identity12(I.inv);
-            I.root = 0;  // fixed up below
-            I.slot_base = 0;
-            I.prim_base = 0;  // the world triangles' records carry their full primitive index
-            I.virt_base = 0;
-            I.material = 0xFFFFFFFFu;  // per triangle record
-            I.n_tris = n_world;
-            I.inv_scale = 1.0f;
-            I.extent = extent;
-            c->dev_insts.push_back(I);
-            boxes.push_back({d.root_min[0], d.root_min[1], d.root_min[2], d.root_max[0], d.root_max[1], d.root_max[2]});
-        }
-        uint32_t virt = n_world, prim = n_prims + n_world;
-        for (uint32_t i = 0; i < s->n_instances; ++i) {
-            const PrtInstance& pi = s->instances[i];
-            if (pi.mesh >= s->n_instanced_meshes) return fail(c, PRT_ERR_INVALID, "instance %u: mesh out of range", i);
-            if (pi.material_id >= s->n_materials) return fail(c, PRT_ERR_INVALID, "instance %u: material out of range", i);
-            // rotation + uniform scale + translation only: transpose(M3) * M3 = s^2 * I, and inv * mat = I
-            const float* M = pi.mat;
-            double s2 = 0.0;
-            if (!is_similarity(pi.mat, pi.inv, &s2))
-                return fail(c, PRT_ERR_INVALID,
-                            "instance %u: the transform must be rotation + uniform scale + translation with inv = inverse(mat) "
-                            "(the reference's local ray, primitive.cpp:29-30, is only a ray transform for those)", i);
-            const Blas& B = blas[pi.mesh];
-            DevInstance I{};
-            to_dev_mat(pi.mat, I.mat);
-            to_dev_mat(pi.inv, I.inv);
-            I.slot_base = B.slot_base;
-            I.prim_base = prim;
-            I.virt_base = virt;
-            I.material = pi.material_id;
-            I.n_tris = B.n_tris;
-            I.inv_scale = (float)(1.0 / std::sqrt(s2));
-            I.extent = B.extent;
-            I.root = pi.mesh;  // mesh index for now; node base below
-            c->dev_insts.push_back(I);
-            virt += B.n_tris;
-            prim += B.n_tris;
-            // world box: the 8 corners of the mesh box through Mat, widened by a relative slack for the fp32 rounding
-            // of Mat * p anywhere inside the box
-            std::array<float, 6> bx{FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
-            float mag = 0.0f;
-            for (int corner = 0; corner < 8; ++corner) {
-                const float p3[3] = {(corner & 1) ? B.mx[0] : B.mn[0], (corner & 2) ? B.mx[1] : B.mn[1], (corner & 4) ? B.mx[2] : B.mn[2]};
-                for (int a = 0; a < 3; ++a) {
-                    const float wv = (M[a] * p3[0] + M[4 + a] * p3[1]) + (M[8 + a] * p3[2] + M[12 + a]);
-                    bx[a] = std::min(bx[a], wv);
-                    bx[3 + a] = std::max(bx[3 + a], wv);
-                    mag = std::max(mag, std::fabs(wv));
-                }
-            }
-            for (int a = 0; a < 3; ++a) {
-                bx[a] -= 1e-5f * (mag + 1e-30f);
-                bx[3 + a] += 1e-5f * (mag + 1e-30f);
-            }
-            boxes.push_back(bx);
-        }
-        if ((uint64_t)virt + n_prims >= 0xFFFFFFF0ull) return fail(c, PRT_ERR_INVALID, "too many placed triangles");
-        // top-level tree: the same builder over one degenerate "triangle" per instance that spans its world box
-        const uint32_t n_inst_total = (uint32_t)c->dev_insts.size();
-        std::vector<float> pv(9 * (size_t)n_inst_total);
-        for (uint32_t i = 0; i < n_inst_total; ++i) {
-            const std::array<float, 6>& bx = boxes[i];
-            const float tri[9] = {bx[0], bx[1], bx[2], bx[3], bx[4], bx[5], bx[0], bx[4], bx[2]};
-            memcpy(&pv[9 * (size_t)i], tri, sizeof(tri));
-        }
-        BvhBuild top;
-        if (gpu_any) {  // the same device builder over the copies' boxes; a record's primitive index is the instance it stands for
-            std::vector<float> rec(12 * (size_t)n_inst_total);
-            // (an instance in a hit leaf is ENTERED, a level switch of ~150 instructions, without a box test of its own:
-            // a leaf cost this high makes the optimisation put every instance into a leaf of its own wherever the boxes
-            // differ; copies whose boxes coincide may still share a leaf, which costs a redundant entry, never a result)
-            const int brc = device_build(c, pv.data(), nullptr, nullptr, n_inst_total, 0u, top.nodes8, top.depth8, rec.data(), nullptr, nullptr, 64.0f);
-            if (brc == kDeviceBuildGaveUp) return fail(c, PRT_ERR_INVALID, "top-level tree: the device builder gave up; use gpu_build = 0 for this scene");
-            if (brc) return brc;
-            top.order.resize(n_inst_total);
-            for (uint32_t sl = 0; sl < n_inst_total; ++sl) memcpy(&top.order[sl], &rec[12 * (size_t)sl + 3], 4);
-        } else if (!bvh_build(pv.data(), n_inst_total, kMaxLeaf, 1, kMaxStack, &top) || top.nodes8.empty()) {
-            return fail(c, PRT_ERR_INVALID, "top-level BVH construction failed");
-        }
-        c->tlas_inst = top.order;
-        // one node array: [top level][world meshes' tree][instanced meshes' trees]; child_base / tri_base made absolute
-        c->nodes8_all = top.nodes8;
-        uint32_t max_blas_depth = 0;
-        auto append = [&](const std::vector<uint32_t>& n8, uint32_t slot_base) -> uint32_t {
-            const uint32_t node_base = (uint32_t)(c->nodes8_all.size() / 20);
-            const size_t at = c->nodes8_all.size();
-            c->nodes8_all.insert(c->nodes8_all.end(), n8.begin(), n8.end());
-            for (size_t k = at; k < c->nodes8_all.size(); k += 20) {
-                c->nodes8_all[k + 4] += node_base;
-                c->nodes8_all[k + 5] += slot_base;
-            }
-            return node_base;
-        };
-        uint32_t world_root = 0;
-        if (n_world) {
-            world_root = append(c->bvh.nodes8, 0);
-            max_blas_depth = c->bvh.depth8;
-        }
-        for (Blas& B : blas) {
-            B.node_base = append(B.bvh.nodes8, B.slot_base);
-            max_blas_depth = std::max(max_blas_depth, B.bvh.depth8);
-        }
-        for (size_t i = 0; i < c->dev_insts.size(); ++i) {
-            DevInstance& I = c->dev_insts[i];
-            I.root = (n_world && i == 0) ? world_root : blas[I.root].node_base;
-        }
-        if (top.depth8 + max_blas_depth > 12u)
-            return fail(c, PRT_ERR_INVALID, "two-level BVH too deep for the traversal stack (%u + %u > 12)", top.depth8, max_blas_depth);
-        // scene-wide quantities the producers use
-        for (int a = 0; a < 3; ++a) {
-            d.root_min[a] = FLT_MAX;
-            d.root_max[a] = -FLT_MAX;
-        }
-        for (const std::array<float, 6>& bx : boxes)
-            for (int a = 0; a < 3; ++a) {
-                d.root_min[a] = std::min(d.root_min[a], bx[a]);
-                d.root_max[a] = std::max(d.root_max[a], bx[3 + a]);
-                extent = std::max(extent, std::max(std::fabs(bx[a]), std::fabs(bx[3 + a])));
-            }
-        d.extent = extent;
-        d.n_insts = n_inst_total;
-        d.n_nodes = std::max(d.n_nodes, 1u);  // "the scene has a BVH"
-        d.n_tris = (uint32_t)slots;
-        bi.n_nodes8 = (uint32_t)(c->nodes8_all.size() / 20);
-        bi.depth8 = top.depth8 + max_blas_depth;
-        bi.n_triangles = (uint32_t)slots;
-        bi.tri_bytes = (uint64_t)c->tri_records.size() * 4;
-        // world meshes + every placed mesh + the top level: device time, or the host builders' wall time
-        bi.build_ms = gpu_any ? (float)c->gpu_build_ms
-                              : (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
+    rc = prt_compile_scene(s, opt, &hs, &c->err);
+    const bool use_gb = !rc && gb.d_nodes8 && hs.scene_device_built;
+    if (!use_gb) {
+        free_dev(gb.d_nodes8);
+        free_dev(gb.d_tris);
+        free_dev(gb.d_nrms);
     }
-    c->scene_device_built = gpu_build || (gpu_any && s->n_instances != 0u);
+    if (rc) return rc;
+    c->hs = std::move(hs);
     if (!c->has_device) {  // host-only context: BVH built, nothing to upload
+        fill_dev_scene(c, 0u, 0u);
         c->has_scene = true;
         return PRT_OK;
     }
-    return upload_scene(c, (gpu_build && s->n_instances == 0) ? &gb : nullptr);
+    return upload_scene(c, use_gb ? &gb : nullptr);
 }
 
 // Replicates the scene of `src` (host copies of the flattened primitives, trees and triangle records) onto the device
@@ -1352,24 +856,9 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     if (!src->has_scene) return fail(dst, PRT_ERR_INVALID, "prt_clone_scene: the source context has no scene");
     if (dst == src) return PRT_OK;
     dst->has_scene = false;
-    dst->materials = src->materials;
-    dst->prims = src->prims;
-    dst->bvh = src->bvh;
-    dst->tri_records = src->tri_records;
-    dst->nrm_records = src->nrm_records;
-    dst->gpu_build_ms = src->gpu_build_ms;
-    dst->nodes8_all = src->nodes8_all;
-    dst->dev_insts = src->dev_insts;
-    dst->tlas_inst = src->tlas_inst;
-    dst->abvh = src->abvh;
-    dst->bvh_info = src->bvh_info;
-    dst->dsc = src->dsc;  // scalar fields; every device pointer is replaced by upload_scene
-    dst->scene_device_built = src->scene_device_built;
-    dst->mesh_sizes = src->mesh_sizes;
-    dst->lights = src->lights;
-    dst->prim_light = src->prim_light;
-    dst->n_emitters_unsampled = src->n_emitters_unsampled;
+    dst->hs = src->hs;
     if (!dst->has_device) {
+        fill_dev_scene(dst, 0u, 0u);
         dst->has_scene = true;
         return PRT_OK;
     }
@@ -1385,12 +874,12 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     if (!meshes && n_meshes) return fail(c, PRT_ERR_INVALID, "null mesh array");
     if (c->dsc.n_insts) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: scenes with placed copies are rebuilt, not refitted");
-    if (!c->dsc.nodes8 || c->bvh.nodes8.empty()) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes needs the compressed 8-wide tree");
-    if (2 * (size_t)n_meshes != c->mesh_sizes.size()) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: the scene has %zu meshes", c->mesh_sizes.size() / 2);
+    if (!c->dsc.nodes8 || c->hs.bvh.nodes8.empty()) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes needs the compressed 8-wide tree");
+    if (2 * (size_t)n_meshes != c->hs.mesh_sizes.size()) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: the scene has %zu meshes", c->hs.mesh_sizes.size() / 2);
     uint64_t n_tris = 0;
     for (uint32_t m = 0; m < n_meshes; ++m) {
         const PrtMesh& me = meshes[m];
-        if (me.n_vertices != c->mesh_sizes[2 * m] || me.n_triangles != c->mesh_sizes[2 * m + 1])
+        if (me.n_vertices != c->hs.mesh_sizes[2 * m] || me.n_triangles != c->hs.mesh_sizes[2 * m + 1])
             return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: mesh %u has another topology than at prt_set_scene", m);
         if (me.n_triangles && (!me.positions || !me.normals || !me.indices)) return fail(c, PRT_ERR_INVALID, "mesh %u: positions, normals and indices are required", m);
         n_tris += me.n_triangles;
@@ -1398,27 +887,11 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     if (n_tris != c->dsc.n_tris || n_tris == 0) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: triangle count mismatch");
     std::vector<float> verts(9 * (size_t)n_tris), norms(9 * (size_t)n_tris);
     float extent = 0.0f;
-    {
-        size_t t = 0;
-        for (uint32_t m = 0; m < n_meshes; ++m) {
-            const PrtMesh& me = meshes[m];
-            for (uint32_t k = 0; k < me.n_triangles; ++k, ++t)
-                for (int v = 0; v < 3; ++v) {
-                    const uint32_t vi = me.indices[3 * (size_t)k + v];
-                    if (vi >= me.n_vertices) return fail(c, PRT_ERR_INVALID, "mesh %u: vertex index out of range", m);
-                    for (int a = 0; a < 3; ++a) {
-                        const float pv = me.positions[3 * (size_t)vi + a];
-                        if (!std::isfinite(pv)) return fail(c, PRT_ERR_INVALID, "mesh %u: non-finite vertex", m);
-                        verts[9 * t + 3 * v + a] = pv;
-                        norms[9 * t + 3 * v + a] = me.normals[3 * (size_t)vi + a];
-                        extent = std::max(extent, std::fabs(pv));
-                    }
-                }
-        }
-    }
+    for (size_t m = 0, t = 0; m < n_meshes; t += meshes[m++].n_triangles)
+        if ((rc = prt_flatten_mesh(meshes[m], "mesh", (uint32_t)m, verts.data() + 9 * t, norms.data() + 9 * t, &extent, nullptr, nullptr, &c->err))) return rc;
     // the nodes of every tree level, from the host copy of the tree (breadth-first search from the root: the builders emit
     // their nodes in different orders, none of which the refit relies on)
-    const std::vector<uint32_t>& n8 = c->bvh.nodes8;
+    const std::vector<uint32_t>& n8 = c->hs.bvh.nodes8;
     const uint32_t n_nodes = (uint32_t)(n8.size() / 20);
     std::vector<uint32_t> level_nodes{0u}, level_start{0u, 1u};
     level_nodes.reserve(n_nodes);
@@ -1458,9 +931,9 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
         return fail(c, PRT_ERR_HIP, "prt_refit_meshes: %s (%d)", e != hipSuccess ? hipGetErrorString(e) : "refit failed", brc);
     }
     // host copies (prt_bvh_read8 / prt_bvh_read, prt_clone_scene) follow the device
-    e = hipMemcpy2D(c->bvh.nodes8.data(), 80, c->d_nodes8, (size_t)c->dsc.node_stride * 16, 80, n_nodes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && c->tri_records.size() == 12 * (size_t)n_tris) e = hipMemcpy(c->tri_records.data(), c->d_tris, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && c->nrm_records.size() == 12 * (size_t)n_tris) e = hipMemcpy(c->nrm_records.data(), c->d_nrms, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
+    e = hipMemcpy2D(c->hs.bvh.nodes8.data(), 80, c->d_nodes8, (size_t)c->dsc.node_stride * 16, 80, n_nodes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && c->hs.tri_records.size() == 12 * (size_t)n_tris) e = hipMemcpy(c->hs.tri_records.data(), c->d_tris, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && c->hs.nrm_records.size() == 12 * (size_t)n_tris) e = hipMemcpy(c->hs.nrm_records.data(), c->d_nrms, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
     HIPCHECK(c, e);
     // the binary and 4-wide trees (A/B kernels, overflow fallback of deep host-built trees) still describe the OLD
     // geometry: they go, and the instance selection falls to the 8-wide kernels that need neither (prt_launch_traverse)
@@ -1468,23 +941,24 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     free_dev(c->d_nodes4);
     c->dsc.nodes = nullptr;
     c->dsc.nodes4 = nullptr;
-    c->bvh.nodes.clear();
-    c->bvh.nodes4.clear();
-    c->scene_device_built = true;
+    c->hs.bvh.nodes.clear();
+    c->hs.bvh.nodes4.clear();
+    c->hs.scene_device_built = true;
     c->variant = 0;
+    PrtSceneScalars& k = c->hs.sc;  // (a clone of this scene starts from the refitted bounds too)
     for (int a = 0; a < 3; ++a) {
-        c->dsc.root_min[a] = root_box[a];
-        c->dsc.root_max[a] = root_box[3 + a];
+        c->dsc.root_min[a] = k.root_min[a] = root_box[a];
+        c->dsc.root_max[a] = k.root_max[a] = root_box[3 + a];
     }
     float ext_all = extent;
-    if (!c->abvh.nodes4.empty()) ext_all = std::max(ext_all, c->dsc.extent);  // (the primitive walk's pad scales with the larger of the two)
-    c->dsc.extent = ext_all;
-    c->bvh_info.refit_ms = (float)c->refit_ms;
-    ++c->bvh_info.refits;
-    c->bvh_info.n_nodes = 0;      // (the binary and 4-wide trees are gone)
-    c->bvh_info.n_nodes4 = 0;
-    c->bvh_info.node_bytes = 0;
-    c->bvh_info.max_stack4 = 0;
+    if (!c->hs.abvh.nodes4.empty()) ext_all = std::max(ext_all, k.extent);  // (the primitive walk's pad scales with the larger of the two)
+    c->dsc.extent = k.extent = ext_all;
+    c->hs.bvh_info.refit_ms = (float)c->refit_ms;
+    ++c->hs.bvh_info.refits;
+    c->hs.bvh_info.n_nodes = 0;      // (the binary and 4-wide trees are gone)
+    c->hs.bvh_info.n_nodes4 = 0;
+    c->hs.bvh_info.node_bytes = 0;
+    c->hs.bvh_info.max_stack4 = 0;
     return PRT_OK;
 }
 
@@ -1573,10 +1047,10 @@ int prt_set_lighting(PrtContext* c, const PrtLighting* l) {
 int prt_light_info(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint32_t* prim, float* pmf) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
-    const uint32_t n = (uint32_t)(c->lights.size() / (4 * PRT_LIGHT_F4));
+    const uint32_t n = (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4));
     if (n_lights) *n_lights = n;
     for (uint32_t l = 0; l < n && l < capacity; ++l) {
-        const float* r = &c->lights[4 * PRT_LIGHT_F4 * l];
+        const float* r = &c->hs.lights[4 * PRT_LIGHT_F4 * l];
         if (prim) memcpy(&prim[l], &r[19], 4);
         if (pmf) pmf[l] = r[7];
     }
@@ -1586,8 +1060,8 @@ int prt_light_info(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint32_
 int prt_get_light_stats(PrtContext* c, PrtLightStats* out) {
     if (!c || !out) return PRT_ERR_INVALID;
     memset(out, 0, sizeof(*out));
-    out->n_lights = (uint32_t)(c->lights.size() / (4 * PRT_LIGHT_F4));
-    out->n_emitters_unsampled = c->n_emitters_unsampled;
+    out->n_lights = (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4));
+    out->n_emitters_unsampled = c->hs.n_emitters_unsampled;
     if (!c->has_device || !c->d_light_stats) return PRT_OK;
     int rc = need_device(c);
     if (rc) return rc;
@@ -1762,7 +1236,7 @@ static int enqueue_query(PrtContext* c, uint32_t n, const float* d_o, const floa
     if ((rc = ensure_counters(c))) return rc;
     if ((rc = ensure_spill(c))) return rc;
     uint32_t* cnt = c->d_counts + (size_t)(PRT_MAX_DEPTH + 1) * PRT_CNT_STRIDE;  // a counter slot the render loop never uses
-    const int stack_depth = c->bvh.max_depth <= 31 ? 31 : 63;
+    const int stack_depth = c->hs.bvh.max_depth <= 31 ? 31 : 63;
     const bool walk8 = c->variant == 0 || c->dsc.n_insts || !c->dsc.nodes;
     if (d_tmax) {
         // occlusion: every ray seeded with "miss at d2 = tmax^2", the analytic scan from that bound, the any-hit walk
@@ -1771,8 +1245,8 @@ static int enqueue_query(PrtContext* c, uint32_t n, const float* d_o, const floa
         prt_launch_scan_prims_bounded(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n);
         if (c->dsc.n_nodes) {
             if (walk8)
-                prt_launch_occluded(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->bvh.max_depth,
-                                    c->bvh.max_stack4, c->tune);
+                prt_launch_occluded(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->hs.bvh.max_depth,
+                                    c->hs.bvh.max_stack4, c->tune);
             else
                 prt_launch_intersect(c->stream, c->dsc, c->rb[0], cnt, n, stack_depth, c->variant, nullptr);
         }
@@ -1782,8 +1256,8 @@ static int enqueue_query(PrtContext* c, uint32_t n, const float* d_o, const floa
         prt_launch_scan_prims(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n, nullptr);
         if (c->dsc.n_nodes) {
             if (walk8)
-                prt_launch_traverse(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->bvh.max_depth,
-                                    c->bvh.max_stack4, c->tune, nullptr);
+                prt_launch_traverse(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->hs.bvh.max_depth,
+                                    c->hs.bvh.max_stack4, c->tune, nullptr);
             else
                 prt_launch_intersect(c->stream, c->dsc, c->rb[0], cnt, n, stack_depth, c->variant, nullptr);
         }
@@ -1866,7 +1340,7 @@ int prt_scatter(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* h
     if (!in_dirs || !hits || !rng_state || !scattered || !attenuation || !emitted || !out_origins || !out_dirs)
         return fail(c, PRT_ERR_INVALID, "null array");
     for (uint32_t i = 0; i < n; ++i)
-        if (hits[i].material_id >= c->materials.size()) return fail(c, PRT_ERR_INVALID, "hit %u: material out of range", i);
+        if (hits[i].material_id >= c->hs.materials.size()) return fail(c, PRT_ERR_INVALID, "hit %u: material out of range", i);
     const size_t b3 = (size_t)n * 12, b1 = (size_t)n * 4, bh = (size_t)n * sizeof(PrtHit);
     if ((rc = ensure_scratch(c, 5 * b3 + 2 * b1 + bh + 64))) return rc;
     char* base = (char*)c->d_scratch;
@@ -1909,7 +1383,7 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
     if (!in_dirs || !hits || !keys || !shadow_dirs || !tmax || !light || !contrib || !pdf_light || !pdf_bsdf || !w_light || !w_bsdf)
         return fail(c, PRT_ERR_INVALID, "null array");
     for (uint32_t i = 0; i < n; ++i)
-        if (hits[i].prim >= 0 && hits[i].material_id >= c->materials.size())
+        if (hits[i].prim >= 0 && hits[i].material_id >= c->hs.materials.size())
             return fail(c, PRT_ERR_INVALID, "hit %u: material out of range", i);
     const size_t b3 = (size_t)n * 12, b1 = (size_t)n * 4, bh = (size_t)n * sizeof(PrtHit), bf = (size_t)n * 44;
     if ((rc = ensure_scratch(c, bh + b3 + 2 * b1 + bf + 64))) return rc;
@@ -2040,7 +1514,7 @@ int prt_measure_traversal(PrtContext* c, uint32_t max_depth, uint32_t seed, uint
     out->samples = (uint64_t)std::max(1, c->measure_spp);
     out->bvh_node_visits = t[0];
     out->bvh_tri_tests = t[1];
-    out->prim_tests = (uint64_t)c->prims.size() * out->rays_total;  // every ray scans every analytic primitive
+    out->prim_tests = (uint64_t)c->hs.prims.size() * out->rays_total;  // every ray scans every analytic primitive
     out->node_lane_slots = t[3];
     out->tri_lane_slots = t[4];
     out->max_stack_used = t[5];
@@ -2110,21 +1584,21 @@ int prt_kernel_instance(PrtContext* c, char* name, uint32_t capacity) {
 int prt_bvh_info(PrtContext* c, PrtBvhInfo* out) {
     if (!c || !out) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
-    *out = c->bvh_info;
+    *out = c->hs.bvh_info;
     return PRT_OK;
 }
 
 int prt_bvh_read4(PrtContext* c, float* nodes4) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
-    if (nodes4) memcpy(nodes4, c->bvh.nodes4.data(), c->bvh.nodes4.size() * 4);
+    if (nodes4) memcpy(nodes4, c->hs.bvh.nodes4.data(), c->hs.bvh.nodes4.size() * 4);
     return PRT_OK;
 }
 
 int prt_bvh_read8(PrtContext* c, uint32_t* nodes8) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
-    const std::vector<uint32_t>& n8 = c->nodes8_all.empty() ? c->bvh.nodes8 : c->nodes8_all;
+    const std::vector<uint32_t>& n8 = c->hs.nodes8_all.empty() ? c->hs.bvh.nodes8 : c->hs.nodes8_all;
     if (nodes8) memcpy(nodes8, n8.data(), n8.size() * 4);
     return PRT_OK;
 }
@@ -2132,8 +1606,8 @@ int prt_bvh_read8(PrtContext* c, uint32_t* nodes8) {
 int prt_bvh_read(PrtContext* c, float* nodes, float* tris) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
-    if (nodes) memcpy(nodes, c->bvh.nodes.data(), c->bvh.nodes.size() * 4);
-    if (tris) memcpy(tris, c->tri_records.data(), c->tri_records.size() * 4);
+    if (nodes) memcpy(nodes, c->hs.bvh.nodes.data(), c->hs.bvh.nodes.size() * 4);
+    if (tris) memcpy(tris, c->hs.tri_records.data(), c->hs.tri_records.size() * 4);
     return PRT_OK;
 }
 

@@ -6,35 +6,15 @@
 #include <stdint.h>
 
 #include "../../include/prt.h"
+#include "prt_scene_pod.h"  // DevPrim, DevInstance
 
 struct f3 {
     float x, y, z;
 };
 
-struct DevPrim {  // 28 dwords; mat/inv keep rows 0..2 of glm's column-major mat4 (cols 0..3)
-    uint32_t shape_type;
-    float p0, p1;
-    uint32_t material;
-    float mat[12];  // mat[c*3 + r]
-    float inv[12];
-};
-
 struct DevCamera {  // the Camera members GetCameraRay reads (reference: src/core/camera.h:134-141)
     f3 pos, front, right, up;
     float W, H, tan_fov_y;
-};
-
-// One placed mesh copy (PrtInstance) as the kernels see it: 128 B.  mat / inv: rows 0..2 of the column-major mat4
-// (like DevPrim).  root: its mesh's root in nodes8; slot_base: first triangle slot of its mesh in tris / tri_normals;
-// prim_base: global primitive index of its first triangle (tie-break order); virt_base: first hit id of this copy
-// minus n_prims (hit id = n_prims + virt_base + slot - slot_base).
-struct DevInstance {
-    float mat[12];
-    float inv[12];
-    uint32_t root, slot_base, prim_base, virt_base;
-    uint32_t material, n_tris;
-    float inv_scale;  // 1 / uniform scale of mat
-    float extent;     // max |coordinate| of the mesh in its own space (culling pad)
 };
 
 struct DevScene {
@@ -61,7 +41,7 @@ struct DevScene {
     float pad;     // culling pad coefficient (2^-18): pad_ray = pad * (|o|_1 + extent)
     // primitive walk only: + (abvh_q[0] * A + abvh_q[1]) * A + abvh_q[2] with A = |o|_1, an upper envelope of
     // K / R_i * (A + |c_i|_1)^2 over the scene's spheres (world radius R_i, centre c_i): how far OUTSIDE a sphere a ray may
-    // pass and still be a hit in the reference's fp32 arithmetic (see prt_set_scene)
+    // pass and still be a hit in the reference's fp32 arithmetic (see build_prim_bvh in prt_scene.cpp)
     float abvh_q[3];
     float extent;  // max |coordinate| of any mesh vertex
     float root_min[3], root_max[3];  // bounds of all triangles (BVH root box)
@@ -151,12 +131,11 @@ struct PrtPathArgs {
 
 #define PRT_CNT_STRIDE 64u  // uint32 per bounce in the counter array: [0] front, [32] back, [16] finished-in-producer counts, [48] shadow rays (lighting modes)
 
-// Light table (PrtLighting, include/prt.h), read-only, 5 x float4 per light:
+// Light table (PrtLighting, include/prt.h), read-only, PRT_LIGHT_F4 = 5 (prt_scene_pod.h) x float4 per light:
 //   [0] centre.xyz, R (sphere) | area w h s^2 (quad)   [1] edge u = w * column 0 of Mat, pmf   [2] edge v = h * column 2, cdf
 //   [3] unit normal of the quad plane, kind (0 sphere, 1 quad; bits)   [4] emission rgb, primitive index (bits)
 // prim_light[p]: light index of analytic primitive p, 0xFFFFFFFF if it is not in the light set.  Passed only to the
 // lighting kernels (DevScene stays as it is: the lighting-off instances keep their code).
-#define PRT_LIGHT_F4 5u
 struct DevLights {
     const float4* lights;
     const uint32_t* prim_light;

@@ -1,0 +1,641 @@
+// prt_scene.cpp — the scene compiler (prt_scene.h): validates a PrtSceneDesc and turns it into the host arrays the kernels
+// walk.  No HIP in here; the device-side tree builder arrives as a callable (PrtSceneOptions::device_build).
+#include "prt_scene.h"
+
+#include <algorithm>
+#include <array>
+#include <cfloat>
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <utility>
+
+namespace {
+
+constexpr uint32_t kMaxLeaf = 3;  // the compressed 8-wide node encodes at most 3 triangles per leaf (bvh.h)
+constexpr uint32_t kMaxStack = 63;  // LDS stack entries per lane: 31 (5 blocks/CU) or 63 (2 blocks/CU)
+constexpr int kHostBuildFailed = -1001;  // build_tree: the host builder refused (the caller words the message)
+
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
+int fail(std::string* err, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    *err = buf;
+    return PRT_ERR_INVALID;
+}
+
+void to_dev_mat(const float* m16, float* m12) {
+    for (int col = 0; col < 4; ++col)
+        for (int r = 0; r < 3; ++r) m12[col * 3 + r] = m16[col * 4 + r];
+}
+
+// g = transpose(M3) * M3 of a column-major mat4's upper 3x3, in double; true if it is s^2 * I (s^2 = g[0][0] = *s2_out)
+bool gram_is_uniform_scale(const float* M, double* s2_out) {
+    double g[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            g[a][b] = (double)M[4 * a] * M[4 * b] + (double)M[4 * a + 1] * M[4 * b + 1] + (double)M[4 * a + 2] * M[4 * b + 2];
+    const double s2 = g[0][0];
+    bool ok = s2 > 1e-20 && std::isfinite(s2);
+    for (int a = 0; a < 3 && ok; ++a)
+        for (int b = 0; b < 3; ++b)
+            if (std::fabs(g[a][b] - (a == b ? s2 : 0.0)) > 1e-4 * s2) ok = false;
+    *s2_out = s2;
+    return ok;
+}
+
+bool affine_bottom_row(const float* M) { return M[3] == 0.0f && M[7] == 0.0f && M[11] == 0.0f && M[15] == 1.0f; }
+
+// Rotation + uniform scale + translation with inv = inverse(mat) (column-major mat4s): transpose(M3) * M3 = s^2 * I, bottom row
+// (0, 0, 0, 1), inv * mat = I.  Only for such transforms is the reference's local ray (primitive.cpp:29-30) a ray transform.
+// *s2_out = s^2.
+bool is_similarity(const float* M, const float* inv, double* s2_out) {
+    bool ok = gram_is_uniform_scale(M, s2_out);
+    for (int r = 0; r < 4 && ok; ++r)
+        for (int cc = 0; cc < 4; ++cc) {
+            double acc = 0.0;
+            for (int kk = 0; kk < 4; ++kk) acc += (double)inv[4 * kk + r] * (double)M[4 * cc + kk];
+            if (std::fabs(acc - (r == cc ? 1.0 : 0.0)) > 1e-3) ok = false;
+        }
+    return ok && affine_bottom_row(M);
+}
+
+// The light set of a scene (include/prt.h PrtLighting): emissive analytic primitives with positive mean emission and a
+// rotation + uniform scale + translation transform with inv = inverse(mat) (the test compile_instances applies to placed
+// copies: only then is the surface the reference intersects, primitive.cpp:29-30, the one sampled here).  pmf ~ emitting
+// area x mean(rgb), computed in double.  Every other emissive primitive (mesh and placed triangles, other transforms)
+// counts in n_emitters_unsampled.
+void build_light_table(PrtHostScene* c, const PrtSceneDesc* s) {
+    c->lights.clear();
+    c->prim_light.assign(s->n_primitives, 0xFFFFFFFFu);
+    c->n_emitters_unsampled = 0;
+    auto emissive = [&](uint32_t m) { return m < s->n_materials && s->materials[m].type == PRT_MAT_EMISSIVE; };
+    std::vector<double> power;
+    for (uint32_t i = 0; i < s->n_primitives; ++i) {
+        const PrtPrimitive& p = s->primitives[i];
+        if (!emissive(p.material_id)) continue;
+        const float* M = p.mat;
+        double s2 = 0.0;
+        if (!is_similarity(p.mat, p.inv, &s2)) {
+            ++c->n_emitters_unsampled;
+            continue;
+        }
+        const float* rgb = s->materials[p.material_id].rgb;
+        const double mean = ((double)rgb[0] + (double)rgb[1] + (double)rgb[2]) / 3.0;
+        const bool quad = p.shape_type == PRT_SHAPE_QUAD;
+        const double w = p.shape_param[0], h = p.shape_param[1];
+        const double area = quad ? std::fabs(w * h) * s2 : 4.0 * M_PI * w * w * s2;
+        const double pw = (quad ? 2.0 * area : area) * mean;  // a quad emits from both faces
+        if (!(pw > 0.0) || !std::isfinite(pw)) continue;      // emits nothing: not a light, nothing unsampled either
+        float rec[4 * PRT_LIGHT_F4] = {};
+        rec[0] = M[12];
+        rec[1] = M[13];
+        rec[2] = M[14];
+        rec[3] = quad ? (float)area : (float)(std::fabs(w) * std::sqrt(s2));
+        const double nx = (double)M[1] * M[10] - (double)M[2] * M[9], ny = (double)M[2] * M[8] - (double)M[0] * M[10],
+                     nz = (double)M[0] * M[9] - (double)M[1] * M[8];
+        const double nl = std::sqrt(nx * nx + ny * ny + nz * nz);
+        for (int a = 0; a < 3; ++a) {
+            rec[4 + a] = quad ? (float)(w * M[a]) : 0.0f;
+            rec[8 + a] = quad ? (float)(h * M[8 + a]) : 0.0f;
+        }
+        if (quad) {
+            rec[12] = (float)(nx / nl);
+            rec[13] = (float)(ny / nl);
+            rec[14] = (float)(nz / nl);
+        }
+        const uint32_t kind = quad ? 1u : 0u;
+        memcpy(&rec[15], &kind, 4);
+        rec[16] = rgb[0];
+        rec[17] = rgb[1];
+        rec[18] = rgb[2];
+        memcpy(&rec[19], &i, 4);
+        c->prim_light[i] = (uint32_t)power.size();
+        power.push_back(pw);
+        c->lights.insert(c->lights.end(), rec, rec + 4 * PRT_LIGHT_F4);
+    }
+    double total = 0.0;
+    for (double pw : power) total += pw;
+    double acc = 0.0;
+    for (size_t l = 0; l < power.size(); ++l) {
+        acc += power[l];
+        c->lights[4 * PRT_LIGHT_F4 * l + 7] = (float)(power[l] / total);                                 // pmf
+        c->lights[4 * PRT_LIGHT_F4 * l + 11] = l + 1 == power.size() ? 1.0f : (float)(acc / total);  // cdf
+    }
+    for (uint32_t m = 0; m < s->n_meshes; ++m)
+        if (emissive(s->meshes[m].material_id)) c->n_emitters_unsampled += s->meshes[m].n_triangles;
+    for (uint32_t i = 0; i < s->n_instances; ++i) {
+        const PrtInstance& pi = s->instances[i];
+        if (emissive(pi.material_id) && pi.mesh < s->n_instanced_meshes) c->n_emitters_unsampled += s->instanced_meshes[pi.mesh].n_triangles;
+    }
+}
+
+// Triangle / normal records of n triangles in leaf order: {P0, prim_base + input index}, {P1, material}, {P2, -}.  norms /
+// nrm_rec and tri_mat may be null (no normal records; word 7 stays as it is).
+void pack_records(const std::vector<uint32_t>& order, const float* verts, const float* norms, uint32_t n, uint32_t prim_base,
+                  const uint32_t* tri_mat, float* tri_rec, float* nrm_rec) {
+    for (size_t slot = 0; slot < (size_t)n; ++slot) {
+        const uint32_t t = order[slot];
+        float* r = &tri_rec[12 * slot];
+        for (int v = 0; v < 3; ++v)
+            for (int a = 0; a < 3; ++a) {
+                r[4 * v + a] = verts[9 * (size_t)t + 3 * v + a];
+                if (nrm_rec) nrm_rec[12 * slot + 4 * v + a] = norms[9 * (size_t)t + 3 * v + a];
+            }
+        const uint32_t prim = prim_base + t;
+        memcpy(&r[3], &prim, 4);
+        if (tri_mat) memcpy(&r[7], &tri_mat[t], 4);
+    }
+}
+
+// A box as the builders take it: one degenerate "triangle" that spans it
+void box_triangle(const float* mn, const float* mx, float* tri) {
+    const float t9[9] = {mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], mn[0], mx[1], mn[2]};
+    memcpy(tri, t9, sizeof(t9));
+}
+
+// What build_tree builds a tree over: n triangles as 9 floats each (+ normals, + a material per triangle, both may be null)
+struct TreeInput {
+    const float* verts;
+    const float* norms;
+    const uint32_t* tri_mat;
+    uint32_t n, n_prims;
+};
+
+// One tree: the device builder first where there is one (opt.device_build; records come back in tri_rec / nrm_rec and
+// *on_device is set), else the host builder (the caller packs the records from out->order).  A valid mesh is never
+// refused because the DEVICE builder could not cope with it (a tree deeper than device_depth_limit allows, or more
+// clustering passes than its guard allows: degenerate inputs such as thousands of coincident triangles): the host
+// builder, with its forced median splits, takes over.  The one exception, host_fallback = false (the top-level tree):
+// kPrtDeviceBuildGaveUp goes back to the caller.  Returns PRT_OK, kHostBuildFailed, or the device builder's error.
+int build_tree(const PrtSceneOptions& opt, const TreeInput& in, float leaf_cost, bool keep, uint32_t device_depth_limit, bool host_fallback,
+               int host_threads, BvhBuild* out, float* tri_rec, float* nrm_rec, bool* on_device, double* gpu_ms, std::string* err) {
+    *on_device = false;
+    if (opt.device_build && in.n > 0) {
+        // host copies for the read-back entry points (prt_bvh_read / prt_bvh_read8) and for scenes whose node array is put
+        // together on the host (placed copies); the binary and 4-wide trees of the A/B kernels are not built in this mode
+        *out = BvhBuild();
+        out->max_leaf = 3;
+        const int brc = opt.device_build(in.verts, in.norms, in.tri_mat, in.n, in.n_prims, leaf_cost, keep, out->nodes8, out->depth8, tri_rec,
+                                         nrm_rec, gpu_ms, err);
+        if (brc && brc != kPrtDeviceBuildGaveUp) return brc;
+        if (!brc && out->depth8 <= device_depth_limit) {
+            *on_device = true;
+            return PRT_OK;
+        }
+        if (!host_fallback) return kPrtDeviceBuildGaveUp;
+        *out = BvhBuild();
+        std::fill_n(tri_rec, 12 * (size_t)in.n, 0.0f);  // (a tree that came back too deep came back with its records)
+        if (nrm_rec) std::fill_n(nrm_rec, 12 * (size_t)in.n, 0.0f);
+    }
+    return bvh_build(in.verts, in.n, kMaxLeaf, host_threads, kMaxStack, out) ? PRT_OK : kHostBuildFailed;
+}
+
+// What the steps of prt_compile_scene hand on to each other
+struct Work {
+    std::vector<float> verts, norms;  // the world-space meshes, 9 floats per triangle
+    std::vector<uint32_t> tri_mat;
+    uint32_t n_world = 0;             // their triangles
+    bool world_on_device = false;     // their tree came from the device builder
+    Clock::time_point t_build0;
+    double host_build_ms = 0.0;       // wall time of the tree builds (reported when the host built them)
+    uint32_t depth8 = 0;              // levels of the 8-wide tree (two-level scenes: top level + deepest mesh tree)
+};
+
+int compile_prims(const PrtSceneDesc* s, PrtHostScene& hs, std::string* err) {
+    hs.materials.assign(s->materials, s->materials + s->n_materials);
+    for (uint32_t i = 0; i < s->n_primitives; ++i) {
+        const PrtPrimitive& p = s->primitives[i];
+        if (p.shape_type != PRT_SHAPE_CIRCLE && p.shape_type != PRT_SHAPE_QUAD)
+            return fail(err, "primitive %u: analytic shapes are CIRCLE or QUAD (triangles come as meshes)", i);
+        if (p.material_id >= s->n_materials) return fail(err, "primitive %u: material out of range", i);
+        DevPrim d;
+        d.shape_type = p.shape_type;
+        d.p0 = p.shape_param[0];
+        d.p1 = p.shape_param[1];
+        d.material = p.material_id;
+        to_dev_mat(p.mat, d.mat);
+        to_dev_mat(p.inv, d.inv);
+        hs.prims.push_back(d);
+    }
+    return PRT_OK;
+}
+
+// The world-space meshes: validated, flattened, one tree over all of them, records in its leaf order; the scene-wide
+// scalars as far as they are known here
+int compile_world_meshes(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene& hs, Work& w, std::string* err) {
+    uint64_t n_tris = 0;
+    for (uint32_t m = 0; m < s->n_meshes; ++m) {
+        const PrtMesh& me = s->meshes[m];
+        if (me.n_triangles && (!me.positions || !me.normals || !me.indices))
+            return fail(err, "mesh %u: positions, normals and indices are required", m);
+        if (me.material_id >= s->n_materials) return fail(err, "mesh %u: material out of range", m);
+        n_tris += me.n_triangles;
+    }
+    if (n_tris >= (1ull << 26)) return fail(err, "too many triangles (limit 2^26 - 1)");
+    w.n_world = (uint32_t)n_tris;
+    w.verts.resize(9 * (size_t)n_tris);
+    w.norms.resize(9 * (size_t)n_tris);
+    w.tri_mat.resize((size_t)n_tris);
+    PrtSceneScalars& d = hs.sc;
+    for (int k = 0; k < 3; ++k) {
+        d.root_min[k] = FLT_MAX;
+        d.root_max[k] = -FLT_MAX;
+    }
+    size_t t = 0;
+    for (uint32_t m = 0; m < s->n_meshes; ++m) {
+        const PrtMesh& me = s->meshes[m];
+        const int rc = prt_flatten_mesh(me, "mesh", m, w.verts.data() + 9 * t, w.norms.data() + 9 * t, &d.extent, d.root_min, d.root_max, err);
+        if (rc) return rc;
+        std::fill_n(w.tri_mat.begin() + (ptrdiff_t)t, me.n_triangles, me.material_id);
+        t += me.n_triangles;
+        hs.mesh_sizes.push_back(me.n_vertices);
+        hs.mesh_sizes.push_back(me.n_triangles);
+    }
+    const uint32_t n_prims = (uint32_t)hs.prims.size();
+    hs.tri_records.assign(12 * (size_t)n_tris, 0.0f);
+    hs.nrm_records.assign(12 * (size_t)n_tris, 0.0f);
+    w.t_build0 = Clock::now();
+    // (only a scene without placed copies walks the device builder's arrays as they are: `keep`)
+    const int rc = build_tree(opt, TreeInput{w.verts.data(), w.norms.data(), w.tri_mat.data(), w.n_world, n_prims}, 0.0f, s->n_instances == 0, 15u,
+                              true, 0, &hs.bvh, hs.tri_records.data(), hs.nrm_records.data(), &w.world_on_device, &hs.gpu_build_ms, err);
+    if (rc == kHostBuildFailed) return fail(err, "BVH deeper than the traversal stack (%u > %u)", hs.bvh.max_depth, kMaxStack);
+    if (rc) return rc;
+    w.host_build_ms = ms_since(w.t_build0);
+    w.depth8 = hs.bvh.depth8;
+    // global primitive index: analytic first, then triangles in input order
+    if (!w.world_on_device)
+        pack_records(hs.bvh.order, w.verts.data(), w.norms.data(), w.n_world, n_prims, w.tri_mat.data(), hs.tri_records.data(), hs.nrm_records.data());
+    d.n_prims = n_prims;
+    // "the scene has a BVH" for the producers' classification
+    d.n_nodes = w.world_on_device ? (uint32_t)(hs.bvh.nodes8.size() / 20) : (uint32_t)(hs.bvh.nodes.size() / 16);
+    d.n_tris = w.n_world;
+    d.pad = opt.pad_coeff;
+    memcpy(d.sky, s->sky, sizeof(d.sky));
+    return PRT_OK;
+}
+
+// World box of one analytic primitive under a uniform-scale transform (s2 = scale^2), widened by a relative slack; for
+// spheres quad_pad grows to the envelope described at DevScene::abvh_q.  False if the box is not finite.
+bool prim_world_box(const PrtPrimitive& p, double s2, float* mn, float* mx, double* quad_pad) {
+    const float* M = p.mat;
+    for (int a = 0; a < 3; ++a) {
+        mn[a] = FLT_MAX;
+        mx[a] = -FLT_MAX;
+    }
+    if (p.shape_type == PRT_SHAPE_CIRCLE) {  // sphere of radius r around the local origin
+        const double R = std::fabs((double)p.shape_param[0]) * std::sqrt(s2);
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = (float)((double)M[12 + a] - R);
+            mx[a] = (float)((double)M[12 + a] + R);
+        }
+        // phantom hits of the fp32 discriminant: up to K * dist^2 / R outside the sphere, dist <= |o|_1 + |c|_1
+        // (K = 1e-6: measured worst 2.0e-7 over 3.6e7 grazing rays at 3..1000 units, analytic bound 4.8e-7)
+        if (R > 0.0) {
+            const double q = 1e-6 / R, c1 = std::fabs((double)M[12]) + std::fabs((double)M[13]) + std::fabs((double)M[14]);
+            quad_pad[0] = std::max(quad_pad[0], q);
+            quad_pad[1] = std::max(quad_pad[1], 2.0 * q * c1);
+            quad_pad[2] = std::max(quad_pad[2], q * c1 * c1);
+        }
+    } else {  // quad in the local plane y = 0
+        for (int corner = 0; corner < 4; ++corner) {
+            const float lx = ((corner & 1) ? 0.5f : -0.5f) * p.shape_param[0], lz = ((corner & 2) ? 0.5f : -0.5f) * p.shape_param[1];
+            for (int a = 0; a < 3; ++a) {
+                const float wv = (M[a] * lx + M[4 + a] * 0.0f) + (M[8 + a] * lz + M[12 + a]);
+                mn[a] = std::min(mn[a], wv);
+                mx[a] = std::max(mx[a], wv);
+            }
+        }
+    }
+    float mag = 0.0f;
+    for (int a = 0; a < 3; ++a) mag = std::max(mag, std::max(std::fabs(mn[a]), std::fabs(mx[a])));
+    const float slack = 1e-5f * (mag + (float)std::sqrt(s2) * (std::fabs(p.shape_param[0]) + std::fabs(p.shape_param[1]))) + 1e-30f;
+    bool finite = true;
+    for (int a = 0; a < 3; ++a) {
+        mn[a] -= slack;
+        mx[a] += slack;
+        if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) finite = false;
+    }
+    return finite;
+}
+
+// BVH over the analytic primitives (only when there are many: the reference scans all of them for every ray,
+// primitive.cpp:26; its default scene RANDOM_BALLS_LARGE has 809).  World boxes are only valid bounds of the
+// reference's hits when the primitive's transform is rotation + uniform scale + translation (inv is not looked at:
+// the boxes come from mat alone); one primitive that is not keeps the linear scan for the whole scene.
+void build_prim_bvh(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene& hs) {
+    const uint32_t n_prims = (uint32_t)hs.prims.size();
+    if (!opt.prim_bvh || n_prims <= 16u) return;
+    float extent_prims = 0.0f;
+    double quad_pad[3] = {0.0, 0.0, 0.0};
+    std::vector<float> pv(9 * (size_t)n_prims);
+    bool ok = true;
+    for (uint32_t i = 0; i < n_prims && ok; ++i) {
+        const PrtPrimitive& p = s->primitives[i];
+        double s2 = 0.0;
+        if (!gram_is_uniform_scale(p.mat, &s2) || !affine_bottom_row(p.mat)) {
+            ok = false;
+            break;
+        }
+        float mn[3], mx[3];
+        ok = prim_world_box(p, s2, mn, mx, quad_pad);
+        for (int a = 0; a < 3; ++a) extent_prims = std::max(extent_prims, std::max(std::fabs(mn[a]), std::fabs(mx[a])));
+        box_triangle(mn, mx, &pv[9 * (size_t)i]);
+    }
+    // (a walk that would need more than ABVH_STACK entries falls back to the scan)
+    if (ok && (!bvh_build(pv.data(), n_prims, kMaxLeaf, 1, kMaxStack, &hs.abvh) || hs.abvh.nodes4.empty())) ok = false;
+    if (!ok) hs.abvh = BvhBuild();
+    if (hs.abvh.nodes4.empty()) return;
+    hs.sc.extent = std::max(hs.sc.extent, extent_prims);  // the culling pad of the primitive walk scales with the scene
+    for (int k = 0; k < 3; ++k) hs.sc.abvh_q[k] = (float)(quad_pad[k] * 1.0000002);  // (rounded up)
+}
+
+struct Blas {  // one instanced mesh: its tree in its own space and where its triangles / nodes went
+    BvhBuild bvh;
+    uint32_t slot_base = 0, node_base = 0, n_tris = 0;
+    float mn[3], mx[3], extent = 0.0f;
+};
+
+// One tree per instanced mesh in its own space; its records go behind the world meshes' (and each other's) in
+// hs.tri_records / nrm_records.  *slots_io: triangle slots so far.
+int build_instanced_meshes(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene& hs, std::vector<Blas>& blas, uint64_t* slots_io,
+                           std::string* err) {
+    uint64_t slots = *slots_io;
+    for (uint32_t m = 0; m < s->n_instanced_meshes; ++m) {
+        const PrtMesh& me = s->instanced_meshes[m];
+        if (!me.n_triangles || !me.positions || !me.normals || !me.indices)
+            return fail(err, "instanced mesh %u: positions, normals and indices are required", m);
+        Blas& B = blas[m];
+        B.n_tris = me.n_triangles;
+        std::vector<float> v(9 * (size_t)me.n_triangles), nn(9 * (size_t)me.n_triangles);
+        for (int a = 0; a < 3; ++a) {
+            B.mn[a] = FLT_MAX;
+            B.mx[a] = -FLT_MAX;
+        }
+        int rc = prt_flatten_mesh(me, "instanced mesh", m, v.data(), nn.data(), &B.extent, B.mn, B.mx, err);
+        if (rc) return rc;
+        B.slot_base = (uint32_t)slots;
+        slots += me.n_triangles;
+        if (slots >= (1ull << 26)) return fail(err, "too many triangles (limit 2^26 - 1)");
+        // triangle / normal records in this mesh's leaf order: {P0, face index}, {P1, -}, {P2, -}
+        hs.tri_records.resize(12 * (size_t)slots, 0.0f);
+        hs.nrm_records.resize(12 * (size_t)slots, 0.0f);
+        float* tri_rec = &hs.tri_records[12 * (size_t)B.slot_base];
+        float* nrm_rec = &hs.nrm_records[12 * (size_t)B.slot_base];
+        bool on_device = false;
+        rc = build_tree(opt, TreeInput{v.data(), nn.data(), nullptr, me.n_triangles, 0u}, 0.0f, false, 0xFFFFFFFFu, true, 0, &B.bvh, tri_rec, nrm_rec,
+                        &on_device, &hs.gpu_build_ms, err);
+        if (rc == kHostBuildFailed || (!rc && !on_device && B.bvh.nodes8.empty())) return fail(err, "instanced mesh %u: BVH construction failed", m);
+        if (rc) return rc;
+        if (!on_device) pack_records(B.bvh.order, v.data(), nn.data(), me.n_triangles, 0u, nullptr, tri_rec, nrm_rec);
+    }
+    *slots_io = slots;
+    return PRT_OK;
+}
+
+// The instance table, [identity instance of the world-space meshes] + the placed copies (root = mesh index for now), and
+// every instance's world box
+int build_instance_table(const PrtSceneDesc* s, PrtHostScene& hs, const Work& w, const std::vector<Blas>& blas,
+                         std::vector<std::array<float, 6>>& boxes, std::string* err) {
+    const PrtSceneScalars& d = hs.sc;
+    auto identity12 = [](float* m12) {
+        for (int k = 0; k < 12; ++k) m12[k] = 0.0f;
+        m12[0] = m12[4] = m12[8] = 1.0f;
+    };
+    if (w.n_world) {
+        DevInstance I{};
+        identity12(I.mat);
+        identity12(I.inv);
+        I.root = 0;  // fixed up by assemble_two_level
+        I.slot_base = 0;
+        I.prim_base = 0;  // the world triangles' records carry their full primitive index
+        I.virt_base = 0;
+        I.material = 0xFFFFFFFFu;  // per triangle record
+        I.n_tris = w.n_world;
+        I.inv_scale = 1.0f;
+        I.extent = d.extent;
+        hs.dev_insts.push_back(I);
+        boxes.push_back({d.root_min[0], d.root_min[1], d.root_min[2], d.root_max[0], d.root_max[1], d.root_max[2]});
+    }
+    uint32_t virt = w.n_world, prim = d.n_prims + w.n_world;
+    for (uint32_t i = 0; i < s->n_instances; ++i) {
+        const PrtInstance& pi = s->instances[i];
+        if (pi.mesh >= s->n_instanced_meshes) return fail(err, "instance %u: mesh out of range", i);
+        if (pi.material_id >= s->n_materials) return fail(err, "instance %u: material out of range", i);
+        // rotation + uniform scale + translation only: transpose(M3) * M3 = s^2 * I, and inv * mat = I
+        const float* M = pi.mat;
+        double s2 = 0.0;
+        if (!is_similarity(pi.mat, pi.inv, &s2))
+            return fail(err,
+                        "instance %u: the transform must be rotation + uniform scale + translation with inv = inverse(mat) "
+                        "(the reference's local ray, primitive.cpp:29-30, is only a ray transform for those)", i);
+        const Blas& B = blas[pi.mesh];
+        DevInstance I{};
+        to_dev_mat(pi.mat, I.mat);
+        to_dev_mat(pi.inv, I.inv);
+        I.slot_base = B.slot_base;
+        I.prim_base = prim;
+        I.virt_base = virt;
+        I.material = pi.material_id;
+        I.n_tris = B.n_tris;
+        I.inv_scale = (float)(1.0 / std::sqrt(s2));
+        I.extent = B.extent;
+        I.root = pi.mesh;  // mesh index for now; node base in assemble_two_level
+        hs.dev_insts.push_back(I);
+        virt += B.n_tris;
+        prim += B.n_tris;
+        // world box: the 8 corners of the mesh box through Mat, widened by a relative slack for the fp32 rounding
+        // of Mat * p anywhere inside the box
+        std::array<float, 6> bx{FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
+        float mag = 0.0f;
+        for (int corner = 0; corner < 8; ++corner) {
+            const float p3[3] = {(corner & 1) ? B.mx[0] : B.mn[0], (corner & 2) ? B.mx[1] : B.mn[1], (corner & 4) ? B.mx[2] : B.mn[2]};
+            for (int a = 0; a < 3; ++a) {
+                const float wv = (M[a] * p3[0] + M[4 + a] * p3[1]) + (M[8 + a] * p3[2] + M[12 + a]);
+                bx[a] = std::min(bx[a], wv);
+                bx[3 + a] = std::max(bx[3 + a], wv);
+                mag = std::max(mag, std::fabs(wv));
+            }
+        }
+        for (int a = 0; a < 3; ++a) {
+            bx[a] -= 1e-5f * (mag + 1e-30f);
+            bx[3 + a] += 1e-5f * (mag + 1e-30f);
+        }
+        boxes.push_back(bx);
+    }
+    if ((uint64_t)virt + d.n_prims >= 0xFFFFFFF0ull) return fail(err, "too many placed triangles");
+    return PRT_OK;
+}
+
+// The top-level tree over the instances' world boxes and the scene's one node array: [top level][world meshes' tree]
+// [instanced meshes' trees], child_base / tri_base made absolute, every instance's root set
+int assemble_two_level(const PrtSceneOptions& opt, PrtHostScene& hs, Work& w, std::vector<Blas>& blas, const std::vector<std::array<float, 6>>& boxes,
+                       std::string* err) {
+    // the same builders over one degenerate "triangle" per instance that spans its world box
+    const uint32_t n_inst_total = (uint32_t)hs.dev_insts.size();
+    std::vector<float> pv(9 * (size_t)n_inst_total);
+    for (uint32_t i = 0; i < n_inst_total; ++i) box_triangle(&boxes[i][0], &boxes[i][3], &pv[9 * (size_t)i]);
+    BvhBuild top;
+    std::vector<float> rec(12 * (size_t)n_inst_total);
+    bool on_device = false;
+    // (device builder: an instance in a hit leaf is ENTERED, a level switch of ~150 instructions, without a box test of its
+    // own: a leaf cost this high makes the optimisation put every instance into a leaf of its own wherever the boxes
+    // differ; copies whose boxes coincide may still share a leaf, which costs a redundant entry, never a result)
+    const int rc = build_tree(opt, TreeInput{pv.data(), nullptr, nullptr, n_inst_total, 0u}, 64.0f, false, 0xFFFFFFFFu, false, 1, &top, rec.data(),
+                              nullptr, &on_device, &hs.gpu_build_ms, err);
+    if (rc == kPrtDeviceBuildGaveUp) return fail(err, "top-level tree: the device builder gave up; use gpu_build = 0 for this scene");
+    if (rc == kHostBuildFailed || (!rc && !on_device && top.nodes8.empty())) return fail(err, "top-level BVH construction failed");
+    if (rc) return rc;
+    if (on_device) {  // a record's primitive index is the instance it stands for
+        top.order.resize(n_inst_total);
+        for (uint32_t sl = 0; sl < n_inst_total; ++sl) memcpy(&top.order[sl], &rec[12 * (size_t)sl + 3], 4);
+    }
+    hs.tlas_inst = top.order;
+    hs.nodes8_all = top.nodes8;
+    uint32_t max_blas_depth = 0;
+    auto append = [&](const std::vector<uint32_t>& n8, uint32_t slot_base) -> uint32_t {
+        const uint32_t node_base = (uint32_t)(hs.nodes8_all.size() / 20);
+        const size_t at = hs.nodes8_all.size();
+        hs.nodes8_all.insert(hs.nodes8_all.end(), n8.begin(), n8.end());
+        for (size_t k = at; k < hs.nodes8_all.size(); k += 20) {
+            hs.nodes8_all[k + 4] += node_base;
+            hs.nodes8_all[k + 5] += slot_base;
+        }
+        return node_base;
+    };
+    uint32_t world_root = 0;
+    if (w.n_world) {
+        world_root = append(hs.bvh.nodes8, 0);
+        max_blas_depth = hs.bvh.depth8;
+    }
+    for (Blas& B : blas) {
+        B.node_base = append(B.bvh.nodes8, B.slot_base);
+        max_blas_depth = std::max(max_blas_depth, B.bvh.depth8);
+    }
+    for (size_t i = 0; i < hs.dev_insts.size(); ++i) {
+        DevInstance& I = hs.dev_insts[i];
+        I.root = (w.n_world && i == 0) ? world_root : blas[I.root].node_base;
+    }
+    if (top.depth8 + max_blas_depth > 12u)
+        return fail(err, "two-level BVH too deep for the traversal stack (%u + %u > 12)", top.depth8, max_blas_depth);
+    w.depth8 = top.depth8 + max_blas_depth;
+    return PRT_OK;
+}
+
+// Placed mesh copies (PrtInstance): one tree per instanced mesh in its own space + a top-level tree over the copies'
+// world boxes; the world-space meshes become one identity instance
+int compile_instances(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene& hs, Work& w, std::string* err) {
+    if (!s->n_instances) return PRT_OK;
+    if (w.n_world && hs.bvh.nodes8.empty()) return fail(err, "instances need the 8-wide tree (leaves <= 3 triangles)");
+    std::vector<Blas> blas(s->n_instanced_meshes);
+    uint64_t slots = w.n_world;
+    int rc = build_instanced_meshes(s, opt, hs, blas, &slots, err);
+    if (rc) return rc;
+    std::vector<std::array<float, 6>> boxes;
+    if ((rc = build_instance_table(s, hs, w, blas, boxes, err))) return rc;
+    if ((rc = assemble_two_level(opt, hs, w, blas, boxes, err))) return rc;
+    // scene-wide quantities the producers use
+    PrtSceneScalars& d = hs.sc;
+    for (int a = 0; a < 3; ++a) {
+        d.root_min[a] = FLT_MAX;
+        d.root_max[a] = -FLT_MAX;
+    }
+    for (const std::array<float, 6>& bx : boxes)
+        for (int a = 0; a < 3; ++a) {
+            d.root_min[a] = std::min(d.root_min[a], bx[a]);
+            d.root_max[a] = std::max(d.root_max[a], bx[3 + a]);
+            d.extent = std::max(d.extent, std::max(std::fabs(bx[a]), std::fabs(bx[3 + a])));
+        }
+    d.n_insts = (uint32_t)hs.dev_insts.size();
+    d.n_nodes = std::max(d.n_nodes, 1u);  // "the scene has a BVH"
+    d.n_tris = (uint32_t)slots;
+    w.host_build_ms = ms_since(w.t_build0);  // world meshes + every placed mesh + the top level
+    return PRT_OK;
+}
+
+void fill_info(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene& hs, const Work& w) {
+    hs.scene_device_built = w.world_on_device || (opt.device_build && s->n_instances != 0u);
+    PrtBvhInfo& bi = hs.bvh_info;
+    bi.n_nodes = (uint32_t)(hs.bvh.nodes.size() / 16);
+    bi.n_triangles = hs.sc.n_tris;
+    bi.max_depth = hs.bvh.max_depth;
+    bi.max_leaf_size = hs.bvh.max_leaf;
+    bi.sah_cost = hs.bvh.sah_cost;
+    bi.pad_abs = opt.pad_coeff;
+    bi.node_bytes = (uint64_t)hs.bvh.nodes4.size() * 4;
+    bi.n_nodes4 = (uint32_t)(hs.bvh.nodes4.size() / 32);
+    bi.max_stack4 = hs.bvh.max_stack4;
+    bi.n_nodes8 = (uint32_t)((s->n_instances ? hs.nodes8_all : hs.bvh.nodes8).size() / 20);
+    bi.depth8 = w.depth8;
+    // device time of the builder's runs, or the host builders' wall time
+    bi.build_ms = (float)(hs.scene_device_built ? hs.gpu_build_ms : w.host_build_ms);
+    bi.built_on_device = hs.scene_device_built ? 1u : 0u;
+    bi.refit_ms = 0.0f;
+    bi.refits = 0u;
+    bi.tri_bytes = (uint64_t)hs.tri_records.size() * 4;
+}
+
+}  // namespace
+
+int prt_flatten_mesh(const PrtMesh& me, const char* what, uint32_t m, float* verts, float* norms, float* extent, float* mn, float* mx,
+                     std::string* err) {
+    float ext = *extent, lo[3], hi[3];  // (locals: the stores to verts / norms may alias the callers' accumulators)
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = mn ? mn[a] : 0.0f;
+        hi[a] = mn ? mx[a] : 0.0f;
+    }
+    for (uint32_t k = 0; k < me.n_triangles; ++k)
+        for (int v = 0; v < 3; ++v) {
+            const uint32_t vi = me.indices[3 * (size_t)k + v];
+            if (vi >= me.n_vertices) return fail(err, "%s %u: vertex index out of range", what, m);
+            for (int a = 0; a < 3; ++a) {
+                const float pv = me.positions[3 * (size_t)vi + a];
+                if (!std::isfinite(pv)) return fail(err, "%s %u: non-finite vertex", what, m);
+                verts[9 * (size_t)k + 3 * v + a] = pv;
+                norms[9 * (size_t)k + 3 * v + a] = me.normals[3 * (size_t)vi + a];
+                ext = std::max(ext, std::fabs(pv));
+                lo[a] = std::min(lo[a], pv);
+                hi[a] = std::max(hi[a], pv);
+            }
+        }
+    *extent = ext;
+    for (int a = 0; a < 3 && mn; ++a) {
+        mn[a] = lo[a];
+        mx[a] = hi[a];
+    }
+    return PRT_OK;
+}
+
+int prt_check_scene_arrays(const PrtSceneDesc* s, std::string* err) {
+    if ((s->n_materials && !s->materials) || (s->n_primitives && !s->primitives) || (s->n_meshes && !s->meshes) ||
+        (s->n_instanced_meshes && !s->instanced_meshes) || (s->n_instances && !s->instances))
+        return fail(err, "null array in scene description");
+    return PRT_OK;
+}
+
+int prt_compile_scene(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene* out, std::string* err) {
+    int rc = prt_check_scene_arrays(s, err);
+    if (rc) return rc;
+    // a fresh scene, except that the two big record arrays keep the storage *out came with (96 bytes per triangle that a
+    // context which sets its scene again need not unmap and fault in anew; compile_world_meshes overwrites all of it)
+    PrtHostScene fresh;
+    fresh.tri_records.swap(out->tri_records);
+    fresh.nrm_records.swap(out->nrm_records);
+    *out = std::move(fresh);
+    PrtHostScene& hs = *out;
+    Work w;
+    if ((rc = compile_prims(s, hs, err))) return rc;
+    build_light_table(&hs, s);
+    if ((rc = compile_world_meshes(s, opt, hs, w, err))) return rc;
+    build_prim_bvh(s, opt, hs);
+    if ((rc = compile_instances(s, opt, hs, w, err))) return rc;
+    fill_info(s, opt, hs, w);
+    return PRT_OK;
+}

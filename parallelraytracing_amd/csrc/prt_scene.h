@@ -1,0 +1,78 @@
+// prt_scene.h — the scene compiler: PrtSceneDesc (include/prt.h) -> PrtHostScene, everything the kernels need about a
+// scene as host arrays (flattened primitives, light table, trees, triangle records in leaf order, instance table).
+// HIP-free: prt_scene.cpp builds with a plain C++ compiler (tests/sanitize_host.cpp runs it under ASan / UBSan); the
+// C-ABI layer (prt_api.cpp) owns the device copies and supplies the device-side tree builder as a callable.
+#pragma once
+#include <stdint.h>
+
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "../../include/prt.h"
+#include "bvh.h"
+#include "prt_scene_pod.h"
+
+// The scalar half of DevScene (prt_kernels.h; same names, same meaning); upload_scene puts the device pointers next to it.
+struct PrtSceneScalars {
+    uint32_t n_insts;
+    uint32_t n_prims;
+    uint32_t n_nodes;
+    uint32_t n_tris;
+    float pad;
+    float abvh_q[3];
+    float extent;
+    float root_min[3], root_max[3];
+    float sky[3];
+};
+
+struct PrtHostScene {
+    std::vector<PrtMaterial> materials;
+    std::vector<DevPrim> prims;
+    BvhBuild bvh;                      // the world-space meshes' tree
+    std::vector<float> tri_records;    // 12 floats per triangle, leaf order
+    std::vector<float> nrm_records;    // 12 floats per triangle, leaf order
+    double gpu_build_ms = 0.0;
+    bool scene_device_built = false;   // the scene's 8-wide tree came from the device-side builder (no binary / 4-wide tree)
+    std::vector<uint32_t> mesh_sizes;  // per world-space mesh of the scene: n_vertices, n_triangles (prt_refit_meshes checks them)
+    std::vector<uint32_t> nodes8_all;  // scenes with placed mesh copies: top-level tree + every mesh's tree
+    std::vector<DevInstance> dev_insts;
+    std::vector<uint32_t> tlas_inst;   // top-level leaf slot -> instance
+    BvhBuild abvh;                     // BVH over the analytic primitives' world boxes (scenes with many of them)
+    PrtBvhInfo bvh_info{};
+    PrtSceneScalars sc{};
+    std::vector<float> lights;         // the light table: 4 * PRT_LIGHT_F4 floats per light (prt_kernels.h DevLights)
+    std::vector<uint32_t> prim_light;  // per analytic primitive: its light index, 0xFFFFFFFF if not in the light set
+    uint32_t n_emitters_unsampled = 0;
+};
+
+// The device-side builder of the 8-wide tree over n triangles given as 9 floats each (+ normals, + a material per
+// triangle; both may be null): nodes8 / depth and the triangle / normal records in the tree's slot order come back
+// (nrm_rec may be null); its device time is added to *ms.  keep: the device arrays stay with the supplier (the world
+// meshes' tree of a scene without placed copies).  Returns PRT_OK, kPrtDeviceBuildGaveUp (the builder could not cope
+// with this input; the host builder can) or a PRT_ERR_* code with *err set.
+constexpr int kPrtDeviceBuildGaveUp = -1000;  // internal: not a PRT_ERR_* code
+using PrtDeviceBuilder = std::function<int(const float* verts, const float* norms, const uint32_t* tri_mat, uint32_t n, uint32_t n_prims,
+                                           float leaf_cost, bool keep, std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec,
+                                           float* nrm_rec, double* ms, std::string* err)>;
+
+struct PrtSceneOptions {
+    float pad_coeff;                // culling pad = pad_coeff x the coordinates' magnitude
+    bool prim_bvh;                  // build a BVH over the analytic primitives when there are many
+    PrtDeviceBuilder device_build;  // null: every tree is built on the host
+};
+
+// The description's top-level arrays: none null with a non-zero count (PRT_ERR_INVALID, message in *err).  First step of
+// prt_compile_scene; prt_set_scene asks on its own beforehand, because a description this malformed leaves the context's
+// present scene alone.
+int prt_check_scene_arrays(const PrtSceneDesc* s, std::string* err);
+
+// Compiles `s` into *out, of which nothing survives but the storage of its record arrays.  On failure (PRT_ERR_*, message
+// in *err) *out is unspecified.
+int prt_compile_scene(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene* out, std::string* err);
+
+// One PrtMesh as 9 floats per triangle into verts / norms (n_triangles x 9 each), with the checks every consumer of
+// caller-supplied index buffers needs: indices in range, vertices finite ("<what> <m>: ..." in *err, PRT_ERR_INVALID).
+// *extent grows to the largest |coordinate|; mn / mx (may be null) grow to the box.
+int prt_flatten_mesh(const PrtMesh& me, const char* what, uint32_t m, float* verts, float* norms, float* extent, float* mn, float* mx,
+                     std::string* err);
