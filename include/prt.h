@@ -148,7 +148,8 @@ typedef struct PrtSampling {
  *    uniformly in the cone they subtend from the shading point (not at all from inside or within PRT_LIGHT_SPHERE_MARGIN
  *    of their surface: pdf 0).  A light is picked with pmf proportional to emitting area x mean(rgb): quads 2 w h s^2,
  *    spheres 4 pi r^2 s^2.  Emissive mesh triangles, placed copies and analytic emitters with any other transform are
- *    never sampled; their emission counts on scattered hits at weight 1 (PrtLightStats.n_emitters_unsampled).
+ *    never sampled by default (prt_set_light_sources adds the triangles: "Triangle lights" below); their emission counts
+ *    on scattered hits at weight 1 (PrtLightStats.n_emitters_unsampled).
  *  Where: one light sample at every Lambertian vertex that scatters (segment index k with k + 1 < max_depth); never at
  *    metal, dielectric or emissive vertices.  It adds thr * (albedo / pi) * Le * max(0, n.w) * w_L / (pmf * pdf_w) if the
  *    shadow ray (x, w) with tmax = t_light * (1 - PRT_LIGHT_SHADOW_EPS) is not occluded (prt_occluded's semantics), with
@@ -175,6 +176,33 @@ typedef struct PrtLightStats {
     uint32_t n_lights;
     uint32_t n_emitters_unsampled; /* emissive primitives outside the light set (mesh / placed triangles, other transforms) */
 } PrtLightStats;
+/* Triangle lights (prt_set_light_sources; default PRT_LIGHT_SOURCES_ANALYTIC = everything above, unchanged).  With
+ * ANALYTIC | MESH the candidates are the analytic lights above (primitive order) followed by every triangle of an
+ * Emissive world-space mesh (mesh and face order) and of an Emissive placed copy (instance and face order): global
+ * primitive order.
+ *  Triangle: world vertices v0, v1, v2 as fp32 (placed copies: Mat * v evaluated in double, rounded once), e1 = v1 - v0,
+ *    e2 = v2 - v0, area A = |e1 x e2| / 2, geometric normal n_g = (e1 x e2) / |e1 x e2|, both in double, stored as fp32.
+ *    Emission Le = the material's rgb; both faces emit (as quads do).  Power 2 A mean(rgb); zero or non-finite power: not
+ *    a light and not counted as unsampled.
+ *  Point: with the stream's u1, u2: s = sqrt(u1), p = v0 + (s (1 - u2)) e1 + (s u2) e2; w = (p - x) / |p - x|,
+ *    t_light = |p - x|, tmax = t_light (1 - PRT_LIGHT_SHADOW_EPS).
+ *  pdf: pdf_w = d2 / (A |n_g . w|), the quad's formula; 0 where the denominator is 0.  For the light sample
+ *    d2 = |p - x|^2; for a scattered segment that hits the triangle, d2 of the hit.
+ *  Selection (all candidates, analytic ones too, while the MESH bit is set): P_i the powers in candidate order, C_i their
+ *    running sum in double, T_i = floor(C_i / C_n * 2^32 + 0.5) as a 64-bit integer (T_0 = 0, T_n = 2^32),
+ *    r0 = pcg_hash(pcg_hash(key + the light stream's constant)): the 32-bit state after the stream's first step, whose
+ *    top 24 bits are u0 of the default rule.  The light is the smallest i with r0 < T_i, and its pmf is
+ *    (T_i - T_{i-1}) / 2^32: the number the estimator, the MIS weights and prt_light_info use, equal to the selection
+ *    probability exactly for any number of lights (the kernels hold it rounded to fp32).  A candidate with an empty
+ *    interval is never picked and is NOT in the light set: n_lights, prt_light_info, the `light` output of
+ *    prt_sample_light and the MIS weights see the candidates with T_i > T_{i-1}, in global primitive order.  u1, u2 are
+ *    the stream's second and third draws, as above.
+ *  Weights, estimator, where samples are taken, clamp, roulette, RNG stream: as above.  A scattered segment from a
+ *    Lambertian vertex that hits a light-set triangle is weighted w_B = 1 - w_L for that pair; a triangle outside the
+ *    set, or with pmf 0, keeps weight 1.
+ *  n_emitters_unsampled then counts analytic emitters with a non-similarity transform plus candidates with positive
+ *    power and an empty interval. */
+enum { PRT_LIGHT_SOURCES_ANALYTIC = 1, PRT_LIGHT_SOURCES_MESH = 2 }; /* bit mask */
 
 /* Closest-hit record of one ray (what Scene::Intersect returns, src/core/surface_interaction.h:6-13,
  * plus the winning primitive index and the world distance^2 the reference minimises,
@@ -299,6 +327,16 @@ int prt_set_samples_in_flight(PrtContext* ctx, uint32_t n);
  * returns PRT_ERR_INVALID.  Works on host-only contexts too (it only records the mode). */
 int prt_set_lighting(PrtContext* ctx, const PrtLighting* l);
 int prt_get_light_stats(PrtContext* ctx, PrtLightStats* out);
+/* Which emitters the light set holds ("Triangle lights" above): PRT_LIGHT_SOURCES_ANALYTIC (default) or ANALYTIC | MESH;
+ * 0, MESH alone or unknown bits: PRT_ERR_INVALID.  Before or after prt_set_scene, host-only contexts too; the mask stays
+ * with the context across prt_set_scene, and prt_clone_scene copies the source's mask with its tables.  The table with
+ * triangles in it is built on the host with every scene (80 bytes + one threshold per candidate) and uploaded only while
+ * the MESH bit is set.  prt_refit_meshes with the MESH bit set rebuilds that table on the host from the new vertices
+ * and uploads it again: O(candidates), about 90 bytes per candidate over the bus, not part of the reported refit time. */
+int prt_set_light_sources(PrtContext* ctx, uint32_t mask);
+/* The exact pmf of the current light set: width[l] = T_l - T_{l-1}, pmf = width / 2^32 (prt_light_info's float is this
+ * number rounded).  With the default mask there are no thresholds: PRT_ERR_INVALID. */
+int prt_light_intervals(PrtContext* ctx, uint32_t capacity, uint32_t* n_lights, uint64_t* width);
 /* The light set of the current scene (host-only contexts too): n_lights, and for the first min(n_lights, capacity)
  * lights the primitive index and the pmf (prim / pmf may be NULL). */
 int prt_light_info(PrtContext* ctx, uint32_t capacity, uint32_t* n_lights, uint32_t* prim, float* pmf);
@@ -428,6 +466,7 @@ int prt_group_film_clear(PrtGroup* g);
 int prt_group_set_sampling(PrtGroup* g, const PrtSampling* s);
 int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n);
 int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l);
+int prt_group_set_light_sources(PrtGroup* g, uint32_t mask);
 /* shadow-ray counts summed over the ranks; n_lights / n_emitters_unsampled as rank 0 has them */
 int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out);
 int prt_group_set_param(PrtGroup* g, const char* name, int value);

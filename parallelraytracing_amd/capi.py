@@ -92,6 +92,8 @@ class PrtLightStats(C.Structure):
 
 # PrtLighting.mode (include/prt.h)
 LIGHTING_MODES = {"off": 0, "mis": 1, "nee": 2}
+# prt_set_light_sources masks (include/prt.h PRT_LIGHT_SOURCES_*)
+LIGHT_SOURCES = {"analytic": 1, "all": 3}
 
 
 class PrtBvhInfo(C.Structure):
@@ -141,6 +143,9 @@ SIGNATURES = {
     "prt_group_get_stats": (C.c_int, [_vp, C.POINTER(PrtStats)]),
     "prt_group_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),
     "prt_group_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
+    "prt_group_set_light_sources": (C.c_int, [_vp, C.c_uint32]),
+    "prt_set_light_sources": (C.c_int, [_vp, C.c_uint32]),
+    "prt_light_intervals": (C.c_int, [_vp, C.c_uint32, _u32p, C.POINTER(C.c_uint64)]),
     "prt_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),
     "prt_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
     "prt_light_info": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _fp]),

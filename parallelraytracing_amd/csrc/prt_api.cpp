@@ -125,6 +125,12 @@ struct PrtContext {
     uint32_t lighting = PRT_LIGHTING_OFF;
     void* d_lights = nullptr;
     void* d_prim_light = nullptr;
+    uint32_t light_sources = PRT_LIGHT_SOURCES_ANALYTIC;  // prt_set_light_sources
+    int light_buckets = 1;             // the bucket table brackets the search over the thresholds (0: plain binary search; A/B)
+    void* d_ml_records = nullptr;      // PrtMeshLights (prt_scene.h), on the device only while the MESH bit is set
+    void* d_ml_thr = nullptr;
+    void* d_ml_bucket = nullptr;
+    void* d_ml_runs = nullptr;
     PrtLightBufs lb{};                 // shadow rays, pdf of the previous scatter, light radiance: cap_light paths each
     uint64_t cap_light = 0;
     unsigned long long* d_light_stats = nullptr;  // [slot][shadow rays, occluded], since prt_reset_stats
@@ -236,10 +242,49 @@ int ensure_light_state(PrtContext* c, uint64_t n_paths) {
     return PRT_OK;
 }
 
+bool mesh_lights_on(const PrtContext* c) { return (c->light_sources & PRT_LIGHT_SOURCES_MESH) != 0u; }
+
+// with the MESH bit: the candidate table, n_lights = the candidates the search can return (0: nothing to sample)
 DevLights dev_lights(const PrtContext* c) {
+    const uint32_t mode = c->lighting == PRT_LIGHTING_NEE ? (uint32_t)PRT_LIGHTING_NEE : (uint32_t)PRT_LIGHTING_NEE_MIS;
+    if (mesh_lights_on(c)) return DevLights{(const float4*)c->d_ml_records, (const uint32_t*)c->d_prim_light, c->hs.ml.n_search, mode};
     return DevLights{(const float4*)c->d_lights, (const uint32_t*)c->d_prim_light,
-                     (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4)),
-                     c->lighting == PRT_LIGHTING_NEE ? (uint32_t)PRT_LIGHTING_NEE : (uint32_t)PRT_LIGHTING_NEE_MIS};
+                     (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4)), mode};
+}
+
+DevMeshLights dev_mesh_lights(const PrtContext* c) {
+    return DevMeshLights{(const uint32_t*)c->d_ml_thr, c->light_buckets ? (const uint32_t*)c->d_ml_bucket : nullptr,
+                         (const DevLightRun*)c->d_ml_runs, c->hs.ml.bucket_shift, (uint32_t)c->hs.ml.runs.size()};
+}
+
+uint32_t light_set_size(const PrtContext* c) {
+    return mesh_lights_on(c) ? (uint32_t)c->hs.ml.visible.size() : (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4));
+}
+
+void free_mesh_lights(PrtContext* c) {
+    free_dev(c->d_ml_records);
+    free_dev(c->d_ml_thr);
+    free_dev(c->d_ml_bucket);
+    free_dev(c->d_ml_runs);
+}
+
+// the candidate table of the current scene onto the device (prt_set_light_sources, upload_scene, prt_refit_meshes)
+int upload_mesh_lights(PrtContext* c) {
+    static_assert(sizeof(DevLightRun) == sizeof(PrtLightRun), "DevLightRun is PrtLightRun");
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    free_mesh_lights(c);
+    const PrtMeshLights& ml = c->hs.ml;
+    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    HIPCHECK(c, up(&c->d_ml_records, ml.records.data(), ml.records.size() * 4));
+    HIPCHECK(c, up(&c->d_ml_thr, ml.thr.data(), ml.thr.size() * 4));
+    HIPCHECK(c, up(&c->d_ml_bucket, ml.bucket.data(), ml.bucket.size() * 4));
+    HIPCHECK(c, up(&c->d_ml_runs, ml.runs.data(), ml.runs.size() * sizeof(PrtLightRun)));
+    return PRT_OK;
 }
 
 int ensure_counters(PrtContext* c) {
@@ -292,6 +337,7 @@ void free_scene(PrtContext* c) {
     free_dev(c->d_nrms);
     free_dev(c->d_lights);
     free_dev(c->d_prim_light);
+    free_mesh_lights(c);
     c->has_scene = false;
 }
 
@@ -430,6 +476,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
         c->pix_records_blank = false;
     }
     const DevLights lt = dev_lights(c);
+    const DevMeshLights mlt = dev_mesh_lights(c);
     if (lit) {  // the paths' light radiance starts at zero (paths that end with their primary ray never get a light sample)
         if ((rc = ensure_light_state(c, n_paths))) return rc;
         HIPCHECK(c, hipMemsetAsync(c->lb.lrad, 0, (size_t)n_paths * sizeof(float4), c->stream));
@@ -506,7 +553,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
         if ((rc = begin_event(c, 2, &ep))) return rc;
         if (lit) {
             prt_launch_shade_nee(c->stream, c->dsc, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
-                                 c->sampling, n_rays_known);
+                                 c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr);
             if (lt.n_lights) {
                 // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
                 // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
@@ -649,6 +696,10 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
     if (!gb) {
         HIPCHECK(c, upload(&c->d_tris, c->hs.tri_records.data(), c->hs.tri_records.size() * 4));
         HIPCHECK(c, upload(&c->d_nrms, c->hs.nrm_records.data(), c->hs.nrm_records.size() * 4));
+    }
+    if (mesh_lights_on(c)) {
+        const int rc_ml = upload_mesh_lights(c);
+        if (rc_ml) return rc_ml;
     }
     fill_dev_scene(c, node_stride, c->hs.bvh_info.depth8);
     const int rc_cnt = ensure_counters(c);
@@ -857,6 +908,7 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     if (dst == src) return PRT_OK;
     dst->has_scene = false;
     dst->hs = src->hs;
+    dst->light_sources = src->light_sources;
     if (!dst->has_device) {
         fill_dev_scene(dst, 0u, 0u);
         dst->has_scene = true;
@@ -959,6 +1011,9 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     c->hs.bvh_info.n_nodes4 = 0;
     c->hs.bvh_info.node_bytes = 0;
     c->hs.bvh_info.max_stack4 = 0;
+    // triangle lights follow the geometry: the candidate table again from the new vertices (host), uploaded if in use
+    prt_rebuild_mesh_lights(&c->hs, verts.data());
+    if (mesh_lights_on(c)) return upload_mesh_lights(c);
     return PRT_OK;
 }
 
@@ -1044,9 +1099,44 @@ int prt_set_lighting(PrtContext* c, const PrtLighting* l) {
     return PRT_OK;
 }
 
+int prt_set_light_sources(PrtContext* c, uint32_t mask) {
+    if (!c) return PRT_ERR_INVALID;
+    if (mask != (uint32_t)PRT_LIGHT_SOURCES_ANALYTIC && mask != (uint32_t)(PRT_LIGHT_SOURCES_ANALYTIC | PRT_LIGHT_SOURCES_MESH))
+        return fail(c, PRT_ERR_INVALID, "light sources: PRT_LIGHT_SOURCES_ANALYTIC or ANALYTIC | MESH, not %u", mask);
+    const bool was_on = mesh_lights_on(c);
+    c->light_sources = mask;
+    if (!c->has_device || !c->has_scene || was_on == mesh_lights_on(c)) return PRT_OK;
+    if (mesh_lights_on(c)) return upload_mesh_lights(c);
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    free_mesh_lights(c);
+    return PRT_OK;
+}
+
+int prt_light_intervals(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint64_t* width) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (!mesh_lights_on(c)) return fail(c, PRT_ERR_INVALID, "prt_light_intervals: the default light sources have no thresholds");
+    const uint32_t n = (uint32_t)c->hs.ml.visible.size();
+    if (n_lights) *n_lights = n;
+    for (uint32_t l = 0; l < n && l < capacity && width; ++l) width[l] = c->hs.ml.width[l];
+    return PRT_OK;
+}
+
 int prt_light_info(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint32_t* prim, float* pmf) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (mesh_lights_on(c)) {
+        const PrtMeshLights& ml = c->hs.ml;
+        const uint32_t nv = (uint32_t)ml.visible.size();
+        if (n_lights) *n_lights = nv;
+        for (uint32_t l = 0; l < nv && l < capacity; ++l) {
+            const float* r = &ml.records[4 * PRT_LIGHT_F4 * (size_t)ml.visible[l]];
+            if (prim) memcpy(&prim[l], &r[19], 4);
+            if (pmf) pmf[l] = r[7];
+        }
+        return PRT_OK;
+    }
     const uint32_t n = (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4));
     if (n_lights) *n_lights = n;
     for (uint32_t l = 0; l < n && l < capacity; ++l) {
@@ -1060,8 +1150,8 @@ int prt_light_info(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint32_
 int prt_get_light_stats(PrtContext* c, PrtLightStats* out) {
     if (!c || !out) return PRT_ERR_INVALID;
     memset(out, 0, sizeof(*out));
-    out->n_lights = (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4));
-    out->n_emitters_unsampled = c->hs.n_emitters_unsampled;
+    out->n_lights = light_set_size(c);
+    out->n_emitters_unsampled = mesh_lights_on(c) ? c->hs.ml.n_emitters_unsampled : c->hs.n_emitters_unsampled;
     if (!c->has_device || !c->d_light_stats) return PRT_OK;
     int rc = need_device(c);
     if (rc) return rc;
@@ -1402,7 +1492,8 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
     HIPCHECK(c, hipMemcpyAsync(d_h, hits, bh, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipMemcpyAsync(d_in, in_dirs, b3, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipMemcpyAsync(d_k, keys, b1, hipMemcpyHostToDevice, c->stream));
-    prt_launch_sample_light_test(c->stream, c->dsc, dev_lights(c), n, d_in, d_h, d_k, d_f, d_l);
+    const DevMeshLights mlt = dev_mesh_lights(c);
+    prt_launch_sample_light_test(c->stream, c->dsc, dev_lights(c), n, d_in, d_h, d_k, d_f, d_l, mesh_lights_on(c) ? &mlt : nullptr);
     HIPCHECK(c, hipGetLastError());
     std::vector<float> f((size_t)n * 11);
     HIPCHECK(c, hipMemcpyAsync(f.data(), d_f, bf, hipMemcpyDeviceToHost, c->stream));
@@ -1419,6 +1510,8 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
         pdf_bsdf[i] = r[8];
         w_light[i] = r[9];
         w_bsdf[i] = r[10];
+        // (the kernel reports the candidate; the light set proper leaves out the candidates with an empty interval)
+        if (mesh_lights_on(c) && light[i] != 0xFFFFFFFFu) light[i] = c->hs.ml.cand_visible[light[i]];
     }
     return PRT_OK;
 }
@@ -1641,6 +1734,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "fuse" && (value == 0 || value == 1)) c->tune.fuse = (uint32_t)value;
     else if (n == "tri_min" && value >= 0 && value <= 1024) c->tune.tri_min = (uint32_t)value;  // 0 = auto
     else if (n == "refill_min" && value >= 1 && value <= 64) c->tune.refill_min = (uint32_t)value;
+    else if (n == "light_buckets" && (value == 0 || value == 1)) c->light_buckets = value;
     else if (n == "exit_max" && value >= 0 && value < 64) c->tune.exit_max = (uint32_t)value;
     else return fail(c, PRT_ERR_INVALID, "unknown parameter or bad value: %s = %d", name, value);
     return PRT_OK;

@@ -312,6 +312,11 @@ int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l) {
     return for_each_rank(g, [&](uint32_t r) { return prt_set_lighting(g->ctx[r], l); }, false);
 }
 
+int prt_group_set_light_sources(PrtGroup* g, uint32_t mask) {
+    if (!g) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_light_sources(g->ctx[r], mask); }, false);
+}
+
 int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out) {
     if (!g || !out || g->ctx.empty()) return PRT_ERR_INVALID;
     memset(out, 0, sizeof(*out));

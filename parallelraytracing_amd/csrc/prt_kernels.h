@@ -142,6 +142,24 @@ struct DevLights {
     uint32_t n_lights;
     uint32_t mode;  // PRT_LIGHTING_NEE_MIS / PRT_LIGHTING_NEE
 };
+// Triangle lights (prt_set_light_sources with PRT_LIGHT_SOURCES_MESH; host side: PrtMeshLights, prt_scene.h).  DevLights
+// then holds the CANDIDATE table (same records; triangles: [0] v0, area  [1] e1, pmf  [2] e2, -  [3] n_g, kind 2
+// [4] emission, primitive index) with n_lights = the candidates the search can return, and this goes with it, to the
+// kernel instances of their own that sample triangles (the default instances keep their arguments and their code):
+//   thr[i] = T_{i+1}: the light of the 32-bit draw r0 is the smallest i with r0 < thr[i], else n_lights - 1
+//   bucket[r0 >> bucket_shift] .. bucket[(r0 >> bucket_shift) + 1] brackets that i (null: search all of thr)
+//   runs: per emissive mesh / placed copy, ascending prim_first: triangle with global primitive index p in
+//   [prim_first, prim_first + n_tris) is candidate light_first + (p - prim_first)
+struct DevLightRun {
+    uint32_t prim_first, n_tris, light_first, world;
+};
+struct DevMeshLights {
+    const uint32_t* thr;
+    const uint32_t* bucket;
+    const DevLightRun* runs;
+    uint32_t bucket_shift;
+    uint32_t n_runs;
+};
 // What the lighting shade step needs beyond k_shade's arguments: the shadow-ray buffer (o = x, path id; d = w, -;
 // t = clamped contribution rgb, tmax; hit / hd2 seeded as k_pack_occlusion_rays seeds them), the per-path pdf of the
 // previous scatter (pB, < 0: the previous vertex was not Lambertian) and the per-path light radiance.
@@ -210,10 +228,12 @@ void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, con
 // cursors reset for the next bounce); the film accumulation of rad + lrad
 void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
                           const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
-                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known);
+                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
+                          const DevMeshLights* ml = nullptr);  // ml: the instances that sample triangle lights
 void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBufs& lb, const uint32_t* count_ptr,
                             uint32_t* work, uint32_t max_rays);
 void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, const PrtTileMap& tm,
                                uint32_t S, uint32_t max_depth, bool update_film, unsigned long long* ray_stats);
 void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
-                                  const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light);
+                                  const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light,
+                                  const DevMeshLights* ml = nullptr);

@@ -2950,8 +2950,10 @@ PRT_DEV float sphere_cone_omc(float4 L0, f3 x) {
 
 // Solid-angle pdf with which the light (records L0, L3) samples the unit direction w from x, whose point on the light lies
 // at distance^2 d2: quad d2 / (A |n_l.w|), sphere 1 / (2 pi (1 - cos theta_max)); 0 = the light cannot sample w.
+// (MESHL: the instances that know triangle lights, kind 2: the quad's formula with the triangle's area and normal)
+template <bool MESHL = false>
 PRT_DEV float light_pdf_w(float4 L0, float4 L3, f3 x, f3 w, float d2) {
-    if (__float_as_uint(L3.w) == 1u) {
+    if (MESHL ? __float_as_uint(L3.w) != 0u : __float_as_uint(L3.w) == 1u) {
         const float den = L0.w * __builtin_fabsf(dot3(mk3(L3.x, L3.y, L3.z), w));
         return den > 0.0f ? d2 / den : 0.0f;
     }
@@ -2968,17 +2970,58 @@ struct LightSample {
     uint32_t light;
 };
 
-// One light sample from x with the draws of key's own stream (the path's state is not advanced): the light by its CDF,
-// then a point uniform by area (quad) or a direction uniform in the cone (sphere).  false: no sample (pdf 0).
-PRT_DEV bool sample_light(const DevLights& lt, f3 x, uint32_t key, LightSample& s) {
+// Triangle lights: the candidate of the 32-bit draw r0, the smallest i with r0 < T_{i+1} = thr[i] (n_lights - 1 if none:
+// T_n = 2^32).  thr is a dense uint32 array (4 B per candidate against the records' 80 B: ~3.5 MB for 870 k lights, which
+// stays in L2 / MALL where the records do not).  Plain binary search: ceil(log2 n) DEPENDENT loads per lane, and the
+// lanes of a wave draw independently, so every step is a fully divergent gather.  The bucket table (about one bucket
+// per candidate, at most 2^20) gives the candidates of the first and last draw of r0's bucket, which bracket the
+// answer: two independent loads, then a search over the few thresholds that fall inside one bucket (often none).  The
+// result is the same index either way.
+PRT_DEV uint32_t select_light(const DevLights& lt, const DevMeshLights& ml, uint32_t r0) {
+    uint32_t lo = 0u, hi = lt.n_lights - 1u;
+    if (ml.bucket) {
+        const uint32_t b = ml.bucket_shift < 32u ? r0 >> ml.bucket_shift : 0u;
+        lo = ml.bucket[b];
+        hi = ml.bucket[b + 1u];
+    }
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (r0 < ml.thr[mid]) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+
+// Candidate of the triangle with global primitive index `prim` (a triangle with an Emissive material lies in a run);
+// 0xFFFFFFFF if it lies in none.
+PRT_DEV uint32_t triangle_light(const DevMeshLights& ml, uint32_t prim) {
+    if (!ml.n_runs) return 0xFFFFFFFFu;
+    uint32_t lo = 0u, hi = ml.n_runs;  // the last run with prim_first <= prim
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ml.runs[mid].prim_first <= prim) lo = mid; else hi = mid;
+    }
+    const DevLightRun r = ml.runs[lo];
+    return prim - r.prim_first < r.n_tris ? r.light_first + (prim - r.prim_first) : 0xFFFFFFFFu;
+}
+
+// One light sample from x with the draws of key's own stream (the path's state is not advanced): the light by its CDF
+// (MESHL: by the integer thresholds, select_light), then a point uniform by area (quad, triangle) or a direction uniform
+// in the cone (sphere).  false: no sample (pdf 0).
+template <bool MESHL = false>
+PRT_DEV bool sample_light(const DevLights& lt, f3 x, uint32_t key, LightSample& s, const DevMeshLights* ml = nullptr) {
     uint32_t ls = pcg_hash(key + PRT_LIGHT_RNG);
     const float u0 = rnd01(ls);
+    const uint32_t r0 = ls;  // the state after the stream's first step: u0 is its top 24 bits
     const float u1 = rnd01(ls);
     const float u2 = rnd01(ls);
     uint32_t lo = 0u, hi = lt.n_lights - 1u;  // smallest i with u0 < cdf[i] (cdf[n - 1] = 1)
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (u0 < lt.lights[PRT_LIGHT_F4 * mid + 2u].w) hi = mid; else lo = mid + 1u;
+    if (MESHL) {
+        lo = select_light(lt, *ml, r0);
+    } else {
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (u0 < lt.lights[PRT_LIGHT_F4 * mid + 2u].w) hi = mid; else lo = mid + 1u;
+        }
     }
     const float4* L = lt.lights + PRT_LIGHT_F4 * lo;
     const float4 L0 = L[0], L1 = L[1], L2 = L[2], L3 = L[3], L4 = L[4];
@@ -2993,6 +3036,14 @@ PRT_DEV bool sample_light(const DevLights& lt, f3 x, uint32_t key, LightSample& 
         t_light = __builtin_sqrtf(d2);
         s.w = dv * (1.0f / t_light);
         pdf_w = light_pdf_w(L0, L3, x, s.w, d2);
+    } else if (MESHL && __float_as_uint(L3.w) == 2u) {  // triangle: s = sqrt(u1), p = v0 + (s (1 - u2)) e1 + (s u2) e2
+        const float sq = __builtin_sqrtf(u1);
+        const f3 p = c + mk3(L1.x, L1.y, L1.z) * (sq * (1.0f - u2)) + mk3(L2.x, L2.y, L2.z) * (sq * u2);
+        const f3 dv = p - x;
+        const float d2 = dot3(dv, dv);
+        t_light = __builtin_sqrtf(d2);
+        s.w = dv * (1.0f / t_light);
+        pdf_w = light_pdf_w<true>(L0, L3, x, s.w, d2);
     } else {  // sphere: 1 - cos theta = u1 (1 - cos theta_max), phi = 2 pi u2 about the direction to the centre
         const float omc = sphere_cone_omc(L0, x);
         if (!(omc > 0.0f)) return false;
@@ -3033,11 +3084,14 @@ PRT_DEV float light_weight(uint32_t mode, float pl, float pb) {
 
 // Weight of the emission of analytic primitive `prim` met by a segment scattered at x by a Lambertian vertex with pdf pb
 // (direction w, hit at distance^2 d2): 1 - w_L of the same pair; 1 for emitters outside the light set or where pL = 0.
-PRT_DEV float bsdf_hit_weight(const DevLights& lt, uint32_t prim, f3 x, f3 w, float d2, float pb) {
-    const uint32_t li = lt.prim_light[prim];
+// MESHL: `prim` is a global primitive index, analytic (< n_prims) or a triangle's.
+template <bool MESHL = false>
+PRT_DEV float bsdf_hit_weight(const DevLights& lt, uint32_t prim, f3 x, f3 w, float d2, float pb, const DevMeshLights* ml = nullptr,
+                              uint32_t n_prims = 0u) {
+    const uint32_t li = (MESHL && prim >= n_prims) ? triangle_light(*ml, prim) : lt.prim_light[prim];
     if (li == 0xFFFFFFFFu) return 1.0f;
     const float4* L = lt.lights + PRT_LIGHT_F4 * li;
-    const float pl = L[1].w * light_pdf_w(L[0], L[3], x, w, d2);
+    const float pl = L[1].w * light_pdf_w<MESHL>(L[0], L[3], x, w, d2);
     if (!(pl > 0.0f)) return 1.0f;
     if (lt.mode == (uint32_t)PRT_LIGHTING_NEE) return 0.0f;
     const float r = pl / pb;  // pb = 0: r = inf, weight 0
@@ -3047,9 +3101,10 @@ PRT_DEV float bsdf_hit_weight(const DevLights& lt, uint32_t prim, f3 x, f3 w, fl
 // Light sample of a Lambertian vertex (position x, shading normal n, albedo, throughput thr before its roulette) with the
 // key of the path's state at the vertex.  false: no sample (pdf 0).  Otherwise s, pb = max(0, n.w) / pi, the weight wl and
 // `contrib`, the clamped term a shadow ray (x, s.w, s.tmax) delivers if unoccluded (zero, and no shadow ray, if n.w <= 0).
+template <bool MESHL = false>
 PRT_DEV bool light_sample_term(const DevLights& lt, f3 x, f3 n, f3 albedo, f3 thr, uint32_t key, float clamp, LightSample& s,
-                               float& pb, float& wl, f3& contrib) {
-    if (!sample_light(lt, x, key, s)) return false;
+                               float& pb, float& wl, f3& contrib, const DevMeshLights* ml = nullptr) {
+    if (!sample_light<MESHL>(lt, x, key, s, ml)) return false;
     const float c = dot3(n, s.w);
     pb = (c > 0.0f ? c : 0.0f) * PRT_INV_PI;
     wl = light_weight(lt.mode, s.pdf_l, pb);
@@ -3068,11 +3123,12 @@ PRT_DEV bool light_sample_term(const DevLights& lt, f3 x, f3 n, f3 albedo, f3 th
 // advance_path<1, INST, ABVH, SHADE_BLOCK> (no fused segment) with light sampling: the same vertex, the same draws, the same
 // segments; in addition the light sample (`shadow`) of a Lambertian vertex that scatters, emission of light-set emitters
 // met after a Lambertian vertex weighted by bsdf_hit_weight, and pb_next = the pdf of the scatter (-1: not Lambertian).
-template <bool INST, bool ABVH>
+// MESHL (ml: the triangle lights' tables): the light set holds triangles too, so a segment's triangle hit is weighted as well.
+template <bool INST, bool ABVH, bool MESHL = false>
 PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t id, f3& o, f3& d, f3& thr, uint32_t& rng,
                              uint32_t& depth, uint32_t max_depth, const PrtSampling& sp, float4* __restrict__ rad_slot,
                              uint32_t& id0, float& d2_0, float pb_prev, float& pb_next, bool& shadow, f3& sx, f3& sw,
-                             float& stmax, f3& scontrib) {
+                             float& stmax, f3& scontrib, const DevMeshLights* ml = nullptr) {
     if (id == HIT_MISS) {
         st_stream(rad_slot, path_result(thr * mk3(sc.sky[0], sc.sky[1], sc.sky[2]), sp.clamp, depth));
         return 0;
@@ -3091,8 +3147,9 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
     }
     if (!scattered) {
         f3 L = thr * emitted;
-        if (type == 4u && id < sc.n_prims && pb_prev >= 0.0f) {
-            const float wb = bsdf_hit_weight(lt, id, o, d, w.d2, pb_prev);
+        if (type == 4u && (MESHL || id < sc.n_prims) && pb_prev >= 0.0f) {
+            const float wb = MESHL ? bsdf_hit_weight<MESHL>(lt, (uint32_t)w.prim, o, d, w.d2, pb_prev, ml, sc.n_prims)
+                                   : bsdf_hit_weight(lt, id, o, d, w.d2, pb_prev);
             if (wb != 1.0f) L = L * wb;
         }
         st_stream(rad_slot, path_result(L, sp.clamp, depth));
@@ -3101,7 +3158,7 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
     if (type == 1u && lt.n_lights) {  // (scattered: depth + 1 < max_depth)
         LightSample ls;
         float pb, wl;
-        if (light_sample_term(lt, w.pos, w.normal, mk3(rgbs.x, rgbs.y, rgbs.z), thr, key, sp.clamp, ls, pb, wl, scontrib) &&
+        if (light_sample_term<MESHL>(lt, w.pos, w.normal, mk3(rgbs.x, rgbs.y, rgbs.z), thr, key, sp.clamp, ls, pb, wl, scontrib, ml) &&
             pb > 0.0f) {
             shadow = true;
             sw = ls.w;
@@ -3139,7 +3196,7 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
         const float4 e = sc.mat_rgbs[m];
         f3 L = thr * mk3(e.x, e.y, e.z);
         if (pb_next >= 0.0f) {
-            const float wb = bsdf_hit_weight(lt, id0, o, d, d2_0, pb_next);
+            const float wb = bsdf_hit_weight<MESHL>(lt, id0, o, d, d2_0, pb_next, ml, sc.n_prims);  // (id0: an analytic hit of the scan)
             if (wb != 1.0f) L = L * wb;
         }
         st_stream(rad_slot, path_result(L, sp.clamp, depth));
@@ -3148,15 +3205,14 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
     return 2;
 }
 
-template <bool INST, bool ABVH>
-__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee(DevScene sc, DevLights lt, const float4* __restrict__ ro,
-                                                          const float4* __restrict__ rd, const float4* __restrict__ rt,
-                                                          const uint32_t* __restrict__ hit, float4* __restrict__ no,
-                                                          float4* __restrict__ nd, float4* __restrict__ nt,
-                                                          uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
-                                                          PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
-                                                          uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
-                                                          uint32_t cap, PrtSampling sp) {
+// The lighting shade step; MESHL / ml: see advance_path_nee (k_shade_nee passes false / null and compiles to the code it had
+// before there were triangle lights; k_shade_nee_mesh is the instance with them).
+template <bool INST, bool ABVH, bool MESHL>
+PRT_DEV void shade_nee_step(DevScene sc, DevLights lt, const DevMeshLights* ml, const float4* __restrict__ ro,
+                            const float4* __restrict__ rd, const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
+                            float4* __restrict__ no, float4* __restrict__ nd, float4* __restrict__ nt, uint32_t* __restrict__ nhit,
+                            float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                            uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
     const uint32_t nA = CNT_A(counts, iter), nB = CNT_B(counts, iter);
     const uint32_t count = nA + nB;
     if (blockIdx.x * (uint32_t)SHADE_BLOCK >= count) return;  // whole block exits together
@@ -3184,8 +3240,8 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee(DevScene sc, DevLight
         // pdf of the scatter that started this segment (segment 0 starts at the camera)
         const float pb_prev = depth ? lb.pdf_b[pid] : -1.0f;
         if (id != HIT_DEAD) {
-            const int r = advance_path_nee<INST, ABVH>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
-                                                       pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb);
+            const int r = advance_path_nee<INST, ABVH, MESHL>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
+                                                       pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb, ml);
             front = r == 1;
             back = r == 2;
         }
@@ -3210,6 +3266,31 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee(DevScene sc, DevLight
         lb.sh.hit[ss] = HIT_MISS;
         lb.sh.hd2[ss] = stmax * stmax;
     }
+}
+
+template <bool INST, bool ABVH>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee(DevScene sc, DevLights lt, const float4* __restrict__ ro,
+                                                          const float4* __restrict__ rd, const float4* __restrict__ rt,
+                                                          const uint32_t* __restrict__ hit, float4* __restrict__ no,
+                                                          float4* __restrict__ nd, float4* __restrict__ nt,
+                                                          uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
+                                                          PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                                                          uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
+                                                          uint32_t cap, PrtSampling sp) {
+    shade_nee_step<INST, ABVH, false>(sc, lt, nullptr, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter, max_depth, cap, sp);
+}
+
+// k_shade_nee with triangle lights in the light set (prt_set_light_sources with PRT_LIGHT_SOURCES_MESH)
+template <bool INST, bool ABVH>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_mesh(DevScene sc, DevLights lt, DevMeshLights ml, const float4* __restrict__ ro,
+                                                               const float4* __restrict__ rd, const float4* __restrict__ rt,
+                                                               const uint32_t* __restrict__ hit, float4* __restrict__ no,
+                                                               float4* __restrict__ nd, float4* __restrict__ nt,
+                                                               uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
+                                                               PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                                                               uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
+                                                               uint32_t cap, PrtSampling sp) {
+    shade_nee_step<INST, ABVH, true>(sc, lt, &ml, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter, max_depth, cap, sp);
 }
 
 // After the shadow walk: every unoccluded shadow ray adds its contribution to its path's light radiance (at most one shadow
@@ -3263,9 +3344,10 @@ __global__ void __launch_bounds__(256) k_light_accum(DevScene sc, PrtLightBufs l
 // prt_sample_light: one light sample per (hit, key) through the render's own light_sample_term (throughput 1, no clamp) and,
 // for the same pair of vertices, the weight bsdf_hit_weight gives a scattered segment in direction w that meets the light;
 // out 11 floats per ray: w.xyz, tmax, contrib.rgb, pdf_light, pdf_bsdf, w_light, w_bsdf
-__global__ void k_sample_light_test(DevScene sc, DevLights lt, uint32_t n, const float* __restrict__ in_d,
-                                    const PrtHit* __restrict__ hits, const uint32_t* __restrict__ keys, float* __restrict__ out,
-                                    uint32_t* __restrict__ out_light) {
+template <bool MESHL>
+PRT_DEV void sample_light_test(DevScene sc, DevLights lt, const DevMeshLights* ml, uint32_t n, const float* __restrict__ in_d,
+                               const PrtHit* __restrict__ hits, const uint32_t* __restrict__ keys, float* __restrict__ out,
+                               uint32_t* __restrict__ out_light) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const PrtHit h = hits[i];
@@ -3277,17 +3359,30 @@ __global__ void k_sample_light_test(DevScene sc, DevLights lt, uint32_t n, const
         LightSample s;
         float pb = 0.0f, wl = 0.0f;
         f3 C;
-        if (light_sample_term(lt, x, mk3(h.normal[0], h.normal[1], h.normal[2]), mk3(a.x, a.y, a.z), mk3(1.f, 1.f, 1.f), keys[i],
-                              0.0f, s, pb, wl, C)) {
+        if (light_sample_term<MESHL>(lt, x, mk3(h.normal[0], h.normal[1], h.normal[2]), mk3(a.x, a.y, a.z), mk3(1.f, 1.f, 1.f), keys[i],
+                                     0.0f, s, pb, wl, C, ml)) {
             light = s.light;
             const uint32_t prim = __float_as_uint(lt.lights[PRT_LIGHT_F4 * s.light + 4u].w);
             const float vals[11] = {s.w.x, s.w.y, s.w.z, s.tmax, C.x, C.y, C.z, s.pdf_l, pb, wl,
-                                    bsdf_hit_weight(lt, prim, x, s.w, s.t_light * s.t_light, pb)};
+                                    bsdf_hit_weight<MESHL>(lt, prim, x, s.w, s.t_light * s.t_light, pb, ml, sc.n_prims)};
             for (int j = 0; j < 11; ++j) r[j] = vals[j];
         }
     }
     for (int j = 0; j < 11; ++j) out[11 * (size_t)i + j] = r[j];
     out_light[i] = light;
+}
+
+__global__ void k_sample_light_test(DevScene sc, DevLights lt, uint32_t n, const float* __restrict__ in_d,
+                                    const PrtHit* __restrict__ hits, const uint32_t* __restrict__ keys, float* __restrict__ out,
+                                    uint32_t* __restrict__ out_light) {
+    sample_light_test<false>(sc, lt, nullptr, n, in_d, hits, keys, out, out_light);
+}
+
+// (the `light` it reports is the candidate; prt_sample_light maps it to the light set)
+__global__ void k_sample_light_test_mesh(DevScene sc, DevLights lt, DevMeshLights ml, uint32_t n, const float* __restrict__ in_d,
+                                         const PrtHit* __restrict__ hits, const uint32_t* __restrict__ keys, float* __restrict__ out,
+                                         uint32_t* __restrict__ out_light) {
+    sample_light_test<true>(sc, lt, &ml, n, in_d, hits, keys, out, out_light);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3687,17 +3782,27 @@ void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, con
 
 void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
                           const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
-                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known) {
+                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known, const DevMeshLights* ml) {
     const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
     const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
 #define PRT_SHADE_NEE(IN, AB)                                                                                          \
     hipLaunchKernelGGL((k_shade_nee<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, in.o, in.d, in.t, in.hit, out.o,  \
                        out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
-    if (sc.abvh_nodes) {
+#define PRT_SHADE_NEE_MESH(IN, AB)                                                                                         \
+    hipLaunchKernelGGL((k_shade_nee_mesh<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *ml, in.o, in.d, in.t, in.hit,  \
+                       out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+    if (ml) {  // triangle lights in the light set
+        if (sc.abvh_nodes) {
+            if (sc.n_insts) PRT_SHADE_NEE_MESH(true, true); else PRT_SHADE_NEE_MESH(false, true);
+        } else {
+            if (sc.n_insts) PRT_SHADE_NEE_MESH(true, false); else PRT_SHADE_NEE_MESH(false, false);
+        }
+    } else if (sc.abvh_nodes) {
         if (sc.n_insts) PRT_SHADE_NEE(true, true); else PRT_SHADE_NEE(false, true);
     } else {
         if (sc.n_insts) PRT_SHADE_NEE(true, false); else PRT_SHADE_NEE(false, false);
     }
+#undef PRT_SHADE_NEE_MESH
 #undef PRT_SHADE_NEE
 }
 
@@ -3714,6 +3819,10 @@ void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* 
 }
 
 void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
-                                  const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light) {
+                                  const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light, const DevMeshLights* ml) {
+    if (ml) {
+        hipLaunchKernelGGL(k_sample_light_test_mesh, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, *ml, n, in_d, hits, keys, out_f, out_light);
+        return;
+    }
     hipLaunchKernelGGL(k_sample_light_test, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, n, in_d, hits, keys, out_f, out_light);
 }

@@ -129,12 +129,15 @@ void build_light_table(PrtHostScene* c, const PrtSceneDesc* s) {
         c->lights[4 * PRT_LIGHT_F4 * l + 7] = (float)(power[l] / total);                                 // pmf
         c->lights[4 * PRT_LIGHT_F4 * l + 11] = l + 1 == power.size() ? 1.0f : (float)(acc / total);  // cdf
     }
+    c->light_power = power;
+    const uint32_t n_not_similar = c->n_emitters_unsampled;
     for (uint32_t m = 0; m < s->n_meshes; ++m)
         if (emissive(s->meshes[m].material_id)) c->n_emitters_unsampled += s->meshes[m].n_triangles;
     for (uint32_t i = 0; i < s->n_instances; ++i) {
         const PrtInstance& pi = s->instances[i];
         if (emissive(pi.material_id) && pi.mesh < s->n_instanced_meshes) c->n_emitters_unsampled += s->instanced_meshes[pi.mesh].n_triangles;
     }
+    c->ml_tris_counted = c->n_emitters_unsampled - n_not_similar;
 }
 
 // Triangle / normal records of n triangles in leaf order: {P0, prim_base + input index}, {P1, material}, {P2, -}.  norms /
@@ -208,6 +211,165 @@ struct Work {
     double host_build_ms = 0.0;       // wall time of the tree builds (reported when the host built them)
     uint32_t depth8 = 0;              // levels of the 8-wide tree (two-level scenes: top level + deepest mesh tree)
 };
+
+// ---- the light set with emissive triangles (PrtMeshLights, prt_scene.h; contract: include/prt.h "Triangle lights") ----
+
+// Candidate records of n triangles given as fp32 world vertices (9 floats each), appended to ml.records / ml.power at
+// candidate `at`: {v0 | A}, {e1 | pmf}, {e2 | -}, {n_g | kind 2}, {Le | global primitive index}.  e1, e2, A, n_g in double,
+// stored as fp32; power 2 A mean(rgb), 0 where that is not a positive finite number.
+void write_tri_candidates(PrtMeshLights& ml, size_t at, const float* verts, uint32_t n, const float* rgb, uint32_t prim_first) {
+    const double mean = ((double)rgb[0] + (double)rgb[1] + (double)rgb[2]) / 3.0;
+    for (uint32_t t = 0; t < n; ++t) {
+        const float* v = &verts[9 * (size_t)t];
+        float* rec = &ml.records[4 * PRT_LIGHT_F4 * (at + t)];
+        std::fill_n(rec, 4 * PRT_LIGHT_F4, 0.0f);
+        double e1[3], e2[3];
+        for (int a = 0; a < 3; ++a) {
+            e1[a] = (double)v[3 + a] - (double)v[a];
+            e2[a] = (double)v[6 + a] - (double)v[a];
+            rec[a] = v[a];
+            rec[4 + a] = (float)e1[a];
+            rec[8 + a] = (float)e2[a];
+        }
+        const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+        const double cl = std::sqrt(cx * cx + cy * cy + cz * cz);
+        const double area = 0.5 * cl;
+        rec[3] = (float)area;
+        if (cl > 0.0 && std::isfinite(cl)) {
+            rec[12] = (float)(cx / cl);
+            rec[13] = (float)(cy / cl);
+            rec[14] = (float)(cz / cl);
+        }
+        const uint32_t kind = 2u, prim = prim_first + t;
+        memcpy(&rec[15], &kind, 4);
+        rec[16] = rgb[0];
+        rec[17] = rgb[1];
+        rec[18] = rgb[2];
+        memcpy(&rec[19], &prim, 4);
+        const double pw = 2.0 * area * mean;
+        ml.power[at + t] = (pw > 0.0 && std::isfinite(pw)) ? pw : 0.0;
+    }
+}
+
+// Thresholds T_i = floor(C_i / C_n * 2^32 + 0.5) of the running power sums C_i (double, candidate order), the pmf
+// (T_i - T_{i-1}) / 2^32 into every record, the light set proper, the search array and its bucket table.
+void finish_mesh_lights(PrtHostScene& hs, uint32_t n_not_similar) {
+    PrtMeshLights& ml = hs.ml;
+    const size_t n = ml.power.size();
+    ml.thr.clear();
+    ml.bucket.clear();
+    ml.visible.clear();
+    ml.width.clear();
+    ml.cand_visible.assign(n, 0xFFFFFFFFu);
+    ml.n_search = 0;
+    ml.bucket_shift = 32;
+    ml.n_emitters_unsampled = n_not_similar;
+    double total = 0.0;
+    for (double pw : ml.power) total += pw;  // (the order of the running sum below: C_n = total exactly, T_n = 2^32)
+    std::vector<uint64_t> T(n + 1, 0);
+    if (total > 0.0 && std::isfinite(total)) {
+        double acc = 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            acc += ml.power[i];
+            const double x = std::floor(acc / total * 4294967296.0 + 0.5);
+            T[i + 1] = std::min<uint64_t>((uint64_t)x, 1ull << 32);
+        }
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t wd = T[i + 1] - T[i];
+        ml.records[4 * PRT_LIGHT_F4 * i + 7] = (float)((double)wd / 4294967296.0);
+        if (wd) {
+            ml.cand_visible[i] = (uint32_t)ml.visible.size();
+            ml.visible.push_back((uint32_t)i);
+            ml.width.push_back(wd);
+            ml.n_search = (uint32_t)i + 1u;
+        } else if (ml.power[i] > 0.0) {
+            ++ml.n_emitters_unsampled;
+        }
+    }
+    if (!ml.n_search) return;
+    ml.thr.resize(ml.n_search - 1u);
+    for (uint32_t i = 0; i + 1u < ml.n_search; ++i) ml.thr[i] = (uint32_t)T[i + 1];  // (< 2^32: a non-empty interval follows)
+    // about one bucket per candidate, at most 2^20 (4 MiB): the bucket of r0's top bits brackets the search
+    uint32_t bits = 0;
+    while (bits < 20u && (1u << bits) < ml.n_search) ++bits;
+    ml.bucket_shift = 32u - bits;
+    ml.bucket.resize(((size_t)1 << bits) + 1);
+    uint32_t i = 0;
+    for (size_t b = 0; b < ((size_t)1 << bits); ++b) {
+        const uint64_t r0 = bits ? (uint64_t)b << ml.bucket_shift : 0ull;
+        while (i + 1u < ml.n_search && !(r0 < ml.thr[i])) ++i;
+        ml.bucket[b] = i;
+    }
+    ml.bucket.back() = ml.n_search - 1u;
+}
+
+uint32_t count_not_similar(const PrtHostScene& hs) {
+    // (build_light_table: the analytic emitters it counted; the mesh and placed triangles it counted are candidates here)
+    return hs.n_emitters_unsampled - hs.ml_tris_counted;
+}
+
+// The candidate table of a compiled scene.  w.verts: the world-space meshes as flattened by compile_world_meshes.
+void build_mesh_lights(const PrtSceneDesc* s, PrtHostScene& hs, const Work& w) {
+    PrtMeshLights& ml = hs.ml;
+    ml = PrtMeshLights();
+    auto emissive = [&](uint32_t m) { return m < s->n_materials && s->materials[m].type == PRT_MAT_EMISSIVE; };
+    const size_t n_analytic = hs.lights.size() / (4 * PRT_LIGHT_F4);
+    size_t n = n_analytic;
+    uint32_t prim = (uint32_t)hs.prims.size();
+    for (uint32_t m = 0; m < s->n_meshes; ++m) {
+        const uint32_t nt = s->meshes[m].n_triangles;
+        if (emissive(s->meshes[m].material_id) && nt) {
+            ml.runs.push_back(PrtLightRun{prim, nt, (uint32_t)n, 1u});
+            n += nt;
+        }
+        prim += nt;
+    }
+    for (uint32_t i = 0; i < s->n_instances; ++i) {
+        const PrtInstance& pi = s->instances[i];
+        const uint32_t nt = s->instanced_meshes[pi.mesh].n_triangles;
+        if (emissive(pi.material_id)) {
+            ml.runs.push_back(PrtLightRun{prim, nt, (uint32_t)n, 0u});
+            n += nt;
+        }
+        prim += nt;
+    }
+    ml.records.assign(4 * PRT_LIGHT_F4 * n, 0.0f);
+    ml.power.assign(n, 0.0);
+    std::copy(hs.lights.begin(), hs.lights.end(), ml.records.begin());
+    std::copy(hs.light_power.begin(), hs.light_power.end(), ml.power.begin());
+    for (size_t l = 0; l < n_analytic; ++l) ml.records[4 * PRT_LIGHT_F4 * l + 11] = 0.0f;  // (no float CDF in this table)
+    size_t run = 0;
+    prim = (uint32_t)hs.prims.size();
+    for (uint32_t m = 0; m < s->n_meshes; ++m) {
+        const uint32_t nt = s->meshes[m].n_triangles;
+        if (emissive(s->meshes[m].material_id) && nt) {
+            const PrtLightRun& r = ml.runs[run++];
+            write_tri_candidates(ml, r.light_first, &w.verts[9 * (size_t)(prim - hs.prims.size())], nt, s->materials[s->meshes[m].material_id].rgb, prim);
+        }
+        prim += nt;
+    }
+    std::vector<float> v;
+    for (uint32_t i = 0; i < s->n_instances; ++i) {
+        const PrtInstance& pi = s->instances[i];
+        const PrtMesh& me = s->instanced_meshes[pi.mesh];
+        if (emissive(pi.material_id)) {
+            // world vertices of the copy: Mat * v in double, rounded once (indices and vertices were checked by
+            // build_instanced_meshes)
+            v.resize(9 * (size_t)me.n_triangles);
+            const float* M = pi.mat;
+            for (size_t k = 0; k < 3 * (size_t)me.n_triangles; ++k) {
+                const float* q = &me.positions[3 * (size_t)me.indices[k]];
+                for (int a = 0; a < 3; ++a)
+                    v[3 * k + a] = (float)(((double)M[a] * q[0] + (double)M[4 + a] * q[1]) + ((double)M[8 + a] * q[2] + (double)M[12 + a]));
+            }
+            const PrtLightRun& r = ml.runs[run++];
+            write_tri_candidates(ml, r.light_first, v.data(), me.n_triangles, s->materials[pi.material_id].rgb, prim);
+        }
+        prim += me.n_triangles;
+    }
+    finish_mesh_lights(hs, count_not_similar(hs));
+}
 
 int compile_prims(const PrtSceneDesc* s, PrtHostScene& hs, std::string* err) {
     hs.materials.assign(s->materials, s->materials + s->n_materials);
@@ -613,6 +775,17 @@ int prt_flatten_mesh(const PrtMesh& me, const char* what, uint32_t m, float* ver
     return PRT_OK;
 }
 
+void prt_rebuild_mesh_lights(PrtHostScene* hs, const float* verts) {
+    PrtMeshLights& ml = hs->ml;
+    for (const PrtLightRun& r : ml.runs) {
+        if (!r.world) continue;
+        float rgb[3];
+        memcpy(rgb, &ml.records[4 * PRT_LIGHT_F4 * (size_t)r.light_first + 16], sizeof(rgb));
+        write_tri_candidates(ml, r.light_first, &verts[9 * (size_t)(r.prim_first - hs->prims.size())], r.n_tris, rgb, r.prim_first);
+    }
+    finish_mesh_lights(*hs, count_not_similar(*hs));
+}
+
 int prt_check_scene_arrays(const PrtSceneDesc* s, std::string* err) {
     if ((s->n_materials && !s->materials) || (s->n_primitives && !s->primitives) || (s->n_meshes && !s->meshes) ||
         (s->n_instanced_meshes && !s->instanced_meshes) || (s->n_instances && !s->instances))
@@ -636,6 +809,7 @@ int prt_compile_scene(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHost
     if ((rc = compile_world_meshes(s, opt, hs, w, err))) return rc;
     build_prim_bvh(s, opt, hs);
     if ((rc = compile_instances(s, opt, hs, w, err))) return rc;
+    build_mesh_lights(s, hs, w);
     fill_info(s, opt, hs, w);
     return PRT_OK;
 }

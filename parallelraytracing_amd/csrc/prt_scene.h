@@ -26,6 +26,32 @@ struct PrtSceneScalars {
     float sky[3];
 };
 
+// One emissive world-space mesh or placed copy in the candidate table: its triangles' global primitive indices are
+// [prim_first, prim_first + n_tris) and candidate light_first + k is its face k (DevLightRun, prt_kernels.h, is this struct).
+struct PrtLightRun {
+    uint32_t prim_first, n_tris, light_first, world;  // world: 1 = a world-space mesh (prt_rebuild_mesh_lights rewrites it)
+};
+
+// The light set under PRT_LIGHT_SOURCES_ANALYTIC | PRT_LIGHT_SOURCES_MESH (include/prt.h "Triangle lights"), built with
+// every scene whatever the context's mask.  CANDIDATES, in global primitive order: the analytic lights of
+// PrtHostScene::lights, then every triangle of an Emissive world-space mesh, then every triangle of an Emissive placed
+// copy.  A candidate without power keeps its slot with an empty interval, so that a mesh is one contiguous run and the
+// primitive -> light lookup is one base per run.  The light set proper (`visible`) is the candidates whose interval
+// [T_{i-1}, T_i) is not empty.
+struct PrtMeshLights {
+    std::vector<float> records;      // 4 * PRT_LIGHT_F4 floats per candidate (prt_kernels.h DevLights; triangles: kind 2)
+    std::vector<double> power;       // per candidate; 0: not a light
+    std::vector<uint32_t> thr;       // thr[i] = T_{i+1} for i + 1 < n_search: the search is "smallest i with r0 < thr[i], else n_search - 1"
+    uint32_t n_search = 0;           // 1 + the last candidate with a non-empty interval (every T before it is < 2^32)
+    std::vector<uint32_t> bucket;    // bucket[b] = the candidate picked by r0 = b << bucket_shift; 2^(32 - bucket_shift) + 1 entries
+    uint32_t bucket_shift = 32;
+    std::vector<PrtLightRun> runs;   // ascending prim_first
+    std::vector<uint32_t> visible;   // light of the set -> candidate
+    std::vector<uint32_t> cand_visible;  // candidate -> light of the set, 0xFFFFFFFF for an empty interval
+    std::vector<uint64_t> width;     // per light of the set: T_i - T_{i-1}; pmf = width / 2^32
+    uint32_t n_emitters_unsampled = 0;
+};
+
 struct PrtHostScene {
     std::vector<PrtMaterial> materials;
     std::vector<DevPrim> prims;
@@ -44,6 +70,9 @@ struct PrtHostScene {
     std::vector<float> lights;         // the light table: 4 * PRT_LIGHT_F4 floats per light (prt_kernels.h DevLights)
     std::vector<uint32_t> prim_light;  // per analytic primitive: its light index, 0xFFFFFFFF if not in the light set
     uint32_t n_emitters_unsampled = 0;
+    std::vector<double> light_power;   // per light of `lights`: emitting area x mean(rgb)
+    uint32_t ml_tris_counted = 0;      // the part of n_emitters_unsampled that is mesh / placed triangles
+    PrtMeshLights ml;                  // the light set with emissive triangles in it (PRT_LIGHT_SOURCES_MESH)
 };
 
 // The device-side builder of the 8-wide tree over n triangles given as 9 floats each (+ normals, + a material per
@@ -70,6 +99,11 @@ int prt_check_scene_arrays(const PrtSceneDesc* s, std::string* err);
 // Compiles `s` into *out, of which nothing survives but the storage of its record arrays.  On failure (PRT_ERR_*, message
 // in *err) *out is unspecified.
 int prt_compile_scene(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene* out, std::string* err);
+
+// prt_refit_meshes: the world-space meshes' triangles moved (verts: 9 floats per triangle, mesh and face order, all
+// of them).  Rewrites the records and powers of the world-space runs of hs->ml and every threshold; the
+// result equals what prt_compile_scene builds for the new geometry.  O(candidates) on the host.
+void prt_rebuild_mesh_lights(PrtHostScene* hs, const float* verts);
 
 // One PrtMesh as 9 floats per triangle into verts / norms (n_triangles x 9 each), with the checks every consumer of
 // caller-supplied index buffers needs: indices in range, vertices finite ("<what> <m>: ..." in *err, PRT_ERR_INVALID).

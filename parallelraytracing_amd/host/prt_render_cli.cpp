@@ -2,7 +2,7 @@
 // (src/main.cpp:138-170 builds Film/Scene/Camera and Inits the backends; :504-527 is the frame loop).
 //   prt_render [--preset NAME | --ply FILE [--refine N]] [--width W --height H] [--spp N] [--depth D]
 //              [--seed S] [--camera x y z] [--out PREFIX] [--gpus N | --devices a,b,c] [--sif S] [--frames K]
-//              [--lighting off|nee|mis]
+//              [--lighting off|nee|mis] [--light-sources analytic|all]
 // --gpus N tiles the image over devices 0..N-1 (--devices: any list; a device may repeat, which rehearses the multi-GPU
 // path on one GPU); the frame is gathered to the first device once per frame (RCCL over xGMI, or peer copies).
 // Writes PREFIX.ppm (tonemapped RGBA8 as PPM) and PREFIX.pfm (mean radiance).
@@ -26,6 +26,7 @@ static int preset_id(const std::string& n) {
 int main(int argc, char** argv) {
     std::string preset = "CORNELL", ply, out = "frame";
     uint32_t W = 256, H = 256, spp = 1, depth = 2, seed = 0, refine = 0, sif = 0, frames = 1, lighting = PRT_LIGHTING_OFF;
+    uint32_t light_sources = PRT_LIGHT_SOURCES_ANALYTIC;
     std::vector<int> devices{0};
     float cam[3] = {5.0f, 5.0f, 8.0f};
     bool cam_set = false;
@@ -49,6 +50,12 @@ int main(int argc, char** argv) {
             else if (m == "nee") lighting = PRT_LIGHTING_NEE;
             else if (m == "mis") lighting = PRT_LIGHTING_NEE_MIS;
             else { fprintf(stderr, "--lighting takes off, nee or mis\n"); return 2; }
+        }
+        else if (a == "--light-sources") {
+            const std::string m = next();
+            if (m == "analytic") light_sources = PRT_LIGHT_SOURCES_ANALYTIC;
+            else if (m == "all") light_sources = PRT_LIGHT_SOURCES_ANALYTIC | PRT_LIGHT_SOURCES_MESH;
+            else { fprintf(stderr, "--light-sources takes analytic or all\n"); return 2; }
         }
         else if (a == "--gpus") { const int n = atoi(next()); devices.clear(); for (int d = 0; d < n; ++d) devices.push_back(d); }
         else if (a == "--devices") { devices.clear(); std::string l = next(); for (size_t p = 0; p < l.size();) { size_t e = l.find(',', p); if (e == std::string::npos) e = l.size(); devices.push_back(atoi(l.substr(p, e - p).c_str())); p = e + 1; } }
@@ -82,6 +89,7 @@ int main(int argc, char** argv) {
         r.Init(film, *scene, camera);
         if (sif) r.SetSamplesInFlight(sif);
         if (lighting != PRT_LIGHTING_OFF) r.SetLighting(lighting);
+        if (light_sources != (uint32_t)PRT_LIGHT_SOURCES_ANALYTIC) r.SetLightSources(light_sources);
         if (frames > 1) {  // warm-up frame (first-touch allocations, clocks), then the timed ones
             r.Render(spp);
             r.Clear();

@@ -164,6 +164,8 @@ public:
         const PrtLighting l{mode};
         check(prt_group_set_lighting(grp_, &l));
     }
+    // Which emitters the light set holds: PRT_LIGHT_SOURCES_ANALYTIC (default) or ANALYTIC | MESH (emissive triangles too)
+    void SetLightSources(uint32_t mask) { check(prt_group_set_light_sources(grp_, mask)); }
     PrtLightStats LightStats() {
         PrtLightStats s{};
         check(prt_group_get_light_stats(grp_, &s));

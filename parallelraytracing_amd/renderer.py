@@ -377,6 +377,21 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_set_lighting(self._ctx, C.byref(capi.PrtLighting(m))))
         return m
 
+    def set_light_sources(self, sources) -> int:
+        """Which emitters the light set holds (include/prt.h "Triangle lights"): "analytic" (default) | "all" (analytic
+        emitters + the triangles of emissive meshes and placed copies), or a PRT_LIGHT_SOURCES_* mask."""
+        m = capi.LIGHT_SOURCES[sources] if isinstance(sources, str) else int(sources)
+        self._check(capi.lib().prt_set_light_sources(self._ctx, m))
+        return m
+
+    def light_intervals(self) -> np.ndarray:
+        """With "all": the integer width T_l - T_{l-1} of every light's interval ([n] uint64); pmf = width / 2^32 exactly."""
+        n = C.c_uint32(0)
+        self._check(capi.lib().prt_light_intervals(self._ctx, 0, C.byref(n), None))
+        w = np.zeros(n.value, np.uint64)
+        self._check(capi.lib().prt_light_intervals(self._ctx, n.value, C.byref(n), w.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return w
+
     def light_info(self) -> Tuple[np.ndarray, np.ndarray]:
         """The light set of the current scene: (primitive index [n] uint32, pmf [n] float32).  Host-only contexts too."""
         n = C.c_uint32(0)
@@ -719,6 +734,11 @@ class HipWavefrontGroupRenderer:
     def set_lighting(self, mode) -> int:
         m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
         self._check(capi.lib().prt_group_set_lighting(self._grp, C.byref(capi.PrtLighting(m))))
+        return m
+
+    def set_light_sources(self, sources) -> int:
+        m = capi.LIGHT_SOURCES[sources] if isinstance(sources, str) else int(sources)
+        self._check(capi.lib().prt_group_set_light_sources(self._grp, m))
         return m
 
     def light_info(self) -> Tuple[np.ndarray, np.ndarray]:
