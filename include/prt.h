@@ -95,6 +95,13 @@ typedef struct PrtMesh {
  * through Inv, distance measured in world space.  The transform must be rotation + uniform scale + translation
  * (prt_set_scene rejects anything else): only then is the reference's direction transform a ray transform, so that
  * an acceleration structure in the mesh's space returns what the reference's linear scan returns.
+ * Bounds of that check: the scale must exceed 1e-10 (s^2 > 1e-20) and inv * mat = I must hold to 1e-3 of the largest term of
+ * each entry (absolute 1e-3 where the terms are below 1): (1e-5 of it in the translation column, never below 1e-3): a copy at scale 2^-10 placed 1e4 away passes, one at 2^-40 is
+ * refused with PRT_ERR_INVALID.
+ * Coordinate range: results do not depend on the tree, the builder, a tunable or a refit for any unit of length, as long as
+ * squared distances stay finite, normal binary32 numbers (coordinates between about 2^-60 and 2^60); tested bit for bit against
+ * the linear scan for scales 2^-40 .. 2^40 and offsets up to 1e5 (tests/test_gpu_scale.py).  The
+ * reference's own absolute length remains: a hit needs a ray parameter t >= 1e-3.
  * `mesh` indexes PrtSceneDesc.instanced_meshes (their own material_id is ignored). */
 typedef struct PrtInstance {
     uint32_t mesh;

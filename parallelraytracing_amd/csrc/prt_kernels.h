@@ -17,6 +17,15 @@ struct DevCamera {  // the Camera members GetCameraRay reads (reference: src/cor
     float W, H, tan_fov_y;
 };
 
+// Smallest |component| of a unit direction that the slab tests of every walk divide by (a smaller one, zero included, is
+// replaced by +-PRT_DIR_MIN with its sign).  Conservative: along such an axis the ray moves less than t * 2^-40, and every
+// t that can matter is below 2 (|o|_1 + extent), so the ray stays within 2^-39 (|o|_1 + extent) of its origin, 2^-21 of
+// the per-ray pad 2^-18 (|o|_1 + extent) the planes are moved out by; the slab of a box the ray can hit therefore still
+// contains [0, t].  Scale-free, and the reciprocal is at most 2^40: (coordinate +- pad) * 2^40 and cell * 2^40 stay finite
+// for every coordinate whose squared distances are finite (< 2^63).  (It was 1e-30: (o +- pad) * 1e30 overflowed once a
+// coordinate exceeded 3.4e8, the slab became [-inf, -inf] and the root was culled: DESIGN.md section 0b.)
+#define PRT_DIR_MIN 9.094947017729282e-13f  // 2^-40
+
 struct DevScene {
     const DevPrim* prims;
     const float4* mat_rgbs;     // rgb + scalar

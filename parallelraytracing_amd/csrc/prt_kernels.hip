@@ -526,9 +526,9 @@ PRT_DEV void scan_analytic(const DevScene& sc, f3 o, f3 d, Closest& best, uint32
     // worst-case bound), which a world box padded in proportion to the distance alone would cull.
     const float A1 = __builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z);
     const float pad = sc.pad * (A1 + sc.extent) + ((sc.abvh_q[0] * A1 + sc.abvh_q[1]) * A1 + sc.abvh_q[2]);
-    const float ix = 1.0f / (__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-    const float iy = 1.0f / (__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-    const float iz = 1.0f / (__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+    const float ix = 1.0f / (__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+    const float iy = 1.0f / (__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+    const float iz = 1.0f / (__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
     const float ax = (o.x + pad) * ix, ay = (o.y + pad) * iy, az = (o.z + pad) * iz;
     const float bx = (o.x - pad) * ix, by = (o.y - pad) * iy, bz = (o.z - pad) * iz;
     float tlimit = limit_from_d2(best.d2, pad);
@@ -610,9 +610,9 @@ __device__ __forceinline__ bool classify_ray(const DevScene& sc, f3 o, f3 d, uin
     // producers are VALU-bound: SQ_ACTIVE_INST_VALU x waves per SIMD > 1 for k_shade).
     const f3 ld = d;
     const float pad = sc.pad * (__builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z) + sc.extent);
-    const float ix = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-    const float iy = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-    const float iz = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+    const float ix = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+    const float iy = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+    const float iz = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
     const float x0 = __builtin_fmaf(sc.root_min[0], ix, -(o.x + pad) * ix), x1 = __builtin_fmaf(sc.root_max[0], ix, -(o.x - pad) * ix);
     const float y0 = __builtin_fmaf(sc.root_min[1], iy, -(o.y + pad) * iy), y1 = __builtin_fmaf(sc.root_max[1], iy, -(o.y - pad) * iy);
     const float z0 = __builtin_fmaf(sc.root_min[2], iz, -(o.z + pad) * iz), z1 = __builtin_fmaf(sc.root_max[2], iz, -(o.z - pad) * iz);
@@ -650,9 +650,9 @@ PRT_DEV void traverse_ifif(const DevScene& sc, f3 o, f3 d, Closest& best, uint32
     const f3 ld = normalize3(d);
     // Culling only (never changes a result): per-ray conservative padding of every box by `pad`.
     const float pad = sc.pad * (__builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z) + sc.extent);
-    const float ix = 1.0f / (__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-    const float iy = 1.0f / (__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-    const float iz = 1.0f / (__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+    const float ix = 1.0f / (__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+    const float iy = 1.0f / (__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+    const float iz = 1.0f / (__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
     // plane "min" is moved by -pad, plane "max" by +pad:  t_min = min*inv - (o+pad)*inv, t_max = max*inv - (o-pad)*inv
     const float ax = (o.x + pad) * ix, ay = (o.y + pad) * iy, az = (o.z + pad) * iz;
     const float bx = (o.x - pad) * ix, by = (o.y - pad) * iy, bz = (o.z - pad) * iz;
@@ -745,9 +745,9 @@ PRT_DEV void traverse_ww(const DevScene& sc, f3 o, f3 d, Closest& best, uint32_t
                          uint32_t& n_tris) {
     const f3 ld = normalize3(d);  // TransformNormal(identity, d), primitive.cpp:30
     const float pad = sc.pad * (__builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z) + sc.extent);
-    const float ix = 1.0f / (__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-    const float iy = 1.0f / (__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-    const float iz = 1.0f / (__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+    const float ix = 1.0f / (__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+    const float iy = 1.0f / (__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+    const float iz = 1.0f / (__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
     const float ax = (o.x + pad) * ix, ay = (o.y + pad) * iy, az = (o.z + pad) * iz;
     const float bx = (o.x - pad) * ix, by = (o.y - pad) * iy, bz = (o.z - pad) * iz;
     float tlimit = limit_from_d2(best.d2, pad);
@@ -1111,9 +1111,9 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse_persistent(DevScene sc,
                         o = mk3(O.x, O.y, O.z);
                         ld = normalize3(mk3(D.x, D.y, D.z));  // TransformNormal(identity, d), primitive.cpp:30
                         pad = sc.pad * (__builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z) + sc.extent);
-                        ix = 1.0f / (__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-                        iy = 1.0f / (__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-                        iz = 1.0f / (__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+                        ix = 1.0f / (__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+                        iy = 1.0f / (__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+                        iz = 1.0f / (__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
                         ax = (o.x + pad) * ix; ay = (o.y + pad) * iy; az = (o.z + pad) * iz;
                         bx = (o.x - pad) * ix; by = (o.y - pad) * iy; bz = (o.z - pad) * iz;
                         best.id = hid;
@@ -1310,9 +1310,9 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse4_persistent(DevScene sc
                         o = mk3(O.x, O.y, O.z);
                         ld = normalize3(mk3(D.x, D.y, D.z));  // TransformNormal(identity, d), primitive.cpp:30
                         pad = sc.pad * (__builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z) + sc.extent);
-                        ix = 1.0f / (__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-                        iy = 1.0f / (__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-                        iz = 1.0f / (__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+                        ix = 1.0f / (__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+                        iy = 1.0f / (__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+                        iz = 1.0f / (__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
                         ax = (o.x + pad) * ix; ay = (o.y + pad) * iy; az = (o.z + pad) * iz;
                         bx = (o.x - pad) * ix; by = (o.y - pad) * iy; bz = (o.z - pad) * iz;
                         best.id = hid;
@@ -1922,9 +1922,9 @@ __device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __rest
                     gx = 0u;
                     in_blas = false;
                 }
-                ix = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-                iy = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-                iz = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+                ix = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+                iy = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+                iz = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
                 const bool nx = ix < 0.0f, ny = iy < 0.0f, nz = iz < 0.0f;
                 anx = (nx ? o.x - pad : o.x + pad) * ix; afx = (nx ? o.x + pad : o.x - pad) * ix;
                 any = (ny ? o.y - pad : o.y + pad) * iy; afy = (ny ? o.y + pad : o.y - pad) * iy;
@@ -2015,9 +2015,9 @@ __device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __rest
                 if (r == 1) {  // start the walk of (o, pd): the set-up of a refill
                     ld = normalize3(pd);  // TransformNormal(identity, d), primitive.cpp:30
                     pad = sc.pad * (__builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z) + sc.extent);
-                    ix = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-                    iy = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-                    iz = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+                    ix = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+                    iy = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+                    iz = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
                     const bool nx = ix < 0.0f, ny = iy < 0.0f, nz = iz < 0.0f;
                     anx = (nx ? o.x - pad : o.x + pad) * ix; afx = (nx ? o.x + pad : o.x - pad) * ix;
                     any = (ny ? o.y - pad : o.y + pad) * iy; afy = (ny ? o.y + pad : o.y - pad) * iy;
@@ -2089,9 +2089,9 @@ __device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __rest
                         o = mk3(O.x, O.y, O.z);
                         ld = normalize3(mk3(D.x, D.y, D.z));  // TransformNormal(identity, d), primitive.cpp:30
                         pad = sc.pad * (__builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z) + sc.extent);
-                        ix = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.x) < 1e-30f ? __builtin_copysignf(1e-30f, ld.x) : ld.x);
-                        iy = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.y) < 1e-30f ? __builtin_copysignf(1e-30f, ld.y) : ld.y);
-                        iz = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.z) < 1e-30f ? __builtin_copysignf(1e-30f, ld.z) : ld.z);
+                        ix = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.x) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.x) : ld.x);
+                        iy = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.y) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.y) : ld.y);
+                        iz = __builtin_amdgcn_rcpf(__builtin_fabsf(ld.z) < PRT_DIR_MIN ? __builtin_copysignf(PRT_DIR_MIN, ld.z) : ld.z);
                         // (v_rcp_f32, 1 ulp, instead of IEEE divisions: these reciprocals only feed the box tests, whose
                         // pad of 2^-18 of the coordinates' magnitude is 32x the 2^-23 that costs; the triangle tests use the
                         // ray itself)

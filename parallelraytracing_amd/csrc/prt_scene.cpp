@@ -60,9 +60,17 @@ bool is_similarity(const float* M, const float* inv, double* s2_out) {
     bool ok = gram_is_uniform_scale(M, s2_out);
     for (int r = 0; r < 4 && ok; ++r)
         for (int cc = 0; cc < 4; ++cc) {
-            double acc = 0.0;
-            for (int kk = 0; kk < 4; ++kk) acc += (double)inv[4 * kk + r] * (double)M[4 * cc + kk];
-            if (std::fabs(acc - (r == cc ? 1.0 : 0.0)) > 1e-3) ok = false;
+            // relative to the terms' magnitude: the translation column of inv * mat sums terms of size |t| / s, each known
+            // to fp32 only (a copy at scale 2^-10 placed 1e4 away: terms of 1e7, their rounding alone is 1); for the
+            // rotation part the terms are below 1 and the bound is the absolute 1e-3 it always was, which is also the floor
+            double acc = 0.0, mag = 1.0;
+            for (int kk = 0; kk < 4; ++kk) {
+                const double term = (double)inv[4 * kk + r] * (double)M[4 * cc + kk];
+                acc += term;
+                mag = std::max(mag, std::fabs(term));
+            }
+            // (translation column: 1e-5 of the largest term, 170 x the rounding of an fp32 term)
+            if (!(std::fabs(acc - (r == cc ? 1.0 : 0.0)) <= (cc == 3 ? std::max(1e-3, 1e-5 * mag) : 1e-3 * mag))) ok = false;
         }
     return ok && affine_bottom_row(M);
 }

@@ -172,6 +172,9 @@ class Scene:
         mat, inv = make_transform(scale, euler_deg, translation)
         p.mat[:] = mat.tolist()
         p.inv[:] = inv.tolist()
+        # (scale, euler, translation) the record was made from: a Python-side note for tools that rebuild a scene under another
+        # transform (tests/scale_cases.py); not part of the C record, lost on a copy of it
+        p.srt = (tuple(float(v) for v in scale), tuple(float(v) for v in euler_deg), tuple(float(v) for v in translation))
         self.primitives.append(p)
 
     def AddCircle(self, radius, material, scale=(1, 1, 1), euler_deg=(0, 0, 0), translation=(0, 0, 0)):
@@ -201,6 +204,7 @@ class Scene:
         mat, inv = make_transform(sc, euler_deg, translation)
         inst.mat[:] = mat.tolist()
         inst.inv[:] = inv.tolist()
+        inst.srt = (tuple(float(v) for v in sc), tuple(float(v) for v in euler_deg), tuple(float(v) for v in translation))
         self.instances.append(inst)
         return len(self.instances) - 1
 

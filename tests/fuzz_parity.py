@@ -2,6 +2,8 @@
 """Randomized parity: random scenes (analytic primitives of every material, refined meshes, placed copies), random cameras,
 builders, kernel tunables and sampling flags; every frame bit for bit against the oracle (throughput form) + ray counts.
 --lighting: the same generators with emissive analytic primitives and light sampling, every sample against the float64 replay.
+--scale: scene, camera and rays moved by a (scale, translation) drawn from tests/scale_cases.py's non-extreme table; the oracle
+         then always scans linearly (its own BVH carries absolute pads).
   python tests/fuzz_parity.py --cases 200 --seed 1      (GPU box; ~0.3 s per case)
 Test infrastructure (it calls the oracle): a checker, not a product path; tests/test_gpu_fuzz.py runs a seeded subset."""
 import argparse
@@ -15,6 +17,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import parallelraytracing_amd as prt  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+
+import scale_cases  # noqa: E402
 
 MESHES = {}
 
@@ -67,15 +71,26 @@ def random_scene(rng):
     return sc, ", ".join(desc), kind, world
 
 
-def run_case(case, seed):
+def draw_move(case, seed):
+    """--scale: the (name, s, T) of a case, from a stream of its own (the other draws of the case stay what they are)."""
+    return scale_cases.draw(np.random.default_rng([seed, case, 31337]))
+
+
+def run_case(case, seed, scale=False):
     rng = np.random.default_rng([seed, case])
     scene, desc, kind, _ = random_scene(rng)
     W, H = int(rng.choice([17, 64, 96, 131])), int(rng.choice([9, 48, 72]))
+    if scale and scene.n_triangles > 6000:  # (the oracle scans linearly here: keep its share of the wall time down)
+        W, H = min(W, 64), min(H, 48)
     pos = rng.normal(size=3)
     pos = pos / np.linalg.norm(pos) * rng.uniform(3, 14)
     pos[1] = abs(pos[1]) + 0.3
     front = -pos + rng.uniform(-1, 1, 3)
     cam = prt.Camera(position=tuple(float(v) for v in pos), front=tuple(float(v) for v in front), width=W, height=H)
+    if scale:
+        mname, ms, mT = draw_move(case, seed)
+        scene, cam = scale_cases.move_scene(scene, ms, mT), scale_cases.move_camera(cam, ms, mT)
+        desc += f", moved {mname}"
     depth = int(rng.integers(1, 9))
     spp = int(rng.integers(1, 4))
     rseed = int(rng.integers(0, 1 << 30))
@@ -118,7 +133,8 @@ def run_case(case, seed):
     try:
         r.Init(film, scene, cam)
     except prt.PrtError as e:  # e.g. a tree too deep for the two-level kernel: must be a clean error
-        return f"case {case}: Init refused ({str(e)[:80]}) [{desc}]", True
+        # (a MOVED scene that is refused is a failure: the unmoved one is accepted, and the table is the supported range)
+        return f"case {case}: Init refused ({str(e)[:80]}) [{desc}]", not scale
     sp = None
     if rng.random() < 0.4:
         sp = r.set_sampling(jitter=int(rng.integers(0, 2)), rr_depth=int(rng.choice([0, 1, 3])), clamp=float(rng.choice([0.0, 1.5])))
@@ -129,7 +145,7 @@ def run_case(case, seed):
     osc = orc.OracleScene(scene.desc())
     # small meshes: the oracle scans linearly as the reference does (its own BVH only for the big ones, to stay fast)
     acc, wts, rays = osc.render(cam.desc(), W, H, spp=spp, max_depth=depth, seed=rseed, iterative=True,
-                                use_bvh=scene.n_triangles > 6000, n_threads=8, sampling=sp)
+                                use_bvh=scene.n_triangles > 6000 and not scale, n_threads=8, sampling=sp)
     st = r.stats()
     nbad = int((film.accum != acc).any(axis=-1).sum())
     ok = nbad == 0 and np.array_equal(film.weights, wts) and st.rays_total == rays
@@ -138,12 +154,17 @@ def run_case(case, seed):
     return msg, ok
 
 
-def run_ray_case(case, seed, n=4096):
+def run_ray_case(case, seed, n=4096, scale=False):
     """Closest hit of awkward rays against the oracle's BRUTE-FORCE scan: directions with zero components (infinite slab
     reciprocals), axis-parallel rays inside box planes, origins on vertices / inside the mesh / far away, near-degenerate
     directions; a random scene and builder as above."""
     rng = np.random.default_rng([seed, case, 77])
     scene, desc, kind, world = random_scene(rng)
+    base = scene
+    if scale:
+        mname, ms, mT = draw_move(case, seed)
+        scene = scale_cases.move_scene(base, ms, mT)
+        desc += f", moved {mname}"
     r = prt.HipWavefrontRenderer(device=0, max_depth=2, seed=0)
     params = {}
     if kind != "none" and rng.random() < 0.5:
@@ -173,6 +194,8 @@ def run_ray_case(case, seed, n=4096):
         sel = verts[rng.integers(0, len(verts), size=q)]
         d[6 * q:7 * q] = sel - o[6 * q:7 * q]                   # aimed exactly at mesh vertices (if the mesh is in the scene)
     d = np.stack([prt.glm_normalize(v) if np.any(v != 0) else np.array([0, 0, 1], np.float32) for v in d]).astype(np.float32)
+    if scale:  # (a uniform scale and a translation leave directions alone)
+        o, d = scale_cases.move_rays(o, d, ms, mT)
     got = r.closest_hit(o, d)
     want = orc.OracleScene(scene.desc()).closest_hit(o, d, use_bvh=False, n_threads=8)
     bad = []
@@ -493,14 +516,15 @@ def main():
     ap.add_argument("--rays", action="store_true", help="closest-hit cases with awkward rays against the brute-force scan")
     ap.add_argument("--lighting", action="store_true", help="light-sampled frames against the float64 per-path replay")
     ap.add_argument("--no-render", action="store_true", help="--lighting: the reference side alone (no GPU): redraw rate")
+    ap.add_argument("--scale", action="store_true", help="frames and --rays: move scene, camera and rays by a (scale, translation) of tests/scale_cases.py")
     a = ap.parse_args()
     t0 = time.time()
     bad = 0
     for case in range(a.first, a.first + a.cases):
         msg, ok = (run_lighting_case(case, a.seed, render=not a.no_render)[:2] if a.lighting else
-                   run_ray_case(case, a.seed) if a.rays else run_sequence_case(case, a.seed) if a.sequences else
+                   run_ray_case(case, a.seed, scale=a.scale) if a.rays else run_sequence_case(case, a.seed) if a.sequences else
                    run_graze_case(case, a.seed) if a.graze else
-                   run_graze_quads_case(case, a.seed, cos_lo=a.cos_lo)[:2] if a.graze_quads else run_case(case, a.seed))
+                   run_graze_quads_case(case, a.seed, cos_lo=a.cos_lo)[:2] if a.graze_quads else run_case(case, a.seed, scale=a.scale))
         if not ok:
             bad += 1
         if a.verbose or not ok or "refused" in msg:

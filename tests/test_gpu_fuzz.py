@@ -60,6 +60,22 @@ def test_awkward_rays_against_the_brute_force_scan(first):
     assert bad == []
 
 
+@pytest.mark.parametrize("first", [0])
+def test_random_scenes_and_awkward_rays_moved_across_coordinate_scales(first):
+    """fuzz_parity --scale: the generators above with scene, camera and rays moved by a (scale, translation) drawn from the
+    non-extreme table of tests/scale_cases.py (scales 2^-20 .. 2^20, offsets up to 1e5); the oracle scans linearly (its own
+    BVH has absolute pads).  30 frames + 30 ray cases."""
+    import time
+    t0 = time.time()
+    bad = []
+    for case in range(first, first + 30):
+        for msg, ok in (fuzz.run_case(case, seed=19, scale=True), fuzz.run_ray_case(case, seed=23, n=2048, scale=True)):
+            if not ok:
+                bad.append(msg)
+    print(f"scale fuzz slice: 60 cases in {time.time() - t0:.1f} s", flush=True)
+    assert bad == []
+
+
 def test_grazing_rays_from_far_away_keep_the_reference_spheres_phantom_hits():
     """Circle::Intersect's discriminant b*b - 4*a*c (shape.h:160-163) cancels for a far origin: a ray that passes up to
     ~2e-7 * dist^2 / R OUTSIDE a sphere is still a hit of the reference's arithmetic.  The walk over the primitives' world
