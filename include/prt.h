@@ -307,10 +307,47 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src);
  * src/backend/optix/renderer.cpp:736-871): the scene's world-space meshes again, with NEW positions / normals and the SAME
  * vertex counts, triangle counts and index buffers as at prt_set_scene.  The compressed 8-wide tree keeps its topology; its
  * triangle records are rewritten and its boxes refitted bottom-up and re-quantized on the device.  Scenes with placed
- * copies (PrtInstance) are not refitted (PRT_ERR_INVALID).  After a refit the A/B kernels over the binary / 4-wide
+ * copies (PrtInstance) are not refitted (PRT_ERR_INVALID): their copies move through prt_set_instance_transforms
+ * below, which leaves every mesh tree alone.  After a refit the A/B kernels over the binary / 4-wide
  * trees are unavailable (those trees are dropped).  Results equal a fresh prt_set_scene of the new geometry bit for bit
  * (the closest hit does not depend on the tree); traversal gets slower as the deformation grows. */
 int prt_refit_meshes(PrtContext* ctx, const PrtMesh* meshes, uint32_t n_meshes);
+/* Moving placed copies (rigid-body animation for the price of the top level; the reference's OptiX backend rebuilds its
+ * instance level only when transforms change, src/backend/optix/renderer.cpp:703-871): instances[i] replaces mat / inv of
+ * placed copy i of the current scene.  PRT_ERR_INVALID, with the scene exactly what it was and usable: n is not the
+ * scene's n_instances, a copy's mesh or material_id is not what prt_set_scene got, the scene has no placed copies, a
+ * transform fails prt_set_scene's test (rotation + uniform scale + translation, inv = inverse(mat)), or the new
+ * two-level tree would be too deep for the traversal stack.  Everything is checked before anything is written.
+ *   PRT_INSTANCES_REFIT    the top-level tree keeps its topology: a device pass recomputes every copy's transform
+ *                          record and world box, the top-level boxes are recomputed bottom-up and re-quantized in
+ *                          place.  A box that does not fit its node's grid makes the call fall back to the rebuild.
+ *   PRT_INSTANCES_REBUILD  a new top-level tree over the new boxes from the builder the scene was built with goes in
+ *                          front of the mesh trees; if its node count differs, a device pass rebases the mesh trees'
+ *                          child_base and the instances' root.
+ * Neither mode rebuilds, re-uploads or refits a mesh tree or a triangle record; primitive order and hit ids stay.
+ * The scene-wide bounds, the host copies (prt_bvh_read8, prt_clone_scene) and the triangle lights of placed copies
+ * follow (the light table is uploaded again while the MESH bit is set).  The call waits for the context's stream; film,
+ * camera, sampling, lighting mode, tunables and statistics are not touched.  A host-only context performs the host
+ * rebuild whatever the mode.  Results equal a fresh prt_set_scene of the moved description bit for bit.  A HIP
+ * failure midway leaves the context without a scene. */
+enum { PRT_INSTANCES_REFIT = 0, PRT_INSTANCES_REBUILD = 1 };
+int prt_set_instance_transforms(PrtContext* ctx, const PrtInstance* instances, uint32_t n, uint32_t mode);
+typedef struct PrtInstanceUpdateInfo {
+    uint32_t updates;   /* successful prt_set_instance_transforms calls since the scene was set */
+    uint32_t last_mode; /* what the last one actually ran (a refit that did not fit reports PRT_INSTANCES_REBUILD) */
+    uint32_t top_nodes; /* nodes of the top-level tree now: the first top_nodes nodes of prt_bvh_read8 */
+    uint32_t top_depth; /* its levels */
+    float last_ms;      /* host wall time of the last call, its wait for the device included */
+} PrtInstanceUpdateInfo;
+int prt_instance_update_info(PrtContext* ctx, PrtInstanceUpdateInfo* out);
+/* The instance level of a scene with placed copies, next to prt_bvh_read8: *n_instances = the instances of the top-level
+ * tree (the identity instance of the world-space meshes first, if the scene has any, then the placed copies in input
+ * order) = its leaf slots.  For k < min(capacity, *n_instances), each array that is not null: slot_instance[k] = the
+ * instance in top-level leaf slot k; root[k] = the root node of instance k's mesh tree in prt_bvh_read8; slot_base[k] =
+ * the first triangle record of its mesh in prt_bvh_read; prim_base[k] = the global primitive index of its first
+ * triangle (0 for the world-space meshes, whose records carry their own). */
+int prt_instances_read(PrtContext* ctx, uint32_t capacity, uint32_t* n_instances, uint32_t* slot_instance, uint32_t* root,
+                       uint32_t* slot_base, uint32_t* prim_base);
 int prt_set_camera(PrtContext* ctx, const PrtCameraDesc* cam);
 /* Film::Resize + Clear (src/core/film.cu:11-35) and the image partition of this context:
  * 8x8-pixel tiles, tile t (row-major) belongs to rank t % world_size. */
@@ -467,6 +504,8 @@ PrtContext* prt_group_context(PrtGroup* g, uint32_t rank);   /* per-rank tunable
 int prt_group_set_scene(PrtGroup* g, const PrtSceneDesc* scene);   /* built on rank 0, cloned to the others */
 /* prt_refit_meshes on every rank (each refits the tree on its own device, in parallel; the meshes are read by all ranks). */
 int prt_group_refit_meshes(PrtGroup* g, const PrtMesh* meshes, uint32_t n_meshes);
+/* prt_set_instance_transforms on every rank (each updates the top level on its own device, in parallel). */
+int prt_group_set_instance_transforms(PrtGroup* g, const PrtInstance* instances, uint32_t n, uint32_t mode);
 int prt_group_set_camera(PrtGroup* g, const PrtCameraDesc* cam);
 int prt_group_set_film(PrtGroup* g, uint32_t width, uint32_t height);
 int prt_group_film_clear(PrtGroup* g);

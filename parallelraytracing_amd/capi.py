@@ -104,6 +104,14 @@ class PrtBvhInfo(C.Structure):
                 ("built_on_device", C.c_uint32), ("refit_ms", C.c_float), ("refits", C.c_uint32)]
 
 
+class PrtInstanceUpdateInfo(C.Structure):
+    _fields_ = [("updates", C.c_uint32), ("last_mode", C.c_uint32), ("top_nodes", C.c_uint32), ("top_depth", C.c_uint32),
+                ("last_ms", C.c_float)]
+
+
+# prt_set_instance_transforms modes (include/prt.h PRT_INSTANCES_*)
+INSTANCE_MODES = {"refit": 0, "rebuild": 1}
+
 # numpy dtype mirror of PrtHit (40 bytes)
 HIT_DTYPE = [("prim", "<i4"), ("front_face", "<u4"), ("material_id", "<u4"), ("d2", "<f4"),
              ("position", "<f4", (3,)), ("normal", "<f4", (3,))]
@@ -179,6 +187,10 @@ SIGNATURES = {
     "prt_kernel_instance": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),
     "prt_measure_shade_divergence": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "prt_refit_meshes": (C.c_int, [_vp, C.POINTER(PrtMesh), C.c_uint32]),
+    "prt_set_instance_transforms": (C.c_int, [_vp, C.POINTER(PrtInstance), C.c_uint32, C.c_uint32]),
+    "prt_group_set_instance_transforms": (C.c_int, [_vp, C.POINTER(PrtInstance), C.c_uint32, C.c_uint32]),
+    "prt_instance_update_info": (C.c_int, [_vp, C.POINTER(PrtInstanceUpdateInfo)]),
+    "prt_instances_read": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p]),
     "prt_bvh_read": (C.c_int, [_vp, _fp, _fp]),
     "prt_set_sampling": (C.c_int, [_vp, C.POINTER(PrtSampling)]),
     "prt_bvh_read4": (C.c_int, [_vp, _fp]),

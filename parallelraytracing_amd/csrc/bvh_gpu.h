@@ -40,3 +40,19 @@ int prt_sort_rays(hipStream_t st, const float4* ro, const float4* rd, uint32_t n
 int prt_gpu_bvh8_refit(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
                        const uint32_t* level_start, uint32_t n_levels, const float* d_verts, const float* d_norms, uint32_t n_tris,
                        uint32_t n_prims, float4* d_tris, float4* d_nrms, float root_box[6]);
+
+// ---- moving placed copies (prt_set_instance_transforms); all three enqueue on `st` and return 0 or a hipError_t ----
+// One thread per top-level leaf slot.  d_xf: 32 floats per placed copy (PrtInstance::mat, ::inv); d_inst_mesh[i]: the row
+// of d_mesh_box (6 floats: min, max) instance i takes its box from: its mesh's box in its own space, or, for the n_world
+// (0 | 1) leading identity instance of the world-space meshes, its world box as it is.  d_slot_inst: leaf slot ->
+// instance (n_insts entries).  Writes mat / inv / inv_scale of every placed copy of d_insts (DevInstance) and, into
+// d_recs[3 * slot ..], every instance's world box as the builders' degenerate triangle with the instance in word 3.
+int prt_gpu_place_copies(hipStream_t st, const float* d_xf, const float* d_mesh_box, const uint32_t* d_inst_mesh, const uint32_t* d_slot_inst,
+                         uint32_t n_insts, uint32_t n_world, void* d_insts, float4* d_recs);
+// The refit of prt_gpu_bvh8_refit over records that are already in place (d_recs of prt_gpu_place_copies): boxes
+// bottom-up, nodes re-quantized.  Synchronous.  Returns 0, a hipError_t, or -6 like prt_gpu_bvh8_refit.
+int prt_gpu_bvh8_refit_top(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
+                           const uint32_t* level_start, uint32_t n_levels, const float4* d_recs, float root_box[6]);
+// child_base of nodes [first_node, n_nodes) and root of n_insts instances (DevInstance) grow by delta (mod 2^32).
+int prt_gpu_rebase(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t first_node, uint32_t n_nodes, void* d_insts,
+                   uint32_t n_insts, uint32_t delta);

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "bvh_gpu.h"
+#include "prt_scene_pod.h"
 
 namespace {
 
@@ -1199,10 +1200,9 @@ __global__ void k_refit_boxes(const float4* __restrict__ tris, const uint32_t* _
 }
 }  // namespace
 
-int prt_gpu_bvh8_refit(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
-                       const uint32_t* level_start, uint32_t n_levels, const float* d_verts, const float* d_norms, uint32_t n_tris,
-                       uint32_t n_prims, float4* d_tris, float4* d_nrms, float root_box[6]) {
-    if (n_nodes == 0 || n_tris == 0 || n_levels == 0) return 0;
+// Boxes bottom-up over records that are in place, then the re-quantization: the part of a refit that both callers share
+static int refit_levels(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
+                        const uint32_t* level_start, uint32_t n_levels, const float4* d_tris, float root_box[6]) {
     float *cbox = nullptr, *nbox = nullptr;
     uint32_t *counters = nullptr, *d_list = nullptr;
     auto drop = [&]() {
@@ -1221,11 +1221,10 @@ int prt_gpu_bvh8_refit(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dword
         drop();
         return (int)e;
     }
-    hipLaunchKernelGGL(k_refit_records, dim3((n_tris + 255u) / 256u), dim3(256), 0, st, d_verts, d_norms, n_tris, n_prims, d_tris, d_nrms);
     for (uint32_t l = n_levels; l-- > 0;) {  // deepest level first: a node's internal children are on the next level
         const uint32_t b = level_start[l], en = level_start[l + 1];
         if (en > b)
-            hipLaunchKernelGGL(k_refit_boxes, dim3((en - b + 127u) / 128u), dim3(128), 0, st, (const float4*)d_tris, (const uint32_t*)d_nodes8,
+            hipLaunchKernelGGL(k_refit_boxes, dim3((en - b + 127u) / 128u), dim3(128), 0, st, d_tris, (const uint32_t*)d_nodes8,
                                stride_dwords, cbox, nbox, (const uint32_t*)d_list, b, en);
     }
     hipLaunchKernelGGL(k_quantize, dim3((n_nodes + 127u) / 128u), dim3(128), 0, st, d_nodes8, (const float*)cbox, (const float*)nbox, n_nodes,
@@ -1237,6 +1236,107 @@ int prt_gpu_bvh8_refit(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dword
     drop();
     if (e != hipSuccess) return (int)e;
     return flags[2] ? -6 : 0;  // a box that does not fit its node's 8-bit grid (non-finite or absurdly large coordinates)
+}
+
+int prt_gpu_bvh8_refit(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
+                       const uint32_t* level_start, uint32_t n_levels, const float* d_verts, const float* d_norms, uint32_t n_tris,
+                       uint32_t n_prims, float4* d_tris, float4* d_nrms, float root_box[6]) {
+    if (n_nodes == 0 || n_tris == 0 || n_levels == 0) return 0;
+    hipLaunchKernelGGL(k_refit_records, dim3((n_tris + 255u) / 256u), dim3(256), 0, st, d_verts, d_norms, n_tris, n_prims, d_tris, d_nrms);
+    return refit_levels(st, d_nodes8, stride_dwords, n_nodes, level_nodes, level_start, n_levels, (const float4*)d_tris, root_box);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Moving placed copies (prt_set_instance_transforms): the mesh trees stay, only the top level follows the new transforms.
+//   k_place_copies  one thread per top-level leaf slot: the slot's instance gets its new mat / inv / inv_scale, and its
+//                   world box goes into the slot's record as the degenerate "triangle" the builders take (the host's
+//                   place_copy, prt_scene.cpp, in the same fp32 expressions; -ffp-contract=off here as there)
+//   refit_levels    the top-level nodes' boxes bottom-up from those records, re-quantized in place (topology kept)
+//   k_rebase_*      a rebuilt top level with another node count moved the mesh trees: child_base / root follow
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+__global__ void k_place_copies(const float* __restrict__ xf, const float* __restrict__ mesh_box, const uint32_t* __restrict__ inst_mesh,
+                               const uint32_t* __restrict__ slot_inst, uint32_t n_slots, uint32_t n_world, DevInstance* __restrict__ insts,
+                               float4* __restrict__ recs) {
+    const uint32_t slot = blockIdx.x * 128u + threadIdx.x;
+    if (slot >= n_slots) return;
+    const uint32_t inst = slot_inst[slot];
+    if (inst >= n_slots) return;  // (cannot happen: slot_inst is a permutation of the instances)
+    float mn[3], mx[3];
+    if (inst < n_world) {  // the identity instance of the world-space meshes: its box came along behind the meshes' boxes
+        const float* wb = mesh_box + 6 * (size_t)inst_mesh[inst];
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = wb[a];
+            mx[a] = wb[3 + a];
+        }
+    } else {
+        const float* M = xf + 32 * (size_t)(inst - n_world);  // PrtInstance::mat, ::inv: column-major mat4s
+        const float* b = mesh_box + 6 * (size_t)inst_mesh[inst];
+        DevInstance* I = insts + inst;
+        for (int col = 0; col < 4; ++col)
+            for (int r = 0; r < 3; ++r) {
+                I->mat[col * 3 + r] = M[col * 4 + r];
+                I->inv[col * 3 + r] = M[16 + col * 4 + r];
+            }
+        const double s2 = (double)M[0] * M[0] + (double)M[1] * M[1] + (double)M[2] * M[2];
+        I->inv_scale = (float)(1.0 / sqrt(s2));
+        float mag = 0.0f;
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = 3.402823466e+38f;
+            mx[a] = -3.402823466e+38f;
+        }
+        for (int corner = 0; corner < 8; ++corner) {
+            const float p3[3] = {(corner & 1) ? b[3] : b[0], (corner & 2) ? b[4] : b[1], (corner & 4) ? b[5] : b[2]};
+            for (int a = 0; a < 3; ++a) {
+                const float wv = (M[a] * p3[0] + M[4 + a] * p3[1]) + (M[8 + a] * p3[2] + M[12 + a]);
+                mn[a] = fminf(mn[a], wv);
+                mx[a] = fmaxf(mx[a], wv);
+                mag = fmaxf(mag, fabsf(wv));
+            }
+        }
+        for (int a = 0; a < 3; ++a) {
+            mn[a] -= 1e-5f * (mag + 1e-30f);
+            mx[a] += 1e-5f * (mag + 1e-30f);
+        }
+    }
+    recs[3 * (size_t)slot + 0] = make_float4(mn[0], mn[1], mn[2], __uint_as_float(inst));
+    recs[3 * (size_t)slot + 1] = make_float4(mx[0], mx[1], mx[2], 0.0f);
+    recs[3 * (size_t)slot + 2] = make_float4(mn[0], mx[1], mn[2], 0.0f);
+}
+
+__global__ void k_rebase_nodes(uint32_t* __restrict__ nodes8, uint32_t stride_dwords, uint32_t first, uint32_t n_nodes, uint32_t delta) {
+    const uint32_t nd = first + blockIdx.x * 256u + threadIdx.x;
+    if (nd >= n_nodes) return;
+    nodes8[(size_t)stride_dwords * nd + 4] += delta;
+}
+
+__global__ void k_rebase_roots(DevInstance* __restrict__ insts, uint32_t n, uint32_t delta) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) insts[i].root += delta;
+}
+}  // namespace
+
+int prt_gpu_place_copies(hipStream_t st, const float* d_xf, const float* d_mesh_box, const uint32_t* d_inst_mesh, const uint32_t* d_slot_inst,
+                         uint32_t n_insts, uint32_t n_world, void* d_insts, float4* d_recs) {
+    if (!n_insts) return 0;
+    hipLaunchKernelGGL(k_place_copies, dim3((n_insts + 127u) / 128u), dim3(128), 0, st, d_xf, d_mesh_box, d_inst_mesh, d_slot_inst, n_insts, n_world,
+                       (DevInstance*)d_insts, d_recs);
+    return (int)hipGetLastError();
+}
+
+int prt_gpu_bvh8_refit_top(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
+                           const uint32_t* level_start, uint32_t n_levels, const float4* d_recs, float root_box[6]) {
+    if (n_nodes == 0 || n_levels == 0) return 0;
+    return refit_levels(st, d_nodes8, stride_dwords, n_nodes, level_nodes, level_start, n_levels, d_recs, root_box);
+}
+
+int prt_gpu_rebase(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t first_node, uint32_t n_nodes, void* d_insts,
+                   uint32_t n_insts, uint32_t delta) {
+    if (n_nodes > first_node)
+        hipLaunchKernelGGL(k_rebase_nodes, dim3((n_nodes - first_node + 255u) / 256u), dim3(256), 0, st, d_nodes8, stride_dwords, first_node, n_nodes,
+                           delta);
+    if (n_insts) hipLaunchKernelGGL(k_rebase_roots, dim3((n_insts + 255u) / 256u), dim3(256), 0, st, (DevInstance*)d_insts, n_insts, delta);
+    return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -50,6 +50,7 @@ struct PrtContext {
     bool has_scene = false;
     PrtHostScene hs;                   // the compiled scene (prt_scene.h): every host array the device copies come from
     double refit_ms = 0.0;             // device time of the last prt_refit_meshes (records + boxes + quantization)
+    PrtInstanceUpdateInfo inst_info{}; // prt_set_instance_transforms calls since the scene was set (top_nodes / top_depth: from hs)
     DevScene dsc{};
     void* d_prims = nullptr;
     void* d_mat_rgbs = nullptr;
@@ -713,7 +714,8 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
 // scene compiler works with (prt_scene.h PrtDeviceBuilder); with `keep` the device arrays stay allocated and are handed
 // to the caller.  The builder's time is added to *ms.
 int device_build(PrtContext* c, const float* verts, const float* norms, const uint32_t* tri_mat, uint32_t n, uint32_t n_prims,
-                 std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, PrtGpuBvh* keep, float leaf_cost, double* ms) {
+                 std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, PrtGpuBvh* keep, float leaf_cost, double* ms,
+                 int builder) {
     float cmin[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, cmax[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (size_t t = 0; t < (size_t)n; ++t)
         for (int a = 0; a < 3; ++a) {
@@ -745,7 +747,7 @@ int device_build(PrtContext* c, const float* verts, const float* norms, const ui
     PrtGpuBvh gb{};
     const auto t0 = std::chrono::steady_clock::now();
     // gpu_build 1: the quality builder (PLOC + optimal collapse); 2: the Morton octree (fastest build, slower to traverse)
-    const int brc = c->gpu_build == 2
+    const int brc = builder == 2
                         ? prt_gpu_bvh8_build(c->stream, (const float*)dv, (const float*)dn, (const uint32_t*)dm, n, n_prims, cmin, cmax, &gb)
                         : prt_gpu_bvh8_build_ploc(c->stream, (const float*)dv, (const float*)dn, (const uint32_t*)dm, n, n_prims, cmin, cmax, &gb, leaf_cost);
     *ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -769,6 +771,28 @@ int device_build(PrtContext* c, const float* verts, const float* norms, const ui
     }
     if (e != hipSuccess) return fail(c, PRT_ERR_HIP, "device-side BVH build: %s", hipGetErrorString(e));
     return PRT_OK;
+}
+
+// The nodes of every level of the 8-wide tree whose n_nodes nodes lead the array n8, root first (breadth-first search from
+// node 0: the builders emit their nodes in different orders, none of which a refit relies on).  0, or 1 + the node at
+// which the tree turned out malformed; a tree that does not reach all of its nodes leaves level_nodes short.
+uint32_t tree_levels(const std::vector<uint32_t>& n8, uint32_t n_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_start) {
+    level_nodes.assign(1, 0u);
+    level_start.assign({0u, 1u});
+    level_nodes.reserve(n_nodes);
+    for (;;) {
+        const uint32_t b = level_start[level_start.size() - 2], e = level_start.back();
+        for (uint32_t li = b; li < e; ++li) {
+            const uint32_t nd = level_nodes[li];
+            const uint32_t imask = n8[20 * (size_t)nd + 3] >> 24, child_base = n8[20 * (size_t)nd + 4];
+            const uint32_t kids = (uint32_t)__builtin_popcount(imask);
+            if ((uint64_t)child_base + kids > n_nodes || level_nodes.size() + kids > n_nodes) return nd + 1u;
+            for (uint32_t k = 0; k < kids; ++k) level_nodes.push_back(child_base + k);
+        }
+        if (level_nodes.size() == e) break;
+        level_start.push_back((uint32_t)level_nodes.size());
+    }
+    return 0u;
 }
 
 int check_ready(PrtContext* c) {
@@ -879,7 +903,8 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     if (c->gpu_build && c->has_device)
         opt.device_build = [&](const float* verts, const float* norms, const uint32_t* tri_mat, uint32_t n, uint32_t n_prims, float leaf_cost,
                                bool keep, std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, double* ms, std::string* err) {
-            const int brc = device_build(c, verts, norms, tri_mat, n, n_prims, nodes8, depth, tri_rec, nrm_rec, keep ? &gb : nullptr, leaf_cost, ms);
+            const int brc = device_build(c, verts, norms, tri_mat, n, n_prims, nodes8, depth, tri_rec, nrm_rec, keep ? &gb : nullptr, leaf_cost, ms,
+                                         c->gpu_build);
             if (brc) *err = c->err;
             return brc;
         };
@@ -892,6 +917,8 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     }
     if (rc) return rc;
     c->hs = std::move(hs);
+    c->hs.builder = opt.device_build ? (uint32_t)c->gpu_build : 0u;
+    c->inst_info = PrtInstanceUpdateInfo{};
     if (!c->has_device) {  // host-only context: BVH built, nothing to upload
         fill_dev_scene(c, 0u, 0u);
         c->has_scene = true;
@@ -908,6 +935,7 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     if (dst == src) return PRT_OK;
     dst->has_scene = false;
     dst->hs = src->hs;
+    dst->inst_info = PrtInstanceUpdateInfo{};
     dst->light_sources = src->light_sources;
     if (!dst->has_device) {
         fill_dev_scene(dst, 0u, 0u);
@@ -941,25 +969,12 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     float extent = 0.0f;
     for (size_t m = 0, t = 0; m < n_meshes; t += meshes[m++].n_triangles)
         if ((rc = prt_flatten_mesh(meshes[m], "mesh", (uint32_t)m, verts.data() + 9 * t, norms.data() + 9 * t, &extent, nullptr, nullptr, &c->err))) return rc;
-    // the nodes of every tree level, from the host copy of the tree (breadth-first search from the root: the builders emit
-    // their nodes in different orders, none of which the refit relies on)
+    // the nodes of every tree level, from the host copy of the tree
     const std::vector<uint32_t>& n8 = c->hs.bvh.nodes8;
     const uint32_t n_nodes = (uint32_t)(n8.size() / 20);
-    std::vector<uint32_t> level_nodes{0u}, level_start{0u, 1u};
-    level_nodes.reserve(n_nodes);
-    for (;;) {
-        const uint32_t b = level_start[level_start.size() - 2], e = level_start.back();
-        for (uint32_t li = b; li < e; ++li) {
-            const uint32_t nd = level_nodes[li];
-            const uint32_t imask = n8[20 * (size_t)nd + 3] >> 24, child_base = n8[20 * (size_t)nd + 4];
-            const uint32_t kids = (uint32_t)__builtin_popcount(imask);
-            if ((uint64_t)child_base + kids > n_nodes || level_nodes.size() + kids > n_nodes)
-                return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: malformed tree (node %u)", nd);
-            for (uint32_t k = 0; k < kids; ++k) level_nodes.push_back(child_base + k);
-        }
-        if (level_nodes.size() == e) break;
-        level_start.push_back((uint32_t)level_nodes.size());
-    }
+    std::vector<uint32_t> level_nodes, level_start;
+    if (const uint32_t bad = tree_levels(n8, n_nodes, level_nodes, level_start))
+        return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: malformed tree (node %u)", bad - 1u);
     if (level_nodes.size() != n_nodes) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: %zu of %u nodes reachable from the root", level_nodes.size(), n_nodes);
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     void *dv = nullptr, *dn = nullptr;
@@ -1014,6 +1029,189 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     // triangle lights follow the geometry: the candidate table again from the new vertices (host), uploaded if in use
     prt_rebuild_mesh_lights(&c->hs, verts.data());
     if (mesh_lights_on(c)) return upload_mesh_lights(c);
+    return PRT_OK;
+}
+
+// Rigid-body motion of the placed copies (include/prt.h "Moving placed copies"): only the top level follows.  The host
+// half (checks, instance table, world boxes, host / device build of a new top level, light candidates) is prt_scene.cpp's;
+// this function owns the device half: bvh_gpu.hip's k_place_copies, the top-level refit and the rebase pass.
+int prt_set_instance_transforms(PrtContext* c, const PrtInstance* instances, uint32_t n, uint32_t mode) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (mode != (uint32_t)PRT_INSTANCES_REFIT && mode != (uint32_t)PRT_INSTANCES_REBUILD)
+        return fail(c, PRT_ERR_INVALID, "prt_set_instance_transforms: mode is PRT_INSTANCES_REFIT or PRT_INSTANCES_REBUILD, not %u", mode);
+    int rc = prt_check_instance_update(c->hs, instances, n, &c->err);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    PrtHostScene& hs = c->hs;
+    PrtInstanceUpdate up;
+    prt_instance_tables(hs, instances, &up);
+    PrtSceneOptions opt{c->pad_coeff, c->abvh_enabled != 0, nullptr};
+    const int builder = c->has_device ? (int)hs.builder : 0;
+    if (builder)
+        opt.device_build = [&](const float* verts, const float* norms, const uint32_t* tri_mat, uint32_t nt, uint32_t n_prims, float leaf_cost, bool,
+                               std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, double* ms, std::string* err) {
+            const int brc = device_build(c, verts, norms, tri_mat, nt, n_prims, nodes8, depth, tri_rec, nrm_rec, nullptr, leaf_cost, ms, builder);
+            if (brc) *err = c->err;
+            return brc;
+        };
+    auto done = [&](uint32_t ran) {
+        ++c->inst_info.updates;
+        c->inst_info.last_mode = ran;
+        c->inst_info.last_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return PRT_OK;
+    };
+    if (!c->has_device) {  // host-only context: the host rebuild, whatever the mode
+        if ((rc = prt_build_top_level(opt, hs, &up, &hs.gpu_build_ms, &c->err))) return rc;
+        prt_commit_top_level(&hs, up);
+        prt_commit_instances(&hs, up, instances);
+        fill_dev_scene(c, 0u, 0u);
+        return done(PRT_INSTANCES_REBUILD);
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    // what the device pass reads: the transforms, the mesh boxes (+ the world meshes' world box as the last row), the row
+    // of every instance, and the records it writes
+    const uint32_t n_total = (uint32_t)hs.dev_insts.size(), n_world = hs.n_world_insts, n_meshes = (uint32_t)hs.placed_meshes.size();
+    const uint32_t stride = c->dsc.node_stride, old_top = hs.top_nodes, n_all = (uint32_t)(hs.nodes8_all.size() / 20);
+    std::vector<float> xf(32 * (size_t)n), mesh_box(6 * ((size_t)n_meshes + 1));
+    std::vector<uint32_t> inst_mesh(n_total, n_meshes);
+    for (uint32_t i = 0; i < n; ++i) {
+        memcpy(&xf[32 * (size_t)i], instances[i].mat, 64);
+        memcpy(&xf[32 * (size_t)i + 16], instances[i].inv, 64);
+        inst_mesh[n_world + i] = hs.inst_mesh[i];
+    }
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        memcpy(&mesh_box[6 * (size_t)m], hs.placed_meshes[m].mn, 12);
+        memcpy(&mesh_box[6 * (size_t)m + 3], hs.placed_meshes[m].mx, 12);
+    }
+    memcpy(&mesh_box[6 * (size_t)n_meshes], hs.world_box.data(), 24);
+    void *d_xf = nullptr, *d_box = nullptr, *d_im = nullptr, *d_recs = nullptr, *d_new = nullptr;
+    auto drop = [&]() {
+        (void)hipFree(d_xf);
+        (void)hipFree(d_box);
+        (void)hipFree(d_im);
+        (void)hipFree(d_recs);
+    };
+    auto up_to = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess && src && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    hipError_t e = up_to(&d_xf, xf.data(), xf.size() * 4);
+    if (e == hipSuccess) e = up_to(&d_box, mesh_box.data(), mesh_box.size() * 4);
+    if (e == hipSuccess) e = up_to(&d_im, inst_mesh.data(), inst_mesh.size() * 4);
+    if (e == hipSuccess) e = up_to(&d_recs, nullptr, 48 * (size_t)n_total);
+    if (e != hipSuccess) {  // (nothing of the scene written yet)
+        drop();
+        return fail(c, PRT_ERR_HIP, "prt_set_instance_transforms: %s", hipGetErrorString(e));
+    }
+    auto broken = [&](hipError_t he, int brc) {
+        drop();
+        (void)hipFree(d_new);
+        c->has_scene = false;  // the device arrays may be half rewritten
+        return fail(c, PRT_ERR_HIP, "prt_set_instance_transforms: %s (%d)", he != hipSuccess ? hipGetErrorString(he) : "device pass failed", brc);
+    };
+    const size_t node_bytes = (size_t)stride * 16;
+    bool top_dirty = false;  // the device's top level no longer matches the host copy
+    if (mode == (uint32_t)PRT_INSTANCES_REFIT) {
+        std::vector<uint32_t> level_nodes, level_start;
+        if (tree_levels(hs.nodes8_all, old_top, level_nodes, level_start) || level_nodes.size() != old_top) {
+            drop();
+            return fail(c, PRT_ERR_INVALID, "prt_set_instance_transforms: malformed top-level tree");
+        }
+        int brc = prt_gpu_place_copies(c->stream, (const float*)d_xf, (const float*)d_box, (const uint32_t*)d_im, (const uint32_t*)c->d_tlas_inst,
+                                       n_total, n_world, c->d_insts, (float4*)d_recs);
+        float root_box[6];
+        if (!brc)
+            brc = prt_gpu_bvh8_refit_top(c->stream, (uint32_t*)c->d_nodes8, stride * 4u, old_top, level_nodes.data(), level_start.data(),
+                                         (uint32_t)level_start.size() - 1u, (const float4*)d_recs, root_box);
+        if (brc && brc != -6) return broken(hipSuccess, brc);
+        if (!brc) {
+            prt_commit_instances(&hs, up, instances);
+            // the host copies follow the device: the re-quantized top level and the instance table
+            e = hipMemcpy2D(hs.nodes8_all.data(), 80, c->d_nodes8, node_bytes, 80, old_top, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(hs.dev_insts.data(), c->d_insts, (size_t)n_total * sizeof(DevInstance), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return broken(e, 0);
+            drop();
+            fill_dev_scene(c, stride, hs.bvh_info.depth8);
+            if (mesh_lights_on(c) && (rc = upload_mesh_lights(c))) return rc;
+            return done(PRT_INSTANCES_REFIT);
+        }
+        top_dirty = true;  // a box did not fit its node's grid: a new topology it is
+    }
+    rc = prt_build_top_level(opt, hs, &up, &hs.gpu_build_ms, &c->err);
+    if (rc) {
+        if (top_dirty) {  // the scene stays what it was: the refit's half-written top level and instances go back
+            e = hipMemcpy2D(c->d_nodes8, node_bytes, hs.nodes8_all.data(), 80, 80, old_top, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(c->d_insts, hs.dev_insts.data(), (size_t)n_total * sizeof(DevInstance), hipMemcpyHostToDevice);
+            if (e != hipSuccess) return broken(e, 0);
+        }
+        drop();
+        return rc;
+    }
+    const uint32_t new_top = (uint32_t)(up.top_nodes8.size() / 20), delta = new_top - old_top, new_all = n_all - old_top + new_top;
+    uint32_t* d_n8 = (uint32_t*)c->d_nodes8;
+    if (delta) {  // the mesh trees move behind the new top level, device to device
+        e = hipMalloc(&d_new, node_bytes * new_all);
+        if (e == hipSuccess && stride != 5u) e = hipMemset(d_new, 0, node_bytes * new_top);
+        if (e == hipSuccess)
+            e = hipMemcpy((char*)d_new + node_bytes * new_top, (const char*)c->d_nodes8 + node_bytes * old_top, node_bytes * (n_all - old_top),
+                          hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {  // (the scene is still whole unless the refit wrote to it)
+            if (top_dirty) return broken(e, 0);
+            drop();
+            (void)hipFree(d_new);
+            return fail(c, PRT_ERR_HIP, "prt_set_instance_transforms: %s", hipGetErrorString(e));
+        }
+        d_n8 = (uint32_t*)d_new;
+    }
+    e = hipMemcpy2D(d_n8, node_bytes, up.top_nodes8.data(), 80, 80, new_top, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->d_tlas_inst, up.top_order.data(), (size_t)n_total * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();  // (copies on the null stream return early; the kernels run on c->stream)
+    if (e != hipSuccess) return broken(e, 0);
+    int brc = prt_gpu_place_copies(c->stream, (const float*)d_xf, (const float*)d_box, (const uint32_t*)d_im, (const uint32_t*)c->d_tlas_inst, n_total,
+                                   n_world, c->d_insts, (float4*)d_recs);
+    if (!brc && delta) brc = prt_gpu_rebase(c->stream, d_n8, stride * 4u, new_top, new_all, c->d_insts, n_total, delta);
+    e = hipStreamSynchronize(c->stream);
+    if (brc || e != hipSuccess) return broken(e, brc);
+    if (delta) {
+        (void)hipFree(c->d_nodes8);
+        c->d_nodes8 = d_new;
+        d_new = nullptr;
+    }
+    prt_commit_top_level(&hs, up);
+    prt_commit_instances(&hs, up, instances);
+    e = hipMemcpy(hs.dev_insts.data(), c->d_insts, (size_t)n_total * sizeof(DevInstance), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return broken(e, 0);
+    drop();
+    fill_dev_scene(c, stride, hs.bvh_info.depth8);
+    if (mesh_lights_on(c) && (rc = upload_mesh_lights(c))) return rc;
+    return done(PRT_INSTANCES_REBUILD);
+}
+
+int prt_instance_update_info(PrtContext* c, PrtInstanceUpdateInfo* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    *out = c->inst_info;
+    out->top_nodes = c->hs.top_nodes;
+    out->top_depth = c->hs.top_depth;
+    return PRT_OK;
+}
+
+int prt_instances_read(PrtContext* c, uint32_t capacity, uint32_t* n_instances, uint32_t* slot_instance, uint32_t* root, uint32_t* slot_base,
+                       uint32_t* prim_base) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    const uint32_t n = (uint32_t)c->hs.dev_insts.size();
+    if (n_instances) *n_instances = n;
+    for (uint32_t k = 0; k < n && k < capacity; ++k) {
+        const DevInstance& I = c->hs.dev_insts[k];
+        if (slot_instance) slot_instance[k] = c->hs.tlas_inst[k];
+        if (root) root[k] = I.root;
+        if (slot_base) slot_base[k] = I.slot_base;
+        if (prim_base) prim_base[k] = I.prim_base;
+    }
     return PRT_OK;
 }
 

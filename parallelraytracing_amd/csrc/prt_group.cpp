@@ -264,6 +264,11 @@ int prt_group_refit_meshes(PrtGroup* g, const PrtMesh* meshes, uint32_t n_meshes
     return for_each_rank(g, [&](uint32_t r) { return prt_refit_meshes(g->ctx[r], meshes, n_meshes); });
 }
 
+int prt_group_set_instance_transforms(PrtGroup* g, const PrtInstance* instances, uint32_t n, uint32_t mode) {
+    if (!g || g->ctx.empty()) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_instance_transforms(g->ctx[r], instances, n, mode); });
+}
+
 int prt_group_set_camera(PrtGroup* g, const PrtCameraDesc* cam) {
     if (!g) return PRT_ERR_INVALID;
     return for_each_rank(g, [&](uint32_t r) { return prt_set_camera(g->ctx[r], cam); }, false);

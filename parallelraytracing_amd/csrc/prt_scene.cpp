@@ -570,6 +570,32 @@ int build_instanced_meshes(const PrtSceneDesc* s, const PrtSceneOptions& opt, Pr
     return PRT_OK;
 }
 
+// mat / inv / inv_scale of one placed copy (s2: scale^2 of its checked transform) and its world box: the 8 corners of its
+// mesh's box through Mat, widened by a relative slack for the fp32 rounding of Mat * p anywhere inside the box.  The
+// device pass of prt_set_instance_transforms (bvh_gpu.hip k_place_copies) evaluates the same fp32 expressions.
+void place_copy(const PrtInstance& pi, double s2, const float* bmn, const float* bmx, DevInstance* I, std::array<float, 6>* box) {
+    const float* M = pi.mat;
+    to_dev_mat(pi.mat, I->mat);
+    to_dev_mat(pi.inv, I->inv);
+    I->inv_scale = (float)(1.0 / std::sqrt(s2));
+    std::array<float, 6> bx{FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
+    float mag = 0.0f;
+    for (int corner = 0; corner < 8; ++corner) {
+        const float p3[3] = {(corner & 1) ? bmx[0] : bmn[0], (corner & 2) ? bmx[1] : bmn[1], (corner & 4) ? bmx[2] : bmn[2]};
+        for (int a = 0; a < 3; ++a) {
+            const float wv = (M[a] * p3[0] + M[4 + a] * p3[1]) + (M[8 + a] * p3[2] + M[12 + a]);
+            bx[a] = std::min(bx[a], wv);
+            bx[3 + a] = std::max(bx[3 + a], wv);
+            mag = std::max(mag, std::fabs(wv));
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        bx[a] -= 1e-5f * (mag + 1e-30f);
+        bx[3 + a] += 1e-5f * (mag + 1e-30f);
+    }
+    *box = bx;
+}
+
 // The instance table, [identity instance of the world-space meshes] + the placed copies (root = mesh index for now), and
 // every instance's world box
 int build_instance_table(const PrtSceneDesc* s, PrtHostScene& hs, const Work& w, const std::vector<Blas>& blas,
@@ -593,6 +619,7 @@ int build_instance_table(const PrtSceneDesc* s, PrtHostScene& hs, const Work& w,
         I.extent = d.extent;
         hs.dev_insts.push_back(I);
         boxes.push_back({d.root_min[0], d.root_min[1], d.root_min[2], d.root_max[0], d.root_max[1], d.root_max[2]});
+        hs.world_box = boxes.back();
     }
     uint32_t virt = w.n_world, prim = d.n_prims + w.n_world;
     for (uint32_t i = 0; i < s->n_instances; ++i) {
@@ -600,7 +627,6 @@ int build_instance_table(const PrtSceneDesc* s, PrtHostScene& hs, const Work& w,
         if (pi.mesh >= s->n_instanced_meshes) return fail(err, "instance %u: mesh out of range", i);
         if (pi.material_id >= s->n_materials) return fail(err, "instance %u: material out of range", i);
         // rotation + uniform scale + translation only: transpose(M3) * M3 = s^2 * I, and inv * mat = I
-        const float* M = pi.mat;
         double s2 = 0.0;
         if (!is_similarity(pi.mat, pi.inv, &s2))
             return fail(err,
@@ -608,58 +634,38 @@ int build_instance_table(const PrtSceneDesc* s, PrtHostScene& hs, const Work& w,
                         "(the reference's local ray, primitive.cpp:29-30, is only a ray transform for those)", i);
         const Blas& B = blas[pi.mesh];
         DevInstance I{};
-        to_dev_mat(pi.mat, I.mat);
-        to_dev_mat(pi.inv, I.inv);
+        std::array<float, 6> bx;
+        place_copy(pi, s2, B.mn, B.mx, &I, &bx);
         I.slot_base = B.slot_base;
         I.prim_base = prim;
         I.virt_base = virt;
         I.material = pi.material_id;
         I.n_tris = B.n_tris;
-        I.inv_scale = (float)(1.0 / std::sqrt(s2));
         I.extent = B.extent;
         I.root = pi.mesh;  // mesh index for now; node base in assemble_two_level
         hs.dev_insts.push_back(I);
+        hs.inst_mesh.push_back(pi.mesh);
         virt += B.n_tris;
         prim += B.n_tris;
-        // world box: the 8 corners of the mesh box through Mat, widened by a relative slack for the fp32 rounding
-        // of Mat * p anywhere inside the box
-        std::array<float, 6> bx{FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
-        float mag = 0.0f;
-        for (int corner = 0; corner < 8; ++corner) {
-            const float p3[3] = {(corner & 1) ? B.mx[0] : B.mn[0], (corner & 2) ? B.mx[1] : B.mn[1], (corner & 4) ? B.mx[2] : B.mn[2]};
-            for (int a = 0; a < 3; ++a) {
-                const float wv = (M[a] * p3[0] + M[4 + a] * p3[1]) + (M[8 + a] * p3[2] + M[12 + a]);
-                bx[a] = std::min(bx[a], wv);
-                bx[3 + a] = std::max(bx[3 + a], wv);
-                mag = std::max(mag, std::fabs(wv));
-            }
-        }
-        for (int a = 0; a < 3; ++a) {
-            bx[a] -= 1e-5f * (mag + 1e-30f);
-            bx[3 + a] += 1e-5f * (mag + 1e-30f);
-        }
         boxes.push_back(bx);
     }
     if ((uint64_t)virt + d.n_prims >= 0xFFFFFFF0ull) return fail(err, "too many placed triangles");
     return PRT_OK;
 }
 
-// The top-level tree over the instances' world boxes and the scene's one node array: [top level][world meshes' tree]
-// [instanced meshes' trees], child_base / tri_base made absolute, every instance's root set
-int assemble_two_level(const PrtSceneOptions& opt, PrtHostScene& hs, Work& w, std::vector<Blas>& blas, const std::vector<std::array<float, 6>>& boxes,
-                       std::string* err) {
-    // the same builders over one degenerate "triangle" per instance that spans its world box
-    const uint32_t n_inst_total = (uint32_t)hs.dev_insts.size();
+// The top-level tree over the instances' world boxes, by the same builders over one degenerate "triangle" per instance
+// that spans its world box; order: leaf slot -> instance
+int build_top_level(const PrtSceneOptions& opt, const std::vector<std::array<float, 6>>& boxes, BvhBuild& top, double* gpu_ms, std::string* err) {
+    const uint32_t n_inst_total = (uint32_t)boxes.size();
     std::vector<float> pv(9 * (size_t)n_inst_total);
     for (uint32_t i = 0; i < n_inst_total; ++i) box_triangle(&boxes[i][0], &boxes[i][3], &pv[9 * (size_t)i]);
-    BvhBuild top;
     std::vector<float> rec(12 * (size_t)n_inst_total);
     bool on_device = false;
     // (device builder: an instance in a hit leaf is ENTERED, a level switch of ~150 instructions, without a box test of its
     // own: a leaf cost this high makes the optimisation put every instance into a leaf of its own wherever the boxes
     // differ; copies whose boxes coincide may still share a leaf, which costs a redundant entry, never a result)
     const int rc = build_tree(opt, TreeInput{pv.data(), nullptr, nullptr, n_inst_total, 0u}, 64.0f, false, 0xFFFFFFFFu, false, 1, &top, rec.data(),
-                              nullptr, &on_device, &hs.gpu_build_ms, err);
+                              nullptr, &on_device, gpu_ms, err);
     if (rc == kPrtDeviceBuildGaveUp) return fail(err, "top-level tree: the device builder gave up; use gpu_build = 0 for this scene");
     if (rc == kHostBuildFailed || (!rc && !on_device && top.nodes8.empty())) return fail(err, "top-level BVH construction failed");
     if (rc) return rc;
@@ -667,6 +673,16 @@ int assemble_two_level(const PrtSceneOptions& opt, PrtHostScene& hs, Work& w, st
         top.order.resize(n_inst_total);
         for (uint32_t sl = 0; sl < n_inst_total; ++sl) memcpy(&top.order[sl], &rec[12 * (size_t)sl + 3], 4);
     }
+    return PRT_OK;
+}
+
+// The top-level tree over the instances' world boxes and the scene's one node array: [top level][world meshes' tree]
+// [instanced meshes' trees], child_base / tri_base made absolute, every instance's root set
+int assemble_two_level(const PrtSceneOptions& opt, PrtHostScene& hs, Work& w, std::vector<Blas>& blas, const std::vector<std::array<float, 6>>& boxes,
+                       std::string* err) {
+    BvhBuild top;
+    const int rc = build_top_level(opt, boxes, top, &hs.gpu_build_ms, err);
+    if (rc) return rc;
     hs.tlas_inst = top.order;
     hs.nodes8_all = top.nodes8;
     uint32_t max_blas_depth = 0;
@@ -696,7 +712,38 @@ int assemble_two_level(const PrtSceneOptions& opt, PrtHostScene& hs, Work& w, st
     if (top.depth8 + max_blas_depth > 12u)
         return fail(err, "two-level BVH too deep for the traversal stack (%u + %u > 12)", top.depth8, max_blas_depth);
     w.depth8 = top.depth8 + max_blas_depth;
+    // what prt_set_instance_transforms starts from
+    hs.n_world_insts = w.n_world ? 1u : 0u;
+    hs.top_nodes = (uint32_t)(top.nodes8.size() / 20);
+    hs.top_depth = top.depth8;
+    hs.max_mesh_depth = max_blas_depth;
+    for (const Blas& B : blas) {
+        PrtPlacedMesh pm{};
+        memcpy(pm.mn, B.mn, sizeof(pm.mn));
+        memcpy(pm.mx, B.mx, sizeof(pm.mx));
+        pm.slot_base = B.slot_base;
+        pm.node_base = B.node_base;
+        pm.depth8 = B.bvh.depth8;
+        pm.n_tris = B.n_tris;
+        hs.placed_meshes.push_back(pm);
+    }
     return PRT_OK;
+}
+
+// root_min / root_max / extent of a scene with placed copies from its instances' world boxes
+void scene_bounds(PrtHostScene& hs, const std::vector<std::array<float, 6>>& boxes) {
+    PrtSceneScalars& d = hs.sc;
+    d.extent = hs.extent_base;
+    for (int a = 0; a < 3; ++a) {
+        d.root_min[a] = FLT_MAX;
+        d.root_max[a] = -FLT_MAX;
+    }
+    for (const std::array<float, 6>& bx : boxes)
+        for (int a = 0; a < 3; ++a) {
+            d.root_min[a] = std::min(d.root_min[a], bx[a]);
+            d.root_max[a] = std::max(d.root_max[a], bx[3 + a]);
+            d.extent = std::max(d.extent, std::max(std::fabs(bx[a]), std::fabs(bx[3 + a])));
+        }
 }
 
 // Placed mesh copies (PrtInstance): one tree per instanced mesh in its own space + a top-level tree over the copies'
@@ -713,16 +760,8 @@ int compile_instances(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHost
     if ((rc = assemble_two_level(opt, hs, w, blas, boxes, err))) return rc;
     // scene-wide quantities the producers use
     PrtSceneScalars& d = hs.sc;
-    for (int a = 0; a < 3; ++a) {
-        d.root_min[a] = FLT_MAX;
-        d.root_max[a] = -FLT_MAX;
-    }
-    for (const std::array<float, 6>& bx : boxes)
-        for (int a = 0; a < 3; ++a) {
-            d.root_min[a] = std::min(d.root_min[a], bx[a]);
-            d.root_max[a] = std::max(d.root_max[a], bx[3 + a]);
-            d.extent = std::max(d.extent, std::max(std::fabs(bx[a]), std::fabs(bx[3 + a])));
-        }
+    hs.extent_base = d.extent;
+    scene_bounds(hs, boxes);
     d.n_insts = (uint32_t)hs.dev_insts.size();
     d.n_nodes = std::max(d.n_nodes, 1u);  // "the scene has a BVH"
     d.n_tris = (uint32_t)slots;
@@ -783,15 +822,108 @@ int prt_flatten_mesh(const PrtMesh& me, const char* what, uint32_t m, float* ver
     return PRT_OK;
 }
 
-void prt_rebuild_mesh_lights(PrtHostScene* hs, const float* verts) {
+void prt_rebuild_mesh_lights(PrtHostScene* hs, const float* verts, const PrtInstance* placed) {
     PrtMeshLights& ml = hs->ml;
+    std::vector<float> v;
+    size_t copy = 0;  // (runs and copies both ascend in prim_first / prim_base)
     for (const PrtLightRun& r : ml.runs) {
-        if (!r.world) continue;
+        if (r.world ? !verts : !placed) continue;
         float rgb[3];
         memcpy(rgb, &ml.records[4 * PRT_LIGHT_F4 * (size_t)r.light_first + 16], sizeof(rgb));
-        write_tri_candidates(ml, r.light_first, &verts[9 * (size_t)(r.prim_first - hs->prims.size())], r.n_tris, rgb, r.prim_first);
+        if (r.world) {
+            write_tri_candidates(ml, r.light_first, &verts[9 * (size_t)(r.prim_first - hs->prims.size())], r.n_tris, rgb, r.prim_first);
+            continue;
+        }
+        while (copy < hs->inst_mesh.size() && hs->dev_insts[hs->n_world_insts + copy].prim_base != r.prim_first) ++copy;
+        if (copy == hs->inst_mesh.size()) break;  // (cannot happen: every placed run is one copy)
+        // world vertices of the copy as build_mesh_lights forms them: Mat * v in double, rounded once.  The mesh's
+        // vertices in face order come from its triangle records (word 3 of a record: the face)
+        const PrtPlacedMesh& pm = hs->placed_meshes[hs->inst_mesh[copy]];
+        const float* M = placed[copy].mat;
+        v.assign(9 * (size_t)pm.n_tris, 0.0f);
+        for (size_t sl = 0; sl < (size_t)pm.n_tris; ++sl) {
+            const float* rec = &hs->tri_records[12 * ((size_t)pm.slot_base + sl)];
+            uint32_t face = 0;
+            memcpy(&face, &rec[3], 4);
+            if (face >= pm.n_tris) continue;
+            for (int k = 0; k < 3; ++k) {
+                const float* q = &rec[4 * k];
+                for (int a = 0; a < 3; ++a)
+                    v[9 * (size_t)face + 3 * k + a] = (float)(((double)M[a] * q[0] + (double)M[4 + a] * q[1]) + ((double)M[8 + a] * q[2] + (double)M[12 + a]));
+            }
+        }
+        write_tri_candidates(ml, r.light_first, v.data(), pm.n_tris, rgb, r.prim_first);
     }
     finish_mesh_lights(*hs, count_not_similar(*hs));
+}
+
+int prt_check_instance_update(const PrtHostScene& hs, const PrtInstance* instances, uint32_t n, std::string* err) {
+    if (hs.inst_mesh.empty()) return fail(err, "prt_set_instance_transforms: the scene has no placed copies");
+    if (n != hs.inst_mesh.size()) return fail(err, "prt_set_instance_transforms: the scene has %zu placed copies, not %u", hs.inst_mesh.size(), n);
+    if (!instances) return fail(err, "null instance array");
+    for (uint32_t i = 0; i < n; ++i) {
+        const PrtInstance& pi = instances[i];
+        if (pi.mesh != hs.inst_mesh[i] || pi.material_id != hs.dev_insts[hs.n_world_insts + i].material)
+            return fail(err, "prt_set_instance_transforms: copy %u has another mesh or material than at prt_set_scene", i);
+        double s2 = 0.0;
+        if (!is_similarity(pi.mat, pi.inv, &s2))
+            return fail(err, "instance %u: the transform must be rotation + uniform scale + translation with inv = inverse(mat)", i);
+    }
+    return PRT_OK;
+}
+
+void prt_instance_tables(const PrtHostScene& hs, const PrtInstance* instances, PrtInstanceUpdate* up) {
+    up->insts = hs.dev_insts;
+    up->boxes.clear();
+    if (hs.n_world_insts) {  // the identity instance of the world meshes: their box, as prt_compile_scene left it
+        up->boxes.push_back(hs.world_box);
+    }
+    for (size_t i = 0; i < hs.inst_mesh.size(); ++i) {
+        const PrtPlacedMesh& pm = hs.placed_meshes[hs.inst_mesh[i]];
+        double s2 = 0.0;
+        (void)is_similarity(instances[i].mat, instances[i].inv, &s2);
+        std::array<float, 6> bx;
+        place_copy(instances[i], s2, pm.mn, pm.mx, &up->insts[hs.n_world_insts + i], &bx);
+        up->boxes.push_back(bx);
+    }
+}
+
+int prt_build_top_level(const PrtSceneOptions& opt, const PrtHostScene& hs, PrtInstanceUpdate* up, double* gpu_ms, std::string* err) {
+    BvhBuild top;
+    const int rc = build_top_level(opt, up->boxes, top, gpu_ms, err);
+    if (rc) return rc;
+    if (top.depth8 + hs.max_mesh_depth > 12u)
+        return fail(err, "two-level BVH too deep for the traversal stack (%u + %u > 12)", top.depth8, hs.max_mesh_depth);
+    up->top_nodes8 = std::move(top.nodes8);
+    up->top_order = std::move(top.order);
+    up->top_depth = top.depth8;
+    return PRT_OK;
+}
+
+void prt_commit_top_level(PrtHostScene* hs, const PrtInstanceUpdate& up) {
+    const uint32_t n_new = (uint32_t)(up.top_nodes8.size() / 20), delta = n_new - hs->top_nodes;  // (mod 2^32)
+    std::vector<uint32_t> all(up.top_nodes8);
+    all.insert(all.end(), hs->nodes8_all.begin() + 20 * (ptrdiff_t)hs->top_nodes, hs->nodes8_all.end());
+    for (size_t k = up.top_nodes8.size(); k < all.size() && delta; k += 20) all[k + 4] += delta;
+    hs->nodes8_all.swap(all);
+    for (DevInstance& I : hs->dev_insts) I.root += delta;
+    for (PrtPlacedMesh& pm : hs->placed_meshes) pm.node_base += delta;
+    hs->tlas_inst = up.top_order;
+    hs->top_nodes = n_new;
+    hs->top_depth = up.top_depth;
+    hs->bvh_info.n_nodes8 = (uint32_t)(hs->nodes8_all.size() / 20);
+    hs->bvh_info.depth8 = up.top_depth + hs->max_mesh_depth;
+}
+
+void prt_commit_instances(PrtHostScene* hs, const PrtInstanceUpdate& up, const PrtInstance* instances) {
+    for (size_t i = hs->n_world_insts; i < hs->dev_insts.size(); ++i) {
+        DevInstance& I = hs->dev_insts[i];
+        memcpy(I.mat, up.insts[i].mat, sizeof(I.mat));
+        memcpy(I.inv, up.insts[i].inv, sizeof(I.inv));
+        I.inv_scale = up.insts[i].inv_scale;
+    }
+    scene_bounds(*hs, up.boxes);
+    prt_rebuild_mesh_lights(hs, nullptr, instances);
 }
 
 int prt_check_scene_arrays(const PrtSceneDesc* s, std::string* err) {

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <array>
 #include <functional>
 #include <string>
 #include <vector>
@@ -52,6 +53,15 @@ struct PrtMeshLights {
     uint32_t n_emitters_unsampled = 0;
 };
 
+// One instanced mesh of a compiled scene: what moving its copies needs to know about it (prt_update_instances)
+struct PrtPlacedMesh {
+    float mn[3], mx[3];  // its box in its own space
+    uint32_t slot_base;  // first triangle slot of its records
+    uint32_t node_base;  // its tree's root in nodes8_all
+    uint32_t depth8;     // levels of its tree
+    uint32_t n_tris;
+};
+
 struct PrtHostScene {
     std::vector<PrtMaterial> materials;
     std::vector<DevPrim> prims;
@@ -64,6 +74,15 @@ struct PrtHostScene {
     std::vector<uint32_t> nodes8_all;  // scenes with placed mesh copies: top-level tree + every mesh's tree
     std::vector<DevInstance> dev_insts;
     std::vector<uint32_t> tlas_inst;   // top-level leaf slot -> instance
+    std::vector<PrtPlacedMesh> placed_meshes;  // per instanced mesh (scenes with placed copies)
+    std::vector<uint32_t> inst_mesh;   // per placed copy: its instanced mesh
+    std::array<float, 6> world_box{};  // the world box of that identity instance
+    uint32_t n_world_insts = 0;        // 1: dev_insts[0] is the identity instance of the world-space meshes
+    uint32_t top_nodes = 0;            // nodes of the top-level tree: nodes8_all[0 .. 20 * top_nodes)
+    uint32_t top_depth = 0;            // its levels
+    uint32_t max_mesh_depth = 0;       // levels of the deepest tree below it
+    float extent_base = 0.0f;          // sc.extent before the copies' world boxes went into it
+    uint32_t builder = 0;              // prt_set_param("gpu_build") the scene was built with (set by the C-ABI layer)
     BvhBuild abvh;                     // BVH over the analytic primitives' world boxes (scenes with many of them)
     PrtBvhInfo bvh_info{};
     PrtSceneScalars sc{};
@@ -101,9 +120,33 @@ int prt_check_scene_arrays(const PrtSceneDesc* s, std::string* err);
 int prt_compile_scene(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHostScene* out, std::string* err);
 
 // prt_refit_meshes: the world-space meshes' triangles moved (verts: 9 floats per triangle, mesh and face order, all
-// of them).  Rewrites the records and powers of the world-space runs of hs->ml and every threshold; the
-// result equals what prt_compile_scene builds for the new geometry.  O(candidates) on the host.
-void prt_rebuild_mesh_lights(PrtHostScene* hs, const float* verts);
+// of them; null: they stayed).  prt_set_instance_transforms: the placed copies moved (placed: the scene's n_instances
+// copies with their new transforms; null: they stayed).  Rewrites the records and powers of the runs that moved and every
+// threshold; the result equals what prt_compile_scene builds for the new geometry.  O(candidates) on the host.
+void prt_rebuild_mesh_lights(PrtHostScene* hs, const float* verts, const PrtInstance* placed = nullptr);
+
+// ---- moving placed copies (prt_set_instance_transforms) ----
+// What an update works out before anything of the scene is written.
+struct PrtInstanceUpdate {
+    std::vector<DevInstance> insts;               // the whole instance table with the new mat / inv / inv_scale (root: as in the scene)
+    std::vector<std::array<float, 6>> boxes;      // every instance's world box (build_instance_table's rule)
+    std::vector<uint32_t> top_nodes8, top_order;  // prt_build_top_level: the new top-level tree (child_base from 0) and slot -> instance
+    uint32_t top_depth = 0;
+};
+
+// The checks of prt_set_instance_transforms: the scene has placed copies, n is their number, mesh and material of every
+// copy are what prt_set_scene got, every transform passes prt_set_scene's test (PRT_ERR_INVALID, message in *err).
+int prt_check_instance_update(const PrtHostScene& hs, const PrtInstance* instances, uint32_t n, std::string* err);
+// insts / boxes of `up` for checked transforms.
+void prt_instance_tables(const PrtHostScene& hs, const PrtInstance* instances, PrtInstanceUpdate* up);
+// A new top-level tree over up->boxes with the builder prt_compile_scene used, into `up`; PRT_ERR_INVALID if it would be
+// too deep for the traversal stack.  *gpu_ms grows by the device builder's time.  The scene is not written.
+int prt_build_top_level(const PrtSceneOptions& opt, const PrtHostScene& hs, PrtInstanceUpdate* up, double* gpu_ms, std::string* err);
+// The tree of prt_build_top_level goes in front of the mesh trees of hs->nodes8_all (their child_base and the instances'
+// root rebased if the node count changed), tlas_inst, depths and bvh_info follow.  Before prt_commit_instances.
+void prt_commit_top_level(PrtHostScene* hs, const PrtInstanceUpdate& up);
+// dev_insts (root stays), the scene-wide bounds and the placed copies' triangle lights follow the new transforms.
+void prt_commit_instances(PrtHostScene* hs, const PrtInstanceUpdate& up, const PrtInstance* instances);
 
 // One PrtMesh as 9 floats per triangle into verts / norms (n_triangles x 9 each), with the checks every consumer of
 // caller-supplied index buffers needs: indices in range, vertices finite ("<what> <m>: ..." in *err, PRT_ERR_INVALID).

@@ -63,6 +63,29 @@ public:
         meshes.push_back(PrtMesh{prt_mesh_positions(m), prt_mesh_normals(m), prt_mesh_indices(m), prt_mesh_vertex_count(m),
                                  prt_mesh_triangle_count(m), material});
     }
+    // A mesh that is placed, not flattened (PrtInstance): returns its index for AddInstance
+    uint32_t AddInstancedMeshPly(const std::string& path) {
+        PrtMeshData* m = nullptr;
+        char err[256] = {0};
+        if (prt_mesh_load_ply(path.c_str(), &m, err, sizeof(err))) throw Error(std::string("PLY: ") + err);
+        owned_.push_back(m);
+        instanced_meshes.push_back(PrtMesh{prt_mesh_positions(m), prt_mesh_normals(m), prt_mesh_indices(m), prt_mesh_vertex_count(m),
+                                           prt_mesh_triangle_count(m), 0u});
+        return (uint32_t)instanced_meshes.size() - 1;
+    }
+    // A placed copy (uniform scale only); SetInstanceTransform moves it, HipWavefrontRenderer::UpdateInstances follows
+    uint32_t AddInstance(uint32_t mesh, uint32_t material, float scale, const float euler_deg[3], const float translation[3]) {
+        PrtInstance in{};
+        in.mesh = mesh;
+        in.material_id = material;
+        instances.push_back(in);
+        SetInstanceTransform((uint32_t)instances.size() - 1, scale, euler_deg, translation);
+        return (uint32_t)instances.size() - 1;
+    }
+    void SetInstanceTransform(uint32_t i, float scale, const float euler_deg[3], const float translation[3]) {
+        const float sc[3] = {scale, scale, scale};
+        prt_make_transform(sc, euler_deg, translation, instances.at(i).mat, instances.at(i).inv);
+    }
     PrtSceneDesc desc() const {
         PrtSceneDesc d{};
         d.materials = materials.data();
@@ -74,11 +97,17 @@ public:
         d.sky[0] = sky[0];
         d.sky[1] = sky[1];
         d.sky[2] = sky[2];
+        d.instanced_meshes = instanced_meshes.data();
+        d.instances = instances.data();
+        d.n_instanced_meshes = (uint32_t)instanced_meshes.size();
+        d.n_instances = (uint32_t)instances.size();
         return d;
     }
     std::vector<PrtMaterial> materials;
     std::vector<PrtPrimitive> primitives;
     std::vector<PrtMesh> meshes;
+    std::vector<PrtMesh> instanced_meshes;
+    std::vector<PrtInstance> instances;
     float sky[3] = {0.4f, 0.3f, 0.6f};  // src/backend/cpu/renderer.h:31
 
 private:
@@ -156,6 +185,17 @@ public:
     void Render(uint32_t spp) {
         check(prt_group_render(grp_, spp, max_depth_, seed_, frame_));
         frame_ += spp;
+    }
+    // The placed copies of `scene` moved (Scene::SetInstanceTransform): every GPU's top level follows, no mesh tree is
+    // rebuilt and the film is not cleared.  mode: PRT_INSTANCES_REFIT (topology kept) / PRT_INSTANCES_REBUILD
+    void UpdateInstances(const Scene& scene, uint32_t mode = PRT_INSTANCES_REFIT) {
+        check(prt_group_set_instance_transforms(grp_, scene.instances.data(), (uint32_t)scene.instances.size(), mode));
+    }
+    PrtInstanceUpdateInfo InstanceUpdateInfo(uint32_t rank = 0) {
+        PrtInstanceUpdateInfo info{};
+        PrtContext* c = prt_group_context(grp_, rank);
+        if (prt_instance_update_info(c, &info)) throw Error(std::string("prt_instance_update_info: ") + prt_last_error(c));
+        return info;
     }
     void SetSamplesInFlight(uint32_t n) { check(prt_group_set_samples_in_flight(grp_, n)); }
     void SetParam(const char* name, int value) { check(prt_group_set_param(grp_, name, value)); }

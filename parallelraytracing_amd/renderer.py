@@ -208,6 +208,16 @@ class Scene:
         self.instances.append(inst)
         return len(self.instances) - 1
 
+    def SetInstanceTransform(self, i: int, scale=1.0, euler_deg=(0, 0, 0), translation=(0, 0, 0)):
+        """Placed copy `i` (the index AddInstance returned) gets a new transform; arguments as for AddInstance.  A renderer
+        initialised with this scene follows through UpdateInstances (no rebuild of any mesh tree)."""
+        inst = self.instances[i]
+        sc = (scale, scale, scale) if np.isscalar(scale) else scale
+        mat, inv = make_transform(sc, euler_deg, translation)
+        inst.mat[:] = mat.tolist()
+        inst.inv[:] = inv.tolist()
+        inst.srt = (tuple(float(v) for v in sc), tuple(float(v) for v in euler_deg), tuple(float(v) for v in translation))
+
     @property
     def n_triangles(self) -> int:
         return (sum(m.n_triangles for m, _ in self.meshes)
@@ -620,6 +630,28 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_refit_meshes(self._ctx, d.meshes, d.n_meshes))
         self._scene = scene
 
+    def UpdateInstances(self, scene: "Scene", mode: str = "refit"):
+        """prt_set_instance_transforms: `scene`'s placed copies carry new transforms (Scene.SetInstanceTransform) over the
+        meshes and materials the renderer was initialised with.  mode "refit" keeps the top-level tree's topology and
+        refits it on the device, "rebuild" builds a new top level; no mesh tree is touched, the film is not cleared."""
+        insts = (PrtInstance * max(1, len(scene.instances)))(*scene.instances)
+        self._check(capi.lib().prt_set_instance_transforms(self._ctx, insts, len(scene.instances), capi.INSTANCE_MODES[mode]))
+        self._scene = scene
+
+    def instance_update_info(self) -> "capi.PrtInstanceUpdateInfo":
+        info = capi.PrtInstanceUpdateInfo()
+        self._check(capi.lib().prt_instance_update_info(self._ctx, C.byref(info)))
+        return info
+
+    def instances_read(self) -> dict:
+        """prt_instances_read: slot_instance, root, slot_base, prim_base, one uint32 per instance of the top-level tree."""
+        n = C.c_uint32(0)
+        L = capi.lib()
+        self._check(L.prt_instances_read(self._ctx, 0, C.byref(n), None, None, None, None))
+        out = {k: np.zeros(n.value, np.uint32) for k in ("slot_instance", "root", "slot_base", "prim_base")}
+        self._check(L.prt_instances_read(self._ctx, n.value, C.byref(n), *[out[k].ctypes.data_as(_u32p) for k in out]))
+        return out
+
     def measure_shade_divergence(self, sample: int = 0) -> np.ndarray:
         """prt_measure_shade_divergence: [max_depth, 16] counters of the material mix per wave of the shade kernel."""
         out = np.zeros((self.max_depth, 16), np.uint64)
@@ -715,6 +747,18 @@ class HipWavefrontGroupRenderer:
         d = scene.desc()
         scene._keep = d
         self._check(capi.lib().prt_group_refit_meshes(self._grp, d.meshes, d.n_meshes))
+
+    def UpdateInstances(self, scene: Scene, mode: str = "refit"):
+        """prt_group_set_instance_transforms: every rank moves its copy of the top level to `scene`'s new transforms."""
+        insts = (PrtInstance * max(1, len(scene.instances)))(*scene.instances)
+        self._check(capi.lib().prt_group_set_instance_transforms(self._grp, insts, len(scene.instances), capi.INSTANCE_MODES[mode]))
+
+    def instance_update_info(self, rank: int = 0) -> "capi.PrtInstanceUpdateInfo":
+        info = capi.PrtInstanceUpdateInfo()
+        L = capi.lib()
+        if L.prt_instance_update_info(L.prt_group_context(self._grp, int(rank)), C.byref(info)):
+            raise PrtError(f"prt_instance_update_info failed on rank {rank}")
+        return info
 
     def ProgressiveRender(self, spp: int = 1):
         self._check(capi.lib().prt_group_render(self._grp, spp, self.max_depth, self.seed, self.frame_index))
