@@ -164,7 +164,7 @@ typedef struct PrtSampling {
  *  Weights: NEE_MIS: power heuristic, w_L = pL^2 / (pL^2 + pB^2), pL = pmf * pdf_w, pB = max(0, n.w) / pi; a scattered
  *    segment from a Lambertian vertex that hits a light-set emitter counts its emission at w_B = 1 - w_L for that pair
  *    of vertices.  NEE: w_L = 1, w_B = 0 except w_B = 1 where pL = 0.  Emission seen from the camera or after a metal /
- *    dielectric vertex keeps weight 1; the sky is never sampled.
+ *    dielectric vertex keeps weight 1; the constant sky is never sampled (an environment image is: "Environment light").
  *  RNG: the light sample draws from pcg_hash(state at the vertex + a constant of its own) and never advances the path's
  *    own state, so the scattered path, its segments and rays_per_depth are draw for draw those of lighting OFF. */
 enum { PRT_LIGHTING_OFF = 0, PRT_LIGHTING_NEE_MIS = 1, PRT_LIGHTING_NEE = 2 };
@@ -210,6 +210,52 @@ typedef struct PrtLightStats {
  *  n_emitters_unsampled then counts analytic emitters with a non-similarity transform plus candidates with positive
  *    power and an empty interval. */
 enum { PRT_LIGHT_SOURCES_ANALYTIC = 1, PRT_LIGHT_SOURCES_MESH = 2 }; /* bit mask */
+/* Environment light (prt_set_environment; NULL = the constant `sky`, bit for bit the behaviour above).  A lat-long
+ * image of radiance, piecewise constant (nearest texel), a property of the context like the lighting mode and the light
+ * source mask: set before or after prt_set_scene, kept across it, copied by prt_clone_scene, host-only contexts too (they
+ * only build the tables).  While it is set PrtSceneDesc.sky is ignored.
+ *  Lookup of a unit direction d: phi = atan2f(d.z, d.x), u = phi / (2 pi) + 0.5, column j = min(W - 1, floor(u W));
+ *    theta = acosf(clamp(d.y, -1, 1)), v = theta / pi, row i = min(H - 1, floor(v H)).  Every miss delivers
+ *    thr * env[i][j] where it delivered thr * sky: camera rays, scattered rays, and the segments the producers end
+ *    themselves because they cannot hit a triangle; the clamp applies as before.
+ *  Distribution (host, double): texel weight w_ij = mean(rgb_ij) Omega_i, Omega_i = (2 pi / W) (cos(pi i / H) -
+ *    cos(pi (i + 1) / H)).  Row thresholds R_i = floor(sum_{k <= i} sum_j w_kj / total * 2^32 + 0.5) as 64-bit integers
+ *    (R_H = 2^32); per row, column thresholds C_ij the same way from w_ij over the row's sum.  Texel pmf
+ *    p_ij = (R_i - R_{i-1}) (C_ij - C_{i,j-1}) / 2^64 exactly.  A texel or row with an empty interval is never sampled
+ *    (pmf 0); an all-black map has no distribution.
+ *  Selection: T_e = floor(light_share 2^32 + 0.5); T_e = 2^32 if the current light set is empty; T_e = 0 if the map has
+ *    no distribution or light_share is 0.  r_e = pcg_hash(key + PRT_ENV_RNG) (key: the path's state at the vertex): the
+ *    environment is sampled iff r_e < T_e, otherwise the selection above runs unchanged (default and threshold rule).
+ *    Every other light's pmf is multiplied by (2^32 - T_e) / 2^32 in double and rounded once to fp32: the number the
+ *    estimator, the MIS weights and prt_light_info use.  prt_light_intervals reports the exact product: while T_e > 0,
+ *    width[l] = (T_l - T_{l-1}) (2^32 - T_e) and pmf = width / 2^64; with T_e = 0 the factor is exactly 1 and nothing
+ *    changes (width in units of 2^-32).
+ *  Sample (the light stream, pcg_hash(key + its constant), stepped by pcg_hash): row = smallest i with s1 < R_i, column =
+ *    smallest j with s2 < C_ij (s1, s2: the 32-bit states after the first and second step), u1, u2 = the top 24 bits of the
+ *    states after the third and fourth step.  u = (j + u1) / W, v = (i + u2) / H, phi = 2 pi u - pi, theta = pi v,
+ *    w = (sin theta cos phi, cos theta, sin theta sin phi).  Le = env[i][j] (no second lookup), pdf_w = p_ij W H /
+ *    (2 pi^2 sin theta) (0 where sin theta = 0), pL = (T_e / 2^32) pdf_w, shadow ray (x, w) with tmax = +inf.  Where
+ *    samples are taken, estimator, clamp, throughput before roulette, power heuristic: as for the other lights.
+ *  Miss after a Lambertian vertex: weighted w_B = 1 / (1 + (pL / pB)^2), pL at the texel the lookup of d gives with
+ *    sin theta = sqrt(max(0, 1 - d.y^2)) (evaluated as (1 - d.y)(1 + d.y)); NEE: 0 where pL > 0, else 1.  Misses seen from the camera or after a metal /
+ *    dielectric vertex keep weight 1.  Lighting OFF, or T_e = 0: the environment is just the radiance of a miss.
+ *  Results do not depend on a tunable: with an environment set every batch takes the unfused pipeline. */
+#define PRT_ENV_RNG 0x3C6EF372u          /* the environment-or-lights draw: pcg_hash(path state at the vertex + this) */
+#define PRT_LIGHT_ENVIRONMENT 0xFFFFFFFEu /* prt_sample_light's `light` for an environment sample */
+#define PRT_ENV_MAX_WIDTH 16384u
+#define PRT_ENV_MAX_HEIGHT 8192u
+typedef struct PrtEnvironment {
+    const float* rgb;      /* height*width*3 floats, row 0 = +Y pole (top), copied */
+    uint32_t width, height;
+    float light_share;     /* probability that a light sample goes to the environment, [0,1]; 0: never sampled */
+} PrtEnvironment;
+typedef struct PrtEnvironmentInfo {
+    uint32_t is_set;       /* 0: the constant sky (everything else is 0 then) */
+    uint32_t width, height;
+    uint32_t n_sampled;    /* texels with a non-empty interval (0: no distribution) */
+    uint64_t t_env;        /* T_e for the current scene and light source mask */
+    float light_share;
+} PrtEnvironmentInfo;
 
 /* Closest-hit record of one ray (what Scene::Intersect returns, src/core/surface_interaction.h:6-13,
  * plus the winning primitive index and the world distance^2 the reference minimises,
@@ -378,6 +424,19 @@ int prt_get_light_stats(PrtContext* ctx, PrtLightStats* out);
  * the MESH bit is set.  prt_refit_meshes with the MESH bit set rebuilds that table on the host from the new vertices
  * and uploads it again: O(candidates), about 90 bytes per candidate over the bus, not part of the reported refit time. */
 int prt_set_light_sources(PrtContext* ctx, uint32_t mask);
+/* The environment light ("Environment light" above).  PRT_ERR_INVALID, with the previous environment intact: width or
+ * height 0, width > PRT_ENV_MAX_WIDTH, height > PRT_ENV_MAX_HEIGHT, a null image, a negative or non-finite texel,
+ * light_share outside [0, 1] (NaN included).  Waits for the context's stream; the light tables are uploaded again when
+ * T_e changed. */
+int prt_set_environment(PrtContext* ctx, const PrtEnvironment* env);
+int prt_environment_info(PrtContext* ctx, PrtEnvironmentInfo* out);
+/* The exact interval widths: row_width[i] = R_i - R_{i-1} (H entries), col_width[i * W + j] = C_ij - C_{i,j-1} (H * W
+ * entries; a row without weight has none).  Either may be NULL.  Host-only contexts too; no environment or no
+ * distribution: PRT_ERR_INVALID. */
+int prt_environment_intervals(PrtContext* ctx, uint64_t* row_width, uint64_t* col_width);
+/* The render's own device lookup for n unit directions (host arrays, each output may be NULL): rgb (3 floats),
+ * texel = i * W + j, pdf_w = the solid-angle density with which the environment sample picks that direction (without T_e). */
+int prt_environment_eval(PrtContext* ctx, uint32_t n, const float* dirs, float* rgb, uint32_t* texel, float* pdf_w);
 /* The exact pmf of the current light set: width[l] = T_l - T_{l-1}, pmf = width / 2^32 (prt_light_info's float is this
  * number rounded).  With the default mask there are no thresholds: PRT_ERR_INVALID. */
 int prt_light_intervals(PrtContext* ctx, uint32_t capacity, uint32_t* n_lights, uint64_t* width);
@@ -390,7 +449,8 @@ int prt_light_info(PrtContext* ctx, uint32_t capacity, uint32_t* n_lights, uint3
  * pdf_light = pmf * pdf_w, pdf_bsdf = max(0, n.w) / pi, w_light under the context's lighting mode (OFF is taken as
  * NEE_MIS), and w_bsdf: the weight a scattered segment from the same vertex along the same direction gets when it meets
  * that light (the render's own evaluation; 1 - w_light up to rounding).  hits[i].normal is the shading normal as
- * prt_closest_hit returns it (flipped to the incoming side). */
+ * prt_closest_hit returns it (flipped to the incoming side).  An environment sample reports light =
+ * PRT_LIGHT_ENVIRONMENT, tmax = +inf and w_bsdf = the weight of a miss along that direction. */
 int prt_sample_light(PrtContext* ctx, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,
                      float* shadow_dirs, float* tmax, uint32_t* light, float* contrib, float* pdf_light, float* pdf_bsdf,
                      float* w_light, float* w_bsdf);
@@ -513,6 +573,7 @@ int prt_group_set_sampling(PrtGroup* g, const PrtSampling* s);
 int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n);
 int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l);
 int prt_group_set_light_sources(PrtGroup* g, uint32_t mask);
+int prt_group_set_environment(PrtGroup* g, const PrtEnvironment* env);   /* on every rank */
 /* shadow-ray counts summed over the ranks; n_lights / n_emitters_unsampled as rank 0 has them */
 int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out);
 int prt_group_set_param(PrtGroup* g, const char* name, int value);
@@ -556,6 +617,10 @@ void prt_make_transform(const float scale[3], const float euler_deg[3], const fl
 /* Offline framebuffer dump (stands in for the GLFW/OpenGL viewer, src/main.cpp:504-527). */
 int prt_write_ppm(const char* path, const uint8_t* rgba8, uint32_t width, uint32_t height);
 int prt_write_pfm(const char* path, const float* rgb, uint32_t width, uint32_t height);
+/* Colour PFM ("PF", either byte order; stored bottom-to-top, returned top-to-bottom, width*height*3 floats to be released
+ * with prt_image_free).  Greyscale files, bad headers, short bodies, sizes beyond 2^28 pixels: PRT_ERR_IO. */
+int prt_read_pfm(const char* path, float** rgb, uint32_t* width, uint32_t* height);
+void prt_image_free(float* rgb);
 
 #ifdef __cplusplus
 }

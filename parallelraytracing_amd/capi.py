@@ -90,6 +90,18 @@ class PrtLightStats(C.Structure):
                 ("n_emitters_unsampled", C.c_uint32)]
 
 
+class PrtEnvironment(C.Structure):
+    _fields_ = [("rgb", C.POINTER(C.c_float)), ("width", C.c_uint32), ("height", C.c_uint32), ("light_share", C.c_float)]
+
+
+class PrtEnvironmentInfo(C.Structure):
+    _fields_ = [("is_set", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("n_sampled", C.c_uint32),
+                ("t_env", C.c_uint64), ("light_share", C.c_float)]
+
+
+LIGHT_ENVIRONMENT = 0xFFFFFFFE  # PRT_LIGHT_ENVIRONMENT
+ENV_RNG = 0x3C6EF372            # PRT_ENV_RNG
+
 # PrtLighting.mode (include/prt.h)
 LIGHTING_MODES = {"off": 0, "mis": 1, "nee": 2}
 # prt_set_light_sources masks (include/prt.h PRT_LIGHT_SOURCES_*)
@@ -154,6 +166,13 @@ SIGNATURES = {
     "prt_group_set_light_sources": (C.c_int, [_vp, C.c_uint32]),
     "prt_set_light_sources": (C.c_int, [_vp, C.c_uint32]),
     "prt_light_intervals": (C.c_int, [_vp, C.c_uint32, _u32p, C.POINTER(C.c_uint64)]),
+    "prt_set_environment": (C.c_int, [_vp, C.POINTER(PrtEnvironment)]),
+    "prt_group_set_environment": (C.c_int, [_vp, C.POINTER(PrtEnvironment)]),
+    "prt_environment_info": (C.c_int, [_vp, C.POINTER(PrtEnvironmentInfo)]),
+    "prt_environment_intervals": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "prt_environment_eval": (C.c_int, [_vp, C.c_uint32, _fp, _fp, _u32p, _fp]),
+    "prt_read_pfm": (C.c_int, [C.c_char_p, C.POINTER(_fp), _u32p, _u32p]),
+    "prt_image_free": (None, [_fp]),
     "prt_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),
     "prt_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
     "prt_light_info": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _fp]),

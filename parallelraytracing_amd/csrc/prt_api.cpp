@@ -135,6 +135,14 @@ struct PrtContext {
     PrtLightBufs lb{};                 // shadow rays, pdf of the previous scatter, light radiance: cap_light paths each
     uint64_t cap_light = 0;
     unsigned long long* d_light_stats = nullptr;  // [slot][shadow rays, occluded], since prt_reset_stats
+
+    // ---- environment light (PrtEnvironment, include/prt.h): a property of the context, kept across scenes ----
+    PrtEnvTables env;                  // W = 0: the constant sky
+    void* d_env_texels = nullptr;
+    void* d_env_row = nullptr;
+    void* d_env_col = nullptr;
+    void* d_env_last = nullptr;
+    uint64_t t_env_dev = 0;            // the T_e the pmfs of the light tables on the device are scaled with
 };
 
 namespace {
@@ -262,6 +270,59 @@ uint32_t light_set_size(const PrtContext* c) {
     return mesh_lights_on(c) ? (uint32_t)c->hs.ml.visible.size() : (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4));
 }
 
+// ---- environment light ----
+bool env_on(const PrtContext* c) { return c->env.W != 0u; }
+// T_e for the current scene and light source mask (no scene: an empty light set)
+uint64_t env_threshold(const PrtContext* c) { return prt_environment_threshold(c->env, light_set_size(c)); }
+
+DevEnv dev_env(const PrtContext* c) {
+    const uint64_t te = env_threshold(c);
+    return DevEnv{(const float4*)c->d_env_texels, (const uint32_t*)c->d_env_row, (const uint32_t*)c->d_env_col,
+                  (const uint32_t*)c->d_env_last, c->env.W, c->env.H, c->env.row_last, (uint32_t)te, te == 4294967296ull ? 1u : 0u,
+                  (float)((double)te / 4294967296.0)};
+}
+
+void free_env(PrtContext* c) {
+    free_dev(c->d_env_texels);
+    free_dev(c->d_env_row);
+    free_dev(c->d_env_col);
+    free_dev(c->d_env_last);
+}
+
+// c->env onto the device (prt_set_environment, prt_clone_scene)
+int upload_env(PrtContext* c) {
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    free_env(c);
+    if (!env_on(c)) return PRT_OK;
+    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    HIPCHECK(c, up(&c->d_env_texels, c->env.texels.data(), c->env.texels.size() * 4));
+    HIPCHECK(c, up(&c->d_env_row, c->env.row_thr.data(), c->env.row_thr.size() * 4));
+    HIPCHECK(c, up(&c->d_env_col, c->env.col_thr.data(), c->env.col_thr.size() * 4));
+    HIPCHECK(c, up(&c->d_env_last, c->env.col_last.data(), c->env.col_last.size() * 4));
+    return PRT_OK;
+}
+
+// The pmfs of the light tables on the device carry the factor (2^32 - T_e) / 2^32 (include/prt.h "Environment light"):
+// rewrites both tables in place from the host copies when T_e is not what they were scaled with.
+int sync_light_tables(PrtContext* c) {
+    const uint64_t te = env_threshold(c);
+    if (te == c->t_env_dev || !c->has_device) return PRT_OK;
+    std::vector<float> a, b;
+    const bool ml = mesh_lights_on(c) && c->d_ml_records;
+    prt_scaled_light_tables(c->hs, te, &a, ml ? &b : nullptr);
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    if (!a.empty() && c->d_lights) HIPCHECK(c, hipMemcpy(c->d_lights, a.data(), a.size() * 4, hipMemcpyHostToDevice));
+    if (ml && !b.empty()) HIPCHECK(c, hipMemcpy(c->d_ml_records, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+    c->t_env_dev = te;
+    return PRT_OK;
+}
+
 void free_mesh_lights(PrtContext* c) {
     free_dev(c->d_ml_records);
     free_dev(c->d_ml_thr);
@@ -285,7 +346,8 @@ int upload_mesh_lights(PrtContext* c) {
     HIPCHECK(c, up(&c->d_ml_thr, ml.thr.data(), ml.thr.size() * 4));
     HIPCHECK(c, up(&c->d_ml_bucket, ml.bucket.data(), ml.bucket.size() * 4));
     HIPCHECK(c, up(&c->d_ml_runs, ml.runs.data(), ml.runs.size() * sizeof(PrtLightRun)));
-    return PRT_OK;
+    c->t_env_dev = c->t_env_dev ? ~0ull : 0ull;  // (the records went up unscaled: a scaled default table is rewritten with them)
+    return sync_light_tables(c);
 }
 
 int ensure_counters(PrtContext* c) {
@@ -415,8 +477,13 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // bounces is the better deal
     // Lighting modes (PrtLighting) run k_shade_nee, which shades one segment per call: no fused segments, no compact primary
     // rays, no path route (tunables: the frame does not depend on them)
+    // An environment image (prt_set_environment) runs the instances of its own, unfused as well
     const bool lit = c->lighting != PRT_LIGHTING_OFF;
-    const uint32_t fuse = (!lit && c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
+    const bool envon = env_on(c);
+    if ((rc = sync_light_tables(c))) return rc;
+    const DevEnv denv = dev_env(c);
+    const DevEnv* envp = envon ? &denv : nullptr;
+    const uint32_t fuse = (!lit && !envon && c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
     // The ray count of a bounce is only known on the device.  With big batches a k_shade grid sized for the worst case is
     // a million blocks, most of which find nothing to do (~0.5 ms per launch, 4 % of a C3 step).  The host therefore
     // reads the counts of bounce d back WHILE the traversal kernel of bounce d runs (the copy is enqueued right after
@@ -446,7 +513,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // bit-identical (tests run both routes).  OFF by default (prt_set_param("path_kernel", 1 | 2)): measured, it ties with
     // the pipeline up to ~250 k paths per call and loses above (profiles/r3_path_kernel.txt, TUNING.md): both are bound
     // by a path's chain of dependent node fetches, and the pipeline shades with full waves.
-    const bool path_route = !lit && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
+    const bool path_route = !lit && !envon && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
                             !trav_stats && !c->d_shade_div && c->variant == 0 && fuse == 0u && c->sort_rays == 0u &&
                             prt_path_kernel_applies(c->dsc, c->tune);
     if (path_route) {
@@ -466,7 +533,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // front/back counters of every bounce start at zero (the producers add to them atomically)
     HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
     // compact primary rays (PrtPrimary): the default pipeline without jitter / roulette / clamp / fusion
-    const bool compact = !lit && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
+    const bool compact = !lit && !envon && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
                          c->sampling.jitter == 0u && c->sampling.rr_depth == 0u && !(c->sampling.clamp > 0.0f) && fuse == 0u &&
                          prt_traverse_takes_primary(c->dsc, c->tune);
     if (compact && c->pix_entries < c->tm.n_pix_local) {
@@ -486,7 +553,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                              1.0f / (float)c->tm.n_pix_local, first_sample, seed};
     if ((rc = begin_event(c, 0, &ep))) return rc;
     prt_launch_raygen(c->stream, c->dsc, c->cam, c->tm, n_paths, first_sample, seed, c->rb[0], c->d_rad, c->d_counts,
-                      c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr);
+                      c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr, envp);
     if ((rc = end_event(c, &ep))) return rc;
     if (exact) HIPCHECK(c, read_back(0));
     for (uint32_t d = 0; d < max_depth; ++d) {
@@ -554,8 +621,8 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
         if ((rc = begin_event(c, 2, &ep))) return rc;
         if (lit) {
             prt_launch_shade_nee(c->stream, c->dsc, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
-                                 c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr);
-            if (lt.n_lights) {
+                                 c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
+            if (lt.n_lights || (envon && (denv.t_all | denv.t_env))) {
                 // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
                 // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
                 const uint32_t* scount = c->d_counts + (size_t)d * PRT_CNT_STRIDE + 48u;
@@ -575,7 +642,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
             }
         } else {
             prt_launch_shade(c->stream, c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, fuse, c->sampling,
-                             n_rays_known, (compact && d == 0) ? &primary : nullptr);
+                             n_rays_known, (compact && d == 0) ? &primary : nullptr, envp);
         }
         if ((rc = end_event(c, &ep))) return rc;
         if (exact && d + 1 < max_depth) HIPCHECK(c, read_back(d + 1));
@@ -706,7 +773,8 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
     const int rc_cnt = ensure_counters(c);
     if (rc_cnt) return rc_cnt;
     c->has_scene = true;
-    return PRT_OK;
+    c->t_env_dev = 0;  // (both tables went up unscaled)
+    return sync_light_tables(c);
 }
 
 // Device-side build (csrc/bvh_gpu.hip) of the 8-wide tree over n triangles given as 9 floats each (+ normals, + a material
@@ -834,6 +902,7 @@ void prt_destroy(PrtContext* c) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         free_scene(c);
+        free_env(c);
         free_path_state(c);
         free_light_state(c);
         free_dev(c->d_light_stats);
@@ -937,11 +1006,14 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     dst->hs = src->hs;
     dst->inst_info = PrtInstanceUpdateInfo{};
     dst->light_sources = src->light_sources;
+    dst->env = src->env;
     if (!dst->has_device) {
         fill_dev_scene(dst, 0u, 0u);
         dst->has_scene = true;
         return PRT_OK;
     }
+    const int rc_env = upload_env(dst);
+    if (rc_env) return rc_env;
     return upload_scene(dst, nullptr);
 }
 
@@ -1311,25 +1383,92 @@ int prt_set_light_sources(PrtContext* c, uint32_t mask) {
     return PRT_OK;
 }
 
+int prt_set_environment(PrtContext* c, const PrtEnvironment* e) {
+    if (!c) return PRT_ERR_INVALID;
+    PrtEnvTables t;  // (built aside: a refused image leaves the context's environment as it was)
+    if (e) {
+        const int rc = prt_build_environment(e, &t, &c->err);
+        if (rc) return rc;
+    }
+    if (c->has_device) {
+        const int rc = need_device(c);
+        if (rc) return rc;
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+    }
+    c->env = std::move(t);
+    if (!c->has_device) return PRT_OK;
+    const int rc = upload_env(c);
+    if (rc) return rc;
+    return c->has_scene ? sync_light_tables(c) : PRT_OK;
+}
+
+int prt_environment_info(PrtContext* c, PrtEnvironmentInfo* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    memset(out, 0, sizeof(*out));
+    if (!env_on(c)) return PRT_OK;
+    out->is_set = 1u;
+    out->width = c->env.W;
+    out->height = c->env.H;
+    out->n_sampled = c->env.n_sampled;
+    out->t_env = env_threshold(c);
+    out->light_share = c->env.light_share;
+    return PRT_OK;
+}
+
+int prt_environment_intervals(PrtContext* c, uint64_t* row_width, uint64_t* col_width) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!env_on(c)) return fail(c, PRT_ERR_INVALID, "prt_environment_intervals: no environment is set");
+    if (c->env.row_width.empty()) return fail(c, PRT_ERR_INVALID, "prt_environment_intervals: an all-black map has no distribution");
+    if (row_width) memcpy(row_width, c->env.row_width.data(), c->env.row_width.size() * sizeof(uint64_t));
+    if (col_width) memcpy(col_width, c->env.col_width.data(), c->env.col_width.size() * sizeof(uint64_t));
+    return PRT_OK;
+}
+
+int prt_environment_eval(PrtContext* c, uint32_t n, const float* dirs, float* rgb, uint32_t* texel, float* pdf_w) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!env_on(c)) return fail(c, PRT_ERR_INVALID, "prt_environment_eval: no environment is set");
+    if (n == 0) return PRT_OK;
+    if (!dirs) return fail(c, PRT_ERR_INVALID, "null array");
+    const size_t b3 = ((size_t)n * 12 + 15) & ~(size_t)15, b1 = ((size_t)n * 4 + 15) & ~(size_t)15;
+    if ((rc = ensure_scratch(c, 2 * b3 + 2 * b1))) return rc;
+    char* base = (char*)c->d_scratch;
+    float* d_d = (float*)base;
+    float* d_rgb = (float*)(base + b3);
+    uint32_t* d_t = (uint32_t*)(base + 2 * b3);
+    float* d_p = (float*)(base + 2 * b3 + b1);
+    HIPCHECK(c, hipMemcpyAsync(d_d, dirs, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    prt_launch_environment_eval(c->stream, dev_env(c), n, d_d, d_rgb, d_t, d_p);
+    HIPCHECK(c, hipGetLastError());
+    if (rgb) HIPCHECK(c, hipMemcpyAsync(rgb, d_rgb, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (texel) HIPCHECK(c, hipMemcpyAsync(texel, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (pdf_w) HIPCHECK(c, hipMemcpyAsync(pdf_w, d_p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
 int prt_light_intervals(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint64_t* width) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     if (!mesh_lights_on(c)) return fail(c, PRT_ERR_INVALID, "prt_light_intervals: the default light sources have no thresholds");
     const uint32_t n = (uint32_t)c->hs.ml.visible.size();
     if (n_lights) *n_lights = n;
-    for (uint32_t l = 0; l < n && l < capacity && width; ++l) width[l] = c->hs.ml.width[l];
+    const uint64_t te = env_threshold(c);  // (T_e > 0: the exact product with 2^32 - T_e, in units of 2^-64)
+    for (uint32_t l = 0; l < n && l < capacity && width; ++l) width[l] = te ? c->hs.ml.width[l] * (4294967296ull - te) : c->hs.ml.width[l];
     return PRT_OK;
 }
 
 int prt_light_info(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint32_t* prim, float* pmf) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    std::vector<float> lights_s, records_s;  // (the pmfs with the environment's factor: what the kernels use)
+    prt_scaled_light_tables(c->hs, env_threshold(c), mesh_lights_on(c) ? nullptr : &lights_s, mesh_lights_on(c) ? &records_s : nullptr);
     if (mesh_lights_on(c)) {
         const PrtMeshLights& ml = c->hs.ml;
         const uint32_t nv = (uint32_t)ml.visible.size();
         if (n_lights) *n_lights = nv;
         for (uint32_t l = 0; l < nv && l < capacity; ++l) {
-            const float* r = &ml.records[4 * PRT_LIGHT_F4 * (size_t)ml.visible[l]];
+            const float* r = &records_s[4 * PRT_LIGHT_F4 * (size_t)ml.visible[l]];
             if (prim) memcpy(&prim[l], &r[19], 4);
             if (pmf) pmf[l] = r[7];
         }
@@ -1338,7 +1477,7 @@ int prt_light_info(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint32_
     const uint32_t n = (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4));
     if (n_lights) *n_lights = n;
     for (uint32_t l = 0; l < n && l < capacity; ++l) {
-        const float* r = &c->hs.lights[4 * PRT_LIGHT_F4 * l];
+        const float* r = &lights_s[4 * PRT_LIGHT_F4 * l];
         if (prim) memcpy(&prim[l], &r[19], 4);
         if (pmf) pmf[l] = r[7];
     }
@@ -1691,7 +1830,10 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
     HIPCHECK(c, hipMemcpyAsync(d_in, in_dirs, b3, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipMemcpyAsync(d_k, keys, b1, hipMemcpyHostToDevice, c->stream));
     const DevMeshLights mlt = dev_mesh_lights(c);
-    prt_launch_sample_light_test(c->stream, c->dsc, dev_lights(c), n, d_in, d_h, d_k, d_f, d_l, mesh_lights_on(c) ? &mlt : nullptr);
+    if ((rc = sync_light_tables(c))) return rc;
+    const DevEnv denv = dev_env(c);
+    prt_launch_sample_light_test(c->stream, c->dsc, dev_lights(c), n, d_in, d_h, d_k, d_f, d_l, mesh_lights_on(c) ? &mlt : nullptr,
+                                 env_on(c) ? &denv : nullptr);
     HIPCHECK(c, hipGetLastError());
     std::vector<float> f((size_t)n * 11);
     HIPCHECK(c, hipMemcpyAsync(f.data(), d_f, bf, hipMemcpyDeviceToHost, c->stream));
@@ -1709,7 +1851,7 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
         w_light[i] = r[9];
         w_bsdf[i] = r[10];
         // (the kernel reports the candidate; the light set proper leaves out the candidates with an empty interval)
-        if (mesh_lights_on(c) && light[i] != 0xFFFFFFFFu) light[i] = c->hs.ml.cand_visible[light[i]];
+        if (mesh_lights_on(c) && light[i] != 0xFFFFFFFFu && light[i] != PRT_LIGHT_ENVIRONMENT) light[i] = c->hs.ml.cand_visible[light[i]];
     }
     return PRT_OK;
 }

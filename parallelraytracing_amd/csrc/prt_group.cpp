@@ -322,6 +322,11 @@ int prt_group_set_light_sources(PrtGroup* g, uint32_t mask) {
     return for_each_rank(g, [&](uint32_t r) { return prt_set_light_sources(g->ctx[r], mask); }, false);
 }
 
+int prt_group_set_environment(PrtGroup* g, const PrtEnvironment* env) {
+    if (!g) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_environment(g->ctx[r], env); }, false);
+}
+
 int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out) {
     if (!g || !out || g->ctx.empty()) return PRT_ERR_INVALID;
     memset(out, 0, sizeof(*out));

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <fstream>
@@ -750,3 +751,83 @@ extern "C" int prt_write_pfm(const char* path, const float* rgb, uint32_t width,
     fclose(f);
     return PRT_OK;
 }
+
+// Colour PFM reader: "PF", width, height, scale (its sign is the byte order: negative = little-endian), separated by
+// white space, ONE white-space byte after the scale, then height rows of width * 3 floats, bottom row first.  The scale's
+// magnitude is not applied (prt_write_pfm writes 1).  Every malformed input is PRT_ERR_IO.
+extern "C" int prt_read_pfm(const char* path, float** rgb, uint32_t* width, uint32_t* height) {
+    if (!path || !rgb || !width || !height) return PRT_ERR_INVALID;
+    *rgb = nullptr;
+    *width = *height = 0;
+    FILE* f = fopen(path, "rb");
+    if (!f) return PRT_ERR_IO;
+    char head[128];
+    const size_t got = fread(head, 1, sizeof(head) - 1, f);
+    head[got] = 0;
+    size_t pos = 0;
+    auto is_space = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r'; };
+    auto token = [&](char* out, size_t cap) -> bool {  // the next white-space delimited token, at most cap - 1 bytes
+        while (pos < got && is_space(head[pos])) ++pos;
+        size_t n = 0;
+        while (pos < got && !is_space(head[pos])) {
+            if (n + 1 >= cap) return false;
+            out[n++] = head[pos++];
+        }
+        out[n] = 0;
+        return n > 0 && pos < got;  // (a token the header ends in is not terminated)
+    };
+    char t_magic[8], t_w[16], t_h[16], t_s[40];
+    bool ok = token(t_magic, sizeof(t_magic)) && strcmp(t_magic, "PF") == 0 && token(t_w, sizeof(t_w)) && token(t_h, sizeof(t_h)) &&
+              token(t_s, sizeof(t_s));
+    unsigned long w = 0, h = 0;
+    double scale = 0.0;
+    if (ok) {
+        char* end = nullptr;
+        for (const char* p = t_w; *p; ++p) ok = ok && *p >= '0' && *p <= '9';
+        for (const char* p = t_h; *p; ++p) ok = ok && *p >= '0' && *p <= '9';
+        if (ok) {
+            w = strtoul(t_w, &end, 10);
+            h = strtoul(t_h, &end, 10);
+            scale = strtod(t_s, &end);
+            ok = *end == 0 && std::isfinite(scale) && scale != 0.0 && w > 0 && h > 0 && w <= (1ul << 28) && h <= (1ul << 28) &&
+                 (unsigned long long)w * h <= (1ull << 28);
+        }
+    }
+    if (!ok) {
+        fclose(f);
+        return PRT_ERR_IO;
+    }
+    const size_t body = pos + 1;  // one white-space byte ends the header
+    const size_t n = 3 * (size_t)w * (size_t)h;
+    // (the body must be there before anything is allocated for it: a header may claim any size)
+    if (fseek(f, 0, SEEK_END) != 0 || ftell(f) < 0 || (unsigned long long)ftell(f) < (unsigned long long)body + n * sizeof(float)) {
+        fclose(f);
+        return PRT_ERR_IO;
+    }
+    float* out = (float*)malloc(n * sizeof(float));
+    if (!out) {
+        fclose(f);
+        return PRT_ERR_NOMEM;
+    }
+    ok = fseek(f, (long)body, SEEK_SET) == 0;
+    for (unsigned long y = 0; ok && y < h; ++y)  // bottom row first
+        ok = fread(out + 3 * (size_t)(h - 1 - y) * w, sizeof(float), 3 * (size_t)w, f) == 3 * (size_t)w;
+    fclose(f);
+    if (!ok) {
+        free(out);
+        return PRT_ERR_IO;
+    }
+    if (scale > 0.0) {  // big-endian floats
+        unsigned char* b = (unsigned char*)out;
+        for (size_t k = 0; k < n; ++k) {
+            std::swap(b[4 * k + 0], b[4 * k + 3]);
+            std::swap(b[4 * k + 1], b[4 * k + 2]);
+        }
+    }
+    *rgb = out;
+    *width = (uint32_t)w;
+    *height = (uint32_t)h;
+    return PRT_OK;
+}
+
+extern "C" void prt_image_free(float* rgb) { free(rgb); }

@@ -169,6 +169,22 @@ struct DevMeshLights {
     uint32_t bucket_shift;
     uint32_t n_runs;
 };
+// Environment light (PrtEnvironment, include/prt.h; host side: PrtEnvTables, prt_scene.h), passed only to the kernel
+// instances of its own (k_raygen_env, k_shade_env, k_shade_nee_env, k_shade_nee_mesh_env): DevScene and the other instances
+// stay as they are.  texels: rgb, pdf_w x sin(theta) of the texel; row_thr / col_thr: the 32-bit thresholds, searched up to
+// row_last / col_last[row] (the last entry's 2^32 is implicit).
+struct DevEnv {
+    const float4* texels;
+    const uint32_t* row_thr;
+    const uint32_t* col_thr;
+    const uint32_t* col_last;
+    uint32_t W, H;
+    uint32_t row_last;
+    uint32_t t_env;    // low 32 bits of T_e: the environment is sampled iff t_all or r_e < t_env
+    uint32_t t_all;    // T_e = 2^32
+    float p_env;       // fl(T_e / 2^32)
+};
+
 // What the lighting shade step needs beyond k_shade's arguments: the shadow-ray buffer (o = x, path id; d = w, -;
 // t = clamped contribution rgb, tmax; hit / hd2 seeded as k_pack_occlusion_rays seeds them), the per-path pdf of the
 // previous scatter (pB, < 0: the previous vertex was not Lambertian) and the per-path light radiance.
@@ -181,7 +197,8 @@ struct PrtLightBufs {
 
 void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, uint32_t n_paths,
                        uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
-                       uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix = nullptr);
+                       uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix = nullptr,
+                       const DevEnv* env = nullptr);  // env: the instance with an environment image (never compact)
 void prt_launch_scan_prims(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                            uint32_t* work, uint32_t max_rays, unsigned long long* stats);
 void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
@@ -199,7 +216,8 @@ void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& i
                           uint32_t max_rays, int stack_depth, int variant, unsigned long long* stats);
 void prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
                       uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap,
-                      uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary = nullptr);
+                      uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary = nullptr,
+                      const DevEnv* env = nullptr);  // env: the instance with an environment image (no fusion, no compact primaries)
 // diagnostic: per-wave material mix of what k_shade of bounce `iter` is about to shade (16 words per bounce in `out`)
 void prt_launch_shade_divstats(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* counts, uint32_t iter,
                                uint32_t cap, unsigned long long* out, const PrtPrimary* primary = nullptr);
@@ -238,11 +256,15 @@ void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, con
 void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
                           const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
                           uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
-                          const DevMeshLights* ml = nullptr);  // ml: the instances that sample triangle lights
+                          const DevMeshLights* ml = nullptr,  // ml: the instances that sample triangle lights
+                          const DevEnv* env = nullptr);       // env: the instances with an environment light
 void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBufs& lb, const uint32_t* count_ptr,
                             uint32_t* work, uint32_t max_rays);
 void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, const PrtTileMap& tm,
                                uint32_t S, uint32_t max_depth, bool update_film, unsigned long long* ray_stats);
 void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
                                   const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light,
-                                  const DevMeshLights* ml = nullptr);
+                                  const DevMeshLights* ml = nullptr, const DevEnv* env = nullptr);
+// prt_environment_eval: lookup of n directions (3 floats each): rgb (3 floats), texel, pdf_w; any output may be null
+void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, const float* dirs, float* rgb, uint32_t* texel,
+                                 float* pdf_w);

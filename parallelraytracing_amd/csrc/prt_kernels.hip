@@ -211,17 +211,50 @@ PRT_DEV float4 path_result(f3 L, float clamp, uint32_t depth) {
     return make_float4(L.x, L.y, L.z, __uint_as_float(depth));
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Environment image (PrtEnvironment, include/prt.h "Environment light"; DevEnv): lat-long, nearest texel.  Only the ENV
+// instances of the producers call these; the others keep the constant sky and their code.
+// ---------------------------------------------------------------------------------------------------------
+#define PRT_ENV_INV_TWO_PI 0.159154943091895336f
+#define PRT_ENV_INV_PI 0.318309886183790672f
+// texel i * W + j of the unit direction d: always in range, a NaN direction included (texel 0)
+PRT_DEV uint32_t env_texel(const DevEnv& env, f3 d) {
+    const float x = __builtin_fmaf(atan2f(d.z, d.x), PRT_ENV_INV_TWO_PI, 0.5f) * (float)env.W;
+    float cy = d.y < -1.0f ? -1.0f : d.y;
+    cy = cy > 1.0f ? 1.0f : cy;
+    const float y = (acosf(cy) * PRT_ENV_INV_PI) * (float)env.H;
+    uint32_t j = x > 0.0f ? (uint32_t)x : 0u;
+    uint32_t i = y > 0.0f ? (uint32_t)y : 0u;
+    j = j < env.W - 1u ? j : env.W - 1u;
+    i = i < env.H - 1u ? i : env.H - 1u;
+    return i * env.W + j;
+}
+// radiance of a miss along d, and the solid-angle density with which the environment sample picks d (without T_e)
+PRT_DEV f3 env_radiance(const DevEnv& env, f3 d, float& pdf_w) {
+    const float4 t = env.texels[env_texel(env, d)];
+    const float s2 = (1.0f - d.y) * (1.0f + d.y);  // 1 - d.y^2 without the cancellation near the poles
+    const float sin_t = __builtin_sqrtf(s2 > 0.0f ? s2 : 0.0f);
+    pdf_w = sin_t > 0.0f ? t.w / sin_t : 0.0f;
+    return mk3(t.x, t.y, t.z);
+}
+PRT_DEV f3 env_radiance(const DevEnv& env, f3 d) {
+    const float4 t = env.texels[env_texel(env, d)];
+    return mk3(t.x, t.y, t.z);
+}
+
 // PRE: (pre_a, pre_b) = the hit record k_primary_hit computed for this path's pixel: {position, hit id}, {normal, material
 // | front face << 31}.  It replaces world_hit_from_id for the first segment when it was computed for the same hit id (it
 // always was: all samples of a pixel trace the same primary ray; the comparison keeps the kernel correct by itself).
-template <int BUDGET, bool INST, bool ABVH, int BLOCK, bool PRE = false>
+// ENV (env: DevEnv): a miss delivers the environment image's texel where it delivers the constant sky.
+template <int BUDGET, bool INST, bool ABVH, int BLOCK, bool PRE = false, bool ENV = false>
 PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr, uint32_t& rng, uint32_t& depth,
                          uint32_t max_depth, const PrtSampling& sp, float4* __restrict__ rad_slot, uint32_t& id0,
-                         float& d2_0, float4 pre_a = float4{0.f, 0.f, 0.f, 0.f}, float4 pre_b = float4{0.f, 0.f, 0.f, 0.f}) {
+                         float& d2_0, float4 pre_a = float4{0.f, 0.f, 0.f, 0.f}, float4 pre_b = float4{0.f, 0.f, 0.f, 0.f},
+                         const DevEnv* env = nullptr) {
 #pragma unroll
     for (int it = 0; it <= BUDGET; ++it) {
         if (id == HIT_MISS) {  // the miss branch of IntersectClosestKernel, renderer.cu:263-271
-            st_stream(rad_slot, path_result(thr * mk3(sc.sky[0], sc.sky[1], sc.sky[2]), sp.clamp, depth));
+            st_stream(rad_slot, path_result(thr * (ENV ? env_radiance(*env, d) : mk3(sc.sky[0], sc.sky[1], sc.sky[2])), sp.clamp, depth));
             return 0;
         }
         if (it == BUDGET) {  // only reached with an analytic id (the ray was classified "cannot hit a triangle")
@@ -287,14 +320,14 @@ PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr,
 #define RAYGEN_GROUP_NOJITTER 64u  // without jitter: one wave's worth of samples per pixel and block (pixel-major slots)
 // SAMPLING = false compiles the Russian-roulette / clamp code out: with it in, k_shade needs 82 instead of 74 SGPRs,
 // which costs a wave per SIMD, i.e. with 1024-thread blocks one of the two blocks per CU (measured: shade 50 % slower).
-template <bool JITTER, bool SAMPLING, bool ABVH, bool COMPACT = false>
-__global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S,
-                                                            uint32_t first_sample, uint32_t seed,
-                                                            float4* __restrict__ ro, float4* __restrict__ rd,
-                                                            float4* __restrict__ rt, uint32_t* __restrict__ hit,
-                                                            float* __restrict__ hd2, float4* __restrict__ rad,
-                                                            uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
-                                                            uint32_t max_depth, PrtSampling sp_arg, float4* __restrict__ pix) {
+// (ENV / env: see advance_path; k_raygen passes false / null and compiles to the code it had before there was an environment
+// image, k_raygen_env is the instance with one)
+template <bool JITTER, bool SAMPLING, bool ABVH, bool COMPACT, bool ENV>
+PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, uint32_t first_sample, uint32_t seed,
+                         float4* __restrict__ ro, float4* __restrict__ rd, float4* __restrict__ rt, uint32_t* __restrict__ hit,
+                         float* __restrict__ hd2, float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                         uint32_t* __restrict__ work, uint32_t max_depth, PrtSampling sp_arg, float4* __restrict__ pix,
+                         const DevEnv* env) {
     const PrtSampling sp = SAMPLING ? sp_arg : PrtSampling{0u, 0u, 0.0f};
     const uint32_t pl = blockIdx.x * (uint32_t)PRODUCER_BLOCK + threadIdx.x;
     if (blockIdx.y == 0 && pl < 8u) work[32u * pl] = 0u;  // chunk cursors of the traversal kernel that follows
@@ -331,7 +364,8 @@ __global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen(DevScene sc, DevCamer
         if (valid) {
             front = front0;
             if (!front) {
-                const int r = advance_path<0, false, ABVH, PRODUCER_BLOCK>(sc, id00, o, d, thr, rng, depth, max_depth, sp, &L0, id0, d2_0);
+                const int r = advance_path<0, false, ABVH, PRODUCER_BLOCK, false, ENV>(sc, id00, o, d, thr, rng, depth, max_depth, sp, &L0, id0, d2_0,
+                                                                                         float4{0.f, 0.f, 0.f, 0.f}, float4{0.f, 0.f, 0.f, 0.f}, env);
                 back = r == 2;
             }
         }
@@ -449,7 +483,8 @@ __global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen(DevScene sc, DevCamer
                     front = classify_ray<ABVH, PRODUCER_BLOCK>(sc, o, d, id0, d2_0);
                 }
                 if (!front) {
-                    const int r = advance_path<0, false, ABVH, PRODUCER_BLOCK>(sc, id0, o, d, thr, rng, depth, max_depth, sp, &rad[i], id0, d2_0);
+                    const int r = advance_path<0, false, ABVH, PRODUCER_BLOCK, false, ENV>(sc, id0, o, d, thr, rng, depth, max_depth, sp, &rad[i], id0, d2_0,
+                                                                                             float4{0.f, 0.f, 0.f, 0.f}, float4{0.f, 0.f, 0.f, 0.f}, env);
                     front = r == 1;
                     back = r == 2;
                 }
@@ -478,6 +513,31 @@ __global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen(DevScene sc, DevCamer
         }
         __syncthreads();  // block_alloc2k's LDS counts are reused by the next trip (see block_alloc2's contract)
     }
+}
+
+template <bool JITTER, bool SAMPLING, bool ABVH, bool COMPACT = false>
+__global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S,
+                                                            uint32_t first_sample, uint32_t seed,
+                                                            float4* __restrict__ ro, float4* __restrict__ rd,
+                                                            float4* __restrict__ rt, uint32_t* __restrict__ hit,
+                                                            float* __restrict__ hd2, float4* __restrict__ rad,
+                                                            uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                            uint32_t max_depth, PrtSampling sp_arg, float4* __restrict__ pix) {
+    raygen_step<JITTER, SAMPLING, ABVH, COMPACT, false>(sc, cam, tm, S, first_sample, seed, ro, rd, rt, hit, hd2, rad, counts, work,
+                                                        max_depth, sp_arg, pix, nullptr);
+}
+
+// k_raygen under an environment image (prt_set_environment): full ray records always, sampling options compiled in
+template <bool JITTER, bool ABVH>
+__global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen_env(DevScene sc, DevEnv env, DevCamera cam, PrtTileMap tm, uint32_t S,
+                                                                uint32_t first_sample, uint32_t seed,
+                                                                float4* __restrict__ ro, float4* __restrict__ rd,
+                                                                float4* __restrict__ rt, uint32_t* __restrict__ hit,
+                                                                float* __restrict__ hd2, float4* __restrict__ rad,
+                                                                uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                                uint32_t max_depth, PrtSampling sp_arg) {
+    raygen_step<JITTER, true, ABVH, false, true>(sc, cam, tm, S, first_sample, seed, ro, rd, rt, hit, hd2, rad, counts, work,
+                                                 max_depth, sp_arg, nullptr, &env);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2420,15 +2480,13 @@ __global__ void __launch_bounds__(256, WAVES) k_occluded8_persistent(DevScene sc
 // Radiance can only be non-zero at the event that ends a path (emissive materials never scatter,
 // material.h:119-122), so the path carries throughput only and writes rad[path] once, when it ends.
 // ---------------------------------------------------------------------------------------------------------
-template <int FUSE, bool SAMPLING, bool INST, bool ABVH, bool PRIM = false>
-__global__ void __launch_bounds__(SHADE_BLOCK) k_shade(DevScene sc, const float4* __restrict__ ro,
-                                                      const float4* __restrict__ rd, const float4* __restrict__ rt,
-                                                      const uint32_t* __restrict__ hit, float4* __restrict__ no,
-                                                      float4* __restrict__ nd, float4* __restrict__ nt,
-                                                      uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
-                                                      float4* __restrict__ rad, uint32_t* __restrict__ counts,
-                                                      uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
-                                                      uint32_t cap, PrtSampling sp_arg, PrtPrimary pr) {
+// (ENV / env: see advance_path; k_shade passes false / null and keeps its code, k_shade_env is the instance with an image)
+template <int FUSE, bool SAMPLING, bool INST, bool ABVH, bool PRIM, bool ENV>
+PRT_DEV void shade_step(DevScene sc, const float4* __restrict__ ro, const float4* __restrict__ rd, const float4* __restrict__ rt,
+                        const uint32_t* __restrict__ hit, float4* __restrict__ no, float4* __restrict__ nd, float4* __restrict__ nt,
+                        uint32_t* __restrict__ nhit, float* __restrict__ nhd2, float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                        uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp_arg, PrtPrimary pr,
+                        const DevEnv* env) {
     // PRIM: the first k_shade of a batch whose k_raygen stored compact primary rays (PrtPrimary): ray, RNG seed,
     // throughput (1,1,1) and segment index (0) follow from the path id
     const PrtSampling sp = SAMPLING ? sp_arg : PrtSampling{0u, 0u, 0.0f};
@@ -2469,7 +2527,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade(DevScene sc, const float4
             d = mk3(D.x, D.y, D.z);
         }
         if (id != HIT_DEAD) {
-            const int r = advance_path<1 + FUSE, INST, ABVH, SHADE_BLOCK, PRIM>(sc, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0, pre_a, pre_b);
+            const int r = advance_path<1 + FUSE, INST, ABVH, SHADE_BLOCK, PRIM, ENV>(sc, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0, pre_a, pre_b, env);
             front = r == 1;
             back = r == 2;
         }
@@ -2483,6 +2541,33 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade(DevScene sc, const float4
         st_stream(&nhit[slot], id0);
         st_stream(&nhd2[slot], d2_0);
     }
+}
+
+template <int FUSE, bool SAMPLING, bool INST, bool ABVH, bool PRIM = false>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade(DevScene sc, const float4* __restrict__ ro,
+                                                      const float4* __restrict__ rd, const float4* __restrict__ rt,
+                                                      const uint32_t* __restrict__ hit, float4* __restrict__ no,
+                                                      float4* __restrict__ nd, float4* __restrict__ nt,
+                                                      uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
+                                                      float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                                                      uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
+                                                      uint32_t cap, PrtSampling sp_arg, PrtPrimary pr) {
+    shade_step<FUSE, SAMPLING, INST, ABVH, PRIM, false>(sc, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, rad, counts, work, iter, max_depth,
+                                                        cap, sp_arg, pr, nullptr);
+}
+
+// k_shade under an environment image: one segment per call, sampling options compiled in
+template <bool INST, bool ABVH>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_env(DevScene sc, DevEnv env, const float4* __restrict__ ro,
+                                                          const float4* __restrict__ rd, const float4* __restrict__ rt,
+                                                          const uint32_t* __restrict__ hit, float4* __restrict__ no,
+                                                          float4* __restrict__ nd, float4* __restrict__ nt,
+                                                          uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
+                                                          float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                                                          uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
+                                                          uint32_t cap, PrtSampling sp_arg) {
+    shade_step<0, true, INST, ABVH, false, true>(sc, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, rad, counts, work, iter, max_depth, cap,
+                                                 sp_arg, PrtPrimary{}, &env);
 }
 
 // Compact primary rays: the surface interaction of a pixel's primary hit, ONCE per pixel.  Without jitter every sample of
@@ -3120,16 +3205,103 @@ PRT_DEV bool light_sample_term(const DevLights& lt, f3 x, f3 n, f3 albedo, f3 th
     return true;
 }
 
+// ---- environment light (include/prt.h "Environment light") ----
+// The environment-or-lights draw of the vertex with path state `key`: true = this vertex's light sample goes to the image.
+PRT_DEV bool env_selected(const DevEnv& env, uint32_t key) {
+    const uint32_t re = pcg_hash(key + PRT_ENV_RNG);
+    return env.t_all != 0u || re < env.t_env;
+}
+
+// smallest i in [0, last] with r < thr[i], else last (the last entry's threshold, 2^32, is implicit): ceil(log2(last + 1))
+// dependent loads from a table the L2 holds
+PRT_DEV uint32_t env_search(const uint32_t* __restrict__ thr, uint32_t last, uint32_t r) {
+    uint32_t lo = 0u, hi = last;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (r < thr[mid]) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+
+// One environment sample with the draws of key's light stream: texel by the row and column thresholds, direction uniform
+// in (u, v) inside the texel.  Le is the sampled texel's (no second lookup); tmax = +inf.  false: no sample (pdf 0).
+PRT_DEV bool sample_environment(const DevEnv& env, uint32_t key, LightSample& s) {
+    uint32_t ls = pcg_hash(key + PRT_LIGHT_RNG);
+    ls = pcg_hash(ls);
+    const uint32_t i = env_search(env.row_thr, env.row_last, ls);
+    ls = pcg_hash(ls);
+    const uint32_t j = env_search(env.col_thr + (size_t)i * env.W, env.col_last[i], ls);
+    const float u1 = rnd01(ls);
+    const float u2 = rnd01(ls);
+    const float4 t = env.texels[(size_t)i * env.W + j];
+    const float u = ((float)j + u1) / (float)env.W;
+    const float v = ((float)i + u2) / (float)env.H;
+    float sp, cp, st, ct;
+    sincosf(__builtin_fmaf(PRT_TWO_PI, u, -3.14159265358979324f), &sp, &cp);
+    sincosf(3.14159265358979324f * v, &st, &ct);
+    s.w = mk3(st * cp, ct, st * sp);
+    s.t_light = __builtin_inff();
+    s.tmax = __builtin_inff();
+    s.le = mk3(t.x, t.y, t.z);
+    s.light = PRT_LIGHT_ENVIRONMENT;
+    s.pdf_l = st > 0.0f ? env.p_env * (t.w / st) : 0.0f;
+    return s.pdf_l > 0.0f && s.pdf_l < 3.0e38f;
+}
+
+// light_sample_term for the environment sample: the same estimator, weight and clamp
+PRT_DEV bool env_sample_term(const DevEnv& env, uint32_t mode, f3 n, f3 albedo, f3 thr, uint32_t key, float clamp, LightSample& s,
+                             float& pb, float& wl, f3& contrib) {
+    if (!sample_environment(env, key, s)) return false;
+    const float c = dot3(n, s.w);
+    pb = (c > 0.0f ? c : 0.0f) * PRT_INV_PI;
+    wl = light_weight(mode, s.pdf_l, pb);
+    contrib = mk3(0.0f, 0.0f, 0.0f);
+    if (c > 0.0f) {
+        contrib = ((thr * albedo) * s.le) * ((pb * wl) / s.pdf_l);
+        if (clamp > 0.0f) {
+            contrib.x = contrib.x > clamp ? clamp : contrib.x;
+            contrib.y = contrib.y > clamp ? clamp : contrib.y;
+            contrib.z = contrib.z > clamp ? clamp : contrib.z;
+        }
+    }
+    return true;
+}
+
+// Radiance of a miss along d and its weight after a Lambertian vertex that scattered with pdf pb (pb < 0: the camera, or a
+// metal / dielectric vertex: weight 1): 1 - w_L of the same pair; 1 where the environment cannot sample d (pL = 0).
+PRT_DEV f3 env_miss(const DevEnv& env, uint32_t mode, f3 d, float pb, float& wb) {
+    float pdf_w;
+    const f3 le = env_radiance(env, d, pdf_w);
+    wb = 1.0f;
+    if (pb >= 0.0f) {
+        const float pl = env.p_env * pdf_w;
+        if (pl > 0.0f) {
+            const float r = pl / pb;  // pb = 0: r = inf, weight 0
+            wb = mode == (uint32_t)PRT_LIGHTING_NEE ? 0.0f : 1.0f / (1.0f + r * r);
+        }
+    }
+    return le;
+}
+
 // advance_path<1, INST, ABVH, SHADE_BLOCK> (no fused segment) with light sampling: the same vertex, the same draws, the same
 // segments; in addition the light sample (`shadow`) of a Lambertian vertex that scatters, emission of light-set emitters
 // met after a Lambertian vertex weighted by bsdf_hit_weight, and pb_next = the pdf of the scatter (-1: not Lambertian).
 // MESHL (ml: the triangle lights' tables): the light set holds triangles too, so a segment's triangle hit is weighted as well.
-template <bool INST, bool ABVH, bool MESHL = false>
+// ENV (env: DevEnv): an environment light: a miss delivers its texel, weighted after a Lambertian vertex (env_miss), and a
+// Lambertian vertex whose environment-or-lights draw says so sends its light sample there (sample_environment).
+template <bool INST, bool ABVH, bool MESHL = false, bool ENV = false>
 PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t id, f3& o, f3& d, f3& thr, uint32_t& rng,
                              uint32_t& depth, uint32_t max_depth, const PrtSampling& sp, float4* __restrict__ rad_slot,
                              uint32_t& id0, float& d2_0, float pb_prev, float& pb_next, bool& shadow, f3& sx, f3& sw,
-                             float& stmax, f3& scontrib, const DevMeshLights* ml = nullptr) {
+                             float& stmax, f3& scontrib, const DevMeshLights* ml = nullptr, const DevEnv* env = nullptr) {
     if (id == HIT_MISS) {
+        if (ENV) {
+            float wb;
+            f3 L = thr * env_miss(*env, lt.mode, d, pb_prev, wb);
+            if (wb != 1.0f) L = L * wb;
+            st_stream(rad_slot, path_result(L, sp.clamp, depth));
+            return 0;
+        }
         st_stream(rad_slot, path_result(thr * mk3(sc.sky[0], sc.sky[1], sc.sky[2]), sp.clamp, depth));
         return 0;
     }
@@ -3155,7 +3327,15 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
         st_stream(rad_slot, path_result(L, sp.clamp, depth));
         return 0;
     }
-    if (type == 1u && lt.n_lights) {  // (scattered: depth + 1 < max_depth)
+    if (ENV && type == 1u && (env->t_all | env->t_env) != 0u && env_selected(*env, key)) {
+        LightSample ls;
+        float pb, wl;
+        if (env_sample_term(*env, lt.mode, w.normal, mk3(rgbs.x, rgbs.y, rgbs.z), thr, key, sp.clamp, ls, pb, wl, scontrib) && pb > 0.0f) {
+            shadow = true;
+            sw = ls.w;
+            stmax = ls.tmax;
+        }
+    } else if (type == 1u && lt.n_lights) {  // (scattered: depth + 1 < max_depth)
         LightSample ls;
         float pb, wl;
         if (light_sample_term<MESHL>(lt, w.pos, w.normal, mk3(rgbs.x, rgbs.y, rgbs.z), thr, key, sp.clamp, ls, pb, wl, scontrib, ml) &&
@@ -3188,6 +3368,13 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
     if (classify_ray<ABVH, SHADE_BLOCK>(sc, o, d, id0, d2_0)) return 1;
     // the new segment cannot hit a triangle: its closest hit is the analytic scan's (advance_path's budget step)
     if (id0 == HIT_MISS) {
+        if (ENV) {
+            float wb;
+            f3 L = thr * env_miss(*env, lt.mode, d, pb_next, wb);
+            if (wb != 1.0f) L = L * wb;
+            st_stream(rad_slot, path_result(L, sp.clamp, depth));
+            return 0;
+        }
         st_stream(rad_slot, path_result(thr * mk3(sc.sky[0], sc.sky[1], sc.sky[2]), sp.clamp, depth));
         return 0;
     }
@@ -3207,12 +3394,13 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
 
 // The lighting shade step; MESHL / ml: see advance_path_nee (k_shade_nee passes false / null and compiles to the code it had
 // before there were triangle lights; k_shade_nee_mesh is the instance with them).
-template <bool INST, bool ABVH, bool MESHL>
+template <bool INST, bool ABVH, bool MESHL, bool ENV = false>
 PRT_DEV void shade_nee_step(DevScene sc, DevLights lt, const DevMeshLights* ml, const float4* __restrict__ ro,
                             const float4* __restrict__ rd, const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
                             float4* __restrict__ no, float4* __restrict__ nd, float4* __restrict__ nt, uint32_t* __restrict__ nhit,
                             float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
-                            uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
+                            uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp,
+                            const DevEnv* env = nullptr) {
     const uint32_t nA = CNT_A(counts, iter), nB = CNT_B(counts, iter);
     const uint32_t count = nA + nB;
     if (blockIdx.x * (uint32_t)SHADE_BLOCK >= count) return;  // whole block exits together
@@ -3240,8 +3428,8 @@ PRT_DEV void shade_nee_step(DevScene sc, DevLights lt, const DevMeshLights* ml, 
         // pdf of the scatter that started this segment (segment 0 starts at the camera)
         const float pb_prev = depth ? lb.pdf_b[pid] : -1.0f;
         if (id != HIT_DEAD) {
-            const int r = advance_path_nee<INST, ABVH, MESHL>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
-                                                       pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb, ml);
+            const int r = advance_path_nee<INST, ABVH, MESHL, ENV>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
+                                                            pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb, ml, env);
             front = r == 1;
             back = r == 2;
         }
@@ -3291,6 +3479,31 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_mesh(DevScene sc, Dev
                                                                uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
                                                                uint32_t cap, PrtSampling sp) {
     shade_nee_step<INST, ABVH, true>(sc, lt, &ml, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter, max_depth, cap, sp);
+}
+
+// k_shade_nee / k_shade_nee_mesh with an environment light (prt_set_environment)
+template <bool INST, bool ABVH>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_env(DevScene sc, DevLights lt, DevEnv env, const float4* __restrict__ ro,
+                                                              const float4* __restrict__ rd, const float4* __restrict__ rt,
+                                                              const uint32_t* __restrict__ hit, float4* __restrict__ no,
+                                                              float4* __restrict__ nd, float4* __restrict__ nt,
+                                                              uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
+                                                              PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                                                              uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
+                                                              uint32_t cap, PrtSampling sp) {
+    shade_nee_step<INST, ABVH, false, true>(sc, lt, nullptr, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter, max_depth, cap, sp, &env);
+}
+
+template <bool INST, bool ABVH>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_mesh_env(DevScene sc, DevLights lt, DevMeshLights ml, DevEnv env,
+                                                                   const float4* __restrict__ ro, const float4* __restrict__ rd,
+                                                                   const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
+                                                                   float4* __restrict__ no, float4* __restrict__ nd,
+                                                                   float4* __restrict__ nt, uint32_t* __restrict__ nhit,
+                                                                   float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad,
+                                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                                   uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
+    shade_nee_step<INST, ABVH, true, true>(sc, lt, &ml, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter, max_depth, cap, sp, &env);
 }
 
 // After the shadow walk: every unoccluded shadow ray adds its contribution to its path's light radiance (at most one shadow
@@ -3344,16 +3557,28 @@ __global__ void __launch_bounds__(256) k_light_accum(DevScene sc, PrtLightBufs l
 // prt_sample_light: one light sample per (hit, key) through the render's own light_sample_term (throughput 1, no clamp) and,
 // for the same pair of vertices, the weight bsdf_hit_weight gives a scattered segment in direction w that meets the light;
 // out 11 floats per ray: w.xyz, tmax, contrib.rgb, pdf_light, pdf_bsdf, w_light, w_bsdf
-template <bool MESHL>
+template <bool MESHL, bool ENV = false>
 PRT_DEV void sample_light_test(DevScene sc, DevLights lt, const DevMeshLights* ml, uint32_t n, const float* __restrict__ in_d,
                                const PrtHit* __restrict__ hits, const uint32_t* __restrict__ keys, float* __restrict__ out,
-                               uint32_t* __restrict__ out_light) {
+                               uint32_t* __restrict__ out_light, const DevEnv* env = nullptr) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const PrtHit h = hits[i];
     float r[11] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     uint32_t light = 0xFFFFFFFFu;
-    if (h.prim >= 0 && sc.mat_type[h.material_id] == 1u && lt.n_lights) {
+    if (ENV && h.prim >= 0 && sc.mat_type[h.material_id] == 1u && (env->t_all | env->t_env) != 0u && env_selected(*env, keys[i])) {
+        const float4 a = sc.mat_rgbs[h.material_id];
+        LightSample s;
+        float pb = 0.0f, wl = 0.0f, wb = 1.0f;
+        f3 C;
+        if (env_sample_term(*env, lt.mode, mk3(h.normal[0], h.normal[1], h.normal[2]), mk3(a.x, a.y, a.z), mk3(1.f, 1.f, 1.f), keys[i], 0.0f,
+                            s, pb, wl, C)) {
+            light = s.light;
+            (void)env_miss(*env, lt.mode, s.w, pb, wb);
+            const float vals[11] = {s.w.x, s.w.y, s.w.z, s.tmax, C.x, C.y, C.z, s.pdf_l, pb, wl, wb};
+            for (int j = 0; j < 11; ++j) r[j] = vals[j];
+        }
+    } else if (h.prim >= 0 && sc.mat_type[h.material_id] == 1u && lt.n_lights) {
         const float4 a = sc.mat_rgbs[h.material_id];
         const f3 x = mk3(h.position[0], h.position[1], h.position[2]);
         LightSample s;
@@ -3385,6 +3610,35 @@ __global__ void k_sample_light_test_mesh(DevScene sc, DevLights lt, DevMeshLight
     sample_light_test<true>(sc, lt, &ml, n, in_d, hits, keys, out, out_light);
 }
 
+__global__ void k_sample_light_test_env(DevScene sc, DevLights lt, DevEnv env, uint32_t n, const float* __restrict__ in_d,
+                                        const PrtHit* __restrict__ hits, const uint32_t* __restrict__ keys, float* __restrict__ out,
+                                        uint32_t* __restrict__ out_light) {
+    sample_light_test<false, true>(sc, lt, nullptr, n, in_d, hits, keys, out, out_light, &env);
+}
+
+__global__ void k_sample_light_test_mesh_env(DevScene sc, DevLights lt, DevMeshLights ml, DevEnv env, uint32_t n,
+                                             const float* __restrict__ in_d, const PrtHit* __restrict__ hits,
+                                             const uint32_t* __restrict__ keys, float* __restrict__ out, uint32_t* __restrict__ out_light) {
+    sample_light_test<true, true>(sc, lt, &ml, n, in_d, hits, keys, out, out_light, &env);
+}
+
+// prt_environment_eval: the render's own lookup (env_radiance) per direction
+__global__ void k_environment_eval(DevEnv env, uint32_t n, const float* __restrict__ dirs, float* __restrict__ rgb,
+                                   uint32_t* __restrict__ texel, float* __restrict__ pdf_w) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const f3 d = mk3(dirs[3 * (size_t)i], dirs[3 * (size_t)i + 1], dirs[3 * (size_t)i + 2]);
+    float pw;
+    const f3 le = env_radiance(env, d, pw);
+    if (rgb) {
+        rgb[3 * (size_t)i + 0] = le.x;
+        rgb[3 * (size_t)i + 1] = le.y;
+        rgb[3 * (size_t)i + 2] = le.z;
+    }
+    if (texel) texel[i] = env_texel(env, d);
+    if (pdf_w) pdf_w[i] = pw;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Host launchers (plain functions; prt_api.cpp has no kernel syntax).
 // ---------------------------------------------------------------------------------------------------------
@@ -3392,10 +3646,22 @@ static inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + 255u) / 2
 
 void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, uint32_t n_paths,
                        uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
-                       uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix) {
+                       uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix, const DevEnv* env) {
     const uint32_t S = tm.n_pix_local ? n_paths / tm.n_pix_local : 0u;
     const uint32_t group = sp.jitter ? (uint32_t)RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
     const dim3 grid((tm.n_pix_local + PRODUCER_BLOCK - 1) / PRODUCER_BLOCK, (S + group - 1) / group);
+    if (env) {
+#define PRT_RAYGEN_ENV(J, AB)                                                                                           \
+    hipLaunchKernelGGL((k_raygen_env<J, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, *env, cam, tm, S, first_sample, seed, \
+                       out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp)
+        if (sc.abvh_nodes) {
+            if (sp.jitter) PRT_RAYGEN_ENV(true, true); else PRT_RAYGEN_ENV(false, true);
+        } else {
+            if (sp.jitter) PRT_RAYGEN_ENV(true, false); else PRT_RAYGEN_ENV(false, false);
+        }
+#undef PRT_RAYGEN_ENV
+        return;
+    }
 #define PRT_RAYGEN(J, SA, AB)                                                                                       \
     hipLaunchKernelGGL((k_raygen<J, SA, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, cam, tm, S, first_sample, seed,  \
                        out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp, nullptr)
@@ -3689,10 +3955,22 @@ void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& i
 
 void prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
                       uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap,
-                      uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary) {
+                      uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary, const DevEnv* env) {
     // n_rays_known: the ray count of this bounce if the host has it already (0xFFFFFFFF: size the grid for `cap`)
     const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
     const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
+    if (env) {
+#define PRT_SHADE_ENV(IN, AB)                                                                                              \
+    hipLaunchKernelGGL((k_shade_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, *env, in.o, in.d, in.t, in.hit, out.o, out.d, \
+                       out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp)
+        if (sc.abvh_nodes) {
+            if (sc.n_insts) PRT_SHADE_ENV(true, true); else PRT_SHADE_ENV(false, true);
+        } else {
+            if (sc.n_insts) PRT_SHADE_ENV(true, false); else PRT_SHADE_ENV(false, false);
+        }
+#undef PRT_SHADE_ENV
+        return;
+    }
 #define PRT_SHADE(F, SA, IN, AB)                                                                                    \
     hipLaunchKernelGGL((k_shade<F, SA, IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, in.o, in.d, in.t, in.hit, out.o, \
                        out.d, out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp, PrtPrimary{})
@@ -3782,9 +4060,32 @@ void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, con
 
 void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
                           const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
-                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known, const DevMeshLights* ml) {
+                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known, const DevMeshLights* ml,
+                          const DevEnv* env) {
     const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
     const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
+    if (env) {
+#define PRT_SHADE_NEE_ENV(IN, AB)                                                                                            \
+    hipLaunchKernelGGL((k_shade_nee_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *env, in.o, in.d, in.t, in.hit, out.o, \
+                       out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+#define PRT_SHADE_NEE_MESH_ENV(IN, AB)                                                                                        \
+    hipLaunchKernelGGL((k_shade_nee_mesh_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *ml, *env, in.o, in.d, in.t, in.hit, \
+                       out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+        if (ml) {
+            if (sc.abvh_nodes) {
+                if (sc.n_insts) PRT_SHADE_NEE_MESH_ENV(true, true); else PRT_SHADE_NEE_MESH_ENV(false, true);
+            } else {
+                if (sc.n_insts) PRT_SHADE_NEE_MESH_ENV(true, false); else PRT_SHADE_NEE_MESH_ENV(false, false);
+            }
+        } else if (sc.abvh_nodes) {
+            if (sc.n_insts) PRT_SHADE_NEE_ENV(true, true); else PRT_SHADE_NEE_ENV(false, true);
+        } else {
+            if (sc.n_insts) PRT_SHADE_NEE_ENV(true, false); else PRT_SHADE_NEE_ENV(false, false);
+        }
+#undef PRT_SHADE_NEE_MESH_ENV
+#undef PRT_SHADE_NEE_ENV
+        return;
+    }
 #define PRT_SHADE_NEE(IN, AB)                                                                                          \
     hipLaunchKernelGGL((k_shade_nee<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, in.o, in.d, in.t, in.hit, out.o,  \
                        out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
@@ -3819,10 +4120,23 @@ void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* 
 }
 
 void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
-                                  const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light, const DevMeshLights* ml) {
+                                  const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light, const DevMeshLights* ml,
+                                  const DevEnv* env) {
+    if (env) {
+        if (ml)
+            hipLaunchKernelGGL(k_sample_light_test_mesh_env, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, *ml, *env, n, in_d, hits, keys, out_f, out_light);
+        else
+            hipLaunchKernelGGL(k_sample_light_test_env, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, *env, n, in_d, hits, keys, out_f, out_light);
+        return;
+    }
     if (ml) {
         hipLaunchKernelGGL(k_sample_light_test_mesh, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, *ml, n, in_d, hits, keys, out_f, out_light);
         return;
     }
     hipLaunchKernelGGL(k_sample_light_test, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, n, in_d, hits, keys, out_f, out_light);
+}
+
+void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, const float* dirs, float* rgb, uint32_t* texel,
+                                 float* pdf_w) {
+    hipLaunchKernelGGL(k_environment_eval, dim3(blocks_for(n)), dim3(256), 0, st, env, n, dirs, rgb, texel, pdf_w);
 }

@@ -926,6 +926,118 @@ void prt_commit_instances(PrtHostScene* hs, const PrtInstanceUpdate& up, const P
     prt_rebuild_mesh_lights(hs, nullptr, instances);
 }
 
+// ---- the environment light (PrtEnvTables, prt_scene.h; contract: include/prt.h "Environment light") ----
+namespace {
+// thresholds floor(C_i / C_n * 2^32 + 0.5) of the running sums of w[0..n) as interval widths; false: no weight at all
+bool interval_widths(const double* w, uint32_t n, uint64_t* width) {
+    double total = 0.0;
+    for (uint32_t i = 0; i < n; ++i) total += w[i];
+    if (!(total > 0.0)) {
+        for (uint32_t i = 0; i < n; ++i) width[i] = 0;
+        return false;
+    }
+    double acc = 0.0;
+    uint64_t prev = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        acc += w[i];
+        uint64_t T = i + 1u == n ? 4294967296ull : (uint64_t)std::floor(acc / total * 4294967296.0 + 0.5);
+        if (T > 4294967296ull) T = 4294967296ull;
+        if (T < prev) T = prev;
+        width[i] = T - prev;
+        prev = T;
+    }
+    return true;
+}
+// thr[i] = T_{i+1} for i < last (every one below 2^32: a non-empty interval follows); returns last
+uint32_t search_table(const uint64_t* width, uint32_t n, uint32_t* thr) {
+    uint32_t last = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (width[i]) last = i;
+    uint64_t T = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        T += width[i];
+        thr[i] = i < last ? (uint32_t)T : 0xFFFFFFFFu;
+    }
+    return last;
+}
+}  // namespace
+
+int prt_build_environment(const PrtEnvironment* env, PrtEnvTables* out, std::string* err) {
+    if (!env->rgb) return fail(err, "environment: null image");
+    if (env->width == 0u || env->height == 0u) return fail(err, "environment: %u x %u", env->width, env->height);
+    if (env->width > PRT_ENV_MAX_WIDTH || env->height > PRT_ENV_MAX_HEIGHT)
+        return fail(err, "environment: %u x %u exceeds %u x %u", env->width, env->height, PRT_ENV_MAX_WIDTH, PRT_ENV_MAX_HEIGHT);
+    if (!(env->light_share >= 0.0f && env->light_share <= 1.0f)) return fail(err, "environment: light_share %g outside [0, 1]", (double)env->light_share);
+    const uint32_t W = env->width, H = env->height;
+    const size_t n = (size_t)W * H;
+    for (size_t k = 0; k < 3 * n; ++k)
+        if (!(env->rgb[k] >= 0.0f && env->rgb[k] <= FLT_MAX)) return fail(err, "environment: texel %zu is negative or not finite", k / 3);
+    PrtEnvTables t;
+    t.W = W;
+    t.H = H;
+    t.light_share = env->light_share;
+    t.texels.assign(4 * n, 0.0f);
+    const double kPi = 3.14159265358979323846;
+    std::vector<double> w(n), row_w(H);
+    for (uint32_t i = 0; i < H; ++i) {
+        const double omega = (2.0 * kPi / W) * (std::cos(kPi * i / H) - std::cos(kPi * (i + 1.0) / H));
+        double sum = 0.0;
+        for (uint32_t j = 0; j < W; ++j) {
+            const float* p = env->rgb + 3 * ((size_t)i * W + j);
+            w[(size_t)i * W + j] = (((double)p[0] + (double)p[1] + (double)p[2]) / 3.0) * omega;
+            sum += w[(size_t)i * W + j];
+            for (int ch = 0; ch < 3; ++ch) t.texels[4 * ((size_t)i * W + j) + ch] = p[ch];
+        }
+        row_w[i] = sum;
+    }
+    std::vector<uint64_t> rw(H), cw(n);
+    if (interval_widths(row_w.data(), H, rw.data())) {
+        for (uint32_t i = 0; i < H; ++i) interval_widths(&w[(size_t)i * W], W, &cw[(size_t)i * W]);
+        t.row_thr.resize(H);
+        t.col_thr.resize(n);
+        t.col_last.resize(H);
+        t.row_last = search_table(rw.data(), H, t.row_thr.data());
+        const double k_pdf = (double)W * (double)H / (2.0 * kPi * kPi);
+        for (uint32_t i = 0; i < H; ++i) {
+            t.col_last[i] = search_table(&cw[(size_t)i * W], W, &t.col_thr[(size_t)i * W]);
+            for (uint32_t j = 0; j < W; ++j) {
+                const uint64_t c = rw[i] ? cw[(size_t)i * W + j] : 0u;
+                if (c) ++t.n_sampled;
+                // p_ij = rw cw / 2^64: both factors are integers <= 2^32, exact in double; the product is rounded once
+                const double p = ((double)rw[i] / 4294967296.0) * ((double)c / 4294967296.0);
+                t.texels[4 * ((size_t)i * W + j) + 3] = (float)(p * k_pdf);
+            }
+        }
+        t.row_width = std::move(rw);
+        t.col_width = std::move(cw);
+    }
+    *out = std::move(t);
+    return PRT_OK;
+}
+
+uint64_t prt_environment_threshold(const PrtEnvTables& env, uint32_t n_lights) {
+    if (!env.W || env.row_width.empty() || !(env.light_share > 0.0f)) return 0u;
+    if (n_lights == 0u) return 4294967296ull;
+    return (uint64_t)std::floor((double)env.light_share * 4294967296.0 + 0.5);
+}
+
+float prt_scaled_pmf(double pmf, uint64_t t_env) { return (float)(pmf * ((double)(4294967296ull - t_env) / 4294967296.0)); }
+
+void prt_scaled_light_tables(const PrtHostScene& hs, uint64_t t_env, std::vector<float>* lights, std::vector<float>* ml_records) {
+    if (lights) {
+        *lights = hs.lights;
+        double total = 0.0;
+        for (double pw : hs.light_power) total += pw;  // (build_light_table's sum)
+        for (size_t l = 0; t_env && l < hs.light_power.size(); ++l)
+            (*lights)[4 * PRT_LIGHT_F4 * l + 7] = prt_scaled_pmf(hs.light_power[l] / total, t_env);
+    }
+    if (ml_records) {
+        *ml_records = hs.ml.records;
+        for (size_t v = 0; t_env && v < hs.ml.visible.size(); ++v)
+            (*ml_records)[4 * PRT_LIGHT_F4 * (size_t)hs.ml.visible[v] + 7] = prt_scaled_pmf((double)hs.ml.width[v] / 4294967296.0, t_env);
+    }
+}
+
 int prt_check_scene_arrays(const PrtSceneDesc* s, std::string* err) {
     if ((s->n_materials && !s->materials) || (s->n_primitives && !s->primitives) || (s->n_meshes && !s->meshes) ||
         (s->n_instanced_meshes && !s->instanced_meshes) || (s->n_instances && !s->instances))

@@ -53,6 +53,27 @@ struct PrtMeshLights {
     uint32_t n_emitters_unsampled = 0;
 };
 
+// The environment light (include/prt.h "Environment light"): the image and its sampling tables, a property of the
+// context, not of a scene.  Built on the host in double.
+struct PrtEnvTables {
+    uint32_t W = 0, H = 0;           // 0 x 0: no environment
+    float light_share = 0.0f;
+    std::vector<float> texels;       // 4 floats per texel: rgb, fl(p_ij W H / (2 pi^2)) = pdf_w x sin(theta)
+    std::vector<uint64_t> row_width; // R_i - R_{i-1}; empty: no distribution
+    std::vector<uint64_t> col_width; // C_ij - C_{i,j-1}, H x W
+    std::vector<uint32_t> row_thr;   // row_thr[i] = R_{i+1} for i < row_last: the row is "smallest i with r < row_thr[i], else row_last"
+    std::vector<uint32_t> col_thr;   // H x W, col_thr[i W + j] = C_{i,j+1} for j < col_last[i]
+    std::vector<uint32_t> col_last;  // per row: the last column with a non-empty interval
+    uint32_t row_last = 0;           // the last row with a non-empty interval
+    uint32_t n_sampled = 0;          // texels with a non-empty interval
+};
+// Checks `env` (PRT_ERR_INVALID, message in *err, *out untouched) and builds its tables.
+int prt_build_environment(const PrtEnvironment* env, PrtEnvTables* out, std::string* err);
+// T_e for an environment and a light set of n_lights lights (0 without an environment).
+uint64_t prt_environment_threshold(const PrtEnvTables& env, uint32_t n_lights);
+// fl32(pmf (2^32 - T_e) / 2^32) for a pmf given in double
+float prt_scaled_pmf(double pmf, uint64_t t_env);
+
 // One instanced mesh of a compiled scene: what moving its copies needs to know about it (prt_update_instances)
 struct PrtPlacedMesh {
     float mn[3], mx[3];  // its box in its own space
@@ -93,6 +114,10 @@ struct PrtHostScene {
     uint32_t ml_tris_counted = 0;      // the part of n_emitters_unsampled that is mesh / placed triangles
     PrtMeshLights ml;                  // the light set with emissive triangles in it (PRT_LIGHT_SOURCES_MESH)
 };
+
+// The light tables as the kernels get them under an environment with threshold t_env: copies of hs.lights / hs.ml.records
+// whose pmf entries are prt_scaled_pmf of the exact pmf (t_env = 0: the tables themselves).  Either output may be null.
+void prt_scaled_light_tables(const PrtHostScene& hs, uint64_t t_env, std::vector<float>* lights, std::vector<float>* ml_records);
 
 // The device-side builder of the 8-wide tree over n triangles given as 9 floats each (+ normals, + a material per
 // triangle; both may be null): nodes8 / depth and the triangle / normal records in the tree's slot order come back

@@ -206,6 +206,25 @@ public:
     }
     // Which emitters the light set holds: PRT_LIGHT_SOURCES_ANALYTIC (default) or ANALYTIC | MESH (emissive triangles too)
     void SetLightSources(uint32_t mask) { check(prt_group_set_light_sources(grp_, mask)); }
+    // Environment light (PrtEnvironment): rgb = height * width * 3 floats, row 0 = the +Y pole; null = the constant sky again
+    void SetEnvironment(const float* rgb, uint32_t width, uint32_t height, float light_share = 0.5f) {
+        if (!rgb) {
+            check(prt_group_set_environment(grp_, nullptr));
+            return;
+        }
+        const PrtEnvironment e{rgb, width, height, light_share};
+        check(prt_group_set_environment(grp_, &e));
+    }
+    // ... from a colour PFM file (prt_read_pfm)
+    void SetEnvironmentPfm(const std::string& path, float light_share = 0.5f) {
+        float* rgb = nullptr;
+        uint32_t w = 0, h = 0;
+        if (prt_read_pfm(path.c_str(), &rgb, &w, &h)) throw Error("cannot read " + path + " as a colour PFM");
+        const PrtEnvironment e{rgb, w, h, light_share};
+        const int rc = prt_group_set_environment(grp_, &e);
+        prt_image_free(rgb);
+        check(rc);
+    }
     PrtLightStats LightStats() {
         PrtLightStats s{};
         check(prt_group_get_light_stats(grp_, &s));

@@ -398,6 +398,34 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_set_light_sources(self._ctx, m))
         return m
 
+    def set_environment(self, rgb, light_share: float = 0.5):
+        """Environment light (include/prt.h "Environment light"): rgb [H, W, 3] lat-long radiance, row 0 = the +Y pole; None
+        = back to the scene's constant sky.  light_share = the probability that a light sample goes to the image."""
+        self._check(_set_environment(capi.lib().prt_set_environment, self._ctx, rgb, light_share))
+
+    def environment_info(self) -> "capi.PrtEnvironmentInfo":
+        s = capi.PrtEnvironmentInfo()
+        self._check(capi.lib().prt_environment_info(self._ctx, C.byref(s)))
+        return s
+
+    def environment_intervals(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The exact interval widths (row [H] uint64, column [H, W] uint64); texel pmf = row x column / 2^64.  Host-only
+        contexts too."""
+        i = self.environment_info()
+        row, col = np.zeros(i.height, np.uint64), np.zeros((i.height, i.width), np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._check(capi.lib().prt_environment_intervals(self._ctx, row.ctypes.data_as(u64p), col.ctypes.data_as(u64p)))
+        return row, col
+
+    def environment_eval(self, dirs) -> dict:
+        """prt_environment_eval: the render's own lookup per unit direction: rgb [n, 3], texel [n] (i * W + j), pdf_w [n]."""
+        d = _f32(dirs).reshape(-1, 3)
+        n = d.shape[0]
+        rgb, texel, pdf = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        self._check(capi.lib().prt_environment_eval(self._ctx, n, d.ctypes.data_as(_fp), rgb.ctypes.data_as(_fp),
+                                                    texel.ctypes.data_as(_u32p), pdf.ctypes.data_as(_fp)))
+        return {"rgb": rgb, "texel": texel, "pdf_w": pdf}
+
     def light_intervals(self) -> np.ndarray:
         """With "all": the integer width T_l - T_{l-1} of every light's interval ([n] uint64); pmf = width / 2^32 exactly."""
         n = C.c_uint32(0)
@@ -789,6 +817,10 @@ class HipWavefrontGroupRenderer:
         self._check(capi.lib().prt_group_set_light_sources(self._grp, m))
         return m
 
+    def set_environment(self, rgb, light_share: float = 0.5):
+        """HipWavefrontRenderer.set_environment on every rank."""
+        self._check(_set_environment(capi.lib().prt_group_set_environment, self._grp, rgb, light_share))
+
     def light_info(self) -> Tuple[np.ndarray, np.ndarray]:
         """The light set as rank 0 holds it (every rank holds the same)."""
         L = capi.lib()
@@ -821,6 +853,28 @@ class HipWavefrontGroupRenderer:
         s = PrtStats()
         self._check(capi.lib().prt_group_get_stats(self._grp, C.byref(s)))
         return s
+
+
+def _set_environment(fn, handle, rgb, light_share) -> int:
+    if rgb is None:
+        return fn(handle, None)
+    a = _f32(rgb)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("environment: rgb must be [H, W, 3]")
+    e = capi.PrtEnvironment(a.ctypes.data_as(_fp), a.shape[1], a.shape[0], float(light_share))
+    return fn(handle, C.byref(e))
+
+
+def read_pfm(path: str) -> np.ndarray:
+    """prt_read_pfm: a colour PFM as [H, W, 3] float32, top row first."""
+    p, w, h = _fp(), C.c_uint32(0), C.c_uint32(0)
+    rc = capi.lib().prt_read_pfm(path.encode(), C.byref(p), C.byref(w), C.byref(h))
+    if rc:
+        raise PrtError(f"prt_read_pfm({path}) failed ({rc})")
+    try:
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3)).copy()
+    finally:
+        capi.lib().prt_image_free(p)
 
 
 def write_ppm(path: str, rgba8: np.ndarray):
