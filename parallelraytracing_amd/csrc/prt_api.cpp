@@ -103,6 +103,8 @@ struct PrtContext {
     float pad_coeff = kPadCoeff;  // prt_set_param("pad_log2", n): culling pad = 2^-n of the coordinates' magnitude (A/B; before prt_set_scene)
     int node_stride = 0;      // prt_set_param("node_stride", 5 | 8): uint4 per 8-wide node slot, 0 = by tree size (upload_scene); before prt_set_scene
     int compact_primary = 1;  // prt_set_param("compact_primary", 0): k_raygen stores full ray records (A/B)
+    int primary_walk = 1;     // prt_set_param("primary_walk", 0): compact primary rays are walked once per sample, not once per pixel (A/B)
+    bool batch_walked = false;  // the last run_batch took the one-walk-per-pixel route (prt_measure_traversal counts its list)
     int gpu_build = 0;  // prt_set_param("gpu_build", 1): the next prt_set_scene builds the 8-wide tree on the device
     PrtSampling sampling{0u, 0u, 0.0f};
     // grid 256 CUs x 4 blocks, 256-ray chunks, refill at 16 idle lanes, leave the node loop at <= 16 walkers, triangle
@@ -465,6 +467,7 @@ f3 h_cross(f3 a, f3 b) { return f3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x,
 int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, uint32_t first_sample, bool accumulate,
               unsigned long long* trav_stats) {
     const uint64_t n_paths64 = (uint64_t)S_cur * c->tm.n_pix_local;
+    c->batch_walked = false;
     if (n_paths64 == 0) return PRT_OK;
     if (n_paths64 > 0xFFFFFF00ull) return fail(c, PRT_ERR_INVALID, "too many paths in flight");
     const uint32_t n_paths = (uint32_t)n_paths64;
@@ -549,11 +552,19 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
         if ((rc = ensure_light_state(c, n_paths))) return rc;
         HIPCHECK(c, hipMemsetAsync(c->lb.lrad, 0, (size_t)n_paths * sizeof(float4), c->stream));
     }
+    // One walk per pixel (PrtPrimary): bounce 0's traversal runs over the list of front pixels that k_raygen writes into
+    // rb[0].hd2, counted in word PRT_CNT_LIST of bounce 0's counters (zeroed above), and leaves its hits in rb[0].hit per list
+    // slot.  A batch of ONE sample keeps its path slots: they ARE that list (one path per pixel, in the same order), and
+    // k_raygen saves the second store and atomic.
+    const bool walk = compact && c->primary_walk && S_cur > 1u;
+    c->batch_walked = walk;
     const PrtPrimary primary{(const uint32_t*)c->rb[0].t, c->d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, c->tm.n_pix_local,
-                             1.0f / (float)c->tm.n_pix_local, first_sample, seed};
+                             1.0f / (float)c->tm.n_pix_local, first_sample, seed, walk ? 1u : 0u};
+    PrtPrimary primary_list = primary;  // what the traversal sees: list slots in place of path slots
+    if (walk) primary_list.pid = (const uint32_t*)c->rb[0].hd2;
     if ((rc = begin_event(c, 0, &ep))) return rc;
     prt_launch_raygen(c->stream, c->dsc, c->cam, c->tm, n_paths, first_sample, seed, c->rb[0], c->d_rad, c->d_counts,
-                      c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr, envp);
+                      c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr, envp, walk);
     if ((rc = end_event(c, &ep))) return rc;
     if (exact) HIPCHECK(c, read_back(0));
     for (uint32_t d = 0; d < max_depth; ++d) {
@@ -591,8 +602,12 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                         tune.perm = q + 3 * (size_t)n_paths;
                     }
                 }
-                prt_launch_traverse(c->stream, c->dsc, in, front_count, c->d_work, c->d_spill, n_paths, c->hs.bvh.max_depth,
-                                    c->hs.bvh.max_stack4, tune, trav_stats, (compact && d == 0) ? &primary : nullptr);
+                if (walk && d == 0)
+                    prt_launch_traverse(c->stream, c->dsc, in, c->d_counts + PRT_CNT_LIST, c->d_work, c->d_spill, c->tm.n_pix_local,
+                                        c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune, trav_stats, &primary_list);
+                else
+                    prt_launch_traverse(c->stream, c->dsc, in, front_count, c->d_work, c->d_spill, n_paths, c->hs.bvh.max_depth,
+                                        c->hs.bvh.max_stack4, tune, trav_stats, (compact && d == 0) ? &primary : nullptr);
             }
             else
                 prt_launch_intersect(c->stream, c->dsc, in, front_count, n_paths, stack_depth, c->variant, trav_stats);
@@ -1939,7 +1954,8 @@ int prt_measure_traversal(PrtContext* c, uint32_t max_depth, uint32_t seed, uint
     memset(out, 0, sizeof(*out));
     uint64_t front = 0;
     for (uint32_t d = 0; d < max_depth; ++d) {
-        front += cnt[(size_t)d * PRT_CNT_STRIDE];  // rays handed to the traversal kernel in bounce iteration d
+        // rays handed to the traversal kernel in bounce iteration d (bounce 0 with one walk per pixel: the front-pixel list)
+        front += cnt[(size_t)d * PRT_CNT_STRIDE + ((d == 0 && c->batch_walked) ? PRT_CNT_LIST : 0u)];
         out->rays_per_depth[d] = after[d] - before[d];
         out->rays_total += out->rays_per_depth[d];
     }
@@ -2060,6 +2076,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "path_max" && value >= 1) c->tune.path_max = (uint32_t)value;
     else if (n == "sort_rays" && value >= 0 && value <= 2) c->sort_rays = (uint32_t)value;
     else if (n == "compact_primary" && (value == 0 || value == 1)) c->compact_primary = value;
+    else if (n == "primary_walk" && (value == 0 || value == 1)) c->primary_walk = value;
     else if (n == "node_stride" && (value == 0 || value == 5 || value == 8)) c->node_stride = value;
     else if (n == "pad_log2" && value >= 8 && value <= 22) c->pad_coeff = std::ldexp(1.0f, -value);
     else if (n == "tail" && value >= 0 && value <= 64) c->tune.tail = (uint32_t)value;

@@ -112,18 +112,26 @@ struct PrtRayBuf {
 // distance) instead of 56 B plus ONE 16-B record per pixel (direction, pixel index), and the first bounce's traversal
 // and k_shade rebuild the ray from those (C3: 372 M stored primary rays per 256-spp batch = 16 GB less written by
 // k_raygen and 12 GB less read by the first k_shade; round 3: the analytic scan's hit of a primary ray is per pixel too, so a
-// path's slot holds its id only).  Every primary ray is still traced on its own.  pid aliases the
-// `t` array of the ray buffer (first 4 bytes per slot).
+// path's slot holds its id only).  pid aliases the `t` array of the ray buffer (first 4 bytes per slot).
+// One walk per pixel (walk = 1, the default; prt_set_param("primary_walk", 0) restores one walk per sample): all samples
+// of a pixel share the pixel-centre ray, so k_raygen also writes a dense LIST of the front pixels (local pixel index = the
+// path id of the pixel's sample 0; its counter is word PRT_CNT_LIST of bounce 0's counters), the first traversal runs
+// over that list (its PrtPrimary has pid = the list) and leaves the closest hit in hit[list slot], and the first k_shade
+// and k_primary_hit take a front path's hit from there through the pixel's end record.  The list lives in the hd2 array of
+// bounce 0's ray buffer and the hits in its hit array: compact k_raygen writes neither per ray slot.
 struct PrtPrimary {
-    const uint32_t* pid;  // path id per ray slot
+    const uint32_t* pid;  // path id per ray slot (the traversal's copy with walk = 1: per list slot)
     const float4* pix;    // per local pixel: camera-ray direction, pixel index y * W + x (bits); then n_pix_local more records:
                           // what the pixel's paths deliver if they end with their primary ray (read by k_accumulate; for
-                          // pixels whose paths go on: x = ray slot of the first stored sample); then 2 x n_pix_local more:
-                          // the primary hit's surface interaction (k_primary_hit): {position, hit id}, {normal, material | front << 31}
+                          // pixels whose paths go on: y, z = the analytic scan's hit and distance^2, x = the pixel's list
+                          // slot, 0xFFFFFFFF for a back pixel; with walk = 0 the ray slot of the first stored sample); then
+                          // 2 x n_pix_local more: the primary hit's surface interaction (k_primary_hit): {position, hit id},
+                          // {normal, material | front << 31}
     float origin[3];      // camera position
     uint32_t n_pix_local;
     float inv_n;          // 1 / n_pix_local (first guess of path id / n_pix_local, corrected exactly)
     uint32_t first_sample, seed;
+    uint32_t walk;        // 1: the first traversal walked one ray per front pixel (hit[] is indexed by list slot), 0: one per path slot
 };
 
 // The PATH instance of k_traverse8_persistent (small batches: the reference's one sample per ProgressiveRender call): ONE
@@ -139,6 +147,7 @@ struct PrtPathArgs {
 };
 
 #define PRT_CNT_STRIDE 64u  // uint32 per bounce in the counter array: [0] front, [32] back, [16] finished-in-producer counts, [48] shadow rays (lighting modes)
+#define PRT_CNT_LIST 8u     // bounce 0 only: entries of the front-pixel list (PrtPrimary, walk = 1)
 
 // Light table (PrtLighting, include/prt.h), read-only, PRT_LIGHT_F4 = 5 (prt_scene_pod.h) x float4 per light:
 //   [0] centre.xyz, R (sphere) | area w h s^2 (quad)   [1] edge u = w * column 0 of Mat, pmf   [2] edge v = h * column 2, cdf
@@ -198,7 +207,8 @@ struct PrtLightBufs {
 void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, uint32_t n_paths,
                        uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
                        uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix = nullptr,
-                       const DevEnv* env = nullptr);  // env: the instance with an environment image (never compact)
+                       const DevEnv* env = nullptr,  // env: the instance with an environment image (never compact)
+                       bool primary_walk = false);   // compact only: write the front-pixel list into out.hd2 (PrtPrimary)
 void prt_launch_scan_prims(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                            uint32_t* work, uint32_t max_rays, unsigned long long* stats);
 void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,

@@ -312,7 +312,8 @@ PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr,
 
 // All S samples of a pixel start with the same pixel-centre ray (no jitter: cpu/renderer.cpp:45), so one thread
 // computes the camera ray and its classification once and emits it for RAYGEN_GROUP samples, each with its own RNG
-// seed and path id; every sample's primary ray is still traced on its own by the traversal kernel.
+// seed and path id.  With compact primary rays the traversal kernel walks the ray once per pixel (PrtPrimary, walk = 1);
+// on every other route each sample's primary ray is still traced on its own.
 #define RAYGEN_GROUP 8
 #ifndef RAYGEN_ALLOC
 #define RAYGEN_ALLOC 4  // jittered rays per slot reservation (divides RAYGEN_GROUP)
@@ -373,6 +374,20 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
         const uint32_t slot0 = block_alloc2<PRODUCER_BLOCK>(front, back, false, &CNT_A(counts, 0), &CNT_B(counts, 0),
                                                             &CNT_C(counts, 0), n_paths, s1 - s0, &stride, &base);
         uint32_t first_slot = slot0;  // slot of this pixel's sample s0
+        // One walk per pixel (PrtPrimary, walk = 1; hd2 is then the list, else null): the block's front pixels go on the
+        // dense list the first traversal runs over, in the order block_alloc2 ranked them (its ballots; one more atomic
+        // per block).  Entry = the local pixel index = the path id of the pixel's sample 0.
+        const bool walk = COMPACT && hd2 != nullptr;
+        uint32_t list_slot = 0xFFFFFFFFu;  // (what a stored back pixel's record carries)
+        if (walk && blockIdx.y == 0) {  // block-uniform
+            __shared__ uint32_t s_list_base;
+            if (front && slot0 == base) s_list_base = atomicAdd(&counts[PRT_CNT_LIST], stride);
+            __syncthreads();
+            if (front) {
+                list_slot = s_list_base + (slot0 - base);
+                ((uint32_t*)hd2)[list_slot] = pl;
+            }
+        }
         if (s1 - s0 < 8u) {
             // few samples per pixel in this batch (interactive use: ProgressiveRender adds ONE sample per call): SAMPLE-major
             // slots, every thread stores its own pixel's copies, coalesced across the pixels of a wave
@@ -397,7 +412,8 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
             // PIXEL-major slots: the (up to 64) samples of a pixel that this block handles sit next to each other, so a
             // wave of the first bounce's traversal / k_shade works on IDENTICAL rays: no divergence in the node loop (and,
             // with placed copies, level switches in lockstep), one cache line per node for the whole wave, one triangle /
-            // one material per wave in k_shade.  Each of them is still traced on its own.  Written wave-transposed (pixel
+            // one material per wave in k_shade.  (Full records: each of them is traced on its own; compact: the first
+            // traversal walks the front-pixel list instead, one ray per pixel.)  Written wave-transposed (pixel
             // by pixel, one sample per lane): 256-B stores of path ids (COMPACT) or 1-KB stores of full records.
             const uint32_t mult = s1 - s0;
             const bool stored = slot0 != 0xFFFFFFFFu;
@@ -445,11 +461,12 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
             if (COMPACT) {
                 // whether the pixel's paths end with their primary ray, and with what, is the same for all its samples: one
                 // record per pixel (w = 0xFFFFFFFE: they go on, look in rad[]) instead of S copies in rad[]
-                // (a "they go on" record: x = the ray slot of the pixel's first stored sample, for k_primary_hit; y, z = the
-                // analytic scan's closest hit and its distance^2, the same for every sample of the pixel: the paths' slots
-                // carry the path id only, 4 B instead of 12)
+                // (a "they go on" record: x = where the pixel's walked hit will be, for k_primary_hit and the first k_shade:
+                // the pixel's list slot, 0xFFFFFFFF for a back pixel (one walk per sample: the ray slot of the pixel's first
+                // stored sample); y, z = the analytic scan's closest hit and its distance^2, the same for every sample of
+                // the pixel: the paths' slots carry the path id only, 4 B instead of 12)
                 if (in_range && blockIdx.y == 0)
-                    pix[tm.n_pix_local + pl] = stored ? make_float4(__uint_as_float(first_slot), __uint_as_float(id0), d2_0, __uint_as_float(0xFFFFFFFEu)) : L0;
+                    pix[tm.n_pix_local + pl] = stored ? make_float4(__uint_as_float(walk ? list_slot : first_slot), __uint_as_float(id0), d2_0, __uint_as_float(0xFFFFFFFEu)) : L0;
             } else if (in_range && !stored) {
                 // the path ended with its primary ray (sky / light seen directly), or there is none
                 for (uint32_t sl = s0; sl < s1; ++sl) rad[sl * tm.n_pix_local + pl] = L0;
@@ -2503,13 +2520,16 @@ PRT_DEV void shade_step(DevScene sc, const float4* __restrict__ ro, const float4
     float4 pre_a = make_float4(0.f, 0.f, 0.f, 0.f), pre_b = pre_a;
     if (k < count) {
         const uint32_t src = k < nA ? k : cap - 1u - (k - nA);  // front part, then back part
-        uint32_t id = (PRIM && k >= nA) ? HIT_MISS : ld_stream(&hit[src]);
+        uint32_t id = (PRIM && (k >= nA || pr.walk)) ? HIT_MISS : ld_stream(&hit[src]);
         if (PRIM) {
             pid = ld_stream(&pr.pid[src]);
             uint32_t pixel, sample, lp;
             primary_ray(pr, pid, o, d, pixel, sample, &lp);
-            // a back-side primary ray was never walked: its closest hit is the analytic scan's, kept per pixel (k_raygen)
+            // a back-side primary ray was never walked: its closest hit is the analytic scan's, kept per pixel (k_raygen);
+            // a front-side one was walked once for its pixel (walk = 1): the hit sits at the pixel's list slot (in big
+            // batches a wave holds the samples of one pixel: both loads are wave-uniform)
             if (k >= nA) id = __float_as_uint(pr.pix[pr.n_pix_local + lp].y);
+            else if (pr.walk) id = hit[__float_as_uint(pr.pix[pr.n_pix_local + lp].x)];
             rng = path_seed(pixel, pr.first_sample + sample, pr.seed);
             depth = 0u;
             thr = mk3(1.f, 1.f, 1.f);
@@ -2571,11 +2591,11 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_env(DevScene sc, DevEnv e
 }
 
 // Compact primary rays: the surface interaction of a pixel's primary hit, ONCE per pixel.  Without jitter every sample of
-// a pixel traces the same pixel-centre ray (cpu/renderer.cpp:45) -- each of them through the traversal kernel on its own --
-// and finds the same closest hit, so the first k_shade of a batch used to rebuild the same position / normal / material
-// (Triangle::Intersect or the analytic shape again: ~150 wave instructions) once per SAMPLE; a wave there holds 64 samples
-// of one pixel.  This kernel rebuilds it per PIXEL from the hit id of the pixel's first stored sample, and k_shade<PRIM>
-// uses the record for every sample whose own hit id equals the record's (otherwise it computes the hit itself).
+// a pixel traces the same pixel-centre ray (cpu/renderer.cpp:45) and finds the same closest hit, so the first k_shade of a
+// batch used to rebuild the same position / normal / material (Triangle::Intersect or the analytic shape again: ~150 wave
+// instructions) once per SAMPLE; a wave there holds 64 samples of one pixel.  This kernel rebuilds it per PIXEL from the
+// pixel's walked hit (pr.walk: hit[list slot]; one walk per sample: the hit of the pixel's first stored sample), and
+// k_shade<PRIM> uses the record for every sample whose own hit id equals the record's (otherwise it computes the hit itself).
 __global__ void __launch_bounds__(256) k_primary_hit(DevScene sc, PrtPrimary pr, const uint32_t* __restrict__ hit,
                                                      float4* __restrict__ pix, const uint32_t* __restrict__ counts) {
     const uint32_t pl = blockIdx.x * 256u + threadIdx.x;
@@ -2583,10 +2603,11 @@ __global__ void __launch_bounds__(256) k_primary_hit(DevScene sc, PrtPrimary pr,
     const float4 E = pix[pr.n_pix_local + pl];
     float4 a = make_float4(0.f, 0.f, 0.f, __uint_as_float(HIT_DEAD)), b = make_float4(0.f, 0.f, 0.f, 0.f);  // no record
     if (__float_as_uint(E.w) == 0xFFFFFFFEu) {  // the pixel's paths were stored
-        // front-side slots (below the front count) were walked: their hit is the traversal's; back-side paths keep the
-        // analytic scan's hit of the pixel's record
+        // front pixels (a list slot, not the sentinel; one walk per sample: a ray slot below the front count) were walked:
+        // their hit is the traversal's; back-side paths keep the analytic scan's hit of the pixel's record
         const uint32_t first = __float_as_uint(E.x);
-        const uint32_t id = first < CNT_A(counts, 0) ? hit[first] : __float_as_uint(E.y);
+        const bool walked = pr.walk ? first != 0xFFFFFFFFu : first < CNT_A(counts, 0);
+        const uint32_t id = walked ? hit[first] : __float_as_uint(E.y);
         if (id != HIT_MISS && id != HIT_DEAD) {
             const float4 P = pix[pl];
             WorldHit w;
@@ -2618,11 +2639,12 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_divstats(DevScene sc, con
     if (k < count) {
         const uint32_t src = k < nA ? k : cap - 1u - (k - nA);
         uint32_t id;
-        if (compact && k >= nA) {  // compact primary rays: a back-side path's hit is its pixel's analytic one (k_shade<PRIM>)
+        if (compact && (k >= nA || pr.walk)) {  // compact primary rays: a back-side path's hit is its pixel's analytic one, a front-side one its pixel's walked one (k_shade<PRIM>)
             f3 o_, d_;
             uint32_t pixel, sample, lp;
             primary_ray(pr, pr.pid[src], o_, d_, pixel, sample, &lp);
-            id = __float_as_uint(pr.pix[pr.n_pix_local + lp].y);
+            const float4 E = pr.pix[pr.n_pix_local + lp];
+            id = k >= nA ? __float_as_uint(E.y) : hit[__float_as_uint(E.x)];
         } else {
             id = hit[src];
         }
@@ -3646,7 +3668,8 @@ static inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + 255u) / 2
 
 void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, uint32_t n_paths,
                        uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
-                       uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix, const DevEnv* env) {
+                       uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix, const DevEnv* env,
+                       bool primary_walk) {
     const uint32_t S = tm.n_pix_local ? n_paths / tm.n_pix_local : 0u;
     const uint32_t group = sp.jitter ? (uint32_t)RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
     const dim3 grid((tm.n_pix_local + PRODUCER_BLOCK - 1) / PRODUCER_BLOCK, (S + group - 1) / group);
@@ -3671,8 +3694,10 @@ void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam,
     } else if (sp.jitter) {
         if (sa) PRT_RAYGEN(true, true, false); else PRT_RAYGEN(true, false, false);
     } else if (compact_pix && !sa) {
+        // (the compact instance stores nothing in hit / hd2 per ray slot: its hd2 argument is the front-pixel list, or null)
         hipLaunchKernelGGL((k_raygen<false, false, false, true>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, cam, tm, S, first_sample,
-                           seed, out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp, compact_pix);
+                           seed, out.o, out.d, out.t, out.hit, primary_walk ? out.hd2 : nullptr, rad, counts, work, max_depth, sp,
+                           compact_pix);
     } else {
         if (sa) PRT_RAYGEN(false, true, false); else PRT_RAYGEN(false, false, false);
     }
