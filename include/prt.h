@@ -127,7 +127,7 @@ typedef struct PrtSceneDesc {
 } PrtSceneDesc;
 
 /* Pinhole camera; right/up are derived exactly as Camera::Camera does (src/core/camera.h:10-16);
- * vertical FoV is fixed at 1 rad (src/core/camera.h:111). */
+ * vertical FoV is 1 rad (src/core/camera.h:111) unless PrtLens below sets another. */
 typedef struct PrtCameraDesc {
     float position[3];
     float front[3];
@@ -147,6 +147,36 @@ typedef struct PrtSampling {
     uint32_t rr_depth;
     float clamp;
 } PrtSampling;
+
+/* Thin lens and field of view (prt_set_lens; NULL = all zero = the pinhole above with its 1 rad, bit for bit).  A property
+ * of the context like PrtSampling: kept across prt_set_camera, prt_set_scene and prt_set_film, host-only contexts too
+ * (they only record it).  PrtCameraDesc is not touched.
+ *  fov_y          vertical field of view in radians, 0 < fov_y < pi; 0 = the reference's 1 rad
+ *  aperture       lens RADIUS in world units, >= 0; 0 = pinhole
+ *  focus_distance distance along `front` of the plane in focus (the plane perpendicular to `front`, not a sphere round
+ *                 the camera); > 0 required while aperture > 0, ignored otherwise
+ * Arithmetic (fp32, no contraction, in this order):
+ *    tan_fov_y = tanf(0.5f * fov_y), or tanf(0.5f) when fov_y == 0
+ *    ndcX = (px / W) * 2 - 1, ndcY = 1 - (py / H) * 2, aspect = W / H      (Camera::GetCameraRay, as before)
+ *    pcx = ndcX * aspect * tan_fov_y, pcy = ndcY * tan_fov_y
+ *  aperture == 0: the pinhole ray, d = normalize3(dc.x right + dc.y up + dc.z (-front)) with dc = normalize3((pcx, pcy,
+ *    -1)), o = pos; no RNG draw.
+ *  aperture > 0:
+ *    u3 = rnd01(rng); u4 = rnd01(rng)      after the two jitter draws when jitter is on, else the path's first two draws
+ *    r = aperture * sqrtf(u3), phi = 6.2831855f * u4, lx = r * cosf(phi), ly = r * sinf(phi)
+ *    dc = normalize3((pcx * focus - lx, pcy * focus - ly, -focus))
+ *    d = normalize3(dc.x * right + dc.y * up + dc.z * (-front))
+ *    o = pos + lx * right + ly * up        ((pos + lx * right) + ly * up, component-wise)
+ *    Without jitter (px, py) is the pixel centre.  The rest of the path is draw for draw what it is without a lens, from
+ *    the advanced state.
+ * Routes: with aperture > 0 every batch generates one full ray record per sample (what jitter does); compact primary rays,
+ * the one-walk-per-pixel list and the one-launch path instance are not taken.  With aperture == 0 a fov_y only changes
+ * tan_fov_y and every route stays available.  Results never depend on a tunable. */
+typedef struct PrtLens {
+    float fov_y;
+    float aperture;
+    float focus_distance;
+} PrtLens;
 
 /* Next-event estimation toward analytic emitters (DESIGN.md §3 "Light sampling"); NULL / mode OFF = the reference's
  * estimator, where direct light is found only by a scattered ray that hits an emitter.
@@ -411,6 +441,11 @@ int prt_render_async(PrtContext* ctx, uint32_t spp, uint32_t max_depth, uint32_t
 int prt_synchronize(PrtContext* ctx);
 /* Sampling upgrades for the following prt_render calls (NULL = all off). */
 int prt_set_sampling(PrtContext* ctx, const PrtSampling* sampling);
+/* The lens for the following prt_render calls ("Thin lens and field of view" above; NULL = all zero).  PRT_ERR_INVALID,
+ * with the previous lens intact: a NaN in any field, fov_y < 0 or >= pi, aperture < 0 or not finite, aperture > 0 with a
+ * focus_distance that is not finite or <= 0. */
+int prt_set_lens(PrtContext* ctx, const PrtLens* lens);
+int prt_get_lens(PrtContext* ctx, PrtLens* out);
 /* Samples kept in flight together (paths = local pixels * n); default 1. */
 int prt_set_samples_in_flight(PrtContext* ctx, uint32_t n);
 /* Light sampling for the following prt_render calls (PrtLighting above; NULL = off).  A mode other than PRT_LIGHTING_*
@@ -478,6 +513,10 @@ int prt_film_display(PrtContext* ctx, float exposure, float gamma, uint8_t* rgba
 /* ---- function-level entry points (used by the parity tests; all go through the same kernels) -- */
 /* Camera::GetCameraRay at pixel-space points (px,py)  (src/core/camera.h:103-132). Host in/out. */
 int prt_camera_rays(PrtContext* ctx, uint32_t n, const float* px, const float* py, float* origins, float* dirs);
+/* The render's own device code for n pixel-space points under the context's lens.  keys = the path's RNG state BEFORE the
+ * lens draws, advanced in place by two draws while aperture > 0 and left alone otherwise.  Host in/out. */
+int prt_camera_rays_lens(PrtContext* ctx, uint32_t n, const float* px, const float* py, uint32_t* keys, float* origins,
+                         float* dirs);
 /* Scene::Intersect for n rays (src/core/scene.h:22-25).  Host in/out. */
 int prt_closest_hit(PrtContext* ctx, uint32_t n, const float* origins, const float* dirs, PrtHit* hits);
 /* The same from DEVICE arrays (n x 3 floats each; d_hits: n PrtHit records), enqueued on the context's stream with no
@@ -570,6 +609,7 @@ int prt_group_set_camera(PrtGroup* g, const PrtCameraDesc* cam);
 int prt_group_set_film(PrtGroup* g, uint32_t width, uint32_t height);
 int prt_group_film_clear(PrtGroup* g);
 int prt_group_set_sampling(PrtGroup* g, const PrtSampling* s);
+int prt_group_set_lens(PrtGroup* g, const PrtLens* lens);
 int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n);
 int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l);
 int prt_group_set_light_sources(PrtGroup* g, uint32_t mask);

@@ -81,6 +81,10 @@ class PrtSampling(C.Structure):
     _fields_ = [("jitter", C.c_uint32), ("rr_depth", C.c_uint32), ("clamp", C.c_float)]
 
 
+class PrtLens(C.Structure):
+    _fields_ = [("fov_y", C.c_float), ("aperture", C.c_float), ("focus_distance", C.c_float)]
+
+
 class PrtLighting(C.Structure):
     _fields_ = [("mode", C.c_uint32)]
 
@@ -156,6 +160,10 @@ SIGNATURES = {
     "prt_group_film_clear": (C.c_int, [_vp]),
     "prt_group_set_sampling": (C.c_int, [_vp, C.POINTER(PrtSampling)]),
     "prt_group_set_samples_in_flight": (C.c_int, [_vp, C.c_uint32]),
+    "prt_group_set_lens": (C.c_int, [_vp, C.POINTER(PrtLens)]),
+    "prt_set_lens": (C.c_int, [_vp, C.POINTER(PrtLens)]),
+    "prt_get_lens": (C.c_int, [_vp, C.POINTER(PrtLens)]),
+    "prt_camera_rays_lens": (C.c_int, [_vp, C.c_uint32, _fp, _fp, _u32p, _fp, _fp]),
     "prt_group_set_param": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "prt_group_render": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "prt_group_film_read": (C.c_int, [_vp, _fp, _fp]),

@@ -107,6 +107,7 @@ struct PrtContext {
     bool batch_walked = false;  // the last run_batch took the one-walk-per-pixel route (prt_measure_traversal counts its list)
     int gpu_build = 0;  // prt_set_param("gpu_build", 1): the next prt_set_scene builds the 8-wide tree on the device
     PrtSampling sampling{0u, 0u, 0.0f};
+    PrtLens lens{0.0f, 0.0f, 0.0f};  // prt_set_lens: a property of the context, kept across camera / scene / film
     // grid 256 CUs x 4 blocks, 256-ray chunks, refill at 16 idle lanes, leave the node loop at <= 16 walkers, triangle
     // phase after 24 queueing lane-steps, 8-wide tree (all measured best on C3, tools/sweep.py); XCD affinity off
     PrtTravTuning tune{1024u, 256u, 16u, 0xFFFFFFFFu /* exit_max: auto */, 0u, 2u, 0u /* tri_min: auto */, 0u, 0u, 0u, 1u, 8u, 1u, 0u, nullptr, 0u, 2500000u, 2u /* big */, 8u /* static_small */, 96u /* big_min */, 32u /* big_keep */, 1u};
@@ -236,7 +237,10 @@ void free_light_state(PrtContext* c) {
 int ensure_light_state(PrtContext* c, uint64_t n_paths) {
     if (!c->d_light_stats) {
         HIPCHECK(c, hipMalloc((void**)&c->d_light_stats, kLightStatWords * sizeof(unsigned long long)));
-        HIPCHECK(c, hipMemset(c->d_light_stats, 0, kLightStatWords * sizeof(unsigned long long)));
+        // on the context's stream: a hipMemset of device memory on the null stream may return before it has run and is not
+        // ordered against the (non-blocking) render stream, so the first batch's counts could be zeroed after they were
+        // added (seen with the three contexts of a group on one GPU: one rank's first sample missing from the shadow rays)
+        HIPCHECK(c, hipMemsetAsync(c->d_light_stats, 0, kLightStatWords * sizeof(unsigned long long), c->stream));
     }
     c->lb.stats = c->d_light_stats;
     if (n_paths <= c->cap_light) return PRT_OK;
@@ -455,6 +459,9 @@ int drain_events(PrtContext* c) {
     return PRT_OK;
 }
 
+// PrtLens.fov_y -> DevCamera.tan_fov_y; 0 = the reference's 1 rad (src/core/camera.h:111)
+float lens_tan_fov_y(const PrtLens& l) { return l.fov_y == 0.0f ? tanf(0.5f) : tanf(0.5f * l.fov_y); }
+
 // glm-order helpers for the camera basis (Camera::Camera, src/core/camera.h:10-16)
 f3 h_normalize(f3 v) {
     const float d = (v.x * v.x + v.y * v.y) + v.z * v.z;
@@ -516,7 +523,12 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // bit-identical (tests run both routes).  OFF by default (prt_set_param("path_kernel", 1 | 2)): measured, it ties with
     // the pipeline up to ~250 k paths per call and loses above (profiles/r3_path_kernel.txt, TUNING.md): both are bound
     // by a path's chain of dependent node fetches, and the pipeline shades with full waves.
-    const bool path_route = !lit && !envon && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
+    // A thin lens (PrtLens with aperture > 0): every sample has a primary ray of its own, with its own origin: the per-sample
+    // full-record route that jitter takes; no compact primary rays (and so no one-walk-per-pixel list, no k_primary_hit) and
+    // no path route, which generates its rays itself
+    const bool lens_on = c->lens.aperture > 0.0f;
+    const DevLens dlens{c->lens.aperture, c->lens.focus_distance};
+    const bool path_route = !lit && !envon && !lens_on && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
                             !trav_stats && !c->d_shade_div && c->variant == 0 && fuse == 0u && c->sort_rays == 0u &&
                             prt_path_kernel_applies(c->dsc, c->tune);
     if (path_route) {
@@ -536,7 +548,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // front/back counters of every bounce start at zero (the producers add to them atomically)
     HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
     // compact primary rays (PrtPrimary): the default pipeline without jitter / roulette / clamp / fusion
-    const bool compact = !lit && !envon && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
+    const bool compact = !lit && !envon && !lens_on && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
                          c->sampling.jitter == 0u && c->sampling.rr_depth == 0u && !(c->sampling.clamp > 0.0f) && fuse == 0u &&
                          prt_traverse_takes_primary(c->dsc, c->tune);
     if (compact && c->pix_entries < c->tm.n_pix_local) {
@@ -564,7 +576,8 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     if (walk) primary_list.pid = (const uint32_t*)c->rb[0].hd2;
     if ((rc = begin_event(c, 0, &ep))) return rc;
     prt_launch_raygen(c->stream, c->dsc, c->cam, c->tm, n_paths, first_sample, seed, c->rb[0], c->d_rad, c->d_counts,
-                      c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr, envp, walk);
+                      c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr, envp, walk,
+                      lens_on ? &dlens : nullptr);
     if ((rc = end_event(c, &ep))) return rc;
     if (exact) HIPCHECK(c, read_back(0));
     for (uint32_t d = 0; d < max_depth; ++d) {
@@ -577,7 +590,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                 PrtTravTuning tune = c->tune;
                 tune.probe_slot = d;
                 tune.perm = nullptr;
-                if (c->sort_rays && !(compact && d == 0) && (d > 0 || c->sampling.jitter)) {
+                if (c->sort_rays && !(compact && d == 0) && (d > 0 || c->sampling.jitter || lens_on)) {
                     // measurement aid (tools/sort_ab.py): the host needs the ray count, so this path synchronises; the sort
                     // is timed as its own stage (scan_ms), the traversal that follows as usual
                     uint32_t n_front = 0;
@@ -1312,8 +1325,29 @@ int prt_set_camera(PrtContext* c, const PrtCameraDesc* cam) {
     k.up = h_normalize(h_cross(k.right, k.front));
     k.W = cam->width;
     k.H = cam->height;
-    k.tan_fov_y = tanf(0.5f);  // src/core/camera.h:111
+    k.tan_fov_y = lens_tan_fov_y(c->lens);
     c->has_camera = true;
+    return PRT_OK;
+}
+
+int prt_set_lens(PrtContext* c, const PrtLens* lens) {
+    if (!c) return PRT_ERR_INVALID;
+    const PrtLens l = lens ? *lens : PrtLens{0.0f, 0.0f, 0.0f};
+    if (std::isnan(l.fov_y) || std::isnan(l.aperture) || std::isnan(l.focus_distance))
+        return fail(c, PRT_ERR_INVALID, "bad lens: NaN");
+    if (l.fov_y < 0.0f || !(l.fov_y < 3.14159265358979323846f))  // (the fp32 nearest to pi is above pi: refused as well)
+        return fail(c, PRT_ERR_INVALID, "bad lens: fov_y must be 0 (the default, 1 rad) or in (0, pi)");
+    if (l.aperture < 0.0f || !std::isfinite(l.aperture)) return fail(c, PRT_ERR_INVALID, "bad lens: aperture must be finite and >= 0");
+    if (l.aperture > 0.0f && (!std::isfinite(l.focus_distance) || !(l.focus_distance > 0.0f)))
+        return fail(c, PRT_ERR_INVALID, "bad lens: aperture > 0 needs a finite focus_distance > 0");
+    c->lens = l;
+    c->cam.tan_fov_y = lens_tan_fov_y(l);  // (prt_set_camera writes the rest, and this again)
+    return PRT_OK;
+}
+
+int prt_get_lens(PrtContext* c, PrtLens* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    *out = c->lens;
     return PRT_OK;
 }
 
@@ -1669,6 +1703,34 @@ int prt_camera_rays(PrtContext* c, uint32_t n, const float* px, const float* py,
     return PRT_OK;
 }
 
+int prt_camera_rays_lens(PrtContext* c, uint32_t n, const float* px, const float* py, uint32_t* keys, float* origins,
+                         float* dirs) {
+    if (c && !(c->lens.aperture > 0.0f)) return prt_camera_rays(c, n, px, py, origins, dirs);  // pinhole: no draw, keys left alone
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_camera) return fail(c, PRT_ERR_INVALID, "prt_set_camera has not been called");
+    if (n == 0) return PRT_OK;
+    if (!px || !py || !keys || !origins || !dirs) return fail(c, PRT_ERR_INVALID, "null array");
+    const size_t b1 = (size_t)n * 4, b3 = (size_t)n * 12;
+    if ((rc = ensure_scratch(c, 3 * b1 + 2 * b3))) return rc;
+    char* base = (char*)c->d_scratch;
+    float* d_px = (float*)base;
+    float* d_py = (float*)(base + b1);
+    uint32_t* d_keys = (uint32_t*)(base + 2 * b1);
+    float* d_o = (float*)(base + 3 * b1);
+    float* d_d = (float*)(base + 3 * b1 + b3);
+    HIPCHECK(c, hipMemcpyAsync(d_px, px, b1, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_py, py, b1, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_keys, keys, b1, hipMemcpyHostToDevice, c->stream));
+    prt_launch_camera_rays_lens(c->stream, c->cam, DevLens{c->lens.aperture, c->lens.focus_distance}, n, d_px, d_py, d_keys, d_o, d_d);
+    HIPCHECK(c, hipGetLastError());
+    HIPCHECK(c, hipMemcpyAsync(keys, d_keys, b1, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(origins, d_o, b3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(dirs, d_d, b3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
 // The ray-query pipeline on the context's stream, from device arrays (n x 3 origins / directions): closest hit
 // (d_tmax == nullptr: PrtHit records into d_hits) or occlusion (one byte per ray into d_occ).  No host wait.
 static int enqueue_query(PrtContext* c, uint32_t n, const float* d_o, const float* d_d, const float* d_tmax, PrtHit* d_hits,
@@ -1905,8 +1967,9 @@ int prt_reset_stats(PrtContext* c) {
     if ((rc = drain_events(c))) return rc;
     memset(&c->stats, 0, sizeof(c->stats));
     c->dead_paths = 0;
-    if (c->d_ray_stats) HIPCHECK(c, hipMemset(c->d_ray_stats, 0, kRayStatWords * sizeof(unsigned long long)));
-    if (c->d_light_stats) HIPCHECK(c, hipMemset(c->d_light_stats, 0, kLightStatWords * sizeof(unsigned long long)));
+    // (stream-ordered, like the counting kernels that follow: see ensure_light_state)
+    if (c->d_ray_stats) HIPCHECK(c, hipMemsetAsync(c->d_ray_stats, 0, kRayStatWords * sizeof(unsigned long long), c->stream));
+    if (c->d_light_stats) HIPCHECK(c, hipMemsetAsync(c->d_light_stats, 0, kLightStatWords * sizeof(unsigned long long), c->stream));
     return PRT_OK;
 }
 
@@ -1925,7 +1988,7 @@ int prt_measure_traversal(PrtContext* c, uint32_t max_depth, uint32_t seed, uint
     c->timing = false;
     // the per-depth ray counters are cumulative: this run counts into the scratch set
     unsigned long long before[PRT_MAX_DEPTH] = {}, after[PRT_MAX_DEPTH];
-    HIPCHECK(c, hipMemset(c->d_ray_stats + kRayStatWords, 0, kRayStatWords * sizeof(unsigned long long)));
+    HIPCHECK(c, hipMemsetAsync(c->d_ray_stats + kRayStatWords, 0, kRayStatWords * sizeof(unsigned long long), c->stream));
     c->ray_stats_target = c->d_ray_stats + kRayStatWords;
     // measure_spp (prt_set_param) samples in one batch: the counters scale, the per-phase cycle split becomes that of a
     // loaded kernel

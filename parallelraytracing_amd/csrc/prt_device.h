@@ -362,6 +362,27 @@ PRT_DEV void camera_ray(const DevCamera& c, float px, float py, f3& o, f3& d) {
     o = c.pos;
 }
 
+// Thin lens (PrtLens, include/prt.h "Thin lens and field of view"; aperture > 0 only): the ray from a point of the lens disk
+// (the path's next two draws) through the point where the pinhole ray of (px, py) meets the plane in focus.  The render
+// (raygen_step<LENS>) and prt_camera_rays_lens both call this.
+PRT_DEV void lens_camera_ray(const DevCamera& c, const DevLens& l, float px, float py, uint32_t& rng, f3& o, f3& d) {
+    float ndcX = (px / c.W) * 2.0f - 1.0f;
+    float ndcY = 1.0f - (py / c.H) * 2.0f;
+    float aspect = c.W / c.H;
+    float pcx = ndcX * aspect * c.tan_fov_y;
+    float pcy = ndcY * c.tan_fov_y;
+    const float u3 = rnd01(rng);
+    const float u4 = rnd01(rng);
+    const float r = l.aperture * __builtin_sqrtf(u3);
+    const float phi = 6.2831855f * u4;
+    const float lx = r * cosf(phi);
+    const float ly = r * sinf(phi);
+    f3 dc = normalize3(mk3(pcx * l.focus - lx, pcy * l.focus - ly, -l.focus));
+    f3 dw = dc.x * c.right + dc.y * c.up + dc.z * -c.front;
+    d = normalize3(dw);
+    o = c.pos + lx * c.right + ly * c.up;
+}
+
 // ---- wave64 helpers --------------------------------------------------------------------------------------
 PRT_DEV uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 

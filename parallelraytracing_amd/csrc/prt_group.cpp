@@ -307,6 +307,11 @@ int prt_group_set_sampling(PrtGroup* g, const PrtSampling* s) {
     return for_each_rank(g, [&](uint32_t r) { return prt_set_sampling(g->ctx[r], s); }, false);
 }
 
+int prt_group_set_lens(PrtGroup* g, const PrtLens* lens) {
+    if (!g) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_lens(g->ctx[r], lens); }, false);
+}
+
 int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n_samples) {
     if (!g) return PRT_ERR_INVALID;
     return for_each_rank(g, [&](uint32_t r) { return prt_set_samples_in_flight(g->ctx[r], n_samples); }, false);

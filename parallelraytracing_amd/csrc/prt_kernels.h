@@ -14,7 +14,12 @@ struct f3 {
 
 struct DevCamera {  // the Camera members GetCameraRay reads (reference: src/core/camera.h:134-141)
     f3 pos, front, right, up;
-    float W, H, tan_fov_y;
+    float W, H, tan_fov_y;  // tan_fov_y: tanf(0.5f) (the reference's 1 rad), or tanf(0.5f * PrtLens.fov_y)
+};
+// Thin lens (PrtLens, include/prt.h "Thin lens and field of view"), passed only to the kernel instances of its own
+// (k_raygen_lens, k_raygen_lens_env, k_camera_rays_lens) while aperture > 0: DevCamera and the other instances stay as they are.
+struct DevLens {
+    float aperture, focus;
 };
 
 // Smallest |component| of a unit direction that the slab tests of every walk divide by (a smaller one, zero included, is
@@ -208,7 +213,8 @@ void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam,
                        uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
                        uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix = nullptr,
                        const DevEnv* env = nullptr,  // env: the instance with an environment image (never compact)
-                       bool primary_walk = false);   // compact only: write the front-pixel list into out.hd2 (PrtPrimary)
+                       bool primary_walk = false,    // compact only: write the front-pixel list into out.hd2 (PrtPrimary)
+                       const DevLens* lens = nullptr);  // lens: the instances with a thin lens (one full record per sample, never compact)
 void prt_launch_scan_prims(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                            uint32_t* work, uint32_t max_rays, unsigned long long* stats);
 void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
@@ -244,6 +250,9 @@ void prt_launch_tonemap(hipStream_t st, const float* rgb, const float* weight, u
                         float inv_gamma, uint8_t* out);
 void prt_launch_camera_rays(hipStream_t st, const DevCamera& cam, uint32_t n, const float* px, const float* py,
                             float* o, float* d);
+// prt_camera_rays_lens: lens_camera_ray for n points; keys (RNG states) are advanced in place
+void prt_launch_camera_rays_lens(hipStream_t st, const DevCamera& cam, const DevLens& lens, uint32_t n, const float* px,
+                                 const float* py, uint32_t* keys, float* o, float* d);
 void prt_launch_pack_rays(hipStream_t st, uint32_t n, const float* o, const float* d, const PrtRayBuf& out,
                           uint32_t* counts);
 void prt_launch_hit_records(hipStream_t st, const DevScene& sc, uint32_t n, const PrtRayBuf& in, PrtHit* out);

@@ -323,12 +323,15 @@ PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr,
 // which costs a wave per SIMD, i.e. with 1024-thread blocks one of the two blocks per CU (measured: shade 50 % slower).
 // (ENV / env: see advance_path; k_raygen passes false / null and compiles to the code it had before there was an environment
 // image, k_raygen_env is the instance with one)
-template <bool JITTER, bool SAMPLING, bool ABVH, bool COMPACT, bool ENV>
+// LENS (lens: DevLens; PrtLens with aperture > 0): every sample has a primary ray of its own, from its own point of the lens,
+// so LENS takes the per-sample branch below whether JITTER is on or not (off: the pixel centre) and stores each ray's own
+// origin.  The other instances pass false and compile to the code they had before there was a lens.
+template <bool JITTER, bool SAMPLING, bool ABVH, bool COMPACT, bool ENV, bool LENS = false>
 PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, uint32_t first_sample, uint32_t seed,
                          float4* __restrict__ ro, float4* __restrict__ rd, float4* __restrict__ rt, uint32_t* __restrict__ hit,
                          float* __restrict__ hd2, float4* __restrict__ rad, uint32_t* __restrict__ counts,
                          uint32_t* __restrict__ work, uint32_t max_depth, PrtSampling sp_arg, float4* __restrict__ pix,
-                         const DevEnv* env) {
+                         const DevEnv* env, const DevLens* lens = nullptr) {
     const PrtSampling sp = SAMPLING ? sp_arg : PrtSampling{0u, 0u, 0.0f};
     const uint32_t pl = blockIdx.x * (uint32_t)PRODUCER_BLOCK + threadIdx.x;
     if (blockIdx.y == 0 && pl < 8u) work[32u * pl] = 0u;  // chunk cursors of the traversal kernel that follows
@@ -343,17 +346,17 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
         valid = tile_pixel(tm, pl, px, py);
         if (valid) {
             pixel = py * tm.W + px;
-            if (!JITTER) {  // pixel centre, the same ray for every sample (cpu/renderer.cpp:45)
+            if (!JITTER && !LENS) {  // pixel centre, the same ray for every sample (cpu/renderer.cpp:45)
                 camera_ray(cam, (float)px + 0.5f, (float)py + 0.5f, o0, d0);
                 if (COMPACT && blockIdx.y == 0) pix[pl] = make_float4(d0.x, d0.y, d0.z, __uint_as_float(pixel));
                 front0 = classify_ray<ABVH, PRODUCER_BLOCK>(sc, o0, d0, id00, d2_00);
             }
         }
     }
-    const uint32_t group = JITTER ? RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
+    const uint32_t group = (JITTER || LENS) ? RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
     const uint32_t s0 = blockIdx.y * group;
     const uint32_t s1 = (s0 + group < S) ? s0 + group : S;
-    if (!JITTER) {
+    if (!JITTER && !LENS) {
         // Without jitter whether the pixel's primary ray is stored (front / back) or ends right here does not depend
         // on the sample: decide once, reserve the slots of all samples of this group with ONE atomic per side per
         // block, and only the RNG seed and the path id differ per copy.
@@ -477,9 +480,12 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
     // Jittered primary rays, RAYGEN_ALLOC samples of the pixel per slot reservation.  What is stored per ray is its
     // direction, RNG state and the analytic scan's result: with no shading budget advance_path never scatters, so the origin
     // stays the camera position, the throughput 1 and the segment index 0 (paths that end right here write rad[] inside).
-    constexpr int KA = ABVH ? 2 : RAYGEN_ALLOC;  // (the primitive-BVH walk needs the registers: 4 rays would spill)
+    // LENS: the origin is the ray's own point of the lens, kept per ray next to its direction.
+    // (with 4 rays per reservation the lens instances need 101-105 VGPRs, a wave per SIMD less than the jittered ones at 93-96)
+    constexpr int KA = (ABVH || LENS) ? 2 : RAYGEN_ALLOC;  // (the primitive-BVH walk needs the registers: 4 rays would spill)
     for (uint32_t sl = s0; sl < s1; sl += KA) {  // block-uniform trip count
         f3 dk[KA];
+        f3 ok[KA];  // (LENS only)
         uint32_t rngk[KA], idk[KA], slotk[KA];
         float d2k[KA];
         bool frontk[KA], backk[KA];
@@ -494,9 +500,12 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
             if (sk < s1 && valid) {
                 rng = path_seed(pixel, first_sample + sk, seed);
                 {  // (x + u1, y + u2): the path's first two draws (optix/device_programs.cu:172-173)
-                    const float u1 = rnd01(rng);
-                    const float u2 = rnd01(rng);
-                    camera_ray(cam, (float)px + u1, (float)py + u2, o, d);
+                    const float u1 = JITTER ? rnd01(rng) : 0.5f;
+                    const float u2 = JITTER ? rnd01(rng) : 0.5f;
+                    if (LENS)  // then the two lens draws (PrtLens, include/prt.h)
+                        lens_camera_ray(cam, *lens, (float)px + u1, (float)py + u2, rng, o, d);
+                    else
+                        camera_ray(cam, (float)px + u1, (float)py + u2, o, d);
                     front = classify_ray<ABVH, PRODUCER_BLOCK>(sc, o, d, id0, d2_0);
                 }
                 if (!front) {
@@ -509,6 +518,7 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
                 rad[i] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xFFFFFFFFu));  // partial tiles outside the image: no path
             }
             dk[kk] = d;
+            if (LENS) ok[kk] = o;
             rngk[kk] = rng;
             idk[kk] = id0;
             d2k[kk] = d2_0;
@@ -521,7 +531,8 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
             const uint32_t slot = slotk[kk];
             if (slot != 0xFFFFFFFFu) {
                 const uint32_t i = (sl + (uint32_t)kk) * tm.n_pix_local + pl;
-                ro[slot] = make_float4(cam.pos.x, cam.pos.y, cam.pos.z, __uint_as_float(i));
+                const f3 ok_ = LENS ? ok[kk] : cam.pos;
+                ro[slot] = make_float4(ok_.x, ok_.y, ok_.z, __uint_as_float(i));
                 rd[slot] = make_float4(dk[kk].x, dk[kk].y, dk[kk].z, __uint_as_float(rngk[kk]));
                 rt[slot] = make_float4(1.f, 1.f, 1.f, __uint_as_float(0u));
                 hit[slot] = idk[kk];
@@ -555,6 +566,31 @@ __global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen_env(DevScene sc, DevE
                                                                 uint32_t max_depth, PrtSampling sp_arg) {
     raygen_step<JITTER, true, ABVH, false, true>(sc, cam, tm, S, first_sample, seed, ro, rd, rt, hit, hd2, rad, counts, work,
                                                  max_depth, sp_arg, nullptr, &env);
+}
+
+// k_raygen with a thin lens (prt_set_lens with aperture > 0): one full ray record per sample with the ray's own origin,
+// sampling options compiled in; with an environment image: k_raygen_lens_env
+template <bool JITTER, bool ABVH>
+__global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen_lens(DevScene sc, DevLens lens, DevCamera cam, PrtTileMap tm, uint32_t S,
+                                                                 uint32_t first_sample, uint32_t seed,
+                                                                 float4* __restrict__ ro, float4* __restrict__ rd,
+                                                                 float4* __restrict__ rt, uint32_t* __restrict__ hit,
+                                                                 float* __restrict__ hd2, float4* __restrict__ rad,
+                                                                 uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                                 uint32_t max_depth, PrtSampling sp_arg) {
+    raygen_step<JITTER, true, ABVH, false, false, true>(sc, cam, tm, S, first_sample, seed, ro, rd, rt, hit, hd2, rad, counts, work,
+                                                        max_depth, sp_arg, nullptr, nullptr, &lens);
+}
+template <bool JITTER, bool ABVH>
+__global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen_lens_env(DevScene sc, DevEnv env, DevLens lens, DevCamera cam, PrtTileMap tm,
+                                                                     uint32_t S, uint32_t first_sample, uint32_t seed,
+                                                                     float4* __restrict__ ro, float4* __restrict__ rd,
+                                                                     float4* __restrict__ rt, uint32_t* __restrict__ hit,
+                                                                     float* __restrict__ hd2, float4* __restrict__ rad,
+                                                                     uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                                     uint32_t max_depth, PrtSampling sp_arg) {
+    raygen_step<JITTER, true, ABVH, false, true, true>(sc, cam, tm, S, first_sample, seed, ro, rd, rt, hit, hd2, rad, counts, work,
+                                                       max_depth, sp_arg, nullptr, &env, &lens);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2872,6 +2908,21 @@ __global__ void __launch_bounds__(256) k_tonemap(const float* __restrict__ rgb, 
 
 // ---------------------------------------------------------------------------------------------------------
 // Function-level kernels behind prt_camera_rays / prt_closest_hit / prt_scatter (parity tests).
+__global__ void k_camera_rays_lens(DevCamera cam, DevLens lens, uint32_t n, const float* __restrict__ px, const float* __restrict__ py,
+                                   uint32_t* __restrict__ keys, float* __restrict__ o_out, float* __restrict__ d_out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 o, d;
+    uint32_t rng = keys[i];
+    lens_camera_ray(cam, lens, px[i], py[i], rng, o, d);
+    keys[i] = rng;
+    o_out[3 * (size_t)i + 0] = o.x;
+    o_out[3 * (size_t)i + 1] = o.y;
+    o_out[3 * (size_t)i + 2] = o.z;
+    d_out[3 * (size_t)i + 0] = d.x;
+    d_out[3 * (size_t)i + 1] = d.y;
+    d_out[3 * (size_t)i + 2] = d.z;
+}
 // ---------------------------------------------------------------------------------------------------------
 __global__ void k_camera_rays(DevCamera cam, uint32_t n, const float* __restrict__ px, const float* __restrict__ py,
                               float* __restrict__ o_out, float* __restrict__ d_out) {
@@ -3669,10 +3720,28 @@ static inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + 255u) / 2
 void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, uint32_t n_paths,
                        uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
                        uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix, const DevEnv* env,
-                       bool primary_walk) {
+                       bool primary_walk, const DevLens* lens) {
     const uint32_t S = tm.n_pix_local ? n_paths / tm.n_pix_local : 0u;
-    const uint32_t group = sp.jitter ? (uint32_t)RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
+    const uint32_t group = (sp.jitter || lens) ? (uint32_t)RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
     const dim3 grid((tm.n_pix_local + PRODUCER_BLOCK - 1) / PRODUCER_BLOCK, (S + group - 1) / group);
+    if (lens) {  // a thin lens: the per-sample instances of its own (full ray records, never compact)
+#define PRT_RAYGEN_LENS(J, AB)                                                                                                  \
+    do {                                                                                                                        \
+        if (env)                                                                                                                \
+            hipLaunchKernelGGL((k_raygen_lens_env<J, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, *env, *lens, cam, tm, S,       \
+                               first_sample, seed, out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp);   \
+        else                                                                                                                    \
+            hipLaunchKernelGGL((k_raygen_lens<J, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, *lens, cam, tm, S, first_sample,   \
+                               seed, out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp);                 \
+    } while (0)
+        if (sc.abvh_nodes) {
+            if (sp.jitter) PRT_RAYGEN_LENS(true, true); else PRT_RAYGEN_LENS(false, true);
+        } else {
+            if (sp.jitter) PRT_RAYGEN_LENS(true, false); else PRT_RAYGEN_LENS(false, false);
+        }
+#undef PRT_RAYGEN_LENS
+        return;
+    }
     if (env) {
 #define PRT_RAYGEN_ENV(J, AB)                                                                                           \
     hipLaunchKernelGGL((k_raygen_env<J, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, *env, cam, tm, S, first_sample, seed, \
@@ -4045,6 +4114,10 @@ void prt_launch_tonemap(hipStream_t st, const float* rgb, const float* weight, u
                        exposure, inv_gamma, out);
 }
 
+void prt_launch_camera_rays_lens(hipStream_t st, const DevCamera& cam, const DevLens& lens, uint32_t n, const float* px,
+                                 const float* py, uint32_t* keys, float* o, float* d) {
+    hipLaunchKernelGGL(k_camera_rays_lens, dim3(blocks_for(n)), dim3(256), 0, st, cam, lens, n, px, py, keys, o, d);
+}
 void prt_launch_camera_rays(hipStream_t st, const DevCamera& cam, uint32_t n, const float* px, const float* py,
                             float* o, float* d) {
     hipLaunchKernelGGL(k_camera_rays, dim3(blocks_for(n)), dim3(256), 0, st, cam, n, px, py, o, d);

@@ -3,6 +3,9 @@
 //   prt_render [--preset NAME | --ply FILE [--refine N]] [--width W --height H] [--spp N] [--depth D]
 //              [--seed S] [--camera x y z] [--out PREFIX] [--gpus N | --devices a,b,c] [--sif S] [--frames K]
 //              [--lighting off|nee|mis] [--light-sources analytic|all] [--env FILE.pfm [--env-share Q]]
+//              [--fov-deg D] [--aperture R --focus F]
+// --fov-deg sets the vertical field of view in degrees (default: the reference's 1 rad); --aperture R (lens radius, world
+// units) with --focus F (distance of the plane in focus along the view direction) renders with a thin lens.
 // --env lights the scene with a lat-long colour PFM (top row = the +Y pole) instead of the constant sky; with a lighting
 // mode, a light sample goes to the image with probability Q (default 0.5).
 // --gpus N tiles the image over devices 0..N-1 (--devices: any list; a device may repeat, which rehearses the multi-GPU
@@ -27,7 +30,8 @@ static int preset_id(const std::string& n) {
 
 int main(int argc, char** argv) {
     std::string preset = "CORNELL", ply, out = "frame", env;
-    float env_share = 0.5f;
+    float env_share = 0.5f, aperture = 0.0f, focus = 0.0f;
+    double fov_deg = 0.0;
     uint32_t W = 256, H = 256, spp = 1, depth = 2, seed = 0, refine = 0, sif = 0, frames = 1, lighting = PRT_LIGHTING_OFF;
     uint32_t light_sources = PRT_LIGHT_SOURCES_ANALYTIC;
     std::vector<int> devices{0};
@@ -62,6 +66,9 @@ int main(int argc, char** argv) {
         }
         else if (a == "--env") env = next();
         else if (a == "--env-share") env_share = (float)atof(next());
+        else if (a == "--fov-deg") fov_deg = atof(next());
+        else if (a == "--aperture") aperture = (float)atof(next());
+        else if (a == "--focus") focus = (float)atof(next());
         else if (a == "--gpus") { const int n = atoi(next()); devices.clear(); for (int d = 0; d < n; ++d) devices.push_back(d); }
         else if (a == "--devices") { devices.clear(); std::string l = next(); for (size_t p = 0; p < l.size();) { size_t e = l.find(',', p); if (e == std::string::npos) e = l.size(); devices.push_back(atoi(l.substr(p, e - p).c_str())); p = e + 1; } }
         else if (a == "--camera") { for (int k = 0; k < 3; ++k) cam[k] = (float)atof(next()); cam_set = true; }
@@ -96,6 +103,7 @@ int main(int argc, char** argv) {
         if (lighting != PRT_LIGHTING_OFF) r.SetLighting(lighting);
         if (light_sources != (uint32_t)PRT_LIGHT_SOURCES_ANALYTIC) r.SetLightSources(light_sources);
         if (!env.empty()) r.SetEnvironmentPfm(env, env_share);
+        if (fov_deg != 0.0 || aperture != 0.0f) r.SetLens((float)(fov_deg * 3.14159265358979323846 / 180.0), aperture, focus);
         if (frames > 1) {  // warm-up frame (first-touch allocations, clocks), then the timed ones
             r.Render(spp);
             r.Clear();

@@ -199,6 +199,12 @@ public:
     }
     void SetSamplesInFlight(uint32_t n) { check(prt_group_set_samples_in_flight(grp_, n)); }
     void SetParam(const char* name, int value) { check(prt_group_set_param(grp_, name, value)); }
+    // Thin lens and field of view (PrtLens): fov_y in radians (0 = the reference's 1 rad), aperture = lens radius in world
+    // units (0 = pinhole), focus_distance along the camera's front; kept across SetCamera / Init
+    void SetLens(float fov_y = 0.0f, float aperture = 0.0f, float focus_distance = 0.0f) {
+        const PrtLens l{fov_y, aperture, focus_distance};
+        check(prt_group_set_lens(grp_, &l));
+    }
     // Light sampling toward the analytic emitters (PrtLighting): PRT_LIGHTING_OFF / _NEE_MIS / _NEE
     void SetLighting(uint32_t mode) {
         const PrtLighting l{mode};

@@ -385,6 +385,19 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_set_sampling(self._ctx, C.byref(sp)))
         return sp
 
+    def set_lens(self, fov_y: float = 0.0, aperture: float = 0.0, focus_distance: float = 0.0) -> capi.PrtLens:
+        """Thin lens and field of view (include/prt.h PrtLens): fov_y in radians (0 = the reference's 1 rad), aperture = the
+        lens radius in world units (0 = pinhole), focus_distance = distance along `front` of the plane in focus.  All zero =
+        the reference's camera.  Stays with the renderer across SetCamera / Init."""
+        ln = capi.PrtLens(float(fov_y), float(aperture), float(focus_distance))
+        self._check(capi.lib().prt_set_lens(self._ctx, C.byref(ln)))
+        return ln
+
+    def get_lens(self) -> capi.PrtLens:
+        ln = capi.PrtLens()
+        self._check(capi.lib().prt_get_lens(self._ctx, C.byref(ln)))
+        return ln
+
     def set_lighting(self, mode) -> int:
         """Light sampling toward the analytic emitters (include/prt.h PrtLighting): "off" | "mis" | "nee" or 0 | 1 | 2."""
         m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
@@ -506,6 +519,21 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_camera_rays(self._ctx, n, px.ctypes.data_as(_fp), py.ctypes.data_as(_fp),
                                                o.ctypes.data_as(_fp), d.ctypes.data_as(_fp)))
         return o, d
+
+    def camera_rays_lens(self, px, py, keys):
+        """The render's primary rays under the current lens for pixel-space points (px, py) and RNG states `keys` (the
+        path's state before the lens draws).  Returns (origins, dirs, keys after): two draws further while aperture > 0."""
+        px, py = _f32(px).ravel(), _f32(py).ravel()
+        k = np.array(keys, dtype=np.uint32).ravel()  # a copy: advanced in place
+        n = px.size
+        if py.size != n or k.size != n:
+            raise ValueError("px, py and keys must have the same number of elements")
+        o = np.empty((n, 3), np.float32)
+        d = np.empty((n, 3), np.float32)
+        self._check(capi.lib().prt_camera_rays_lens(self._ctx, n, px.ctypes.data_as(_fp), py.ctypes.data_as(_fp),
+                                                    k.ctypes.data_as(C.POINTER(C.c_uint32)), o.ctypes.data_as(_fp),
+                                                    d.ctypes.data_as(_fp)))
+        return o, d, k
 
     def closest_hit(self, origins, dirs) -> np.ndarray:
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)
@@ -806,6 +834,12 @@ class HipWavefrontGroupRenderer:
         sp = PrtSampling(int(jitter), int(rr_depth), float(clamp))
         self._check(capi.lib().prt_group_set_sampling(self._grp, C.byref(sp)))
         return sp
+
+    def set_lens(self, fov_y: float = 0.0, aperture: float = 0.0, focus_distance: float = 0.0) -> capi.PrtLens:
+        """Thin lens and field of view on every rank (HipWavefrontRenderer.set_lens)."""
+        ln = capi.PrtLens(float(fov_y), float(aperture), float(focus_distance))
+        self._check(capi.lib().prt_group_set_lens(self._grp, C.byref(ln)))
+        return ln
 
     def set_lighting(self, mode) -> int:
         m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
