@@ -287,6 +287,59 @@ typedef struct PrtEnvironmentInfo {
     float light_share;
 } PrtEnvironmentInfo;
 
+/* Image textures (prt_set_textures; NULL = none, bit for bit the behaviour above).  A texture replaces the constant rgb of
+ * a Lambertian or Metal material as ALBEDO: the attenuation of Lambertian / Metal::Scatter (and so the throughput, the
+ * roulette and everything after it) and the albedo / pi of the light sample in every lighting mode.  Emission and the
+ * dielectric's attenuation are never textured.  Scatter directions, RNG draws, segments, rays_per_depth, MIS weights and
+ * hit records do not depend on the albedo: with roulette off they are draw for draw those of the untextured scene.
+ * prt_scatter and prt_sample_light keep the material's constant rgb: their inputs carry no UV.
+ *  UV of a hit (fp32, no contraction, in this order):
+ *    triangle of a world-space mesh or of a placed copy: b1, b2 as Triangle::Intersect computes them for the winning triangle
+ *      (a copy: in the mesh's space, from the local ray); w0 = 1.0f - b1 - b2; u = (w0 * u0 + b1 * u1) + b2 * u2, v likewise;
+ *      u0, u1, u2: the UVs of the face's three vertices in index order.  The placed copies of a mesh share its UVs.
+ *    quad: p = the local hit point of Quad::Intersect (before Mat); u = p.x / w + 0.5f, v = p.z / h + 0.5f.
+ *    A sphere cannot carry a textured material (no parametrisation: PRT_ERR_INVALID).
+ *  Lookup of (u, v) in a W x H texture; v = 0 is the BOTTOM row:
+ *    wrap: REPEAT a = u - floorf(u); CLAMP a = fminf(fmaxf(u, 0.0f), 1.0f); b from v the same way
+ *    X = a * W, Y = (1.0f - b) * H
+ *    NEAREST: j = min(W - 1, (uint32)floorf(X)), i = min(H - 1, (uint32)floorf(Y)), rgb = texel[i][j]
+ *    BILINEAR: x = X - 0.5f, x0 = floorf(x), fx = x - x0; y0, fy from Y - 0.5f the same way; columns (int)x0 and (int)x0 + 1,
+ *      rows likewise; an index k of an axis of size N becomes ((k % N) + N) % N under REPEAT and min(max(k, 0), N - 1) under
+ *      CLAMP; per channel c = (c00 * (1.0f - fx) + c01 * fx) * (1.0f - fy) + (c10 * (1.0f - fx) + c11 * fx) * fy (first
+ *      index: the row).
+ *  The binding belongs to the current scene: prt_set_textures needs one, prt_set_scene drops the binding, prt_clone_scene
+ *  copies it, prt_refit_meshes and prt_set_instance_transforms keep it (the UV table is stored per mesh triangle in face order,
+ *  outside every tree).  Host-only contexts validate the set and build the tables.
+ *  Routes: while a binding textures at least one material every batch takes the unfused full-record pipeline (no fused
+ *  segment, no compact primary rays, no one-walk-per-pixel list, no path instance): the rule of the environment image.
+ *  Results never depend on a tunable, on batching or on the partition. */
+enum { PRT_TEX_NEAREST = 0, PRT_TEX_BILINEAR = 1 };
+enum { PRT_TEX_REPEAT = 0, PRT_TEX_CLAMP = 1 };
+#define PRT_TEXTURE_NONE 0xFFFFFFFFu
+#define PRT_TEX_MAX_SIZE 16384u
+typedef struct PrtTexture {
+    const float* rgb;      /* height*width*3 floats, row 0 = top, copied */
+    uint32_t width, height, filter, wrap;
+} PrtTexture;
+typedef struct PrtTextureSet {
+    const PrtTexture* textures;
+    uint32_t n_textures;
+    const uint32_t* material_texture;       /* texture index or PRT_TEXTURE_NONE per material */
+    uint32_t n_materials;
+    const float* const* mesh_uvs;           /* per PrtSceneDesc.meshes[i]: n_vertices*2 floats, or NULL */
+    uint32_t n_meshes;
+    const float* const* instanced_mesh_uvs; /* per instanced_meshes[i], shared by its placed copies; or NULL */
+    uint32_t n_instanced_meshes;
+} PrtTextureSet;
+typedef struct PrtTextureInfo {
+    uint32_t is_set;               /* 0: no binding (everything else is 0 then) */
+    uint32_t n_textures;
+    uint32_t n_textured_materials; /* 0: the binding changes no route and no result */
+    uint32_t n_uv_triangles;       /* triangles of the face-order UV table (24 bytes each) */
+    uint64_t n_texels;             /* texels of the pool (16 bytes each) */
+    uint64_t device_bytes;         /* what the binding occupies on the device (0 on a host-only context) */
+} PrtTextureInfo;
+
 /* Closest-hit record of one ray (what Scene::Intersect returns, src/core/surface_interaction.h:6-13,
  * plus the winning primitive index and the world distance^2 the reference minimises,
  * src/core/primitive.cpp:42-48).  prim < 0: miss. */
@@ -472,6 +525,21 @@ int prt_environment_intervals(PrtContext* ctx, uint64_t* row_width, uint64_t* co
 /* The render's own device lookup for n unit directions (host arrays, each output may be NULL): rgb (3 floats),
  * texel = i * W + j, pdf_w = the solid-angle density with which the environment sample picks that direction (without T_e). */
 int prt_environment_eval(PrtContext* ctx, uint32_t n, const float* dirs, float* rgb, uint32_t* texel, float* pdf_w);
+/* The texture binding of the current scene ("Image textures" above; NULL = none).  PRT_ERR_INVALID, with the previous
+ * binding intact and everything checked before anything is written: no scene; n_materials, n_meshes or n_instanced_meshes
+ * differ from the scene's; a texture index out of range; a width or height of 0 or above PRT_TEX_MAX_SIZE; a null image; a
+ * negative or non-finite texel; an unknown filter or wrap; a UV that is not finite or of magnitude above 2^20; a textured
+ * material that is not Lambertian or Metal; a mesh or placed copy with a textured material and no UVs; an analytic sphere
+ * with a textured material.  Waits for the context's stream. */
+int prt_set_textures(PrtContext* ctx, const PrtTextureSet* set);
+int prt_texture_info(PrtContext* ctx, PrtTextureInfo* out);
+/* The render's own device lookup for n (texture, uv) pairs: host arrays, uv 2 floats and rgb 3 floats per pair.  Needs a
+ * device and a binding; a texture index out of range or a uv that is not finite or above 2^20 in magnitude: PRT_ERR_INVALID. */
+int prt_texture_eval(PrtContext* ctx, uint32_t n, const uint32_t* texture, const float* uv, float* rgb);
+/* prt_closest_hit plus what the shade kernels derive from the hit under the binding: uv (2 floats; 0 for a miss or a
+ * sphere) and albedo (3 floats: the looked-up colour where the hit's material is textured, else the material's rgb; 0
+ * for a miss).  Each output may be NULL.  Needs a device and a binding. */
+int prt_hit_uv(PrtContext* ctx, uint32_t n, const float* origins, const float* dirs, PrtHit* hits, float* uv, float* albedo);
 /* The exact pmf of the current light set: width[l] = T_l - T_{l-1}, pmf = width / 2^32 (prt_light_info's float is this
  * number rounded).  With the default mask there are no thresholds: PRT_ERR_INVALID. */
 int prt_light_intervals(PrtContext* ctx, uint32_t capacity, uint32_t* n_lights, uint64_t* width);
@@ -534,7 +602,8 @@ int prt_occluded(PrtContext* ctx, uint32_t n, const float* origins, const float*
 int prt_occluded_device(PrtContext* ctx, uint32_t n, const void* d_origins, const void* d_dirs, const void* d_tmax,
                         void* d_occluded);
 /* MaterialHandle::Scatter + Emit for n (ray, hit, rng state) tuples (src/core/material.h:139-161).
- * rng_state is advanced in place. scattered[i] = 0/1. */
+ * rng_state is advanced in place. scattered[i] = 0/1.  The attenuation is the material's constant rgb whatever textures are
+ * bound (the inputs carry no UV); so is the albedo of prt_sample_light's contrib. */
 int prt_scatter(PrtContext* ctx, uint32_t n, const float* in_dirs, const PrtHit* hits, uint32_t* rng_state,
                 uint32_t* scattered, float* attenuation, float* emitted, float* out_origins, float* out_dirs);
 
@@ -614,6 +683,7 @@ int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n);
 int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l);
 int prt_group_set_light_sources(PrtGroup* g, uint32_t mask);
 int prt_group_set_environment(PrtGroup* g, const PrtEnvironment* env);   /* on every rank */
+int prt_group_set_textures(PrtGroup* g, const PrtTextureSet* set);     /* on every rank, after prt_group_set_scene */
 /* shadow-ray counts summed over the ranks; n_lights / n_emitters_unsampled as rank 0 has them */
 int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out);
 int prt_group_set_param(PrtGroup* g, const char* name, int value);
@@ -644,7 +714,13 @@ int prt_mesh_had_normals(const PrtMeshData* m);
 int prt_mesh_refine(PrtMeshData* m, uint32_t target_triangles);
 /* positions = mat * positions, normals = normalize(mat3(inverse-transpose) * normals). */
 int prt_mesh_transform(PrtMeshData* m, const float mat[16], const float inv[16]);
+/* dst keeps (gets) UVs only if both sides have them or dst is empty; otherwise the result has none (never an error). */
 int prt_mesh_append(PrtMeshData* dst, const PrtMeshData* src);
+/* Per-vertex UVs (n_vertices*2 floats, NULL: none): the PLY properties s/t, u/v or texture_u/texture_v of any scalar
+ * type.  prt_mesh_refine gives a new vertex (uv_a + uv_b) * 0.5f; prt_mesh_transform leaves UVs alone. */
+const float* prt_mesh_uvs(const PrtMeshData* m);
+int prt_mesh_had_uvs(const PrtMeshData* m);
+int prt_mesh_set_uvs(PrtMeshData* m, const float* uvs); /* n_vertices*2 floats, copied; NULL drops them */
 
 /* Scene presets (src/core/scene.cpp:62-350) flattened into materials + primitives.
  * Pass NULL arrays to query counts. */

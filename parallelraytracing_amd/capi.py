@@ -103,6 +103,29 @@ class PrtEnvironmentInfo(C.Structure):
                 ("t_env", C.c_uint64), ("light_share", C.c_float)]
 
 
+class PrtTexture(C.Structure):
+    _fields_ = [("rgb", C.POINTER(C.c_float)), ("width", C.c_uint32), ("height", C.c_uint32), ("filter", C.c_uint32),
+                ("wrap", C.c_uint32)]
+
+
+class PrtTextureSet(C.Structure):
+    _fields_ = [("textures", C.POINTER(PrtTexture)), ("n_textures", C.c_uint32),
+                ("material_texture", C.POINTER(C.c_uint32)), ("n_materials", C.c_uint32),
+                ("mesh_uvs", C.POINTER(C.POINTER(C.c_float))), ("n_meshes", C.c_uint32),
+                ("instanced_mesh_uvs", C.POINTER(C.POINTER(C.c_float))), ("n_instanced_meshes", C.c_uint32)]
+
+
+class PrtTextureInfo(C.Structure):
+    _fields_ = [("is_set", C.c_uint32), ("n_textures", C.c_uint32), ("n_textured_materials", C.c_uint32),
+                ("n_uv_triangles", C.c_uint32), ("n_texels", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+# PrtTexture.filter / wrap (include/prt.h PRT_TEX_*)
+TEX_FILTERS = {"nearest": 0, "bilinear": 1}
+TEX_WRAPS = {"repeat": 0, "clamp": 1}
+TEXTURE_NONE = 0xFFFFFFFF  # PRT_TEXTURE_NONE
+TEX_MAX_SIZE = 16384       # PRT_TEX_MAX_SIZE
+
 LIGHT_ENVIRONMENT = 0xFFFFFFFE  # PRT_LIGHT_ENVIRONMENT
 ENV_RNG = 0x3C6EF372            # PRT_ENV_RNG
 
@@ -179,6 +202,14 @@ SIGNATURES = {
     "prt_environment_info": (C.c_int, [_vp, C.POINTER(PrtEnvironmentInfo)]),
     "prt_environment_intervals": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "prt_environment_eval": (C.c_int, [_vp, C.c_uint32, _fp, _fp, _u32p, _fp]),
+    "prt_set_textures": (C.c_int, [_vp, C.POINTER(PrtTextureSet)]),
+    "prt_group_set_textures": (C.c_int, [_vp, C.POINTER(PrtTextureSet)]),
+    "prt_texture_info": (C.c_int, [_vp, C.POINTER(PrtTextureInfo)]),
+    "prt_texture_eval": (C.c_int, [_vp, C.c_uint32, _u32p, _fp, _fp]),
+    "prt_hit_uv": (C.c_int, [_vp, C.c_uint32, _fp, _fp, C.POINTER(PrtHit), _fp, _fp]),
+    "prt_mesh_uvs": (_fp, [_vp]),
+    "prt_mesh_had_uvs": (C.c_int, [_vp]),
+    "prt_mesh_set_uvs": (C.c_int, [_vp, _fp]),
     "prt_read_pfm": (C.c_int, [C.c_char_p, C.POINTER(_fp), _u32p, _u32p]),
     "prt_image_free": (None, [_fp]),
     "prt_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),

@@ -146,6 +146,15 @@ struct PrtContext {
     void* d_env_col = nullptr;
     void* d_env_last = nullptr;
     uint64_t t_env_dev = 0;            // the T_e the pmfs of the light tables on the device are scaled with
+
+    // ---- image textures (PrtTextureSet, include/prt.h): a property of the current scene ----
+    PrtTexTables tex;                  // is_set = false: no binding
+    void* d_tex_texels = nullptr;
+    void* d_tex_desc = nullptr;
+    void* d_tex_mat = nullptr;
+    void* d_tex_uvs = nullptr;
+    void* d_tex_inst = nullptr;
+    uint64_t tex_bytes = 0;            // device bytes of the binding
 };
 
 namespace {
@@ -311,6 +320,55 @@ int upload_env(PrtContext* c) {
     HIPCHECK(c, up(&c->d_env_col, c->env.col_thr.data(), c->env.col_thr.size() * 4));
     HIPCHECK(c, up(&c->d_env_last, c->env.col_last.data(), c->env.col_last.size() * 4));
     return PRT_OK;
+}
+
+// ---- image textures ----
+// true: the binding changes what a batch computes (and the route it takes)
+bool tex_on(const PrtContext* c) { return c->tex.is_set && c->tex.n_textured_materials != 0u; }
+
+DevTex dev_tex(const PrtContext* c) {
+    return DevTex{(const float4*)c->d_tex_texels, (const uint4*)c->d_tex_desc, (const uint32_t*)c->d_tex_mat, (const float2*)c->d_tex_uvs,
+                  (const uint32_t*)c->d_tex_inst, c->tex.n_textures};
+}
+
+void free_tex(PrtContext* c) {
+    free_dev(c->d_tex_texels);
+    free_dev(c->d_tex_desc);
+    free_dev(c->d_tex_mat);
+    free_dev(c->d_tex_uvs);
+    free_dev(c->d_tex_inst);
+    c->tex_bytes = 0;
+}
+
+// c->tex onto the device (prt_set_textures, prt_clone_scene); waits for the context's stream
+int upload_tex(PrtContext* c) {
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    free_tex(c);
+    if (!c->tex.is_set) return PRT_OK;
+    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) c->tex_bytes += bytes;
+        return e;
+    };
+    const PrtTexTables& t = c->tex;
+    HIPCHECK(c, up(&c->d_tex_texels, t.texels.data(), t.texels.size() * 4));
+    HIPCHECK(c, up(&c->d_tex_desc, t.desc.data(), t.desc.size() * 4));
+    HIPCHECK(c, up(&c->d_tex_mat, t.mat_tex.data(), t.mat_tex.size() * 4));
+    HIPCHECK(c, up(&c->d_tex_uvs, t.uvs.data(), t.uvs.size() * 4));
+    HIPCHECK(c, up(&c->d_tex_inst, t.inst_uv_base.data(), t.inst_uv_base.size() * 4));
+    return PRT_OK;
+}
+
+// prt_set_scene: the binding goes with the scene it was made for
+void drop_tex(PrtContext* c) {
+    if (c->has_device && c->d_tex_texels) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        free_tex(c);
+    }
+    c->tex = PrtTexTables();
 }
 
 // The pmfs of the light tables on the device carry the factor (2^32 - T_e) / 2^32 (include/prt.h "Environment light"):
@@ -493,7 +551,11 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     if ((rc = sync_light_tables(c))) return rc;
     const DevEnv denv = dev_env(c);
     const DevEnv* envp = envon ? &denv : nullptr;
-    const uint32_t fuse = (!lit && !envon && c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
+    // A texture binding (prt_set_textures) that textures a material runs the instances of its own by the same rule: unfused,
+    // full ray records, no path route
+    const bool texon = tex_on(c);
+    const DevTex dtex = dev_tex(c);
+    const uint32_t fuse = (!lit && !envon && !texon && c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
     // The ray count of a bounce is only known on the device.  With big batches a k_shade grid sized for the worst case is
     // a million blocks, most of which find nothing to do (~0.5 ms per launch, 4 % of a C3 step).  The host therefore
     // reads the counts of bounce d back WHILE the traversal kernel of bounce d runs (the copy is enqueued right after
@@ -528,7 +590,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // no path route, which generates its rays itself
     const bool lens_on = c->lens.aperture > 0.0f;
     const DevLens dlens{c->lens.aperture, c->lens.focus_distance};
-    const bool path_route = !lit && !envon && !lens_on && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
+    const bool path_route = !lit && !envon && !texon && !lens_on && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
                             !trav_stats && !c->d_shade_div && c->variant == 0 && fuse == 0u && c->sort_rays == 0u &&
                             prt_path_kernel_applies(c->dsc, c->tune);
     if (path_route) {
@@ -548,7 +610,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // front/back counters of every bounce start at zero (the producers add to them atomically)
     HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
     // compact primary rays (PrtPrimary): the default pipeline without jitter / roulette / clamp / fusion
-    const bool compact = !lit && !envon && !lens_on && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
+    const bool compact = !lit && !envon && !texon && !lens_on && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
                          c->sampling.jitter == 0u && c->sampling.rr_depth == 0u && !(c->sampling.clamp > 0.0f) && fuse == 0u &&
                          prt_traverse_takes_primary(c->dsc, c->tune);
     if (compact && c->pix_entries < c->tm.n_pix_local) {
@@ -648,8 +710,12 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
         if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, c->d_counts, d, n_paths, c->d_shade_div, (compact && d == 0) ? &primary : nullptr);
         if ((rc = begin_event(c, 2, &ep))) return rc;
         if (lit) {
-            prt_launch_shade_nee(c->stream, c->dsc, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
-                                 c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
+            if (texon)
+                prt_launch_shade_nee_tex(c->stream, c->dsc, dtex, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
+                                         c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
+            else
+                prt_launch_shade_nee(c->stream, c->dsc, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
+                                     c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
             if (lt.n_lights || (envon && (denv.t_all | denv.t_env))) {
                 // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
                 // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
@@ -668,6 +734,9 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                 }
                 prt_launch_light_accum(c->stream, c->dsc, c->lb, scount, c->d_work, nmax);
             }
+        } else if (texon) {
+            prt_launch_shade_tex(c->stream, c->dsc, dtex, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, c->sampling,
+                                 n_rays_known, envp);
         } else {
             prt_launch_shade(c->stream, c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, fuse, c->sampling,
                              n_rays_known, (compact && d == 0) ? &primary : nullptr, envp);
@@ -931,6 +1000,7 @@ void prt_destroy(PrtContext* c) {
         (void)hipStreamSynchronize(c->stream);
         free_scene(c);
         free_env(c);
+        free_tex(c);
         free_path_state(c);
         free_light_state(c);
         free_dev(c->d_light_stats);
@@ -990,6 +1060,7 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     // A scene the context held before is gone whatever happens: a failure below leaves the context WITHOUT a scene (the
     // next render fails with PRT_ERR_INVALID); has_scene is set again only after the last upload.
     c->has_scene = false;
+    drop_tex(c);
     PrtHostScene hs = std::move(c->hs);  // (the compiler recycles the record arrays' storage; everything else goes)
     c->hs = PrtHostScene();
     PrtSceneOptions opt{c->pad_coeff, c->abvh_enabled != 0, nullptr};
@@ -1031,7 +1102,9 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     if (!src->has_scene) return fail(dst, PRT_ERR_INVALID, "prt_clone_scene: the source context has no scene");
     if (dst == src) return PRT_OK;
     dst->has_scene = false;
+    drop_tex(dst);
     dst->hs = src->hs;
+    dst->tex = src->tex;
     dst->inst_info = PrtInstanceUpdateInfo{};
     dst->light_sources = src->light_sources;
     dst->env = src->env;
@@ -1042,6 +1115,8 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     }
     const int rc_env = upload_env(dst);
     if (rc_env) return rc_env;
+    const int rc_tex = upload_tex(dst);
+    if (rc_tex) return rc_tex;
     return upload_scene(dst, nullptr);
 }
 
@@ -1451,6 +1526,64 @@ int prt_set_environment(PrtContext* c, const PrtEnvironment* e) {
     return c->has_scene ? sync_light_tables(c) : PRT_OK;
 }
 
+int prt_set_textures(PrtContext* c, const PrtTextureSet* set) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_textures: prt_set_scene has not been called");
+    PrtTexTables t;  // (built aside: a refused set leaves the context's binding as it was)
+    if (set) {
+        const int rc = prt_build_textures(c->hs, set, &t, &c->err);
+        if (rc) return rc;
+    }
+    c->tex = std::move(t);
+    if (!c->has_device) return PRT_OK;
+    const int rc = upload_tex(c);
+    if (rc) {  // a HIP failure midway: no binding rather than half of one
+        free_tex(c);
+        c->tex = PrtTexTables();
+    }
+    return rc;
+}
+
+int prt_texture_info(PrtContext* c, PrtTextureInfo* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    *out = PrtTextureInfo{};
+    if (!c->tex.is_set) return PRT_OK;
+    out->is_set = 1u;
+    out->n_textures = c->tex.n_textures;
+    out->n_textured_materials = c->tex.n_textured_materials;
+    out->n_uv_triangles = (uint32_t)(c->tex.uvs.size() / 6);
+    out->n_texels = c->tex.texels.size() / 4;
+    out->device_bytes = c->tex_bytes;
+    return PRT_OK;
+}
+
+int prt_texture_eval(PrtContext* c, uint32_t n, const uint32_t* texture, const float* uv, float* rgb) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->tex.is_set) return fail(c, PRT_ERR_INVALID, "prt_texture_eval: no textures are bound");
+    if (n == 0) return PRT_OK;
+    if (!texture || !uv || !rgb) return fail(c, PRT_ERR_INVALID, "null array");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (texture[i] >= c->tex.n_textures) return fail(c, PRT_ERR_INVALID, "prt_texture_eval: texture %u out of range (pair %u)", texture[i], i);
+        for (int k = 0; k < 2; ++k)
+            if (!std::isfinite(uv[2 * (size_t)i + k]) || std::fabs(uv[2 * (size_t)i + k]) > 1048576.0f)
+                return fail(c, PRT_ERR_INVALID, "prt_texture_eval: uv %u is not finite or above 2^20", i);
+    }
+    const size_t bt = ((size_t)n * 4 + 15) & ~(size_t)15, bu = ((size_t)n * 8 + 15) & ~(size_t)15, br = (size_t)n * 12;
+    if ((rc = ensure_scratch(c, bt + bu + br + 64))) return rc;
+    char* base = (char*)c->d_scratch;
+    uint32_t* d_t = (uint32_t*)base;
+    float* d_u = (float*)(base + bt);
+    float* d_r = (float*)(base + bt + bu);
+    HIPCHECK(c, hipMemcpyAsync(d_t, texture, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_u, uv, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    prt_launch_texture_eval(c->stream, dev_tex(c), n, d_t, d_u, d_r);
+    HIPCHECK(c, hipGetLastError());
+    HIPCHECK(c, hipMemcpyAsync(rgb, d_r, br, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
 int prt_environment_info(PrtContext* c, PrtEnvironmentInfo* out) {
     if (!c || !out) return PRT_ERR_INVALID;
     memset(out, 0, sizeof(*out));
@@ -1788,6 +1921,35 @@ int prt_closest_hit(PrtContext* c, uint32_t n, const float* origins, const float
     HIPCHECK(c, hipMemcpyAsync(d_d, dirs, b3, hipMemcpyHostToDevice, c->stream));
     if ((rc = enqueue_query(c, n, d_o, d_d, nullptr, d_h, nullptr))) return rc;
     HIPCHECK(c, hipMemcpyAsync(hits, d_h, bh, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+int prt_hit_uv(PrtContext* c, uint32_t n, const float* origins, const float* dirs, PrtHit* hits, float* uv, float* albedo) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (!c->tex.is_set) return fail(c, PRT_ERR_INVALID, "prt_hit_uv: no textures are bound");
+    if (n == 0) return PRT_OK;
+    if (!origins || !dirs) return fail(c, PRT_ERR_INVALID, "null array");
+    const size_t b3 = ((size_t)n * 12 + 15) & ~(size_t)15;
+    const size_t bh = ((size_t)n * sizeof(PrtHit) + 15) & ~(size_t)15;
+    const size_t b2 = ((size_t)n * 8 + 15) & ~(size_t)15;
+    if ((rc = ensure_scratch(c, 3 * b3 + bh + b2 + 64))) return rc;
+    char* base = (char*)c->d_scratch;
+    float* d_o = (float*)base;
+    float* d_d = (float*)(base + b3);
+    PrtHit* d_h = (PrtHit*)(base + 2 * b3);
+    float* d_uv = (float*)(base + 2 * b3 + bh);
+    float* d_a = (float*)(base + 2 * b3 + bh + b2);
+    HIPCHECK(c, hipMemcpyAsync(d_o, origins, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_d, dirs, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    if ((rc = enqueue_query(c, n, d_o, d_d, nullptr, d_h, nullptr))) return rc;
+    prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), n, c->rb[0], d_uv, d_a);  // (the query left rays and final hit ids in rb[0])
+    HIPCHECK(c, hipGetLastError());
+    if (hits) HIPCHECK(c, hipMemcpyAsync(hits, d_h, (size_t)n * sizeof(PrtHit), hipMemcpyDeviceToHost, c->stream));
+    if (uv) HIPCHECK(c, hipMemcpyAsync(uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (albedo) HIPCHECK(c, hipMemcpyAsync(albedo, d_a, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }

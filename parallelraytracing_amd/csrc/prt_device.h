@@ -186,7 +186,10 @@ struct WorldHit {
     bool has, front;
 };
 
-PRT_DEV void analytic_hit(const DevPrim& p, f3 o, f3 d, WorldHit& w) {
+// TEX (uv: 2 floats): the hit's texture coordinates too (include/prt.h "Image textures"): a quad's from the local hit point
+// before Mat, a sphere's are 0 (it cannot carry a textured material)
+template <bool TEX = false>
+PRT_DEV void analytic_hit(const DevPrim& p, f3 o, f3 d, WorldHit& w, float* uv = nullptr) {
     f3 lo = transform_point(p.inv, o);
     f3 ld = transform_normal(p.mat, d);
     ShapeHit h;
@@ -201,9 +204,25 @@ PRT_DEV void analytic_hit(const DevPrim& p, f3 o, f3 d, WorldHit& w) {
     w.front = h.front;
     w.material = p.material;
     w.d2 = dist2(o, w.pos);
+    if (TEX) {
+        const bool quad = p.shape_type != 0u;
+        uv[0] = quad ? h.pos.x / p.p0 + 0.5f : 0.0f;
+        uv[1] = quad ? h.pos.z / p.p1 + 0.5f : 0.0f;
+    }
 }
 
-PRT_DEV void triangle_world_hit(const DevScene& sc, uint32_t slot, f3 o, f3 d, WorldHit& w) {
+// UV of a triangle hit with Triangle::Intersect's b1, b2: entry `e` of the face-order UV table (DevTex)
+PRT_DEV void triangle_uv(const DevTex& tex, uint32_t e, float b1, float b2, float* uv) {
+    const float2 t0 = tex.uvs[3 * (size_t)e + 0];
+    const float2 t1 = tex.uvs[3 * (size_t)e + 1];
+    const float2 t2 = tex.uvs[3 * (size_t)e + 2];
+    const float w0 = 1.0f - b1 - b2;
+    uv[0] = (w0 * t0.x + b1 * t1.x) + b2 * t2.x;
+    uv[1] = (w0 * t0.y + b1 * t1.y) + b2 * t2.y;
+}
+
+template <bool TEX = false>
+PRT_DEV void triangle_world_hit(const DevScene& sc, uint32_t slot, f3 o, f3 d, WorldHit& w, const DevTex* tex = nullptr, float* uv = nullptr) {
     const float4 a = sc.tris[3 * (size_t)slot + 0];
     const float4 b = sc.tris[3 * (size_t)slot + 1];
     const float4 c = sc.tris[3 * (size_t)slot + 2];
@@ -226,12 +245,14 @@ PRT_DEV void triangle_world_hit(const DevScene& sc, uint32_t slot, f3 o, f3 d, W
     w.material = __float_as_uint(b.w);
     w.prim = (int32_t)__float_as_uint(a.w);
     w.d2 = dist2(o, pos);
+    if (TEX) triangle_uv(*tex, __float_as_uint(a.w) - sc.n_prims, b1, b2, uv);
 }
 
 // A triangle of a placed mesh copy: the loop body of PrimitiveList::Intersect with the copy's Transform
 // (src/core/primitive.cpp:29-43): local ray, Triangle::Intersect in the mesh's space, position back through Mat, normal
 // through Inv, distance in world space.  v = hit id - n_prims.
-PRT_DEV void instance_world_hit(const DevScene& sc, uint32_t v, f3 o, f3 d, WorldHit& w) {
+template <bool TEX = false>
+PRT_DEV void instance_world_hit(const DevScene& sc, uint32_t v, f3 o, f3 d, WorldHit& w, const DevTex* tex = nullptr, float* uv = nullptr) {
     uint32_t lo = 0, hi = sc.n_insts;  // the copy whose [virt_base, virt_base + n_tris) holds v
     while (hi - lo > 1u) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -262,18 +283,70 @@ PRT_DEV void instance_world_hit(const DevScene& sc, uint32_t v, f3 o, f3 d, Worl
     w.material = I.material == 0xFFFFFFFFu ? __float_as_uint(b.w) : I.material;  // world-space meshes: per triangle
     w.prim = (int32_t)(I.prim_base + __float_as_uint(a.w));
     w.d2 = dist2(o, w.pos);
+    if (TEX) triangle_uv(*tex, tex->inst_uv_base[lo] + __float_as_uint(a.w), b1, b2, uv);
 }
 
-template <bool INST = false>
-PRT_DEV void world_hit_from_id(const DevScene& sc, uint32_t id, f3 o, f3 d, WorldHit& w) {
+template <bool INST = false, bool TEX = false>
+PRT_DEV void world_hit_from_id(const DevScene& sc, uint32_t id, f3 o, f3 d, WorldHit& w, const DevTex* tex = nullptr, float* uv = nullptr) {
     if (id < sc.n_prims) {
-        analytic_hit(sc.prims[id], o, d, w);
+        analytic_hit<TEX>(sc.prims[id], o, d, w, uv);
         w.prim = (int32_t)id;
     } else if (INST) {
-        instance_world_hit(sc, id - sc.n_prims, o, d, w);
+        instance_world_hit<TEX>(sc, id - sc.n_prims, o, d, w, tex, uv);
     } else {
-        triangle_world_hit(sc, id - sc.n_prims, o, d, w);
+        triangle_world_hit<TEX>(sc, id - sc.n_prims, o, d, w, tex, uv);
     }
+}
+
+// ---- image textures (include/prt.h "Image textures"): the lookup of (u, v) in texture t, fp32 in the header's order ----
+PRT_DEV float tex_wrap(float u, uint32_t clamp) {
+    return clamp ? __builtin_fminf(__builtin_fmaxf(u, 0.0f), 1.0f) : u - __builtin_floorf(u);
+}
+// index k of an axis of size N into [0, N - 1], for every int k
+PRT_DEV uint32_t tex_index(int k, int N, uint32_t clamp) {
+    if (clamp) return (uint32_t)(k < 0 ? 0 : (k > N - 1 ? N - 1 : k));
+    const int r = k % N;
+    return (uint32_t)(r < 0 ? r + N : r);
+}
+PRT_DEV f3 texture_lookup(const DevTex& tex, uint32_t t, float u, float v) {
+    const uint4 D = tex.desc[t];
+    const uint32_t W = D.y, H = D.z, clamp = D.w >> 1;
+    const float4* __restrict__ px = tex.texels + D.x;
+    const float a = tex_wrap(u, clamp), b = tex_wrap(v, clamp);
+    const float X = a * (float)W;
+    const float Y = (1.0f - b) * (float)H;
+    if ((D.w & 1u) == 0u) {  // nearest: X, Y >= 0, so the conversion is the floor (a NaN goes to texel 0)
+        uint32_t j = X > 0.0f ? (uint32_t)X : 0u;
+        uint32_t i = Y > 0.0f ? (uint32_t)Y : 0u;
+        j = j < W - 1u ? j : W - 1u;
+        i = i < H - 1u ? i : H - 1u;
+        const float4 c = px[(size_t)i * W + j];
+        return mk3(c.x, c.y, c.z);
+    }
+    const float x = X - 0.5f, y = Y - 0.5f;
+    const float x0 = __builtin_floorf(x), y0 = __builtin_floorf(y);
+    const float fx = x - x0, fy = y - y0;
+    const int kx = (int)x0, ky = (int)y0;
+    const uint32_t j0 = tex_index(kx, (int)W, clamp), j1 = tex_index(kx + 1, (int)W, clamp);
+    const uint32_t i0 = tex_index(ky, (int)H, clamp), i1 = tex_index(ky + 1, (int)H, clamp);
+    const float4 c00 = px[(size_t)i0 * W + j0], c01 = px[(size_t)i0 * W + j1];
+    const float4 c10 = px[(size_t)i1 * W + j0], c11 = px[(size_t)i1 * W + j1];
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    return mk3((c00.x * gx + c01.x * fx) * gy + (c10.x * gx + c11.x * fx) * fy,
+               (c00.y * gx + c01.y * fx) * gy + (c10.y * gx + c11.y * fx) * fy,
+               (c00.z * gx + c01.z * fx) * gy + (c10.z * gx + c11.z * fx) * fy);
+}
+// rgb + scalar of the material at a hit with texture coordinates uv: the looked-up colour where the material is textured
+PRT_DEV float4 textured_rgbs(const DevScene& sc, const DevTex& tex, uint32_t material, const float* uv) {
+    float4 rgbs = sc.mat_rgbs[material];
+    const uint32_t t = tex.mat_tex[material];
+    if (t != PRT_TEXTURE_NONE) {
+        const f3 c = texture_lookup(tex, t, uv[0], uv[1]);
+        rgbs.x = c.x;
+        rgbs.y = c.y;
+        rgbs.z = c.z;
+    }
+    return rgbs;
 }
 
 // ---- materials (src/core/material.h) -------------------------------------------------------------------

@@ -332,6 +332,11 @@ int prt_group_set_environment(PrtGroup* g, const PrtEnvironment* env) {
     return for_each_rank(g, [&](uint32_t r) { return prt_set_environment(g->ctx[r], env); }, false);
 }
 
+int prt_group_set_textures(PrtGroup* g, const PrtTextureSet* set) {
+    if (!g) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_textures(g->ctx[r], set); }, false);
+}
+
 int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out) {
     if (!g || !out || g->ctx.empty()) return PRT_ERR_INVALID;
     memset(out, 0, sizeof(*out));

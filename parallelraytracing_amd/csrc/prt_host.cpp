@@ -490,11 +490,11 @@ static int load_ply_impl(const char* path, PrtMeshData** out, char* err, size_t 
         return e != tmp;
     };
     bool ok = true;
-    bool have_normals = false;
+    bool have_normals = false, have_uvs = false;
     for (const PlyElem& e : elems) {
         const bool is_vertex = e.name == "vertex";
         const bool is_face = e.name == "face";
-        int ix = -1, iy = -1, iz = -1, inx = -1, iny = -1, inz = -1, ilist = -1;
+        int ix = -1, iy = -1, iz = -1, inx = -1, iny = -1, inz = -1, ilist = -1, iu = -1, iv = -1;
         for (size_t k = 0; k < e.props.size(); ++k) {
             const std::string& n = e.props[k].name;
             if (n == "x") ix = (int)k;
@@ -503,6 +503,9 @@ static int load_ply_impl(const char* path, PrtMeshData** out, char* err, size_t 
             if (n == "nx") inx = (int)k;
             if (n == "ny") iny = (int)k;
             if (n == "nz") inz = (int)k;
+            // per-vertex UVs under any of their three usual spellings, any scalar type (the first spelling found stands)
+            if (!e.props[k].is_list && iu < 0 && (n == "s" || n == "u" || n == "texture_u")) iu = (int)k;
+            if (!e.props[k].is_list && iv < 0 && (n == "t" || n == "v" || n == "texture_v")) iv = (int)k;
             if (e.props[k].is_list && (n == "vertex_indices" || n == "vertex_index")) ilist = (int)k;
         }
         if (is_vertex) {
@@ -510,6 +513,12 @@ static int load_ply_impl(const char* path, PrtMeshData** out, char* err, size_t 
             have_normals = inx >= 0 && iny >= 0 && inz >= 0;
             m->pos.resize(3 * e.count);
             if (have_normals) m->nrm.resize(3 * e.count);
+            have_uvs = iu >= 0 && iv >= 0;
+            // two per vertex or none: a later vertex element without UVs must not keep an earlier one's
+            if (have_uvs)
+                m->uv.resize(2 * e.count);
+            else
+                m->uv.clear();
         }
         std::vector<double> vals(e.props.size());
         std::vector<uint32_t> poly;
@@ -558,6 +567,10 @@ static int load_ply_impl(const char* path, PrtMeshData** out, char* err, size_t 
                     m->nrm[3 * i + 1] = (float)vals[(size_t)iny];
                     m->nrm[3 * i + 2] = (float)vals[(size_t)inz];
                 }
+                if (have_uvs) {
+                    m->uv[2 * i + 0] = (float)vals[(size_t)iu];
+                    m->uv[2 * i + 1] = (float)vals[(size_t)iv];
+                }
             } else if (is_face && ilist >= 0) {
                 // The reference assumes triangles (mesh.cpp:96,132); polygons are fan-triangulated here.
                 for (size_t j = 1; j + 1 < poly.size(); ++j) {
@@ -602,10 +615,21 @@ extern "C" const float* prt_mesh_positions(const PrtMeshData* m) { return m ? m-
 extern "C" const float* prt_mesh_normals(const PrtMeshData* m) { return m ? m->nrm.data() : nullptr; }
 extern "C" const uint32_t* prt_mesh_indices(const PrtMeshData* m) { return m ? m->idx.data() : nullptr; }
 extern "C" int prt_mesh_had_normals(const PrtMeshData* m) { return m && m->had_normals ? 1 : 0; }
+extern "C" const float* prt_mesh_uvs(const PrtMeshData* m) { return m && !m->uv.empty() ? m->uv.data() : nullptr; }
+extern "C" int prt_mesh_had_uvs(const PrtMeshData* m) { return m && !m->uv.empty() ? 1 : 0; }
+extern "C" int prt_mesh_set_uvs(PrtMeshData* m, const float* uvs) {
+    if (!m) return PRT_ERR_INVALID;
+    if (!uvs) {
+        m->uv.clear();
+        return PRT_OK;
+    }
+    m->uv.assign(uvs, uvs + 2 * (m->pos.size() / 3));
+    return PRT_OK;
+}
 
 // Deterministic longest-edge bisection: repeatedly split the globally longest edge (ties: smaller
 // vertex pair) at its midpoint, splitting every triangle that shares it, until the triangle count
-// reaches the target.  New vertex: position = (a+b)*0.5, normal = normalize(na+nb).
+// reaches the target.  New vertex: position = (a+b)*0.5, normal = normalize(na+nb), uv = (uv_a + uv_b) * 0.5f.
 extern "C" int prt_mesh_refine(PrtMeshData* m, uint32_t target) {
     if (!m) return PRT_ERR_INVALID;
     struct EdgeRec {
@@ -670,6 +694,8 @@ extern "C" int prt_mesh_refine(PrtMeshData* m, uint32_t target) {
         }
         const float l = std::sqrt((nn[0] * nn[0] + nn[1] * nn[1]) + nn[2] * nn[2]);
         for (int k = 0; k < 3; ++k) m->nrm.push_back(l > 0.0f ? nn[k] / l : m->nrm[3 * (size_t)a + k]);
+        if (!m->uv.empty())
+            for (int k = 0; k < 2; ++k) m->uv.push_back((m->uv[2 * (size_t)a + k] + m->uv[2 * (size_t)b + k]) * 0.5f);
         for (int side = 0; side < 2; ++side) {
             const int32_t t = rec.tri[side];
             if (t < 0) continue;
@@ -716,7 +742,16 @@ extern "C" int prt_mesh_transform(PrtMeshData* m, const float mat[16], const flo
 
 extern "C" int prt_mesh_append(PrtMeshData* dst, const PrtMeshData* src) {
     if (!dst || !src) return PRT_ERR_INVALID;
+    if (dst == src) {  // (a vector must not be inserted into itself)
+        const PrtMeshData copy = *src;
+        return prt_mesh_append(dst, &copy);
+    }
     const uint32_t base = (uint32_t)(dst->pos.size() / 3);
+    // UVs survive only if every vertex of the result has one: both sides carry them, or dst is empty
+    if (!src->uv.empty() && (base == 0u || !dst->uv.empty()))
+        dst->uv.insert(dst->uv.end(), src->uv.begin(), src->uv.end());
+    else
+        dst->uv.clear();
     dst->pos.insert(dst->pos.end(), src->pos.begin(), src->pos.end());
     dst->nrm.insert(dst->nrm.end(), src->nrm.begin(), src->nrm.end());
     for (uint32_t i : src->idx) dst->idx.push_back(base + i);

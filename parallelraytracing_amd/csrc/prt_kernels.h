@@ -199,6 +199,21 @@ struct DevEnv {
     float p_env;       // fl(T_e / 2^32)
 };
 
+// Image textures (PrtTextureSet, include/prt.h "Image textures"; host side: PrtTexTables, prt_scene.h), passed only to the
+// kernel instances of its own (k_shade_tex, k_shade_nee_tex, k_texture_eval, k_hit_uv): DevScene and the other instances
+// stay as they are.  texels: one pool, rgb + 0; desc[t] = {first texel, W, H, filter | wrap << 1}; mat_tex[material] = texture
+// or PRT_TEXTURE_NONE; uvs: 3 x float2 per mesh triangle in FACE order, the world-space meshes first (entry = the global
+// primitive index the record carries - n_prims), then every instanced mesh once; inst_uv_base[instance] + the index the
+// record carries is the entry of a triangle met through an instance (unsigned arithmetic; null without placed copies).
+struct DevTex {
+    const float4* texels;
+    const uint4* desc;
+    const uint32_t* mat_tex;
+    const float2* uvs;
+    const uint32_t* inst_uv_base;
+    uint32_t n_textures;
+};
+
 // What the lighting shade step needs beyond k_shade's arguments: the shadow-ray buffer (o = x, path id; d = w, -;
 // t = clamped contribution rgb, tmax; hit / hd2 seeded as k_pack_occlusion_rays seeds them), the per-path pdf of the
 // previous scatter (pB, < 0: the previous vertex was not Lambertian) and the per-path light radiance.
@@ -287,3 +302,16 @@ void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevL
 // prt_environment_eval: lookup of n directions (3 floats each): rgb (3 floats), texel, pdf_w; any output may be null
 void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, const float* dirs, float* rgb, uint32_t* texel,
                                  float* pdf_w);
+// Image textures: the shade steps of a scene with a texture binding (env / ml may be null; never fused, never compact),
+// and the two function-level kernels that run the same device functions
+void prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
+                          uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp,
+                          uint32_t n_rays_known, const DevEnv* env);
+void prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const DevLights& lt, const PrtRayBuf& in,
+                              const PrtRayBuf& out, const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work,
+                              uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
+                              const DevMeshLights* ml, const DevEnv* env);
+// prt_texture_eval: texture_lookup for n (texture, uv) pairs
+void prt_launch_texture_eval(hipStream_t st, const DevTex& tex, uint32_t n, const uint32_t* texture, const float* uv, float* rgb);
+// prt_hit_uv: after the closest-hit pipeline on `in`: uv (2 floats) and albedo (3 floats) of every ray's hit; either may be null
+void prt_launch_hit_uv(hipStream_t st, const DevScene& sc, const DevTex& tex, uint32_t n, const PrtRayBuf& in, float* uv, float* albedo);

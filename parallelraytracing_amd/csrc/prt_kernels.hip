@@ -246,11 +246,12 @@ PRT_DEV f3 env_radiance(const DevEnv& env, f3 d) {
 // | front face << 31}.  It replaces world_hit_from_id for the first segment when it was computed for the same hit id (it
 // always was: all samples of a pixel trace the same primary ray; the comparison keeps the kernel correct by itself).
 // ENV (env: DevEnv): a miss delivers the environment image's texel where it delivers the constant sky.
-template <int BUDGET, bool INST, bool ABVH, int BLOCK, bool PRE = false, bool ENV = false>
+// TEX (tex: DevTex): the albedo of a vertex whose material is textured is the lookup at the hit's UV (k_shade_tex only).
+template <int BUDGET, bool INST, bool ABVH, int BLOCK, bool PRE = false, bool ENV = false, bool TEX = false>
 PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr, uint32_t& rng, uint32_t& depth,
                          uint32_t max_depth, const PrtSampling& sp, float4* __restrict__ rad_slot, uint32_t& id0,
                          float& d2_0, float4 pre_a = float4{0.f, 0.f, 0.f, 0.f}, float4 pre_b = float4{0.f, 0.f, 0.f, 0.f},
-                         const DevEnv* env = nullptr) {
+                         const DevEnv* env = nullptr, const DevTex* tex = nullptr) {
 #pragma unroll
     for (int it = 0; it <= BUDGET; ++it) {
         if (id == HIT_MISS) {  // the miss branch of IntersectClosestKernel, renderer.cu:263-271
@@ -268,16 +269,19 @@ PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr,
             return 2;
         }
         WorldHit w;
+        float uv[2] = {0.0f, 0.0f};
         if (PRE && it == 0 && __float_as_uint(pre_a.w) == id) {
             w.pos = mk3(pre_a.x, pre_a.y, pre_a.z);
             w.normal = mk3(pre_b.x, pre_b.y, pre_b.z);
             w.material = __float_as_uint(pre_b.w) & 0x7FFFFFFFu;
             w.front = (__float_as_uint(pre_b.w) >> 31) != 0u;
+        } else if (TEX) {
+            world_hit_from_id<INST, true>(sc, id, o, d, w, tex, uv);
         } else {
             world_hit_from_id<INST>(sc, id, o, d, w);
         }
         const uint32_t type = sc.mat_type[w.material];
-        const float4 rgbs = sc.mat_rgbs[w.material];
+        const float4 rgbs = TEX ? textured_rgbs(sc, *tex, w.material, uv) : sc.mat_rgbs[w.material];
         f3 atten, emitted, so, sd;
         bool scattered = false;
         if (depth + 1u >= max_depth) {
@@ -2534,12 +2538,12 @@ __global__ void __launch_bounds__(256, WAVES) k_occluded8_persistent(DevScene sc
 // material.h:119-122), so the path carries throughput only and writes rad[path] once, when it ends.
 // ---------------------------------------------------------------------------------------------------------
 // (ENV / env: see advance_path; k_shade passes false / null and keeps its code, k_shade_env is the instance with an image)
-template <int FUSE, bool SAMPLING, bool INST, bool ABVH, bool PRIM, bool ENV>
+template <int FUSE, bool SAMPLING, bool INST, bool ABVH, bool PRIM, bool ENV, bool TEX = false>
 PRT_DEV void shade_step(DevScene sc, const float4* __restrict__ ro, const float4* __restrict__ rd, const float4* __restrict__ rt,
                         const uint32_t* __restrict__ hit, float4* __restrict__ no, float4* __restrict__ nd, float4* __restrict__ nt,
                         uint32_t* __restrict__ nhit, float* __restrict__ nhd2, float4* __restrict__ rad, uint32_t* __restrict__ counts,
                         uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp_arg, PrtPrimary pr,
-                        const DevEnv* env) {
+                        const DevEnv* env, const DevTex* tex = nullptr) {
     // PRIM: the first k_shade of a batch whose k_raygen stored compact primary rays (PrtPrimary): ray, RNG seed,
     // throughput (1,1,1) and segment index (0) follow from the path id
     const PrtSampling sp = SAMPLING ? sp_arg : PrtSampling{0u, 0u, 0.0f};
@@ -2583,7 +2587,7 @@ PRT_DEV void shade_step(DevScene sc, const float4* __restrict__ ro, const float4
             d = mk3(D.x, D.y, D.z);
         }
         if (id != HIT_DEAD) {
-            const int r = advance_path<1 + FUSE, INST, ABVH, SHADE_BLOCK, PRIM, ENV>(sc, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0, pre_a, pre_b, env);
+            const int r = advance_path<1 + FUSE, INST, ABVH, SHADE_BLOCK, PRIM, ENV, TEX>(sc, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0, pre_a, pre_b, env, tex);
             front = r == 1;
             back = r == 2;
         }
@@ -2624,6 +2628,21 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_env(DevScene sc, DevEnv e
                                                           uint32_t cap, PrtSampling sp_arg) {
     shade_step<0, true, INST, ABVH, false, true>(sc, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, rad, counts, work, iter, max_depth, cap,
                                                  sp_arg, PrtPrimary{}, &env);
+}
+
+// k_shade / k_shade_env under a texture binding (include/prt.h "Image textures"): one segment per call, sampling options
+// compiled in; `env` is read only by the ENV instances
+template <bool INST, bool ABVH, bool ENV>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_tex(DevScene sc, DevTex tex, DevEnv env, const float4* __restrict__ ro,
+                                                          const float4* __restrict__ rd, const float4* __restrict__ rt,
+                                                          const uint32_t* __restrict__ hit, float4* __restrict__ no,
+                                                          float4* __restrict__ nd, float4* __restrict__ nt,
+                                                          uint32_t* __restrict__ nhit, float* __restrict__ nhd2,
+                                                          float4* __restrict__ rad, uint32_t* __restrict__ counts,
+                                                          uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth,
+                                                          uint32_t cap, PrtSampling sp_arg) {
+    shade_step<0, true, INST, ABVH, false, ENV, true>(sc, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, rad, counts, work, iter, max_depth, cap,
+                                                      sp_arg, PrtPrimary{}, ENV ? &env : nullptr, &tex);
 }
 
 // Compact primary rays: the surface interaction of a pixel's primary hit, ONCE per pixel.  Without jitter every sample of
@@ -3362,11 +3381,13 @@ PRT_DEV f3 env_miss(const DevEnv& env, uint32_t mode, f3 d, float pb, float& wb)
 // MESHL (ml: the triangle lights' tables): the light set holds triangles too, so a segment's triangle hit is weighted as well.
 // ENV (env: DevEnv): an environment light: a miss delivers its texel, weighted after a Lambertian vertex (env_miss), and a
 // Lambertian vertex whose environment-or-lights draw says so sends its light sample there (sample_environment).
-template <bool INST, bool ABVH, bool MESHL = false, bool ENV = false>
+// TEX (tex: DevTex): the albedo (attenuation and light-sample term) of a textured vertex is the lookup at the hit's UV.
+template <bool INST, bool ABVH, bool MESHL = false, bool ENV = false, bool TEX = false>
 PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t id, f3& o, f3& d, f3& thr, uint32_t& rng,
                              uint32_t& depth, uint32_t max_depth, const PrtSampling& sp, float4* __restrict__ rad_slot,
                              uint32_t& id0, float& d2_0, float pb_prev, float& pb_next, bool& shadow, f3& sx, f3& sw,
-                             float& stmax, f3& scontrib, const DevMeshLights* ml = nullptr, const DevEnv* env = nullptr) {
+                             float& stmax, f3& scontrib, const DevMeshLights* ml = nullptr, const DevEnv* env = nullptr,
+                             const DevTex* tex = nullptr) {
     if (id == HIT_MISS) {
         if (ENV) {
             float wb;
@@ -3379,9 +3400,13 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
         return 0;
     }
     WorldHit w;
-    world_hit_from_id<INST>(sc, id, o, d, w);
+    float uv[2] = {0.0f, 0.0f};
+    if (TEX)
+        world_hit_from_id<INST, true>(sc, id, o, d, w, tex, uv);
+    else
+        world_hit_from_id<INST>(sc, id, o, d, w);
     const uint32_t type = sc.mat_type[w.material];
-    const float4 rgbs = sc.mat_rgbs[w.material];
+    const float4 rgbs = TEX ? textured_rgbs(sc, *tex, w.material, uv) : sc.mat_rgbs[w.material];
     const uint32_t key = rng;  // the path's state at the vertex
     f3 atten, emitted, so, sd;
     bool scattered = false;
@@ -3467,13 +3492,13 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
 
 // The lighting shade step; MESHL / ml: see advance_path_nee (k_shade_nee passes false / null and compiles to the code it had
 // before there were triangle lights; k_shade_nee_mesh is the instance with them).
-template <bool INST, bool ABVH, bool MESHL, bool ENV = false>
+template <bool INST, bool ABVH, bool MESHL, bool ENV = false, bool TEX = false>
 PRT_DEV void shade_nee_step(DevScene sc, DevLights lt, const DevMeshLights* ml, const float4* __restrict__ ro,
                             const float4* __restrict__ rd, const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
                             float4* __restrict__ no, float4* __restrict__ nd, float4* __restrict__ nt, uint32_t* __restrict__ nhit,
                             float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
                             uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp,
-                            const DevEnv* env = nullptr) {
+                            const DevEnv* env = nullptr, const DevTex* tex = nullptr) {
     const uint32_t nA = CNT_A(counts, iter), nB = CNT_B(counts, iter);
     const uint32_t count = nA + nB;
     if (blockIdx.x * (uint32_t)SHADE_BLOCK >= count) return;  // whole block exits together
@@ -3501,8 +3526,8 @@ PRT_DEV void shade_nee_step(DevScene sc, DevLights lt, const DevMeshLights* ml, 
         // pdf of the scatter that started this segment (segment 0 starts at the camera)
         const float pb_prev = depth ? lb.pdf_b[pid] : -1.0f;
         if (id != HIT_DEAD) {
-            const int r = advance_path_nee<INST, ABVH, MESHL, ENV>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
-                                                            pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb, ml, env);
+            const int r = advance_path_nee<INST, ABVH, MESHL, ENV, TEX>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
+                                                            pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb, ml, env, tex);
             front = r == 1;
             back = r == 2;
         }
@@ -3577,6 +3602,65 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_mesh_env(DevScene sc,
                                                                    uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
                                                                    uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
     shade_nee_step<INST, ABVH, true, true>(sc, lt, &ml, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter, max_depth, cap, sp, &env);
+}
+
+// The lighting shade step under a texture binding: every combination of triangle lights (MESHL) and environment light
+// (ENV) in one kernel template; `ml` / `env` are read only by the instances that have them
+template <bool INST, bool ABVH, bool MESHL, bool ENV>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_tex(DevScene sc, DevTex tex, DevLights lt, DevMeshLights ml, DevEnv env,
+                                                              const float4* __restrict__ ro, const float4* __restrict__ rd,
+                                                              const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
+                                                              float4* __restrict__ no, float4* __restrict__ nd,
+                                                              float4* __restrict__ nt, uint32_t* __restrict__ nhit,
+                                                              float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad,
+                                                              uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                              uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
+    shade_nee_step<INST, ABVH, MESHL, ENV, true>(sc, lt, MESHL ? &ml : nullptr, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work,
+                                                 iter, max_depth, cap, sp, ENV ? &env : nullptr, &tex);
+}
+
+// prt_texture_eval: texture_lookup for n (texture, uv) pairs (the host checked the texture indices)
+__global__ void k_texture_eval(DevTex tex, uint32_t n, const uint32_t* __restrict__ texture, const float* __restrict__ uv,
+                               float* __restrict__ rgb) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const f3 c = texture_lookup(tex, texture[i], uv[2 * i], uv[2 * i + 1]);
+    rgb[3 * i + 0] = c.x;
+    rgb[3 * i + 1] = c.y;
+    rgb[3 * i + 2] = c.z;
+}
+
+// prt_hit_uv: the TEX hit reconstruction of the shade kernels for the rays of a finished closest-hit query
+__global__ void k_hit_uv(DevScene sc, DevTex tex, uint32_t n, const float4* __restrict__ ro, const float4* __restrict__ rd,
+                         const uint32_t* __restrict__ hit, float* __restrict__ uv_out, float* __restrict__ albedo) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    float uv[2] = {0.0f, 0.0f};
+    f3 a = mk3(0.0f, 0.0f, 0.0f);
+    const uint32_t id = hit[i];
+    if (id != HIT_MISS && id != HIT_DEAD) {
+        const float4 O = ro[i], D = rd[i];
+        WorldHit w;
+        if (sc.n_insts)
+            world_hit_from_id<true, true>(sc, id, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), w, &tex, uv);
+        else
+            world_hit_from_id<false, true>(sc, id, mk3(O.x, O.y, O.z), mk3(D.x, D.y, D.z), w, &tex, uv);
+        if (w.has) {
+            const float4 rgbs = textured_rgbs(sc, tex, w.material, uv);
+            a = mk3(rgbs.x, rgbs.y, rgbs.z);
+        } else {
+            uv[0] = uv[1] = 0.0f;
+        }
+    }
+    if (uv_out) {
+        uv_out[2 * i + 0] = uv[0];
+        uv_out[2 * i + 1] = uv[1];
+    }
+    if (albedo) {
+        albedo[3 * i + 0] = a.x;
+        albedo[3 * i + 1] = a.y;
+        albedo[3 * i + 2] = a.z;
+    }
 }
 
 // After the shadow walk: every unoccluded shadow ray adds its contribution to its path's light radiance (at most one shadow
@@ -4237,4 +4321,62 @@ void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevL
 void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, const float* dirs, float* rgb, uint32_t* texel,
                                  float* pdf_w) {
     hipLaunchKernelGGL(k_environment_eval, dim3(blocks_for(n)), dim3(256), 0, st, env, n, dirs, rgb, texel, pdf_w);
+}
+
+void prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
+                          uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp,
+                          uint32_t n_rays_known, const DevEnv* env) {
+    const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
+    const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
+    const DevEnv e = env ? *env : DevEnv{};
+#define PRT_SHADE_TEX(IN, AB, EN)                                                                                              \
+    hipLaunchKernelGGL((k_shade_tex<IN, AB, EN>), grid, dim3(SHADE_BLOCK), 0, st, sc, tex, e, in.o, in.d, in.t, in.hit, out.o, out.d, \
+                       out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp)
+#define PRT_SHADE_TEX2(IN, AB)                                           \
+    do {                                                                 \
+        if (env) PRT_SHADE_TEX(IN, AB, true); else PRT_SHADE_TEX(IN, AB, false); \
+    } while (0)
+    if (sc.abvh_nodes) {
+        if (sc.n_insts) PRT_SHADE_TEX2(true, true); else PRT_SHADE_TEX2(false, true);
+    } else {
+        if (sc.n_insts) PRT_SHADE_TEX2(true, false); else PRT_SHADE_TEX2(false, false);
+    }
+#undef PRT_SHADE_TEX2
+#undef PRT_SHADE_TEX
+}
+
+void prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const DevLights& lt, const PrtRayBuf& in,
+                              const PrtRayBuf& out, const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work,
+                              uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
+                              const DevMeshLights* ml, const DevEnv* env) {
+    const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
+    const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
+    const DevEnv e = env ? *env : DevEnv{};
+    const DevMeshLights m = ml ? *ml : DevMeshLights{};
+#define PRT_SHADE_NEE_TEX(IN, AB, ME, EN)                                                                                          \
+    hipLaunchKernelGGL((k_shade_nee_tex<IN, AB, ME, EN>), grid, dim3(SHADE_BLOCK), 0, st, sc, tex, lt, m, e, in.o, in.d, in.t, in.hit, \
+                       out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+#define PRT_SHADE_NEE_TEX2(IN, AB)                                                       \
+    do {                                                                                 \
+        if (ml) {                                                                        \
+            if (env) PRT_SHADE_NEE_TEX(IN, AB, true, true); else PRT_SHADE_NEE_TEX(IN, AB, true, false);   \
+        } else {                                                                         \
+            if (env) PRT_SHADE_NEE_TEX(IN, AB, false, true); else PRT_SHADE_NEE_TEX(IN, AB, false, false); \
+        }                                                                                \
+    } while (0)
+    if (sc.abvh_nodes) {
+        if (sc.n_insts) PRT_SHADE_NEE_TEX2(true, true); else PRT_SHADE_NEE_TEX2(false, true);
+    } else {
+        if (sc.n_insts) PRT_SHADE_NEE_TEX2(true, false); else PRT_SHADE_NEE_TEX2(false, false);
+    }
+#undef PRT_SHADE_NEE_TEX2
+#undef PRT_SHADE_NEE_TEX
+}
+
+void prt_launch_texture_eval(hipStream_t st, const DevTex& tex, uint32_t n, const uint32_t* texture, const float* uv, float* rgb) {
+    hipLaunchKernelGGL(k_texture_eval, dim3(blocks_for(n)), dim3(256), 0, st, tex, n, texture, uv, rgb);
+}
+
+void prt_launch_hit_uv(hipStream_t st, const DevScene& sc, const DevTex& tex, uint32_t n, const PrtRayBuf& in, float* uv, float* albedo) {
+    hipLaunchKernelGGL(k_hit_uv, dim3(blocks_for(n)), dim3(256), 0, st, sc, tex, n, in.o, in.d, in.hit, uv, albedo);
 }

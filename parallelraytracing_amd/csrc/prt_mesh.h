@@ -9,5 +9,6 @@ struct PrtMeshData {
     std::vector<float> pos;     // 3 per vertex
     std::vector<float> nrm;     // 3 per vertex
     std::vector<uint32_t> idx;  // 3 per triangle
+    std::vector<float> uv;      // 2 per vertex, or empty: the mesh has no UVs
     bool had_normals = false;
 };

@@ -428,6 +428,8 @@ int compile_world_meshes(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtH
         t += me.n_triangles;
         hs.mesh_sizes.push_back(me.n_vertices);
         hs.mesh_sizes.push_back(me.n_triangles);
+        hs.mesh_material.push_back(me.material_id);
+        if (me.n_triangles) hs.mesh_indices.insert(hs.mesh_indices.end(), me.indices, me.indices + 3 * (size_t)me.n_triangles);
     }
     const uint32_t n_prims = (uint32_t)hs.prims.size();
     hs.tri_records.assign(12 * (size_t)n_tris, 0.0f);
@@ -551,6 +553,8 @@ int build_instanced_meshes(const PrtSceneDesc* s, const PrtSceneOptions& opt, Pr
         }
         int rc = prt_flatten_mesh(me, "instanced mesh", m, v.data(), nn.data(), &B.extent, B.mn, B.mx, err);
         if (rc) return rc;
+        hs.placed_indices.emplace_back(me.indices, me.indices + 3 * (size_t)me.n_triangles);
+        hs.placed_vertices.push_back(me.n_vertices);
         B.slot_base = (uint32_t)slots;
         slots += me.n_triangles;
         if (slots >= (1ull << 26)) return fail(err, "too many triangles (limit 2^26 - 1)");
@@ -1038,6 +1042,119 @@ void prt_scaled_light_tables(const PrtHostScene& hs, uint64_t t_env, std::vector
     }
 }
 
+// ---- image textures (include/prt.h "Image textures") ----
+int prt_build_textures(const PrtHostScene& hs, const PrtTextureSet* set, PrtTexTables* out, std::string* err) {
+    if (!set) return fail(err, "prt_set_textures: null set");
+    const uint32_t n_mats = (uint32_t)hs.materials.size();
+    const uint32_t n_meshes = (uint32_t)(hs.mesh_sizes.size() / 2);
+    if (set->n_materials != n_mats) return fail(err, "prt_set_textures: the scene has %u materials, not %u", n_mats, set->n_materials);
+    if (set->n_meshes != n_meshes) return fail(err, "prt_set_textures: the scene has %u meshes, not %u", n_meshes, set->n_meshes);
+    if (set->n_instanced_meshes != hs.n_instanced_meshes)
+        return fail(err, "prt_set_textures: the scene has %u instanced meshes, not %u", hs.n_instanced_meshes, set->n_instanced_meshes);
+    if ((set->n_textures && !set->textures) || (n_mats && !set->material_texture) || (n_meshes && !set->mesh_uvs) ||
+        (set->n_instanced_meshes && !set->instanced_mesh_uvs))
+        return fail(err, "prt_set_textures: null array in the texture set");
+    PrtTexTables t;
+    t.is_set = true;
+    t.n_textures = set->n_textures;
+    // textures: sizes, modes, texels
+    uint64_t n_texels = 0;
+    for (uint32_t k = 0; k < set->n_textures; ++k) {
+        const PrtTexture& tx = set->textures[k];
+        if (tx.width == 0u || tx.height == 0u || tx.width > PRT_TEX_MAX_SIZE || tx.height > PRT_TEX_MAX_SIZE)
+            return fail(err, "texture %u: %u x %u (each side must be 1 .. %u)", k, tx.width, tx.height, PRT_TEX_MAX_SIZE);
+        if (!tx.rgb) return fail(err, "texture %u: null image", k);
+        if (tx.filter != PRT_TEX_NEAREST && tx.filter != PRT_TEX_BILINEAR) return fail(err, "texture %u: unknown filter %u", k, tx.filter);
+        if (tx.wrap != PRT_TEX_REPEAT && tx.wrap != PRT_TEX_CLAMP) return fail(err, "texture %u: unknown wrap %u", k, tx.wrap);
+        n_texels += (uint64_t)tx.width * tx.height;
+    }
+    if (n_texels >= (1ull << 32)) return fail(err, "prt_set_textures: too many texels (limit 2^32 - 1)");
+    for (uint32_t k = 0; k < set->n_textures; ++k) {
+        const PrtTexture& tx = set->textures[k];
+        const size_t n = (size_t)tx.width * tx.height;
+        for (size_t i = 0; i < 3 * n; ++i)
+            if (!(tx.rgb[i] >= 0.0f) || !std::isfinite(tx.rgb[i])) return fail(err, "texture %u: negative or non-finite texel", k);
+    }
+    // materials
+    t.mat_tex.assign(set->material_texture, set->material_texture + n_mats);
+    std::vector<uint8_t> textured(n_mats, 0);
+    for (uint32_t m = 0; m < n_mats; ++m) {
+        const uint32_t tx = t.mat_tex[m];
+        if (tx == PRT_TEXTURE_NONE) continue;
+        if (tx >= set->n_textures) return fail(err, "material %u: texture %u out of range", m, tx);
+        if (hs.materials[m].type != PRT_MAT_LAMBERTIAN && hs.materials[m].type != PRT_MAT_METAL)
+            return fail(err, "material %u: only Lambertian and Metal materials take a texture", m);
+        textured[m] = 1;
+        ++t.n_textured_materials;
+    }
+    // who uses a textured material: no sphere, no mesh or placed copy without UVs
+    for (size_t i = 0; i < hs.prims.size(); ++i)
+        if (hs.prims[i].shape_type == PRT_SHAPE_CIRCLE && textured[hs.prims[i].material])
+            return fail(err, "primitive %zu: a sphere cannot carry a textured material", i);
+    for (uint32_t m = 0; m < n_meshes; ++m)
+        if (hs.mesh_sizes[2 * m + 1] && textured[hs.mesh_material[m]] && !set->mesh_uvs[m])
+            return fail(err, "mesh %u: a textured material needs UVs", m);
+    const bool placed = !hs.inst_mesh.empty();
+    for (size_t i = 0; placed && i < hs.inst_mesh.size(); ++i)
+        if (textured[hs.dev_insts[hs.n_world_insts + i].material] && !set->instanced_mesh_uvs[hs.inst_mesh[i]])
+            return fail(err, "instance %zu: a textured material needs UVs on its mesh", i);
+    auto uv_ok = [](const float* uv, size_t n_vertices) {
+        for (size_t i = 0; i < 2 * n_vertices; ++i)
+            if (!std::isfinite(uv[i]) || std::fabs(uv[i]) > 1048576.0f) return false;
+        return true;
+    };
+    for (uint32_t m = 0; m < n_meshes; ++m)
+        if (set->mesh_uvs[m] && !uv_ok(set->mesh_uvs[m], hs.mesh_sizes[2 * m])) return fail(err, "mesh %u: a UV is not finite or above 2^20", m);
+    for (uint32_t m = 0; placed && m < hs.n_instanced_meshes; ++m)
+        if (set->instanced_mesh_uvs[m] && !uv_ok(set->instanced_mesh_uvs[m], hs.placed_vertices[m]))
+            return fail(err, "instanced mesh %u: a UV is not finite or above 2^20", m);
+    // ---- everything is checked: the tables ----
+    t.texels.resize(4 * (size_t)n_texels);
+    t.desc.resize(4 * (size_t)set->n_textures);
+    size_t at = 0;
+    for (uint32_t k = 0; k < set->n_textures; ++k) {
+        const PrtTexture& tx = set->textures[k];
+        t.desc[4 * (size_t)k + 0] = (uint32_t)at;
+        t.desc[4 * (size_t)k + 1] = tx.width;
+        t.desc[4 * (size_t)k + 2] = tx.height;
+        t.desc[4 * (size_t)k + 3] = tx.filter | (tx.wrap << 1);
+        const size_t n = (size_t)tx.width * tx.height;
+        for (size_t i = 0; i < n; ++i) {
+            t.texels[4 * (at + i) + 0] = tx.rgb[3 * i + 0];
+            t.texels[4 * (at + i) + 1] = tx.rgb[3 * i + 1];
+            t.texels[4 * (at + i) + 2] = tx.rgb[3 * i + 2];
+            t.texels[4 * (at + i) + 3] = 0.0f;
+        }
+        at += n;
+    }
+    size_t n_uv_tris = hs.mesh_indices.size() / 3;
+    std::vector<uint32_t> placed_base(hs.placed_indices.size(), 0u);
+    for (size_t m = 0; m < hs.placed_indices.size(); ++m) {
+        placed_base[m] = (uint32_t)n_uv_tris;
+        n_uv_tris += hs.placed_indices[m].size() / 3;
+    }
+    t.uvs.assign(6 * n_uv_tris, 0.0f);
+    auto fill = [&](float* dst, const uint32_t* idx, size_t n_idx, const float* uv) {
+        for (size_t i = 0; uv && i < n_idx; ++i) {
+            dst[2 * i + 0] = uv[2 * (size_t)idx[i] + 0];
+            dst[2 * i + 1] = uv[2 * (size_t)idx[i] + 1];
+        }
+    };
+    size_t tri = 0;
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        const size_t n = hs.mesh_sizes[2 * m + 1];
+        fill(t.uvs.data() + 6 * tri, hs.mesh_indices.data() + 3 * tri, 3 * n, set->mesh_uvs[m]);
+        tri += n;
+    }
+    for (size_t m = 0; m < hs.placed_indices.size(); ++m)
+        fill(t.uvs.data() + 6 * (size_t)placed_base[m], hs.placed_indices[m].data(), hs.placed_indices[m].size(), set->instanced_mesh_uvs[m]);
+    t.inst_uv_base.resize(hs.dev_insts.size());
+    for (size_t i = 0; i < hs.dev_insts.size(); ++i)
+        t.inst_uv_base[i] = i < hs.n_world_insts ? 0u - hs.sc.n_prims : placed_base[hs.inst_mesh[i - hs.n_world_insts]];
+    *out = std::move(t);
+    return PRT_OK;
+}
+
 int prt_check_scene_arrays(const PrtSceneDesc* s, std::string* err) {
     if ((s->n_materials && !s->materials) || (s->n_primitives && !s->primitives) || (s->n_meshes && !s->meshes) ||
         (s->n_instanced_meshes && !s->instanced_meshes) || (s->n_instances && !s->instances))
@@ -1057,6 +1174,7 @@ int prt_compile_scene(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHost
     PrtHostScene& hs = *out;
     Work w;
     if ((rc = compile_prims(s, hs, err))) return rc;
+    hs.n_instanced_meshes = s->n_instanced_meshes;
     build_light_table(&hs, s);
     if ((rc = compile_world_meshes(s, opt, hs, w, err))) return rc;
     build_prim_bvh(s, opt, hs);

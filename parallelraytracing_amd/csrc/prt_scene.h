@@ -113,7 +113,32 @@ struct PrtHostScene {
     std::vector<double> light_power;   // per light of `lights`: emitting area x mean(rgb)
     uint32_t ml_tris_counted = 0;      // the part of n_emitters_unsampled that is mesh / placed triangles
     PrtMeshLights ml;                  // the light set with emissive triangles in it (PRT_LIGHT_SOURCES_MESH)
+    // what a texture binding needs of the description beyond the above (prt_build_textures): the index buffers in face order
+    std::vector<uint32_t> mesh_indices;    // the world-space meshes', mesh and face order: 3 per triangle
+    std::vector<uint32_t> mesh_material;   // per world-space mesh
+    std::vector<std::vector<uint32_t>> placed_indices;  // per instanced mesh (scenes with placed copies)
+    std::vector<uint32_t> placed_vertices; // per instanced mesh: n_vertices
+    uint32_t n_instanced_meshes = 0;       // of the description (they are compiled only when it has placed copies)
 };
+
+// The texture binding of a scene (include/prt.h "Image textures"): one pool of texels, a descriptor per texture, the
+// texture of every material and the UV table.  The UV table is per mesh triangle in FACE order (6 floats: u0 v0 u1 v1 u2
+// v2), the world-space meshes' triangles first (entry = global primitive index - n_prims), then every instanced mesh's
+// once, shared by its placed copies; inst_uv_base[i] + (the index a triangle record of instance i carries) is the entry
+// (unsigned arithmetic: the identity instance of the world-space meshes gets -n_prims).  No tree, builder, refit or
+// instance update touches it.  A mesh without UVs has zeros.
+struct PrtTexTables {
+    bool is_set = false;
+    uint32_t n_textures = 0;
+    uint32_t n_textured_materials = 0;
+    std::vector<float> texels;           // 4 floats per texel: rgb, 0
+    std::vector<uint32_t> desc;          // 4 per texture: first texel, W, H, filter | wrap << 1
+    std::vector<uint32_t> mat_tex;       // per material: texture or PRT_TEXTURE_NONE
+    std::vector<float> uvs;              // 6 floats per triangle
+    std::vector<uint32_t> inst_uv_base;  // per instance of PrtHostScene::dev_insts
+};
+// Checks `set` against the compiled scene (PRT_ERR_INVALID, message in *err, *out untouched) and builds the tables.
+int prt_build_textures(const PrtHostScene& hs, const PrtTextureSet* set, PrtTexTables* out, std::string* err);
 
 // The light tables as the kernels get them under an environment with threshold t_env: copies of hs.lights / hs.ml.records
 // whose pmf entries are prt_scaled_pmf of the exact pmf (t_env = 0: the tables themselves).  Either output may be null.

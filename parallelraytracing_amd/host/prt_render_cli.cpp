@@ -4,6 +4,9 @@
 //              [--seed S] [--camera x y z] [--out PREFIX] [--gpus N | --devices a,b,c] [--sif S] [--frames K]
 //              [--lighting off|nee|mis] [--light-sources analytic|all] [--env FILE.pfm [--env-share Q]]
 //              [--fov-deg D] [--aperture R --focus F]
+//              [--ground-texture FILE.pfm] [--mesh-texture FILE.pfm] [--texture-filter nearest|bilinear]
+// --ground-texture / --mesh-texture (with --ply) take the albedo of the ground quad / of the mesh from a colour PFM (top
+// row first, repeated outside [0, 1]); the mesh needs per-vertex UVs in its PLY (s/t, u/v or texture_u/texture_v).
 // --fov-deg sets the vertical field of view in degrees (default: the reference's 1 rad); --aperture R (lens radius, world
 // units) with --focus F (distance of the plane in focus along the view direction) renders with a thin lens.
 // --env lights the scene with a lat-long colour PFM (top row = the +Y pole) instead of the constant sky; with a lighting
@@ -29,7 +32,8 @@ static int preset_id(const std::string& n) {
 }
 
 int main(int argc, char** argv) {
-    std::string preset = "CORNELL", ply, out = "frame", env;
+    std::string preset = "CORNELL", ply, out = "frame", env, ground_tex, mesh_tex;
+    uint32_t tex_filter = PRT_TEX_NEAREST;
     float env_share = 0.5f, aperture = 0.0f, focus = 0.0f;
     double fov_deg = 0.0;
     uint32_t W = 256, H = 256, spp = 1, depth = 2, seed = 0, refine = 0, sif = 0, frames = 1, lighting = PRT_LIGHTING_OFF;
@@ -69,10 +73,22 @@ int main(int argc, char** argv) {
         else if (a == "--fov-deg") fov_deg = atof(next());
         else if (a == "--aperture") aperture = (float)atof(next());
         else if (a == "--focus") focus = (float)atof(next());
+        else if (a == "--ground-texture") ground_tex = next();
+        else if (a == "--mesh-texture") mesh_tex = next();
+        else if (a == "--texture-filter") {
+            const std::string m = next();
+            if (m == "nearest") tex_filter = PRT_TEX_NEAREST;
+            else if (m == "bilinear") tex_filter = PRT_TEX_BILINEAR;
+            else { fprintf(stderr, "--texture-filter takes nearest or bilinear\n"); return 2; }
+        }
         else if (a == "--gpus") { const int n = atoi(next()); devices.clear(); for (int d = 0; d < n; ++d) devices.push_back(d); }
         else if (a == "--devices") { devices.clear(); std::string l = next(); for (size_t p = 0; p < l.size();) { size_t e = l.find(',', p); if (e == std::string::npos) e = l.size(); devices.push_back(atoi(l.substr(p, e - p).c_str())); p = e + 1; } }
         else if (a == "--camera") { for (int k = 0; k < 3; ++k) cam[k] = (float)atof(next()); cam_set = true; }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
+    }
+    if ((!ground_tex.empty() || !mesh_tex.empty()) && ply.empty()) {
+        fprintf(stderr, "--ground-texture and --mesh-texture go with --ply (the presets have no ground quad or mesh of their own)\n");
+        return 2;
     }
     try {
         std::unique_ptr<prt::Scene> scene;
@@ -85,6 +101,11 @@ int main(int argc, char** argv) {
             scene->AddPrimitive(PRT_SHAPE_QUAD, 20, 20, ground, one, zero, gt);
             scene->AddPrimitive(PRT_SHAPE_QUAD, 4, 4, light, one, flip, lt);
             scene->AddMeshPly(ply, body, refine);
+            if (!ground_tex.empty()) scene->SetMaterialTexture(ground, scene->AddTexturePfm(ground_tex, tex_filter));
+            if (!mesh_tex.empty()) {
+                if (!scene->MeshHasUVs(0)) { fprintf(stderr, "error: --mesh-texture: %s has no per-vertex UVs\n", ply.c_str()); return 1; }
+                scene->SetMaterialTexture(body, scene->AddTexturePfm(mesh_tex, tex_filter));
+            }
             if (!cam_set) { cam[0] = 1.2f; cam[1] = 0.4f; cam[2] = 1.9f; }
         } else {
             const int id = preset_id(preset);

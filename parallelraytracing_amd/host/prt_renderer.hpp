@@ -62,6 +62,7 @@ public:
         owned_.push_back(m);
         meshes.push_back(PrtMesh{prt_mesh_positions(m), prt_mesh_normals(m), prt_mesh_indices(m), prt_mesh_vertex_count(m),
                                  prt_mesh_triangle_count(m), material});
+        mesh_uvs.push_back(prt_mesh_uvs(m));  // the file's s/t (u/v, texture_u/texture_v), or null
     }
     // A mesh that is placed, not flattened (PrtInstance): returns its index for AddInstance
     uint32_t AddInstancedMeshPly(const std::string& path) {
@@ -71,7 +72,52 @@ public:
         owned_.push_back(m);
         instanced_meshes.push_back(PrtMesh{prt_mesh_positions(m), prt_mesh_normals(m), prt_mesh_indices(m), prt_mesh_vertex_count(m),
                                            prt_mesh_triangle_count(m), 0u});
+        instanced_mesh_uvs.push_back(prt_mesh_uvs(m));
         return (uint32_t)instanced_meshes.size() - 1;
+    }
+    // Image textures (include/prt.h "Image textures"): rgb = height * width * 3 floats, row 0 = top, copied
+    uint32_t AddTexture(const float* rgb, uint32_t width, uint32_t height, uint32_t filter = PRT_TEX_NEAREST, uint32_t wrap = PRT_TEX_REPEAT) {
+        texels_.emplace_back(rgb, rgb + (size_t)width * height * 3);
+        tex_meta_.push_back(PrtTexture{nullptr, width, height, filter, wrap});
+        return (uint32_t)tex_meta_.size() - 1;
+    }
+    // ... from a colour PFM file (prt_read_pfm)
+    uint32_t AddTexturePfm(const std::string& path, uint32_t filter = PRT_TEX_NEAREST, uint32_t wrap = PRT_TEX_REPEAT) {
+        float* rgb = nullptr;
+        uint32_t w = 0, h = 0;
+        if (prt_read_pfm(path.c_str(), &rgb, &w, &h)) throw Error("cannot read " + path + " as a colour PFM");
+        const uint32_t t = AddTexture(rgb, w, h, filter, wrap);
+        prt_image_free(rgb);
+        return t;
+    }
+    // the albedo of a Lambertian / Metal material comes from `texture` (PRT_TEXTURE_NONE: its rgb again)
+    void SetMaterialTexture(uint32_t material, uint32_t texture) {
+        if (material_texture.size() < materials.size()) material_texture.resize(materials.size(), PRT_TEXTURE_NONE);
+        material_texture.at(material) = texture;
+    }
+    bool HasTextures() const { return !tex_meta_.empty(); }
+    bool MeshHasUVs(uint32_t mesh) const { return mesh_uvs.at(mesh) != nullptr; }
+    // valid while the scene lives and is not changed (the arrays it points into are caches of this scene: the scene's own
+    // description is not touched).  mesh_uvs / instanced_mesh_uvs hold one entry per mesh: a scene whose mesh vectors were
+    // filled by hand keeps them in step, or is refused here
+    PrtTextureSet textureSet() const {
+        if (mesh_uvs.size() != meshes.size() || instanced_mesh_uvs.size() != instanced_meshes.size())
+            throw Error("Scene: mesh_uvs / instanced_mesh_uvs need one entry (or null) per mesh");
+        if (material_texture.size() > materials.size()) throw Error("Scene: material_texture is longer than materials");
+        set_material_texture_ = material_texture;
+        set_material_texture_.resize(materials.size(), PRT_TEXTURE_NONE);
+        set_textures_ = tex_meta_;
+        for (size_t k = 0; k < set_textures_.size(); ++k) set_textures_[k].rgb = texels_[k].data();
+        PrtTextureSet t{};
+        t.textures = set_textures_.data();
+        t.n_textures = (uint32_t)set_textures_.size();
+        t.material_texture = set_material_texture_.data();
+        t.n_materials = (uint32_t)materials.size();
+        t.mesh_uvs = mesh_uvs.data();
+        t.n_meshes = (uint32_t)meshes.size();
+        t.instanced_mesh_uvs = instanced_mesh_uvs.data();
+        t.n_instanced_meshes = (uint32_t)instanced_meshes.size();
+        return t;
     }
     // A placed copy (uniform scale only); SetInstanceTransform moves it, HipWavefrontRenderer::UpdateInstances follows
     uint32_t AddInstance(uint32_t mesh, uint32_t material, float scale, const float euler_deg[3], const float translation[3]) {
@@ -108,10 +154,16 @@ public:
     std::vector<PrtMesh> meshes;
     std::vector<PrtMesh> instanced_meshes;
     std::vector<PrtInstance> instances;
+    std::vector<const float*> mesh_uvs, instanced_mesh_uvs;  // per mesh: its per-vertex UVs, or null
+    std::vector<uint32_t> material_texture;                  // per material (shorter: the rest has none)
     float sky[3] = {0.4f, 0.3f, 0.6f};  // src/backend/cpu/renderer.h:31
 
 private:
     std::vector<PrtMeshData*> owned_;
+    std::vector<std::vector<float>> texels_;
+    std::vector<PrtTexture> tex_meta_;
+    mutable std::vector<PrtTexture> set_textures_;  // what the last textureSet() points into
+    mutable std::vector<uint32_t> set_material_texture_;
 };
 
 // Camera(position, front, width, height) (reference: src/core/camera.h:10-16)
@@ -172,6 +224,7 @@ public:
     void Init(Film& film, const Scene& scene, const Camera& camera) override {
         PrtSceneDesc d = scene.desc();
         check(prt_group_set_scene(grp_, &d));  // flattened + BVH built once, cloned to the other GPUs
+        if (scene.HasTextures()) SetTextures(scene);
         check(prt_group_set_film(grp_, film.width, film.height));
         film_ = &film;
         frame_ = 0;
@@ -231,6 +284,13 @@ public:
         prt_image_free(rgb);
         check(rc);
     }
+    // Binds the scene's textures (Scene::AddTexture / SetMaterialTexture, the meshes' UVs) on every GPU; `scene` must be the
+    // one Init got.  Init does this itself; UpdateInstances keeps the binding.
+    void SetTextures(const Scene& scene) {
+        const PrtTextureSet t = scene.textureSet();
+        check(prt_group_set_textures(grp_, &t));
+    }
+    void ClearTextures() { check(prt_group_set_textures(grp_, nullptr)); }
     PrtLightStats LightStats() {
         PrtLightStats s{};
         check(prt_group_get_light_stats(grp_, &s));

@@ -55,7 +55,7 @@ def make_transform(scale, euler_deg, translation) -> Tuple[np.ndarray, np.ndarra
 class Mesh:
     """Triangle mesh: vertices / normals / indices, as the reference's Mesh (src/core/mesh.h:12-14)."""
 
-    def __init__(self, ply_path: Optional[str] = None, *, vertices=None, normals=None, indices=None):
+    def __init__(self, ply_path: Optional[str] = None, *, vertices=None, normals=None, indices=None, uvs=None):
         L = capi.lib()
         h = C.c_void_p()
         if ply_path is not None:
@@ -72,6 +72,8 @@ class Mesh:
             if rc:
                 raise PrtError("prt_mesh_create failed (index out of range?)")
         self._h = h
+        if uvs is not None:
+            self.SetUVs(uvs)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -99,6 +101,27 @@ class Mesh:
     def GetIndices(self) -> np.ndarray:
         return np.ctypeslib.as_array(capi.lib().prt_mesh_indices(self._h), (self.n_triangles, 3)).copy()
 
+    @property
+    def had_uvs(self) -> bool:
+        return bool(capi.lib().prt_mesh_had_uvs(self._h))
+
+    def GetUVs(self) -> Optional[np.ndarray]:
+        """Per-vertex texture coordinates [n_vertices, 2] (a PLY's s/t, u/v or texture_u/texture_v), or None."""
+        p = capi.lib().prt_mesh_uvs(self._h)
+        return np.ctypeslib.as_array(p, (self.n_vertices, 2)).copy() if p else None
+
+    def SetUVs(self, uvs) -> "Mesh":
+        """uvs [n_vertices, 2], or None to drop them."""
+        if uvs is None:
+            capi.lib().prt_mesh_set_uvs(self._h, None)
+            return self
+        a = _f32(uvs)
+        if a.shape != (self.n_vertices, 2):
+            raise ValueError(f"uvs: shape {a.shape}, expected ({self.n_vertices}, 2)")
+        if capi.lib().prt_mesh_set_uvs(self._h, a.ctypes.data_as(_fp)):
+            raise PrtError("prt_mesh_set_uvs failed")
+        return self
+
     def refine(self, target_triangles: int) -> "Mesh":
         if capi.lib().prt_mesh_refine(self._h, int(target_triangles)):
             raise PrtError("prt_mesh_refine failed (non-manifold edge)")
@@ -114,7 +137,7 @@ class Mesh:
         return self
 
     def copy(self) -> "Mesh":
-        return Mesh(vertices=self.GetVertices(), normals=self.GetNormals(), indices=self.GetIndices())
+        return Mesh(vertices=self.GetVertices(), normals=self.GetNormals(), indices=self.GetIndices(), uvs=self.GetUVs())
 
 
 class Scene:
@@ -129,7 +152,10 @@ class Scene:
         self.instanced_meshes: List[Mesh] = []
         self.instances: List[PrtInstance] = []
         self.sky = tuple(float(x) for x in sky)
+        self.textures: List[Tuple[np.ndarray, int, int]] = []  # (rgb [H, W, 3], filter, wrap)
+        self.material_texture: dict = {}                       # material -> texture
         self._keep = None
+        self._keep_tex = None
         if preset is not None:
             pid = capi.PRESET_NAMES[preset] if isinstance(preset, str) else int(preset)
             nm, npr = C.c_uint32(0), C.c_uint32(0)
@@ -217,6 +243,42 @@ class Scene:
         inst.mat[:] = mat.tolist()
         inst.inv[:] = inv.tolist()
         inst.srt = (tuple(float(v) for v in sc), tuple(float(v) for v in euler_deg), tuple(float(v) for v in translation))
+
+    # ---- image textures (include/prt.h "Image textures") ----
+    def AddTexture(self, rgb, filter="nearest", wrap="repeat") -> int:
+        """An image [H, W, 3] of albedo, row 0 = top; filter "nearest" | "bilinear", wrap "repeat" | "clamp"."""
+        a = _f32(rgb).copy()
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("texture: rgb must be [H, W, 3]")
+        f = capi.TEX_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        w = capi.TEX_WRAPS[wrap] if isinstance(wrap, str) else int(wrap)
+        self.textures.append((a, f, w))
+        return len(self.textures) - 1
+
+    def SetMaterialTexture(self, material: int, texture: Optional[int]):
+        """The albedo of a Lambertian or Metal material comes from `texture` (an index AddTexture returned); None: its rgb."""
+        if texture is None:
+            self.material_texture.pop(int(material), None)
+        else:
+            self.material_texture[int(material)] = int(texture)
+
+    def texture_set(self) -> Optional["capi.PrtTextureSet"]:
+        """The PrtTextureSet of this scene (meshes' UVs included), or None if it has no textures at all."""
+        if not self.textures and not self.material_texture:
+            return None
+        L = capi.lib()
+        tex = (capi.PrtTexture * max(1, len(self.textures)))()
+        for k, (a, f, w) in enumerate(self.textures):
+            tex[k].rgb = a.ctypes.data_as(_fp)
+            tex[k].width, tex[k].height, tex[k].filter, tex[k].wrap = a.shape[1], a.shape[0], f, w
+        mt = (C.c_uint32 * max(1, len(self.materials)))(*[self.material_texture.get(m, capi.TEXTURE_NONE)
+                                                        for m in range(len(self.materials))])
+        uv = (_fp * max(1, len(self.meshes)))(*[L.prt_mesh_uvs(m._h) for m, _ in self.meshes])
+        iuv = (_fp * max(1, len(self.instanced_meshes)))(*[L.prt_mesh_uvs(m._h) for m in self.instanced_meshes])
+        ts = capi.PrtTextureSet(tex, len(self.textures), mt, len(self.materials), uv, len(self.meshes), iuv,
+                                len(self.instanced_meshes))
+        self._keep_tex = (tex, mt, uv, iuv)
+        return ts
 
     @property
     def n_triangles(self) -> int:
@@ -350,6 +412,8 @@ class HipWavefrontRenderer:
         L = capi.lib()
         d = scene.desc()
         self._check(L.prt_set_scene(self._ctx, C.byref(d)))
+        if scene.textures or scene.material_texture:  # (prt_set_scene dropped the previous scene's binding)
+            self.set_textures(scene)
         self._check(L.prt_set_film(self._ctx, film.width, film.height, self.rank, self.world_size))
         self.film = film
         film._renderer = self
@@ -420,6 +484,37 @@ class HipWavefrontRenderer:
         s = capi.PrtEnvironmentInfo()
         self._check(capi.lib().prt_environment_info(self._ctx, C.byref(s)))
         return s
+
+    def set_textures(self, scene: Optional["Scene"]):
+        """Binds `scene`'s textures (Scene.AddTexture / SetMaterialTexture, the meshes' UVs) to the current scene, which must
+        be the one `scene` describes; a scene without textures, or None, removes the binding.  Init does this itself;
+        Refit and UpdateInstances keep the binding (include/prt.h "Image textures")."""
+        ts = scene.texture_set() if scene is not None else None
+        self._check(capi.lib().prt_set_textures(self._ctx, None if ts is None else C.byref(ts)))
+
+    def texture_info(self) -> "capi.PrtTextureInfo":
+        s = capi.PrtTextureInfo()
+        self._check(capi.lib().prt_texture_info(self._ctx, C.byref(s)))
+        return s
+
+    def texture_eval(self, texture, uv) -> np.ndarray:
+        """prt_texture_eval: the render's own lookup, rgb [n, 3] for uv [n, 2] in `texture` (one index, or one per uv)."""
+        u = _f32(uv).reshape(-1, 2)
+        n = u.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(texture, np.uint32), (n,)))
+        rgb = np.zeros((n, 3), np.float32)
+        self._check(capi.lib().prt_texture_eval(self._ctx, n, t.ctypes.data_as(_u32p), u.ctypes.data_as(_fp), rgb.ctypes.data_as(_fp)))
+        return rgb
+
+    def hit_uv(self, origins, dirs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """prt_hit_uv: (hits as closest_hit returns them, uv [n, 2], albedo [n, 3]) through the shade kernels' device code."""
+        o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)
+        n = o.shape[0]
+        hits = np.zeros(n, dtype=capi.HIT_DTYPE)
+        uv, alb = np.zeros((n, 2), np.float32), np.zeros((n, 3), np.float32)
+        self._check(capi.lib().prt_hit_uv(self._ctx, n, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp),
+                                          hits.ctypes.data_as(C.POINTER(PrtHit)), uv.ctypes.data_as(_fp), alb.ctypes.data_as(_fp)))
+        return hits, uv, alb
 
     def environment_intervals(self) -> Tuple[np.ndarray, np.ndarray]:
         """The exact interval widths (row [H] uint64, column [H, W] uint64); texel pmf = row x column / 2^64.  Host-only
@@ -745,6 +840,8 @@ class HipWavefrontRenderer:
         """For host-only contexts (device < 0): build the BVH without a GPU."""
         d = scene.desc()
         self._check(capi.lib().prt_set_scene(self._ctx, C.byref(d)))
+        if scene.textures or scene.material_texture:
+            self.set_textures(scene)
 
 
 class HipWavefrontGroupRenderer:
@@ -789,6 +886,8 @@ class HipWavefrontGroupRenderer:
         L = capi.lib()
         d = scene.desc()
         self._check(L.prt_group_set_scene(self._grp, C.byref(d)))
+        if scene.textures or scene.material_texture:
+            self.set_textures(scene)
         self._check(L.prt_group_set_film(self._grp, film.width, film.height))
         self.film = film
         self.frame_index = 0
@@ -854,6 +953,18 @@ class HipWavefrontGroupRenderer:
     def set_environment(self, rgb, light_share: float = 0.5):
         """HipWavefrontRenderer.set_environment on every rank."""
         self._check(_set_environment(capi.lib().prt_group_set_environment, self._grp, rgb, light_share))
+
+    def set_textures(self, scene: Optional[Scene]):
+        """HipWavefrontRenderer.set_textures on every rank."""
+        ts = scene.texture_set() if scene is not None else None
+        self._check(capi.lib().prt_group_set_textures(self._grp, None if ts is None else C.byref(ts)))
+
+    def texture_info(self, rank: int = 0) -> "capi.PrtTextureInfo":
+        s = capi.PrtTextureInfo()
+        L = capi.lib()
+        if L.prt_texture_info(L.prt_group_context(self._grp, int(rank)), C.byref(s)):
+            raise PrtError(f"prt_texture_info failed on rank {rank}")
+        return s
 
     def light_info(self) -> Tuple[np.ndarray, np.ndarray]:
         """The light set as rank 0 holds it (every rank holds the same)."""

@@ -30,6 +30,19 @@ def mesh_scene(mesh: Mesh, mesh_albedo=(0.8, 0.8, 0.8)) -> Scene:
     return sc
 
 
+def checker(n: int, a=(0.9, 0.9, 0.9), b=(0.1, 0.1, 0.1)) -> np.ndarray:
+    """An n x n checkerboard image [n, n, 3] for Scene.AddTexture: colour `a` where row + column is even, `b` elsewhere."""
+    i, j = np.indices((int(n), int(n)))
+    return np.where(((i + j) % 2 == 0)[..., None], np.asarray(a, np.float32), np.asarray(b, np.float32)).astype(np.float32)
+
+
+def planar_uvs(mesh: Mesh, axes=(0, 2)) -> np.ndarray:
+    """Per-vertex UVs [n_vertices, 2]: two coordinates of the vertices, scaled to [0, 1] over the mesh's box."""
+    v = mesh.GetVertices()[:, list(axes)]
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    return ((v - lo) / np.maximum(hi - lo, np.float32(1e-30))).astype(np.float32)
+
+
 def refined(ply: str, target_triangles: int) -> Mesh:
     m = Mesh(asset(ply))
     if target_triangles > m.n_triangles:
