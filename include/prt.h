@@ -625,6 +625,14 @@ int prt_kernel_occupancy(PrtContext* ctx, PrtOccupancy* out);
  * prt_kernel_occupancy describes): "lean8_5waves", "deep15_4waves", "inst12_4waves", "wide11_5waves", "bvh4", "bvh2".
  * Written NUL-terminated into name[capacity].  The same decision function drives the launch (csrc/prt_kernels.hip). */
 int prt_kernel_instance(PrtContext* ctx, char* name, uint32_t capacity);
+/* Name of the shade kernel instance that the context's last batch launched (the last bounce's, if a batch's bounces differ:
+ * compact primary rays shade bounce 0 with an instance of their own), with its template arguments as the compiler's symbol
+ * table spells them: "k_shade<0, true, false, false, false>", "k_shade_env<false, true>", "k_shade_nee_mesh<true, false>",
+ * "k_shade_tex<INST, ABVH, ENV>", "k_shade_nee_tex<INST, ABVH, MESHL, ENV>", ...  The string is written by the launch macro
+ * itself from the template arguments it launches with (csrc/prt_kernels.hip), so it cannot differ from what ran.  Empty
+ * before the first batch and after a batch on the path-kernel route, which launches no shade kernel.  Read-only; written
+ * NUL-terminated into name[capacity]. */
+int prt_shade_instance(PrtContext* ctx, char* name, uint32_t capacity);
 /* Copies the built BVH out (host arrays): nodes n_nodes*16 floats (layout: csrc/bvh.h), tris
  * n_triangles*12 floats in leaf order.  Either pointer may be NULL.  Works on host-only contexts. */
 int prt_bvh_read(PrtContext* ctx, float* nodes, float* tris);

@@ -104,6 +104,7 @@ struct PrtContext {
     int node_stride = 0;      // prt_set_param("node_stride", 5 | 8): uint4 per 8-wide node slot, 0 = by tree size (upload_scene); before prt_set_scene
     int compact_primary = 1;  // prt_set_param("compact_primary", 0): k_raygen stores full ray records (A/B)
     int primary_walk = 1;     // prt_set_param("primary_walk", 0): compact primary rays are walked once per sample, not once per pixel (A/B)
+    const char* shade_instance = "";  // the shade kernel instance the last run_batch launched, as its launch macro spelled it (prt_shade_instance)
     bool batch_walked = false;  // the last run_batch took the one-walk-per-pixel route (prt_measure_traversal counts its list)
     int gpu_build = 0;  // prt_set_param("gpu_build", 1): the next prt_set_scene builds the 8-wide tree on the device
     PrtSampling sampling{0u, 0u, 0.0f};
@@ -593,6 +594,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     const bool path_route = !lit && !envon && !texon && !lens_on && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
                             !trav_stats && !c->d_shade_div && c->variant == 0 && fuse == 0u && c->sort_rays == 0u &&
                             prt_path_kernel_applies(c->dsc, c->tune);
+    c->shade_instance = "";  // (the path route launches no shade kernel)
     if (path_route) {
         HIPCHECK(c, hipMemsetAsync(c->d_work, 0, 256 * sizeof(uint32_t), c->stream));  // the cursors; the error flags in [256] stay for prt_synchronize
         PrtPathArgs pa{c->cam, c->tm, c->sampling, c->d_rad, first_sample, seed, max_depth, n_paths};
@@ -711,11 +713,11 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
         if ((rc = begin_event(c, 2, &ep))) return rc;
         if (lit) {
             if (texon)
-                prt_launch_shade_nee_tex(c->stream, c->dsc, dtex, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
-                                         c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
+                c->shade_instance = prt_launch_shade_nee_tex(c->stream, c->dsc, dtex, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
+                                                             c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
             else
-                prt_launch_shade_nee(c->stream, c->dsc, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
-                                     c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
+                c->shade_instance = prt_launch_shade_nee(c->stream, c->dsc, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
+                                                         c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
             if (lt.n_lights || (envon && (denv.t_all | denv.t_env))) {
                 // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
                 // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
@@ -735,11 +737,11 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                 prt_launch_light_accum(c->stream, c->dsc, c->lb, scount, c->d_work, nmax);
             }
         } else if (texon) {
-            prt_launch_shade_tex(c->stream, c->dsc, dtex, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, c->sampling,
-                                 n_rays_known, envp);
+            c->shade_instance = prt_launch_shade_tex(c->stream, c->dsc, dtex, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
+                                                     c->sampling, n_rays_known, envp);
         } else {
-            prt_launch_shade(c->stream, c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, fuse, c->sampling,
-                             n_rays_known, (compact && d == 0) ? &primary : nullptr, envp);
+            c->shade_instance = prt_launch_shade(c->stream, c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, fuse,
+                                                 c->sampling, n_rays_known, (compact && d == 0) ? &primary : nullptr, envp);
         }
         if ((rc = end_event(c, &ep))) return rc;
         if (exact && d + 1 < max_depth) HIPCHECK(c, read_back(d + 1));
@@ -2252,6 +2254,12 @@ int prt_kernel_instance(PrtContext* c, char* name, uint32_t capacity) {
     if (!c || !name || capacity == 0u) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     snprintf(name, capacity, "%s", prt_traverse_instance(c->dsc, c->tune));
+    return PRT_OK;
+}
+
+int prt_shade_instance(PrtContext* c, char* name, uint32_t capacity) {
+    if (!c || !name || capacity == 0u) return PRT_ERR_INVALID;
+    snprintf(name, capacity, "%s", c->shade_instance);
     return PRT_OK;
 }
 

@@ -245,10 +245,12 @@ int prt_traverse_occupancy(const DevScene& sc, const PrtTravTuning& tune, int* b
 const char* prt_traverse_instance(const DevScene& sc, const PrtTravTuning& tune);
 void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                           uint32_t max_rays, int stack_depth, int variant, unsigned long long* stats);
-void prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
-                      uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap,
-                      uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary = nullptr,
-                      const DevEnv* env = nullptr);  // env: the instance with an environment image (no fusion, no compact primaries)
+// The four shade launchers return the name of the instance they launched, spelled by the launch macro from its own template
+// arguments ("k_shade_tex<false, true, false>"): what prt_shade_instance reports
+const char* prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
+                             uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap,
+                             uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary = nullptr,
+                             const DevEnv* env = nullptr);  // env: the instance with an environment image (no fusion, no compact primaries)
 // diagnostic: per-wave material mix of what k_shade of bounce `iter` is about to shade (16 words per bounce in `out`)
 void prt_launch_shade_divstats(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* counts, uint32_t iter,
                                uint32_t cap, unsigned long long* out, const PrtPrimary* primary = nullptr);
@@ -287,11 +289,11 @@ void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, con
 // lighting modes (PrtLighting): the shade step with a light sample per Lambertian vertex (shadow rays into lb.sh, counted
 // in counts[iter * stride + 48]); after the shadow walk, the unoccluded contributions into lb.lrad (and the traversal
 // cursors reset for the next bounce); the film accumulation of rad + lrad
-void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
-                          const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
-                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
-                          const DevMeshLights* ml = nullptr,  // ml: the instances that sample triangle lights
-                          const DevEnv* env = nullptr);       // env: the instances with an environment light
+const char* prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
+                                 const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
+                                 uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
+                                 const DevMeshLights* ml = nullptr,  // ml: the instances that sample triangle lights
+                                 const DevEnv* env = nullptr);       // env: the instances with an environment light
 void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBufs& lb, const uint32_t* count_ptr,
                             uint32_t* work, uint32_t max_rays);
 void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, const PrtTileMap& tm,
@@ -304,13 +306,13 @@ void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, 
                                  float* pdf_w);
 // Image textures: the shade steps of a scene with a texture binding (env / ml may be null; never fused, never compact),
 // and the two function-level kernels that run the same device functions
-void prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
-                          uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp,
-                          uint32_t n_rays_known, const DevEnv* env);
-void prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const DevLights& lt, const PrtRayBuf& in,
-                              const PrtRayBuf& out, const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work,
-                              uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
-                              const DevMeshLights* ml, const DevEnv* env);
+const char* prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
+                                 uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp,
+                                 uint32_t n_rays_known, const DevEnv* env);
+const char* prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const DevLights& lt, const PrtRayBuf& in,
+                                     const PrtRayBuf& out, const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work,
+                                     uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
+                                     const DevMeshLights* ml, const DevEnv* env);
 // prt_texture_eval: texture_lookup for n (texture, uv) pairs
 void prt_launch_texture_eval(hipStream_t st, const DevTex& tex, uint32_t n, const uint32_t* texture, const float* uv, float* rgb);
 // prt_hit_uv: after the closest-hit pipeline on `in`: uv (2 floats) and albedo (3 floats) of every ray's hit; either may be null

@@ -4131,29 +4131,39 @@ void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& i
 #undef PRT_LAUNCH_I
 }
 
-void prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
+const char* prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
                       uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap,
                       uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary, const DevEnv* env) {
     // n_rays_known: the ray count of this bounce if the host has it already (0xFFFFFFFF: size the grid for `cap`)
     const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
     const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
+    // (every launch macro of the shade launchers names its instance from the very template arguments it launches with:
+    // prt_shade_instance reports that string, so the name and the launch cannot drift apart)
+    const char* name = "";
     if (env) {
 #define PRT_SHADE_ENV(IN, AB)                                                                                              \
-    hipLaunchKernelGGL((k_shade_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, *env, in.o, in.d, in.t, in.hit, out.o, out.d, \
-                       out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp)
+    do {                                                                                                                   \
+        name = "k_shade_env<" #IN ", " #AB ">";                                                                           \
+        hipLaunchKernelGGL((k_shade_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, *env, in.o, in.d, in.t, in.hit, out.o, out.d, \
+                           out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp);                         \
+    } while (0)
         if (sc.abvh_nodes) {
             if (sc.n_insts) PRT_SHADE_ENV(true, true); else PRT_SHADE_ENV(false, true);
         } else {
             if (sc.n_insts) PRT_SHADE_ENV(true, false); else PRT_SHADE_ENV(false, false);
         }
 #undef PRT_SHADE_ENV
-        return;
+        return name;
     }
-#define PRT_SHADE(F, SA, IN, AB)                                                                                    \
-    hipLaunchKernelGGL((k_shade<F, SA, IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, in.o, in.d, in.t, in.hit, out.o, \
-                       out.d, out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp, PrtPrimary{})
+#define PRT_SHADE(F, SA, IN, AB)                                                                                        \
+    do {                                                                                                                \
+        name = "k_shade<" #F ", " #SA ", " #IN ", " #AB ", false>";                                                     \
+        hipLaunchKernelGGL((k_shade<F, SA, IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, in.o, in.d, in.t, in.hit, out.o, \
+                           out.d, out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp, PrtPrimary{}); \
+    } while (0)
     const bool sa = sp.rr_depth != 0u || sp.clamp > 0.0f;
     if (primary) {  // (the host only asks for this with the default instance's conditions: no placed copies, no primitive BVH, no sampling options, no fusion)
+        name = "k_shade<0, false, false, false, true>";
         hipLaunchKernelGGL((k_shade<0, false, false, false, true>), grid, dim3(SHADE_BLOCK), 0, st, sc, in.o, in.d, in.t, in.hit,
                            out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp, *primary);
     } else if (sc.abvh_nodes) {  // many analytic primitives: general instances with the BVH scan
@@ -4166,6 +4176,7 @@ void prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, c
         if (sa) PRT_SHADE(0, true, false, false); else PRT_SHADE(0, false, false, false);
     }
 #undef PRT_SHADE
+    return name;
 }
 
 void prt_launch_shade_divstats(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* counts, uint32_t iter,
@@ -4240,19 +4251,26 @@ void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, con
                        atten, emitted, o_out, d_out);
 }
 
-void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
+const char* prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
                           const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
                           uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known, const DevMeshLights* ml,
                           const DevEnv* env) {
     const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
     const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
+    const char* name = "";
     if (env) {
 #define PRT_SHADE_NEE_ENV(IN, AB)                                                                                            \
-    hipLaunchKernelGGL((k_shade_nee_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *env, in.o, in.d, in.t, in.hit, out.o, \
-                       out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+    do {                                                                                                                     \
+        name = "k_shade_nee_env<" #IN ", " #AB ">";                                                                         \
+        hipLaunchKernelGGL((k_shade_nee_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *env, in.o, in.d, in.t, in.hit, out.o, \
+                           out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);                \
+    } while (0)
 #define PRT_SHADE_NEE_MESH_ENV(IN, AB)                                                                                        \
-    hipLaunchKernelGGL((k_shade_nee_mesh_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *ml, *env, in.o, in.d, in.t, in.hit, \
-                       out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+    do {                                                                                                                      \
+        name = "k_shade_nee_mesh_env<" #IN ", " #AB ">";                                                                     \
+        hipLaunchKernelGGL((k_shade_nee_mesh_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *ml, *env, in.o, in.d, in.t, in.hit, \
+                           out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);          \
+    } while (0)
         if (ml) {
             if (sc.abvh_nodes) {
                 if (sc.n_insts) PRT_SHADE_NEE_MESH_ENV(true, true); else PRT_SHADE_NEE_MESH_ENV(false, true);
@@ -4266,14 +4284,20 @@ void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& l
         }
 #undef PRT_SHADE_NEE_MESH_ENV
 #undef PRT_SHADE_NEE_ENV
-        return;
+        return name;
     }
-#define PRT_SHADE_NEE(IN, AB)                                                                                          \
-    hipLaunchKernelGGL((k_shade_nee<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, in.o, in.d, in.t, in.hit, out.o,  \
-                       out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
-#define PRT_SHADE_NEE_MESH(IN, AB)                                                                                         \
-    hipLaunchKernelGGL((k_shade_nee_mesh<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *ml, in.o, in.d, in.t, in.hit,  \
-                       out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+#define PRT_SHADE_NEE(IN, AB)                                                                                             \
+    do {                                                                                                                  \
+        name = "k_shade_nee<" #IN ", " #AB ">";                                                                          \
+        hipLaunchKernelGGL((k_shade_nee<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, in.o, in.d, in.t, in.hit, out.o, \
+                           out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);             \
+    } while (0)
+#define PRT_SHADE_NEE_MESH(IN, AB)                                                                                            \
+    do {                                                                                                                      \
+        name = "k_shade_nee_mesh<" #IN ", " #AB ">";                                                                         \
+        hipLaunchKernelGGL((k_shade_nee_mesh<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *ml, in.o, in.d, in.t, in.hit, \
+                           out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);          \
+    } while (0)
     if (ml) {  // triangle lights in the light set
         if (sc.abvh_nodes) {
             if (sc.n_insts) PRT_SHADE_NEE_MESH(true, true); else PRT_SHADE_NEE_MESH(false, true);
@@ -4287,6 +4311,7 @@ void prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& l
     }
 #undef PRT_SHADE_NEE_MESH
 #undef PRT_SHADE_NEE
+    return name;
 }
 
 void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBufs& lb, const uint32_t* count_ptr,
@@ -4323,15 +4348,19 @@ void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, 
     hipLaunchKernelGGL(k_environment_eval, dim3(blocks_for(n)), dim3(256), 0, st, env, n, dirs, rgb, texel, pdf_w);
 }
 
-void prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
+const char* prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
                           uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp,
                           uint32_t n_rays_known, const DevEnv* env) {
     const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
     const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
     const DevEnv e = env ? *env : DevEnv{};
-#define PRT_SHADE_TEX(IN, AB, EN)                                                                                              \
-    hipLaunchKernelGGL((k_shade_tex<IN, AB, EN>), grid, dim3(SHADE_BLOCK), 0, st, sc, tex, e, in.o, in.d, in.t, in.hit, out.o, out.d, \
-                       out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp)
+    const char* name = "";
+#define PRT_SHADE_TEX(IN, AB, EN)                                                                                                  \
+    do {                                                                                                                           \
+        name = "k_shade_tex<" #IN ", " #AB ", " #EN ">";                                                                          \
+        hipLaunchKernelGGL((k_shade_tex<IN, AB, EN>), grid, dim3(SHADE_BLOCK), 0, st, sc, tex, e, in.o, in.d, in.t, in.hit, out.o, out.d, \
+                           out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp);                                 \
+    } while (0)
 #define PRT_SHADE_TEX2(IN, AB)                                           \
     do {                                                                 \
         if (env) PRT_SHADE_TEX(IN, AB, true); else PRT_SHADE_TEX(IN, AB, false); \
@@ -4343,9 +4372,10 @@ void prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex,
     }
 #undef PRT_SHADE_TEX2
 #undef PRT_SHADE_TEX
+    return name;
 }
 
-void prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const DevLights& lt, const PrtRayBuf& in,
+const char* prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const DevLights& lt, const PrtRayBuf& in,
                               const PrtRayBuf& out, const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work,
                               uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
                               const DevMeshLights* ml, const DevEnv* env) {
@@ -4353,9 +4383,13 @@ void prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& 
     const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
     const DevEnv e = env ? *env : DevEnv{};
     const DevMeshLights m = ml ? *ml : DevMeshLights{};
-#define PRT_SHADE_NEE_TEX(IN, AB, ME, EN)                                                                                          \
-    hipLaunchKernelGGL((k_shade_nee_tex<IN, AB, ME, EN>), grid, dim3(SHADE_BLOCK), 0, st, sc, tex, lt, m, e, in.o, in.d, in.t, in.hit, \
-                       out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp)
+    const char* name = "";
+#define PRT_SHADE_NEE_TEX(IN, AB, ME, EN)                                                                                              \
+    do {                                                                                                                               \
+        name = "k_shade_nee_tex<" #IN ", " #AB ", " #ME ", " #EN ">";                                                                 \
+        hipLaunchKernelGGL((k_shade_nee_tex<IN, AB, ME, EN>), grid, dim3(SHADE_BLOCK), 0, st, sc, tex, lt, m, e, in.o, in.d, in.t, in.hit, \
+                           out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);                   \
+    } while (0)
 #define PRT_SHADE_NEE_TEX2(IN, AB)                                                       \
     do {                                                                                 \
         if (ml) {                                                                        \
@@ -4371,6 +4405,7 @@ void prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& 
     }
 #undef PRT_SHADE_NEE_TEX2
 #undef PRT_SHADE_NEE_TEX
+    return name;
 }
 
 void prt_launch_texture_eval(hipStream_t st, const DevTex& tex, uint32_t n, const uint32_t* texture, const float* uv, float* rgb) {

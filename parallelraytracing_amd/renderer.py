@@ -816,6 +816,13 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_kernel_instance(self._ctx, buf, 64))
         return buf.value.decode()
 
+    def shade_instance(self) -> str:
+        """Name of the shade kernel instance the last batch launched, as its launch spelled it (prt_shade_instance);
+        "" before the first batch."""
+        buf = C.create_string_buffer(96)
+        self._check(capi.lib().prt_shade_instance(self._ctx, buf, 96))
+        return buf.value.decode()
+
     def bvh_read(self):
         b = self.bvh_info()
         nodes = np.zeros((b.n_nodes, 16), np.float32)

@@ -204,6 +204,12 @@ class TexScene:
 
 
 # ---- the walker: lighting_replay.walk with the looked-up colour as albedo ----------------------------------------------------
+MISS_RGB = None   # lighting off under an environment image: a function of the missing rays' directions [m, 3] -> rgb [m, 3]
+#                   float32 in the sky's place (a GPU test hands in the device's own lookup, prt_environment_eval, which
+#                   tests/test_gpu_environment.py holds to the float64 mapping: a float64 lookup cannot settle a direction on a
+#                   texel edge, and a frame compared bit for bit needs every miss)
+
+
 def walk(scene, osc, cam, W, H, max_depth, seed, pix, samp, sampling=(0, 0, 0.0), use_bvh=False, n_threads=None):
     """lighting_replay.walk of a scene with textures (Scene.AddTexture / SetMaterialTexture): the same record; at a vertex whose
     material is textured the attenuation and the `albedo` entry are the looked-up colour.  Every record also carries `uv`."""
@@ -236,7 +242,7 @@ def walk(scene, osc, cam, W, H, max_depth, seed, pix, samp, sampling=(0, 0, 0.0)
         colour = ts.albedo(hits, uv)
         is_tex = ts.textured(hits)
         term = np.zeros((m, 3), F)
-        term[~hit] = thr[~hit] * sky
+        term[~hit] = thr[~hit] * (sky if MISS_RGB is None else np.asarray(MISS_RGB(d[~hit]), F).reshape(-1, 3))
         mtype = np.zeros(m, np.int64)
         albedo = np.zeros((m, 3), F)
         scattered = np.zeros(m, bool)
@@ -337,11 +343,22 @@ def scene_a(mode="full"):
     return dict(name="A_" + mode, scene=sc, cam=cam, W=W, H=H, depth=4, sampling=(0, 0, 0.0), use_bvh=True)
 
 
-def scene_b(emissive_copy=False, copies=True):
+def _small_emissive_cube(at, scale):
+    """cube_uv.ply as a world-space mesh of 12 triangles, `scale` of its size around `at` (for a scene without placed copies)."""
+    from parallelraytracing_amd import scenes
+    cube = prt.Mesh(scenes.asset("cube_uv.ply"))
+    mat, inv = prt.make_transform((scale, scale, scale), (0.0, 10.0, 0.0), at)
+    cube.transform(mat, inv)
+    return cube
+
+
+def scene_b(emissive_copy=False, copies=True, emissive_sphere=False, emissive_mesh=False):
     """B: a 10,000-triangle bunny with planar UVs (a world-space mesh; 16 x 16 random image, bilinear, repeat) and two placed
     copies of the cube at different scale and rotation that share one UV array (8 x 8 checker, nearest, repeat; 3 x 5 random
     image, bilinear, repeat) on an untextured ground under an emissive quad.  40 x 30, depth 4.  emissive_copy: a third, small
-    emissive copy (a triangle light for the MESH light sources); copies = False: the bunny alone (a scene that can be refitted)."""
+    emissive copy (a triangle light for the MESH light sources); copies = False: the bunny alone (a scene that can be refitted).
+    emissive_sphere: a third analytic primitive, a floating sphere light; emissive_mesh: the small emissive cube as a world-space
+    mesh (a triangle light in a scene without placed copies)."""
     from parallelraytracing_amd import scenes
     W, H = 40, 30
     sc = prt.Scene(preset=None)
@@ -352,9 +369,13 @@ def scene_b(emissive_copy=False, copies=True):
     c2 = sc.AddMetal((0.9, 0.9, 0.9), 0.3)
     sc.AddQuad(20.0, 20.0, ground, translation=(0.0, -1.0, 0.0))
     sc.AddQuad(4.0, 4.0, light, euler_deg=(180.0, 0.0, 0.0), translation=(0.0, 5.0, 0.0))
+    if emissive_sphere:
+        sc.AddCircle(0.25, sc.AddEmissive((6.0, 8.0, 12.0)), translation=(-1.6, 0.9, 1.6))
     bunny = prt.Mesh(scenes.asset("bunny.ply"))
     bunny.SetUVs(scenes.planar_uvs(bunny, (0, 1)) * F(3.0))
     sc.AddMesh(bunny, fur)
+    if emissive_mesh:
+        sc.AddMesh(_small_emissive_cube((0.2, 1.6, 1.5), 0.15), sc.AddEmissive((40.0, 30.0, 20.0)))
     cube = prt.Mesh(scenes.asset("cube_uv.ply"))
     if copies:
         sc.AddInstance(cube, c1, scale=0.45, euler_deg=(15.0, 30.0, 0.0), translation=(-1.6, -0.3, 0.6))
@@ -366,6 +387,107 @@ def scene_b(emissive_copy=False, copies=True):
     sc.SetMaterialTexture(c2, sc.AddTexture(_random_image(5, 3, 3), "bilinear", "repeat"))
     cam = prt.Camera((0.6, 1.2, 4.5), width=W, height=H)
     return dict(name="B", scene=sc, cam=cam, W=W, H=H, depth=4, sampling=(0, 0, 0.0), use_bvh=True)
+
+
+def scene_e(emissive_mesh=False):
+    """E: scene B's bunny alone (no placed copies; two quads and a sphere, so no primitive BVH) under the emissive quad and a
+    floating sphere light; emissive_mesh: plus the small emissive cube as a world-space mesh."""
+    return dict(scene_b(copies=False, emissive_sphere=True, emissive_mesh=emissive_mesh), name="E")
+
+
+# the textured quads of scenes C, D and Q: (width, height, scale, euler_deg, translation, texture).  Non-square, turned about one,
+# two and three axes, one scaled; the upright pair faces the camera with opposite faces and the fourth lies face down, so that
+# quads are hit on their back faces; textures 0 .. 3 are the four filter x wrap combinations.
+_QUADS = (
+    (9.0, 4.0, 1.0, (90.0, 0.0, 0.0), (0.0, 1.0, -2.5), 1),        # the back wall
+    (1.6, 1.0, 1.0, (35.0, 40.0, 0.0), (-2.2, 0.0, 0.8), 2),
+    (1.2, 1.8, 1.0, (200.0, 30.0, 15.0), (2.3, 0.1, 0.6), 3),       # face down
+    (1.0, 0.6, 1.7, (50.0, -30.0, 10.0), (-0.9, -0.2, 2.2), 1),     # scaled
+    (0.9, 1.3, 1.0, (90.0, 0.0, 0.0), (1.2, -0.3, 2.0), 0),         # upright
+    (0.9, 1.3, 1.0, (-90.0, 20.0, 0.0), (-2.4, -0.3, 2.4), 2),      # upright, the other face toward the camera
+)
+
+
+def _textured_quads(sc, extra=0):
+    """The ground (8 x 8 checker, nearest, repeat), _QUADS and `extra` small tilted quads on a ring, each with a material of its
+    own bound to one of four textures (nearest / bilinear x repeat / clamp), under the emissive quad.  -> indices of the quads
+    that are turned about at least two axes."""
+    from parallelraytracing_amd import scenes
+    tex = [sc.AddTexture(scenes.checker(8), "nearest", "repeat"), sc.AddTexture(_random_image(5, 3, 5), "bilinear", "clamp"),
+           sc.AddTexture(_random_image(4, 4, 6), "nearest", "clamp"), sc.AddTexture(scenes.checker(4, (0.9, 0.8, 0.3), (0.2, 0.3, 0.6)), "bilinear", "repeat")]
+
+    def quad(w, h, scale, euler, at, t, metal=False):
+        m = sc.AddMetal((0.8, 0.8, 0.8), 0.2) if metal else sc.AddLambertian((0.7, 0.7, 0.7))
+        sc.SetMaterialTexture(m, tex[t])
+        sc.AddQuad(w, h, m, scale=(scale, scale, scale), euler_deg=euler, translation=at)
+        return len(sc.primitives) - 1
+
+    quad(20.0, 20.0, 1.0, (0.0, 0.0, 0.0), (0.0, -1.0, 0.0), 0)
+    sc.AddQuad(4.0, 4.0, sc.AddEmissive((15.0, 15.0, 15.0)), euler_deg=(180.0, 0.0, 0.0), translation=(0.0, 5.0, 0.0))
+    rotated = []
+    for k, (w, h, s, e, at, t) in enumerate(_QUADS):
+        q = quad(w, h, s, e, at, t, metal=k == 2)
+        if sum(a % 180.0 != 0.0 for a in e) >= 2:
+            rotated.append(q)
+    for k in range(extra):
+        a = 2.0 * np.pi * (k + 0.5) / extra
+        rotated.append(quad(0.6, 0.4, 1.0 + 0.1 * (k % 3), (25.0 + 11.0 * k, 30.0 * k, 7.0 * k), (3.3 * np.cos(a), -0.6, 3.3 * np.sin(a)), k % 4))
+    return rotated
+
+
+def scene_c(emissive_mesh=False, copies=False, emissive_copy=False):
+    """C: 22 analytic primitives, every one placed by rotation + uniform scale + translation, so the primitive BVH is built, and
+    no placed copy: the ground, the emissive quad, the six textured quads of _QUADS, a metal sphere, a floating sphere light and
+    twelve small Lambertian spheres on a ring, around scene B's 10,000-triangle bunny, whose planar UVs reach -1 .. 2 under a
+    bilinear, clamped image.  40 x 30, depth 4.  emissive_mesh: the small emissive cube as a world-space mesh.
+    D (copies = True): plus two textured placed copies of the cube, whose shared UVs reach -0.5 .. 1.5, and with emissive_copy a
+    third, small emissive one."""
+    from parallelraytracing_amd import scenes
+    W, H = 40, 30
+    sc = prt.Scene(preset=None)
+    rotated = _textured_quads(sc)
+    sc.AddCircle(0.45, sc.AddMetal((0.9, 0.8, 0.6), 0.1), translation=(2.6, -0.5, 2.2))
+    sc.AddCircle(0.25, sc.AddEmissive((6.0, 8.0, 12.0)), translation=(-1.5, 0.9, 1.8))
+    for k in range(12):
+        a = 2.0 * np.pi * k / 12.0
+        sc.AddCircle(0.1, sc.AddLambertian((0.3 + 0.05 * k, 0.8 - 0.04 * k, 0.5)), scale=(1.2, 1.2, 1.2), euler_deg=(0.0, 30.0 * k, 0.0),
+                     translation=(3.1 * np.cos(a), -0.85, 3.1 * np.sin(a)))
+    assert len(sc.primitives) >= 20
+    fur = sc.AddLambertian((0.8, 0.7, 0.6))
+    bunny = prt.Mesh(scenes.asset("bunny.ply"))
+    bunny.SetUVs(scenes.planar_uvs(bunny, (0, 1)) * F(3.0) - F(1.0))
+    sc.AddMesh(bunny, fur)
+    sc.SetMaterialTexture(fur, sc.AddTexture(_random_image(16, 16, 2), "bilinear", "clamp"))
+    if emissive_mesh:
+        sc.AddMesh(_small_emissive_cube((0.4, 1.5, 2.0), 0.12), sc.AddEmissive((40.0, 30.0, 20.0)))
+    if copies:
+        cube = prt.Mesh(scenes.asset("cube_uv.ply"))
+        cube.SetUVs(cube.GetUVs() * F(2.0) - F(0.5))
+        c1, c2 = sc.AddLambertian((0.6, 0.6, 0.6)), sc.AddMetal((0.9, 0.9, 0.9), 0.3)
+        sc.AddInstance(cube, c1, scale=0.3, euler_deg=(15.0, 30.0, 0.0), translation=(0.2, -0.5, 2.6))
+        sc.AddInstance(cube, c2, scale=0.25, euler_deg=(0.0, 65.0, 20.0), translation=(1.9, -0.5, 3.0))
+        if emissive_copy:
+            sc.AddInstance(cube, sc.AddEmissive((40.0, 30.0, 20.0)), scale=0.12, euler_deg=(0.0, 10.0, 0.0), translation=(0.4, 1.5, 2.0))
+        sc.SetMaterialTexture(c1, sc.AddTexture(scenes.checker(8), "nearest", "repeat"))
+        sc.SetMaterialTexture(c2, sc.AddTexture(_random_image(5, 3, 3), "bilinear", "repeat"))
+    cam = prt.Camera((0.6, 1.6, 5.5), width=W, height=H)
+    return dict(name="D" if copies else "C", scene=sc, cam=cam, W=W, H=H, depth=4, sampling=(0, 0, 0.0), use_bvh=True, rotated_quads=rotated)
+
+
+def scene_d(emissive_copy=False):
+    return scene_c(copies=True, emissive_copy=emissive_copy)
+
+
+def scene_q(big=False):
+    """Q: quads only, no triangle at all (no tree: a batch launches no traversal).  The ground, the emissive quad and _QUADS, every
+    one but the emitter textured: 8 primitives, scanned linearly; big: plus 12 small tilted quads on a ring, 20 primitives, walked
+    through the primitive BVH.  40 x 30, depth 4."""
+    W, H = 40, 30
+    sc = prt.Scene(preset=None)
+    rotated = _textured_quads(sc, extra=12 if big else 0)
+    assert len(sc.primitives) == (20 if big else 8)
+    cam = prt.Camera((0.6, 1.6, 5.5), width=W, height=H)
+    return dict(name="Q_big" if big else "Q_small", scene=sc, cam=cam, W=W, H=H, depth=4, sampling=(0, 0, 0.0), use_bvh=True, rotated_quads=rotated)
 
 
 def primary_and_random_rays(c, n_random=2000, seed=3):
@@ -393,6 +515,9 @@ def eval_grid(W, H):
 
 # ---- the lighting cases: textured frames through the existing float64 replays ------------------------------------------------
 LIGHTING_CASES = ("A_mis_analytic", "B_nee_analytic", "B_mis_mesh", "A_mis_env", "B_nee_mesh_env")
+# the cases of tests/test_gpu_texture_instances.py: scenes C (primitive BVH), D (primitive BVH and placed copies) and E (neither)
+INSTANCE_LIGHTING_CASES = ("C_mis_analytic", "C_nee_mesh", "C_mis_env", "C_nee_mesh_env", "D_nee_analytic", "D_mis_mesh", "D_nee_analytic_env",
+                           "D_mis_mesh_env", "E_mis_analytic", "E_nee_mesh", "E_mis_env", "E_nee_mesh_env")
 
 
 def patch_walk(monkeypatch):
@@ -409,7 +534,9 @@ def lighting_case(name):
     import environment_replay as er
     import mesh_light_replay as mr
     scene, mode, sources = name.split("_")[0], name.split("_")[1], ("all" if "mesh" in name else "analytic")
-    c = scene_a() if scene == "A" else scene_b(emissive_copy=sources == "all")
+    mesh = sources == "all"
+    c = {"A": scene_a, "B": lambda: scene_b(emissive_copy=mesh), "C": lambda: scene_c(emissive_mesh=mesh),
+         "D": lambda: scene_d(emissive_copy=mesh), "E": lambda: scene_e(emissive_mesh=mesh)}[scene]()
     c = dict(c, sources=sources, env="sun", light_share=0.5)
     if name.endswith("_env"):
         return c, mode, lambda c, osc: er.replay_case(c, mode, osc=osc)
