@@ -558,6 +558,76 @@ int prt_sample_light(PrtContext* ctx, uint32_t n, const float* in_dirs, const Pr
                      float* shadow_dirs, float* tmax, uint32_t* light, float* contrib, float* pdf_light, float* pdf_bsdf,
                      float* w_light, float* w_bsdf);
 
+/* ---- Film statistics and adaptive sampling ------------------------------------------------------
+ * Film statistics.  While they are on (prt_set_film_statistics; off by default) the context keeps, beside every local
+ * pixel's {r, g, b, weight} sums, the first two moments {A, Q} of its samples' luminance.  For every sample added to the
+ * film, in sample order, with r, g, b exactly the three numbers that are added to the film (under a lighting mode the
+ * component-wise fp32 sums rad + lrad):
+ *     y = fl(fl(fl(0.2126f r) + fl(0.7152f g)) + fl(0.0722f b));   A = fl(A + y);   Q = fl(Q + fl(y y))
+ * single fp32 operations, never contracted.  Statistics change neither the route of a batch (compact primary rays, the
+ * one-walk-per-pixel list and the path kernel all still run; prt_kernel_instance / prt_shade_instance report what they
+ * reported) nor one bit of the film: the accumulate kernels of their own (k_accumulate_stat) add the same samples in the
+ * same order.  prt_film_clear and prt_set_film clear (resize) the moments with the film.  A pixel outside the image or not
+ * owned by this rank has none.
+ *
+ * The stopping rule, in double, in this order, of a pixel's film weight n and moments A, Q:
+ *     m = A / n;  V = max(0, Q / n - m m);  lhs = V / (n - 1);  t = threshold (m + noise_floor);
+ *     unconverged = n < 2 || lhs > t t
+ * i.e. a pixel is converged once the standard error of its mean luminance is at most `threshold` times (the mean +
+ * noise_floor).  It is written once (csrc/prt_adaptive.h) and compiled for the device and for the host;
+ * prt_adaptive_unconverged is the host's copy.  A pixel outside the image is converged.  An 8x8 tile is ACTIVE while any of
+ * its pixels is unconverged: a wave ballot, no floating-point reduction, so the decision cannot depend on an order.
+ *
+ * prt_render_adaptive adds a different number of samples to every tile.  Pass 0 adds min_spp samples (indices first_sample
+ * .. first_sample + min_spp - 1) to every tile exactly as prt_render would; min_spp = 0 skips it and starts from what the
+ * film holds (that is how a finished frame is refined further: a later first_sample, so that no index is used twice).
+ * Then, with `added` = the samples this call has given the still-active tiles so far (min_spp after pass 0):
+ *     1. select: of the tiles active so far (at first: all local tiles) those that are active by the rule now;
+ *     2. read their number back (one small wait per pass);
+ *     3. stop if there is none, or if added >= max_spp;
+ *     4. add k = min(step_spp, max_spp - added) samples, indices first_sample + added .. + k - 1, to the active tiles only,
+ *        split into batches of samples_in_flight as prt_render splits; added += k.
+ * A tile that drops out never returns (it receives nothing, so the rule keeps saying what it said), hence all tiles of a
+ * pass share one index range, and a pixel that ends with weight n more than it had holds samples first_sample ..
+ * first_sample + n - 1 of this call: since the RNG is keyed by (global pixel, sample, seed) and samples are added in sample
+ * order, it equals that pixel of a uniform n-sample prt_render bit for bit, and its film weight is its sample count.  The
+ * passes over a tile list always take the unfused full-record pipeline (no fused segment, no compact primary rays, no path
+ * kernel; every shade instance, lighting mode, environment, lens and texture binding works under it), which computes the
+ * samples the other routes compute.  The result does not depend on a tunable, on samples_in_flight, on the tree's builder
+ * or on the partition (tiles are decided one by one: a 3-rank partition assembles to the 1-rank film).
+ * rays_per_depth, rays_total and the light statistics count what ran; PrtStats.samples counts whole-film samples only
+ * (pass 0).  Synchronous on return.
+ * PRT_ERR_INVALID, with nothing rendered (checked before the device is, so host-only contexts refuse the same way):
+ * statistics off; threshold or noise_floor negative or NaN; both 0; max_spp < min_spp; step_spp == 0 with max_spp >
+ * min_spp; max_depth out of range. */
+typedef struct PrtAdaptive {
+    uint32_t min_spp, step_spp, max_spp;
+    float threshold, noise_floor;
+} PrtAdaptive;
+typedef struct PrtAdaptiveInfo {
+    uint32_t passes;          /* passes over a tile list that rendered (pass 0 is not one) */
+    uint32_t tiles_local;     /* tiles of this rank */
+    uint32_t tiles_converged; /* tiles the rule stopped (at any count, max_spp included) */
+    uint32_t tiles_capped;    /* tiles still active when max_spp was reached */
+    uint32_t min_tile_spp;    /* fewest / most samples this call gave a tile (0 / 0 for a rank without tiles) */
+    uint32_t max_tile_spp;
+    uint64_t pixel_samples;   /* samples this call added to pixels inside the image */
+} PrtAdaptiveInfo;
+/* on != 0 / 0.  A call that changes the setting clears the film (and waits for the stream); one that does not is a no-op.
+ * Host-only contexts only record the setting.  The setting stays with the context across prt_set_film / prt_set_scene. */
+int prt_set_film_statistics(PrtContext* ctx, int on);
+int prt_get_film_statistics(const PrtContext* ctx); /* 1 / 0 */
+/* The moments in Film layout (H*W floats each, either may be NULL): A into sum_y, Q into sum_y2; 0 for pixels this rank
+ * does not own.  Statistics off: PRT_ERR_INVALID. */
+int prt_film_statistics_read(PrtContext* ctx, float* sum_y, float* sum_y2);
+/* Per pixel (H*W floats), evaluated in double on the host and rounded once: sqrt(V / (n - 1)) / (m + noise_floor) with n,
+ * m, V as in the rule; +inf where n < 2 (pixels this rank does not own included); IEEE 0 / 0 = NaN where a black pixel
+ * meets noise_floor = 0.  noise_floor negative or NaN, or statistics off: PRT_ERR_INVALID. */
+int prt_film_noise_read(PrtContext* ctx, float noise_floor, float* rel_err);
+int prt_adaptive_unconverged(float n, float A, float Q, float threshold, float noise_floor); /* 1 / 0 */
+int prt_render_adaptive(PrtContext* ctx, const PrtAdaptive* cfg, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
+                        PrtAdaptiveInfo* out /* may be NULL */);
+
 /* ---- Film read-back (Film::m_Accum / m_Weights; src/core/film.h:54-60) ------------------------ */
 /* Whole film to host, row-major, top-left origin; only pixels owned by this rank are non-zero. */
 int prt_film_read(PrtContext* ctx, float* rgb_sum, float* weight);
@@ -697,6 +767,12 @@ int prt_group_get_light_stats(PrtGroup* g, PrtLightStats* out);
 int prt_group_set_param(PrtGroup* g, const char* name, int value);
 /* Renderer::ProgressiveRender x spp on every rank's tiles, then the gather + un-tiling on rank 0's device. */
 int prt_group_render(PrtGroup* g, uint32_t spp, uint32_t max_depth, uint32_t seed, uint32_t first_sample);
+/* prt_set_film_statistics on every rank; prt_render_adaptive on every rank's own tiles in parallel (each rank runs its own
+ * loop: tiles are decided one by one), then the gather.  Info: sums over the ranks; passes = the most any rank ran;
+ * min_tile_spp / max_tile_spp over the ranks that own tiles.  prt_group_film_read's weights are the sample-count map. */
+int prt_group_set_film_statistics(PrtGroup* g, int on);
+int prt_group_render_adaptive(PrtGroup* g, const PrtAdaptive* cfg, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
+                              PrtAdaptiveInfo* out);
 /* Whole film (all ranks' tiles) to host / tonemapped to host RGBA8, as prt_film_read / prt_film_display. */
 int prt_group_film_read(PrtGroup* g, float* rgb_sum, float* weight);
 int prt_group_film_display(PrtGroup* g, float exposure, float gamma, uint8_t* rgba8);

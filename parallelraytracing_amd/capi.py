@@ -85,6 +85,18 @@ class PrtLens(C.Structure):
     _fields_ = [("fov_y", C.c_float), ("aperture", C.c_float), ("focus_distance", C.c_float)]
 
 
+class PrtAdaptive(C.Structure):
+    """Settings of prt_render_adaptive (include/prt.h "Film statistics and adaptive sampling")."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
+                ("noise_floor", C.c_float)]
+
+
+class PrtAdaptiveInfo(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("tiles_local", C.c_uint32), ("tiles_converged", C.c_uint32),
+                ("tiles_capped", C.c_uint32), ("min_tile_spp", C.c_uint32), ("max_tile_spp", C.c_uint32),
+                ("pixel_samples", C.c_uint64)]
+
+
 class PrtLighting(C.Structure):
     _fields_ = [("mode", C.c_uint32)]
 
@@ -212,6 +224,14 @@ SIGNATURES = {
     "prt_mesh_set_uvs": (C.c_int, [_vp, _fp]),
     "prt_read_pfm": (C.c_int, [C.c_char_p, C.POINTER(_fp), _u32p, _u32p]),
     "prt_image_free": (None, [_fp]),
+    "prt_set_film_statistics": (C.c_int, [_vp, C.c_int]),
+    "prt_get_film_statistics": (C.c_int, [_vp]),
+    "prt_film_statistics_read": (C.c_int, [_vp, _fp, _fp]),
+    "prt_film_noise_read": (C.c_int, [_vp, C.c_float, _fp]),
+    "prt_adaptive_unconverged": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "prt_render_adaptive": (C.c_int, [_vp, C.POINTER(PrtAdaptive), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PrtAdaptiveInfo)]),
+    "prt_group_set_film_statistics": (C.c_int, [_vp, C.c_int]),
+    "prt_group_render_adaptive": (C.c_int, [_vp, C.POINTER(PrtAdaptive), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PrtAdaptiveInfo)]),
     "prt_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),
     "prt_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
     "prt_light_info": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _fp]),

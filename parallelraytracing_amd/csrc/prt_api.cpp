@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -22,6 +23,7 @@
 #include "../../include/prt.h"
 #include "bvh.h"
 #include "bvh_gpu.h"
+#include "prt_adaptive.h"
 #include "prt_kernels.h"
 #include "prt_scene.h"
 
@@ -74,6 +76,13 @@ struct PrtContext {
     PrtTileMap tm{};
     uint32_t valid_local = 0;  // pixels of this rank inside the image
     float4* d_film_local = nullptr;
+    // film statistics (prt_set_film_statistics, include/prt.h "Film statistics and adaptive sampling"): {A, Q} per local pixel
+    // beside d_film_local, allocated only while they are on; the tile flags and the two tile lists of prt_render_adaptive
+    bool film_stats = false;
+    float2* d_film_stat = nullptr;
+    uint32_t* d_tile_sel = nullptr;  // [0] the active count, then flags / list A / list B of tile_sel_entries tiles each
+    uint32_t tile_sel_entries = 0;
+    uint32_t* h_tile_count = nullptr;  // pinned: the active count of a pass
 
     // ---- path state ----
     uint32_t S = 1;
@@ -529,10 +538,32 @@ f3 h_normalize(f3 v) {
 }
 f3 h_cross(f3 a, f3 b) { return f3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
 
-// One batch of S_cur samples: raygen -> (intersect, shade) x max_depth -> [accumulate]
-int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, uint32_t first_sample, bool accumulate,
-              unsigned long long* trav_stats) {
-    const uint64_t n_paths64 = (uint64_t)S_cur * c->tm.n_pix_local;
+// The whole film as a batch view (PrtBatchView, prt_kernels.h): the context's own tile map, no tile list.
+PrtBatchView whole_film(const PrtContext* c) { return PrtBatchView{c->tm, nullptr}; }
+
+// The accumulate launch of a batch.  With film statistics off the launchers and kernels the context always had; with them on
+// (or for a tile list) the instances of k_accumulate_stat, which add the same samples to the film in the same order.
+void launch_accumulate(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t max_depth, bool accumulate, bool lit,
+                       const float4* pix_end) {
+    if (c->film_stats || view.list)
+        prt_launch_accumulate_stat(c->stream, c->d_rad, lit ? c->lb.lrad : nullptr, c->d_film_local, c->d_film_stat, view.tm, S_cur,
+                                   max_depth, accumulate, c->ray_stats_target, pix_end, view.list);
+    else if (lit)
+        prt_launch_accumulate_lit(c->stream, c->d_rad, c->lb.lrad, c->d_film_local, view.tm, S_cur, max_depth, accumulate,
+                                  c->ray_stats_target);
+    else
+        prt_launch_accumulate(c->stream, c->d_rad, c->d_film_local, view.tm, S_cur, max_depth, accumulate, c->ray_stats_target, pix_end);
+}
+
+// One batch of S_cur samples: raygen -> (intersect, shade) x max_depth -> [accumulate].  `view` says which pixels: the whole
+// film (whole_film), or the tiles of a list (prt_render_adaptive): view.tm then counts the listed tiles only, compact local
+// pixel pl is lane pl & 63 of tile view.list[pl >> 6], and the batch takes the unfused full-record pipeline.
+int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
+              bool accumulate, unsigned long long* trav_stats) {
+    const PrtTileMap& tm = view.tm;
+    const bool listed = view.list != nullptr;
+    if (listed && !c->d_film_stat) return fail(c, PRT_ERR_INVALID, "a tile list needs film statistics");
+    const uint64_t n_paths64 = (uint64_t)S_cur * tm.n_pix_local;
     c->batch_walked = false;
     if (n_paths64 == 0) return PRT_OK;
     if (n_paths64 > 0xFFFFFF00ull) return fail(c, PRT_ERR_INVALID, "too many paths in flight");
@@ -556,7 +587,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // full ray records, no path route
     const bool texon = tex_on(c);
     const DevTex dtex = dev_tex(c);
-    const uint32_t fuse = (!lit && !envon && !texon && c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
+    const uint32_t fuse = (!lit && !envon && !texon && !listed && c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
     // The ray count of a bounce is only known on the device.  With big batches a k_shade grid sized for the worst case is
     // a million blocks, most of which find nothing to do (~0.5 ms per launch, 4 % of a C3 step).  The host therefore
     // reads the counts of bounce d back WHILE the traversal kernel of bounce d runs (the copy is enqueued right after
@@ -591,35 +622,35 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // no path route, which generates its rays itself
     const bool lens_on = c->lens.aperture > 0.0f;
     const DevLens dlens{c->lens.aperture, c->lens.focus_distance};
-    const bool path_route = !lit && !envon && !texon && !lens_on && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
+    const bool path_route = !lit && !envon && !texon && !lens_on && !listed && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
                             !trav_stats && !c->d_shade_div && c->variant == 0 && fuse == 0u && c->sort_rays == 0u &&
                             prt_path_kernel_applies(c->dsc, c->tune);
     c->shade_instance = "";  // (the path route launches no shade kernel)
     if (path_route) {
         HIPCHECK(c, hipMemsetAsync(c->d_work, 0, 256 * sizeof(uint32_t), c->stream));  // the cursors; the error flags in [256] stay for prt_synchronize
-        PrtPathArgs pa{c->cam, c->tm, c->sampling, c->d_rad, first_sample, seed, max_depth, n_paths};
+        PrtPathArgs pa{c->cam, tm, c->sampling, c->d_rad, first_sample, seed, max_depth, n_paths};
         if ((rc = begin_event(c, 1, &ep))) return rc;
         prt_launch_path(c->stream, c->dsc, pa, c->d_work, c->tune);
         if ((rc = end_event(c, &ep))) return rc;
         ++c->stats.intersect_launches;
         if ((rc = begin_event(c, 3, &ep))) return rc;
-        prt_launch_accumulate(c->stream, c->d_rad, c->d_film_local, c->tm, S_cur, max_depth, accumulate, c->ray_stats_target, nullptr);
+        launch_accumulate(c, view, S_cur, max_depth, accumulate, false, nullptr);
         if ((rc = end_event(c, &ep))) return rc;
-        if (accumulate) c->stats.samples += S_cur;
+        if (accumulate) c->stats.samples += S_cur;  // (never a tile list here)
         HIPCHECK(c, hipGetLastError());
         return PRT_OK;
     }
     // front/back counters of every bounce start at zero (the producers add to them atomically)
     HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
     // compact primary rays (PrtPrimary): the default pipeline without jitter / roulette / clamp / fusion
-    const bool compact = !lit && !envon && !texon && !lens_on && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
+    const bool compact = !lit && !envon && !texon && !lens_on && !listed && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
                          c->sampling.jitter == 0u && c->sampling.rr_depth == 0u && !(c->sampling.clamp > 0.0f) && fuse == 0u &&
                          prt_traverse_takes_primary(c->dsc, c->tune);
-    if (compact && c->pix_entries < c->tm.n_pix_local) {
+    if (compact && c->pix_entries < tm.n_pix_local) {
         free_dev(c->d_pix);
         c->pix_entries = 0;
-        HIPCHECK(c, hipMalloc((void**)&c->d_pix, 4 * (size_t)c->tm.n_pix_local * sizeof(float4)));
-        c->pix_entries = c->tm.n_pix_local;
+        HIPCHECK(c, hipMalloc((void**)&c->d_pix, 4 * (size_t)tm.n_pix_local * sizeof(float4)));
+        c->pix_entries = tm.n_pix_local;
         c->pix_records_blank = false;
     }
     const DevLights lt = dev_lights(c);
@@ -634,14 +665,18 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // k_raygen saves the second store and atomic.
     const bool walk = compact && c->primary_walk && S_cur > 1u;
     c->batch_walked = walk;
-    const PrtPrimary primary{(const uint32_t*)c->rb[0].t, c->d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, c->tm.n_pix_local,
-                             1.0f / (float)c->tm.n_pix_local, first_sample, seed, walk ? 1u : 0u};
+    const PrtPrimary primary{(const uint32_t*)c->rb[0].t, c->d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, tm.n_pix_local,
+                             1.0f / (float)tm.n_pix_local, first_sample, seed, walk ? 1u : 0u};
     PrtPrimary primary_list = primary;  // what the traversal sees: list slots in place of path slots
     if (walk) primary_list.pid = (const uint32_t*)c->rb[0].hd2;
     if ((rc = begin_event(c, 0, &ep))) return rc;
-    prt_launch_raygen(c->stream, c->dsc, c->cam, c->tm, n_paths, first_sample, seed, c->rb[0], c->d_rad, c->d_counts,
-                      c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr, envp, walk,
-                      lens_on ? &dlens : nullptr);
+    if (listed)
+        prt_launch_raygen_list(c->stream, c->dsc, c->cam, tm, view.list, n_paths, first_sample, seed, c->rb[0], c->d_rad, c->d_counts,
+                               c->d_work, max_depth, c->sampling, envp, lens_on ? &dlens : nullptr);
+    else
+        prt_launch_raygen(c->stream, c->dsc, c->cam, tm, n_paths, first_sample, seed, c->rb[0], c->d_rad, c->d_counts,
+                          c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr, envp, walk,
+                          lens_on ? &dlens : nullptr);
     if ((rc = end_event(c, &ep))) return rc;
     if (exact) HIPCHECK(c, read_back(0));
     for (uint32_t d = 0; d < max_depth; ++d) {
@@ -680,7 +715,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                     }
                 }
                 if (walk && d == 0)
-                    prt_launch_traverse(c->stream, c->dsc, in, c->d_counts + PRT_CNT_LIST, c->d_work, c->d_spill, c->tm.n_pix_local,
+                    prt_launch_traverse(c->stream, c->dsc, in, c->d_counts + PRT_CNT_LIST, c->d_work, c->d_spill, tm.n_pix_local,
                                         c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune, trav_stats, &primary_list);
                 else
                     prt_launch_traverse(c->stream, c->dsc, in, front_count, c->d_work, c->d_spill, n_paths, c->hs.bvh.max_depth,
@@ -698,7 +733,7 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
                     if ((rc = end_event(c, &ep))) return rc;
                     c->pix_records_blank = false;
                 } else if (!c->pix_records_blank) {  // "no record" for every pixel (hit id 0xFFFFFFFF never equals a hit k_shade looks up); stays so until k_primary_hit runs again
-                    HIPCHECK(c, hipMemsetAsync(c->d_pix + 2 * (size_t)c->tm.n_pix_local, 0xFF, 2 * (size_t)c->tm.n_pix_local * sizeof(float4), c->stream));
+                    HIPCHECK(c, hipMemsetAsync(c->d_pix + 2 * (size_t)tm.n_pix_local, 0xFF, 2 * (size_t)tm.n_pix_local * sizeof(float4), c->stream));
                     c->pix_records_blank = true;
                 }
             }
@@ -749,14 +784,9 @@ int run_batch(PrtContext* c, uint32_t S_cur, uint32_t max_depth, uint32_t seed, 
     // film += the batch's samples (unless this is a measurement run) and per-depth ray counts from the paths' last
     // segment indices
     if ((rc = begin_event(c, 3, &ep))) return rc;
-    if (lit)
-        prt_launch_accumulate_lit(c->stream, c->d_rad, c->lb.lrad, c->d_film_local, c->tm, S_cur, max_depth, accumulate,
-                                  c->ray_stats_target);
-    else
-        prt_launch_accumulate(c->stream, c->d_rad, c->d_film_local, c->tm, S_cur, max_depth, accumulate, c->ray_stats_target,
-                              compact ? c->d_pix + c->tm.n_pix_local : nullptr);
+    launch_accumulate(c, view, S_cur, max_depth, accumulate, lit, compact ? c->d_pix + tm.n_pix_local : nullptr);
     if ((rc = end_event(c, &ep))) return rc;
-    if (accumulate) c->stats.samples += S_cur;
+    if (accumulate && !listed) c->stats.samples += S_cur;  // (whole-film samples only)
     HIPCHECK(c, hipGetLastError());
     return PRT_OK;
 }
@@ -971,6 +1001,37 @@ int check_ready(PrtContext* c) {
     return PRT_OK;
 }
 
+// This rank's film_local (float4 per local pixel) and moments (float2) on the host, for the two read-back calls below.
+int read_local_moments(PrtContext* c, std::vector<float>* film, std::vector<float>* stat) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_film) return fail(c, PRT_ERR_INVALID, "prt_set_film has not been called");
+    if (!c->film_stats || !c->d_film_stat) return fail(c, PRT_ERR_INVALID, "film statistics are off (prt_set_film_statistics)");
+    const size_t n = c->tm.n_pix_local;
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    if (film) {
+        film->assign(4 * n, 0.0f);
+        if (n) HIPCHECK(c, hipMemcpy(film->data(), c->d_film_local, n * sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    stat->assign(2 * n, 0.0f);
+    if (n) HIPCHECK(c, hipMemcpy(stat->data(), c->d_film_stat, n * sizeof(float2), hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+// fn(local pixel, film pixel) for every pixel of this rank's tiles that lies in the image (the device's tile_pixel)
+template <class F>
+void for_each_local_pixel(const PrtTileMap& tm, F fn) {
+    for (uint32_t lt = 0; lt < tm.n_tiles_local; ++lt) {
+        const uint32_t gt = lt * tm.world + tm.rank;
+        const uint32_t tx = gt % tm.tiles_x, ty = gt / tm.tiles_x;
+        for (uint32_t lane = 0; lane < 64u; ++lane) {
+            const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+            if (x < tm.W && y < tm.H) fn((size_t)lt * 64u + lane, (size_t)y * tm.W + x);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1007,6 +1068,9 @@ void prt_destroy(PrtContext* c) {
         free_light_state(c);
         free_dev(c->d_light_stats);
         free_dev(c->d_film_local);
+        free_dev(c->d_film_stat);
+        free_dev(c->d_tile_sel);
+        if (c->h_tile_count) (void)hipHostFree(c->h_tile_count);
         free_dev(c->d_counts);
         free_dev(c->d_ray_stats);
         if (c->h_flag) (void)hipHostFree(c->h_flag);
@@ -1458,7 +1522,9 @@ int prt_set_film(PrtContext* c, uint32_t width, uint32_t height, uint32_t rank, 
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     free_dev(c->d_film_local);
+    free_dev(c->d_film_stat);
     HIPCHECK(c, hipMalloc((void**)&c->d_film_local, std::max<size_t>((size_t)tm.stride, 64) * sizeof(float4)));
+    if (c->film_stats) HIPCHECK(c, hipMalloc((void**)&c->d_film_stat, std::max<size_t>((size_t)tm.stride, 64) * sizeof(float2)));
     int rc = ensure_counters(c);
     if (rc) return rc;
     return prt_film_clear(c);
@@ -1469,9 +1535,27 @@ int prt_film_clear(PrtContext* c) {
     if (rc) return rc;
     if (!c->has_film) return fail(c, PRT_ERR_INVALID, "prt_set_film has not been called");
     HIPCHECK(c, hipMemsetAsync(c->d_film_local, 0, std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float4), c->stream));
+    if (c->d_film_stat)
+        HIPCHECK(c, hipMemsetAsync(c->d_film_stat, 0, std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float2), c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
+
+int prt_set_film_statistics(PrtContext* c, int on) {
+    if (!c) return PRT_ERR_INVALID;
+    const bool want = on != 0;
+    if (want == c->film_stats) return PRT_OK;
+    c->film_stats = want;
+    if (!c->has_device) return PRT_OK;  // host-only: the setting is all there is
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    free_dev(c->d_film_stat);
+    if (!c->has_film) return PRT_OK;  // (prt_set_film allocates the moments with the film)
+    if (want) HIPCHECK(c, hipMalloc((void**)&c->d_film_stat, std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float2)));
+    return prt_film_clear(c);
+}
+
+int prt_get_film_statistics(const PrtContext* c) { return (c && c->film_stats) ? 1 : 0; }
 
 int prt_set_sampling(PrtContext* c, const PrtSampling* sp) {
     if (!c) return PRT_ERR_INVALID;
@@ -1694,7 +1778,7 @@ int prt_render_async(PrtContext* c, uint32_t spp, uint32_t max_depth, uint32_t s
     uint32_t done = 0;
     while (done < spp) {
         const uint32_t S_cur = std::min(c->S, spp - done);
-        rc = run_batch(c, S_cur, max_depth, seed, first_sample + done, true, nullptr);
+        rc = run_batch(c, whole_film(c), S_cur, max_depth, seed, first_sample + done, true, nullptr);
         if (rc) return rc;
         done += S_cur;
     }
@@ -1797,6 +1881,125 @@ int prt_film_read(PrtContext* c, float* rgb_sum, float* weight) {
     if (weight) HIPCHECK(c, hipMemcpyAsync(weight, d_w, npix * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
+}
+
+int prt_film_statistics_read(PrtContext* c, float* sum_y, float* sum_y2) {
+    std::vector<float> stat;
+    int rc = read_local_moments(c, nullptr, &stat);
+    if (rc) return rc;
+    const size_t npix = (size_t)c->tm.W * c->tm.H;
+    if (sum_y) std::fill(sum_y, sum_y + npix, 0.0f);
+    if (sum_y2) std::fill(sum_y2, sum_y2 + npix, 0.0f);
+    for_each_local_pixel(c->tm, [&](size_t pl, size_t p) {
+        if (sum_y) sum_y[p] = stat[2 * pl];
+        if (sum_y2) sum_y2[p] = stat[2 * pl + 1];
+    });
+    return PRT_OK;
+}
+
+int prt_film_noise_read(PrtContext* c, float noise_floor, float* rel_err) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!(noise_floor >= 0.0f) || !rel_err) return fail(c, PRT_ERR_INVALID, "bad arguments to prt_film_noise_read");
+    std::vector<float> film, stat;
+    int rc = read_local_moments(c, &film, &stat);
+    if (rc) return rc;
+    const size_t npix = (size_t)c->tm.W * c->tm.H;
+    std::fill(rel_err, rel_err + npix, std::numeric_limits<float>::infinity());
+    for_each_local_pixel(c->tm, [&](size_t pl, size_t p) {
+        const float n = film[4 * pl + 3];
+        if (n < 2.0f) return;
+        const double dn = (double)n, m = (double)stat[2 * pl] / dn;
+        const double d = (double)stat[2 * pl + 1] / dn - m * m;
+        const double V = d > 0.0 ? d : 0.0;
+        rel_err[p] = (float)(std::sqrt(V / (dn - 1.0)) / (m + (double)noise_floor));
+    });
+    return PRT_OK;
+}
+
+int prt_adaptive_unconverged(float n, float A, float Q, float threshold, float noise_floor) {
+    return prt_adaptive_rule(n, A, Q, threshold, noise_floor) ? 1 : 0;
+}
+
+int prt_render_adaptive(PrtContext* c, const PrtAdaptive* cfg, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
+                        PrtAdaptiveInfo* out) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!cfg) return fail(c, PRT_ERR_INVALID, "prt_render_adaptive: null settings");
+    if (!c->film_stats) return fail(c, PRT_ERR_INVALID, "prt_render_adaptive needs film statistics (prt_set_film_statistics)");
+    if (!(cfg->threshold >= 0.0f) || !(cfg->noise_floor >= 0.0f))
+        return fail(c, PRT_ERR_INVALID, "threshold and noise_floor must be >= 0 (and not NaN)");
+    if (cfg->threshold == 0.0f && cfg->noise_floor == 0.0f) return fail(c, PRT_ERR_INVALID, "threshold and noise_floor are both 0");
+    if (cfg->max_spp < cfg->min_spp) return fail(c, PRT_ERR_INVALID, "max_spp < min_spp");
+    if (cfg->step_spp == 0u && cfg->max_spp > cfg->min_spp) return fail(c, PRT_ERR_INVALID, "step_spp is 0 with max_spp > min_spp");
+    if (max_depth == 0 || max_depth > PRT_MAX_DEPTH) return fail(c, PRT_ERR_INVALID, "max_depth must be 1..%d", PRT_MAX_DEPTH);
+    int rc = check_ready(c);
+    if (rc) return rc;
+    HIPCHECK(c, hipSetDevice(c->device));
+    PrtAdaptiveInfo info{};
+    const uint32_t n_tiles = c->tm.n_tiles_local;
+    info.tiles_local = n_tiles;
+    if (out) *out = info;
+    // count words, flags and two lists of n_tiles entries each; the pinned words the count is read into
+    if (c->tile_sel_entries < n_tiles || !c->d_tile_sel) {
+        free_dev(c->d_tile_sel);
+        c->tile_sel_entries = 0;
+        HIPCHECK(c, hipMalloc((void**)&c->d_tile_sel, (16 + 3 * (size_t)std::max(n_tiles, 1u)) * sizeof(uint32_t)));
+        c->tile_sel_entries = std::max(n_tiles, 1u);
+    }
+    if (!c->h_tile_count) HIPCHECK(c, hipHostMalloc((void**)&c->h_tile_count, 64, hipHostMallocDefault));
+    uint32_t* d_count = c->d_tile_sel;
+    uint32_t* d_flags = c->d_tile_sel + 16;
+    uint32_t* d_list[2] = {d_flags + c->tile_sel_entries, d_flags + 2 * (size_t)c->tile_sel_entries};
+    uint32_t added = 0;
+    if (cfg->min_spp) {  // pass 0: every tile, the ordinary route
+        if ((rc = prt_render_async(c, cfg->min_spp, max_depth, seed, first_sample))) return rc;
+        added = cfg->min_spp;
+        info.pixel_samples = (uint64_t)cfg->min_spp * c->valid_local;
+    }
+    const uint32_t* prev = nullptr;
+    uint32_t n_prev = n_tiles, cur = 0;
+    bool any = false;
+    auto stopped_at = [&](uint32_t spp) {
+        info.min_tile_spp = any ? std::min(info.min_tile_spp, spp) : spp;
+        info.max_tile_spp = any ? std::max(info.max_tile_spp, spp) : spp;
+        any = true;
+    };
+    while (n_prev) {
+        // which of the tiles that were active until now still are; ONE small wait per pass for their number
+        prt_launch_tile_select(c->stream, c->d_film_local, c->d_film_stat, c->tm, prev, n_prev, cfg->threshold, cfg->noise_floor,
+                               d_flags, d_list[cur], d_count);
+        HIPCHECK(c, hipGetLastError());
+        HIPCHECK(c, hipMemcpyAsync(c->h_tile_count, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        const uint32_t n_act = c->h_tile_count[0], pix_act = c->h_tile_count[1];
+        if (n_act > n_prev) return fail(c, PRT_ERR_HIP, "tile selection returned %u of %u tiles", n_act, n_prev);
+        if (n_act < n_prev) {
+            info.tiles_converged += n_prev - n_act;
+            stopped_at(added);
+        }
+        if (n_act == 0u) break;
+        if (added >= cfg->max_spp) {
+            info.tiles_capped = n_act;
+            stopped_at(added);
+            break;
+        }
+        const uint32_t k = std::min(cfg->step_spp, cfg->max_spp - added);
+        PrtBatchView view{c->tm, d_list[cur]};
+        view.tm.n_tiles_local = n_act;
+        view.tm.n_pix_local = n_act * 64u;
+        for (uint32_t done = 0; done < k;) {  // split by samples_in_flight as prt_render splits
+            const uint32_t S_cur = std::min(c->S, k - done);
+            if ((rc = run_batch(c, view, S_cur, max_depth, seed, first_sample + added + done, true, nullptr))) return rc;
+            done += S_cur;
+        }
+        added += k;
+        info.pixel_samples += (uint64_t)k * pix_act;
+        ++info.passes;
+        prev = d_list[cur];
+        n_prev = n_act;
+        cur ^= 1u;
+    }
+    if (out) *out = info;
+    return prt_synchronize(c);
 }
 
 int prt_film_display(PrtContext* c, float exposure, float gamma, uint8_t* rgba8) {
@@ -2156,7 +2359,7 @@ int prt_measure_traversal(PrtContext* c, uint32_t max_depth, uint32_t seed, uint
     c->ray_stats_target = c->d_ray_stats + kRayStatWords;
     // measure_spp (prt_set_param) samples in one batch: the counters scale, the per-phase cycle split becomes that of a
     // loaded kernel
-    rc = run_batch(c, (uint32_t)std::max(1, c->measure_spp), max_depth, seed, sample, false, c->d_trav_stats);
+    rc = run_batch(c, whole_film(c), (uint32_t)std::max(1, c->measure_spp), max_depth, seed, sample, false, c->d_trav_stats);
     c->ray_stats_target = c->d_ray_stats;
     c->timing = timing;
     c->stats.intersect_launches = launches;
@@ -2216,7 +2419,7 @@ int prt_measure_shade_divergence(PrtContext* c, uint32_t max_depth, uint32_t see
         const bool timing = c->timing;
         const uint64_t launches = c->stats.intersect_launches;
         c->timing = false;
-        rc = run_batch(c, (uint32_t)std::max(1, c->measure_spp), max_depth, seed, sample, false, nullptr);
+        rc = run_batch(c, whole_film(c), (uint32_t)std::max(1, c->measure_spp), max_depth, seed, sample, false, nullptr);
         c->timing = timing;
         c->stats.intersect_launches = launches;
         c->d_shade_div = nullptr;

@@ -370,6 +370,38 @@ int prt_group_render(PrtGroup* g, uint32_t spp, uint32_t max_depth, uint32_t see
     return gather_and_resolve(g);
 }
 
+int prt_group_set_film_statistics(PrtGroup* g, int on) {
+    if (!g) return PRT_ERR_INVALID;
+    g->film_current = false;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_film_statistics(g->ctx[r], on); }, false);
+}
+
+int prt_group_render_adaptive(PrtGroup* g, const PrtAdaptive* cfg, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
+                              PrtAdaptiveInfo* out) {
+    if (!g || g->ctx.empty()) return PRT_ERR_INVALID;
+    g->film_current = false;
+    std::vector<PrtAdaptiveInfo> infos(g->ctx.size());
+    int rc = for_each_rank(g, [&](uint32_t r) { return prt_render_adaptive(g->ctx[r], cfg, max_depth, seed, first_sample, &infos[r]); });
+    if (rc) return rc;
+    if (out) {
+        PrtAdaptiveInfo t{};
+        bool any = false;
+        for (const PrtAdaptiveInfo& i : infos) {
+            t.passes = std::max(t.passes, i.passes);
+            t.tiles_local += i.tiles_local;
+            t.tiles_converged += i.tiles_converged;
+            t.tiles_capped += i.tiles_capped;
+            t.pixel_samples += i.pixel_samples;
+            if (!i.tiles_local) continue;
+            t.min_tile_spp = any ? std::min(t.min_tile_spp, i.min_tile_spp) : i.min_tile_spp;
+            t.max_tile_spp = any ? std::max(t.max_tile_spp, i.max_tile_spp) : i.max_tile_spp;
+            any = true;
+        }
+        *out = t;
+    }
+    return gather_and_resolve(g);
+}
+
 int prt_group_film_read(PrtGroup* g, float* rgb_sum, float* weight) {
     if (!g || g->ctx.empty()) return PRT_ERR_INVALID;
     if (!g->film_current) {

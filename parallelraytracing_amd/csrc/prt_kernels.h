@@ -69,6 +69,15 @@ struct PrtTileMap {
     uint32_t stride;         // ceil(tiles_total / world) * 64: per-rank payload (float4 units), equal on all ranks
 };
 
+// What a batch renders (run_batch, prt_api.cpp).  list = null: the whole film, tm = the context's tile map.  list != null (a
+// pass of prt_render_adaptive): the ascending local tile indices that are still active; tm is the context's tile map with
+// n_tiles_local = the number of listed tiles and n_pix_local = 64 x that, so compact local pixel pl (what path ids and ray
+// grids are made of) is lane pl & 63 of local tile list[pl >> 6], film pixel (list[pl >> 6] << 6) + (pl & 63) of film_local.
+struct PrtBatchView {
+    PrtTileMap tm;
+    const uint32_t* list;
+};
+
 // Tunables of k_traverse_persistent (prt_set_param).
 struct PrtTravTuning {
     uint32_t grid_blocks;  // resident 256-thread blocks of the persistent grid
@@ -317,3 +326,20 @@ const char* prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const D
 void prt_launch_texture_eval(hipStream_t st, const DevTex& tex, uint32_t n, const uint32_t* texture, const float* uv, float* rgb);
 // prt_hit_uv: after the closest-hit pipeline on `in`: uv (2 floats) and albedo (3 floats) of every ray's hit; either may be null
 void prt_launch_hit_uv(hipStream_t st, const DevScene& sc, const DevTex& tex, uint32_t n, const PrtRayBuf& in, float* uv, float* albedo);
+
+// Film statistics and adaptive sampling (include/prt.h "Film statistics and adaptive sampling"): kernels of their own; the
+// launchers above and their kernels stay as they are.
+// k_accumulate_stat<LIT, LIST>: k_accumulate (lrad = null, pix_end optional) or k_accumulate_lit (lrad given) that also adds
+// every sample's luminance and its square to stat[pixel] = {A, Q}; with `list` (PrtBatchView) pixels are scattered through it.
+void prt_launch_accumulate_stat(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, float2* stat,
+                                const PrtTileMap& tm, uint32_t S, uint32_t max_depth, bool update_film,
+                                unsigned long long* ray_stats, const float4* pix_end, const uint32_t* list);
+// k_raygen_list<JITTER, ABVH, ENV, LENS>: full ray records for the tiles of `list`, sampling options compiled in
+void prt_launch_raygen_list(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, const uint32_t* list,
+                            uint32_t n_paths, uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad,
+                            uint32_t* counts, uint32_t* work, uint32_t max_depth, const PrtSampling& sp, const DevEnv* env,
+                            const DevLens* lens);
+// k_tile_select + k_tile_compact: of the n_in tiles of `prev` (null: local tiles 0 .. n_in - 1) those with an unconverged pixel
+// (prt_adaptive.h), in the same (ascending) order, into `out`; their number into *count.  flags: n_in words of scratch.
+void prt_launch_tile_select(hipStream_t st, const float4* film_local, const float2* stat, const PrtTileMap& tm, const uint32_t* prev,
+                            uint32_t n_in, float threshold, float noise_floor, uint32_t* flags, uint32_t* out, uint32_t* count);

@@ -14,6 +14,7 @@
 //  * wave64 ballot compaction into the next bounce's buffer: one atomic per 1024-thread block.
 #include "prt_kernels.h"
 
+#include "prt_adaptive.h"
 #include "prt_device.h"
 
 #define HIT_MISS 0xFFFFFFFFu
@@ -330,12 +331,14 @@ PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr,
 // LENS (lens: DevLens; PrtLens with aperture > 0): every sample has a primary ray of its own, from its own point of the lens,
 // so LENS takes the per-sample branch below whether JITTER is on or not (off: the pixel centre) and stores each ray's own
 // origin.  The other instances pass false and compile to the code they had before there was a lens.
-template <bool JITTER, bool SAMPLING, bool ABVH, bool COMPACT, bool ENV, bool LENS = false>
+// LIST (list: PrtBatchView, prt_kernels.h; k_raygen_list only): tm counts the listed tiles, pl is a compact local pixel, and
+// only the pixel's place in the image comes from its own tile list[pl >> 6]; slots and path ids are made of compact pixels.
+template <bool JITTER, bool SAMPLING, bool ABVH, bool COMPACT, bool ENV, bool LENS = false, bool LIST = false>
 PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, uint32_t first_sample, uint32_t seed,
                          float4* __restrict__ ro, float4* __restrict__ rd, float4* __restrict__ rt, uint32_t* __restrict__ hit,
                          float* __restrict__ hd2, float4* __restrict__ rad, uint32_t* __restrict__ counts,
                          uint32_t* __restrict__ work, uint32_t max_depth, PrtSampling sp_arg, float4* __restrict__ pix,
-                         const DevEnv* env, const DevLens* lens = nullptr) {
+                         const DevEnv* env, const DevLens* lens = nullptr, const uint32_t* __restrict__ list = nullptr) {
     const PrtSampling sp = SAMPLING ? sp_arg : PrtSampling{0u, 0u, 0.0f};
     const uint32_t pl = blockIdx.x * (uint32_t)PRODUCER_BLOCK + threadIdx.x;
     if (blockIdx.y == 0 && pl < 8u) work[32u * pl] = 0u;  // chunk cursors of the traversal kernel that follows
@@ -347,7 +350,7 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
     uint32_t id00 = HIT_MISS, pixel = 0, px = 0, py = 0;
     float d2_00 = 3.402823466e+38f;
     if (in_range) {
-        valid = tile_pixel(tm, pl, px, py);
+        valid = tile_pixel(tm, LIST ? (list[pl >> 6] << 6) | (pl & 63u) : pl, px, py);
         if (valid) {
             pixel = py * tm.W + px;
             if (!JITTER && !LENS) {  // pixel centre, the same ray for every sample (cpu/renderer.cpp:45)
@@ -595,6 +598,22 @@ __global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen_lens_env(DevScene sc,
                                                                      uint32_t max_depth, PrtSampling sp_arg) {
     raygen_step<JITTER, true, ABVH, false, true, true>(sc, cam, tm, S, first_sample, seed, ro, rd, rt, hit, hd2, rad, counts, work,
                                                        max_depth, sp_arg, nullptr, &env, &lens);
+}
+
+// k_raygen for the tiles of a list (a pass of prt_render_adaptive; PrtBatchView): one full ray record per sample, sampling
+// options compiled in, every combination of jitter, primitive BVH, environment image and thin lens in one kernel name
+template <bool JITTER, bool ABVH, bool ENV, bool LENS>
+__global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen_list(DevScene sc, DevEnv env, DevLens lens, DevCamera cam, PrtTileMap tm,
+                                                                 const uint32_t* __restrict__ list, uint32_t S,
+                                                                 uint32_t first_sample, uint32_t seed,
+                                                                 float4* __restrict__ ro, float4* __restrict__ rd,
+                                                                 float4* __restrict__ rt, uint32_t* __restrict__ hit,
+                                                                 float* __restrict__ hd2, float4* __restrict__ rad,
+                                                                 uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                                 uint32_t max_depth, PrtSampling sp_arg) {
+    raygen_step<JITTER, true, ABVH, false, ENV, LENS, true>(sc, cam, tm, S, first_sample, seed, ro, rd, rt, hit, hd2, rad, counts, work,
+                                                            max_depth, sp_arg, nullptr, ENV ? &env : nullptr, LENS ? &lens : nullptr,
+                                                            list);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2880,6 +2899,143 @@ __global__ void __launch_bounds__(256) k_accumulate_lit(const float4* __restrict
     }
 }
 
+// Film statistics (prt_set_film_statistics): k_accumulate / k_accumulate_lit (LIT: a sample is rad + lrad) that also keep the
+// second moments of the samples' luminance, stat[pixel] = {A, Q}: per sample, in sample order, y = (0.2126 r + 0.7152 g) +
+// 0.0722 b of exactly the r, g, b added to the film, A += y, Q += y y (single fp32 operations, never contracted).  The film
+// gets the same additions in the same order as without statistics.  (Kernels of their own: the two above keep their code.)
+// LIST (a pass of prt_render_adaptive; PrtBatchView): tm counts the listed tiles; rad / lrad are indexed by compact local
+// pixels, film_local and stat by (list[pl >> 6] << 6) + lane.  No pix_end then, and none with LIT.
+template <bool LIT, bool LIST>
+__global__ void __launch_bounds__(256) k_accumulate_stat(const float4* __restrict__ rad, const float4* __restrict__ lrad,
+                                                         float4* __restrict__ film_local, float2* __restrict__ stat, PrtTileMap tm,
+                                                         uint32_t S, uint32_t max_depth, int update_film,
+                                                         unsigned long long* __restrict__ ray_stats,
+                                                         const float4* __restrict__ pix_end, const uint32_t* __restrict__ list) {
+    __shared__ uint32_t s_ends[PRT_MAX_DEPTH];  // per-depth ray counts: see k_accumulate
+    if (threadIdx.x < PRT_MAX_DEPTH) s_ends[threadIdx.x] = 0u;
+    __syncthreads();
+    for (uint32_t pl0 = blockIdx.x * 256u; pl0 < tm.n_pix_local; pl0 += gridDim.x * 256u) {  // block-uniform trip count
+    const uint32_t pl = pl0 + threadIdx.x;
+    const bool in_range = pl < tm.n_pix_local;
+    uint32_t fl = pl;  // the pixel's place in film_local
+    if (LIST && in_range) fl = (list[pl >> 6] << 6) | (pl & 63u);
+    uint32_t x, y;
+    const bool valid = in_range && tile_pixel(tm, fl, x, y);
+    float4 f = valid ? film_local[fl] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float2 m2 = valid ? stat[fl] : make_float2(0.f, 0.f);
+    float4 E = make_float4(0.f, 0.f, 0.f, __uint_as_float((LIT || LIST) ? 0xFFFFFFFFu : 0xFFFFFFFEu));
+    if (!LIT && !LIST && valid && pix_end) E = pix_end[pl];
+    const bool ended = !LIT && !LIST && __float_as_uint(E.w) != 0xFFFFFFFEu;
+    const float weight = 1.0f;
+    const uint32_t lane = lane_id();
+    for (uint32_t s0 = 0; s0 < S; s0 += 8u) {  // block-uniform trip counts; eight loads in flight (k_accumulate)
+        float4 r[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j)
+            r[j] = (valid && !ended && s0 + j < S) ? ld_stream(&rad[(size_t)(s0 + j) * tm.n_pix_local + pl]) : E;
+        if (LIT) {
+#pragma unroll
+            for (uint32_t j = 0; j < 8u; ++j) {
+                if (valid && s0 + j < S) {
+                    const float4 l = ld_stream(&lrad[(size_t)(s0 + j) * tm.n_pix_local + pl]);
+                    r[j].x = r[j].x + l.x;
+                    r[j].y = r[j].y + l.y;
+                    r[j].z = r[j].z + l.z;
+                }
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j) {
+            if (s0 + j >= S) break;
+            uint32_t e = 0xFFFFFFFFu;
+            if (valid) {
+                f.x += r[j].x * weight;
+                f.y += r[j].y * weight;
+                f.z += r[j].z * weight;
+                f.w += weight;
+                const float lum = __fadd_rn(__fadd_rn(__fmul_rn(0.2126f, r[j].x), __fmul_rn(0.7152f, r[j].y)), __fmul_rn(0.0722f, r[j].z));
+                m2.x = __fadd_rn(m2.x, lum);
+                m2.y = __fadd_rn(m2.y, __fmul_rn(lum, lum));
+                e = __float_as_uint(r[j].w);
+            }
+            for (uint32_t dd = 0; dd < max_depth; ++dd) {
+                const unsigned long long mk = __ballot(e == dd);
+                if (mk != 0ull && lane == 0) atomicAdd(&s_ends[dd], (uint32_t)__popcll(mk));
+            }
+        }
+    }
+    if (valid && update_film) {
+        film_local[fl] = f;
+        stat[fl] = m2;
+    }
+    }
+    __syncthreads();
+    if (threadIdx.x < max_depth) {
+        unsigned long long n = 0;
+        for (uint32_t e = threadIdx.x; e < max_depth; ++e) n += s_ends[e];
+        if (n) atomicAdd(&ray_stats[(blockIdx.x & (PRT_RAY_STAT_SLOTS - 1u)) * PRT_MAX_DEPTH + threadIdx.x], n);
+    }
+}
+
+// Tile selection of prt_render_adaptive: one wave per tile of the previous list (prev = null: local tile w itself), one pixel
+// per lane.  A pixel outside the image is converged; the others by prt_adaptive_rule on their film weight and moments.  The tile
+// stays active while any lane is unconverged: a ballot, so the decision involves no floating-point reduction.
+__global__ void __launch_bounds__(256) k_tile_select(const float4* __restrict__ film_local, const float2* __restrict__ stat,
+                                                     PrtTileMap tm, const uint32_t* __restrict__ prev, uint32_t n_in, float threshold,
+                                                     float noise_floor, uint32_t* __restrict__ flags) {
+    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);  // wave-uniform
+    if (w >= n_in) return;
+    const uint32_t t = prev ? prev[w] : w;
+    const uint32_t pl = (t << 6) | lane_id();
+    uint32_t x, y;
+    bool unconverged = false;
+    const bool inside = tile_pixel(tm, pl, x, y);
+    if (inside) {
+        const float2 m2 = stat[pl];
+        unconverged = prt_adaptive_rule(film_local[pl].w, m2.x, m2.y, threshold, noise_floor);
+    }
+    const unsigned long long mk = __ballot(unconverged), in_image = __ballot(inside);
+    // the flag of an active tile is its number of pixels inside the image (never 0: an unconverged pixel is one of them)
+    if (lane_id() == 0u) flags[w] = mk != 0ull ? (uint32_t)__popcll(in_image) : 0u;
+}
+
+// Ordered compaction of k_tile_select's flags: out = the flagged entries of prev (null: their own indices) in their order,
+// count[0] = how many, count[1] = the sum of their flags (the pixels of the active tiles inside the image).  ONE block walks the flags 1024 at a time (a 4K film has 130 k tiles: 127 trips), so the order needs no
+// second pass: ranks within a trip from wave ballots and a scan of the 16 wave totals, the running total carried in a register.
+__global__ void __launch_bounds__(1024) k_tile_compact(const uint32_t* __restrict__ flags, const uint32_t* __restrict__ prev,
+                                                       uint32_t n_in, uint32_t* __restrict__ out, uint32_t* __restrict__ count) {
+    __shared__ uint32_t s_wave[16];
+    __shared__ uint32_t s_pixels;
+    if (threadIdx.x == 0u) s_pixels = 0u;
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+    uint32_t run = 0u, pixels = 0u;
+    for (uint32_t i0 = 0; i0 < n_in; i0 += 1024u) {  // block-uniform trip count
+        const uint32_t i = i0 + threadIdx.x;
+        const uint32_t flag = i < n_in ? flags[i] : 0u;
+        const bool on = flag != 0u;
+        pixels += flag;
+        const unsigned long long mk = __ballot(on);
+        if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(mk);
+        __syncthreads();
+        uint32_t before = 0u, total = 0u;
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const uint32_t nk = s_wave[k];
+            if (k < wave) before += nk;
+            total += nk;
+        }
+        if (on) out[run + before + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull))] = prev ? prev[i] : i;
+        run += total;
+        __syncthreads();  // s_wave is rewritten by the next trip
+    }
+    __syncthreads();
+    if (pixels) atomicAdd(&s_pixels, pixels);  // (integers: the order does not matter)
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        count[0] = run;
+        count[1] = s_pixels;
+    }
+}
+
 
 // Un-tile `world` gathered rank payloads (each `stride` float4) into the Film layout
 // (m_Accum[3*(y*W+x)+c], m_Weights[y*W+x]; src/core/film.h:54-60).
@@ -4414,4 +4570,59 @@ void prt_launch_texture_eval(hipStream_t st, const DevTex& tex, uint32_t n, cons
 
 void prt_launch_hit_uv(hipStream_t st, const DevScene& sc, const DevTex& tex, uint32_t n, const PrtRayBuf& in, float* uv, float* albedo) {
     hipLaunchKernelGGL(k_hit_uv, dim3(blocks_for(n)), dim3(256), 0, st, sc, tex, n, in.o, in.d, in.hit, uv, albedo);
+}
+
+
+void prt_launch_accumulate_stat(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, float2* stat,
+                                const PrtTileMap& tm, uint32_t S, uint32_t max_depth, bool update_film,
+                                unsigned long long* ray_stats, const float4* pix_end, const uint32_t* list) {
+    const uint32_t nb = blocks_for(tm.n_pix_local ? tm.n_pix_local : 1);
+    const dim3 grid(nb < 8192u ? nb : 8192u);
+#define PRT_ACC_STAT(LI, LS)                                                                                                  \
+    hipLaunchKernelGGL((k_accumulate_stat<LI, LS>), grid, dim3(256), 0, st, rad, lrad, film_local, stat, tm, S, max_depth, \
+                       update_film ? 1 : 0, ray_stats, pix_end, list)
+    if (list) {
+        if (lrad) PRT_ACC_STAT(true, true); else PRT_ACC_STAT(false, true);
+    } else {
+        if (lrad) PRT_ACC_STAT(true, false); else PRT_ACC_STAT(false, false);
+    }
+#undef PRT_ACC_STAT
+}
+
+void prt_launch_raygen_list(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, const uint32_t* list,
+                            uint32_t n_paths, uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad,
+                            uint32_t* counts, uint32_t* work, uint32_t max_depth, const PrtSampling& sp, const DevEnv* env,
+                            const DevLens* lens) {
+    const uint32_t S = tm.n_pix_local ? n_paths / tm.n_pix_local : 0u;
+    const uint32_t group = (sp.jitter || lens) ? (uint32_t)RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
+    const dim3 grid((tm.n_pix_local + PRODUCER_BLOCK - 1) / PRODUCER_BLOCK, (S + group - 1) / group);
+    const DevEnv e = env ? *env : DevEnv{};
+    const DevLens l = lens ? *lens : DevLens{0.0f, 0.0f};
+#define PRT_RAYGEN_LIST(J, AB, EN, LE)                                                                                          \
+    hipLaunchKernelGGL((k_raygen_list<J, AB, EN, LE>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, e, l, cam, tm, list, S, first_sample, \
+                       seed, out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp)
+#define PRT_RAYGEN_LIST2(J, AB)                                \
+    do {                                                       \
+        if (env) {                                             \
+            if (lens) PRT_RAYGEN_LIST(J, AB, true, true);      \
+            else PRT_RAYGEN_LIST(J, AB, true, false);          \
+        } else {                                               \
+            if (lens) PRT_RAYGEN_LIST(J, AB, false, true);     \
+            else PRT_RAYGEN_LIST(J, AB, false, false);         \
+        }                                                      \
+    } while (0)
+    if (sc.abvh_nodes) {
+        if (sp.jitter) PRT_RAYGEN_LIST2(true, true); else PRT_RAYGEN_LIST2(false, true);
+    } else {
+        if (sp.jitter) PRT_RAYGEN_LIST2(true, false); else PRT_RAYGEN_LIST2(false, false);
+    }
+#undef PRT_RAYGEN_LIST2
+#undef PRT_RAYGEN_LIST
+}
+
+void prt_launch_tile_select(hipStream_t st, const float4* film_local, const float2* stat, const PrtTileMap& tm, const uint32_t* prev,
+                            uint32_t n_in, float threshold, float noise_floor, uint32_t* flags, uint32_t* out, uint32_t* count) {
+    if (n_in) hipLaunchKernelGGL(k_tile_select, dim3((n_in + 3u) / 4u), dim3(256), 0, st, film_local, stat, tm, prev, n_in, threshold,
+                                 noise_floor, flags);
+    hipLaunchKernelGGL(k_tile_compact, dim3(1), dim3(1024), 0, st, flags, prev, n_in, out, count);
 }

@@ -5,6 +5,12 @@
 //              [--lighting off|nee|mis] [--light-sources analytic|all] [--env FILE.pfm [--env-share Q]]
 //              [--fov-deg D] [--aperture R --focus F]
 //              [--ground-texture FILE.pfm] [--mesh-texture FILE.pfm] [--texture-filter nearest|bilinear]
+//              [--adaptive THRESHOLD [--min-spp N --spp-step N --max-spp N --noise-floor F]
+//               [--samples-out FILE.pfm] [--noise-out FILE.pfm]]
+// --adaptive T renders with tile-adaptive sampling (prt_render_adaptive) instead of --spp samples everywhere: --min-spp
+// (default 8) samples for every pixel, then --spp-step (8) at a time for the 8x8 tiles that still hold a pixel whose standard
+// error exceeds T x (mean luminance + --noise-floor (0.01)), up to --max-spp (64).  --samples-out writes every pixel's sample
+// count and --noise-out its relative standard error, as colour PFMs with the value in all three channels.
 // --ground-texture / --mesh-texture (with --ply) take the albedo of the ground quad / of the mesh from a colour PFM (top
 // row first, repeated outside [0, 1]); the mesh needs per-vertex UVs in its PLY (s/t, u/v or texture_u/texture_v).
 // --fov-deg sets the vertical field of view in degrees (default: the reference's 1 rad); --aperture R (lens radius, world
@@ -38,6 +44,9 @@ int main(int argc, char** argv) {
     double fov_deg = 0.0;
     uint32_t W = 256, H = 256, spp = 1, depth = 2, seed = 0, refine = 0, sif = 0, frames = 1, lighting = PRT_LIGHTING_OFF;
     uint32_t light_sources = PRT_LIGHT_SOURCES_ANALYTIC;
+    bool adaptive = false;
+    PrtAdaptive ad{8u, 8u, 64u, 0.0f, 0.01f};
+    std::string samples_out, noise_out;
     std::vector<int> devices{0};
     float cam[3] = {5.0f, 5.0f, 8.0f};
     bool cam_set = false;
@@ -81,6 +90,13 @@ int main(int argc, char** argv) {
             else if (m == "bilinear") tex_filter = PRT_TEX_BILINEAR;
             else { fprintf(stderr, "--texture-filter takes nearest or bilinear\n"); return 2; }
         }
+        else if (a == "--adaptive") { ad.threshold = (float)atof(next()); adaptive = true; }
+        else if (a == "--min-spp") ad.min_spp = (uint32_t)atoi(next());
+        else if (a == "--spp-step") ad.step_spp = (uint32_t)atoi(next());
+        else if (a == "--max-spp") ad.max_spp = (uint32_t)atoi(next());
+        else if (a == "--noise-floor") ad.noise_floor = (float)atof(next());
+        else if (a == "--samples-out") samples_out = next();
+        else if (a == "--noise-out") noise_out = next();
         else if (a == "--gpus") { const int n = atoi(next()); devices.clear(); for (int d = 0; d < n; ++d) devices.push_back(d); }
         else if (a == "--devices") { devices.clear(); std::string l = next(); for (size_t p = 0; p < l.size();) { size_t e = l.find(',', p); if (e == std::string::npos) e = l.size(); devices.push_back(atoi(l.substr(p, e - p).c_str())); p = e + 1; } }
         else if (a == "--camera") { for (int k = 0; k < 3; ++k) cam[k] = (float)atof(next()); cam_set = true; }
@@ -88,6 +104,10 @@ int main(int argc, char** argv) {
     }
     if ((!ground_tex.empty() || !mesh_tex.empty()) && ply.empty()) {
         fprintf(stderr, "--ground-texture and --mesh-texture go with --ply (the presets have no ground quad or mesh of their own)\n");
+        return 2;
+    }
+    if (!adaptive && (!samples_out.empty() || !noise_out.empty())) {
+        fprintf(stderr, "--samples-out and --noise-out go with --adaptive\n");
         return 2;
     }
     try {
@@ -125,13 +145,18 @@ int main(int argc, char** argv) {
         if (light_sources != (uint32_t)PRT_LIGHT_SOURCES_ANALYTIC) r.SetLightSources(light_sources);
         if (!env.empty()) r.SetEnvironmentPfm(env, env_share);
         if (fov_deg != 0.0 || aperture != 0.0f) r.SetLens((float)(fov_deg * 3.14159265358979323846 / 180.0), aperture, focus);
+        if (adaptive) r.SetFilmStatistics(true);
+        PrtAdaptiveInfo ainfo{};
         if (frames > 1) {  // warm-up frame (first-touch allocations, clocks), then the timed ones
             r.Render(spp);
             r.Clear();
         }
         const PrtStats st0 = r.Stats();
         const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t f = 0; f < frames; ++f) r.Render(spp);  // each call ends with the gather to the first device
+        for (uint32_t f = 0; f < frames; ++f) {  // each call ends with the gather to the first device
+            if (adaptive) ainfo = r.RenderAdaptive(ad);
+            else r.Render(spp);
+        }
         const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         r.Download();
         r.UpdateDisplay();
@@ -143,8 +168,23 @@ int main(int argc, char** argv) {
             fprintf(stderr, "cannot write %s.ppm/.pfm\n", out.c_str());
             return 1;
         }
+        auto write_grey = [&](const std::string& path, const std::vector<float>& v) {
+            std::vector<float> rgb((size_t)W * H * 3);
+            for (size_t i = 0; i < (size_t)W * H; ++i) rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = v[i];
+            return prt_write_pfm(path.c_str(), rgb.data(), W, H);
+        };
+        if (!samples_out.empty() && write_grey(samples_out, film.weights)) { fprintf(stderr, "cannot write %s\n", samples_out.c_str()); return 1; }
+        if (!noise_out.empty()) {
+            std::vector<float> noise;
+            r.NoiseMap(ad.noise_floor, noise);
+            if (write_grey(noise_out, noise)) { fprintf(stderr, "cannot write %s\n", noise_out.c_str()); return 1; }
+        }
+        if (adaptive)
+            printf("adaptive (last frame): threshold %g, %u..%u spp in steps of %u: %u passes, %llu pixel-samples, %u tiles: %u converged, %u at the cap, %u..%u spp per tile\n",
+                   ad.threshold, ad.min_spp, ad.max_spp, ad.step_spp, ainfo.passes, (unsigned long long)ainfo.pixel_samples, ainfo.tiles_local,
+                   ainfo.tiles_converged, ainfo.tiles_capped, ainfo.min_tile_spp, ainfo.max_tile_spp);
         printf("%ux%u, %u spp, max_depth %u, %u GPU(s) [gather: %s]: %llu rays in %.3f s = %.1f Mrays/s -> %s.ppm, %s.pfm\n", W, H,
-               spp * frames, depth, r.DeviceCount(), r.Transport(), (unsigned long long)(st.rays_total - st0.rays_total), s,
+               (adaptive ? ad.max_spp : spp) * frames, depth, r.DeviceCount(), r.Transport(), (unsigned long long)(st.rays_total - st0.rays_total), s,
                (st.rays_total - st0.rays_total) / s / 1e6,
                out.c_str(), out.c_str());
     } catch (const std::exception& e) {

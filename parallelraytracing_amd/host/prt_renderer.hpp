@@ -239,6 +239,35 @@ public:
         check(prt_group_render(grp_, spp, max_depth_, seed_, frame_));
         frame_ += spp;
     }
+    // Film statistics (prt_set_film_statistics): second moments of every pixel's luminance beside the film; switching them
+    // clears the film.  RenderAdaptive needs them on.
+    void SetFilmStatistics(bool on) {
+        check(prt_group_set_film_statistics(grp_, on ? 1 : 0));
+        if (on != stats_on_) frame_ = 0;
+        stats_on_ = on;
+    }
+    // Tile-adaptive sampling (prt_render_adaptive): min_spp samples everywhere, then step_spp at a time to the 8x8 tiles that
+    // still hold a pixel whose standard error exceeds threshold * (mean + noise_floor), up to max_spp.  After Download() the
+    // film's weights are the per-pixel sample counts.  The next Render / RenderAdaptive continues after max_spp indices.
+    PrtAdaptiveInfo RenderAdaptive(const PrtAdaptive& cfg) {
+        PrtAdaptiveInfo info{};
+        check(prt_group_render_adaptive(grp_, &cfg, max_depth_, seed_, frame_, &info));
+        frame_ += cfg.max_spp;
+        return info;
+    }
+    // Per-pixel relative standard error (prt_film_noise_read), width * height floats: every pixel from the rank that owns its tile
+    void NoiseMap(float noise_floor, std::vector<float>& out) {
+        const uint32_t n = prt_group_size(grp_), W = film_->width, H = film_->height, tiles_x = (W + 7u) / 8u;
+        out.assign((size_t)W * H, 0.0f);
+        std::vector<float> part((size_t)W * H);
+        for (uint32_t r = 0; r < n; ++r) {
+            PrtContext* c = prt_group_context(grp_, r);
+            if (prt_film_noise_read(c, noise_floor, part.data())) throw Error(std::string("prt_film_noise_read: ") + prt_last_error(c));
+            for (uint32_t y = 0; y < H; ++y)
+                for (uint32_t x = 0; x < W; ++x)
+                    if (((y / 8u) * tiles_x + x / 8u) % n == r) out[(size_t)y * W + x] = part[(size_t)y * W + x];
+        }
+    }
     // The placed copies of `scene` moved (Scene::SetInstanceTransform): every GPU's top level follows, no mesh tree is
     // rebuilt and the film is not cleared.  mode: PRT_INSTANCES_REFIT (topology kept) / PRT_INSTANCES_REBUILD
     void UpdateInstances(const Scene& scene, uint32_t mode = PRT_INSTANCES_REFIT) {
@@ -324,6 +353,7 @@ private:
     PrtGroup* grp_ = nullptr;
     Film* film_ = nullptr;
     uint32_t max_depth_, seed_, frame_ = 0;
+    bool stats_on_ = false;
 };
 
 }  // namespace prt

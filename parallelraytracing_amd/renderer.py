@@ -462,6 +462,42 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_get_lens(self._ctx, C.byref(ln)))
         return ln
 
+    def set_film_statistics(self, on: bool = True):
+        """Second moments of every pixel's luminance beside the film (include/prt.h "Film statistics and adaptive sampling").
+        Switching them clears the film (and restarts the sample index)."""
+        L = capi.lib()
+        if bool(on) != bool(L.prt_get_film_statistics(self._ctx)):
+            self.frame_index = 0
+        self._check(L.prt_set_film_statistics(self._ctx, 1 if on else 0))
+
+    def film_statistics(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(sum of y, sum of y^2) per pixel, film layout (H, W) float32; zero for pixels this rank does not own."""
+        f = self.film
+        a = np.zeros((f.height, f.width), np.float32)
+        q = np.zeros((f.height, f.width), np.float32)
+        self._check(capi.lib().prt_film_statistics_read(self._ctx, a.ctypes.data_as(_fp), q.ctypes.data_as(_fp)))
+        return a, q
+
+    def noise_map(self, noise_floor: float = 0.01) -> np.ndarray:
+        """Relative standard error of every pixel's mean luminance (prt_film_noise_read), (H, W) float32; +inf below 2 samples."""
+        f = self.film
+        out = np.zeros((f.height, f.width), np.float32)
+        self._check(capi.lib().prt_film_noise_read(self._ctx, float(noise_floor), out.ctypes.data_as(_fp)))
+        return out
+
+    def render_adaptive(self, threshold: float, min_spp: int = 8, step_spp: int = 8, max_spp: int = 64,
+                        noise_floor: float = 0.01, first_sample: Optional[int] = None) -> "capi.PrtAdaptiveInfo":
+        """Tile-adaptive sampling (prt_render_adaptive): min_spp samples everywhere, then step_spp at a time to the 8x8 tiles
+        that still hold an unconverged pixel, up to max_spp.  Needs set_film_statistics(True).  first_sample defaults to the
+        renderer's running index, which then moves on by max_spp (so a later call never reuses an index)."""
+        cfg = capi.PrtAdaptive(int(min_spp), int(step_spp), int(max_spp), float(threshold), float(noise_floor))
+        info = capi.PrtAdaptiveInfo()
+        first = self.frame_index if first_sample is None else int(first_sample)
+        self._check(capi.lib().prt_render_adaptive(self._ctx, C.byref(cfg), self.max_depth, self.seed, first, C.byref(info)))
+        if first_sample is None:
+            self.frame_index += int(max_spp)
+        return info
+
     def set_lighting(self, mode) -> int:
         """Light sampling toward the analytic emitters (include/prt.h PrtLighting): "off" | "mis" | "nee" or 0 | 1 | 2."""
         m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
@@ -946,6 +982,49 @@ class HipWavefrontGroupRenderer:
         ln = capi.PrtLens(float(fov_y), float(aperture), float(focus_distance))
         self._check(capi.lib().prt_group_set_lens(self._grp, C.byref(ln)))
         return ln
+
+    def set_film_statistics(self, on: bool = True):
+        """HipWavefrontRenderer.set_film_statistics on every rank."""
+        L = capi.lib()
+        if bool(on) != bool(L.prt_get_film_statistics(L.prt_group_context(self._grp, 0))):
+            self.frame_index = 0
+        self._check(L.prt_group_set_film_statistics(self._grp, 1 if on else 0))
+
+    def _per_rank(self, read) -> np.ndarray:
+        """Assembles an (H, W) map from the ranks' own read-backs: every pixel from the rank that owns its 8x8 tile."""
+        L = capi.lib()
+        f = self.film
+        n = self.n_devices
+        ys, xs = np.mgrid[0:f.height, 0:f.width]
+        owner = ((ys // 8) * ((f.width + 7) // 8) + xs // 8) % n
+        out = np.zeros((f.height, f.width), np.float32)
+        for r in range(n):
+            ctx = L.prt_group_context(self._grp, r)
+            part = np.zeros((f.height, f.width), np.float32)
+            if read(ctx, part):
+                raise PrtError(L.prt_last_error(ctx).decode())
+            out[owner == r] = part[owner == r]
+        return out
+
+    def film_statistics(self) -> Tuple[np.ndarray, np.ndarray]:
+        L = capi.lib()
+        return (self._per_rank(lambda ctx, p: L.prt_film_statistics_read(ctx, p.ctypes.data_as(_fp), None)),
+                self._per_rank(lambda ctx, p: L.prt_film_statistics_read(ctx, None, p.ctypes.data_as(_fp))))
+
+    def noise_map(self, noise_floor: float = 0.01) -> np.ndarray:
+        L = capi.lib()
+        return self._per_rank(lambda ctx, p: L.prt_film_noise_read(ctx, float(noise_floor), p.ctypes.data_as(_fp)))
+
+    def render_adaptive(self, threshold: float, min_spp: int = 8, step_spp: int = 8, max_spp: int = 64,
+                        noise_floor: float = 0.01, first_sample: Optional[int] = None) -> "capi.PrtAdaptiveInfo":
+        """HipWavefrontRenderer.render_adaptive: every rank loops over its own tiles, then the gather; info summed."""
+        cfg = capi.PrtAdaptive(int(min_spp), int(step_spp), int(max_spp), float(threshold), float(noise_floor))
+        info = capi.PrtAdaptiveInfo()
+        first = self.frame_index if first_sample is None else int(first_sample)
+        self._check(capi.lib().prt_group_render_adaptive(self._grp, C.byref(cfg), self.max_depth, self.seed, first, C.byref(info)))
+        if first_sample is None:
+            self.frame_index += int(max_spp)
+        return info
 
     def set_lighting(self, mode) -> int:
         m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
