@@ -439,7 +439,11 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src);
  * copies (PrtInstance) are not refitted (PRT_ERR_INVALID): their copies move through prt_set_instance_transforms
  * below, which leaves every mesh tree alone.  After a refit the A/B kernels over the binary / 4-wide
  * trees are unavailable (those trees are dropped).  Results equal a fresh prt_set_scene of the new geometry bit for bit
- * (the closest hit does not depend on the tree); traversal gets slower as the deformation grows. */
+ * (the closest hit does not depend on the tree); traversal gets slower as the deformation grows.
+ * A tree of more than 16 levels (PrtBvhInfo.depth8 > 16; only the host builder makes those) is not refitted:
+ * PRT_ERR_INVALID with a message that names the depth, before anything is written, the scene exactly what it was and
+ * usable.  Without the 4-wide tree no kernel instance holds its deepest rays (the deepest stack, 15 entries, covers 16
+ * levels); the caller rebuilds with prt_set_scene. */
 int prt_refit_meshes(PrtContext* ctx, const PrtMesh* meshes, uint32_t n_meshes);
 /* Moving placed copies (rigid-body animation for the price of the top level; the reference's OptiX backend rebuilds its
  * instance level only when transforms change, src/backend/optix/renderer.cpp:703-871): instances[i] replaces mat / inv of
@@ -690,6 +694,11 @@ int prt_measure_traversal(PrtContext* ctx, uint32_t max_depth, uint32_t seed, ui
  * [14] sum over waves of distinct scattering types present, [15] waves with a scattering lane.  out: 16 * max_depth words. */
 int prt_measure_shade_divergence(PrtContext* ctx, uint32_t max_depth, uint32_t seed, uint32_t sample, uint64_t* out);
 int prt_bvh_info(PrtContext* ctx, PrtBvhInfo* out);
+/* Rows per thread of the global spill area behind the LDS stacks of the spill-capable kernels, for a scene whose 4-wide
+ * tree stacks at most max_stack4 entries (PrtBvhInfo.max_stack4) and whose binary tree has max_depth levels
+ * (PrtBvhInfo.max_depth): the 4-wide instance keeps 27 entries in LDS, the binary one 31 of its max_depth - 1; one row of
+ * slack; never fewer than 64.  A pure function (no context); the library sizes the area with it per scene. */
+uint32_t prt_spill_rows(uint32_t max_stack4, uint32_t max_depth);
 int prt_kernel_occupancy(PrtContext* ctx, PrtOccupancy* out);
 /* Name of the traversal kernel instance the current scene and tunables select (what prt_render launches and what
  * prt_kernel_occupancy describes): "lean8_5waves", "deep15_4waves", "inst12_4waves", "wide11_5waves", "bvh4", "bvh2".

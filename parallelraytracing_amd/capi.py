@@ -261,6 +261,7 @@ SIGNATURES = {
     "prt_reset_stats": (C.c_int, [_vp]),
     "prt_measure_traversal": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PrtStats)]),
     "prt_bvh_info": (C.c_int, [_vp, C.POINTER(PrtBvhInfo)]),
+    "prt_spill_rows": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "prt_kernel_occupancy": (C.c_int, [_vp, C.POINTER(PrtOccupancy)]),
     "prt_kernel_instance": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),
     "prt_shade_instance": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),

@@ -439,9 +439,9 @@ int ensure_counters(PrtContext* c) {
     return PRT_OK;
 }
 
-// global spill area of the traversal stacks: [63 - stack_lds entries][grid threads]
+// global spill area of the traversal stacks: [prt_spill_rows of the scene's trees][grid threads]
 int ensure_spill(PrtContext* c) {
-    const size_t need = (size_t)c->tune.grid_blocks * 256u * 64u;
+    const size_t need = (size_t)c->tune.grid_blocks * 256u * prt_spill_rows(c->hs.bvh.max_stack4, c->hs.bvh.max_depth);
     if (need <= c->spill_entries) return PRT_OK;
     free_dev(c->d_spill);
     c->spill_entries = 0;
@@ -1197,6 +1197,11 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     if (c->dsc.n_insts) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: scenes with placed copies are rebuilt, not refitted");
     if (!c->dsc.nodes8 || c->hs.bvh.nodes8.empty()) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes needs the compressed 8-wide tree");
     if (2 * (size_t)n_meshes != c->hs.mesh_sizes.size()) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: the scene has %zu meshes", c->hs.mesh_sizes.size() / 2);
+    // the refit drops the 4-wide tree, and with it the re-walk of the rays that overflow the 8-wide kernels' stacks: the deepest
+    // of those (deep15_4waves, 15 entries) holds every ray of a tree of 16 levels and no more
+    if (c->hs.bvh_info.depth8 > 16u)
+        return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: a tree of %u levels (depth8 > 16) is rebuilt with prt_set_scene, not refitted",
+                    c->hs.bvh_info.depth8);
     uint64_t n_tris = 0;
     for (uint32_t m = 0; m < n_meshes; ++m) {
         const PrtMesh& me = meshes[m];

@@ -4026,7 +4026,8 @@ __global__ void k_reset_cursors(uint32_t* work) {
 
 bool prt_traverse_takes_primary(const DevScene& sc, const PrtTravTuning& tune) {
     // the 5-waves instance of the 8-wide kernel, and a tree shallow enough that no ray can reach the overflow list (its
-    // re-traversal reads full ray records)
+    // re-traversal reads full ray records).  (The RAW stack_cap: on a scene without a 4-wide tree, where the launchers
+    // ignore the hook (t8_tuning), a set hook still sends bounce 0 down the general route.  Same rays, same hits.)
     return sc.nodes8 && !sc.n_insts && (tune.wide == 2u || !sc.nodes4) && (tune.stack_lds == 0u || tune.stack_lds == 6u) &&
            tune.stack_cap == 0u && sc.depth8 <= 9u;
 }
@@ -4040,12 +4041,21 @@ bool prt_traverse_takes_primary(const DevScene& sc, const PrtTravTuning& tune) {
 //                  HOST-built trees, whose rare deeper rays go through the overflow list to the 4-wide tree (C5)
 //   deep15_4waves  deeper trees without a 4-wide fallback (device-built): 15 entries, 4 waves per SIMD
 enum PrtT8Kind { T8_NONE = 0, T8_INST12_4, T8_WIDE11_5, T8_LEAN8_5, T8_DEEP15_4 };
+// Without a 4-wide tree (device-built and refitted scenes) nothing re-walks the rays of the overflow list, so a forced
+// instance whose stack the tree's depth exceeds (stack_lds 5 beyond 12 levels, 6 beyond 9) is not taken: the choice falls
+// back to the default's, and the launchers ignore the stack_cap test hook (t8_tuning).  Such scenes have at most 16 levels
+// (the device builders stop at 15, prt_refit_meshes refuses deeper trees), which deep15_4waves holds.
 static PrtT8Kind t8_kind(const DevScene& sc, const PrtTravTuning& tune) {
     if (!((tune.wide == 2u || sc.n_insts || !sc.nodes4) && sc.nodes8)) return T8_NONE;
     if (sc.n_insts) return T8_INST12_4;
-    if (tune.stack_lds == 5u) return T8_WIDE11_5;
-    const bool lean = tune.stack_lds == 6u || (tune.stack_lds == 0u && (sc.depth8 <= 9u || sc.nodes4 != nullptr));
+    const bool rewalk = sc.nodes4 != nullptr;
+    if (tune.stack_lds == 5u && (rewalk || sc.depth8 <= 12u)) return T8_WIDE11_5;
+    const bool lean = (tune.stack_lds == 0u || tune.stack_lds == 6u) && (rewalk || sc.depth8 <= 9u);
     return lean ? T8_LEAN8_5 : T8_DEEP15_4;
+}
+static PrtTravTuning t8_tuning(const DevScene& sc, PrtTravTuning tune) {
+    if (!sc.nodes4 && !sc.n_insts) tune.stack_cap = 0u;
+    return tune;
 }
 const char* prt_traverse_instance(const DevScene& sc, const PrtTravTuning& tune) {
     switch (t8_kind(sc, tune)) {
@@ -4063,7 +4073,7 @@ void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
     // exit_max "auto" (0xFFFFFFFF, the context's default): the two-level instance leaves its node loop at <= 32 walkers
     // (its lanes wait for level switches that the wave does together; C5I +4.4 % against 16, gpurun_out/r3_sweep_C5I_b.log),
     // every other instance at <= 16
-    PrtTravTuning tune = tune_in;
+    PrtTravTuning tune = t8_tuning(sc, tune_in);
     if (tune.exit_max == 0xFFFFFFFFu) tune.exit_max = t8_kind(sc, tune_in) == T8_INST12_4 ? 32u : 16u;
     // tri_min "auto" (0, the context's default): a triangle phase starts after 24 queueing lane-steps, but after 12 on one-level
     // trees far beyond the caches (one node per 128-B line: C5 +1.7 %; 16: +0.8 to +1.9 %), whose walks gain more from an earlier
@@ -4193,7 +4203,7 @@ void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
         prt_launch_traverse(st, sc, in, count_ptr, work, spill, max_rays, tree_depth, stack4, tune_in, nullptr);
         return;
     }
-    PrtTravTuning tune = tune_in;  // the "auto" values exactly as prt_launch_traverse resolves them
+    PrtTravTuning tune = t8_tuning(sc, tune_in);  // the "auto" values exactly as prt_launch_traverse resolves them
     if (tune.exit_max == 0xFFFFFFFFu) tune.exit_max = kind == T8_INST12_4 ? 32u : 16u;
     if (tune.tri_min == 0u) tune.tri_min = (kind != T8_INST12_4 && sc.node_stride == 8u) ? 12u : 24u;
     tune.perm = nullptr;
@@ -4231,6 +4241,7 @@ void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
 
 // The PATH instance (PrtPathArgs): whole paths in one launch, for small batches.  One-level scenes with the 8-wide tree,
 // a tree its 15-entry stack holds, and no primitive BVH (classify_ray's walk keeps a per-thread LDS stack of its own).
+// (The RAW stack_cap here too: a set hook selects the pipeline, also where t8_tuning makes the launchers ignore it.)
 bool prt_path_kernel_applies(const DevScene& sc, const PrtTravTuning& tune) {
     return sc.nodes8 && !sc.n_insts && !sc.abvh_nodes && sc.depth8 <= 16u && tune.wide == 2u && tune.stack_cap == 0u;
 }

@@ -12,6 +12,14 @@
 #include <cstring>
 #include <utility>
 
+// include/prt.h: the 4-wide spill-capable instance keeps 27 entries in LDS (k_traverse4_persistent<27, 5, 1>), the binary one
+// 31 of its max_depth - 1 pushes (k_traverse_persistent<31, 5, 1>); row r of the area holds stack entry STACK_L + r
+extern "C" uint32_t prt_spill_rows(uint32_t max_stack4, uint32_t max_depth) {
+    const uint32_t rows4 = max_stack4 > 27u ? max_stack4 - 27u : 0u;
+    const uint32_t rows2 = max_depth > 32u ? max_depth - 32u : 0u;
+    return std::max(64u, std::max(rows4, rows2) + 1u);
+}
+
 namespace {
 
 constexpr uint32_t kMaxLeaf = 3;  // the compressed 8-wide node encodes at most 3 triangles per leaf (bvh.h)

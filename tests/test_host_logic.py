@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import deep_trees
 import util
 from util import orc, prt
 
@@ -494,53 +495,17 @@ def test_bvh8_python_traversal_agrees_with_oracle_linear_scan():
     d = np.stack([prt.glm_normalize(v) for v in (-o + rng.uniform(-0.8, 0.8, size=o.shape).astype(np.float32))])
     want = util.oracle_scene(sc).closest_hit(o, d, use_bvh=False, n_threads=8)
     assert (want["prim"] >= 0).sum() > 60
-    octs = set()
-    max_sp = 0
-    for k in range(len(o)):
-        if want["prim"][k] < 0:
-            continue
-        dk = d[k].astype(np.float64)
-        inv = 1.0 / np.where(np.abs(dk) < 1e-20, 1e-20, dk)
-        neg = inv < 0
-        octinv = 7 - (int(neg[0]) | int(neg[1]) << 1 | int(neg[2]) << 2)
-        octs.add(octinv)
-        tlimit = np.sqrt(float(want["d2"][k])) * 1.001 + 1e-3
-        reached = []
-        gx, gy, stack = 0, 1 << (24 + octinv), []
-        order_ok = True
-        while True:
-            if not gy > 0x00FFFFFF:
-                if not stack:
-                    break
-                gx, gy = stack.pop()
-            bit = gy.bit_length() - 1
-            assert 24 <= bit <= 31
-            gy &= ~(1 << bit)
-            if gy > 0x00FFFFFF:
-                stack.append((gx, gy))
-                max_sp = max(max_sp, len(stack))
-            slot = (bit - 24) ^ octinv
-            idx = gx + bin(gy & ((1 << slot) - 1) & 0xFF).count("1")
-            lo, hi = D["lo"][idx] - 1e-4, D["hi"][idx] + 1e-4
-            near = np.where(neg, hi, lo)
-            far = np.where(neg, lo, hi)
-            tn = np.maximum(((near - o[k]) * inv).max(axis=1), 0.0)
-            tf = np.minimum(((far - o[k]) * inv).min(axis=1), tlimit)
-            hitmask = 0
-            for i in range(8):
-                meta = int(D["meta"][idx, i])
-                if meta == 0 or not tn[i] <= tf[i]:
-                    continue
-                inner = (meta & (meta << 1)) & 0x10
-                bidx = (meta ^ (octinv if inner else 0)) & 0x1F
-                hitmask |= (meta >> 5) << bidx
-            gx, gy = int(D["child_base"][idx]), (hitmask & 0xFF000000) | int(D["imask"][idx])
-            tm = hitmask & 0x00FFFFFF
-            while tm:
-                t = (tm & -tm).bit_length() - 1
-                tm &= tm - 1
-                reached.append(int(prim_of_slot[int(D["tri_base"][idx]) + t]))
-        assert int(want["prim"][k]) in reached and len(reached) == len(set(reached)) and order_ok
+    # (the emulation itself is tests/deep_trees.py walk8, shared with the deep-tree tests: all rays in lockstep)
+    hit = np.nonzero(want["prim"] >= 0)[0]
+    need, leaves = deep_trees.walk8(D, o[hit], d[hit], 1e-4, np.sqrt(want["d2"][hit].astype(np.float64)) * 1.001 + 1e-3)
+    reached = [[] for _ in hit]
+    for j, first, mask, _, _ in leaves:
+        reached[j] += [int(prim_of_slot[s]) for s in deep_trees.leaf_slots(first, mask)]
+    neg = d[hit] < 0
+    octs = set((7 - (neg[:, 0].astype(int) | neg[:, 1].astype(int) << 1 | neg[:, 2].astype(int) << 2)).tolist())
+    max_sp = int(need.max())
+    for j, k in enumerate(hit):
+        assert int(want["prim"][k]) in reached[j] and len(reached[j]) == len(set(reached[j]))
     assert len(octs) == 8 and max_sp < r.bvh_info().depth8
 
 
