@@ -541,28 +541,55 @@ f3 h_cross(f3 a, f3 b) { return f3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x,
 // The whole film as a batch view (PrtBatchView, prt_kernels.h): the context's own tile map, no tile list.
 PrtBatchView whole_film(const PrtContext* c) { return PrtBatchView{c->tm, nullptr}; }
 
-// The accumulate launch of a batch.  With film statistics off the launchers and kernels the context always had; with them on
-// (or for a tile list) the instances of k_accumulate_stat, which add the same samples to the film in the same order.
-void launch_accumulate(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t max_depth, bool accumulate, bool lit,
-                       const float4* pix_end) {
-    if (c->film_stats || view.list)
-        prt_launch_accumulate_stat(c->stream, c->d_rad, lit ? c->lb.lrad : nullptr, c->d_film_local, c->d_film_stat, view.tm, S_cur,
-                                   max_depth, accumulate, c->ray_stats_target, pix_end, view.list);
-    else if (lit)
-        prt_launch_accumulate_lit(c->stream, c->d_rad, c->lb.lrad, c->d_film_local, view.tm, S_cur, max_depth, accumulate,
-                                  c->ray_stats_target);
+// The tree walk of a prepared ray buffer (analytic scan done, hit / hd2 seeded) on the context's stream: the closest hit, or
+// with `any` the any-hit walk behind prt_occluded and the shadow rays.  The persistent kernels, or k_intersect where another
+// traversal variant is forced (A/B; it finds the closest hit from the seeded bound, which answers an occlusion query as well).
+void walk_rays(PrtContext* c, const PrtRayBuf& rays, const uint32_t* count, uint32_t max_rays, bool any, const PrtTravTuning& tune,
+               unsigned long long* stats, const PrtPrimary* primary) {
+    if (!prt_route_walk8(c->variant == 0, c->dsc.n_insts != 0u, c->dsc.nodes != nullptr))
+        prt_launch_intersect(c->stream, c->dsc, rays, count, max_rays, c->hs.bvh.max_depth <= 31 ? 31 : 63, c->variant, stats);
+    else if (any)
+        prt_launch_occluded(c->stream, c->dsc, rays, count, c->d_work, c->d_spill, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune);
     else
-        prt_launch_accumulate(c->stream, c->d_rad, c->d_film_local, view.tm, S_cur, max_depth, accumulate, c->ray_stats_target, pix_end);
+        prt_launch_traverse(c->stream, c->dsc, rays, count, c->d_work, c->d_spill, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4,
+                            tune, stats, primary);
+}
+
+// Measurement aid (sort_rays, tools/sort_ab.py): the front rays of `in` in sorted order through tune->perm.  The host needs
+// the ray count, so this synchronises; the sort is timed as its own stage (scan_ms), the traversal that follows (`ep`) as usual.
+int sort_front_rays(PrtContext* c, const PrtRayBuf& in, const uint32_t* front_count, uint32_t n_paths, EventPair* ep, PrtTravTuning* tune) {
+    int rc;
+    uint32_t n_front = 0;
+    HIPCHECK(c, hipMemcpyAsync(&n_front, front_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    if (n_front <= 1u) return PRT_OK;
+    if (c->sort_entries < n_paths) {
+        free_dev(c->d_sort);
+        c->sort_entries = 0;
+        c->sort_temp = prt_sort_rays_temp_bytes(n_paths);
+        HIPCHECK(c, hipMalloc((void**)&c->d_sort, 4 * (size_t)n_paths * sizeof(uint32_t) + c->sort_temp));
+        c->sort_entries = n_paths;
+    }
+    EventPair es{};
+    if ((rc = begin_event(c, 4, &es))) return rc;
+    uint32_t* q = c->d_sort;
+    if (prt_sort_rays(c->stream, in.o, in.d, n_front, c->dsc.root_min, c->dsc.root_max, c->sort_rays, q, q + n_paths,
+                      q + 2 * (size_t)n_paths, q + 3 * (size_t)n_paths, q + 4 * (size_t)n_paths, c->sort_temp))
+        return fail(c, PRT_ERR_HIP, "ray sort failed");
+    if ((rc = end_event(c, &es))) return rc;
+    if (c->timing) HIPCHECK(c, hipEventRecord(ep->a, c->stream));  // the traversal's own time starts after the sort
+    tune->perm = q + 3 * (size_t)n_paths;
+    return PRT_OK;
 }
 
 // One batch of S_cur samples: raygen -> (intersect, shade) x max_depth -> [accumulate].  `view` says which pixels: the whole
-// film (whole_film), or the tiles of a list (prt_render_adaptive): view.tm then counts the listed tiles only, compact local
-// pixel pl is lane pl & 63 of tile view.list[pl >> 6], and the batch takes the unfused full-record pipeline.
+// film (whole_film), or the tiles of a list (prt_render_adaptive): view.tm then counts the listed tiles only and compact local
+// pixel pl is lane pl & 63 of tile view.list[pl >> 6].  The route (which stages run, which kernel instances) is prt_plan_route's
+// (prt_route.h; DESIGN.md section 3 "Routes of a batch"): this function collects the facts and follows the plan.
 int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
               bool accumulate, unsigned long long* trav_stats) {
     const PrtTileMap& tm = view.tm;
-    const bool listed = view.list != nullptr;
-    if (listed && !c->d_film_stat) return fail(c, PRT_ERR_INVALID, "a tile list needs film statistics");
+    if (view.list && !c->d_film_stat) return fail(c, PRT_ERR_INVALID, "a tile list needs film statistics");
     const uint64_t n_paths64 = (uint64_t)S_cur * tm.n_pix_local;
     c->batch_walked = false;
     if (n_paths64 == 0) return PRT_OK;
@@ -570,24 +597,37 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     const uint32_t n_paths = (uint32_t)n_paths64;
     int rc = ensure_path_state(c, n_paths);
     if (rc) return rc;
-    const int stack_depth = c->hs.bvh.max_depth <= 31 ? 31 : 63;
     if ((rc = ensure_spill(c))) return rc;
-    // k_shade shades one analytic-only segment in place per call (never stored, never re-read: shade -24 % on C3) when
-    // the scene has a BVH and few analytic primitives; with many of them (RANDOM_BALLS presets) compacting between
-    // bounces is the better deal
-    // Lighting modes (PrtLighting) run k_shade_nee, which shades one segment per call: no fused segments, no compact primary
-    // rays, no path route (tunables: the frame does not depend on them)
-    // An environment image (prt_set_environment) runs the instances of its own, unfused as well
-    const bool lit = c->lighting != PRT_LIGHTING_OFF;
-    const bool envon = env_on(c);
     if ((rc = sync_light_tables(c))) return rc;
+    PrtRouteFacts f{};
+    f.lit = c->lighting != PRT_LIGHTING_OFF;
+    f.mesh_lights = mesh_lights_on(c);
+    f.env = env_on(c);
+    f.tex = tex_on(c);
+    f.lens = c->lens.aperture > 0.0f;
+    f.listed = view.list != nullptr;
+    f.film_stats = c->film_stats;
+    f.has_nodes = c->dsc.n_nodes != 0u;
+    f.has_bvh2 = c->dsc.nodes != nullptr;
+    f.insts = c->dsc.n_insts != 0u;
+    f.abvh = c->dsc.abvh_nodes != nullptr;
+    f.few_prims = c->dsc.n_prims <= 16u;
+    f.jitter = c->sampling.jitter != 0u;
+    f.sa = c->sampling.rr_depth != 0u || c->sampling.clamp > 0.0f;
+    f.multi_sample = S_cur > 1u;
+    f.variant0 = c->variant == 0;
+    f.compact_primary = c->compact_primary;
+    f.primary_walk = c->primary_walk;
+    f.takes_primary = prt_traverse_takes_primary(c->dsc, c->tune);
+    f.primary_hit = c->tune.primary_hit != 0u;
+    f.path_gate = !trav_stats && !c->d_shade_div && c->sort_rays == 0u && n_paths <= c->tune.path_max && prt_path_kernel_applies(c->dsc, c->tune);
+    f.path_kernel = c->tune.path_kernel;
+    f.fuse = c->tune.fuse;
+    const PrtRoutePlan plan = prt_plan_route(f);
+    const bool lit = f.lit, compact = plan.compact, walk = plan.walk;
     const DevEnv denv = dev_env(c);
-    const DevEnv* envp = envon ? &denv : nullptr;
-    // A texture binding (prt_set_textures) that textures a material runs the instances of its own by the same rule: unfused,
-    // full ray records, no path route
-    const bool texon = tex_on(c);
     const DevTex dtex = dev_tex(c);
-    const uint32_t fuse = (!lit && !envon && !texon && !listed && c->dsc.n_nodes && c->dsc.n_prims <= 16u) ? c->tune.fuse : 0u;
+    const DevLens dlens{c->lens.aperture, c->lens.focus_distance};
     // The ray count of a bounce is only known on the device.  With big batches a k_shade grid sized for the worst case is
     // a million blocks, most of which find nothing to do (~0.5 ms per launch, 4 % of a C3 step).  The host therefore
     // reads the counts of bounce d back WHILE the traversal kernel of bounce d runs (the copy is enqueued right after
@@ -611,41 +651,35 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         return e != hipSuccess ? e : hipEventRecord(c->ev_counts[d], c->count_stream);
     };
     EventPair ep{};
+    // film += the batch's samples (unless this is a measurement run) and per-depth ray counts from the paths' last segment indices
+    auto accumulate_batch = [&]() -> int {
+        if ((rc = begin_event(c, 3, &ep))) return rc;
+        const PrtAccumulateArgs aa{c->d_rad, lit ? c->lb.lrad : nullptr, c->d_film_local, c->d_film_stat, tm, S_cur, max_depth,
+                                   accumulate, c->ray_stats_target, compact ? c->d_pix + tm.n_pix_local : nullptr, view.list};
+        if (!prt_launch_accumulate(c->stream, plan.accumulate, aa)) return fail(c, PRT_ERR_INVALID, "no such accumulate instance");
+        if ((rc = end_event(c, &ep))) return rc;
+        if (accumulate && !view.list) c->stats.samples += S_cur;  // (whole-film samples only)
+        HIPCHECK(c, hipGetLastError());
+        return PRT_OK;
+    };
+    c->shade_instance = "";  // (the path route launches no shade kernel)
     // Small batches (the reference's contract: ONE sample per ProgressiveRender call, cpu/renderer.cpp:49) can run as one
     // launch of the PATH instance of the traversal kernel, which carries whole paths (prt_kernels.h PrtPathArgs), instead
     // of raygen + 2 x max_depth launches.  Same arithmetic, same draws, same rad[] / k_accumulate: the frame is
     // bit-identical (tests run both routes).  OFF by default (prt_set_param("path_kernel", 1 | 2)): measured, it ties with
     // the pipeline up to ~250 k paths per call and loses above (profiles/r3_path_kernel.txt, TUNING.md): both are bound
     // by a path's chain of dependent node fetches, and the pipeline shades with full waves.
-    // A thin lens (PrtLens with aperture > 0): every sample has a primary ray of its own, with its own origin: the per-sample
-    // full-record route that jitter takes; no compact primary rays (and so no one-walk-per-pixel list, no k_primary_hit) and
-    // no path route, which generates its rays itself
-    const bool lens_on = c->lens.aperture > 0.0f;
-    const DevLens dlens{c->lens.aperture, c->lens.focus_distance};
-    const bool path_route = !lit && !envon && !texon && !lens_on && !listed && c->tune.path_kernel != 0u && (c->tune.path_kernel == 2u || S_cur == 1u) && n_paths <= c->tune.path_max &&
-                            !trav_stats && !c->d_shade_div && c->variant == 0 && fuse == 0u && c->sort_rays == 0u &&
-                            prt_path_kernel_applies(c->dsc, c->tune);
-    c->shade_instance = "";  // (the path route launches no shade kernel)
-    if (path_route) {
+    if (plan.path) {
         HIPCHECK(c, hipMemsetAsync(c->d_work, 0, 256 * sizeof(uint32_t), c->stream));  // the cursors; the error flags in [256] stay for prt_synchronize
         PrtPathArgs pa{c->cam, tm, c->sampling, c->d_rad, first_sample, seed, max_depth, n_paths};
         if ((rc = begin_event(c, 1, &ep))) return rc;
         prt_launch_path(c->stream, c->dsc, pa, c->d_work, c->tune);
         if ((rc = end_event(c, &ep))) return rc;
         ++c->stats.intersect_launches;
-        if ((rc = begin_event(c, 3, &ep))) return rc;
-        launch_accumulate(c, view, S_cur, max_depth, accumulate, false, nullptr);
-        if ((rc = end_event(c, &ep))) return rc;
-        if (accumulate) c->stats.samples += S_cur;  // (never a tile list here)
-        HIPCHECK(c, hipGetLastError());
-        return PRT_OK;
+        return accumulate_batch();
     }
     // front/back counters of every bounce start at zero (the producers add to them atomically)
     HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
-    // compact primary rays (PrtPrimary): the default pipeline without jitter / roulette / clamp / fusion
-    const bool compact = !lit && !envon && !texon && !lens_on && !listed && c->compact_primary && c->variant == 0 && c->dsc.n_nodes != 0u && !c->dsc.abvh_nodes &&
-                         c->sampling.jitter == 0u && c->sampling.rr_depth == 0u && !(c->sampling.clamp > 0.0f) && fuse == 0u &&
-                         prt_traverse_takes_primary(c->dsc, c->tune);
     if (compact && c->pix_entries < tm.n_pix_local) {
         free_dev(c->d_pix);
         c->pix_entries = 0;
@@ -663,71 +697,38 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     // rb[0].hd2, counted in word PRT_CNT_LIST of bounce 0's counters (zeroed above), and leaves its hits in rb[0].hit per list
     // slot.  A batch of ONE sample keeps its path slots: they ARE that list (one path per pixel, in the same order), and
     // k_raygen saves the second store and atomic.
-    const bool walk = compact && c->primary_walk && S_cur > 1u;
     c->batch_walked = walk;
     const PrtPrimary primary{(const uint32_t*)c->rb[0].t, c->d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, tm.n_pix_local,
                              1.0f / (float)tm.n_pix_local, first_sample, seed, walk ? 1u : 0u};
     PrtPrimary primary_list = primary;  // what the traversal sees: list slots in place of path slots
     if (walk) primary_list.pid = (const uint32_t*)c->rb[0].hd2;
     if ((rc = begin_event(c, 0, &ep))) return rc;
-    if (listed)
-        prt_launch_raygen_list(c->stream, c->dsc, c->cam, tm, view.list, n_paths, first_sample, seed, c->rb[0], c->d_rad, c->d_counts,
-                               c->d_work, max_depth, c->sampling, envp, lens_on ? &dlens : nullptr);
-    else
-        prt_launch_raygen(c->stream, c->dsc, c->cam, tm, n_paths, first_sample, seed, c->rb[0], c->d_rad, c->d_counts,
-                          c->d_work, max_depth, c->sampling, compact ? c->d_pix : nullptr, envp, walk,
-                          lens_on ? &dlens : nullptr);
+    const PrtRaygenArgs ra{&c->dsc, c->cam, tm, n_paths, first_sample, seed, max_depth, c->rb[0], c->d_rad, c->d_counts, c->d_work, c->sampling,
+                           compact ? c->d_pix : nullptr, walk, f.env ? &denv : nullptr, f.lens ? &dlens : nullptr, view.list};
+    if (!prt_launch_raygen(c->stream, plan.raygen, ra)) return fail(c, PRT_ERR_INVALID, "no such raygen instance");
     if ((rc = end_event(c, &ep))) return rc;
     if (exact) HIPCHECK(c, read_back(0));
     for (uint32_t d = 0; d < max_depth; ++d) {
         const PrtRayBuf& in = c->rb[d & 1];
         const PrtRayBuf& out = c->rb[(d + 1) & 1];
         const uint32_t* front_count = c->d_counts + (size_t)d * PRT_CNT_STRIDE;
+        const PrtPrimary* prim_d = (compact && d == 0) ? &primary : nullptr;
         if (c->dsc.n_nodes) {  // only the front part of the buffer can hit a triangle
             if ((rc = begin_event(c, 1, &ep))) return rc;
-            if (c->variant == 0 || c->dsc.n_insts || !c->dsc.nodes) {  // placed copies / device-built trees: the 8-wide kernel only
-                PrtTravTuning tune = c->tune;
-                tune.probe_slot = d;
-                tune.perm = nullptr;
-                if (c->sort_rays && !(compact && d == 0) && (d > 0 || c->sampling.jitter || lens_on)) {
-                    // measurement aid (tools/sort_ab.py): the host needs the ray count, so this path synchronises; the sort
-                    // is timed as its own stage (scan_ms), the traversal that follows as usual
-                    uint32_t n_front = 0;
-                    HIPCHECK(c, hipMemcpyAsync(&n_front, front_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-                    HIPCHECK(c, hipStreamSynchronize(c->stream));
-                    if (n_front > 1u) {
-                        if (c->sort_entries < n_paths) {
-                            free_dev(c->d_sort);
-                            c->sort_entries = 0;
-                            c->sort_temp = prt_sort_rays_temp_bytes(n_paths);
-                            HIPCHECK(c, hipMalloc((void**)&c->d_sort, 4 * (size_t)n_paths * sizeof(uint32_t) + c->sort_temp));
-                            c->sort_entries = n_paths;
-                        }
-                        EventPair es{};
-                        if ((rc = begin_event(c, 4, &es))) return rc;
-                        uint32_t* q = c->d_sort;
-                        if (prt_sort_rays(c->stream, in.o, in.d, n_front, c->dsc.root_min, c->dsc.root_max, c->sort_rays, q, q + n_paths,
-                                          q + 2 * (size_t)n_paths, q + 3 * (size_t)n_paths, q + 4 * (size_t)n_paths, c->sort_temp))
-                            return fail(c, PRT_ERR_HIP, "ray sort failed");
-                        if ((rc = end_event(c, &es))) return rc;
-                        if (c->timing) HIPCHECK(c, hipEventRecord(ep.a, c->stream));  // the traversal's own time starts after the sort
-                        tune.perm = q + 3 * (size_t)n_paths;
-                    }
-                }
-                if (walk && d == 0)
-                    prt_launch_traverse(c->stream, c->dsc, in, c->d_counts + PRT_CNT_LIST, c->d_work, c->d_spill, tm.n_pix_local,
-                                        c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune, trav_stats, &primary_list);
-                else
-                    prt_launch_traverse(c->stream, c->dsc, in, front_count, c->d_work, c->d_spill, n_paths, c->hs.bvh.max_depth,
-                                        c->hs.bvh.max_stack4, tune, trav_stats, (compact && d == 0) ? &primary : nullptr);
-            }
+            PrtTravTuning tune = c->tune;
+            tune.probe_slot = d;
+            tune.perm = nullptr;
+            if (plan.walk8 && c->sort_rays && !prim_d && (d > 0 || c->sampling.jitter || f.lens))
+                if ((rc = sort_front_rays(c, in, front_count, n_paths, &ep, &tune))) return rc;
+            if (walk && d == 0)
+                walk_rays(c, in, c->d_counts + PRT_CNT_LIST, tm.n_pix_local, false, tune, trav_stats, &primary_list);
             else
-                prt_launch_intersect(c->stream, c->dsc, in, front_count, n_paths, stack_depth, c->variant, trav_stats);
+                walk_rays(c, in, front_count, n_paths, false, tune, trav_stats, prim_d);
             if ((rc = end_event(c, &ep))) return rc;
             ++c->stats.intersect_launches;
-            if (compact && d == 0) {
+            if (prim_d) {
                 // (a batch of ONE sample has nothing to share: k_shade rebuilds the hit itself, one launch less)
-                if (c->tune.primary_hit && S_cur > 1u) {  // (timed with the shade stage)
+                if (plan.primary_hit) {  // (timed with the shade stage)
                     if ((rc = begin_event(c, 2, &ep))) return rc;
                     prt_launch_primary_hit(c->stream, c->dsc, primary, in.hit, c->d_pix, c->d_counts);
                     if ((rc = end_event(c, &ep))) return rc;
@@ -744,51 +745,27 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
             n_rays_known = c->h_counts[64 * (size_t)d] + c->h_counts[64 * (size_t)d + 32];
             if (n_rays_known == 0u) break;  // every path has ended: the later bounces have nothing to do
         }
-        if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, c->d_counts, d, n_paths, c->d_shade_div, (compact && d == 0) ? &primary : nullptr);
+        if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, c->d_counts, d, n_paths, c->d_shade_div, prim_d);
         if ((rc = begin_event(c, 2, &ep))) return rc;
-        if (lit) {
-            if (texon)
-                c->shade_instance = prt_launch_shade_nee_tex(c->stream, c->dsc, dtex, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
-                                                             c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
-            else
-                c->shade_instance = prt_launch_shade_nee(c->stream, c->dsc, lt, in, out, c->lb, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
-                                                         c->sampling, n_rays_known, mesh_lights_on(c) ? &mlt : nullptr, envp);
-            if (lt.n_lights || (envon && (denv.t_all | denv.t_env))) {
-                // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
-                // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
-                const uint32_t* scount = c->d_counts + (size_t)d * PRT_CNT_STRIDE + 48u;
-                const uint32_t nmax = n_rays_known == 0xFFFFFFFFu ? n_paths : n_rays_known;
-                prt_launch_scan_prims_bounded(c->stream, c->dsc, c->lb.sh, scount, c->d_work, nmax);
-                if (c->dsc.n_nodes) {
-                    if (c->variant == 0 || c->dsc.n_insts || !c->dsc.nodes) {
-                        PrtTravTuning tune = c->tune;
-                        tune.perm = nullptr;
-                        prt_launch_occluded(c->stream, c->dsc, c->lb.sh, scount, c->d_work, c->d_spill, nmax, c->hs.bvh.max_depth,
-                                            c->hs.bvh.max_stack4, tune);
-                    } else {
-                        prt_launch_intersect(c->stream, c->dsc, c->lb.sh, scount, nmax, stack_depth, c->variant, nullptr);
-                    }
-                }
-                prt_launch_light_accum(c->stream, c->dsc, c->lb, scount, c->d_work, nmax);
-            }
-        } else if (texon) {
-            c->shade_instance = prt_launch_shade_tex(c->stream, c->dsc, dtex, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths,
-                                                     c->sampling, n_rays_known, envp);
-        } else {
-            c->shade_instance = prt_launch_shade(c->stream, c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, fuse,
-                                                 c->sampling, n_rays_known, (compact && d == 0) ? &primary : nullptr, envp);
+        const PrtShadeInst shade = d == 0 ? plan.shade0 : plan.shade;
+        const PrtShadeArgs sa{&c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, c->sampling, n_rays_known, prim_d,
+                              f.env ? &denv : nullptr, f.tex ? &dtex : nullptr, lit ? &lt : nullptr, (lit && f.mesh_lights) ? &mlt : nullptr,
+                              lit ? &c->lb : nullptr};
+        if (!prt_launch_shade(c->stream, shade, sa)) return fail(c, PRT_ERR_INVALID, "no such shade instance");
+        c->shade_instance = prt_shade_name(shade);
+        if (lit && (lt.n_lights || (f.env && (denv.t_all | denv.t_env)))) {
+            // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
+            // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
+            const uint32_t* scount = c->d_counts + (size_t)d * PRT_CNT_STRIDE + 48u;
+            const uint32_t nmax = n_rays_known == 0xFFFFFFFFu ? n_paths : n_rays_known;
+            prt_launch_scan_prims_bounded(c->stream, c->dsc, c->lb.sh, scount, c->d_work, nmax);
+            if (c->dsc.n_nodes) walk_rays(c, c->lb.sh, scount, nmax, true, c->tune, nullptr, nullptr);
+            prt_launch_light_accum(c->stream, c->dsc, c->lb, scount, c->d_work, nmax);
         }
         if ((rc = end_event(c, &ep))) return rc;
         if (exact && d + 1 < max_depth) HIPCHECK(c, read_back(d + 1));
     }
-    // film += the batch's samples (unless this is a measurement run) and per-depth ray counts from the paths' last
-    // segment indices
-    if ((rc = begin_event(c, 3, &ep))) return rc;
-    launch_accumulate(c, view, S_cur, max_depth, accumulate, lit, compact ? c->d_pix + tm.n_pix_local : nullptr);
-    if ((rc = end_event(c, &ep))) return rc;
-    if (accumulate && !listed) c->stats.samples += S_cur;  // (whole-film samples only)
-    HIPCHECK(c, hipGetLastError());
-    return PRT_OK;
+    return accumulate_batch();
 }
 
 // The one place that fills c->dsc: the compiled scene's scalars next to the context's device pointers (all null on a
@@ -2083,33 +2060,18 @@ static int enqueue_query(PrtContext* c, uint32_t n, const float* d_o, const floa
     if ((rc = ensure_counters(c))) return rc;
     if ((rc = ensure_spill(c))) return rc;
     uint32_t* cnt = c->d_counts + (size_t)(PRT_MAX_DEPTH + 1) * PRT_CNT_STRIDE;  // a counter slot the render loop never uses
-    const int stack_depth = c->hs.bvh.max_depth <= 31 ? 31 : 63;
-    const bool walk8 = c->variant == 0 || c->dsc.n_insts || !c->dsc.nodes;
     if (d_tmax) {
         // occlusion: every ray seeded with "miss at d2 = tmax^2", the analytic scan from that bound, the any-hit walk
         // (or, with another traversal variant forced, the closest hit, which k_occlusion_bytes compares with the bound)
         prt_launch_pack_occlusion_rays(c->stream, n, d_o, d_d, d_tmax, c->rb[0], cnt);
         prt_launch_scan_prims_bounded(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n);
-        if (c->dsc.n_nodes) {
-            if (walk8)
-                prt_launch_occluded(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->hs.bvh.max_depth,
-                                    c->hs.bvh.max_stack4, c->tune);
-            else
-                prt_launch_intersect(c->stream, c->dsc, c->rb[0], cnt, n, stack_depth, c->variant, nullptr);
-        }
-        prt_launch_occlusion_bytes(c->stream, c->dsc, n, c->rb[0], d_tmax, d_occ);
     } else {
         prt_launch_pack_rays(c->stream, n, d_o, d_d, c->rb[0], cnt);
         prt_launch_scan_prims(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n, nullptr);
-        if (c->dsc.n_nodes) {
-            if (walk8)
-                prt_launch_traverse(c->stream, c->dsc, c->rb[0], cnt, c->d_work, c->d_spill, n, c->hs.bvh.max_depth,
-                                    c->hs.bvh.max_stack4, c->tune, nullptr);
-            else
-                prt_launch_intersect(c->stream, c->dsc, c->rb[0], cnt, n, stack_depth, c->variant, nullptr);
-        }
-        prt_launch_hit_records(c->stream, c->dsc, n, c->rb[0], d_hits);
     }
+    if (c->dsc.n_nodes) walk_rays(c, c->rb[0], cnt, n, d_tmax != nullptr, c->tune, nullptr, nullptr);
+    if (d_tmax) prt_launch_occlusion_bytes(c->stream, c->dsc, n, c->rb[0], d_tmax, d_occ);
+    else prt_launch_hit_records(c->stream, c->dsc, n, c->rb[0], d_hits);
     HIPCHECK(c, hipGetLastError());
     return PRT_OK;
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/prt.h"
+#include "prt_route.h"      // the instance lists and the plan of a batch
 #include "prt_scene_pod.h"  // DevPrim, DevInstance
 
 struct f3 {
@@ -233,12 +234,25 @@ struct PrtLightBufs {
     unsigned long long* stats;  // [PRT_RAY_STAT_SLOTS][2]: shadow rays, occluded (block b adds to slot b mod SLOTS)
 };
 
-void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, uint32_t n_paths,
-                       uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
-                       uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix = nullptr,
-                       const DevEnv* env = nullptr,  // env: the instance with an environment image (never compact)
-                       bool primary_walk = false,    // compact only: write the front-pixel list into out.hd2 (PrtPrimary)
-                       const DevLens* lens = nullptr);  // lens: the instances with a thin lens (one full record per sample, never compact)
+// The three stage launchers of a batch.  Each takes the instance prt_plan_route (prt_route.h) chose and one argument struct;
+// the optional pointers are read only by the instances whose kernels take them (null otherwise).  false: no such instance.
+struct PrtRaygenArgs {
+    const DevScene* sc;
+    DevCamera cam;
+    PrtTileMap tm;
+    uint32_t n_paths, first_sample, seed, max_depth;
+    PrtRayBuf out;
+    float4* rad;
+    uint32_t* counts;
+    uint32_t* work;
+    PrtSampling sp;
+    float4* compact_pix;   // the compact instance: the pixel records (PrtPrimary.pix)
+    bool primary_walk;     // the compact instance: write the front-pixel list into out.hd2 (PrtPrimary)
+    const DevEnv* env;     // the instances with an environment image
+    const DevLens* lens;   // the instances with a thin lens (one full record per sample)
+    const uint32_t* list;  // k_raygen_list: the tiles of a PrtBatchView
+};
+bool prt_launch_raygen(hipStream_t st, PrtRaygenInst inst, const PrtRaygenArgs& a);
 void prt_launch_scan_prims(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                            uint32_t* work, uint32_t max_rays, unsigned long long* stats);
 void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
@@ -254,12 +268,23 @@ int prt_traverse_occupancy(const DevScene& sc, const PrtTravTuning& tune, int* b
 const char* prt_traverse_instance(const DevScene& sc, const PrtTravTuning& tune);
 void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                           uint32_t max_rays, int stack_depth, int variant, unsigned long long* stats);
-// The four shade launchers return the name of the instance they launched, spelled by the launch macro from its own template
-// arguments ("k_shade_tex<false, true, false>"): what prt_shade_instance reports
-const char* prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
-                             uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap,
-                             uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary = nullptr,
-                             const DevEnv* env = nullptr);  // env: the instance with an environment image (no fusion, no compact primaries)
+struct PrtShadeArgs {
+    const DevScene* sc;
+    PrtRayBuf in, out;
+    float4* rad;
+    uint32_t* counts;
+    uint32_t* work;
+    uint32_t depth, max_depth, cap;
+    PrtSampling sp;
+    uint32_t n_rays_known;             // the bounce's ray count if the host has it (0xFFFFFFFF: the grid is sized for `cap`)
+    const PrtPrimary* primary;         // bounce 0 of compact primary rays
+    const DevEnv* env;
+    const DevTex* tex;
+    const DevLights* lights;           // lighting modes: the shade step takes a light sample per Lambertian vertex (shadow rays
+    const DevMeshLights* mesh_lights;  // into lb->sh, counted in counts[depth * stride + 48]); mesh_lights: triangle lights
+    const PrtLightBufs* lb;
+};
+bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a);
 // diagnostic: per-wave material mix of what k_shade of bounce `iter` is about to shade (16 words per bounce in `out`)
 void prt_launch_shade_divstats(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* counts, uint32_t iter,
                                uint32_t cap, unsigned long long* out, const PrtPrimary* primary = nullptr);
@@ -267,9 +292,21 @@ void prt_launch_shade_divstats(hipStream_t st, const DevScene& sc, const PrtRayB
 // first traversal and the first k_shade of a batch
 void prt_launch_primary_hit(hipStream_t st, const DevScene& sc, const PrtPrimary& pr, const uint32_t* hit, float4* pix,
                             const uint32_t* counts);
-void prt_launch_accumulate(hipStream_t st, const float4* rad, float4* film_local, const PrtTileMap& tm, uint32_t S,
-                           uint32_t max_depth, bool update_film, unsigned long long* ray_stats,
-                           const float4* pix_end = nullptr);
+// film += the batch's samples.  k_accumulate (pix_end optional), k_accumulate_lit (rad + lrad), or k_accumulate_stat<LIT, LIST>,
+// which also adds every sample's luminance and its square to stat[pixel] = {A, Q} and with `list` scatters pixels through it.
+struct PrtAccumulateArgs {
+    const float4* rad;
+    const float4* lrad;  // the paths' light radiance (lit instances)
+    float4* film_local;
+    float2* stat;
+    PrtTileMap tm;
+    uint32_t S, max_depth;
+    bool update_film;
+    unsigned long long* ray_stats;
+    const float4* pix_end;  // compact primary rays: what a pixel's paths deliver if they end with their primary ray
+    const uint32_t* list;
+};
+bool prt_launch_accumulate(hipStream_t st, PrtAccumulateInst inst, const PrtAccumulateArgs& a);
 void prt_launch_resolve(hipStream_t st, const float4* gathered, uint32_t world, uint32_t stride, uint32_t W,
                         uint32_t H, float* rgb, float* weight);
 void prt_launch_tonemap(hipStream_t st, const float* rgb, const float* weight, uint32_t n_pix, float exposure,
@@ -295,50 +332,23 @@ void prt_launch_occlusion_bytes(hipStream_t st, const DevScene& sc, uint32_t n, 
 void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, const float* in_d, const PrtHit* hits,
                              uint32_t* rng_io, uint32_t* scattered, float* atten, float* emitted, float* o_out,
                              float* d_out);
-// lighting modes (PrtLighting): the shade step with a light sample per Lambertian vertex (shadow rays into lb.sh, counted
-// in counts[iter * stride + 48]); after the shadow walk, the unoccluded contributions into lb.lrad (and the traversal
-// cursors reset for the next bounce); the film accumulation of rad + lrad
-const char* prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
-                                 const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
-                                 uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
-                                 const DevMeshLights* ml = nullptr,  // ml: the instances that sample triangle lights
-                                 const DevEnv* env = nullptr);       // env: the instances with an environment light
+// lighting modes (PrtLighting): after the shadow walk, the unoccluded contributions into lb.lrad (and the traversal cursors
+// reset for the next bounce)
 void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBufs& lb, const uint32_t* count_ptr,
                             uint32_t* work, uint32_t max_rays);
-void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, const PrtTileMap& tm,
-                               uint32_t S, uint32_t max_depth, bool update_film, unsigned long long* ray_stats);
 void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
                                   const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light,
                                   const DevMeshLights* ml = nullptr, const DevEnv* env = nullptr);
 // prt_environment_eval: lookup of n directions (3 floats each): rgb (3 floats), texel, pdf_w; any output may be null
 void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, const float* dirs, float* rgb, uint32_t* texel,
                                  float* pdf_w);
-// Image textures: the shade steps of a scene with a texture binding (env / ml may be null; never fused, never compact),
-// and the two function-level kernels that run the same device functions
-const char* prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
-                                 uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp,
-                                 uint32_t n_rays_known, const DevEnv* env);
-const char* prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const DevLights& lt, const PrtRayBuf& in,
-                                     const PrtRayBuf& out, const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work,
-                                     uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
-                                     const DevMeshLights* ml, const DevEnv* env);
+// Image textures: the two function-level kernels that run the device functions of the texture shade instances
 // prt_texture_eval: texture_lookup for n (texture, uv) pairs
 void prt_launch_texture_eval(hipStream_t st, const DevTex& tex, uint32_t n, const uint32_t* texture, const float* uv, float* rgb);
 // prt_hit_uv: after the closest-hit pipeline on `in`: uv (2 floats) and albedo (3 floats) of every ray's hit; either may be null
 void prt_launch_hit_uv(hipStream_t st, const DevScene& sc, const DevTex& tex, uint32_t n, const PrtRayBuf& in, float* uv, float* albedo);
 
-// Film statistics and adaptive sampling (include/prt.h "Film statistics and adaptive sampling"): kernels of their own; the
-// launchers above and their kernels stay as they are.
-// k_accumulate_stat<LIT, LIST>: k_accumulate (lrad = null, pix_end optional) or k_accumulate_lit (lrad given) that also adds
-// every sample's luminance and its square to stat[pixel] = {A, Q}; with `list` (PrtBatchView) pixels are scattered through it.
-void prt_launch_accumulate_stat(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, float2* stat,
-                                const PrtTileMap& tm, uint32_t S, uint32_t max_depth, bool update_film,
-                                unsigned long long* ray_stats, const float4* pix_end, const uint32_t* list);
-// k_raygen_list<JITTER, ABVH, ENV, LENS>: full ray records for the tiles of `list`, sampling options compiled in
-void prt_launch_raygen_list(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, const uint32_t* list,
-                            uint32_t n_paths, uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad,
-                            uint32_t* counts, uint32_t* work, uint32_t max_depth, const PrtSampling& sp, const DevEnv* env,
-                            const DevLens* lens);
+// Film statistics and adaptive sampling (include/prt.h "Film statistics and adaptive sampling")
 // k_tile_select + k_tile_compact: of the n_in tiles of `prev` (null: local tiles 0 .. n_in - 1) those with an unconverged pixel
 // (prt_adaptive.h), in the same (ascending) order, into `out`; their number into *count.  flags: n_in words of scratch.
 void prt_launch_tile_select(hipStream_t st, const float4* film_local, const float2* stat, const PrtTileMap& tm, const uint32_t* prev,

@@ -3957,60 +3957,46 @@ __global__ void k_environment_eval(DevEnv env, uint32_t n, const float* __restri
 // ---------------------------------------------------------------------------------------------------------
 static inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
 
-void prt_launch_raygen(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, uint32_t n_paths,
-                       uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad, uint32_t* counts,
-                       uint32_t* work, uint32_t max_depth, const PrtSampling& sp, float4* compact_pix, const DevEnv* env,
-                       bool primary_walk, const DevLens* lens) {
-    const uint32_t S = tm.n_pix_local ? n_paths / tm.n_pix_local : 0u;
-    const uint32_t group = (sp.jitter || lens) ? (uint32_t)RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
-    const dim3 grid((tm.n_pix_local + PRODUCER_BLOCK - 1) / PRODUCER_BLOCK, (S + group - 1) / group);
-    if (lens) {  // a thin lens: the per-sample instances of its own (full ray records, never compact)
-#define PRT_RAYGEN_LENS(J, AB)                                                                                                  \
-    do {                                                                                                                        \
-        if (env)                                                                                                                \
-            hipLaunchKernelGGL((k_raygen_lens_env<J, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, *env, *lens, cam, tm, S,       \
-                               first_sample, seed, out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp);   \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((k_raygen_lens<J, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, *lens, cam, tm, S, first_sample,   \
-                               seed, out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp);                 \
-    } while (0)
-        if (sc.abvh_nodes) {
-            if (sp.jitter) PRT_RAYGEN_LENS(true, true); else PRT_RAYGEN_LENS(false, true);
-        } else {
-            if (sp.jitter) PRT_RAYGEN_LENS(true, false); else PRT_RAYGEN_LENS(false, false);
-        }
-#undef PRT_RAYGEN_LENS
-        return;
+// An optional argument that a kernel takes by value: the caller's, or an empty one for the instances that never read it.
+template <class T>
+static const T& or_empty(const T* p) {
+    static const T none{};
+    return p ? *p : none;
+}
+
+// The three stage launchers of a batch: `inst` is the instance prt_plan_route (prt_route.h) chose, the `case`s are that
+// header's instance lists, so an instance's name and its launch are one spelling.  false: no such instance.
+bool prt_launch_raygen(hipStream_t st, PrtRaygenInst inst, const PrtRaygenArgs& a) {
+    const uint32_t S = a.tm.n_pix_local ? a.n_paths / a.tm.n_pix_local : 0u;
+    const uint32_t group = (a.sp.jitter || a.lens) ? (uint32_t)RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
+    const dim3 grid((a.tm.n_pix_local + PRODUCER_BLOCK - 1) / PRODUCER_BLOCK, (S + group - 1) / group);
+    const DevScene& sc = *a.sc;
+    const DevEnv& e = or_empty(a.env);
+    const DevLens& l = or_empty(a.lens);
+#define PRT_RAYGEN_HEAD a.cam, a.tm, S, a.first_sample, a.seed, a.out.o, a.out.d, a.out.t, a.out.hit
+#define PRT_RAYGEN_TAIL a.rad, a.counts, a.work, a.max_depth, a.sp
+#define PRT_RAYGEN_ARGS_PLAIN sc, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL, nullptr
+    // (the compact instance stores nothing in hit / hd2 per ray slot: its hd2 argument is the front-pixel list, or null)
+#define PRT_RAYGEN_ARGS_COMPACT sc, PRT_RAYGEN_HEAD, a.primary_walk ? a.out.hd2 : nullptr, PRT_RAYGEN_TAIL, a.compact_pix
+#define PRT_RAYGEN_ARGS_ENV sc, e, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL
+#define PRT_RAYGEN_ARGS_LENS sc, l, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL
+#define PRT_RAYGEN_ARGS_LENS_ENV sc, e, l, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL
+#define PRT_RAYGEN_ARGS_LIST sc, e, l, a.cam, a.tm, a.list, S, a.first_sample, a.seed, a.out.o, a.out.d, a.out.t, a.out.hit, a.out.hd2, PRT_RAYGEN_TAIL
+#define PRT_RAYGEN_CASE(sig, kernel, tag, ...) \
+    case PRT_INST(kernel, tag): hipLaunchKernelGGL((kernel<__VA_ARGS__>), grid, dim3(PRODUCER_BLOCK), 0, st, PRT_RAYGEN_ARGS_##sig); return true;
+    switch (inst) {
+        PRT_RAYGEN_INSTANCES(PRT_RAYGEN_CASE)
+        default: return false;
     }
-    if (env) {
-#define PRT_RAYGEN_ENV(J, AB)                                                                                           \
-    hipLaunchKernelGGL((k_raygen_env<J, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, *env, cam, tm, S, first_sample, seed, \
-                       out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp)
-        if (sc.abvh_nodes) {
-            if (sp.jitter) PRT_RAYGEN_ENV(true, true); else PRT_RAYGEN_ENV(false, true);
-        } else {
-            if (sp.jitter) PRT_RAYGEN_ENV(true, false); else PRT_RAYGEN_ENV(false, false);
-        }
-#undef PRT_RAYGEN_ENV
-        return;
-    }
-#define PRT_RAYGEN(J, SA, AB)                                                                                       \
-    hipLaunchKernelGGL((k_raygen<J, SA, AB>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, cam, tm, S, first_sample, seed,  \
-                       out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp, nullptr)
-    const bool sa = sp.rr_depth != 0u || sp.clamp > 0.0f;
-    if (sc.abvh_nodes) {  // many analytic primitives: the general instances with the BVH scan
-        if (sp.jitter) PRT_RAYGEN(true, true, true); else PRT_RAYGEN(false, true, true);
-    } else if (sp.jitter) {
-        if (sa) PRT_RAYGEN(true, true, false); else PRT_RAYGEN(true, false, false);
-    } else if (compact_pix && !sa) {
-        // (the compact instance stores nothing in hit / hd2 per ray slot: its hd2 argument is the front-pixel list, or null)
-        hipLaunchKernelGGL((k_raygen<false, false, false, true>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, cam, tm, S, first_sample,
-                           seed, out.o, out.d, out.t, out.hit, primary_walk ? out.hd2 : nullptr, rad, counts, work, max_depth, sp,
-                           compact_pix);
-    } else {
-        if (sa) PRT_RAYGEN(false, true, false); else PRT_RAYGEN(false, false, false);
-    }
-#undef PRT_RAYGEN
+#undef PRT_RAYGEN_CASE
+#undef PRT_RAYGEN_ARGS_LIST
+#undef PRT_RAYGEN_ARGS_LENS_ENV
+#undef PRT_RAYGEN_ARGS_LENS
+#undef PRT_RAYGEN_ARGS_ENV
+#undef PRT_RAYGEN_ARGS_COMPACT
+#undef PRT_RAYGEN_ARGS_PLAIN
+#undef PRT_RAYGEN_TAIL
+#undef PRT_RAYGEN_HEAD
 }
 
 void prt_launch_scan_prims(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
@@ -4067,19 +4053,49 @@ const char* prt_traverse_instance(const DevScene& sc, const PrtTravTuning& tune)
     }
 }
 
-void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
-                         uint32_t* work, uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4,
-                         const PrtTravTuning& tune_in, unsigned long long* stats, const PrtPrimary* primary) {
+// What a walk of max_rays rays launches with, closest-hit (prt_launch_traverse) or any-hit (prt_launch_occluded) alike: the
+// kind, the tunables with their "auto" values resolved, the grid, and for the 8-wide instances the 5-wave grid and tunables,
+// the stack entries and whether the overflow list is re-walked.
+struct T8Launch {
+    PrtT8Kind kind;
+    PrtTravTuning tune, t5;  // t5: the lean instance's (5 waves per SIMD)
+    uint32_t grid, grid5;    // grid5: 5 instead of 4 resident blocks per CU
+    uint32_t stack_l;
+    bool rewalk;             // overflow list -> the spill-capable 4-wide instance
+};
+static T8Launch t8_resolve(const DevScene& sc, const PrtTravTuning& tune_in, uint32_t max_rays) {
+    T8Launch r;
+    r.kind = t8_kind(sc, tune_in);
+    r.tune = t8_tuning(sc, tune_in);
     // exit_max "auto" (0xFFFFFFFF, the context's default): the two-level instance leaves its node loop at <= 32 walkers
     // (its lanes wait for level switches that the wave does together; C5I +4.4 % against 16, gpurun_out/r3_sweep_C5I_b.log),
     // every other instance at <= 16
-    PrtTravTuning tune = t8_tuning(sc, tune_in);
-    if (tune.exit_max == 0xFFFFFFFFu) tune.exit_max = t8_kind(sc, tune_in) == T8_INST12_4 ? 32u : 16u;
+    if (r.tune.exit_max == 0xFFFFFFFFu) r.tune.exit_max = r.kind == T8_INST12_4 ? 32u : 16u;
     // tri_min "auto" (0, the context's default): a triangle phase starts after 24 queueing lane-steps, but after 12 on one-level
     // trees far beyond the caches (one node per 128-B line: C5 +1.7 %; 16: +0.8 to +1.9 %), whose walks gain more from an earlier
     // culling bound than a phase's fixed part costs.  On trees the caches hold 12 / 16 cost 0.5-2 % (C2, C3), and the two-level
     // instance at its exit_max of 32 is best at 24 too (16: -1.5 %).  tools/sweep.py, TUNING.md
-    if (tune.tri_min == 0u) tune.tri_min = (t8_kind(sc, tune_in) != T8_INST12_4 && sc.node_stride == 8u) ? 12u : 24u;
+    if (r.tune.tri_min == 0u) r.tune.tri_min = (r.kind != T8_INST12_4 && sc.node_stride == 8u) ? 12u : 24u;
+    uint32_t g = r.tune.grid_blocks;
+    const uint32_t need_blocks = blocks_for(max_rays);
+    if (g > need_blocks) g = need_blocks;
+    if (g == 0) g = 1;
+    r.grid = g;
+    r.grid5 = g == r.tune.grid_blocks ? g + g / 4u : g;
+    r.stack_l = r.kind == T8_INST12_4 ? 12u : r.kind == T8_WIDE11_5 ? 11u : r.kind == T8_LEAN8_5 ? 8u : 15u;
+    // (the two-level instance has no overflow list: a stack overflow is an error, the host checks the depths)
+    const bool overflow = r.kind != T8_INST12_4 && (r.tune.stack_cap != 0u || sc.depth8 > r.stack_l + 1u);
+    r.t5 = r.tune;
+    if (overflow) r.t5.steal = 0u;  // (a helper cannot hand a ray to the overflow list)
+    r.rewalk = overflow && sc.nodes4;
+    return r;
+}
+
+void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
+                         uint32_t* work, uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4,
+                         const PrtTravTuning& tune_in, unsigned long long* stats, const PrtPrimary* primary) {
+    const T8Launch r = t8_resolve(sc, tune_in, max_rays);
+    const PrtTravTuning& tune = r.tune;
 #ifdef PRT_PROBE_REBOUND
     // diagnostic build (tools/bounce_stats.py --rebound): the instrumented launch is preceded by a plain one that leaves
     // every ray's FINAL hit distance as its initial culling bound, so the instrumented walk's visit counts are those of a
@@ -4089,11 +4105,7 @@ void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
         hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
     }
 #endif
-    uint32_t g = tune.grid_blocks;
-    const uint32_t need_blocks = blocks_for(max_rays);
-    if (g > need_blocks) g = need_blocks;
-    if (g == 0) g = 1;
-    const dim3 grid(g), block(256);
+    const dim3 grid(r.grid), block(256);
     uint32_t* ovf = work + 512;  // [0] = count, [1..] = ray slots that overflowed the LDS stack
     const uint32_t* no_list = nullptr;
 #define PRT_LAUNCH_T(KERNEL, L, W, MODE, GRID, COUNT, LIST)                                                        \
@@ -4105,7 +4117,7 @@ void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
             hipLaunchKernelGGL((KERNEL<L, W, MODE, false>), GRID, block, 0, st, sc, in.o, in.d, in.hit, in.hd2,    \
                                COUNT, work, spill, LIST, ovf, tune, stats);                                        \
     } while (0)
-    const PrtT8Kind kind = t8_kind(sc, tune);
+    const PrtT8Kind kind = r.kind;
     if (kind != T8_NONE) {  // (device-built scenes only have the 8-wide tree)
         // default: compressed 8-wide tree; a ray needs at most depth8 - 1 stacked node groups.  15 entries at
         // 4 waves/SIMD or 11 entries at 5 waves/SIMD (tune.stack_lds == 5); deeper rays take the overflow list.
@@ -4128,13 +4140,11 @@ void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
         // force one for A/B runs
         // (deeper host-built trees: rays that need more than 8 entries go through the overflow list to the 4-wide
         // spill-capable instance; C5, 11 levels: deepest stack 8, no such ray)
-        const uint32_t stack_l = kind == T8_WIDE11_5 ? 11u : kind == T8_LEAN8_5 ? 8u : 15u;
         if (kind == T8_WIDE11_5) {
             PRT_LAUNCH_8(11, 5, false);
         } else if (kind == T8_LEAN8_5) {
-            const dim3 grid5(g == tune.grid_blocks ? g + g / 4u : g);  // 5 instead of 4 resident blocks per CU
-            PrtTravTuning t5 = tune;
-            if (tune.stack_cap != 0u || sc.depth8 > stack_l + 1u) t5.steal = 0u;  // (a helper cannot hand a ray to the overflow list)
+            const dim3 grid5(r.grid5);
+            const PrtTravTuning& t5 = r.t5;
             if (stats && primary)
                 hipLaunchKernelGGL((k_traverse8_persistent<8, 5, true, false, true, true>), grid5, block, 0, st, sc, in.o, in.d,
                                    in.hit, in.hd2, count_ptr, work, ovf, t5, stats, *primary, PrtPathArgs{});
@@ -4153,7 +4163,7 @@ void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
 #undef PRT_LAUNCH_8
         // overflow list -> the spill-capable 4-wide instance.  Not launched when the tree is too shallow for any ray to
         // overflow (C3: 9 levels = 8 stacked groups at most): two tiny launches and their gaps are ~12 us per bounce
-        if (sc.nodes4 && (tune.stack_cap != 0u || sc.depth8 > stack_l + 1u)) {
+        if (r.rewalk) {
             hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
             PRT_LAUNCH_T(k_traverse4_persistent, 27, 5, 1, dim3(8), ovf, ovf + 1);
         }
@@ -4198,44 +4208,28 @@ void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
 // without the 8-wide tree (or with another one forced): the closest-hit walk from the seeded bound.
 void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr, uint32_t* work,
                          uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune_in) {
-    const PrtT8Kind kind = t8_kind(sc, tune_in);
-    if (kind == T8_NONE) {
+    if (t8_kind(sc, tune_in) == T8_NONE) {
         prt_launch_traverse(st, sc, in, count_ptr, work, spill, max_rays, tree_depth, stack4, tune_in, nullptr);
         return;
     }
-    PrtTravTuning tune = t8_tuning(sc, tune_in);  // the "auto" values exactly as prt_launch_traverse resolves them
-    if (tune.exit_max == 0xFFFFFFFFu) tune.exit_max = kind == T8_INST12_4 ? 32u : 16u;
-    if (tune.tri_min == 0u) tune.tri_min = (kind != T8_INST12_4 && sc.node_stride == 8u) ? 12u : 24u;
-    tune.perm = nullptr;
-    uint32_t g = tune.grid_blocks;
-    const uint32_t need_blocks = blocks_for(max_rays);
-    if (g > need_blocks) g = need_blocks;
-    if (g == 0) g = 1;
-    const dim3 grid(g), block(256);
+    PrtTravTuning tune_o = tune_in;
+    tune_o.perm = nullptr;
+    const T8Launch r = t8_resolve(sc, tune_o, max_rays);
+    const dim3 block(256);
     uint32_t* ovf = work + 512;
 #define PRT_LAUNCH_O(L, W, IN, LN, GRID, TUNE)                                                                       \
-    hipLaunchKernelGGL((k_occluded8_persistent<L, W, IN, LN>), GRID, block, 0, st, sc, in.o, in.d, in.hit, in.hd2,  \
+    hipLaunchKernelGGL((k_occluded8_persistent<L, W, IN, LN>), dim3(GRID), block, 0, st, sc, in.o, in.d, in.hit, in.hd2,  \
                        count_ptr, work, ovf, TUNE)
-    if (kind == T8_INST12_4) {  // a stack overflow is an error (prt_synchronize / the host form report it)
-        PRT_LAUNCH_O(12, 4, true, false, grid, tune);
-        return;
-    }
-    const uint32_t stack_l = kind == T8_WIDE11_5 ? 11u : kind == T8_LEAN8_5 ? 8u : 15u;
-    if (kind == T8_WIDE11_5) {
-        PRT_LAUNCH_O(11, 5, false, false, grid, tune);
-    } else if (kind == T8_LEAN8_5) {
-        const dim3 grid5(g == tune.grid_blocks ? g + g / 4u : g);
-        PrtTravTuning t5 = tune;
-        if (tune.stack_cap != 0u || sc.depth8 > stack_l + 1u) t5.steal = 0u;
-        PRT_LAUNCH_O(8, 5, false, true, grid5, t5);
-    } else {
-        PRT_LAUNCH_O(15, 4, false, false, grid, tune);
-    }
+    // (two-level: a stack overflow is an error; prt_synchronize / the host form report it)
+    if (r.kind == T8_INST12_4) PRT_LAUNCH_O(12, 4, true, false, r.grid, r.tune);
+    else if (r.kind == T8_WIDE11_5) PRT_LAUNCH_O(11, 5, false, false, r.grid, r.tune);
+    else if (r.kind == T8_LEAN8_5) PRT_LAUNCH_O(8, 5, false, true, r.grid5, r.t5);
+    else PRT_LAUNCH_O(15, 4, false, false, r.grid, r.tune);
 #undef PRT_LAUNCH_O
-    if (sc.nodes4 && (tune.stack_cap != 0u || sc.depth8 > stack_l + 1u)) {
+    if (r.rewalk) {
         hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
         hipLaunchKernelGGL((k_traverse4_persistent<27, 5, 1, false>), dim3(8), block, 0, st, sc, in.o, in.d, in.hit, in.hd2,
-                           ovf, work, spill, ovf + 1, ovf, tune, (unsigned long long*)nullptr);
+                           ovf, work, spill, ovf + 1, ovf, r.tune, (unsigned long long*)nullptr);
     }
 }
 
@@ -4298,52 +4292,44 @@ void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& i
 #undef PRT_LAUNCH_I
 }
 
-const char* prt_launch_shade(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
-                      uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap,
-                      uint32_t fuse_max, const PrtSampling& sp, uint32_t n_rays_known, const PrtPrimary* primary, const DevEnv* env) {
+bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a) {
     // n_rays_known: the ray count of this bounce if the host has it already (0xFFFFFFFF: size the grid for `cap`)
-    const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
+    const uint32_t n_for_grid = a.n_rays_known == 0xFFFFFFFFu ? a.cap : (a.n_rays_known ? a.n_rays_known : 1u);
     const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
-    // (every launch macro of the shade launchers names its instance from the very template arguments it launches with:
-    // prt_shade_instance reports that string, so the name and the launch cannot drift apart)
-    const char* name = "";
-    if (env) {
-#define PRT_SHADE_ENV(IN, AB)                                                                                              \
-    do {                                                                                                                   \
-        name = "k_shade_env<" #IN ", " #AB ">";                                                                           \
-        hipLaunchKernelGGL((k_shade_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, *env, in.o, in.d, in.t, in.hit, out.o, out.d, \
-                           out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp);                         \
-    } while (0)
-        if (sc.abvh_nodes) {
-            if (sc.n_insts) PRT_SHADE_ENV(true, true); else PRT_SHADE_ENV(false, true);
-        } else {
-            if (sc.n_insts) PRT_SHADE_ENV(true, false); else PRT_SHADE_ENV(false, false);
-        }
-#undef PRT_SHADE_ENV
-        return name;
+    const DevScene& sc = *a.sc;
+    const PrtPrimary& pr = or_empty(a.primary);
+    const DevEnv& e = or_empty(a.env);
+    const DevTex& tex = or_empty(a.tex);
+    const DevLights& lt = or_empty(a.lights);
+    const DevMeshLights& m = or_empty(a.mesh_lights);
+    const PrtLightBufs& lb = or_empty(a.lb);
+#define PRT_SHADE_RAYS a.in.o, a.in.d, a.in.t, a.in.hit, a.out.o, a.out.d, a.out.t, a.out.hit, a.out.hd2
+#define PRT_SHADE_TAIL a.rad, a.counts, a.work, a.depth, a.max_depth, a.cap, a.sp
+#define PRT_SHADE_ARGS_PLAIN sc, PRT_SHADE_RAYS, PRT_SHADE_TAIL, pr
+#define PRT_SHADE_ARGS_ENV sc, e, PRT_SHADE_RAYS, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_TEX sc, tex, e, PRT_SHADE_RAYS, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_NEE sc, lt, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_NEE_ENV sc, lt, e, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_NEE_MESH sc, lt, m, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_NEE_MESH_ENV sc, lt, m, e, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_NEE_TEX sc, tex, lt, m, e, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
+#define PRT_SHADE_CASE(sig, kernel, tag, ...) \
+    case PRT_INST(kernel, tag): hipLaunchKernelGGL((kernel<__VA_ARGS__>), grid, dim3(SHADE_BLOCK), 0, st, PRT_SHADE_ARGS_##sig); return true;
+    switch (inst) {
+        PRT_SHADE_INSTANCES(PRT_SHADE_CASE)
+        default: return false;
     }
-#define PRT_SHADE(F, SA, IN, AB)                                                                                        \
-    do {                                                                                                                \
-        name = "k_shade<" #F ", " #SA ", " #IN ", " #AB ", false>";                                                     \
-        hipLaunchKernelGGL((k_shade<F, SA, IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, in.o, in.d, in.t, in.hit, out.o, \
-                           out.d, out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp, PrtPrimary{}); \
-    } while (0)
-    const bool sa = sp.rr_depth != 0u || sp.clamp > 0.0f;
-    if (primary) {  // (the host only asks for this with the default instance's conditions: no placed copies, no primitive BVH, no sampling options, no fusion)
-        name = "k_shade<0, false, false, false, true>";
-        hipLaunchKernelGGL((k_shade<0, false, false, false, true>), grid, dim3(SHADE_BLOCK), 0, st, sc, in.o, in.d, in.t, in.hit,
-                           out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp, *primary);
-    } else if (sc.abvh_nodes) {  // many analytic primitives: general instances with the BVH scan
-        if (sc.n_insts) PRT_SHADE(0, true, true, true); else PRT_SHADE(0, true, false, true);
-    } else if (sc.n_insts) {  // scenes with placed mesh copies: one general instance
-        PRT_SHADE(0, true, true, false);
-    } else if (fuse_max) {
-        if (sa) PRT_SHADE(1, true, false, false); else PRT_SHADE(1, false, false, false);
-    } else {
-        if (sa) PRT_SHADE(0, true, false, false); else PRT_SHADE(0, false, false, false);
-    }
-#undef PRT_SHADE
-    return name;
+#undef PRT_SHADE_CASE
+#undef PRT_SHADE_ARGS_NEE_TEX
+#undef PRT_SHADE_ARGS_NEE_MESH_ENV
+#undef PRT_SHADE_ARGS_NEE_MESH
+#undef PRT_SHADE_ARGS_NEE_ENV
+#undef PRT_SHADE_ARGS_NEE
+#undef PRT_SHADE_ARGS_TEX
+#undef PRT_SHADE_ARGS_ENV
+#undef PRT_SHADE_ARGS_PLAIN
+#undef PRT_SHADE_TAIL
+#undef PRT_SHADE_RAYS
 }
 
 void prt_launch_shade_divstats(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* counts, uint32_t iter,
@@ -4357,11 +4343,26 @@ void prt_launch_primary_hit(hipStream_t st, const DevScene& sc, const PrtPrimary
     hipLaunchKernelGGL(k_primary_hit, dim3(blocks_for(pr.n_pix_local)), dim3(256), 0, st, sc, pr, hit, pix, counts);
 }
 
-void prt_launch_accumulate(hipStream_t st, const float4* rad, float4* film_local, const PrtTileMap& tm, uint32_t S,
-                           uint32_t max_depth, bool update_film, unsigned long long* ray_stats, const float4* pix_end) {
-    const uint32_t nb = blocks_for(tm.n_pix_local ? tm.n_pix_local : 1);
-    hipLaunchKernelGGL(k_accumulate, dim3(nb < 8192u ? nb : 8192u), dim3(256), 0, st, rad, film_local, tm, S, max_depth,
-                       update_film ? 1 : 0, ray_stats, pix_end);
+bool prt_launch_accumulate(hipStream_t st, PrtAccumulateInst inst, const PrtAccumulateArgs& a) {
+    const uint32_t nb = blocks_for(a.tm.n_pix_local ? a.tm.n_pix_local : 1);
+    const dim3 grid(nb < 8192u ? nb : 8192u);
+    const int upd = a.update_film ? 1 : 0;
+#define PRT_ACC_ARGS_PLAIN a.rad, a.film_local, a.tm, a.S, a.max_depth, upd, a.ray_stats, a.pix_end
+#define PRT_ACC_ARGS_LIT a.rad, a.lrad, a.film_local, a.tm, a.S, a.max_depth, upd, a.ray_stats
+#define PRT_ACC_ARGS_STAT a.rad, a.lrad, a.film_local, a.stat, a.tm, a.S, a.max_depth, upd, a.ray_stats, a.pix_end, a.list
+#define PRT_ACC_CASE_N(sig, kernel) \
+    case PRT_I_##kernel: hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, PRT_ACC_ARGS_##sig); return true;
+#define PRT_ACC_CASE_T(sig, kernel, tag, ...) \
+    case PRT_INST(kernel, tag): hipLaunchKernelGGL((kernel<__VA_ARGS__>), grid, dim3(256), 0, st, PRT_ACC_ARGS_##sig); return true;
+    switch (inst) {
+        PRT_ACCUMULATE_INSTANCES(PRT_ACC_CASE_N, PRT_ACC_CASE_T)
+        default: return false;
+    }
+#undef PRT_ACC_CASE_T
+#undef PRT_ACC_CASE_N
+#undef PRT_ACC_ARGS_STAT
+#undef PRT_ACC_ARGS_LIT
+#undef PRT_ACC_ARGS_PLAIN
 }
 
 void prt_launch_resolve(hipStream_t st, const float4* gathered, uint32_t world, uint32_t stride, uint32_t W,
@@ -4418,79 +4419,9 @@ void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, con
                        atten, emitted, o_out, d_out);
 }
 
-const char* prt_launch_shade_nee(hipStream_t st, const DevScene& sc, const DevLights& lt, const PrtRayBuf& in, const PrtRayBuf& out,
-                          const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work, uint32_t depth,
-                          uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known, const DevMeshLights* ml,
-                          const DevEnv* env) {
-    const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
-    const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
-    const char* name = "";
-    if (env) {
-#define PRT_SHADE_NEE_ENV(IN, AB)                                                                                            \
-    do {                                                                                                                     \
-        name = "k_shade_nee_env<" #IN ", " #AB ">";                                                                         \
-        hipLaunchKernelGGL((k_shade_nee_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *env, in.o, in.d, in.t, in.hit, out.o, \
-                           out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);                \
-    } while (0)
-#define PRT_SHADE_NEE_MESH_ENV(IN, AB)                                                                                        \
-    do {                                                                                                                      \
-        name = "k_shade_nee_mesh_env<" #IN ", " #AB ">";                                                                     \
-        hipLaunchKernelGGL((k_shade_nee_mesh_env<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *ml, *env, in.o, in.d, in.t, in.hit, \
-                           out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);          \
-    } while (0)
-        if (ml) {
-            if (sc.abvh_nodes) {
-                if (sc.n_insts) PRT_SHADE_NEE_MESH_ENV(true, true); else PRT_SHADE_NEE_MESH_ENV(false, true);
-            } else {
-                if (sc.n_insts) PRT_SHADE_NEE_MESH_ENV(true, false); else PRT_SHADE_NEE_MESH_ENV(false, false);
-            }
-        } else if (sc.abvh_nodes) {
-            if (sc.n_insts) PRT_SHADE_NEE_ENV(true, true); else PRT_SHADE_NEE_ENV(false, true);
-        } else {
-            if (sc.n_insts) PRT_SHADE_NEE_ENV(true, false); else PRT_SHADE_NEE_ENV(false, false);
-        }
-#undef PRT_SHADE_NEE_MESH_ENV
-#undef PRT_SHADE_NEE_ENV
-        return name;
-    }
-#define PRT_SHADE_NEE(IN, AB)                                                                                             \
-    do {                                                                                                                  \
-        name = "k_shade_nee<" #IN ", " #AB ">";                                                                          \
-        hipLaunchKernelGGL((k_shade_nee<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, in.o, in.d, in.t, in.hit, out.o, \
-                           out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);             \
-    } while (0)
-#define PRT_SHADE_NEE_MESH(IN, AB)                                                                                            \
-    do {                                                                                                                      \
-        name = "k_shade_nee_mesh<" #IN ", " #AB ">";                                                                         \
-        hipLaunchKernelGGL((k_shade_nee_mesh<IN, AB>), grid, dim3(SHADE_BLOCK), 0, st, sc, lt, *ml, in.o, in.d, in.t, in.hit, \
-                           out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);          \
-    } while (0)
-    if (ml) {  // triangle lights in the light set
-        if (sc.abvh_nodes) {
-            if (sc.n_insts) PRT_SHADE_NEE_MESH(true, true); else PRT_SHADE_NEE_MESH(false, true);
-        } else {
-            if (sc.n_insts) PRT_SHADE_NEE_MESH(true, false); else PRT_SHADE_NEE_MESH(false, false);
-        }
-    } else if (sc.abvh_nodes) {
-        if (sc.n_insts) PRT_SHADE_NEE(true, true); else PRT_SHADE_NEE(false, true);
-    } else {
-        if (sc.n_insts) PRT_SHADE_NEE(true, false); else PRT_SHADE_NEE(false, false);
-    }
-#undef PRT_SHADE_NEE_MESH
-#undef PRT_SHADE_NEE
-    return name;
-}
-
 void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBufs& lb, const uint32_t* count_ptr,
                             uint32_t* work, uint32_t max_rays) {
     hipLaunchKernelGGL(k_light_accum, dim3(blocks_for(max_rays ? max_rays : 1u)), dim3(256), 0, st, sc, lb, count_ptr, work);
-}
-
-void prt_launch_accumulate_lit(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, const PrtTileMap& tm,
-                               uint32_t S, uint32_t max_depth, bool update_film, unsigned long long* ray_stats) {
-    const uint32_t nb = blocks_for(tm.n_pix_local ? tm.n_pix_local : 1);
-    hipLaunchKernelGGL(k_accumulate_lit, dim3(nb < 8192u ? nb : 8192u), dim3(256), 0, st, rad, lrad, film_local, tm, S,
-                       max_depth, update_film ? 1 : 0, ray_stats);
 }
 
 void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
@@ -4515,66 +4446,6 @@ void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, 
     hipLaunchKernelGGL(k_environment_eval, dim3(blocks_for(n)), dim3(256), 0, st, env, n, dirs, rgb, texel, pdf_w);
 }
 
-const char* prt_launch_shade_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const PrtRayBuf& in, const PrtRayBuf& out, float4* rad,
-                          uint32_t* counts, uint32_t* work, uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp,
-                          uint32_t n_rays_known, const DevEnv* env) {
-    const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
-    const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
-    const DevEnv e = env ? *env : DevEnv{};
-    const char* name = "";
-#define PRT_SHADE_TEX(IN, AB, EN)                                                                                                  \
-    do {                                                                                                                           \
-        name = "k_shade_tex<" #IN ", " #AB ", " #EN ">";                                                                          \
-        hipLaunchKernelGGL((k_shade_tex<IN, AB, EN>), grid, dim3(SHADE_BLOCK), 0, st, sc, tex, e, in.o, in.d, in.t, in.hit, out.o, out.d, \
-                           out.t, out.hit, out.hd2, rad, counts, work, depth, max_depth, cap, sp);                                 \
-    } while (0)
-#define PRT_SHADE_TEX2(IN, AB)                                           \
-    do {                                                                 \
-        if (env) PRT_SHADE_TEX(IN, AB, true); else PRT_SHADE_TEX(IN, AB, false); \
-    } while (0)
-    if (sc.abvh_nodes) {
-        if (sc.n_insts) PRT_SHADE_TEX2(true, true); else PRT_SHADE_TEX2(false, true);
-    } else {
-        if (sc.n_insts) PRT_SHADE_TEX2(true, false); else PRT_SHADE_TEX2(false, false);
-    }
-#undef PRT_SHADE_TEX2
-#undef PRT_SHADE_TEX
-    return name;
-}
-
-const char* prt_launch_shade_nee_tex(hipStream_t st, const DevScene& sc, const DevTex& tex, const DevLights& lt, const PrtRayBuf& in,
-                              const PrtRayBuf& out, const PrtLightBufs& lb, float4* rad, uint32_t* counts, uint32_t* work,
-                              uint32_t depth, uint32_t max_depth, uint32_t cap, const PrtSampling& sp, uint32_t n_rays_known,
-                              const DevMeshLights* ml, const DevEnv* env) {
-    const uint32_t n_for_grid = n_rays_known == 0xFFFFFFFFu ? cap : (n_rays_known ? n_rays_known : 1u);
-    const dim3 grid((uint32_t)((n_for_grid + SHADE_BLOCK - 1) / SHADE_BLOCK));
-    const DevEnv e = env ? *env : DevEnv{};
-    const DevMeshLights m = ml ? *ml : DevMeshLights{};
-    const char* name = "";
-#define PRT_SHADE_NEE_TEX(IN, AB, ME, EN)                                                                                              \
-    do {                                                                                                                               \
-        name = "k_shade_nee_tex<" #IN ", " #AB ", " #ME ", " #EN ">";                                                                 \
-        hipLaunchKernelGGL((k_shade_nee_tex<IN, AB, ME, EN>), grid, dim3(SHADE_BLOCK), 0, st, sc, tex, lt, m, e, in.o, in.d, in.t, in.hit, \
-                           out.o, out.d, out.t, out.hit, out.hd2, lb, rad, counts, work, depth, max_depth, cap, sp);                   \
-    } while (0)
-#define PRT_SHADE_NEE_TEX2(IN, AB)                                                       \
-    do {                                                                                 \
-        if (ml) {                                                                        \
-            if (env) PRT_SHADE_NEE_TEX(IN, AB, true, true); else PRT_SHADE_NEE_TEX(IN, AB, true, false);   \
-        } else {                                                                         \
-            if (env) PRT_SHADE_NEE_TEX(IN, AB, false, true); else PRT_SHADE_NEE_TEX(IN, AB, false, false); \
-        }                                                                                \
-    } while (0)
-    if (sc.abvh_nodes) {
-        if (sc.n_insts) PRT_SHADE_NEE_TEX2(true, true); else PRT_SHADE_NEE_TEX2(false, true);
-    } else {
-        if (sc.n_insts) PRT_SHADE_NEE_TEX2(true, false); else PRT_SHADE_NEE_TEX2(false, false);
-    }
-#undef PRT_SHADE_NEE_TEX2
-#undef PRT_SHADE_NEE_TEX
-    return name;
-}
-
 void prt_launch_texture_eval(hipStream_t st, const DevTex& tex, uint32_t n, const uint32_t* texture, const float* uv, float* rgb) {
     hipLaunchKernelGGL(k_texture_eval, dim3(blocks_for(n)), dim3(256), 0, st, tex, n, texture, uv, rgb);
 }
@@ -4583,53 +4454,6 @@ void prt_launch_hit_uv(hipStream_t st, const DevScene& sc, const DevTex& tex, ui
     hipLaunchKernelGGL(k_hit_uv, dim3(blocks_for(n)), dim3(256), 0, st, sc, tex, n, in.o, in.d, in.hit, uv, albedo);
 }
 
-
-void prt_launch_accumulate_stat(hipStream_t st, const float4* rad, const float4* lrad, float4* film_local, float2* stat,
-                                const PrtTileMap& tm, uint32_t S, uint32_t max_depth, bool update_film,
-                                unsigned long long* ray_stats, const float4* pix_end, const uint32_t* list) {
-    const uint32_t nb = blocks_for(tm.n_pix_local ? tm.n_pix_local : 1);
-    const dim3 grid(nb < 8192u ? nb : 8192u);
-#define PRT_ACC_STAT(LI, LS)                                                                                                  \
-    hipLaunchKernelGGL((k_accumulate_stat<LI, LS>), grid, dim3(256), 0, st, rad, lrad, film_local, stat, tm, S, max_depth, \
-                       update_film ? 1 : 0, ray_stats, pix_end, list)
-    if (list) {
-        if (lrad) PRT_ACC_STAT(true, true); else PRT_ACC_STAT(false, true);
-    } else {
-        if (lrad) PRT_ACC_STAT(true, false); else PRT_ACC_STAT(false, false);
-    }
-#undef PRT_ACC_STAT
-}
-
-void prt_launch_raygen_list(hipStream_t st, const DevScene& sc, const DevCamera& cam, const PrtTileMap& tm, const uint32_t* list,
-                            uint32_t n_paths, uint32_t first_sample, uint32_t seed, const PrtRayBuf& out, float4* rad,
-                            uint32_t* counts, uint32_t* work, uint32_t max_depth, const PrtSampling& sp, const DevEnv* env,
-                            const DevLens* lens) {
-    const uint32_t S = tm.n_pix_local ? n_paths / tm.n_pix_local : 0u;
-    const uint32_t group = (sp.jitter || lens) ? (uint32_t)RAYGEN_GROUP : RAYGEN_GROUP_NOJITTER;
-    const dim3 grid((tm.n_pix_local + PRODUCER_BLOCK - 1) / PRODUCER_BLOCK, (S + group - 1) / group);
-    const DevEnv e = env ? *env : DevEnv{};
-    const DevLens l = lens ? *lens : DevLens{0.0f, 0.0f};
-#define PRT_RAYGEN_LIST(J, AB, EN, LE)                                                                                          \
-    hipLaunchKernelGGL((k_raygen_list<J, AB, EN, LE>), grid, dim3(PRODUCER_BLOCK), 0, st, sc, e, l, cam, tm, list, S, first_sample, \
-                       seed, out.o, out.d, out.t, out.hit, out.hd2, rad, counts, work, max_depth, sp)
-#define PRT_RAYGEN_LIST2(J, AB)                                \
-    do {                                                       \
-        if (env) {                                             \
-            if (lens) PRT_RAYGEN_LIST(J, AB, true, true);      \
-            else PRT_RAYGEN_LIST(J, AB, true, false);          \
-        } else {                                               \
-            if (lens) PRT_RAYGEN_LIST(J, AB, false, true);     \
-            else PRT_RAYGEN_LIST(J, AB, false, false);         \
-        }                                                      \
-    } while (0)
-    if (sc.abvh_nodes) {
-        if (sp.jitter) PRT_RAYGEN_LIST2(true, true); else PRT_RAYGEN_LIST2(false, true);
-    } else {
-        if (sp.jitter) PRT_RAYGEN_LIST2(true, false); else PRT_RAYGEN_LIST2(false, false);
-    }
-#undef PRT_RAYGEN_LIST2
-#undef PRT_RAYGEN_LIST
-}
 
 void prt_launch_tile_select(hipStream_t st, const float4* film_local, const float2* stat, const PrtTileMap& tm, const uint32_t* prev,
                             uint32_t n_in, float threshold, float noise_floor, uint32_t* flags, uint32_t* out, uint32_t* count) {

@@ -1,9 +1,9 @@
 """Every texture instance of the shade kernels on one MI355X, against the replays (tests/texture_replay.py, whose gate and
 undecidable shares tests/test_texture_replay.py checks on the CPU), and three routes of a batch that no other test takes.
 
-prt_launch_shade_tex / prt_launch_shade_nee_tex choose one of 24 instances from four facts: INST (placed copies), ABVH (the
+prt_plan_route (csrc/prt_route.h) chooses one of 24 texture instances from four facts: INST (placed copies), ABVH (the
 primitive BVH: more than 16 analytic primitives and prim_bvh = 1), MESHL (triangle lights), ENV (an environment image).
-Renderer.shade_instance() names the instance a batch launched, in the launch macro's own words; every test here asserts it.
+Renderer.shade_instance() names the instance a batch launched, in the instance list's own words; every test here asserts it.
 Scenes: C (22 primitives, no copies), D (C + placed copies), Q_small / Q_big (8 / 20 quads, no triangle at all), E (scene B's
 bunny alone, 3 primitives), A and B of tests/test_gpu_textures.py.  "pb0": the same case with prim_bvh = 0, asserted
 bit-identical to the frames of the case beside it.
