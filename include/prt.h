@@ -712,6 +712,12 @@ int prt_kernel_instance(PrtContext* ctx, char* name, uint32_t capacity);
  * before the first batch and after a batch on the path-kernel route, which launches no shade kernel.  Read-only; written
  * NUL-terminated into name[capacity]. */
 int prt_shade_instance(PrtContext* ctx, char* name, uint32_t capacity);
+/* The last-segment route of the context's last batch (the "last_segment" tunable as the batch's plan took it: 0 = every stored
+ * ray was walked and shaded, 1 = last segments that the analytic scan decides ended in their producer, 2 = and the last walk
+ * was the seeded any-hit walk),
+ * and, if front_rays is not NULL, the number of rays that batch handed to its last tree walk (segment max_depth - 1; 0 after
+ * a batch on the path-kernel route).  Reading the count waits for the context's stream. */
+int prt_last_segment(PrtContext* ctx, uint32_t* active, uint32_t* front_rays);
 /* Copies the built BVH out (host arrays): nodes n_nodes*16 floats (layout: csrc/bvh.h), tris
  * n_triangles*12 floats in leaf order.  Either pointer may be NULL.  Works on host-only contexts. */
 int prt_bvh_read(PrtContext* ctx, float* nodes, float* tris);
@@ -731,7 +737,10 @@ int prt_set_variant(PrtContext* ctx, int variant);
  * included: 1 = PLOC + SAH top + optimal collapse, ~20 ms for 870 k triangles, traverses within 2-3 % of the host tree;
  * 2 = Morton octree, ~3 ms, ~20 % slower to traverse), "node_stride" (before prt_set_scene: 5 = 8-wide nodes packed at
  * 80 B, 8 = one node per 128-B line, 0 = by tree size, default), "pad_log2" (before prt_set_scene: the culling pad is 2^-n of
- * the coordinates' magnitude, default 18; A/B only).  Results never depend on a tunable.  Unknown names / bad values
+ * the coordinates' magnitude, default 18; A/B only), "last_segment" (the last segment of a path in scenes without emissive
+ * triangles, prt_last_segment: 0 = walked and shaded like any other; 1 = it ends in the shade launch that produces it where
+ * the analytic scan alone decides what the film gets; 2, default = 1, and the rays still walked get the any-hit walk seeded
+ * with their analytic hit).  Results never depend on a tunable.  Unknown names / bad values
  * return PRT_ERR_INVALID. */
 int prt_set_param(PrtContext* ctx, const char* name, int value);
 

@@ -265,6 +265,7 @@ SIGNATURES = {
     "prt_kernel_occupancy": (C.c_int, [_vp, C.POINTER(PrtOccupancy)]),
     "prt_kernel_instance": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),
     "prt_shade_instance": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),
+    "prt_last_segment": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "prt_measure_shade_divergence": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "prt_refit_meshes": (C.c_int, [_vp, C.POINTER(PrtMesh), C.c_uint32]),
     "prt_set_instance_transforms": (C.c_int, [_vp, C.POINTER(PrtInstance), C.c_uint32, C.c_uint32]),

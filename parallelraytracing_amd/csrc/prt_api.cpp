@@ -122,6 +122,9 @@ struct PrtContext {
     // phase after 24 queueing lane-steps, 8-wide tree (all measured best on C3, tools/sweep.py); XCD affinity off
     PrtTravTuning tune{1024u, 256u, 16u, 0xFFFFFFFFu /* exit_max: auto */, 0u, 2u, 0u /* tri_min: auto */, 0u, 0u, 0u, 1u, 8u, 1u, 0u, nullptr, 0u, 2500000u, 2u /* big */, 8u /* static_small */, 96u /* big_min */, 32u /* big_keep */, 1u};
     unsigned long long* d_shade_div = nullptr;  // diagnostic (prt_measure_shade_divergence): 16 words per bounce, or null
+    uint32_t last_segment = 2;    // a path's last segment (prt_route.h): 1 = it ends in its producer where the analytic scan decides it, 2 = and the rest is walked any-hit; 0 / 1: A/B
+    uint32_t last_segment_active = 0;  // what the last run_batch's plan made of it (prt_last_segment)
+    uint32_t last_batch_depth = 0;     // max_depth of the last run_batch that ran the pipeline (0: none, or the path route)
     uint32_t sort_rays = 0;       // measurement aid: 1 / 2 = bounces >= 1 (and jittered bounce 0) walk their rays in sorted order
     uint32_t* d_sort = nullptr;   // keys, keys2, idx, idx2 (n_paths each) + rocPRIM's temporary storage
     size_t sort_entries = 0, sort_temp = 0;
@@ -545,11 +548,11 @@ PrtBatchView whole_film(const PrtContext* c) { return PrtBatchView{c->tm, nullpt
 // with `any` the any-hit walk behind prt_occluded and the shadow rays.  The persistent kernels, or k_intersect where another
 // traversal variant is forced (A/B; it finds the closest hit from the seeded bound, which answers an occlusion query as well).
 void walk_rays(PrtContext* c, const PrtRayBuf& rays, const uint32_t* count, uint32_t max_rays, bool any, const PrtTravTuning& tune,
-               unsigned long long* stats, const PrtPrimary* primary) {
+               unsigned long long* stats, const PrtPrimary* primary, bool seeded = false) {
     if (!prt_route_walk8(c->variant == 0, c->dsc.n_insts != 0u, c->dsc.nodes != nullptr))
         prt_launch_intersect(c->stream, c->dsc, rays, count, max_rays, c->hs.bvh.max_depth <= 31 ? 31 : 63, c->variant, stats);
     else if (any)
-        prt_launch_occluded(c->stream, c->dsc, rays, count, c->d_work, c->d_spill, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune);
+        prt_launch_occluded(c->stream, c->dsc, rays, count, c->d_work, c->d_spill, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune, seeded);
     else
         prt_launch_traverse(c->stream, c->dsc, rays, count, c->d_work, c->d_spill, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4,
                             tune, stats, primary);
@@ -623,6 +626,10 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     f.path_gate = !trav_stats && !c->d_shade_div && c->sort_rays == 0u && n_paths <= c->tune.path_max && prt_path_kernel_applies(c->dsc, c->tune);
     f.path_kernel = c->tune.path_kernel;
     f.fuse = c->tune.fuse;
+    f.mesh_emissive = c->hs.mesh_emissive;
+    f.depth_ge2 = max_depth >= 2u;
+    f.sort_rays = c->sort_rays != 0u;
+    f.last_segment = c->last_segment;
     const PrtRoutePlan plan = prt_plan_route(f);
     const bool lit = f.lit, compact = plan.compact, walk = plan.walk;
     const DevEnv denv = dev_env(c);
@@ -663,6 +670,8 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         return PRT_OK;
     };
     c->shade_instance = "";  // (the path route launches no shade kernel)
+    c->last_segment_active = plan.last_segment;
+    c->last_batch_depth = plan.path ? 0u : max_depth;
     // Small batches (the reference's contract: ONE sample per ProgressiveRender call, cpu/renderer.cpp:49) can run as one
     // launch of the PATH instance of the traversal kernel, which carries whole paths (prt_kernels.h PrtPathArgs), instead
     // of raygen + 2 x max_depth launches.  Same arithmetic, same draws, same rad[] / k_accumulate: the frame is
@@ -722,6 +731,10 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
                 if ((rc = sort_front_rays(c, in, front_count, n_paths, &ep, &tune))) return rc;
             if (walk && d == 0)
                 walk_rays(c, in, c->d_counts + PRT_CNT_LIST, tm.n_pix_local, false, tune, trav_stats, &primary_list);
+            else if (plan.last_segment == 2u && d + 1u == max_depth && !trav_stats)
+                // the last segment's stored rays only ask whether a triangle lies in front of their seed: the seeded any-hit walk
+                // (instrumented batches keep the closest-hit walk, which answers the same question)
+                walk_rays(c, in, front_count, n_paths, true, tune, nullptr, nullptr, true);
             else
                 walk_rays(c, in, front_count, n_paths, false, tune, trav_stats, prim_d);
             if ((rc = end_event(c, &ep))) return rc;
@@ -748,7 +761,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, c->d_counts, d, n_paths, c->d_shade_div, prim_d);
         if ((rc = begin_event(c, 2, &ep))) return rc;
         const PrtShadeInst shade = d == 0 ? plan.shade0 : plan.shade;
-        const PrtShadeArgs sa{&c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, c->sampling, n_rays_known, prim_d,
+        const PrtShadeArgs sa{&c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, c->sampling, n_rays_known, prim_d, plan.last_segment,
                               f.env ? &denv : nullptr, f.tex ? &dtex : nullptr, lit ? &lt : nullptr, (lit && f.mesh_lights) ? &mlt : nullptr,
                               lit ? &c->lb : nullptr};
         if (!prt_launch_shade(c->stream, shade, sa)) return fail(c, PRT_ERR_INVALID, "no such shade instance");
@@ -2433,6 +2446,21 @@ int prt_shade_instance(PrtContext* c, char* name, uint32_t capacity) {
     return PRT_OK;
 }
 
+int prt_last_segment(PrtContext* c, uint32_t* active, uint32_t* front_rays) {
+    if (!c || !active) return PRT_ERR_INVALID;
+    *active = c->last_segment_active;
+    if (front_rays) {
+        *front_rays = 0u;
+        if (c->last_batch_depth != 0u && c->d_counts) {
+            HIPCHECK(c, hipSetDevice(c->device));
+            HIPCHECK(c, hipStreamSynchronize(c->stream));
+            HIPCHECK(c, hipMemcpy(front_rays, c->d_counts + (size_t)(c->last_batch_depth - 1u) * PRT_CNT_STRIDE, sizeof(uint32_t),
+                                  hipMemcpyDeviceToHost));
+        }
+    }
+    return PRT_OK;
+}
+
 int prt_bvh_info(PrtContext* c, PrtBvhInfo* out) {
     if (!c || !out) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
@@ -2478,6 +2506,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "path_kernel" && value >= 0 && value <= 2) c->tune.path_kernel = (uint32_t)value;
     else if (n == "path_max" && value >= 1) c->tune.path_max = (uint32_t)value;
     else if (n == "sort_rays" && value >= 0 && value <= 2) c->sort_rays = (uint32_t)value;
+    else if (n == "last_segment" && value >= 0 && value <= 2) c->last_segment = (uint32_t)value;
     else if (n == "compact_primary" && (value == 0 || value == 1)) c->compact_primary = value;
     else if (n == "primary_walk" && (value == 0 || value == 1)) c->primary_walk = value;
     else if (n == "node_stride" && (value == 0 || value == 5 || value == 8)) c->node_stride = value;

@@ -268,6 +268,9 @@ int prt_traverse_occupancy(const DevScene& sc, const PrtTravTuning& tune, int* b
 const char* prt_traverse_instance(const DevScene& sc, const PrtTravTuning& tune);
 void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                           uint32_t max_rays, int stack_depth, int variant, unsigned long long* stats);
+// The last-segment route reaches k_shade / k_shade_env / k_shade_tex as this bit of their max_depth argument (a run-time flag:
+// their instances and names stay what they are); max_depth itself is at most PRT_MAX_DEPTH.
+#define PRT_LAST_SEGMENT_FLAG 0x80000000u
 struct PrtShadeArgs {
     const DevScene* sc;
     PrtRayBuf in, out;
@@ -278,6 +281,7 @@ struct PrtShadeArgs {
     PrtSampling sp;
     uint32_t n_rays_known;             // the bounce's ray count if the host has it (0xFFFFFFFF: the grid is sized for `cap`)
     const PrtPrimary* primary;         // bounce 0 of compact primary rays
+    uint32_t last_segment;             // PrtRoutePlan.last_segment: non-zero sets PRT_LAST_SEGMENT_FLAG in the max_depth of k_shade / _env / _tex
     const DevEnv* env;
     const DevTex* tex;
     const DevLights* lights;           // lighting modes: the shade step takes a light sample per Lambertian vertex (shadow rays
@@ -326,7 +330,8 @@ void prt_launch_pack_occlusion_rays(hipStream_t st, uint32_t n, const float* o, 
 void prt_launch_scan_prims_bounded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                                    uint32_t* work, uint32_t max_rays);
 void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr, uint32_t* work,
-                         uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune);
+                         uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune,
+                         bool seeded = false);  // seeded: the SEEDED instances (a closest-hit walk's buffer, every ray walked)
 void prt_launch_occlusion_bytes(hipStream_t st, const DevScene& sc, uint32_t n, const PrtRayBuf& in, const float* tmax,
                                 uint8_t* out);
 void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, const float* in_d, const PrtHit* hits,

@@ -248,15 +248,26 @@ PRT_DEV f3 env_radiance(const DevEnv& env, f3 d) {
 // always was: all samples of a pixel trace the same primary ray; the comparison keeps the kernel correct by itself).
 // ENV (env: DevEnv): a miss delivers the environment image's texel where it delivers the constant sky.
 // TEX (tex: DevTex): the albedo of a vertex whose material is textured is the lookup at the hit's UV (k_shade_tex only).
-template <int BUDGET, bool INST, bool ABVH, int BLOCK, bool PRE = false, bool ENV = false, bool TEX = false>
+// LASTSEG && last_route (PRT_LAST_SEGMENT_FLAG, run-time; the plan sets it only without fusion and without emissive triangles;
+// LASTSEG = false compiles it out: k_raygen, the fusing k_shade instances and the path instance keep their code): a path's
+// last segment delivers throughput x emission of its closest hit and nothing else.  Its producer ends it when the analytic
+// scan's hit id0 does not emit: the closest hit is id0 or a triangle, throughput x 0 either way, so the ray is neither
+// stored nor walked; only a miss or an emissive id0 that a triangle may block is.  Its consumer writes throughput x 0 for a
+// triangle id without rebuilding the hit.  The products are the ones the full route forms (x the zero vector, not a literal
+// zero: an infinite throughput gives the same NaN), with the same segment index.
+template <int BUDGET, bool INST, bool ABVH, int BLOCK, bool PRE = false, bool ENV = false, bool TEX = false, bool LASTSEG = false>
 PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr, uint32_t& rng, uint32_t& depth,
                          uint32_t max_depth, const PrtSampling& sp, float4* __restrict__ rad_slot, uint32_t& id0,
                          float& d2_0, float4 pre_a = float4{0.f, 0.f, 0.f, 0.f}, float4 pre_b = float4{0.f, 0.f, 0.f, 0.f},
-                         const DevEnv* env = nullptr, const DevTex* tex = nullptr) {
+                         const DevEnv* env = nullptr, const DevTex* tex = nullptr, bool last_route = false) {
 #pragma unroll
     for (int it = 0; it <= BUDGET; ++it) {
         if (id == HIT_MISS) {  // the miss branch of IntersectClosestKernel, renderer.cu:263-271
             st_stream(rad_slot, path_result(thr * (ENV ? env_radiance(*env, d) : mk3(sc.sky[0], sc.sky[1], sc.sky[2])), sp.clamp, depth));
+            return 0;
+        }
+        if (LASTSEG && last_route && it == 0 && depth + 1u >= max_depth && id >= sc.n_prims) {  // a triangle ends the path and emits nothing
+            st_stream(rad_slot, path_result(thr * mk3(0.f, 0.f, 0.f), sp.clamp, depth));
             return 0;
         }
         if (it == BUDGET) {  // only reached with an analytic id (the ray was classified "cannot hit a triangle")
@@ -309,7 +320,14 @@ PRT_DEV int advance_path(const DevScene& sc, uint32_t id, f3& o, f3& d, f3& thr,
             thr = mk3(thr.x / p, thr.y / p, thr.z / p);
         }
         ++depth;
-        if (classify_ray<ABVH, BLOCK>(sc, o, d, id0, d2_0)) return 1;
+        if (LASTSEG) {
+            const bool front = classify_ray<ABVH, BLOCK>(sc, o, d, id0, d2_0);
+            if (last_route && depth + 1u >= max_depth && id0 != HIT_MISS && sc.mat_type[sc.prims[id0].material] != 4u) {
+                st_stream(rad_slot, path_result(thr * mk3(0.f, 0.f, 0.f), sp.clamp, depth));
+                return 0;
+            }
+            if (front) return 1;
+        } else if (classify_ray<ABVH, BLOCK>(sc, o, d, id0, d2_0)) return 1;
         id = id0;
     }
     return 2;  // not reached
@@ -1767,7 +1785,11 @@ __global__ void __launch_bounds__(256, WAVES) k_traverse4_persistent(DevScene sc
 // d2 = tmax^2" (k_pack_occlusion_rays + k_scan_prims_bounded); a ray whose seeded hit is already a blocker is not walked,
 // and a lane whose ray has a triangle accepted below its bound in a triangle phase is done: its stack and pending group
 // are dropped (the phase has tested all queued items, the queue is empty after it) and its helpers end with it.
-template <int STACK_L, int WAVES, bool STATS, bool INST, bool LEAN, bool PRIM, bool PATH, bool ANY>
+// SEEDED (ANY only; the last walk of a batch on the last-segment route, setting 2): the seed may be an ANALYTIC id at its
+// distance, exactly as the closest-hit walk is seeded, and every ray of the buffer is walked.  The question is whether a
+// triangle key lies strictly below the seed key (d2 bits << 32 | id0: the predicate of the closest-hit walk, ties included);
+// hit[] gets the first such triangle found, or keeps the seed.  A blocker is then a slot that names a TRIANGLE.
+template <int STACK_L, int WAVES, bool STATS, bool INST, bool LEAN, bool PRIM, bool PATH, bool ANY, bool SEEDED = false>
 __device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __restrict__ ro, const float4* __restrict__ rd,
                                                uint32_t* __restrict__ hit, const float* __restrict__ hd2,
                                                const uint32_t* __restrict__ count_ptr, uint32_t* __restrict__ work,
@@ -1808,6 +1830,7 @@ __device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __rest
     constexpr bool STEAL = LEAN && !INST;
     static_assert(!PATH || (!LEAN && !INST && !PRIM && !STATS), "the path instance is the plain one-level kernel");
     static_assert(!ANY || (!PATH && !PRIM && !STATS), "the any-hit walk reads plain ray buffers");
+    static_assert(!SEEDED || ANY, "a seeded walk is an any-hit walk");
     const uint32_t count = PATH ? pa.n_paths : *count_ptr;
     // PATH: the path a busy lane carries (k = its path id): direction as stored (the walk normalises it again, as the
     // reference's TransformNormal does), throughput, RNG state, segment index; need_shade: the walk of the current
@@ -2199,7 +2222,7 @@ __device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __rest
                 if (idle && qi_seq < cur_end) {
                     const uint32_t qi = (!PRIM && tune.perm) ? tune.perm[qi_seq] : qi_seq;  // (sort_rays: a measurement aid)
                     uint32_t hid = PRIM ? HIT_MISS : ld_stream(&hit[qi]);
-                    if (hid != HIT_DEAD && !(ANY && hid != HIT_MISS)) {  // (ANY: an analytic hit below tmax already blocks)
+                    if (hid != HIT_DEAD && !(ANY && !SEEDED && hid != HIT_MISS)) {  // (ANY: an analytic hit below tmax already blocks; SEEDED: it is the seed)
                         float4 O, D;
                         float hd2_0 = 0.0f;
                         if (PRIM) {
@@ -2452,10 +2475,12 @@ __device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __rest
                 if (LEAN) {
                     tlimit = limit_from_d2(__uint_as_float((uint32_t)(won >> 32)), pad);  // same value if nothing changed
                     // ANY: the ray (of this lane, or of the root it helps) has a blocker once its slot names a triangle
-                    if (ANY && k != 0xFFFFFFFFu &&
-                        ((volatile uint32_t*)s_slot)[(STEAL && k >= 0xFFFFFF00u) ? wbase + (k & 63u) : tid] != HIT_MISS) {
-                        gy = 0u;
-                        sp = 0;
+                    if (ANY && k != 0xFFFFFFFFu) {
+                        const uint32_t sl = ((volatile uint32_t*)s_slot)[(STEAL && k >= 0xFFFFFF00u) ? wbase + (k & 63u) : tid];
+                        if (sl != HIT_MISS && (!SEEDED || sl >= sc.n_prims)) {  // (SEEDED: an analytic id is the seed, not a blocker)
+                            gy = 0u;
+                            sp = 0;
+                        }
                     }
                 } else if (won != key_best) {
                     best.d2 = __uint_as_float((uint32_t)(won >> 32));
@@ -2550,6 +2575,20 @@ __global__ void __launch_bounds__(256, WAVES) k_occluded8_persistent(DevScene sc
                                                                           nullptr, PrtPrimary{}, PrtPathArgs{});
 }
 
+// The last walk of a batch on the last-segment route, setting 2: the SEEDED any-hit walk (traverse8_body).  hit[] holds the
+// closest-hit walk's seeds, an analytic id or HIT_MISS at hd2[], all of them walked; on return a triangle id where one lies
+// in front of the seed, the seed elsewhere.  A kernel of its own: the instances of k_occluded8_persistent keep their code.
+template <int STACK_L, int WAVES, bool INST, bool LEAN = false>
+__global__ void __launch_bounds__(256, WAVES) k_occluded8_seeded(DevScene sc, const float4* __restrict__ ro,
+                                                                const float4* __restrict__ rd, uint32_t* __restrict__ hit,
+                                                                const float* __restrict__ hd2,
+                                                                const uint32_t* __restrict__ count_ptr,
+                                                                uint32_t* __restrict__ work, uint32_t* __restrict__ ovf,
+                                                                PrtTravTuning tune) {
+    traverse8_body<STACK_L, WAVES, false, INST, LEAN, false, false, true, true>(sc, ro, rd, hit, hd2, count_ptr, work, ovf, tune,
+                                                                                nullptr, PrtPrimary{}, PrtPathArgs{});
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Shade + scatter + compaction (ShadeHitsKernel, renderer.cu:274-335; the miss branch of
 // IntersectClosestKernel, renderer.cu:263-271; path logic of TraceRayGPU, cuda_megakernel/renderer.cu:81-119).
@@ -2561,8 +2600,10 @@ template <int FUSE, bool SAMPLING, bool INST, bool ABVH, bool PRIM, bool ENV, bo
 PRT_DEV void shade_step(DevScene sc, const float4* __restrict__ ro, const float4* __restrict__ rd, const float4* __restrict__ rt,
                         const uint32_t* __restrict__ hit, float4* __restrict__ no, float4* __restrict__ nd, float4* __restrict__ nt,
                         uint32_t* __restrict__ nhit, float* __restrict__ nhd2, float4* __restrict__ rad, uint32_t* __restrict__ counts,
-                        uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp_arg, PrtPrimary pr,
+                        uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth_arg, uint32_t cap, PrtSampling sp_arg, PrtPrimary pr,
                         const DevEnv* env, const DevTex* tex = nullptr) {
+    const bool last_route = (max_depth_arg & PRT_LAST_SEGMENT_FLAG) != 0u;  // (advance_path)
+    const uint32_t max_depth = max_depth_arg & ~PRT_LAST_SEGMENT_FLAG;
     // PRIM: the first k_shade of a batch whose k_raygen stored compact primary rays (PrtPrimary): ray, RNG seed,
     // throughput (1,1,1) and segment index (0) follow from the path id
     const PrtSampling sp = SAMPLING ? sp_arg : PrtSampling{0u, 0u, 0.0f};
@@ -2606,7 +2647,7 @@ PRT_DEV void shade_step(DevScene sc, const float4* __restrict__ ro, const float4
             d = mk3(D.x, D.y, D.z);
         }
         if (id != HIT_DEAD) {
-            const int r = advance_path<1 + FUSE, INST, ABVH, SHADE_BLOCK, PRIM, ENV, TEX>(sc, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0, pre_a, pre_b, env, tex);
+            const int r = advance_path<1 + FUSE, INST, ABVH, SHADE_BLOCK, PRIM, ENV, TEX, FUSE == 0>(sc, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0, pre_a, pre_b, env, tex, last_route);
             front = r == 1;
             back = r == 2;
         }
@@ -4207,7 +4248,7 @@ void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
 // are re-walked by the 4-wide closest-hit instance from their seeded bound, which answers the query as well).  Scenes
 // without the 8-wide tree (or with another one forced): the closest-hit walk from the seeded bound.
 void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr, uint32_t* work,
-                         uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune_in) {
+                         uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune_in, bool seeded) {
     if (t8_kind(sc, tune_in) == T8_NONE) {
         prt_launch_traverse(st, sc, in, count_ptr, work, spill, max_rays, tree_depth, stack4, tune_in, nullptr);
         return;
@@ -4217,9 +4258,15 @@ void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in
     const T8Launch r = t8_resolve(sc, tune_o, max_rays);
     const dim3 block(256);
     uint32_t* ovf = work + 512;
-#define PRT_LAUNCH_O(L, W, IN, LN, GRID, TUNE)                                                                       \
-    hipLaunchKernelGGL((k_occluded8_persistent<L, W, IN, LN>), dim3(GRID), block, 0, st, sc, in.o, in.d, in.hit, in.hd2,  \
-                       count_ptr, work, ovf, TUNE)
+#define PRT_LAUNCH_O(L, W, IN, LN, GRID, TUNE)                                                                                 \
+    do {                                                                                                                       \
+        if (seeded)                                                                                                            \
+            hipLaunchKernelGGL((k_occluded8_seeded<L, W, IN, LN>), dim3(GRID), block, 0, st, sc, in.o, in.d, in.hit,           \
+                               in.hd2, count_ptr, work, ovf, TUNE);                                                            \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((k_occluded8_persistent<L, W, IN, LN>), dim3(GRID), block, 0, st, sc, in.o, in.d, in.hit,        \
+                               in.hd2, count_ptr, work, ovf, TUNE);                                                            \
+    } while (0)
     // (two-level: a stack overflow is an error; prt_synchronize / the host form report it)
     if (r.kind == T8_INST12_4) PRT_LAUNCH_O(12, 4, true, false, r.grid, r.tune);
     else if (r.kind == T8_WIDE11_5) PRT_LAUNCH_O(11, 5, false, false, r.grid, r.tune);
@@ -4304,10 +4351,13 @@ bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a) 
     const DevMeshLights& m = or_empty(a.mesh_lights);
     const PrtLightBufs& lb = or_empty(a.lb);
 #define PRT_SHADE_RAYS a.in.o, a.in.d, a.in.t, a.in.hit, a.out.o, a.out.d, a.out.t, a.out.hit, a.out.hd2
-#define PRT_SHADE_TAIL a.rad, a.counts, a.work, a.depth, a.max_depth, a.cap, a.sp
-#define PRT_SHADE_ARGS_PLAIN sc, PRT_SHADE_RAYS, PRT_SHADE_TAIL, pr
-#define PRT_SHADE_ARGS_ENV sc, e, PRT_SHADE_RAYS, PRT_SHADE_TAIL
-#define PRT_SHADE_ARGS_TEX sc, tex, e, PRT_SHADE_RAYS, PRT_SHADE_TAIL
+#define PRT_SHADE_TAIL_D(D) a.rad, a.counts, a.work, a.depth, D, a.cap, a.sp
+#define PRT_SHADE_TAIL PRT_SHADE_TAIL_D(a.max_depth)
+    // (only k_shade / k_shade_env / k_shade_tex know the flag bit: the NEE family never sees it, whatever the plan says)
+#define PRT_SHADE_TAIL_LS PRT_SHADE_TAIL_D((a.last_segment ? a.max_depth | PRT_LAST_SEGMENT_FLAG : a.max_depth))
+#define PRT_SHADE_ARGS_PLAIN sc, PRT_SHADE_RAYS, PRT_SHADE_TAIL_LS, pr
+#define PRT_SHADE_ARGS_ENV sc, e, PRT_SHADE_RAYS, PRT_SHADE_TAIL_LS
+#define PRT_SHADE_ARGS_TEX sc, tex, e, PRT_SHADE_RAYS, PRT_SHADE_TAIL_LS
 #define PRT_SHADE_ARGS_NEE sc, lt, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
 #define PRT_SHADE_ARGS_NEE_ENV sc, lt, e, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
 #define PRT_SHADE_ARGS_NEE_MESH sc, lt, m, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
@@ -4328,7 +4378,9 @@ bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a) 
 #undef PRT_SHADE_ARGS_TEX
 #undef PRT_SHADE_ARGS_ENV
 #undef PRT_SHADE_ARGS_PLAIN
+#undef PRT_SHADE_TAIL_LS
 #undef PRT_SHADE_TAIL
+#undef PRT_SHADE_TAIL_D
 #undef PRT_SHADE_RAYS
 }
 

@@ -103,6 +103,11 @@ struct PrtRouteFacts {
     bool path_gate;        // !trav_stats && !d_shade_div && sort_rays == 0 && n_paths <= tune.path_max && prt_path_kernel_applies(dsc, tune)
     uint32_t path_kernel;  // tune.path_kernel: 0 off, 1 batches of one sample, 2 any batch
     uint32_t fuse;         // tune.fuse
+    // the last segment of a path as a visibility query (DESIGN.md section 3 "The last segment")
+    bool mesh_emissive;     // a mesh or a placed copy has an emissive material (PrtHostScene::mesh_emissive)
+    bool depth_ge2;         // max_depth >= 2: the last segment has a shade launch as its producer
+    bool sort_rays;         // the sort_rays measurement aid is on
+    uint32_t last_segment;  // the last_segment tunable: 0 off, 1 end decided last segments in their producer, 2 = 1 + the last walk is any-hit
 };
 
 struct PrtRoutePlan {
@@ -115,6 +120,9 @@ struct PrtRoutePlan {
     PrtRaygenInst raygen;
     PrtShadeInst shade0, shade;  // bounce 0, later bounces
     PrtAccumulateInst accumulate;
+    uint32_t last_segment;  // 0: every stored ray is walked and shaded; 1: the producer of a path's last segment ends it when the
+                            // analytic scan decides what the film gets, and the last shade launch does not rebuild a triangle hit;
+                            // 2: and the last walk is the seeded any-hit walk (k_occluded8_seeded)
 };
 
 // Whether a tree walk runs the persistent kernels (prt_launch_traverse / prt_launch_occluded) or, with variant 1 or 2 forced,
@@ -163,5 +171,11 @@ inline PrtRoutePlan prt_plan_route(const PrtRouteFacts& f) {
 
     if (f.film_stats || f.listed) p.accumulate = PrtAccumulateInst(PRT_INST(k_accumulate_stat, ff) + ((uint32_t)f.lit << 1 | (uint32_t)f.listed));
     else p.accumulate = f.lit ? PRT_I_k_accumulate_lit : PRT_I_k_accumulate;  // (the path route is never lit)
+
+    // Without fusion every ray of shade launch d has segment index d, so launch max_depth - 2 produces exactly the last segments
+    // and launch max_depth - 1 consumes them; with no emissive triangle a last segment whose analytic hit does not emit
+    // delivers throughput x 0 whatever the walk finds.  (The NEE family weights the last hit by MIS and stays as it is.)
+    const bool last_ok = !p.path && p.fuse == 0u && !f.lit && !f.mesh_emissive && f.has_nodes && p.walk8 && !f.sort_rays && f.depth_ge2;
+    p.last_segment = last_ok ? f.last_segment : 0u;
     return p;
 }

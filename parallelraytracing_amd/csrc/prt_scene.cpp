@@ -147,11 +147,17 @@ void build_light_table(PrtHostScene* c, const PrtSceneDesc* s) {
     }
     c->light_power = power;
     const uint32_t n_not_similar = c->n_emitters_unsampled;
+    c->mesh_emissive = false;  // (by material alone: an emissive mesh without triangles counts, which only keeps a route off)
     for (uint32_t m = 0; m < s->n_meshes; ++m)
-        if (emissive(s->meshes[m].material_id)) c->n_emitters_unsampled += s->meshes[m].n_triangles;
+        if (emissive(s->meshes[m].material_id)) {
+            c->n_emitters_unsampled += s->meshes[m].n_triangles;
+            c->mesh_emissive = true;
+        }
     for (uint32_t i = 0; i < s->n_instances; ++i) {
         const PrtInstance& pi = s->instances[i];
-        if (emissive(pi.material_id) && pi.mesh < s->n_instanced_meshes) c->n_emitters_unsampled += s->instanced_meshes[pi.mesh].n_triangles;
+        if (!emissive(pi.material_id)) continue;
+        c->mesh_emissive = true;
+        if (pi.mesh < s->n_instanced_meshes) c->n_emitters_unsampled += s->instanced_meshes[pi.mesh].n_triangles;
     }
     c->ml_tris_counted = c->n_emitters_unsampled - n_not_similar;
 }

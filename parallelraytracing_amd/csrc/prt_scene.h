@@ -112,6 +112,7 @@ struct PrtHostScene {
     uint32_t n_emitters_unsampled = 0;
     std::vector<double> light_power;   // per light of `lights`: emitting area x mean(rgb)
     uint32_t ml_tris_counted = 0;      // the part of n_emitters_unsampled that is mesh / placed triangles
+    bool mesh_emissive = false;        // a mesh or a placed copy has an emissive material (prt_route.h: the last-segment route needs none)
     PrtMeshLights ml;                  // the light set with emissive triangles in it (PRT_LIGHT_SOURCES_MESH)
     // what a texture binding needs of the description beyond the above (prt_build_textures): the index buffers in face order
     std::vector<uint32_t> mesh_indices;    // the world-space meshes', mesh and face order: 3 per triangle

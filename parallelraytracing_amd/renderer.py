@@ -859,6 +859,13 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_shade_instance(self._ctx, buf, 96))
         return buf.value.decode()
 
+    def last_segment(self):
+        """(setting the last batch's plan took for the last-segment route, rays that batch handed to its last tree walk)
+        (prt_last_segment); (0, 0) before the first batch."""
+        active, front = C.c_uint32(0), C.c_uint32(0)
+        self._check(capi.lib().prt_last_segment(self._ctx, C.byref(active), C.byref(front)))
+        return active.value, front.value
+
     def bvh_read(self):
         b = self.bvh_info()
         nodes = np.zeros((b.n_nodes, 16), np.float32)
