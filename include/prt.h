@@ -632,6 +632,98 @@ int prt_adaptive_unconverged(float n, float A, float Q, float threshold, float n
 int prt_render_adaptive(PrtContext* ctx, const PrtAdaptive* cfg, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
                         PrtAdaptiveInfo* out /* may be NULL */);
 
+/* ---- First-hit feature images and the edge-avoiding film denoiser ---------------------------------
+ * Feature images (prt_render_features).  For every pixel of the film ONE pinhole ray through the pixel centre
+ * (x + 0.5, y + 0.5): the context's camera with PrtLens.fov_y honoured and the aperture ignored (prt_camera_rays' ray), no
+ * jitter, no random number.  The pass covers the whole W x H image whatever rank / world_size the film has (the scene is
+ * replicated on every rank: nothing is gathered).  The ray's closest hit is exactly what prt_closest_hit returns for it.
+ * Per pixel, Film layout (row 0 on top):
+ *    albedo[3]    Lambertian or Metal hit: the material's rgb, or the textured colour prt_hit_uv reports while a binding
+ *                 textures at least one material; Dielectric hit, Emissive hit or a miss: (1, 1, 1)
+ *    normal[3], position[3]   PrtHit.normal (already flipped to the incoming side) and PrtHit.position; zeros for a miss
+ *    prim (int32) PrtHit.prim, -1 for a miss
+ *    depth        sqrtf(d2), 0 for a miss (exported only: the filter uses positions)
+ * The pass is its own: no render route, kernel instance, film bit, ray count or statistic of a render call changes.  The
+ * records stay on the device with the context (three 16-byte records per pixel) until one of prt_set_scene,
+ * prt_clone_scene (into this context), prt_set_camera, prt_set_film, prt_set_lens, prt_set_textures, prt_refit_meshes or
+ * prt_set_instance_transforms is called, successful or not; prt_features_read without a current set is PRT_ERR_INVALID.
+ * Limitations: the features are the FIRST hit of the CENTRE ray.  They do not follow mirrors or glass (a mirror shows its
+ * own plane, a glass ball its own surface), and they do not average over a lens or over jitter (a defocused or
+ * anti-aliased edge has the features of one side).
+ *
+ * The filter contract (prt_denoise and everything built on it): an edge-avoiding a-trous wavelet filter guided by the
+ * variance of the mean luminance and by the features above.
+ * Inputs per pixel p: mean colour c(p), variance of the mean luminance var(p), albedo, normal N_p, position P_p, prim
+ * (prim < 0: a miss).  Parameters: PrtDenoise below (NULL = the defaults).
+ * Arithmetic: everything is fp32, one rounding per written operation, never contracted; a dot product is (x + y) + z;
+ * lum(c) = (0.2126f r + 0.7152f g) + 0.0722f b as in the film statistics; / and sqrtf are correctly rounded.
+ * Constants: k5 = (1/16, 1/4, 3/8, 1/4, 1/16), k3 = (1/4, 1/2, 1/4), RHO_MIN = 2^-6, EPS_L = 2^-20, TINY = 2^-100,
+ * W_MIN = 2^-30.
+ * Demodulation (demodulate != 0): rho = max(albedo, RHO_MIN) per channel, (1, 1, 1) for a miss; c_0 = c / rho per
+ *   channel, var_0 = var / (lum(rho) * lum(rho)).  Otherwise c_0 = c, var_0 = var.  l_0 = lum(c_0).
+ * Iteration i = 0 .. iterations - 1, step s = 2^i:
+ *   variance prefilter  g(p) = (sum of (k3[dy] k3[dx]) * var_i(q)) / (sum of k3[dy] k3[dx]) over the in-image pixels q of
+ *     the 3 x 3 neighbourhood of p at step 1, row-major, each term k * var added to a running sum (the k's sum likewise: it
+ *     is exact); den(p) = sigma_l * sqrtf(g(p)) + EPS_L.
+ *   taps (dy, dx) in [-2, 2]^2, row-major (dy outer), q = p + s (dx, dy); a tap outside the image is skipped;
+ *     h = k5[dy] * k5[dx] (exact).
+ *   weight of a tap:
+ *     the centre tap: w = h
+ *     off-centre, one of p, q a miss and the other a hit: w = 0
+ *     off-centre, both misses: wn = 1, xz = 0
+ *     off-centre, both hits: wn = max(0, N_p . N_q), then wn = wn * wn repeated normal_power_log2 times;
+ *       D = P_q - P_p; xz = |D . N_p| / (sigma_z * sqrtf(D . D) + TINY): the sine of the offset's angle to p's tangent
+ *       plane, free of the unit of length
+ *     and for both of the last two: xl = |l_i(p) - l_i(q)| / den(p); x = xl + xz;
+ *       w = (h * wn) / ((1 + x) + (0.5f * x) * x); w < W_MIN becomes 0
+ *   running fp32 sums in tap order, every tap in the image included (w = 0 adds 0):
+ *     Sw += w;  Sc += w * c_i(q) per channel;  Sv += (w * w) * var_i(q)
+ *   c_{i+1}(p) = Sc / Sw per channel; var_{i+1}(p) = Sv / (Sw * Sw); l_{i+1} = lum(c_{i+1}).  Sw >= 9/64 always.
+ * Outputs (K = iterations): out = c_K * rho per channel and var_out = var_K * (lum(rho) * lum(rho)) with demodulation,
+ *   c_K and var_K without.  iterations = 0 without demodulation returns the inputs.
+ * The falloff 1 / (1 + x + x^2 / 2) is deliberate: exp(-x) for small x, made of exact operations; no expf, no powf.  The
+ * variance prefilter is NOT edge-aware: a pixel's output depends on a neighbouring region only through that region's
+ * variance images, never through its colours (a region behind a feature edge gets weight 0 exactly).
+ * Non-finite inputs give unspecified values in the pixels whose footprint reaches them; never a fault, never an access
+ * out of range.  Subnormal intermediates are outside what "bit for bit" covers.  tests/denoise_replay.py restates these
+ * lines in numpy float32.  Results depend on no tunable, not on samples_in_flight, the tree builder or the partition. */
+typedef struct PrtDenoise {
+    uint32_t iterations;        /* 0..6, default 5 */
+    float sigma_l;              /* > 0, default 4 */
+    float sigma_z;              /* > 0, default 0.1 */
+    uint32_t normal_power_log2; /* 0..8, default 6 (the normal weight is max(0, N.N)^64) */
+    uint32_t demodulate;        /* 0 / not 0, default 1 */
+} PrtDenoise;
+#define PRT_DENOISE_MAX_PIXELS (1u << 28)
+void prt_denoise_defaults(PrtDenoise* out);
+/* The variance of the mean luminance prt_film_denoise feeds the filter with, from a pixel's film weight n and moments
+ * A, Q, in double and rounded once: m = A / n; V = max(0, Q / n - m m); var = V / (n - 1).  Where 0 < n < 2:
+ * var = fl(m) * fl(m) (one sample says nothing about its spread: the filter takes the pixel for as noisy as it is
+ * bright).  n = 0: 0.  Written once (csrc/prt_denoise_contract.h) for the device and the host; this is the host's copy. */
+float prt_denoise_variance(float n, float A, float Q);
+/* Needs a scene, a camera and a film; synchronous.  PRT_ERR_INVALID beyond the usual: a film above 2^28 pixels. */
+int prt_render_features(PrtContext* ctx);
+/* Copies the current feature set out (host arrays, H*W*3 floats / H*W floats / H*W int32; each may be NULL). */
+int prt_features_read(PrtContext* ctx, float* albedo, float* normal, float* position, float* depth, int32_t* prim);
+/* The filter on host arrays (mean, albedo, normal, position, out: W*H*3 floats; var, var_out: W*H floats; prim: W*H
+ * int32; var_out may be NULL).  Synchronous.  Needs a device, but neither a scene nor a film.  PRT_ERR_INVALID, checked
+ * before the device is asked for (host-only contexts refuse alike): iterations > 6, a sigma <= 0 or NaN,
+ * normal_power_log2 > 8, a null array, W * H = 0 or above 2^28. */
+int prt_denoise(PrtContext* ctx, const PrtDenoise* cfg, uint32_t W, uint32_t H, const float* mean, const float* var,
+                const float* albedo, const float* normal, const float* position, const int32_t* prim, float* out,
+                float* var_out);
+/* The same on DEVICE arrays, enqueued on the context's stream with no host wait. */
+int prt_denoise_device(PrtContext* ctx, const PrtDenoise* cfg, uint32_t W, uint32_t H, const void* d_mean, const void* d_var,
+                       const void* d_albedo, const void* d_normal, const void* d_position, const void* d_prim, void* d_out,
+                       void* d_var_out);
+/* The context's own film through the filter: mean = rgb_sum / weight per channel (fp32), var = prt_denoise_variance of the
+ * pixel's weight and moments; a pixel of weight 0 has mean 0 and variance 0.  rgb_out: H*W*3 floats, var_out: H*W floats or
+ * NULL, host arrays; synchronous.  Film statistics must be on (PRT_ERR_INVALID otherwise, before the device is asked
+ * for); the feature set is rendered first if there is no current one; the film must own the whole image (world_size 1: a
+ * partitioned context is refused with a message that names prt_group_film_denoise).  Everything stays on the device (a
+ * prepare kernel of its own reads the film and the moments); neither is modified by a bit. */
+int prt_film_denoise(PrtContext* ctx, const PrtDenoise* cfg, float* rgb_out, float* var_out);
+
 /* ---- Film read-back (Film::m_Accum / m_Weights; src/core/film.h:54-60) ------------------------ */
 /* Whole film to host, row-major, top-left origin; only pixels owned by this rank are non-zero. */
 int prt_film_read(PrtContext* ctx, float* rgb_sum, float* weight);
@@ -740,7 +832,8 @@ int prt_set_variant(PrtContext* ctx, int variant);
  * the coordinates' magnitude, default 18; A/B only), "last_segment" (the last segment of a path in scenes without emissive
  * triangles, prt_last_segment: 0 = walked and shaded like any other; 1 = it ends in the shade launch that produces it where
  * the analytic scan alone decides what the film gets; 2, default = 1, and the rays still walked get the any-hit walk seeded
- * with their analytic hit).  Results never depend on a tunable.  Unknown names / bad values
+ * with their analytic hit), "denoise_lds" (which iterations of the denoiser stage their block's footprint in LDS: 0 = none, 1, default = step 1,
+ * 2 = steps 1 and 2; A/B).  Results never depend on a tunable.  Unknown names / bad values
  * return PRT_ERR_INVALID. */
 int prt_set_param(PrtContext* ctx, const char* name, int value);
 
@@ -791,6 +884,10 @@ int prt_group_render(PrtGroup* g, uint32_t spp, uint32_t max_depth, uint32_t see
 int prt_group_set_film_statistics(PrtGroup* g, int on);
 int prt_group_render_adaptive(PrtGroup* g, const PrtAdaptive* cfg, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
                               PrtAdaptiveInfo* out);
+/* prt_film_denoise for the gathered film: the ranks' moments are summed on the host (a pixel its rank does not own holds 0,
+ * so the sum is exact), mean and variance are computed on the host by the lines prt_film_denoise's prepare kernel
+ * compiles, and rank 0 renders the features and runs the filter: the result equals the single context's bit for bit. */
+int prt_group_film_denoise(PrtGroup* g, const PrtDenoise* cfg, float* rgb_out, float* var_out);
 /* Whole film (all ranks' tiles) to host / tonemapped to host RGBA8, as prt_film_read / prt_film_display. */
 int prt_group_film_read(PrtGroup* g, float* rgb_sum, float* weight);
 int prt_group_film_display(PrtGroup* g, float exposure, float gamma, uint8_t* rgba8);

@@ -97,6 +97,15 @@ class PrtAdaptiveInfo(C.Structure):
                 ("pixel_samples", C.c_uint64)]
 
 
+class PrtDenoise(C.Structure):
+    """Settings of the film denoiser (include/prt.h "The filter contract"); prt_denoise_defaults fills the defaults."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_l", C.c_float), ("sigma_z", C.c_float),
+                ("normal_power_log2", C.c_uint32), ("demodulate", C.c_uint32)]
+
+
+DENOISE_MAX_PIXELS = 1 << 28  # PRT_DENOISE_MAX_PIXELS
+
+
 class PrtLighting(C.Structure):
     _fields_ = [("mode", C.c_uint32)]
 
@@ -232,6 +241,14 @@ SIGNATURES = {
     "prt_render_adaptive": (C.c_int, [_vp, C.POINTER(PrtAdaptive), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PrtAdaptiveInfo)]),
     "prt_group_set_film_statistics": (C.c_int, [_vp, C.c_int]),
     "prt_group_render_adaptive": (C.c_int, [_vp, C.POINTER(PrtAdaptive), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PrtAdaptiveInfo)]),
+    "prt_denoise_defaults": (None, [C.POINTER(PrtDenoise)]),
+    "prt_denoise_variance": (C.c_float, [C.c_float, C.c_float, C.c_float]),
+    "prt_render_features": (C.c_int, [_vp]),
+    "prt_features_read": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
+    "prt_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), C.c_uint32, C.c_uint32, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), _fp, _fp]),
+    "prt_denoise_device": (C.c_int, [_vp, C.POINTER(PrtDenoise), C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "prt_film_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), _fp, _fp]),
+    "prt_group_film_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), _fp, _fp]),
     "prt_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),
     "prt_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
     "prt_light_info": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _fp]),

@@ -24,6 +24,8 @@
 #include "bvh.h"
 #include "bvh_gpu.h"
 #include "prt_adaptive.h"
+#include "prt_denoise.h"
+#include "prt_denoise_contract.h"
 #include "prt_kernels.h"
 #include "prt_scene.h"
 
@@ -168,6 +170,17 @@ struct PrtContext {
     void* d_tex_uvs = nullptr;
     void* d_tex_inst = nullptr;
     uint64_t tex_bytes = 0;            // device bytes of the binding
+
+    // ---- first-hit features and the film denoiser (include/prt.h): the records of prt_render_features, valid until a call
+    // that changes what the centre rays see; the filter's workspace (packed records of the array entry points, the two
+    // colour + variance buffers, staging for host arrays) ----
+    PrtFeatureBufs feat{nullptr, nullptr, nullptr};  // one allocation: feat.alb is its base
+    uint32_t feat_cap = 0;                           // pixels it holds
+    uint32_t feat_W = 0, feat_H = 0;
+    bool feat_valid = false;
+    void* d_dn = nullptr;
+    size_t dn_bytes = 0;
+    int dn_lds = 1;  // prt_set_param("denoise_lds", n): which iterations stage their block's footprint in LDS: 0 none, 1 step 1 (default: measured faster there, slower at step 2), 2 steps 1 and 2; the same bits
 };
 
 namespace {
@@ -1076,6 +1089,8 @@ void prt_destroy(PrtContext* c) {
         free_dev(c->d_spill);
         free_dev(c->d_sort);
         free_dev(c->d_scratch);
+        free_dev(c->feat.alb);
+        free_dev(c->d_dn);
         for (EventPair& ep : c->events) {
             (void)hipEventDestroy(ep.a);
             (void)hipEventDestroy(ep.b);
@@ -1111,6 +1126,7 @@ int prt_get_device(const PrtContext* c) { return c ? c->device : -1; }
 
 int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     if (!c || !s) return PRT_ERR_INVALID;
+    c->feat_valid = false;
     int rc = prt_check_scene_arrays(s, &c->err);
     if (rc) return rc;
     // A scene the context held before is gone whatever happens: a failure below leaves the context WITHOUT a scene (the
@@ -1157,6 +1173,7 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     if (!dst || !src) return PRT_ERR_INVALID;
     if (!src->has_scene) return fail(dst, PRT_ERR_INVALID, "prt_clone_scene: the source context has no scene");
     if (dst == src) return PRT_OK;
+    dst->feat_valid = false;
     dst->has_scene = false;
     drop_tex(dst);
     dst->hs = src->hs;
@@ -1180,6 +1197,7 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
 // triangle counts, same index buffers as at prt_set_scene).  The 8-wide tree keeps its topology and is refitted on the
 // device (csrc/bvh_gpu.hip prt_gpu_bvh8_refit): records rewritten, boxes recomputed bottom-up, nodes re-quantized.
 int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
+    if (c) c->feat_valid = false;
     int rc = need_device(c);
     if (rc) return rc;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
@@ -1273,6 +1291,7 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
 // this function owns the device half: bvh_gpu.hip's k_place_copies, the top-level refit and the rebase pass.
 int prt_set_instance_transforms(PrtContext* c, const PrtInstance* instances, uint32_t n, uint32_t mode) {
     if (!c) return PRT_ERR_INVALID;
+    c->feat_valid = false;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     if (mode != (uint32_t)PRT_INSTANCES_REFIT && mode != (uint32_t)PRT_INSTANCES_REBUILD)
         return fail(c, PRT_ERR_INVALID, "prt_set_instance_transforms: mode is PRT_INSTANCES_REFIT or PRT_INSTANCES_REBUILD, not %u", mode);
@@ -1453,6 +1472,7 @@ int prt_instances_read(PrtContext* c, uint32_t capacity, uint32_t* n_instances, 
 
 int prt_set_camera(PrtContext* c, const PrtCameraDesc* cam) {
     if (!c || !cam) return PRT_ERR_INVALID;
+    c->feat_valid = false;
     if (!(cam->width > 0.0f) || !(cam->height > 0.0f)) return fail(c, PRT_ERR_INVALID, "camera width/height must be > 0");
     DevCamera& k = c->cam;
     k.pos = f3{cam->position[0], cam->position[1], cam->position[2]};
@@ -1468,6 +1488,7 @@ int prt_set_camera(PrtContext* c, const PrtCameraDesc* cam) {
 
 int prt_set_lens(PrtContext* c, const PrtLens* lens) {
     if (!c) return PRT_ERR_INVALID;
+    c->feat_valid = false;
     const PrtLens l = lens ? *lens : PrtLens{0.0f, 0.0f, 0.0f};
     if (std::isnan(l.fov_y) || std::isnan(l.aperture) || std::isnan(l.focus_distance))
         return fail(c, PRT_ERR_INVALID, "bad lens: NaN");
@@ -1489,6 +1510,7 @@ int prt_get_lens(PrtContext* c, PrtLens* out) {
 
 int prt_set_film(PrtContext* c, uint32_t width, uint32_t height, uint32_t rank, uint32_t world) {
     if (!c) return PRT_ERR_INVALID;
+    c->feat_valid = false;
     if (width == 0 || height == 0 || world == 0 || rank >= world)
         return fail(c, PRT_ERR_INVALID, "bad film size or partition (%ux%u, rank %u of %u)", width, height, rank, world);
     if ((uint64_t)width * height > 0x7FFFFFFFull) return fail(c, PRT_ERR_INVALID, "film too large");
@@ -1609,6 +1631,7 @@ int prt_set_environment(PrtContext* c, const PrtEnvironment* e) {
 
 int prt_set_textures(PrtContext* c, const PrtTextureSet* set) {
     if (!c) return PRT_ERR_INVALID;
+    c->feat_valid = false;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_textures: prt_set_scene has not been called");
     PrtTexTables t;  // (built aside: a refused set leaves the context's binding as it was)
     if (set) {
@@ -2182,6 +2205,195 @@ int prt_occluded_device(PrtContext* c, uint32_t n, const void* d_origins, const 
                          (uint8_t*)d_occluded);
 }
 
+// ---- first-hit features and the film denoiser (include/prt.h) ---------------------------------------
+void prt_denoise_defaults(PrtDenoise* out) {
+    if (out) *out = prt_denoise_default_config();
+}
+
+float prt_denoise_variance(float n, float A, float Q) { return prt_denoise_variance_rule(n, A, Q); }
+
+static int ensure_dn(PrtContext* c, size_t bytes) {
+    if (bytes <= c->dn_bytes) return PRT_OK;
+    free_dev(c->d_dn);
+    c->dn_bytes = 0;
+    HIPCHECK(c, hipMalloc(&c->d_dn, bytes));
+    c->dn_bytes = bytes;
+    return PRT_OK;
+}
+
+int prt_render_features(PrtContext* c) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    c->feat_valid = false;
+    const PrtTileMap& tm = c->tm;
+    const uint64_t n64 = (uint64_t)tm.W * tm.H;
+    if (n64 > (uint64_t)PRT_DENOISE_MAX_PIXELS) return fail(c, PRT_ERR_INVALID, "prt_render_features: more than 2^28 pixels");
+    const uint32_t n = (uint32_t)n64;
+    if (n > c->feat_cap) {
+        free_dev(c->feat.alb);
+        c->feat = PrtFeatureBufs{nullptr, nullptr, nullptr};
+        c->feat_cap = 0;
+        HIPCHECK(c, hipMalloc((void**)&c->feat.alb, 3 * (size_t)n * sizeof(float4)));
+        c->feat.nrm = c->feat.alb + n;
+        c->feat.pos = c->feat.alb + 2 * (size_t)n;
+        c->feat_cap = n;
+    } else {
+        c->feat.nrm = c->feat.alb + n;
+        c->feat.pos = c->feat.alb + 2 * (size_t)n;
+    }
+    // one pinhole ray through every pixel centre (k_camera_rays: fov_y honoured, no lens, no draw), the ray-query pipeline
+    // of prt_closest_hit_device, the textured albedo of prt_hit_uv while a binding textures something, then the records
+    const size_t b1 = ((size_t)n * 4 + 15) & ~(size_t)15, b3 = ((size_t)n * 12 + 15) & ~(size_t)15;
+    const size_t bh = ((size_t)n * sizeof(PrtHit) + 15) & ~(size_t)15;
+    if ((rc = ensure_scratch(c, 2 * b1 + 3 * b3 + bh + 64))) return rc;
+    char* base = (char*)c->d_scratch;
+    float* d_px = (float*)base;
+    float* d_py = (float*)(base + b1);
+    float* d_o = (float*)(base + 2 * b1);
+    float* d_d = (float*)(base + 2 * b1 + b3);
+    PrtHit* d_h = (PrtHit*)(base + 2 * b1 + 2 * b3);
+    float* d_a = (float*)(base + 2 * b1 + 2 * b3 + bh);
+    prt_launch_dn_pixel_grid(c->stream, tm.W, tm.H, d_px, d_py);
+    prt_launch_camera_rays(c->stream, c->cam, n, d_px, d_py, d_o, d_d);
+    HIPCHECK(c, hipGetLastError());
+    if ((rc = enqueue_query(c, n, d_o, d_d, nullptr, d_h, nullptr))) return rc;
+    const bool textured = tex_on(c);
+    if (textured) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), n, c->rb[0], nullptr, d_a);  // (rays and final hit ids are in rb[0])
+    prt_launch_dn_pack_features(c->stream, n, d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, c->feat);
+    HIPCHECK(c, hipGetLastError());
+    if ((rc = prt_synchronize(c))) return rc;
+    c->feat_W = tm.W;
+    c->feat_H = tm.H;
+    c->feat_valid = true;
+    return PRT_OK;
+}
+
+int prt_features_read(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->feat_valid) return fail(c, PRT_ERR_INVALID, "no current feature set (prt_render_features)");
+    int rc = need_device(c);
+    if (rc) return rc;
+    const size_t n = (size_t)c->feat_W * c->feat_H;
+    std::vector<float> rec(12 * n);
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    HIPCHECK(c, hipMemcpy(rec.data(), c->feat.alb, 3 * n * sizeof(float4), hipMemcpyDeviceToHost));
+    const float *a = rec.data(), *nr = rec.data() + 4 * n, *ps = rec.data() + 8 * n;
+    for (size_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) {
+            if (albedo) albedo[3 * i + k] = a[4 * i + k];
+            if (normal) normal[3 * i + k] = nr[4 * i + k];
+            if (position) position[3 * i + k] = ps[4 * i + k];
+        }
+        if (depth) depth[i] = ps[4 * i + 3];
+        if (prim) memcpy(&prim[i], &nr[4 * i + 3], sizeof(int32_t));
+    }
+    return PRT_OK;
+}
+
+// The iterations and the finish on the context's stream.  cv[0] holds c_0 / var_0; cv[0] and cv[1] ping-pong.
+static int enqueue_filter(PrtContext* c, const PrtDenoise& cfg, uint32_t W, uint32_t H, PrtFeatureBufs f, float4* cv0, float4* cv1,
+                          float* d_out, float* d_var_out) {
+    float4* cv[2] = {cv0, cv1};
+    int cur = 0;
+    for (uint32_t i = 0; i < cfg.iterations; ++i) {
+        const PrtAtrousParams p{W, H, 1u << i, cfg.sigma_l, cfg.sigma_z, cfg.normal_power_log2};
+        const bool staged = (c->dn_lds == 1 && p.step == 1u) || (c->dn_lds == 2 && p.step <= 2u);
+        if (!(staged && prt_launch_dn_atrous_lds(c->stream, p, cv[cur], f, cv[cur ^ 1])))
+            prt_launch_dn_atrous(c->stream, p, cv[cur], f, cv[cur ^ 1]);
+        cur ^= 1;
+    }
+    prt_launch_dn_finish(c->stream, W * H, cv[cur], f, cfg.demodulate, d_out, d_var_out);
+    HIPCHECK(c, hipGetLastError());
+    return PRT_OK;
+}
+
+// prt_denoise_device's work; ws: 5 n float4 of workspace (packed records, then the two colour + variance buffers)
+static int enqueue_denoise_arrays(PrtContext* c, const PrtDenoise& cfg, uint32_t W, uint32_t H, const float* d_mean, const float* d_var,
+                                  const float* d_albedo, const float* d_normal, const float* d_position, const int32_t* d_prim,
+                                  float* d_out, float* d_var_out, float4* ws) {
+    const uint32_t n = W * H;
+    const PrtFeatureBufs f{ws, ws + n, ws + 2 * (size_t)n};
+    float4 *cv0 = ws + 3 * (size_t)n, *cv1 = ws + 4 * (size_t)n;
+    prt_launch_dn_pack_arrays(c->stream, n, d_albedo, d_normal, d_position, d_prim, f);
+    prt_launch_dn_prepare(c->stream, n, d_mean, d_var, f, cfg.demodulate, cv0);
+    return enqueue_filter(c, cfg, W, H, f, cv0, cv1, d_out, d_var_out);
+}
+
+int prt_denoise_device(PrtContext* c, const PrtDenoise* cfg, uint32_t W, uint32_t H, const void* d_mean, const void* d_var,
+                       const void* d_albedo, const void* d_normal, const void* d_position, const void* d_prim, void* d_out,
+                       void* d_var_out) {
+    if (!c) return PRT_ERR_INVALID;
+    const char* bad = prt_denoise_check(cfg, W, H, d_mean && d_var && d_albedo && d_normal && d_position && d_prim && d_out);
+    if (bad) return fail(c, PRT_ERR_INVALID, "%s", bad);
+    int rc = need_device(c);
+    if (rc) return rc;
+    const PrtDenoise k = cfg ? *cfg : prt_denoise_default_config();
+    const size_t n = (size_t)W * H;
+    if ((rc = ensure_dn(c, 5 * n * sizeof(float4)))) return rc;
+    return enqueue_denoise_arrays(c, k, W, H, (const float*)d_mean, (const float*)d_var, (const float*)d_albedo, (const float*)d_normal,
+                                  (const float*)d_position, (const int32_t*)d_prim, (float*)d_out, (float*)d_var_out, (float4*)c->d_dn);
+}
+
+int prt_denoise(PrtContext* c, const PrtDenoise* cfg, uint32_t W, uint32_t H, const float* mean, const float* var, const float* albedo,
+                const float* normal, const float* position, const int32_t* prim, float* out, float* var_out) {
+    if (!c) return PRT_ERR_INVALID;
+    const char* bad = prt_denoise_check(cfg, W, H, mean && var && albedo && normal && position && prim && out);
+    if (bad) return fail(c, PRT_ERR_INVALID, "%s", bad);
+    int rc = need_device(c);
+    if (rc) return rc;
+    const PrtDenoise k = cfg ? *cfg : prt_denoise_default_config();
+    const size_t n = (size_t)W * H;
+    // workspace: 5 n float4 for the filter, then the staged arrays: mean, albedo, normal, position, out (3 n floats each),
+    // var, prim, var_out (n each)
+    if ((rc = ensure_dn(c, 5 * n * sizeof(float4) + 18 * n * sizeof(float)))) return rc;
+    float* st = (float*)((float4*)c->d_dn + 5 * n);
+    float *d_mean = st, *d_alb = st + 3 * n, *d_nrm = st + 6 * n, *d_pos = st + 9 * n, *d_out = st + 12 * n;
+    float *d_var = st + 15 * n, *d_vout = st + 17 * n;
+    int32_t* d_prim = (int32_t*)(st + 16 * n);
+    HIPCHECK(c, hipMemcpyAsync(d_mean, mean, n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_var, var, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_alb, albedo, n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_nrm, normal, n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_pos, position, n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_prim, prim, n * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = enqueue_denoise_arrays(c, k, W, H, d_mean, d_var, d_alb, d_nrm, d_pos, d_prim, d_out, var_out ? d_vout : nullptr,
+                                     (float4*)c->d_dn)))
+        return rc;
+    HIPCHECK(c, hipMemcpyAsync(out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIPCHECK(c, hipMemcpyAsync(var_out, d_vout, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+int prt_film_denoise(PrtContext* c, const PrtDenoise* cfg, float* rgb_out, float* var_out) {
+    if (!c) return PRT_ERR_INVALID;
+    const char* bad = prt_denoise_check(cfg, 1u, 1u, rgb_out != nullptr);
+    if (bad) return fail(c, PRT_ERR_INVALID, "%s", bad);
+    if (!c->film_stats) return fail(c, PRT_ERR_INVALID, "prt_film_denoise: film statistics are off (prt_set_film_statistics)");
+    if (c->has_film && c->tm.world != 1u)
+        return fail(c, PRT_ERR_INVALID,
+                    "prt_film_denoise: this context owns rank %u of %u of the image; the gathered film is filtered by prt_group_film_denoise",
+                    c->tm.rank, c->tm.world);
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if (!c->d_film_stat) return fail(c, PRT_ERR_INVALID, "prt_film_denoise: film statistics are off (prt_set_film_statistics)");
+    const PrtTileMap& tm = c->tm;
+    if ((uint64_t)tm.W * tm.H > (uint64_t)PRT_DENOISE_MAX_PIXELS) return fail(c, PRT_ERR_INVALID, "denoise: more than 2^28 pixels");
+    if (!c->feat_valid && (rc = prt_render_features(c))) return rc;
+    const PrtDenoise k = cfg ? *cfg : prt_denoise_default_config();
+    const size_t n = (size_t)tm.W * tm.H;
+    if ((rc = ensure_dn(c, 2 * n * sizeof(float4) + 4 * n * sizeof(float)))) return rc;
+    float4 *cv0 = (float4*)c->d_dn, *cv1 = cv0 + n;
+    float* d_out = (float*)(cv1 + n);
+    float* d_vout = d_out + 3 * n;
+    prt_launch_dn_film_prepare(c->stream, tm, c->d_film_local, c->d_film_stat, c->feat, k.demodulate, cv0);
+    if ((rc = enqueue_filter(c, k, tm.W, tm.H, c->feat, cv0, cv1, d_out, var_out ? d_vout : nullptr))) return rc;
+    HIPCHECK(c, hipMemcpyAsync(rgb_out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIPCHECK(c, hipMemcpyAsync(var_out, d_vout, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
 int prt_scatter(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* hits, uint32_t* rng_state,
                 uint32_t* scattered, float* attenuation, float* emitted, float* out_origins, float* out_dirs) {
     int rc = need_device(c);
@@ -2524,6 +2736,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "tri_min" && value >= 0 && value <= 1024) c->tune.tri_min = (uint32_t)value;  // 0 = auto
     else if (n == "refill_min" && value >= 1 && value <= 64) c->tune.refill_min = (uint32_t)value;
     else if (n == "light_buckets" && (value == 0 || value == 1)) c->light_buckets = value;
+    else if (n == "denoise_lds" && value >= 0 && value <= 2) c->dn_lds = value;
     else if (n == "exit_max" && value >= 0 && value < 64) c->tune.exit_max = (uint32_t)value;
     else return fail(c, PRT_ERR_INVALID, "unknown parameter or bad value: %s = %d", name, value);
     return PRT_OK;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/prt.h"
+#include "prt_denoise_contract.h"
 
 namespace {
 
@@ -400,6 +401,42 @@ int prt_group_render_adaptive(PrtGroup* g, const PrtAdaptive* cfg, uint32_t max_
         *out = t;
     }
     return gather_and_resolve(g);
+}
+
+int prt_group_film_denoise(PrtGroup* g, const PrtDenoise* cfg, float* rgb_out, float* var_out) {
+    if (!g || g->ctx.empty()) return PRT_ERR_INVALID;
+    const char* bad = prt_denoise_check(cfg, 1u, 1u, rgb_out != nullptr);
+    if (bad) return gfail(g, PRT_ERR_INVALID, "%s", bad);
+    if (!prt_get_film_statistics(g->ctx[0]))
+        return gfail(g, PRT_ERR_INVALID, "prt_group_film_denoise: film statistics are off (prt_group_set_film_statistics)");
+    if (!g->d_gathered) return gfail(g, PRT_ERR_INVALID, "prt_group_set_film has not been called");
+    const size_t npix = (size_t)g->W * g->H;
+    if ((bad = prt_denoise_check(cfg, g->W, g->H, true))) return gfail(g, PRT_ERR_INVALID, "%s", bad);
+    // the gathered film, and the ranks' moments summed: a pixel its rank does not own reads 0, so the sum is exact
+    std::vector<float> rgb(3 * npix), w(npix), A(npix, 0.0f), Q(npix, 0.0f), a(npix), q(npix);
+    int rc = prt_group_film_read(g, rgb.data(), w.data());
+    if (rc) return rc;
+    for (size_t r = 0; r < g->ctx.size(); ++r) {
+        if ((rc = prt_film_statistics_read(g->ctx[r], a.data(), q.data())))
+            return gfail(g, rc, "rank %zu: %s", r, prt_last_error(g->ctx[r]));
+        for (size_t i = 0; i < npix; ++i) {
+            A[i] += a[i];
+            Q[i] += q[i];
+        }
+    }
+    std::vector<float>& var = a;  // (reused)
+    for (size_t i = 0; i < npix; ++i) {
+        var[i] = prt_denoise_variance_rule(w[i], A[i], Q[i]);
+        for (int k = 0; k < 3; ++k) rgb[3 * i + k] = prt_denoise_mean_rule(rgb[3 * i + k], w[i]);
+    }
+    // features and filter on rank 0 (the scene is on every rank; the feature pass covers the whole image)
+    PrtContext* c0 = g->ctx[0];
+    std::vector<float> alb(3 * npix), nrm(3 * npix), pos(3 * npix);
+    std::vector<int32_t> prim(npix);
+    if ((rc = prt_render_features(c0)) || (rc = prt_features_read(c0, alb.data(), nrm.data(), pos.data(), nullptr, prim.data())) ||
+        (rc = prt_denoise(c0, cfg, g->W, g->H, rgb.data(), var.data(), alb.data(), nrm.data(), pos.data(), prim.data(), rgb_out, var_out)))
+        return gfail(g, rc, "rank 0: %s", prt_last_error(c0));
+    return PRT_OK;
 }
 
 int prt_group_film_read(PrtGroup* g, float* rgb_sum, float* weight) {

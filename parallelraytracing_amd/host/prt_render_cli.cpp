@@ -7,6 +7,12 @@
 //              [--ground-texture FILE.pfm] [--mesh-texture FILE.pfm] [--texture-filter nearest|bilinear]
 //              [--adaptive THRESHOLD [--min-spp N --spp-step N --max-spp N --noise-floor F]
 //               [--samples-out FILE.pfm] [--noise-out FILE.pfm]]
+//              [--denoise [--denoise-iterations N --denoise-sigma-l S --denoise-sigma-z S --no-demodulate]]
+//              [--features-out PREFIX]
+// --denoise turns the film statistics on and, beside the noisy frame, writes PREFIX_denoised.pfm / .ppm: the film through the
+// edge-avoiding a-trous filter (prt_group_film_denoise; 5 iterations, sigma_l 4, sigma_z 0.1 unless set), guided by the
+// variance of every pixel's mean and by the first hit of its centre ray.  --features-out P writes those first-hit images as
+// colour PFMs: P_albedo.pfm, P_normal.pfm, P_position.pfm and P_depth.pfm (the value in all three channels).
 // --adaptive T renders with tile-adaptive sampling (prt_render_adaptive) instead of --spp samples everywhere: --min-spp
 // (default 8) samples for every pixel, then --spp-step (8) at a time for the 8x8 tiles that still hold a pixel whose standard
 // error exceeds T x (mean luminance + --noise-floor (0.01)), up to --max-spp (64).  --samples-out writes every pixel's sample
@@ -21,6 +27,7 @@
 // path on one GPU); the frame is gathered to the first device once per frame (RCCL over xGMI, or peer copies).
 // Writes PREFIX.ppm (tonemapped RGBA8 as PPM) and PREFIX.pfm (mean radiance).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,7 +53,10 @@ int main(int argc, char** argv) {
     uint32_t light_sources = PRT_LIGHT_SOURCES_ANALYTIC;
     bool adaptive = false;
     PrtAdaptive ad{8u, 8u, 64u, 0.0f, 0.01f};
-    std::string samples_out, noise_out;
+    std::string samples_out, noise_out, features_out;
+    bool denoise = false;
+    PrtDenoise dn;
+    prt_denoise_defaults(&dn);
     std::vector<int> devices{0};
     float cam[3] = {5.0f, 5.0f, 8.0f};
     bool cam_set = false;
@@ -95,6 +105,12 @@ int main(int argc, char** argv) {
         else if (a == "--spp-step") ad.step_spp = (uint32_t)atoi(next());
         else if (a == "--max-spp") ad.max_spp = (uint32_t)atoi(next());
         else if (a == "--noise-floor") ad.noise_floor = (float)atof(next());
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iterations") dn.iterations = (uint32_t)atoi(next());
+        else if (a == "--denoise-sigma-l") dn.sigma_l = (float)atof(next());
+        else if (a == "--denoise-sigma-z") dn.sigma_z = (float)atof(next());
+        else if (a == "--no-demodulate") dn.demodulate = 0u;
+        else if (a == "--features-out") features_out = next();
         else if (a == "--samples-out") samples_out = next();
         else if (a == "--noise-out") noise_out = next();
         else if (a == "--gpus") { const int n = atoi(next()); devices.clear(); for (int d = 0; d < n; ++d) devices.push_back(d); }
@@ -145,7 +161,7 @@ int main(int argc, char** argv) {
         if (light_sources != (uint32_t)PRT_LIGHT_SOURCES_ANALYTIC) r.SetLightSources(light_sources);
         if (!env.empty()) r.SetEnvironmentPfm(env, env_share);
         if (fov_deg != 0.0 || aperture != 0.0f) r.SetLens((float)(fov_deg * 3.14159265358979323846 / 180.0), aperture, focus);
-        if (adaptive) r.SetFilmStatistics(true);
+        if (adaptive || denoise) r.SetFilmStatistics(true);
         PrtAdaptiveInfo ainfo{};
         if (frames > 1) {  // warm-up frame (first-touch allocations, clocks), then the timed ones
             r.Render(spp);
@@ -178,6 +194,35 @@ int main(int argc, char** argv) {
             std::vector<float> noise;
             r.NoiseMap(ad.noise_floor, noise);
             if (write_grey(noise_out, noise)) { fprintf(stderr, "cannot write %s\n", noise_out.c_str()); return 1; }
+        }
+        if (denoise) {
+            std::vector<float> dmean;
+            r.Denoise(&dn, dmean);
+            // the preview: Film::UpdateDisplay's Reinhard + gamma 2.2 of the denoised mean (exposure 1), on the host
+            std::vector<uint8_t> rgba((size_t)W * H * 4, 255);
+            for (size_t i = 0; i < (size_t)W * H; ++i)
+                for (int c = 0; c < 3; ++c) {
+                    const float v = dmean[3 * i + c] > 0.0f ? dmean[3 * i + c] : 0.0f;
+                    const float t = std::pow(v / (1.0f + v), 1.0f / 2.2f);
+                    rgba[4 * i + c] = (uint8_t)((t < 1.0f ? t : 1.0f) * 255.0f + 0.5f);
+                }
+            if (prt_write_pfm((out + "_denoised.pfm").c_str(), dmean.data(), W, H) || prt_write_ppm((out + "_denoised.ppm").c_str(), rgba.data(), W, H)) {
+                fprintf(stderr, "cannot write %s_denoised.pfm/.ppm\n", out.c_str());
+                return 1;
+            }
+            printf("denoised: %u iterations, sigma_l %g, sigma_z %g, demodulate %u -> %s_denoised.pfm, %s_denoised.ppm\n", dn.iterations, dn.sigma_l,
+                   dn.sigma_z, dn.demodulate, out.c_str(), out.c_str());
+        }
+        if (!features_out.empty()) {
+            prt::HipWavefrontRenderer::Features ft;
+            r.RenderFeatures(ft);
+            if (prt_write_pfm((features_out + "_albedo.pfm").c_str(), ft.albedo.data(), W, H) ||
+                prt_write_pfm((features_out + "_normal.pfm").c_str(), ft.normal.data(), W, H) ||
+                prt_write_pfm((features_out + "_position.pfm").c_str(), ft.position.data(), W, H) ||
+                write_grey(features_out + "_depth.pfm", ft.depth)) {
+                fprintf(stderr, "cannot write %s_*.pfm\n", features_out.c_str());
+                return 1;
+            }
         }
         if (adaptive)
             printf("adaptive (last frame): threshold %g, %u..%u spp in steps of %u: %u passes, %llu pixel-samples, %u tiles: %u converged, %u at the cap, %u..%u spp per tile\n",

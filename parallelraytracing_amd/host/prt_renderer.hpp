@@ -268,6 +268,33 @@ public:
                     if (((y / 8u) * tiles_x + x / 8u) % n == r) out[(size_t)y * W + x] = part[(size_t)y * W + x];
         }
     }
+    // First-hit feature images of the pixel-centre rays (prt_render_features, on the first device: every GPU holds the
+    // scene): albedo / normal / position width * height * 3 floats, depth and prim width * height.  They do not follow mirrors
+    // or glass and do not average over a lens or jitter.
+    struct Features {
+        std::vector<float> albedo, normal, position, depth;
+        std::vector<int32_t> prim;
+    };
+    void RenderFeatures(Features& out) {
+        const size_t n = (size_t)film_->width * film_->height;
+        out.albedo.assign(3 * n, 0.0f);
+        out.normal.assign(3 * n, 0.0f);
+        out.position.assign(3 * n, 0.0f);
+        out.depth.assign(n, 0.0f);
+        out.prim.assign(n, -1);
+        PrtContext* c = prt_group_context(grp_, 0);
+        if (prt_render_features(c) || prt_features_read(c, out.albedo.data(), out.normal.data(), out.position.data(), out.depth.data(), out.prim.data()))
+            throw Error(std::string("prt_render_features: ") + prt_last_error(c));
+    }
+    // The gathered film through the edge-avoiding filter (prt_group_film_denoise; include/prt.h "The filter contract"):
+    // width * height * 3 floats of denoised mean radiance, and the filtered variance if asked.  Needs SetFilmStatistics(true).
+    // cfg = nullptr: the defaults.
+    void Denoise(const PrtDenoise* cfg, std::vector<float>& rgb, std::vector<float>* var = nullptr) {
+        const size_t n = (size_t)film_->width * film_->height;
+        rgb.assign(3 * n, 0.0f);
+        if (var) var->assign(n, 0.0f);
+        check(prt_group_film_denoise(grp_, cfg, rgb.data(), var ? var->data() : nullptr));
+    }
     // The placed copies of `scene` moved (Scene::SetInstanceTransform): every GPU's top level follows, no mesh tree is
     // rebuilt and the film is not cleared.  mode: PRT_INSTANCES_REFIT (topology kept) / PRT_INSTANCES_REBUILD
     void UpdateInstances(const Scene& scene, uint32_t mode = PRT_INSTANCES_REFIT) {

@@ -378,6 +378,31 @@ def hits_to_numpy(t) -> np.ndarray:
     return a.view(np.dtype(capi.HIT_DTYPE)).reshape(-1)
 
 
+def _denoise_config(**cfg) -> "capi.PrtDenoise":
+    """PrtDenoise with the library's defaults (prt_denoise_defaults), then the given fields."""
+    k = capi.PrtDenoise()
+    capi.lib().prt_denoise_defaults(C.byref(k))
+    for name, v in cfg.items():
+        if name in ("sigma_l", "sigma_z"):
+            setattr(k, name, float(v))
+        elif name in ("iterations", "normal_power_log2", "demodulate"):
+            setattr(k, name, int(v))
+        else:
+            raise TypeError(f"denoise: unknown setting {name!r} (iterations, sigma_l, sigma_z, normal_power_log2, demodulate)")
+    return k
+
+
+def _read_features(check, ctx, W: int, H: int) -> dict:
+    L = capi.lib()
+    check(L.prt_render_features(ctx))
+    out = dict(albedo=np.zeros((H, W, 3), np.float32), normal=np.zeros((H, W, 3), np.float32),
+               position=np.zeros((H, W, 3), np.float32), depth=np.zeros((H, W), np.float32), prim=np.zeros((H, W), np.int32))
+    check(L.prt_features_read(ctx, out["albedo"].ctypes.data_as(_fp), out["normal"].ctypes.data_as(_fp),
+                              out["position"].ctypes.data_as(_fp), out["depth"].ctypes.data_as(_fp),
+                              out["prim"].ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
+
+
 class HipWavefrontRenderer:
     """The MI355X backend behind the reference's Renderer interface (src/core/renderer.h:8-16)."""
 
@@ -497,6 +522,69 @@ class HipWavefrontRenderer:
         if first_sample is None:
             self.frame_index += int(max_spp)
         return info
+
+    def render_features(self) -> dict:
+        """First-hit feature images of the pixel-centre rays (prt_render_features): albedo, normal, position (H, W, 3)
+        float32, depth (H, W) float32, prim (H, W) int32 (-1: a miss); the whole image whatever the partition.  They do not
+        follow mirrors or glass and do not average over a lens or jitter."""
+        f = self.film
+        return _read_features(self._check, self._ctx, f.width, f.height)
+
+    def denoise(self, return_variance: bool = False, **cfg):
+        """The film through the edge-avoiding filter (prt_film_denoise; include/prt.h "The filter contract"): the (H, W, 3)
+        float32 denoised mean, with return_variance also the (H, W) filtered variance.  Needs set_film_statistics(True) and a
+        film that owns the whole image.  cfg: iterations, sigma_l, sigma_z, normal_power_log2, demodulate."""
+        k = _denoise_config(**cfg)
+        f = self.film
+        out = np.zeros((f.height, f.width, 3), np.float32)
+        var = np.zeros((f.height, f.width), np.float32) if return_variance else None
+        self._check(capi.lib().prt_film_denoise(self._ctx, C.byref(k), out.ctypes.data_as(_fp),
+                                                var.ctypes.data_as(_fp) if return_variance else None))
+        return (out, var) if return_variance else out
+
+    def denoise_arrays(self, mean, var, albedo, normal, position, prim, return_variance: bool = False, **cfg):
+        """The filter on arrays of the caller's (prt_denoise / prt_denoise_device): mean, albedo, normal, position (H, W, 3)
+        float32, var (H, W) float32, prim (H, W) int32.  numpy arrays: the host form, numpy results.  torch tensors on the
+        renderer's device: the device form, tensors on that device, ordered after torch's current stream."""
+        k = _denoise_config(**cfg)
+        try:
+            import torch
+            is_t = any(isinstance(a, torch.Tensor) for a in (mean, var, albedo, normal, position, prim))
+        except ImportError:
+            is_t = False
+        if is_t:
+            H, W = (int(mean.shape[0]), int(mean.shape[1])) if isinstance(mean, torch.Tensor) and mean.dim() == 3 else (-1, -1)
+            for name, t in (("mean", mean), ("albedo", albedo), ("normal", normal), ("position", position)):
+                self._check_tensor(name, t, (H, W, 3))
+            self._check_tensor("var", var, (H, W))
+            if not isinstance(prim, torch.Tensor) or prim.dtype != torch.int32:
+                raise ValueError("prim: expected a torch.int32 tensor")
+            if prim.device != mean.device or tuple(prim.shape) != (H, W) or not prim.is_contiguous():
+                raise ValueError(f"prim: expected a contiguous ({H}, {W}) tensor on {mean.device}")
+            out = torch.empty((H, W, 3), dtype=torch.float32, device=mean.device)
+            vout = torch.empty((H, W), dtype=torch.float32, device=mean.device) if return_variance else None
+            self._on_context_stream(lambda: capi.lib().prt_denoise_device(
+                self._ctx, C.byref(k), W, H, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), C.c_void_p(albedo.data_ptr()),
+                C.c_void_p(normal.data_ptr()), C.c_void_p(position.data_ptr()), C.c_void_p(prim.data_ptr()),
+                C.c_void_p(out.data_ptr()), C.c_void_p(vout.data_ptr()) if return_variance else None))
+            return (out, vout) if return_variance else out
+        m = _f32(mean)
+        if m.ndim != 3 or m.shape[2] != 3:
+            raise ValueError(f"mean: expected an (H, W, 3) array, got {m.shape}")
+        H, W = m.shape[:2]
+        a, nr, ps, v = _f32(albedo), _f32(normal), _f32(position), _f32(var)
+        pr = np.ascontiguousarray(prim, dtype=np.int32)
+        for name, arr, shape in (("albedo", a, (H, W, 3)), ("normal", nr, (H, W, 3)), ("position", ps, (H, W, 3)),
+                                 ("var", v, (H, W)), ("prim", pr, (H, W))):
+            if arr.shape != shape:
+                raise ValueError(f"{name}: shape {arr.shape}, expected {shape}")
+        out = np.zeros((H, W, 3), np.float32)
+        vout = np.zeros((H, W), np.float32) if return_variance else None
+        self._check(capi.lib().prt_denoise(self._ctx, C.byref(k), W, H, m.ctypes.data_as(_fp), v.ctypes.data_as(_fp),
+                                           a.ctypes.data_as(_fp), nr.ctypes.data_as(_fp), ps.ctypes.data_as(_fp),
+                                           pr.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(_fp),
+                                           vout.ctypes.data_as(_fp) if return_variance else None))
+        return (out, vout) if return_variance else out
 
     def set_lighting(self, mode) -> int:
         """Light sampling toward the analytic emitters (include/prt.h PrtLighting): "off" | "mis" | "nee" or 0 | 1 | 2."""
@@ -1032,6 +1120,26 @@ class HipWavefrontGroupRenderer:
         if first_sample is None:
             self.frame_index += int(max_spp)
         return info
+
+    def render_features(self) -> dict:
+        """HipWavefrontRenderer.render_features on rank 0 (every rank holds the scene; the pass covers the whole image)."""
+        L = capi.lib()
+        ctx = L.prt_group_context(self._grp, 0)
+
+        def check(rc):
+            if rc:
+                raise PrtError(L.prt_last_error(ctx).decode())
+        return _read_features(check, ctx, self.film.width, self.film.height)
+
+    def denoise(self, return_variance: bool = False, **cfg):
+        """HipWavefrontRenderer.denoise for the gathered film (prt_group_film_denoise): the single renderer's result bit for bit."""
+        k = _denoise_config(**cfg)
+        f = self.film
+        out = np.zeros((f.height, f.width, 3), np.float32)
+        var = np.zeros((f.height, f.width), np.float32) if return_variance else None
+        self._check(capi.lib().prt_group_film_denoise(self._grp, C.byref(k), out.ctypes.data_as(_fp),
+                                                      var.ctypes.data_as(_fp) if return_variance else None))
+        return (out, var) if return_variance else out
 
     def set_lighting(self, mode) -> int:
         m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
