@@ -724,6 +724,113 @@ int prt_denoise_device(PrtContext* ctx, const PrtDenoise* cfg, uint32_t W, uint3
  * prepare kernel of its own reads the film and the moments); neither is modified by a bit. */
 int prt_film_denoise(PrtContext* ctx, const PrtDenoise* cfg, float* rgb_out, float* var_out);
 
+/* ---- Temporal reprojection: film history carried across moving frames ------------------------------
+ * The temporal half of SVGF in front of the spatial filter above: last frame's accumulated colour and luminance moments
+ * are carried to where each surface point is now, rejected at disocclusions, and blended with the new frame's samples;
+ * the blended moments give the a-trous filter a variance even where a frame holds one sample.
+ * Arithmetic: everything is fp32, one rounding per written operation, never contracted; a dot product a . b is
+ * (a.x b.x + a.y b.y) + a.z b.z; /, sqrtf and floorf are exact IEEE; the one variance line is in double, rounded once.
+ * Previous camera K (PrtCameraBasis): what prt_set_camera / prt_set_lens gave the kernels at the previous step.  K.W and
+ *   K.H must equal the image's W and H (PRT_ERR_INVALID otherwise).
+ * Inputs per current pixel p: mean colour c, film weight n, luminance sums A, Q with m1 = A / n, m2 = Q / n (both 0
+ *   where !(n > 0)), prim, and Pprev, Nprev: the first-hit point and normal AS THEY WERE in the previous frame.
+ * History per pixel q of the previous frame: colour hc, length hn (a float counted in samples), moments h1, h2, and that
+ *   frame's hP, hN, hprim.
+ * Previous surface: (Pprev, Nprev) = (P, N) unless prim lies in the primitive range [prim_base[k], prim_base[k] + the
+ *   triangles of its mesh) of placed copy k (prim_base as prt_instances_read reports it; the identity instance of the
+ *   world-space meshes is not a placed copy) and a previous transform of copy k is given.  Then, with M = mat, I = inv as
+ *   column-major 4 x 4 (PrtInstance), transform_point(M, p) component r = (M[r] p.x + M[4 + r] p.y) + (M[8 + r] p.z +
+ *   M[12 + r] * 1.0f) and lin(M, n) component r = (M[r] n.x + M[4 + r] n.y) + M[8 + r] n.z:
+ *     Pprev = transform_point(Mprev_k, transform_point(Inv_cur_k, P))
+ *     Nprev = normalize3(lin(Mprev_k, lin(Inv_cur_k, N))),  normalize3(v) = v * (1.0f / sqrtf(v . v)) per component
+ *   (rotation + uniform scale: exact in direction).  Deformed world-space meshes are not followed: prt_refit_meshes drops
+ *   the history.
+ * No history for p: there is no history at all; prim < 0 (a miss is deterministic without jitter and needs none);
+ *   !(z > 0) with v = Pprev - K.pos, z = v . K.front; the projected point is outside the image; the valid tap weight
+ *   Sb < 2^-6.  Then the outputs are c, N' = n, m1, m2, var = prt_denoise_variance(n, A, Q), status 0.
+ * Projection, aspect = K.W / K.H:  x = v . K.right;  y = v . K.up;
+ *     ndcX = (x / z) / (aspect * K.tan_fov_y);  ndcY = (y / z) / K.tan_fov_y
+ *     fx = ((ndcX + 1.0f) * 0.5f) * K.W - 0.5f;  fy = ((1.0f - ndcY) * 0.5f) * K.H - 0.5f
+ *   inside iff fx > -1 && fx < K.W && fy > -1 && fy < K.H (a NaN fails).  ix = floorf(fx), tx = fx - ix; iy, ty likewise.
+ * Taps (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) in that order; bilinear weight b = bx * by with bx =
+ *   1.0f - tx for the tap at ix and tx for the tap at ix + 1, by likewise (the x factor first).  A tap q is valid iff it is
+ *   inside the image, hn(q) > 0, hprim(q) >= 0, Nprev . hN(q) >= normal_min, and |D . Nprev| <= plane_tol * sqrtf(v . v)
+ *   with D = hP(q) - Pprev: a plane distance relative to the distance from the previous camera, free of the unit of
+ *   length.  A NaN fails each test.
+ *   Running fp32 sums in tap order over the valid taps: Sb += b; S += b * hc per channel; b * hn; b * h1; b * h2.  Each sum
+ *   divided by Sb: hc, Nh, H1, H2.
+ * Blend:  N' = fminf(Nh + n, max_history);  a = fminf(n / N', 1.0f);  c' = hc + a * (c - hc) per channel;
+ *   m1' = H1 + a * (m1 - H1);  m2' = H2 + a * (m2 - H2).
+ * Variance, in double, rounded once:  V = max(0, m2' - m1' m1');  var' = (float)(V / max(N' - 1, 1)).  Status 1.
+ * New history: c', N', m1', m2', the current frame's position, normal and prim, the current basis and the current
+ *   transforms of the placed copies.  The a-trous output is display only and is never fed back.
+ * Limits: first-hit features only (no specular chains: a mirror carries the history of its own plane); no 3 x 3 fallback
+ *   search where the four taps fail; deforming meshes reset the history; a colour border inside one plane (a texture, a
+ *   shadow edge) bleeds by up to a pixel per frame of history, because nothing geometric tells its sides apart; no
+ *   multi-GPU form.  Non-finite positions make a pixel take no history; a tap index is never read out of range.
+ *   Subnormal intermediates are outside what "bit for bit" covers.  tests/temporal_replay.py restates these lines in numpy
+ *   float32. */
+typedef struct PrtTemporal {
+    float max_history; /* >= 1, default 32: the history length is capped here, so a = n / N' never falls below n / max_history */
+    float normal_min;  /* in [-1, 1], default 0.9 */
+    float plane_tol;   /* >= 0, default 0.01 */
+} PrtTemporal;
+typedef struct PrtCameraBasis {
+    float pos[3], right[3], up[3], front[3];
+    float W, H, tan_fov_y;
+} PrtCameraBasis;
+typedef struct PrtTemporalInfo {
+    uint32_t steps;        /* successful prt_film_temporal calls since the history was last dropped */
+    uint32_t resets;       /* how often the history was dropped since the context was created (prt_temporal_reset and every
+                              call of the list below, whether a history existed or not) */
+    uint32_t hit_pixels;   /* last step: pixels with prim >= 0 */
+    uint32_t reprojected;  /* last step: pixels with status 1 */
+    uint64_t device_bytes; /* device bytes held for all of this: the history sets and the step's workspace, the motion table,
+                              and the workspace of prt_temporal_reproject / _device */
+} PrtTemporalInfo;
+#define PRT_TEMPORAL_MAX_PIXELS (1u << 28)
+void prt_temporal_defaults(PrtTemporal* out);
+/* The basis the kernels have now (prt_set_camera's right / up / normalised front, prt_set_lens' tan_fov_y).  Needs a
+ * camera. */
+int prt_get_camera_basis(PrtContext* ctx, PrtCameraBasis* out);
+/* The pure function on host arrays (c, Pprev, Nprev, hc, hP, hN, c_out: W*H*3 floats; n, A, Q, hn, h1, h2, n_out, m1_out,
+ * m2_out, var_out: W*H floats; prim, hprim: W*H int32; status: W*H bytes).  hc == NULL (then every history array is
+ * ignored): no history at all.  var_out and status may be NULL.  Synchronous; needs a device but neither a scene nor a
+ * film.  PRT_ERR_INVALID, checked before the device is asked for (host-only contexts refuse alike): max_history < 1 or
+ * NaN, normal_min outside [-1, 1] or NaN, plane_tol negative or NaN, a null array, W * H = 0 or above 2^28, H above
+ * 262140 (one launch covers 65535 blocks of 4 rows), K's W / H not the image's. */
+int prt_temporal_reproject(PrtContext* ctx, const PrtTemporal* cfg, uint32_t W, uint32_t H, const PrtCameraBasis* K, const float* c,
+                           const float* n, const float* A, const float* Q, const int32_t* prim, const float* Pprev, const float* Nprev,
+                           const float* hc, const float* hn, const float* h1, const float* h2, const float* hP, const float* hN,
+                           const int32_t* hprim, float* c_out, float* n_out, float* m1_out, float* m2_out, float* var_out,
+                           uint8_t* status);
+/* The same on DEVICE arrays, enqueued on the context's stream with no host wait. */
+int prt_temporal_reproject_device(PrtContext* ctx, const PrtTemporal* cfg, uint32_t W, uint32_t H, const PrtCameraBasis* K, const void* d_c,
+                                  const void* d_n, const void* d_A, const void* d_Q, const void* d_prim, const void* d_Pprev,
+                                  const void* d_Nprev, const void* d_hc, const void* d_hn, const void* d_h1, const void* d_h2,
+                                  const void* d_hP, const void* d_hN, const void* d_hprim, void* d_c_out, void* d_n_out, void* d_m1_out,
+                                  void* d_m2_out, void* d_var_out, void* d_status);
+/* The previous-surface rule against the context's current scene, on the host (the lines the film kernel compiles): n points
+ * with their normals and prims; prev_instances: the n_prev placed copies as they were (mat is read), n_prev = the scene's
+ * placed copies, or 0 (nothing moved: the outputs are the inputs).  Needs a scene, no device.  PRT_ERR_INVALID: a null
+ * array, n_prev neither 0 nor the scene's count. */
+int prt_temporal_prev_surface(PrtContext* ctx, uint32_t n, const float* position, const float* normal, const int32_t* prim,
+                              const PrtInstance* prev_instances, uint32_t n_prev, float* Pprev, float* Nprev);
+/* One frame step on the context's own film: c = rgb_sum / weight, n = weight, A, Q = the moments, the current feature set
+ * as the surface (rendered first if there is no current one), the history the context keeps from the previous step.  The
+ * blended frame then goes through the spatial filter (dn, the contract above, the variance being var'), or is returned
+ * as it is (dn == NULL).  rgb_out: H*W*3 floats; var_out, history_out (N' per pixel): H*W floats or NULL; host arrays,
+ * synchronous; nothing else leaves the device.  Film statistics must be on; the film must own the whole image (world_size
+ * 1: a partitioned context is refused; a group form does not exist yet).  Film and moments are not modified by a bit: the
+ * caller clears the film between frames (prt_film_clear), and a film that was not cleared is counted again.
+ * The history is dropped by prt_temporal_reset, prt_set_scene, prt_clone_scene into the context, prt_set_film,
+ * prt_refit_meshes, prt_set_textures and a prt_set_film_statistics that changes the setting; prt_set_camera, prt_set_lens
+ * and prt_set_instance_transforms keep it: motion is what it is for. */
+int prt_film_temporal(PrtContext* ctx, const PrtTemporal* cfg, const PrtDenoise* dn /* NULL: no spatial filter */, float* rgb_out,
+                      float* var_out, float* history_out);
+int prt_temporal_reset(PrtContext* ctx);
+int prt_temporal_info(PrtContext* ctx, PrtTemporalInfo* out);
+
 /* ---- Film read-back (Film::m_Accum / m_Weights; src/core/film.h:54-60) ------------------------ */
 /* Whole film to host, row-major, top-left origin; only pixels owned by this rank are non-zero. */
 int prt_film_read(PrtContext* ctx, float* rgb_sum, float* weight);

@@ -106,6 +106,25 @@ class PrtDenoise(C.Structure):
 DENOISE_MAX_PIXELS = 1 << 28  # PRT_DENOISE_MAX_PIXELS
 
 
+class PrtTemporal(C.Structure):
+    """Settings of the temporal reprojection (include/prt.h "Temporal reprojection"); prt_temporal_defaults fills the defaults."""
+    _fields_ = [("max_history", C.c_float), ("normal_min", C.c_float), ("plane_tol", C.c_float)]
+
+
+class PrtCameraBasis(C.Structure):
+    """The camera as the kernels have it (prt_get_camera_basis)."""
+    _fields_ = [("pos", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("front", C.c_float * 3),
+                ("W", C.c_float), ("H", C.c_float), ("tan_fov_y", C.c_float)]
+
+
+class PrtTemporalInfo(C.Structure):
+    _fields_ = [("steps", C.c_uint32), ("resets", C.c_uint32), ("hit_pixels", C.c_uint32), ("reprojected", C.c_uint32),
+                ("device_bytes", C.c_uint64)]
+
+
+TEMPORAL_MAX_PIXELS = 1 << 28  # PRT_TEMPORAL_MAX_PIXELS
+
+
 class PrtLighting(C.Structure):
     _fields_ = [("mode", C.c_uint32)]
 
@@ -249,6 +268,17 @@ SIGNATURES = {
     "prt_denoise_device": (C.c_int, [_vp, C.POINTER(PrtDenoise), C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "prt_film_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), _fp, _fp]),
     "prt_group_film_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), _fp, _fp]),
+    "prt_temporal_defaults": (None, [C.POINTER(PrtTemporal)]),
+    "prt_get_camera_basis": (C.c_int, [_vp, C.POINTER(PrtCameraBasis)]),
+    "prt_temporal_reproject": (C.c_int, [_vp, C.POINTER(PrtTemporal), C.c_uint32, C.c_uint32, C.POINTER(PrtCameraBasis),
+                                         _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), _fp, _fp,
+                                         _fp, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32),
+                                         _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_uint8)]),
+    "prt_temporal_reproject_device": (C.c_int, [_vp, C.POINTER(PrtTemporal), C.c_uint32, C.c_uint32, C.POINTER(PrtCameraBasis)] + [_vp] * 20),
+    "prt_temporal_prev_surface": (C.c_int, [_vp, C.c_uint32, _fp, _fp, C.POINTER(C.c_int32), C.POINTER(PrtInstance), C.c_uint32, _fp, _fp]),
+    "prt_film_temporal": (C.c_int, [_vp, C.POINTER(PrtTemporal), C.POINTER(PrtDenoise), _fp, _fp, _fp]),
+    "prt_temporal_reset": (C.c_int, [_vp]),
+    "prt_temporal_info": (C.c_int, [_vp, C.POINTER(PrtTemporalInfo)]),
     "prt_set_lighting": (C.c_int, [_vp, C.POINTER(PrtLighting)]),
     "prt_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
     "prt_light_info": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _fp]),

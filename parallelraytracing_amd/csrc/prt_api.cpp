@@ -28,6 +28,8 @@
 #include "prt_denoise_contract.h"
 #include "prt_kernels.h"
 #include "prt_scene.h"
+#include "prt_temporal.h"
+#include "prt_temporal_contract.h"
 
 namespace {
 
@@ -180,6 +182,21 @@ struct PrtContext {
     bool feat_valid = false;
     void* d_dn = nullptr;
     size_t dn_bytes = 0;
+    // ---- temporal reprojection (include/prt.h): two history sets that ping-pong, the blended planar frame, status and
+    // counters in one allocation; the basis and the placed copies' matrices of the step that wrote the history ----
+    void* d_tp = nullptr;
+    size_t tp_bytes = 0;
+    void* d_tp_mt = nullptr;           // the motion table of a step (PrtMotionTable)
+    size_t tp_mt_bytes = 0;
+    void* d_tpa = nullptr;             // workspace of the array entry points
+    size_t tpa_bytes = 0;
+    uint32_t tp_W = 0, tp_H = 0;
+    int tp_set = 0;                    // which set holds the history
+    bool tp_valid = false;
+    PrtCameraBasis tp_K{};
+    std::vector<float> tp_mats;        // 12 floats per placed copy
+    std::vector<uint32_t> tp_mt_host;  // staging of the motion table
+    PrtTemporalInfo tp_info{};
     int dn_lds = 1;  // prt_set_param("denoise_lds", n): which iterations stage their block's footprint in LDS: 0 none, 1 step 1 (default: measured faster there, slower at step 2), 2 steps 1 and 2; the same bits
 };
 
@@ -213,6 +230,14 @@ int need_device(PrtContext* c) {
     const hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return fail(c, PRT_ERR_HIP, "hipSetDevice(%d) failed: %s", c->device, hipGetErrorString(e));
     return PRT_OK;
+}
+
+void drop_history(PrtContext* c) {
+    c->tp_valid = false;
+    c->tp_info.steps = 0;
+    c->tp_info.hit_pixels = 0;
+    c->tp_info.reprojected = 0;
+    ++c->tp_info.resets;
 }
 
 void free_dev(void*& p) {
@@ -1091,6 +1116,9 @@ void prt_destroy(PrtContext* c) {
         free_dev(c->d_scratch);
         free_dev(c->feat.alb);
         free_dev(c->d_dn);
+        free_dev(c->d_tp);
+        free_dev(c->d_tp_mt);
+        free_dev(c->d_tpa);
         for (EventPair& ep : c->events) {
             (void)hipEventDestroy(ep.a);
             (void)hipEventDestroy(ep.b);
@@ -1127,6 +1155,7 @@ int prt_get_device(const PrtContext* c) { return c ? c->device : -1; }
 int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     if (!c || !s) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    drop_history(c);
     int rc = prt_check_scene_arrays(s, &c->err);
     if (rc) return rc;
     // A scene the context held before is gone whatever happens: a failure below leaves the context WITHOUT a scene (the
@@ -1174,6 +1203,7 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     if (!src->has_scene) return fail(dst, PRT_ERR_INVALID, "prt_clone_scene: the source context has no scene");
     if (dst == src) return PRT_OK;
     dst->feat_valid = false;
+    drop_history(dst);
     dst->has_scene = false;
     drop_tex(dst);
     dst->hs = src->hs;
@@ -1198,6 +1228,7 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
 // device (csrc/bvh_gpu.hip prt_gpu_bvh8_refit): records rewritten, boxes recomputed bottom-up, nodes re-quantized.
 int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     if (c) c->feat_valid = false;
+    if (c) drop_history(c);
     int rc = need_device(c);
     if (rc) return rc;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
@@ -1511,6 +1542,7 @@ int prt_get_lens(PrtContext* c, PrtLens* out) {
 int prt_set_film(PrtContext* c, uint32_t width, uint32_t height, uint32_t rank, uint32_t world) {
     if (!c) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    drop_history(c);
     if (width == 0 || height == 0 || world == 0 || rank >= world)
         return fail(c, PRT_ERR_INVALID, "bad film size or partition (%ux%u, rank %u of %u)", width, height, rank, world);
     if ((uint64_t)width * height > 0x7FFFFFFFull) return fail(c, PRT_ERR_INVALID, "film too large");
@@ -1563,6 +1595,7 @@ int prt_set_film_statistics(PrtContext* c, int on) {
     const bool want = on != 0;
     if (want == c->film_stats) return PRT_OK;
     c->film_stats = want;
+    drop_history(c);
     if (!c->has_device) return PRT_OK;  // host-only: the setting is all there is
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
@@ -1632,6 +1665,7 @@ int prt_set_environment(PrtContext* c, const PrtEnvironment* e) {
 int prt_set_textures(PrtContext* c, const PrtTextureSet* set) {
     if (!c) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    drop_history(c);
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_textures: prt_set_scene has not been called");
     PrtTexTables t;  // (built aside: a refused set leaves the context's binding as it was)
     if (set) {
@@ -2391,6 +2425,268 @@ int prt_film_denoise(PrtContext* c, const PrtDenoise* cfg, float* rgb_out, float
     HIPCHECK(c, hipMemcpyAsync(rgb_out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
     if (var_out) HIPCHECK(c, hipMemcpyAsync(var_out, d_vout, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+// ---- temporal reprojection (include/prt.h) -----------------------------------------------------------
+void prt_temporal_defaults(PrtTemporal* out) {
+    if (out) *out = prt_temporal_default_config();
+}
+
+int prt_get_camera_basis(PrtContext* c, PrtCameraBasis* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    if (!c->has_camera) return fail(c, PRT_ERR_INVALID, "prt_set_camera has not been called");
+    const DevCamera& k = c->cam;
+    *out = PrtCameraBasis{{k.pos.x, k.pos.y, k.pos.z}, {k.right.x, k.right.y, k.right.z}, {k.up.x, k.up.y, k.up.z},
+                          {k.front.x, k.front.y, k.front.z}, k.W, k.H, k.tan_fov_y};
+    return PRT_OK;
+}
+
+int prt_temporal_reset(PrtContext* c) {
+    if (!c) return PRT_ERR_INVALID;
+    drop_history(c);
+    return PRT_OK;
+}
+
+int prt_temporal_info(PrtContext* c, PrtTemporalInfo* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    *out = c->tp_info;
+    out->device_bytes = (uint64_t)c->tp_bytes + c->tp_mt_bytes + c->tpa_bytes;
+    return PRT_OK;
+}
+
+static int ensure_buf(PrtContext* c, void*& p, size_t& have, size_t bytes) {
+    if (bytes <= have) return PRT_OK;
+    free_dev(p);
+    have = 0;
+    HIPCHECK(c, hipMalloc(&p, bytes));
+    have = bytes;
+    return PRT_OK;
+}
+
+// Pixels of a record layout: n padded to a multiple of 4, so that every record array starts 16-byte aligned
+static size_t tp_padded(size_t n) { return (n + 3) & ~(size_t)3; }
+
+// A history set in 56 n bytes at base (n = tp_padded(pixels)): cn, nrm, pos (16 n each), mm (8 n)
+static PrtHistoryBufs history_at(char* base, size_t n) {
+    return PrtHistoryBufs{(float4*)base, (float2*)(base + 48 * n), (float4*)(base + 16 * n), (float4*)(base + 32 * n)};
+}
+
+// prt_temporal_reproject_device's work; ws: 136 tp_padded(n) bytes (the current frame's records, the history's, the new cn / mm)
+static int enqueue_temporal_arrays(PrtContext* c, const PrtTemporal& cfg, uint32_t W, uint32_t H, const PrtCameraBasis& K, const float* d_c,
+                                   const float* d_n, const float* d_A, const float* d_Q, const int32_t* d_prim, const float* d_P,
+                                   const float* d_N, const float* d_hc, const float* d_hn, const float* d_h1, const float* d_h2,
+                                   const float* d_hP, const float* d_hN, const int32_t* d_hprim, float* d_c_out, float* d_n_out,
+                                   float* d_m1_out, float* d_m2_out, float* d_var_out, uint8_t* d_status, char* ws) {
+    const size_t n = (size_t)W * H, np = tp_padded(n);
+    const PrtHistoryBufs cur = history_at(ws, np);
+    PrtHistoryBufs prev = history_at(ws + 56 * np, np);
+    const PrtHistoryBufs next{(float4*)(ws + 112 * np), (float2*)(ws + 128 * np), nullptr, nullptr};
+    prt_launch_tp_pack_frame(c->stream, (uint32_t)n, d_c, d_n, d_A, d_Q, d_prim, d_P, d_N, cur.cn, cur.mm, cur.nrm, cur.pos);
+    if (d_hc) prt_launch_tp_pack_frame(c->stream, (uint32_t)n, d_hc, d_hn, d_h1, d_h2, d_hprim, d_hP, d_hN, prev.cn, prev.mm, prev.nrm, prev.pos);
+    else prev = PrtHistoryBufs{nullptr, nullptr, nullptr, nullptr};
+    prt_launch_tp_reproject(c->stream, W, H, cfg, K, PrtTemporalFrame{cur.cn, cur.mm, cur.nrm, cur.pos}, prev, next, d_c_out, d_var_out, d_status,
+                            nullptr);
+    prt_launch_tp_unpack(c->stream, (uint32_t)n, next, d_n_out, d_m1_out, d_m2_out);
+    HIPCHECK(c, hipGetLastError());
+    return PRT_OK;
+}
+
+int prt_temporal_reproject_device(PrtContext* c, const PrtTemporal* cfg, uint32_t W, uint32_t H, const PrtCameraBasis* K, const void* d_c,
+                                  const void* d_n, const void* d_A, const void* d_Q, const void* d_prim, const void* d_Pprev,
+                                  const void* d_Nprev, const void* d_hc, const void* d_hn, const void* d_h1, const void* d_h2,
+                                  const void* d_hP, const void* d_hN, const void* d_hprim, void* d_c_out, void* d_n_out, void* d_m1_out,
+                                  void* d_m2_out, void* d_var_out, void* d_status) {
+    if (!c) return PRT_ERR_INVALID;
+    const bool hist_ok = !d_hc || (d_hn && d_h1 && d_h2 && d_hP && d_hN && d_hprim);
+    const char* bad = prt_temporal_check(cfg, W, H, K, K && d_c && d_n && d_A && d_Q && d_prim && d_Pprev && d_Nprev && hist_ok && d_c_out &&
+                                                            d_n_out && d_m1_out && d_m2_out);
+    if (bad) return fail(c, PRT_ERR_INVALID, "%s", bad);
+    int rc = need_device(c);
+    if (rc) return rc;
+    const PrtTemporal k = cfg ? *cfg : prt_temporal_default_config();
+    const size_t n = (size_t)W * H;
+    if ((rc = ensure_buf(c, c->d_tpa, c->tpa_bytes, 136 * tp_padded(n)))) return rc;
+    return enqueue_temporal_arrays(c, k, W, H, *K, (const float*)d_c, (const float*)d_n, (const float*)d_A, (const float*)d_Q,
+                                   (const int32_t*)d_prim, (const float*)d_Pprev, (const float*)d_Nprev, (const float*)d_hc, (const float*)d_hn,
+                                   (const float*)d_h1, (const float*)d_h2, (const float*)d_hP, (const float*)d_hN, (const int32_t*)d_hprim,
+                                   (float*)d_c_out, (float*)d_n_out, (float*)d_m1_out, (float*)d_m2_out, (float*)d_var_out, (uint8_t*)d_status,
+                                   (char*)c->d_tpa);
+}
+
+int prt_temporal_reproject(PrtContext* c, const PrtTemporal* cfg, uint32_t W, uint32_t H, const PrtCameraBasis* K, const float* cc,
+                           const float* nn, const float* A, const float* Q, const int32_t* prim, const float* Pprev, const float* Nprev,
+                           const float* hc, const float* hn, const float* h1, const float* h2, const float* hP, const float* hN,
+                           const int32_t* hprim, float* c_out, float* n_out, float* m1_out, float* m2_out, float* var_out, uint8_t* status) {
+    if (!c) return PRT_ERR_INVALID;
+    const bool hist_ok = !hc || (hn && h1 && h2 && hP && hN && hprim);
+    const char* bad =
+        prt_temporal_check(cfg, W, H, K, K && cc && nn && A && Q && prim && Pprev && Nprev && hist_ok && c_out && n_out && m1_out && m2_out);
+    if (bad) return fail(c, PRT_ERR_INVALID, "%s", bad);
+    int rc = need_device(c);
+    if (rc) return rc;
+    const PrtTemporal k = cfg ? *cfg : prt_temporal_default_config();
+    const size_t n = (size_t)W * H;
+    // workspace: 136 tp_padded(n) bytes of records, then the staged arrays: the frame (13 n floats), the history (13 n), the outputs
+    // (7 n), the status (n bytes)
+    if ((rc = ensure_buf(c, c->d_tpa, c->tpa_bytes, 136 * tp_padded(n) + 33 * n * sizeof(float) + n))) return rc;
+    float* st = (float*)((char*)c->d_tpa + 136 * tp_padded(n));
+    float *d_c = st, *d_P = st + 3 * n, *d_N = st + 6 * n, *d_n = st + 9 * n, *d_A = st + 10 * n, *d_Q = st + 11 * n;
+    int32_t* d_prim = (int32_t*)(st + 12 * n);
+    float* hs = st + 13 * n;
+    float *d_hc = hs, *d_hP = hs + 3 * n, *d_hN = hs + 6 * n, *d_hn = hs + 9 * n, *d_h1 = hs + 10 * n, *d_h2 = hs + 11 * n;
+    int32_t* d_hprim = (int32_t*)(hs + 12 * n);
+    float* os = st + 26 * n;
+    float *d_co = os, *d_no = os + 3 * n, *d_m1o = os + 4 * n, *d_m2o = os + 5 * n, *d_vo = os + 6 * n;
+    uint8_t* d_st = (uint8_t*)(os + 7 * n);
+    auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream); };
+    HIPCHECK(c, up(d_c, cc, n * 12));
+    HIPCHECK(c, up(d_P, Pprev, n * 12));
+    HIPCHECK(c, up(d_N, Nprev, n * 12));
+    HIPCHECK(c, up(d_n, nn, n * 4));
+    HIPCHECK(c, up(d_A, A, n * 4));
+    HIPCHECK(c, up(d_Q, Q, n * 4));
+    HIPCHECK(c, up(d_prim, prim, n * 4));
+    if (hc) {
+        HIPCHECK(c, up(d_hc, hc, n * 12));
+        HIPCHECK(c, up(d_hP, hP, n * 12));
+        HIPCHECK(c, up(d_hN, hN, n * 12));
+        HIPCHECK(c, up(d_hn, hn, n * 4));
+        HIPCHECK(c, up(d_h1, h1, n * 4));
+        HIPCHECK(c, up(d_h2, h2, n * 4));
+        HIPCHECK(c, up(d_hprim, hprim, n * 4));
+    }
+    if ((rc = enqueue_temporal_arrays(c, k, W, H, *K, d_c, d_n, d_A, d_Q, d_prim, d_P, d_N, hc ? d_hc : nullptr, d_hn, d_h1, d_h2, d_hP, d_hN,
+                                      d_hprim, d_co, d_no, d_m1o, d_m2o, var_out ? d_vo : nullptr, status ? d_st : nullptr, (char*)c->d_tpa)))
+        return rc;
+    auto down = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream); };
+    HIPCHECK(c, down(c_out, d_co, n * 12));
+    HIPCHECK(c, down(n_out, d_no, n * 4));
+    HIPCHECK(c, down(m1_out, d_m1o, n * 4));
+    HIPCHECK(c, down(m2_out, d_m2o, n * 4));
+    if (var_out) HIPCHECK(c, down(var_out, d_vo, n * 4));
+    if (status) HIPCHECK(c, down(status, d_st, n));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+int prt_temporal_prev_surface(PrtContext* c, uint32_t n, const float* position, const float* normal, const int32_t* prim,
+                              const PrtInstance* prev_instances, uint32_t n_prev, float* Pprev, float* Nprev) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!position || !normal || !prim || !Pprev || !Nprev || (n_prev && !prev_instances)) return fail(c, PRT_ERR_INVALID, "temporal: null array");
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    const PrtHostScene& hs = c->hs;
+    const uint32_t n_copies = (uint32_t)hs.dev_insts.size() - hs.n_world_insts;
+    if (n_prev && n_prev != n_copies)
+        return fail(c, PRT_ERR_INVALID, "prt_temporal_prev_surface: %u previous transforms for a scene of %u placed copies", n_prev, n_copies);
+    std::vector<uint32_t> range(2 * (size_t)n_prev);
+    std::vector<float> prev(12 * (size_t)n_prev);
+    for (uint32_t k = 0; k < n_prev; ++k) {
+        const DevInstance& I = hs.dev_insts[hs.n_world_insts + k];
+        range[2 * (size_t)k] = I.prim_base;
+        range[2 * (size_t)k + 1] = I.n_tris;
+        for (int col = 0; col < 4; ++col)
+            for (int r = 0; r < 3; ++r) prev[12 * (size_t)k + col * 3 + r] = prev_instances[k].mat[col * 4 + r];
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        PrtTpV3 P{position[3 * (size_t)i], position[3 * (size_t)i + 1], position[3 * (size_t)i + 2]};
+        PrtTpV3 N{normal[3 * (size_t)i], normal[3 * (size_t)i + 1], normal[3 * (size_t)i + 2]};
+        const int32_t k = prt_temporal_find_copy(range.data(), n_prev, prim[i]);
+        if (k >= 0) prt_temporal_prev_surface_rule(hs.dev_insts[hs.n_world_insts + (uint32_t)k].inv, &prev[12 * (size_t)k], P, N, &P, &N);
+        Pprev[3 * (size_t)i] = P.x, Pprev[3 * (size_t)i + 1] = P.y, Pprev[3 * (size_t)i + 2] = P.z;
+        Nprev[3 * (size_t)i] = N.x, Nprev[3 * (size_t)i + 1] = N.y, Nprev[3 * (size_t)i + 2] = N.z;
+    }
+    return PRT_OK;
+}
+
+int prt_film_temporal(PrtContext* c, const PrtTemporal* cfg, const PrtDenoise* dn, float* rgb_out, float* var_out, float* history_out) {
+    if (!c) return PRT_ERR_INVALID;
+    const char* bad = prt_temporal_check(cfg, 1u, 1u, nullptr, rgb_out != nullptr);
+    if (!bad && dn) bad = prt_denoise_check(dn, 1u, 1u, true);
+    if (bad) return fail(c, PRT_ERR_INVALID, "%s", bad);
+    if (!c->film_stats) return fail(c, PRT_ERR_INVALID, "prt_film_temporal: film statistics are off (prt_set_film_statistics)");
+    if (c->has_film && c->tm.world != 1u)
+        return fail(c, PRT_ERR_INVALID,
+                    "prt_film_temporal: this context owns rank %u of %u of the image; a group form of the temporal step does not exist yet",
+                    c->tm.rank, c->tm.world);
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if (!c->d_film_stat) return fail(c, PRT_ERR_INVALID, "prt_film_temporal: film statistics are off (prt_set_film_statistics)");
+    const PrtTileMap& tm = c->tm;
+    if ((bad = prt_temporal_check(cfg, tm.W, tm.H, nullptr, true))) return fail(c, PRT_ERR_INVALID, "%s", bad);
+    if (!c->feat_valid && (rc = prt_render_features(c))) return rc;
+    const PrtTemporal k = cfg ? *cfg : prt_temporal_default_config();
+    const size_t n = (size_t)tm.W * tm.H, np = tp_padded(n);
+    // two history sets (56 np each), the blended planar frame: mean (12 np), var (4 np), N' / m1' / m2' (12 np), the counters
+    // (16 bytes), the status (n)
+    const size_t need = 140 * np + 16 + n;
+    if (need > c->tp_bytes) {
+        c->tp_valid = false;  // (a grown buffer holds no history; prt_set_film dropped it anyway)
+        if ((rc = ensure_buf(c, c->d_tp, c->tp_bytes, need))) return rc;
+    }
+    if (c->tp_valid && (c->tp_W != tm.W || c->tp_H != tm.H)) c->tp_valid = false;
+    // (a camera whose width / height is not the film's: its basis projects into another image, so the history does not apply)
+    if (c->tp_valid && !(c->tp_K.W == (float)tm.W && c->tp_K.H == (float)tm.H)) c->tp_valid = false;
+    char* base = (char*)c->d_tp;
+    const PrtHistoryBufs prev = c->tp_valid ? history_at(base + 56 * np * (size_t)c->tp_set, np) : PrtHistoryBufs{nullptr, nullptr, nullptr, nullptr};
+    const int next_set = c->tp_valid ? (c->tp_set ^ 1) : 0;
+    const PrtHistoryBufs next = history_at(base + 56 * np * (size_t)next_set, np);
+    float* d_mean = (float*)(base + 112 * np);
+    float* d_var = d_mean + 3 * np;
+    float* d_hist = d_var + np;  // N', m1', m2' (n each)
+    uint32_t* d_counts = (uint32_t*)(base + 140 * np);
+    uint8_t* d_status = (uint8_t*)(base + 140 * np + 16);
+    // the placed copies now against their matrices at the previous step
+    const PrtHostScene& hs = c->hs;
+    const uint32_t n_copies = (uint32_t)hs.dev_insts.size() - hs.n_world_insts;
+    PrtMotionTable mt{nullptr, nullptr, 0u};
+    if (c->tp_valid && n_copies && c->tp_mats.size() == 12 * (size_t)n_copies) {
+        std::vector<uint32_t>& h = c->tp_mt_host;  // {prim_base, n_tris} x n_copies (padded to 16 bytes), then 24 floats per copy
+        const size_t r_words = (2 * (size_t)n_copies + 3) & ~(size_t)3;
+        h.assign(r_words + 24 * (size_t)n_copies, 0u);
+        for (uint32_t i = 0; i < n_copies; ++i) {
+            const DevInstance& I = hs.dev_insts[hs.n_world_insts + i];
+            h[2 * (size_t)i] = I.prim_base;
+            h[2 * (size_t)i + 1] = I.n_tris;
+            memcpy(&h[r_words + 24 * (size_t)i], I.inv, 48);
+            memcpy(&h[r_words + 24 * (size_t)i + 12], &c->tp_mats[12 * (size_t)i], 48);
+        }
+        if ((rc = ensure_buf(c, c->d_tp_mt, c->tp_mt_bytes, h.size() * 4))) return rc;
+        HIPCHECK(c, hipMemcpyAsync(c->d_tp_mt, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->stream));
+        mt = PrtMotionTable{(const uint32_t*)c->d_tp_mt, (const float4*)((const uint32_t*)c->d_tp_mt + r_words), n_copies};
+    }
+    HIPCHECK(c, hipMemsetAsync(d_counts, 0, 16, c->stream));
+    prt_launch_tp_reproject_film(c->stream, tm, k, c->tp_K, c->d_film_local, c->d_film_stat, c->feat.nrm, c->feat.pos, mt, prev, next, d_mean, d_var,
+                                 d_status, d_counts);
+    HIPCHECK(c, hipGetLastError());
+    if (history_out) prt_launch_tp_unpack(c->stream, (uint32_t)n, next, d_hist, d_hist + n, d_hist + 2 * n);
+    const float *d_rgb = d_mean, *d_v = d_var;
+    if (dn) {
+        if ((rc = ensure_dn(c, 2 * n * sizeof(float4) + 4 * n * sizeof(float)))) return rc;
+        float4 *cv0 = (float4*)c->d_dn, *cv1 = cv0 + n;
+        float* d_out = (float*)(cv1 + n);
+        prt_launch_dn_prepare(c->stream, (uint32_t)n, d_mean, d_var, c->feat, dn->demodulate, cv0);
+        if ((rc = enqueue_filter(c, *dn, tm.W, tm.H, c->feat, cv0, cv1, d_out, d_out + 3 * n))) return rc;
+        d_rgb = d_out;
+        d_v = d_out + 3 * n;
+    }
+    uint32_t counts[4] = {0u, 0u, 0u, 0u};
+    HIPCHECK(c, hipMemcpyAsync(rgb_out, d_rgb, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIPCHECK(c, hipMemcpyAsync(var_out, d_v, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (history_out) HIPCHECK(c, hipMemcpyAsync(history_out, d_hist, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    // the new history: the set just written, the basis and the copies' matrices of this frame
+    c->tp_set = next_set;
+    c->tp_W = tm.W;
+    c->tp_H = tm.H;
+    (void)prt_get_camera_basis(c, &c->tp_K);
+    c->tp_mats.resize(12 * (size_t)n_copies);
+    for (uint32_t i = 0; i < n_copies; ++i) memcpy(&c->tp_mats[12 * (size_t)i], hs.dev_insts[hs.n_world_insts + i].mat, 48);
+    c->tp_valid = true;
+    ++c->tp_info.steps;
+    c->tp_info.hit_pixels = counts[0];
+    c->tp_info.reprojected = counts[1];
     return PRT_OK;
 }
 

@@ -9,6 +9,11 @@
 //               [--samples-out FILE.pfm] [--noise-out FILE.pfm]]
 //              [--denoise [--denoise-iterations N --denoise-sigma-l S --denoise-sigma-z S --no-demodulate]]
 //              [--features-out PREFIX]
+//              [--frames N --orbit-deg D [--temporal [--temporal-max-history H]]]
+// --orbit-deg D turns --frames N into an animation: frame f is rendered with --spp samples (sample indices f * spp ...) from the
+// camera turned f * D degrees about the vertical axis through the origin, looking at the origin, on a cleared film, and written
+// as PREFIX_fNNN.pfm.  --temporal carries the film history across the frames (prt_film_temporal: reprojection, disocclusion
+// test, blend; then the a-trous filter if --denoise is given) and writes PREFIX_fNNN_temporal.pfm beside each frame.  One GPU.
 // --denoise turns the film statistics on and, beside the noisy frame, writes PREFIX_denoised.pfm / .ppm: the film through the
 // edge-avoiding a-trous filter (prt_group_film_denoise; 5 iterations, sigma_l 4, sigma_z 0.1 unless set), guided by the
 // variance of every pixel's mean and by the first hit of its centre ray.  --features-out P writes those first-hit images as
@@ -57,6 +62,10 @@ int main(int argc, char** argv) {
     bool denoise = false;
     PrtDenoise dn;
     prt_denoise_defaults(&dn);
+    bool orbit = false, temporal = false;
+    double orbit_deg = 0.0;
+    PrtTemporal tp;
+    prt_temporal_defaults(&tp);
     std::vector<int> devices{0};
     float cam[3] = {5.0f, 5.0f, 8.0f};
     bool cam_set = false;
@@ -111,6 +120,9 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-sigma-z") dn.sigma_z = (float)atof(next());
         else if (a == "--no-demodulate") dn.demodulate = 0u;
         else if (a == "--features-out") features_out = next();
+        else if (a == "--orbit-deg") { orbit_deg = atof(next()); orbit = true; }
+        else if (a == "--temporal") temporal = true;
+        else if (a == "--temporal-max-history") tp.max_history = (float)atof(next());
         else if (a == "--samples-out") samples_out = next();
         else if (a == "--noise-out") noise_out = next();
         else if (a == "--gpus") { const int n = atoi(next()); devices.clear(); for (int d = 0; d < n; ++d) devices.push_back(d); }
@@ -124,6 +136,18 @@ int main(int argc, char** argv) {
     }
     if (!adaptive && (!samples_out.empty() || !noise_out.empty())) {
         fprintf(stderr, "--samples-out and --noise-out go with --adaptive\n");
+        return 2;
+    }
+    if (temporal && !orbit) {
+        fprintf(stderr, "--temporal goes with --frames N --orbit-deg D\n");
+        return 2;
+    }
+    if (orbit && adaptive) {
+        fprintf(stderr, "--orbit-deg renders --spp samples per frame: it does not go with --adaptive\n");
+        return 2;
+    }
+    if (temporal && devices.size() != 1) {
+        fprintf(stderr, "--temporal runs on one GPU: a group form of the temporal step does not exist yet\n");
         return 2;
     }
     try {
@@ -161,7 +185,35 @@ int main(int argc, char** argv) {
         if (light_sources != (uint32_t)PRT_LIGHT_SOURCES_ANALYTIC) r.SetLightSources(light_sources);
         if (!env.empty()) r.SetEnvironmentPfm(env, env_share);
         if (fov_deg != 0.0 || aperture != 0.0f) r.SetLens((float)(fov_deg * 3.14159265358979323846 / 180.0), aperture, focus);
-        if (adaptive || denoise) r.SetFilmStatistics(true);
+        if (adaptive || denoise || temporal) r.SetFilmStatistics(true);
+        if (orbit) {  // the animation: one cleared film per frame, the camera on a circle about the vertical axis
+            std::vector<float> mean((size_t)W * H * 3), trgb;
+            for (uint32_t f = 0; f < frames; ++f) {
+                const double a = (double)f * orbit_deg * 3.14159265358979323846 / 180.0;
+                const float px = (float)((double)cam[0] * std::cos(a) + (double)cam[2] * std::sin(a));
+                const float pz = (float)(-(double)cam[0] * std::sin(a) + (double)cam[2] * std::cos(a));
+                camera.position[0] = px, camera.position[1] = cam[1], camera.position[2] = pz;
+                for (int k = 0; k < 3; ++k) camera.front[k] = -camera.position[k];
+                r.SetCamera(camera);
+                r.Clear();
+                r.SetFrameIndex(f * spp);
+                r.Render(spp);
+                r.Download();
+                for (size_t i = 0; i < (size_t)W * H; ++i)
+                    for (int c = 0; c < 3; ++c) mean[3 * i + c] = film.weights[i] > 0 ? film.accum[3 * i + c] / film.weights[i] : 0.0f;
+                char tag[32];
+                snprintf(tag, sizeof(tag), "_f%03u", f);
+                bool bad = prt_write_pfm((out + tag + ".pfm").c_str(), mean.data(), W, H) != 0;
+                if (temporal && !bad) {
+                    r.TemporalStep(&tp, denoise ? &dn : nullptr, trgb);
+                    bad = prt_write_pfm((out + tag + "_temporal.pfm").c_str(), trgb.data(), W, H) != 0;
+                }
+                if (bad) { fprintf(stderr, "cannot write %s%s*.pfm\n", out.c_str(), tag); return 1; }
+            }
+            printf("%u frames of %u spp, %g degrees per frame%s%s -> %s_fNNN%s.pfm\n", frames, spp, orbit_deg, temporal ? ", temporal" : "",
+                   temporal && denoise ? " + a-trous" : "", out.c_str(), temporal ? "[_temporal]" : "");
+            return 0;
+        }
         PrtAdaptiveInfo ainfo{};
         if (frames > 1) {  // warm-up frame (first-touch allocations, clocks), then the timed ones
             r.Render(spp);

@@ -295,6 +295,27 @@ public:
         if (var) var->assign(n, 0.0f);
         check(prt_group_film_denoise(grp_, cfg, rgb.data(), var ? var->data() : nullptr));
     }
+    // One frame step of the temporal reprojection (prt_film_temporal; include/prt.h "Temporal reprojection") on the first
+    // device, which must own the whole image (one GPU: a group form does not exist yet): the film blended with the history
+    // the context keeps, through the spatial filter if dn is not null.  width * height * 3 floats; var / history (N' per
+    // pixel) if asked.  Needs SetFilmStatistics(true); the film is not touched: Clear() it between frames and keep the sample
+    // index running with SetFrameIndex.  tp = nullptr: the defaults.
+    void TemporalStep(const PrtTemporal* tp, const PrtDenoise* dn, std::vector<float>& rgb, std::vector<float>* var = nullptr,
+                      std::vector<float>* history = nullptr) {
+        const size_t n = (size_t)film_->width * film_->height;
+        rgb.assign(3 * n, 0.0f);
+        if (var) var->assign(n, 0.0f);
+        if (history) history->assign(n, 0.0f);
+        PrtContext* c = prt_group_context(grp_, 0);
+        if (prt_film_temporal(c, tp, dn, rgb.data(), var ? var->data() : nullptr, history ? history->data() : nullptr))
+            throw Error(std::string("prt_film_temporal: ") + prt_last_error(c));
+    }
+    void TemporalReset() {
+        PrtContext* c = prt_group_context(grp_, 0);
+        if (prt_temporal_reset(c)) throw Error(std::string("prt_temporal_reset: ") + prt_last_error(c));
+    }
+    // The sample index the next Render starts at (Clear() sets it to 0): an animation keeps it running across its frames.
+    void SetFrameIndex(uint32_t first_sample) { frame_ = first_sample; }
     // The placed copies of `scene` moved (Scene::SetInstanceTransform): every GPU's top level follows, no mesh tree is
     // rebuilt and the film is not cleared.  mode: PRT_INSTANCES_REFIT (topology kept) / PRT_INSTANCES_REBUILD
     void UpdateInstances(const Scene& scene, uint32_t mode = PRT_INSTANCES_REFIT) {

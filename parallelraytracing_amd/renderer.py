@@ -392,6 +392,34 @@ def _denoise_config(**cfg) -> "capi.PrtDenoise":
     return k
 
 
+def _temporal_config(**cfg) -> "capi.PrtTemporal":
+    """PrtTemporal with the library's defaults (prt_temporal_defaults), then the given fields."""
+    k = capi.PrtTemporal()
+    capi.lib().prt_temporal_defaults(C.byref(k))
+    for name, v in cfg.items():
+        if name not in ("max_history", "normal_min", "plane_tol"):
+            raise TypeError(f"temporal: unknown setting {name!r} (max_history, normal_min, plane_tol)")
+        setattr(k, name, float(v))
+    return k
+
+
+def _basis_dict(k: "capi.PrtCameraBasis") -> dict:
+    d = {name: np.array(list(getattr(k, name)), np.float32) for name in ("pos", "right", "up", "front")}
+    d.update(W=np.float32(k.W), H=np.float32(k.H), tan_fov_y=np.float32(k.tan_fov_y))
+    return d
+
+
+def _basis_struct(d) -> "capi.PrtCameraBasis":
+    if isinstance(d, capi.PrtCameraBasis):
+        return d
+    k = capi.PrtCameraBasis()
+    for name in ("pos", "right", "up", "front"):
+        v = np.asarray(d[name], np.float32).reshape(3)
+        setattr(k, name, (C.c_float * 3)(*[float(x) for x in v]))
+    k.W, k.H, k.tan_fov_y = float(d["W"]), float(d["H"]), float(d["tan_fov_y"])
+    return k
+
+
 def _read_features(check, ctx, W: int, H: int) -> dict:
     L = capi.lib()
     check(L.prt_render_features(ctx))
@@ -585,6 +613,125 @@ class HipWavefrontRenderer:
                                            pr.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(_fp),
                                            vout.ctypes.data_as(_fp) if return_variance else None))
         return (out, vout) if return_variance else out
+
+    def camera_basis(self) -> dict:
+        """The camera as the kernels have it (prt_get_camera_basis): pos, right, up, front (3 float32 each), W, H, tan_fov_y."""
+        k = capi.PrtCameraBasis()
+        self._check(capi.lib().prt_get_camera_basis(self._ctx, C.byref(k)))
+        return _basis_dict(k)
+
+    def temporal_step(self, return_variance: bool = False, return_history: bool = False, denoise=None, **cfg):
+        """One frame step of the temporal reprojection on the film (prt_film_temporal; include/prt.h "Temporal reprojection"):
+        the (H, W, 3) float32 frame blended with the history the renderer keeps, through the spatial filter if denoise is a
+        dict of its settings ({} = the defaults; None = no filter).  With return_variance / return_history also the (H, W)
+        variance / history length.  The film is not touched: clear it between frames.  cfg: max_history, normal_min,
+        plane_tol."""
+        k = _temporal_config(**cfg)
+        dn = None if denoise is None else _denoise_config(**denoise)
+        f = self.film
+        out = np.zeros((f.height, f.width, 3), np.float32)
+        var = np.zeros((f.height, f.width), np.float32) if return_variance else None
+        hist = np.zeros((f.height, f.width), np.float32) if return_history else None
+        self._check(capi.lib().prt_film_temporal(self._ctx, C.byref(k), C.byref(dn) if dn is not None else None, out.ctypes.data_as(_fp),
+                                                 var.ctypes.data_as(_fp) if return_variance else None,
+                                                 hist.ctypes.data_as(_fp) if return_history else None))
+        res = (out,) + ((var,) if return_variance else ()) + ((hist,) if return_history else ())
+        return res if len(res) > 1 else out
+
+    def temporal_reset(self):
+        self._check(capi.lib().prt_temporal_reset(self._ctx))
+
+    def temporal_info(self) -> "capi.PrtTemporalInfo":
+        info = capi.PrtTemporalInfo()
+        self._check(capi.lib().prt_temporal_info(self._ctx, C.byref(info)))
+        return info
+
+    def temporal_prev_surface(self, position, normal, prim, prev_instances=()):
+        """prt_temporal_prev_surface: where the points (n, 3) with normals (n, 3) and prims (n,) of the current scene were
+        when its placed copies had the transforms of prev_instances (PrtInstance records; empty: nothing moved)."""
+        p, nr = _f32(position).reshape(-1, 3), _f32(normal).reshape(-1, 3)
+        pr = np.ascontiguousarray(prim, dtype=np.int32).reshape(-1)
+        if not (len(p) == len(nr) == len(pr)):
+            raise ValueError("position, normal and prim must have one entry per point")
+        insts = (PrtInstance * max(1, len(prev_instances)))(*prev_instances)
+        po, no = np.zeros_like(p), np.zeros_like(nr)
+        self._check(capi.lib().prt_temporal_prev_surface(self._ctx, len(p), p.ctypes.data_as(_fp), nr.ctypes.data_as(_fp),
+                                                         pr.ctypes.data_as(C.POINTER(C.c_int32)), insts, len(prev_instances),
+                                                         po.ctypes.data_as(_fp), no.ctypes.data_as(_fp)))
+        return po, no
+
+    def temporal_arrays(self, basis, c, n, A, Q, prim, Pprev, Nprev, history=None, return_variance: bool = True, return_status: bool = True,
+                        **cfg):
+        """The reprojection on arrays of the caller's (prt_temporal_reproject / _device).  basis: camera_basis()'s dict of the
+        PREVIOUS frame; c, Pprev, Nprev (H, W, 3) float32; n, A, Q (H, W) float32; prim (H, W) int32; history: None or a dict
+        of hc, hP, hN (H, W, 3), hn, h1, h2 (H, W) and hprim (H, W) int32.  numpy arrays: the host form, numpy results.
+        torch tensors on the renderer's device: the device form, ordered after torch's current stream.  Returns a dict of c,
+        n, m1, m2 and, if asked, var and status (uint8)."""
+        k = _temporal_config(**cfg)
+        K = _basis_struct(basis)
+        h = history or {}
+        names3, names1 = ("c", "Pprev", "Nprev"), ("n", "A", "Q")
+        cur = dict(c=c, n=n, A=A, Q=Q, prim=prim, Pprev=Pprev, Nprev=Nprev)
+        hist_names = ("hc", "hn", "h1", "h2", "hP", "hN", "hprim")
+        if history is not None and set(h) != set(hist_names):
+            raise ValueError(f"history: expected the keys {hist_names}")
+        try:
+            import torch
+            is_t = any(isinstance(a, torch.Tensor) for a in list(cur.values()) + list(h.values()))
+        except ImportError:
+            is_t = False
+        L = capi.lib()
+        if is_t:
+            H, W = (int(c.shape[0]), int(c.shape[1])) if isinstance(c, torch.Tensor) and c.dim() == 3 else (-1, -1)
+
+            def chk(name, t):
+                if name in ("prim", "hprim"):
+                    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                        raise ValueError(f"{name}: expected a torch.int32 tensor")
+                    if t.device != c.device or tuple(t.shape) != (H, W) or not t.is_contiguous():
+                        raise ValueError(f"{name}: expected a contiguous ({H}, {W}) tensor on {c.device}")
+                else:
+                    self._check_tensor(name, t, (H, W, 3) if name in names3 + ("hc", "hP", "hN") else (H, W))
+            for name, t in list(cur.items()) + list(h.items()):
+                chk(name, t)
+            o = dict(c=torch.empty((H, W, 3), dtype=torch.float32, device=c.device))
+            for name in ("n", "m1", "m2") + (("var",) if return_variance else ()):
+                o[name] = torch.empty((H, W), dtype=torch.float32, device=c.device)
+            if return_status:
+                o["status"] = torch.empty((H, W), dtype=torch.uint8, device=c.device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            self._on_context_stream(lambda: L.prt_temporal_reproject_device(
+                self._ctx, C.byref(k), W, H, C.byref(K), *[ptr(cur[x]) for x in ("c", "n", "A", "Q", "prim", "Pprev", "Nprev")],
+                *[ptr(h.get(x)) for x in hist_names], ptr(o["c"]), ptr(o["n"]), ptr(o["m1"]), ptr(o["m2"]), ptr(o.get("var")),
+                ptr(o.get("status"))))
+            return o
+        a = {x: _f32(cur[x]) for x in names3 + names1}
+        a["prim"] = np.ascontiguousarray(prim, dtype=np.int32)
+        if a["c"].ndim != 3 or a["c"].shape[2] != 3:
+            raise ValueError(f"c: expected an (H, W, 3) array, got {a['c'].shape}")
+        H, W = a["c"].shape[:2]
+        if history is not None:
+            for x in hist_names:
+                a[x] = np.ascontiguousarray(h[x], dtype=np.int32) if x == "hprim" else _f32(h[x])
+        for name, arr in a.items():
+            shape = (H, W, 3) if name in names3 + ("hc", "hP", "hN") else (H, W)
+            if arr.shape != shape:
+                raise ValueError(f"{name}: shape {arr.shape}, expected {shape}")
+        o = dict(c=np.zeros((H, W, 3), np.float32), n=np.zeros((H, W), np.float32), m1=np.zeros((H, W), np.float32),
+                 m2=np.zeros((H, W), np.float32))
+        if return_variance:
+            o["var"] = np.zeros((H, W), np.float32)
+        if return_status:
+            o["status"] = np.zeros((H, W), np.uint8)
+        ip = C.POINTER(C.c_int32)
+        ptr = lambda x, t=_fp: a[x].ctypes.data_as(t) if x in a else None
+        self._check(L.prt_temporal_reproject(
+            self._ctx, C.byref(k), W, H, C.byref(K), ptr("c"), ptr("n"), ptr("A"), ptr("Q"), ptr("prim", ip), ptr("Pprev"), ptr("Nprev"),
+            ptr("hc"), ptr("hn"), ptr("h1"), ptr("h2"), ptr("hP"), ptr("hN"), ptr("hprim", ip), o["c"].ctypes.data_as(_fp),
+            o["n"].ctypes.data_as(_fp), o["m1"].ctypes.data_as(_fp), o["m2"].ctypes.data_as(_fp),
+            o["var"].ctypes.data_as(_fp) if return_variance else None,
+            o["status"].ctypes.data_as(C.POINTER(C.c_uint8)) if return_status else None))
+        return o
 
     def set_lighting(self, mode) -> int:
         """Light sampling toward the analytic emitters (include/prt.h PrtLighting): "off" | "mis" | "nee" or 0 | 1 | 2."""
@@ -1140,6 +1287,11 @@ class HipWavefrontGroupRenderer:
         self._check(capi.lib().prt_group_film_denoise(self._grp, C.byref(k), out.ctypes.data_as(_fp),
                                                       var.ctypes.data_as(_fp) if return_variance else None))
         return (out, var) if return_variance else out
+
+    def temporal_step(self, *args, **kwargs):
+        """The temporal step has no group form yet: the refusal prt_film_temporal gives a partitioned context."""
+        raise PrtError("temporal_step: a group form of the temporal step does not exist yet (prt_film_temporal needs a film that owns the "
+                       "whole image: HipWavefrontRenderer with world_size 1)")
 
     def set_lighting(self, mode) -> int:
         m = capi.LIGHTING_MODES[mode] if isinstance(mode, str) else int(mode)
