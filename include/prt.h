@@ -631,6 +631,18 @@ int prt_film_noise_read(PrtContext* ctx, float noise_floor, float* rel_err);
 int prt_adaptive_unconverged(float n, float A, float Q, float threshold, float noise_floor); /* 1 / 0 */
 int prt_render_adaptive(PrtContext* ctx, const PrtAdaptive* cfg, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
                         PrtAdaptiveInfo* out /* may be NULL */);
+/* Function level: step 1 of the loop (select) on caller-supplied moments, through the kernels the loop launches.  n, sum_y,
+ * sum_y2: H*W floats each in Film layout (the film weight and the moments A, Q of every pixel); pixels this rank does not
+ * own are ignored.  prev: n_prev local tile indices (tile lt of this rank is global tile lt * world + rank), or NULL for
+ * local tiles 0 .. n_prev - 1.  list (room for n_prev entries) receives the entries of prev that are active by the rule,
+ * in the order of prev, and 0xFFFFFFFF in the entries past them; counts[0] = how many, counts[1] = the pixels of those
+ * tiles that lie inside the image.  Needs only
+ * prt_set_film; the context's film and statistics are neither read nor written (the images go to scratch memory in tile
+ * layout, padding lanes zero).  Synchronous on return.
+ * PRT_ERR_INVALID (checked on the host before the device is): a null array; n_prev above the local tile count; a
+ * prev[i] >= the local tile count; threshold or noise_floor negative or NaN; both 0. */
+int prt_tile_select(PrtContext* ctx, const float* n, const float* sum_y, const float* sum_y2, const uint32_t* prev /* may be NULL */,
+                    uint32_t n_prev, float threshold, float noise_floor, uint32_t* list, uint32_t* counts /* [2] */);
 
 /* ---- First-hit feature images and the edge-avoiding film denoiser ---------------------------------
  * Feature images (prt_render_features).  For every pixel of the film ONE pinhole ray through the pixel centre

@@ -258,6 +258,7 @@ SIGNATURES = {
     "prt_film_noise_read": (C.c_int, [_vp, C.c_float, _fp]),
     "prt_adaptive_unconverged": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "prt_render_adaptive": (C.c_int, [_vp, C.POINTER(PrtAdaptive), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PrtAdaptiveInfo)]),
+    "prt_tile_select": (C.c_int, [_vp, _fp, _fp, _fp, _u32p, C.c_uint32, C.c_float, C.c_float, _u32p, _u32p]),
     "prt_group_set_film_statistics": (C.c_int, [_vp, C.c_int]),
     "prt_group_render_adaptive": (C.c_int, [_vp, C.POINTER(PrtAdaptive), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PrtAdaptiveInfo)]),
     "prt_denoise_defaults": (None, [C.POINTER(PrtDenoise)]),

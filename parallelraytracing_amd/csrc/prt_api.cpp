@@ -2788,6 +2788,59 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
     return PRT_OK;
 }
 
+int prt_tile_select(PrtContext* c, const float* n, const float* sum_y, const float* sum_y2, const uint32_t* prev, uint32_t n_prev,
+                    float threshold, float noise_floor, uint32_t* list, uint32_t* counts) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_film) return fail(c, PRT_ERR_INVALID, "prt_set_film has not been called");
+    if (!n || !sum_y || !sum_y2 || !list || !counts) return fail(c, PRT_ERR_INVALID, "prt_tile_select: null array");
+    if (!(threshold >= 0.0f) || !(noise_floor >= 0.0f))
+        return fail(c, PRT_ERR_INVALID, "threshold and noise_floor must be >= 0 (and not NaN)");
+    if (threshold == 0.0f && noise_floor == 0.0f) return fail(c, PRT_ERR_INVALID, "threshold and noise_floor are both 0");
+    const PrtTileMap& tm = c->tm;
+    if (n_prev > tm.n_tiles_local)
+        return fail(c, PRT_ERR_INVALID, "prt_tile_select: n_prev %u above the %u local tiles", n_prev, tm.n_tiles_local);
+    for (uint32_t i = 0; prev && i < n_prev; ++i)
+        if (prev[i] >= tm.n_tiles_local)
+            return fail(c, PRT_ERR_INVALID, "prt_tile_select: prev[%u] = %u is not one of the %u local tiles", i, prev[i], tm.n_tiles_local);
+    int rc = need_device(c);
+    if (rc) return rc;
+    // the images in tile layout, as the film and its moments lie on the device; padding lanes (of partial tiles and of the
+    // tail) stay zero, which the rule calls unconverged (n < 2): only the kernel's `inside` test keeps them out
+    const size_t n_pix = std::max<size_t>(tm.n_pix_local, 64), n_ent = std::max(n_prev, 1u);
+    std::vector<float> film(4 * n_pix, 0.0f), stat(2 * n_pix, 0.0f);
+    for_each_local_pixel(tm, [&](size_t pl, size_t p) {
+        film[4 * pl + 3] = n[p];
+        stat[2 * pl] = sum_y[p];
+        stat[2 * pl + 1] = sum_y2[p];
+    });
+    const size_t b_film = n_pix * sizeof(float4), b_stat = n_pix * sizeof(float2), b_ent = n_ent * sizeof(uint32_t);
+    if ((rc = ensure_scratch(c, b_film + b_stat + 3 * b_ent + 64 + 4 * 16))) return rc;
+    char* base = (char*)c->d_scratch;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base + off;
+        off += (bytes + 15) & ~(size_t)15;
+        return p;
+    };
+    float4* d_film = (float4*)take(b_film);
+    float2* d_stat = (float2*)take(b_stat);
+    uint32_t* d_count = (uint32_t*)take(64);
+    uint32_t* d_prev = (uint32_t*)take(b_ent);
+    uint32_t* d_flags = (uint32_t*)take(b_ent);
+    uint32_t* d_list = (uint32_t*)take(b_ent);
+    HIPCHECK(c, hipMemcpyAsync(d_film, film.data(), b_film, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(d_stat, stat.data(), b_stat, hipMemcpyHostToDevice, c->stream));
+    if (prev && n_prev) HIPCHECK(c, hipMemcpyAsync(d_prev, prev, (size_t)n_prev * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemsetAsync(d_list, 0xFF, b_ent, c->stream));  // (an entry the kernel leaves unwritten shows as one)
+    prt_launch_tile_select(c->stream, d_film, d_stat, tm, prev ? d_prev : nullptr, n_prev, threshold, noise_floor, d_flags, d_list,
+                           d_count);
+    HIPCHECK(c, hipGetLastError());
+    HIPCHECK(c, hipMemcpyAsync(counts, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (n_prev) HIPCHECK(c, hipMemcpyAsync(list, d_list, (size_t)n_prev * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
 // ---- measurement -----------------------------------------------------------------------------------
 int prt_enable_timing(PrtContext* c, int on) {
     if (!c) return PRT_ERR_INVALID;

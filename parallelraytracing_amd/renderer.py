@@ -551,6 +551,38 @@ class HipWavefrontRenderer:
             self.frame_index += int(max_spp)
         return info
 
+    def set_film(self, film: Film):
+        """The film alone (prt_set_film), for the entry points that need neither scene nor camera."""
+        self._check(capi.lib().prt_set_film(self._ctx, film.width, film.height, self.rank, self.world_size))
+        self.film = film
+        film._renderer = self
+        self.frame_index = 0
+
+    def local_tile_count(self) -> int:
+        """8x8 tiles of the film that this rank owns (global tile g belongs to rank g % world_size)."""
+        f = self.film
+        tiles = ((f.width + 7) // 8) * ((f.height + 7) // 8)
+        return (tiles - self.rank + self.world_size - 1) // self.world_size if tiles > self.rank else 0
+
+    def tile_select(self, n, sum_y, sum_y2, threshold: float, noise_floor: float = 0.01, prev=None):
+        """prt_tile_select: the adaptive loop's selection stage on (H, W) float32 images of film weight and moments.  prev:
+        local tile indices (None: every local tile).  Returns (list, count, pixels): list has len(prev) entries, the first
+        `count` of them the active tiles in the order of prev, the others 0xFFFFFFFF."""
+        f = self.film
+        imgs = [np.ascontiguousarray(a, np.float32) for a in (n, sum_y, sum_y2)]
+        if any(a.shape != (f.height, f.width) for a in imgs):
+            raise ValueError("n, sum_y and sum_y2 must be [H, W]")
+        if prev is None:
+            n_prev, p_prev = self.local_tile_count(), None
+        else:
+            prev = np.ascontiguousarray(prev, np.uint32).reshape(-1)
+            n_prev, p_prev = prev.size, prev.ctypes.data_as(_u32p)
+        lst = np.zeros(max(n_prev, 1), np.uint32)
+        counts = np.zeros(2, np.uint32)
+        self._check(capi.lib().prt_tile_select(self._ctx, *[a.ctypes.data_as(_fp) for a in imgs], p_prev, n_prev, float(threshold),
+                                               float(noise_floor), lst.ctypes.data_as(_u32p), counts.ctypes.data_as(_u32p)))
+        return lst[:n_prev], int(counts[0]), int(counts[1])
+
     def render_features(self) -> dict:
         """First-hit feature images of the pixel-centre rays (prt_render_features): albedo, normal, position (H, W, 3)
         float32, depth (H, W) float32, prim (H, W) int32 (-1: a miss); the whole image whatever the partition.  They do not

@@ -92,13 +92,15 @@ class Replay:
 
     def run(self, min_spp, step_spp, max_spp, threshold, noise_floor, first_sample=0, ranks=1):
         """Returns a dict: counts (per tile, samples of this call), ranges (per tile: (first, count)), the info fields for
-        the whole film, margins (|lhs - t^2| / t^2 of every pixel decision made at n >= 2 with t^2 > 0) and, with ranks > 1,
-        `per_rank`: the info fields of every rank of a round-robin partition (each rank loops over its own tiles)."""
+        the whole film, margins (|lhs - t^2| / t^2 of every pixel decision made at n >= 2 with t^2 > 0), `per_rank`: the info
+        fields of every rank of a round-robin partition (each rank loops over its own tiles), and `selects`: per rank, for
+        every select of its loop in turn, (the number of tiles it was given, the global ids of those it kept, ascending)."""
         nt = len(self.tiles)
         counts = np.zeros(nt, np.int64)
         margins = []
         info = [dict(passes=0, tiles_local=len(range(r, nt, ranks)), tiles_converged=0, tiles_capped=0, stops=[],
                      pixel_samples=0) for r in range(ranks)]
+        selects = [[] for r in range(ranks)]
         if min_spp:
             for s in range(min_spp):
                 self._add(first_sample + s, range(nt))
@@ -120,6 +122,7 @@ class Replay:
                         margins.extend((np.abs(lhs - t2) / t2)[ok].ravel().tolist())
                     if unconverged(self.n[sl], self.A[sl], self.Q[sl], threshold, noise_floor).any():
                         still.append(i)
+                selects[r].append((len(active), np.array(still, np.int64)))
                 if len(still) < len(active):
                     I["tiles_converged"] += len(active) - len(still)
                     I["stops"].append(added)
@@ -145,7 +148,7 @@ class Replay:
                      tiles_converged=sum(I["tiles_converged"] for I in info), tiles_capped=sum(I["tiles_capped"] for I in info),
                      pixel_samples=sum(I["pixel_samples"] for I in info),
                      min_tile_spp=min(I["min_tile_spp"] for I in with_tiles), max_tile_spp=max(I["max_tile_spp"] for I in with_tiles))
-        return dict(counts=counts, info=total, per_rank=info, margins=np.array(margins, np.float64),
+        return dict(counts=counts, info=total, per_rank=info, margins=np.array(margins, np.float64), selects=selects,
                     ranges=[(first_sample, int(c)) for c in counts])
 
     def _pixels(self, i):
@@ -175,3 +178,14 @@ def replay_info(rep):
 # seed 3, first_sample 0, 8 / 8 / 96 samples, noise floor 0.01
 FIXTURE = dict(W=44, H=28, depth=4, seed=3, min_spp=8, step_spp=8, max_spp=96, noise_floor=0.01, cam_pos=(5.0, 5.0, 8.0))
 FIXTURE_THRESHOLDS = {"CORNELL": 0.10, "DEFAULT": 0.15}
+
+# A film whose tile lists span k_tile_compact's trips of 1024 flags: 56 x 44 = 2464 tiles, both edges partial; as 3 ranks
+# 822 / 821 / 821 local tiles.  4 / 4 / 32 samples, first_sample 0.
+FIXTURE_WIDE = dict(W=444, H=348, depth=4, seed=3, min_spp=4, step_spp=4, max_spp=32, noise_floor=0.01, cam_pos=(5.0, 5.0, 8.0),
+                    preset="CORNELL", threshold=0.2)
+
+
+def runs(ids):
+    """The number of runs of consecutive tile ids in an ascending list."""
+    ids = np.asarray(ids, np.int64)
+    return int(len(ids) > 0) + int((np.diff(ids) != 1).sum())

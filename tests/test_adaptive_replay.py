@@ -1,6 +1,7 @@
 """CPU-side tests of film statistics and tile-adaptive sampling (include/prt.h "Film statistics and adaptive sampling"):
 the exported stopping rule against its float64 restatement (tests/adaptive_replay.py), every refusal of prt_render_adaptive
-on a host-only context, the ctypes struct sizes, and the gate conditions of the two fixtures the GPU tests replay.
+on a host-only context, the ctypes struct sizes, and the gate conditions of the fixtures the GPU tests replay (the two 44 x 28
+ones below, and FIXTURE_WIDE, whose tile lists span several trips of the compaction kernel).
 
 Fixtures (adaptive_replay.FIXTURE): CORNELL at threshold 0.10 and DEFAULT at 0.15, (5, 5, 8) camera toward the origin,
 44 x 28 film, depth 4, seed 3, first_sample 0, 8 / 8 / 96 samples, noise floor 0.01.  The replay over the oracle's per-sample
@@ -155,3 +156,43 @@ def test_replay_partition_and_continuation():
     assert out3["info"]["pixel_samples"] == out["info"]["pixel_samples"]
     more = rp3.run(0, 8, 16, 0.10, fx["noise_floor"], first_sample=96)
     assert (more["counts"][out["counts"] < 96] == 0).all() and more["counts"].max() == 16
+
+
+@functools.lru_cache(maxsize=None)
+def wide_replay(ranks=1):
+    fx = ar.FIXTURE_WIDE
+    osc = util.oracle_scene(prt.Scene(fx["preset"]))
+    cam = prt.Camera(position=fx["cam_pos"], width=fx["W"], height=fx["H"]).desc()
+    frame = functools.lru_cache(maxsize=None)(lambda s: osc.render(cam, fx["W"], fx["H"], spp=1, first_sample=s, max_depth=fx["depth"],
+                                                                    seed=fx["seed"], iterative=True, n_threads=16)[0])
+    rp = ar.Replay(fx["W"], fx["H"], frame)
+    return rp, rp.run(fx["min_spp"], fx["step_spp"], fx["max_spp"], fx["threshold"], fx["noise_floor"], ranks=ranks)
+
+
+def test_wide_fixture_gate_conditions():
+    """FIXTURE_WIDE (444 x 348, 2464 tiles, CORNELL at threshold 0.2, 4 / 4 / 32 samples) is worth running only while its tile
+    lists span trips of 1024 flags, shrink, and are ragged.  Conditions on the inputs: should the oracle ever move them,
+    choose another fixture.  Measured: 7 passes; selects of 2464, 1858, 1568, 1520, 1511, 1509, 1509, 1509 tiles; 955 tiles
+    converged, 1509 at the cap; up to 219 runs of consecutive tiles in a list."""
+    fx = ar.FIXTURE_WIDE
+    rp, out = wide_replay()
+    assert len(rp.tiles) == 56 * 44 == 2464 and fx["W"] % 8 and fx["H"] % 8
+    sel = out["selects"][0]
+    print("selects", [(n_in, len(kept)) for n_in, kept in sel], "runs", [ar.runs(kept) for _, kept in sel], out["info"])
+    assert sel[0][0] == 2464 and all(sel[i + 1][0] == len(sel[i][1]) for i in range(len(sel) - 1))
+    assert sum(1 for n_in, kept in sel[1:] if n_in > 1024) >= 3          # a non-null prev and more than one trip
+    assert sum(1 for n_in, kept in sel if len(kept) < n_in) >= 3          # the output is smaller than the input
+    assert max(ar.runs(kept) for _, kept in sel) >= 100                   # ragged lists
+    counts = out["counts"]
+    assert len(np.unique(counts)) >= 3                                    # tiles stop at three or more sample counts
+    assert (counts == fx["min_spp"]).any() and (counts == fx["max_spp"]).any()
+    assert out["margins"].size and out["margins"].min() >= 1e-9          # one rounding in float64 cannot flip a tile
+    info = out["info"]
+    assert info["passes"] == len(sel) - 1 and info["tiles_converged"] + info["tiles_capped"] == 2464
+    assert info["pixel_samples"] == int(rp.n.sum()) and np.array_equal(rp.n, rp.count_map(counts))
+    # three ranks decide their own tiles: the same film, each rank's lists past one wave of 64 and ragged
+    rp3, out3 = wide_replay(3)
+    assert np.array_equal(out3["counts"], counts) and np.array_equal(rp3.accum, rp.accum)
+    assert [I["tiles_local"] for I in out3["per_rank"]] == [822, 821, 821]
+    assert all(len(s) >= 3 and s[1][0] > 64 for s in out3["selects"])
+    assert sum(I["pixel_samples"] for I in out3["per_rank"]) == info["pixel_samples"]

@@ -1,8 +1,9 @@
 """Film statistics and tile-adaptive sampling on the GPU (include/prt.h "Film statistics and adaptive sampling").  Every
 comparison is bit for bit: the moments against the numpy restatement (tests/adaptive_replay.py) of one-sample frames, the
 adaptive film, sample counts, ray totals and info against the replay of the oracle's frames, and, where no oracle exists,
-every pixel against the uniform render of its own sample count.  The film is 44 x 28 (partial tiles on two edges) unless
-stated otherwise."""
+every pixel against the uniform render of its own sample count.  The film is 44 x 28 (partial tiles on two edges, 24 tiles:
+every tile list fits one wave) unless stated otherwise; the tests "on the wide film" run 444 x 348 (2464 tiles)."""
+import concurrent.futures
 import functools
 import os
 import subprocess
@@ -134,14 +135,23 @@ def test_switching_statistics_clears_the_film_and_read_back_needs_them():
 
 
 # ---- 2. adaptive against the replay of the oracle's frames -----------------------------------------------------------------------
+def _oracle_scene_of(key):
+    """(scene, oracle keywords) of a preset name or of a key of MESH_SCENES (the oracle walks a mesh through its BVH)."""
+    if key in MESH_SCENES:
+        return MESH_SCENES[key](), dict(use_bvh=True)
+    return prt.Scene(key), dict()
+
+
 @functools.lru_cache(maxsize=None)
 def _oracle_frames(preset, cam_pos=FX["cam_pos"], w=W, h=H):
-    osc = util.oracle_scene(prt.Scene(preset))
+    scene, kw = _oracle_scene_of(preset)
+    osc = util.oracle_scene(scene)
     cam = prt.Camera(position=cam_pos, width=w, height=h).desc()
+    threads = 16 if w * h > 64 * 64 else 8
 
     @functools.lru_cache(maxsize=None)
     def frame(s):
-        f = osc.render(cam, w, h, spp=1, first_sample=s, max_depth=FX["depth"], seed=FX["seed"], iterative=True, n_threads=8)[0]
+        f = osc.render(cam, w, h, spp=1, first_sample=s, max_depth=FX["depth"], seed=FX["seed"], iterative=True, n_threads=threads, **kw)[0]
         f.setflags(write=False)
         return f
 
@@ -151,35 +161,148 @@ def _oracle_frames(preset, cam_pos=FX["cam_pos"], w=W, h=H):
 def _oracle_rect_film(preset, ranges_per_tile, cam_pos=FX["cam_pos"], w=W, h=H):
     """The oracle's film of per-tile rect renders: for every tile each (first_sample, count) range in turn; and its rays."""
     osc, cam, _ = _oracle_frames(preset, cam_pos, w, h)
+    kw = dict(use_bvh=True) if preset in MESH_SCENES else {}
     acc = np.zeros((h, w, 3), np.float32)
     wts = np.zeros((h, w), np.float32)
-    rays = 0
-    for rect, ranges in zip(ar.tiles(w, h), ranges_per_tile):
-        for first, count in ranges:
-            if count:
-                rays += osc.render(cam, w, h, spp=count, first_sample=first, max_depth=FX["depth"], seed=FX["seed"], iterative=True,
-                                   n_threads=1, rect=rect, accum=acc, weights=wts)[2]
+
+    def some(jobs):
+        rays = 0
+        for rect, ranges in jobs:
+            for first, count in ranges:
+                if count:
+                    rays += osc.render(cam, w, h, spp=count, first_sample=first, max_depth=FX["depth"], seed=FX["seed"], iterative=True,
+                                       n_threads=1, rect=rect, accum=acc, weights=wts, **kw)[2]
+        return rays
+
+    jobs = list(zip(ar.tiles(w, h), ranges_per_tile))
+    if len(jobs) <= 64:
+        rays = some(jobs)
+    else:   # tiles are disjoint and a tile's ranges stay in order within one job, so threads change no bit
+        workers = min(16, len(os.sched_getaffinity(0)))
+        with concurrent.futures.ThreadPoolExecutor(workers) as pool:
+            rays = sum(pool.map(some, [jobs[i::4 * workers] for i in range(4 * workers)]))
     return acc, wts, rays
+
+
+def _check_against_the_replay(scene, want, rp, ref_film, cfg, sif, w=W, h=H):
+    """One adaptive frame of `scene` against the replay `want` of the oracle's frames and the oracle's per-tile rect film."""
+    thr, mn, step, mx, floor = cfg
+    r, film = _renderer(scene, w=w, h=h, sif=sif)
+    info = r.render_adaptive(thr, mn, step, mx, floor)
+    r.download()
+    assert np.array_equal(film.weights, rp.count_map(want["counts"]))
+    acc, wts, rays = ref_film
+    assert _same(film.accum, acc) and _same(film.weights, wts)
+    st = r.stats()
+    assert st.rays_total == rays
+    assert st.rays_per_depth[0] == int(wts.sum()) and st.samples == mn
+    assert ar.info_dict(info) == ar.replay_info(want)
+    gA, gQ = r.film_statistics()
+    assert _same(gA, rp.A) and _same(gQ, rp.Q)
+    assert r.frame_index == mx
+    return film
 
 
 @pytest.mark.parametrize("preset", sorted(ar.FIXTURE_THRESHOLDS))
 def test_adaptive_equals_the_replay(preset):
     thr = ar.FIXTURE_THRESHOLDS[preset]
+    cfg = (thr, FX["min_spp"], FX["step_spp"], FX["max_spp"], FX["noise_floor"])
     rp = ar.Replay(W, H, _oracle_frames(preset)[2])
-    want = rp.run(FX["min_spp"], FX["step_spp"], FX["max_spp"], thr, FX["noise_floor"])
-    r, film = _renderer(prt.Scene(preset), sif=16)
-    info = r.render_adaptive(thr, FX["min_spp"], FX["step_spp"], FX["max_spp"], FX["noise_floor"])
+    want = rp.run(*cfg[1:4], thr, FX["noise_floor"])
+    ref_film = _oracle_rect_film(preset, [[rg] for rg in want["ranges"]])
+    _check_against_the_replay(prt.Scene(preset), want, rp, ref_film, cfg, 16)
+
+
+# The same on 444 x 348 (adaptive_replay.FIXTURE_WIDE: 2464 tiles, 822 / 821 / 821 as three ranks): the tile lists take several
+# trips of 1024 flags through k_tile_compact, with a carry and with ranks in every wave, and a listed batch has ~100 k compact
+# pixels (tests/test_adaptive_replay.py asserts that the fixture's lists are that long, shrink and are ragged).
+WIDE = ar.FIXTURE_WIDE
+WW, WH = WIDE["W"], WIDE["H"]
+WIDE_CFG = (WIDE["threshold"], WIDE["min_spp"], WIDE["step_spp"], WIDE["max_spp"], WIDE["noise_floor"])
+MESH_WIDE_CFG = (0.2, 4, 4, 24, 0.01)
+assert (WIDE["depth"], WIDE["seed"], WIDE["cam_pos"]) == (FX["depth"], FX["seed"], FX["cam_pos"])
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_reference(key, cfg, ranks=1):
+    """(replay, its result, the oracle's rect film) of a 444 x 348 frame; computed once, read only."""
+    thr, mn, step, mx, floor = cfg
+    rp = ar.Replay(WW, WH, _oracle_frames(key, FX["cam_pos"], WW, WH)[2])
+    want = rp.run(mn, step, mx, thr, floor, ranks=ranks)
+    ref_film = _oracle_rect_film(key, [[rg] for rg in want["ranges"]], FX["cam_pos"], WW, WH) if ranks == 1 else None
+    return rp, want, ref_film
+
+
+@pytest.mark.parametrize("sif", [16, 3])   # 3: a step of 4 samples is two listed batches, 3 + 1
+def test_adaptive_equals_the_replay_on_the_wide_film(sif):
+    rp, want, ref_film = _wide_reference(WIDE["preset"], WIDE_CFG)
+    assert sum(1 for n_in, _ in want["selects"][0][1:] if n_in > 1024) >= 3   # (test_adaptive_replay.py holds the fixture to more)
+    _check_against_the_replay(prt.Scene(WIDE["preset"]), want, rp, ref_film, WIDE_CFG, sif, WW, WH)
+
+
+def test_adaptive_equals_the_replay_on_the_wide_film_of_a_mesh_scene():
+    """RANDOM_BALLS_SMALL plus the bunny: the listed batches run the primitive BVH and the mesh tree at ~120 k compact pixels."""
+    rp, want, ref_film = _wide_reference("balls_bunny", MESH_WIDE_CFG)
+    sel = want["selects"][0]
+    print("selects", [(n_in, len(kept)) for n_in, kept in sel], "runs", max(ar.runs(kept) for _, kept in sel))
+    assert sum(1 for n_in, _ in sel[1:] if n_in > 1024) >= 3 and max(ar.runs(kept) for _, kept in sel) >= 100
+    _check_against_the_replay(_balls_and_bunny(), want, rp, ref_film, MESH_WIDE_CFG, 16, WW, WH)
+
+
+def _wide_frame(rank=0, world=1):
+    r, film = _renderer(prt.Scene(WIDE["preset"]), w=WW, h=WH, sif=16, rank=rank, world=world)
+    info = r.render_adaptive(*WIDE_CFG)
     r.download()
-    assert np.array_equal(film.weights, rp.count_map(want["counts"]))
-    acc, wts, rays = _oracle_rect_film(preset, [[rg] for rg in want["ranges"]])
-    assert _same(film.accum, acc) and _same(film.weights, wts)
-    st = r.stats()
-    assert st.rays_total == rays
-    assert st.rays_per_depth[0] == int(wts.sum()) and st.samples == FX["min_spp"]
-    assert ar.info_dict(info) == ar.replay_info(want)
-    gA, gQ = r.film_statistics()
-    assert _same(gA, rp.A) and _same(gQ, rp.Q)
-    assert r.frame_index == FX["max_spp"]
+    return film, info
+
+
+def test_three_ranks_of_the_wide_film():
+    want3 = _wide_reference(WIDE["preset"], WIDE_CFG, 3)[1]
+    one, info1 = _wide_frame()
+    acc = np.zeros_like(one.accum)
+    wts = np.zeros_like(one.weights)
+    for rank in range(3):
+        film, info = _wide_frame(rank, 3)
+        assert ar.info_dict(info) == {k: int(want3["per_rank"][rank][k]) for k in ar.INFO_FIELDS}, rank
+        assert not film.accum[film.weights == 0].any() and not wts[film.weights > 0].any()
+        acc += film.accum
+        wts += film.weights
+    assert _same(acc, one.accum) and _same(wts, one.weights)
+    assert ar.info_dict(info1) == ar.replay_info(want3)   # (the totals of the three loops are the one-rank loop's)
+    # the same three ranks as a group on one device
+    gfilm = prt.Film(WW, WH)
+    g = prt.HipWavefrontGroupRenderer([0, 0, 0], max_depth=FX["depth"], seed=FX["seed"])
+    g.Init(gfilm, prt.Scene(WIDE["preset"]), prt.Camera(position=FX["cam_pos"], width=WW, height=WH))
+    g.set_samples_in_flight(16)
+    g.set_film_statistics(True)
+    ginfo = g.render_adaptive(*WIDE_CFG)
+    g.download()
+    assert _same(gfilm.accum, one.accum) and _same(gfilm.weights, one.weights)
+    assert ar.info_dict(ginfo) == ar.replay_info(want3)
+
+
+def test_tile_lists_regrow_with_the_film():
+    """One renderer at 44 x 28, then 444 x 348, then 44 x 28 again: each frame is a fresh renderer's (the selection buffers of
+    prt_render_adaptive are sized by the first call and regrown by the second)."""
+    small_cfg = (ar.FIXTURE_THRESHOLDS["CORNELL"], FX["min_spp"], FX["step_spp"], FX["max_spp"], FX["noise_floor"])
+
+    def frame(r, film):
+        info = r.render_adaptive(*cfg)
+        r.download()
+        A, Q = r.film_statistics()
+        return film.accum.copy(), film.weights.copy(), A, Q, ar.info_dict(info)
+
+    r = None
+    for w, h, cfg in ((W, H, small_cfg), (WW, WH, WIDE_CFG), (W, H, small_cfg)):
+        fresh = frame(*_renderer(prt.Scene("CORNELL"), w=w, h=h, sif=16))
+        if r is None:
+            r, film = _renderer(prt.Scene("CORNELL"), w=w, h=h, sif=16)
+        else:
+            film = prt.Film(w, h)
+            r.Init(film, prt.Scene("CORNELL"), prt.Camera(position=FX["cam_pos"], width=w, height=h))
+        got = frame(r, film)
+        assert all(_same(a, b) for a, b in zip(got[:4], fresh[:4])) and got[4] == fresh[4], (w, h)
+        assert len(np.unique(got[1])) >= 3
 
 
 # ---- 3. self-consistency where no oracle exists ----------------------------------------------------------------------------------
@@ -231,6 +354,9 @@ def _balls_and_bunny():
     return sc
 
 
+MESH_SCENES = {"balls_bunny": _balls_and_bunny}   # oracle scene keys that are not presets
+
+
 def _env_image():
     rng = np.random.default_rng(5)
     img = rng.uniform(0.05, 0.6, (8, 16, 3)).astype(np.float32)
@@ -251,11 +377,10 @@ SELF_CASES = {
 }
 
 
-@pytest.mark.parametrize("case", sorted(SELF_CASES))
-def test_every_pixel_equals_the_uniform_render_of_its_count(case):
+def _check_every_pixel_against_uniform_renders(case, w=W, h=H):
     cs = SELF_CASES[case]
     scene = cs["scene"]()
-    r, film = _renderer(scene, cs["cam"], depth=4, setup=cs.get("setup"), sif=4)
+    r, film = _renderer(scene, cs["cam"], w, h, depth=4, setup=cs.get("setup"), sif=4)
     info = r.render_adaptive(0.12, 4, 4, 16, 0.01)
     r.download()
     acc, wts = film.accum.copy(), film.weights.copy()
@@ -264,9 +389,8 @@ def test_every_pixel_equals_the_uniform_render_of_its_count(case):
     print(case, "counts", {n: int((wts == n).sum()) for n in counts}, ar.info_dict(info))
     assert set(counts) <= {4, 8, 12, 16} and len(counts) >= 2          # (a frame with one count would test nothing)
     assert info.pixel_samples == int(wts.sum()) == st.rays_per_depth[0] and st.samples == 4
-    for y0 in range(0, H, 8):                                           # whole tiles share a count
-        for x0 in range(0, W, 8):
-            assert len(np.unique(wts[y0:y0 + 8, x0:x0 + 8])) == 1
+    for x0, y0, x1, y1 in ar.tiles(w, h):                               # whole tiles share a count
+        assert (wts[y0:y1, x0:x1] == wts[y0, x0]).all()
     if cs.get("lit"):
         assert r.light_stats().shadow_rays > 0
     r.set_film_statistics(False)   # the uniform renders run the routes they always ran
@@ -277,6 +401,21 @@ def test_every_pixel_equals_the_uniform_render_of_its_count(case):
         r.download()
         at = wts == n
         assert _same(film.accum[at], acc[at]), (case, n)
+    return wts, info
+
+
+@pytest.mark.parametrize("case", sorted(SELF_CASES))
+def test_every_pixel_equals_the_uniform_render_of_its_count(case):
+    _check_every_pixel_against_uniform_renders(case)
+
+
+def test_every_pixel_equals_the_uniform_render_of_its_count_on_the_wide_film():
+    """mis_mesh_lights at 444 x 348: a lit route (shadow rays, the lit accumulation) through listed batches of ~100 k compact
+    pixels, from lists that span trips of 1024 flags: more than 1024 tiles are still active after the first select, so the
+    second one reads a list of that length."""
+    wts, info = _check_every_pixel_against_uniform_renders("mis_mesh_lights", WW, WH)
+    beyond_min = sum(1 for x0, y0, x1, y1 in ar.tiles(WW, WH) if wts[y0, x0] > 4)
+    assert info.tiles_local == 2464 and info.passes >= 2 and beyond_min > 1024
 
 
 # ---- 4. invariance ---------------------------------------------------------------------------------------------------------------
