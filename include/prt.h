@@ -240,6 +240,65 @@ typedef struct PrtLightStats {
  *  n_emitters_unsampled then counts analytic emitters with a non-similarity transform plus candidates with positive
  *    power and an empty interval. */
 enum { PRT_LIGHT_SOURCES_ANALYTIC = 1, PRT_LIGHT_SOURCES_MESH = 2 }; /* bit mask */
+/* Clustered light selection (prt_set_light_selection; default PRT_LIGHT_SELECTION_POWER = everything above, unchanged).
+ * A property of the context like the lighting mode and the source mask: set before or after prt_set_scene, kept across it,
+ * copied by prt_clone_scene, host-only contexts too.  It takes effect only while PRT_LIGHT_SOURCES_MESH is set (only then
+ * does the integer rule select lights); with the default mask it is recorded and inactive (PrtLightClusterInfo.active).
+ * With it a light is picked in two steps: one of at most PRT_LIGHT_MAX_CLUSTERS spatial clusters by power / distance^2 to
+ * the cluster's box from the vertex, then a light inside the cluster by integer thresholds.  No hierarchy, no orientation
+ * term.  The light set, the point on the light, pdf_w, the MIS weights, the shadow rays, the RNG stream and the
+ * environment-or-lights draw (which runs first) are those of "Triangle lights" / "Environment light".
+ *  Clusters (host, double, built with every scene whatever the context's settings, and again by prt_refit_meshes /
+ *    prt_set_instance_transforms with the candidate table: equal to a fresh prt_set_scene of the moved geometry):
+ *    Members: the light set (candidates with a non-empty global interval); every member lies in exactly one cluster; at
+ *      most max_clusters clusters, none empty.
+ *    A light's world box: triangle: min / max of its fp32 world vertices; quad: the corners c +- u/2 +- v/2 from the
+ *      record in double, rounded outward; sphere: c +- R, rounded outward.  A cluster's box lo, hi (fp32): the union.
+ *    r2: the squared half diagonal of the box in double, rounded up to fp32, never below 1e-30f.
+ *    W_c: the sum of the members' global widths T_i - T_{i-1} (64-bit; the W_c sum to 2^32); phi_c = fl32(W_c / 2^32).
+ *    Inside a cluster the members are in candidate order, P_i their powers (the candidate table's doubles), S_j the
+ *      running sums: U_{c,j} = floor(S_j / S_n * 2^32 + 0.5), U_{c,0} = 0, U_{c,n} = 2^32; pmf_in = (U_j - U_{j-1}) / 2^32,
+ *      held by the kernels rounded once to fp32 (under an environment multiplied by (2^32 - T_e) / 2^32 in double before
+ *      that one rounding, as the global pmf is).  A member with an empty inner interval is never picked under clustered
+ *      selection, has pmf 0, keeps weight 1 when a scattered segment hits it and counts in n_emitters_unsampled while the
+ *      selection is active.  Light indices (prt_light_info, prt_sample_light's `light`) stay the global light set's;
+ *      prt_light_info's pmf stays the global one.
+ *    Grouping (deterministic): start with one cluster; split the cluster with the largest W_c r2_c that can be split until
+ *      max_clusters is reached or none can.  A split orders the members by box centre along an axis (ties: candidate
+ *      order) and cuts the order in two.  Where a plane perpendicular to an axis separates the members' boxes (no box
+ *      straddles it) the cut is the separating plane whose halves are nearest in power, on the first axis that has one in
+ *      descending order of the extent of the centres; otherwise the cut is the power median along the longest axis.  A
+ *      cluster whose members' centres coincide is not split.  So two emissive meshes with disjoint boxes, alone in a
+ *      scene, end in different clusters when max_clusters >= 2.
+ *  Cluster choice at a vertex x (fp32, every operation rounded once in this order, no contraction; comparisons as
+ *    selects, so that a NaN falls through), K clusters:
+ *      for c = 0 .. K-1, per axis k: t = lo_k - x_k; u = x_k - hi_k; d_k = t > u ? t : u; d_k = d_k > 0 ? d_k : 0
+ *        D2 = (d_x d_x + d_y d_y) + d_z d_z; den = D2 > r2_c ? D2 : r2_c; w_c = phi_c / den; cum_c = cum_{c-1} + w_c (cum_{-1} = 0)
+ *      total = cum_{K-1}; if !(total > 0 && total < inf): w_c = phi_c for every c, cum and total again
+ *      inv = 1.0f / total
+ *      q_c = (cum_c inv) 16777216.0f; M_c = q_c < 16777216.0f ? (uint32) q_c : 2^24 for c < K-1 (q_c >= 0, so the
+ *        conversion is the floor; a NaN gives 2^24); M_{K-1} = 2^24; M_{-1} = 0
+ *      m = r0 >> 8 (r0: the state after the light stream's first step: u0's 24-bit integer)
+ *      cluster = the smallest c with m < M_c; P_c = (M_c - M_{c-1}) 2^-24 (exact in fp32; 0 where M_c <= M_{c-1})
+ *    Member: the smallest j with r3 < U_{c,j}, r3 the 32-bit state after the stream's FOURTH step; u1, u2 stay the second
+ *    and third draws.  The light's pmf is fl(P_c pmf_in), pdf_light = pmf pdf_w as before.  P_c is both the probability
+ *    that the cluster is drawn (m uniform on 24 bits) and the number divided by; pmf_in likewise for r3.  A cluster with
+ *    M_c = M_{c-1} is never drawn from x: its lights have pmf 0 there.
+ *  A scattered segment from a Lambertian vertex x (the segment's origin) that hits light i of cluster c is weighted with
+ *    pL = fl(fl(P_c(x) pmf_in_i) pdf_w), P_c(x) from the same evaluation; pL = 0: weight 1. */
+enum { PRT_LIGHT_SELECTION_POWER = 0, PRT_LIGHT_SELECTION_CLUSTERED = 1 };
+#define PRT_LIGHT_MAX_CLUSTERS 64u
+typedef struct PrtLightSelection {
+    uint32_t mode;
+    uint32_t max_clusters; /* 1..64; 0 = default 32 */
+} PrtLightSelection;
+typedef struct PrtLightClusterInfo {
+    uint32_t mode;          /* the recorded PRT_LIGHT_SELECTION_* */
+    uint32_t active;        /* 1: CLUSTERED and PRT_LIGHT_SOURCES_MESH is set */
+    uint32_t n_clusters;    /* of the current scene (0: no scene or no light) */
+    uint32_t max_clusters;  /* what the clusters were built for (the default resolved) */
+    uint32_t n_empty_inner; /* members whose interval inside their cluster is empty */
+} PrtLightClusterInfo;
 /* Environment light (prt_set_environment; NULL = the constant `sky`, bit for bit the behaviour above).  A lat-long
  * image of radiance, piecewise constant (nearest texel), a property of the context like the lighting mode and the light
  * source mask: set before or after prt_set_scene, kept across it, copied by prt_clone_scene, host-only contexts too (they
@@ -516,6 +575,22 @@ int prt_get_light_stats(PrtContext* ctx, PrtLightStats* out);
  * the MESH bit is set.  prt_refit_meshes with the MESH bit set rebuilds that table on the host from the new vertices
  * and uploads it again: O(candidates), about 90 bytes per candidate over the bus, not part of the reported refit time. */
 int prt_set_light_sources(PrtContext* ctx, uint32_t mask);
+/* How a light is picked ("Clustered light selection" above; NULL = power, 32 clusters).  An unknown mode or
+ * max_clusters > PRT_LIGHT_MAX_CLUSTERS: PRT_ERR_INVALID, the previous selection intact.  A new max_clusters rebuilds the
+ * current scene's clusters on the host (and uploads them while the MESH bit is set). */
+int prt_set_light_selection(PrtContext* ctx, const PrtLightSelection* sel);
+int prt_light_cluster_info(PrtContext* ctx, PrtLightClusterInfo* out);
+/* The clusters of the current scene (host-only contexts too; they exist whatever the mode): n_clusters, and for the first
+ * min(n_clusters, capacity): lo, hi (3 floats each), r2, phi, the power width W_c and the number of members.  Each output
+ * may be NULL. */
+int prt_light_clusters(PrtContext* ctx, uint32_t capacity, uint32_t* n_clusters, float* lo, float* hi, float* r2, float* phi,
+                       uint64_t* power_width, uint32_t* n_members);
+/* Per light of the global light set (prt_light_info's order), the first min(n_lights, capacity): its cluster and the width
+ * U_j - U_{j-1} of its interval inside the cluster.  Host-only contexts too. */
+int prt_light_cluster_members(PrtContext* ctx, uint32_t capacity, uint32_t* n_lights, uint32_t* cluster, uint64_t* inner_width);
+/* The device's own M_c for n points (x: 3 floats each; M: n x n_clusters, point-major) through the code the render uses.
+ * Needs a device, a scene with a light and the MESH bit (the tables are on the device only then); any selection mode. */
+int prt_light_cluster_pmf(PrtContext* ctx, uint32_t n, const float* x, uint32_t* M);
 /* The environment light ("Environment light" above).  PRT_ERR_INVALID, with the previous environment intact: width or
  * height 0, width > PRT_ENV_MAX_WIDTH, height > PRT_ENV_MAX_HEIGHT, a null image, a negative or non-finite texel,
  * light_share outside [0, 1] (NaN included).  Waits for the context's stream; the light tables are uploaded again when
@@ -557,7 +632,8 @@ int prt_light_info(PrtContext* ctx, uint32_t capacity, uint32_t* n_lights, uint3
  * NEE_MIS), and w_bsdf: the weight a scattered segment from the same vertex along the same direction gets when it meets
  * that light (the render's own evaluation; 1 - w_light up to rounding).  hits[i].normal is the shading normal as
  * prt_closest_hit returns it (flipped to the incoming side).  An environment sample reports light =
- * PRT_LIGHT_ENVIRONMENT, tmax = +inf and w_bsdf = the weight of a miss along that direction. */
+ * PRT_LIGHT_ENVIRONMENT, tmax = +inf and w_bsdf = the weight of a miss along that direction.  The light is picked by the
+ * active selection (prt_set_light_selection): under clustered selection pdf_light = fl(P_c pmf_in) pdf_w. */
 int prt_sample_light(PrtContext* ctx, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,
                      float* shadow_dirs, float* tmax, uint32_t* light, float* contrib, float* pdf_light, float* pdf_bsdf,
                      float* w_light, float* w_bsdf);
@@ -990,6 +1066,7 @@ int prt_group_set_lens(PrtGroup* g, const PrtLens* lens);
 int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n);
 int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l);
 int prt_group_set_light_sources(PrtGroup* g, uint32_t mask);
+int prt_group_set_light_selection(PrtGroup* g, const PrtLightSelection* sel);
 int prt_group_set_environment(PrtGroup* g, const PrtEnvironment* env);   /* on every rank */
 int prt_group_set_textures(PrtGroup* g, const PrtTextureSet* set);     /* on every rank, after prt_group_set_scene */
 /* shadow-ray counts summed over the ranks; n_lights / n_emitters_unsampled as rank 0 has them */

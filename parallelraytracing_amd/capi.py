@@ -173,6 +173,18 @@ ENV_RNG = 0x3C6EF372            # PRT_ENV_RNG
 LIGHTING_MODES = {"off": 0, "mis": 1, "nee": 2}
 # prt_set_light_sources masks (include/prt.h PRT_LIGHT_SOURCES_*)
 LIGHT_SOURCES = {"analytic": 1, "all": 3}
+# PrtLightSelection.mode (include/prt.h PRT_LIGHT_SELECTION_*)
+LIGHT_SELECTIONS = {"power": 0, "clustered": 1}
+LIGHT_MAX_CLUSTERS = 64
+
+
+class PrtLightSelection(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("max_clusters", C.c_uint32)]
+
+
+class PrtLightClusterInfo(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("active", C.c_uint32), ("n_clusters", C.c_uint32), ("max_clusters", C.c_uint32),
+                ("n_empty_inner", C.c_uint32)]
 
 
 class PrtBvhInfo(C.Structure):
@@ -236,6 +248,12 @@ SIGNATURES = {
     "prt_group_get_light_stats": (C.c_int, [_vp, C.POINTER(PrtLightStats)]),
     "prt_group_set_light_sources": (C.c_int, [_vp, C.c_uint32]),
     "prt_set_light_sources": (C.c_int, [_vp, C.c_uint32]),
+    "prt_set_light_selection": (C.c_int, [_vp, C.POINTER(PrtLightSelection)]),
+    "prt_group_set_light_selection": (C.c_int, [_vp, C.POINTER(PrtLightSelection)]),
+    "prt_light_cluster_info": (C.c_int, [_vp, C.POINTER(PrtLightClusterInfo)]),
+    "prt_light_clusters": (C.c_int, [_vp, C.c_uint32, _u32p, _fp, _fp, _fp, _fp, C.POINTER(C.c_uint64), _u32p]),
+    "prt_light_cluster_members": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint64)]),
+    "prt_light_cluster_pmf": (C.c_int, [_vp, C.c_uint32, _fp, _u32p]),
     "prt_light_intervals": (C.c_int, [_vp, C.c_uint32, _u32p, C.POINTER(C.c_uint64)]),
     "prt_set_environment": (C.c_int, [_vp, C.POINTER(PrtEnvironment)]),
     "prt_group_set_environment": (C.c_int, [_vp, C.POINTER(PrtEnvironment)]),

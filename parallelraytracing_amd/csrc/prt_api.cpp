@@ -147,6 +147,14 @@ struct PrtContext {
     void* d_lights = nullptr;
     void* d_prim_light = nullptr;
     uint32_t light_sources = PRT_LIGHT_SOURCES_ANALYTIC;  // prt_set_light_sources
+    uint32_t light_selection = PRT_LIGHT_SELECTION_POWER;  // prt_set_light_selection (PrtLightSelection.mode)
+    uint32_t light_max_clusters = 0;   // PrtLightSelection.max_clusters as given (0: the default)
+    void* d_lc_boxes = nullptr;        // PrtLightClusters (prt_scene.h), on the device with the candidate table
+    void* d_lc_range = nullptr;
+    void* d_lc_members = nullptr;
+    void* d_lc_thr = nullptr;
+    void* d_lc_cand = nullptr;
+    void* d_lc_pmf = nullptr;          // per candidate: fl32(pmf_in (2^32 - T_e) / 2^32)
     int light_buckets = 1;             // the bucket table brackets the search over the thresholds (0: plain binary search; A/B)
     void* d_ml_records = nullptr;      // PrtMeshLights (prt_scene.h), on the device only while the MESH bit is set
     void* d_ml_thr = nullptr;
@@ -332,6 +340,14 @@ DevMeshLights dev_mesh_lights(const PrtContext* c) {
                          (const DevLightRun*)c->d_ml_runs, c->hs.ml.bucket_shift, (uint32_t)c->hs.ml.runs.size()};
 }
 
+// clustered selection takes effect only while the integer rule selects lights
+bool clusters_on(const PrtContext* c) { return mesh_lights_on(c) && c->light_selection == (uint32_t)PRT_LIGHT_SELECTION_CLUSTERED; }
+
+DevLightClusters dev_light_clusters(const PrtContext* c) {
+    return DevLightClusters{(const float4*)c->d_lc_boxes, (const uint4*)c->d_lc_range, (const uint32_t*)c->d_lc_members,
+                            (const uint32_t*)c->d_lc_thr, (const uint32_t*)c->d_lc_cand, (const float*)c->d_lc_pmf, c->hs.lc.n_clusters()};
+}
+
 uint32_t light_set_size(const PrtContext* c) {
     return mesh_lights_on(c) ? (uint32_t)c->hs.ml.visible.size() : (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4));
 }
@@ -434,6 +450,10 @@ int sync_light_tables(PrtContext* c) {
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     if (!a.empty() && c->d_lights) HIPCHECK(c, hipMemcpy(c->d_lights, a.data(), a.size() * 4, hipMemcpyHostToDevice));
     if (ml && !b.empty()) HIPCHECK(c, hipMemcpy(c->d_ml_records, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+    if (ml && c->d_lc_pmf) {
+        prt_cluster_pmf_in(c->hs, te, &a);
+        if (!a.empty()) HIPCHECK(c, hipMemcpy(c->d_lc_pmf, a.data(), a.size() * 4, hipMemcpyHostToDevice));
+    }
     c->t_env_dev = te;
     return PRT_OK;
 }
@@ -443,6 +463,12 @@ void free_mesh_lights(PrtContext* c) {
     free_dev(c->d_ml_thr);
     free_dev(c->d_ml_bucket);
     free_dev(c->d_ml_runs);
+    free_dev(c->d_lc_boxes);
+    free_dev(c->d_lc_range);
+    free_dev(c->d_lc_members);
+    free_dev(c->d_lc_thr);
+    free_dev(c->d_lc_cand);
+    free_dev(c->d_lc_pmf);
 }
 
 // the candidate table of the current scene onto the device (prt_set_light_sources, upload_scene, prt_refit_meshes)
@@ -461,6 +487,15 @@ int upload_mesh_lights(PrtContext* c) {
     HIPCHECK(c, up(&c->d_ml_thr, ml.thr.data(), ml.thr.size() * 4));
     HIPCHECK(c, up(&c->d_ml_bucket, ml.bucket.data(), ml.bucket.size() * 4));
     HIPCHECK(c, up(&c->d_ml_runs, ml.runs.data(), ml.runs.size() * sizeof(PrtLightRun)));
+    const PrtLightClusters& lc = c->hs.lc;  // (12 bytes per candidate more; they go up whatever the selection mode)
+    std::vector<float> pmf_in;
+    prt_cluster_pmf_in(c->hs, 0u, &pmf_in);
+    HIPCHECK(c, up(&c->d_lc_boxes, lc.boxes.data(), lc.boxes.size() * 4));
+    HIPCHECK(c, up(&c->d_lc_range, lc.range.data(), lc.range.size() * 4));
+    HIPCHECK(c, up(&c->d_lc_members, lc.members.data(), lc.members.size() * 4));
+    HIPCHECK(c, up(&c->d_lc_thr, lc.thr.data(), lc.thr.size() * 4));
+    HIPCHECK(c, up(&c->d_lc_cand, lc.cand_cluster.data(), lc.cand_cluster.size() * 4));
+    HIPCHECK(c, up(&c->d_lc_pmf, pmf_in.data(), pmf_in.size() * 4));
     c->t_env_dev = c->t_env_dev ? ~0ull : 0ull;  // (the records went up unscaled: a scaled default table is rewritten with them)
     return sync_light_tables(c);
 }
@@ -643,6 +678,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     PrtRouteFacts f{};
     f.lit = c->lighting != PRT_LIGHTING_OFF;
     f.mesh_lights = mesh_lights_on(c);
+    f.light_clusters = clusters_on(c);
     f.env = env_on(c);
     f.tex = tex_on(c);
     f.lens = c->lens.aperture > 0.0f;
@@ -736,6 +772,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     }
     const DevLights lt = dev_lights(c);
     const DevMeshLights mlt = dev_mesh_lights(c);
+    const DevLightClusters lct = dev_light_clusters(c);
     if (lit) {  // the paths' light radiance starts at zero (paths that end with their primary ray never get a light sample)
         if ((rc = ensure_light_state(c, n_paths))) return rc;
         HIPCHECK(c, hipMemsetAsync(c->lb.lrad, 0, (size_t)n_paths * sizeof(float4), c->stream));
@@ -801,7 +838,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         const PrtShadeInst shade = d == 0 ? plan.shade0 : plan.shade;
         const PrtShadeArgs sa{&c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, c->sampling, n_rays_known, prim_d, plan.last_segment,
                               f.env ? &denv : nullptr, f.tex ? &dtex : nullptr, lit ? &lt : nullptr, (lit && f.mesh_lights) ? &mlt : nullptr,
-                              lit ? &c->lb : nullptr};
+                              lit ? &c->lb : nullptr, (lit && f.light_clusters) ? &lct : nullptr};
         if (!prt_launch_shade(c->stream, shade, sa)) return fail(c, PRT_ERR_INVALID, "no such shade instance");
         c->shade_instance = prt_shade_name(shade);
         if (lit && (lt.n_lights || (f.env && (denv.t_all | denv.t_env)))) {
@@ -1164,7 +1201,7 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     drop_tex(c);
     PrtHostScene hs = std::move(c->hs);  // (the compiler recycles the record arrays' storage; everything else goes)
     c->hs = PrtHostScene();
-    PrtSceneOptions opt{c->pad_coeff, c->abvh_enabled != 0, nullptr};
+    PrtSceneOptions opt{c->pad_coeff, c->abvh_enabled != 0, nullptr, c->light_max_clusters};
     // device-side build (prt_set_param("gpu_build", 1 | 2)) on a context with a device: world meshes, placed copies and the
     // top-level tree.  The world meshes' device arrays (`keep`) stay with this layer: they become the scene's arrays below,
     // or go if the compiler did not take that tree after all (deeper than the kernels' stacks: the host builder's stands)
@@ -1210,6 +1247,8 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     dst->tex = src->tex;
     dst->inst_info = PrtInstanceUpdateInfo{};
     dst->light_sources = src->light_sources;
+    dst->light_selection = src->light_selection;
+    dst->light_max_clusters = src->light_max_clusters;
     dst->env = src->env;
     if (!dst->has_device) {
         fill_dev_scene(dst, 0u, 0u);
@@ -1643,6 +1682,92 @@ int prt_set_light_sources(PrtContext* c, uint32_t mask) {
     return PRT_OK;
 }
 
+int prt_set_light_selection(PrtContext* c, const PrtLightSelection* sel) {
+    if (!c) return PRT_ERR_INVALID;
+    const PrtLightSelection s = sel ? *sel : PrtLightSelection{PRT_LIGHT_SELECTION_POWER, 0u};
+    if (s.mode != (uint32_t)PRT_LIGHT_SELECTION_POWER && s.mode != (uint32_t)PRT_LIGHT_SELECTION_CLUSTERED)
+        return fail(c, PRT_ERR_INVALID, "light selection: PRT_LIGHT_SELECTION_POWER or CLUSTERED, not %u", s.mode);
+    if (s.max_clusters > PRT_LIGHT_MAX_CLUSTERS)
+        return fail(c, PRT_ERR_INVALID, "light selection: at most %u clusters, not %u", PRT_LIGHT_MAX_CLUSTERS, s.max_clusters);
+    c->light_selection = s.mode;
+    c->light_max_clusters = s.max_clusters;
+    const uint32_t K = s.max_clusters ? s.max_clusters : 32u;
+    if (!c->has_scene || c->hs.lc.max_clusters == K) return PRT_OK;
+    if (c->has_device && mesh_lights_on(c)) {  // (nothing in flight reads the tables that are about to go)
+        HIPCHECK(c, hipSetDevice(c->device));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+    }
+    prt_build_light_clusters(&c->hs, K);
+    if (c->has_device && mesh_lights_on(c)) return upload_mesh_lights(c);
+    return PRT_OK;
+}
+
+int prt_light_cluster_info(PrtContext* c, PrtLightClusterInfo* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    memset(out, 0, sizeof(*out));
+    out->mode = c->light_selection;
+    out->active = clusters_on(c) ? 1u : 0u;
+    out->max_clusters = c->light_max_clusters ? c->light_max_clusters : 32u;
+    if (!c->has_scene) return PRT_OK;
+    out->n_clusters = c->hs.lc.n_clusters();
+    out->n_empty_inner = c->hs.lc.n_empty_inner;
+    return PRT_OK;
+}
+
+int prt_light_clusters(PrtContext* c, uint32_t capacity, uint32_t* n_clusters, float* lo, float* hi, float* r2, float* phi,
+                       uint64_t* power_width, uint32_t* n_members) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    const PrtLightClusters& lc = c->hs.lc;
+    if (n_clusters) *n_clusters = lc.n_clusters();
+    for (uint32_t k = 0; k < lc.n_clusters() && k < capacity; ++k) {
+        const float* b = &lc.boxes[8 * (size_t)k];
+        if (lo) memcpy(&lo[3 * k], b, 12);
+        if (hi) memcpy(&hi[3 * k], b + 4, 12);
+        if (phi) phi[k] = b[3];
+        if (r2) r2[k] = b[7];
+        if (power_width) power_width[k] = lc.power_width[k];
+        if (n_members) n_members[k] = lc.range[4 * (size_t)k + 2];
+    }
+    return PRT_OK;
+}
+
+int prt_light_cluster_members(PrtContext* c, uint32_t capacity, uint32_t* n_lights, uint32_t* cluster, uint64_t* inner_width) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    const PrtMeshLights& ml = c->hs.ml;
+    const PrtLightClusters& lc = c->hs.lc;
+    const uint32_t n = (uint32_t)ml.visible.size();
+    if (n_lights) *n_lights = n;
+    for (uint32_t l = 0; l < n && l < capacity; ++l) {
+        const uint32_t cand = ml.visible[l];
+        if (cluster) cluster[l] = lc.cand_cluster[cand];
+        if (inner_width) inner_width[l] = lc.inner_width[lc.cand_member[cand]];
+    }
+    return PRT_OK;
+}
+
+int prt_light_cluster_pmf(PrtContext* c, uint32_t n, const float* x, uint32_t* M) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (!mesh_lights_on(c)) return fail(c, PRT_ERR_INVALID, "prt_light_cluster_pmf: the cluster tables are on the device only with PRT_LIGHT_SOURCES_MESH");
+    const uint32_t K = c->hs.lc.n_clusters();
+    if (!K) return fail(c, PRT_ERR_INVALID, "prt_light_cluster_pmf: the scene has no light");
+    if (n == 0) return PRT_OK;
+    if (!x || !M) return fail(c, PRT_ERR_INVALID, "null array");
+    const size_t bx = ((size_t)n * 12 + 15) & ~(size_t)15, bm = (size_t)n * K * 4;
+    if ((rc = ensure_scratch(c, bx + bm + 64))) return rc;
+    float* d_x = (float*)c->d_scratch;
+    uint32_t* d_m = (uint32_t*)((char*)c->d_scratch + bx);
+    HIPCHECK(c, hipMemcpyAsync(d_x, x, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    prt_launch_light_cluster_pmf(c->stream, dev_light_clusters(c), n, d_x, d_m);
+    HIPCHECK(c, hipGetLastError());
+    HIPCHECK(c, hipMemcpyAsync(M, d_m, bm, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
 int prt_set_environment(PrtContext* c, const PrtEnvironment* e) {
     if (!c) return PRT_ERR_INVALID;
     PrtEnvTables t;  // (built aside: a refused image leaves the context's environment as it was)
@@ -1809,6 +1934,7 @@ int prt_get_light_stats(PrtContext* c, PrtLightStats* out) {
     memset(out, 0, sizeof(*out));
     out->n_lights = light_set_size(c);
     out->n_emitters_unsampled = mesh_lights_on(c) ? c->hs.ml.n_emitters_unsampled : c->hs.n_emitters_unsampled;
+    if (clusters_on(c)) out->n_emitters_unsampled += c->hs.lc.n_empty_inner;
     if (!c->has_device || !c->d_light_stats) return PRT_OK;
     int rc = need_device(c);
     if (rc) return rc;
@@ -2762,10 +2888,11 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
     HIPCHECK(c, hipMemcpyAsync(d_in, in_dirs, b3, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipMemcpyAsync(d_k, keys, b1, hipMemcpyHostToDevice, c->stream));
     const DevMeshLights mlt = dev_mesh_lights(c);
+    const DevLightClusters lct = dev_light_clusters(c);
     if ((rc = sync_light_tables(c))) return rc;
     const DevEnv denv = dev_env(c);
     prt_launch_sample_light_test(c->stream, c->dsc, dev_lights(c), n, d_in, d_h, d_k, d_f, d_l, mesh_lights_on(c) ? &mlt : nullptr,
-                                 env_on(c) ? &denv : nullptr);
+                                 env_on(c) ? &denv : nullptr, clusters_on(c) ? &lct : nullptr);
     HIPCHECK(c, hipGetLastError());
     std::vector<float> f((size_t)n * 11);
     HIPCHECK(c, hipMemcpyAsync(f.data(), d_f, bf, hipMemcpyDeviceToHost, c->stream));

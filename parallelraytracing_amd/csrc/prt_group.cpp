@@ -328,6 +328,11 @@ int prt_group_set_light_sources(PrtGroup* g, uint32_t mask) {
     return for_each_rank(g, [&](uint32_t r) { return prt_set_light_sources(g->ctx[r], mask); }, false);
 }
 
+int prt_group_set_light_selection(PrtGroup* g, const PrtLightSelection* sel) {
+    if (!g) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_light_selection(g->ctx[r], sel); }, false);
+}
+
 int prt_group_set_environment(PrtGroup* g, const PrtEnvironment* env) {
     if (!g) return PRT_ERR_INVALID;
     return for_each_rank(g, [&](uint32_t r) { return prt_set_environment(g->ctx[r], env); }, false);

@@ -193,6 +193,21 @@ struct DevMeshLights {
     uint32_t bucket_shift;
     uint32_t n_runs;
 };
+// Clustered light selection (PrtLightSelection, include/prt.h; host side: PrtLightClusters, prt_scene.h), passed only to
+// the kernel instances of its own (k_shade_nee_clus*, k_sample_light_test_clus*, k_light_cluster_pmf) beside DevLights /
+// DevMeshLights.  boxes: per cluster {lo.xyz, phi}, {hi.xyz, r2}; range: per cluster {first member, last member with a
+// non-empty inner interval, members, 0}; members: cluster-major, the candidate; thr: cluster-major, U_{c,j} of member j (the
+// member of the 32-bit draw r3 is the smallest j in [first, last] with r3 < thr[j], else last); per candidate its cluster
+// (0xFFFFFFFF: none) and fl32 pmf_in (with the environment's factor).
+struct DevLightClusters {
+    const float4* boxes;
+    const uint4* range;
+    const uint32_t* members;
+    const uint32_t* thr;
+    const uint32_t* cand_cluster;
+    const float* cand_pmf_in;
+    uint32_t n_clusters;
+};
 // Environment light (PrtEnvironment, include/prt.h; host side: PrtEnvTables, prt_scene.h), passed only to the kernel
 // instances of its own (k_raygen_env, k_shade_env, k_shade_nee_env, k_shade_nee_mesh_env): DevScene and the other instances
 // stay as they are.  texels: rgb, pdf_w x sin(theta) of the texel; row_thr / col_thr: the 32-bit thresholds, searched up to
@@ -287,6 +302,7 @@ struct PrtShadeArgs {
     const DevLights* lights;           // lighting modes: the shade step takes a light sample per Lambertian vertex (shadow rays
     const DevMeshLights* mesh_lights;  // into lb->sh, counted in counts[depth * stride + 48]); mesh_lights: triangle lights
     const PrtLightBufs* lb;
+    const DevLightClusters* clusters;  // clustered light selection (the k_shade_nee_clus* instances)
 };
 bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a);
 // diagnostic: per-wave material mix of what k_shade of bounce `iter` is about to shade (16 words per bounce in `out`)
@@ -343,7 +359,9 @@ void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBu
                             uint32_t* work, uint32_t max_rays);
 void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
                                   const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light,
-                                  const DevMeshLights* ml = nullptr, const DevEnv* env = nullptr);
+                                  const DevMeshLights* ml = nullptr, const DevEnv* env = nullptr, const DevLightClusters* lc = nullptr);
+// prt_light_cluster_pmf: the cluster thresholds M_c of n points (3 floats each), n x n_clusters
+void prt_launch_light_cluster_pmf(hipStream_t st, const DevLightClusters& lc, uint32_t n, const float* x, uint32_t* M);
 // prt_environment_eval: lookup of n directions (3 floats each): rgb (3 floats), texel, pdf_w; any output may be null
 void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, const float* dirs, float* rgb, uint32_t* texel,
                                  float* pdf_w);

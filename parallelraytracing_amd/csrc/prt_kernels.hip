@@ -3378,18 +3378,113 @@ PRT_DEV uint32_t triangle_light(const DevMeshLights& ml, uint32_t prim) {
     return prim - r.prim_first < r.n_tris ? r.light_first + (prim - r.prim_first) : 0xFFFFFFFFu;
 }
 
+// ---- clustered light selection (include/prt.h "Clustered light selection"; DevLightClusters) ----
+// The thresholds M_c of the cluster choice at x, handed to f(c, M_{c-1}, M_c) for c = 0 .. K-1 in order.  Two passes over the
+// cluster records instead of K running sums in registers: the first adds up the total (and the fallback's, the sum of
+// phi), the second repeats the same additions and scales each running sum.  c and the record addresses are the same in
+// every lane, so the records come through the scalar data cache; per cluster and pass: 6 subtractions, 6 selects, 5 for
+// D2, one select, one division, one addition.  (Ending the second pass once every lane of the wave has its cluster was
+// measured and is slower: the lanes' draws are independent, so a wave is done only near the end, and the ballot costs more.)
+template <class F>
+PRT_DEV void cluster_thresholds(const DevLightClusters& lc, f3 x, F f) {
+    const uint32_t K = lc.n_clusters;
+    float tot = 0.0f, tot_phi = 0.0f;
+    for (uint32_t c = 0; c < K; ++c) {
+        const float4 lo = lc.boxes[2u * c], hi = lc.boxes[2u * c + 1u];
+        float t = lo.x - x.x, u = x.x - hi.x;
+        float dx = t > u ? t : u;
+        dx = dx > 0.0f ? dx : 0.0f;
+        t = lo.y - x.y, u = x.y - hi.y;
+        float dy = t > u ? t : u;
+        dy = dy > 0.0f ? dy : 0.0f;
+        t = lo.z - x.z, u = x.z - hi.z;
+        float dz = t > u ? t : u;
+        dz = dz > 0.0f ? dz : 0.0f;
+        const float D2 = (dx * dx + dy * dy) + dz * dz;
+        const float den = D2 > hi.w ? D2 : hi.w;
+        tot = tot + lo.w / den;
+        tot_phi = tot_phi + lo.w;
+    }
+    const bool fb = !(tot > 0.0f && tot < __builtin_inff());  // (position-independent fallback: D2 overflowed, or a NaN)
+    const float inv = 1.0f / (fb ? tot_phi : tot);
+    float cum = 0.0f;
+    uint32_t m_prev = 0u;
+    for (uint32_t c = 0; c < K; ++c) {
+        const float4 lo = lc.boxes[2u * c], hi = lc.boxes[2u * c + 1u];
+        float t = lo.x - x.x, u = x.x - hi.x;
+        float dx = t > u ? t : u;
+        dx = dx > 0.0f ? dx : 0.0f;
+        t = lo.y - x.y, u = x.y - hi.y;
+        float dy = t > u ? t : u;
+        dy = dy > 0.0f ? dy : 0.0f;
+        t = lo.z - x.z, u = x.z - hi.z;
+        float dz = t > u ? t : u;
+        dz = dz > 0.0f ? dz : 0.0f;
+        const float D2 = (dx * dx + dy * dy) + dz * dz;
+        const float den = D2 > hi.w ? D2 : hi.w;
+        cum = cum + (fb ? lo.w : lo.w / den);
+        const float q = (cum * inv) * 16777216.0f;
+        const uint32_t mc = (c + 1u < K && q < 16777216.0f) ? (uint32_t)q : 16777216u;
+        f(c, m_prev, mc);
+        m_prev = mc;
+    }
+}
+
+// P_c = (M_c - M_{c-1}) 2^-24 (exact); 0 for an empty or inverted interval
+PRT_DEV float cluster_prob(uint32_t m_prev, uint32_t mc) { return mc > m_prev ? (float)(mc - m_prev) * (1.0f / 16777216.0f) : 0.0f; }
+
+// The cluster of the 24-bit draw m at x (the smallest c with m < M_c) and its probability
+PRT_DEV uint32_t select_cluster(const DevLightClusters& lc, f3 x, uint32_t m, float& P) {
+    uint32_t cl = lc.n_clusters - 1u;
+    bool found = false;
+    P = 0.0f;
+    cluster_thresholds(lc, x, [&](uint32_t c, uint32_t m_prev, uint32_t mc) {
+        if (!found && m < mc) {
+            found = true;
+            cl = c;
+            P = cluster_prob(m_prev, mc);
+        }
+    });
+    return cl;
+}
+
+// P_c(x) of a given cluster: the same evaluation
+PRT_DEV float cluster_prob_at(const DevLightClusters& lc, f3 x, uint32_t cl) {
+    float P = 0.0f;
+    cluster_thresholds(lc, x, [&](uint32_t c, uint32_t m_prev, uint32_t mc) {
+        if (c == cl) P = cluster_prob(m_prev, mc);
+    });
+    return P;
+}
+
 // One light sample from x with the draws of key's own stream (the path's state is not advanced): the light by its CDF
 // (MESHL: by the integer thresholds, select_light), then a point uniform by area (quad, triangle) or a direction uniform
 // in the cone (sphere).  false: no sample (pdf 0).
-template <bool MESHL = false>
-PRT_DEV bool sample_light(const DevLights& lt, f3 x, uint32_t key, LightSample& s, const DevMeshLights* ml = nullptr) {
+// CLUS (lc: the cluster tables): the cluster by select_cluster with u0's 24 bits, the member by the cluster's own integer
+// thresholds with the state after the stream's fourth step; pmf = P_c pmf_in.
+template <bool MESHL = false, bool CLUS = false>
+PRT_DEV bool sample_light(const DevLights& lt, f3 x, uint32_t key, LightSample& s, const DevMeshLights* ml = nullptr,
+                          const DevLightClusters* lc = nullptr) {
     uint32_t ls = pcg_hash(key + PRT_LIGHT_RNG);
     const float u0 = rnd01(ls);
     const uint32_t r0 = ls;  // the state after the stream's first step: u0 is its top 24 bits
     const float u1 = rnd01(ls);
     const float u2 = rnd01(ls);
     uint32_t lo = 0u, hi = lt.n_lights - 1u;  // smallest i with u0 < cdf[i] (cdf[n - 1] = 1)
-    if (MESHL) {
+    float pmf_c = 0.0f;
+    if (CLUS) {
+        const uint32_t r3 = pcg_hash(ls);
+        float P;
+        const uint32_t cl = select_cluster(*lc, x, r0 >> 8, P);
+        const uint4 rg = lc->range[cl];
+        uint32_t ja = rg.x, jb = rg.y;  // the smallest member j in [first, last] with r3 < U_j, else last: log2(members) dependent loads
+        while (ja < jb) {
+            const uint32_t mid = (ja + jb) >> 1;
+            if (r3 < lc->thr[mid]) jb = mid; else ja = mid + 1u;
+        }
+        lo = lc->members[ja];
+        pmf_c = P * lc->cand_pmf_in[lo];
+    } else if (MESHL) {
         lo = select_light(lt, *ml, r0);
     } else {
         while (lo < hi) {
@@ -3445,7 +3540,7 @@ PRT_DEV bool sample_light(const DevLights& lt, f3 x, uint32_t key, LightSample& 
     }
     s.t_light = t_light;
     s.tmax = t_light * (1.0f - PRT_LIGHT_SHADOW_EPS);
-    s.pdf_l = L1.w * pdf_w;
+    s.pdf_l = (CLUS ? pmf_c : L1.w) * pdf_w;
     return s.pdf_l > 0.0f && s.pdf_l < 3.0e38f && s.tmax > 0.0f;
 }
 
@@ -3459,13 +3554,20 @@ PRT_DEV float light_weight(uint32_t mode, float pl, float pb) {
 // Weight of the emission of analytic primitive `prim` met by a segment scattered at x by a Lambertian vertex with pdf pb
 // (direction w, hit at distance^2 d2): 1 - w_L of the same pair; 1 for emitters outside the light set or where pL = 0.
 // MESHL: `prim` is a global primitive index, analytic (< n_prims) or a triangle's.
-template <bool MESHL = false>
+// CLUS: the light's pmf is P_c(x) pmf_in of its cluster c, evaluated at the segment's origin x.
+template <bool MESHL = false, bool CLUS = false>
 PRT_DEV float bsdf_hit_weight(const DevLights& lt, uint32_t prim, f3 x, f3 w, float d2, float pb, const DevMeshLights* ml = nullptr,
-                              uint32_t n_prims = 0u) {
+                              uint32_t n_prims = 0u, const DevLightClusters* lc = nullptr) {
     const uint32_t li = (MESHL && prim >= n_prims) ? triangle_light(*ml, prim) : lt.prim_light[prim];
     if (li == 0xFFFFFFFFu) return 1.0f;
     const float4* L = lt.lights + PRT_LIGHT_F4 * li;
-    const float pl = L[1].w * light_pdf_w<MESHL>(L[0], L[3], x, w, d2);
+    float pmf = 0.0f;
+    if (CLUS) {
+        const float pin = lc->cand_pmf_in[li];
+        if (!(pin > 0.0f)) return 1.0f;  // (outside the light set, or an empty interval inside its cluster)
+        pmf = cluster_prob_at(*lc, x, lc->cand_cluster[li]) * pin;
+    }
+    const float pl = (CLUS ? pmf : L[1].w) * light_pdf_w<MESHL>(L[0], L[3], x, w, d2);
     if (!(pl > 0.0f)) return 1.0f;
     if (lt.mode == (uint32_t)PRT_LIGHTING_NEE) return 0.0f;
     const float r = pl / pb;  // pb = 0: r = inf, weight 0
@@ -3475,10 +3577,10 @@ PRT_DEV float bsdf_hit_weight(const DevLights& lt, uint32_t prim, f3 x, f3 w, fl
 // Light sample of a Lambertian vertex (position x, shading normal n, albedo, throughput thr before its roulette) with the
 // key of the path's state at the vertex.  false: no sample (pdf 0).  Otherwise s, pb = max(0, n.w) / pi, the weight wl and
 // `contrib`, the clamped term a shadow ray (x, s.w, s.tmax) delivers if unoccluded (zero, and no shadow ray, if n.w <= 0).
-template <bool MESHL = false>
+template <bool MESHL = false, bool CLUS = false>
 PRT_DEV bool light_sample_term(const DevLights& lt, f3 x, f3 n, f3 albedo, f3 thr, uint32_t key, float clamp, LightSample& s,
-                               float& pb, float& wl, f3& contrib, const DevMeshLights* ml = nullptr) {
-    if (!sample_light<MESHL>(lt, x, key, s, ml)) return false;
+                               float& pb, float& wl, f3& contrib, const DevMeshLights* ml = nullptr, const DevLightClusters* lc = nullptr) {
+    if (!sample_light<MESHL, CLUS>(lt, x, key, s, ml, lc)) return false;
     const float c = dot3(n, s.w);
     pb = (c > 0.0f ? c : 0.0f) * PRT_INV_PI;
     wl = light_weight(lt.mode, s.pdf_l, pb);
@@ -3579,12 +3681,13 @@ PRT_DEV f3 env_miss(const DevEnv& env, uint32_t mode, f3 d, float pb, float& wb)
 // ENV (env: DevEnv): an environment light: a miss delivers its texel, weighted after a Lambertian vertex (env_miss), and a
 // Lambertian vertex whose environment-or-lights draw says so sends its light sample there (sample_environment).
 // TEX (tex: DevTex): the albedo (attenuation and light-sample term) of a textured vertex is the lookup at the hit's UV.
-template <bool INST, bool ABVH, bool MESHL = false, bool ENV = false, bool TEX = false>
+// CLUS (lc: DevLightClusters; implies MESHL): clustered light selection in the light sample and in the weight of a hit light.
+template <bool INST, bool ABVH, bool MESHL = false, bool ENV = false, bool TEX = false, bool CLUS = false>
 PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t id, f3& o, f3& d, f3& thr, uint32_t& rng,
                              uint32_t& depth, uint32_t max_depth, const PrtSampling& sp, float4* __restrict__ rad_slot,
                              uint32_t& id0, float& d2_0, float pb_prev, float& pb_next, bool& shadow, f3& sx, f3& sw,
                              float& stmax, f3& scontrib, const DevMeshLights* ml = nullptr, const DevEnv* env = nullptr,
-                             const DevTex* tex = nullptr) {
+                             const DevTex* tex = nullptr, const DevLightClusters* lc = nullptr) {
     if (id == HIT_MISS) {
         if (ENV) {
             float wb;
@@ -3615,7 +3718,7 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
     if (!scattered) {
         f3 L = thr * emitted;
         if (type == 4u && (MESHL || id < sc.n_prims) && pb_prev >= 0.0f) {
-            const float wb = MESHL ? bsdf_hit_weight<MESHL>(lt, (uint32_t)w.prim, o, d, w.d2, pb_prev, ml, sc.n_prims)
+            const float wb = MESHL ? bsdf_hit_weight<MESHL, CLUS>(lt, (uint32_t)w.prim, o, d, w.d2, pb_prev, ml, sc.n_prims, lc)
                                    : bsdf_hit_weight(lt, id, o, d, w.d2, pb_prev);
             if (wb != 1.0f) L = L * wb;
         }
@@ -3633,7 +3736,7 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
     } else if (type == 1u && lt.n_lights) {  // (scattered: depth + 1 < max_depth)
         LightSample ls;
         float pb, wl;
-        if (light_sample_term<MESHL>(lt, w.pos, w.normal, mk3(rgbs.x, rgbs.y, rgbs.z), thr, key, sp.clamp, ls, pb, wl, scontrib, ml) &&
+        if (light_sample_term<MESHL, CLUS>(lt, w.pos, w.normal, mk3(rgbs.x, rgbs.y, rgbs.z), thr, key, sp.clamp, ls, pb, wl, scontrib, ml, lc) &&
             pb > 0.0f) {
             shadow = true;
             sw = ls.w;
@@ -3678,7 +3781,7 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
         const float4 e = sc.mat_rgbs[m];
         f3 L = thr * mk3(e.x, e.y, e.z);
         if (pb_next >= 0.0f) {
-            const float wb = bsdf_hit_weight<MESHL>(lt, id0, o, d, d2_0, pb_next, ml, sc.n_prims);  // (id0: an analytic hit of the scan)
+            const float wb = bsdf_hit_weight<MESHL, CLUS>(lt, id0, o, d, d2_0, pb_next, ml, sc.n_prims, lc);  // (id0: an analytic hit of the scan)
             if (wb != 1.0f) L = L * wb;
         }
         st_stream(rad_slot, path_result(L, sp.clamp, depth));
@@ -3689,13 +3792,13 @@ PRT_DEV int advance_path_nee(const DevScene& sc, const DevLights& lt, uint32_t i
 
 // The lighting shade step; MESHL / ml: see advance_path_nee (k_shade_nee passes false / null and compiles to the code it had
 // before there were triangle lights; k_shade_nee_mesh is the instance with them).
-template <bool INST, bool ABVH, bool MESHL, bool ENV = false, bool TEX = false>
+template <bool INST, bool ABVH, bool MESHL, bool ENV = false, bool TEX = false, bool CLUS = false>
 PRT_DEV void shade_nee_step(DevScene sc, DevLights lt, const DevMeshLights* ml, const float4* __restrict__ ro,
                             const float4* __restrict__ rd, const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
                             float4* __restrict__ no, float4* __restrict__ nd, float4* __restrict__ nt, uint32_t* __restrict__ nhit,
                             float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad, uint32_t* __restrict__ counts,
                             uint32_t* __restrict__ work, uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp,
-                            const DevEnv* env = nullptr, const DevTex* tex = nullptr) {
+                            const DevEnv* env = nullptr, const DevTex* tex = nullptr, const DevLightClusters* lc = nullptr) {
     const uint32_t nA = CNT_A(counts, iter), nB = CNT_B(counts, iter);
     const uint32_t count = nA + nB;
     if (blockIdx.x * (uint32_t)SHADE_BLOCK >= count) return;  // whole block exits together
@@ -3723,8 +3826,8 @@ PRT_DEV void shade_nee_step(DevScene sc, DevLights lt, const DevMeshLights* ml, 
         // pdf of the scatter that started this segment (segment 0 starts at the camera)
         const float pb_prev = depth ? lb.pdf_b[pid] : -1.0f;
         if (id != HIT_DEAD) {
-            const int r = advance_path_nee<INST, ABVH, MESHL, ENV, TEX>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
-                                                            pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb, ml, env, tex);
+            const int r = advance_path_nee<INST, ABVH, MESHL, ENV, TEX, CLUS>(sc, lt, id, o, d, thr, rng, depth, max_depth, sp, &rad[pid], id0, d2_0,
+                                                            pb_prev, pb_next, shadow, sx, sw, stmax, sc_rgb, ml, env, tex, lc);
             front = r == 1;
             back = r == 2;
         }
@@ -3814,6 +3917,47 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_tex(DevScene sc, DevT
                                                               uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
     shade_nee_step<INST, ABVH, MESHL, ENV, true>(sc, lt, MESHL ? &ml : nullptr, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work,
                                                  iter, max_depth, cap, sp, ENV ? &env : nullptr, &tex);
+}
+
+// The lighting shade step under clustered light selection (prt_set_light_selection; triangle lights are in the light set):
+// k_shade_nee_mesh / k_shade_nee_mesh_env / the mesh-light half of k_shade_nee_tex with the cluster tables
+template <bool INST, bool ABVH>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_clus(DevScene sc, DevLights lt, DevMeshLights ml, DevLightClusters lc,
+                                                               const float4* __restrict__ ro, const float4* __restrict__ rd,
+                                                               const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
+                                                               float4* __restrict__ no, float4* __restrict__ nd,
+                                                               float4* __restrict__ nt, uint32_t* __restrict__ nhit,
+                                                               float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad,
+                                                               uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                               uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
+    shade_nee_step<INST, ABVH, true, false, false, true>(sc, lt, &ml, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter,
+                                                         max_depth, cap, sp, nullptr, nullptr, &lc);
+}
+
+template <bool INST, bool ABVH>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_clus_env(DevScene sc, DevLights lt, DevMeshLights ml, DevLightClusters lc, DevEnv env,
+                                                                   const float4* __restrict__ ro, const float4* __restrict__ rd,
+                                                                   const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
+                                                                   float4* __restrict__ no, float4* __restrict__ nd,
+                                                                   float4* __restrict__ nt, uint32_t* __restrict__ nhit,
+                                                                   float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad,
+                                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                                   uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
+    shade_nee_step<INST, ABVH, true, true, false, true>(sc, lt, &ml, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter,
+                                                        max_depth, cap, sp, &env, nullptr, &lc);
+}
+
+template <bool INST, bool ABVH, bool ENV>
+__global__ void __launch_bounds__(SHADE_BLOCK) k_shade_nee_clus_tex(DevScene sc, DevTex tex, DevLights lt, DevMeshLights ml, DevLightClusters lc,
+                                                                   DevEnv env, const float4* __restrict__ ro, const float4* __restrict__ rd,
+                                                                   const float4* __restrict__ rt, const uint32_t* __restrict__ hit,
+                                                                   float4* __restrict__ no, float4* __restrict__ nd,
+                                                                   float4* __restrict__ nt, uint32_t* __restrict__ nhit,
+                                                                   float* __restrict__ nhd2, PrtLightBufs lb, float4* __restrict__ rad,
+                                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
+                                                                   uint32_t iter, uint32_t max_depth, uint32_t cap, PrtSampling sp) {
+    shade_nee_step<INST, ABVH, true, ENV, true, true>(sc, lt, &ml, ro, rd, rt, hit, no, nd, nt, nhit, nhd2, lb, rad, counts, work, iter,
+                                                      max_depth, cap, sp, ENV ? &env : nullptr, &tex, &lc);
 }
 
 // prt_texture_eval: texture_lookup for n (texture, uv) pairs (the host checked the texture indices)
@@ -3911,10 +4055,10 @@ __global__ void __launch_bounds__(256) k_light_accum(DevScene sc, PrtLightBufs l
 // prt_sample_light: one light sample per (hit, key) through the render's own light_sample_term (throughput 1, no clamp) and,
 // for the same pair of vertices, the weight bsdf_hit_weight gives a scattered segment in direction w that meets the light;
 // out 11 floats per ray: w.xyz, tmax, contrib.rgb, pdf_light, pdf_bsdf, w_light, w_bsdf
-template <bool MESHL, bool ENV = false>
+template <bool MESHL, bool ENV = false, bool CLUS = false>
 PRT_DEV void sample_light_test(DevScene sc, DevLights lt, const DevMeshLights* ml, uint32_t n, const float* __restrict__ in_d,
                                const PrtHit* __restrict__ hits, const uint32_t* __restrict__ keys, float* __restrict__ out,
-                               uint32_t* __restrict__ out_light, const DevEnv* env = nullptr) {
+                               uint32_t* __restrict__ out_light, const DevEnv* env = nullptr, const DevLightClusters* lc = nullptr) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const PrtHit h = hits[i];
@@ -3938,12 +4082,12 @@ PRT_DEV void sample_light_test(DevScene sc, DevLights lt, const DevMeshLights* m
         LightSample s;
         float pb = 0.0f, wl = 0.0f;
         f3 C;
-        if (light_sample_term<MESHL>(lt, x, mk3(h.normal[0], h.normal[1], h.normal[2]), mk3(a.x, a.y, a.z), mk3(1.f, 1.f, 1.f), keys[i],
-                                     0.0f, s, pb, wl, C, ml)) {
+        if (light_sample_term<MESHL, CLUS>(lt, x, mk3(h.normal[0], h.normal[1], h.normal[2]), mk3(a.x, a.y, a.z), mk3(1.f, 1.f, 1.f), keys[i],
+                                           0.0f, s, pb, wl, C, ml, lc)) {
             light = s.light;
             const uint32_t prim = __float_as_uint(lt.lights[PRT_LIGHT_F4 * s.light + 4u].w);
             const float vals[11] = {s.w.x, s.w.y, s.w.z, s.tmax, C.x, C.y, C.z, s.pdf_l, pb, wl,
-                                    bsdf_hit_weight<MESHL>(lt, prim, x, s.w, s.t_light * s.t_light, pb, ml, sc.n_prims)};
+                                    bsdf_hit_weight<MESHL, CLUS>(lt, prim, x, s.w, s.t_light * s.t_light, pb, ml, sc.n_prims, lc)};
             for (int j = 0; j < 11; ++j) r[j] = vals[j];
         }
     }
@@ -3974,6 +4118,28 @@ __global__ void k_sample_light_test_mesh_env(DevScene sc, DevLights lt, DevMeshL
                                              const float* __restrict__ in_d, const PrtHit* __restrict__ hits,
                                              const uint32_t* __restrict__ keys, float* __restrict__ out, uint32_t* __restrict__ out_light) {
     sample_light_test<true, true>(sc, lt, &ml, n, in_d, hits, keys, out, out_light, &env);
+}
+
+// prt_sample_light under clustered light selection
+__global__ void k_sample_light_test_clus(DevScene sc, DevLights lt, DevMeshLights ml, DevLightClusters lc, uint32_t n,
+                                         const float* __restrict__ in_d, const PrtHit* __restrict__ hits,
+                                         const uint32_t* __restrict__ keys, float* __restrict__ out, uint32_t* __restrict__ out_light) {
+    sample_light_test<true, false, true>(sc, lt, &ml, n, in_d, hits, keys, out, out_light, nullptr, &lc);
+}
+
+__global__ void k_sample_light_test_clus_env(DevScene sc, DevLights lt, DevMeshLights ml, DevLightClusters lc, DevEnv env, uint32_t n,
+                                             const float* __restrict__ in_d, const PrtHit* __restrict__ hits,
+                                             const uint32_t* __restrict__ keys, float* __restrict__ out, uint32_t* __restrict__ out_light) {
+    sample_light_test<true, true, true>(sc, lt, &ml, n, in_d, hits, keys, out, out_light, &env, &lc);
+}
+
+// prt_light_cluster_pmf: the thresholds M_c of n points through cluster_thresholds, M[i * n_clusters + c]
+__global__ void k_light_cluster_pmf(DevLightClusters lc, uint32_t n, const float* __restrict__ x, uint32_t* __restrict__ M) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint32_t* row = M + (size_t)i * lc.n_clusters;
+    cluster_thresholds(lc, mk3(x[3 * (size_t)i], x[3 * (size_t)i + 1], x[3 * (size_t)i + 2]),
+                       [&](uint32_t c, uint32_t, uint32_t mc) { row[c] = mc; });
 }
 
 // prt_environment_eval: the render's own lookup (env_radiance) per direction
@@ -4349,6 +4515,7 @@ bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a) 
     const DevTex& tex = or_empty(a.tex);
     const DevLights& lt = or_empty(a.lights);
     const DevMeshLights& m = or_empty(a.mesh_lights);
+    const DevLightClusters& lc = or_empty(a.clusters);
     const PrtLightBufs& lb = or_empty(a.lb);
 #define PRT_SHADE_RAYS a.in.o, a.in.d, a.in.t, a.in.hit, a.out.o, a.out.d, a.out.t, a.out.hit, a.out.hd2
 #define PRT_SHADE_TAIL_D(D) a.rad, a.counts, a.work, a.depth, D, a.cap, a.sp
@@ -4363,6 +4530,9 @@ bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a) 
 #define PRT_SHADE_ARGS_NEE_MESH sc, lt, m, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
 #define PRT_SHADE_ARGS_NEE_MESH_ENV sc, lt, m, e, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
 #define PRT_SHADE_ARGS_NEE_TEX sc, tex, lt, m, e, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_NEE_CLUS sc, lt, m, lc, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_NEE_CLUS_ENV sc, lt, m, lc, e, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
+#define PRT_SHADE_ARGS_NEE_CLUS_TEX sc, tex, lt, m, lc, e, PRT_SHADE_RAYS, lb, PRT_SHADE_TAIL
 #define PRT_SHADE_CASE(sig, kernel, tag, ...) \
     case PRT_INST(kernel, tag): hipLaunchKernelGGL((kernel<__VA_ARGS__>), grid, dim3(SHADE_BLOCK), 0, st, PRT_SHADE_ARGS_##sig); return true;
     switch (inst) {
@@ -4370,6 +4540,9 @@ bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a) 
         default: return false;
     }
 #undef PRT_SHADE_CASE
+#undef PRT_SHADE_ARGS_NEE_CLUS_TEX
+#undef PRT_SHADE_ARGS_NEE_CLUS_ENV
+#undef PRT_SHADE_ARGS_NEE_CLUS
 #undef PRT_SHADE_ARGS_NEE_TEX
 #undef PRT_SHADE_ARGS_NEE_MESH_ENV
 #undef PRT_SHADE_ARGS_NEE_MESH
@@ -4478,7 +4651,14 @@ void prt_launch_light_accum(hipStream_t st, const DevScene& sc, const PrtLightBu
 
 void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevLights& lt, uint32_t n, const float* in_d,
                                   const PrtHit* hits, const uint32_t* keys, float* out_f, uint32_t* out_light, const DevMeshLights* ml,
-                                  const DevEnv* env) {
+                                  const DevEnv* env, const DevLightClusters* lc) {
+    if (lc && ml) {
+        if (env)
+            hipLaunchKernelGGL(k_sample_light_test_clus_env, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, *ml, *lc, *env, n, in_d, hits, keys, out_f, out_light);
+        else
+            hipLaunchKernelGGL(k_sample_light_test_clus, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, *ml, *lc, n, in_d, hits, keys, out_f, out_light);
+        return;
+    }
     if (env) {
         if (ml)
             hipLaunchKernelGGL(k_sample_light_test_mesh_env, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, *ml, *env, n, in_d, hits, keys, out_f, out_light);
@@ -4491,6 +4671,10 @@ void prt_launch_sample_light_test(hipStream_t st, const DevScene& sc, const DevL
         return;
     }
     hipLaunchKernelGGL(k_sample_light_test, dim3(blocks_for(n)), dim3(256), 0, st, sc, lt, n, in_d, hits, keys, out_f, out_light);
+}
+
+void prt_launch_light_cluster_pmf(hipStream_t st, const DevLightClusters& lc, uint32_t n, const float* x, uint32_t* M) {
+    hipLaunchKernelGGL(k_light_cluster_pmf, dim3(blocks_for(n)), dim3(256), 0, st, lc, n, x, M);
 }
 
 void prt_launch_environment_eval(hipStream_t st, const DevEnv& env, uint32_t n, const float* dirs, float* rgb, uint32_t* texel,

@@ -45,7 +45,10 @@
     PRT_ROWS2(T, NEE_ENV, k_shade_nee_env) \
     PRT_ROWS2(T, NEE_MESH, k_shade_nee_mesh) \
     PRT_ROWS2(T, NEE_MESH_ENV, k_shade_nee_mesh_env) \
-    PRT_ROWS4(T, NEE_TEX, k_shade_nee_tex)
+    PRT_ROWS4(T, NEE_TEX, k_shade_nee_tex) \
+    PRT_ROWS2(T, NEE_CLUS, k_shade_nee_clus) \
+    PRT_ROWS2(T, NEE_CLUS_ENV, k_shade_nee_clus_env) \
+    PRT_ROWS3(T, NEE_CLUS_TEX, k_shade_nee_clus_tex)
 #define PRT_ACCUMULATE_INSTANCES(N, T) \
     N(PLAIN, k_accumulate) \
     N(LIT, k_accumulate_lit) \
@@ -79,6 +82,7 @@ struct PrtRouteFacts {
     // features, each with kernel instances of its own
     bool lit;          // lighting != PRT_LIGHTING_OFF: a light sample per Lambertian vertex (k_shade_nee*)
     bool mesh_lights;  // light_sources has PRT_LIGHT_SOURCES_MESH: triangle lights in the light set (read only with lit)
+    bool light_clusters;  // clustered light selection is set (read only with lit and mesh_lights: k_shade_nee_clus*)
     bool env;          // an environment image is set
     bool tex;          // a texture binding textures a material
     bool lens;         // lens.aperture > 0: a primary ray of its own per sample
@@ -156,7 +160,10 @@ inline PrtRoutePlan prt_plan_route(const PrtRouteFacts& f) {
     else if (p.compact) p.raygen = PRT_INST(k_raygen, ffft);
     else p.raygen = f.sa ? PRT_INST(k_raygen, ftff) : PRT_INST(k_raygen, ffff);
 
+    const bool cl = f.mesh_lights && f.light_clusters;
     if (p.path) p.shade = PRT_SHADE_NONE;
+    else if (f.lit && f.tex && cl) p.shade = PrtShadeInst(PRT_INST(k_shade_nee_clus_tex, fff) + (in << 2 | ab << 1 | en));
+    else if (f.lit && cl) p.shade = PrtShadeInst((f.env ? PRT_INST(k_shade_nee_clus_env, ff) : PRT_INST(k_shade_nee_clus, ff)) + (in << 1 | ab));
     else if (f.lit && f.tex) p.shade = PrtShadeInst(PRT_INST(k_shade_nee_tex, ffff) + (in << 3 | ab << 2 | ml << 1 | en));
     else if (f.lit)
         p.shade = PrtShadeInst((f.mesh_lights ? (f.env ? PRT_INST(k_shade_nee_mesh_env, ff) : PRT_INST(k_shade_nee_mesh, ff))

@@ -247,6 +247,8 @@ void write_tri_candidates(PrtMeshLights& ml, size_t at, const float* verts, uint
         std::fill_n(rec, 4 * PRT_LIGHT_F4, 0.0f);
         double e1[3], e2[3];
         for (int a = 0; a < 3; ++a) {
+            ml.box[6 * (at + t) + a] = std::min(v[a], std::min(v[3 + a], v[6 + a]));
+            ml.box[6 * (at + t) + 3 + a] = std::max(v[a], std::max(v[3 + a], v[6 + a]));
             e1[a] = (double)v[3 + a] - (double)v[a];
             e2[a] = (double)v[6 + a] - (double)v[a];
             rec[a] = v[a];
@@ -270,6 +272,29 @@ void write_tri_candidates(PrtMeshLights& ml, size_t at, const float* verts, uint
         memcpy(&rec[19], &prim, 4);
         const double pw = 2.0 * area * mean;
         ml.power[at + t] = (pw > 0.0 && std::isfinite(pw)) ? pw : 0.0;
+    }
+}
+
+// ---- a light's world box (include/prt.h "Clustered light selection") ----
+float round_down(double d) {
+    const float f = (float)d;
+    return (double)f > d ? std::nextafterf(f, -INFINITY) : f;
+}
+float round_up(double d) {
+    const float f = (float)d;
+    return (double)f < d ? std::nextafterf(f, INFINITY) : f;
+}
+
+// World box of an analytic light from its record: the quad's corners c +- u/2 +- v/2, the sphere's c +- R; in double,
+// rounded outward.
+void analytic_light_box(const float* rec, float* box) {
+    uint32_t kind = 0;
+    memcpy(&kind, &rec[15], 4);
+    for (int a = 0; a < 3; ++a) {
+        const double c = rec[a];
+        const double h = kind == 1u ? 0.5 * std::fabs((double)rec[4 + a]) + 0.5 * std::fabs((double)rec[8 + a]) : std::fabs((double)rec[3]);
+        box[a] = round_down(c - h);
+        box[3 + a] = round_up(c + h);
     }
 }
 
@@ -309,6 +334,7 @@ void finish_mesh_lights(PrtHostScene& hs, uint32_t n_not_similar) {
             ++ml.n_emitters_unsampled;
         }
     }
+    prt_build_light_clusters(&hs, hs.lc.max_clusters);
     if (!ml.n_search) return;
     ml.thr.resize(ml.n_search - 1u);
     for (uint32_t i = 0; i + 1u < ml.n_search; ++i) ml.thr[i] = (uint32_t)T[i + 1];  // (< 2^32: a non-empty interval follows)
@@ -358,9 +384,11 @@ void build_mesh_lights(const PrtSceneDesc* s, PrtHostScene& hs, const Work& w) {
     }
     ml.records.assign(4 * PRT_LIGHT_F4 * n, 0.0f);
     ml.power.assign(n, 0.0);
+    ml.box.assign(6 * n, 0.0f);
     std::copy(hs.lights.begin(), hs.lights.end(), ml.records.begin());
     std::copy(hs.light_power.begin(), hs.light_power.end(), ml.power.begin());
     for (size_t l = 0; l < n_analytic; ++l) ml.records[4 * PRT_LIGHT_F4 * l + 11] = 0.0f;  // (no float CDF in this table)
+    for (size_t l = 0; l < n_analytic; ++l) analytic_light_box(&ml.records[4 * PRT_LIGHT_F4 * l], &ml.box[6 * l]);
     size_t run = 0;
     prim = (uint32_t)hs.prims.size();
     for (uint32_t m = 0; m < s->n_meshes; ++m) {
@@ -1056,6 +1084,164 @@ void prt_scaled_light_tables(const PrtHostScene& hs, uint64_t t_env, std::vector
     }
 }
 
+// ---- clustered light selection (PrtLightClusters, prt_scene.h; contract: include/prt.h "Clustered light selection") ----
+namespace {
+struct ClusterBuild {
+    std::vector<uint32_t> m;  // candidates of the light set, ascending
+    float lo[3], hi[3];
+    uint64_t W = 0;           // sum of the members' global widths
+    float r2 = 1e-30f;
+    double key = 0.0;         // W r2: the cluster split next has the largest
+    bool fixed = false;       // nothing to split
+};
+
+void fit_cluster(const PrtMeshLights& ml, ClusterBuild& c) {
+    for (int a = 0; a < 3; ++a) c.lo[a] = INFINITY, c.hi[a] = -INFINITY;
+    c.W = 0;
+    for (uint32_t i : c.m) {
+        for (int a = 0; a < 3; ++a) {
+            c.lo[a] = std::min(c.lo[a], ml.box[6 * (size_t)i + a]);
+            c.hi[a] = std::max(c.hi[a], ml.box[6 * (size_t)i + 3 + a]);
+        }
+        c.W += ml.width[ml.cand_visible[i]];
+    }
+    double d2 = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        const double h = 0.5 * ((double)c.hi[a] - (double)c.lo[a]);
+        d2 += h * h;
+    }
+    c.r2 = round_up(d2);
+    if (!(c.r2 >= 1e-30f)) c.r2 = 1e-30f;  // (a NaN too)
+    c.key = (double)c.W * (double)c.r2;
+    c.fixed = c.m.size() < 2;
+}
+
+// Splits c by a plane perpendicular to an axis into the members before and after it, ordered by box centre along that
+// axis (ties: candidate order).  Where a plane separates the members' boxes (no box straddles it), the cut is the
+// separating plane whose halves' powers are nearest to equal, on the first axis that has one, axes in descending order of
+// the extent of the box centres; otherwise it is the power median along the longest axis.  false: the centres coincide.
+bool split_cluster(const PrtMeshLights& ml, const ClusterBuild& c, ClusterBuild& left, ClusterBuild& right) {
+    const size_t n = c.m.size();
+    auto centre2 = [&](uint32_t i, int a) { return (double)ml.box[6 * (size_t)i + a] + (double)ml.box[6 * (size_t)i + 3 + a]; };
+    double ext[3];
+    int axes[3] = {0, 1, 2};
+    for (int a = 0; a < 3; ++a) {
+        double mn = INFINITY, mx = -INFINITY;
+        for (uint32_t i : c.m) {
+            mn = std::min(mn, centre2(i, a));
+            mx = std::max(mx, centre2(i, a));
+        }
+        ext[a] = mx - mn;
+    }
+    std::stable_sort(axes, axes + 3, [&](int p, int q) { return ext[p] > ext[q]; });
+    if (!(ext[axes[0]] > 0.0) || n < 2) return false;
+    double total = 0.0;
+    for (uint32_t i : c.m) total += ml.power[i];
+    std::vector<uint32_t> order, first_order;
+    std::vector<float> suffix_lo(n + 1);
+    size_t cut = 0, first_median = 0;
+    for (int k = 0; k < 3 && !cut && ext[axes[k]] > 0.0; ++k) {
+        const int a = axes[k];
+        order = c.m;
+        std::sort(order.begin(), order.end(), [&](uint32_t p, uint32_t q) {
+            const double cp = centre2(p, a), cq = centre2(q, a);
+            return cp != cq ? cp < cq : p < q;
+        });
+        suffix_lo[n] = INFINITY;
+        for (size_t j = n; j-- > 0;) suffix_lo[j] = std::min(suffix_lo[j + 1], ml.box[6 * (size_t)order[j] + a]);
+        float prefix_hi = -INFINITY;
+        double acc = 0.0, best = INFINITY;
+        size_t median = 0;
+        for (size_t j = 0; j + 1 < n; ++j) {  // the cut after member j
+            prefix_hi = std::max(prefix_hi, ml.box[6 * (size_t)order[j] + 3 + a]);
+            acc += ml.power[order[j]];
+            if (!median && acc >= 0.5 * total) median = j + 1;
+            const double off = std::fabs(acc - 0.5 * total);
+            if (prefix_hi < suffix_lo[j + 1] && off < best) {
+                best = off;
+                cut = j + 1;
+            }
+        }
+        if (k == 0) {
+            first_median = median ? median : n - 1;
+            if (!cut) first_order = order;
+        }
+    }
+    if (!cut) {
+        order.swap(first_order);
+        cut = first_median;
+    }
+    left.m.assign(order.begin(), order.begin() + cut);
+    right.m.assign(order.begin() + cut, order.end());
+    std::sort(left.m.begin(), left.m.end());
+    std::sort(right.m.begin(), right.m.end());
+    fit_cluster(ml, left);
+    fit_cluster(ml, right);
+    return true;
+}
+}  // namespace
+
+void prt_build_light_clusters(PrtHostScene* hs, uint32_t max_clusters) {
+    const PrtMeshLights& ml = hs->ml;
+    PrtLightClusters& lc = hs->lc;
+    const uint32_t K = max_clusters ? std::min(max_clusters, PRT_LIGHT_MAX_CLUSTERS) : 32u;
+    lc = PrtLightClusters();
+    lc.max_clusters = K;
+    lc.cand_cluster.assign(ml.power.size(), 0xFFFFFFFFu);
+    lc.cand_member.assign(ml.power.size(), 0xFFFFFFFFu);
+    if (ml.visible.empty()) return;
+    std::vector<ClusterBuild> cl(1);
+    cl[0].m = ml.visible;
+    fit_cluster(ml, cl[0]);
+    while (cl.size() < K) {
+        size_t pick = cl.size();
+        for (size_t i = 0; i < cl.size(); ++i)
+            if (!cl[i].fixed && (pick == cl.size() || cl[i].key > cl[pick].key)) pick = i;
+        if (pick == cl.size()) break;
+        ClusterBuild l, r;
+        if (!split_cluster(ml, cl[pick], l, r)) {
+            cl[pick].fixed = true;
+            continue;
+        }
+        cl[pick] = std::move(l);  // (the halves take the parent's place: the order is a function of the splits alone)
+        cl.insert(cl.begin() + (std::ptrdiff_t)pick + 1, std::move(r));
+    }
+    for (size_t ci = 0; ci < cl.size(); ++ci) {
+        const ClusterBuild& c = cl[ci];
+        const uint32_t first = (uint32_t)lc.members.size(), n = (uint32_t)c.m.size();
+        const float phi = (float)((double)c.W / 4294967296.0);
+        const float b[8] = {c.lo[0], c.lo[1], c.lo[2], phi, c.hi[0], c.hi[1], c.hi[2], c.r2};
+        lc.boxes.insert(lc.boxes.end(), b, b + 8);
+        lc.power_width.push_back(c.W);
+        double total = 0.0;
+        for (uint32_t i : c.m) total += ml.power[i];
+        double acc = 0.0;
+        uint64_t prev = 0;
+        uint32_t last = first;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t i = c.m[j];
+            acc += ml.power[i];
+            uint64_t U = std::min<uint64_t>((uint64_t)std::floor(acc / total * 4294967296.0 + 0.5), 1ull << 32);
+            if (j + 1 == n) U = 1ull << 32;
+            lc.cand_cluster[i] = (uint32_t)ci;
+            lc.cand_member[i] = first + j;
+            lc.members.push_back(i);
+            lc.thr.push_back((uint32_t)U);
+            lc.inner_width.push_back(U - prev);
+            if (U > prev) last = first + j; else ++lc.n_empty_inner;
+            prev = U;
+        }
+        const uint32_t rg[4] = {first, last, n, 0u};
+        lc.range.insert(lc.range.end(), rg, rg + 4);
+    }
+}
+
+void prt_cluster_pmf_in(const PrtHostScene& hs, uint64_t t_env, std::vector<float>* out) {
+    const PrtLightClusters& lc = hs.lc;
+    out->assign(lc.cand_cluster.size(), 0.0f);
+    for (size_t k = 0; k < lc.members.size(); ++k) (*out)[lc.members[k]] = prt_scaled_pmf((double)lc.inner_width[k] / 4294967296.0, t_env);
+}
+
 // ---- image textures (include/prt.h "Image textures") ----
 int prt_build_textures(const PrtHostScene& hs, const PrtTextureSet* set, PrtTexTables* out, std::string* err) {
     if (!set) return fail(err, "prt_set_textures: null set");
@@ -1186,6 +1372,7 @@ int prt_compile_scene(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHost
     fresh.nrm_records.swap(out->nrm_records);
     *out = std::move(fresh);
     PrtHostScene& hs = *out;
+    hs.lc.max_clusters = opt.light_clusters ? std::min(opt.light_clusters, PRT_LIGHT_MAX_CLUSTERS) : 32u;
     Work w;
     if ((rc = compile_prims(s, hs, err))) return rc;
     hs.n_instanced_meshes = s->n_instanced_meshes;

@@ -50,7 +50,26 @@ struct PrtMeshLights {
     std::vector<uint32_t> visible;   // light of the set -> candidate
     std::vector<uint32_t> cand_visible;  // candidate -> light of the set, 0xFFFFFFFF for an empty interval
     std::vector<uint64_t> width;     // per light of the set: T_i - T_{i-1}; pmf = width / 2^32
+    std::vector<float> box;          // per candidate: its world box lo.xyz, hi.xyz ("Clustered light selection": a light's world box)
     uint32_t n_emitters_unsampled = 0;
+};
+
+// Clustered light selection (include/prt.h "Clustered light selection"): a flat list of at most max_clusters spatial
+// clusters over the light set of PrtMeshLights, built with it (finish of every candidate table: prt_compile_scene,
+// prt_rebuild_mesh_lights) and by prt_build_light_clusters when max_clusters changes.  Members are cluster-major, in
+// candidate order inside a cluster.
+struct PrtLightClusters {
+    uint32_t max_clusters = 32;          // what the table was built for (1..PRT_LIGHT_MAX_CLUSTERS)
+    std::vector<float> boxes;            // 8 floats per cluster: lo.xyz | phi, hi.xyz | r2
+    std::vector<uint32_t> range;         // 4 per cluster: first member, last member with a non-empty inner interval, members, 0
+    std::vector<uint64_t> power_width;   // per cluster: W_c, the sum of its members' global widths (they sum to 2^32)
+    std::vector<uint32_t> members;       // cluster-major: candidate
+    std::vector<uint32_t> thr;           // cluster-major: low 32 bits of U_{c,j} of member j (the last non-empty member's 2^32 is implicit)
+    std::vector<uint64_t> inner_width;   // cluster-major: U_{c,j} - U_{c,j-1}
+    std::vector<uint32_t> cand_cluster;  // per candidate: its cluster, 0xFFFFFFFF outside the light set
+    std::vector<uint32_t> cand_member;   // per candidate: its slot in members / inner_width
+    uint32_t n_empty_inner = 0;          // members whose inner interval is empty (never picked under clustered selection)
+    uint32_t n_clusters() const { return (uint32_t)power_width.size(); }
 };
 
 // The environment light (include/prt.h "Environment light"): the image and its sampling tables, a property of the
@@ -114,6 +133,7 @@ struct PrtHostScene {
     uint32_t ml_tris_counted = 0;      // the part of n_emitters_unsampled that is mesh / placed triangles
     bool mesh_emissive = false;        // a mesh or a placed copy has an emissive material (prt_route.h: the last-segment route needs none)
     PrtMeshLights ml;                  // the light set with emissive triangles in it (PRT_LIGHT_SOURCES_MESH)
+    PrtLightClusters lc;               // its spatial clusters (PRT_LIGHT_SELECTION_CLUSTERED)
     // what a texture binding needs of the description beyond the above (prt_build_textures): the index buffers in face order
     std::vector<uint32_t> mesh_indices;    // the world-space meshes', mesh and face order: 3 per triangle
     std::vector<uint32_t> mesh_material;   // per world-space mesh
@@ -145,6 +165,11 @@ int prt_build_textures(const PrtHostScene& hs, const PrtTextureSet* set, PrtTexT
 // whose pmf entries are prt_scaled_pmf of the exact pmf (t_env = 0: the tables themselves).  Either output may be null.
 void prt_scaled_light_tables(const PrtHostScene& hs, uint64_t t_env, std::vector<float>* lights, std::vector<float>* ml_records);
 
+// The clusters of hs->ml for at most max_clusters clusters (0: the default 32) into hs->lc.
+void prt_build_light_clusters(PrtHostScene* hs, uint32_t max_clusters);
+// Per candidate fl32(pmf_in (2^32 - T_e) / 2^32), what the kernels multiply P_c with (0 outside the light set / empty inner interval)
+void prt_cluster_pmf_in(const PrtHostScene& hs, uint64_t t_env, std::vector<float>* out);
+
 // The device-side builder of the 8-wide tree over n triangles given as 9 floats each (+ normals, + a material per
 // triangle; both may be null): nodes8 / depth and the triangle / normal records in the tree's slot order come back
 // (nrm_rec may be null); its device time is added to *ms.  keep: the device arrays stay with the supplier (the world
@@ -159,6 +184,7 @@ struct PrtSceneOptions {
     float pad_coeff;                // culling pad = pad_coeff x the coordinates' magnitude
     bool prim_bvh;                  // build a BVH over the analytic primitives when there are many
     PrtDeviceBuilder device_build;  // null: every tree is built on the host
+    uint32_t light_clusters = 0;    // PrtLightSelection.max_clusters of the context (0: the default 32)
 };
 
 // The description's top-level arrays: none null with a non-zero count (PRT_ERR_INVALID, message in *err).  First step of

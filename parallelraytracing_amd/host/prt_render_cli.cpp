@@ -2,7 +2,8 @@
 // (src/main.cpp:138-170 builds Film/Scene/Camera and Inits the backends; :504-527 is the frame loop).
 //   prt_render [--preset NAME | --ply FILE [--refine N]] [--width W --height H] [--spp N] [--depth D]
 //              [--seed S] [--camera x y z] [--out PREFIX] [--gpus N | --devices a,b,c] [--sif S] [--frames K]
-//              [--lighting off|nee|mis] [--light-sources analytic|all] [--env FILE.pfm [--env-share Q]]
+//              [--lighting off|nee|mis] [--light-sources analytic|all] [--light-selection power|clustered [--light-clusters N]]
+//              [--env FILE.pfm [--env-share Q]]
 //              [--fov-deg D] [--aperture R --focus F]
 //              [--ground-texture FILE.pfm] [--mesh-texture FILE.pfm] [--texture-filter nearest|bilinear]
 //              [--adaptive THRESHOLD [--min-spp N --spp-step N --max-spp N --noise-floor F]
@@ -56,6 +57,7 @@ int main(int argc, char** argv) {
     double fov_deg = 0.0;
     uint32_t W = 256, H = 256, spp = 1, depth = 2, seed = 0, refine = 0, sif = 0, frames = 1, lighting = PRT_LIGHTING_OFF;
     uint32_t light_sources = PRT_LIGHT_SOURCES_ANALYTIC;
+    PrtLightSelection light_selection{PRT_LIGHT_SELECTION_POWER, 0u};
     bool adaptive = false;
     PrtAdaptive ad{8u, 8u, 64u, 0.0f, 0.01f};
     std::string samples_out, noise_out, features_out;
@@ -95,6 +97,17 @@ int main(int argc, char** argv) {
             if (m == "analytic") light_sources = PRT_LIGHT_SOURCES_ANALYTIC;
             else if (m == "all") light_sources = PRT_LIGHT_SOURCES_ANALYTIC | PRT_LIGHT_SOURCES_MESH;
             else { fprintf(stderr, "--light-sources takes analytic or all\n"); return 2; }
+        }
+        else if (a == "--light-selection") {
+            const std::string m = next();
+            if (m == "power") light_selection.mode = PRT_LIGHT_SELECTION_POWER;
+            else if (m == "clustered") light_selection.mode = PRT_LIGHT_SELECTION_CLUSTERED;
+            else { fprintf(stderr, "--light-selection takes power or clustered\n"); return 2; }
+        }
+        else if (a == "--light-clusters") {
+            const int n = atoi(next());
+            if (n < 1 || n > (int)PRT_LIGHT_MAX_CLUSTERS) { fprintf(stderr, "--light-clusters takes 1 to %u\n", PRT_LIGHT_MAX_CLUSTERS); return 2; }
+            light_selection.max_clusters = (uint32_t)n;
         }
         else if (a == "--env") env = next();
         else if (a == "--env-share") env_share = (float)atof(next());
@@ -183,6 +196,7 @@ int main(int argc, char** argv) {
         if (sif) r.SetSamplesInFlight(sif);
         if (lighting != PRT_LIGHTING_OFF) r.SetLighting(lighting);
         if (light_sources != (uint32_t)PRT_LIGHT_SOURCES_ANALYTIC) r.SetLightSources(light_sources);
+        if (light_selection.mode != (uint32_t)PRT_LIGHT_SELECTION_POWER || light_selection.max_clusters) r.SetLightSelection(light_selection);
         if (!env.empty()) r.SetEnvironmentPfm(env, env_share);
         if (fov_deg != 0.0 || aperture != 0.0f) r.SetLens((float)(fov_deg * 3.14159265358979323846 / 180.0), aperture, focus);
         if (adaptive || denoise || temporal) r.SetFilmStatistics(true);

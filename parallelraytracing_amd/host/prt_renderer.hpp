@@ -342,6 +342,8 @@ public:
     }
     // Which emitters the light set holds: PRT_LIGHT_SOURCES_ANALYTIC (default) or ANALYTIC | MESH (emissive triangles too)
     void SetLightSources(uint32_t mask) { check(prt_group_set_light_sources(grp_, mask)); }
+    // Clustered light selection (include/prt.h "Clustered light selection"); it takes effect with PRT_LIGHT_SOURCES_MESH
+    void SetLightSelection(const PrtLightSelection& sel) { check(prt_group_set_light_selection(grp_, &sel)); }
     // Environment light (PrtEnvironment): rgb = height * width * 3 floats, row 0 = the +Y pole; null = the constant sky again
     void SetEnvironment(const float* rgb, uint32_t width, uint32_t height, float light_share = 0.5f) {
         if (!rgb) {

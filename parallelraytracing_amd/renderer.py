@@ -778,6 +778,52 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_set_light_sources(self._ctx, m))
         return m
 
+    def set_light_selection(self, selection="power", max_clusters: int = 32) -> int:
+        """How a light is picked (include/prt.h "Clustered light selection"): "power" (default) | "clustered" (a spatial
+        cluster by power / distance^2 to its box, then a light inside it), or a PRT_LIGHT_SELECTION_* value.  Takes
+        effect only with set_light_sources("all")."""
+        m = capi.LIGHT_SELECTIONS[selection] if isinstance(selection, str) else int(selection)
+        self._check(capi.lib().prt_set_light_selection(self._ctx, C.byref(capi.PrtLightSelection(m, int(max_clusters)))))
+        return m
+
+    def light_cluster_info(self) -> "capi.PrtLightClusterInfo":
+        s = capi.PrtLightClusterInfo()
+        self._check(capi.lib().prt_light_cluster_info(self._ctx, C.byref(s)))
+        return s
+
+    def light_clusters(self) -> dict:
+        """The clusters of the current scene: lo, hi [K, 3], r2, phi [K] float32, power_width [K] uint64 (they sum to
+        2^32), n_members [K].  Host-only contexts too."""
+        n = C.c_uint32(0)
+        L = capi.lib()
+        self._check(L.prt_light_clusters(self._ctx, 0, C.byref(n), None, None, None, None, None, None))
+        K = n.value
+        o = dict(lo=np.zeros((K, 3), np.float32), hi=np.zeros((K, 3), np.float32), r2=np.zeros(K, np.float32),
+                 phi=np.zeros(K, np.float32), power_width=np.zeros(K, np.uint64), n_members=np.zeros(K, np.uint32))
+        self._check(L.prt_light_clusters(self._ctx, K, C.byref(n), o["lo"].ctypes.data_as(_fp), o["hi"].ctypes.data_as(_fp),
+                                         o["r2"].ctypes.data_as(_fp), o["phi"].ctypes.data_as(_fp),
+                                         o["power_width"].ctypes.data_as(C.POINTER(C.c_uint64)), o["n_members"].ctypes.data_as(_u32p)))
+        return o
+
+    def light_cluster_members(self) -> Tuple[np.ndarray, np.ndarray]:
+        """Per light of the light set (light_info's order): (cluster [n] uint32, inner width U_j - U_{j-1} [n] uint64)."""
+        n = C.c_uint32(0)
+        L = capi.lib()
+        self._check(L.prt_light_cluster_members(self._ctx, 0, C.byref(n), None, None))
+        cl, w = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64)
+        self._check(L.prt_light_cluster_members(self._ctx, n.value, C.byref(n), cl.ctypes.data_as(_u32p),
+                                                w.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return cl, w
+
+    def light_cluster_pmf(self, x) -> np.ndarray:
+        """prt_light_cluster_pmf: the device's thresholds M_c [n, K] uint32 of the cluster choice at the points x [n, 3];
+        P_c = (M_c - M_{c-1}) / 2^24."""
+        p = _f32(x).reshape(-1, 3)
+        K = self.light_cluster_info().n_clusters
+        M = np.zeros((p.shape[0], K), np.uint32)
+        self._check(capi.lib().prt_light_cluster_pmf(self._ctx, p.shape[0], p.ctypes.data_as(_fp), M.ctypes.data_as(_u32p)))
+        return M
+
     def set_environment(self, rgb, light_share: float = 0.5):
         """Environment light (include/prt.h "Environment light"): rgb [H, W, 3] lat-long radiance, row 0 = the +Y pole; None
         = back to the scene's constant sky.  light_share = the probability that a light sample goes to the image."""
@@ -1351,6 +1397,28 @@ class HipWavefrontGroupRenderer:
             raise PrtError(f"prt_texture_info failed on rank {rank}")
         return s
 
+    def set_light_selection(self, selection="power", max_clusters: int = 32) -> int:
+        """HipWavefrontRenderer.set_light_selection on every rank."""
+        m = capi.LIGHT_SELECTIONS[selection] if isinstance(selection, str) else int(selection)
+        self._check(capi.lib().prt_group_set_light_selection(self._grp, C.byref(capi.PrtLightSelection(m, int(max_clusters)))))
+        return m
+
+    def _rank_view(self, rank: int = 0) -> "_RankView":
+        return _RankView(capi.lib().prt_group_context(self._grp, int(rank)))
+
+    def light_cluster_info(self, rank: int = 0) -> "capi.PrtLightClusterInfo":
+        return self._rank_view(rank).light_cluster_info()
+
+    def light_clusters(self) -> dict:
+        """The clusters as rank 0 holds them (every rank holds the same)."""
+        return self._rank_view().light_clusters()
+
+    def light_cluster_members(self) -> Tuple[np.ndarray, np.ndarray]:
+        return self._rank_view().light_cluster_members()
+
+    def light_cluster_pmf(self, x, rank: int = 0) -> np.ndarray:
+        return self._rank_view(rank).light_cluster_pmf(x)
+
     def light_info(self) -> Tuple[np.ndarray, np.ndarray]:
         """The light set as rank 0 holds it (every rank holds the same)."""
         L = capi.lib()
@@ -1383,6 +1451,22 @@ class HipWavefrontGroupRenderer:
         s = PrtStats()
         self._check(capi.lib().prt_group_get_stats(self._grp, C.byref(s)))
         return s
+
+
+class _RankView:
+    """One rank's context of a group (borrowed, never destroyed) behind the single renderer's cluster read-backs."""
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise PrtError(capi.lib().prt_last_error(self._ctx).decode())
+
+    light_cluster_info = HipWavefrontRenderer.light_cluster_info
+    light_clusters = HipWavefrontRenderer.light_clusters
+    light_cluster_members = HipWavefrontRenderer.light_cluster_members
+    light_cluster_pmf = HipWavefrontRenderer.light_cluster_pmf
 
 
 def _set_environment(fn, handle, rgb, light_share) -> int:
