@@ -735,9 +735,44 @@ int prt_tile_select(PrtContext* ctx, const float* n, const float* sum_y, const f
  * records stay on the device with the context (three 16-byte records per pixel) until one of prt_set_scene,
  * prt_clone_scene (into this context), prt_set_camera, prt_set_film, prt_set_lens, prt_set_textures, prt_refit_meshes or
  * prt_set_instance_transforms is called, successful or not; prt_features_read without a current set is PRT_ERR_INVALID.
- * Limitations: the features are the FIRST hit of the CENTRE ray.  They do not follow mirrors or glass (a mirror shows its
- * own plane, a glass ball its own surface), and they do not average over a lens or over jitter (a defocused or
- * anti-aliased edge has the features of one side).
+ * Limitations: the features are the FIRST hit of the CENTRE ray.  This set does not follow mirrors or glass (a mirror
+ * shows its own plane, a glass ball its own surface; "Guide features through specular chains" below is the opt-in that
+ * does), and it does not average over a lens or over jitter (a defocused or anti-aliased edge has the features of one side).
+ *
+ * Guide features through specular chains (PrtFeatureTrace below; off by default: with max_specular = 0 no route, kernel
+ * instance, film bit, ray count, statistic or feature record differs from what is described above).
+ * Two sets.  The FIRST-HIT set is exactly what is described above (same kernels, same bits; prt_features_read).  While
+ * max_specular > 0, prt_render_features also writes a GUIDE set, three more 16-byte records per pixel, which
+ * prt_features_read_guide reads; with max_specular = 0 there is none, and prt_features_read_guide returns the first-hit set
+ * with bounces = 0.  The spatial filter of prt_film_denoise, prt_group_film_denoise and the dn != NULL stage of
+ * prt_film_temporal takes the guide set while max_specular > 0; the reprojection of prt_film_temporal keeps the first-hit
+ * set (a mirror is reprojected as its own plane, which is right for geometry); prt_denoise and prt_denoise_device take the
+ * caller's arrays.  Both sets are dropped together by every call of the list above and by prt_set_feature_trace.
+ * The chain.  fp32, one rounding per written operation, never contracted; reflect3, refract3, fresnel_reflectance,
+ * normalize3, dot3 and glm_min are the device functions of the shade kernels (csrc/prt_device.h).  Per pixel, start with
+ * (o, d) = the centre ray, T = (1, 1, 1), L = 0, k = 0.
+ *  1. h = the closest hit of (o, d), exactly what prt_closest_hit returns (for k = 0 it is the first-hit pass's record).
+ *     A miss is a terminal miss.
+ *  2. The hit's material has type t, colour rgb (the colour prt_hit_uv reports for this segment's hit while a binding
+ *     textures at least one material) and scalar s; N = h.normal (flipped to the incoming side).
+ *     Metal, s <= roughness_max and k < max_specular: r = normalize3(normalize3(reflect3(d, N))) (material_scatter's Metal
+ *       branch without its roughness term); follow iff dot3(r, N) > 0 and r is finite; then T = T * rgb per channel, d' = r.
+ *     Dielectric, k < max_specular: ri, cos_theta, sin_theta and cannot as material_scatter computes them;
+ *       refl = cannot || fresnel_reflectance(cos_theta, ri) > 0.5f (the more probable branch of the stochastic scatter; no
+ *       random number); d' = normalize3(refl ? reflect3(d, N) : refract3(d, N, ri)); follow iff d' is finite; T unchanged.
+ *     Following: L = L + sqrtf(h.d2), o = h.position, d = d', k = k + 1, back to 1 (the closest hit's own t >= 1e-3 keeps
+ *       the next segment off the surface it starts on).
+ *     Everything else is terminal: Lambertian, Emissive, a rough Metal, a test above that fails, k = max_specular.
+ *  3. Terminal hit: albedo = T * a per channel (a = rgb or the textured colour for Lambertian / Metal, (1, 1, 1) for
+ *     Dielectric / Emissive); normal, position, prim = h's; depth = L + sqrtf(h.d2); bounces = k.
+ *     Terminal miss: albedo = T, normal = position = 0, prim = -1, depth = 0, bounces = k (the filter's rho for a miss stays
+ *     (1, 1, 1), as the filter contract says).
+ *  4. bounces is stored as a float in the .w of the guide set's albedo record; the first-hit set's .w stays 0.
+ * Limitations: one deterministic branch per dielectric vertex (at a glass surface whose reflectance is near 0.5, half of
+ * the light went the other way); the features after a chain are those of the surface SEEN (a floor seen in a mirror and
+ * the same floor seen directly may be filtered together: after demodulation by T x albedo this is intended for Lambertian
+ * surfaces); a Metal rougher than roughness_max is an ordinary surface; the temporal history still reprojects by the first
+ * hit; the centre ray only, no lens, no jitter.  tests/guide_features_replay.py restates the chain in numpy float32.
  *
  * The filter contract (prt_denoise and everything built on it): an edge-avoiding a-trous wavelet filter guided by the
  * variance of the mean luminance and by the features above.
@@ -793,6 +828,22 @@ float prt_denoise_variance(float n, float A, float Q);
 int prt_render_features(PrtContext* ctx);
 /* Copies the current feature set out (host arrays, H*W*3 floats / H*W floats / H*W int32; each may be NULL). */
 int prt_features_read(PrtContext* ctx, float* albedo, float* normal, float* position, float* depth, int32_t* prim);
+/* "Guide features through specular chains" above.  A property of the context, like PrtLens: kept across prt_set_scene,
+ * prt_set_camera and prt_set_film, and recorded by host-only contexts too. */
+typedef struct PrtFeatureTrace {
+    uint32_t max_specular;  /* 0..8 specular vertices followed; 0 = first hit only (default) */
+    float roughness_max;    /* a Metal with scalar <= this is a mirror; >= 0, finite; default 0.1f */
+} PrtFeatureTrace;
+#define PRT_FEATURE_MAX_SPECULAR 8u
+void prt_feature_trace_defaults(PrtFeatureTrace* out);          /* {0, 0.1f} */
+/* NULL = the defaults.  PRT_ERR_INVALID with the previous setting intact (checked before the device is asked for):
+ * max_specular > 8; roughness_max negative, NaN or infinite.  Drops the current feature set, as prt_set_lens does. */
+int prt_set_feature_trace(PrtContext* ctx, const PrtFeatureTrace* ft);
+int prt_get_feature_trace(PrtContext* ctx, PrtFeatureTrace* out);
+/* Copies the guide set out (arrays as for prt_features_read, bounces: H*W uint32; each may be NULL); with max_specular = 0
+ * the first-hit set and bounces = 0.  PRT_ERR_INVALID without a current feature set. */
+int prt_features_read_guide(PrtContext* ctx, float* albedo, float* normal, float* position, float* depth, int32_t* prim,
+                            uint32_t* bounces);
 /* The filter on host arrays (mean, albedo, normal, position, out: W*H*3 floats; var, var_out: W*H floats; prim: W*H
  * int32; var_out may be NULL).  Synchronous.  Needs a device, but neither a scene nor a film.  PRT_ERR_INVALID, checked
  * before the device is asked for (host-only contexts refuse alike): iterations > 6, a sigma <= 0 or NaN,
@@ -852,7 +903,8 @@ int prt_film_denoise(PrtContext* ctx, const PrtDenoise* cfg, float* rgb_out, flo
  * Variance, in double, rounded once:  V = max(0, m2' - m1' m1');  var' = (float)(V / max(N' - 1, 1)).  Status 1.
  * New history: c', N', m1', m2', the current frame's position, normal and prim, the current basis and the current
  *   transforms of the placed copies.  The a-trous output is display only and is never fed back.
- * Limits: first-hit features only (no specular chains: a mirror carries the history of its own plane); no 3 x 3 fallback
+ * Limits: the reprojection uses first-hit features only (no specular chains: a mirror carries the history of its own plane,
+ * also while PrtFeatureTrace lets the spatial stage follow them); no 3 x 3 fallback
  *   search where the four taps fail; deforming meshes reset the history; a colour border inside one plane (a texture, a
  *   shadow edge) bleeds by up to a pixel per frame of history, because nothing geometric tells its sides apart; no
  *   multi-GPU form.  Non-finite positions make a pixel take no history; a tap index is never read out of range.
@@ -1063,6 +1115,7 @@ int prt_group_set_film(PrtGroup* g, uint32_t width, uint32_t height);
 int prt_group_film_clear(PrtGroup* g);
 int prt_group_set_sampling(PrtGroup* g, const PrtSampling* s);
 int prt_group_set_lens(PrtGroup* g, const PrtLens* lens);
+int prt_group_set_feature_trace(PrtGroup* g, const PrtFeatureTrace* ft); /* every rank; prt_group_film_denoise: rank 0's guide set */
 int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n);
 int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l);
 int prt_group_set_light_sources(PrtGroup* g, uint32_t mask);

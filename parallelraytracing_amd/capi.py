@@ -85,6 +85,11 @@ class PrtLens(C.Structure):
     _fields_ = [("fov_y", C.c_float), ("aperture", C.c_float), ("focus_distance", C.c_float)]
 
 
+class PrtFeatureTrace(C.Structure):
+    """Guide features through specular chains (include/prt.h): 0 = first hit only."""
+    _fields_ = [("max_specular", C.c_uint32), ("roughness_max", C.c_float)]
+
+
 class PrtAdaptive(C.Structure):
     """Settings of prt_render_adaptive (include/prt.h "Film statistics and adaptive sampling")."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
@@ -283,6 +288,11 @@ SIGNATURES = {
     "prt_denoise_variance": (C.c_float, [C.c_float, C.c_float, C.c_float]),
     "prt_render_features": (C.c_int, [_vp]),
     "prt_features_read": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32)]),
+    "prt_feature_trace_defaults": (None, [C.POINTER(PrtFeatureTrace)]),
+    "prt_set_feature_trace": (C.c_int, [_vp, C.POINTER(PrtFeatureTrace)]),
+    "prt_get_feature_trace": (C.c_int, [_vp, C.POINTER(PrtFeatureTrace)]),
+    "prt_group_set_feature_trace": (C.c_int, [_vp, C.POINTER(PrtFeatureTrace)]),
+    "prt_features_read_guide": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), _u32p]),
     "prt_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), C.c_uint32, C.c_uint32, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), _fp, _fp]),
     "prt_denoise_device": (C.c_int, [_vp, C.POINTER(PrtDenoise), C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "prt_film_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), _fp, _fp]),

@@ -26,6 +26,7 @@
 #include "prt_adaptive.h"
 #include "prt_denoise.h"
 #include "prt_denoise_contract.h"
+#include "prt_features.h"
 #include "prt_kernels.h"
 #include "prt_scene.h"
 #include "prt_temporal.h"
@@ -188,6 +189,12 @@ struct PrtContext {
     uint32_t feat_cap = 0;                           // pixels it holds
     uint32_t feat_W = 0, feat_H = 0;
     bool feat_valid = false;
+    // the guide set through specular chains (PrtFeatureTrace): written beside the first-hit set while max_specular > 0,
+    // current only while feat_valid is (every site that drops the one drops the other)
+    PrtFeatureTrace ftrace{0u, 0.1f};                // prt_set_feature_trace: a property of the context, like the lens
+    PrtFeatureBufs guide{nullptr, nullptr, nullptr}; // one allocation: guide.alb is its base
+    uint32_t guide_cap = 0;
+    bool guide_valid = false;
     void* d_dn = nullptr;
     size_t dn_bytes = 0;
     // ---- temporal reprojection (include/prt.h): two history sets that ping-pong, the blended planar frame, status and
@@ -1152,6 +1159,7 @@ void prt_destroy(PrtContext* c) {
         free_dev(c->d_sort);
         free_dev(c->d_scratch);
         free_dev(c->feat.alb);
+        free_dev(c->guide.alb);
         free_dev(c->d_dn);
         free_dev(c->d_tp);
         free_dev(c->d_tp_mt);
@@ -2385,10 +2393,23 @@ int prt_render_features(PrtContext* c) {
     int rc = check_ready(c);
     if (rc) return rc;
     c->feat_valid = false;
+    c->guide_valid = false;
     const PrtTileMap& tm = c->tm;
     const uint64_t n64 = (uint64_t)tm.W * tm.H;
     if (n64 > (uint64_t)PRT_DENOISE_MAX_PIXELS) return fail(c, PRT_ERR_INVALID, "prt_render_features: more than 2^28 pixels");
     const uint32_t n = (uint32_t)n64;
+    const bool follow = c->ftrace.max_specular > 0u;
+    if (follow) {
+        if (n > c->guide_cap) {
+            free_dev(c->guide.alb);
+            c->guide = PrtFeatureBufs{nullptr, nullptr, nullptr};
+            c->guide_cap = 0;
+            HIPCHECK(c, hipMalloc((void**)&c->guide.alb, 3 * (size_t)n * sizeof(float4)));
+            c->guide_cap = n;
+        }
+        c->guide.nrm = c->guide.alb + n;
+        c->guide.pos = c->guide.alb + 2 * (size_t)n;
+    }
     if (n > c->feat_cap) {
         free_dev(c->feat.alb);
         c->feat = PrtFeatureBufs{nullptr, nullptr, nullptr};
@@ -2405,7 +2426,9 @@ int prt_render_features(PrtContext* c) {
     // of prt_closest_hit_device, the textured albedo of prt_hit_uv while a binding textures something, then the records
     const size_t b1 = ((size_t)n * 4 + 15) & ~(size_t)15, b3 = ((size_t)n * 12 + 15) & ~(size_t)15;
     const size_t bh = ((size_t)n * sizeof(PrtHit) + 15) & ~(size_t)15;
-    if ((rc = ensure_scratch(c, 2 * b1 + 3 * b3 + bh + 64))) return rc;
+    // (following: a second ray list, two state lists of two float4 each, and one live count per round)
+    const size_t first = 2 * b1 + 3 * b3 + bh, bs = (size_t)n * sizeof(float4);
+    if ((rc = ensure_scratch(c, first + (follow ? 2 * b3 + 4 * bs + 64 : 0) + 64))) return rc;
     char* base = (char*)c->d_scratch;
     float* d_px = (float*)base;
     float* d_py = (float*)(base + b1);
@@ -2421,22 +2444,77 @@ int prt_render_features(PrtContext* c) {
     if (textured) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), n, c->rb[0], nullptr, d_a);  // (rays and final hit ids are in rb[0])
     prt_launch_dn_pack_features(c->stream, n, d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, c->feat);
     HIPCHECK(c, hipGetLastError());
+    if (follow) {
+        // The guide set: the start kernel decides every pixel at k = 0 from the records above (nothing is traced twice) and
+        // leaves the live chains in list 1; each round reads the 4-byte live count (one small wait, as prt_render_adaptive
+        // has per pass), queries the live rays only, and steps them into the other list.  After round r every live chain
+        // has followed r + 2 vertices, so round max_specular - 1 ends them all.
+        char* ext = base + first;
+        PrtChainList lists[2] = {{d_o, d_d, (float4*)(ext + 2 * b3), (float4*)(ext + 2 * b3 + bs)},
+                                 {(float*)ext, (float*)(ext + b3), (float4*)(ext + 2 * b3 + 2 * bs), (float4*)(ext + 2 * b3 + 3 * bs)}};
+        uint32_t* d_cnt = (uint32_t*)(ext + 2 * b3 + 4 * bs);
+        HIPCHECK(c, hipMemsetAsync(d_cnt, 0, (PRT_FEATURE_MAX_SPECULAR + 1u) * sizeof(uint32_t), c->stream));
+        PrtChainArgs a{d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, c->ftrace, c->guide, d_cnt};
+        prt_launch_ft_start(c->stream, n, d_d, a, lists[1]);
+        HIPCHECK(c, hipGetLastError());
+        int cur = 1;
+        for (uint32_t r = 0; r < c->ftrace.max_specular; ++r) {
+            uint32_t live = 0;
+            HIPCHECK(c, hipMemcpyAsync(&live, d_cnt + r, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHECK(c, hipStreamSynchronize(c->stream));
+            if (live == 0u) break;
+            if (live > n) return fail(c, PRT_ERR_HIP, "prt_render_features: live count %u above %u pixels", live, n);
+            if ((rc = enqueue_query(c, live, lists[cur].o, lists[cur].d, nullptr, d_h, nullptr))) return rc;
+            if (textured) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), live, c->rb[0], nullptr, d_a);
+            a.count = d_cnt + r + 1;
+            prt_launch_ft_step(c->stream, live, lists[cur], a, lists[cur ^ 1]);
+            HIPCHECK(c, hipGetLastError());
+            cur ^= 1;
+        }
+    }
     if ((rc = prt_synchronize(c))) return rc;
     c->feat_W = tm.W;
     c->feat_H = tm.H;
     c->feat_valid = true;
+    c->guide_valid = follow;
     return PRT_OK;
 }
 
-int prt_features_read(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim) {
+void prt_feature_trace_defaults(PrtFeatureTrace* out) {
+    if (out) *out = PrtFeatureTrace{0u, 0.1f};
+}
+
+int prt_set_feature_trace(PrtContext* c, const PrtFeatureTrace* ft) {
     if (!c) return PRT_ERR_INVALID;
+    c->feat_valid = false;
+    c->guide_valid = false;
+    const PrtFeatureTrace t = ft ? *ft : PrtFeatureTrace{0u, 0.1f};
+    if (t.max_specular > PRT_FEATURE_MAX_SPECULAR) return fail(c, PRT_ERR_INVALID, "bad feature trace: max_specular must be 0..8");
+    if (!std::isfinite(t.roughness_max) || t.roughness_max < 0.0f)
+        return fail(c, PRT_ERR_INVALID, "bad feature trace: roughness_max must be finite and >= 0");
+    c->ftrace = t;
+    return PRT_OK;
+}
+
+int prt_get_feature_trace(PrtContext* c, PrtFeatureTrace* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    *out = c->ftrace;
+    return PRT_OK;
+}
+
+// The set the spatial filter is guided by: the guide set while the mode is on, else the first-hit set.
+static PrtFeatureBufs filter_features(const PrtContext* c) { return c->guide_valid ? c->guide : c->feat; }
+
+// A feature set's records to planar host arrays (each may be null); bounces: the albedo record's .w.
+static int read_feature_records(PrtContext* c, PrtFeatureBufs f, float* albedo, float* normal, float* position, float* depth, int32_t* prim,
+                                uint32_t* bounces) {
     if (!c->feat_valid) return fail(c, PRT_ERR_INVALID, "no current feature set (prt_render_features)");
     int rc = need_device(c);
     if (rc) return rc;
     const size_t n = (size_t)c->feat_W * c->feat_H;
     std::vector<float> rec(12 * n);
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    HIPCHECK(c, hipMemcpy(rec.data(), c->feat.alb, 3 * n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHECK(c, hipMemcpy(rec.data(), f.alb, 3 * n * sizeof(float4), hipMemcpyDeviceToHost));
     const float *a = rec.data(), *nr = rec.data() + 4 * n, *ps = rec.data() + 8 * n;
     for (size_t i = 0; i < n; ++i) {
         for (int k = 0; k < 3; ++k) {
@@ -2446,8 +2524,19 @@ int prt_features_read(PrtContext* c, float* albedo, float* normal, float* positi
         }
         if (depth) depth[i] = ps[4 * i + 3];
         if (prim) memcpy(&prim[i], &nr[4 * i + 3], sizeof(int32_t));
+        if (bounces) bounces[i] = (uint32_t)a[4 * i + 3];
     }
     return PRT_OK;
+}
+
+int prt_features_read_guide(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim, uint32_t* bounces) {
+    if (!c) return PRT_ERR_INVALID;
+    return read_feature_records(c, filter_features(c), albedo, normal, position, depth, prim, bounces);
+}
+
+int prt_features_read(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim) {
+    if (!c) return PRT_ERR_INVALID;
+    return read_feature_records(c, c->feat, albedo, normal, position, depth, prim, nullptr);
 }
 
 // The iterations and the finish on the context's stream.  cv[0] holds c_0 / var_0; cv[0] and cv[1] ping-pong.
@@ -2546,8 +2635,9 @@ int prt_film_denoise(PrtContext* c, const PrtDenoise* cfg, float* rgb_out, float
     float4 *cv0 = (float4*)c->d_dn, *cv1 = cv0 + n;
     float* d_out = (float*)(cv1 + n);
     float* d_vout = d_out + 3 * n;
-    prt_launch_dn_film_prepare(c->stream, tm, c->d_film_local, c->d_film_stat, c->feat, k.demodulate, cv0);
-    if ((rc = enqueue_filter(c, k, tm.W, tm.H, c->feat, cv0, cv1, d_out, var_out ? d_vout : nullptr))) return rc;
+    const PrtFeatureBufs gf = filter_features(c);
+    prt_launch_dn_film_prepare(c->stream, tm, c->d_film_local, c->d_film_stat, gf, k.demodulate, cv0);
+    if ((rc = enqueue_filter(c, k, tm.W, tm.H, gf, cv0, cv1, d_out, var_out ? d_vout : nullptr))) return rc;
     HIPCHECK(c, hipMemcpyAsync(rgb_out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
     if (var_out) HIPCHECK(c, hipMemcpyAsync(var_out, d_vout, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
@@ -2791,8 +2881,9 @@ int prt_film_temporal(PrtContext* c, const PrtTemporal* cfg, const PrtDenoise* d
         if ((rc = ensure_dn(c, 2 * n * sizeof(float4) + 4 * n * sizeof(float)))) return rc;
         float4 *cv0 = (float4*)c->d_dn, *cv1 = cv0 + n;
         float* d_out = (float*)(cv1 + n);
-        prt_launch_dn_prepare(c->stream, (uint32_t)n, d_mean, d_var, c->feat, dn->demodulate, cv0);
-        if ((rc = enqueue_filter(c, *dn, tm.W, tm.H, c->feat, cv0, cv1, d_out, d_out + 3 * n))) return rc;
+        const PrtFeatureBufs gf = filter_features(c);
+        prt_launch_dn_prepare(c->stream, (uint32_t)n, d_mean, d_var, gf, dn->demodulate, cv0);
+        if ((rc = enqueue_filter(c, *dn, tm.W, tm.H, gf, cv0, cv1, d_out, d_out + 3 * n))) return rc;
         d_rgb = d_out;
         d_v = d_out + 3 * n;
     }

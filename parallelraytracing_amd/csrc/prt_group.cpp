@@ -308,6 +308,11 @@ int prt_group_set_sampling(PrtGroup* g, const PrtSampling* s) {
     return for_each_rank(g, [&](uint32_t r) { return prt_set_sampling(g->ctx[r], s); }, false);
 }
 
+int prt_group_set_feature_trace(PrtGroup* g, const PrtFeatureTrace* ft) {
+    if (!g || g->ctx.empty()) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_feature_trace(g->ctx[r], ft); }, false);
+}
+
 int prt_group_set_lens(PrtGroup* g, const PrtLens* lens) {
     if (!g) return PRT_ERR_INVALID;
     return for_each_rank(g, [&](uint32_t r) { return prt_set_lens(g->ctx[r], lens); }, false);
@@ -438,7 +443,7 @@ int prt_group_film_denoise(PrtGroup* g, const PrtDenoise* cfg, float* rgb_out, f
     PrtContext* c0 = g->ctx[0];
     std::vector<float> alb(3 * npix), nrm(3 * npix), pos(3 * npix);
     std::vector<int32_t> prim(npix);
-    if ((rc = prt_render_features(c0)) || (rc = prt_features_read(c0, alb.data(), nrm.data(), pos.data(), nullptr, prim.data())) ||
+    if ((rc = prt_render_features(c0)) || (rc = prt_features_read_guide(c0, alb.data(), nrm.data(), pos.data(), nullptr, prim.data(), nullptr)) ||
         (rc = prt_denoise(c0, cfg, g->W, g->H, rgb.data(), var.data(), alb.data(), nrm.data(), pos.data(), prim.data(), rgb_out, var_out)))
         return gfail(g, rc, "rank 0: %s", prt_last_error(c0));
     return PRT_OK;

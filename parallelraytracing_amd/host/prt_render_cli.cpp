@@ -8,7 +8,8 @@
 //              [--ground-texture FILE.pfm] [--mesh-texture FILE.pfm] [--texture-filter nearest|bilinear]
 //              [--adaptive THRESHOLD [--min-spp N --spp-step N --max-spp N --noise-floor F]
 //               [--samples-out FILE.pfm] [--noise-out FILE.pfm]]
-//              [--denoise [--denoise-iterations N --denoise-sigma-l S --denoise-sigma-z S --no-demodulate]]
+//              [--denoise [--denoise-iterations N --denoise-sigma-l S --denoise-sigma-z S --no-demodulate]
+//               [--follow-specular N [--mirror-roughness R]]]
 //              [--features-out PREFIX]
 //              [--frames N --orbit-deg D [--temporal [--temporal-max-history H]]]
 // --orbit-deg D turns --frames N into an animation: frame f is rendered with --spp samples (sample indices f * spp ...) from the
@@ -19,6 +20,10 @@
 // edge-avoiding a-trous filter (prt_group_film_denoise; 5 iterations, sigma_l 4, sigma_z 0.1 unless set), guided by the
 // variance of every pixel's mean and by the first hit of its centre ray.  --features-out P writes those first-hit images as
 // colour PFMs: P_albedo.pfm, P_normal.pfm, P_position.pfm and P_depth.pfm (the value in all three channels).
+// --follow-specular N (1..8) lets the filter's features follow up to N mirror / glass vertices of the centre ray
+// (prt_set_feature_trace; a Metal with roughness <= --mirror-roughness, default 0.1, is a mirror): the reflected image is
+// filtered by what is seen in the mirror, not as the mirror's plane.  --features-out then also writes P_guide_albedo.pfm,
+// P_guide_normal.pfm, P_guide_position.pfm, P_guide_depth.pfm and P_guide_bounces.pfm.
 // --adaptive T renders with tile-adaptive sampling (prt_render_adaptive) instead of --spp samples everywhere: --min-spp
 // (default 8) samples for every pixel, then --spp-step (8) at a time for the 8x8 tiles that still hold a pixel whose standard
 // error exceeds T x (mean luminance + --noise-floor (0.01)), up to --max-spp (64).  --samples-out writes every pixel's sample
@@ -64,6 +69,8 @@ int main(int argc, char** argv) {
     bool denoise = false;
     PrtDenoise dn;
     prt_denoise_defaults(&dn);
+    PrtFeatureTrace ftrace;
+    prt_feature_trace_defaults(&ftrace);
     bool orbit = false, temporal = false;
     double orbit_deg = 0.0;
     PrtTemporal tp;
@@ -132,6 +139,8 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-sigma-l") dn.sigma_l = (float)atof(next());
         else if (a == "--denoise-sigma-z") dn.sigma_z = (float)atof(next());
         else if (a == "--no-demodulate") dn.demodulate = 0u;
+        else if (a == "--follow-specular") ftrace.max_specular = (uint32_t)atoi(next());
+        else if (a == "--mirror-roughness") ftrace.roughness_max = (float)atof(next());
         else if (a == "--features-out") features_out = next();
         else if (a == "--orbit-deg") { orbit_deg = atof(next()); orbit = true; }
         else if (a == "--temporal") temporal = true;
@@ -199,6 +208,7 @@ int main(int argc, char** argv) {
         if (light_selection.mode != (uint32_t)PRT_LIGHT_SELECTION_POWER || light_selection.max_clusters) r.SetLightSelection(light_selection);
         if (!env.empty()) r.SetEnvironmentPfm(env, env_share);
         if (fov_deg != 0.0 || aperture != 0.0f) r.SetLens((float)(fov_deg * 3.14159265358979323846 / 180.0), aperture, focus);
+        if (ftrace.max_specular) r.SetFeatureTrace(ftrace.max_specular, ftrace.roughness_max);
         if (adaptive || denoise || temporal) r.SetFilmStatistics(true);
         if (orbit) {  // the animation: one cleared film per frame, the camera on a circle about the vertical axis
             std::vector<float> mean((size_t)W * H * 3), trgb;
@@ -288,6 +298,18 @@ int main(int argc, char** argv) {
                 write_grey(features_out + "_depth.pfm", ft.depth)) {
                 fprintf(stderr, "cannot write %s_*.pfm\n", features_out.c_str());
                 return 1;
+            }
+            if (ftrace.max_specular) {
+                std::vector<uint32_t> bounces;
+                r.RenderGuideFeatures(ft, bounces);
+                const std::vector<float> fb(bounces.begin(), bounces.end());
+                if (prt_write_pfm((features_out + "_guide_albedo.pfm").c_str(), ft.albedo.data(), W, H) ||
+                    prt_write_pfm((features_out + "_guide_normal.pfm").c_str(), ft.normal.data(), W, H) ||
+                    prt_write_pfm((features_out + "_guide_position.pfm").c_str(), ft.position.data(), W, H) ||
+                    write_grey(features_out + "_guide_depth.pfm", ft.depth) || write_grey(features_out + "_guide_bounces.pfm", fb)) {
+                    fprintf(stderr, "cannot write %s_guide_*.pfm\n", features_out.c_str());
+                    return 1;
+                }
             }
         }
         if (adaptive)

@@ -286,6 +286,21 @@ public:
         if (prt_render_features(c) || prt_features_read(c, out.albedo.data(), out.normal.data(), out.position.data(), out.depth.data(), out.prim.data()))
             throw Error(std::string("prt_render_features: ") + prt_last_error(c));
     }
+    // The guide set through specular chains (prt_features_read_guide, SetFeatureTrace): the same images at the end of each
+    // pixel's chain, and the vertices it followed.  With max_specular = 0: the first-hit set and bounces = 0.
+    void RenderGuideFeatures(Features& out, std::vector<uint32_t>& bounces) {
+        const size_t n = (size_t)film_->width * film_->height;
+        out.albedo.assign(3 * n, 0.0f);
+        out.normal.assign(3 * n, 0.0f);
+        out.position.assign(3 * n, 0.0f);
+        out.depth.assign(n, 0.0f);
+        out.prim.assign(n, -1);
+        bounces.assign(n, 0u);
+        PrtContext* c = prt_group_context(grp_, 0);
+        if (prt_render_features(c) || prt_features_read_guide(c, out.albedo.data(), out.normal.data(), out.position.data(), out.depth.data(),
+                                                              out.prim.data(), bounces.data()))
+            throw Error(std::string("prt_render_features: ") + prt_last_error(c));
+    }
     // The gathered film through the edge-avoiding filter (prt_group_film_denoise; include/prt.h "The filter contract"):
     // width * height * 3 floats of denoised mean radiance, and the filtered variance if asked.  Needs SetFilmStatistics(true).
     // cfg = nullptr: the defaults.
@@ -334,6 +349,12 @@ public:
     void SetLens(float fov_y = 0.0f, float aperture = 0.0f, float focus_distance = 0.0f) {
         const PrtLens l{fov_y, aperture, focus_distance};
         check(prt_group_set_lens(grp_, &l));
+    }
+    // Guide features through specular chains (PrtFeatureTrace): the denoiser's features follow up to max_specular (0..8)
+    // mirror / glass vertices; a Metal with roughness <= roughness_max is a mirror.  0 = first hit only (the default)
+    void SetFeatureTrace(uint32_t max_specular = 0u, float roughness_max = 0.1f) {
+        const PrtFeatureTrace ft{max_specular, roughness_max};
+        check(prt_group_set_feature_trace(grp_, &ft));
     }
     // Light sampling toward the analytic emitters (PrtLighting): PRT_LIGHTING_OFF / _NEE_MIS / _NEE
     void SetLighting(uint32_t mode) {

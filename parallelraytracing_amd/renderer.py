@@ -428,6 +428,16 @@ def _read_features(check, ctx, W: int, H: int) -> dict:
     check(L.prt_features_read(ctx, out["albedo"].ctypes.data_as(_fp), out["normal"].ctypes.data_as(_fp),
                               out["position"].ctypes.data_as(_fp), out["depth"].ctypes.data_as(_fp),
                               out["prim"].ctypes.data_as(C.POINTER(C.c_int32))))
+    ft = capi.PrtFeatureTrace()
+    check(L.prt_get_feature_trace(ctx, C.byref(ft)))
+    if ft.max_specular > 0:   # the guide set through specular chains, beside the first-hit set
+        g = dict(albedo=np.zeros((H, W, 3), np.float32), normal=np.zeros((H, W, 3), np.float32),
+                 position=np.zeros((H, W, 3), np.float32), depth=np.zeros((H, W), np.float32), prim=np.zeros((H, W), np.int32),
+                 bounces=np.zeros((H, W), np.uint32))
+        check(L.prt_features_read_guide(ctx, g["albedo"].ctypes.data_as(_fp), g["normal"].ctypes.data_as(_fp),
+                                        g["position"].ctypes.data_as(_fp), g["depth"].ctypes.data_as(_fp),
+                                        g["prim"].ctypes.data_as(C.POINTER(C.c_int32)), g["bounces"].ctypes.data_as(_u32p)))
+        out["guide"] = g
     return out
 
 
@@ -515,6 +525,20 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_get_lens(self._ctx, C.byref(ln)))
         return ln
 
+    def set_feature_trace(self, max_specular: int = 0, roughness_max: float = 0.1) -> capi.PrtFeatureTrace:
+        """Guide features through specular chains (include/prt.h PrtFeatureTrace): follow up to max_specular (0..8) mirror
+        or glass vertices of every centre ray; a Metal with roughness <= roughness_max is a mirror.  0 (the default) = first
+        hit only.  While on, render_features() gains "guide", and denoise() / temporal_step(denoise=...) filter by it.  Stays
+        with the renderer across SetCamera / Init."""
+        ft = capi.PrtFeatureTrace(int(max_specular), float(roughness_max))
+        self._check(capi.lib().prt_set_feature_trace(self._ctx, C.byref(ft)))
+        return ft
+
+    def get_feature_trace(self) -> capi.PrtFeatureTrace:
+        ft = capi.PrtFeatureTrace()
+        self._check(capi.lib().prt_get_feature_trace(self._ctx, C.byref(ft)))
+        return ft
+
     def set_film_statistics(self, on: bool = True):
         """Second moments of every pixel's luminance beside the film (include/prt.h "Film statistics and adaptive sampling").
         Switching them clears the film (and restarts the sample index)."""
@@ -586,7 +610,8 @@ class HipWavefrontRenderer:
     def render_features(self) -> dict:
         """First-hit feature images of the pixel-centre rays (prt_render_features): albedo, normal, position (H, W, 3)
         float32, depth (H, W) float32, prim (H, W) int32 (-1: a miss); the whole image whatever the partition.  They do not
-        follow mirrors or glass and do not average over a lens or jitter."""
+        follow mirrors or glass and do not average over a lens or jitter.  While set_feature_trace(max_specular > 0) is on,
+        "guide" holds the same five images at the end of each pixel's specular chain, plus bounces (H, W) uint32."""
         f = self.film
         return _read_features(self._check, self._ctx, f.width, f.height)
 
@@ -1302,6 +1327,12 @@ class HipWavefrontGroupRenderer:
         ln = capi.PrtLens(float(fov_y), float(aperture), float(focus_distance))
         self._check(capi.lib().prt_group_set_lens(self._grp, C.byref(ln)))
         return ln
+
+    def set_feature_trace(self, max_specular: int = 0, roughness_max: float = 0.1) -> capi.PrtFeatureTrace:
+        """Guide features through specular chains on every rank (HipWavefrontRenderer.set_feature_trace)."""
+        ft = capi.PrtFeatureTrace(int(max_specular), float(roughness_max))
+        self._check(capi.lib().prt_group_set_feature_trace(self._grp, C.byref(ft)))
+        return ft
 
     def set_film_statistics(self, on: bool = True):
         """HipWavefrontRenderer.set_film_statistics on every rank."""
