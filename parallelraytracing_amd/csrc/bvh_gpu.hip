@@ -303,9 +303,15 @@ __global__ void k_records(const float* __restrict__ verts, const float* __restri
 //      atomic, leaf triangles consecutive slots from another; quantization as in k_quantize (double precision, contained).
 // =========================================================================================================
 #define PLOC_RADIUS_MAX 64
-static int g_ploc_radius = 24;   // search radius in Morton order (PRT_PLOC_RADIUS; tuned on C3, tools/build_compare.py)
-static int g_ploc_top = 0;       // 1: the top of the tree by full-search clustering on the device (PRT_PLOC_TOP=device)
-static float g_ploc_ci = 0.6f;   // cost of one triangle test relative to one 8-wide node visit (PRT_PLOC_CI)
+// The builder's tunables are read from the environment AT EACH BUILD; unset or empty gives the default.  (They were
+// file-scope statics overwritten only when the variable was set: one build with PRT_PLOC_TOP=device made every later
+// build of the process cluster its top on the device.)
+#define PLOC_RADIUS_DEFAULT 24   // search radius in Morton order (PRT_PLOC_RADIUS; tuned on C3, tools/build_compare.py)
+#define PLOC_CI_DEFAULT 0.6f     // cost of one triangle test relative to one 8-wide node visit (PRT_PLOC_CI)
+static const char* ploc_env(const char* name) {  // the variable's value, or null if it is unset or empty
+    const char* e = getenv(name);
+    return e && *e ? e : nullptr;
+}
 
 __device__ __forceinline__ float half_area6(const float* lo, const float* hi) {
     const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
@@ -904,9 +910,13 @@ int prt_gpu_bvh8_build_ploc(hipStream_t st, const float* d_verts, const float* d
     out->d_nodes8 = nullptr;
     out->d_tris = out->d_nrms = nullptr;
     if (n_tris == 0) return 0;
-    if (const char* e = getenv("PRT_PLOC_RADIUS")) g_ploc_radius = std::min(PLOC_RADIUS_MAX, std::max(1, atoi(e)));
-    if (const char* e = getenv("PRT_PLOC_CI")) g_ploc_ci = (float)atof(e);
-    const float ploc_ci = leaf_cost > 0.0f ? leaf_cost : g_ploc_ci;
+    const char* env_radius = ploc_env("PRT_PLOC_RADIUS");
+    const char* env_ci = ploc_env("PRT_PLOC_CI");
+    const char* env_top = ploc_env("PRT_PLOC_TOP");
+    const int ploc_radius = env_radius ? std::min(PLOC_RADIUS_MAX, std::max(1, atoi(env_radius))) : PLOC_RADIUS_DEFAULT;
+    // 1 (PRT_PLOC_TOP=device): the top of the tree by full-search clustering on the device; 0 (default): the host's sweep
+    const int ploc_top = env_top && !strcmp(env_top, "device") ? 1 : 0;
+    const float ploc_ci = leaf_cost > 0.0f ? leaf_cost : env_ci ? (float)atof(env_ci) : PLOC_CI_DEFAULT;
     const uint32_t n = n_tris;
     const uint32_t n_bin = 2u * n;  // binary nodes: n leaves + n - 1 internal
     const uint32_t max_nodes = n + 16u;
@@ -979,10 +989,9 @@ int prt_gpu_bvh8_build_ploc(hipStream_t st, const float* d_verts, const float* d
     uint32_t* cl_in = cl_a;
     uint32_t* cl_out = cl_b;
     pass_begin.push_back(n);
-    // g_ploc_top = 1 (PRT_PLOC_TOP=device): the passes go on below PLOC_TOP clusters with the FULL search, down to the root,
+    // ploc_top = 1 (PRT_PLOC_TOP=device): the passes go on below PLOC_TOP clusters with the FULL search, down to the root,
     // and no part of the build runs on the host; 0 (default): the host's SAH sweep builds the top (2b below)
-    if (const char* e = getenv("PRT_PLOC_TOP")) g_ploc_top = !strcmp(e, "device") ? 1 : 0;
-    const uint32_t stop_at = g_ploc_top ? 1u : PLOC_TOP;
+    const uint32_t stop_at = ploc_top ? 1u : PLOC_TOP;
     for (uint32_t pass = 0; m > stop_at; ++pass) {
         if (pass > 4096u) {  // every pass merges at least the globally best pair: cannot happen
             cleanup(false);
@@ -990,7 +999,7 @@ int prt_gpu_bvh8_build_ploc(hipStream_t st, const float* d_verts, const float* d
         }
         const dim3 g((m + 255u) / 256u), b(256);
         if (m > PLOC_TOP)
-            hipLaunchKernelGGL(k_ploc_nn, g, b, 0, st, cl_in, m, box, nn, g_ploc_radius);
+            hipLaunchKernelGGL(k_ploc_nn, g, b, 0, st, cl_in, m, box, nn, ploc_radius);
         else
             hipLaunchKernelGGL(k_ploc_nn_full, g, b, 0, st, cl_in, m, box, nn);
         hipLaunchKernelGGL(k_ploc_flags, g, b, 0, st, nn, m, flags);
@@ -1020,7 +1029,7 @@ int prt_gpu_bvh8_build_ploc(hipStream_t st, const float* d_verts, const float* d
     }
     // 2b. the top of the tree over the m remaining clusters: full-sweep SAH on the host, its DP rows as well
     uint32_t root_bin = 0u;
-    if (m == 1u) {  // the passes went all the way (g_ploc_top): the last cluster is the root
+    if (m == 1u) {  // the passes went all the way (PRT_PLOC_TOP=device): the last cluster is the root
         GB_TRY(hipMemcpyAsync(&root_bin, cl_in, 4, hipMemcpyDeviceToHost, st));
         GB_TRY(hipStreamSynchronize(st));
     } else {

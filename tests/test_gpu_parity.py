@@ -630,6 +630,7 @@ def test_device_built_tree_is_valid_and_gives_the_same_hits(ply, target, mode, m
     n8 = r.bvh_read8()
     _, tris = r.bvh_read()
     fill, depth = util.check_bvh8(n8, tris)
+    assert util.check_bvh8_tight(n8, tris) == len(n8)
     assert depth == info.depth8 and min(fill) >= 1 and (np.mean(fill) >= 2.0)
     prim = tris[:, 3].view(np.uint32).astype(np.int64) - len(scene.primitives)
     assert sorted(prim.tolist()) == list(range(mesh.n_triangles))
@@ -1007,6 +1008,7 @@ def test_refitted_tree_is_valid_and_renders_the_deformed_mesh_bit_exact(builder,
     n8 = r.bvh_read8()
     _, tris = r.bvh_read()
     fill, levels = util.check_bvh8(n8, tris)
+    assert util.check_bvh8_tight(n8, tris) == len(n8)
     assert levels == r.bvh_info().depth8
     prim = tris[:, 3].view(np.uint32).astype(np.int64) - len(scene2.primitives)
     assert sorted(prim.tolist()) == list(range(moved.n_triangles))

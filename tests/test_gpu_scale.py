@@ -242,7 +242,8 @@ def _bunny(vertices):
 @pytest.mark.parametrize("builder", [0, 1, 2])
 def test_refit_far_beyond_a_small_deformation(builder):
     """One Init, then prt_refit_meshes to: the mesh translated by 10^3 of its extent, scaled by 2^8, squashed onto the
-    plane y = const, and the original again.  After every step the tree read back is valid, closest hits, occlusion and a
+    plane y = const, and the original again.  After every step the tree read back is valid and its boxes are the tightest
+    the format allows (util.check_bvh8_tight: squashing and restoring must shrink them again), closest hits, occlusion and a
     frame equal the oracle's linear scan and a fresh Init of the same geometry, and bvh_info().refits counts the steps.
 
     The squashed mesh holds slivers (triangles that stood upright: areas down to 1e-7 on edges of 0.15), and from a distance
@@ -268,6 +269,7 @@ def test_refit_far_beyond_a_small_deformation(builder):
         _, tris = r.bvh_read()
         _, levels = util.check_bvh8(n8, tris)
         assert levels == r.bvh_info().depth8
+        assert util.check_bvh8_tight(n8, tris) == len(n8), what   # a refit shrinks boxes as well as it grows them
         fam = sc.ray_families(scene, np.random.default_rng([17, k]), n=256)
         o, d = sc.all_rays(fam)
         lo, hi = sc.world_box(scene)

@@ -470,6 +470,7 @@ def test_bvh8_structure(ply, target):
     nt = mesh.n_triangles
     assert info.n_nodes8 == len(n8) > 0 and info.max_leaf_size <= 3
     fill, depth = util.check_bvh8(n8, tris)
+    assert util.check_bvh8_tight(n8, tris) == len(n8)
     assert info.depth8 == depth and info.depth8 <= 16
     print("bvh8 fill", np.mean(fill), len(n8), info.depth8, np.bincount(fill))
     assert np.mean(fill) > 5.0 or len(n8) < 16   # the collapse fills the nodes

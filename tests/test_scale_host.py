@@ -23,6 +23,7 @@ def test_host_tree_is_valid_at_every_scale(name):
     n8 = r.bvh_read8()
     _, tris = r.bvh_read()
     fill, depth = util.check_bvh8(n8, tris)
+    assert util.check_bvh8_tight(n8, tris) == len(n8)
     info = r.bvh_info()
     assert info.n_nodes8 == len(n8) and info.depth8 == depth and info.n_triangles == scene.n_triangles
     V = tris.reshape(-1, 3, 4)[:, :, :3].astype(np.float64)
@@ -45,6 +46,7 @@ def test_host_two_level_tree_is_valid_with_scaled_copies(scale):
     alone.AddMesh(scene.instanced_meshes[0], alone.AddLambertian((1, 1, 1)))
     one = _host(alone)
     util.check_bvh8(one.bvh_read8(), one.bvh_read()[1])
+    util.check_bvh8_tight(one.bvh_read8(), one.bvh_read()[1])
 
 
 def _replay_case(name, dir_min, n=256):

@@ -123,3 +123,152 @@ def check_bvh8(n8, tris):
             exact_hi[n] = np.maximum(exact_hi[n], exact_hi[c])
     assert np.array_equal(exact_lo[0], V.reshape(-1, 3).min(axis=0)) and np.array_equal(D["p"][0], exact_lo[0])
     return fill, int(level.max())
+
+
+# ---- the tight-box rule (DESIGN.md "What a device-built tree is held to") ----------------------------------------------
+def _exact_sub(a, b):
+    """a - b for float64 arrays, and where that difference is exact (the error term of TwoSum is zero)."""
+    nb = -b
+    s = a + nb
+    bv = s - a
+    err = (a - (s - bv)) + (nb - bv)
+    return s, err == 0.0
+
+
+def _fraction_exponent(lo, hi):
+    from fractions import Fraction
+    lo, hi = Fraction(float(lo)), Fraction(float(hi))
+    ext, big = hi - lo, max(abs(lo), abs(hi))
+    e = -126
+    if big > 0:
+        fl = big.numerator.bit_length() - big.denominator.bit_length()   # floor(log2(big)) or one above it
+        if Fraction(2) ** fl > big:
+            fl -= 1
+        e = max(e, fl - 30)
+    while ext > 255 * Fraction(2) ** e:   # ceil(ext / 2^e) <= 255  <=>  ext <= 255 * 2^e
+        e += 1
+    return e
+
+
+def grid_exponent(lo, hi):
+    """The cell exponent of one axis of a node whose exact bounds are [lo, hi] (fp32 values, any shape): the smallest e
+    with ceil((hi - lo) / 2^e) <= 255, subject to e >= max(-126, floor(log2(max(|lo|, |hi|))) - 30).  Integer arithmetic
+    on the operands' exponents (frexp) where hi - lo is exact in a double, rational arithmetic where it is not."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    ext, ok = _exact_sub(hi, lo)
+    mant, ex = np.frexp(ext)                          # ext = mant * 2^ex, mant in [0.5, 1)
+    e = np.where(mant <= 255.0 / 256.0, ex - 8, ex - 7).astype(np.int64)   # ext <= 255 * 2^e
+    e = np.where(ext > 0.0, e, -126)
+    big = np.maximum(np.abs(lo), np.abs(hi))
+    _, bx = np.frexp(big)
+    e = np.where(big > 0.0, np.maximum(e, bx.astype(np.int64) - 1 - 30), e)
+    e = np.maximum(e, -126)
+    for i in zip(*np.nonzero(~ok)):
+        e[i] = _fraction_exponent(lo[i], hi[i])
+    return e
+
+
+def grid_planes(p, e, lo, hi):
+    """The 8-bit planes of a child box [lo, hi] on the grid p + q * 2^e: qlo = the largest integer with p + qlo * 2^e <= lo
+    (at least 0), qhi = the smallest with p + qhi * 2^e >= hi.  Exact: lo - p and hi - p in doubles where they are exact
+    there (division by a power of two is), rational arithmetic elsewhere.  Arrays broadcast against each other."""
+    import math
+    from fractions import Fraction
+    p, lo, hi = (np.asarray(x, np.float64) for x in (p, lo, hi))
+    p, e, lo, hi = np.broadcast_arrays(p, np.asarray(e, np.int64), lo, hi)
+    cell = np.ldexp(1.0, e)
+    dlo, ok_lo = _exact_sub(lo, p)
+    dhi, ok_hi = _exact_sub(hi, p)
+    with np.errstate(over="ignore"):
+        qlo = np.maximum(np.floor(dlo / cell), 0.0)
+        qhi = np.ceil(dhi / cell)
+    for i in zip(*np.nonzero(~(ok_lo & ok_hi))):
+        c = Fraction(2) ** int(e[i])
+        qlo[i] = max(math.floor((Fraction(float(lo[i])) - Fraction(float(p[i]))) / c), 0)
+        qhi[i] = math.ceil((Fraction(float(hi[i])) - Fraction(float(p[i]))) / c)
+    return qlo, qhi
+
+
+def slot_fields(n8):
+    """Per node and slot of the [n, 20] node array: occupied, internal, triangle count and first triangle record of a leaf
+    slot, node index of an internal slot's child (child_base + rank among the internal slots)."""
+    meta = np.stack([(n8[:, 6 + (i >> 2)] >> (8 * (i & 3))) & 0xFF for i in range(8)], axis=1).astype(np.int64)
+    bit = ((n8[:, 3:4] >> 24).astype(np.int64) >> np.arange(8)[None, :]) & 1
+    occ = meta != 0
+    inner = occ & (bit == 1)
+    unary = meta >> 5
+    cnt = np.where(occ & ~inner, (unary & 1) + ((unary >> 1) & 1) + ((unary >> 2) & 1), 0)
+    first = n8[:, 5:6].astype(np.int64) + (meta & 31)
+    child = n8[:, 4:5].astype(np.int64) + np.cumsum(inner, axis=1) - inner
+    return dict(meta=meta, bit=bit, occ=occ, inner=inner, cnt=cnt, first=first, child=child)
+
+
+def tree_levels(S):
+    """Node indices per level, breadth first from node 0, the children of a node in slot order (S = slot_fields)."""
+    levels = [np.zeros(1, np.int64)]
+    while True:
+        cur = levels[-1]
+        nxt = S["child"][cur][S["inner"][cur]]   # (row-major: node by node, slot by slot)
+        if len(nxt) == 0:
+            return levels
+        levels.append(nxt)
+
+
+def check_bvh8_tight(n8, tris):
+    """Every box of a one-level 8-wide tree is the TIGHTEST its format allows (check_bvh8 asks for containment only).
+    In exact arithmetic, from the nodes and the triangle records alone:
+      * a node's origin is the exact minimum of the triangles below it;
+      * each axis exponent is the minimal one: the smallest e with ceil(ext / 2^e) <= 255 that is at least
+        max(-126, floor(log2(big)) - 30), ext and big (the larger magnitude of the two bounds) from the exact bounds;
+      * the six planes of an occupied slot are qlo = the largest integer with p + qlo 2^e <= lo (clamped at 0) and
+        qhi = the smallest with p + qhi 2^e >= hi, for the exact bounds [lo, hi] of what lies below that slot;
+      * an empty slot holds the inverted box (255 / 0), meta 0 and no internal bit.
+    The answer is unique, so there is no tolerance.  The rule holds for all three device builders, for refitted trees and
+    for the host builder: bvh.cpp's boxes are plain unions of the triangles' fp32 bounds, nothing pads or widens them (the
+    culling pad, bvh_info().pad_abs, is applied by the traversal kernels to the decoded planes, not stored in the tree).
+    Vectorised over the nodes of a level.  Returns the number of nodes checked (all of them)."""
+    nt, N = len(tris), len(n8)
+    V = tris.reshape(nt, 3, 4)[:, :, :3]
+    tlo, thi = V.min(axis=1), V.max(axis=1)
+    S = slot_fields(n8)
+    slot_lo = np.full((N, 8, 3), np.inf, np.float32)
+    slot_hi = np.full((N, 8, 3), -np.inf, np.float32)
+    for k in range(3):
+        sel = S["cnt"] > k
+        idx = S["first"][sel] + k
+        assert (idx < nt).all()
+        slot_lo[sel] = np.minimum(slot_lo[sel], tlo[idx])
+        slot_hi[sel] = np.maximum(slot_hi[sel], thi[idx])
+    node_lo = np.full((N, 3), np.inf, np.float32)
+    node_hi = np.full((N, 3), -np.inf, np.float32)
+    levels = tree_levels(S)
+    assert sum(len(lv) for lv in levels) == N and len(np.unique(np.concatenate(levels))) == N
+    for lv in reversed(levels):
+        ni, si = np.nonzero(S["inner"][lv])
+        nd, c = lv[ni], S["child"][lv[ni], si]
+        slot_lo[nd, si], slot_hi[nd, si] = node_lo[c], node_hi[c]
+        node_lo[lv], node_hi[lv] = slot_lo[lv].min(axis=1), slot_hi[lv].max(axis=1)
+
+    def first_bad(ok, what):
+        if not ok.all():
+            n = int(np.nonzero(~ok.reshape(N, -1).all(axis=1))[0][0])
+            raise AssertionError(f"node {n}: {what}; words {[hex(int(x)) for x in n8[n]]}, exact bounds {node_lo[n]!r} .. {node_hi[n]!r}")
+
+    origin = n8[:, 0:3].copy().view(np.float32)
+    first_bad(origin == node_lo, "the origin is not the exact minimum of the triangles below the node")
+    eb = np.stack([(n8[:, 3] >> (8 * a)) & 0xFF for a in range(3)], axis=1).astype(np.int64) - 127
+    want_e = grid_exponent(node_lo, node_hi)
+    first_bad(eb == want_e, "an axis exponent is not the minimal one")
+
+    def planes(w):
+        return np.stack([(n8[:, w + (i >> 2)] >> (8 * (i & 3))) & 0xFF for i in range(8)], axis=1).astype(np.float64)
+    qlo = np.stack([planes(8), planes(10), planes(12)], axis=2)   # [n, slot, axis]
+    qhi = np.stack([planes(14), planes(16), planes(18)], axis=2)
+    occ = S["occ"][:, :, None]
+    safe_lo, safe_hi = np.where(occ, slot_lo, node_lo[:, None, :]), np.where(occ, slot_hi, node_lo[:, None, :])
+    want_lo, want_hi = grid_planes(node_lo[:, None, :], want_e[:, None, :], safe_lo, safe_hi)
+    want_lo, want_hi = np.where(occ, want_lo, 255.0), np.where(occ, want_hi, 0.0)
+    first_bad(qlo == want_lo, "a lower plane is not the tightest one (or an empty slot's is not 255)")
+    first_bad(qhi == want_hi, "an upper plane is not the tightest one (or an empty slot's is not 0)")
+    first_bad(S["occ"] | (S["bit"] == 0), "an empty slot has its internal bit set")
+    return N
