@@ -1051,6 +1051,15 @@ int prt_kernel_instance(PrtContext* ctx, char* name, uint32_t capacity);
  * before the first batch and after a batch on the path-kernel route, which launches no shade kernel.  Read-only; written
  * NUL-terminated into name[capacity]. */
 int prt_shade_instance(PrtContext* ctx, char* name, uint32_t capacity);
+/* What the context's last batch launched, stage by stage: the raygen instance, the shade instance of bounce 0 when it differs
+ * from the later bounces' (compact primary rays; empty otherwise), the shade instance of the later bounces (what
+ * prt_shade_instance reports) and the accumulate instance, each recorded where it is launched.  A stage that launched nothing
+ * reports the empty string: raygen and both shades on the path-kernel route, every stage before the first batch.
+ * prt_instance_name enumerates the instance lists of csrc/prt_route.h (index 0, 1, ...; PRT_STAGE_SHADE0 walks the shade list)
+ * and returns PRT_ERR_INVALID past the end, so a test can hold the set of names it saw to the whole list. */
+enum { PRT_STAGE_RAYGEN = 0, PRT_STAGE_SHADE0 = 1, PRT_STAGE_SHADE = 2, PRT_STAGE_ACCUMULATE = 3 };
+int prt_batch_instance(PrtContext* ctx, uint32_t stage, char* name, uint32_t capacity);
+int prt_instance_name(uint32_t stage, uint32_t index, char* name, uint32_t capacity);
 /* The last-segment route of the context's last batch (the "last_segment" tunable as the batch's plan took it: 0 = every stored
  * ray was walked and shaded, 1 = last segments that the analytic scan decides ended in their producer, 2 = and the last walk
  * was the seeded any-hit walk),

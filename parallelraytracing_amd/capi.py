@@ -176,6 +176,7 @@ ENV_RNG = 0x3C6EF372            # PRT_ENV_RNG
 
 # PrtLighting.mode (include/prt.h)
 LIGHTING_MODES = {"off": 0, "mis": 1, "nee": 2}
+STAGES = {"raygen": 0, "shade0": 1, "shade": 2, "accumulate": 3}  # PRT_STAGE_* (prt_batch_instance, prt_instance_name)
 # prt_set_light_sources masks (include/prt.h PRT_LIGHT_SOURCES_*)
 LIGHT_SOURCES = {"analytic": 1, "all": 3}
 # PrtLightSelection.mode (include/prt.h PRT_LIGHT_SELECTION_*)
@@ -341,6 +342,8 @@ SIGNATURES = {
     "prt_kernel_occupancy": (C.c_int, [_vp, C.POINTER(PrtOccupancy)]),
     "prt_kernel_instance": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),
     "prt_shade_instance": (C.c_int, [_vp, C.c_char_p, C.c_uint32]),
+    "prt_batch_instance": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_uint32]),
+    "prt_instance_name": (C.c_int, [C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32]),
     "prt_last_segment": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "prt_measure_shade_divergence": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "prt_refit_meshes": (C.c_int, [_vp, C.POINTER(PrtMesh), C.c_uint32]),

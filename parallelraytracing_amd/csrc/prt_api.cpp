@@ -119,6 +119,7 @@ struct PrtContext {
     int compact_primary = 1;  // prt_set_param("compact_primary", 0): k_raygen stores full ray records (A/B)
     int primary_walk = 1;     // prt_set_param("primary_walk", 0): compact primary rays are walked once per sample, not once per pixel (A/B)
     const char* shade_instance = "";  // the shade kernel instance the last run_batch launched, as its launch macro spelled it (prt_shade_instance)
+    const char* batch_instance[4] = {"", "", "", ""};  // what the last run_batch launched, by PRT_STAGE_* (prt_batch_instance)
     bool batch_walked = false;  // the last run_batch took the one-walk-per-pixel route (prt_measure_traversal counts its list)
     int gpu_build = 0;  // prt_set_param("gpu_build", 1): the next prt_set_scene builds the 8-wide tree on the device
     PrtSampling sampling{0u, 0u, 0.0f};
@@ -745,12 +746,14 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         const PrtAccumulateArgs aa{c->d_rad, lit ? c->lb.lrad : nullptr, c->d_film_local, c->d_film_stat, tm, S_cur, max_depth,
                                    accumulate, c->ray_stats_target, compact ? c->d_pix + tm.n_pix_local : nullptr, view.list};
         if (!prt_launch_accumulate(c->stream, plan.accumulate, aa)) return fail(c, PRT_ERR_INVALID, "no such accumulate instance");
+        c->batch_instance[PRT_STAGE_ACCUMULATE] = prt_accumulate_name(plan.accumulate);
         if ((rc = end_event(c, &ep))) return rc;
         if (accumulate && !view.list) c->stats.samples += S_cur;  // (whole-film samples only)
         HIPCHECK(c, hipGetLastError());
         return PRT_OK;
     };
     c->shade_instance = "";  // (the path route launches no shade kernel)
+    for (const char*& n : c->batch_instance) n = "";
     c->last_segment_active = plan.last_segment;
     c->last_batch_depth = plan.path ? 0u : max_depth;
     // Small batches (the reference's contract: ONE sample per ProgressiveRender call, cpu/renderer.cpp:49) can run as one
@@ -797,6 +800,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     const PrtRaygenArgs ra{&c->dsc, c->cam, tm, n_paths, first_sample, seed, max_depth, c->rb[0], c->d_rad, c->d_counts, c->d_work, c->sampling,
                            compact ? c->d_pix : nullptr, walk, f.env ? &denv : nullptr, f.lens ? &dlens : nullptr, view.list};
     if (!prt_launch_raygen(c->stream, plan.raygen, ra)) return fail(c, PRT_ERR_INVALID, "no such raygen instance");
+    c->batch_instance[PRT_STAGE_RAYGEN] = prt_raygen_name(plan.raygen);
     if ((rc = end_event(c, &ep))) return rc;
     if (exact) HIPCHECK(c, read_back(0));
     for (uint32_t d = 0; d < max_depth; ++d) {
@@ -848,6 +852,8 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
                               lit ? &c->lb : nullptr, (lit && f.light_clusters) ? &lct : nullptr};
         if (!prt_launch_shade(c->stream, shade, sa)) return fail(c, PRT_ERR_INVALID, "no such shade instance");
         c->shade_instance = prt_shade_name(shade);
+        // (bounce 0 is a stage of its own only where its instance differs from the later bounces')
+        c->batch_instance[(d == 0 && plan.shade0 != plan.shade) ? PRT_STAGE_SHADE0 : PRT_STAGE_SHADE] = c->shade_instance;
         if (lit && (lt.n_lights || (f.env && (denv.t_all | denv.t_env)))) {
             // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
             // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
@@ -3222,6 +3228,23 @@ int prt_kernel_instance(PrtContext* c, char* name, uint32_t capacity) {
 int prt_shade_instance(PrtContext* c, char* name, uint32_t capacity) {
     if (!c || !name || capacity == 0u) return PRT_ERR_INVALID;
     snprintf(name, capacity, "%s", c->shade_instance);
+    return PRT_OK;
+}
+
+int prt_batch_instance(PrtContext* c, uint32_t stage, char* name, uint32_t capacity) {
+    if (!c || !name || capacity == 0u || stage > PRT_STAGE_ACCUMULATE) return PRT_ERR_INVALID;
+    snprintf(name, capacity, "%s", c->batch_instance[stage]);
+    return PRT_OK;
+}
+
+int prt_instance_name(uint32_t stage, uint32_t index, char* name, uint32_t capacity) {
+    if (!name || capacity == 0u) return PRT_ERR_INVALID;
+    const char* s = nullptr;
+    if (stage == PRT_STAGE_RAYGEN && index < PRT_RAYGEN_NONE) s = prt_raygen_name(PrtRaygenInst(index));
+    else if ((stage == PRT_STAGE_SHADE0 || stage == PRT_STAGE_SHADE) && index < PRT_SHADE_NONE) s = prt_shade_name(PrtShadeInst(index));
+    else if (stage == PRT_STAGE_ACCUMULATE && index < PRT_ACCUMULATE_NONE) s = prt_accumulate_name(PrtAccumulateInst(index));
+    if (!s) return PRT_ERR_INVALID;
+    snprintf(name, capacity, "%s", s);
     return PRT_OK;
 }
 

@@ -1197,6 +1197,11 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_shade_instance(self._ctx, buf, 96))
         return buf.value.decode()
 
+    def batch_instances(self) -> dict:
+        """What the last batch launched, stage by stage (prt_batch_instance): {"raygen", "shade0", "shade", "accumulate"} ->
+        instance name, "" for a stage that launched nothing ("shade0": bounce 0 only where its instance differs)."""
+        return _batch_instances(self._check, self._ctx)
+
     def last_segment(self):
         """(setting the last batch's plan took for the last-segment route, rays that batch handed to its last tree walk)
         (prt_last_segment); (0, 0) before the first batch."""
@@ -1434,6 +1439,11 @@ class HipWavefrontGroupRenderer:
         self._check(capi.lib().prt_group_set_light_selection(self._grp, C.byref(capi.PrtLightSelection(m, int(max_clusters)))))
         return m
 
+    def batch_instances(self, rank: int = 0) -> dict:
+        """HipWavefrontRenderer.batch_instances of one rank's context (every rank plans its batches from the same facts)."""
+        v = self._rank_view(rank)
+        return _batch_instances(v._check, v._ctx)
+
     def _rank_view(self, rank: int = 0) -> "_RankView":
         return _RankView(capi.lib().prt_group_context(self._grp, int(rank)))
 
@@ -1498,6 +1508,25 @@ class _RankView:
     light_clusters = HipWavefrontRenderer.light_clusters
     light_cluster_members = HipWavefrontRenderer.light_cluster_members
     light_cluster_pmf = HipWavefrontRenderer.light_cluster_pmf
+
+
+def _batch_instances(check, ctx) -> dict:
+    out = {}
+    buf = C.create_string_buffer(96)
+    for stage, k in capi.STAGES.items():
+        check(capi.lib().prt_batch_instance(ctx, k, buf, 96))
+        out[stage] = buf.value.decode()
+    return out
+
+
+def instance_names(stage: str) -> list:
+    """Every kernel instance a batch can launch in `stage` ("raygen", "shade", "accumulate"; "shade0" walks the shade list), in
+    the order of the instance lists of csrc/prt_route.h (prt_instance_name)."""
+    out = []
+    buf = C.create_string_buffer(96)
+    while capi.lib().prt_instance_name(capi.STAGES[stage], len(out), buf, 96) == 0:
+        out.append(buf.value.decode())
+    return out
 
 
 def _set_environment(fn, handle, rgb, light_share) -> int:

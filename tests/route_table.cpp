@@ -2,9 +2,13 @@
 // plan, the number of combinations that map to it, and an order-independent 64-bit hash of their indices (the sum of
 // splitmix64(index) mod 2^64).  tests/test_route_table.py compares the output with tests/golden/route_table.txt, which was
 // recorded from the hand-written launchers and route expressions of the commit before prt_route.h existed.
+// With the argument "clusters" it runs a second pass instead: every combination twice, light_clusters false and true, one line
+// per distinct (lit && mesh_lights, plan without clusters, plan with clusters) and the number of combinations behind it;
+// tests/test_route_table.py states in its own words how the two plans of a line may differ.
 // Plain g++, no HIP:  g++ -std=c++17 -O2 -I parallelraytracing_amd/csrc tests/route_table.cpp
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <string>
 #include <tuple>
@@ -52,10 +56,37 @@ static uint64_t splitmix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-int main() {
-    struct Sum {
-        uint64_t n = 0, h = 0;
-    };
+static std::string text_of(const Row& r) {
+    char buf[512];
+    snprintf(buf, sizeof buf, "path=%u compact=%u walk=%u fuse=%u primary_hit=%u walk8=%u raygen=%s shade0=%s shade=%s accumulate=%s",
+             r.path, r.compact, r.walk, r.fuse, r.primary_hit, r.walk8, *r.raygen ? r.raygen : "-", *r.shade0 ? r.shade0 : "-",
+             *r.shade ? r.shade : "-", r.accumulate);
+    return buf;
+}
+
+struct Sum {
+    uint64_t n = 0, h = 0;
+};
+
+// The second pass: "mesh_lit=<lit && mesh_lights> | <plan, light_clusters false> | <plan, light_clusters true> count=<n>"
+static int clusters_pass() {
+    std::map<std::tuple<bool, Row, Row>, uint64_t> pairs;
+    for (uint32_t idx = 0; idx < N_INDEX; ++idx) {
+        PrtRouteFacts f = facts_of(idx);
+        if (!possible(f)) continue;
+        const Row off = row_of(f);
+        f.light_clusters = true;
+        ++pairs[{f.lit && f.mesh_lights, off, row_of(f)}];
+    }
+    std::map<std::string, uint64_t> lines;
+    for (const auto& [k, n] : pairs)
+        lines[std::string("mesh_lit=") + (std::get<0>(k) ? "1" : "0") + " | " + text_of(std::get<1>(k)) + " | " + text_of(std::get<2>(k))] += n;
+    for (const auto& [l, n] : lines) printf("%s count=%llu\n", l.c_str(), (unsigned long long)n);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) return strcmp(argv[1], "clusters") ? 2 : clusters_pass();
     std::map<Row, Sum> rows;  // (names compare by address here; equal texts are merged below)
     for (uint32_t idx = 0; idx < N_INDEX; ++idx) {
         const PrtRouteFacts f = facts_of(idx);
@@ -66,11 +97,7 @@ int main() {
     }
     std::map<std::string, Sum> lines;
     for (const auto& [r, s] : rows) {
-        char buf[512];
-        snprintf(buf, sizeof buf, "path=%u compact=%u walk=%u fuse=%u primary_hit=%u walk8=%u raygen=%s shade0=%s shade=%s accumulate=%s",
-                 r.path, r.compact, r.walk, r.fuse, r.primary_hit, r.walk8, *r.raygen ? r.raygen : "-", *r.shade0 ? r.shade0 : "-",
-                 *r.shade ? r.shade : "-", r.accumulate);
-        Sum& t = lines[buf];
+        Sum& t = lines[text_of(r)];
         t.n += s.n;
         t.h += s.h;
     }

@@ -352,13 +352,14 @@ def _small_emissive_cube(at, scale):
     return cube
 
 
-def scene_b(emissive_copy=False, copies=True, emissive_sphere=False, emissive_mesh=False):
+def scene_b(emissive_copy=False, copies=True, emissive_sphere=False, emissive_mesh=False, textured=True):
     """B: a 10,000-triangle bunny with planar UVs (a world-space mesh; 16 x 16 random image, bilinear, repeat) and two placed
     copies of the cube at different scale and rotation that share one UV array (8 x 8 checker, nearest, repeat; 3 x 5 random
     image, bilinear, repeat) on an untextured ground under an emissive quad.  40 x 30, depth 4.  emissive_copy: a third, small
     emissive copy (a triangle light for the MESH light sources); copies = False: the bunny alone (a scene that can be refitted).
     emissive_sphere: a third analytic primitive, a floating sphere light; emissive_mesh: the small emissive cube as a world-space
-    mesh (a triangle light in a scene without placed copies)."""
+    mesh (a triangle light in a scene without placed copies).  textured = False: the same geometry, materials and UVs with no
+    material bound to a texture (the scene the untextured instances render: tests/test_gpu_batch_instances.py)."""
     from parallelraytracing_amd import scenes
     W, H = 40, 30
     sc = prt.Scene(preset=None)
@@ -382,17 +383,18 @@ def scene_b(emissive_copy=False, copies=True, emissive_sphere=False, emissive_me
         sc.AddInstance(cube, c2, scale=0.3, euler_deg=(0.0, 65.0, 20.0), translation=(1.5, -0.4, 0.8))
     if emissive_copy:
         sc.AddInstance(cube, sc.AddEmissive((4.0, 3.0, 2.0)), scale=0.15, euler_deg=(0.0, 10.0, 0.0), translation=(0.2, 1.6, 1.5))
-    sc.SetMaterialTexture(fur, sc.AddTexture(_random_image(16, 16, 2), "bilinear", "repeat"))
-    sc.SetMaterialTexture(c1, sc.AddTexture(scenes.checker(8), "nearest", "repeat"))
-    sc.SetMaterialTexture(c2, sc.AddTexture(_random_image(5, 3, 3), "bilinear", "repeat"))
+    if textured:
+        sc.SetMaterialTexture(fur, sc.AddTexture(_random_image(16, 16, 2), "bilinear", "repeat"))
+        sc.SetMaterialTexture(c1, sc.AddTexture(scenes.checker(8), "nearest", "repeat"))
+        sc.SetMaterialTexture(c2, sc.AddTexture(_random_image(5, 3, 3), "bilinear", "repeat"))
     cam = prt.Camera((0.6, 1.2, 4.5), width=W, height=H)
     return dict(name="B", scene=sc, cam=cam, W=W, H=H, depth=4, sampling=(0, 0, 0.0), use_bvh=True)
 
 
-def scene_e(emissive_mesh=False):
+def scene_e(emissive_mesh=False, textured=True):
     """E: scene B's bunny alone (no placed copies; two quads and a sphere, so no primitive BVH) under the emissive quad and a
     floating sphere light; emissive_mesh: plus the small emissive cube as a world-space mesh."""
-    return dict(scene_b(copies=False, emissive_sphere=True, emissive_mesh=emissive_mesh), name="E")
+    return dict(scene_b(copies=False, emissive_sphere=True, emissive_mesh=emissive_mesh, textured=textured), name="E")
 
 
 # the textured quads of scenes C, D and Q: (width, height, scale, euler_deg, translation, texture).  Non-square, turned about one,
@@ -408,7 +410,7 @@ _QUADS = (
 )
 
 
-def _textured_quads(sc, extra=0):
+def _textured_quads(sc, extra=0, textured=True):
     """The ground (8 x 8 checker, nearest, repeat), _QUADS and `extra` small tilted quads on a ring, each with a material of its
     own bound to one of four textures (nearest / bilinear x repeat / clamp), under the emissive quad.  -> indices of the quads
     that are turned about at least two axes."""
@@ -418,7 +420,8 @@ def _textured_quads(sc, extra=0):
 
     def quad(w, h, scale, euler, at, t, metal=False):
         m = sc.AddMetal((0.8, 0.8, 0.8), 0.2) if metal else sc.AddLambertian((0.7, 0.7, 0.7))
-        sc.SetMaterialTexture(m, tex[t])
+        if textured:
+            sc.SetMaterialTexture(m, tex[t])
         sc.AddQuad(w, h, m, scale=(scale, scale, scale), euler_deg=euler, translation=at)
         return len(sc.primitives) - 1
 
@@ -435,17 +438,17 @@ def _textured_quads(sc, extra=0):
     return rotated
 
 
-def scene_c(emissive_mesh=False, copies=False, emissive_copy=False):
+def scene_c(emissive_mesh=False, copies=False, emissive_copy=False, textured=True):
     """C: 22 analytic primitives, every one placed by rotation + uniform scale + translation, so the primitive BVH is built, and
     no placed copy: the ground, the emissive quad, the six textured quads of _QUADS, a metal sphere, a floating sphere light and
     twelve small Lambertian spheres on a ring, around scene B's 10,000-triangle bunny, whose planar UVs reach -1 .. 2 under a
     bilinear, clamped image.  40 x 30, depth 4.  emissive_mesh: the small emissive cube as a world-space mesh.
     D (copies = True): plus two textured placed copies of the cube, whose shared UVs reach -0.5 .. 1.5, and with emissive_copy a
-    third, small emissive one."""
+    third, small emissive one.  textured = False: no material is bound to a texture (scene_b)."""
     from parallelraytracing_amd import scenes
     W, H = 40, 30
     sc = prt.Scene(preset=None)
-    rotated = _textured_quads(sc)
+    rotated = _textured_quads(sc, textured=textured)
     sc.AddCircle(0.45, sc.AddMetal((0.9, 0.8, 0.6), 0.1), translation=(2.6, -0.5, 2.2))
     sc.AddCircle(0.25, sc.AddEmissive((6.0, 8.0, 12.0)), translation=(-1.5, 0.9, 1.8))
     for k in range(12):
@@ -457,7 +460,8 @@ def scene_c(emissive_mesh=False, copies=False, emissive_copy=False):
     bunny = prt.Mesh(scenes.asset("bunny.ply"))
     bunny.SetUVs(scenes.planar_uvs(bunny, (0, 1)) * F(3.0) - F(1.0))
     sc.AddMesh(bunny, fur)
-    sc.SetMaterialTexture(fur, sc.AddTexture(_random_image(16, 16, 2), "bilinear", "clamp"))
+    if textured:
+        sc.SetMaterialTexture(fur, sc.AddTexture(_random_image(16, 16, 2), "bilinear", "clamp"))
     if emissive_mesh:
         sc.AddMesh(_small_emissive_cube((0.4, 1.5, 2.0), 0.12), sc.AddEmissive((40.0, 30.0, 20.0)))
     if copies:
@@ -468,14 +472,15 @@ def scene_c(emissive_mesh=False, copies=False, emissive_copy=False):
         sc.AddInstance(cube, c2, scale=0.25, euler_deg=(0.0, 65.0, 20.0), translation=(1.9, -0.5, 3.0))
         if emissive_copy:
             sc.AddInstance(cube, sc.AddEmissive((40.0, 30.0, 20.0)), scale=0.12, euler_deg=(0.0, 10.0, 0.0), translation=(0.4, 1.5, 2.0))
-        sc.SetMaterialTexture(c1, sc.AddTexture(scenes.checker(8), "nearest", "repeat"))
-        sc.SetMaterialTexture(c2, sc.AddTexture(_random_image(5, 3, 3), "bilinear", "repeat"))
+        if textured:
+            sc.SetMaterialTexture(c1, sc.AddTexture(scenes.checker(8), "nearest", "repeat"))
+            sc.SetMaterialTexture(c2, sc.AddTexture(_random_image(5, 3, 3), "bilinear", "repeat"))
     cam = prt.Camera((0.6, 1.6, 5.5), width=W, height=H)
     return dict(name="D" if copies else "C", scene=sc, cam=cam, W=W, H=H, depth=4, sampling=(0, 0, 0.0), use_bvh=True, rotated_quads=rotated)
 
 
-def scene_d(emissive_copy=False):
-    return scene_c(copies=True, emissive_copy=emissive_copy)
+def scene_d(emissive_copy=False, textured=True):
+    return scene_c(copies=True, emissive_copy=emissive_copy, textured=textured)
 
 
 def scene_q(big=False):
@@ -528,15 +533,17 @@ def patch_walk(monkeypatch):
         monkeypatch.setattr(mod, "walk", walk)
 
 
-def lighting_case(name):
+def lighting_case(name, textured=True):
     """-> (case, mode, replay function of (case, osc)): mis and nee, analytic and mesh light sources, with and without an
-    environment image; shared by the CPU test of the undecidable share and the GPU test."""
+    environment image; shared by the CPU test of the undecidable share and the GPU test.  textured = False: the untextured
+    scenes B .. E (the replays then need no patch_walk)."""
     import environment_replay as er
     import mesh_light_replay as mr
     scene, mode, sources = name.split("_")[0], name.split("_")[1], ("all" if "mesh" in name else "analytic")
     mesh = sources == "all"
-    c = {"A": scene_a, "B": lambda: scene_b(emissive_copy=mesh), "C": lambda: scene_c(emissive_mesh=mesh),
-         "D": lambda: scene_d(emissive_copy=mesh), "E": lambda: scene_e(emissive_mesh=mesh)}[scene]()
+    c = {"A": lambda: scene_a("full" if textured else "none"), "B": lambda: scene_b(emissive_copy=mesh, textured=textured),
+         "C": lambda: scene_c(emissive_mesh=mesh, textured=textured), "D": lambda: scene_d(emissive_copy=mesh, textured=textured),
+         "E": lambda: scene_e(emissive_mesh=mesh, textured=textured)}[scene]()
     c = dict(c, sources=sources, env="sun", light_share=0.5)
     if name.endswith("_env"):
         return c, mode, lambda c, osc: er.replay_case(c, mode, osc=osc)
