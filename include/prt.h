@@ -772,7 +772,46 @@ int prt_tile_select(PrtContext* ctx, const float* n, const float* sum_y, const f
  * the light went the other way); the features after a chain are those of the surface SEEN (a floor seen in a mirror and
  * the same floor seen directly may be filtered together: after demodulation by T x albedo this is intended for Lambertian
  * surfaces); a Metal rougher than roughness_max is an ordinary surface; the temporal history still reprojects by the first
- * hit; the centre ray only, no lens, no jitter.  tests/guide_features_replay.py restates the chain in numpy float32.
+ * hit; the centre ray only, no lens, no jitter ("Sampled guide features" below is the opt-in that averages over both).
+ * tests/guide_features_replay.py restates the chain in numpy float32.
+ *
+ * Sampled guide features (PrtFeatureSampling below; off by default: with samples = 0 no route, kernel instance, film bit,
+ * ray count, statistic, feature record or denoised pixel differs from what is described above).
+ * A third set, the SAMPLED set: the average, over K = samples of the render's own primary rays per pixel, of the features at
+ * the end of each ray's specular chain.  While samples > 0, prt_render_features also writes it (three more 16-byte records
+ * per pixel; the first-hit and guide sets keep their bits) and prt_features_read_sampled reads it; without a current
+ * sampled set prt_features_read_sampled is PRT_ERR_INVALID.  The spatial filter of prt_film_denoise, prt_group_film_denoise
+ * (rank 0's set) and the dn != NULL stage of prt_film_temporal takes the sampled set while samples > 0, otherwise the guide
+ * set while max_specular > 0, otherwise the first-hit set; the reprojection of prt_film_temporal keeps the first-hit set;
+ * prt_features_read and prt_features_read_guide return what they return with samples = 0.  The sampled set is dropped with
+ * the other sets by every call of the list above, by prt_set_feature_trace and by prt_set_feature_sampling; while
+ * samples > 0 a prt_set_sampling that changes jitter drops all sets too (with samples = 0 it drops nothing).
+ * The rule.  fp32, one rounding per written operation, never contracted.  The film has W x H pixels, pixel p = y W + x,
+ * samples s = 0 .. K - 1.
+ *  1. Sample rays.  key = path_seed(p, first_sample + s, seed), the render's seed function.  The pixel-space point is the
+ *     centre (x + 0.5f, y + 0.5f); with PrtSampling.jitter it is (x + u1, y + u2), u1 and u2 the key's first two draws, as
+ *     the render forms it.  (o, d) is what prt_camera_rays_lens returns for that point and the advanced key under the
+ *     context's PrtLens.  These are the primary rays prt_render(spp = K, seed, first_sample) traces; the whole image is
+ *     covered whatever the partition, as for the other sets.
+ *  2. Per-sample record.  The rule of "Guide features through specular chains" started from (o, d) of the sample instead of
+ *     the centre ray, with the context's PrtFeatureTrace (max_specular = 0: the ray is terminal at its first hit, the
+ *     first-hit rule): albedo_s, normal_s, position_s, depth_s, prim_s; a terminal miss has albedo_s = T.  The texture
+ *     binding applies as it does there.
+ *  3. Sums, in sample order s = 0, 1, ..., running fp32.  Sa += albedo_s per channel for every sample; for the samples with
+ *     prim_s >= 0: Sn += normal_s, Sp += position_s, Sd += depth_s, hits += 1.  prim = prim_s of the lowest such s.
+ *  4. Finish.  albedo = Sa * (1.0f / (float)K).  hits == 0: normal = position = 0, depth = 0, prim = -1.  Otherwise, with
+ *     ih = 1.0f / (float)hits: position = Sp * ih, depth = Sd * ih, l2 = dot3(Sn, Sn),
+ *     normal = l2 > 0 ? Sn * (1.0f / sqrtf(l2)) : 0.  The normal is renormalised on purpose: the filter raises N_p . N_q to
+ *     the 64th power, so an unnormalised mean would switch the filter off exactly where it is needed.
+ *  5. Degenerate case.  With jitter == 0 and aperture == 0 every sample is the centre ray: the sampled set is then a bit
+ *     for bit copy of the guide set (of the first-hit set when max_specular = 0) with hits = prim >= 0 ? 1 : 0, and nothing
+ *     is traced K times.
+ * The samples are traced in chunks of whole samples (about 2^22 rays; prt_set_param("feature_chunk", samples per chunk),
+ * 0 = by that budget); the sums are ordered, so no result depends on the chunking.
+ * Limitations: a pixel with at least one hit counts as a hit for the filter's hit / miss test (partial coverage is not
+ * weighted); positions and depths are means of possibly distant surfaces; the temporal history still reprojects by the
+ * centre ray's first hit; no variance of the features.  tests/feature_samples_replay.py restates the sums and the finish in
+ * numpy float32.
  *
  * The filter contract (prt_denoise and everything built on it): an edge-avoiding a-trous wavelet filter guided by the
  * variance of the mean luminance and by the features above.
@@ -844,6 +883,23 @@ int prt_get_feature_trace(PrtContext* ctx, PrtFeatureTrace* out);
  * the first-hit set and bounces = 0.  PRT_ERR_INVALID without a current feature set. */
 int prt_features_read_guide(PrtContext* ctx, float* albedo, float* normal, float* position, float* depth, int32_t* prim,
                             uint32_t* bounces);
+/* "Sampled guide features" above.  A property of the context, like PrtFeatureTrace: kept across prt_set_scene,
+ * prt_set_camera and prt_set_film, and recorded by host-only contexts too. */
+typedef struct PrtFeatureSampling {   /* 12 bytes */
+    uint32_t samples;       /* 0 = off (default); 1..PRT_FEATURE_MAX_SAMPLES */
+    uint32_t seed;          /* the seed of the prt_render calls whose samples are meant */
+    uint32_t first_sample;  /* their first sample index */
+} PrtFeatureSampling;
+#define PRT_FEATURE_MAX_SAMPLES 64u
+void prt_feature_sampling_defaults(PrtFeatureSampling* out);    /* {0, 0, 0} */
+/* NULL = the defaults.  PRT_ERR_INVALID with the previous setting intact (checked before the device is asked for):
+ * samples > 64.  Every call drops all feature sets, refusals included, as prt_set_feature_trace does. */
+int prt_set_feature_sampling(PrtContext* ctx, const PrtFeatureSampling* fs);
+int prt_get_feature_sampling(PrtContext* ctx, PrtFeatureSampling* out);
+/* Copies the sampled set out (arrays as for prt_features_read, hits: H*W uint32, the samples of the pixel that hit
+ * something; each may be NULL).  PRT_ERR_INVALID without a current sampled set (samples = 0 included). */
+int prt_features_read_sampled(PrtContext* ctx, float* albedo, float* normal, float* position, float* depth, int32_t* prim,
+                              uint32_t* hits);
 /* The filter on host arrays (mean, albedo, normal, position, out: W*H*3 floats; var, var_out: W*H floats; prim: W*H
  * int32; var_out may be NULL).  Synchronous.  Needs a device, but neither a scene nor a film.  PRT_ERR_INVALID, checked
  * before the device is asked for (host-only contexts refuse alike): iterations > 6, a sigma <= 0 or NaN,
@@ -1125,6 +1181,7 @@ int prt_group_film_clear(PrtGroup* g);
 int prt_group_set_sampling(PrtGroup* g, const PrtSampling* s);
 int prt_group_set_lens(PrtGroup* g, const PrtLens* lens);
 int prt_group_set_feature_trace(PrtGroup* g, const PrtFeatureTrace* ft); /* every rank; prt_group_film_denoise: rank 0's guide set */
+int prt_group_set_feature_sampling(PrtGroup* g, const PrtFeatureSampling* fs); /* every rank; prt_group_film_denoise: rank 0's sampled set */
 int prt_group_set_samples_in_flight(PrtGroup* g, uint32_t n);
 int prt_group_set_lighting(PrtGroup* g, const PrtLighting* l);
 int prt_group_set_light_sources(PrtGroup* g, uint32_t mask);

@@ -90,6 +90,11 @@ class PrtFeatureTrace(C.Structure):
     _fields_ = [("max_specular", C.c_uint32), ("roughness_max", C.c_float)]
 
 
+class PrtFeatureSampling(C.Structure):
+    """Sampled guide features (include/prt.h): samples = 0 = off; seed and first_sample of the prt_render calls meant."""
+    _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint32), ("first_sample", C.c_uint32)]
+
+
 class PrtAdaptive(C.Structure):
     """Settings of prt_render_adaptive (include/prt.h "Film statistics and adaptive sampling")."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
@@ -294,6 +299,11 @@ SIGNATURES = {
     "prt_get_feature_trace": (C.c_int, [_vp, C.POINTER(PrtFeatureTrace)]),
     "prt_group_set_feature_trace": (C.c_int, [_vp, C.POINTER(PrtFeatureTrace)]),
     "prt_features_read_guide": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), _u32p]),
+    "prt_feature_sampling_defaults": (None, [C.POINTER(PrtFeatureSampling)]),
+    "prt_set_feature_sampling": (C.c_int, [_vp, C.POINTER(PrtFeatureSampling)]),
+    "prt_get_feature_sampling": (C.c_int, [_vp, C.POINTER(PrtFeatureSampling)]),
+    "prt_group_set_feature_sampling": (C.c_int, [_vp, C.POINTER(PrtFeatureSampling)]),
+    "prt_features_read_sampled": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), _u32p]),
     "prt_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), C.c_uint32, C.c_uint32, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int32), _fp, _fp]),
     "prt_denoise_device": (C.c_int, [_vp, C.POINTER(PrtDenoise), C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "prt_film_denoise": (C.c_int, [_vp, C.POINTER(PrtDenoise), _fp, _fp]),

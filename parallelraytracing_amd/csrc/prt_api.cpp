@@ -26,6 +26,7 @@
 #include "prt_adaptive.h"
 #include "prt_denoise.h"
 #include "prt_denoise_contract.h"
+#include "prt_feature_samples.h"
 #include "prt_features.h"
 #include "prt_kernels.h"
 #include "prt_scene.h"
@@ -196,6 +197,12 @@ struct PrtContext {
     PrtFeatureBufs guide{nullptr, nullptr, nullptr}; // one allocation: guide.alb is its base
     uint32_t guide_cap = 0;
     bool guide_valid = false;
+    // the sampled set (PrtFeatureSampling): written beside the others while samples > 0, current only while feat_valid is
+    PrtFeatureSampling fsamp{0u, 0u, 0u};            // prt_set_feature_sampling: a property of the context, like ftrace
+    PrtFeatureBufs samp{nullptr, nullptr, nullptr};  // one allocation: samp.alb is its base; the running sums until finished
+    uint32_t samp_cap = 0;
+    bool samp_valid = false;
+    int feature_chunk = 0;  // prt_set_param("feature_chunk", n): samples per chunk of the sampled pass, 0 = by the ray budget
     void* d_dn = nullptr;
     size_t dn_bytes = 0;
     // ---- temporal reprojection (include/prt.h): two history sets that ping-pong, the blended planar frame, status and
@@ -1166,6 +1173,7 @@ void prt_destroy(PrtContext* c) {
         free_dev(c->d_scratch);
         free_dev(c->feat.alb);
         free_dev(c->guide.alb);
+        free_dev(c->samp.alb);
         free_dev(c->d_dn);
         free_dev(c->d_tp);
         free_dev(c->d_tp_mt);
@@ -1664,7 +1672,9 @@ int prt_set_sampling(PrtContext* c, const PrtSampling* sp) {
     if (!c) return PRT_ERR_INVALID;
     if (sp && (sp->jitter > 1u || sp->rr_depth > PRT_MAX_DEPTH || !(sp->clamp >= 0.0f)))
         return fail(c, PRT_ERR_INVALID, "bad sampling options");
-    c->sampling = sp ? *sp : PrtSampling{0u, 0u, 0.0f};
+    const PrtSampling ns = sp ? *sp : PrtSampling{0u, 0u, 0.0f};
+    if (c->fsamp.samples > 0u && ns.jitter != c->sampling.jitter) c->feat_valid = false;  // the sampled set's rays are the render's
+    c->sampling = ns;
     return PRT_OK;
 }
 
@@ -2395,6 +2405,108 @@ static int ensure_dn(PrtContext* c, size_t bytes) {
     return PRT_OK;
 }
 
+// Scratch bytes enqueue_chains needs at `ext` for n rays: a second ray list, two state lists of two float4 each, and one
+// live count per round.
+static size_t chain_scratch_bytes(uint32_t n) {
+    const size_t b3 = ((size_t)n * 12 + 15) & ~(size_t)15, bs = (size_t)n * sizeof(float4);
+    return 2 * b3 + 4 * bs + 64;
+}
+
+// The specular chains of n rays (d_o, d_d) whose closest hits are in d_h (and whose textured albedo is in d_a, or null): the
+// start kernel decides every ray at k = 0 from those records (nothing is traced twice) and leaves the live chains in list 1;
+// each round reads the 4-byte live count (one small wait, as prt_render_adaptive has per pass), queries the live rays only,
+// and steps them into the other list.  After round r every live chain has followed r + 2 vertices, so round
+// max_specular - 1 ends them all.  Ray i's records go to out[i].  d_o, d_d, d_h and d_a are overwritten.
+static int enqueue_chains(PrtContext* c, uint32_t n, float* d_o, float* d_d, PrtHit* d_h, float* d_a, char* ext, PrtFeatureBufs out) {
+    int rc;
+    const size_t b3 = ((size_t)n * 12 + 15) & ~(size_t)15, bs = (size_t)n * sizeof(float4);
+    PrtChainList lists[2] = {{d_o, d_d, (float4*)(ext + 2 * b3), (float4*)(ext + 2 * b3 + bs)},
+                             {(float*)ext, (float*)(ext + b3), (float4*)(ext + 2 * b3 + 2 * bs), (float4*)(ext + 2 * b3 + 3 * bs)}};
+    uint32_t* d_cnt = (uint32_t*)(ext + 2 * b3 + 4 * bs);
+    HIPCHECK(c, hipMemsetAsync(d_cnt, 0, (PRT_FEATURE_MAX_SPECULAR + 1u) * sizeof(uint32_t), c->stream));
+    PrtChainArgs a{d_h, d_a, c->dsc.mat_rgbs, c->dsc.mat_type, c->ftrace, out, d_cnt};
+    prt_launch_ft_start(c->stream, n, d_d, a, lists[1]);
+    HIPCHECK(c, hipGetLastError());
+    int cur = 1;
+    for (uint32_t r = 0; r < c->ftrace.max_specular; ++r) {
+        uint32_t live = 0;
+        HIPCHECK(c, hipMemcpyAsync(&live, d_cnt + r, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        if (live == 0u) break;
+        if (live > n) return fail(c, PRT_ERR_HIP, "prt_render_features: live count %u above %u rays", live, n);
+        if ((rc = enqueue_query(c, live, lists[cur].o, lists[cur].d, nullptr, d_h, nullptr))) return rc;
+        if (d_a) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), live, c->rb[0], nullptr, d_a);
+        a.count = d_cnt + r + 1;
+        prt_launch_ft_step(c->stream, live, lists[cur], a, lists[cur ^ 1]);
+        HIPCHECK(c, hipGetLastError());
+        cur ^= 1;
+    }
+    return PRT_OK;
+}
+
+// The sampled set (include/prt.h "Sampled guide features") of the n = W x H pixels, after the other sets are enqueued.
+// Degenerate (no jitter, no lens): a copy of the centre-ray set.  Otherwise chunks of whole samples: the render's primary
+// rays of the chunk, sample-major; the ray-query pipeline and the per-ray records exactly as above, with the slot in the
+// place of the pixel (following: the chain kernels write every slot's record, so the first-hit pack is not needed); the
+// ordered reduce into the set's own records; the finish after the last chunk.
+static int enqueue_feature_samples(PrtContext* c, uint32_t n) {
+    int rc;
+    const uint32_t K = c->fsamp.samples;
+    const bool follow = c->ftrace.max_specular > 0u;
+    if (n > c->samp_cap) {
+        free_dev(c->samp.alb);
+        c->samp = PrtFeatureBufs{nullptr, nullptr, nullptr};
+        c->samp_cap = 0;
+        HIPCHECK(c, hipMalloc((void**)&c->samp.alb, 3 * (size_t)n * sizeof(float4)));
+        c->samp_cap = n;
+    }
+    c->samp.nrm = c->samp.alb + n;
+    c->samp.pos = c->samp.alb + 2 * (size_t)n;
+    if (c->sampling.jitter == 0u && !(c->lens.aperture > 0.0f)) {
+        const PrtFeatureBufs src = follow ? c->guide : c->feat;
+        prt_launch_fs_finish(c->stream, n, K, &src, c->samp);
+        HIPCHECK(c, hipGetLastError());
+        return PRT_OK;
+    }
+    // samples per chunk: about 2^22 rays unless a chunk size is forced, never more than 2^28 rays, at least one sample
+    uint32_t cs = c->feature_chunk > 0 ? (uint32_t)c->feature_chunk : std::max<uint32_t>(1u, (1u << 22) / n);
+    cs = std::min(std::min(cs, K), std::max<uint32_t>(1u, (uint32_t)PRT_DENOISE_MAX_PIXELS / n));
+    const uint32_t m = cs * n;
+    // the scratch below and the path state of m rays may be reallocated: nothing enqueued above may still be using them
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    const size_t b3 = ((size_t)m * 12 + 15) & ~(size_t)15, bh = ((size_t)m * sizeof(PrtHit) + 15) & ~(size_t)15;
+    const size_t br = 3 * (size_t)m * sizeof(float4);
+    const size_t first = 3 * b3 + bh + br;
+    if ((rc = ensure_scratch(c, first + (follow ? chain_scratch_bytes(m) : 0) + 64))) return rc;
+    char* base = (char*)c->d_scratch;
+    float* d_o = (float*)base;
+    float* d_d = (float*)(base + b3);
+    float* d_a = (float*)(base + 2 * b3);
+    PrtHit* d_h = (PrtHit*)(base + 3 * b3);
+    float4* d_r = (float4*)(base + 3 * b3 + bh);
+    const bool textured = tex_on(c);
+    const DevLens dlens{c->lens.aperture, c->lens.focus_distance};
+    for (uint32_t s0 = 0; s0 < K; s0 += cs) {
+        const PrtSampleChunk ch{c->tm.W, c->tm.H, s0, std::min(cs, K - s0), c->fsamp.first_sample, c->fsamp.seed, c->sampling.jitter};
+        const uint32_t mc = ch.cs * n;
+        const PrtFeatureBufs rec{d_r, d_r + mc, d_r + 2 * (size_t)mc};
+        prt_launch_fs_rays(c->stream, c->cam, dlens, ch, d_o, d_d);
+        HIPCHECK(c, hipGetLastError());
+        if ((rc = enqueue_query(c, mc, d_o, d_d, nullptr, d_h, nullptr))) return rc;
+        if (textured) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), mc, c->rb[0], nullptr, d_a);
+        if (follow) {
+            if ((rc = enqueue_chains(c, mc, d_o, d_d, d_h, textured ? d_a : nullptr, base + first, rec))) return rc;
+        } else {
+            prt_launch_dn_pack_features(c->stream, mc, d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, rec);
+        }
+        prt_launch_fs_reduce(c->stream, ch, rec, c->samp);
+        HIPCHECK(c, hipGetLastError());
+    }
+    prt_launch_fs_finish(c->stream, n, K, nullptr, c->samp);
+    HIPCHECK(c, hipGetLastError());
+    return PRT_OK;
+}
+
 int prt_render_features(PrtContext* c) {
     int rc = check_ready(c);
     if (rc) return rc;
@@ -2432,9 +2544,8 @@ int prt_render_features(PrtContext* c) {
     // of prt_closest_hit_device, the textured albedo of prt_hit_uv while a binding textures something, then the records
     const size_t b1 = ((size_t)n * 4 + 15) & ~(size_t)15, b3 = ((size_t)n * 12 + 15) & ~(size_t)15;
     const size_t bh = ((size_t)n * sizeof(PrtHit) + 15) & ~(size_t)15;
-    // (following: a second ray list, two state lists of two float4 each, and one live count per round)
-    const size_t first = 2 * b1 + 3 * b3 + bh, bs = (size_t)n * sizeof(float4);
-    if ((rc = ensure_scratch(c, first + (follow ? 2 * b3 + 4 * bs + 64 : 0) + 64))) return rc;
+    const size_t first = 2 * b1 + 3 * b3 + bh;
+    if ((rc = ensure_scratch(c, first + (follow ? chain_scratch_bytes(n) : 0) + 64))) return rc;
     char* base = (char*)c->d_scratch;
     float* d_px = (float*)base;
     float* d_py = (float*)(base + b1);
@@ -2450,39 +2561,14 @@ int prt_render_features(PrtContext* c) {
     if (textured) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), n, c->rb[0], nullptr, d_a);  // (rays and final hit ids are in rb[0])
     prt_launch_dn_pack_features(c->stream, n, d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, c->feat);
     HIPCHECK(c, hipGetLastError());
-    if (follow) {
-        // The guide set: the start kernel decides every pixel at k = 0 from the records above (nothing is traced twice) and
-        // leaves the live chains in list 1; each round reads the 4-byte live count (one small wait, as prt_render_adaptive
-        // has per pass), queries the live rays only, and steps them into the other list.  After round r every live chain
-        // has followed r + 2 vertices, so round max_specular - 1 ends them all.
-        char* ext = base + first;
-        PrtChainList lists[2] = {{d_o, d_d, (float4*)(ext + 2 * b3), (float4*)(ext + 2 * b3 + bs)},
-                                 {(float*)ext, (float*)(ext + b3), (float4*)(ext + 2 * b3 + 2 * bs), (float4*)(ext + 2 * b3 + 3 * bs)}};
-        uint32_t* d_cnt = (uint32_t*)(ext + 2 * b3 + 4 * bs);
-        HIPCHECK(c, hipMemsetAsync(d_cnt, 0, (PRT_FEATURE_MAX_SPECULAR + 1u) * sizeof(uint32_t), c->stream));
-        PrtChainArgs a{d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, c->ftrace, c->guide, d_cnt};
-        prt_launch_ft_start(c->stream, n, d_d, a, lists[1]);
-        HIPCHECK(c, hipGetLastError());
-        int cur = 1;
-        for (uint32_t r = 0; r < c->ftrace.max_specular; ++r) {
-            uint32_t live = 0;
-            HIPCHECK(c, hipMemcpyAsync(&live, d_cnt + r, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHECK(c, hipStreamSynchronize(c->stream));
-            if (live == 0u) break;
-            if (live > n) return fail(c, PRT_ERR_HIP, "prt_render_features: live count %u above %u pixels", live, n);
-            if ((rc = enqueue_query(c, live, lists[cur].o, lists[cur].d, nullptr, d_h, nullptr))) return rc;
-            if (textured) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), live, c->rb[0], nullptr, d_a);
-            a.count = d_cnt + r + 1;
-            prt_launch_ft_step(c->stream, live, lists[cur], a, lists[cur ^ 1]);
-            HIPCHECK(c, hipGetLastError());
-            cur ^= 1;
-        }
-    }
+    if (follow && (rc = enqueue_chains(c, n, d_o, d_d, d_h, textured ? d_a : nullptr, base + first, c->guide))) return rc;
+    if (c->fsamp.samples > 0u && (rc = enqueue_feature_samples(c, n))) return rc;
     if ((rc = prt_synchronize(c))) return rc;
     c->feat_W = tm.W;
     c->feat_H = tm.H;
     c->feat_valid = true;
     c->guide_valid = follow;
+    c->samp_valid = c->fsamp.samples > 0u;
     return PRT_OK;
 }
 
@@ -2508,8 +2594,31 @@ int prt_get_feature_trace(PrtContext* c, PrtFeatureTrace* out) {
     return PRT_OK;
 }
 
-// The set the spatial filter is guided by: the guide set while the mode is on, else the first-hit set.
-static PrtFeatureBufs filter_features(const PrtContext* c) { return c->guide_valid ? c->guide : c->feat; }
+void prt_feature_sampling_defaults(PrtFeatureSampling* out) {
+    if (out) *out = PrtFeatureSampling{0u, 0u, 0u};
+}
+
+int prt_set_feature_sampling(PrtContext* c, const PrtFeatureSampling* fs) {
+    if (!c) return PRT_ERR_INVALID;
+    c->feat_valid = false;
+    c->guide_valid = false;
+    c->samp_valid = false;
+    const PrtFeatureSampling t = fs ? *fs : PrtFeatureSampling{0u, 0u, 0u};
+    if (t.samples > PRT_FEATURE_MAX_SAMPLES) return fail(c, PRT_ERR_INVALID, "bad feature sampling: samples must be 0..64");
+    c->fsamp = t;
+    return PRT_OK;
+}
+
+int prt_get_feature_sampling(PrtContext* c, PrtFeatureSampling* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    *out = c->fsamp;
+    return PRT_OK;
+}
+
+// The centre-ray set the guide readers return: the guide set while that mode is on, else the first-hit set.
+static PrtFeatureBufs centre_features(const PrtContext* c) { return c->guide_valid ? c->guide : c->feat; }
+// The set the spatial filter is guided by: the sampled set while that mode is on, else the centre-ray set.
+static PrtFeatureBufs filter_features(const PrtContext* c) { return c->samp_valid ? c->samp : centre_features(c); }
 
 // A feature set's records to planar host arrays (each may be null); bounces: the albedo record's .w.
 static int read_feature_records(PrtContext* c, PrtFeatureBufs f, float* albedo, float* normal, float* position, float* depth, int32_t* prim,
@@ -2537,7 +2646,13 @@ static int read_feature_records(PrtContext* c, PrtFeatureBufs f, float* albedo, 
 
 int prt_features_read_guide(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim, uint32_t* bounces) {
     if (!c) return PRT_ERR_INVALID;
-    return read_feature_records(c, filter_features(c), albedo, normal, position, depth, prim, bounces);
+    return read_feature_records(c, centre_features(c), albedo, normal, position, depth, prim, bounces);
+}
+
+int prt_features_read_sampled(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim, uint32_t* hits) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->feat_valid || !c->samp_valid) return fail(c, PRT_ERR_INVALID, "no current sampled feature set (prt_set_feature_sampling, prt_render_features)");
+    return read_feature_records(c, c->samp, albedo, normal, position, depth, prim, hits);
 }
 
 int prt_features_read(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim) {
@@ -3327,6 +3442,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "refill_min" && value >= 1 && value <= 64) c->tune.refill_min = (uint32_t)value;
     else if (n == "light_buckets" && (value == 0 || value == 1)) c->light_buckets = value;
     else if (n == "denoise_lds" && value >= 0 && value <= 2) c->dn_lds = value;
+    else if (n == "feature_chunk" && value >= 0 && value <= (int)PRT_FEATURE_MAX_SAMPLES) c->feature_chunk = value;
     else if (n == "exit_max" && value >= 0 && value < 64) c->tune.exit_max = (uint32_t)value;
     else return fail(c, PRT_ERR_INVALID, "unknown parameter or bad value: %s = %d", name, value);
     return PRT_OK;

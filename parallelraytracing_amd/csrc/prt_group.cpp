@@ -313,6 +313,11 @@ int prt_group_set_feature_trace(PrtGroup* g, const PrtFeatureTrace* ft) {
     return for_each_rank(g, [&](uint32_t r) { return prt_set_feature_trace(g->ctx[r], ft); }, false);
 }
 
+int prt_group_set_feature_sampling(PrtGroup* g, const PrtFeatureSampling* fs) {
+    if (!g || g->ctx.empty()) return PRT_ERR_INVALID;
+    return for_each_rank(g, [&](uint32_t r) { return prt_set_feature_sampling(g->ctx[r], fs); }, false);
+}
+
 int prt_group_set_lens(PrtGroup* g, const PrtLens* lens) {
     if (!g) return PRT_ERR_INVALID;
     return for_each_rank(g, [&](uint32_t r) { return prt_set_lens(g->ctx[r], lens); }, false);
@@ -443,7 +448,12 @@ int prt_group_film_denoise(PrtGroup* g, const PrtDenoise* cfg, float* rgb_out, f
     PrtContext* c0 = g->ctx[0];
     std::vector<float> alb(3 * npix), nrm(3 * npix), pos(3 * npix);
     std::vector<int32_t> prim(npix);
-    if ((rc = prt_render_features(c0)) || (rc = prt_features_read_guide(c0, alb.data(), nrm.data(), pos.data(), nullptr, prim.data(), nullptr)) ||
+    // (the filter's set: the sampled one while PrtFeatureSampling is on, else the guide / first-hit set)
+    PrtFeatureSampling fs{0u, 0u, 0u};
+    prt_get_feature_sampling(c0, &fs);
+    if ((rc = prt_render_features(c0)) ||
+        (rc = fs.samples ? prt_features_read_sampled(c0, alb.data(), nrm.data(), pos.data(), nullptr, prim.data(), nullptr)
+                         : prt_features_read_guide(c0, alb.data(), nrm.data(), pos.data(), nullptr, prim.data(), nullptr)) ||
         (rc = prt_denoise(c0, cfg, g->W, g->H, rgb.data(), var.data(), alb.data(), nrm.data(), pos.data(), prim.data(), rgb_out, var_out)))
         return gfail(g, rc, "rank 0: %s", prt_last_error(c0));
     return PRT_OK;

@@ -9,7 +9,7 @@
 //              [--adaptive THRESHOLD [--min-spp N --spp-step N --max-spp N --noise-floor F]
 //               [--samples-out FILE.pfm] [--noise-out FILE.pfm]]
 //              [--denoise [--denoise-iterations N --denoise-sigma-l S --denoise-sigma-z S --no-demodulate]
-//               [--follow-specular N [--mirror-roughness R]]]
+//               [--follow-specular N [--mirror-roughness R]] [--feature-samples K]]
 //              [--features-out PREFIX]
 //              [--frames N --orbit-deg D [--temporal [--temporal-max-history H]]]
 // --orbit-deg D turns --frames N into an animation: frame f is rendered with --spp samples (sample indices f * spp ...) from the
@@ -24,6 +24,11 @@
 // (prt_set_feature_trace; a Metal with roughness <= --mirror-roughness, default 0.1, is a mirror): the reflected image is
 // filtered by what is seen in the mirror, not as the mirror's plane.  --features-out then also writes P_guide_albedo.pfm,
 // P_guide_normal.pfm, P_guide_position.pfm, P_guide_depth.pfm and P_guide_bounces.pfm.
+// --feature-samples K (1..64) averages the filter's features over the first K of each pixel's own primary rays, through the
+// lens and the jitter (prt_set_feature_sampling with the run's seed and first sample index; with --frames N --orbit-deg D,
+// every frame's own): a defocused pixel gets the mixture of surfaces its film holds.  It needs --denoise or
+// --features-out; --features-out then also writes P_sampled_albedo.pfm, P_sampled_normal.pfm, P_sampled_position.pfm,
+// P_sampled_depth.pfm and P_sampled_hits.pfm.
 // --adaptive T renders with tile-adaptive sampling (prt_render_adaptive) instead of --spp samples everywhere: --min-spp
 // (default 8) samples for every pixel, then --spp-step (8) at a time for the 8x8 tiles that still hold a pixel whose standard
 // error exceeds T x (mean luminance + --noise-floor (0.01)), up to --max-spp (64).  --samples-out writes every pixel's sample
@@ -71,6 +76,7 @@ int main(int argc, char** argv) {
     prt_denoise_defaults(&dn);
     PrtFeatureTrace ftrace;
     prt_feature_trace_defaults(&ftrace);
+    uint32_t feature_samples = 0;
     bool orbit = false, temporal = false;
     double orbit_deg = 0.0;
     PrtTemporal tp;
@@ -141,6 +147,7 @@ int main(int argc, char** argv) {
         else if (a == "--no-demodulate") dn.demodulate = 0u;
         else if (a == "--follow-specular") ftrace.max_specular = (uint32_t)atoi(next());
         else if (a == "--mirror-roughness") ftrace.roughness_max = (float)atof(next());
+        else if (a == "--feature-samples") feature_samples = (uint32_t)atoi(next());
         else if (a == "--features-out") features_out = next();
         else if (a == "--orbit-deg") { orbit_deg = atof(next()); orbit = true; }
         else if (a == "--temporal") temporal = true;
@@ -158,6 +165,10 @@ int main(int argc, char** argv) {
     }
     if (!adaptive && (!samples_out.empty() || !noise_out.empty())) {
         fprintf(stderr, "--samples-out and --noise-out go with --adaptive\n");
+        return 2;
+    }
+    if (feature_samples && !denoise && features_out.empty()) {
+        fprintf(stderr, "--feature-samples goes with --denoise or --features-out\n");
         return 2;
     }
     if (temporal && !orbit) {
@@ -209,6 +220,7 @@ int main(int argc, char** argv) {
         if (!env.empty()) r.SetEnvironmentPfm(env, env_share);
         if (fov_deg != 0.0 || aperture != 0.0f) r.SetLens((float)(fov_deg * 3.14159265358979323846 / 180.0), aperture, focus);
         if (ftrace.max_specular) r.SetFeatureTrace(ftrace.max_specular, ftrace.roughness_max);
+        if (feature_samples) r.SetFeatureSampling(feature_samples, seed, 0u);
         if (adaptive || denoise || temporal) r.SetFilmStatistics(true);
         if (orbit) {  // the animation: one cleared film per frame, the camera on a circle about the vertical axis
             std::vector<float> mean((size_t)W * H * 3), trgb;
@@ -221,6 +233,7 @@ int main(int argc, char** argv) {
                 r.SetCamera(camera);
                 r.Clear();
                 r.SetFrameIndex(f * spp);
+                if (feature_samples) r.SetFeatureSampling(feature_samples, seed, f * spp);
                 r.Render(spp);
                 r.Download();
                 for (size_t i = 0; i < (size_t)W * H; ++i)
@@ -308,6 +321,18 @@ int main(int argc, char** argv) {
                     prt_write_pfm((features_out + "_guide_position.pfm").c_str(), ft.position.data(), W, H) ||
                     write_grey(features_out + "_guide_depth.pfm", ft.depth) || write_grey(features_out + "_guide_bounces.pfm", fb)) {
                     fprintf(stderr, "cannot write %s_guide_*.pfm\n", features_out.c_str());
+                    return 1;
+                }
+            }
+            if (feature_samples) {
+                std::vector<uint32_t> hits;
+                r.RenderSampledFeatures(ft, hits);
+                const std::vector<float> fh(hits.begin(), hits.end());
+                if (prt_write_pfm((features_out + "_sampled_albedo.pfm").c_str(), ft.albedo.data(), W, H) ||
+                    prt_write_pfm((features_out + "_sampled_normal.pfm").c_str(), ft.normal.data(), W, H) ||
+                    prt_write_pfm((features_out + "_sampled_position.pfm").c_str(), ft.position.data(), W, H) ||
+                    write_grey(features_out + "_sampled_depth.pfm", ft.depth) || write_grey(features_out + "_sampled_hits.pfm", fh)) {
+                    fprintf(stderr, "cannot write %s_sampled_*.pfm\n", features_out.c_str());
                     return 1;
                 }
             }

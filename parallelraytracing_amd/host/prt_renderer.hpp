@@ -301,6 +301,21 @@ public:
                                                               out.prim.data(), bounces.data()))
             throw Error(std::string("prt_render_features: ") + prt_last_error(c));
     }
+    // The sampled set (prt_features_read_sampled, SetFeatureSampling): the same images averaged over the render's own primary
+    // rays of every pixel, and how many of them hit something.  Needs SetFeatureSampling(samples > 0).
+    void RenderSampledFeatures(Features& out, std::vector<uint32_t>& hits) {
+        const size_t n = (size_t)film_->width * film_->height;
+        out.albedo.assign(3 * n, 0.0f);
+        out.normal.assign(3 * n, 0.0f);
+        out.position.assign(3 * n, 0.0f);
+        out.depth.assign(n, 0.0f);
+        out.prim.assign(n, -1);
+        hits.assign(n, 0u);
+        PrtContext* c = prt_group_context(grp_, 0);
+        if (prt_render_features(c) || prt_features_read_sampled(c, out.albedo.data(), out.normal.data(), out.position.data(), out.depth.data(),
+                                                                out.prim.data(), hits.data()))
+            throw Error(std::string("prt_render_features: ") + prt_last_error(c));
+    }
     // The gathered film through the edge-avoiding filter (prt_group_film_denoise; include/prt.h "The filter contract"):
     // width * height * 3 floats of denoised mean radiance, and the filtered variance if asked.  Needs SetFilmStatistics(true).
     // cfg = nullptr: the defaults.
@@ -355,6 +370,12 @@ public:
     void SetFeatureTrace(uint32_t max_specular = 0u, float roughness_max = 0.1f) {
         const PrtFeatureTrace ft{max_specular, roughness_max};
         check(prt_group_set_feature_trace(grp_, &ft));
+    }
+    // Sampled guide features (PrtFeatureSampling): the denoiser's features are averaged over `samples` (0..64) of the
+    // render's own primary rays per pixel, those of sample indices first_sample ... under `seed`.  0 = off (the default)
+    void SetFeatureSampling(uint32_t samples = 0u, uint32_t seed = 0u, uint32_t first_sample = 0u) {
+        const PrtFeatureSampling fs{samples, seed, first_sample};
+        check(prt_group_set_feature_sampling(grp_, &fs));
     }
     // Light sampling toward the analytic emitters (PrtLighting): PRT_LIGHTING_OFF / _NEE_MIS / _NEE
     void SetLighting(uint32_t mode) {

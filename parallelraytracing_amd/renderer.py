@@ -438,6 +438,16 @@ def _read_features(check, ctx, W: int, H: int) -> dict:
                                         g["position"].ctypes.data_as(_fp), g["depth"].ctypes.data_as(_fp),
                                         g["prim"].ctypes.data_as(C.POINTER(C.c_int32)), g["bounces"].ctypes.data_as(_u32p)))
         out["guide"] = g
+    fs = capi.PrtFeatureSampling()
+    check(L.prt_get_feature_sampling(ctx, C.byref(fs)))
+    if fs.samples > 0:        # the sampled set: the render's own primary rays averaged per pixel
+        g = dict(albedo=np.zeros((H, W, 3), np.float32), normal=np.zeros((H, W, 3), np.float32),
+                 position=np.zeros((H, W, 3), np.float32), depth=np.zeros((H, W), np.float32), prim=np.zeros((H, W), np.int32),
+                 hits=np.zeros((H, W), np.uint32))
+        check(L.prt_features_read_sampled(ctx, g["albedo"].ctypes.data_as(_fp), g["normal"].ctypes.data_as(_fp),
+                                          g["position"].ctypes.data_as(_fp), g["depth"].ctypes.data_as(_fp),
+                                          g["prim"].ctypes.data_as(C.POINTER(C.c_int32)), g["hits"].ctypes.data_as(_u32p)))
+        out["sampled"] = g
     return out
 
 
@@ -539,6 +549,21 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_get_feature_trace(self._ctx, C.byref(ft)))
         return ft
 
+    def set_feature_sampling(self, samples: int = 0, seed=None, first_sample: int = 0) -> capi.PrtFeatureSampling:
+        """Sampled guide features (include/prt.h PrtFeatureSampling): the features averaged over `samples` (0..64) of the
+        render's own primary rays per pixel, those of samples first_sample .. first_sample + samples - 1 under `seed`
+        (None: the renderer's own seed), through the lens and the jitter, each followed as set_feature_trace says.  0 (the
+        default) = off.  While on, render_features() gains "sampled", and denoise() / temporal_step(denoise=...) filter by
+        it.  Stays with the renderer across SetCamera / Init."""
+        fs = capi.PrtFeatureSampling(int(samples), int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample))
+        self._check(capi.lib().prt_set_feature_sampling(self._ctx, C.byref(fs)))
+        return fs
+
+    def get_feature_sampling(self) -> capi.PrtFeatureSampling:
+        fs = capi.PrtFeatureSampling()
+        self._check(capi.lib().prt_get_feature_sampling(self._ctx, C.byref(fs)))
+        return fs
+
     def set_film_statistics(self, on: bool = True):
         """Second moments of every pixel's luminance beside the film (include/prt.h "Film statistics and adaptive sampling").
         Switching them clears the film (and restarts the sample index)."""
@@ -611,7 +636,10 @@ class HipWavefrontRenderer:
         """First-hit feature images of the pixel-centre rays (prt_render_features): albedo, normal, position (H, W, 3)
         float32, depth (H, W) float32, prim (H, W) int32 (-1: a miss); the whole image whatever the partition.  They do not
         follow mirrors or glass and do not average over a lens or jitter.  While set_feature_trace(max_specular > 0) is on,
-        "guide" holds the same five images at the end of each pixel's specular chain, plus bounces (H, W) uint32."""
+        "guide" holds the same five images at the end of each pixel's specular chain, plus bounces (H, W) uint32.  While
+        set_feature_sampling(samples > 0) is on, "sampled" holds the five images averaged over that many of the render's own
+        primary rays per pixel (lens and jitter included, each ray followed like the guide set's; the normal renormalised,
+        prim that of the first sample that hit), plus hits (H, W) uint32: how many of the pixel's samples hit something."""
         f = self.film
         return _read_features(self._check, self._ctx, f.width, f.height)
 
@@ -1338,6 +1366,20 @@ class HipWavefrontGroupRenderer:
         ft = capi.PrtFeatureTrace(int(max_specular), float(roughness_max))
         self._check(capi.lib().prt_group_set_feature_trace(self._grp, C.byref(ft)))
         return ft
+
+    def set_feature_sampling(self, samples: int = 0, seed=None, first_sample: int = 0) -> capi.PrtFeatureSampling:
+        """Sampled guide features on every rank (HipWavefrontRenderer.set_feature_sampling)."""
+        fs = capi.PrtFeatureSampling(int(samples), int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample))
+        self._check(capi.lib().prt_group_set_feature_sampling(self._grp, C.byref(fs)))
+        return fs
+
+    def get_feature_sampling(self) -> capi.PrtFeatureSampling:
+        """Rank 0's setting (every rank holds the same)."""
+        fs = capi.PrtFeatureSampling()
+        L = capi.lib()
+        if L.prt_get_feature_sampling(L.prt_group_context(self._grp, 0), C.byref(fs)):
+            raise PrtError("prt_get_feature_sampling failed")
+        return fs
 
     def set_film_statistics(self, on: bool = True):
         """HipWavefrontRenderer.set_film_statistics on every rank."""
