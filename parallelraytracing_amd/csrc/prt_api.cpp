@@ -32,6 +32,7 @@
 #include "prt_scene.h"
 #include "prt_temporal.h"
 #include "prt_temporal_contract.h"
+#include "prt_workspace.h"
 
 namespace {
 
@@ -43,6 +44,14 @@ constexpr size_t kLightStatWords = 2 * (size_t)PRT_RAY_STAT_SLOTS;  // k_light_a
 struct EventPair {
     hipEvent_t a, b;
     int kind;  // 0 raygen, 1 intersect (dominant kernel), 2 shade, 3 accumulate, 4 analytic-primitive scan
+};
+
+// A device allocation that only grows.  A failed ensure leaves it empty.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int ensure(PrtContext* c, size_t need);
+    void release();
 };
 
 }  // namespace
@@ -103,8 +112,7 @@ struct PrtContext {
     unsigned long long* d_trav_stats = nullptr; // 3
 
     // ---- scratch for the function-level entry points ----
-    void* d_scratch = nullptr;
-    size_t scratch_bytes = 0;
+    DevBuf scratch;
 
     // ---- stats ----
     bool timing = false;
@@ -142,8 +150,7 @@ struct PrtContext {
     uint32_t* d_work = nullptr;   // chunk cursor of the persistent traversal kernel
     float4* d_pix = nullptr;      // compact primary rays: one record per local pixel (PrtPrimary)
     uint32_t pix_entries = 0;
-    uint32_t* d_spill = nullptr;  // global part of the per-lane traversal stacks
-    size_t spill_entries = 0;
+    DevBuf spill;                 // global part of the per-lane traversal stacks (uint32_t entries)
 
     // ---- light sampling (PrtLighting, include/prt.h) ----
     uint32_t lighting = PRT_LIGHTING_OFF;
@@ -187,32 +194,25 @@ struct PrtContext {
     // ---- first-hit features and the film denoiser (include/prt.h): the records of prt_render_features, valid until a call
     // that changes what the centre rays see; the filter's workspace (packed records of the array entry points, the two
     // colour + variance buffers, staging for host arrays) ----
-    PrtFeatureBufs feat{nullptr, nullptr, nullptr};  // one allocation: feat.alb is its base
-    uint32_t feat_cap = 0;                           // pixels it holds
+    DevBuf feat;                                     // 3 x feat_W x feat_H float4 (feature_view)
     uint32_t feat_W = 0, feat_H = 0;
     bool feat_valid = false;
     // the guide set through specular chains (PrtFeatureTrace): written beside the first-hit set while max_specular > 0,
     // current only while feat_valid is (every site that drops the one drops the other)
     PrtFeatureTrace ftrace{0u, 0.1f};                // prt_set_feature_trace: a property of the context, like the lens
-    PrtFeatureBufs guide{nullptr, nullptr, nullptr}; // one allocation: guide.alb is its base
-    uint32_t guide_cap = 0;
+    DevBuf guide;
     bool guide_valid = false;
     // the sampled set (PrtFeatureSampling): written beside the others while samples > 0, current only while feat_valid is
     PrtFeatureSampling fsamp{0u, 0u, 0u};            // prt_set_feature_sampling: a property of the context, like ftrace
-    PrtFeatureBufs samp{nullptr, nullptr, nullptr};  // one allocation: samp.alb is its base; the running sums until finished
-    uint32_t samp_cap = 0;
+    DevBuf samp;                                     // the running sums until finished
     bool samp_valid = false;
     int feature_chunk = 0;  // prt_set_param("feature_chunk", n): samples per chunk of the sampled pass, 0 = by the ray budget
-    void* d_dn = nullptr;
-    size_t dn_bytes = 0;
+    DevBuf dn;
     // ---- temporal reprojection (include/prt.h): two history sets that ping-pong, the blended planar frame, status and
     // counters in one allocation; the basis and the placed copies' matrices of the step that wrote the history ----
-    void* d_tp = nullptr;
-    size_t tp_bytes = 0;
-    void* d_tp_mt = nullptr;           // the motion table of a step (PrtMotionTable)
-    size_t tp_mt_bytes = 0;
-    void* d_tpa = nullptr;             // workspace of the array entry points
-    size_t tpa_bytes = 0;
+    DevBuf tp;
+    DevBuf tp_mt;                      // the motion table of a step (PrtMotionTable)
+    DevBuf tpa;                        // workspace of the array entry points
     uint32_t tp_W = 0, tp_H = 0;
     int tp_set = 0;                    // which set holds the history
     bool tp_valid = false;
@@ -276,6 +276,85 @@ void free_dev(T*& p) {
         p = nullptr;
     }
 }
+
+void DevBuf::release() {
+    free_dev(p);
+    bytes = 0;
+}
+
+int DevBuf::ensure(PrtContext* c, size_t need) {
+    if (need <= bytes) return PRT_OK;
+    release();
+    HIPCHECK(c, hipMalloc(&p, need));
+    bytes = need;
+    return PRT_OK;
+}
+
+// Grows buf to the size of a layout (prt_workspace.h) and hands out the pointers the layout declared, inside buf.
+int commit(PrtContext* c, const PrtWorkspace& ws, DevBuf& buf) {
+    const int rc = buf.ensure(c, ws.bytes());
+    if (rc || ws.bind(buf.p, buf.bytes)) return rc;
+    return fail(c, PRT_ERR_INVALID, "a workspace of %d arrays in %zu bytes does not fit its buffer of %zu", ws.regions(), ws.bytes(), buf.bytes);
+}
+
+// count elements host -> device / device -> host, asynchronously on the context's stream
+template <class T>
+int upload(PrtContext* c, T* dst, const T* src, size_t count) {
+    HIPCHECK(c, hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    return PRT_OK;
+}
+template <class T>
+int download(PrtContext* c, T* dst, const T* src, size_t count) {
+    HIPCHECK(c, hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    return PRT_OK;
+}
+
+// A feature set of n pixels in one array of 3 n records: albedo, normal, position.
+PrtFeatureBufs feature_view(void* base, size_t n) {
+    float4* a = (float4*)base;
+    return PrtFeatureBufs{a, a + n, a + 2 * n};
+}
+
+// ---- the layouts several entry points share ----
+// What enqueue_chains needs beside its arguments for up to n rays: a second ray list, two state lists of two float4 each,
+// and one live count per round.  A caller declares it behind its own arrays, in the same layout.
+struct ChainScratch {
+    float *o, *d;
+    float4* s[4];
+    uint32_t* cnt;
+    void declare(PrtWorkspace& ws, size_t n) {
+        ws.add(&o, 3 * n).add(&d, 3 * n);
+        for (float4*& p : s) ws.add(&p, n);
+        ws.add(&cnt, PRT_FEATURE_MAX_SPECULAR + 1u);
+    }
+};
+
+// The filter's workspace for n pixels: the two colour + variance buffers; for the array entry points the packed records
+// (a feature set) before them, for the film's forms the planar outputs behind them.
+struct FilterScratch {
+    float4 *rec = nullptr, *cv0 = nullptr, *cv1 = nullptr;
+    float *out = nullptr, *var = nullptr;
+    void declare_arrays(PrtWorkspace& ws, size_t n) { ws.add(&rec, 3 * n).add(&cv0, n).add(&cv1, n); }
+    int commit_film(PrtContext* c, size_t n) {
+        PrtWorkspace ws;
+        ws.add(&cv0, n).add(&cv1, n).add(&out, 3 * n).add(&var, n);
+        return commit(c, ws, c->dn);
+    }
+};
+
+// A history set of n pixels: cn, nrm, pos and mm, one array each
+void declare_history(PrtWorkspace& ws, PrtHistoryBufs* h, size_t n) { ws.add(&h->cn, n).add(&h->nrm, n).add(&h->pos, n).add(&h->mm, n); }
+
+// The array entry points' records of n pixels: the current frame's, the history's, the new cn / mm
+struct TemporalScratch {
+    PrtHistoryBufs cur, prev, next;
+    void declare(PrtWorkspace& ws, size_t n) {
+        declare_history(ws, &cur, n);
+        declare_history(ws, &prev, n);
+        next.nrm = next.pos = nullptr;
+        ws.add(&next.cn, n).add(&next.mm, n);
+    }
+};
 
 void free_path_state(PrtContext* c) {
     for (int i = 0; i < 2; ++i) {
@@ -533,21 +612,7 @@ int ensure_counters(PrtContext* c) {
 // global spill area of the traversal stacks: [prt_spill_rows of the scene's trees][grid threads]
 int ensure_spill(PrtContext* c) {
     const size_t need = (size_t)c->tune.grid_blocks * 256u * prt_spill_rows(c->hs.bvh.max_stack4, c->hs.bvh.max_depth);
-    if (need <= c->spill_entries) return PRT_OK;
-    free_dev(c->d_spill);
-    c->spill_entries = 0;
-    HIPCHECK(c, hipMalloc((void**)&c->d_spill, need * sizeof(uint32_t)));
-    c->spill_entries = need;
-    return PRT_OK;
-}
-
-int ensure_scratch(PrtContext* c, size_t bytes) {
-    if (bytes <= c->scratch_bytes) return PRT_OK;
-    free_dev(c->d_scratch);
-    c->scratch_bytes = 0;
-    HIPCHECK(c, hipMalloc(&c->d_scratch, bytes));
-    c->scratch_bytes = bytes;
-    return PRT_OK;
+    return c->spill.ensure(c, need * sizeof(uint32_t));
 }
 
 void free_scene(PrtContext* c) {
@@ -640,9 +705,9 @@ void walk_rays(PrtContext* c, const PrtRayBuf& rays, const uint32_t* count, uint
     if (!prt_route_walk8(c->variant == 0, c->dsc.n_insts != 0u, c->dsc.nodes != nullptr))
         prt_launch_intersect(c->stream, c->dsc, rays, count, max_rays, c->hs.bvh.max_depth <= 31 ? 31 : 63, c->variant, stats);
     else if (any)
-        prt_launch_occluded(c->stream, c->dsc, rays, count, c->d_work, c->d_spill, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune, seeded);
+        prt_launch_occluded(c->stream, c->dsc, rays, count, c->d_work, (uint32_t*)c->spill.p, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune, seeded);
     else
-        prt_launch_traverse(c->stream, c->dsc, rays, count, c->d_work, c->d_spill, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4,
+        prt_launch_traverse(c->stream, c->dsc, rays, count, c->d_work, (uint32_t*)c->spill.p, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4,
                             tune, stats, primary);
 }
 
@@ -1168,16 +1233,8 @@ void prt_destroy(PrtContext* c) {
         }
         free_dev(c->d_work);
         free_dev(c->d_pix);
-        free_dev(c->d_spill);
         free_dev(c->d_sort);
-        free_dev(c->d_scratch);
-        free_dev(c->feat.alb);
-        free_dev(c->guide.alb);
-        free_dev(c->samp.alb);
-        free_dev(c->d_dn);
-        free_dev(c->d_tp);
-        free_dev(c->d_tp_mt);
-        free_dev(c->d_tpa);
+        for (DevBuf* b : {&c->spill, &c->scratch, &c->feat, &c->guide, &c->samp, &c->dn, &c->tp, &c->tp_mt, &c->tpa}) b->release();
         for (EventPair& ep : c->events) {
             (void)hipEventDestroy(ep.a);
             (void)hipEventDestroy(ep.b);
@@ -1780,14 +1837,16 @@ int prt_light_cluster_pmf(PrtContext* c, uint32_t n, const float* x, uint32_t* M
     if (!K) return fail(c, PRT_ERR_INVALID, "prt_light_cluster_pmf: the scene has no light");
     if (n == 0) return PRT_OK;
     if (!x || !M) return fail(c, PRT_ERR_INVALID, "null array");
-    const size_t bx = ((size_t)n * 12 + 15) & ~(size_t)15, bm = (size_t)n * K * 4;
-    if ((rc = ensure_scratch(c, bx + bm + 64))) return rc;
-    float* d_x = (float*)c->d_scratch;
-    uint32_t* d_m = (uint32_t*)((char*)c->d_scratch + bx);
-    HIPCHECK(c, hipMemcpyAsync(d_x, x, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    const size_t n3 = 3 * (size_t)n, nK = (size_t)n * K;
+    float* d_x;
+    uint32_t* d_m;
+    PrtWorkspace ws;
+    ws.add(&d_x, n3).add(&d_m, nK);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_x, x, n3))) return rc;
     prt_launch_light_cluster_pmf(c->stream, dev_light_clusters(c), n, d_x, d_m);
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(M, d_m, bm, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, M, d_m, nK))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -1856,17 +1915,16 @@ int prt_texture_eval(PrtContext* c, uint32_t n, const uint32_t* texture, const f
             if (!std::isfinite(uv[2 * (size_t)i + k]) || std::fabs(uv[2 * (size_t)i + k]) > 1048576.0f)
                 return fail(c, PRT_ERR_INVALID, "prt_texture_eval: uv %u is not finite or above 2^20", i);
     }
-    const size_t bt = ((size_t)n * 4 + 15) & ~(size_t)15, bu = ((size_t)n * 8 + 15) & ~(size_t)15, br = (size_t)n * 12;
-    if ((rc = ensure_scratch(c, bt + bu + br + 64))) return rc;
-    char* base = (char*)c->d_scratch;
-    uint32_t* d_t = (uint32_t*)base;
-    float* d_u = (float*)(base + bt);
-    float* d_r = (float*)(base + bt + bu);
-    HIPCHECK(c, hipMemcpyAsync(d_t, texture, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_u, uv, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    uint32_t* d_t;
+    float *d_u, *d_r;
+    PrtWorkspace ws;
+    ws.add(&d_t, n1).add(&d_u, 2 * n1).add(&d_r, 3 * n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_t, texture, n1)) || (rc = upload(c, d_u, uv, 2 * n1))) return rc;
     prt_launch_texture_eval(c->stream, dev_tex(c), n, d_t, d_u, d_r);
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(rgb, d_r, br, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, rgb, d_r, 3 * n1))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -1899,19 +1957,18 @@ int prt_environment_eval(PrtContext* c, uint32_t n, const float* dirs, float* rg
     if (!env_on(c)) return fail(c, PRT_ERR_INVALID, "prt_environment_eval: no environment is set");
     if (n == 0) return PRT_OK;
     if (!dirs) return fail(c, PRT_ERR_INVALID, "null array");
-    const size_t b3 = ((size_t)n * 12 + 15) & ~(size_t)15, b1 = ((size_t)n * 4 + 15) & ~(size_t)15;
-    if ((rc = ensure_scratch(c, 2 * b3 + 2 * b1))) return rc;
-    char* base = (char*)c->d_scratch;
-    float* d_d = (float*)base;
-    float* d_rgb = (float*)(base + b3);
-    uint32_t* d_t = (uint32_t*)(base + 2 * b3);
-    float* d_p = (float*)(base + 2 * b3 + b1);
-    HIPCHECK(c, hipMemcpyAsync(d_d, dirs, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    float *d_d, *d_rgb, *d_p;
+    uint32_t* d_t;
+    PrtWorkspace ws;
+    ws.add(&d_d, 3 * n1).add(&d_rgb, 3 * n1).add(&d_t, n1).add(&d_p, n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_d, dirs, 3 * n1))) return rc;
     prt_launch_environment_eval(c->stream, dev_env(c), n, d_d, d_rgb, d_t, d_p);
     HIPCHECK(c, hipGetLastError());
-    if (rgb) HIPCHECK(c, hipMemcpyAsync(rgb, d_rgb, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (texel) HIPCHECK(c, hipMemcpyAsync(texel, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (pdf_w) HIPCHECK(c, hipMemcpyAsync(pdf_w, d_p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (rgb && (rc = download(c, rgb, d_rgb, 3 * n1))) return rc;
+    if (texel && (rc = download(c, texel, d_t, n1))) return rc;
+    if (pdf_w && (rc = download(c, pdf_w, d_p, n1))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2057,9 +2114,9 @@ static int resolve_own(PrtContext* c, float** d_rgb, float** d_w, uint8_t** d_rg
     const size_t off_rgb = (gathered + 255) & ~(size_t)255;
     const size_t off_w = off_rgb + ((npix * 12 + 255) & ~(size_t)255);
     const size_t off_b = off_w + ((npix * 4 + 255) & ~(size_t)255);
-    int rc = ensure_scratch(c, off_b + npix * 4);
+    int rc = c->scratch.ensure(c, off_b + npix * 4);
     if (rc) return rc;
-    char* base = (char*)c->d_scratch;
+    char* base = (char*)c->scratch.p;
     HIPCHECK(c, hipMemsetAsync(base, 0, gathered, c->stream));
     HIPCHECK(c, hipMemcpyAsync(base + (size_t)tm.rank * tm.stride * sizeof(float4), c->d_film_local,
                                (size_t)tm.stride * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
@@ -2226,19 +2283,15 @@ int prt_camera_rays(PrtContext* c, uint32_t n, const float* px, const float* py,
     if (!c->has_camera) return fail(c, PRT_ERR_INVALID, "prt_set_camera has not been called");
     if (n == 0) return PRT_OK;
     if (!px || !py || !origins || !dirs) return fail(c, PRT_ERR_INVALID, "null array");
-    const size_t b1 = (size_t)n * 4, b3 = (size_t)n * 12;
-    if ((rc = ensure_scratch(c, 2 * b1 + 2 * b3))) return rc;
-    char* base = (char*)c->d_scratch;
-    float* d_px = (float*)base;
-    float* d_py = (float*)(base + b1);
-    float* d_o = (float*)(base + 2 * b1);
-    float* d_d = (float*)(base + 2 * b1 + b3);
-    HIPCHECK(c, hipMemcpyAsync(d_px, px, b1, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_py, py, b1, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    float *d_px, *d_py, *d_o, *d_d;
+    PrtWorkspace ws;
+    ws.add(&d_px, n1).add(&d_py, n1).add(&d_o, 3 * n1).add(&d_d, 3 * n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_px, px, n1)) || (rc = upload(c, d_py, py, n1))) return rc;
     prt_launch_camera_rays(c->stream, c->cam, n, d_px, d_py, d_o, d_d);
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(origins, d_o, b3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(dirs, d_d, b3, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, origins, d_o, 3 * n1)) || (rc = download(c, dirs, d_d, 3 * n1))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2251,22 +2304,16 @@ int prt_camera_rays_lens(PrtContext* c, uint32_t n, const float* px, const float
     if (!c->has_camera) return fail(c, PRT_ERR_INVALID, "prt_set_camera has not been called");
     if (n == 0) return PRT_OK;
     if (!px || !py || !keys || !origins || !dirs) return fail(c, PRT_ERR_INVALID, "null array");
-    const size_t b1 = (size_t)n * 4, b3 = (size_t)n * 12;
-    if ((rc = ensure_scratch(c, 3 * b1 + 2 * b3))) return rc;
-    char* base = (char*)c->d_scratch;
-    float* d_px = (float*)base;
-    float* d_py = (float*)(base + b1);
-    uint32_t* d_keys = (uint32_t*)(base + 2 * b1);
-    float* d_o = (float*)(base + 3 * b1);
-    float* d_d = (float*)(base + 3 * b1 + b3);
-    HIPCHECK(c, hipMemcpyAsync(d_px, px, b1, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_py, py, b1, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_keys, keys, b1, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    float *d_px, *d_py, *d_o, *d_d;
+    uint32_t* d_keys;
+    PrtWorkspace ws;
+    ws.add(&d_px, n1).add(&d_py, n1).add(&d_keys, n1).add(&d_o, 3 * n1).add(&d_d, 3 * n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_px, px, n1)) || (rc = upload(c, d_py, py, n1)) || (rc = upload(c, d_keys, keys, n1))) return rc;
     prt_launch_camera_rays_lens(c->stream, c->cam, DevLens{c->lens.aperture, c->lens.focus_distance}, n, d_px, d_py, d_keys, d_o, d_d);
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(keys, d_keys, b1, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(origins, d_o, b3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(dirs, d_d, b3, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, keys, d_keys, n1)) || (rc = download(c, origins, d_o, 3 * n1)) || (rc = download(c, dirs, d_d, 3 * n1))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2302,17 +2349,15 @@ int prt_closest_hit(PrtContext* c, uint32_t n, const float* origins, const float
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     if (n == 0) return PRT_OK;
     if (!origins || !dirs || !hits) return fail(c, PRT_ERR_INVALID, "null array");
-    const size_t b3 = (size_t)n * 12;
-    const size_t bh = (size_t)n * sizeof(PrtHit);
-    if ((rc = ensure_scratch(c, 2 * b3 + bh + 64))) return rc;
-    char* base = (char*)c->d_scratch;
-    float* d_o = (float*)base;
-    float* d_d = (float*)(base + b3);
-    PrtHit* d_h = (PrtHit*)(base + ((2 * b3 + 15) & ~(size_t)15));
-    HIPCHECK(c, hipMemcpyAsync(d_o, origins, b3, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_d, dirs, b3, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    float *d_o, *d_d;
+    PrtHit* d_h;
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * n1).add(&d_d, 3 * n1).add(&d_h, n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_o, origins, 3 * n1)) || (rc = upload(c, d_d, dirs, 3 * n1))) return rc;
     if ((rc = enqueue_query(c, n, d_o, d_d, nullptr, d_h, nullptr))) return rc;
-    HIPCHECK(c, hipMemcpyAsync(hits, d_h, bh, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, hits, d_h, n1))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2324,24 +2369,19 @@ int prt_hit_uv(PrtContext* c, uint32_t n, const float* origins, const float* dir
     if (!c->tex.is_set) return fail(c, PRT_ERR_INVALID, "prt_hit_uv: no textures are bound");
     if (n == 0) return PRT_OK;
     if (!origins || !dirs) return fail(c, PRT_ERR_INVALID, "null array");
-    const size_t b3 = ((size_t)n * 12 + 15) & ~(size_t)15;
-    const size_t bh = ((size_t)n * sizeof(PrtHit) + 15) & ~(size_t)15;
-    const size_t b2 = ((size_t)n * 8 + 15) & ~(size_t)15;
-    if ((rc = ensure_scratch(c, 3 * b3 + bh + b2 + 64))) return rc;
-    char* base = (char*)c->d_scratch;
-    float* d_o = (float*)base;
-    float* d_d = (float*)(base + b3);
-    PrtHit* d_h = (PrtHit*)(base + 2 * b3);
-    float* d_uv = (float*)(base + 2 * b3 + bh);
-    float* d_a = (float*)(base + 2 * b3 + bh + b2);
-    HIPCHECK(c, hipMemcpyAsync(d_o, origins, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_d, dirs, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    float *d_o, *d_d, *d_uv, *d_a;
+    PrtHit* d_h;
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * n1).add(&d_d, 3 * n1).add(&d_h, n1).add(&d_uv, 2 * n1).add(&d_a, 3 * n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_o, origins, 3 * n1)) || (rc = upload(c, d_d, dirs, 3 * n1))) return rc;
     if ((rc = enqueue_query(c, n, d_o, d_d, nullptr, d_h, nullptr))) return rc;
     prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), n, c->rb[0], d_uv, d_a);  // (the query left rays and final hit ids in rb[0])
     HIPCHECK(c, hipGetLastError());
-    if (hits) HIPCHECK(c, hipMemcpyAsync(hits, d_h, (size_t)n * sizeof(PrtHit), hipMemcpyDeviceToHost, c->stream));
-    if (uv) HIPCHECK(c, hipMemcpyAsync(uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (albedo) HIPCHECK(c, hipMemcpyAsync(albedo, d_a, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (hits && (rc = download(c, hits, d_h, n1))) return rc;
+    if (uv && (rc = download(c, uv, d_uv, 2 * n1))) return rc;
+    if (albedo && (rc = download(c, albedo, d_a, 3 * n1))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2361,19 +2401,15 @@ int prt_occluded(PrtContext* c, uint32_t n, const float* origins, const float* d
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     if (n == 0) return PRT_OK;
     if (!origins || !dirs || !tmax || !occluded) return fail(c, PRT_ERR_INVALID, "null array");
-    const size_t b3 = (size_t)n * 12, b1 = (size_t)n * 4;
-    const size_t off_t = (2 * b3 + 15) & ~(size_t)15, off_b = (off_t + b1 + 15) & ~(size_t)15;
-    if ((rc = ensure_scratch(c, off_b + n + 64))) return rc;
-    char* base = (char*)c->d_scratch;
-    float* d_o = (float*)base;
-    float* d_d = (float*)(base + b3);
-    float* d_t = (float*)(base + off_t);
-    uint8_t* d_b = (uint8_t*)(base + off_b);
-    HIPCHECK(c, hipMemcpyAsync(d_o, origins, b3, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_d, dirs, b3, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_t, tmax, b1, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    float *d_o, *d_d, *d_t;
+    uint8_t* d_b;
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * n1).add(&d_d, 3 * n1).add(&d_t, n1).add(&d_b, n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_o, origins, 3 * n1)) || (rc = upload(c, d_d, dirs, 3 * n1)) || (rc = upload(c, d_t, tmax, n1))) return rc;
     if ((rc = enqueue_query(c, n, d_o, d_d, d_t, nullptr, d_b))) return rc;
-    HIPCHECK(c, hipMemcpyAsync(occluded, d_b, n, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, occluded, d_b, n1))) return rc;
     // waits for the stream and reports a ray the walk had to give up (two-level stack overflow): never a silent "not occluded"
     return prt_synchronize(c);
 }
@@ -2396,33 +2432,16 @@ void prt_denoise_defaults(PrtDenoise* out) {
 
 float prt_denoise_variance(float n, float A, float Q) { return prt_denoise_variance_rule(n, A, Q); }
 
-static int ensure_dn(PrtContext* c, size_t bytes) {
-    if (bytes <= c->dn_bytes) return PRT_OK;
-    free_dev(c->d_dn);
-    c->dn_bytes = 0;
-    HIPCHECK(c, hipMalloc(&c->d_dn, bytes));
-    c->dn_bytes = bytes;
-    return PRT_OK;
-}
-
-// Scratch bytes enqueue_chains needs at `ext` for n rays: a second ray list, two state lists of two float4 each, and one
-// live count per round.
-static size_t chain_scratch_bytes(uint32_t n) {
-    const size_t b3 = ((size_t)n * 12 + 15) & ~(size_t)15, bs = (size_t)n * sizeof(float4);
-    return 2 * b3 + 4 * bs + 64;
-}
-
 // The specular chains of n rays (d_o, d_d) whose closest hits are in d_h (and whose textured albedo is in d_a, or null): the
 // start kernel decides every ray at k = 0 from those records (nothing is traced twice) and leaves the live chains in list 1;
 // each round reads the 4-byte live count (one small wait, as prt_render_adaptive has per pass), queries the live rays only,
 // and steps them into the other list.  After round r every live chain has followed r + 2 vertices, so round
 // max_specular - 1 ends them all.  Ray i's records go to out[i].  d_o, d_d, d_h and d_a are overwritten.
-static int enqueue_chains(PrtContext* c, uint32_t n, float* d_o, float* d_d, PrtHit* d_h, float* d_a, char* ext, PrtFeatureBufs out) {
+static int enqueue_chains(PrtContext* c, uint32_t n, float* d_o, float* d_d, PrtHit* d_h, float* d_a, const ChainScratch& x,
+                          PrtFeatureBufs out) {
     int rc;
-    const size_t b3 = ((size_t)n * 12 + 15) & ~(size_t)15, bs = (size_t)n * sizeof(float4);
-    PrtChainList lists[2] = {{d_o, d_d, (float4*)(ext + 2 * b3), (float4*)(ext + 2 * b3 + bs)},
-                             {(float*)ext, (float*)(ext + b3), (float4*)(ext + 2 * b3 + 2 * bs), (float4*)(ext + 2 * b3 + 3 * bs)}};
-    uint32_t* d_cnt = (uint32_t*)(ext + 2 * b3 + 4 * bs);
+    PrtChainList lists[2] = {{d_o, d_d, x.s[0], x.s[1]}, {x.o, x.d, x.s[2], x.s[3]}};
+    uint32_t* d_cnt = x.cnt;
     HIPCHECK(c, hipMemsetAsync(d_cnt, 0, (PRT_FEATURE_MAX_SPECULAR + 1u) * sizeof(uint32_t), c->stream));
     PrtChainArgs a{d_h, d_a, c->dsc.mat_rgbs, c->dsc.mat_type, c->ftrace, out, d_cnt};
     prt_launch_ft_start(c->stream, n, d_d, a, lists[1]);
@@ -2453,18 +2472,11 @@ static int enqueue_feature_samples(PrtContext* c, uint32_t n) {
     int rc;
     const uint32_t K = c->fsamp.samples;
     const bool follow = c->ftrace.max_specular > 0u;
-    if (n > c->samp_cap) {
-        free_dev(c->samp.alb);
-        c->samp = PrtFeatureBufs{nullptr, nullptr, nullptr};
-        c->samp_cap = 0;
-        HIPCHECK(c, hipMalloc((void**)&c->samp.alb, 3 * (size_t)n * sizeof(float4)));
-        c->samp_cap = n;
-    }
-    c->samp.nrm = c->samp.alb + n;
-    c->samp.pos = c->samp.alb + 2 * (size_t)n;
+    if ((rc = c->samp.ensure(c, 3 * (size_t)n * sizeof(float4)))) return rc;
+    const PrtFeatureBufs samp = feature_view(c->samp.p, n);
     if (c->sampling.jitter == 0u && !(c->lens.aperture > 0.0f)) {
-        const PrtFeatureBufs src = follow ? c->guide : c->feat;
-        prt_launch_fs_finish(c->stream, n, K, &src, c->samp);
+        const PrtFeatureBufs src = feature_view(follow ? c->guide.p : c->feat.p, n);
+        prt_launch_fs_finish(c->stream, n, K, &src, samp);
         HIPCHECK(c, hipGetLastError());
         return PRT_OK;
     }
@@ -2474,35 +2486,34 @@ static int enqueue_feature_samples(PrtContext* c, uint32_t n) {
     const uint32_t m = cs * n;
     // the scratch below and the path state of m rays may be reallocated: nothing enqueued above may still be using them
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    const size_t b3 = ((size_t)m * 12 + 15) & ~(size_t)15, bh = ((size_t)m * sizeof(PrtHit) + 15) & ~(size_t)15;
-    const size_t br = 3 * (size_t)m * sizeof(float4);
-    const size_t first = 3 * b3 + bh + br;
-    if ((rc = ensure_scratch(c, first + (follow ? chain_scratch_bytes(m) : 0) + 64))) return rc;
-    char* base = (char*)c->d_scratch;
-    float* d_o = (float*)base;
-    float* d_d = (float*)(base + b3);
-    float* d_a = (float*)(base + 2 * b3);
-    PrtHit* d_h = (PrtHit*)(base + 3 * b3);
-    float4* d_r = (float4*)(base + 3 * b3 + bh);
+    const size_t m1 = m;
+    float *d_o, *d_d, *d_a;
+    PrtHit* d_h;
+    float4* d_r;
+    ChainScratch chain;
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * m1).add(&d_d, 3 * m1).add(&d_a, 3 * m1).add(&d_h, m1).add(&d_r, 3 * m1);
+    if (follow) chain.declare(ws, m1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
     const bool textured = tex_on(c);
     const DevLens dlens{c->lens.aperture, c->lens.focus_distance};
     for (uint32_t s0 = 0; s0 < K; s0 += cs) {
         const PrtSampleChunk ch{c->tm.W, c->tm.H, s0, std::min(cs, K - s0), c->fsamp.first_sample, c->fsamp.seed, c->sampling.jitter};
         const uint32_t mc = ch.cs * n;
-        const PrtFeatureBufs rec{d_r, d_r + mc, d_r + 2 * (size_t)mc};
+        const PrtFeatureBufs rec = feature_view(d_r, mc);
         prt_launch_fs_rays(c->stream, c->cam, dlens, ch, d_o, d_d);
         HIPCHECK(c, hipGetLastError());
         if ((rc = enqueue_query(c, mc, d_o, d_d, nullptr, d_h, nullptr))) return rc;
         if (textured) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), mc, c->rb[0], nullptr, d_a);
         if (follow) {
-            if ((rc = enqueue_chains(c, mc, d_o, d_d, d_h, textured ? d_a : nullptr, base + first, rec))) return rc;
+            if ((rc = enqueue_chains(c, mc, d_o, d_d, d_h, textured ? d_a : nullptr, chain, rec))) return rc;
         } else {
             prt_launch_dn_pack_features(c->stream, mc, d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, rec);
         }
-        prt_launch_fs_reduce(c->stream, ch, rec, c->samp);
+        prt_launch_fs_reduce(c->stream, ch, rec, samp);
         HIPCHECK(c, hipGetLastError());
     }
-    prt_launch_fs_finish(c->stream, n, K, nullptr, c->samp);
+    prt_launch_fs_finish(c->stream, n, K, nullptr, samp);
     HIPCHECK(c, hipGetLastError());
     return PRT_OK;
 }
@@ -2517,51 +2528,27 @@ int prt_render_features(PrtContext* c) {
     if (n64 > (uint64_t)PRT_DENOISE_MAX_PIXELS) return fail(c, PRT_ERR_INVALID, "prt_render_features: more than 2^28 pixels");
     const uint32_t n = (uint32_t)n64;
     const bool follow = c->ftrace.max_specular > 0u;
-    if (follow) {
-        if (n > c->guide_cap) {
-            free_dev(c->guide.alb);
-            c->guide = PrtFeatureBufs{nullptr, nullptr, nullptr};
-            c->guide_cap = 0;
-            HIPCHECK(c, hipMalloc((void**)&c->guide.alb, 3 * (size_t)n * sizeof(float4)));
-            c->guide_cap = n;
-        }
-        c->guide.nrm = c->guide.alb + n;
-        c->guide.pos = c->guide.alb + 2 * (size_t)n;
-    }
-    if (n > c->feat_cap) {
-        free_dev(c->feat.alb);
-        c->feat = PrtFeatureBufs{nullptr, nullptr, nullptr};
-        c->feat_cap = 0;
-        HIPCHECK(c, hipMalloc((void**)&c->feat.alb, 3 * (size_t)n * sizeof(float4)));
-        c->feat.nrm = c->feat.alb + n;
-        c->feat.pos = c->feat.alb + 2 * (size_t)n;
-        c->feat_cap = n;
-    } else {
-        c->feat.nrm = c->feat.alb + n;
-        c->feat.pos = c->feat.alb + 2 * (size_t)n;
-    }
+    const size_t n1 = n;
+    if (follow && (rc = c->guide.ensure(c, 3 * n1 * sizeof(float4)))) return rc;
+    if ((rc = c->feat.ensure(c, 3 * n1 * sizeof(float4)))) return rc;
     // one pinhole ray through every pixel centre (k_camera_rays: fov_y honoured, no lens, no draw), the ray-query pipeline
     // of prt_closest_hit_device, the textured albedo of prt_hit_uv while a binding textures something, then the records
-    const size_t b1 = ((size_t)n * 4 + 15) & ~(size_t)15, b3 = ((size_t)n * 12 + 15) & ~(size_t)15;
-    const size_t bh = ((size_t)n * sizeof(PrtHit) + 15) & ~(size_t)15;
-    const size_t first = 2 * b1 + 3 * b3 + bh;
-    if ((rc = ensure_scratch(c, first + (follow ? chain_scratch_bytes(n) : 0) + 64))) return rc;
-    char* base = (char*)c->d_scratch;
-    float* d_px = (float*)base;
-    float* d_py = (float*)(base + b1);
-    float* d_o = (float*)(base + 2 * b1);
-    float* d_d = (float*)(base + 2 * b1 + b3);
-    PrtHit* d_h = (PrtHit*)(base + 2 * b1 + 2 * b3);
-    float* d_a = (float*)(base + 2 * b1 + 2 * b3 + bh);
+    float *d_px, *d_py, *d_o, *d_d, *d_a;
+    PrtHit* d_h;
+    ChainScratch chain;
+    PrtWorkspace ws;
+    ws.add(&d_px, n1).add(&d_py, n1).add(&d_o, 3 * n1).add(&d_d, 3 * n1).add(&d_h, n1).add(&d_a, 3 * n1);
+    if (follow) chain.declare(ws, n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
     prt_launch_dn_pixel_grid(c->stream, tm.W, tm.H, d_px, d_py);
     prt_launch_camera_rays(c->stream, c->cam, n, d_px, d_py, d_o, d_d);
     HIPCHECK(c, hipGetLastError());
     if ((rc = enqueue_query(c, n, d_o, d_d, nullptr, d_h, nullptr))) return rc;
     const bool textured = tex_on(c);
     if (textured) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), n, c->rb[0], nullptr, d_a);  // (rays and final hit ids are in rb[0])
-    prt_launch_dn_pack_features(c->stream, n, d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, c->feat);
+    prt_launch_dn_pack_features(c->stream, n, d_h, textured ? d_a : nullptr, c->dsc.mat_rgbs, c->dsc.mat_type, feature_view(c->feat.p, n1));
     HIPCHECK(c, hipGetLastError());
-    if (follow && (rc = enqueue_chains(c, n, d_o, d_d, d_h, textured ? d_a : nullptr, base + first, c->guide))) return rc;
+    if (follow && (rc = enqueue_chains(c, n, d_o, d_d, d_h, textured ? d_a : nullptr, chain, feature_view(c->guide.p, n1)))) return rc;
     if (c->fsamp.samples > 0u && (rc = enqueue_feature_samples(c, n))) return rc;
     if ((rc = prt_synchronize(c))) return rc;
     c->feat_W = tm.W;
@@ -2615,10 +2602,12 @@ int prt_get_feature_sampling(PrtContext* c, PrtFeatureSampling* out) {
     return PRT_OK;
 }
 
+// A set as the last prt_render_features wrote it.
+static PrtFeatureBufs current_set(const PrtContext* c, const DevBuf& set) { return feature_view(set.p, (size_t)c->feat_W * c->feat_H); }
 // The centre-ray set the guide readers return: the guide set while that mode is on, else the first-hit set.
-static PrtFeatureBufs centre_features(const PrtContext* c) { return c->guide_valid ? c->guide : c->feat; }
+static PrtFeatureBufs centre_features(const PrtContext* c) { return current_set(c, c->guide_valid ? c->guide : c->feat); }
 // The set the spatial filter is guided by: the sampled set while that mode is on, else the centre-ray set.
-static PrtFeatureBufs filter_features(const PrtContext* c) { return c->samp_valid ? c->samp : centre_features(c); }
+static PrtFeatureBufs filter_features(const PrtContext* c) { return c->samp_valid ? current_set(c, c->samp) : centre_features(c); }
 
 // A feature set's records to planar host arrays (each may be null); bounces: the albedo record's .w.
 static int read_feature_records(PrtContext* c, PrtFeatureBufs f, float* albedo, float* normal, float* position, float* depth, int32_t* prim,
@@ -2652,12 +2641,12 @@ int prt_features_read_guide(PrtContext* c, float* albedo, float* normal, float* 
 int prt_features_read_sampled(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim, uint32_t* hits) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->feat_valid || !c->samp_valid) return fail(c, PRT_ERR_INVALID, "no current sampled feature set (prt_set_feature_sampling, prt_render_features)");
-    return read_feature_records(c, c->samp, albedo, normal, position, depth, prim, hits);
+    return read_feature_records(c, current_set(c, c->samp), albedo, normal, position, depth, prim, hits);
 }
 
 int prt_features_read(PrtContext* c, float* albedo, float* normal, float* position, float* depth, int32_t* prim) {
     if (!c) return PRT_ERR_INVALID;
-    return read_feature_records(c, c->feat, albedo, normal, position, depth, prim, nullptr);
+    return read_feature_records(c, current_set(c, c->feat), albedo, normal, position, depth, prim, nullptr);
 }
 
 // The iterations and the finish on the context's stream.  cv[0] holds c_0 / var_0; cv[0] and cv[1] ping-pong.
@@ -2677,16 +2666,15 @@ static int enqueue_filter(PrtContext* c, const PrtDenoise& cfg, uint32_t W, uint
     return PRT_OK;
 }
 
-// prt_denoise_device's work; ws: 5 n float4 of workspace (packed records, then the two colour + variance buffers)
+// prt_denoise_device's work; s: declare_arrays for W x H pixels
 static int enqueue_denoise_arrays(PrtContext* c, const PrtDenoise& cfg, uint32_t W, uint32_t H, const float* d_mean, const float* d_var,
                                   const float* d_albedo, const float* d_normal, const float* d_position, const int32_t* d_prim,
-                                  float* d_out, float* d_var_out, float4* ws) {
+                                  float* d_out, float* d_var_out, const FilterScratch& s) {
     const uint32_t n = W * H;
-    const PrtFeatureBufs f{ws, ws + n, ws + 2 * (size_t)n};
-    float4 *cv0 = ws + 3 * (size_t)n, *cv1 = ws + 4 * (size_t)n;
+    const PrtFeatureBufs f = feature_view(s.rec, n);
     prt_launch_dn_pack_arrays(c->stream, n, d_albedo, d_normal, d_position, d_prim, f);
-    prt_launch_dn_prepare(c->stream, n, d_mean, d_var, f, cfg.demodulate, cv0);
-    return enqueue_filter(c, cfg, W, H, f, cv0, cv1, d_out, d_var_out);
+    prt_launch_dn_prepare(c->stream, n, d_mean, d_var, f, cfg.demodulate, s.cv0);
+    return enqueue_filter(c, cfg, W, H, f, s.cv0, s.cv1, d_out, d_var_out);
 }
 
 int prt_denoise_device(PrtContext* c, const PrtDenoise* cfg, uint32_t W, uint32_t H, const void* d_mean, const void* d_var,
@@ -2699,9 +2687,12 @@ int prt_denoise_device(PrtContext* c, const PrtDenoise* cfg, uint32_t W, uint32_
     if (rc) return rc;
     const PrtDenoise k = cfg ? *cfg : prt_denoise_default_config();
     const size_t n = (size_t)W * H;
-    if ((rc = ensure_dn(c, 5 * n * sizeof(float4)))) return rc;
+    FilterScratch s;
+    PrtWorkspace ws;
+    s.declare_arrays(ws, n);
+    if ((rc = commit(c, ws, c->dn))) return rc;
     return enqueue_denoise_arrays(c, k, W, H, (const float*)d_mean, (const float*)d_var, (const float*)d_albedo, (const float*)d_normal,
-                                  (const float*)d_position, (const int32_t*)d_prim, (float*)d_out, (float*)d_var_out, (float4*)c->d_dn);
+                                  (const float*)d_position, (const int32_t*)d_prim, (float*)d_out, (float*)d_var_out, s);
 }
 
 int prt_denoise(PrtContext* c, const PrtDenoise* cfg, uint32_t W, uint32_t H, const float* mean, const float* var, const float* albedo,
@@ -2713,24 +2704,20 @@ int prt_denoise(PrtContext* c, const PrtDenoise* cfg, uint32_t W, uint32_t H, co
     if (rc) return rc;
     const PrtDenoise k = cfg ? *cfg : prt_denoise_default_config();
     const size_t n = (size_t)W * H;
-    // workspace: 5 n float4 for the filter, then the staged arrays: mean, albedo, normal, position, out (3 n floats each),
-    // var, prim, var_out (n each)
-    if ((rc = ensure_dn(c, 5 * n * sizeof(float4) + 18 * n * sizeof(float)))) return rc;
-    float* st = (float*)((float4*)c->d_dn + 5 * n);
-    float *d_mean = st, *d_alb = st + 3 * n, *d_nrm = st + 6 * n, *d_pos = st + 9 * n, *d_out = st + 12 * n;
-    float *d_var = st + 15 * n, *d_vout = st + 17 * n;
-    int32_t* d_prim = (int32_t*)(st + 16 * n);
-    HIPCHECK(c, hipMemcpyAsync(d_mean, mean, n * 12, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_var, var, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_alb, albedo, n * 12, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_nrm, normal, n * 12, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_pos, position, n * 12, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_prim, prim, n * 4, hipMemcpyHostToDevice, c->stream));
-    if ((rc = enqueue_denoise_arrays(c, k, W, H, d_mean, d_var, d_alb, d_nrm, d_pos, d_prim, d_out, var_out ? d_vout : nullptr,
-                                     (float4*)c->d_dn)))
-        return rc;
-    HIPCHECK(c, hipMemcpyAsync(out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (var_out) HIPCHECK(c, hipMemcpyAsync(var_out, d_vout, n * 4, hipMemcpyDeviceToHost, c->stream));
+    // workspace: the filter's, then the staged arrays
+    FilterScratch s;
+    float *d_mean, *d_alb, *d_nrm, *d_pos, *d_out, *d_var, *d_vout;
+    int32_t* d_prim;
+    PrtWorkspace ws;
+    s.declare_arrays(ws, n);
+    ws.add(&d_mean, 3 * n).add(&d_alb, 3 * n).add(&d_nrm, 3 * n).add(&d_pos, 3 * n).add(&d_out, 3 * n);
+    ws.add(&d_var, n).add(&d_prim, n).add(&d_vout, n);
+    if ((rc = commit(c, ws, c->dn))) return rc;
+    if ((rc = upload(c, d_mean, mean, 3 * n)) || (rc = upload(c, d_var, var, n)) || (rc = upload(c, d_alb, albedo, 3 * n))) return rc;
+    if ((rc = upload(c, d_nrm, normal, 3 * n)) || (rc = upload(c, d_pos, position, 3 * n)) || (rc = upload(c, d_prim, prim, n))) return rc;
+    if ((rc = enqueue_denoise_arrays(c, k, W, H, d_mean, d_var, d_alb, d_nrm, d_pos, d_prim, d_out, var_out ? d_vout : nullptr, s))) return rc;
+    if ((rc = download(c, out, d_out, 3 * n))) return rc;
+    if (var_out && (rc = download(c, var_out, d_vout, n))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2752,15 +2739,13 @@ int prt_film_denoise(PrtContext* c, const PrtDenoise* cfg, float* rgb_out, float
     if (!c->feat_valid && (rc = prt_render_features(c))) return rc;
     const PrtDenoise k = cfg ? *cfg : prt_denoise_default_config();
     const size_t n = (size_t)tm.W * tm.H;
-    if ((rc = ensure_dn(c, 2 * n * sizeof(float4) + 4 * n * sizeof(float)))) return rc;
-    float4 *cv0 = (float4*)c->d_dn, *cv1 = cv0 + n;
-    float* d_out = (float*)(cv1 + n);
-    float* d_vout = d_out + 3 * n;
+    FilterScratch s;
+    if ((rc = s.commit_film(c, n))) return rc;
     const PrtFeatureBufs gf = filter_features(c);
-    prt_launch_dn_film_prepare(c->stream, tm, c->d_film_local, c->d_film_stat, gf, k.demodulate, cv0);
-    if ((rc = enqueue_filter(c, k, tm.W, tm.H, gf, cv0, cv1, d_out, var_out ? d_vout : nullptr))) return rc;
-    HIPCHECK(c, hipMemcpyAsync(rgb_out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (var_out) HIPCHECK(c, hipMemcpyAsync(var_out, d_vout, n * 4, hipMemcpyDeviceToHost, c->stream));
+    prt_launch_dn_film_prepare(c->stream, tm, c->d_film_local, c->d_film_stat, gf, k.demodulate, s.cv0);
+    if ((rc = enqueue_filter(c, k, tm.W, tm.H, gf, s.cv0, s.cv1, s.out, var_out ? s.var : nullptr))) return rc;
+    if ((rc = download(c, rgb_out, s.out, 3 * n))) return rc;
+    if (var_out && (rc = download(c, var_out, s.var, n))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2788,37 +2773,19 @@ int prt_temporal_reset(PrtContext* c) {
 int prt_temporal_info(PrtContext* c, PrtTemporalInfo* out) {
     if (!c || !out) return PRT_ERR_INVALID;
     *out = c->tp_info;
-    out->device_bytes = (uint64_t)c->tp_bytes + c->tp_mt_bytes + c->tpa_bytes;
+    out->device_bytes = (uint64_t)c->tp.bytes + c->tp_mt.bytes + c->tpa.bytes;
     return PRT_OK;
 }
 
-static int ensure_buf(PrtContext* c, void*& p, size_t& have, size_t bytes) {
-    if (bytes <= have) return PRT_OK;
-    free_dev(p);
-    have = 0;
-    HIPCHECK(c, hipMalloc(&p, bytes));
-    have = bytes;
-    return PRT_OK;
-}
-
-// Pixels of a record layout: n padded to a multiple of 4, so that every record array starts 16-byte aligned
-static size_t tp_padded(size_t n) { return (n + 3) & ~(size_t)3; }
-
-// A history set in 56 n bytes at base (n = tp_padded(pixels)): cn, nrm, pos (16 n each), mm (8 n)
-static PrtHistoryBufs history_at(char* base, size_t n) {
-    return PrtHistoryBufs{(float4*)base, (float2*)(base + 48 * n), (float4*)(base + 16 * n), (float4*)(base + 32 * n)};
-}
-
-// prt_temporal_reproject_device's work; ws: 136 tp_padded(n) bytes (the current frame's records, the history's, the new cn / mm)
+// prt_temporal_reproject_device's work; s: declared for W x H pixels
 static int enqueue_temporal_arrays(PrtContext* c, const PrtTemporal& cfg, uint32_t W, uint32_t H, const PrtCameraBasis& K, const float* d_c,
                                    const float* d_n, const float* d_A, const float* d_Q, const int32_t* d_prim, const float* d_P,
                                    const float* d_N, const float* d_hc, const float* d_hn, const float* d_h1, const float* d_h2,
                                    const float* d_hP, const float* d_hN, const int32_t* d_hprim, float* d_c_out, float* d_n_out,
-                                   float* d_m1_out, float* d_m2_out, float* d_var_out, uint8_t* d_status, char* ws) {
-    const size_t n = (size_t)W * H, np = tp_padded(n);
-    const PrtHistoryBufs cur = history_at(ws, np);
-    PrtHistoryBufs prev = history_at(ws + 56 * np, np);
-    const PrtHistoryBufs next{(float4*)(ws + 112 * np), (float2*)(ws + 128 * np), nullptr, nullptr};
+                                   float* d_m1_out, float* d_m2_out, float* d_var_out, uint8_t* d_status, const TemporalScratch& s) {
+    const size_t n = (size_t)W * H;
+    const PrtHistoryBufs cur = s.cur, next = s.next;
+    PrtHistoryBufs prev = s.prev;
     prt_launch_tp_pack_frame(c->stream, (uint32_t)n, d_c, d_n, d_A, d_Q, d_prim, d_P, d_N, cur.cn, cur.mm, cur.nrm, cur.pos);
     if (d_hc) prt_launch_tp_pack_frame(c->stream, (uint32_t)n, d_hc, d_hn, d_h1, d_h2, d_hprim, d_hP, d_hN, prev.cn, prev.mm, prev.nrm, prev.pos);
     else prev = PrtHistoryBufs{nullptr, nullptr, nullptr, nullptr};
@@ -2843,12 +2810,15 @@ int prt_temporal_reproject_device(PrtContext* c, const PrtTemporal* cfg, uint32_
     if (rc) return rc;
     const PrtTemporal k = cfg ? *cfg : prt_temporal_default_config();
     const size_t n = (size_t)W * H;
-    if ((rc = ensure_buf(c, c->d_tpa, c->tpa_bytes, 136 * tp_padded(n)))) return rc;
+    TemporalScratch s;
+    PrtWorkspace ws;
+    s.declare(ws, n);
+    if ((rc = commit(c, ws, c->tpa))) return rc;
     return enqueue_temporal_arrays(c, k, W, H, *K, (const float*)d_c, (const float*)d_n, (const float*)d_A, (const float*)d_Q,
                                    (const int32_t*)d_prim, (const float*)d_Pprev, (const float*)d_Nprev, (const float*)d_hc, (const float*)d_hn,
                                    (const float*)d_h1, (const float*)d_h2, (const float*)d_hP, (const float*)d_hN, (const int32_t*)d_hprim,
                                    (float*)d_c_out, (float*)d_n_out, (float*)d_m1_out, (float*)d_m2_out, (float*)d_var_out, (uint8_t*)d_status,
-                                   (char*)c->d_tpa);
+                                   s);
 }
 
 int prt_temporal_reproject(PrtContext* c, const PrtTemporal* cfg, uint32_t W, uint32_t H, const PrtCameraBasis* K, const float* cc,
@@ -2864,45 +2834,30 @@ int prt_temporal_reproject(PrtContext* c, const PrtTemporal* cfg, uint32_t W, ui
     if (rc) return rc;
     const PrtTemporal k = cfg ? *cfg : prt_temporal_default_config();
     const size_t n = (size_t)W * H;
-    // workspace: 136 tp_padded(n) bytes of records, then the staged arrays: the frame (13 n floats), the history (13 n), the outputs
-    // (7 n), the status (n bytes)
-    if ((rc = ensure_buf(c, c->d_tpa, c->tpa_bytes, 136 * tp_padded(n) + 33 * n * sizeof(float) + n))) return rc;
-    float* st = (float*)((char*)c->d_tpa + 136 * tp_padded(n));
-    float *d_c = st, *d_P = st + 3 * n, *d_N = st + 6 * n, *d_n = st + 9 * n, *d_A = st + 10 * n, *d_Q = st + 11 * n;
-    int32_t* d_prim = (int32_t*)(st + 12 * n);
-    float* hs = st + 13 * n;
-    float *d_hc = hs, *d_hP = hs + 3 * n, *d_hN = hs + 6 * n, *d_hn = hs + 9 * n, *d_h1 = hs + 10 * n, *d_h2 = hs + 11 * n;
-    int32_t* d_hprim = (int32_t*)(hs + 12 * n);
-    float* os = st + 26 * n;
-    float *d_co = os, *d_no = os + 3 * n, *d_m1o = os + 4 * n, *d_m2o = os + 5 * n, *d_vo = os + 6 * n;
-    uint8_t* d_st = (uint8_t*)(os + 7 * n);
-    auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream); };
-    HIPCHECK(c, up(d_c, cc, n * 12));
-    HIPCHECK(c, up(d_P, Pprev, n * 12));
-    HIPCHECK(c, up(d_N, Nprev, n * 12));
-    HIPCHECK(c, up(d_n, nn, n * 4));
-    HIPCHECK(c, up(d_A, A, n * 4));
-    HIPCHECK(c, up(d_Q, Q, n * 4));
-    HIPCHECK(c, up(d_prim, prim, n * 4));
+    // workspace: the records, then the staged arrays: the frame, the history, the outputs
+    TemporalScratch s;
+    float *d_c, *d_P, *d_N, *d_n, *d_A, *d_Q, *d_hc, *d_hP, *d_hN, *d_hn, *d_h1, *d_h2, *d_co, *d_no, *d_m1o, *d_m2o, *d_vo;
+    int32_t *d_prim, *d_hprim;
+    uint8_t* d_st;
+    PrtWorkspace ws;
+    s.declare(ws, n);
+    ws.add(&d_c, 3 * n).add(&d_P, 3 * n).add(&d_N, 3 * n).add(&d_n, n).add(&d_A, n).add(&d_Q, n).add(&d_prim, n);
+    ws.add(&d_hc, 3 * n).add(&d_hP, 3 * n).add(&d_hN, 3 * n).add(&d_hn, n).add(&d_h1, n).add(&d_h2, n).add(&d_hprim, n);
+    ws.add(&d_co, 3 * n).add(&d_no, n).add(&d_m1o, n).add(&d_m2o, n).add(&d_vo, n).add(&d_st, n);
+    if ((rc = commit(c, ws, c->tpa))) return rc;
+    if ((rc = upload(c, d_c, cc, 3 * n)) || (rc = upload(c, d_P, Pprev, 3 * n)) || (rc = upload(c, d_N, Nprev, 3 * n))) return rc;
+    if ((rc = upload(c, d_n, nn, n)) || (rc = upload(c, d_A, A, n)) || (rc = upload(c, d_Q, Q, n)) || (rc = upload(c, d_prim, prim, n))) return rc;
     if (hc) {
-        HIPCHECK(c, up(d_hc, hc, n * 12));
-        HIPCHECK(c, up(d_hP, hP, n * 12));
-        HIPCHECK(c, up(d_hN, hN, n * 12));
-        HIPCHECK(c, up(d_hn, hn, n * 4));
-        HIPCHECK(c, up(d_h1, h1, n * 4));
-        HIPCHECK(c, up(d_h2, h2, n * 4));
-        HIPCHECK(c, up(d_hprim, hprim, n * 4));
+        if ((rc = upload(c, d_hc, hc, 3 * n)) || (rc = upload(c, d_hP, hP, 3 * n)) || (rc = upload(c, d_hN, hN, 3 * n))) return rc;
+        if ((rc = upload(c, d_hn, hn, n)) || (rc = upload(c, d_h1, h1, n)) || (rc = upload(c, d_h2, h2, n)) || (rc = upload(c, d_hprim, hprim, n))) return rc;
     }
     if ((rc = enqueue_temporal_arrays(c, k, W, H, *K, d_c, d_n, d_A, d_Q, d_prim, d_P, d_N, hc ? d_hc : nullptr, d_hn, d_h1, d_h2, d_hP, d_hN,
-                                      d_hprim, d_co, d_no, d_m1o, d_m2o, var_out ? d_vo : nullptr, status ? d_st : nullptr, (char*)c->d_tpa)))
+                                      d_hprim, d_co, d_no, d_m1o, d_m2o, var_out ? d_vo : nullptr, status ? d_st : nullptr, s)))
         return rc;
-    auto down = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream); };
-    HIPCHECK(c, down(c_out, d_co, n * 12));
-    HIPCHECK(c, down(n_out, d_no, n * 4));
-    HIPCHECK(c, down(m1_out, d_m1o, n * 4));
-    HIPCHECK(c, down(m2_out, d_m2o, n * 4));
-    if (var_out) HIPCHECK(c, down(var_out, d_vo, n * 4));
-    if (status) HIPCHECK(c, down(status, d_st, n));
+    if ((rc = download(c, c_out, d_co, 3 * n)) || (rc = download(c, n_out, d_no, n))) return rc;
+    if ((rc = download(c, m1_out, d_m1o, n)) || (rc = download(c, m2_out, d_m2o, n))) return rc;
+    if (var_out && (rc = download(c, var_out, d_vo, n))) return rc;
+    if (status && (rc = download(c, status, d_st, n))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2953,26 +2908,25 @@ int prt_film_temporal(PrtContext* c, const PrtTemporal* cfg, const PrtDenoise* d
     if ((bad = prt_temporal_check(cfg, tm.W, tm.H, nullptr, true))) return fail(c, PRT_ERR_INVALID, "%s", bad);
     if (!c->feat_valid && (rc = prt_render_features(c))) return rc;
     const PrtTemporal k = cfg ? *cfg : prt_temporal_default_config();
-    const size_t n = (size_t)tm.W * tm.H, np = tp_padded(n);
-    // two history sets (56 np each), the blended planar frame: mean (12 np), var (4 np), N' / m1' / m2' (12 np), the counters
-    // (16 bytes), the status (n)
-    const size_t need = 140 * np + 16 + n;
-    if (need > c->tp_bytes) {
-        c->tp_valid = false;  // (a grown buffer holds no history; prt_set_film dropped it anyway)
-        if ((rc = ensure_buf(c, c->d_tp, c->tp_bytes, need))) return rc;
-    }
+    const size_t n = (size_t)tm.W * tm.H;
+    // two history sets, the blended planar frame (mean, var, N' / m1' / m2'), the counters, the status: a layout of W x H
+    // alone, so that a step finds the sets where the step before it at this size left them
+    PrtHistoryBufs set[2];
+    float *d_mean, *d_var, *d_hist, *d_m1, *d_m2;
+    uint32_t* d_counts;
+    uint8_t* d_status;
+    PrtWorkspace ws;
+    declare_history(ws, &set[0], n);
+    declare_history(ws, &set[1], n);
+    ws.add(&d_mean, 3 * n).add(&d_var, n).add(&d_hist, n).add(&d_m1, n).add(&d_m2, n).add(&d_counts, 4).add(&d_status, n);
+    if (ws.bytes() > c->tp.bytes) c->tp_valid = false;  // (a grown buffer holds no history; prt_set_film dropped it anyway)
+    if ((rc = commit(c, ws, c->tp))) return rc;
     if (c->tp_valid && (c->tp_W != tm.W || c->tp_H != tm.H)) c->tp_valid = false;
     // (a camera whose width / height is not the film's: its basis projects into another image, so the history does not apply)
     if (c->tp_valid && !(c->tp_K.W == (float)tm.W && c->tp_K.H == (float)tm.H)) c->tp_valid = false;
-    char* base = (char*)c->d_tp;
-    const PrtHistoryBufs prev = c->tp_valid ? history_at(base + 56 * np * (size_t)c->tp_set, np) : PrtHistoryBufs{nullptr, nullptr, nullptr, nullptr};
+    const PrtHistoryBufs prev = c->tp_valid ? set[c->tp_set] : PrtHistoryBufs{nullptr, nullptr, nullptr, nullptr};
     const int next_set = c->tp_valid ? (c->tp_set ^ 1) : 0;
-    const PrtHistoryBufs next = history_at(base + 56 * np * (size_t)next_set, np);
-    float* d_mean = (float*)(base + 112 * np);
-    float* d_var = d_mean + 3 * np;
-    float* d_hist = d_var + np;  // N', m1', m2' (n each)
-    uint32_t* d_counts = (uint32_t*)(base + 140 * np);
-    uint8_t* d_status = (uint8_t*)(base + 140 * np + 16);
+    const PrtHistoryBufs next = set[next_set];
     // the placed copies now against their matrices at the previous step
     const PrtHostScene& hs = c->hs;
     const uint32_t n_copies = (uint32_t)hs.dev_insts.size() - hs.n_world_insts;
@@ -2988,31 +2942,32 @@ int prt_film_temporal(PrtContext* c, const PrtTemporal* cfg, const PrtDenoise* d
             memcpy(&h[r_words + 24 * (size_t)i], I.inv, 48);
             memcpy(&h[r_words + 24 * (size_t)i + 12], &c->tp_mats[12 * (size_t)i], 48);
         }
-        if ((rc = ensure_buf(c, c->d_tp_mt, c->tp_mt_bytes, h.size() * 4))) return rc;
-        HIPCHECK(c, hipMemcpyAsync(c->d_tp_mt, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->stream));
-        mt = PrtMotionTable{(const uint32_t*)c->d_tp_mt, (const float4*)((const uint32_t*)c->d_tp_mt + r_words), n_copies};
+        if ((rc = c->tp_mt.ensure(c, h.size() * sizeof(uint32_t)))) return rc;
+        uint32_t* d_mt = (uint32_t*)c->tp_mt.p;
+        if ((rc = upload(c, d_mt, h.data(), h.size()))) return rc;
+        mt = PrtMotionTable{d_mt, (const float4*)(d_mt + r_words), n_copies};
     }
     HIPCHECK(c, hipMemsetAsync(d_counts, 0, 16, c->stream));
-    prt_launch_tp_reproject_film(c->stream, tm, k, c->tp_K, c->d_film_local, c->d_film_stat, c->feat.nrm, c->feat.pos, mt, prev, next, d_mean, d_var,
+    const PrtFeatureBufs first = current_set(c, c->feat);
+    prt_launch_tp_reproject_film(c->stream, tm, k, c->tp_K, c->d_film_local, c->d_film_stat, first.nrm, first.pos, mt, prev, next, d_mean, d_var,
                                  d_status, d_counts);
     HIPCHECK(c, hipGetLastError());
-    if (history_out) prt_launch_tp_unpack(c->stream, (uint32_t)n, next, d_hist, d_hist + n, d_hist + 2 * n);
+    if (history_out) prt_launch_tp_unpack(c->stream, (uint32_t)n, next, d_hist, d_m1, d_m2);
     const float *d_rgb = d_mean, *d_v = d_var;
     if (dn) {
-        if ((rc = ensure_dn(c, 2 * n * sizeof(float4) + 4 * n * sizeof(float)))) return rc;
-        float4 *cv0 = (float4*)c->d_dn, *cv1 = cv0 + n;
-        float* d_out = (float*)(cv1 + n);
+        FilterScratch s;
+        if ((rc = s.commit_film(c, n))) return rc;
         const PrtFeatureBufs gf = filter_features(c);
-        prt_launch_dn_prepare(c->stream, (uint32_t)n, d_mean, d_var, gf, dn->demodulate, cv0);
-        if ((rc = enqueue_filter(c, *dn, tm.W, tm.H, gf, cv0, cv1, d_out, d_out + 3 * n))) return rc;
-        d_rgb = d_out;
-        d_v = d_out + 3 * n;
+        prt_launch_dn_prepare(c->stream, (uint32_t)n, d_mean, d_var, gf, dn->demodulate, s.cv0);
+        if ((rc = enqueue_filter(c, *dn, tm.W, tm.H, gf, s.cv0, s.cv1, s.out, s.var))) return rc;
+        d_rgb = s.out;
+        d_v = s.var;
     }
     uint32_t counts[4] = {0u, 0u, 0u, 0u};
-    HIPCHECK(c, hipMemcpyAsync(rgb_out, d_rgb, n * 12, hipMemcpyDeviceToHost, c->stream));
-    if (var_out) HIPCHECK(c, hipMemcpyAsync(var_out, d_v, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (history_out) HIPCHECK(c, hipMemcpyAsync(history_out, d_hist, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, rgb_out, d_rgb, 3 * n))) return rc;
+    if (var_out && (rc = download(c, var_out, d_v, n))) return rc;
+    if (history_out && (rc = download(c, history_out, d_hist, n))) return rc;
+    if ((rc = download(c, counts, d_counts, 4))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     // the new history: the set just written, the basis and the copies' matrices of this frame
     c->tp_set = next_set;
@@ -3038,34 +2993,19 @@ int prt_scatter(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* h
         return fail(c, PRT_ERR_INVALID, "null array");
     for (uint32_t i = 0; i < n; ++i)
         if (hits[i].material_id >= c->hs.materials.size()) return fail(c, PRT_ERR_INVALID, "hit %u: material out of range", i);
-    const size_t b3 = (size_t)n * 12, b1 = (size_t)n * 4, bh = (size_t)n * sizeof(PrtHit);
-    if ((rc = ensure_scratch(c, 5 * b3 + 2 * b1 + bh + 64))) return rc;
-    char* base = (char*)c->d_scratch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += (bytes + 15) & ~(size_t)15;
-        return p;
-    };
-    PrtHit* d_h = (PrtHit*)take(bh);
-    float* d_in = (float*)take(b3);
-    uint32_t* d_rng = (uint32_t*)take(b1);
-    uint32_t* d_sc = (uint32_t*)take(b1);
-    float* d_at = (float*)take(b3);
-    float* d_em = (float*)take(b3);
-    float* d_oo = (float*)take(b3);
-    float* d_od = (float*)take(b3);
-    HIPCHECK(c, hipMemcpyAsync(d_h, hits, bh, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_in, in_dirs, b3, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_rng, rng_state, b1, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    PrtHit* d_h;
+    float *d_in, *d_at, *d_em, *d_oo, *d_od;
+    uint32_t *d_rng, *d_sc;
+    PrtWorkspace ws;
+    ws.add(&d_h, n1).add(&d_in, 3 * n1).add(&d_rng, n1).add(&d_sc, n1).add(&d_at, 3 * n1).add(&d_em, 3 * n1).add(&d_oo, 3 * n1).add(&d_od, 3 * n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_h, hits, n1)) || (rc = upload(c, d_in, in_dirs, 3 * n1)) || (rc = upload(c, d_rng, rng_state, n1))) return rc;
     prt_launch_scatter_test(c->stream, c->dsc, n, d_in, d_h, d_rng, d_sc, d_at, d_em, d_oo, d_od);
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(rng_state, d_rng, b1, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(scattered, d_sc, b1, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(attenuation, d_at, b3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(emitted, d_em, b3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(out_origins, d_oo, b3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(out_dirs, d_od, b3, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, rng_state, d_rng, n1)) || (rc = download(c, scattered, d_sc, n1))) return rc;
+    if ((rc = download(c, attenuation, d_at, 3 * n1)) || (rc = download(c, emitted, d_em, 3 * n1))) return rc;
+    if ((rc = download(c, out_origins, d_oo, 3 * n1)) || (rc = download(c, out_dirs, d_od, 3 * n1))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -3082,23 +3022,14 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
     for (uint32_t i = 0; i < n; ++i)
         if (hits[i].prim >= 0 && hits[i].material_id >= c->hs.materials.size())
             return fail(c, PRT_ERR_INVALID, "hit %u: material out of range", i);
-    const size_t b3 = (size_t)n * 12, b1 = (size_t)n * 4, bh = (size_t)n * sizeof(PrtHit), bf = (size_t)n * 44;
-    if ((rc = ensure_scratch(c, bh + b3 + 2 * b1 + bf + 64))) return rc;
-    char* base = (char*)c->d_scratch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += (bytes + 15) & ~(size_t)15;
-        return p;
-    };
-    PrtHit* d_h = (PrtHit*)take(bh);
-    float* d_in = (float*)take(b3);
-    uint32_t* d_k = (uint32_t*)take(b1);
-    uint32_t* d_l = (uint32_t*)take(b1);
-    float* d_f = (float*)take(bf);
-    HIPCHECK(c, hipMemcpyAsync(d_h, hits, bh, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_in, in_dirs, b3, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_k, keys, b1, hipMemcpyHostToDevice, c->stream));
+    const size_t n1 = n;
+    PrtHit* d_h;
+    float *d_in, *d_f;  // d_f: 11 floats per ray
+    uint32_t *d_k, *d_l;
+    PrtWorkspace ws;
+    ws.add(&d_h, n1).add(&d_in, 3 * n1).add(&d_k, n1).add(&d_l, n1).add(&d_f, 11 * n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_h, hits, n1)) || (rc = upload(c, d_in, in_dirs, 3 * n1)) || (rc = upload(c, d_k, keys, n1))) return rc;
     const DevMeshLights mlt = dev_mesh_lights(c);
     const DevLightClusters lct = dev_light_clusters(c);
     if ((rc = sync_light_tables(c))) return rc;
@@ -3106,9 +3037,8 @@ int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtH
     prt_launch_sample_light_test(c->stream, c->dsc, dev_lights(c), n, d_in, d_h, d_k, d_f, d_l, mesh_lights_on(c) ? &mlt : nullptr,
                                  env_on(c) ? &denv : nullptr, clusters_on(c) ? &lct : nullptr);
     HIPCHECK(c, hipGetLastError());
-    std::vector<float> f((size_t)n * 11);
-    HIPCHECK(c, hipMemcpyAsync(f.data(), d_f, bf, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(light, d_l, b1, hipMemcpyDeviceToHost, c->stream));
+    std::vector<float> f(11 * n1);
+    if ((rc = download(c, f.data(), d_f, 11 * n1)) || (rc = download(c, light, d_l, n1))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < n; ++i) {
         const float* r = &f[11 * i];
@@ -3152,30 +3082,20 @@ int prt_tile_select(PrtContext* c, const float* n, const float* sum_y, const flo
         stat[2 * pl] = sum_y[p];
         stat[2 * pl + 1] = sum_y2[p];
     });
-    const size_t b_film = n_pix * sizeof(float4), b_stat = n_pix * sizeof(float2), b_ent = n_ent * sizeof(uint32_t);
-    if ((rc = ensure_scratch(c, b_film + b_stat + 3 * b_ent + 64 + 4 * 16))) return rc;
-    char* base = (char*)c->d_scratch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += (bytes + 15) & ~(size_t)15;
-        return p;
-    };
-    float4* d_film = (float4*)take(b_film);
-    float2* d_stat = (float2*)take(b_stat);
-    uint32_t* d_count = (uint32_t*)take(64);
-    uint32_t* d_prev = (uint32_t*)take(b_ent);
-    uint32_t* d_flags = (uint32_t*)take(b_ent);
-    uint32_t* d_list = (uint32_t*)take(b_ent);
-    HIPCHECK(c, hipMemcpyAsync(d_film, film.data(), b_film, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(d_stat, stat.data(), b_stat, hipMemcpyHostToDevice, c->stream));
-    if (prev && n_prev) HIPCHECK(c, hipMemcpyAsync(d_prev, prev, (size_t)n_prev * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemsetAsync(d_list, 0xFF, b_ent, c->stream));  // (an entry the kernel leaves unwritten shows as one)
+    float4* d_film;
+    float2* d_stat;
+    uint32_t *d_count, *d_prev, *d_flags, *d_list;
+    PrtWorkspace ws;
+    ws.add(&d_film, n_pix).add(&d_stat, n_pix).add(&d_count, 16).add(&d_prev, n_ent).add(&d_flags, n_ent).add(&d_list, n_ent);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, (float*)d_film, film.data(), 4 * n_pix)) || (rc = upload(c, (float*)d_stat, stat.data(), 2 * n_pix))) return rc;
+    if (prev && n_prev && (rc = upload(c, d_prev, prev, n_prev))) return rc;
+    HIPCHECK(c, hipMemsetAsync(d_list, 0xFF, n_ent * sizeof(uint32_t), c->stream));  // (an entry the kernel leaves unwritten shows as one)
     prt_launch_tile_select(c->stream, d_film, d_stat, tm, prev ? d_prev : nullptr, n_prev, threshold, noise_floor, d_flags, d_list,
                            d_count);
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(counts, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (n_prev) HIPCHECK(c, hipMemcpyAsync(list, d_list, (size_t)n_prev * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = download(c, counts, d_count, 2))) return rc;
+    if (n_prev && (rc = download(c, list, d_list, n_prev))) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }

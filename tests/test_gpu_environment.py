@@ -21,6 +21,7 @@ import pytest
 
 import environment_replay as er
 import lighting_replay as lr
+import util
 from util import orc, prt
 
 pytestmark = pytest.mark.gpu
@@ -102,6 +103,11 @@ def test_device_lookup_returns_the_float64_texel(name):
     ok = stable & (sin_t > 1e-3)
     np.testing.assert_allclose(out["pdf_w"][ok], pdf[ok], rtol=2e-6)
     assert np.all(out["pdf_w"][stable & (pdf == 0)] == 0)
+    for n in util.WORKSPACE_COUNTS:
+        part, sel = r.environment_eval(d[:n]), stable[:n]
+        assert np.array_equal(part["texel"][sel], (i * env.W + j)[:n][sel].astype(np.uint32)), n
+        assert np.array_equal(part["rgb"][sel].view(np.uint32), env.rgb[i, j][:n][sel].view(np.uint32)), n
+        np.testing.assert_allclose(part["pdf_w"][ok[:n]], pdf[:n][ok[:n]], rtol=2e-6)
 
 
 @pytest.mark.parametrize("scene,name", [("DEFAULT", "sun"), ("ico", "lognormal"), ("placed", "blackrows"), ("DEFAULT", "5x3")])

@@ -24,6 +24,7 @@ import light_cluster_replay as lcr
 import lighting_replay as lr
 import mesh_light_replay as mr
 import texture_replay as tr
+import util
 from parallelraytracing_amd import scenes
 from test_gpu_mesh_lights import _agree
 from util import orc, prt
@@ -142,6 +143,9 @@ def test_cluster_pmf_equals_the_float32_restatement_bit_for_bit(ctx):
             assert np.all(np.abs(P - phi[None, :]) <= 2.0 ** -22), kind                  # the fallback: P_c = phi_c
         if kind == "inside" and K > 1:
             assert (np.diff(got.astype(np.int64), axis=1) > 0).any()
+    x = np.random.default_rng(19).uniform(-12.0, 12.0, (max(util.WORKSPACE_COUNTS), 3)).astype(np.float32)
+    for n in util.WORKSPACE_COUNTS:
+        assert np.array_equal(r.light_cluster_pmf(x[:n]), lcr.thresholds(t, x[:n])), (ctx["name"], n)
 
 
 def test_cluster_pmf_with_a_cluster_that_is_never_drawn():

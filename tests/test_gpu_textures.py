@@ -96,6 +96,9 @@ def test_texture_eval_equals_the_restatement_bit_for_bit():
         assert len(bad) == 0, (img.shape, filt, wrp, uv[bad[:4]], got[bad[:4]], want[bad[:4]])
         n += len(uv)
     assert n > 10000
+    for n in util.WORKSPACE_COUNTS:      # (the last combination's grid, cut to each length)
+        got = r.texture_eval(t, uv[:n])
+        assert np.array_equal(_bits(got), _bits(tr.lookup(img, filt, wrp, uv[:n, 0], uv[:n, 1]))), n
     # refusals of the eval call itself
     with pytest.raises(prt.PrtError, match="out of range"):
         r.texture_eval(12, [[0.5, 0.5]])
@@ -126,6 +129,13 @@ def test_hit_uv_equals_the_restatement_bit_for_bit(name):
         assert uv[cube].min() < -0.2 and uv[cube].max() > 1.2
         ground = hits["prim"] == 0
         assert uv[ground].min() >= 0.0 and uv[ground].max() <= 1.0 and ground.sum() > 500
+    o, d = tr.primary_and_random_rays(c, n_random=3000, seed=4)
+    want_hits = orc.OracleScene(c["scene"].desc()).closest_hit(o, d, use_bvh=True, n_threads=lr.n_threads_default())
+    for n in util.WORKSPACE_COUNTS:
+        hits, uv, alb = r.hit_uv(o[:n], d[:n])
+        assert util.hits_equal(hits, want_hits[:n]) == [], n
+        want_uv, _ = ts.hit_uv(o[:n], d[:n], hits)
+        assert np.array_equal(uv, want_uv) and np.array_equal(_bits(alb), _bits(ts.albedo(hits, want_uv))), n
 
 
 # ---- 3. frames, lighting off --------------------------------------------------------------------------------------------------

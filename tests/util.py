@@ -13,6 +13,9 @@ from oracle import oracle as orc  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 PRESETS = ["DEFAULT", "LIGHT_TEST", "MATERIAL_TEST", "CORNELL", "RANDOM_BALLS_SMALL"]
+# Array lengths for the function-level entry points, called in this order on one context: the shared device workspace grows,
+# shrinks, grows again and shrinks; 1 .. 7 elements leave every array but the first off a 16-byte multiple unless it is padded.
+WORKSPACE_COUNTS = (65, 1, 2, 3, 5, 7, 4099, 3)
 
 
 def oracle_scene(scene: "prt.Scene") -> "orc.OracleScene":
