@@ -1076,6 +1076,51 @@ int prt_occluded_device(PrtContext* ctx, uint32_t n, const void* d_origins, cons
 int prt_scatter(PrtContext* ctx, uint32_t n, const float* in_dirs, const PrtHit* hits, uint32_t* rng_state,
                 uint32_t* scattered, float* attenuation, float* emitted, float* out_origins, float* out_dirs);
 
+/* ---- Radiance query: whole paths for rays the caller supplies ----------------------------------
+ * "What radiance arrives along this ray?" for n rays from outside a render: light probes, lightmap texels, panoramic,
+ * fisheye or orthographic cameras, training data.  The path of ray i, sample s is the reference's iterative path
+ * (TraceRayGPU, src/backend/cuda_megakernel/renderer.cu:81-119), which is what a render follows:
+ *  RNG state: with rng_state given the path starts from rng_state[i], `samples` must be 1 and the state the path ends with
+ *    is written back (as prt_scatter advances its states).  With rng_state NULL the path starts from
+ *    path_seed(i, first_sample + s, seed): the ray index stands where the pixel index stands in a render, so the query
+ *    over a film's own primary rays, ray index = pixel index, follows the render's paths draw for draw.
+ *  Path: up to max_depth segments.  Each takes the closest hit exactly as prt_closest_hit returns it (directions are used
+ *    as given, not normalised); then L += thr * emitted, Material::Scatter, thr *= attenuation, the scattered direction
+ *    normalised: fp32, no contraction, the order of the shade kernels.  The material's draws are made on the last
+ *    segment too (the state written back is the reference's; a render skips them there, its radiance is the same).
+ *  Miss: L += thr * sky, or thr * the environment image's texel of the direction while one is set (prt_set_environment).
+ *  Textures: a textured Lambertian or Metal takes its albedo from the binding at the hit's UV, as a render does.
+ *  Sampling: PrtSampling.rr_depth (one draw after the material's own, before segment index >= rr_depth) and clamp (on the
+ *    radiance a path delivers) apply as in a render; jitter has no meaning here and is ignored.  So is the lens.
+ *  Lighting: the estimator is always the reference's unidirectional one.  prt_set_lighting, prt_set_light_sources and
+ *    prt_set_light_selection do not change a bit of the result; the expectation is the same for every setting.
+ *  Outputs: rgb_sum[i] = the fp32 sum over s ascending (from 0.0f) of the clamped path radiance: a sum, not a mean, as in
+ *    the film.  segments[i] = the segments walked, summed over the samples.  max_depth == 0: every output is zero and
+ *    rng_state is left alone.
+ *  Side effects: none on the film, film statistics, feature sets, temporal history, ray / light statistics and batch
+ *    instance names; a render after a query equals the same render without it bit for bit.
+ *  PRT_ERR_INVALID: no scene; a null query, origins, dirs or rgb_sum; samples == 0 or > PRT_RADIANCE_MAX_SAMPLES; rng_state
+ *    together with samples > 1; n * samples > 2^32 - 1.  n == 0 is OK and does nothing.
+ *  Cost: chunks of whole samples (about 2^22 rays, at least one sample), and per chunk up to max_depth rounds of: one
+ *    4-byte read of the live count, the ray-query pipeline of prt_closest_hit_device over the live rays only, the UV pass
+ *    while a binding textures something, one step kernel that compacts the survivors.  Results never depend on the chunk
+ *    size (prt_set_param("radiance_chunk", samples per chunk; 0 = by the ray budget)) or on any other tunable.
+ * Not offered: the group (prt_group_*) and the light-sampling estimators. */
+#define PRT_RADIANCE_MAX_SAMPLES 4096u
+typedef struct PrtRadianceQuery {
+    uint32_t max_depth;     /* segments per path at most; 0: every output is zero */
+    uint32_t samples;       /* >= 1, <= PRT_RADIANCE_MAX_SAMPLES */
+    uint32_t seed;
+    uint32_t first_sample;
+} PrtRadianceQuery;
+/* Host arrays: origins, dirs n x 3 floats; rng_state NULL or n, in / out; rgb_sum 3 n; segments NULL or n.  Synchronous. */
+int prt_radiance(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const float* origins, const float* dirs,
+                 uint32_t* rng_state, float* rgb_sum, uint32_t* segments);
+/* The same from DEVICE arrays, on the context's stream: enqueued, with one small wait per bounce (the live count, as
+ * prt_render_adaptive has one per pass); the outputs are complete in stream order when the call returns. */
+int prt_radiance_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs,
+                        void* d_rng_state, void* d_rgb_sum, void* d_segments);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 int prt_enable_timing(PrtContext* ctx, int on); /* HIP events around every kernel launch */
 int prt_get_stats(PrtContext* ctx, PrtStats* out);
@@ -1145,7 +1190,8 @@ int prt_set_variant(PrtContext* ctx, int variant);
  * triangles, prt_last_segment: 0 = walked and shaded like any other; 1 = it ends in the shade launch that produces it where
  * the analytic scan alone decides what the film gets; 2, default = 1, and the rays still walked get the any-hit walk seeded
  * with their analytic hit), "denoise_lds" (which iterations of the denoiser stage their block's footprint in LDS: 0 = none, 1, default = step 1,
- * 2 = steps 1 and 2; A/B).  Results never depend on a tunable.  Unknown names / bad values
+ * 2 = steps 1 and 2; A/B), "feature_chunk" / "radiance_chunk" (samples per chunk of the sampled feature pass / of prt_radiance; 0, default = by
+ * the ray budget).  Results never depend on a tunable.  Unknown names / bad values
  * return PRT_ERR_INVALID. */
 int prt_set_param(PrtContext* ctx, const char* name, int value);
 

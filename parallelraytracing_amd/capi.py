@@ -95,6 +95,14 @@ class PrtFeatureSampling(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint32), ("first_sample", C.c_uint32)]
 
 
+class PrtRadianceQuery(C.Structure):
+    """Settings of prt_radiance (include/prt.h "Radiance query")."""
+    _fields_ = [("max_depth", C.c_uint32), ("samples", C.c_uint32), ("seed", C.c_uint32), ("first_sample", C.c_uint32)]
+
+
+RADIANCE_MAX_SAMPLES = 4096  # PRT_RADIANCE_MAX_SAMPLES
+
+
 class PrtAdaptive(C.Structure):
     """Settings of prt_render_adaptive (include/prt.h "Film statistics and adaptive sampling")."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
@@ -343,6 +351,8 @@ SIGNATURES = {
     "prt_occluded": (C.c_int, [_vp, C.c_uint32, _fp, _fp, _fp, C.POINTER(C.c_uint8)]),
     "prt_occluded_device": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "prt_scatter": (C.c_int, [_vp, C.c_uint32, _fp, C.POINTER(PrtHit), _u32p, _u32p, _fp, _fp, _fp, _fp]),
+    "prt_radiance": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _fp, _fp, _u32p, _fp, _u32p]),
+    "prt_radiance_device": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "prt_enable_timing": (C.c_int, [_vp, C.c_int]),
     "prt_get_stats": (C.c_int, [_vp, C.POINTER(PrtStats)]),
     "prt_reset_stats": (C.c_int, [_vp]),

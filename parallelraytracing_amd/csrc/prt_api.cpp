@@ -29,6 +29,7 @@
 #include "prt_feature_samples.h"
 #include "prt_features.h"
 #include "prt_kernels.h"
+#include "prt_radiance.h"
 #include "prt_scene.h"
 #include "prt_temporal.h"
 #include "prt_temporal_contract.h"
@@ -207,6 +208,7 @@ struct PrtContext {
     DevBuf samp;                                     // the running sums until finished
     bool samp_valid = false;
     int feature_chunk = 0;  // prt_set_param("feature_chunk", n): samples per chunk of the sampled pass, 0 = by the ray budget
+    int radiance_chunk = 0;  // prt_set_param("radiance_chunk", n): samples per chunk of the radiance query, 0 = by the ray budget
     DevBuf dn;
     // ---- temporal reprojection (include/prt.h): two history sets that ping-pong, the blended planar frame, status and
     // counters in one allocation; the basis and the placed copies' matrices of the step that wrote the history ----
@@ -3010,6 +3012,132 @@ int prt_scatter(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* h
     return PRT_OK;
 }
 
+// ---- radiance query (include/prt.h "Radiance query") --------------------------------------------------
+// What enqueue_radiance needs beside its arguments for chunks of up to m paths: two lists (a ray and two float4 of state
+// each), the hit records and the textured albedo of a round's live rays, one record per slot, and the two live counts that
+// take turns.  A caller declares it behind its own arrays, in the same layout.
+struct RadianceScratch {
+    PrtRadianceList list[2];
+    PrtHit* hits;
+    float* albedo;
+    float4* slots;
+    uint32_t* cnt;
+    void declare(PrtWorkspace& ws, size_t m, bool textured) {
+        for (PrtRadianceList& l : list) ws.add(&l.o, 3 * m).add(&l.d, 3 * m).add(&l.s0, m).add(&l.s1, m);
+        ws.add(&hits, m).add(&slots, m).add(&cnt, (size_t)2);
+        albedo = nullptr;
+        if (textured) ws.add(&albedo, 3 * m);
+    }
+};
+
+// Samples per chunk: about 2^22 rays unless a chunk size is forced, at least one sample (enqueue_feature_samples' rule)
+static uint32_t radiance_chunk(const PrtContext* c, const PrtRadianceQuery& q, uint32_t n) {
+    const uint32_t cs = c->radiance_chunk > 0 ? (uint32_t)c->radiance_chunk : std::max<uint32_t>(1u, (1u << 22) / n);
+    return std::min(cs, q.samples);
+}
+
+// The refusals of both forms, in the order of the header; everything here is decided without a device.
+static int check_radiance(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const void* origins, const void* dirs, const void* rng_state,
+                          const void* rgb_sum) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!q) return fail(c, PRT_ERR_INVALID, "prt_radiance: null query");
+    if (q->samples == 0u || q->samples > PRT_RADIANCE_MAX_SAMPLES)
+        return fail(c, PRT_ERR_INVALID, "prt_radiance: samples = %u, expected 1 .. %u", q->samples, PRT_RADIANCE_MAX_SAMPLES);
+    if (rng_state && q->samples > 1u)
+        return fail(c, PRT_ERR_INVALID, "prt_radiance: rng_state carries one state per ray: samples must be 1, not %u", q->samples);
+    if ((uint64_t)n * q->samples > 0xFFFFFFFFull)
+        return fail(c, PRT_ERR_INVALID, "prt_radiance: %u rays x %u samples exceed 2^32 - 1 paths", n, q->samples);
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (n != 0u && (!origins || !dirs || !rgb_sum)) return fail(c, PRT_ERR_INVALID, "prt_radiance: null array");
+    return PRT_OK;
+}
+
+// The paths of n rays (device arrays) on the context's stream.  Chunks of cs whole samples; per chunk the start kernel
+// leaves every path live in list 0, and each round reads the 4-byte live count (one small wait, as enqueue_chains has),
+// queries the live rays only, looks up the textured albedo of their hits, and steps them into the other list.  Round
+// max_depth - 1 ends every path, so after the rounds every slot is written and the ordered sum adds the chunk to the
+// outputs.  Nothing but x, the outputs, d_rng and the ray-query pipeline's own buffers is written.
+static int enqueue_radiance(PrtContext* c, const PrtRadianceQuery& q, uint32_t n, uint32_t cs, const float* d_o, const float* d_d,
+                            uint32_t* d_rng, float* d_rgb, uint32_t* d_seg, const RadianceScratch& x) {
+    int rc;
+    if (q.max_depth == 0u) {
+        HIPCHECK(c, hipMemsetAsync(d_rgb, 0, 3 * (size_t)n * sizeof(float), c->stream));
+        if (d_seg) HIPCHECK(c, hipMemsetAsync(d_seg, 0, (size_t)n * sizeof(uint32_t), c->stream));
+        return PRT_OK;
+    }
+    PrtRadianceArgs a{x.hits, x.albedo, c->dsc.mat_rgbs, c->dsc.mat_type, env_on(c) ? dev_env(c) : DevEnv{}, {c->dsc.sky[0], c->dsc.sky[1], c->dsc.sky[2]},
+                      c->sampling, q.max_depth, 0u, x.slots, d_rng, nullptr};
+    for (uint32_t s0 = 0; s0 < q.samples; s0 += cs) {
+        const uint32_t ccs = std::min(cs, q.samples - s0);
+        const uint32_t m = ccs * n;
+        prt_launch_rd_start(c->stream, n, ccs, q.first_sample + s0, q.seed, d_o, d_d, d_rng, x.list[0]);
+        HIPCHECK(c, hipGetLastError());
+        uint32_t live = m;
+        int cur = 0;
+        for (uint32_t r = 0; r < q.max_depth; ++r) {
+            if (r > 0u) {
+                HIPCHECK(c, hipMemcpyAsync(&live, x.cnt + (r & 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                HIPCHECK(c, hipStreamSynchronize(c->stream));
+                if (live == 0u) break;
+                if (live > m) return fail(c, PRT_ERR_HIP, "prt_radiance: live count %u above %u paths", live, m);
+            }
+            if ((rc = enqueue_query(c, live, x.list[cur].o, x.list[cur].d, nullptr, x.hits, nullptr))) return rc;
+            if (x.albedo) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), live, c->rb[0], nullptr, x.albedo);  // (rays and final hit ids are in rb[0])
+            a.round = r;
+            a.count = x.cnt + ((r + 1u) & 1u);
+            HIPCHECK(c, hipMemsetAsync(a.count, 0, sizeof(uint32_t), c->stream));
+            prt_launch_rd_step(c->stream, live, x.list[cur], a, x.list[cur ^ 1]);
+            HIPCHECK(c, hipGetLastError());
+            cur ^= 1;
+        }
+        prt_launch_rd_sum(c->stream, n, ccs, s0 == 0u, x.slots, d_rgb, d_seg);
+        HIPCHECK(c, hipGetLastError());
+    }
+    return PRT_OK;
+}
+
+int prt_radiance(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const float* origins, const float* dirs, uint32_t* rng_state,
+                 float* rgb_sum, uint32_t* segments) {
+    int rc = check_radiance(c, q, n, origins, dirs, rng_state, rgb_sum);
+    if (rc || n == 0u) return rc;
+    if ((rc = need_device(c))) return rc;
+    const uint32_t cs = radiance_chunk(c, *q, n);
+    const size_t n1 = n;
+    // the scratch below and the path state of a chunk's rays may be reallocated: nothing enqueued before may still be using them
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    float *d_o, *d_d, *d_rgb;
+    uint32_t *d_rng = nullptr, *d_seg = nullptr;
+    RadianceScratch x;
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * n1).add(&d_d, 3 * n1).add(&d_rgb, 3 * n1);
+    if (rng_state) ws.add(&d_rng, n1);
+    if (segments) ws.add(&d_seg, n1);
+    x.declare(ws, (size_t)cs * n1, tex_on(c));
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_o, origins, 3 * n1)) || (rc = upload(c, d_d, dirs, 3 * n1))) return rc;
+    if (rng_state && (rc = upload(c, d_rng, rng_state, n1))) return rc;
+    if ((rc = enqueue_radiance(c, *q, n, cs, d_o, d_d, d_rng, d_rgb, d_seg, x))) return rc;
+    if ((rc = download(c, rgb_sum, d_rgb, 3 * n1))) return rc;
+    if (rng_state && (rc = download(c, rng_state, d_rng, n1))) return rc;
+    if (segments && (rc = download(c, segments, d_seg, n1))) return rc;
+    return prt_synchronize(c);  // waits for the stream and reports a ray the walk had to give up
+}
+
+int prt_radiance_device(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs, void* d_rng_state,
+                        void* d_rgb_sum, void* d_segments) {
+    int rc = check_radiance(c, q, n, d_origins, d_dirs, d_rng_state, d_rgb_sum);
+    if (rc || n == 0u) return rc;
+    if ((rc = need_device(c))) return rc;
+    const uint32_t cs = radiance_chunk(c, *q, n);
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (as above)
+    RadianceScratch x;
+    PrtWorkspace ws;
+    x.declare(ws, (size_t)cs * n, tex_on(c));
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    return enqueue_radiance(c, *q, n, cs, (const float*)d_origins, (const float*)d_dirs, (uint32_t*)d_rng_state, (float*)d_rgb_sum,
+                            (uint32_t*)d_segments, x);
+}
+
 int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,
                      float* shadow_dirs, float* tmax, uint32_t* light, float* contrib, float* pdf_light, float* pdf_bsdf,
                      float* w_light, float* w_bsdf) {
@@ -3363,6 +3491,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "light_buckets" && (value == 0 || value == 1)) c->light_buckets = value;
     else if (n == "denoise_lds" && value >= 0 && value <= 2) c->dn_lds = value;
     else if (n == "feature_chunk" && value >= 0 && value <= (int)PRT_FEATURE_MAX_SAMPLES) c->feature_chunk = value;
+    else if (n == "radiance_chunk" && value >= 0 && value <= (int)PRT_RADIANCE_MAX_SAMPLES) c->radiance_chunk = value;
     else if (n == "exit_max" && value >= 0 && value < 64) c->tune.exit_max = (uint32_t)value;
     else return fail(c, PRT_ERR_INVALID, "unknown parameter or bad value: %s = %d", name, value);
     return PRT_OK;

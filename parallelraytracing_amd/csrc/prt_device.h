@@ -349,6 +349,37 @@ PRT_DEV float4 textured_rgbs(const DevScene& sc, const DevTex& tex, uint32_t mat
     return rgbs;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Environment image (PrtEnvironment, include/prt.h "Environment light"; DevEnv): lat-long, nearest texel.  Only the ENV
+// instances of the producers and the radiance query's step call these; the others keep the constant sky and their code.
+// ---------------------------------------------------------------------------------------------------------
+#define PRT_ENV_INV_TWO_PI 0.159154943091895336f
+#define PRT_ENV_INV_PI 0.318309886183790672f
+// texel i * W + j of the unit direction d: always in range, a NaN direction included (texel 0)
+PRT_DEV uint32_t env_texel(const DevEnv& env, f3 d) {
+    const float x = __builtin_fmaf(atan2f(d.z, d.x), PRT_ENV_INV_TWO_PI, 0.5f) * (float)env.W;
+    float cy = d.y < -1.0f ? -1.0f : d.y;
+    cy = cy > 1.0f ? 1.0f : cy;
+    const float y = (acosf(cy) * PRT_ENV_INV_PI) * (float)env.H;
+    uint32_t j = x > 0.0f ? (uint32_t)x : 0u;
+    uint32_t i = y > 0.0f ? (uint32_t)y : 0u;
+    j = j < env.W - 1u ? j : env.W - 1u;
+    i = i < env.H - 1u ? i : env.H - 1u;
+    return i * env.W + j;
+}
+// radiance of a miss along d, and the solid-angle density with which the environment sample picks d (without T_e)
+PRT_DEV f3 env_radiance(const DevEnv& env, f3 d, float& pdf_w) {
+    const float4 t = env.texels[env_texel(env, d)];
+    const float s2 = (1.0f - d.y) * (1.0f + d.y);  // 1 - d.y^2 without the cancellation near the poles
+    const float sin_t = __builtin_sqrtf(s2 > 0.0f ? s2 : 0.0f);
+    pdf_w = sin_t > 0.0f ? t.w / sin_t : 0.0f;
+    return mk3(t.x, t.y, t.z);
+}
+PRT_DEV f3 env_radiance(const DevEnv& env, f3 d) {
+    const float4 t = env.texels[env_texel(env, d)];
+    return mk3(t.x, t.y, t.z);
+}
+
 // ---- materials (src/core/material.h) -------------------------------------------------------------------
 // fresnelReflectance (material.h:105-109): std::pow(float,int) promotes to double, i.e. the reference evaluates
 // std::pow((double)(1 - cosine), 5.0) with the host's libm.  The oracle calls exactly that (oracle/prt_oracle.cpp);

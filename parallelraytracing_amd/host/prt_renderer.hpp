@@ -437,6 +437,39 @@ public:
         PrtContext* c = prt_group_context(grp_, 0);
         if (prt_occluded(c, n, origins, dirs, tmax, occluded)) throw Error(std::string("prt_occluded: ") + prt_last_error(c));
     }
+    // Radiance query on the first GPU's context (prt_radiance, include/prt.h "Radiance query"): the fp32 SUM over `samples`
+    // paths per ray of the radiance arriving along n caller-supplied rays (origins / dirs: n x 3 floats, host memory) into
+    // rgb_sum (3 n floats); sample s of ray i starts from the renderer's seed, the ray index and first_sample + s.
+    // rng_state (n, in / out) gives the paths their states instead and needs samples == 1; segments (n) may be null.
+    void Radiance(uint32_t n, const float* origins, const float* dirs, float* rgb_sum, uint32_t samples = 1, uint32_t first_sample = 0,
+                  uint32_t* rng_state = nullptr, uint32_t* segments = nullptr) {
+        PrtContext* c = prt_group_context(grp_, 0);
+        const PrtRadianceQuery q{max_depth_, samples, seed_, first_sample};
+        if (prt_radiance(c, &q, n, origins, dirs, rng_state, rgb_sum, segments)) throw Error(std::string("prt_radiance: ") + prt_last_error(c));
+    }
+    // A lat-long radiance probe at `position`: width x height x 3 floats, the mean over `samples` paths along the unit
+    // direction of every texel centre, in prt_set_environment's layout (row 0 = the +Y pole), so that a probe written with
+    // prt_write_pfm can light another scene through SetEnvironmentPfm.  The directions are those of the Python package's
+    // probe_directions: float64, the C library's sin / cos, rounded once.
+    void RenderProbe(const float position[3], uint32_t width, uint32_t height, uint32_t samples, std::vector<float>& rgb) {
+        const size_t n = (size_t)width * height;
+        const double pi = 3.141592653589793;
+        std::vector<float> o(3 * n), d(3 * n);
+        for (uint32_t i = 0; i < height; ++i) {
+            const double theta = pi * ((i + 0.5) / height), ct = std::cos(theta), st = std::sin(theta);
+            for (uint32_t j = 0; j < width; ++j) {
+                const double phi = 2.0 * pi * ((j + 0.5) / width) - pi;
+                const double x = st * std::cos(phi), y = ct, z = st * std::sin(phi);
+                const double inv = 1.0 / std::sqrt((x * x + y * y) + z * z);
+                const size_t k = 3 * ((size_t)i * width + j);
+                d[k] = (float)(x * inv), d[k + 1] = (float)(y * inv), d[k + 2] = (float)(z * inv);
+                o[k] = position[0], o[k + 1] = position[1], o[k + 2] = position[2];
+            }
+        }
+        rgb.assign(3 * n, 0.0f);
+        Radiance((uint32_t)n, o.data(), d.data(), rgb.data(), samples);
+        for (float& v : rgb) v = v / (float)samples;
+    }
 
 private:
     void check(int rc) {

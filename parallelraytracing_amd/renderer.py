@@ -12,6 +12,7 @@ same shape lives in host/prt_renderer.hpp.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -1149,6 +1150,67 @@ class HipWavefrontRenderer:
                                            od.ctypes.data_as(_fp)))
         return sc.astype(bool), att, em, oo, od, rng
 
+    def radiance(self, o, d, rng_state=None, samples: int = 1, seed=None, first_sample: int = 0, max_depth=None,
+                 return_info: bool = False):
+        """The radiance arriving along n caller-supplied rays (prt_radiance, include/prt.h "Radiance query"): whole paths
+        of up to max_depth segments (default: the renderer's) on the device, `samples` per ray.  o, d: [n, 3] float32,
+        numpy arrays (the host form) or torch tensors on the renderer's device (the device form, ordered after torch's
+        current stream).  rng_state [n] (uint32; torch: int32 or uint32 bits) gives every path its starting state and needs
+        samples == 1; without it sample s of ray i starts from path_seed(i, first_sample + s, seed), seed = the renderer's
+        unless given.  Returns the mean [n, 3] = sum / samples in fp32; with return_info also {"sum": the fp32 sum the
+        library returns, "segments": [n] segments walked, "rng_state": the final states, or None}."""
+        q = capi.PrtRadianceQuery(int(self.max_depth if max_depth is None else max_depth), int(samples),
+                                  int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample) & 0xFFFFFFFF)
+        try:
+            import torch
+            is_t = isinstance(o, torch.Tensor) or isinstance(d, torch.Tensor)
+        except ImportError:
+            is_t = False
+        if is_t:
+            n = int(o.shape[0]) if isinstance(o, torch.Tensor) and o.dim() == 2 else -1
+            self._check_tensor("o", o, (n, 3))
+            self._check_tensor("d", d, (n, 3))
+            rng = None
+            if rng_state is not None:
+                if not isinstance(rng_state, torch.Tensor) or rng_state.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or \
+                        tuple(rng_state.shape) != (n,) or rng_state.device != o.device:
+                    raise ValueError(f"rng_state: expected an int32 / uint32 tensor of shape ({n},) on {o.device}")
+                rng = rng_state.contiguous().clone()
+            total = torch.zeros((n, 3), dtype=torch.float32, device=o.device)
+            seg = torch.zeros(n, dtype=torch.int32, device=o.device)
+            # (n == 0 still goes through the library: it refuses a bad query whatever the count)
+            self._on_context_stream(lambda: capi.lib().prt_radiance_device(
+                self._ctx, C.byref(q), n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                C.c_void_p(rng.data_ptr() if rng is not None else None), C.c_void_p(total.data_ptr()), C.c_void_p(seg.data_ptr())))
+            # (a tensor divisor: torch turns a division by a Python number into a multiplication by its reciprocal)
+            mean = total / torch.full((1, 1), float(q.samples), dtype=torch.float32, device=o.device)
+        else:
+            o, d = _f32(o), _f32(d)
+            if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+                raise ValueError(f"o / d: expected two [n, 3] arrays, got {o.shape} and {d.shape}")
+            n = o.shape[0]
+            rng = None
+            if rng_state is not None:
+                rng = np.array(rng_state, dtype=np.uint32).ravel()  # a copy: advanced in place
+                if rng.size != n:
+                    raise ValueError(f"rng_state: {rng.size} states for {n} rays")
+            total = np.zeros((n, 3), np.float32)
+            seg = np.zeros(n, np.uint32)
+            self._check(capi.lib().prt_radiance(self._ctx, C.byref(q), n, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp),
+                                                rng.ctypes.data_as(_u32p) if rng is not None else None,
+                                                total.ctypes.data_as(_fp), seg.ctypes.data_as(_u32p)))
+            mean = total / np.float32(q.samples)
+        if return_info:
+            return mean, {"sum": total, "segments": seg, "rng_state": rng}
+        return mean
+
+    def render_probe(self, position, H: int, W: int, samples: int = 1, seed=None, first_sample: int = 0, max_depth=None) -> np.ndarray:
+        """A lat-long radiance probe at `position`: [H, W, 3] float32, the mean radiance along probe_directions(H, W),
+        texel index = ray index.  The layout is set_environment's, so a probe of one scene can light another."""
+        d = probe_directions(H, W).reshape(-1, 3)
+        o = np.broadcast_to(_f32(position).reshape(1, 3), d.shape)
+        return self.radiance(o, d, samples=samples, seed=seed, first_sample=first_sample, max_depth=max_depth).reshape(H, W, 3)
+
     def enable_timing(self, on: bool = True):
         self._check(capi.lib().prt_enable_timing(self._ctx, int(on)))
 
@@ -1579,6 +1641,24 @@ def _set_environment(fn, handle, rgb, light_share) -> int:
         raise ValueError("environment: rgb must be [H, W, 3]")
     e = capi.PrtEnvironment(a.ctypes.data_as(_fp), a.shape[1], a.shape[0], float(light_share))
     return fn(handle, C.byref(e))
+
+
+def probe_directions(H: int, W: int) -> np.ndarray:
+    """Unit directions [H, W, 3] float32 of the texel centres of a lat-long image in set_environment's convention (row 0 =
+    +Y pole; include/prt.h "Environment light"): u = (j + 1/2) / W, v = (i + 1/2) / H, phi = 2 pi u - pi, theta = pi v,
+    w = (sin theta cos phi, cos theta, sin theta sin phi).  Evaluated in float64 and rounded once, so each direction is a
+    unit vector to fp32 rounding and looks up its own texel (a centre is half a texel from every edge)."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("probe_directions: H and W must be at least 1")
+    # (sin / cos through the C library, one call per row and column: the C++ adapter's RenderProbe spells the same lines)
+    phi = [2.0 * math.pi * ((j + 0.5) / W) - math.pi for j in range(W)]
+    theta = [math.pi * ((i + 0.5) / H) for i in range(H)]
+    cp, sp = np.array([math.cos(p) for p in phi])[None, :], np.array([math.sin(p) for p in phi])[None, :]
+    ct, st = np.array([math.cos(t) for t in theta])[:, None], np.array([math.sin(t) for t in theta])[:, None]
+    x, y, z = st * cp, np.broadcast_to(ct, (H, W)), st * sp
+    inv = 1.0 / np.sqrt((x * x + y * y) + z * z)
+    return np.stack([x * inv, y * inv, z * inv], axis=-1).astype(np.float32)
 
 
 def read_pfm(path: str) -> np.ndarray:

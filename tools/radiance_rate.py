@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Rays per second of the radiance query (prt_radiance_device) on the 1080p camera rays of C3, beside a one-sample render of
+the same frame at the same depth.
+
+  python tools/radiance_rate.py [--config C3 --reps 7 --out profiles/radiance_rate.json]
+
+The query gets the film's own pixel-centre rays as device tensors, ray index = pixel index, one sample, the renderer's seed:
+the paths the render follows (tests/test_gpu_radiance.py holds the two to the same bits).  Both calls are synchronous; the
+host clock around each, on a warm context, alternating, median of --reps.  The query is expected to be slower: one host wait
+per bounce, no compact primary rays, no shared primary walk, no last-segment route.  Nothing here is a threshold.
+
+Per-round times: the query is timed again at max_depth 1 .. depth; the paths of depth k are the first k rounds of depth
+k + 1, so the differences are what each further round costs (query pipeline over the live rays + step + the count's wait).
+The segments each depth walked are reported with them.  One JSON document goes to --out; every row is printed."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="C3")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radiance_rate.json"))
+    a = ap.parse_args()
+
+    import torch
+
+    import parallelraytracing_amd as prt
+    if not torch.cuda.is_available():
+        raise SystemExit("radiance_rate: no GPU: nothing is measured without one")
+    dev = torch.device("cuda", 0)
+    scene, cam, W, H, _, depth = prt.scenes.config(a.config)
+    r = prt.HipWavefrontRenderer(device=0, max_depth=depth, seed=1)
+    film = prt.Film(W, H)
+    r.Init(film, scene, cam)
+    y, x = np.mgrid[0:H, 0:W]
+    o, d = r.camera_rays((x.ravel() + 0.5).astype(np.float32), (y.ravel() + 0.5).astype(np.float32))
+    o, d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+    n = W * H
+
+    def timed(fn):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize(dev)
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def render():
+        film.Clear()
+        r.frame_index = 0
+        r.reset_stats()
+        ms, _ = timed(r.ProgressiveRender)
+        return ms, int(r.stats().rays_total)
+
+    def query(k):
+        ms, out = timed(lambda: r.radiance(o, d, max_depth=k, return_info=True))
+        return ms, int(out[1]["segments"].sum(dtype=torch.int64).item())
+
+    render()
+    for k in range(1, depth + 1):      # warm: allocations, the first launch of every kernel
+        query(k)
+    t_render, t_query = [], {k: [] for k in range(1, depth + 1)}
+    rays = segs = None
+    for i in range(a.reps):
+        ms, rays = render()
+        t_render.append(ms)
+        for k in (range(1, depth + 1) if i % 2 == 0 else range(depth, 0, -1)):
+            ms, s = query(k)
+            t_query[k].append(ms)
+            if k == depth:
+                segs = s
+    med = {k: float(np.median(v)) for k, v in t_query.items()}
+    mr = float(np.median(t_render))
+    rounds = [dict(round=k - 1, ms=med[k] - (med[k - 1] if k > 1 else 0.0)) for k in range(1, depth + 1)]
+    doc = dict(config=a.config, size=f"{W}x{H}", triangles=int(scene.n_triangles), depth=depth, rays=n, reps=a.reps,
+               device=torch.cuda.get_device_name(0), render_ms=mr, render_segments=rays, render_mrays_s=rays / mr / 1e3,
+               query_ms=med[depth], query_segments=segs, query_mrays_s=segs / med[depth] / 1e3, query_over_render=med[depth] / mr,
+               query_ms_min_max=[float(min(t_query[depth])), float(max(t_query[depth]))],
+               render_ms_min_max=[float(min(t_render)), float(max(t_render))], rounds=rounds)
+    print(json.dumps(doc), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
