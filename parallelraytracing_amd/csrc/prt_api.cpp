@@ -699,18 +699,26 @@ f3 h_cross(f3 a, f3 b) { return f3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x,
 // The whole film as a batch view (PrtBatchView, prt_kernels.h): the context's own tile map, no tile list.
 PrtBatchView whole_film(const PrtContext* c) { return PrtBatchView{c->tm, nullptr}; }
 
+// What the choice of a tree walk's kernel instances reads (PrtWalkFacts, prt_walk.h), from c->dsc (fill_dev_scene), the compiled
+// scene's tree bounds and `tune` (the context's tunables, or a bounce's copy of them).
+PrtWalkFacts walk_facts(const PrtContext* c, const PrtTravTuning& tune, PrtWalkRequest request, uint32_t max_rays, bool stats, bool primary) {
+    PrtWalkFacts f{};
+    f.has8 = c->dsc.nodes8 != nullptr, f.has4 = c->dsc.nodes4 != nullptr, f.has2 = c->dsc.nodes != nullptr;
+    f.insts = c->dsc.n_insts != 0u, f.abvh = c->dsc.abvh_nodes != nullptr;
+    f.depth8 = c->dsc.depth8, f.node_stride = c->dsc.node_stride, f.depth2 = c->hs.bvh.max_depth, f.max_stack4 = c->hs.bvh.max_stack4;
+    f.wide = tune.wide, f.stack_lds = tune.stack_lds, f.stack_cap = tune.stack_cap, f.exit_max = tune.exit_max, f.tri_min = tune.tri_min;
+    f.grid_blocks = tune.grid_blocks, f.steal = tune.steal, f.variant = c->variant, f.max_rays = max_rays, f.request = request, f.stats = stats, f.primary = primary;
+    return f;
+}
+
 // The tree walk of a prepared ray buffer (analytic scan done, hit / hd2 seeded) on the context's stream: the closest hit, or
-// with `any` the any-hit walk behind prt_occluded and the shadow rays.  The persistent kernels, or k_intersect where another
-// traversal variant is forced (A/B; it finds the closest hit from the seeded bound, which answers an occlusion query as well).
+// with `any` the any-hit walk behind prt_occluded and the shadow rays (`seeded`: over a closest-hit walk's buffer, every ray
+// walked).  Fill the facts, plan (prt_plan_walk, prt_walk.h), launch.
 void walk_rays(PrtContext* c, const PrtRayBuf& rays, const uint32_t* count, uint32_t max_rays, bool any, const PrtTravTuning& tune,
                unsigned long long* stats, const PrtPrimary* primary, bool seeded = false) {
-    if (!prt_route_walk8(c->variant == 0, c->dsc.n_insts != 0u, c->dsc.nodes != nullptr))
-        prt_launch_intersect(c->stream, c->dsc, rays, count, max_rays, c->hs.bvh.max_depth <= 31 ? 31 : 63, c->variant, stats);
-    else if (any)
-        prt_launch_occluded(c->stream, c->dsc, rays, count, c->d_work, (uint32_t*)c->spill.p, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4, tune, seeded);
-    else
-        prt_launch_traverse(c->stream, c->dsc, rays, count, c->d_work, (uint32_t*)c->spill.p, max_rays, c->hs.bvh.max_depth, c->hs.bvh.max_stack4,
-                            tune, stats, primary);
+    const PrtWalkRequest request = !any ? PRT_WALK_CLOSEST : seeded ? PRT_WALK_SEEDED : PRT_WALK_ANY;
+    const PrtWalkPlan plan = prt_plan_walk(walk_facts(c, tune, request, max_rays, stats != nullptr, primary != nullptr));
+    prt_launch_walk(c->stream, plan, PrtWalkArgs{&c->dsc, rays, count, c->d_work, (uint32_t*)c->spill.p, stats, primary, &tune});
 }
 
 // Measurement aid (sort_rays, tools/sort_ab.py): the front rays of `in` in sorted order through tune->perm.  The host needs
@@ -757,6 +765,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     if (rc) return rc;
     if ((rc = ensure_spill(c))) return rc;
     if ((rc = sync_light_tables(c))) return rc;
+    const PrtWalkFacts wf = walk_facts(c, c->tune, PRT_WALK_PATH, n_paths, trav_stats != nullptr, false);  // (as the PATH route asks)
     PrtRouteFacts f{};
     f.lit = c->lighting != PRT_LIGHTING_OFF;
     f.mesh_lights = mesh_lights_on(c);
@@ -767,19 +776,19 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     f.listed = view.list != nullptr;
     f.film_stats = c->film_stats;
     f.has_nodes = c->dsc.n_nodes != 0u;
-    f.has_bvh2 = c->dsc.nodes != nullptr;
-    f.insts = c->dsc.n_insts != 0u;
-    f.abvh = c->dsc.abvh_nodes != nullptr;
+    f.has_bvh2 = wf.has2;
+    f.insts = wf.insts;
+    f.abvh = wf.abvh;
     f.few_prims = c->dsc.n_prims <= 16u;
     f.jitter = c->sampling.jitter != 0u;
     f.sa = c->sampling.rr_depth != 0u || c->sampling.clamp > 0.0f;
     f.multi_sample = S_cur > 1u;
-    f.variant0 = c->variant == 0;
+    f.variant0 = wf.variant == 0;
     f.compact_primary = c->compact_primary;
     f.primary_walk = c->primary_walk;
-    f.takes_primary = prt_traverse_takes_primary(c->dsc, c->tune);
+    f.takes_primary = prt_traverse_takes_primary(wf);
     f.primary_hit = c->tune.primary_hit != 0u;
-    f.path_gate = !trav_stats && !c->d_shade_div && c->sort_rays == 0u && n_paths <= c->tune.path_max && prt_path_kernel_applies(c->dsc, c->tune);
+    f.path_gate = !trav_stats && !c->d_shade_div && c->sort_rays == 0u && n_paths <= c->tune.path_max && prt_path_kernel_applies(wf);
     f.path_kernel = c->tune.path_kernel;
     f.fuse = c->tune.fuse;
     f.mesh_emissive = c->hs.mesh_emissive;
@@ -840,7 +849,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         HIPCHECK(c, hipMemsetAsync(c->d_work, 0, 256 * sizeof(uint32_t), c->stream));  // the cursors; the error flags in [256] stay for prt_synchronize
         PrtPathArgs pa{c->cam, tm, c->sampling, c->d_rad, first_sample, seed, max_depth, n_paths};
         if ((rc = begin_event(c, 1, &ep))) return rc;
-        prt_launch_path(c->stream, c->dsc, pa, c->d_work, c->tune);
+        prt_launch_path(c->stream, prt_plan_walk(wf), c->dsc, pa, c->d_work, c->tune);
         if ((rc = end_event(c, &ep))) return rc;
         ++c->stats.intersect_launches;
         return accumulate_batch();
@@ -1408,7 +1417,7 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     if (e == hipSuccess && c->hs.nrm_records.size() == 12 * (size_t)n_tris) e = hipMemcpy(c->hs.nrm_records.data(), c->d_nrms, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
     HIPCHECK(c, e);
     // the binary and 4-wide trees (A/B kernels, overflow fallback of deep host-built trees) still describe the OLD
-    // geometry: they go, and the instance selection falls to the 8-wide kernels that need neither (prt_launch_traverse)
+    // geometry: they go, and the instance selection falls to the 8-wide kernels that need neither (prt_plan_walk)
     free_dev(c->d_nodes);
     free_dev(c->d_nodes4);
     c->dsc.nodes = nullptr;
@@ -3367,7 +3376,8 @@ int prt_kernel_occupancy(PrtContext* c, PrtOccupancy* out) {
     if (!out) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     int nb = 0, vg = 0, sg = 0, lds = 0;
-    if (prt_traverse_occupancy(c->dsc, c->tune, &nb, &vg, &sg, &lds)) return fail(c, PRT_ERR_HIP, "occupancy query failed");
+    const PrtWalkPlan plan = prt_plan_walk(walk_facts(c, c->tune, PRT_WALK_CLOSEST, 0u, false, false));
+    if (prt_walk_occupancy(plan, &nb, &vg, &sg, &lds)) return fail(c, PRT_ERR_HIP, "occupancy query failed");
     hipDeviceProp_t prop;
     HIPCHECK(c, hipGetDeviceProperties(&prop, c->device));
     out->blocks_per_cu = (uint32_t)nb;
@@ -3376,15 +3386,14 @@ int prt_kernel_occupancy(PrtContext* c, PrtOccupancy* out) {
     out->vgprs = (uint32_t)vg;
     out->lds_bytes_per_block = (uint32_t)lds;
     out->compute_units = (uint32_t)prop.multiProcessorCount;
-    out->resident_grid_blocks = !strcmp(prt_traverse_instance(c->dsc, c->tune), "lean8_5waves")
-                                    ? c->tune.grid_blocks + c->tune.grid_blocks / 4u : c->tune.grid_blocks;
+    out->resident_grid_blocks = plan.resident_grid;
     return PRT_OK;
 }
 
 int prt_kernel_instance(PrtContext* c, char* name, uint32_t capacity) {
     if (!c || !name || capacity == 0u) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
-    snprintf(name, capacity, "%s", prt_traverse_instance(c->dsc, c->tune));
+    snprintf(name, capacity, "%s", prt_plan_walk(walk_facts(c, c->tune, PRT_WALK_CLOSEST, 0u, false, false)).name);
     return PRT_OK;
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/prt.h"
 #include "prt_route.h"      // the instance lists and the plan of a batch
+#include "prt_walk.h"       // PrtTravTuning; the walk kernels' instance lists and the plan of a tree walk
 #include "prt_scene_pod.h"  // DevPrim, DevInstance
 
 struct f3 {
@@ -77,32 +78,6 @@ struct PrtTileMap {
 struct PrtBatchView {
     PrtTileMap tm;
     const uint32_t* list;
-};
-
-// Tunables of k_traverse_persistent (prt_set_param).
-struct PrtTravTuning {
-    uint32_t grid_blocks;  // resident 256-thread blocks of the persistent grid
-    uint32_t chunk;        // rays a wave grabs per global atomic (multiple of 64)
-    uint32_t refill_min;   // idle lanes of a wave that trigger a refill
-    uint32_t exit_max;     // leave the node loop when at most this many lanes still search for a leaf (0xFFFFFFFF = per instance: 32 two-level, 16 otherwise)
-    uint32_t xcd_affinity; // 4-wide / binary kernels, A/B: 1 = each XCD drains its own eighth of the ray buffer first (L2 locality), then steals
-    uint32_t wide;         // 2: walk the compressed 8-wide tree (default), 1: the 4-wide tree, 0: the binary tree
-    uint32_t tri_min;      // 8-wide kernel: start a triangle phase once this many lane-steps have queued triangles (0 = per tree: 12 for one-level trees with one node per 128-B line, 24 otherwise)
-    uint32_t fuse;         // k_shade: 1 = shade one analytic-only segment in place per call (default), 0 = store every ray
-    uint32_t stack_cap;    // test hook: the 8-wide kernel treats its stack as this many entries (0 = all of them)
-    uint32_t stack_lds;    // selects the kernel instance (stack entries in LDS / waves per SIMD), see prt_launch_traverse
-    uint32_t exact_grids;  // host: size k_shade's grid from the bounce's ray count read back during the traversal (big batches)
-    uint32_t steal;        // 8-wide kernel at 5 waves/SIMD: a draining wave with at least this many idle lanes lets them take pending subtrees of its remaining rays (0 = off)
-    uint32_t tail;         // 8-wide kernel: the last `tail` 64-ray granules per resident wave are handed out one at a time
-    uint32_t probe_slot;   // instrumented instance only: this launch's timeline goes to stats[16 + 8 * probe_slot ..] (see PRT_TIMELINE)
-    const uint32_t* perm;  // measurement aid (sort_rays): the 8-wide kernel takes ray perm[i] where it would take ray i (nullptr = identity)
-    uint32_t path_kernel;  // host: 0 = off (default); 1 = a batch of ONE sample with at most path_max paths runs as one launch of the path instance of the 8-wide kernel (below); 2 = any batch of at most path_max paths
-    uint32_t path_max;
-    uint32_t big;          // 8-wide kernel: launches with >= big_min granules per resident wave hand out the front of their bulk `big` chunks per grab (1 = off)
-    uint32_t static_small; // 8-wide kernel: launches of single granules only (< 8 per resident wave) deal them to the waves round-robin instead of through the cursor
-    uint32_t big_min;      // (granules per resident wave)
-    uint32_t big_keep;     // granules per resident wave at the end of the bulk that stay ordinary chunks
-    uint32_t primary_hit;  // host: with compact primary rays, rebuild the primary hit's surface interaction once per pixel (k_primary_hit); 0 = per sample in k_shade (A/B)
 };
 
 // Timeline of one launch of the instrumented 8-wide kernel, in s_memrealtime ticks (100 MHz), 8 words per launch:
@@ -270,19 +245,23 @@ struct PrtRaygenArgs {
 bool prt_launch_raygen(hipStream_t st, PrtRaygenInst inst, const PrtRaygenArgs& a);
 void prt_launch_scan_prims(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                            uint32_t* work, uint32_t max_rays, unsigned long long* stats);
-void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
-                         uint32_t* work, uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4,
-                         const PrtTravTuning& tune, unsigned long long* stats, const PrtPrimary* primary = nullptr);
-// one launch for a whole batch of paths (PrtPathArgs); `work` (cursors + error flags) must have been zeroed on the stream
-void prt_launch_path(hipStream_t st, const DevScene& sc, const PrtPathArgs& pa, uint32_t* work, const PrtTravTuning& tune);
-bool prt_path_kernel_applies(const DevScene& sc, const PrtTravTuning& tune);
-// true if prt_launch_traverse would run the instance that can rebuild compact primary rays (and needs no overflow list)
-bool prt_traverse_takes_primary(const DevScene& sc, const PrtTravTuning& tune);
-int prt_traverse_occupancy(const DevScene& sc, const PrtTravTuning& tune, int* blocks_per_cu, int* vgprs, int* sgprs, int* lds_bytes);
-// name of the traversal kernel instance prt_launch_traverse runs for this scene / these tunables (as tools/isa_count.py names them)
-const char* prt_traverse_instance(const DevScene& sc, const PrtTravTuning& tune);
-void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
-                          uint32_t max_rays, int stack_depth, int variant, unsigned long long* stats);
+// A tree walk of a prepared ray buffer (analytic scan done, hit / hd2 seeded): the launches of prt_plan_walk's plan (prt_walk.h),
+// closest hit, any-hit (prt_occluded, shadow rays) or seeded any-hit alike.
+struct PrtWalkArgs {
+    const DevScene* sc;
+    PrtRayBuf rays;
+    const uint32_t* count;      // the rays to walk, on the device
+    uint32_t* work;             // cursors, error flags, overflow list
+    uint32_t* spill;
+    unsigned long long* stats;  // the instrumented launches
+    const PrtPrimary* primary;  // the PRIM launch (compact primary rays)
+    const PrtTravTuning* tune;  // the caller's tunables (perm, probe_slot); a launch overrides what the plan resolved
+};
+void prt_launch_walk(hipStream_t st, const PrtWalkPlan& plan, const PrtWalkArgs& a);
+// one launch for a whole batch of paths (PrtPathArgs, the plan of a PRT_WALK_PATH request); `work` (cursors + error flags) must
+// have been zeroed on the stream
+void prt_launch_path(hipStream_t st, const PrtWalkPlan& plan, const DevScene& sc, const PrtPathArgs& pa, uint32_t* work, const PrtTravTuning& tune);
+int prt_walk_occupancy(const PrtWalkPlan& plan, int* blocks_per_cu, int* vgprs, int* sgprs, int* lds_bytes);
 // The last-segment route reaches k_shade / k_shade_env / k_shade_tex as this bit of their max_depth argument (a run-time flag:
 // their instances and names stay what they are); max_depth itself is at most PRT_MAX_DEPTH.
 #define PRT_LAST_SEGMENT_FLAG 0x80000000u
@@ -345,9 +324,6 @@ void prt_launch_pack_occlusion_rays(hipStream_t st, uint32_t n, const float* o, 
                                     const PrtRayBuf& out, uint32_t* counts);
 void prt_launch_scan_prims_bounded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
                                    uint32_t* work, uint32_t max_rays);
-void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr, uint32_t* work,
-                         uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune,
-                         bool seeded = false);  // seeded: the SEEDED instances (a closest-hit walk's buffer, every ray walked)
 void prt_launch_occlusion_bytes(hipStream_t st, const DevScene& sc, uint32_t n, const PrtRayBuf& in, const float* tmax,
                                 uint8_t* out);
 void prt_launch_scatter_test(hipStream_t st, const DevScene& sc, uint32_t n, const float* in_d, const PrtHit* hits,

@@ -4188,264 +4188,104 @@ __global__ void k_reset_cursors(uint32_t* work) {
     if (threadIdx.x < 8u) work[32u * threadIdx.x] = 0u;
 }
 
-bool prt_traverse_takes_primary(const DevScene& sc, const PrtTravTuning& tune) {
-    // the 5-waves instance of the 8-wide kernel, and a tree shallow enough that no ray can reach the overflow list (its
-    // re-traversal reads full ray records).  (The RAW stack_cap: on a scene without a 4-wide tree, where the launchers
-    // ignore the hook (t8_tuning), a set hook still sends bounce 0 down the general route.  Same rays, same hits.)
-    return sc.nodes8 && !sc.n_insts && (tune.wide == 2u || !sc.nodes4) && (tune.stack_lds == 0u || tune.stack_lds == 6u) &&
-           tune.stack_cap == 0u && sc.depth8 <= 9u;
+// The tree walk.  Which instances a walk launches, with which grid and tunables, is prt_plan_walk's (prt_walk.h); these only
+// follow the plan.  A launch's tunables: the caller's, with what the plan resolved.
+static PrtTravTuning walk_tuning(const PrtTravTuning& in, const PrtWalkLaunch& l) {
+    PrtTravTuning t = in;
+    t.exit_max = l.exit_max, t.tri_min = l.tri_min, t.stack_cap = l.stack_cap, t.steal = l.steal;
+    if (!l.keep_perm) t.perm = nullptr;
+    return t;
 }
 
-// Which traversal kernel instance prt_launch_traverse runs for this scene and these tunables: ONE decision, shared by the
-// launch, the occupancy report and prt_kernel_instance (bench.py names the instance in its line and takes the loops'
-// static instruction counts of exactly that instance).
-//   inst12_4waves  placed mesh copies: two-level walk, 12 stack entries, 4 waves per SIMD
-//   wide11_5waves  A/B (stack_lds = 5): 11 entries, 5 waves per SIMD, ray and best hit in registers
-//   lean8_5waves   default: 8 entries, 5 waves per SIMD (ray and best hit in LDS); trees of <= 9 levels, and deeper
-//                  HOST-built trees, whose rare deeper rays go through the overflow list to the 4-wide tree (C5)
-//   deep15_4waves  deeper trees without a 4-wide fallback (device-built): 15 entries, 4 waves per SIMD
-enum PrtT8Kind { T8_NONE = 0, T8_INST12_4, T8_WIDE11_5, T8_LEAN8_5, T8_DEEP15_4 };
-// Without a 4-wide tree (device-built and refitted scenes) nothing re-walks the rays of the overflow list, so a forced
-// instance whose stack the tree's depth exceeds (stack_lds 5 beyond 12 levels, 6 beyond 9) is not taken: the choice falls
-// back to the default's, and the launchers ignore the stack_cap test hook (t8_tuning).  Such scenes have at most 16 levels
-// (the device builders stop at 15, prt_refit_meshes refuses deeper trees), which deep15_4waves holds.
-static PrtT8Kind t8_kind(const DevScene& sc, const PrtTravTuning& tune) {
-    if (!((tune.wide == 2u || sc.n_insts || !sc.nodes4) && sc.nodes8)) return T8_NONE;
-    if (sc.n_insts) return T8_INST12_4;
-    const bool rewalk = sc.nodes4 != nullptr;
-    if (tune.stack_lds == 5u && (rewalk || sc.depth8 <= 12u)) return T8_WIDE11_5;
-    const bool lean = (tune.stack_lds == 0u || tune.stack_lds == 6u) && (rewalk || sc.depth8 <= 9u);
-    return lean ? T8_LEAN8_5 : T8_DEEP15_4;
+// A row of the 8-wide list crossed with the launch's form: the any-hit kernels, or the closest hit with STATS and, on the LEAN
+// row only, PRIM (bounce 0 of a batch whose k_raygen stored compact primary rays).
+template <int L, int W, bool IN, bool LN>
+static void launch_walk8(hipStream_t st, const PrtWalkLaunch& l, const PrtWalkArgs& a, const PrtTravTuning& tune) {
+    const dim3 grid(l.grid), block(256);
+    const PrtRayBuf& in = a.rays;
+    unsigned long long* stats = l.stats ? a.stats : nullptr;
+#define PRT_WALK8_ARGS *a.sc, in.o, in.d, in.hit, in.hd2, a.count, a.work, a.work + 512, tune
+    if (l.form == PRT_WALK_SEEDED) hipLaunchKernelGGL((k_occluded8_seeded<L, W, IN, LN>), grid, block, 0, st, PRT_WALK8_ARGS);
+    else if (l.form == PRT_WALK_ANY) hipLaunchKernelGGL((k_occluded8_persistent<L, W, IN, LN>), grid, block, 0, st, PRT_WALK8_ARGS);
+    else if (LN && l.prim) {
+        if constexpr (LN) {  // (no PRIM instance of another row exists)
+            if (stats) hipLaunchKernelGGL((k_traverse8_persistent<L, W, true, IN, LN, true>), grid, block, 0, st, PRT_WALK8_ARGS, stats, *a.primary, PrtPathArgs{});
+            else hipLaunchKernelGGL((k_traverse8_persistent<L, W, false, IN, LN, true>), grid, block, 0, st, PRT_WALK8_ARGS, stats, *a.primary, PrtPathArgs{});
+        }
+    } else if (stats) hipLaunchKernelGGL((k_traverse8_persistent<L, W, true, IN, LN>), grid, block, 0, st, PRT_WALK8_ARGS, stats, PrtPrimary{}, PrtPathArgs{});
+    else hipLaunchKernelGGL((k_traverse8_persistent<L, W, false, IN, LN>), grid, block, 0, st, PRT_WALK8_ARGS, stats, PrtPrimary{}, PrtPathArgs{});
+#undef PRT_WALK8_ARGS
 }
-static PrtTravTuning t8_tuning(const DevScene& sc, PrtTravTuning tune) {
-    if (!sc.nodes4 && !sc.n_insts) tune.stack_cap = 0u;
-    return tune;
-}
-const char* prt_traverse_instance(const DevScene& sc, const PrtTravTuning& tune) {
-    switch (t8_kind(sc, tune)) {
-        case T8_INST12_4: return "inst12_4waves";
-        case T8_WIDE11_5: return "wide11_5waves";
-        case T8_LEAN8_5: return "lean8_5waves";
-        case T8_DEEP15_4: return "deep15_4waves";
-        default: return tune.wide ? "bvh4" : "bvh2";
+
+static void launch_walk_row(hipStream_t st, const PrtWalkLaunch& l, const PrtWalkArgs& a) {
+    const PrtTravTuning tune = walk_tuning(*a.tune, l);
+    const dim3 grid(l.grid), block(256);
+    const PrtRayBuf& in = a.rays;
+    uint32_t* ovf = a.work + 512;  // [0] = count, [1..] = ray slots that overflowed the LDS stack
+    const uint32_t* count = l.overflow ? ovf : a.count;
+    const uint32_t* list = l.overflow ? ovf + 1 : nullptr;
+    unsigned long long* stats = l.stats ? a.stats : nullptr;
+    if (l.reset) hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, a.work);
+#define PRT_WALK_T_ARGS *a.sc, in.o, in.d, in.hit, in.hd2, count, a.work, a.spill, list, ovf, tune, stats
+#define PRT_WALK_T(KERNEL, L, W, MODE)                                                                          \
+    {                                                                                                           \
+        if (stats) hipLaunchKernelGGL((KERNEL<L, W, MODE, true>), grid, block, 0, st, PRT_WALK_T_ARGS);         \
+        else hipLaunchKernelGGL((KERNEL<L, W, MODE, false>), grid, block, 0, st, PRT_WALK_T_ARGS);              \
+        break;                                                                                                  \
     }
+#define PRT_WALK8_CASE(name, L, W, IN, LN) case PRT_W8_##name: launch_walk8<L, W, IN, LN>(st, l, a, tune); break;
+#define PRT_WALK4_CASE(tag, L, W, MODE) case PRT_W4_##tag: PRT_WALK_T(k_traverse4_persistent, L, W, MODE)
+#define PRT_WALK2_CASE(tag, L, W, MODE) case PRT_W2_##tag: PRT_WALK_T(k_traverse_persistent, L, W, MODE)
+#define PRT_INTERSECT_CASE(tag, S, V)                                                                                         \
+    case PRT_WI_##tag:                                                                                                        \
+        if (stats) hipLaunchKernelGGL((k_intersect<S, true, V>), grid, block, 0, st, *a.sc, in.o, in.d, in.hit, a.count, stats);  \
+        else hipLaunchKernelGGL((k_intersect<S, false, V>), grid, block, 0, st, *a.sc, in.o, in.d, in.hit, a.count, stats);       \
+        break;
+    switch (l.row) {
+        PRT_WALK8_ROWS(PRT_WALK8_CASE)
+        PRT_WALK4_ROWS(PRT_WALK4_CASE)
+        PRT_WALK2_ROWS(PRT_WALK2_CASE)
+        PRT_INTERSECT_ROWS(PRT_INTERSECT_CASE)
+        case PRT_WALK_ROWS: break;
+    }
+#undef PRT_INTERSECT_CASE
+#undef PRT_WALK2_CASE
+#undef PRT_WALK4_CASE
+#undef PRT_WALK8_CASE
+#undef PRT_WALK_T
+#undef PRT_WALK_T_ARGS
 }
 
-// What a walk of max_rays rays launches with, closest-hit (prt_launch_traverse) or any-hit (prt_launch_occluded) alike: the
-// kind, the tunables with their "auto" values resolved, the grid, and for the 8-wide instances the 5-wave grid and tunables,
-// the stack entries and whether the overflow list is re-walked.
-struct T8Launch {
-    PrtT8Kind kind;
-    PrtTravTuning tune, t5;  // t5: the lean instance's (5 waves per SIMD)
-    uint32_t grid, grid5;    // grid5: 5 instead of 4 resident blocks per CU
-    uint32_t stack_l;
-    bool rewalk;             // overflow list -> the spill-capable 4-wide instance
-};
-static T8Launch t8_resolve(const DevScene& sc, const PrtTravTuning& tune_in, uint32_t max_rays) {
-    T8Launch r;
-    r.kind = t8_kind(sc, tune_in);
-    r.tune = t8_tuning(sc, tune_in);
-    // exit_max "auto" (0xFFFFFFFF, the context's default): the two-level instance leaves its node loop at <= 32 walkers
-    // (its lanes wait for level switches that the wave does together; C5I +4.4 % against 16, gpurun_out/r3_sweep_C5I_b.log),
-    // every other instance at <= 16
-    if (r.tune.exit_max == 0xFFFFFFFFu) r.tune.exit_max = r.kind == T8_INST12_4 ? 32u : 16u;
-    // tri_min "auto" (0, the context's default): a triangle phase starts after 24 queueing lane-steps, but after 12 on one-level
-    // trees far beyond the caches (one node per 128-B line: C5 +1.7 %; 16: +0.8 to +1.9 %), whose walks gain more from an earlier
-    // culling bound than a phase's fixed part costs.  On trees the caches hold 12 / 16 cost 0.5-2 % (C2, C3), and the two-level
-    // instance at its exit_max of 32 is best at 24 too (16: -1.5 %).  tools/sweep.py, TUNING.md
-    if (r.tune.tri_min == 0u) r.tune.tri_min = (r.kind != T8_INST12_4 && sc.node_stride == 8u) ? 12u : 24u;
-    uint32_t g = r.tune.grid_blocks;
-    const uint32_t need_blocks = blocks_for(max_rays);
-    if (g > need_blocks) g = need_blocks;
-    if (g == 0) g = 1;
-    r.grid = g;
-    r.grid5 = g == r.tune.grid_blocks ? g + g / 4u : g;
-    r.stack_l = r.kind == T8_INST12_4 ? 12u : r.kind == T8_WIDE11_5 ? 11u : r.kind == T8_LEAN8_5 ? 8u : 15u;
-    // (the two-level instance has no overflow list: a stack overflow is an error, the host checks the depths)
-    const bool overflow = r.kind != T8_INST12_4 && (r.tune.stack_cap != 0u || sc.depth8 > r.stack_l + 1u);
-    r.t5 = r.tune;
-    if (overflow) r.t5.steal = 0u;  // (a helper cannot hand a ray to the overflow list)
-    r.rewalk = overflow && sc.nodes4;
-    return r;
-}
-
-void prt_launch_traverse(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr,
-                         uint32_t* work, uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4,
-                         const PrtTravTuning& tune_in, unsigned long long* stats, const PrtPrimary* primary) {
-    const T8Launch r = t8_resolve(sc, tune_in, max_rays);
-    const PrtTravTuning& tune = r.tune;
+void prt_launch_walk(hipStream_t st, const PrtWalkPlan& plan, const PrtWalkArgs& a) {
 #ifdef PRT_PROBE_REBOUND
-    // diagnostic build (tools/bounce_stats.py --rebound): the instrumented launch is preceded by a plain one that leaves
-    // every ray's FINAL hit distance as its initial culling bound, so the instrumented walk's visit counts are those of a
+    // diagnostic build (tools/bounce_stats.py --rebound): the instrumented walk is preceded by the same plan with stats off, which
+    // leaves every ray's FINAL hit distance as its initial culling bound, so the instrumented walk's visit counts are those of a
     // traversal that knew the answer from the start: the floor for any visiting order / triangle-test schedule
-    if (stats) {
-        prt_launch_traverse(st, sc, in, count_ptr, work, spill, max_rays, tree_depth, stack4, tune_in, nullptr, primary);
-        hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
+    if (plan.launch[0].stats && a.stats && prt_walk_row(plan.launch[0].row).family != 0u) {
+        PrtWalkPlan plain = plan;
+        plain.launch[0].stats = plain.launch[1].stats = false;
+        prt_launch_walk(st, plain, a);
+        hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, a.work);
     }
 #endif
-    const dim3 grid(r.grid), block(256);
-    uint32_t* ovf = work + 512;  // [0] = count, [1..] = ray slots that overflowed the LDS stack
-    const uint32_t* no_list = nullptr;
-#define PRT_LAUNCH_T(KERNEL, L, W, MODE, GRID, COUNT, LIST)                                                        \
-    do {                                                                                                           \
-        if (stats)                                                                                                 \
-            hipLaunchKernelGGL((KERNEL<L, W, MODE, true>), GRID, block, 0, st, sc, in.o, in.d, in.hit, in.hd2,     \
-                               COUNT, work, spill, LIST, ovf, tune, stats);                                        \
-        else                                                                                                       \
-            hipLaunchKernelGGL((KERNEL<L, W, MODE, false>), GRID, block, 0, st, sc, in.o, in.d, in.hit, in.hd2,    \
-                               COUNT, work, spill, LIST, ovf, tune, stats);                                        \
-    } while (0)
-    const PrtT8Kind kind = r.kind;
-    if (kind != T8_NONE) {  // (device-built scenes only have the 8-wide tree)
-        // default: compressed 8-wide tree; a ray needs at most depth8 - 1 stacked node groups.  15 entries at
-        // 4 waves/SIMD or 11 entries at 5 waves/SIMD (tune.stack_lds == 5); deeper rays take the overflow list.
-#define PRT_LAUNCH_8(L, W, IN)                                                                                     \
-    do {                                                                                                           \
-        if (stats)                                                                                                 \
-            hipLaunchKernelGGL((k_traverse8_persistent<L, W, true, IN>), grid, block, 0, st, sc, in.o, in.d,       \
-                               in.hit, in.hd2, count_ptr, work, ovf, tune, stats, PrtPrimary{}, PrtPathArgs{});    \
-        else                                                                                                       \
-            hipLaunchKernelGGL((k_traverse8_persistent<L, W, false, IN>), grid, block, 0, st, sc, in.o, in.d,      \
-                               in.hit, in.hd2, count_ptr, work, ovf, tune, stats, PrtPrimary{}, PrtPathArgs{});    \
-    } while (0)
-        if (kind == T8_INST12_4) {  // placed mesh copies: two-level walk; a stack overflow is an error (the host checks the depths).
-            // 12 stack entries + the lanes' world rays in LDS = the same 40 KB per block as the one-level instance
-            PRT_LAUNCH_8(12, 4, true);
-            return;
-        }
-        // default: the 5-waves-per-SIMD instance (96 VGPRs: ray and best hit live in LDS, 8 stack entries) for trees of
-        // at most 9 levels (C3: 9), else the 4-waves instance with 15 entries (C5: 11 levels); stack_lds 4 / 5 / 6
-        // force one for A/B runs
-        // (deeper host-built trees: rays that need more than 8 entries go through the overflow list to the 4-wide
-        // spill-capable instance; C5, 11 levels: deepest stack 8, no such ray)
-        if (kind == T8_WIDE11_5) {
-            PRT_LAUNCH_8(11, 5, false);
-        } else if (kind == T8_LEAN8_5) {
-            const dim3 grid5(r.grid5);
-            const PrtTravTuning& t5 = r.t5;
-            if (stats && primary)
-                hipLaunchKernelGGL((k_traverse8_persistent<8, 5, true, false, true, true>), grid5, block, 0, st, sc, in.o, in.d,
-                                   in.hit, in.hd2, count_ptr, work, ovf, t5, stats, *primary, PrtPathArgs{});
-            else if (stats)
-                hipLaunchKernelGGL((k_traverse8_persistent<8, 5, true, false, true>), grid5, block, 0, st, sc, in.o, in.d,
-                                   in.hit, in.hd2, count_ptr, work, ovf, t5, stats, PrtPrimary{}, PrtPathArgs{});
-            else if (primary)  // bounce 0 of a batch whose k_raygen stored compact primary rays
-                hipLaunchKernelGGL((k_traverse8_persistent<8, 5, false, false, true, true>), grid5, block, 0, st, sc, in.o, in.d,
-                                   in.hit, in.hd2, count_ptr, work, ovf, t5, stats, *primary, PrtPathArgs{});
-            else
-                hipLaunchKernelGGL((k_traverse8_persistent<8, 5, false, false, true>), grid5, block, 0, st, sc, in.o, in.d,
-                                   in.hit, in.hd2, count_ptr, work, ovf, t5, stats, PrtPrimary{}, PrtPathArgs{});
-        } else {
-            PRT_LAUNCH_8(15, 4, false);
-        }
-#undef PRT_LAUNCH_8
-        // overflow list -> the spill-capable 4-wide instance.  Not launched when the tree is too shallow for any ray to
-        // overflow (C3: 9 levels = 8 stacked groups at most): two tiny launches and their gaps are ~12 us per bounce
-        if (r.rewalk) {
-            hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
-            PRT_LAUNCH_T(k_traverse4_persistent, 27, 5, 1, dim3(8), ovf, ovf + 1);
-        }
-    } else if (tune.wide) {
-        if (stack4 <= 22 && tune.stack_lds == 24) PRT_LAUNCH_T(k_traverse4_persistent, 22, 6, 0, grid, count_ptr, no_list);
-        else if (stack4 <= 27) PRT_LAUNCH_T(k_traverse4_persistent, 27, 5, 0, grid, count_ptr, no_list);
-        else if (tune.stack_lds == 39 && stack4 <= 35) PRT_LAUNCH_T(k_traverse4_persistent, 35, 4, 0, grid, count_ptr, no_list);
-        else if (tune.stack_lds == 2) {
-            // A/B: LDS-only stack with overflow check, then the spill-capable instance over the (normally empty)
-            // overflow list.  Measured equal to the always-spill instance on C3, which is therefore the default.
-            PRT_LAUNCH_T(k_traverse4_persistent, 27, 5, 2, grid, count_ptr, no_list);
-            hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
-            PRT_LAUNCH_T(k_traverse4_persistent, 27, 5, 1, dim3(8), ovf, ovf + 1);
-        } else if (tune.stack_lds == 3) {
-            // branch-free node step on an LDS-only stack of 25 entries (+3 rows of slack), overflow list -> MODE 1
-            PRT_LAUNCH_T(k_traverse4_persistent, 24, 5, 3, grid, count_ptr, no_list);
-            hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
-            PRT_LAUNCH_T(k_traverse4_persistent, 27, 5, 1, dim3(8), ovf, ovf + 1);
-        } else if (tune.stack_lds == 1) {
-            PRT_LAUNCH_T(k_traverse4_persistent, 27, 5, 1, grid, count_ptr, no_list);  // A/B: 28 entries in LDS + global spill
-        } else {
-            // default: branch-free node step, LDS-only stack of 32 entries (the deepest stack any C3 ray reaches is 17;
-            // the host's worst-case bound is 36), 4 waves/SIMD so that the 116 VGPRs need no scratch (the 5-wave
-            // instances spill 50-70 B/lane and are 9 % slower); a ray that would overflow goes to the overflow list
-            // and is re-traversed by the spill-capable instance.
-            PRT_LAUNCH_T(k_traverse4_persistent, 32, 4, 3, grid, count_ptr, no_list);
-            hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
-            PRT_LAUNCH_T(k_traverse4_persistent, 27, 5, 1, dim3(8), ovf, ovf + 1);
-        }
-    } else {
-        const uint32_t pushes = tree_depth ? tree_depth - 1u : 0u;
-        if (pushes <= 24 && tune.stack_lds == 24) PRT_LAUNCH_T(k_traverse_persistent, 24, 6, 0, grid, count_ptr, no_list);
-        else if (pushes <= 31) PRT_LAUNCH_T(k_traverse_persistent, 31, 5, 0, grid, count_ptr, no_list);
-        else PRT_LAUNCH_T(k_traverse_persistent, 31, 5, 1, grid, count_ptr, no_list);
-    }
-#undef PRT_LAUNCH_T
+    for (uint32_t i = 0; i < plan.n; ++i) launch_walk_row(st, plan.launch[i], a);
 }
 
-// The any-hit walk behind prt_occluded, on a buffer that k_pack_occlusion_rays + k_scan_prims_bounded prepared: the instance
-// t8_kind picks for the closest-hit walk, in its any-hit form, with the same tunables and the same overflow list (its rays
-// are re-walked by the 4-wide closest-hit instance from their seeded bound, which answers the query as well).  Scenes
-// without the 8-wide tree (or with another one forced): the closest-hit walk from the seeded bound.
-void prt_launch_occluded(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr, uint32_t* work,
-                         uint32_t* spill, uint32_t max_rays, uint32_t tree_depth, uint32_t stack4, const PrtTravTuning& tune_in, bool seeded) {
-    if (t8_kind(sc, tune_in) == T8_NONE) {
-        prt_launch_traverse(st, sc, in, count_ptr, work, spill, max_rays, tree_depth, stack4, tune_in, nullptr);
-        return;
-    }
-    PrtTravTuning tune_o = tune_in;
-    tune_o.perm = nullptr;
-    const T8Launch r = t8_resolve(sc, tune_o, max_rays);
-    const dim3 block(256);
-    uint32_t* ovf = work + 512;
-#define PRT_LAUNCH_O(L, W, IN, LN, GRID, TUNE)                                                                                 \
-    do {                                                                                                                       \
-        if (seeded)                                                                                                            \
-            hipLaunchKernelGGL((k_occluded8_seeded<L, W, IN, LN>), dim3(GRID), block, 0, st, sc, in.o, in.d, in.hit,           \
-                               in.hd2, count_ptr, work, ovf, TUNE);                                                            \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((k_occluded8_persistent<L, W, IN, LN>), dim3(GRID), block, 0, st, sc, in.o, in.d, in.hit,        \
-                               in.hd2, count_ptr, work, ovf, TUNE);                                                            \
-    } while (0)
-    // (two-level: a stack overflow is an error; prt_synchronize / the host form report it)
-    if (r.kind == T8_INST12_4) PRT_LAUNCH_O(12, 4, true, false, r.grid, r.tune);
-    else if (r.kind == T8_WIDE11_5) PRT_LAUNCH_O(11, 5, false, false, r.grid, r.tune);
-    else if (r.kind == T8_LEAN8_5) PRT_LAUNCH_O(8, 5, false, true, r.grid5, r.t5);
-    else PRT_LAUNCH_O(15, 4, false, false, r.grid, r.tune);
-#undef PRT_LAUNCH_O
-    if (r.rewalk) {
-        hipLaunchKernelGGL(k_reset_cursors, dim3(1), dim3(64), 0, st, work);
-        hipLaunchKernelGGL((k_traverse4_persistent<27, 5, 1, false>), dim3(8), block, 0, st, sc, in.o, in.d, in.hit, in.hd2,
-                           ovf, work, spill, ovf + 1, ovf, r.tune, (unsigned long long*)nullptr);
-    }
+// The PATH instance (PrtPathArgs): whole paths in one launch, for small batches.  (The deep15 row is the only one with one.)
+void prt_launch_path(hipStream_t st, const PrtWalkPlan& plan, const DevScene& sc, const PrtPathArgs& pa, uint32_t* work, const PrtTravTuning& tune_in) {
+    const PrtTravTuning tune = walk_tuning(tune_in, plan.launch[0]);
+    hipLaunchKernelGGL((k_traverse8_persistent<15, 4, false, false, false, false, true>), dim3(plan.launch[0].grid), dim3(256), 0, st, sc,
+                       (const float4*)nullptr, (const float4*)nullptr, (uint32_t*)nullptr, (const float*)nullptr, (const uint32_t*)nullptr, work,
+                       work + 512, tune, (unsigned long long*)nullptr, PrtPrimary{}, pa);
 }
 
-// The PATH instance (PrtPathArgs): whole paths in one launch, for small batches.  One-level scenes with the 8-wide tree,
-// a tree its 15-entry stack holds, and no primitive BVH (classify_ray's walk keeps a per-thread LDS stack of its own).
-// (The RAW stack_cap here too: a set hook selects the pipeline, also where t8_tuning makes the launchers ignore it.)
-bool prt_path_kernel_applies(const DevScene& sc, const PrtTravTuning& tune) {
-    return sc.nodes8 && !sc.n_insts && !sc.abvh_nodes && sc.depth8 <= 16u && tune.wide == 2u && tune.stack_cap == 0u;
-}
-void prt_launch_path(hipStream_t st, const DevScene& sc, const PrtPathArgs& pa, uint32_t* work, const PrtTravTuning& tune_in) {
-    PrtTravTuning tune = tune_in;
-    if (tune.exit_max == 0xFFFFFFFFu) tune.exit_max = 16u;
-    if (tune.tri_min == 0u) tune.tri_min = 24u;
-    uint32_t g = tune.grid_blocks;
-    const uint32_t need_blocks = blocks_for(pa.n_paths);
-    if (g > need_blocks) g = need_blocks;
-    if (g == 0) g = 1;
-    hipLaunchKernelGGL((k_traverse8_persistent<15, 4, false, false, false, false, true>), dim3(g), dim3(256), 0, st, sc, (const float4*)nullptr,
-                       (const float4*)nullptr, (uint32_t*)nullptr, (const float*)nullptr, (const uint32_t*)nullptr, work, work + 512, tune,
-                       (unsigned long long*)nullptr, PrtPrimary{}, pa);
-}
-
-// Static occupancy of the default traversal kernel instance for this scene (what the wavefront-occupancy figure of
-// the bench line is computed from): resident 256-thread blocks per CU by the runtime's occupancy calculator, and the
-// kernel's register / LDS footprint.
-int prt_traverse_occupancy(const DevScene& sc, const PrtTravTuning& tune, int* blocks_per_cu, int* vgprs, int* sgprs, int* lds_bytes) {
-    const PrtT8Kind kind = t8_kind(sc, tune);
-    const void* fn = kind == T8_INST12_4 ? (const void*)k_traverse8_persistent<12, 4, false, true>
-                     : kind == T8_WIDE11_5 ? (const void*)k_traverse8_persistent<11, 5, false, false>
-                     : kind == T8_LEAN8_5 ? (const void*)k_traverse8_persistent<8, 5, false, false, true>
-                     : kind == T8_DEEP15_4 ? (const void*)k_traverse8_persistent<15, 4, false, false>
-                                           : (const void*)k_traverse4_persistent<32, 4, 3, false>;
+// Static occupancy of the instance plan.occupancy names (what the wavefront-occupancy figure of the bench line is computed from):
+// resident 256-thread blocks per CU by the runtime's occupancy calculator, and the kernel's register / LDS footprint.
+int prt_walk_occupancy(const PrtWalkPlan& plan, int* blocks_per_cu, int* vgprs, int* sgprs, int* lds_bytes) {
+    const void* fn = (const void*)k_traverse4_persistent<32, 4, 3, false>;
+#define PRT_WALK8_CASE(name, L, W, IN, LN) if (plan.occupancy == PRT_W8_##name) fn = (const void*)k_traverse8_persistent<L, W, false, IN, LN>;
+    PRT_WALK8_ROWS(PRT_WALK8_CASE)
+#undef PRT_WALK8_CASE
     hipFuncAttributes at;
     hipError_t e = hipFuncGetAttributes(&at, fn);
     if (e != hipSuccess) return (int)e;
@@ -4457,23 +4297,6 @@ int prt_traverse_occupancy(const DevScene& sc, const PrtTravTuning& tune, int* b
     *sgprs = 0;
     *lds_bytes = (int)at.sharedSizeBytes;
     return 0;
-}
-
-// Variants 1 (while-while) and 2 (one-loop): the fused one-thread-per-ray kernel, kept for A/B runs.
-void prt_launch_intersect(hipStream_t st, const DevScene& sc, const PrtRayBuf& in, const uint32_t* count_ptr, uint32_t max_rays, int stack_depth, int variant,
-                          unsigned long long* stats) {
-    const dim3 grid(blocks_for(max_rays)), block(256);
-#define PRT_LAUNCH_I(S, T, V) \
-    hipLaunchKernelGGL((k_intersect<S, T, V>), grid, block, 0, st, sc, in.o, in.d, in.hit, count_ptr, stats)
-    const bool deep = stack_depth > 31;
-    if (stats) {
-        if (variant == 2) { if (deep) PRT_LAUNCH_I(63, true, 1); else PRT_LAUNCH_I(31, true, 1); }
-        else              { if (deep) PRT_LAUNCH_I(63, true, 0); else PRT_LAUNCH_I(31, true, 0); }
-    } else {
-        if (variant == 2) { if (deep) PRT_LAUNCH_I(63, false, 1); else PRT_LAUNCH_I(31, false, 1); }
-        else              { if (deep) PRT_LAUNCH_I(63, false, 0); else PRT_LAUNCH_I(31, false, 0); }
-    }
-#undef PRT_LAUNCH_I
 }
 
 bool prt_launch_shade(hipStream_t st, PrtShadeInst inst, const PrtShadeArgs& a) {

@@ -6,6 +6,8 @@
 #pragma once
 #include <cstdint>
 
+#include "prt_walk.h"  // the tree walk's own facts and plan; prt_route_walk8
+
 // One row per instance: T(argument list of the kernel, kernel, tag, template arguments...).  The tag spells the arguments
 // (f / t per bool) and makes the enumerator.  A family with every combination of 2, 3 or 4 bools is one PRT_ROWSn line, its rows
 // in counting order of the arguments: the plan's index arithmetic relies on that order.
@@ -102,9 +104,9 @@ struct PrtRouteFacts {
     bool variant0;         // variant == 0: the persistent traversal kernels (1, 2: k_intersect, A/B)
     bool compact_primary;  // the compact_primary switch
     bool primary_walk;     // the primary_walk switch
-    bool takes_primary;    // prt_traverse_takes_primary(dsc, tune)
+    bool takes_primary;    // prt_traverse_takes_primary(walk facts)
     bool primary_hit;      // tune.primary_hit != 0
-    bool path_gate;        // !trav_stats && !d_shade_div && sort_rays == 0 && n_paths <= tune.path_max && prt_path_kernel_applies(dsc, tune)
+    bool path_gate;        // !trav_stats && !d_shade_div && sort_rays == 0 && n_paths <= tune.path_max && prt_path_kernel_applies(walk facts)
     uint32_t path_kernel;  // tune.path_kernel: 0 off, 1 batches of one sample, 2 any batch
     uint32_t fuse;         // tune.fuse
     // the last segment of a path as a visibility query (DESIGN.md section 3 "The last segment")
@@ -119,7 +121,7 @@ struct PrtRoutePlan {
     bool compact;      // compact primary rays (PrtPrimary): bounce 0 rebuilds its rays from the pixel records
     bool walk;         // bounce 0 walks one ray per front pixel
     bool primary_hit;  // k_primary_hit runs between bounce 0's walk and its shade
-    bool walk8;        // a tree walk is prt_launch_traverse / prt_launch_occluded (false: k_intersect, variants 1 and 2)
+    bool walk8;        // a tree walk runs the persistent kernels (false: k_intersect, variants 1 and 2): prt_route_walk8
     uint32_t fuse;     // k_shade's fuse_max
     PrtRaygenInst raygen;
     PrtShadeInst shade0, shade;  // bounce 0, later bounces
@@ -128,10 +130,6 @@ struct PrtRoutePlan {
                             // analytic scan decides what the film gets, and the last shade launch does not rebuild a triangle hit;
                             // 2: and the last walk is the seeded any-hit walk (k_occluded8_seeded)
 };
-
-// Whether a tree walk runs the persistent kernels (prt_launch_traverse / prt_launch_occluded) or, with variant 1 or 2 forced,
-// k_intersect: placed copies and device-built trees (no binary tree) have the 8-wide kernel only.
-inline bool prt_route_walk8(bool variant0, bool insts, bool has_bvh2) { return variant0 || insts || !has_bvh2; }
 
 inline PrtRoutePlan prt_plan_route(const PrtRouteFacts& f) {
     PrtRoutePlan p{};

@@ -26,7 +26,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "parallelraytracing_amd", "csrc")
 
-# template arguments <STACK_L, WAVES, STATS, INST, LEAN, PRIM> as they appear in the mangled names
+# template arguments <STACK_L, WAVES, STATS, INST, LEAN, PRIM, PATH> as they appear in the mangled names: the rows of PRT_WALK8_ROWS
+# (csrc/prt_walk.h), plain closest hit; tests/test_walk_table.py holds every entry to the row of its name
 INSTANCES = {
     "lean8_5waves": "k_traverse8_persistentILi8ELi5ELb0ELb0ELb1ELb0ELb0EE",        # default: trees of <= 9 levels (C2, C3, C4)
     "lean8_5waves_primary": "k_traverse8_persistentILi8ELi5ELb0ELb0ELb1ELb1ELb0EE",  # the same reading compact primary rays (bounce 0)
