@@ -1167,6 +1167,13 @@ int prt_instance_name(uint32_t stage, uint32_t index, char* name, uint32_t capac
  * and, if front_rays is not NULL, the number of rays that batch handed to its last tree walk (segment max_depth - 1; 0 after
  * a batch on the path-kernel route).  Reading the count waits for the context's stream. */
 int prt_last_segment(PrtContext* ctx, uint32_t* active, uint32_t* front_rays);
+/* The primary stage of a still camera (DESIGN.md section 2 "One walk per pixel"): without jitter and without a lens what a
+ * batch computes before its first shade launch (k_raygen, the bounce-0 walk, k_primary_hit) does not depend on the sample
+ * index or the seed, so the context keeps it and a batch with the same camera, scene, film, batch size, max_depth and route
+ * starts at its first shade launch.  *active: 1 if the context's last batch did, 0 if it rebuilt the stage (or took another
+ * route); *reused_batches (may be NULL): the batches that did since the context was created.  The film never depends on it;
+ * prt_set_param("primary_reuse", 0) makes every batch rebuild the stage. */
+int prt_primary_reuse(PrtContext* ctx, uint32_t* active, uint32_t* reused_batches);
 /* Copies the built BVH out (host arrays): nodes n_nodes*16 floats (layout: csrc/bvh.h), tris
  * n_triangles*12 floats in leaf order.  Either pointer may be NULL.  Works on host-only contexts. */
 int prt_bvh_read(PrtContext* ctx, float* nodes, float* tris);
@@ -1189,7 +1196,8 @@ int prt_set_variant(PrtContext* ctx, int variant);
  * the coordinates' magnitude, default 18; A/B only), "last_segment" (the last segment of a path in scenes without emissive
  * triangles, prt_last_segment: 0 = walked and shaded like any other; 1 = it ends in the shade launch that produces it where
  * the analytic scan alone decides what the film gets; 2, default = 1, and the rays still walked get the any-hit walk seeded
- * with their analytic hit), "denoise_lds" (which iterations of the denoiser stage their block's footprint in LDS: 0 = none, 1, default = step 1,
+ * with their analytic hit), "primary_reuse" (1, default: a still camera's primary stage is kept across batches and calls,
+ * prt_primary_reuse; 0 = every batch rebuilds it; setting ANY tunable makes the next batch rebuild it), "denoise_lds" (which iterations of the denoiser stage their block's footprint in LDS: 0 = none, 1, default = step 1,
  * 2 = steps 1 and 2; A/B), "feature_chunk" / "radiance_chunk" (samples per chunk of the sampled feature pass / of prt_radiance; 0, default = by
  * the ray budget).  Results never depend on a tunable.  Unknown names / bad values
  * return PRT_ERR_INVALID. */

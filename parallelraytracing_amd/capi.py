@@ -365,6 +365,7 @@ SIGNATURES = {
     "prt_batch_instance": (C.c_int, [_vp, C.c_uint32, C.c_char_p, C.c_uint32]),
     "prt_instance_name": (C.c_int, [C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32]),
     "prt_last_segment": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "prt_primary_reuse": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "prt_measure_shade_divergence": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "prt_refit_meshes": (C.c_int, [_vp, C.POINTER(PrtMesh), C.c_uint32]),
     "prt_set_instance_transforms": (C.c_int, [_vp, C.POINTER(PrtInstance), C.c_uint32, C.c_uint32]),

@@ -29,6 +29,7 @@
 #include "prt_feature_samples.h"
 #include "prt_features.h"
 #include "prt_kernels.h"
+#include "prt_primary_cache.h"
 #include "prt_radiance.h"
 #include "prt_scene.h"
 #include "prt_temporal.h"
@@ -151,6 +152,21 @@ struct PrtContext {
     uint32_t* d_work = nullptr;   // chunk cursor of the persistent traversal kernel
     float4* d_pix = nullptr;      // compact primary rays: one record per local pixel (PrtPrimary)
     uint32_t pix_entries = 0;
+    // ---- the primary stage of a still camera, kept across batches and calls (prt_primary_cache.h) ----
+    // What k_raygen, the bounce-0 walk and k_primary_hit leave behind on the compact route, besides d_pix and bounce 0's words
+    // of d_counts: the path-id list (4 B per path; in rb[0].t it would be overwritten by bounce 2's rays), the front-pixel list
+    // and the walk's hits (4 B per local pixel each; in rb[0].hd2 / .hit likewise).  Nothing after the first k_shade writes them.
+    uint32_t* d_prim_pid = nullptr;
+    uint32_t* d_prim_list = nullptr;
+    uint32_t* d_prim_hit = nullptr;
+    uint64_t prim_pid_entries = 0;
+    uint32_t prim_pix_entries = 0;
+    PrtPrimaryKey primary_key{};        // what the buffers hold (valid = false: nothing)
+    uint64_t camera_gen = 1, scene_gen = 1;  // PrtPrimaryKey: bumped by every setter that can change what the stage computes
+    uint32_t primary_counts[2] = {0u, 0u};   // bounce 0's front / back ray counts as the host read them at the refresh (exact grids)
+    int primary_reuse = 1;              // prt_set_param("primary_reuse", 0): every batch rebuilds its primary stage (A/B)
+    uint32_t primary_reuse_active = 0;  // the last run_batch started at its first k_shade (prt_primary_reuse)
+    uint32_t primary_reused_batches = 0;  // batches that did, since the context was created
     DevBuf spill;                 // global part of the per-lane traversal stacks (uint32_t entries)
 
     // ---- light sampling (PrtLighting, include/prt.h) ----
@@ -383,6 +399,42 @@ int ensure_path_state(PrtContext* c, uint64_t n_paths) {
     }
     HIPCHECK(c, hipMalloc((void**)&c->d_rad, n * sizeof(float4)));
     c->cap_paths = n;
+    return PRT_OK;
+}
+
+// A setter changed what a batch's primary stage computes from (PrtPrimaryKey, prt_primary_cache.h).
+void touch_scene(PrtContext* c) { ++c->scene_gen; }
+void touch_camera(PrtContext* c) { ++c->camera_gen; }
+
+void free_primary_state(PrtContext* c) {
+    free_dev(c->d_prim_pid);
+    free_dev(c->d_prim_list);
+    free_dev(c->d_prim_hit);
+    c->prim_pid_entries = 0;
+    c->prim_pix_entries = 0;
+    c->primary_key.valid = false;
+}
+
+// The persistent primary buffers of the compact route (sized with the path state; they only grow, and growing drops what they held)
+int ensure_primary_state(PrtContext* c, uint64_t n_paths, uint32_t n_pix_local) {
+    if (n_paths > c->prim_pid_entries) {
+        c->primary_key.valid = false;
+        free_dev(c->d_prim_pid);
+        c->prim_pid_entries = 0;
+        const uint64_t n = std::max<uint64_t>(n_paths, 256);
+        HIPCHECK(c, hipMalloc((void**)&c->d_prim_pid, n * sizeof(uint32_t)));
+        c->prim_pid_entries = n;
+    }
+    if (n_pix_local > c->prim_pix_entries) {
+        c->primary_key.valid = false;
+        free_dev(c->d_prim_list);
+        free_dev(c->d_prim_hit);
+        c->prim_pix_entries = 0;
+        const uint32_t n = std::max<uint32_t>(n_pix_local, 256u);
+        HIPCHECK(c, hipMalloc((void**)&c->d_prim_list, (size_t)n * sizeof(uint32_t)));
+        HIPCHECK(c, hipMalloc((void**)&c->d_prim_hit, (size_t)n * sizeof(uint32_t)));
+        c->prim_pix_entries = n;
+    }
     return PRT_OK;
 }
 
@@ -758,6 +810,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     if (view.list && !c->d_film_stat) return fail(c, PRT_ERR_INVALID, "a tile list needs film statistics");
     const uint64_t n_paths64 = (uint64_t)S_cur * tm.n_pix_local;
     c->batch_walked = false;
+    c->primary_reuse_active = 0u;
     if (n_paths64 == 0) return PRT_OK;
     if (n_paths64 > 0xFFFFFF00ull) return fail(c, PRT_ERR_INVALID, "too many paths in flight");
     const uint32_t n_paths = (uint32_t)n_paths64;
@@ -854,15 +907,48 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         ++c->stats.intersect_launches;
         return accumulate_batch();
     }
-    // front/back counters of every bounce start at zero (the producers add to them atomically)
-    HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
     if (compact && c->pix_entries < tm.n_pix_local) {
         free_dev(c->d_pix);
         c->pix_entries = 0;
+        c->primary_key.valid = false;
         HIPCHECK(c, hipMalloc((void**)&c->d_pix, 4 * (size_t)tm.n_pix_local * sizeof(float4)));
         c->pix_entries = tm.n_pix_local;
         c->pix_records_blank = false;
     }
+    // The primary stage of a still camera (prt_primary_cache.h): on the compact route everything before the
+    // first k_shade is a function of camera, scene, tile map, batch size, max_depth and route, so a batch whose key equals the
+    // held one starts at its first k_shade (REUSE); every other batch runs k_raygen (REFRESH) and, if eligible, leaves a key.
+    // The stage lives where no later bounce writes: d_pix, bounce 0's words of d_counts, and the persistent buffers, which stand
+    // in for rb[0].t / .hd2 / .hit where the hits are per list slot (one walk per pixel; a batch of ONE sample, whose path slots
+    // are that list: at most n_pix_local of them).  One walk per SAMPLE of a multi-sample batch (primary_walk = 0) has a hit per
+    // path slot: it keeps rb[0] and is never reused.
+    const bool instrumented = trav_stats != nullptr || c->d_shade_div != nullptr;
+    const bool persistent = compact && (walk || S_cur == 1u);
+    if (persistent && (rc = ensure_primary_state(c, n_paths, tm.n_pix_local))) return rc;
+    PrtRayBuf rb0 = c->rb[0];
+    if (persistent) rb0.t = (float4*)c->d_prim_pid, rb0.hd2 = (float*)c->d_prim_list, rb0.hit = c->d_prim_hit;
+    PrtPrimaryKey now{};
+    now.valid = persistent && c->primary_reuse != 0 && !instrumented;  // eligible (compact: no jitter, no lens, no tile list)
+    if (now.valid) {
+        const PrtWalkPlan wp0 = prt_plan_walk(walk_facts(c, c->tune, PRT_WALK_CLOSEST, walk ? tm.n_pix_local : n_paths, false, true));
+        now.camera_gen = c->camera_gen, now.scene_gen = c->scene_gen;
+        now.W = tm.W, now.H = tm.H, now.rank = tm.rank, now.world = tm.world, now.n_pix_local = tm.n_pix_local;
+        now.S_cur = S_cur, now.max_depth = max_depth;
+        now.plan = plan;
+        now.walk_row = (uint32_t)wp0.launch[0].row, now.walk_prim = wp0.launch[0].prim;
+        now.compact = compact, now.walk = walk, now.primary_hit = plan.primary_hit, now.lens = f.lens, now.jitter = f.jitter;
+        now.rr_depth = c->sampling.rr_depth, now.clamp = c->sampling.clamp;
+        now.listed = view.list != nullptr, now.instrumented = instrumented, now.exact = exact;
+    }
+    const bool reuse = prt_primary_reusable(c->primary_key, now);
+    c->primary_reuse_active = reuse ? 1u : 0u;
+    if (reuse) ++c->primary_reused_batches;
+    // front/back counters of every bounce start at zero (the producers add to them atomically).  REUSE: from bounce 1's stride.
+    // Bounce 0's words are written by k_raygen alone (front, back, finished, list; k_shade of bounce d adds to bounce d + 1's,
+    // and word 48, the shadow rays, belongs to the lighting modes, which are never compact) and read by the bounce-0 walk,
+    // k_primary_hit and the first k_shade: they stand as the refresh left them.
+    if (reuse) HIPCHECK(c, hipMemsetAsync(c->d_counts + PRT_CNT_STRIDE, 0, (size_t)max_depth * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
+    else HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
     const DevLights lt = dev_lights(c);
     const DevMeshLights mlt = dev_mesh_lights(c);
     const DevLightClusters lct = dev_light_clusters(c);
@@ -871,27 +957,34 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         HIPCHECK(c, hipMemsetAsync(c->lb.lrad, 0, (size_t)n_paths * sizeof(float4), c->stream));
     }
     // One walk per pixel (PrtPrimary): bounce 0's traversal runs over the list of front pixels that k_raygen writes into
-    // rb[0].hd2, counted in word PRT_CNT_LIST of bounce 0's counters (zeroed above), and leaves its hits in rb[0].hit per list
+    // rb0.hd2, counted in word PRT_CNT_LIST of bounce 0's counters (zeroed above), and leaves its hits in rb0.hit per list
     // slot.  A batch of ONE sample keeps its path slots: they ARE that list (one path per pixel, in the same order), and
     // k_raygen saves the second store and atomic.
     c->batch_walked = walk;
-    const PrtPrimary primary{(const uint32_t*)c->rb[0].t, c->d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, tm.n_pix_local,
+    const PrtPrimary primary{(const uint32_t*)rb0.t, c->d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, tm.n_pix_local,
                              1.0f / (float)tm.n_pix_local, first_sample, seed, walk ? 1u : 0u};
     PrtPrimary primary_list = primary;  // what the traversal sees: list slots in place of path slots
-    if (walk) primary_list.pid = (const uint32_t*)c->rb[0].hd2;
-    if ((rc = begin_event(c, 0, &ep))) return rc;
-    const PrtRaygenArgs ra{&c->dsc, c->cam, tm, n_paths, first_sample, seed, max_depth, c->rb[0], c->d_rad, c->d_counts, c->d_work, c->sampling,
-                           compact ? c->d_pix : nullptr, walk, f.env ? &denv : nullptr, f.lens ? &dlens : nullptr, view.list};
-    if (!prt_launch_raygen(c->stream, plan.raygen, ra)) return fail(c, PRT_ERR_INVALID, "no such raygen instance");
+    if (walk) primary_list.pid = (const uint32_t*)rb0.hd2;
+    // (REUSE: the name of the instance whose output the batch uses)
     c->batch_instance[PRT_STAGE_RAYGEN] = prt_raygen_name(plan.raygen);
-    if ((rc = end_event(c, &ep))) return rc;
-    if (exact) HIPCHECK(c, read_back(0));
+    if (!reuse) {
+        c->primary_key.valid = false;  // k_raygen overwrites d_pix and bounce 0's counters: set again below, once the stage stands
+        if ((rc = begin_event(c, 0, &ep))) return rc;
+        const PrtRaygenArgs ra{&c->dsc, c->cam, tm, n_paths, first_sample, seed, max_depth, rb0, c->d_rad, c->d_counts, c->d_work, c->sampling,
+                               compact ? c->d_pix : nullptr, walk, f.env ? &denv : nullptr, f.lens ? &dlens : nullptr, view.list};
+        if (!prt_launch_raygen(c->stream, plan.raygen, ra)) return fail(c, PRT_ERR_INVALID, "no such raygen instance");
+        if ((rc = end_event(c, &ep))) return rc;
+        if (exact) HIPCHECK(c, read_back(0));
+    }
     for (uint32_t d = 0; d < max_depth; ++d) {
-        const PrtRayBuf& in = c->rb[d & 1];
+        const PrtRayBuf& in = d == 0 ? rb0 : c->rb[d & 1];
         const PrtRayBuf& out = c->rb[(d + 1) & 1];
         const uint32_t* front_count = c->d_counts + (size_t)d * PRT_CNT_STRIDE;
         const PrtPrimary* prim_d = (compact && d == 0) ? &primary : nullptr;
-        if (c->dsc.n_nodes) {  // only the front part of the buffer can hit a triangle
+        const bool held = reuse && d == 0;  // bounce 0's hits and the pixels' hit records stand
+        // (REUSE starts at the first k_shade: the cursors and the overflow counter k_raygen zeroes are the bounce-0 walk's, and
+        // every k_shade zeroes them for the walk that follows it)
+        if (c->dsc.n_nodes && !held) {  // only the front part of the buffer can hit a triangle
             if ((rc = begin_event(c, 1, &ep))) return rc;
             PrtTravTuning tune = c->tune;
             tune.probe_slot = d;
@@ -922,11 +1015,15 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
             }
         }
         uint32_t n_rays_known = 0xFFFFFFFFu;
-        if (exact) {
+        if (exact && held) {  // bounce 0's counts as the refresh read them: no copy, no wait
+            n_rays_known = c->primary_counts[0] + c->primary_counts[1];
+        } else if (exact) {
             HIPCHECK(c, hipEventSynchronize(c->ev_counts[d]));
             n_rays_known = c->h_counts[64 * (size_t)d] + c->h_counts[64 * (size_t)d + 32];
-            if (n_rays_known == 0u) break;  // every path has ended: the later bounces have nothing to do
+            if (d == 0) c->primary_counts[0] = c->h_counts[0], c->primary_counts[1] = c->h_counts[32];
         }
+        if (n_rays_known == 0u) break;  // every path has ended: the later bounces have nothing to do
+        if (d == 0 && !reuse && now.valid) c->primary_key = now;  // the stage stands: what the next batch may start from
         if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, c->d_counts, d, n_paths, c->d_shade_div, prim_d);
         if ((rc = begin_event(c, 2, &ep))) return rc;
         const PrtShadeInst shade = d == 0 ? plan.shade0 : plan.shade;
@@ -982,6 +1079,7 @@ void fill_dev_scene(PrtContext* c, uint32_t node_stride, uint32_t depth8) {
     memcpy(d.root_max, k.root_max, sizeof(d.root_max));
     memcpy(d.sky, k.sky, sizeof(d.sky));
     c->dsc = d;
+    touch_scene(c);  // (whatever filled the scene anew: a held primary stage is of the scene before)
 }
 
 // Second half of prt_set_scene / prt_clone_scene: the context's host copies -> its device.  `gb` (device-side build):
@@ -1226,6 +1324,7 @@ void prt_destroy(PrtContext* c) {
         free_env(c);
         free_tex(c);
         free_path_state(c);
+        free_primary_state(c);
         free_light_state(c);
         free_dev(c->d_light_stats);
         free_dev(c->d_film_local);
@@ -1265,6 +1364,7 @@ int prt_set_stream(PrtContext* c, void* hip_stream) {
     int rc = need_device(c);
     if (rc) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
+    touch_scene(c);  // (coarse: the held primary stage was written on the other stream)
     c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     return PRT_OK;
 }
@@ -1282,6 +1382,7 @@ int prt_get_device(const PrtContext* c) { return c ? c->device : -1; }
 int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     if (!c || !s) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    touch_scene(c);
     drop_history(c);
     int rc = prt_check_scene_arrays(s, &c->err);
     if (rc) return rc;
@@ -1330,6 +1431,7 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     if (!src->has_scene) return fail(dst, PRT_ERR_INVALID, "prt_clone_scene: the source context has no scene");
     if (dst == src) return PRT_OK;
     dst->feat_valid = false;
+    touch_scene(dst);
     drop_history(dst);
     dst->has_scene = false;
     drop_tex(dst);
@@ -1357,6 +1459,7 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
 // device (csrc/bvh_gpu.hip prt_gpu_bvh8_refit): records rewritten, boxes recomputed bottom-up, nodes re-quantized.
 int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     if (c) c->feat_valid = false;
+    if (c) touch_scene(c);
     if (c) drop_history(c);
     int rc = need_device(c);
     if (rc) return rc;
@@ -1452,6 +1555,7 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
 int prt_set_instance_transforms(PrtContext* c, const PrtInstance* instances, uint32_t n, uint32_t mode) {
     if (!c) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    touch_scene(c);
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
     if (mode != (uint32_t)PRT_INSTANCES_REFIT && mode != (uint32_t)PRT_INSTANCES_REBUILD)
         return fail(c, PRT_ERR_INVALID, "prt_set_instance_transforms: mode is PRT_INSTANCES_REFIT or PRT_INSTANCES_REBUILD, not %u", mode);
@@ -1633,6 +1737,7 @@ int prt_instances_read(PrtContext* c, uint32_t capacity, uint32_t* n_instances, 
 int prt_set_camera(PrtContext* c, const PrtCameraDesc* cam) {
     if (!c || !cam) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    touch_camera(c);
     if (!(cam->width > 0.0f) || !(cam->height > 0.0f)) return fail(c, PRT_ERR_INVALID, "camera width/height must be > 0");
     DevCamera& k = c->cam;
     k.pos = f3{cam->position[0], cam->position[1], cam->position[2]};
@@ -1649,6 +1754,7 @@ int prt_set_camera(PrtContext* c, const PrtCameraDesc* cam) {
 int prt_set_lens(PrtContext* c, const PrtLens* lens) {
     if (!c) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    touch_camera(c);  // (the field of view is the camera's)
     const PrtLens l = lens ? *lens : PrtLens{0.0f, 0.0f, 0.0f};
     if (std::isnan(l.fov_y) || std::isnan(l.aperture) || std::isnan(l.focus_distance))
         return fail(c, PRT_ERR_INVALID, "bad lens: NaN");
@@ -1671,6 +1777,7 @@ int prt_get_lens(PrtContext* c, PrtLens* out) {
 int prt_set_film(PrtContext* c, uint32_t width, uint32_t height, uint32_t rank, uint32_t world) {
     if (!c) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    touch_scene(c);  // (the tile map is in the key as well)
     drop_history(c);
     if (width == 0 || height == 0 || world == 0 || rank >= world)
         return fail(c, PRT_ERR_INVALID, "bad film size or partition (%ux%u, rank %u of %u)", width, height, rank, world);
@@ -1723,6 +1830,7 @@ int prt_set_film_statistics(PrtContext* c, int on) {
     if (!c) return PRT_ERR_INVALID;
     const bool want = on != 0;
     if (want == c->film_stats) return PRT_OK;
+    touch_scene(c);
     c->film_stats = want;
     drop_history(c);
     if (!c->has_device) return PRT_OK;  // host-only: the setting is all there is
@@ -1740,6 +1848,7 @@ int prt_set_sampling(PrtContext* c, const PrtSampling* sp) {
     if (!c) return PRT_ERR_INVALID;
     if (sp && (sp->jitter > 1u || sp->rr_depth > PRT_MAX_DEPTH || !(sp->clamp >= 0.0f)))
         return fail(c, PRT_ERR_INVALID, "bad sampling options");
+    touch_scene(c);
     const PrtSampling ns = sp ? *sp : PrtSampling{0u, 0u, 0.0f};
     if (c->fsamp.samples > 0u && ns.jitter != c->sampling.jitter) c->feat_valid = false;  // the sampled set's rays are the render's
     c->sampling = ns;
@@ -1756,6 +1865,7 @@ int prt_set_lighting(PrtContext* c, const PrtLighting* l) {
     if (!c) return PRT_ERR_INVALID;
     if (l && l->mode != PRT_LIGHTING_OFF && l->mode != PRT_LIGHTING_NEE_MIS && l->mode != PRT_LIGHTING_NEE)
         return fail(c, PRT_ERR_INVALID, "bad lighting mode %u", l->mode);
+    touch_scene(c);
     c->lighting = l ? l->mode : (uint32_t)PRT_LIGHTING_OFF;
     return PRT_OK;
 }
@@ -1765,6 +1875,7 @@ int prt_set_light_sources(PrtContext* c, uint32_t mask) {
     if (mask != (uint32_t)PRT_LIGHT_SOURCES_ANALYTIC && mask != (uint32_t)(PRT_LIGHT_SOURCES_ANALYTIC | PRT_LIGHT_SOURCES_MESH))
         return fail(c, PRT_ERR_INVALID, "light sources: PRT_LIGHT_SOURCES_ANALYTIC or ANALYTIC | MESH, not %u", mask);
     const bool was_on = mesh_lights_on(c);
+    touch_scene(c);
     c->light_sources = mask;
     if (!c->has_device || !c->has_scene || was_on == mesh_lights_on(c)) return PRT_OK;
     if (mesh_lights_on(c)) return upload_mesh_lights(c);
@@ -1781,6 +1892,7 @@ int prt_set_light_selection(PrtContext* c, const PrtLightSelection* sel) {
         return fail(c, PRT_ERR_INVALID, "light selection: PRT_LIGHT_SELECTION_POWER or CLUSTERED, not %u", s.mode);
     if (s.max_clusters > PRT_LIGHT_MAX_CLUSTERS)
         return fail(c, PRT_ERR_INVALID, "light selection: at most %u clusters, not %u", PRT_LIGHT_MAX_CLUSTERS, s.max_clusters);
+    touch_scene(c);
     c->light_selection = s.mode;
     c->light_max_clusters = s.max_clusters;
     const uint32_t K = s.max_clusters ? s.max_clusters : 32u;
@@ -1864,6 +1976,7 @@ int prt_light_cluster_pmf(PrtContext* c, uint32_t n, const float* x, uint32_t* M
 
 int prt_set_environment(PrtContext* c, const PrtEnvironment* e) {
     if (!c) return PRT_ERR_INVALID;
+    touch_scene(c);
     PrtEnvTables t;  // (built aside: a refused image leaves the context's environment as it was)
     if (e) {
         const int rc = prt_build_environment(e, &t, &c->err);
@@ -1884,6 +1997,7 @@ int prt_set_environment(PrtContext* c, const PrtEnvironment* e) {
 int prt_set_textures(PrtContext* c, const PrtTextureSet* set) {
     if (!c) return PRT_ERR_INVALID;
     c->feat_valid = false;
+    touch_scene(c);
     drop_history(c);
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_textures: prt_set_scene has not been called");
     PrtTexTables t;  // (built aside: a refused set leaves the context's binding as it was)
@@ -3435,6 +3549,13 @@ int prt_last_segment(PrtContext* c, uint32_t* active, uint32_t* front_rays) {
     return PRT_OK;
 }
 
+int prt_primary_reuse(PrtContext* c, uint32_t* active, uint32_t* reused_batches) {
+    if (!c || !active) return PRT_ERR_INVALID;
+    *active = c->primary_reuse_active;
+    if (reused_batches) *reused_batches = c->primary_reused_batches;
+    return PRT_OK;
+}
+
 int prt_bvh_info(PrtContext* c, PrtBvhInfo* out) {
     if (!c || !out) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
@@ -3467,8 +3588,10 @@ int prt_bvh_read(PrtContext* c, float* nodes, float* tris) {
 
 int prt_set_param(PrtContext* c, const char* name, int value) {
     if (!c || !name) return PRT_ERR_INVALID;
+    touch_scene(c);  // any name: a stale primary stage is a wrong image, a spurious rebuild is half a millisecond
     const std::string n = name;
     if (n == "variant") c->variant = value;
+    else if (n == "primary_reuse" && (value == 0 || value == 1)) c->primary_reuse = value;
     else if (n == "grid_blocks" && value > 0 && value <= 8192) c->tune.grid_blocks = (uint32_t)value;
     else if (n == "chunk" && value >= 64 && value % 64 == 0) c->tune.chunk = (uint32_t)value;
     else if (n == "xcd_affinity" && (value == 0 || value == 1)) c->tune.xcd_affinity = (uint32_t)value;
@@ -3508,6 +3631,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
 
 int prt_set_variant(PrtContext* c, int variant) {
     if (!c) return PRT_ERR_INVALID;
+    touch_scene(c);
     c->variant = variant;
     return PRT_OK;
 }

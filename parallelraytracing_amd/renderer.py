@@ -1299,6 +1299,13 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_last_segment(self._ctx, C.byref(active), C.byref(front)))
         return active.value, front.value
 
+    def primary_reuse(self):
+        """(1 if the last batch started at its first shade launch on the primary stage the context held, else 0; batches that
+        did since the context was created) (prt_primary_reuse); (0, 0) before the first batch."""
+        active, reused = C.c_uint32(0), C.c_uint32(0)
+        self._check(capi.lib().prt_primary_reuse(self._ctx, C.byref(active), C.byref(reused)))
+        return active.value, reused.value
+
     def bvh_read(self):
         b = self.bvh_info()
         nodes = np.zeros((b.n_nodes, 16), np.float32)
