@@ -4,6 +4,8 @@ builders, kernel tunables and sampling flags; every frame bit for bit against th
 --lighting: the same generators with emissive analytic primitives and light sampling, every sample against the float64 replay.
 --scale: scene, camera and rays moved by a (scale, translation) drawn from tests/scale_cases.py's non-extreme table; the oracle
          then always scans linearly (its own BVH carries absolute pads).
+--interface: ONE long-lived context (or a group) through generated call sequences of the whole interface, against the model of
+         tests/interface_sequences.py: films, ray counts, every query's answer, and what prt_primary_reuse may say (~0.08 s per case).
   python tests/fuzz_parity.py --cases 200 --seed 1      (GPU box; ~0.3 s per case)
 Test infrastructure (it calls the oracle): a checker, not a product path; tests/test_gpu_fuzz.py runs a seeded subset."""
 import argparse
@@ -303,6 +305,289 @@ def run_sequence_case(case, seed):
     return f"sequence case {case}: ok  {log}", True
 
 
+# ---- the whole interface on one long-lived context (tests/interface_sequences.py: the model, the generator) ---------------------
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _hits_bad(got, want):
+    bad = []
+    for f in ("prim", "front_face", "material_id", "d2", "position", "normal"):
+        same = got[f] == want[f]
+        if got[f].dtype.kind == "f":
+            same = same | (np.isnan(got[f]) & np.isnan(want[f]))
+        if not np.all(same):
+            bad.append(f)
+    return bad
+
+
+def interface_query(r, m, kind, n, rseed):
+    """One query (interface_sequences.QUERIES) on renderer r, its answer against the oracle's for the model m's scene and
+    camera.  The model learns of the call (a measurement is an instrumented batch, the chunked radiance query a set_param).
+    -> a list of what differs, empty if nothing does."""
+    import interface_sequences as iseq
+    bad = []
+    rng = np.random.default_rng([int(rseed), 31])
+    o, d = iseq.query_rays(rseed, n)
+    if kind.startswith("measure_"):
+        m.measure(kind)
+    else:
+        m.query(kind)
+    if kind == "camera_rays":
+        px, py = rng.uniform(0, m.W, n).astype(np.float32), rng.uniform(0, m.H, n).astype(np.float32)
+        go, gd = r.camera_rays(px, py)
+        wo, wd = orc.camera_rays(m.cam.desc(), px, py)
+        if not (np.array_equal(_bits(go), _bits(wo)) and np.array_equal(_bits(gd), _bits(wd))):
+            bad.append("camera_rays")
+    elif kind == "closest_hit":
+        bad += ["closest_hit." + f for f in _hits_bad(r.closest_hit(o, d), m.closest_hit(o, d))]
+    elif kind == "closest_hit_device":
+        import torch
+        dev = torch.device("cuda", 0)
+        got = prt.hits_to_numpy(r.closest_hit_device(torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)))
+        bad += ["closest_hit_device." + f for f in _hits_bad(got, m.closest_hit(o, d))]
+    elif kind == "occluded":
+        want = m.closest_hit(o, d)
+        t = iseq.occlusion_tmax(rseed, want)
+        got = r.occluded(o, d, t)
+        if got.dtype != bool or not np.array_equal(got, iseq.occlusion_contract(want, t, d)):
+            bad.append("occluded")
+    elif kind == "radiance":
+        state = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+        L, seg, st = m.trace(o, d, state)
+        _, info = r.radiance(o, d, rng_state=state, return_info=True)
+        if not (np.array_equal(_bits(info["sum"]), _bits(L)) and np.array_equal(info["segments"], seg) and np.array_equal(info["rng_state"], st)):
+            bad.append("radiance")
+    elif kind == "radiance_chunked":   # 3 samples, one per launch: prt_set_param bumps a generation
+        r.set_param("radiance_chunk", 1)
+        m.set_param("radiance_chunk", 1)
+        first = int(rng.integers(0, 1000))
+        want, segs = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        for s in range(3):   # sample s of ray i is the path of path_seed(i, first_sample + s, seed); the sum in sample order
+            L, seg, _ = m.trace(o, d, m.path_seeds(n, first + s))
+            want = (want + L).astype(np.float32)
+            segs += seg
+        _, info = r.radiance(o, d, samples=3, first_sample=first, return_info=True)
+        if not (np.array_equal(_bits(info["sum"]), _bits(want)) and np.array_equal(info["segments"], segs)):
+            bad.append("radiance_chunked")
+    elif kind == "scatter":
+        hits = m.closest_hit(o, d)
+        sel = hits["prim"] >= 0
+        if sel.any():
+            state = rng.integers(0, 2 ** 32, int(sel.sum()), dtype=np.uint64).astype(np.uint32)
+            got = r.scatter(d[sel], hits[sel], state)
+            want = orc.scatter_batch(list(m.scene.materials), d[sel], hits[sel], state)
+            names = ("scattered", "attenuation", "emitted", "origin", "dir", "rng_state")
+            bad += ["scatter." + nm for nm, g, w in zip(names, got, want) if not np.array_equal(g, w, equal_nan=g.dtype.kind == "f")]
+    elif kind == "render_features":
+        import denoise_replay as dr
+        got = r.render_features()
+        px, py = iseq.pixel_centres(m.W, m.H)
+        co, cd = orc.camera_rays(m.cam.desc(), px, py)
+        want = dr.features_from_hits(m.closest_hit(co, cd), m.scene, m.W, m.H)
+        if not np.array_equal(got["prim"], want["prim"]):
+            bad.append("render_features.prim")
+        bad += ["render_features." + k for k in ("normal", "position", "depth", "albedo") if not np.array_equal(got[k], want[k], equal_nan=True)]
+    elif kind == "display":
+        if m.known and not m.group:
+            disp = r.UpdateDisplay().astype(np.int32)
+            diff = np.abs(disp - orc.tonemap(m.acc, m.wts).astype(np.int32))
+            if diff.max() > 1:   # (powf on the GPU against glibc's: one lsb, tests/test_gpu_parity.py)
+                bad.append(f"display: off by {int(diff.max())}")
+        else:
+            r.UpdateDisplay()
+    elif kind == "download":
+        f = r.download()
+        if m.known and not (np.array_equal(f.accum, m.acc) and np.array_equal(f.weights, m.wts)):
+            bad.append("download")
+    elif kind == "stats":
+        got = int(r.stats().rays_total)
+        if m.known and got != m.rays:
+            bad.append(f"stats: {got} rays, the oracle {m.rays}")
+        r.reset_stats()
+        m.reset_stats()
+        if r.stats().rays_total != 0:
+            bad.append("reset_stats")
+    elif kind == "occupancy":
+        a, b = bytes(r.kernel_occupancy()), bytes(r.kernel_occupancy())
+        if a != b or not any(a):
+            bad.append("kernel_occupancy")
+    elif kind == "bvh_read8":
+        if r.bvh_info().n_nodes8:
+            if not np.array_equal(r.bvh_read8(), r.bvh_read8()):
+                bad.append("bvh_read8")
+    elif kind == "measure_traversal":
+        st = r.measure_traversal(sample=3)
+        _, _, rays = m.osc.render(m.cam.desc(), m.W, m.H, spp=1, first_sample=3, max_depth=m.depth, seed=m.seed, iterative=True,
+                                  use_bvh=m.use_bvh, n_threads=8, sampling=m.sp)
+        if m.covered and int(st.rays_total) != rays:
+            bad.append(f"measure_traversal: {int(st.rays_total)} rays, the oracle {rays}")
+    elif kind == "measure_shade_divergence":
+        if r.measure_shade_divergence(sample=3).shape != (r.max_depth, 16):
+            bad.append("measure_shade_divergence")
+    else:
+        raise ValueError(kind)
+    return bad
+
+
+def check_batches(r, recs, what=""):
+    """After a call that ran the batches `recs` (the model's records): what prt_primary_reuse says of the LAST of them against
+    its verdict.  -> a list of complaints."""
+    import interface_sequences as iseq
+    if not recs or not hasattr(r, "primary_reuse"):
+        return []
+    active, v = r.primary_reuse()[0], recs[-1]["verdict"]
+    if (v == iseq.MUST_NOT and active != 0) or (v == iseq.MUST and active != 1):
+        return [f"{what}: primary_reuse {active} where the model says '{v}' (setters {recs[-1]['setters']}, queries {recs[-1]['queries']})"]
+    return []
+
+
+def excursion_switch(r, kind, on, scene_kind=None):
+    """Turns one of the features the oracle does not cover on or off (interface_sequences.EXCURSIONS)."""
+    import interface_sequences as iseq
+    if kind == "lens":
+        r.set_lens(aperture=0.05, focus_distance=3.0) if on else r.set_lens()
+    elif kind == "environment":
+        r.set_environment(iseq.environment_image() if on else None)
+    elif kind == "textures":
+        r.set_textures(iseq.cube_uv_scene(textured=True) if on else None)
+    elif kind == "mis":
+        r.set_lighting("mis" if on else "off")
+    elif kind == "adaptive":
+        r.set_film_statistics(on)
+
+
+def _excursion_render(r, kind, k):
+    if kind == "adaptive":
+        info = r.render_adaptive(0.05, min_spp=k, step_spp=k, max_spp=2 * k, noise_floor=0.01)
+        passes = int(info.passes)
+    else:
+        r.ProgressiveRender(k)
+        passes = 0
+    f = r.download()
+    return f.accum.copy(), f.weights.copy(), passes
+
+
+def run_excursion(r, m, kind, k):
+    """Clear / feature on / render / feature off / Clear on the long-lived context, and the same from scratch on a fresh one
+    (same scene, camera, film, depth, seed, sampling flags; its own tunables): the two films must be equal byte for byte."""
+    import interface_sequences as iseq
+    bad = []
+    r.film.Clear()
+    r.frame_index = 0
+    excursion_switch(r, kind, True)
+    acc, wts, passes = _excursion_render(r, kind, k)
+    recs = iseq.excursion_model(m, kind, k, listed_passes=min(passes, 1))
+    if kind != "adaptive" or passes <= 1:   # (the model logged one listed pass at the most; the last batch is what is asked)
+        bad += check_batches(r, recs, f"excursion {kind}")
+    sp, sif = m.sp, m.sif
+
+    def from_scratch():
+        fresh = prt.HipWavefrontRenderer(device=0, max_depth=m.depth, seed=m.seed)
+        fresh.Init(prt.Film(m.W, m.H), m.scene, m.cam)
+        fresh.set_param("primary_reuse", 0)
+        fresh.set_samples_in_flight(sif)
+        if sp is not None:
+            fresh.set_sampling(sp.jitter, sp.rr_depth, sp.clamp)
+        excursion_switch(fresh, kind, True)
+        return _excursion_render(fresh, kind, k)
+
+    acc2, wts2, passes2 = from_scratch()
+    if not (np.array_equal(_bits(acc), _bits(acc2)) and np.array_equal(wts, wts2) and passes == passes2):
+        acc3, wts3, _ = from_scratch()   # (do two fresh contexts agree with each other?  If not, the call is not deterministic)
+        bad.append(f"excursion {kind} ({k} samples): {int((acc != acc2).any(axis=-1).sum())} pixels differ from a fresh context's, passes "
+                   f"{passes} / {passes2}; two fresh contexts {'agree' if np.array_equal(_bits(acc2), _bits(acc3)) else 'DIFFER'}")
+    excursion_switch(r, kind, False)
+    r.film.Clear()
+    r.frame_index = 0
+    r.reset_stats()
+    m.reset_stats()
+    return bad
+
+
+def run_interface_case(case, seed):
+    """interface_sequences.generate(seed, case) on ONE long-lived context (or a group of 2-3, which takes the setters only) and
+    on the model: after every render the film and the ray count equal the oracle's and prt_primary_reuse agrees with the model's
+    verdict; after every query its answer equals the oracle's; an excursion's film equals a fresh context's."""
+    import interface_sequences as iseq
+    head, ops = iseq.generate(seed, case)
+    depth, rseed, use_group = head["depth"], head["seed"], head["group"]
+    r = prt.HipWavefrontGroupRenderer([0] * head["k_ctx"], max_depth=depth, seed=rseed) if use_group else \
+        prt.HipWavefrontRenderer(device=0, max_depth=depth, seed=rseed)
+    m = iseq.Model(depth, rseed, use_group)
+    state, log = {}, [f"group x{head['k_ctx']}" if use_group else "single"]
+    try:
+        return _run_interface_ops(case, ops, r, m, use_group, state, log)
+    except prt.PrtError as e:  # (it may be a device fault: main() runs nothing after it)
+        return f"interface case {case}: LIBRARY ERROR {str(e)[:300]} after {log}", False
+
+
+def _run_interface_ops(case, ops, r, m, use_group, state, log):
+    import interface_sequences as iseq
+    for op in ops:
+        k = op[0]
+        log.append(" ".join(str(x) for x in op[:3]))
+        bad = []
+        if k == "init":
+            scene, cam = iseq.apply_setter(m, op, state)
+            film = prt.Film(op[2], op[3])
+            try:
+                r.Init(film, scene, cam)
+            except prt.PrtError as e:  # e.g. a tree too deep for the two-level kernel: must be a clean error
+                return f"interface case {case}: Init refused ({str(e)[:80]}) after {log}", True
+            r.set_sampling(0, 0, 0.0)
+            if not use_group:
+                r.reset_stats()
+                m.reset_stats()
+        elif k == "render":
+            before = int(r.stats().rays_total) if use_group else 0
+            if use_group:
+                r.frame_index = m.fi
+            r.ProgressiveRender(op[1])
+            rays0 = m.rays
+            recs = m.render(op[1])
+            f = r.download()
+            if m.known:
+                if not (np.array_equal(f.accum, m.acc) and np.array_equal(f.weights, m.wts)):
+                    bad.append(f"{int((f.accum != m.acc).any(axis=-1).sum())} bad pixels")
+                got = int(r.stats().rays_total)
+                if (got - before != m.rays - rays0) if use_group else (got != m.rays):
+                    bad.append(f"rays {got - before} vs the oracle's {m.rays - rays0 if use_group else m.rays}")
+            bad += check_batches(r, recs, "render")
+        elif k == "query":
+            bad = interface_query(r, m, op[1], op[2], op[3])
+        elif k == "excursion":
+            bad = run_excursion(r, m, op[1], op[2])
+        else:
+            res = iseq.apply_setter(m, op, state)
+            if k == "camera":
+                r.SetCamera(res)
+            elif k == "clear":
+                if use_group:
+                    r.Clear()
+                else:
+                    r.film.Clear()
+                    r.frame_index = 0
+            elif k == "sampling":
+                r.set_sampling(*op[1:])
+            elif k == "sif":
+                r.set_samples_in_flight(op[1])
+            elif k == "param":
+                r.set_param(op[1], op[2])
+            elif k == "max_depth":
+                r.max_depth = op[1]
+            elif k == "refit":
+                r.Refit(res)
+            elif k == "instances":
+                r.UpdateInstances(res)
+            elif k == "set_film":
+                r.set_film(prt.Film(op[1], op[2]))
+                r.SetCamera(res)
+        if bad:
+            return f"interface case {case}: MISMATCH {bad} after {log}", False
+    return f"interface case {case}: ok  {log}", True
+
+
 def run_graze_case(case, seed, n=100_000):
     """Spheres only, more than 16 of them (so the walk over their world boxes runs), rays aimed to graze them within a few
     rounding margins of the reference's discriminant (2e-7 * dist^2 / R), from 0.5 ... 2000 units away, random radii down
@@ -510,6 +795,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--sequences", action="store_true", help="random call sequences on one long-lived renderer (or a group of contexts)")
+    ap.add_argument("--interface", action="store_true", help="the whole interface on one long-lived renderer against the model of tests/interface_sequences.py")
     ap.add_argument("--graze", action="store_true", help="rays grazing spheres within the reference's rounding margins (walk over the primitives' boxes)")
     ap.add_argument("--graze-quads", action="store_true", help="rays grazing quads along their edges (walk over the primitives' boxes)")
     ap.add_argument("--cos-lo", type=float, default=1e-5, help="--graze-quads: smallest cosine of incidence")
@@ -523,10 +809,15 @@ def main():
     for case in range(a.first, a.first + a.cases):
         msg, ok = (run_lighting_case(case, a.seed, render=not a.no_render)[:2] if a.lighting else
                    run_ray_case(case, a.seed, scale=a.scale) if a.rays else run_sequence_case(case, a.seed) if a.sequences else
+                   run_interface_case(case, a.seed) if a.interface else
                    run_graze_case(case, a.seed) if a.graze else
                    run_graze_quads_case(case, a.seed, cos_lo=a.cos_lo)[:2] if a.graze_quads else run_case(case, a.seed, scale=a.scale))
         if not ok:
             bad += 1
+        if "LIBRARY ERROR" in msg:
+            print(msg, flush=True)
+            print(f"fuzz_parity: stopped at case {case}: the library reported an error", flush=True)
+            sys.exit(2)
         if a.verbose or not ok or "refused" in msg:
             print(msg, flush=True)
         if (case - a.first) % 25 == 24:

@@ -6,7 +6,8 @@ tunables (incl. a stack so small that rays take the overflow list) and the sampl
 compares EVERY pixel and the ray count with the oracle's throughput form (CPURenderer::TraceRay's iterative twin,
 backend/cuda_megakernel/renderer.cu:81-119; PrimitiveList::Intersect semantics, core/primitive.cpp:21-59).
 A longer run (6,300 cases, 0 mismatches) is recorded in DESIGN.md.
-48 further cases render with light sampling and are held, sample by sample, to the float64 replay (tests/lighting_replay.py)."""
+48 further cases render with light sampling and are held, sample by sample, to the float64 replay (tests/lighting_replay.py).
+40 generated call sequences drive one long-lived context through the whole interface (tests/interface_sequences.py)."""
 import importlib.util
 import os
 
@@ -149,6 +150,24 @@ def test_random_call_sequences_on_one_long_lived_renderer():
     bad = []
     for case in range(60):
         msg, ok = fuzz.run_sequence_case(case, seed=13)
+        if not ok:
+            bad.append(msg)
+    assert bad == []
+
+
+@pytest.mark.parametrize("first", range(0, 40, 5))
+def test_the_whole_interface_on_one_long_lived_renderer(first):
+    """fuzz_parity.run_interface_case, the 40 cases whose coverage tests/test_interface_sequences.py counts without a GPU:
+    renders of 1 .. 70 samples, every setter the oracle covers (Refit, UpdateInstances, set_film, max_depth and the tunables,
+    primary_walk / primary_reuse / last_segment among them), the queries between the batches, excursions into lens,
+    environment, textures, light sampling and an adaptive pass, on one context or a group.  After every render the film and
+    the ray count are the oracle's and prt_primary_reuse is what the model of tests/interface_sequences.py allows; after every
+    query its answer is the oracle's; an excursion's film is a fresh context's."""
+    import interface_sequences as iseq
+    assert iseq.CAMPAIGN_CASES == 40
+    bad = []
+    for case in range(first, first + 5):
+        msg, ok = fuzz.run_interface_case(case, seed=iseq.CAMPAIGN_SEED)
         if not ok:
             bad.append(msg)
     assert bad == []
