@@ -1105,7 +1105,7 @@ int prt_scatter(PrtContext* ctx, uint32_t n, const float* in_dirs, const PrtHit*
  *    4-byte read of the live count, the ray-query pipeline of prt_closest_hit_device over the live rays only, the UV pass
  *    while a binding textures something, one step kernel that compacts the survivors.  Results never depend on the chunk
  *    size (prt_set_param("radiance_chunk", samples per chunk; 0 = by the ray budget)) or on any other tunable.
- * Not offered: the group (prt_group_*) and the light-sampling estimators. */
+ * Light sampling: prt_radiance_lit, below.  Not offered: the group (prt_group_*). */
 #define PRT_RADIANCE_MAX_SAMPLES 4096u
 typedef struct PrtRadianceQuery {
     uint32_t max_depth;     /* segments per path at most; 0: every output is zero */
@@ -1120,6 +1120,45 @@ int prt_radiance(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const f
  * prt_render_adaptive has one per pass); the outputs are complete in stream order when the call returns. */
 int prt_radiance_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs,
                         void* d_rng_state, void* d_rgb_sum, void* d_segments);
+
+/* The light-sampled radiance query: prt_radiance's paths with the estimator a prt_render would use now: the context's
+ * lighting mode (prt_set_lighting), light source mask, light selection and environment share.  prt_radiance and
+ * prt_radiance_device keep their contract, their bits and their cost.
+ *  Mode PRT_LIGHTING_OFF: rgb_sum, segments and rng_state are prt_radiance's bit for bit, and no shadow ray is cast.
+ *  Otherwise the path of ray i, sample s is the unlit query's draw for draw: segments and the rng_state written back are
+ *    prt_radiance's (the light stream never advances the path's state), and the path carries what a lit render's path
+ *    carries.  Per segment k, with pb = -1 at k = 0 and the light sum lsum = 0:
+ *    Miss: L += thr * sky; under an environment image thr * its texel, times the MIS weight of (d, pb) where that is not 1
+ *      (pb < 0: weight 1).  The path ends.
+ *    Hit: key = the state before the material's draws; Material::Scatter as in the unlit query, on the last segment too;
+ *      L += thr * emitted, times the weight 1 - w_L of the emitter where the material is Emissive, pb >= 0, the emitter is
+ *      analytic or the MESH bit is set, and the weight is not 1 (the segment's own origin and direction, the hit's d2).
+ *    Light sample: only at a Lambertian vertex that scattered, with k + 1 < max_depth: toward the environment if its draw
+ *      of `key` says so, else toward the light set if it is not empty; with the hit's position and normal, the albedo the
+ *      step attenuates by (the texture binding's where one applies), thr before this vertex's attenuation, `key` and
+ *      PrtSampling.clamp: prt_sample_light's sample, scaled by thr.  A shadow ray (x, w, tmax) is cast iff there is a
+ *      sample and pb(w) > 0; it is occluded by prt_occluded's rule (tmax = +inf toward the environment).  Unoccluded:
+ *      lsum += contrib (clamped on its own), in vertex order.
+ *    Carry on: thr *= attenuation, d = the scattered direction normalised, pb = max(0, n.d) / pi after a Lambertian vertex,
+ *      else -1; the roulette is the unlit step's.
+ *  Sample value: clamp(L) + lsum, one fp32 add per component: what a lit render adds to its film.  rgb_sum[i] = the fp32
+ *    sum of the sample values over s ascending, from 0.0f, whatever the chunking.  So the lit query over a film's own
+ *    primary rays, ray index = pixel index, is the lit render, bit for bit.
+ *  info (may be NULL): the shadow rays this call cast and how many were occluded.  prt_get_light_stats does not move; the
+ *    other side effects are prt_radiance's: none.
+ *  Refusals: prt_radiance's, decided without a device; then PRT_ERR_NO_DEVICE on a host-only context.
+ *  Cost: prt_radiance's rounds; a round's shadow rays are resolved at the top of the next round (the occlusion pipeline
+ *    of prt_occluded_device and one small kernel), after the one wait that reads the live count and the shadow count
+ *    together.  The last segment takes no light sample, so the host waits at most once per round, as in the unlit query,
+ *    plus once per call where info is given.  "radiance_chunk" applies to both queries. */
+typedef struct PrtRadianceLitInfo {
+    uint64_t shadow_rays, shadow_occluded;
+} PrtRadianceLitInfo;
+int prt_radiance_lit(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const float* origins, const float* dirs,
+                     uint32_t* rng_state, float* rgb_sum, uint32_t* segments, PrtRadianceLitInfo* info);
+/* The same from DEVICE arrays on the context's stream.  info is a HOST pointer; NULL: no final wait for it. */
+int prt_radiance_lit_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs,
+                            void* d_rng_state, void* d_rgb_sum, void* d_segments, PrtRadianceLitInfo* info);
 
 /* ---- measurement ----------------------------------------------------------------------------- */
 int prt_enable_timing(PrtContext* ctx, int on); /* HIP events around every kernel launch */

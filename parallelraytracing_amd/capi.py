@@ -103,6 +103,11 @@ class PrtRadianceQuery(C.Structure):
 RADIANCE_MAX_SAMPLES = 4096  # PRT_RADIANCE_MAX_SAMPLES
 
 
+class PrtRadianceLitInfo(C.Structure):
+    """What one prt_radiance_lit call cast (include/prt.h "Radiance query")."""
+    _fields_ = [("shadow_rays", C.c_uint64), ("shadow_occluded", C.c_uint64)]
+
+
 class PrtAdaptive(C.Structure):
     """Settings of prt_render_adaptive (include/prt.h "Film statistics and adaptive sampling")."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
@@ -353,6 +358,9 @@ SIGNATURES = {
     "prt_scatter": (C.c_int, [_vp, C.c_uint32, _fp, C.POINTER(PrtHit), _u32p, _u32p, _fp, _fp, _fp, _fp]),
     "prt_radiance": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _fp, _fp, _u32p, _fp, _u32p]),
     "prt_radiance_device": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "prt_radiance_lit": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _fp, _fp, _u32p, _fp, _u32p, C.POINTER(PrtRadianceLitInfo)]),
+    "prt_radiance_lit_device": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                          C.POINTER(PrtRadianceLitInfo)]),
     "prt_enable_timing": (C.c_int, [_vp, C.c_int]),
     "prt_get_stats": (C.c_int, [_vp, C.POINTER(PrtStats)]),
     "prt_reset_stats": (C.c_int, [_vp]),

@@ -31,6 +31,7 @@
 #include "prt_kernels.h"
 #include "prt_primary_cache.h"
 #include "prt_radiance.h"
+#include "prt_radiance_lit.h"
 #include "prt_scene.h"
 #include "prt_temporal.h"
 #include "prt_temporal_contract.h"
@@ -3259,6 +3260,142 @@ int prt_radiance_device(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, co
     if ((rc = commit(c, ws, c->scratch))) return rc;
     return enqueue_radiance(c, *q, n, cs, (const float*)d_origins, (const float*)d_dirs, (uint32_t*)d_rng_state, (float*)d_rgb_sum,
                             (uint32_t*)d_segments, x);
+}
+
+// ---- light-sampled radiance query (include/prt.h "Radiance query", prt_radiance_lit) -----------------------
+// RadianceScratch's layout for the lit paths: the lists carry pb, and a chunk of up to m paths has its shadow list, the
+// occlusion bytes, one light sum per slot, the live / shadow count pairs that take turns, and the query's counters.
+struct RadianceLitScratch {
+    PrtRadianceLitList list[2];
+    PrtRadianceShadowList sh;
+    PrtHit* hits;
+    float* albedo;
+    float4* slots;
+    float4* lsum;
+    uint8_t* occ;
+    uint32_t* cnt;                // [2][2]: {live, shadow rays} written by the rounds of either parity
+    unsigned long long* stats;    // [PRT_RDL_STAT_SLOTS][2]
+    void declare(PrtWorkspace& ws, size_t m, bool textured) {
+        for (PrtRadianceLitList& l : list) ws.add(&l.l.o, 3 * m).add(&l.l.d, 3 * m).add(&l.l.s0, m).add(&l.l.s1, m).add(&l.pb, m);
+        ws.add(&sh.x, 3 * m).add(&sh.w, 3 * m).add(&sh.tmax, m).add(&sh.cs, m);
+        ws.add(&hits, m).add(&slots, m).add(&lsum, m).add(&occ, m).add(&cnt, (size_t)4).add(&stats, (size_t)2 * PRT_RDL_STAT_SLOTS);
+        albedo = nullptr;
+        if (textured) ws.add(&albedo, 3 * m);
+    }
+};
+
+// enqueue_radiance with light sampling (the context's lighting mode is not OFF).  The shadow rays a round's step appended
+// are resolved at the top of the next round, after the one wait that reads the live count and the shadow count in one
+// 8-byte copy, and before that round's closest-hit query: both pipelines pack into rb[0], one after the other.  The last
+// round (segment max_depth - 1) takes no light sample, and a chunk whose paths all end earlier resolves before it
+// leaves the loop: so there is no wait beyond the unlit query's one per round.  info (host, may be null): one more read.
+static int enqueue_radiance_lit(PrtContext* c, const PrtRadianceQuery& q, uint32_t n, uint32_t cs, const float* d_o, const float* d_d,
+                                uint32_t* d_rng, float* d_rgb, uint32_t* d_seg, const RadianceLitScratch& x, PrtRadianceLitInfo* info) {
+    int rc;
+    if (info) *info = PrtRadianceLitInfo{0u, 0u};
+    if (q.max_depth == 0u) {
+        HIPCHECK(c, hipMemsetAsync(d_rgb, 0, 3 * (size_t)n * sizeof(float), c->stream));
+        if (d_seg) HIPCHECK(c, hipMemsetAsync(d_seg, 0, (size_t)n * sizeof(uint32_t), c->stream));
+        return PRT_OK;
+    }
+    if ((rc = sync_light_tables(c))) return rc;
+    const bool mesh = mesh_lights_on(c), env = env_on(c), clus = clusters_on(c);
+    PrtRadianceLitArgs a{{x.hits, x.albedo, c->dsc.mat_rgbs, c->dsc.mat_type, env ? dev_env(c) : DevEnv{}, {c->dsc.sky[0], c->dsc.sky[1], c->dsc.sky[2]},
+                          c->sampling, q.max_depth, 0u, x.slots, d_rng, nullptr},
+                         dev_lights(c), dev_mesh_lights(c), dev_light_clusters(c), c->dsc.n_prims, x.sh, nullptr};
+    HIPCHECK(c, hipMemsetAsync(x.stats, 0, 2 * PRT_RDL_STAT_SLOTS * sizeof(unsigned long long), c->stream));
+    for (uint32_t s0 = 0; s0 < q.samples; s0 += cs) {
+        const uint32_t ccs = std::min(cs, q.samples - s0);
+        const uint32_t m = ccs * n;
+        prt_launch_rdl_start(c->stream, n, ccs, q.first_sample + s0, q.seed, d_o, d_d, d_rng, x.list[0]);
+        HIPCHECK(c, hipGetLastError());
+        HIPCHECK(c, hipMemsetAsync(x.lsum, 0, (size_t)m * sizeof(float4), c->stream));
+        uint32_t live = m;
+        int cur = 0;
+        for (uint32_t r = 0; r < q.max_depth; ++r) {
+            if (r > 0u) {
+                uint32_t two[2] = {0u, 0u};
+                HIPCHECK(c, hipMemcpyAsync(two, x.cnt + 2u * (r & 1u), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                HIPCHECK(c, hipStreamSynchronize(c->stream));
+                live = two[0];
+                const uint32_t n_sh = two[1];
+                if (live > m || n_sh > m) return fail(c, PRT_ERR_HIP, "prt_radiance_lit: live count %u or shadow count %u above %u paths", live, n_sh, m);
+                if (n_sh != 0u) {  // the shadow rays of round r - 1: prt_occluded's pipeline, then their contributions
+                    if ((rc = enqueue_query(c, n_sh, x.sh.x, x.sh.w, x.sh.tmax, nullptr, x.occ))) return rc;
+                    prt_launch_rdl_light(c->stream, n_sh, x.sh, x.occ, x.lsum, x.stats);
+                    HIPCHECK(c, hipGetLastError());
+                }
+                if (live == 0u) break;
+            }
+            if ((rc = enqueue_query(c, live, x.list[cur].l.o, x.list[cur].l.d, nullptr, x.hits, nullptr))) return rc;
+            if (x.albedo) prt_launch_hit_uv(c->stream, c->dsc, dev_tex(c), live, c->rb[0], nullptr, x.albedo);  // (rays and final hit ids are in rb[0])
+            uint32_t* next = x.cnt + 2u * ((r + 1u) & 1u);
+            a.a.round = r;
+            a.a.count = next;
+            a.scount = next + 1;
+            HIPCHECK(c, hipMemsetAsync(next, 0, 2 * sizeof(uint32_t), c->stream));
+            prt_launch_rdl_step(c->stream, mesh, env, clus, live, x.list[cur], a, x.list[cur ^ 1]);
+            HIPCHECK(c, hipGetLastError());
+            cur ^= 1;
+        }
+        prt_launch_rdl_sum(c->stream, n, ccs, s0 == 0u, x.slots, x.lsum, d_rgb, d_seg);
+        HIPCHECK(c, hipGetLastError());
+    }
+    if (info) {
+        unsigned long long st[2 * PRT_RDL_STAT_SLOTS];
+        HIPCHECK(c, hipMemcpyAsync(st, x.stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t k = 0; k < PRT_RDL_STAT_SLOTS; ++k) {
+            info->shadow_rays += st[2 * k];
+            info->shadow_occluded += st[2 * k + 1];
+        }
+    }
+    return PRT_OK;
+}
+
+int prt_radiance_lit(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const float* origins, const float* dirs, uint32_t* rng_state,
+                     float* rgb_sum, uint32_t* segments, PrtRadianceLitInfo* info) {
+    int rc = check_radiance(c, q, n, origins, dirs, rng_state, rgb_sum);
+    if (info) *info = PrtRadianceLitInfo{0u, 0u};
+    if (rc || n == 0u) return rc;
+    if ((rc = need_device(c))) return rc;
+    if (c->lighting == (uint32_t)PRT_LIGHTING_OFF) return prt_radiance(c, q, n, origins, dirs, rng_state, rgb_sum, segments);
+    const uint32_t cs = radiance_chunk(c, *q, n);
+    const size_t n1 = n;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (as prt_radiance: the scratch may be reallocated)
+    float *d_o, *d_d, *d_rgb;
+    uint32_t *d_rng = nullptr, *d_seg = nullptr;
+    RadianceLitScratch x;
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * n1).add(&d_d, 3 * n1).add(&d_rgb, 3 * n1);
+    if (rng_state) ws.add(&d_rng, n1);
+    if (segments) ws.add(&d_seg, n1);
+    x.declare(ws, (size_t)cs * n1, tex_on(c));
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_o, origins, 3 * n1)) || (rc = upload(c, d_d, dirs, 3 * n1))) return rc;
+    if (rng_state && (rc = upload(c, d_rng, rng_state, n1))) return rc;
+    if ((rc = enqueue_radiance_lit(c, *q, n, cs, d_o, d_d, d_rng, d_rgb, d_seg, x, info))) return rc;
+    if ((rc = download(c, rgb_sum, d_rgb, 3 * n1))) return rc;
+    if (rng_state && (rc = download(c, rng_state, d_rng, n1))) return rc;
+    if (segments && (rc = download(c, segments, d_seg, n1))) return rc;
+    return prt_synchronize(c);  // waits for the stream and reports a ray a walk (closest hit or shadow) had to give up
+}
+
+int prt_radiance_lit_device(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs, void* d_rng_state,
+                            void* d_rgb_sum, void* d_segments, PrtRadianceLitInfo* info) {
+    int rc = check_radiance(c, q, n, d_origins, d_dirs, d_rng_state, d_rgb_sum);
+    if (info) *info = PrtRadianceLitInfo{0u, 0u};
+    if (rc || n == 0u) return rc;
+    if ((rc = need_device(c))) return rc;
+    if (c->lighting == (uint32_t)PRT_LIGHTING_OFF) return prt_radiance_device(c, q, n, d_origins, d_dirs, d_rng_state, d_rgb_sum, d_segments);
+    const uint32_t cs = radiance_chunk(c, *q, n);
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (as above)
+    RadianceLitScratch x;
+    PrtWorkspace ws;
+    x.declare(ws, (size_t)cs * n, tex_on(c));
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    return enqueue_radiance_lit(c, *q, n, cs, (const float*)d_origins, (const float*)d_dirs, (uint32_t*)d_rng_state, (float*)d_rgb_sum,
+                                (uint32_t*)d_segments, x, info);
 }
 
 int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,

@@ -12,11 +12,12 @@
 //               [--follow-specular N [--mirror-roughness R]] [--feature-samples K]]
 //              [--features-out PREFIX]
 //              [--frames N --orbit-deg D [--temporal [--temporal-max-history H]]]
-//              [--probe X,Y,Z --probe-size WxH]
+//              [--probe X,Y,Z --probe-size WxH --probe-lighting]
 // --probe X,Y,Z renders no frame: it writes PREFIX.pfm, a lat-long radiance probe of --probe-size WxH texels (default 64x32)
 // at that point, --spp paths of up to --depth segments per texel along the texel centre's direction (prt_radiance), in the
 // layout --env reads (top row = the +Y pole): a probe of one scene can light another.  The first GPU; the estimator is the
-// unidirectional one whatever --lighting says.
+// unidirectional one whatever --lighting says, unless --probe-lighting is given: then --lighting, --light-sources and
+// --light-selection apply to the probe as they would to a frame (prt_radiance_lit).
 // --orbit-deg D turns --frames N into an animation: frame f is rendered with --spp samples (sample indices f * spp ...) from the
 // camera turned f * D degrees about the vertical axis through the origin, looking at the origin, on a cleared film, and written
 // as PREFIX_fNNN.pfm.  --temporal carries the film history across the frames (prt_film_temporal: reprojection, disocclusion
@@ -86,7 +87,7 @@ int main(int argc, char** argv) {
     double orbit_deg = 0.0;
     PrtTemporal tp;
     prt_temporal_defaults(&tp);
-    bool probe = false;
+    bool probe = false, probe_lighting = false;
     float probe_pos[3] = {0.0f, 0.0f, 0.0f};
     uint32_t probe_w = 64, probe_h = 32;
     std::vector<int> devices{0};
@@ -164,6 +165,7 @@ int main(int argc, char** argv) {
             if (sscanf(next(), "%f,%f,%f", &probe_pos[0], &probe_pos[1], &probe_pos[2]) != 3) { fprintf(stderr, "--probe takes X,Y,Z\n"); return 2; }
             probe = true;
         }
+        else if (a == "--probe-lighting") probe_lighting = true;
         else if (a == "--probe-size") {
             if (sscanf(next(), "%ux%u", &probe_w, &probe_h) != 2 || !probe_w || !probe_h) { fprintf(stderr, "--probe-size takes WxH\n"); return 2; }
         }
@@ -196,6 +198,10 @@ int main(int argc, char** argv) {
     }
     if (probe && (orbit || adaptive || denoise || !features_out.empty())) {
         fprintf(stderr, "--probe renders no frame: it does not go with --orbit-deg, --adaptive, --denoise or --features-out\n");
+        return 2;
+    }
+    if (probe_lighting && !probe) {
+        fprintf(stderr, "--probe-lighting goes with --probe\n");
         return 2;
     }
     if (temporal && devices.size() != 1) {
@@ -243,7 +249,7 @@ int main(int argc, char** argv) {
         if (adaptive || denoise || temporal) r.SetFilmStatistics(true);
         if (probe) {
             std::vector<float> rgb;
-            r.RenderProbe(probe_pos, probe_w, probe_h, spp, rgb);
+            r.RenderProbe(probe_pos, probe_w, probe_h, spp, rgb, probe_lighting);
             if (prt_write_pfm((out + ".pfm").c_str(), rgb.data(), probe_w, probe_h)) { fprintf(stderr, "cannot write %s.pfm\n", out.c_str()); return 1; }
             printf("probe at (%g, %g, %g): %ux%u texels, %u spp, max_depth %u -> %s.pfm\n", probe_pos[0], probe_pos[1], probe_pos[2], probe_w, probe_h, spp,
                    depth, out.c_str());

@@ -441,17 +441,25 @@ public:
     // paths per ray of the radiance arriving along n caller-supplied rays (origins / dirs: n x 3 floats, host memory) into
     // rgb_sum (3 n floats); sample s of ray i starts from the renderer's seed, the ray index and first_sample + s.
     // rng_state (n, in / out) gives the paths their states instead and needs samples == 1; segments (n) may be null.
+    // lighting: the light-sampled query (prt_radiance_lit): the estimator a render would use now (SetLighting,
+    // SetLightSources, SetLightSelection, the environment's light share); lit_info (may be null): its shadow-ray counts.
     void Radiance(uint32_t n, const float* origins, const float* dirs, float* rgb_sum, uint32_t samples = 1, uint32_t first_sample = 0,
-                  uint32_t* rng_state = nullptr, uint32_t* segments = nullptr) {
+                  uint32_t* rng_state = nullptr, uint32_t* segments = nullptr, bool lighting = false, PrtRadianceLitInfo* lit_info = nullptr) {
         PrtContext* c = prt_group_context(grp_, 0);
         const PrtRadianceQuery q{max_depth_, samples, seed_, first_sample};
+        if (lighting) {
+            if (prt_radiance_lit(c, &q, n, origins, dirs, rng_state, rgb_sum, segments, lit_info))
+                throw Error(std::string("prt_radiance_lit: ") + prt_last_error(c));
+            return;
+        }
         if (prt_radiance(c, &q, n, origins, dirs, rng_state, rgb_sum, segments)) throw Error(std::string("prt_radiance: ") + prt_last_error(c));
     }
     // A lat-long radiance probe at `position`: width x height x 3 floats, the mean over `samples` paths along the unit
     // direction of every texel centre, in prt_set_environment's layout (row 0 = the +Y pole), so that a probe written with
     // prt_write_pfm can light another scene through SetEnvironmentPfm.  The directions are those of the Python package's
-    // probe_directions: float64, the C library's sin / cos, rounded once.
-    void RenderProbe(const float position[3], uint32_t width, uint32_t height, uint32_t samples, std::vector<float>& rgb) {
+    // probe_directions: float64, the C library's sin / cos, rounded once.  lighting: Radiance's.
+    void RenderProbe(const float position[3], uint32_t width, uint32_t height, uint32_t samples, std::vector<float>& rgb,
+                     bool lighting = false) {
         const size_t n = (size_t)width * height;
         const double pi = 3.141592653589793;
         std::vector<float> o(3 * n), d(3 * n);
@@ -467,7 +475,7 @@ public:
             }
         }
         rgb.assign(3 * n, 0.0f);
-        Radiance((uint32_t)n, o.data(), d.data(), rgb.data(), samples);
+        Radiance((uint32_t)n, o.data(), d.data(), rgb.data(), samples, 0u, nullptr, nullptr, lighting);
         for (float& v : rgb) v = v / (float)samples;
     }
 

@@ -1151,14 +1151,18 @@ class HipWavefrontRenderer:
         return sc.astype(bool), att, em, oo, od, rng
 
     def radiance(self, o, d, rng_state=None, samples: int = 1, seed=None, first_sample: int = 0, max_depth=None,
-                 return_info: bool = False):
+                 return_info: bool = False, lighting: bool = False):
         """The radiance arriving along n caller-supplied rays (prt_radiance, include/prt.h "Radiance query"): whole paths
         of up to max_depth segments (default: the renderer's) on the device, `samples` per ray.  o, d: [n, 3] float32,
         numpy arrays (the host form) or torch tensors on the renderer's device (the device form, ordered after torch's
         current stream).  rng_state [n] (uint32; torch: int32 or uint32 bits) gives every path its starting state and needs
         samples == 1; without it sample s of ray i starts from path_seed(i, first_sample + s, seed), seed = the renderer's
         unless given.  Returns the mean [n, 3] = sum / samples in fp32; with return_info also {"sum": the fp32 sum the
-        library returns, "segments": [n] segments walked, "rng_state": the final states, or None}."""
+        library returns, "segments": [n] segments walked, "rng_state": the final states, or None}.
+        lighting=True: the light-sampled query (prt_radiance_lit): the estimator a render would use now (set_lighting,
+        set_light_sources, set_light_selection, the environment's light share); the same paths, less noise under small
+        emitters.  With return_info the info then also has "shadow_rays" and "shadow_occluded" of this call."""
+        lit = capi.PrtRadianceLitInfo() if (lighting and return_info) else None
         q = capi.PrtRadianceQuery(int(self.max_depth if max_depth is None else max_depth), int(samples),
                                   int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample) & 0xFFFFFFFF)
         try:
@@ -1179,9 +1183,12 @@ class HipWavefrontRenderer:
             total = torch.zeros((n, 3), dtype=torch.float32, device=o.device)
             seg = torch.zeros(n, dtype=torch.int32, device=o.device)
             # (n == 0 still goes through the library: it refuses a bad query whatever the count)
-            self._on_context_stream(lambda: capi.lib().prt_radiance_device(
-                self._ctx, C.byref(q), n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                C.c_void_p(rng.data_ptr() if rng is not None else None), C.c_void_p(total.data_ptr()), C.c_void_p(seg.data_ptr())))
+            args = (self._ctx, C.byref(q), n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                    C.c_void_p(rng.data_ptr() if rng is not None else None), C.c_void_p(total.data_ptr()), C.c_void_p(seg.data_ptr()))
+            if lighting:
+                self._on_context_stream(lambda: capi.lib().prt_radiance_lit_device(*args, C.byref(lit) if lit is not None else None))
+            else:
+                self._on_context_stream(lambda: capi.lib().prt_radiance_device(*args))
             # (a tensor divisor: torch turns a division by a Python number into a multiplication by its reciprocal)
             mean = total / torch.full((1, 1), float(q.samples), dtype=torch.float32, device=o.device)
         else:
@@ -1196,20 +1203,30 @@ class HipWavefrontRenderer:
                     raise ValueError(f"rng_state: {rng.size} states for {n} rays")
             total = np.zeros((n, 3), np.float32)
             seg = np.zeros(n, np.uint32)
-            self._check(capi.lib().prt_radiance(self._ctx, C.byref(q), n, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp),
-                                                rng.ctypes.data_as(_u32p) if rng is not None else None,
-                                                total.ctypes.data_as(_fp), seg.ctypes.data_as(_u32p)))
+            args = (self._ctx, C.byref(q), n, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp),
+                    rng.ctypes.data_as(_u32p) if rng is not None else None, total.ctypes.data_as(_fp), seg.ctypes.data_as(_u32p))
+            if lighting:
+                self._check(capi.lib().prt_radiance_lit(*args, C.byref(lit) if lit is not None else None))
+            else:
+                self._check(capi.lib().prt_radiance(*args))
             mean = total / np.float32(q.samples)
         if return_info:
-            return mean, {"sum": total, "segments": seg, "rng_state": rng}
+            info = {"sum": total, "segments": seg, "rng_state": rng}
+            if lit is not None:
+                info["shadow_rays"] = int(lit.shadow_rays)
+                info["shadow_occluded"] = int(lit.shadow_occluded)
+            return mean, info
         return mean
 
-    def render_probe(self, position, H: int, W: int, samples: int = 1, seed=None, first_sample: int = 0, max_depth=None) -> np.ndarray:
+    def render_probe(self, position, H: int, W: int, samples: int = 1, seed=None, first_sample: int = 0, max_depth=None,
+                     lighting: bool = False) -> np.ndarray:
         """A lat-long radiance probe at `position`: [H, W, 3] float32, the mean radiance along probe_directions(H, W),
-        texel index = ray index.  The layout is set_environment's, so a probe of one scene can light another."""
+        texel index = ray index.  The layout is set_environment's, so a probe of one scene can light another.
+        lighting: radiance()'s."""
         d = probe_directions(H, W).reshape(-1, 3)
         o = np.broadcast_to(_f32(position).reshape(1, 3), d.shape)
-        return self.radiance(o, d, samples=samples, seed=seed, first_sample=first_sample, max_depth=max_depth).reshape(H, W, 3)
+        return self.radiance(o, d, samples=samples, seed=seed, first_sample=first_sample, max_depth=max_depth,
+                             lighting=lighting).reshape(H, W, 3)
 
     def enable_timing(self, on: bool = True):
         self._check(capi.lib().prt_enable_timing(self._ctx, int(on)))

@@ -2,7 +2,7 @@
 """Rays per second of the radiance query (prt_radiance_device) on the 1080p camera rays of C3, beside a one-sample render of
 the same frame at the same depth.
 
-  python tools/radiance_rate.py [--config C3 --reps 7 --out profiles/radiance_rate.json]
+  python tools/radiance_rate.py [--config C3 --reps 7 --out profiles/radiance_rate.json] [--lighting mis|nee]
 
 The query gets the film's own pixel-centre rays as device tensors, ray index = pixel index, one sample, the renderer's seed:
 the paths the render follows (tests/test_gpu_radiance.py holds the two to the same bits).  Both calls are synchronous; the
@@ -11,7 +11,12 @@ per bounce, no compact primary rays, no shared primary walk, no last-segment rou
 
 Per-round times: the query is timed again at max_depth 1 .. depth; the paths of depth k are the first k rounds of depth
 k + 1, so the differences are what each further round costs (query pipeline over the live rays + step + the count's wait).
-The segments each depth walked are reported with them.  One JSON document goes to --out; every row is printed."""
+The segments each depth walked are reported with them.  One JSON document goes to --out; every row is printed.
+
+--lighting mis|nee sets that lighting mode and times the light-sampled query (radiance(lighting=True), prt_radiance_lit_device)
+in the place of the unlit one, per depth as above, beside a one-sample render under the same lighting and beside the unlit
+query at the full depth; the shadow rays the lit query cast and their rate are reported (default --out:
+profiles/radiance_lit_rate.json)."""
 import argparse
 import json
 import os
@@ -28,8 +33,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="C3")
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "radiance_rate.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--lighting", choices=("mis", "nee"), default=None)
     a = ap.parse_args()
+    lit = a.lighting is not None
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "radiance_lit_rate.json" if lit else "radiance_rate.json")
 
     import torch
 
@@ -41,6 +50,8 @@ def main():
     r = prt.HipWavefrontRenderer(device=0, max_depth=depth, seed=1)
     film = prt.Film(W, H)
     r.Init(film, scene, cam)
+    if lit:
+        r.set_lighting(a.lighting)
     y, x = np.mgrid[0:H, 0:W]
     o, d = r.camera_rays((x.ravel() + 0.5).astype(np.float32), (y.ravel() + 0.5).astype(np.float32))
     o, d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
@@ -60,18 +71,28 @@ def main():
         ms, _ = timed(r.ProgressiveRender)
         return ms, int(r.stats().rays_total)
 
+    shadow = [0, 0]
+
     def query(k):
-        ms, out = timed(lambda: r.radiance(o, d, max_depth=k, return_info=True))
+        ms, out = timed(lambda: r.radiance(o, d, max_depth=k, return_info=True, lighting=lit))
+        if lit and k == depth:
+            shadow[:] = out[1]["shadow_rays"], out[1]["shadow_occluded"]
         return ms, int(out[1]["segments"].sum(dtype=torch.int64).item())
 
+    def unlit_query():
+        return timed(lambda: r.radiance(o, d, max_depth=depth))[0]
+
     render()
+    unlit_query()
     for k in range(1, depth + 1):      # warm: allocations, the first launch of every kernel
         query(k)
-    t_render, t_query = [], {k: [] for k in range(1, depth + 1)}
+    t_render, t_unlit, t_query = [], [], {k: [] for k in range(1, depth + 1)}
     rays = segs = None
     for i in range(a.reps):
         ms, rays = render()
         t_render.append(ms)
+        if lit:
+            t_unlit.append(unlit_query())
         for k in (range(1, depth + 1) if i % 2 == 0 else range(depth, 0, -1)):
             ms, s = query(k)
             t_query[k].append(ms)
@@ -85,6 +106,9 @@ def main():
                query_ms=med[depth], query_segments=segs, query_mrays_s=segs / med[depth] / 1e3, query_over_render=med[depth] / mr,
                query_ms_min_max=[float(min(t_query[depth])), float(max(t_query[depth]))],
                render_ms_min_max=[float(min(t_render)), float(max(t_render))], rounds=rounds)
+    if lit:
+        doc.update(lighting=a.lighting, unlit_query_ms=float(np.median(t_unlit)), shadow_rays=int(shadow[0]), shadow_occluded=int(shadow[1]),
+                   shadow_mrays_s=shadow[0] / med[depth] / 1e3)
     print(json.dumps(doc), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
