@@ -1089,6 +1089,11 @@ int prt_scatter(PrtContext* ctx, uint32_t n, const float* in_dirs, const PrtHit*
  *    normalised: fp32, no contraction, the order of the shade kernels.  The material's draws are made on the last
  *    segment too (the state written back is the reference's; a render skips them there, its radiance is the same).
  *  Miss: L += thr * sky, or thr * the environment image's texel of the direction while one is set (prt_set_environment).
+ *    The lookup is defined for unit directions and the caller's direction is used as given, so on the caller's own
+ *    segment (k = 0) the texel is that of the normalised direction: with l2 = fl((x*x + y*y) + z*z) in fp32, where
+ *    |l2 - 1| > 2^-20 the lookup takes d * (1 / sqrt(l2)) (glm::normalize), otherwise d itself.  A direction normalised
+ *    in fp32 has l2 within about 2^-22 of 1 and is looked up bit for bit as given.  The path's direction is not touched:
+ *    hits, scatter and segments are the reference's for the direction as given.  Later segments are unit by construction.
  *  Textures: a textured Lambertian or Metal takes its albedo from the binding at the hit's UV, as a render does.
  *  Sampling: PrtSampling.rr_depth (one draw after the material's own, before segment index >= rr_depth) and clamp (on the
  *    radiance a path delivers) apply as in a render; jitter has no meaning here and is ignored.  So is the lens.
@@ -1129,7 +1134,8 @@ int prt_radiance_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, 
  *    prt_radiance's (the light stream never advances the path's state), and the path carries what a lit render's path
  *    carries.  Per segment k, with pb = -1 at k = 0 and the light sum lsum = 0:
  *    Miss: L += thr * sky; under an environment image thr * its texel, times the MIS weight of (d, pb) where that is not 1
- *      (pb < 0: weight 1).  The path ends.
+ *      (pb < 0: weight 1).  At k = 0 the texel is looked up by prt_radiance's rule for the caller's own segment: the
+ *      normalised direction where |l2 - 1| > 2^-20, else the direction as given.  The path ends.
  *    Hit: key = the state before the material's draws; Material::Scatter as in the unlit query, on the last segment too;
  *      L += thr * emitted, times the weight 1 - w_L of the emitter where the material is Emissive, pb >= 0, the emitter is
  *      analytic or the MESH bit is set, and the weight is not 1 (the segment's own origin and direction, the hit's d2).

@@ -12,6 +12,15 @@ namespace {
 
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
 
+// The direction whose texel a miss of the caller's own segment reads (include/prt.h "Radiance query", Miss).  env_texel is
+// written for unit directions and the caller's is used as given, so: l2 = fl((x*x + y*y) + z*z); |l2 - 1| > 2^-20: the
+// normalised direction, else the direction as it is.  A direction normalised in fp32 has l2 within about 2^-22 of 1 and
+// keeps its bits.  Every later segment's direction is normalised by the step.
+__device__ inline f3 rd_first_lookup_dir(f3 d) {
+    const float l2 = dot3(d, d);
+    return __builtin_fabsf(l2 - 1.0f) > 9.5367431640625e-07f ? normalize3(d) : d;  // 2^-20
+}
+
 // The chunk's paths, sample-major.  The ray is copied per sample so that a round's list is what the ray-query pipeline
 // packs from and the compaction moves ray and state together.
 __global__ __launch_bounds__(256) void k_rd_start(uint32_t n, uint32_t cs, uint32_t sample0, uint32_t seed, const float* __restrict__ origins,
@@ -52,7 +61,7 @@ __global__ __launch_bounds__(256) void k_rd_step(uint32_t n, PrtRadianceList in,
         d = mk3(in.d[3 * (size_t)j], in.d[3 * (size_t)j + 1], in.d[3 * (size_t)j + 2]);
         const PrtHit h = a.hits[j];
         if (h.prim < 0) {  // a miss: the environment image's texel, or the constant sky
-            L = L + thr * (a.env.W ? env_radiance(a.env, d) : mk3(a.sky[0], a.sky[1], a.sky[2]));
+            L = L + thr * (a.env.W ? env_radiance(a.env, a.round == 0u ? rd_first_lookup_dir(d) : d) : mk3(a.sky[0], a.sky[1], a.sky[2]));
         } else {
             const uint32_t type = a.mat_type[h.material_id];
             float4 rgbs = a.mat_rgbs[h.material_id];

@@ -13,6 +13,13 @@ namespace {
 
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
 
+// prt_radiance.hip's rd_first_lookup_dir: the direction whose texel a miss of the caller's own segment reads.
+// l2 = fl((x*x + y*y) + z*z); |l2 - 1| > 2^-20: the normalised direction, else the direction as it is.
+__device__ inline f3 rdl_first_lookup_dir(f3 d) {
+    const float l2 = dot3(d, d);
+    return __builtin_fabsf(l2 - 1.0f) > 9.5367431640625e-07f ? normalize3(d) : d;  // 2^-20
+}
+
 // k_rd_start, and pb = -1: the caller's ray was scattered by no vertex.
 __global__ __launch_bounds__(256) void k_rdl_start(uint32_t n, uint32_t cs, uint32_t sample0, uint32_t seed, const float* __restrict__ origins,
                                                    const float* __restrict__ dirs, const uint32_t* __restrict__ rng_state, PrtRadianceLitList out) {
@@ -61,7 +68,7 @@ __global__ __launch_bounds__(256) void k_rdl_step(uint32_t n, PrtRadianceLitList
         if (h.prim < 0) {  // a miss: the environment's texel, weighted after a Lambertian vertex, or the constant sky
             if (ENV) {
                 float wb;
-                f3 term = thr * env_miss(a.env, A.lt.mode, d, pb_prev, wb);
+                f3 term = thr * env_miss(a.env, A.lt.mode, a.round == 0u ? rdl_first_lookup_dir(d) : d, pb_prev, wb);
                 if (wb != 1.0f) term = term * wb;
                 L = L + term;
             } else {

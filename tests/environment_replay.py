@@ -204,9 +204,11 @@ def miss_weight(env: EnvMap, t_env, d32, i, j, pb, mode, wrong=None):
 
 # ---- the replay ------------------------------------------------------------------------------------------------------------
 def replay(scene, env: EnvMap, cam, W, H, max_depth, seed, samples, mode, sampling=(0, 0, 0.0), pix=None, use_bvh=False,
-           n_threads=None, wrong=None, osc=None, stability=True, sources="analytic"):
+           n_threads=None, wrong=None, osc=None, stability=True, sources="analytic", start=None):
     """mesh_light_replay.replay under an environment light; mode "off" | "mis" | "nee".  The same Replay record, plus
-    `miss_unstable` [n] (the path ends in a miss within EDGE of a texel edge), `n_env_samples`, `t_env`."""
+    `miss_unstable` [n] (the path ends in a miss within EDGE of a texel edge), `n_env_samples`, `t_env`.  start
+    (lighting_replay.walk): a caller's own segment need not be unit, and its miss looks up the direction normalised in
+    float64 (include/prt.h "Radiance query", Miss)."""
     assert wrong is None or wrong in WRONG, wrong
     osc = osc or orc.OracleScene(scene.desc())
     ls = mr.MeshLightSet(scene, sources)
@@ -222,7 +224,8 @@ def replay(scene, env: EnvMap, cam, W, H, max_depth, seed, samples, mode, sampli
     samples = list(samples)
     apix = np.tile(pix, len(samples))
     asamp = np.repeat(np.asarray(samples, np.int64), len(pix))
-    verts, delivered, last, segs = walk(scene, osc, cam, W, H, max_depth, seed, apix, asamp, sampling, use_bvh, n_threads)
+    verts, delivered, last, segs = walk(scene, osc, cam, W, H, max_depth, seed, apix, asamp, sampling, use_bvh, n_threads,
+                                        start=start)
     n = len(apix)
     r = lr.Replay()
     r.pix, r.samp, r.segments, r.last, r.lights, r.t_env = apix, asamp, segs, last, ls, te
@@ -245,7 +248,11 @@ def replay(scene, env: EnvMap, cam, W, H, max_depth, seed, samples, mode, sampli
         # a miss delivers thr * env[texel of d]: one fp32 product (the walker's term used the constant sky)
         ms = np.nonzero(hits["prim"] < 0)[0]
         if len(ms):
-            mi, mj, edge = lookup64(env, v["d"][ms])
+            dm = v["d"][ms].astype(np.float64)
+            if start is not None and k == 0:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    dm = dm / np.sqrt((dm * dm).sum(1))[:, None]
+            mi, mj, edge = lookup64(env, dm)
             t32 = (v["thr"][ms] * env.rgb[mi, mj]).astype(np.float32)
             term[ms] = t32.astype(np.float64)
             delivered[path[ms]] = lr._clamp32(t32, clamp)

@@ -263,8 +263,23 @@ def primary_rays(cam_desc, W, pix, rng, jitter):
     return o, d, rng
 
 
-def walk(scene, osc, cam, W, H, max_depth, seed, pix, samp, sampling=(0, 0, 0.0), use_bvh=False, n_threads=None):
-    """The lighting-off paths of pixel samples (pix[i], samp[i]), bounce by bounce, in fp32.
+def start_rays(start, pix, samp, seed):
+    """The first segments and RNG states of paths started from caller-supplied rays (include/prt.h "Radiance query"):
+    start = (o, d) or (o, d, rng_state), arrays over the rays; pix[i] is a ray index.  The segment is (o[pix], d[pix]) exactly
+    as given, not normalised.  Without states a path starts from path_seed(ray index, sample, seed); with states from
+    rng_state[pix], and every path must be of one sample index."""
+    o, d = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in start[:2])
+    if len(start) > 2 and start[2] is not None:
+        assert len(np.unique(np.asarray(samp))) <= 1, "rng_state given: samples must be one"
+        rng = np.ascontiguousarray(start[2], np.uint32)[pix].copy()
+    else:
+        rng = _path_seeds(pix, samp, seed)
+    return o[pix].copy(), d[pix].copy(), rng
+
+
+def walk(scene, osc, cam, W, H, max_depth, seed, pix, samp, sampling=(0, 0, 0.0), use_bvh=False, n_threads=None, start=None):
+    """The lighting-off paths of pixel samples (pix[i], samp[i]), bounce by bounce, in fp32.  start (start_rays): the paths of
+    caller-supplied rays instead, pix = ray indices; the camera and the jitter are then ignored.
 
     Returns (vertices, delivered [n, 3] float32, last [n] int, segments).  vertices[k] is a dict of arrays over the paths
     that trace segment k: `path` (index into pix), `hit` (HIT_DTYPE; prim < 0 = the sky), `o`, `d` (the segment), `thr`
@@ -276,8 +291,11 @@ def walk(scene, osc, cam, W, H, max_depth, seed, pix, samp, sampling=(0, 0, 0.0)
     cd = cam.desc()
     pix = np.asarray(pix, np.int64)
     n = len(pix)
-    rng = _path_seeds(pix, samp, seed)
-    o, d, rng = primary_rays(cd, W, pix, rng, jitter)
+    if start is not None:
+        o, d, rng = start_rays(start, pix, samp, seed)
+    else:
+        rng = _path_seeds(pix, samp, seed)
+        o, d, rng = primary_rays(cd, W, pix, rng, jitter)
     thr = np.ones((n, 3), np.float32)
     path = np.arange(n)
     delivered = np.zeros((n, 3), np.float32)
@@ -403,9 +421,10 @@ class Replay:
 
 
 def replay(scene, cam, W, H, max_depth, seed, samples, mode, sampling=(0, 0, 0.0), pix=None, use_bvh=False, n_threads=None,
-           wrong=None, osc=None, stability=True):
+           wrong=None, osc=None, stability=True, start=None):
     """Float64 value of every pixel sample of a light-sampled frame.  samples: iterable of sample indices; pix: pixel indices
-    (default: the whole frame); mode "mis" | "nee" | "off"."""
+    (default: the whole frame); mode "mis" | "nee" | "off".  start: walk's (the light-sampled radiance query: pix = ray
+    indices)."""
     assert wrong is None or wrong in WRONG, wrong
     osc = osc or orc.OracleScene(scene.desc())
     ls = LightSet(scene)
@@ -417,7 +436,8 @@ def replay(scene, cam, W, H, max_depth, seed, samples, mode, sampling=(0, 0, 0.0
     samples = list(samples)
     apix = np.tile(pix, len(samples))
     asamp = np.repeat(np.asarray(samples, np.int64), len(pix))
-    verts, delivered, last, segs = walk(scene, osc, cam, W, H, max_depth, seed, apix, asamp, sampling, use_bvh, n_threads)
+    verts, delivered, last, segs = walk(scene, osc, cam, W, H, max_depth, seed, apix, asamp, sampling, use_bvh, n_threads,
+                                        start=start)
     n = len(apix)
     r = Replay()
     r.pix, r.samp, r.delivered, r.segments, r.last, r.lights = apix, asamp, delivered, segs, last, ls

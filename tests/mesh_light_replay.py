@@ -232,7 +232,7 @@ def hit_weight(ls: MeshLightSet, prim, x, w, d2, pb, mode, wrong=None):
 
 
 def replay(scene, cam, W, H, max_depth, seed, samples, mode, sampling=(0, 0, 0.0), pix=None, use_bvh=False, n_threads=None,
-           wrong=None, osc=None, stability=True, sources="all"):
+           wrong=None, osc=None, stability=True, sources="all", start=None):
     """lighting_replay.replay with the light set of prt_set_light_sources(sources); the same Replay record."""
     assert wrong is None or wrong in WRONG, wrong
     osc = osc or orc.OracleScene(scene.desc())
@@ -245,7 +245,8 @@ def replay(scene, cam, W, H, max_depth, seed, samples, mode, sampling=(0, 0, 0.0
     samples = list(samples)
     apix = np.tile(pix, len(samples))
     asamp = np.repeat(np.asarray(samples, np.int64), len(pix))
-    verts, delivered, last, segs = walk(scene, osc, cam, W, H, max_depth, seed, apix, asamp, sampling, use_bvh, n_threads)
+    verts, delivered, last, segs = walk(scene, osc, cam, W, H, max_depth, seed, apix, asamp, sampling, use_bvh, n_threads,
+                                        start=start)
     n = len(apix)
     r = lr.Replay()
     r.pix, r.samp, r.delivered, r.segments, r.last, r.lights = apix, asamp, delivered, segs, last, ls

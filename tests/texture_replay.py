@@ -210,8 +210,8 @@ MISS_RGB = None   # lighting off under an environment image: a function of the m
 #                   texel edge, and a frame compared bit for bit needs every miss)
 
 
-def walk(scene, osc, cam, W, H, max_depth, seed, pix, samp, sampling=(0, 0, 0.0), use_bvh=False, n_threads=None):
-    """lighting_replay.walk of a scene with textures (Scene.AddTexture / SetMaterialTexture): the same record; at a vertex whose
+def walk(scene, osc, cam, W, H, max_depth, seed, pix, samp, sampling=(0, 0, 0.0), use_bvh=False, n_threads=None, start=None):
+    """lighting_replay.walk (its `start` too) of a scene with textures (Scene.AddTexture / SetMaterialTexture): the same record; at a vertex whose
     material is textured the attenuation and the `albedo` entry are the looked-up colour.  Every record also carries `uv`."""
     ts = TexScene(scene)
     jitter, rr_depth, clamp = int(sampling[0]), int(sampling[1]), float(sampling[2])
@@ -219,8 +219,11 @@ def walk(scene, osc, cam, W, H, max_depth, seed, pix, samp, sampling=(0, 0, 0.0)
     cd = cam.desc()
     pix = np.asarray(pix, np.int64)
     n = len(pix)
-    rng = lr._path_seeds(pix, samp, seed)
-    o, d, rng = lr.primary_rays(cd, W, pix, rng, jitter)
+    if start is not None:
+        o, d, rng = lr.start_rays(start, pix, samp, seed)
+    else:
+        rng = lr._path_seeds(pix, samp, seed)
+        o, d, rng = lr.primary_rays(cd, W, pix, rng, jitter)
     thr = np.ones((n, 3), F)
     path = np.arange(n)
     delivered = np.zeros((n, 3), F)
