@@ -405,6 +405,28 @@ def canonical(n8, tris, n_prims):
                 child=np.where(S["inner"], new_index[np.minimum(S["child"], len(n8) - 1)], -1))
 
 
+def as_read_back(tree, tv, n_prims=2):
+    """The canonical tree as the node / record arrays the library would hand back (records in leaf order)."""
+    N = len(tree["imask"])
+    n8 = np.zeros((N, 20), np.uint32)
+    tris = []
+    n8[:, 0:3] = tree["origin"]
+    n8[:, 3] = ((tree["exp"] + 127) << (8 * np.arange(3))[None, :]).sum(axis=1) | (tree["imask"] << 24)
+    for n in range(N):
+        kids = tree["child"][n][tree["child"][n] >= 0]
+        n8[n, 4] = kids[0] if len(kids) else 0
+        n8[n, 5] = len(tris)
+        for s in range(8):
+            for t in tree["tri"][n, s][tree["tri"][n, s] >= 0]:
+                tris.append(np.concatenate([tv[t, 0], np.asarray([n_prims + t], np.uint32).view(F), tv[t, 1], [F(0)], tv[t, 2], [F(0)]]))
+    for w in range(2):
+        n8[:, 6 + w] = (tree["meta"][:, 4 * w:4 * w + 4] << (8 * np.arange(4))[None, :]).sum(axis=1)
+    for pl in range(6):
+        for w in range(2):
+            n8[:, 8 + 2 * pl + w] = (tree["planes"][:, pl, 4 * w:4 * w + 4] << (8 * np.arange(4))[None, :]).sum(axis=1)
+    return n8, np.asarray(tris, F).reshape(-1, 12)
+
+
 def assert_same_tree(got, want, what=""):
     """Field by field, with the first differing node in the message."""
     assert len(got["imask"]) == len(want["imask"]), f"{what}: {len(got['imask'])} nodes, the replay has {len(want['imask'])}"

@@ -289,28 +289,6 @@ def test_quantization_rule_against_rational_arithmetic():
 
 
 # ---- the whole replay on small meshes: a valid, tight tree ----------------------------------------------------------------------
-def _as_read_back(tree, tv, n_prims=2):
-    """The canonical tree as the node / record arrays the library would hand back (records in leaf order)."""
-    N = len(tree["imask"])
-    n8 = np.zeros((N, 20), np.uint32)
-    tris = []
-    n8[:, 0:3] = tree["origin"]
-    n8[:, 3] = ((tree["exp"] + 127) << (8 * np.arange(3))[None, :]).sum(axis=1) | (tree["imask"] << 24)
-    for n in range(N):
-        kids = tree["child"][n][tree["child"][n] >= 0]
-        n8[n, 4] = kids[0] if len(kids) else 0
-        n8[n, 5] = len(tris)
-        for s in range(8):
-            for t in tree["tri"][n, s][tree["tri"][n, s] >= 0]:
-                tris.append(np.concatenate([tv[t, 0], np.asarray([n_prims + t], np.uint32).view(F), tv[t, 1], [F(0)], tv[t, 2], [F(0)]]))
-    for w in range(2):
-        n8[:, 6 + w] = (tree["meta"][:, 4 * w:4 * w + 4] << (8 * np.arange(4))[None, :]).sum(axis=1)
-    for pl in range(6):
-        for w in range(2):
-            n8[:, 8 + 2 * pl + w] = (tree["planes"][:, pl, 4 * w:4 * w + 4] << (8 * np.arange(4))[None, :]).sum(axis=1)
-    return n8, np.asarray(tris, F).reshape(-1, 12)
-
-
 @pytest.mark.parametrize("n", [1, 2, 3, 4, 9, 300])
 @pytest.mark.parametrize("top", ["host", "device"])
 def test_replayed_tree_is_a_valid_tight_tree_and_survives_the_round_trip(n, top):
@@ -321,7 +299,7 @@ def test_replayed_tree_is_a_valid_tight_tree_and_survives_the_round_trip(n, top)
         tv[100:140] = tv[100]   # duplicated triangles
         tv[:, :, 1][200:] = F(0.0)
     tree = pr.replay(tv, *pr.centroid_bounds(tv), top=top)
-    n8, tris = _as_read_back(tree, tv)
+    n8, tris = pr.as_read_back(tree, tv)
     fill, _ = util.check_bvh8(n8, tris)
     assert util.check_bvh8_tight(n8, tris) == len(n8)
     assert sorted(tree["tri"][tree["tri"] >= 0].tolist()) == list(range(n))
