@@ -504,6 +504,47 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src);
  * usable.  Without the 4-wide tree no kernel instance holds its deepest rays (the deepest stack, 15 entries, covers 16
  * levels); the caller rebuilds with prt_set_scene. */
 int prt_refit_meshes(PrtContext* ctx, const PrtMesh* meshes, uint32_t n_meshes);
+/* Refit from device arrays: prt_refit_meshes for vertex arrays that are on the context's device already (the output of a
+ * skinning, cloth or simulation step there).  meshes[m] is world-space mesh m of the current scene: the vertex counts and
+ * the index buffers are those of prt_set_scene, which the scene kept; nothing is read from the host.  The scenes it takes,
+ * the scene it leaves and the rendered results are those of prt_refit_meshes with the same arrays on the host, bit for
+ * bit; so are the refusals (placed copies, no 8-wide tree, depth8 > 16, a wrong n_meshes), each with the scene intact.
+ *   Stream order: the arrays are read in stream order on the context's stream (prt_set_stream): a producer enqueued on
+ *   that stream needs no synchronisation before the call.  The call is synchronous on return.
+ *   Validation: a first device pass finds the largest |coordinate| of the referenced vertices (prt_refit_meshes' rule,
+ *   so the culling pad is the same) and any non-finite position or supplied normal; its few bytes are read before anything
+ *   of the scene is written.  A non-finite value is PRT_ERR_INVALID with the scene exactly what it was and usable.
+ *   normals == NULL: the mesh gets area-weighted vertex normals computed on the device by the rule of prt_mesh_create
+ *   without normals, bit for bit: per face e1 = b - a, e2 = c - a and e1 x e2 in double without contraction; per vertex the
+ *   double sum over its incident corners in ascending face order (a face's repeated vertex once per corner);
+ *   n = (float)(sum / |sum|), and (0, 1, 0) where |sum| is not > 0.  No floating-point atomics: the order is fixed.
+ *   Host copies: the tree and the records are NOT read back by the call; prt_bvh_read8, prt_bvh_read, prt_clone_scene and
+ *   prt_refit_meshes fetch them when they need them (PrtRefitInfo.host_copies_stale).  With the MESH bit of
+ *   prt_set_light_sources in use or not, the candidate table follows as after prt_refit_meshes; only the emissive
+ *   world-space triangles' vertices (36 bytes each) come back for it.
+ *   What the scene keeps: index and incident-corner tables, the tree's level lists and the refit's working arrays go to the
+ *   device at the first call after prt_set_scene / prt_clone_scene and stay until the scene goes (24 bytes per
+ *   triangle, 16 per vertex, 220 per node, 40 per emissive triangle); from the second call on nothing is allocated and
+ *   nothing is copied up.
+ * Not offered: the group (prt_group_*); a device array lives on one device. */
+typedef struct PrtMeshDeviceArrays {
+    const float* positions;  /* DEVICE pointer, n_vertices*3 floats of world-space mesh m, as at prt_set_scene */
+    const float* normals;    /* DEVICE pointer, n_vertices*3 floats, or NULL: computed on the device (above) */
+} PrtMeshDeviceArrays;
+int prt_refit_meshes_device(PrtContext* ctx, const PrtMeshDeviceArrays* meshes, uint32_t n_meshes);
+/* vertex normals of world-space mesh `mesh` of the current scene for positions on the device, into a device array
+ * (n_vertices*3 floats each; the rule above; stream order as above, synchronous on return; the scene is not touched) */
+int prt_mesh_normals_device(PrtContext* ctx, uint32_t mesh, const float* positions, float* normals_out);
+typedef struct PrtRefitInfo {
+    uint32_t refits;            /* both forms, since prt_set_scene (= PrtBvhInfo.refits) */
+    uint32_t last_form;         /* 0 none, 1 host arrays, 2 device arrays */
+    uint32_t normals_computed;  /* meshes whose normals the last call computed on the device */
+    uint32_t host_copies_stale; /* 1: the host copies of tree and records lag behind the device (refreshed on demand) */
+    float device_ms, wall_ms;   /* of the last call */
+    uint64_t h2d_bytes, d2h_bytes; /* what the last call moved over the bus, every copy it issued counted */
+} PrtRefitInfo;
+/* Works on a host-only context and before the first refit (zeros). */
+int prt_refit_info(PrtContext* ctx, PrtRefitInfo* out);
 /* Moving placed copies (rigid-body animation for the price of the top level; the reference's OptiX backend rebuilds its
  * instance level only when transforms change, src/backend/optix/renderer.cpp:703-871): instances[i] replaces mat / inv of
  * placed copy i of the current scene.  PRT_ERR_INVALID, with the scene exactly what it was and usable: n is not the

@@ -219,6 +219,16 @@ class PrtBvhInfo(C.Structure):
                 ("built_on_device", C.c_uint32), ("refit_ms", C.c_float), ("refits", C.c_uint32)]
 
 
+class PrtMeshDeviceArrays(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p)]
+
+
+class PrtRefitInfo(C.Structure):
+    _fields_ = [("refits", C.c_uint32), ("last_form", C.c_uint32), ("normals_computed", C.c_uint32),
+                ("host_copies_stale", C.c_uint32), ("device_ms", C.c_float), ("wall_ms", C.c_float),
+                ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64)]
+
+
 class PrtInstanceUpdateInfo(C.Structure):
     _fields_ = [("updates", C.c_uint32), ("last_mode", C.c_uint32), ("top_nodes", C.c_uint32), ("top_depth", C.c_uint32),
                 ("last_ms", C.c_float)]
@@ -376,6 +386,9 @@ SIGNATURES = {
     "prt_primary_reuse": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "prt_measure_shade_divergence": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "prt_refit_meshes": (C.c_int, [_vp, C.POINTER(PrtMesh), C.c_uint32]),
+    "prt_refit_meshes_device": (C.c_int, [_vp, C.POINTER(PrtMeshDeviceArrays), C.c_uint32]),
+    "prt_mesh_normals_device": (C.c_int, [_vp, C.c_uint32, _vp, _vp]),
+    "prt_refit_info": (C.c_int, [_vp, C.POINTER(PrtRefitInfo)]),
     "prt_set_instance_transforms": (C.c_int, [_vp, C.POINTER(PrtInstance), C.c_uint32, C.c_uint32]),
     "prt_group_set_instance_transforms": (C.c_int, [_vp, C.POINTER(PrtInstance), C.c_uint32, C.c_uint32]),
     "prt_instance_update_info": (C.c_int, [_vp, C.POINTER(PrtInstanceUpdateInfo)]),

@@ -37,9 +37,46 @@ int prt_sort_rays(hipStream_t st, const float4* ro, const float4* rd, uint32_t n
 // entries); d_verts / d_norms: 9 floats per triangle in INPUT order (d_norms may be null);
 // d_tris / d_nrms: the scene's records in slot order, rewritten in place.  root_box[6] receives the new root bounds.
 // Synchronous.  Returns 0, a hipError_t, or -6 if a box does not fit its node's quantization grid.
+// tally (may be null) grows by the bytes the call copies between host and device.
+struct PrtCopyTally {
+    uint64_t h2d, d2h;
+};
 int prt_gpu_bvh8_refit(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
                        const uint32_t* level_start, uint32_t n_levels, const float* d_verts, const float* d_norms, uint32_t n_tris,
-                       uint32_t n_prims, float4* d_tris, float4* d_nrms, float root_box[6]);
+                       uint32_t n_prims, float4* d_tris, float4* d_nrms, float root_box[6], PrtCopyTally* tally = nullptr);
+
+// ---- refit from device arrays (prt_refit_meshes_device) ----
+// The meshes' vertex arrays: HOST arrays of n_meshes DEVICE pointers (n_vertices x 3 floats each) and the prefixes of
+// PrtRefitTables (prt_scene.h; n_meshes + 1 entries).  The d_* tables below are PrtRefitTables' arrays on the device.
+#define PRT_REFIT_CHUNK 16  // meshes a launch serves; their pointers and ranges are kernel arguments
+struct PrtRefitInputs {
+    uint32_t n_meshes;
+    const float* const* pos;
+    const uint32_t* tri_first;
+    const uint32_t* vert_first;
+};
+// The working arrays of a refit and the tree's level list, kept on the device with the scene:
+// cbox 48 floats, nbox 6 floats per node, 4 counters, level_nodes one entry per node.
+struct PrtRefitScratch {
+    float *cbox, *nbox;
+    uint32_t *counters, *level_nodes;
+};
+// d_out[0] = the bits of the largest finite |position coordinate| over the vertices the index buffers reference,
+// d_out[1] = 1 (a non-finite position) | 2 (a non-finite supplied normal); nrm_supplied: n_meshes device pointers, null
+// entries are skipped.  d_out: 4 words.  Enqueues; returns 0 or a hipError_t.
+int prt_gpu_refit_validate(hipStream_t st, const PrtRefitInputs& in, const float* const* nrm_supplied, const uint32_t* d_corner, uint32_t* d_out);
+// Vertex normals by compute_normals' rule (prt_host.cpp) into nout[m] (n_vertices x 3 floats on the device) for every
+// mesh with nout[m] != null.  Enqueues; returns 0 or a hipError_t.
+int prt_gpu_mesh_normals(hipStream_t st, const PrtRefitInputs& in, float* const* nout, const uint32_t* d_corner, const uint32_t* d_csr_start,
+                         const uint32_t* d_csr_corner);
+// prt_gpu_bvh8_refit with the records gathered through d_corner from `in` and nrm (n_meshes device pointers, none null),
+// over the arrays of `keep` (level_nodes filled).  Synchronous; the same return values.
+int prt_gpu_bvh8_refit_indexed(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_start,
+                               uint32_t n_levels, const PrtRefitInputs& in, const float* const* nrm, const uint32_t* d_corner, uint32_t n_tris,
+                               uint32_t n_prims, float4* d_tris, float4* d_nrms, const PrtRefitScratch& keep, float root_box[6], PrtCopyTally* tally);
+// d_out[9 i ..] = the three vertices of triangle d_light_tris[i] (mesh and face order).  Enqueues; returns 0 or a hipError_t.
+int prt_gpu_light_gather(hipStream_t st, const PrtRefitInputs& in, const uint32_t* d_corner, const uint32_t* d_light_tris, uint32_t n_light_tris,
+                         float* d_out);
 
 // ---- moving placed copies (prt_set_instance_transforms); all three enqueue on `st` and return 0 or a hipError_t ----
 // One thread per top-level leaf slot.  d_xf: 32 floats per placed copy (PrtInstance::mat, ::inv); d_inst_mesh[i]: the row

@@ -1209,22 +1209,30 @@ __global__ void k_refit_boxes(const float4* __restrict__ tris, const uint32_t* _
 }
 }  // namespace
 
-// Boxes bottom-up over records that are in place, then the re-quantization: the part of a refit that both callers share
+// Boxes bottom-up over records that are in place, then the re-quantization: the part of a refit that every caller shares.
+// keep (may be null): the working arrays and the level list a scene holds on the device across calls; without it they
+// are allocated, filled and freed here.  tally (may be null) grows by the bytes copied.
 static int refit_levels(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
-                        const uint32_t* level_start, uint32_t n_levels, const float4* d_tris, float root_box[6]) {
-    float *cbox = nullptr, *nbox = nullptr;
-    uint32_t *counters = nullptr, *d_list = nullptr;
+                        const uint32_t* level_start, uint32_t n_levels, const float4* d_tris, float root_box[6],
+                        const PrtRefitScratch* keep = nullptr, PrtCopyTally* tally = nullptr) {
+    float *cbox = keep ? keep->cbox : nullptr, *nbox = keep ? keep->nbox : nullptr;
+    uint32_t *counters = keep ? keep->counters : nullptr, *d_list = keep ? keep->level_nodes : nullptr;
     auto drop = [&]() {
+        if (keep) return;
         (void)hipFree(cbox);
         (void)hipFree(nbox);
         (void)hipFree(counters);
         (void)hipFree(d_list);
     };
-    hipError_t e = hipMalloc((void**)&cbox, 48 * sizeof(float) * (size_t)n_nodes);
-    if (e == hipSuccess) e = hipMalloc((void**)&nbox, 6 * sizeof(float) * (size_t)n_nodes);
-    if (e == hipSuccess) e = hipMalloc((void**)&counters, 4 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_list, sizeof(uint32_t) * (size_t)n_nodes);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_list, level_nodes, sizeof(uint32_t) * (size_t)n_nodes, hipMemcpyHostToDevice, st);
+    hipError_t e = hipSuccess;
+    if (!keep) {
+        e = hipMalloc((void**)&cbox, 48 * sizeof(float) * (size_t)n_nodes);
+        if (e == hipSuccess) e = hipMalloc((void**)&nbox, 6 * sizeof(float) * (size_t)n_nodes);
+        if (e == hipSuccess) e = hipMalloc((void**)&counters, 4 * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&d_list, sizeof(uint32_t) * (size_t)n_nodes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_list, level_nodes, sizeof(uint32_t) * (size_t)n_nodes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && tally) tally->h2d += sizeof(uint32_t) * (size_t)n_nodes;
+    }
     if (e == hipSuccess) e = hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), st);
     if (e != hipSuccess) {
         drop();
@@ -1242,6 +1250,7 @@ static int refit_levels(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwor
     e = hipMemcpyAsync(flags, counters, sizeof(flags), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(root_box, nbox, 6 * sizeof(float), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (tally) tally->d2h += sizeof(flags) + 6 * sizeof(float);
     drop();
     if (e != hipSuccess) return (int)e;
     return flags[2] ? -6 : 0;  // a box that does not fit its node's 8-bit grid (non-finite or absurdly large coordinates)
@@ -1249,10 +1258,203 @@ static int refit_levels(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwor
 
 int prt_gpu_bvh8_refit(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_nodes,
                        const uint32_t* level_start, uint32_t n_levels, const float* d_verts, const float* d_norms, uint32_t n_tris,
-                       uint32_t n_prims, float4* d_tris, float4* d_nrms, float root_box[6]) {
+                       uint32_t n_prims, float4* d_tris, float4* d_nrms, float root_box[6], PrtCopyTally* tally) {
     if (n_nodes == 0 || n_tris == 0 || n_levels == 0) return 0;
     hipLaunchKernelGGL(k_refit_records, dim3((n_tris + 255u) / 256u), dim3(256), 0, st, d_verts, d_norms, n_tris, n_prims, d_tris, d_nrms);
-    return refit_levels(st, d_nodes8, stride_dwords, n_nodes, level_nodes, level_start, n_levels, (const float4*)d_tris, root_box);
+    return refit_levels(st, d_nodes8, stride_dwords, n_nodes, level_nodes, level_start, n_levels, (const float4*)d_tris, root_box, nullptr, tally);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Refit from device arrays (prt_refit_meshes_device): the meshes' vertex arrays are on the device already, so the records
+// are gathered through the scene's index buffers there.  A launch serves up to PRT_REFIT_CHUNK meshes, whose pointers and
+// ranges travel as kernel arguments (nothing is copied up per call); a thread finds its mesh by comparing against the
+// chunk's prefix, unrolled (no indexed access to the argument block).  All four kernels are gathers, one thread per
+// output element:
+//   k_refit_validate   per corner: the largest |coordinate| and "a non-finite value" over the vertices the index buffers
+//                      reference, which is the set prt_flatten_mesh looks at (block reduction in LDS, integer atomics)
+//   k_mesh_normals     per vertex: compute_normals (prt_host.cpp) through the incident-corner table, in its order, in double
+//   k_refit_indexed    per slot: the triangle / normal records from the vertices of the triangle the record names
+//   k_light_gather     per float: the vertices of the emissive triangles, packed, for the host's candidate table
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+struct RefitChunk {
+    const float* pos[PRT_REFIT_CHUNK];
+    const float* nrm[PRT_REFIT_CHUNK];   // k_refit_validate: the supplied normals or null; k_refit_indexed: every mesh's normals
+    float* nout[PRT_REFIT_CHUNK];        // k_mesh_normals: where the mesh's normals go, null = not asked for
+    uint32_t tri_first[PRT_REFIT_CHUNK]; // entries past the chunk's meshes: 0xFFFFFFFF
+    uint32_t vert_first[PRT_REFIT_CHUNK];
+    uint32_t tri_begin, tri_end, vert_begin, vert_end;  // the chunk's ranges
+};
+struct RefitMesh {
+    const float* pos;
+    const float* nrm;
+    float* nout;
+    uint32_t vert_first;
+};
+__device__ __forceinline__ RefitMesh mesh_of_triangle(const RefitChunk& A, uint32_t t) {
+    RefitMesh r{A.pos[0], A.nrm[0], A.nout[0], A.vert_first[0]};
+#pragma unroll
+    for (int k = 1; k < PRT_REFIT_CHUNK; ++k)
+        if (t >= A.tri_first[k]) r = RefitMesh{A.pos[k], A.nrm[k], A.nout[k], A.vert_first[k]};
+    return r;
+}
+__device__ __forceinline__ RefitMesh mesh_of_vertex(const RefitChunk& A, uint32_t v) {
+    RefitMesh r{A.pos[0], A.nrm[0], A.nout[0], A.vert_first[0]};
+#pragma unroll
+    for (int k = 1; k < PRT_REFIT_CHUNK; ++k)
+        if (v >= A.vert_first[k]) r = RefitMesh{A.pos[k], A.nrm[k], A.nout[k], A.vert_first[k]};
+    return r;
+}
+
+__global__ void __launch_bounds__(256) k_refit_validate(RefitChunk A, const uint32_t* __restrict__ corner, uint32_t* __restrict__ out) {
+    __shared__ uint32_t s_ext[256], s_bad[256];
+    const uint32_t c = 3u * A.tri_begin + blockIdx.x * 256u + threadIdx.x;
+    uint32_t ext = 0u, bad = 0u;  // (the bits of a non-negative float order as the float does)
+    if (c < 3u * A.tri_end) {
+        const RefitMesh M = mesh_of_triangle(A, c / 3u);
+        const size_t v = 3 * (size_t)(corner[c] - M.vert_first);
+        for (int a = 0; a < 3; ++a) {
+            const float p = fabsf(M.pos[v + a]);
+            if (p <= 3.402823466e+38f) ext = max(ext, __float_as_uint(p));
+            else bad |= 1u;
+            if (M.nrm && !(fabsf(M.nrm[v + a]) <= 3.402823466e+38f)) bad |= 2u;
+        }
+    }
+    s_ext[threadIdx.x] = ext;
+    s_bad[threadIdx.x] = bad;
+    __syncthreads();
+    for (uint32_t w = 128u; w > 0u; w >>= 1) {
+        if (threadIdx.x < w) {
+            s_ext[threadIdx.x] = max(s_ext[threadIdx.x], s_ext[threadIdx.x + w]);
+            s_bad[threadIdx.x] |= s_bad[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u) {
+        atomicMax(&out[0], s_ext[0]);
+        if (s_bad[0]) atomicOr(&out[1], s_bad[0]);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_mesh_normals(RefitChunk A, const uint32_t* __restrict__ corner, const uint32_t* __restrict__ csr_start,
+                                                      const uint32_t* __restrict__ csr_corner) {
+    const uint32_t gv = A.vert_begin + blockIdx.x * 256u + threadIdx.x;
+    if (gv >= A.vert_end) return;
+    const RefitMesh M = mesh_of_vertex(A, gv);
+    if (!M.nout) return;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (uint32_t j = csr_start[gv], je = csr_start[gv + 1u]; j < je; ++j) {
+        const size_t f = 3 * (size_t)(csr_corner[j] / 3u);
+        const float* pa = M.pos + 3 * (size_t)(corner[f] - M.vert_first);
+        const float* pb = M.pos + 3 * (size_t)(corner[f + 1] - M.vert_first);
+        const float* pc = M.pos + 3 * (size_t)(corner[f + 2] - M.vert_first);
+        const double e1[3] = {(double)pb[0] - pa[0], (double)pb[1] - pa[1], (double)pb[2] - pa[2]};
+        const double e2[3] = {(double)pc[0] - pa[0], (double)pc[1] - pa[1], (double)pc[2] - pa[2]};
+        acc[0] += e1[1] * e2[2] - e1[2] * e2[1];
+        acc[1] += e1[2] * e2[0] - e1[0] * e2[2];
+        acc[2] += e1[0] * e2[1] - e1[1] * e2[0];
+    }
+    const double l = sqrt(acc[0] * acc[0] + acc[1] * acc[1] + acc[2] * acc[2]);
+    float* n = M.nout + 3 * (size_t)(gv - M.vert_first);
+    const bool ok = l > 0.0;
+    n[0] = ok ? (float)(acc[0] / l) : 0.0f;
+    n[1] = ok ? (float)(acc[1] / l) : 1.0f;
+    n[2] = ok ? (float)(acc[2] / l) : 0.0f;
+}
+
+__global__ void __launch_bounds__(256) k_refit_indexed(RefitChunk A, const uint32_t* __restrict__ corner, uint32_t n, uint32_t n_prims,
+                                                       float4* __restrict__ tris, float4* __restrict__ nrms) {
+    const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
+    if (slot >= n) return;
+    const float4 a = tris[3 * (size_t)slot + 0], b = tris[3 * (size_t)slot + 1];
+    const uint32_t t = __float_as_uint(a.w) - n_prims;
+    if (t < A.tri_begin || t >= A.tri_end) return;  // (another chunk's triangle)
+    const RefitMesh M = mesh_of_triangle(A, t);
+    const size_t i0 = 3 * (size_t)(corner[3 * (size_t)t + 0] - M.vert_first);
+    const size_t i1 = 3 * (size_t)(corner[3 * (size_t)t + 1] - M.vert_first);
+    const size_t i2 = 3 * (size_t)(corner[3 * (size_t)t + 2] - M.vert_first);
+    const float *p = M.pos, *q = M.nrm;
+    tris[3 * (size_t)slot + 0] = make_float4(p[i0], p[i0 + 1], p[i0 + 2], a.w);
+    tris[3 * (size_t)slot + 1] = make_float4(p[i1], p[i1 + 1], p[i1 + 2], b.w);
+    tris[3 * (size_t)slot + 2] = make_float4(p[i2], p[i2 + 1], p[i2 + 2], 0.0f);
+    nrms[3 * (size_t)slot + 0] = make_float4(q[i0], q[i0 + 1], q[i0 + 2], 0.0f);
+    nrms[3 * (size_t)slot + 1] = make_float4(q[i1], q[i1 + 1], q[i1 + 2], 0.0f);
+    nrms[3 * (size_t)slot + 2] = make_float4(q[i2], q[i2 + 1], q[i2 + 2], 0.0f);
+}
+
+__global__ void __launch_bounds__(256) k_light_gather(RefitChunk A, const uint32_t* __restrict__ corner, const uint32_t* __restrict__ light_tris,
+                                                      uint32_t n_floats, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_floats) return;
+    const uint32_t t = light_tris[i / 9u], k = i % 9u;
+    if (t < A.tri_begin || t >= A.tri_end) return;
+    const RefitMesh M = mesh_of_triangle(A, t);
+    out[i] = M.pos[3 * (size_t)(corner[3 * (size_t)t + k / 3u] - M.vert_first) + k % 3u];
+}
+
+// The chunk of meshes [m0, m0 + PRT_REFIT_CHUNK) of `in` as a kernel argument
+RefitChunk refit_chunk(const PrtRefitInputs& in, uint32_t m0, const float* const* nrm, float* const* nout) {
+    RefitChunk A{};
+    const uint32_t cnt = std::min<uint32_t>(PRT_REFIT_CHUNK, in.n_meshes - m0);
+    for (uint32_t k = 0; k < PRT_REFIT_CHUNK; ++k) {
+        const bool on = k < cnt;
+        A.pos[k] = on ? in.pos[m0 + k] : nullptr;
+        A.nrm[k] = on && nrm ? nrm[m0 + k] : nullptr;
+        A.nout[k] = on && nout ? nout[m0 + k] : nullptr;
+        A.tri_first[k] = on ? in.tri_first[m0 + k] : 0xFFFFFFFFu;
+        A.vert_first[k] = on ? in.vert_first[m0 + k] : 0xFFFFFFFFu;
+    }
+    A.tri_begin = in.tri_first[m0];
+    A.tri_end = in.tri_first[m0 + cnt];
+    A.vert_begin = in.vert_first[m0];
+    A.vert_end = in.vert_first[m0 + cnt];
+    return A;
+}
+}  // namespace
+
+int prt_gpu_refit_validate(hipStream_t st, const PrtRefitInputs& in, const float* const* nrm_supplied, const uint32_t* d_corner, uint32_t* d_out) {
+    hipError_t e = hipMemsetAsync(d_out, 0, 4 * sizeof(uint32_t), st);
+    if (e != hipSuccess) return (int)e;
+    for (uint32_t m0 = 0; m0 < in.n_meshes; m0 += PRT_REFIT_CHUNK) {
+        const RefitChunk A = refit_chunk(in, m0, nrm_supplied, nullptr);
+        const uint32_t n = 3u * (A.tri_end - A.tri_begin);
+        if (n) hipLaunchKernelGGL(k_refit_validate, dim3((n + 255u) / 256u), dim3(256), 0, st, A, d_corner, d_out);
+    }
+    return (int)hipGetLastError();
+}
+
+int prt_gpu_mesh_normals(hipStream_t st, const PrtRefitInputs& in, float* const* nout, const uint32_t* d_corner, const uint32_t* d_csr_start,
+                         const uint32_t* d_csr_corner) {
+    for (uint32_t m0 = 0; m0 < in.n_meshes; m0 += PRT_REFIT_CHUNK) {
+        const RefitChunk A = refit_chunk(in, m0, nullptr, nout);
+        bool any = false;
+        for (uint32_t k = 0; k < PRT_REFIT_CHUNK; ++k) any = any || A.nout[k];
+        const uint32_t n = A.vert_end - A.vert_begin;
+        if (n && any) hipLaunchKernelGGL(k_mesh_normals, dim3((n + 255u) / 256u), dim3(256), 0, st, A, d_corner, d_csr_start, d_csr_corner);
+    }
+    return (int)hipGetLastError();
+}
+
+int prt_gpu_bvh8_refit_indexed(hipStream_t st, uint32_t* d_nodes8, uint32_t stride_dwords, uint32_t n_nodes, const uint32_t* level_start,
+                               uint32_t n_levels, const PrtRefitInputs& in, const float* const* nrm, const uint32_t* d_corner, uint32_t n_tris,
+                               uint32_t n_prims, float4* d_tris, float4* d_nrms, const PrtRefitScratch& keep, float root_box[6], PrtCopyTally* tally) {
+    if (n_nodes == 0 || n_tris == 0 || n_levels == 0) return 0;
+    for (uint32_t m0 = 0; m0 < in.n_meshes; m0 += PRT_REFIT_CHUNK) {
+        const RefitChunk A = refit_chunk(in, m0, nrm, nullptr);
+        if (A.tri_end > A.tri_begin)
+            hipLaunchKernelGGL(k_refit_indexed, dim3((n_tris + 255u) / 256u), dim3(256), 0, st, A, d_corner, n_tris, n_prims, d_tris, d_nrms);
+    }
+    return refit_levels(st, d_nodes8, stride_dwords, n_nodes, nullptr, level_start, n_levels, (const float4*)d_tris, root_box, &keep, tally);
+}
+
+int prt_gpu_light_gather(hipStream_t st, const PrtRefitInputs& in, const uint32_t* d_corner, const uint32_t* d_light_tris, uint32_t n_light_tris,
+                         float* d_out) {
+    const uint32_t n = 9u * n_light_tris;
+    for (uint32_t m0 = 0; m0 < in.n_meshes && n; m0 += PRT_REFIT_CHUNK) {
+        const RefitChunk A = refit_chunk(in, m0, nullptr, nullptr);
+        if (A.tri_end > A.tri_begin) hipLaunchKernelGGL(k_light_gather, dim3((n + 255u) / 256u), dim3(256), 0, st, A, d_corner, d_light_tris, n, d_out);
+    }
+    return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

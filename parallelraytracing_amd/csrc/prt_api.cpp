@@ -70,6 +70,20 @@ struct PrtContext {
     bool has_scene = false;
     PrtHostScene hs;                   // the compiled scene (prt_scene.h): every host array the device copies come from
     double refit_ms = 0.0;             // device time of the last prt_refit_meshes (records + boxes + quantization)
+    // refit from device arrays (prt_refit_meshes_device): what the scene keeps on the device after the first call (one
+    // allocation, laid out by prt_workspace.h), and whether hs.bvh.nodes8 / tri_records / nrm_records lag behind the device
+    struct RefitKeep {
+        bool ready = false;
+        std::vector<uint32_t> tri_first, vert_first, level_start;  // PrtRefitTables' small arrays
+        uint32_t n_nodes = 0, n_light_tris = 0;
+        uint32_t *d_corner = nullptr, *d_csr_start = nullptr, *d_csr_corner = nullptr, *d_light_tris = nullptr, *d_valid = nullptr;
+        float *d_normals = nullptr, *d_light_verts = nullptr;  // computed normals of every world-space vertex; the packed emissive triangles
+        PrtRefitScratch scratch{};
+    } rk;
+    DevBuf rk_buf;
+    bool host_copies_stale = false;
+    PrtRefitInfo rinfo{};              // of the last refit, either form (refits: from hs.bvh_info)
+    PrtCopyTally* tally = nullptr;     // while a refit runs: the copies of the helpers it calls are counted here
     PrtInstanceUpdateInfo inst_info{}; // prt_set_instance_transforms calls since the scene was set (top_nodes / top_depth: from hs)
     DevScene dsc{};
     void* d_prims = nullptr;
@@ -598,10 +612,13 @@ int sync_light_tables(PrtContext* c) {
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     if (!a.empty() && c->d_lights) HIPCHECK(c, hipMemcpy(c->d_lights, a.data(), a.size() * 4, hipMemcpyHostToDevice));
+    if (!a.empty() && c->d_lights && c->tally) c->tally->h2d += a.size() * 4;
     if (ml && !b.empty()) HIPCHECK(c, hipMemcpy(c->d_ml_records, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+    if (ml && !b.empty() && c->tally) c->tally->h2d += b.size() * 4;
     if (ml && c->d_lc_pmf) {
         prt_cluster_pmf_in(c->hs, te, &a);
         if (!a.empty()) HIPCHECK(c, hipMemcpy(c->d_lc_pmf, a.data(), a.size() * 4, hipMemcpyHostToDevice));
+        if (!a.empty() && c->tally) c->tally->h2d += a.size() * 4;
     }
     c->t_env_dev = te;
     return PRT_OK;
@@ -630,6 +647,7 @@ int upload_mesh_lights(PrtContext* c) {
     auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
         hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
         if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && c->tally) c->tally->h2d += bytes;
         return e;
     };
     HIPCHECK(c, up(&c->d_ml_records, ml.records.data(), ml.records.size() * 4));
@@ -670,7 +688,31 @@ int ensure_spill(PrtContext* c) {
     return c->spill.ensure(c, need * sizeof(uint32_t));
 }
 
+// What prt_refit_meshes_device keeps with a scene goes with it
+void drop_refit_keep(PrtContext* c) {
+    c->rk_buf.release();
+    c->rk = PrtContext::RefitKeep();
+    c->host_copies_stale = false;
+    c->rinfo = PrtRefitInfo{};
+}
+
+// The host copies of the world-space meshes' tree and records after a refit from device arrays left them behind: every
+// reader of hs.bvh.nodes8 / hs.tri_records / hs.nrm_records comes through here first.
+int refresh_host_copies(PrtContext* c) {
+    if (!c->host_copies_stale) return PRT_OK;
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    PrtHostScene& hs = c->hs;
+    const size_t n_nodes = hs.bvh.nodes8.size() / 20, n_tris = c->dsc.n_tris;
+    if (n_nodes) HIPCHECK(c, hipMemcpy2D(hs.bvh.nodes8.data(), 80, c->d_nodes8, (size_t)c->dsc.node_stride * 16, 80, n_nodes, hipMemcpyDeviceToHost));
+    if (hs.tri_records.size() == 12 * n_tris) HIPCHECK(c, hipMemcpy(hs.tri_records.data(), c->d_tris, 48 * n_tris, hipMemcpyDeviceToHost));
+    if (hs.nrm_records.size() == 12 * n_tris) HIPCHECK(c, hipMemcpy(hs.nrm_records.data(), c->d_nrms, 48 * n_tris, hipMemcpyDeviceToHost));
+    c->host_copies_stale = false;
+    return PRT_OK;
+}
+
 void free_scene(PrtContext* c) {
+    drop_refit_keep(c);
     free_dev(c->d_prims);
     free_dev(c->d_mat_rgbs);
     free_dev(c->d_mat_type);
@@ -1230,28 +1272,6 @@ int device_build(PrtContext* c, const float* verts, const float* norms, const ui
     return PRT_OK;
 }
 
-// The nodes of every level of the 8-wide tree whose n_nodes nodes lead the array n8, root first (breadth-first search from
-// node 0: the builders emit their nodes in different orders, none of which a refit relies on).  0, or 1 + the node at
-// which the tree turned out malformed; a tree that does not reach all of its nodes leaves level_nodes short.
-uint32_t tree_levels(const std::vector<uint32_t>& n8, uint32_t n_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_start) {
-    level_nodes.assign(1, 0u);
-    level_start.assign({0u, 1u});
-    level_nodes.reserve(n_nodes);
-    for (;;) {
-        const uint32_t b = level_start[level_start.size() - 2], e = level_start.back();
-        for (uint32_t li = b; li < e; ++li) {
-            const uint32_t nd = level_nodes[li];
-            const uint32_t imask = n8[20 * (size_t)nd + 3] >> 24, child_base = n8[20 * (size_t)nd + 4];
-            const uint32_t kids = (uint32_t)__builtin_popcount(imask);
-            if ((uint64_t)child_base + kids > n_nodes || level_nodes.size() + kids > n_nodes) return nd + 1u;
-            for (uint32_t k = 0; k < kids; ++k) level_nodes.push_back(child_base + k);
-        }
-        if (level_nodes.size() == e) break;
-        level_start.push_back((uint32_t)level_nodes.size());
-    }
-    return 0u;
-}
-
 int check_ready(PrtContext* c) {
     int rc = need_device(c);
     if (rc) return rc;
@@ -1390,6 +1410,9 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     // A scene the context held before is gone whatever happens: a failure below leaves the context WITHOUT a scene (the
     // next render fails with PRT_ERR_INVALID); has_scene is set again only after the last upload.
     c->has_scene = false;
+    c->host_copies_stale = false;  // (of the scene that goes; its tables on the device go with free_scene)
+    c->rk.ready = false;
+    c->rinfo = PrtRefitInfo{};
     drop_tex(c);
     PrtHostScene hs = std::move(c->hs);  // (the compiler recycles the record arrays' storage; everything else goes)
     c->hs = PrtHostScene();
@@ -1431,6 +1454,8 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     if (!dst || !src) return PRT_ERR_INVALID;
     if (!src->has_scene) return fail(dst, PRT_ERR_INVALID, "prt_clone_scene: the source context has no scene");
     if (dst == src) return PRT_OK;
+    // (the source's host copies are a cache of its device arrays: bringing them up to date changes nothing a caller can see)
+    if (const int rc = refresh_host_copies(const_cast<PrtContext*>(src))) return fail(dst, rc, "prt_clone_scene: %s", src->err.c_str());
     dst->feat_valid = false;
     touch_scene(dst);
     drop_history(dst);
@@ -1453,6 +1478,46 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
     const int rc_tex = upload_tex(dst);
     if (rc_tex) return rc_tex;
     return upload_scene(dst, nullptr);
+}
+
+// What a refit leaves of the scene besides its records and tree, either form: root_box from the refitted root, extent the
+// largest |coordinate| of the new vertices.
+static void commit_refit(PrtContext* c, const float root_box[6], float extent) {
+    // the binary and 4-wide trees (A/B kernels, overflow fallback of deep host-built trees) still describe the OLD
+    // geometry: they go, and the instance selection falls to the 8-wide kernels that need neither (prt_plan_walk)
+    free_dev(c->d_nodes);
+    free_dev(c->d_nodes4);
+    c->dsc.nodes = nullptr;
+    c->dsc.nodes4 = nullptr;
+    c->hs.bvh.nodes.clear();
+    c->hs.bvh.nodes4.clear();
+    c->hs.scene_device_built = true;
+    c->variant = 0;
+    PrtSceneScalars& k = c->hs.sc;  // (a clone of this scene starts from the refitted bounds too)
+    for (int a = 0; a < 3; ++a) {
+        c->dsc.root_min[a] = k.root_min[a] = root_box[a];
+        c->dsc.root_max[a] = k.root_max[a] = root_box[3 + a];
+    }
+    float ext_all = extent;
+    if (!c->hs.abvh.nodes4.empty()) ext_all = std::max(ext_all, k.extent);  // (the primitive walk's pad scales with the larger of the two)
+    c->dsc.extent = k.extent = ext_all;
+    c->hs.bvh_info.refit_ms = (float)c->refit_ms;
+    ++c->hs.bvh_info.refits;
+    c->hs.bvh_info.n_nodes = 0;      // (the binary and 4-wide trees are gone)
+    c->hs.bvh_info.n_nodes4 = 0;
+    c->hs.bvh_info.node_bytes = 0;
+    c->hs.bvh_info.max_stack4 = 0;
+}
+
+// PrtRefitInfo of a refit that went through
+static void refit_done(PrtContext* c, uint32_t form, uint32_t normals_computed, const PrtCopyTally& tally,
+                       std::chrono::steady_clock::time_point t_call) {
+    c->rinfo.last_form = form;
+    c->rinfo.normals_computed = normals_computed;
+    c->rinfo.device_ms = (float)c->refit_ms;
+    c->rinfo.wall_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    c->rinfo.h2d_bytes = tally.h2d;
+    c->rinfo.d2h_bytes = tally.d2h;
 }
 
 // Deforming geometry: the world-space meshes of the current scene with NEW vertex positions / normals (same vertex and
@@ -1483,6 +1548,14 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
         n_tris += me.n_triangles;
     }
     if (n_tris != c->dsc.n_tris || n_tris == 0) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: triangle count mismatch");
+    if ((rc = refresh_host_copies(c))) return rc;  // (a refit from device arrays left them behind; not part of this call's traffic)
+    const auto t_call = std::chrono::steady_clock::now();
+    PrtCopyTally tally{0, 0};
+    struct TallyScope {  // the light tables' uploads below count too
+        PrtContext* c;
+        ~TallyScope() { c->tally = nullptr; }
+    } scope{c};
+    c->tally = &tally;
     std::vector<float> verts(9 * (size_t)n_tris), norms(9 * (size_t)n_tris);
     float extent = 0.0f;
     for (size_t m = 0, t = 0; m < n_meshes; t += meshes[m++].n_triangles)
@@ -1491,7 +1564,7 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     const std::vector<uint32_t>& n8 = c->hs.bvh.nodes8;
     const uint32_t n_nodes = (uint32_t)(n8.size() / 20);
     std::vector<uint32_t> level_nodes, level_start;
-    if (const uint32_t bad = tree_levels(n8, n_nodes, level_nodes, level_start))
+    if (const uint32_t bad = prt_tree_levels(n8, n_nodes, level_nodes, level_start))
         return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: malformed tree (node %u)", bad - 1u);
     if (level_nodes.size() != n_nodes) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: %zu of %u nodes reachable from the root", level_nodes.size(), n_nodes);
     HIPCHECK(c, hipStreamSynchronize(c->stream));
@@ -1500,13 +1573,14 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     if (e == hipSuccess) e = hipMalloc(&dn, 36 * (size_t)n_tris);
     if (e == hipSuccess) e = hipMemcpy(dv, verts.data(), 36 * (size_t)n_tris, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dn, norms.data(), 36 * (size_t)n_tris, hipMemcpyHostToDevice);
+    tally.h2d += 72 * (uint64_t)n_tris;
     float root_box[6] = {0, 0, 0, 0, 0, 0};
     int brc = 0;
     if (e == hipSuccess) {
         const auto t0 = std::chrono::steady_clock::now();
         brc = prt_gpu_bvh8_refit(c->stream, (uint32_t*)c->d_nodes8, c->dsc.node_stride * 4u, n_nodes, level_nodes.data(), level_start.data(),
                                  (uint32_t)level_start.size() - 1u, (const float*)dv, (const float*)dn, (uint32_t)n_tris, c->dsc.n_prims,
-                                 (float4*)c->d_tris, (float4*)c->d_nrms, root_box);
+                                 (float4*)c->d_tris, (float4*)c->d_nrms, root_box, &tally);
         c->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     (void)hipFree(dv);
@@ -1517,36 +1591,167 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
     }
     // host copies (prt_bvh_read8 / prt_bvh_read, prt_clone_scene) follow the device
     e = hipMemcpy2D(c->hs.bvh.nodes8.data(), 80, c->d_nodes8, (size_t)c->dsc.node_stride * 16, 80, n_nodes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && c->hs.tri_records.size() == 12 * (size_t)n_tris) e = hipMemcpy(c->hs.tri_records.data(), c->d_tris, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && c->hs.nrm_records.size() == 12 * (size_t)n_tris) e = hipMemcpy(c->hs.nrm_records.data(), c->d_nrms, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
-    HIPCHECK(c, e);
-    // the binary and 4-wide trees (A/B kernels, overflow fallback of deep host-built trees) still describe the OLD
-    // geometry: they go, and the instance selection falls to the 8-wide kernels that need neither (prt_plan_walk)
-    free_dev(c->d_nodes);
-    free_dev(c->d_nodes4);
-    c->dsc.nodes = nullptr;
-    c->dsc.nodes4 = nullptr;
-    c->hs.bvh.nodes.clear();
-    c->hs.bvh.nodes4.clear();
-    c->hs.scene_device_built = true;
-    c->variant = 0;
-    PrtSceneScalars& k = c->hs.sc;  // (a clone of this scene starts from the refitted bounds too)
-    for (int a = 0; a < 3; ++a) {
-        c->dsc.root_min[a] = k.root_min[a] = root_box[a];
-        c->dsc.root_max[a] = k.root_max[a] = root_box[3 + a];
+    tally.d2h += 80 * (uint64_t)n_nodes;
+    if (e == hipSuccess && c->hs.tri_records.size() == 12 * (size_t)n_tris) {
+        e = hipMemcpy(c->hs.tri_records.data(), c->d_tris, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
+        tally.d2h += 48 * (uint64_t)n_tris;
     }
-    float ext_all = extent;
-    if (!c->hs.abvh.nodes4.empty()) ext_all = std::max(ext_all, k.extent);  // (the primitive walk's pad scales with the larger of the two)
-    c->dsc.extent = k.extent = ext_all;
-    c->hs.bvh_info.refit_ms = (float)c->refit_ms;
-    ++c->hs.bvh_info.refits;
-    c->hs.bvh_info.n_nodes = 0;      // (the binary and 4-wide trees are gone)
-    c->hs.bvh_info.n_nodes4 = 0;
-    c->hs.bvh_info.node_bytes = 0;
-    c->hs.bvh_info.max_stack4 = 0;
+    if (e == hipSuccess && c->hs.nrm_records.size() == 12 * (size_t)n_tris) {
+        e = hipMemcpy(c->hs.nrm_records.data(), c->d_nrms, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
+        tally.d2h += 48 * (uint64_t)n_tris;
+    }
+    HIPCHECK(c, e);
+    commit_refit(c, root_box, extent);
     // triangle lights follow the geometry: the candidate table again from the new vertices (host), uploaded if in use
     prt_rebuild_mesh_lights(&c->hs, verts.data());
-    if (mesh_lights_on(c)) return upload_mesh_lights(c);
+    if (mesh_lights_on(c) && (rc = upload_mesh_lights(c))) return rc;
+    refit_done(c, 1u, 0u, tally, t_call);
+    return PRT_OK;
+}
+
+// The tables and working arrays a refit from device arrays keeps with the scene: built (prt_scene.cpp) and uploaded at the
+// first call, in one allocation; free_scene drops them.
+static int ensure_refit_keep(PrtContext* c, PrtCopyTally* tally) {
+    PrtContext::RefitKeep& rk = c->rk;
+    if (rk.ready) return PRT_OK;
+    PrtRefitTables t;
+    int rc = prt_build_refit_tables(c->hs, &t, &c->err);
+    if (rc) return rc;
+    const size_t n_nodes = t.level_nodes.size(), n_vert = t.vert_first.back(), n_corner = t.corner.size(), n_light = t.light_tris.size();
+    PrtWorkspace ws;
+    ws.add(&rk.d_corner, n_corner).add(&rk.d_csr_start, n_vert + 1).add(&rk.d_csr_corner, n_corner).add(&rk.d_light_tris, n_light);
+    ws.add(&rk.d_valid, 4).add(&rk.d_normals, 3 * n_vert).add(&rk.d_light_verts, 9 * n_light);
+    ws.add(&rk.scratch.cbox, 48 * n_nodes).add(&rk.scratch.nbox, 6 * n_nodes).add(&rk.scratch.counters, 4).add(&rk.scratch.level_nodes, n_nodes);
+    if ((rc = commit(c, ws, c->rk_buf))) {
+        rk = PrtContext::RefitKeep();
+        return rc;
+    }
+    auto up = [&](uint32_t* dst, const std::vector<uint32_t>& src) -> hipError_t {
+        if (src.empty()) return hipSuccess;
+        if (tally) tally->h2d += 4 * (uint64_t)src.size();
+        return hipMemcpyAsync(dst, src.data(), 4 * src.size(), hipMemcpyHostToDevice, c->stream);
+    };
+    hipError_t e = up(rk.d_corner, t.corner);
+    if (e == hipSuccess) e = up(rk.d_csr_start, t.csr_start);
+    if (e == hipSuccess) e = up(rk.d_csr_corner, t.csr_corner);
+    if (e == hipSuccess) e = up(rk.d_light_tris, t.light_tris);
+    if (e == hipSuccess) e = up(rk.scratch.level_nodes, t.level_nodes);
+    const hipError_t es = hipStreamSynchronize(c->stream);  // (the tables go out of scope below)
+    if (e != hipSuccess || es != hipSuccess) {
+        rk = PrtContext::RefitKeep();
+        HIPCHECK(c, e != hipSuccess ? e : es);
+    }
+    rk.tri_first = std::move(t.tri_first);
+    rk.vert_first = std::move(t.vert_first);
+    rk.level_start = std::move(t.level_start);
+    rk.n_nodes = (uint32_t)n_nodes;
+    rk.n_light_tris = (uint32_t)n_light;
+    rk.ready = true;
+    return PRT_OK;
+}
+
+// prt_refit_meshes for vertex arrays on the device (include/prt.h): validated there, records gathered through the scene's
+// index buffers (bvh_gpu.hip prt_gpu_bvh8_refit_indexed), host copies left to refresh_host_copies.
+int prt_refit_meshes_device(PrtContext* c, const PrtMeshDeviceArrays* meshes, uint32_t n_meshes) {
+    if (c) c->feat_valid = false;
+    if (c) touch_scene(c);
+    if (c) drop_history(c);
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (!meshes && n_meshes) return fail(c, PRT_ERR_INVALID, "null mesh array");
+    if (c->dsc.n_insts) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes_device: scenes with placed copies are rebuilt, not refitted");
+    if (!c->dsc.nodes8 || c->hs.bvh.nodes8.empty()) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes_device needs the compressed 8-wide tree");
+    if (2 * (size_t)n_meshes != c->hs.mesh_sizes.size())
+        return fail(c, PRT_ERR_INVALID, "prt_refit_meshes_device: the scene has %zu meshes", c->hs.mesh_sizes.size() / 2);
+    if (c->hs.bvh_info.depth8 > 16u)  // (prt_refit_meshes says why)
+        return fail(c, PRT_ERR_INVALID, "prt_refit_meshes_device: a tree of %u levels (depth8 > 16) is rebuilt with prt_set_scene, not refitted",
+                    c->hs.bvh_info.depth8);
+    uint64_t n_tris = 0;
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        if (c->hs.mesh_sizes[2 * m + 1] && !meshes[m].positions) return fail(c, PRT_ERR_INVALID, "mesh %u: positions are required", m);
+        n_tris += c->hs.mesh_sizes[2 * m + 1];
+    }
+    if (n_tris != c->dsc.n_tris || n_tris == 0) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes_device: triangle count mismatch");
+    const auto t_call = std::chrono::steady_clock::now();
+    PrtCopyTally tally{0, 0};
+    struct TallyScope {
+        PrtContext* c;
+        ~TallyScope() { c->tally = nullptr; }
+    } scope{c};
+    c->tally = &tally;
+    if ((rc = ensure_refit_keep(c, &tally))) return rc;
+    PrtContext::RefitKeep& rk = c->rk;
+    if (rk.n_nodes != c->hs.bvh.nodes8.size() / 20 || rk.level_start.size() < 2) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes_device: no level lists for this tree");
+    std::vector<const float*> pos(n_meshes), nrm_in(n_meshes), nrm(n_meshes);
+    std::vector<float*> nout(n_meshes);
+    uint32_t n_computed = 0;
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        pos[m] = meshes[m].positions;
+        nrm_in[m] = meshes[m].normals;
+        nout[m] = meshes[m].normals || !c->hs.mesh_sizes[2 * m] ? nullptr : rk.d_normals + 3 * (size_t)rk.vert_first[m];
+        nrm[m] = meshes[m].normals ? meshes[m].normals : rk.d_normals + 3 * (size_t)rk.vert_first[m];
+        n_computed += nout[m] ? 1u : 0u;
+    }
+    const PrtRefitInputs in{n_meshes, pos.data(), rk.tri_first.data(), rk.vert_first.data()};
+    // 1. the inputs, before anything of the scene is written
+    uint32_t valid[2] = {0u, 0u};
+    hipError_t e = (hipError_t)prt_gpu_refit_validate(c->stream, in, nrm_in.data(), rk.d_corner, rk.d_valid);
+    if (e == hipSuccess) e = hipMemcpyAsync(valid, rk.d_valid, sizeof(valid), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    tally.d2h += sizeof(valid);
+    HIPCHECK(c, e);
+    if (valid[1]) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes_device: non-finite vertex%s", (valid[1] & 1u) ? "" : " normal");
+    float extent = 0.0f;
+    memcpy(&extent, &valid[0], 4);
+    // 2. normals where none came, the emissive triangles for the host's candidate table, records, boxes, quantization
+    float root_box[6] = {0, 0, 0, 0, 0, 0};
+    const auto t0 = std::chrono::steady_clock::now();
+    int brc = n_computed ? prt_gpu_mesh_normals(c->stream, in, nout.data(), rk.d_corner, rk.d_csr_start, rk.d_csr_corner) : 0;
+    if (!brc) brc = prt_gpu_light_gather(c->stream, in, rk.d_corner, rk.d_light_tris, rk.n_light_tris, rk.d_light_verts);
+    if (!brc)
+        brc = prt_gpu_bvh8_refit_indexed(c->stream, (uint32_t*)c->d_nodes8, c->dsc.node_stride * 4u, rk.n_nodes, rk.level_start.data(),
+                                         (uint32_t)rk.level_start.size() - 1u, in, nrm.data(), rk.d_corner, (uint32_t)n_tris, c->dsc.n_prims,
+                                         (float4*)c->d_tris, (float4*)c->d_nrms, rk.scratch, root_box, &tally);
+    c->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<float> packed(9 * (size_t)rk.n_light_tris);
+    if (!brc && !packed.empty()) {
+        brc = (int)hipMemcpy(packed.data(), rk.d_light_verts, 4 * packed.size(), hipMemcpyDeviceToHost);
+        tally.d2h += 4 * (uint64_t)packed.size();
+    }
+    if (brc) {
+        c->has_scene = false;  // the device arrays may be half rewritten
+        return fail(c, PRT_ERR_HIP, "prt_refit_meshes_device: refit failed (%d)", brc);
+    }
+    c->host_copies_stale = true;
+    commit_refit(c, root_box, extent);
+    prt_rebuild_mesh_lights_packed(&c->hs, packed.data());
+    if (mesh_lights_on(c) && (rc = upload_mesh_lights(c))) return rc;
+    refit_done(c, 2u, n_computed, tally, t_call);
+    return PRT_OK;
+}
+
+int prt_mesh_normals_device(PrtContext* c, uint32_t mesh, const float* positions, float* normals_out) {
+    int rc = need_device(c);
+    if (rc) return rc;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (2 * (size_t)mesh + 1 >= c->hs.mesh_sizes.size()) return fail(c, PRT_ERR_INVALID, "prt_mesh_normals_device: the scene has %zu meshes", c->hs.mesh_sizes.size() / 2);
+    if (!c->hs.mesh_sizes[2 * mesh]) return PRT_OK;
+    if (!positions || !normals_out) return fail(c, PRT_ERR_INVALID, "prt_mesh_normals_device: null array");
+    if ((rc = ensure_refit_keep(c, nullptr))) return rc;
+    const PrtContext::RefitKeep& rk = c->rk;
+    const PrtRefitInputs in{1u, &positions, &rk.tri_first[mesh], &rk.vert_first[mesh]};
+    hipError_t e = (hipError_t)prt_gpu_mesh_normals(c->stream, in, &normals_out, rk.d_corner, rk.d_csr_start, rk.d_csr_corner);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    HIPCHECK(c, e);
+    return PRT_OK;
+}
+
+int prt_refit_info(PrtContext* c, PrtRefitInfo* out) {
+    if (!c || !out) return PRT_ERR_INVALID;
+    *out = c->rinfo;
+    out->refits = c->has_scene ? c->hs.bvh_info.refits : 0u;
+    out->host_copies_stale = c->host_copies_stale ? 1u : 0u;
     return PRT_OK;
 }
 
@@ -1636,7 +1841,7 @@ int prt_set_instance_transforms(PrtContext* c, const PrtInstance* instances, uin
     bool top_dirty = false;  // the device's top level no longer matches the host copy
     if (mode == (uint32_t)PRT_INSTANCES_REFIT) {
         std::vector<uint32_t> level_nodes, level_start;
-        if (tree_levels(hs.nodes8_all, old_top, level_nodes, level_start) || level_nodes.size() != old_top) {
+        if (prt_tree_levels(hs.nodes8_all, old_top, level_nodes, level_start) || level_nodes.size() != old_top) {
             drop();
             return fail(c, PRT_ERR_INVALID, "prt_set_instance_transforms: malformed top-level tree");
         }
@@ -3710,6 +3915,7 @@ int prt_bvh_read4(PrtContext* c, float* nodes4) {
 int prt_bvh_read8(PrtContext* c, uint32_t* nodes8) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (const int rc = refresh_host_copies(c)) return rc;
     const std::vector<uint32_t>& n8 = c->hs.nodes8_all.empty() ? c->hs.bvh.nodes8 : c->hs.nodes8_all;
     if (nodes8) memcpy(nodes8, n8.data(), n8.size() * 4);
     return PRT_OK;
@@ -3718,6 +3924,7 @@ int prt_bvh_read8(PrtContext* c, uint32_t* nodes8) {
 int prt_bvh_read(PrtContext* c, float* nodes, float* tris) {
     if (!c) return PRT_ERR_INVALID;
     if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (const int rc = refresh_host_copies(c)) return rc;
     if (nodes) memcpy(nodes, c->hs.bvh.nodes.data(), c->hs.bvh.nodes.size() * 4);
     if (tris) memcpy(tris, c->hs.tri_records.data(), c->hs.tri_records.size() * 4);
     return PRT_OK;

@@ -903,6 +903,102 @@ void prt_rebuild_mesh_lights(PrtHostScene* hs, const float* verts, const PrtInst
     finish_mesh_lights(*hs, count_not_similar(*hs));
 }
 
+// ---- refit from device arrays ----
+uint32_t prt_tree_levels(const std::vector<uint32_t>& n8, uint32_t n_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_start) {
+    level_nodes.assign(1, 0u);
+    level_start.assign({0u, 1u});
+    level_nodes.reserve(n_nodes);
+    for (;;) {
+        const uint32_t b = level_start[level_start.size() - 2], e = level_start.back();
+        for (uint32_t li = b; li < e; ++li) {
+            const uint32_t nd = level_nodes[li];
+            const uint32_t imask = n8[20 * (size_t)nd + 3] >> 24, child_base = n8[20 * (size_t)nd + 4];
+            const uint32_t kids = (uint32_t)__builtin_popcount(imask);
+            if ((uint64_t)child_base + kids > n_nodes || level_nodes.size() + kids > n_nodes) return nd + 1u;
+            for (uint32_t k = 0; k < kids; ++k) level_nodes.push_back(child_base + k);
+        }
+        if (level_nodes.size() == e) break;
+        level_start.push_back((uint32_t)level_nodes.size());
+    }
+    return 0u;
+}
+
+int prt_build_refit_tables(const PrtHostScene& hs, PrtRefitTables* out, std::string* err) {
+    PrtRefitTables t;
+    const size_t n_meshes = hs.mesh_sizes.size() / 2;
+    t.tri_first.assign(1, 0u);
+    t.vert_first.assign(1, 0u);
+    uint64_t nt = 0, nv = 0;
+    for (size_t m = 0; m < n_meshes; ++m) {
+        nv += hs.mesh_sizes[2 * m];
+        nt += hs.mesh_sizes[2 * m + 1];
+        if (nv >= 0xFFFFFFF0ull || 9 * nt >= 0xFFFFFFF0ull) return fail(err, "refit tables: too many vertices or corners");  // (32-bit thread indices)
+        t.vert_first.push_back((uint32_t)nv);
+        t.tri_first.push_back((uint32_t)nt);
+    }
+    if (hs.mesh_indices.size() != 3 * (size_t)nt) return fail(err, "refit tables: %zu indices for %llu triangles", hs.mesh_indices.size(), (unsigned long long)nt);
+    // corners with their mesh's vertex base; a vertex's incident corners by a counting sort, which keeps ascending order
+    t.corner.resize(3 * (size_t)nt);
+    t.csr_start.assign((size_t)nv + 1, 0u);
+    for (size_t m = 0; m < n_meshes; ++m)
+        for (size_t k = 3 * (size_t)t.tri_first[m]; k < 3 * (size_t)t.tri_first[m + 1]; ++k) {
+            if (hs.mesh_indices[k] >= hs.mesh_sizes[2 * m]) return fail(err, "refit tables: mesh %zu: vertex index out of range", m);
+            t.corner[k] = t.vert_first[m] + hs.mesh_indices[k];
+            ++t.csr_start[(size_t)t.corner[k] + 1];
+        }
+    for (size_t v = 0; v < (size_t)nv; ++v) t.csr_start[v + 1] += t.csr_start[v];
+    t.csr_corner.resize(3 * (size_t)nt);
+    std::vector<uint32_t> fill(t.csr_start.begin(), t.csr_start.end() - 1);
+    for (size_t k = 0; k < t.corner.size(); ++k) t.csr_corner[fill[t.corner[k]]++] = (uint32_t)k;
+    const uint32_t n_nodes = (uint32_t)(hs.bvh.nodes8.size() / 20);
+    if (n_nodes) {  // (a scene without the 8-wide tree is not refitted; its normals can still be asked for)
+        if (const uint32_t bad = prt_tree_levels(hs.bvh.nodes8, n_nodes, t.level_nodes, t.level_start))
+            return fail(err, "refit tables: malformed tree (node %u)", bad - 1u);
+        if (t.level_nodes.size() != n_nodes) return fail(err, "refit tables: %zu of %u nodes reachable from the root", t.level_nodes.size(), n_nodes);
+    }
+    for (const PrtLightRun& r : hs.ml.runs) {
+        if (!r.world) continue;
+        const uint64_t first = (uint64_t)r.prim_first - hs.prims.size();
+        if (r.prim_first < hs.prims.size() || first + r.n_tris > nt) return fail(err, "refit tables: a light run lies outside the meshes");
+        for (uint32_t k = 0; k < r.n_tris; ++k) t.light_tris.push_back((uint32_t)first + k);
+    }
+    *out = std::move(t);
+    return PRT_OK;
+}
+
+void prt_rebuild_mesh_lights_packed(PrtHostScene* hs, const float* packed) {
+    PrtMeshLights& ml = hs->ml;
+    size_t at = 0;  // (light_tris lists the world runs in the order of ml.runs)
+    for (const PrtLightRun& r : ml.runs) {
+        if (!r.world) continue;
+        float rgb[3];
+        memcpy(rgb, &ml.records[4 * PRT_LIGHT_F4 * (size_t)r.light_first + 16], sizeof(rgb));
+        write_tri_candidates(ml, r.light_first, &packed[9 * at], r.n_tris, rgb, r.prim_first);
+        at += r.n_tris;
+    }
+    finish_mesh_lights(*hs, count_not_similar(*hs));
+}
+
+void prt_normals_from_corners(const float* positions, uint32_t n_vertices, const uint32_t* corner, const uint32_t* csr_start,
+                              const uint32_t* csr_corner, float* normals) {
+    for (uint32_t v = 0; v < n_vertices; ++v) {
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (uint32_t j = csr_start[v]; j < csr_start[v + 1]; ++j) {
+            const uint32_t f = csr_corner[j] / 3u;
+            const float* pa = &positions[3 * (size_t)corner[3 * (size_t)f]];
+            const float* pb = &positions[3 * (size_t)corner[3 * (size_t)f + 1]];
+            const float* pc = &positions[3 * (size_t)corner[3 * (size_t)f + 2]];
+            const double e1[3] = {(double)pb[0] - pa[0], (double)pb[1] - pa[1], (double)pb[2] - pa[2]};
+            const double e2[3] = {(double)pc[0] - pa[0], (double)pc[1] - pa[1], (double)pc[2] - pa[2]};
+            acc[0] += e1[1] * e2[2] - e1[2] * e2[1];
+            acc[1] += e1[2] * e2[0] - e1[0] * e2[2];
+            acc[2] += e1[0] * e2[1] - e1[1] * e2[0];
+        }
+        const double l = std::sqrt(acc[0] * acc[0] + acc[1] * acc[1] + acc[2] * acc[2]);
+        for (int k = 0; k < 3; ++k) normals[3 * (size_t)v + k] = l > 0.0 ? (float)(acc[k] / l) : (k == 1 ? 1.0f : 0.0f);
+    }
+}
+
 int prt_check_instance_update(const PrtHostScene& hs, const PrtInstance* instances, uint32_t n, std::string* err) {
     if (hs.inst_mesh.empty()) return fail(err, "prt_set_instance_transforms: the scene has no placed copies");
     if (n != hs.inst_mesh.size()) return fail(err, "prt_set_instance_transforms: the scene has %zu placed copies, not %u", hs.inst_mesh.size(), n);

@@ -202,6 +202,34 @@ int prt_compile_scene(const PrtSceneDesc* s, const PrtSceneOptions& opt, PrtHost
 // threshold; the result equals what prt_compile_scene builds for the new geometry.  O(candidates) on the host.
 void prt_rebuild_mesh_lights(PrtHostScene* hs, const float* verts, const PrtInstance* placed = nullptr);
 
+// ---- refit from device arrays (prt_refit_meshes_device) ----
+// What the device form of the refit keeps per scene, built once from the compiled scene's index buffers and tree.
+struct PrtRefitTables {
+    std::vector<uint32_t> tri_first;    // per world-space mesh, + 1: its first triangle in mesh and face order
+    std::vector<uint32_t> vert_first;   // per world-space mesh, + 1: its first vertex among all world-space vertices
+    std::vector<uint32_t> corner;       // 3 per triangle, mesh and face order: the corner's vertex, vert_first of its mesh added
+    std::vector<uint32_t> csr_start;    // per vertex, + 1: its run in csr_corner
+    std::vector<uint32_t> csr_corner;   // per vertex its incident corners (3 * triangle + corner), ascending: compute_normals' order
+    std::vector<uint32_t> level_nodes;  // prt_tree_levels of the world-space meshes' tree
+    std::vector<uint32_t> level_start;
+    std::vector<uint32_t> light_tris;   // the triangles (mesh and face order) of the emissive world-space runs of hs.ml, run by run
+};
+// The nodes of every level of the 8-wide tree whose n_nodes nodes lead the array n8, root first (breadth-first search from
+// node 0: the builders emit their nodes in different orders, none of which a refit relies on).  0, or 1 + the node at
+// which the tree turned out malformed; a tree that does not reach all of its nodes leaves level_nodes short.
+uint32_t prt_tree_levels(const std::vector<uint32_t>& n8, uint32_t n_nodes, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_start);
+// The tables of a scene without placed copies that has the 8-wide tree (PRT_ERR_INVALID, message in *err: the index
+// buffers do not match mesh_sizes, or the tree is malformed).
+int prt_build_refit_tables(const PrtHostScene& hs, PrtRefitTables* out, std::string* err);
+// prt_rebuild_mesh_lights for world-space meshes that moved, from the vertices of the emissive triangles alone:
+// packed = 9 floats per entry of PrtRefitTables::light_tris, in its order.  The result is that of the full form.
+void prt_rebuild_mesh_lights_packed(PrtHostScene* hs, const float* packed);
+// compute_normals' rule (prt_host.cpp: area-weighted vertex normals, double sums in ascending face order) through the
+// incident-corner table of one mesh: corner / csr_* are PrtRefitTables' with vert_first = 0.  The host statement of what
+// the device kernel computes.
+void prt_normals_from_corners(const float* positions, uint32_t n_vertices, const uint32_t* corner, const uint32_t* csr_start,
+                              const uint32_t* csr_corner, float* normals);
+
 // ---- moving placed copies (prt_set_instance_transforms) ----
 // What an update works out before anything of the scene is written.
 struct PrtInstanceUpdate {

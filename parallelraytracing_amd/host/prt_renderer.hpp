@@ -351,6 +351,20 @@ public:
     void UpdateInstances(const Scene& scene, uint32_t mode = PRT_INSTANCES_REFIT) {
         check(prt_group_set_instance_transforms(grp_, scene.instances.data(), (uint32_t)scene.instances.size(), mode));
     }
+    // The scene's world-space meshes deformed on the GPU (prt_refit_meshes_device): meshes[m] holds DEVICE pointers to the
+    // new positions (and normals, or null: computed on the device) of mesh m, n_vertices x 3 floats each, read in stream
+    // order on the context's stream.  A renderer over one GPU only: a device array lives on one device.
+    void RefitDevice(const std::vector<PrtMeshDeviceArrays>& meshes) {
+        if (prt_group_size(grp_) != 1u) throw Error("RefitDevice: a renderer over several GPUs refits from host arrays");
+        PrtContext* c = prt_group_context(grp_, 0);
+        if (prt_refit_meshes_device(c, meshes.data(), (uint32_t)meshes.size())) throw Error(std::string("prt_refit_meshes_device: ") + prt_last_error(c));
+    }
+    PrtRefitInfo RefitInfo(uint32_t rank = 0) {
+        PrtRefitInfo info{};
+        PrtContext* c = prt_group_context(grp_, rank);
+        if (prt_refit_info(c, &info)) throw Error(std::string("prt_refit_info: ") + prt_last_error(c));
+        return info;
+    }
     PrtInstanceUpdateInfo InstanceUpdateInfo(uint32_t rank = 0) {
         PrtInstanceUpdateInfo info{};
         PrtContext* c = prt_group_context(grp_, rank);

@@ -486,6 +486,7 @@ class HipWavefrontRenderer:
         L = capi.lib()
         d = scene.desc()
         self._check(L.prt_set_scene(self._ctx, C.byref(d)))
+        self._mesh_vertices = [m.n_vertices for m, _ in scene.meshes]  # (RefitDevice checks its tensors against them)
         if scene.textures or scene.material_texture:  # (prt_set_scene dropped the previous scene's binding)
             self.set_textures(scene)
         self._check(L.prt_set_film(self._ctx, film.width, film.height, self.rank, self.world_size))
@@ -1262,6 +1263,38 @@ class HipWavefrontRenderer:
         self._check(capi.lib().prt_refit_meshes(self._ctx, d.meshes, d.n_meshes))
         self._scene = scene
 
+    def RefitDevice(self, positions, normals=None):
+        """prt_refit_meshes_device: Refit for vertex arrays that are on the renderer's device.  positions: one torch
+        tensor, or a list with one per world-space mesh, float32, contiguous, (n_vertices, 3); normals: the same, None
+        (area-weighted vertex normals are computed on the device), or a list with None entries.  The tensors are read
+        in stream order after torch's current stream; nothing is copied to the host but the emissive triangles."""
+        pos, nrm = _device_mesh_arrays(self, getattr(self, "_mesh_vertices", []), positions, normals)
+        arr = (capi.PrtMeshDeviceArrays * max(1, len(pos)))()
+        for m, (p, q) in enumerate(zip(pos, nrm)):
+            arr[m].positions = p.data_ptr()
+            arr[m].normals = None if q is None else q.data_ptr()
+        self._on_context_stream(lambda: capi.lib().prt_refit_meshes_device(self._ctx, arr, len(pos)))
+
+    def mesh_normals_device(self, mesh: int, positions):
+        """prt_mesh_normals_device: the vertex normals the library computes for world-space mesh `mesh` of the scene
+        (Mesh(vertices=, indices=) without normals, bit for bit) for positions on the device: an (n_vertices, 3) tensor."""
+        import torch
+        counts = getattr(self, "_mesh_vertices", [])
+        if not 0 <= int(mesh) < len(counts):
+            raise ValueError(f"mesh {mesh}: the scene has {len(counts)} world-space meshes")
+        self._check_tensor("positions", positions, (counts[int(mesh)], 3))
+        out = torch.empty_like(positions)
+        self._on_context_stream(lambda: capi.lib().prt_mesh_normals_device(
+            self._ctx, int(mesh), C.c_void_p(positions.data_ptr()), C.c_void_p(out.data_ptr())))
+        return out
+
+    def refit_info(self) -> dict:
+        """prt_refit_info as a dict: refits, last_form (0 none, 1 host arrays, 2 device arrays), normals_computed,
+        host_copies_stale, device_ms, wall_ms, h2d_bytes, d2h_bytes of the last Refit / RefitDevice."""
+        info = capi.PrtRefitInfo()
+        self._check(capi.lib().prt_refit_info(self._ctx, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in capi.PrtRefitInfo._fields_}
+
     def UpdateInstances(self, scene: "Scene", mode: str = "refit"):
         """prt_set_instance_transforms: `scene`'s placed copies carry new transforms (Scene.SetInstanceTransform) over the
         meshes and materials the renderer was initialised with.  mode "refit" keeps the top-level tree's topology and
@@ -1393,6 +1426,7 @@ class HipWavefrontGroupRenderer:
         L = capi.lib()
         d = scene.desc()
         self._check(L.prt_group_set_scene(self._grp, C.byref(d)))
+        self._mesh_vertices = [m.n_vertices for m, _ in scene.meshes]
         if scene.textures or scene.material_texture:
             self.set_textures(scene)
         self._check(L.prt_group_set_film(self._grp, film.width, film.height))
@@ -1409,6 +1443,21 @@ class HipWavefrontGroupRenderer:
         d = scene.desc()
         scene._keep = d
         self._check(capi.lib().prt_group_refit_meshes(self._grp, d.meshes, d.n_meshes))
+
+    def RefitDevice(self, positions, normals=None):
+        """HipWavefrontRenderer.RefitDevice on every rank, one after the other (the C interface has no group form: a
+        device array lives on one device).  The tensors are on rank 0's device; the other ranks get copies made by torch."""
+        L = capi.lib()
+        for rank in range(self.n_devices):
+            view = _RankView(L.prt_group_context(self._grp, rank))
+            dev = view._torch_device()
+            move = lambda t: t if t is None or not hasattr(t, "to") or rank == 0 else t.to(dev)
+            one = lambda x: [move(t) for t in x] if isinstance(x, (list, tuple)) else move(x)
+            view._mesh_vertices = self._mesh_vertices
+            view.RefitDevice(one(positions), one(normals))
+
+    def refit_info(self, rank: int = 0) -> dict:
+        return self._rank_view(rank).refit_info()
 
     def UpdateInstances(self, scene: Scene, mode: str = "refit"):
         """prt_group_set_instance_transforms: every rank moves its copy of the top level to `scene`'s new transforms."""
@@ -1636,6 +1685,27 @@ class _RankView:
     light_clusters = HipWavefrontRenderer.light_clusters
     light_cluster_members = HipWavefrontRenderer.light_cluster_members
     light_cluster_pmf = HipWavefrontRenderer.light_cluster_pmf
+    _torch_device = HipWavefrontRenderer._torch_device
+    _check_tensor = HipWavefrontRenderer._check_tensor
+    _on_context_stream = HipWavefrontRenderer._on_context_stream
+    RefitDevice = HipWavefrontRenderer.RefitDevice
+    refit_info = HipWavefrontRenderer.refit_info
+
+
+def _device_mesh_arrays(renderer, counts, positions, normals):
+    """RefitDevice's arguments as two lists with one entry per world-space mesh, checked (dtype, shape, device,
+    contiguity, length) before the library sees a pointer: it has no way to know how long a device array is."""
+    pos = list(positions) if isinstance(positions, (list, tuple)) else [positions]
+    nrm = list(normals) if isinstance(normals, (list, tuple)) else [normals] * len(pos) if normals is None else [normals]
+    if len(pos) != len(counts):
+        raise ValueError(f"positions: {len(pos)} tensors, the scene has {len(counts)} world-space meshes")
+    if len(nrm) != len(counts):
+        raise ValueError(f"normals: {len(nrm)} entries, the scene has {len(counts)} world-space meshes")
+    for m, (p, q) in enumerate(zip(pos, nrm)):
+        renderer._check_tensor(f"positions[{m}]", p, (counts[m], 3))
+        if q is not None:
+            renderer._check_tensor(f"normals[{m}]", q, (counts[m], 3))
+    return pos, nrm
 
 
 def _batch_instances(check, ctx) -> dict:

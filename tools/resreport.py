@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / scratch table of prt_kernels.hip (hipcc -Rpass-analysis=kernel-resource-usage).
 usage: python3 tools/resreport.py [filter] [-- extra hipcc flags]
-report(extra) returns the rows (tests/test_kernel_resources.py pins the occupancy-critical ones)."""
+report(extra) returns the rows (tests/test_kernel_resources.py pins the occupancy-critical ones); source: another unit of
+csrc/ (bvh_gpu.hip: the builders and the refits)."""
 import os
 import re
 import subprocess
@@ -12,9 +13,9 @@ CSRC = os.path.join(ROOT, "parallelraytracing_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
-def report(extra=()):
+def report(extra=(), source="prt_kernels.hip"):
     cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "--offload-arch=gfx950",
-           "-c", os.path.join(CSRC, "prt_kernels.hip"), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + list(extra)
+           "-c", os.path.join(CSRC, source), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + list(extra)
     out = subprocess.run(cmd, capture_output=True, text=True).stderr
     cur = None
     rows = []
