@@ -1207,6 +1207,81 @@ int prt_radiance_lit(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, con
 int prt_radiance_lit_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs,
                             void* d_rng_state, void* d_rgb_sum, void* d_segments, PrtRadianceLitInfo* info);
 
+/* ---- Surface baking: irradiance maps over a mesh's UV layout ------------------------------------
+ * From a mesh to the rays of its texels, on the device: the UV layout is rasterised into a W x H map, every covered texel
+ * becomes a Lambertian path vertex of albedo 1, its rays are followed by the radiance query and summed per texel.
+ *  Target: world-space mesh `index` of the current scene (PRT_BAKE_MESH) or placed copy `index` (PRT_BAKE_INSTANCE), on a
+ *    width x height map, 1 <= width, height <= PRT_TEX_MAX_SIZE.  uvs: n_vertices x 2 floats (host) for this call, a
+ *    lightmap layout being usually a second UV set; NULL: the UVs the current texture binding gave that mesh (a placed
+ *    copy: its instanced mesh).  The convention is the textures': row 0 is the top, v = 0 the bottom row.  UVs are not
+ *    wrapped: what lies outside [0,1]^2 is clipped.  The geometry is the scene's current one, after either refit too.
+ *  Texel t = i * W + j has the centre px = (j + 0.5) / W, py = 1 - (i + 0.5) / H, in double.
+ *  Coverage: face f with UVs a, b, c (fp32 widened to double; every operation below rounded once, no contraction):
+ *      A2 = (bx-ax)(cy-ay) - (by-ay)(cx-ax)
+ *      E0 = (bx-px)(cy-py) - (by-py)(cx-px)   E1 = (cx-px)(ay-py) - (cy-py)(ax-px)   E2 = (ax-px)(by-py) - (ay-py)(bx-px)
+ *    covers the texel iff its UVs are finite, A2 != 0, and E0, E1, E2 are all >= 0 (A2 > 0) or all <= 0 (A2 < 0): edges are
+ *    inclusive, so a shared edge leaves no crack.  The owner is the lowest covering face index, whatever the launch order.
+ *  Surface: b1 = (float)(E1 / A2), b2 = (float)(E2 / A2), w0 = 1.0f - b1 - b2; then in fp32 per component
+ *    x = (w0 * X0 + b1 * X1) + b2 * X2, for the position from the face's vertices and for ns from its vertex normals (the
+ *    hit reconstruction's order).  l2 = dot(ns, ns), (x*x + y*y) + z*z: a texel with !(l2 > 0 && l2 < inf) is degenerate:
+ *    it is not covered, its owner reads 0xFFFFFFFF and n_degenerate counts it.  Otherwise n = ns * (1 / sqrt(l2)).  A placed
+ *    copy's position then goes through Mat and its normal through Inv (renormalised) as a hit's do.
+ *  Rays: sample s of texel t starts from rng = path_seed(t, first_sample + s, seed): the index in the full map, so a
+ *    texel's samples do not depend on coverage elsewhere.  Material::Scatter of a Lambertian of albedo (1,1,1) with the
+ *    incoming direction -n, position p, normal n, front face; o = p, d = the scattered direction normalised once more,
+ *    as the radiance query's step does; the state is the advanced one.
+ *  Paths: from there the path is prt_radiance's path for (o, d, rng_state) with q.max_depth segments, bit for bit (segment
+ *    index 0 is the texel's ray; hit rule, textures, environment, roulette and clamp as there).  lighting != 0: it is
+ *    prt_radiance_lit's path under the context's lighting settings, pb = -1 on segment 0: emission met directly from the
+ *    texel counts at weight 1 and no light sample is taken at the texel itself.
+ *  Texel value: rgb_sum[t] = the fp32 sum, from 0.0f in ascending sample order, of the q.samples path values, whatever the
+ *    chunking (prt_set_param("bake_chunk", samples per chunk; 0 = by the ray budget of "radiance_chunk")).  A sum, as in
+ *    the film: irradiance on the +n side is pi * sum / samples, the exit radiance of a Lambertian of albedo rho is
+ *    rho * sum / samples.  Uncovered texels are 0.
+ *  Gutter fill: `dilate` = N runs N passes.  A texel with coverage 0 whose 8-neighbourhood inside the map holds texels
+ *    with coverage != 0 at the start of the pass gets the fp32 sum of those neighbours' values, in the order (-1,-1),
+ *    (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1) as (row, col), divided by their count as a float, and coverage 2.
+ *  Coverage bytes: 0 = none, 1 = owned, 2 = filled.
+ *  Refusals (PRT_ERR_INVALID, decided before anything is written; scene, film, statistics and histories untouched): no
+ *    scene; a null target; an unknown kind or an index out of range; a bad size, or width * height * samples > 2^32 - 1;
+ *    no UVs (uvs NULL and no binding, or a binding without UVs for that mesh); a UV that is not finite or of magnitude
+ *    above 2^20; prt_radiance's own refusals for q.  After those a host-only context returns PRT_ERR_NO_DEVICE.
+ *  Side effects: prt_radiance's: none.
+ *  Cost: three small passes over faces and texels (one wave per face striding its clipped bounding box; one thread per
+ *    texel; one block compacting the covered texels in ascending order), then per chunk of whole samples one ray kernel,
+ *    the radiance query's rounds over covered texels x samples of the chunk, and one ordered sum.
+ * Not offered: the group (prt_group_*); a light sample at the texel itself. */
+#define PRT_BAKE_MESH 0u
+#define PRT_BAKE_INSTANCE 1u
+typedef struct PrtBakeTarget {
+    uint32_t kind;      /* PRT_BAKE_MESH | PRT_BAKE_INSTANCE */
+    uint32_t index;
+    const float* uvs;   /* n_vertices * 2 floats, or NULL: the texture binding's */
+    uint32_t width, height;
+} PrtBakeTarget;
+typedef struct PrtBakeInfo {
+    uint64_t n_texels, n_covered, n_degenerate;
+    uint64_t n_faces_skipped;  /* A2 == 0 (or a non-finite UV) */
+    uint64_t n_filled;
+    uint64_t rays, segments, shadow_rays, shadow_occluded;
+    double device_ms;
+} PrtBakeInfo;
+/* Host outputs over the full map, each may be NULL: owner [H*W] (0xFFFFFFFF: none), bary [2*H*W] (b1, b2), position and
+ * normal [3*H*W]; zero where uncovered.  info (may be NULL): the texel and face counts. */
+int prt_bake_surface(PrtContext* ctx, const PrtBakeTarget* target, uint32_t* owner, float* bary, float* position,
+                     float* normal, PrtBakeInfo* info);
+/* The rays of sample `sample` of every texel (host, [3*H*W], [3*H*W], [H*W]; zero where uncovered): the function-level
+ * view of the ray kernel, in the manner of prt_camera_rays_lens. */
+int prt_bake_rays(PrtContext* ctx, const PrtBakeTarget* target, uint32_t seed, uint32_t sample, float* origins,
+                  float* dirs, uint32_t* rng_state);
+/* rgb_sum [3*H*W] floats and coverage [H*W] bytes on the host (coverage may be NULL).  Synchronous. */
+int prt_bake_irradiance(PrtContext* ctx, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting,
+                        uint32_t dilate, float* rgb_sum, uint8_t* coverage, PrtBakeInfo* info);
+/* The same with the two outputs as DEVICE pointers (the target's uvs stay a host array): enqueued on the context's stream,
+ * with the waits the query has (and one for the covered count); complete in stream order on return. */
+int prt_bake_irradiance_device(PrtContext* ctx, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting,
+                               uint32_t dilate, void* d_rgb_sum, void* d_coverage, PrtBakeInfo* info);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 int prt_enable_timing(PrtContext* ctx, int on); /* HIP events around every kernel launch */
 int prt_get_stats(PrtContext* ctx, PrtStats* out);

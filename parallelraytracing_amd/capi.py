@@ -108,6 +108,22 @@ class PrtRadianceLitInfo(C.Structure):
     _fields_ = [("shadow_rays", C.c_uint64), ("shadow_occluded", C.c_uint64)]
 
 
+BAKE_MESH, BAKE_INSTANCE = 0, 1  # PRT_BAKE_MESH, PRT_BAKE_INSTANCE
+BAKE_NONE = 0xFFFFFFFF            # owner of an uncovered texel
+
+
+class PrtBakeTarget(C.Structure):
+    """What a bake rasterises (include/prt.h "Surface baking")."""
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("uvs", C.POINTER(C.c_float)), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class PrtBakeInfo(C.Structure):
+    """The counts of one bake (include/prt.h "Surface baking")."""
+    _fields_ = [("n_texels", C.c_uint64), ("n_covered", C.c_uint64), ("n_degenerate", C.c_uint64), ("n_faces_skipped", C.c_uint64),
+                ("n_filled", C.c_uint64), ("rays", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64),
+                ("shadow_occluded", C.c_uint64), ("device_ms", C.c_double)]
+
+
 class PrtAdaptive(C.Structure):
     """Settings of prt_render_adaptive (include/prt.h "Film statistics and adaptive sampling")."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
@@ -371,6 +387,12 @@ SIGNATURES = {
     "prt_radiance_lit": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _fp, _fp, _u32p, _fp, _u32p, C.POINTER(PrtRadianceLitInfo)]),
     "prt_radiance_lit_device": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                           C.POINTER(PrtRadianceLitInfo)]),
+    "prt_bake_surface": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), _u32p, _fp, _fp, _fp, C.POINTER(PrtBakeInfo)]),
+    "prt_bake_rays": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.c_uint32, C.c_uint32, _fp, _fp, _u32p]),
+    "prt_bake_irradiance": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.c_int, C.c_uint32, _fp,
+                                      C.POINTER(C.c_uint8), C.POINTER(PrtBakeInfo)]),
+    "prt_bake_irradiance_device": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.c_int, C.c_uint32, _vp, _vp,
+                                             C.POINTER(PrtBakeInfo)]),
     "prt_enable_timing": (C.c_int, [_vp, C.c_int]),
     "prt_get_stats": (C.c_int, [_vp, C.POINTER(PrtStats)]),
     "prt_reset_stats": (C.c_int, [_vp]),

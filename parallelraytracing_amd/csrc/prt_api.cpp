@@ -32,6 +32,7 @@
 #include "prt_primary_cache.h"
 #include "prt_radiance.h"
 #include "prt_radiance_lit.h"
+#include "prt_bake.h"
 #include "prt_scene.h"
 #include "prt_temporal.h"
 #include "prt_temporal_contract.h"
@@ -240,6 +241,8 @@ struct PrtContext {
     bool samp_valid = false;
     int feature_chunk = 0;  // prt_set_param("feature_chunk", n): samples per chunk of the sampled pass, 0 = by the ray budget
     int radiance_chunk = 0;  // prt_set_param("radiance_chunk", n): samples per chunk of the radiance query, 0 = by the ray budget
+    int bake_chunk = 0;      // prt_set_param("bake_chunk", n): samples per chunk of a bake, 0 = by the ray budget of radiance_chunk
+    DevBuf bake;             // the faces and the map of a bake (prt_bake.h); its rays and the query's lists are in scratch
     DevBuf dn;
     // ---- temporal reprojection (include/prt.h): two history sets that ping-pong, the blended planar frame, status and
     // counters in one allocation; the basis and the placed copies' matrices of the step that wrote the history ----
@@ -1365,7 +1368,7 @@ void prt_destroy(PrtContext* c) {
         free_dev(c->d_work);
         free_dev(c->d_pix);
         free_dev(c->d_sort);
-        for (DevBuf* b : {&c->spill, &c->scratch, &c->feat, &c->guide, &c->samp, &c->dn, &c->tp, &c->tp_mt, &c->tpa}) b->release();
+        for (DevBuf* b : {&c->spill, &c->scratch, &c->feat, &c->guide, &c->samp, &c->dn, &c->tp, &c->tp_mt, &c->tpa, &c->bake}) b->release();
         for (EventPair& ep : c->events) {
             (void)hipEventDestroy(ep.a);
             (void)hipEventDestroy(ep.b);
@@ -3603,6 +3606,315 @@ int prt_radiance_lit_device(PrtContext* c, const PrtRadianceQuery* q, uint32_t n
                                 (uint32_t*)d_segments, x, info);
 }
 
+// ---- surface baking (include/prt.h "Surface baking") -------------------------------------------------------
+// What the refusals leave behind: the map's size, which records hold the target's faces, and the faces' UVs in face order.
+struct BakeTarget {
+    uint32_t W = 0, H = 0, n_faces = 0;
+    bool placed = false;
+    uint32_t inst = 0;        // a placed copy: its entry of hs.dev_insts
+    uint32_t mesh = 0;        // a placed copy: its instanced mesh
+    uint32_t face_first = 0;  // a world-space mesh: its first triangle in mesh and face order
+    std::vector<float> uv6, pos9, nrm9;
+};
+
+// The bake's own arrays in c->bake.
+struct BakeBufs {
+    PrtBakeFaces faces{};
+    PrtBakeMap map{};
+    uint32_t* list = nullptr;
+    uint32_t* counts = nullptr;
+    float* rgb[2] = {nullptr, nullptr};
+    uint8_t* cov2 = nullptr;
+};
+
+// Two events around a call's device work (PrtBakeInfo.device_ms)
+struct BakeTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~BakeTimer() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+// The refusals, in the order of the header; everything here is decided without a device.  q: null for the entry points
+// that trace nothing.
+static int check_bake(PrtContext* c, const PrtBakeTarget* t, const PrtRadianceQuery* q, bool with_query, BakeTarget* b) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (!t) return fail(c, PRT_ERR_INVALID, "prt_bake: null target");
+    const PrtHostScene& hs = c->hs;
+    const uint32_t n_meshes = (uint32_t)(hs.mesh_sizes.size() / 2);
+    const uint32_t* indices = nullptr;
+    uint32_t n_vertices = 0;
+    size_t has_uv_entry = 0;
+    if (t->kind == PRT_BAKE_MESH) {
+        if (t->index >= n_meshes) return fail(c, PRT_ERR_INVALID, "prt_bake: mesh %u of %u", t->index, n_meshes);
+        for (uint32_t m = 0; m < t->index; ++m) b->face_first += hs.mesh_sizes[2 * m + 1];
+        b->n_faces = hs.mesh_sizes[2 * t->index + 1];
+        n_vertices = hs.mesh_sizes[2 * t->index];
+        if (hs.mesh_indices.size() < 3 * ((size_t)b->face_first + b->n_faces)) return fail(c, PRT_ERR_INVALID, "prt_bake: the scene keeps no index buffer of mesh %u", t->index);
+        indices = hs.mesh_indices.data() + 3 * (size_t)b->face_first;
+        has_uv_entry = t->index;
+    } else if (t->kind == PRT_BAKE_INSTANCE) {
+        if (t->index >= hs.inst_mesh.size()) return fail(c, PRT_ERR_INVALID, "prt_bake: placed copy %u of %zu", t->index, hs.inst_mesh.size());
+        b->placed = true;
+        b->inst = hs.n_world_insts + t->index;
+        b->mesh = hs.inst_mesh[t->index];
+        if (b->mesh >= hs.placed_indices.size() || b->mesh >= hs.placed_meshes.size()) return fail(c, PRT_ERR_INVALID, "prt_bake: the scene keeps no index buffer of instanced mesh %u", b->mesh);
+        b->n_faces = (uint32_t)(hs.placed_indices[b->mesh].size() / 3);
+        n_vertices = hs.placed_vertices[b->mesh];
+        indices = hs.placed_indices[b->mesh].data();
+        has_uv_entry = (size_t)n_meshes + b->mesh;
+    } else {
+        return fail(c, PRT_ERR_INVALID, "prt_bake: unknown target kind %u", t->kind);
+    }
+    if (b->n_faces == 0u) return fail(c, PRT_ERR_INVALID, "prt_bake: the target has no faces");
+    if (t->width == 0u || t->height == 0u || t->width > PRT_TEX_MAX_SIZE || t->height > PRT_TEX_MAX_SIZE)
+        return fail(c, PRT_ERR_INVALID, "prt_bake: a %u x %u map, expected 1 .. %u each way", t->width, t->height, PRT_TEX_MAX_SIZE);
+    b->W = t->width;
+    b->H = t->height;
+    b->uv6.resize(6 * (size_t)b->n_faces);
+    if (t->uvs) {
+        for (size_t k = 0; k < 3 * (size_t)b->n_faces; ++k) {
+            if (indices[k] >= n_vertices) return fail(c, PRT_ERR_INVALID, "prt_bake: vertex index out of range");
+            b->uv6[2 * k] = t->uvs[2 * (size_t)indices[k]];
+            b->uv6[2 * k + 1] = t->uvs[2 * (size_t)indices[k] + 1];
+        }
+    } else {
+        const PrtTexTables& tx = c->tex;
+        if (!tx.is_set || has_uv_entry >= tx.mesh_has_uv.size() || !tx.mesh_has_uv[has_uv_entry])
+            return fail(c, PRT_ERR_INVALID, "prt_bake: no UVs: none given and the texture binding has none for this mesh");
+        const size_t first = b->placed ? (size_t)tx.inst_uv_base[b->inst] : (size_t)b->face_first;
+        if (tx.uvs.size() < 6 * (first + b->n_faces)) return fail(c, PRT_ERR_INVALID, "prt_bake: the texture binding's UV table is short");
+        memcpy(b->uv6.data(), tx.uvs.data() + 6 * first, 24 * (size_t)b->n_faces);
+    }
+    for (float v : b->uv6)
+        if (!(std::fabs(v) <= 1048576.0f)) return fail(c, PRT_ERR_INVALID, "prt_bake: a UV is not finite or above 2^20");
+    if (with_query) {
+        if (!q) return fail(c, PRT_ERR_INVALID, "prt_bake: null query");
+        if (q->samples == 0u || q->samples > PRT_RADIANCE_MAX_SAMPLES)
+            return fail(c, PRT_ERR_INVALID, "prt_bake: samples = %u, expected 1 .. %u", q->samples, PRT_RADIANCE_MAX_SAMPLES);
+        if ((uint64_t)b->W * b->H * q->samples > 0xFFFFFFFFull)
+            return fail(c, PRT_ERR_INVALID, "prt_bake: %u x %u texels x %u samples exceed 2^32 - 1 paths", b->W, b->H, q->samples);
+    }
+    return PRT_OK;
+}
+
+// The target's faces out of the triangle and normal records (leaf order, current after either refit) into face order
+static int bake_geometry(PrtContext* c, BakeTarget* b) {
+    if (const int rc = refresh_host_copies(c)) return rc;
+    const PrtHostScene& hs = c->hs;
+    size_t slot0 = 0, n_slots = hs.mesh_indices.size() / 3;
+    uint32_t base = hs.sc.n_prims + b->face_first;  // what face 0's record carries
+    if (b->placed) {
+        slot0 = hs.placed_meshes[b->mesh].slot_base;
+        n_slots = hs.placed_meshes[b->mesh].n_tris;
+        base = 0u;
+    }
+    if (hs.tri_records.size() < 12 * (slot0 + n_slots) || hs.nrm_records.size() < 12 * (slot0 + n_slots))
+        return fail(c, PRT_ERR_INVALID, "prt_bake: the scene keeps no triangle records of the target");
+    b->pos9.assign(9 * (size_t)b->n_faces, 0.0f);
+    b->nrm9.assign(9 * (size_t)b->n_faces, 0.0f);
+    size_t found = 0;
+    for (size_t sl = slot0; sl < slot0 + n_slots; ++sl) {
+        const float* r = &hs.tri_records[12 * sl];
+        const float* nr = &hs.nrm_records[12 * sl];
+        uint32_t prim;
+        memcpy(&prim, &r[3], 4);
+        const uint32_t f = prim - base;
+        if (f >= b->n_faces) continue;
+        for (int v = 0; v < 3; ++v)
+            for (int a = 0; a < 3; ++a) {
+                b->pos9[9 * (size_t)f + 3 * v + a] = r[4 * v + a];
+                b->nrm9[9 * (size_t)f + 3 * v + a] = nr[4 * v + a];
+            }
+        ++found;
+    }
+    if (found != b->n_faces) return fail(c, PRT_ERR_INVALID, "prt_bake: %zu of the target's %u faces are in the scene's records", found, b->n_faces);
+    return PRT_OK;
+}
+
+// Coverage, surface and the texel list of a checked target on the context's stream; counts (host) as of the list.  The
+// arrays are in c->bake; with_rgb: the two value buffers and the second coverage buffer of the gutter fill too.
+static int enqueue_bake_surface(PrtContext* c, BakeTarget* b, bool with_rgb, BakeBufs* x, uint32_t* counts) {
+    int rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (c->bake may be reallocated: nothing enqueued before may still be using it)
+    if ((rc = bake_geometry(c, b))) return rc;
+    const size_t F = b->n_faces, n = (size_t)b->W * b->H;
+    float *d_uv, *d_pos, *d_nrm;
+    PrtWorkspace ws;
+    ws.add(&d_uv, 6 * F).add(&d_pos, 9 * F).add(&d_nrm, 9 * F);
+    ws.add(&x->map.owner, n).add(&x->map.cov, n).add(&x->map.bary, 2 * n).add(&x->map.position, 3 * n).add(&x->map.normal, 3 * n);
+    ws.add(&x->list, n).add(&x->counts, (size_t)PRT_BAKE_COUNTERS);
+    if (with_rgb) ws.add(&x->rgb[0], 3 * n).add(&x->rgb[1], 3 * n).add(&x->cov2, n);
+    if ((rc = commit(c, ws, c->bake))) return rc;
+    if ((rc = upload(c, d_uv, b->uv6.data(), 6 * F)) || (rc = upload(c, d_pos, b->pos9.data(), 9 * F)) || (rc = upload(c, d_nrm, b->nrm9.data(), 9 * F)))
+        return rc;
+    x->map.W = b->W;
+    x->map.H = b->H;
+    x->faces.uv = d_uv;
+    x->faces.pos = d_pos;
+    x->faces.nrm = d_nrm;
+    x->faces.n_faces = b->n_faces;
+    x->faces.placed = b->placed ? 1u : 0u;
+    if (b->placed) {
+        memcpy(x->faces.mat, c->hs.dev_insts[b->inst].mat, 48);
+        memcpy(x->faces.inv, c->hs.dev_insts[b->inst].inv, 48);
+    }
+    HIPCHECK(c, hipMemsetAsync(x->map.owner, 0xFF, n * sizeof(uint32_t), c->stream));
+    HIPCHECK(c, hipMemsetAsync(x->counts, 0, PRT_BAKE_COUNTERS * sizeof(uint32_t), c->stream));
+    prt_launch_bk_cover(c->stream, x->faces, x->map, x->counts);
+    HIPCHECK(c, hipGetLastError());
+    prt_launch_bk_surface(c->stream, x->faces, x->map, x->counts);
+    HIPCHECK(c, hipGetLastError());
+    prt_launch_bk_compact(c->stream, (uint32_t)n, x->map.cov, x->list, x->counts);
+    HIPCHECK(c, hipGetLastError());
+    if ((rc = download(c, counts, x->counts, (size_t)PRT_BAKE_COUNTERS))) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (the host arrays of the uploads above are the caller's until here)
+    if (counts[PRT_BAKE_CNT_COVERED] > n) return fail(c, PRT_ERR_HIP, "prt_bake: %u covered texels of %zu", counts[PRT_BAKE_CNT_COVERED], n);
+    return PRT_OK;
+}
+
+static void bake_info_surface(PrtBakeInfo* info, const BakeTarget& b, const uint32_t* counts) {
+    if (!info) return;
+    *info = PrtBakeInfo{};
+    info->n_texels = (uint64_t)b.W * b.H;
+    info->n_covered = counts[PRT_BAKE_CNT_COVERED];
+    info->n_degenerate = counts[PRT_BAKE_CNT_DEGENERATE];
+    info->n_faces_skipped = counts[PRT_BAKE_CNT_SKIPPED];
+}
+
+int prt_bake_surface(PrtContext* c, const PrtBakeTarget* target, uint32_t* owner, float* bary, float* position, float* normal, PrtBakeInfo* info) {
+    BakeTarget b;
+    int rc = check_bake(c, target, nullptr, false, &b);
+    if (rc) return rc;
+    if ((rc = need_device(c))) return rc;
+    BakeBufs x;
+    uint32_t counts[PRT_BAKE_COUNTERS] = {};
+    if ((rc = enqueue_bake_surface(c, &b, false, &x, counts))) return rc;
+    const size_t n = (size_t)b.W * b.H;
+    if (owner && (rc = download(c, owner, x.map.owner, n))) return rc;
+    if (bary && (rc = download(c, bary, x.map.bary, 2 * n))) return rc;
+    if (position && (rc = download(c, position, x.map.position, 3 * n))) return rc;
+    if (normal && (rc = download(c, normal, x.map.normal, 3 * n))) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    bake_info_surface(info, b, counts);
+    return PRT_OK;
+}
+
+int prt_bake_rays(PrtContext* c, const PrtBakeTarget* target, uint32_t seed, uint32_t sample, float* origins, float* dirs, uint32_t* rng_state) {
+    BakeTarget b;
+    int rc = check_bake(c, target, nullptr, false, &b);
+    if (rc) return rc;
+    if (!origins || !dirs || !rng_state) return fail(c, PRT_ERR_INVALID, "prt_bake_rays: null array");
+    if ((rc = need_device(c))) return rc;
+    BakeBufs x;
+    uint32_t counts[PRT_BAKE_COUNTERS] = {};
+    if ((rc = enqueue_bake_surface(c, &b, false, &x, counts))) return rc;
+    const size_t n = (size_t)b.W * b.H;
+    float *d_o, *d_d;
+    uint32_t* d_rng;
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * n).add(&d_d, 3 * n).add(&d_rng, n);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    prt_launch_bk_rays(c->stream, (uint32_t)n, 1u, sample, seed, nullptr, x.map, d_o, d_d, d_rng);
+    HIPCHECK(c, hipGetLastError());
+    if ((rc = download(c, origins, d_o, 3 * n)) || (rc = download(c, dirs, d_d, 3 * n)) || (rc = download(c, rng_state, d_rng, n))) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+// Both forms of prt_bake_irradiance.  The rays of a chunk of whole samples go through the radiance query's own rounds
+// (enqueue_radiance / enqueue_radiance_lit with the states given, one sample per ray), sample-major over the covered texels,
+// and k_bk_sum adds a texel's values in ascending sample order: nothing depends on the chunk.
+static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting, uint32_t dilate, void* out_rgb,
+                           void* out_cov, bool device_out, PrtBakeInfo* info) {
+    BakeTarget b;
+    int rc = check_bake(c, target, q, true, &b);
+    if (rc) return rc;
+    if (!out_rgb) return fail(c, PRT_ERR_INVALID, "prt_bake_irradiance: null rgb_sum");
+    if ((rc = need_device(c))) return rc;
+    BakeTimer tm;
+    if (info) {
+        HIPCHECK(c, hipEventCreate(&tm.a));
+        HIPCHECK(c, hipEventCreate(&tm.b));
+        HIPCHECK(c, hipEventRecord(tm.a, c->stream));
+    }
+    BakeBufs x;
+    uint32_t counts[PRT_BAKE_COUNTERS] = {};
+    if ((rc = enqueue_bake_surface(c, &b, true, &x, counts))) return rc;
+    bake_info_surface(info, b, counts);
+    const size_t n = (size_t)b.W * b.H;
+    const uint32_t n_cov = counts[PRT_BAKE_CNT_COVERED];
+    HIPCHECK(c, hipMemsetAsync(x.rgb[0], 0, 3 * n * sizeof(float), c->stream));
+    const bool lit = lighting != 0 && c->lighting != (uint32_t)PRT_LIGHTING_OFF;
+    uint64_t shadow[2] = {0u, 0u};
+    if (n_cov != 0u) {
+        uint32_t cs = c->bake_chunk > 0 ? std::min((uint32_t)c->bake_chunk, q->samples) : radiance_chunk(c, *q, n_cov);
+        const size_t m = (size_t)cs * n_cov;
+        float *d_o, *d_d, *d_rgb;
+        uint32_t *d_rng, *d_seg;
+        RadianceScratch xs;
+        RadianceLitScratch xl;
+        PrtWorkspace ws;
+        ws.add(&d_o, 3 * m).add(&d_d, 3 * m).add(&d_rng, m).add(&d_rgb, 3 * m).add(&d_seg, m);
+        if (lit) xl.declare(ws, m, tex_on(c));
+        else xs.declare(ws, m, tex_on(c));
+        if ((rc = commit(c, ws, c->scratch))) return rc;
+        const PrtRadianceQuery q1{q->max_depth, 1u, q->seed, q->first_sample};  // (one sample per ray: the states are given)
+        for (uint32_t s0 = 0; s0 < q->samples; s0 += cs) {
+            const uint32_t ccs = std::min(cs, q->samples - s0);
+            const uint32_t mm = ccs * n_cov;
+            prt_launch_bk_rays(c->stream, n_cov, ccs, q->first_sample + s0, q->seed, x.list, x.map, d_o, d_d, d_rng);
+            HIPCHECK(c, hipGetLastError());
+            if (lit) {
+                PrtRadianceLitInfo li{0u, 0u};
+                if ((rc = enqueue_radiance_lit(c, q1, mm, 1u, d_o, d_d, d_rng, d_rgb, d_seg, xl, info ? &li : nullptr))) return rc;
+                shadow[0] += li.shadow_rays;
+                shadow[1] += li.shadow_occluded;
+            } else if ((rc = enqueue_radiance(c, q1, mm, 1u, d_o, d_d, d_rng, d_rgb, d_seg, xs))) {
+                return rc;
+            }
+            prt_launch_bk_sum(c->stream, n_cov, ccs, s0 == 0u, x.list, d_rgb, d_seg, x.rgb[0], x.counts);
+            HIPCHECK(c, hipGetLastError());
+        }
+    }
+    int cur = 0;
+    uint8_t* cov[2] = {x.map.cov, x.cov2};
+    for (uint32_t p = 0; p < dilate; ++p) {
+        prt_launch_bk_dilate(c->stream, b.W, b.H, cov[cur], x.rgb[cur], cov[cur ^ 1], x.rgb[cur ^ 1], x.counts);
+        HIPCHECK(c, hipGetLastError());
+        cur ^= 1;
+    }
+    const hipMemcpyKind kind = device_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHECK(c, hipMemcpyAsync(out_rgb, x.rgb[cur], 3 * n * sizeof(float), kind, c->stream));
+    if (out_cov) HIPCHECK(c, hipMemcpyAsync(out_cov, cov[cur], n, kind, c->stream));
+    if (info) {
+        if ((rc = download(c, counts, x.counts, (size_t)PRT_BAKE_COUNTERS))) return rc;
+        HIPCHECK(c, hipEventRecord(tm.b, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        HIPCHECK(c, hipEventElapsedTime(&ms, tm.a, tm.b));
+        info->n_filled = counts[PRT_BAKE_CNT_FILLED];
+        info->rays = (uint64_t)n_cov * q->samples;
+        info->segments = (uint64_t)counts[PRT_BAKE_CNT_SEGMENTS] | ((uint64_t)counts[PRT_BAKE_CNT_SEGMENTS + 1u] << 32);
+        info->shadow_rays = shadow[0];
+        info->shadow_occluded = shadow[1];
+        info->device_ms = (double)ms;
+    }
+    return device_out ? PRT_OK : prt_synchronize(c);  // (host form: waits for the stream and reports a ray a walk had to give up)
+}
+
+int prt_bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting, uint32_t dilate, float* rgb_sum,
+                        uint8_t* coverage, PrtBakeInfo* info) {
+    return bake_irradiance(c, target, q, lighting, dilate, rgb_sum, coverage, false, info);
+}
+
+int prt_bake_irradiance_device(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting, uint32_t dilate, void* d_rgb_sum,
+                               void* d_coverage, PrtBakeInfo* info) {
+    return bake_irradiance(c, target, q, lighting, dilate, d_rgb_sum, d_coverage, true, info);
+}
+
 int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,
                      float* shadow_dirs, float* tmax, uint32_t* light, float* contrib, float* pdf_light, float* pdf_bsdf,
                      float* w_light, float* w_bsdf) {
@@ -3968,6 +4280,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "denoise_lds" && value >= 0 && value <= 2) c->dn_lds = value;
     else if (n == "feature_chunk" && value >= 0 && value <= (int)PRT_FEATURE_MAX_SAMPLES) c->feature_chunk = value;
     else if (n == "radiance_chunk" && value >= 0 && value <= (int)PRT_RADIANCE_MAX_SAMPLES) c->radiance_chunk = value;
+    else if (n == "bake_chunk" && value >= 0 && value <= (int)PRT_RADIANCE_MAX_SAMPLES) c->bake_chunk = value;
     else if (n == "exit_max" && value >= 0 && value < 64) c->tune.exit_max = (uint32_t)value;
     else return fail(c, PRT_ERR_INVALID, "unknown parameter or bad value: %s = %d", name, value);
     return PRT_OK;

@@ -1444,6 +1444,8 @@ int prt_build_textures(const PrtHostScene& hs, const PrtTextureSet* set, PrtTexT
     }
     for (size_t m = 0; m < hs.placed_indices.size(); ++m)
         fill(t.uvs.data() + 6 * (size_t)placed_base[m], hs.placed_indices[m].data(), hs.placed_indices[m].size(), set->instanced_mesh_uvs[m]);
+    for (uint32_t m = 0; m < n_meshes; ++m) t.mesh_has_uv.push_back(set->mesh_uvs[m] ? 1u : 0u);
+    for (size_t m = 0; m < hs.placed_indices.size(); ++m) t.mesh_has_uv.push_back(set->instanced_mesh_uvs[m] ? 1u : 0u);
     t.inst_uv_base.resize(hs.dev_insts.size());
     for (size_t i = 0; i < hs.dev_insts.size(); ++i)
         t.inst_uv_base[i] = i < hs.n_world_insts ? 0u - hs.sc.n_prims : placed_base[hs.inst_mesh[i - hs.n_world_insts]];

@@ -157,6 +157,7 @@ struct PrtTexTables {
     std::vector<uint32_t> mat_tex;       // per material: texture or PRT_TEXTURE_NONE
     std::vector<float> uvs;              // 6 floats per triangle
     std::vector<uint32_t> inst_uv_base;  // per instance of PrtHostScene::dev_insts
+    std::vector<uint8_t> mesh_has_uv;    // per world-space mesh, then per instanced mesh: 1 = the set gave it UVs
 };
 // Checks `set` against the compiled scene (PRT_ERR_INVALID, message in *err, *out untouched) and builds the tables.
 int prt_build_textures(const PrtHostScene& hs, const PrtTextureSet* set, PrtTexTables* out, std::string* err);

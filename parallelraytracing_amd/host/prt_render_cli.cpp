@@ -13,6 +13,10 @@
 //              [--features-out PREFIX]
 //              [--frames N --orbit-deg D [--temporal [--temporal-max-history H]]]
 //              [--probe X,Y,Z --probe-size WxH --probe-lighting]
+//              [--bake WxH --bake-dilate N]
+// --bake WxH (with --ply) renders no frame: it writes PREFIX.pfm, the irradiance map of the mesh over the PLY's own UVs
+// (prt_bake_irradiance): --spp paths of up to --depth segments per covered texel, pi * sum / spp, top row first;
+// --bake-dilate N fills the gutters with N passes.  The first GPU; --lighting applies as it would to a frame.
 // --probe X,Y,Z renders no frame: it writes PREFIX.pfm, a lat-long radiance probe of --probe-size WxH texels (default 64x32)
 // at that point, --spp paths of up to --depth segments per texel along the texel centre's direction (prt_radiance), in the
 // layout --env reads (top row = the +Y pole): a probe of one scene can light another.  The first GPU; the estimator is the
@@ -90,6 +94,8 @@ int main(int argc, char** argv) {
     bool probe = false, probe_lighting = false;
     float probe_pos[3] = {0.0f, 0.0f, 0.0f};
     uint32_t probe_w = 64, probe_h = 32;
+    bool bake = false;
+    uint32_t bake_w = 0, bake_h = 0, bake_dilate = 0;
     std::vector<int> devices{0};
     float cam[3] = {5.0f, 5.0f, 8.0f};
     bool cam_set = false;
@@ -166,6 +172,11 @@ int main(int argc, char** argv) {
             probe = true;
         }
         else if (a == "--probe-lighting") probe_lighting = true;
+        else if (a == "--bake") {
+            if (sscanf(next(), "%ux%u", &bake_w, &bake_h) != 2 || !bake_w || !bake_h) { fprintf(stderr, "--bake takes WxH\n"); return 2; }
+            bake = true;
+        }
+        else if (a == "--bake-dilate") bake_dilate = (uint32_t)atoi(next());
         else if (a == "--probe-size") {
             if (sscanf(next(), "%ux%u", &probe_w, &probe_h) != 2 || !probe_w || !probe_h) { fprintf(stderr, "--probe-size takes WxH\n"); return 2; }
         }
@@ -198,6 +209,10 @@ int main(int argc, char** argv) {
     }
     if (probe && (orbit || adaptive || denoise || !features_out.empty())) {
         fprintf(stderr, "--probe renders no frame: it does not go with --orbit-deg, --adaptive, --denoise or --features-out\n");
+        return 2;
+    }
+    if (bake && (ply.empty() || probe || orbit || adaptive || denoise || temporal || !features_out.empty())) {
+        fprintf(stderr, "--bake goes with --ply and renders no frame: it does not go with --probe, --orbit-deg, --adaptive, --denoise, --temporal or --features-out\n");
         return 2;
     }
     if (probe_lighting && !probe) {
@@ -253,6 +268,16 @@ int main(int argc, char** argv) {
             if (prt_write_pfm((out + ".pfm").c_str(), rgb.data(), probe_w, probe_h)) { fprintf(stderr, "cannot write %s.pfm\n", out.c_str()); return 1; }
             printf("probe at (%g, %g, %g): %ux%u texels, %u spp, max_depth %u -> %s.pfm\n", probe_pos[0], probe_pos[1], probe_pos[2], probe_w, probe_h, spp,
                    depth, out.c_str());
+            return 0;
+        }
+        if (bake) {
+            if (!scene->MeshHasUVs(0)) { fprintf(stderr, "error: --bake: %s has no per-vertex UVs\n", ply.c_str()); return 1; }
+            std::vector<float> irr;
+            PrtBakeInfo bi{};
+            r.BakeIrradiance(0u, scene->mesh_uvs.at(0), bake_w, bake_h, spp, irr, bake_dilate, lighting != PRT_LIGHTING_OFF, nullptr, &bi);
+            if (prt_write_pfm((out + ".pfm").c_str(), irr.data(), bake_w, bake_h)) { fprintf(stderr, "cannot write %s.pfm\n", out.c_str()); return 1; }
+            printf("bake: %ux%u texels, %llu covered, %llu filled, %u spp, max_depth %u, %llu segments, %.3f ms on the device -> %s.pfm\n", bake_w, bake_h,
+                   (unsigned long long)bi.n_covered, (unsigned long long)bi.n_filled, spp, depth, (unsigned long long)bi.segments, bi.device_ms, out.c_str());
             return 0;
         }
         if (orbit) {  // the animation: one cleared film per frame, the camera on a circle about the vertical axis

@@ -492,6 +492,24 @@ public:
         Radiance((uint32_t)n, o.data(), d.data(), rgb.data(), samples, 0u, nullptr, nullptr, lighting);
         for (float& v : rgb) v = v / (float)samples;
     }
+    // Surface baking on the first GPU's context (prt_bake_irradiance, include/prt.h "Surface baking"): the irradiance map of
+    // world-space mesh `index` (kind = PRT_BAKE_INSTANCE: placed copy `index`) over its UV layout, width x height x 3 floats,
+    // pi * sum / samples, row 0 on top.  uvs: n_vertices x 2 floats for this call, null: the texture binding's.  dilate:
+    // passes of the gutter fill.  coverage (may be null): width x height bytes, 0 none, 1 owned, 2 filled.  lighting:
+    // Radiance's.  info (may be null): the counts of the call.
+    void BakeIrradiance(uint32_t index, const float* uvs, uint32_t width, uint32_t height, uint32_t samples, std::vector<float>& irradiance,
+                        uint32_t dilate = 0, bool lighting = false, std::vector<uint8_t>* coverage = nullptr, PrtBakeInfo* info = nullptr,
+                        uint32_t kind = PRT_BAKE_MESH, uint32_t first_sample = 0) {
+        PrtContext* c = prt_group_context(grp_, 0);
+        const PrtBakeTarget t{kind, index, uvs, width, height};
+        const PrtRadianceQuery q{max_depth_, samples, seed_, first_sample};
+        const size_t n = (size_t)width * height;
+        irradiance.assign(3 * n, 0.0f);
+        if (coverage) coverage->assign(n, 0);
+        if (prt_bake_irradiance(c, &t, &q, lighting ? 1 : 0, dilate, irradiance.data(), coverage ? coverage->data() : nullptr, info))
+            throw Error(std::string("prt_bake_irradiance: ") + prt_last_error(c));
+        for (float& v : irradiance) v = v * 3.14159274f / (float)samples;
+    }
 
 private:
     void check(int rc) {

@@ -1229,6 +1229,87 @@ class HipWavefrontRenderer:
         return self.radiance(o, d, samples=samples, seed=seed, first_sample=first_sample, max_depth=max_depth,
                              lighting=lighting).reshape(H, W, 3)
 
+    # ---- surface baking (include/prt.h "Surface baking") ---------------------------------------------------------
+    def _bake_target(self, mesh, instance, size, uvs):
+        """The PrtBakeTarget of world-space mesh `mesh` or placed copy `instance` on a size = (H, W) map, and what keeps
+        its UV array alive.  uvs: [n_vertices, 2] for this call, None: the texture binding's."""
+        if (mesh is None) == (instance is None):
+            raise ValueError("bake: give exactly one of mesh= (a world-space mesh) and instance= (a placed copy)")
+        H, W = (int(v) for v in size)
+        if H < 0 or W < 0 or H > 0xFFFFFFFF or W > 0xFFFFFFFF:
+            raise ValueError(f"bake: size {size}")
+        index = int(mesh if mesh is not None else instance)
+        if index < 0:
+            raise ValueError(f"bake: index {index}")
+        uv = None if uvs is None else np.ascontiguousarray(_f32(uvs).reshape(-1, 2))
+        t = capi.PrtBakeTarget(capi.BAKE_MESH if mesh is not None else capi.BAKE_INSTANCE, index,
+                               uv.ctypes.data_as(_fp) if uv is not None else None, W, H)
+        return t, uv, H, W
+
+    @staticmethod
+    def _bake_info(info: "capi.PrtBakeInfo") -> dict:
+        return {name: getattr(info, name) for name, _ in capi.PrtBakeInfo._fields_}
+
+    def bake_surface(self, mesh=None, instance=None, size=(64, 64), uvs=None) -> dict:
+        """The surface under every texel of a size = (H, W) map over the UV layout of world-space mesh `mesh` or placed copy
+        `instance` (prt_bake_surface): {"owner" [H, W] uint32 (capi.BAKE_NONE: uncovered), "coverage" [H, W] uint8,
+        "bary" [H, W, 2] (b1, b2), "position", "normal" [H, W, 3] in world space, "info"}."""
+        t, keep, H, W = self._bake_target(mesh, instance, size, uvs)
+        owner = np.zeros((H, W), np.uint32)
+        bary = np.zeros((H, W, 2), np.float32)
+        pos, nrm = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
+        info = capi.PrtBakeInfo()
+        self._check(capi.lib().prt_bake_surface(self._ctx, C.byref(t), owner.ctypes.data_as(_u32p), bary.ctypes.data_as(_fp),
+                                                pos.ctypes.data_as(_fp), nrm.ctypes.data_as(_fp), C.byref(info)))
+        return {"owner": owner, "coverage": (owner != capi.BAKE_NONE).astype(np.uint8), "bary": bary, "position": pos, "normal": nrm,
+                "info": self._bake_info(info)}
+
+    def bake_rays(self, mesh=None, instance=None, size=(64, 64), uvs=None, sample: int = 0, seed=None) -> dict:
+        """The ray of sample `sample` of every texel (prt_bake_rays): {"o", "d" [H, W, 3], "rng_state" [H, W] uint32}, zero
+        where the texel is uncovered.  radiance(o, d, rng_state=...) over the covered texels follows a bake's paths."""
+        t, keep, H, W = self._bake_target(mesh, instance, size, uvs)
+        o, d = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
+        rng = np.zeros((H, W), np.uint32)
+        self._check(capi.lib().prt_bake_rays(self._ctx, C.byref(t), int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                             int(sample) & 0xFFFFFFFF, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp), rng.ctypes.data_as(_u32p)))
+        return {"o": o, "d": d, "rng_state": rng}
+
+    def bake_irradiance(self, mesh=None, instance=None, size=(64, 64), uvs=None, samples: int = 16, seed=None, first_sample: int = 0,
+                        max_depth=None, lighting: bool = False, dilate: int = 0, out: str = "numpy", return_info: bool = False):
+        """An irradiance map [H, W, 3] over the UV layout of a mesh (prt_bake_irradiance): every covered texel is a
+        Lambertian vertex of albedo 1 whose `samples` paths the radiance query follows; the value is
+        sum * float32(pi) / float32(samples), so a Lambertian surface of albedo rho shows rho / pi times it.  lighting:
+        radiance()'s.  dilate: passes of the gutter fill.  out = "torch": a tensor on the renderer's device through the
+        device form.  return_info: also {"sum": the raw fp32 sums, "coverage": [H, W] uint8 (0 none, 1 owned, 2 filled),
+        "info": the counts of the call}."""
+        if out not in ("numpy", "torch"):
+            raise ValueError(f"out: {out!r}, expected 'numpy' or 'torch'")
+        t, keep, H, W = self._bake_target(mesh, instance, size, uvs)
+        q = capi.PrtRadianceQuery(int(self.max_depth if max_depth is None else max_depth), int(samples),
+                                  int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample) & 0xFFFFFFFF)
+        info = capi.PrtBakeInfo()
+        if out == "torch":
+            import torch
+            dev = self._torch_device()
+            total = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+            cov = torch.zeros((H, W), dtype=torch.uint8, device=dev)
+            self._on_context_stream(lambda: capi.lib().prt_bake_irradiance_device(
+                self._ctx, C.byref(t), C.byref(q), int(bool(lighting)), int(dilate), C.c_void_p(total.data_ptr()), C.c_void_p(cov.data_ptr()),
+                C.byref(info) if return_info else None))
+            # (tensor operands: torch turns a division by a Python number into a multiplication by its reciprocal)
+            irr = total * torch.full((1, 1, 1), float(np.float32(np.pi)), dtype=torch.float32, device=dev) \
+                / torch.full((1, 1, 1), float(q.samples), dtype=torch.float32, device=dev)
+        else:
+            total = np.zeros((H, W, 3), np.float32)
+            cov = np.zeros((H, W), np.uint8)
+            self._check(capi.lib().prt_bake_irradiance(self._ctx, C.byref(t), C.byref(q), int(bool(lighting)), int(dilate),
+                                                       total.ctypes.data_as(_fp), cov.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                       C.byref(info) if return_info else None))
+            irr = total * np.float32(np.pi) / np.float32(q.samples)
+        if return_info:
+            return irr, {"sum": total, "coverage": cov, "info": self._bake_info(info)}
+        return irr
+
     def enable_timing(self, on: bool = True):
         self._check(capi.lib().prt_enable_timing(self._ctx, int(on)))
 
