@@ -1206,6 +1206,20 @@ int prt_radiance_lit(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, con
 /* The same from DEVICE arrays on the context's stream.  info is a HOST pointer; NULL: no final wait for it. */
 int prt_radiance_lit_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs,
                             void* d_rng_state, void* d_rgb_sum, void* d_segments, PrtRadianceLitInfo* info);
+/* The lit query for rays that a Lambertian vertex of the caller's scattered: pb[i] (n floats) is the pdf of that scatter
+ * along ray i, max(0, n.d) / pi, and path (i, s) starts with pb = pb[i] where prt_radiance_lit starts with -1.  The value
+ * is used as given, for every sample of ray i; everything else is prt_radiance_lit's contract.  So an Emissive hit of a
+ * light-set emitter on segment 0, and an environment miss on segment 0, carry the weight 1 - w_L of (origin, direction,
+ * pb[i]) exactly as on a later segment after a Lambertian vertex: a caller who takes the first vertex's light sample
+ * themselves and continues here counts direct light once under PRT_LIGHTING_NEE_MIS and PRT_LIGHTING_NEE.
+ *  pb == NULL: prt_radiance_lit / prt_radiance_lit_device, bit for bit.  A value that is not >= 0 (negative, NaN): no
+ *    weighting on segment 0, as with -1.
+ *  Mode PRT_LIGHTING_OFF: pb is ignored and the result is prt_radiance's.
+ *  Refusals and cost: prt_radiance_lit's. */
+int prt_radiance_lit_pb(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const float* origins, const float* dirs,
+                        uint32_t* rng_state, const float* pb, float* rgb_sum, uint32_t* segments, PrtRadianceLitInfo* info);
+int prt_radiance_lit_pb_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs,
+                               void* d_rng_state, const void* d_pb, void* d_rgb_sum, void* d_segments, PrtRadianceLitInfo* info);
 
 /* ---- Surface baking: irradiance maps over a mesh's UV layout ------------------------------------
  * From a mesh to the rays of its texels, on the device: the UV layout is rasterised into a W x H map, every covered texel
@@ -1233,7 +1247,7 @@ int prt_radiance_lit_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t
  *  Paths: from there the path is prt_radiance's path for (o, d, rng_state) with q.max_depth segments, bit for bit (segment
  *    index 0 is the texel's ray; hit rule, textures, environment, roulette and clamp as there).  lighting != 0: it is
  *    prt_radiance_lit's path under the context's lighting settings, pb = -1 on segment 0: emission met directly from the
- *    texel counts at weight 1 and no light sample is taken at the texel itself.
+ *    texel counts at weight 1 and no light sample is taken at the texel itself (unless texel_light is set: below).
  *  Texel value: rgb_sum[t] = the fp32 sum, from 0.0f in ascending sample order, of the q.samples path values, whatever the
  *    chunking (prt_set_param("bake_chunk", samples per chunk; 0 = by the ray budget of "radiance_chunk")).  A sum, as in
  *    the film: irradiance on the +n side is pi * sum / samples, the exit radiance of a Lambertian of albedo rho is
@@ -1250,7 +1264,31 @@ int prt_radiance_lit_device(PrtContext* ctx, const PrtRadianceQuery* q, uint32_t
  *  Cost: three small passes over faces and texels (one wave per face striding its clipped bounding box; one thread per
  *    texel; one block compacting the covered texels in ascending order), then per chunk of whole samples one ray kernel,
  *    the radiance query's rounds over covered texels x samples of the chunk, and one ordered sum.
- * Not offered: the group (prt_group_*); a light sample at the texel itself. */
+ *  The texel's light sample (prt_bake_irradiance_opt with lighting != 0 and texel_light != 0, under a lighting mode that is
+ *    not PRT_LIGHTING_OFF, with q.max_depth >= 1): the texel is treated as the Lambertian vertex it is, so direct light is
+ *    sampled at the texel and what the texel's own ray meets is MIS-weighted.  For sample s of covered texel t with
+ *    position p and normal n:
+ *    Key: key = path_seed(t, first_sample + s, seed), the state BEFORE the texel's scatter draws (what the lit query's step
+ *      calls `key`).  The light stream never advances the path's state: prt_bake_rays and every path are draw for draw
+ *      what they are without the sample.
+ *    Sample: the one a render's Lambertian vertex takes with albedo (1,1,1) and throughput (1,1,1): toward the environment
+ *      if its draw of `key` says so, else toward the light set if it is not empty; position p, normal n,
+ *      PrtSampling.clamp; the context's mode, source mask, selection and environment share: prt_sample_light's sample for
+ *      a hit at p with normal n on a white Lambertian, its contrib clamped per component.
+ *    Shadow ray: (p, w, tmax) is cast iff there is a sample and n.w > 0; it is occluded by prt_occluded's rule.
+ *      e = the clamped contrib if unoccluded, else 0.
+ *    The texel ray's pdf: ray_pb = (c > 0 ? c : 0) * 0.318309886183790672f with c = (nx dx + ny dy) + nz dz in fp32, d the
+ *      texel's ray direction as prt_bake_rays returns it: the lit step's pdf of a Lambertian scatter.
+ *    Sample value: fl(q + e) per component, q = prt_radiance_lit_pb's sample value for (o, d, rng_state, ray_pb) with
+ *      q.max_depth segments.  e is added after q, not inside the query's light sum: the bake is then a composition of
+ *      public functions (prt_bake_rays, prt_bake_light_samples, prt_occluded, prt_radiance_lit_pb) that can be redone bit
+ *      for bit.  rgb_sum[t] = the fp32 sum of the values in ascending sample order from 0.0f, whatever the chunking.
+ *    max_depth == 0: every output is zero and no sample is taken.  Mode OFF, lighting == 0 or texel_light == 0: no texel
+ *      sample; the result is prt_bake_irradiance's, bit for bit.
+ *    PrtBakeInfo.shadow_rays / shadow_occluded include the texels' shadow rays.
+ *    Cost: per chunk one sample kernel, one more pass of the occlusion pipeline over the chunk's rays (a ray that is not
+ *      cast rides along with tmax = 0, which never occludes) and one add kernel; no host wait beyond the lit bake's.
+ * Not offered: the group (prt_group_*). */
 #define PRT_BAKE_MESH 0u
 #define PRT_BAKE_INSTANCE 1u
 typedef struct PrtBakeTarget {
@@ -1281,6 +1319,27 @@ int prt_bake_irradiance(PrtContext* ctx, const PrtBakeTarget* target, const PrtR
  * with the waits the query has (and one for the covered count); complete in stream order on return. */
 int prt_bake_irradiance_device(PrtContext* ctx, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting,
                                uint32_t dilate, void* d_rgb_sum, void* d_coverage, PrtBakeInfo* info);
+/* The same two calls with their options in a struct; prt_bake_irradiance[_device] are these with texel_light = 0.
+ * texel_light != 0: the texel's light sample, above.  Refusals: a null options pointer, reserved != 0, then
+ * prt_bake_irradiance's in their order, all decided without a device. */
+typedef struct PrtBakeOptions {
+    uint32_t lighting;     /* != 0: prt_radiance_lit's paths */
+    uint32_t texel_light;  /* != 0: a light sample at the texel itself (needs lighting != 0 to have an effect) */
+    uint32_t dilate;
+    uint32_t reserved;     /* must be 0 */
+} PrtBakeOptions;
+int prt_bake_irradiance_opt(PrtContext* ctx, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* options,
+                            float* rgb_sum, uint8_t* coverage, PrtBakeInfo* info);
+int prt_bake_irradiance_opt_device(PrtContext* ctx, const PrtBakeTarget* target, const PrtRadianceQuery* q,
+                                   const PrtBakeOptions* options, void* d_rgb_sum, void* d_coverage, PrtBakeInfo* info);
+/* The light sample of sample `sample` of every texel: the function-level view of the light kernel, in the manner of
+ * prt_bake_rays.  Host arrays over the full map, zero / none where uncovered, each may be NULL: dirs [3*H*W] (the sampled
+ * direction w, also where n.w <= 0), tmax [H*W] (0: no shadow ray is cast), light [H*W] (the light-set index,
+ * PRT_LIGHT_ENVIRONMENT, or 0xFFFFFFFF: no sample), contrib [3*H*W] (clamped, before visibility; 0 where no ray is cast),
+ * ray_pb [H*W].  Under PRT_LIGHTING_OFF the sample is PRT_LIGHTING_NEE_MIS's, as prt_sample_light's is.  Refusals:
+ * prt_bake_rays's. */
+int prt_bake_light_samples(PrtContext* ctx, const PrtBakeTarget* target, uint32_t seed, uint32_t sample, float* dirs, float* tmax,
+                           uint32_t* light, float* contrib, float* ray_pb);
 
 /* ---- measurement ----------------------------------------------------------------------------- */
 int prt_enable_timing(PrtContext* ctx, int on); /* HIP events around every kernel launch */

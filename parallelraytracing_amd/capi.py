@@ -124,6 +124,11 @@ class PrtBakeInfo(C.Structure):
                 ("shadow_occluded", C.c_uint64), ("device_ms", C.c_double)]
 
 
+class PrtBakeOptions(C.Structure):
+    """The options of prt_bake_irradiance_opt (include/prt.h "Surface baking"); reserved must be 0."""
+    _fields_ = [("lighting", C.c_uint32), ("texel_light", C.c_uint32), ("dilate", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class PrtAdaptive(C.Structure):
     """Settings of prt_render_adaptive (include/prt.h "Film statistics and adaptive sampling")."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
@@ -387,12 +392,21 @@ SIGNATURES = {
     "prt_radiance_lit": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _fp, _fp, _u32p, _fp, _u32p, C.POINTER(PrtRadianceLitInfo)]),
     "prt_radiance_lit_device": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                           C.POINTER(PrtRadianceLitInfo)]),
+    "prt_radiance_lit_pb": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _fp, _fp, _u32p, _fp, _fp, _u32p,
+                                      C.POINTER(PrtRadianceLitInfo)]),
+    "prt_radiance_lit_pb_device": (C.c_int, [_vp, C.POINTER(PrtRadianceQuery), C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             C.POINTER(PrtRadianceLitInfo)]),
     "prt_bake_surface": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), _u32p, _fp, _fp, _fp, C.POINTER(PrtBakeInfo)]),
     "prt_bake_rays": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.c_uint32, C.c_uint32, _fp, _fp, _u32p]),
     "prt_bake_irradiance": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.c_int, C.c_uint32, _fp,
                                       C.POINTER(C.c_uint8), C.POINTER(PrtBakeInfo)]),
     "prt_bake_irradiance_device": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.c_int, C.c_uint32, _vp, _vp,
                                              C.POINTER(PrtBakeInfo)]),
+    "prt_bake_irradiance_opt": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.POINTER(PrtBakeOptions), _fp,
+                                          C.POINTER(C.c_uint8), C.POINTER(PrtBakeInfo)]),
+    "prt_bake_irradiance_opt_device": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.POINTER(PrtBakeOptions),
+                                                 _vp, _vp, C.POINTER(PrtBakeInfo)]),
+    "prt_bake_light_samples": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.c_uint32, C.c_uint32, _fp, _fp, _u32p, _fp, _fp]),
     "prt_enable_timing": (C.c_int, [_vp, C.c_int]),
     "prt_get_stats": (C.c_int, [_vp, C.POINTER(PrtStats)]),
     "prt_reset_stats": (C.c_int, [_vp]),

@@ -33,6 +33,7 @@
 #include "prt_radiance.h"
 #include "prt_radiance_lit.h"
 #include "prt_bake.h"
+#include "prt_bake_light.h"
 #include "prt_scene.h"
 #include "prt_temporal.h"
 #include "prt_temporal_contract.h"
@@ -3497,8 +3498,10 @@ struct RadianceLitScratch {
 // 8-byte copy, and before that round's closest-hit query: both pipelines pack into rb[0], one after the other.  The last
 // round (segment max_depth - 1) takes no light sample, and a chunk whose paths all end earlier resolves before it
 // leaves the loop: so there is no wait beyond the unlit query's one per round.  info (host, may be null): one more read.
+// d_pb (may be null): the pdf of the caller's own Lambertian scatter along each ray (prt_radiance_lit_pb).
 static int enqueue_radiance_lit(PrtContext* c, const PrtRadianceQuery& q, uint32_t n, uint32_t cs, const float* d_o, const float* d_d,
-                                uint32_t* d_rng, float* d_rgb, uint32_t* d_seg, const RadianceLitScratch& x, PrtRadianceLitInfo* info) {
+                                uint32_t* d_rng, const float* d_pb, float* d_rgb, uint32_t* d_seg, const RadianceLitScratch& x,
+                                PrtRadianceLitInfo* info) {
     int rc;
     if (info) *info = PrtRadianceLitInfo{0u, 0u};
     if (q.max_depth == 0u) {
@@ -3515,7 +3518,7 @@ static int enqueue_radiance_lit(PrtContext* c, const PrtRadianceQuery& q, uint32
     for (uint32_t s0 = 0; s0 < q.samples; s0 += cs) {
         const uint32_t ccs = std::min(cs, q.samples - s0);
         const uint32_t m = ccs * n;
-        prt_launch_rdl_start(c->stream, n, ccs, q.first_sample + s0, q.seed, d_o, d_d, d_rng, x.list[0]);
+        prt_launch_rdl_start(c->stream, n, ccs, q.first_sample + s0, q.seed, d_o, d_d, d_rng, d_pb, x.list[0]);
         HIPCHECK(c, hipGetLastError());
         HIPCHECK(c, hipMemsetAsync(x.lsum, 0, (size_t)m * sizeof(float4), c->stream));
         uint32_t live = m;
@@ -3561,8 +3564,8 @@ static int enqueue_radiance_lit(PrtContext* c, const PrtRadianceQuery& q, uint32
     return PRT_OK;
 }
 
-int prt_radiance_lit(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const float* origins, const float* dirs, uint32_t* rng_state,
-                     float* rgb_sum, uint32_t* segments, PrtRadianceLitInfo* info) {
+int prt_radiance_lit_pb(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const float* origins, const float* dirs, uint32_t* rng_state,
+                        const float* pb, float* rgb_sum, uint32_t* segments, PrtRadianceLitInfo* info) {
     int rc = check_radiance(c, q, n, origins, dirs, rng_state, rgb_sum);
     if (info) *info = PrtRadianceLitInfo{0u, 0u};
     if (rc || n == 0u) return rc;
@@ -3571,26 +3574,33 @@ int prt_radiance_lit(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const
     const uint32_t cs = radiance_chunk(c, *q, n);
     const size_t n1 = n;
     HIPCHECK(c, hipStreamSynchronize(c->stream));  // (as prt_radiance: the scratch may be reallocated)
-    float *d_o, *d_d, *d_rgb;
+    float *d_o, *d_d, *d_rgb, *d_pb = nullptr;
     uint32_t *d_rng = nullptr, *d_seg = nullptr;
     RadianceLitScratch x;
     PrtWorkspace ws;
     ws.add(&d_o, 3 * n1).add(&d_d, 3 * n1).add(&d_rgb, 3 * n1);
     if (rng_state) ws.add(&d_rng, n1);
     if (segments) ws.add(&d_seg, n1);
+    if (pb) ws.add(&d_pb, n1);
     x.declare(ws, (size_t)cs * n1, tex_on(c));
     if ((rc = commit(c, ws, c->scratch))) return rc;
     if ((rc = upload(c, d_o, origins, 3 * n1)) || (rc = upload(c, d_d, dirs, 3 * n1))) return rc;
     if (rng_state && (rc = upload(c, d_rng, rng_state, n1))) return rc;
-    if ((rc = enqueue_radiance_lit(c, *q, n, cs, d_o, d_d, d_rng, d_rgb, d_seg, x, info))) return rc;
+    if (pb && (rc = upload(c, d_pb, pb, n1))) return rc;
+    if ((rc = enqueue_radiance_lit(c, *q, n, cs, d_o, d_d, d_rng, d_pb, d_rgb, d_seg, x, info))) return rc;
     if ((rc = download(c, rgb_sum, d_rgb, 3 * n1))) return rc;
     if (rng_state && (rc = download(c, rng_state, d_rng, n1))) return rc;
     if (segments && (rc = download(c, segments, d_seg, n1))) return rc;
     return prt_synchronize(c);  // waits for the stream and reports a ray a walk (closest hit or shadow) had to give up
 }
 
-int prt_radiance_lit_device(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs, void* d_rng_state,
-                            void* d_rgb_sum, void* d_segments, PrtRadianceLitInfo* info) {
+int prt_radiance_lit(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const float* origins, const float* dirs, uint32_t* rng_state,
+                     float* rgb_sum, uint32_t* segments, PrtRadianceLitInfo* info) {
+    return prt_radiance_lit_pb(c, q, n, origins, dirs, rng_state, nullptr, rgb_sum, segments, info);
+}
+
+int prt_radiance_lit_pb_device(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs, void* d_rng_state,
+                               const void* d_pb, void* d_rgb_sum, void* d_segments, PrtRadianceLitInfo* info) {
     int rc = check_radiance(c, q, n, d_origins, d_dirs, d_rng_state, d_rgb_sum);
     if (info) *info = PrtRadianceLitInfo{0u, 0u};
     if (rc || n == 0u) return rc;
@@ -3602,8 +3612,13 @@ int prt_radiance_lit_device(PrtContext* c, const PrtRadianceQuery* q, uint32_t n
     PrtWorkspace ws;
     x.declare(ws, (size_t)cs * n, tex_on(c));
     if ((rc = commit(c, ws, c->scratch))) return rc;
-    return enqueue_radiance_lit(c, *q, n, cs, (const float*)d_origins, (const float*)d_dirs, (uint32_t*)d_rng_state, (float*)d_rgb_sum,
-                                (uint32_t*)d_segments, x, info);
+    return enqueue_radiance_lit(c, *q, n, cs, (const float*)d_origins, (const float*)d_dirs, (uint32_t*)d_rng_state, (const float*)d_pb,
+                                (float*)d_rgb_sum, (uint32_t*)d_segments, x, info);
+}
+
+int prt_radiance_lit_device(PrtContext* c, const PrtRadianceQuery* q, uint32_t n, const void* d_origins, const void* d_dirs, void* d_rng_state,
+                            void* d_rgb_sum, void* d_segments, PrtRadianceLitInfo* info) {
+    return prt_radiance_lit_pb_device(c, q, n, d_origins, d_dirs, d_rng_state, nullptr, d_rgb_sum, d_segments, info);
 }
 
 // ---- surface baking (include/prt.h "Surface baking") -------------------------------------------------------
@@ -3827,8 +3842,16 @@ int prt_bake_rays(PrtContext* c, const PrtBakeTarget* target, uint32_t seed, uin
 // Both forms of prt_bake_irradiance.  The rays of a chunk of whole samples go through the radiance query's own rounds
 // (enqueue_radiance / enqueue_radiance_lit with the states given, one sample per ray), sample-major over the covered texels,
 // and k_bk_sum adds a texel's values in ascending sample order: nothing depends on the chunk.
-static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting, uint32_t dilate, void* out_rgb,
+// With the texel's light sample (opt.texel_light under a lit bake with max_depth >= 1): per chunk k_bkl_sample takes the
+// samples and the pdfs of the texels' rays, the lit query starts its paths from those pdfs, one pass of the occlusion
+// pipeline resolves the texels' shadow rays (dense: a ray that is not cast has tmax = 0 and never occludes, so there is no
+// count to wait for) and k_bkl_add adds what arrives to the query's values before the ordered sum.
+static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* opt, void* out_rgb,
                            void* out_cov, bool device_out, PrtBakeInfo* info) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!opt) return fail(c, PRT_ERR_INVALID, "prt_bake_irradiance_opt: null options");
+    if (opt->reserved != 0u) return fail(c, PRT_ERR_INVALID, "prt_bake_irradiance_opt: reserved = %u, expected 0", opt->reserved);
+    const uint32_t dilate = opt->dilate;
     BakeTarget b;
     int rc = check_bake(c, target, q, true, &b);
     if (rc) return rc;
@@ -3847,7 +3870,8 @@ static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const Prt
     const size_t n = (size_t)b.W * b.H;
     const uint32_t n_cov = counts[PRT_BAKE_CNT_COVERED];
     HIPCHECK(c, hipMemsetAsync(x.rgb[0], 0, 3 * n * sizeof(float), c->stream));
-    const bool lit = lighting != 0 && c->lighting != (uint32_t)PRT_LIGHTING_OFF;
+    const bool lit = opt->lighting != 0u && c->lighting != (uint32_t)PRT_LIGHTING_OFF;
+    const bool texel = lit && opt->texel_light != 0u && q->max_depth != 0u;
     uint64_t shadow[2] = {0u, 0u};
     if (n_cov != 0u) {
         uint32_t cs = c->bake_chunk > 0 ? std::min((uint32_t)c->bake_chunk, q->samples) : radiance_chunk(c, *q, n_cov);
@@ -3856,27 +3880,59 @@ static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const Prt
         uint32_t *d_rng, *d_seg;
         RadianceScratch xs;
         RadianceLitScratch xl;
+        PrtBakeLightRays tl{};
+        uint8_t* d_tocc = nullptr;
+        unsigned long long* d_tstats = nullptr;
         PrtWorkspace ws;
         ws.add(&d_o, 3 * m).add(&d_d, 3 * m).add(&d_rng, m).add(&d_rgb, 3 * m).add(&d_seg, m);
         if (lit) xl.declare(ws, m, tex_on(c));
         else xs.declare(ws, m, tex_on(c));
+        if (texel)
+            ws.add(&tl.x, 3 * m).add(&tl.w, 3 * m).add(&tl.tmax, m).add(&tl.contrib, 3 * m).add(&tl.ray_pb, m).add(&d_tocc, m).add(
+                &d_tstats, (size_t)2 * PRT_BKL_STAT_SLOTS);
         if ((rc = commit(c, ws, c->scratch))) return rc;
+        PrtBakeLightArgs la{};
+        if (texel) {
+            if ((rc = sync_light_tables(c))) return rc;
+            la = PrtBakeLightArgs{dev_lights(c), dev_mesh_lights(c), dev_light_clusters(c), env_on(c) ? dev_env(c) : DevEnv{}, c->sampling.clamp};
+            HIPCHECK(c, hipMemsetAsync(d_tstats, 0, 2 * PRT_BKL_STAT_SLOTS * sizeof(unsigned long long), c->stream));
+        }
         const PrtRadianceQuery q1{q->max_depth, 1u, q->seed, q->first_sample};  // (one sample per ray: the states are given)
         for (uint32_t s0 = 0; s0 < q->samples; s0 += cs) {
             const uint32_t ccs = std::min(cs, q->samples - s0);
             const uint32_t mm = ccs * n_cov;
             prt_launch_bk_rays(c->stream, n_cov, ccs, q->first_sample + s0, q->seed, x.list, x.map, d_o, d_d, d_rng);
             HIPCHECK(c, hipGetLastError());
+            if (texel) {
+                prt_launch_bkl_sample(c->stream, mesh_lights_on(c), env_on(c), clusters_on(c), n_cov, ccs, q->first_sample + s0, q->seed, x.list,
+                                      x.map, d_d, la, tl);
+                HIPCHECK(c, hipGetLastError());
+            }
             if (lit) {
                 PrtRadianceLitInfo li{0u, 0u};
-                if ((rc = enqueue_radiance_lit(c, q1, mm, 1u, d_o, d_d, d_rng, d_rgb, d_seg, xl, info ? &li : nullptr))) return rc;
+                if ((rc = enqueue_radiance_lit(c, q1, mm, 1u, d_o, d_d, d_rng, texel ? tl.ray_pb : nullptr, d_rgb, d_seg, xl, info ? &li : nullptr)))
+                    return rc;
                 shadow[0] += li.shadow_rays;
                 shadow[1] += li.shadow_occluded;
             } else if ((rc = enqueue_radiance(c, q1, mm, 1u, d_o, d_d, d_rng, d_rgb, d_seg, xs))) {
                 return rc;
             }
+            if (texel) {  // the texels' shadow rays: prt_occluded's pipeline, then e onto the query's values
+                if ((rc = enqueue_query(c, mm, tl.x, tl.w, tl.tmax, nullptr, d_tocc))) return rc;
+                prt_launch_bkl_add(c->stream, mm, tl, d_tocc, d_rgb, d_tstats);
+                HIPCHECK(c, hipGetLastError());
+            }
             prt_launch_bk_sum(c->stream, n_cov, ccs, s0 == 0u, x.list, d_rgb, d_seg, x.rgb[0], x.counts);
             HIPCHECK(c, hipGetLastError());
+        }
+        if (texel && info) {  // (once per call, and only where info is given)
+            unsigned long long st[2 * PRT_BKL_STAT_SLOTS];
+            HIPCHECK(c, hipMemcpyAsync(st, d_tstats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+            HIPCHECK(c, hipStreamSynchronize(c->stream));
+            for (uint32_t k = 0; k < PRT_BKL_STAT_SLOTS; ++k) {
+                shadow[0] += st[2 * k];
+                shadow[1] += st[2 * k + 1];
+            }
         }
     }
     int cur = 0;
@@ -3907,12 +3963,60 @@ static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const Prt
 
 int prt_bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting, uint32_t dilate, float* rgb_sum,
                         uint8_t* coverage, PrtBakeInfo* info) {
-    return bake_irradiance(c, target, q, lighting, dilate, rgb_sum, coverage, false, info);
+    const PrtBakeOptions opt{lighting != 0 ? 1u : 0u, 0u, dilate, 0u};
+    return bake_irradiance(c, target, q, &opt, rgb_sum, coverage, false, info);
 }
 
 int prt_bake_irradiance_device(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, int lighting, uint32_t dilate, void* d_rgb_sum,
                                void* d_coverage, PrtBakeInfo* info) {
-    return bake_irradiance(c, target, q, lighting, dilate, d_rgb_sum, d_coverage, true, info);
+    const PrtBakeOptions opt{lighting != 0 ? 1u : 0u, 0u, dilate, 0u};
+    return bake_irradiance(c, target, q, &opt, d_rgb_sum, d_coverage, true, info);
+}
+
+int prt_bake_irradiance_opt(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* options, float* rgb_sum,
+                            uint8_t* coverage, PrtBakeInfo* info) {
+    return bake_irradiance(c, target, q, options, rgb_sum, coverage, false, info);
+}
+
+int prt_bake_irradiance_opt_device(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* options,
+                                   void* d_rgb_sum, void* d_coverage, PrtBakeInfo* info) {
+    return bake_irradiance(c, target, q, options, d_rgb_sum, d_coverage, true, info);
+}
+
+int prt_bake_light_samples(PrtContext* c, const PrtBakeTarget* target, uint32_t seed, uint32_t sample, float* dirs, float* tmax, uint32_t* light,
+                           float* contrib, float* ray_pb) {
+    BakeTarget b;
+    int rc = check_bake(c, target, nullptr, false, &b);
+    if (rc) return rc;
+    if ((rc = need_device(c))) return rc;
+    BakeBufs x;
+    uint32_t counts[PRT_BAKE_COUNTERS] = {};
+    if ((rc = enqueue_bake_surface(c, &b, false, &x, counts))) return rc;
+    const size_t n = (size_t)b.W * b.H;
+    float *d_o, *d_d;
+    uint32_t* d_rng;
+    PrtBakeLightRays tl{};
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * n).add(&d_d, 3 * n).add(&d_rng, n);
+    ws.add(&tl.w, 3 * n).add(&tl.tmax, n).add(&tl.contrib, 3 * n).add(&tl.light, n).add(&tl.ray_pb, n);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = sync_light_tables(c))) return rc;
+    const PrtBakeLightArgs la{dev_lights(c), dev_mesh_lights(c), dev_light_clusters(c), env_on(c) ? dev_env(c) : DevEnv{}, c->sampling.clamp};
+    prt_launch_bk_rays(c->stream, (uint32_t)n, 1u, sample, seed, nullptr, x.map, d_o, d_d, d_rng);
+    HIPCHECK(c, hipGetLastError());
+    prt_launch_bkl_sample(c->stream, mesh_lights_on(c), env_on(c), clusters_on(c), (uint32_t)n, 1u, sample, seed, nullptr, x.map, d_d, la, tl);
+    HIPCHECK(c, hipGetLastError());
+    std::vector<uint32_t> cand(light ? n : 0);
+    if (dirs && (rc = download(c, dirs, tl.w, 3 * n))) return rc;
+    if (tmax && (rc = download(c, tmax, tl.tmax, n))) return rc;
+    if (light && (rc = download(c, cand.data(), tl.light, n))) return rc;
+    if (contrib && (rc = download(c, contrib, tl.contrib, 3 * n))) return rc;
+    if (ray_pb && (rc = download(c, ray_pb, tl.ray_pb, n))) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    // (the kernel reports the candidate; the light set proper leaves out the candidates with an empty interval)
+    for (size_t i = 0; light && i < n; ++i)
+        light[i] = (mesh_lights_on(c) && cand[i] != 0xFFFFFFFFu && cand[i] != PRT_LIGHT_ENVIRONMENT) ? c->hs.ml.cand_visible[cand[i]] : cand[i];
+    return PRT_OK;
 }
 
 int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,

@@ -33,9 +33,9 @@ struct PrtRadianceLitArgs {
     uint32_t* scount;    // the shadow list's length: zero before the launch
 };
 
-// prt_launch_rd_start's paths with pb = -1.
+// prt_launch_rd_start's paths with pb = -1 (pb == null), or pb[i] for every sample of ray i.
 void prt_launch_rdl_start(hipStream_t st, uint32_t n, uint32_t cs, uint32_t sample0, uint32_t seed, const float* origins,
-                          const float* dirs, const uint32_t* rng_state, PrtRadianceLitList out);
+                          const float* dirs, const uint32_t* rng_state, const float* pb, PrtRadianceLitList out);
 // prt_launch_rd_step's round with light sampling: the emission of a light-set emitter met after a Lambertian vertex (and
 // the environment's texel after one) weighted, and one light sample per Lambertian vertex that scatters before the last
 // segment, appended to a.sh.  mesh / env / clus choose the instance as prt_sample_light's do (clus implies mesh).

@@ -20,9 +20,11 @@ __device__ inline f3 rdl_first_lookup_dir(f3 d) {
     return __builtin_fabsf(l2 - 1.0f) > 9.5367431640625e-07f ? normalize3(d) : d;  // 2^-20
 }
 
-// k_rd_start, and pb = -1: the caller's ray was scattered by no vertex.
+// k_rd_start, and pb = -1: the caller's ray was scattered by no vertex; or pb[i], the pdf of the caller's own Lambertian
+// scatter along ray i (prt_radiance_lit_pb), for every sample of the ray.
 __global__ __launch_bounds__(256) void k_rdl_start(uint32_t n, uint32_t cs, uint32_t sample0, uint32_t seed, const float* __restrict__ origins,
-                                                   const float* __restrict__ dirs, const uint32_t* __restrict__ rng_state, PrtRadianceLitList out) {
+                                                   const float* __restrict__ dirs, const uint32_t* __restrict__ rng_state,
+                                                   const float* __restrict__ pb, PrtRadianceLitList out) {
     const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (j >= (uint64_t)cs * n) return;
     const uint32_t s_local = (uint32_t)(j / n);
@@ -37,7 +39,7 @@ __global__ __launch_bounds__(256) void k_rdl_start(uint32_t n, uint32_t cs, uint
     out.l.d[w + 2] = dirs[r + 2];
     out.l.s0[j] = make_float4(__uint_as_float((uint32_t)j), __uint_as_float(rng), 1.0f, 1.0f);
     out.l.s1[j] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
-    out.pb[j] = -1.0f;
+    out.pb[j] = pb ? pb[i] : -1.0f;
 }
 
 // One segment of every live path: k_rd_step's, in its order, plus the weights and the light sample of advance_path_nee.
@@ -227,8 +229,8 @@ __global__ __launch_bounds__(256) void k_rdl_sum(uint32_t n, uint32_t cs, uint32
 }  // namespace
 
 void prt_launch_rdl_start(hipStream_t st, uint32_t n, uint32_t cs, uint32_t sample0, uint32_t seed, const float* origins,
-                          const float* dirs, const uint32_t* rng_state, PrtRadianceLitList out) {
-    hipLaunchKernelGGL(k_rdl_start, dim3(blocks_for((uint64_t)cs * n)), dim3(256), 0, st, n, cs, sample0, seed, origins, dirs, rng_state, out);
+                          const float* dirs, const uint32_t* rng_state, const float* pb, PrtRadianceLitList out) {
+    hipLaunchKernelGGL(k_rdl_start, dim3(blocks_for((uint64_t)cs * n)), dim3(256), 0, st, n, cs, sample0, seed, origins, dirs, rng_state, pb, out);
 }
 
 void prt_launch_rdl_step(hipStream_t st, bool mesh, bool env, bool clus, uint32_t n, PrtRadianceLitList in, const PrtRadianceLitArgs& a,

@@ -10,7 +10,7 @@
 #include <cstring>
 
 struct PrtWorkspace {
-    static constexpr int kMaxRegions = 32;
+    static constexpr int kMaxRegions = 48;  // (the lit bake with textures and the texel's light sample declares 33)
 
     // Declares `count` elements of T behind *p, after everything declared before.  *p is null until bind succeeds.
     template <class T>

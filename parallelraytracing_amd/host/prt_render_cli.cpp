@@ -13,10 +13,11 @@
 //              [--features-out PREFIX]
 //              [--frames N --orbit-deg D [--temporal [--temporal-max-history H]]]
 //              [--probe X,Y,Z --probe-size WxH --probe-lighting]
-//              [--bake WxH --bake-dilate N]
+//              [--bake WxH --bake-dilate N --bake-texel-light]
 // --bake WxH (with --ply) renders no frame: it writes PREFIX.pfm, the irradiance map of the mesh over the PLY's own UVs
 // (prt_bake_irradiance): --spp paths of up to --depth segments per covered texel, pi * sum / spp, top row first;
 // --bake-dilate N fills the gutters with N passes.  The first GPU; --lighting applies as it would to a frame.
+// --bake-texel-light (with --lighting nee|mis) also samples the lights at the texel itself (prt_bake_irradiance_opt).
 // --probe X,Y,Z renders no frame: it writes PREFIX.pfm, a lat-long radiance probe of --probe-size WxH texels (default 64x32)
 // at that point, --spp paths of up to --depth segments per texel along the texel centre's direction (prt_radiance), in the
 // layout --env reads (top row = the +Y pole): a probe of one scene can light another.  The first GPU; the estimator is the
@@ -96,6 +97,7 @@ int main(int argc, char** argv) {
     uint32_t probe_w = 64, probe_h = 32;
     bool bake = false;
     uint32_t bake_w = 0, bake_h = 0, bake_dilate = 0;
+    bool bake_texel_light = false;
     std::vector<int> devices{0};
     float cam[3] = {5.0f, 5.0f, 8.0f};
     bool cam_set = false;
@@ -177,6 +179,7 @@ int main(int argc, char** argv) {
             bake = true;
         }
         else if (a == "--bake-dilate") bake_dilate = (uint32_t)atoi(next());
+        else if (a == "--bake-texel-light") bake_texel_light = true;
         else if (a == "--probe-size") {
             if (sscanf(next(), "%ux%u", &probe_w, &probe_h) != 2 || !probe_w || !probe_h) { fprintf(stderr, "--probe-size takes WxH\n"); return 2; }
         }
@@ -213,6 +216,10 @@ int main(int argc, char** argv) {
     }
     if (bake && (ply.empty() || probe || orbit || adaptive || denoise || temporal || !features_out.empty())) {
         fprintf(stderr, "--bake goes with --ply and renders no frame: it does not go with --probe, --orbit-deg, --adaptive, --denoise, --temporal or --features-out\n");
+        return 2;
+    }
+    if (bake_texel_light && (!bake || lighting == PRT_LIGHTING_OFF)) {
+        fprintf(stderr, "--bake-texel-light goes with --bake and --lighting nee or mis\n");
         return 2;
     }
     if (probe_lighting && !probe) {
@@ -274,7 +281,8 @@ int main(int argc, char** argv) {
             if (!scene->MeshHasUVs(0)) { fprintf(stderr, "error: --bake: %s has no per-vertex UVs\n", ply.c_str()); return 1; }
             std::vector<float> irr;
             PrtBakeInfo bi{};
-            r.BakeIrradiance(0u, scene->mesh_uvs.at(0), bake_w, bake_h, spp, irr, bake_dilate, lighting != PRT_LIGHTING_OFF, nullptr, &bi);
+            r.BakeIrradiance(0u, scene->mesh_uvs.at(0), bake_w, bake_h, spp, irr, bake_dilate, lighting != PRT_LIGHTING_OFF, nullptr, &bi, PRT_BAKE_MESH, 0u,
+                             bake_texel_light);
             if (prt_write_pfm((out + ".pfm").c_str(), irr.data(), bake_w, bake_h)) { fprintf(stderr, "cannot write %s.pfm\n", out.c_str()); return 1; }
             printf("bake: %ux%u texels, %llu covered, %llu filled, %u spp, max_depth %u, %llu segments, %.3f ms on the device -> %s.pfm\n", bake_w, bake_h,
                    (unsigned long long)bi.n_covered, (unsigned long long)bi.n_filled, spp, depth, (unsigned long long)bi.segments, bi.device_ms, out.c_str());

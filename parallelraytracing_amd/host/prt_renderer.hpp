@@ -457,12 +457,16 @@ public:
     // rng_state (n, in / out) gives the paths their states instead and needs samples == 1; segments (n) may be null.
     // lighting: the light-sampled query (prt_radiance_lit): the estimator a render would use now (SetLighting,
     // SetLightSources, SetLightSelection, the environment's light share); lit_info (may be null): its shadow-ray counts.
+    // pb (n floats, may be null; needs lighting): the pdf of the caller's own Lambertian scatter along each ray, so that what
+    // the first segment meets is weighted as after a vertex of the path's own (prt_radiance_lit_pb).
     void Radiance(uint32_t n, const float* origins, const float* dirs, float* rgb_sum, uint32_t samples = 1, uint32_t first_sample = 0,
-                  uint32_t* rng_state = nullptr, uint32_t* segments = nullptr, bool lighting = false, PrtRadianceLitInfo* lit_info = nullptr) {
+                  uint32_t* rng_state = nullptr, uint32_t* segments = nullptr, bool lighting = false, PrtRadianceLitInfo* lit_info = nullptr,
+                  const float* pb = nullptr) {
         PrtContext* c = prt_group_context(grp_, 0);
         const PrtRadianceQuery q{max_depth_, samples, seed_, first_sample};
+        if (pb && !lighting) throw Error("Radiance: pb weights light-sampled paths only: pass lighting = true");
         if (lighting) {
-            if (prt_radiance_lit(c, &q, n, origins, dirs, rng_state, rgb_sum, segments, lit_info))
+            if (prt_radiance_lit_pb(c, &q, n, origins, dirs, rng_state, pb, rgb_sum, segments, lit_info))
                 throw Error(std::string("prt_radiance_lit: ") + prt_last_error(c));
             return;
         }
@@ -496,17 +500,20 @@ public:
     // world-space mesh `index` (kind = PRT_BAKE_INSTANCE: placed copy `index`) over its UV layout, width x height x 3 floats,
     // pi * sum / samples, row 0 on top.  uvs: n_vertices x 2 floats for this call, null: the texture binding's.  dilate:
     // passes of the gutter fill.  coverage (may be null): width x height bytes, 0 none, 1 owned, 2 filled.  lighting:
-    // Radiance's.  info (may be null): the counts of the call.
+    // Radiance's.  info (may be null): the counts of the call.  texel_light (needs lighting): a light sample at the texel
+    // itself and the texel's own ray MIS-weighted (prt_bake_irradiance_opt).
     void BakeIrradiance(uint32_t index, const float* uvs, uint32_t width, uint32_t height, uint32_t samples, std::vector<float>& irradiance,
                         uint32_t dilate = 0, bool lighting = false, std::vector<uint8_t>* coverage = nullptr, PrtBakeInfo* info = nullptr,
-                        uint32_t kind = PRT_BAKE_MESH, uint32_t first_sample = 0) {
+                        uint32_t kind = PRT_BAKE_MESH, uint32_t first_sample = 0, bool texel_light = false) {
         PrtContext* c = prt_group_context(grp_, 0);
         const PrtBakeTarget t{kind, index, uvs, width, height};
         const PrtRadianceQuery q{max_depth_, samples, seed_, first_sample};
         const size_t n = (size_t)width * height;
         irradiance.assign(3 * n, 0.0f);
         if (coverage) coverage->assign(n, 0);
-        if (prt_bake_irradiance(c, &t, &q, lighting ? 1 : 0, dilate, irradiance.data(), coverage ? coverage->data() : nullptr, info))
+        if (texel_light && !lighting) throw Error("BakeIrradiance: texel_light belongs to a light-sampled bake: pass lighting = true");
+        const PrtBakeOptions opt{lighting ? 1u : 0u, texel_light ? 1u : 0u, dilate, 0u};
+        if (prt_bake_irradiance_opt(c, &t, &q, &opt, irradiance.data(), coverage ? coverage->data() : nullptr, info))
             throw Error(std::string("prt_bake_irradiance: ") + prt_last_error(c));
         for (float& v : irradiance) v = v * 3.14159274f / (float)samples;
     }

@@ -1152,7 +1152,7 @@ class HipWavefrontRenderer:
         return sc.astype(bool), att, em, oo, od, rng
 
     def radiance(self, o, d, rng_state=None, samples: int = 1, seed=None, first_sample: int = 0, max_depth=None,
-                 return_info: bool = False, lighting: bool = False):
+                 return_info: bool = False, lighting: bool = False, pb=None):
         """The radiance arriving along n caller-supplied rays (prt_radiance, include/prt.h "Radiance query"): whole paths
         of up to max_depth segments (default: the renderer's) on the device, `samples` per ray.  o, d: [n, 3] float32,
         numpy arrays (the host form) or torch tensors on the renderer's device (the device form, ordered after torch's
@@ -1162,7 +1162,12 @@ class HipWavefrontRenderer:
         library returns, "segments": [n] segments walked, "rng_state": the final states, or None}.
         lighting=True: the light-sampled query (prt_radiance_lit): the estimator a render would use now (set_lighting,
         set_light_sources, set_light_selection, the environment's light share); the same paths, less noise under small
-        emitters.  With return_info the info then also has "shadow_rays" and "shadow_occluded" of this call."""
+        emitters.  With return_info the info then also has "shadow_rays" and "shadow_occluded" of this call.
+        pb [n] float32 (numpy or torch, as o / d; needs lighting=True): the rays were scattered by a Lambertian vertex of the
+        caller's with pdf pb[i] = max(0, n.d) / pi, so what the first segment meets is weighted as after a vertex of the
+        path's own (prt_radiance_lit_pb): the continuation of a first vertex shaded outside the library."""
+        if pb is not None and not lighting:
+            raise ValueError("pb: the scatter pdf of the caller's segment weights light-sampled paths only: pass lighting=True")
         lit = capi.PrtRadianceLitInfo() if (lighting and return_info) else None
         q = capi.PrtRadianceQuery(int(self.max_depth if max_depth is None else max_depth), int(samples),
                                   int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample) & 0xFFFFFFFF)
@@ -1186,7 +1191,13 @@ class HipWavefrontRenderer:
             # (n == 0 still goes through the library: it refuses a bad query whatever the count)
             args = (self._ctx, C.byref(q), n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
                     C.c_void_p(rng.data_ptr() if rng is not None else None), C.c_void_p(total.data_ptr()), C.c_void_p(seg.data_ptr()))
-            if lighting:
+            if pb is not None:
+                if not isinstance(pb, torch.Tensor):
+                    raise ValueError("pb: expected a torch tensor with the rays")
+                self._check_tensor("pb", pb, (n,))
+                self._on_context_stream(lambda: capi.lib().prt_radiance_lit_pb_device(
+                    *args[:6], C.c_void_p(pb.data_ptr()), *args[6:], C.byref(lit) if lit is not None else None))
+            elif lighting:
                 self._on_context_stream(lambda: capi.lib().prt_radiance_lit_device(*args, C.byref(lit) if lit is not None else None))
             else:
                 self._on_context_stream(lambda: capi.lib().prt_radiance_device(*args))
@@ -1206,7 +1217,13 @@ class HipWavefrontRenderer:
             seg = np.zeros(n, np.uint32)
             args = (self._ctx, C.byref(q), n, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp),
                     rng.ctypes.data_as(_u32p) if rng is not None else None, total.ctypes.data_as(_fp), seg.ctypes.data_as(_u32p))
-            if lighting:
+            if pb is not None:
+                pbv = np.ascontiguousarray(_f32(pb).ravel())
+                if pbv.size != n:
+                    raise ValueError(f"pb: {pbv.size} values for {n} rays")
+                self._check(capi.lib().prt_radiance_lit_pb(*args[:6], pbv.ctypes.data_as(_fp), *args[6:],
+                                                           C.byref(lit) if lit is not None else None))
+            elif lighting:
                 self._check(capi.lib().prt_radiance_lit(*args, C.byref(lit) if lit is not None else None))
             else:
                 self._check(capi.lib().prt_radiance(*args))
@@ -1274,16 +1291,36 @@ class HipWavefrontRenderer:
                                              int(sample) & 0xFFFFFFFF, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp), rng.ctypes.data_as(_u32p)))
         return {"o": o, "d": d, "rng_state": rng}
 
+    def bake_light_samples(self, mesh=None, instance=None, size=(64, 64), uvs=None, sample: int = 0, seed=None) -> dict:
+        """The light sample of sample `sample` of every texel (prt_bake_light_samples): {"dir" [H, W, 3], "tmax" [H, W] (0: no
+        shadow ray is cast), "light" [H, W] uint32 (capi.BAKE_NONE: no sample, capi.LIGHT_ENVIRONMENT), "contrib" [H, W, 3]
+        (clamped, before visibility), "ray_pb" [H, W]: the pdf of bake_rays' direction}, zero / none where uncovered."""
+        t, keep, H, W = self._bake_target(mesh, instance, size, uvs)
+        w, contrib = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
+        tmax, pb = np.zeros((H, W), np.float32), np.zeros((H, W), np.float32)
+        light = np.full((H, W), capi.BAKE_NONE, np.uint32)
+        self._check(capi.lib().prt_bake_light_samples(self._ctx, C.byref(t), int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                                      int(sample) & 0xFFFFFFFF, w.ctypes.data_as(_fp), tmax.ctypes.data_as(_fp),
+                                                      light.ctypes.data_as(_u32p), contrib.ctypes.data_as(_fp), pb.ctypes.data_as(_fp)))
+        return {"dir": w, "tmax": tmax, "light": light, "contrib": contrib, "ray_pb": pb}
+
     def bake_irradiance(self, mesh=None, instance=None, size=(64, 64), uvs=None, samples: int = 16, seed=None, first_sample: int = 0,
-                        max_depth=None, lighting: bool = False, dilate: int = 0, out: str = "numpy", return_info: bool = False):
+                        max_depth=None, lighting: bool = False, dilate: int = 0, out: str = "numpy", return_info: bool = False,
+                        texel_light: bool = False):
         """An irradiance map [H, W, 3] over the UV layout of a mesh (prt_bake_irradiance): every covered texel is a
         Lambertian vertex of albedo 1 whose `samples` paths the radiance query follows; the value is
         sum * float32(pi) / float32(samples), so a Lambertian surface of albedo rho shows rho / pi times it.  lighting:
         radiance()'s.  dilate: passes of the gutter fill.  out = "torch": a tensor on the renderer's device through the
         device form.  return_info: also {"sum": the raw fp32 sums, "coverage": [H, W] uint8 (0 none, 1 owned, 2 filled),
-        "info": the counts of the call}."""
+        "info": the counts of the call}.  texel_light (needs lighting=True): a light sample at the texel itself, and the
+        texel's own ray MIS-weighted (prt_bake_irradiance_opt): direct light with the noise of a lit render's first vertex."""
         if out not in ("numpy", "torch"):
             raise ValueError(f"out: {out!r}, expected 'numpy' or 'torch'")
+        if texel_light and not lighting:
+            raise ValueError("texel_light: the texel's light sample belongs to a light-sampled bake: pass lighting=True")
+        if int(dilate) < 0 or int(dilate) > 0xFFFFFFFF:
+            raise ValueError(f"dilate: {dilate}")
+        opt = capi.PrtBakeOptions(int(bool(lighting)), int(bool(texel_light)), int(dilate), 0)
         t, keep, H, W = self._bake_target(mesh, instance, size, uvs)
         q = capi.PrtRadianceQuery(int(self.max_depth if max_depth is None else max_depth), int(samples),
                                   int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample) & 0xFFFFFFFF)
@@ -1293,8 +1330,8 @@ class HipWavefrontRenderer:
             dev = self._torch_device()
             total = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
             cov = torch.zeros((H, W), dtype=torch.uint8, device=dev)
-            self._on_context_stream(lambda: capi.lib().prt_bake_irradiance_device(
-                self._ctx, C.byref(t), C.byref(q), int(bool(lighting)), int(dilate), C.c_void_p(total.data_ptr()), C.c_void_p(cov.data_ptr()),
+            self._on_context_stream(lambda: capi.lib().prt_bake_irradiance_opt_device(
+                self._ctx, C.byref(t), C.byref(q), C.byref(opt), C.c_void_p(total.data_ptr()), C.c_void_p(cov.data_ptr()),
                 C.byref(info) if return_info else None))
             # (tensor operands: torch turns a division by a Python number into a multiplication by its reciprocal)
             irr = total * torch.full((1, 1, 1), float(np.float32(np.pi)), dtype=torch.float32, device=dev) \
@@ -1302,9 +1339,9 @@ class HipWavefrontRenderer:
         else:
             total = np.zeros((H, W, 3), np.float32)
             cov = np.zeros((H, W), np.uint8)
-            self._check(capi.lib().prt_bake_irradiance(self._ctx, C.byref(t), C.byref(q), int(bool(lighting)), int(dilate),
-                                                       total.ctypes.data_as(_fp), cov.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                       C.byref(info) if return_info else None))
+            self._check(capi.lib().prt_bake_irradiance_opt(self._ctx, C.byref(t), C.byref(q), C.byref(opt),
+                                                           total.ctypes.data_as(_fp), cov.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                           C.byref(info) if return_info else None))
             irr = total * np.float32(np.pi) / np.float32(q.samples)
         if return_info:
             return irr, {"sum": total, "coverage": cov, "info": self._bake_info(info)}
