@@ -478,6 +478,11 @@ int prt_create(int device_id, PrtContext** out);
 void prt_destroy(PrtContext* ctx);
 const char* prt_last_error(const PrtContext* ctx);
 int prt_version(void);
+/* The process-wide books of what the contexts of this library own on the devices (either may be NULL): bytes of device memory
+ * currently allocated, and allocation calls made so far.  live_bytes returns to its earlier value when a context is destroyed;
+ * alloc_calls stands still across calls in the steady state (a second identical prt_render, a second query of the same size).
+ * prt_group_*'s own exchange buffers and the device-side builder's temporaries are not counted. */
+void prt_device_memory_info(uint64_t* live_bytes, uint64_t* alloc_calls);
 /* Launch on this hipStream_t (e.g. torch's current stream); NULL = the context's own stream. */
 int prt_set_stream(PrtContext* ctx, void* hip_stream);
 /* The hipStream_t the context launches on / its device id (-1: host-only context). */

@@ -273,6 +273,7 @@ SIGNATURES = {
     "prt_destroy": (None, [_vp]),
     "prt_last_error": (C.c_char_p, [_vp]),
     "prt_version": (C.c_int, []),
+    "prt_device_memory_info": (None, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "prt_set_stream": (C.c_int, [_vp, _vp]),
     "prt_get_stream": (C.c_int, [_vp, C.POINTER(_vp)]),
     "prt_get_device": (C.c_int, [_vp]),

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -26,6 +27,7 @@
 #include "prt_adaptive.h"
 #include "prt_denoise.h"
 #include "prt_denoise_contract.h"
+#include "prt_devmem.h"
 #include "prt_feature_samples.h"
 #include "prt_features.h"
 #include "prt_kernels.h"
@@ -39,6 +41,29 @@
 #include "prt_temporal_contract.h"
 #include "prt_workspace.h"
 
+// ---- the seam of prt_devmem.h over HIP, and the process-wide books prt_device_memory_info reads.  These definitions are the
+// only place in this file that allocates or frees device memory, pinned memory or events. ----
+static std::atomic<uint64_t> g_live_bytes{0}, g_alloc_calls{0};
+
+int prt_dev_alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) g_live_bytes += bytes, ++g_alloc_calls;
+    return (int)e;
+}
+void prt_dev_free(void* p, size_t bytes) {
+    (void)hipFree(p);
+    g_live_bytes -= bytes;
+}
+int prt_dev_copy_in(void* dst, const void* src, size_t bytes) { return (int)hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+void prt_dev_adopted(size_t bytes) { g_live_bytes += bytes; }
+void prt_dev_taken(size_t bytes) { g_live_bytes -= bytes; }
+int prt_pinned_alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+void prt_pinned_free(void* p) { (void)hipHostFree(p); }
+int prt_event_create(void** ev, bool timing) {
+    return (int)(timing ? hipEventCreate((hipEvent_t*)ev) : hipEventCreateWithFlags((hipEvent_t*)ev, hipEventDisableTiming));
+}
+void prt_event_destroy(void* ev) { (void)hipEventDestroy((hipEvent_t)ev); }
+
 namespace {
 
 constexpr float kPadCoeff = 1.0f / 262144.0f;  // 2^-18, see traverse() in prt_kernels.hip
@@ -47,16 +72,72 @@ constexpr uint32_t kTravStatsWords = 16 + PRT_TIMELINE_WORDS * (PRT_MAX_DEPTH + 
 constexpr size_t kLightStatWords = 2 * (size_t)PRT_RAY_STAT_SLOTS;  // k_light_accum's [slot][shadow rays, occluded]
 
 struct EventPair {
-    hipEvent_t a, b;
-    int kind;  // 0 raygen, 1 intersect (dominant kernel), 2 shade, 3 accumulate, 4 analytic-primitive scan
+    DevEvent a, b;
+    int kind = 0;  // 0 raygen, 1 intersect (dominant kernel), 2 shade, 3 accumulate, 4 analytic-primitive scan
 };
 
-// A device allocation that only grows.  A failed ensure leaves it empty.
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(PrtContext* c, size_t need);
-    void release();
+hipEvent_t ev(const DevEvent& e) { return (hipEvent_t)e.h; }
+
+// ---- what a context owns on the device, grouped by lifetime (prt_devmem.h): a group is reset by assigning a fresh value ----
+struct RayMem {  // the arrays of one PrtRayBuf
+    DevBuf o, d, t, hit, hd2;
+    int alloc(uint64_t n) {
+        int e = o.ensure(n * sizeof(float4));
+        if (!e) e = d.ensure(n * sizeof(float4));
+        if (!e) e = t.ensure(n * sizeof(float4));
+        if (!e) e = hit.ensure(n * sizeof(uint32_t));
+        if (!e) e = hd2.ensure(n * sizeof(float));
+        return e;
+    }
+    PrtRayBuf view() const { return PrtRayBuf{o.as<float4>(), d.as<float4>(), t.as<float4>(), hit.as<uint32_t>(), hd2.as<float>()}; }
+};
+struct BuiltTree {  // the world meshes' tree as the device-side builder left it (PrtGpuBvh's arrays, adopted)
+    DevBuf nodes8, tris, nrms;
+    uint32_t n_nodes = 0;
+};
+struct SceneMem {  // prt_set_scene .. the next one
+    DevBuf prims, mat_rgbs, mat_type, nodes, nodes4, nodes8, insts, tlas_inst, abvh_nodes, abvh_order, tris, nrms, lights, prim_light;
+    DevBuf refit_keep;  // what prt_refit_meshes_device keeps with the scene (RefitKeep's arrays)
+};
+struct MeshLightMem {  // PrtMeshLights and PrtLightClusters (prt_scene.h), on the device only while the MESH bit is set
+    DevBuf records, thr, bucket, runs;
+    DevBuf lc_boxes, lc_range, lc_members, lc_thr, lc_cand, lc_pmf;  // lc_pmf, per candidate: fl32(pmf_in (2^32 - T_e) / 2^32)
+};
+struct EnvMem {
+    DevBuf texels, row, col, last;
+};
+struct TexMem {
+    DevBuf texels, desc, mat, uvs, inst;
+};
+struct PathMem {  // cap_paths paths
+    RayMem rays[2];
+    DevBuf rad;
+};
+struct LightMem {  // cap_light paths: shadow rays, pdf of the previous scatter, light radiance
+    RayMem sh;
+    DevBuf pdf_b, lrad;
+};
+struct PrimaryMem {  // the persistent primary stage (prt_primary_cache.h)
+    DevBuf pid, list, hit;
+};
+struct FilmMem {
+    DevBuf local;     // float4 per local pixel
+    DevBuf stat;      // float2 {A, Q} per local pixel, only while film statistics are on
+    DevBuf tile_sel;  // [0] the active count, then flags / list A / list B of tile_sel_entries tiles each
+    PinnedBuf tile_count;  // the active count of a pass
+};
+struct WorkMem {  // counters and work arrays, allocated once (ensure_counters) or grown on demand
+    DevBuf counts;       // (PRT_MAX_DEPTH + 2) x PRT_CNT_STRIDE: front/back ray counts per bounce
+    DevBuf ray_stats;    // [2][PRT_RAY_STAT_SLOTS][PRT_MAX_DEPTH]: the context's counters, then a scratch set for measurement runs
+    DevBuf trav_stats;
+    DevBuf work;         // chunk cursors of the persistent traversal kernel, flags, overflow list
+    DevBuf pix;          // compact primary rays: one record per local pixel (PrtPrimary)
+    DevBuf sort;         // keys, keys2, idx, idx2 (n_paths each) + rocPRIM's temporary storage
+    DevBuf light_stats;  // [slot][shadow rays, occluded], since prt_reset_stats
+    PinnedBuf flag;      // the traversal kernels' error flags (work[256]) as of the last prt_synchronize
+    PinnedBuf counts_host;  // the front / back ray counts of each bounce as the host learns them
+    DevEvent ev_counts[PRT_MAX_DEPTH + 2];
+    DevEvent ev_prod[PRT_MAX_DEPTH + 2];  // "the producer of bounce d's counts is done" (render stream -> count stream)
 };
 
 }  // namespace
@@ -82,24 +163,12 @@ struct PrtContext {
         float *d_normals = nullptr, *d_light_verts = nullptr;  // computed normals of every world-space vertex; the packed emissive triangles
         PrtRefitScratch scratch{};
     } rk;
-    DevBuf rk_buf;
     bool host_copies_stale = false;
     PrtRefitInfo rinfo{};              // of the last refit, either form (refits: from hs.bvh_info)
     PrtCopyTally* tally = nullptr;     // while a refit runs: the copies of the helpers it calls are counted here
     PrtInstanceUpdateInfo inst_info{}; // prt_set_instance_transforms calls since the scene was set (top_nodes / top_depth: from hs)
-    DevScene dsc{};
-    void* d_prims = nullptr;
-    void* d_mat_rgbs = nullptr;
-    void* d_mat_type = nullptr;
-    void* d_nodes = nullptr;
-    void* d_nodes4 = nullptr;
-    void* d_nodes8 = nullptr;
-    void* d_insts = nullptr;
-    void* d_tlas_inst = nullptr;
-    void* d_abvh_nodes = nullptr;
-    void* d_abvh_order = nullptr;
-    void* d_tris = nullptr;
-    void* d_nrms = nullptr;
+    DevScene dsc{};  // the kernels' view of `scene` (fill_dev_scene)
+    SceneMem scene;
 
     // ---- camera ----
     bool has_camera = false;
@@ -109,26 +178,20 @@ struct PrtContext {
     bool has_film = false;
     PrtTileMap tm{};
     uint32_t valid_local = 0;  // pixels of this rank inside the image
-    float4* d_film_local = nullptr;
     // film statistics (prt_set_film_statistics, include/prt.h "Film statistics and adaptive sampling"): {A, Q} per local pixel
-    // beside d_film_local, allocated only while they are on; the tile flags and the two tile lists of prt_render_adaptive
+    // beside film.local, allocated only while they are on; the tile flags and the two tile lists of prt_render_adaptive
+    FilmMem film;
     bool film_stats = false;
-    float2* d_film_stat = nullptr;
-    uint32_t* d_tile_sel = nullptr;  // [0] the active count, then flags / list A / list B of tile_sel_entries tiles each
     uint32_t tile_sel_entries = 0;
-    uint32_t* h_tile_count = nullptr;  // pinned: the active count of a pass
 
     // ---- path state ----
     uint32_t S = 1;
     uint64_t cap_paths = 0;
-    PrtRayBuf rb[2] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};
-    float4* d_rad = nullptr;
-    uint32_t* d_counts = nullptr;             // (PRT_MAX_DEPTH + 2) x PRT_CNT_STRIDE: front/back ray counts per bounce
-    unsigned long long* d_ray_stats = nullptr;  // [2][PRT_RAY_STAT_SLOTS][PRT_MAX_DEPTH]: the context's counters, then a scratch set for measurement runs
-    unsigned long long* ray_stats_target = nullptr;  // the set k_accumulate adds to (d_ray_stats, or its scratch half during a measurement)
-    bool pix_records_blank = false;  // d_pix's primary-hit records all say "no record" (batches of one sample)
-    uint32_t* h_flag = nullptr;  // pinned: the traversal kernels' error flags (d_work[256]) as of the last prt_synchronize
-    unsigned long long* d_trav_stats = nullptr; // 3
+    PathMem path;
+    PrtRayBuf rb[2] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};  // views of path.rays
+    WorkMem wk;
+    unsigned long long* ray_stats_target = nullptr;  // the set k_accumulate adds to (wk.ray_stats, or its scratch half during a measurement)
+    bool pix_records_blank = false;  // wk.pix's primary-hit records all say "no record" (batches of one sample)
 
     // ---- scratch for the function-level entry points ----
     DevBuf scratch;
@@ -160,22 +223,14 @@ struct PrtContext {
     uint32_t last_segment_active = 0;  // what the last run_batch's plan made of it (prt_last_segment)
     uint32_t last_batch_depth = 0;     // max_depth of the last run_batch that ran the pipeline (0: none, or the path route)
     uint32_t sort_rays = 0;       // measurement aid: 1 / 2 = bounces >= 1 (and jittered bounce 0) walk their rays in sorted order
-    uint32_t* d_sort = nullptr;   // keys, keys2, idx, idx2 (n_paths each) + rocPRIM's temporary storage
     size_t sort_entries = 0, sort_temp = 0;
-    uint32_t* h_counts = nullptr;  // pinned: the front / back ray counts of each bounce as the host learns them
-    hipEvent_t ev_counts[PRT_MAX_DEPTH + 2] = {};
-    hipEvent_t ev_prod[PRT_MAX_DEPTH + 2] = {};  // "the producer of bounce d's counts is done" (render stream -> count stream)
     hipStream_t count_stream = nullptr;          // the counts' copies to the host run beside the render stream, not in it
-    uint32_t* d_work = nullptr;   // chunk cursor of the persistent traversal kernel
-    float4* d_pix = nullptr;      // compact primary rays: one record per local pixel (PrtPrimary)
     uint32_t pix_entries = 0;
     // ---- the primary stage of a still camera, kept across batches and calls (prt_primary_cache.h) ----
-    // What k_raygen, the bounce-0 walk and k_primary_hit leave behind on the compact route, besides d_pix and bounce 0's words
-    // of d_counts: the path-id list (4 B per path; in rb[0].t it would be overwritten by bounce 2's rays), the front-pixel list
+    // What k_raygen, the bounce-0 walk and k_primary_hit leave behind on the compact route, besides wk.pix and bounce 0's words
+    // of wk.counts: the path-id list (4 B per path; in rb[0].t it would be overwritten by bounce 2's rays), the front-pixel list
     // and the walk's hits (4 B per local pixel each; in rb[0].hd2 / .hit likewise).  Nothing after the first k_shade writes them.
-    uint32_t* d_prim_pid = nullptr;
-    uint32_t* d_prim_list = nullptr;
-    uint32_t* d_prim_hit = nullptr;
+    PrimaryMem prim;
     uint64_t prim_pid_entries = 0;
     uint32_t prim_pix_entries = 0;
     PrtPrimaryKey primary_key{};        // what the buffers hold (valid = false: nothing)
@@ -188,41 +243,23 @@ struct PrtContext {
 
     // ---- light sampling (PrtLighting, include/prt.h) ----
     uint32_t lighting = PRT_LIGHTING_OFF;
-    void* d_lights = nullptr;
-    void* d_prim_light = nullptr;
     uint32_t light_sources = PRT_LIGHT_SOURCES_ANALYTIC;  // prt_set_light_sources
     uint32_t light_selection = PRT_LIGHT_SELECTION_POWER;  // prt_set_light_selection (PrtLightSelection.mode)
     uint32_t light_max_clusters = 0;   // PrtLightSelection.max_clusters as given (0: the default)
-    void* d_lc_boxes = nullptr;        // PrtLightClusters (prt_scene.h), on the device with the candidate table
-    void* d_lc_range = nullptr;
-    void* d_lc_members = nullptr;
-    void* d_lc_thr = nullptr;
-    void* d_lc_cand = nullptr;
-    void* d_lc_pmf = nullptr;          // per candidate: fl32(pmf_in (2^32 - T_e) / 2^32)
     int light_buckets = 1;             // the bucket table brackets the search over the thresholds (0: plain binary search; A/B)
-    void* d_ml_records = nullptr;      // PrtMeshLights (prt_scene.h), on the device only while the MESH bit is set
-    void* d_ml_thr = nullptr;
-    void* d_ml_bucket = nullptr;
-    void* d_ml_runs = nullptr;
-    PrtLightBufs lb{};                 // shadow rays, pdf of the previous scatter, light radiance: cap_light paths each
+    MeshLightMem ml;
+    LightMem light;
+    PrtLightBufs lb{};                 // the kernels' view of `light` and wk.light_stats
     uint64_t cap_light = 0;
-    unsigned long long* d_light_stats = nullptr;  // [slot][shadow rays, occluded], since prt_reset_stats
 
     // ---- environment light (PrtEnvironment, include/prt.h): a property of the context, kept across scenes ----
     PrtEnvTables env;                  // W = 0: the constant sky
-    void* d_env_texels = nullptr;
-    void* d_env_row = nullptr;
-    void* d_env_col = nullptr;
-    void* d_env_last = nullptr;
+    EnvMem envm;
     uint64_t t_env_dev = 0;            // the T_e the pmfs of the light tables on the device are scaled with
 
     // ---- image textures (PrtTextureSet, include/prt.h): a property of the current scene ----
     PrtTexTables tex;                  // is_set = false: no binding
-    void* d_tex_texels = nullptr;
-    void* d_tex_desc = nullptr;
-    void* d_tex_mat = nullptr;
-    void* d_tex_uvs = nullptr;
-    void* d_tex_inst = nullptr;
+    TexMem texm;
     uint64_t tex_bytes = 0;            // device bytes of the binding
 
     // ---- first-hit features and the film denoiser (include/prt.h): the records of prt_render_features, valid until a call
@@ -274,9 +311,10 @@ int fail(PrtContext* c, int code, const char* fmt, ...) {
     return code;
 }
 
+// (call: a hipError_t, or the same code as the int an owner of prt_devmem.h returns)
 #define HIPCHECK(c, call)                                                                              \
     do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
+        const hipError_t e_ = (hipError_t)(call);                                                      \
         if (e_ != hipSuccess) return fail((c), PRT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
@@ -300,36 +338,14 @@ void drop_history(PrtContext* c) {
     ++c->tp_info.resets;
 }
 
-void free_dev(void*& p) {
-    if (p) {
-        (void)hipFree(p);
-        p = nullptr;
-    }
-}
-template <class T>
-void free_dev(T*& p) {
-    if (p) {
-        (void)hipFree((void*)p);
-        p = nullptr;
-    }
-}
-
-void DevBuf::release() {
-    free_dev(p);
-    bytes = 0;
-}
-
-int DevBuf::ensure(PrtContext* c, size_t need) {
-    if (need <= bytes) return PRT_OK;
-    release();
-    HIPCHECK(c, hipMalloc(&p, need));
-    bytes = need;
+int ensure(PrtContext* c, DevBuf& buf, size_t need) {
+    HIPCHECK(c, buf.ensure(need));
     return PRT_OK;
 }
 
 // Grows buf to the size of a layout (prt_workspace.h) and hands out the pointers the layout declared, inside buf.
 int commit(PrtContext* c, const PrtWorkspace& ws, DevBuf& buf) {
-    const int rc = buf.ensure(c, ws.bytes());
+    const int rc = ensure(c, buf, ws.bytes());
     if (rc || ws.bind(buf.p, buf.bytes)) return rc;
     return fail(c, PRT_ERR_INVALID, "a workspace of %d arrays in %zu bytes does not fit its buffer of %zu", ws.regions(), ws.bytes(), buf.bytes);
 }
@@ -393,30 +409,16 @@ struct TemporalScratch {
     }
 };
 
-void free_path_state(PrtContext* c) {
-    for (int i = 0; i < 2; ++i) {
-        free_dev(c->rb[i].o);
-        free_dev(c->rb[i].d);
-        free_dev(c->rb[i].t);
-        free_dev(c->rb[i].hit);
-        free_dev(c->rb[i].hd2);
-    }
-    free_dev(c->d_rad);
-    c->cap_paths = 0;
-}
-
 int ensure_path_state(PrtContext* c, uint64_t n_paths) {
     if (n_paths <= c->cap_paths) return PRT_OK;
-    free_path_state(c);
+    c->path = PathMem();
+    c->cap_paths = 0;
     const uint64_t n = std::max<uint64_t>(n_paths, 256);
-    for (int i = 0; i < 2; ++i) {
-        HIPCHECK(c, hipMalloc((void**)&c->rb[i].o, n * sizeof(float4)));
-        HIPCHECK(c, hipMalloc((void**)&c->rb[i].d, n * sizeof(float4)));
-        HIPCHECK(c, hipMalloc((void**)&c->rb[i].t, n * sizeof(float4)));
-        HIPCHECK(c, hipMalloc((void**)&c->rb[i].hit, n * sizeof(uint32_t)));
-        HIPCHECK(c, hipMalloc((void**)&c->rb[i].hd2, n * sizeof(float)));
-    }
-    HIPCHECK(c, hipMalloc((void**)&c->d_rad, n * sizeof(float4)));
+    int e = c->path.rays[0].alloc(n);
+    if (!e) e = c->path.rays[1].alloc(n);
+    if (!e) e = c->path.rad.ensure(n * sizeof(float4));
+    for (int i = 0; i < 2; ++i) c->rb[i] = c->path.rays[i].view();
+    HIPCHECK(c, e);
     c->cap_paths = n;
     return PRT_OK;
 }
@@ -425,69 +427,47 @@ int ensure_path_state(PrtContext* c, uint64_t n_paths) {
 void touch_scene(PrtContext* c) { ++c->scene_gen; }
 void touch_camera(PrtContext* c) { ++c->camera_gen; }
 
-void free_primary_state(PrtContext* c) {
-    free_dev(c->d_prim_pid);
-    free_dev(c->d_prim_list);
-    free_dev(c->d_prim_hit);
-    c->prim_pid_entries = 0;
-    c->prim_pix_entries = 0;
-    c->primary_key.valid = false;
-}
-
 // The persistent primary buffers of the compact route (sized with the path state; they only grow, and growing drops what they held)
 int ensure_primary_state(PrtContext* c, uint64_t n_paths, uint32_t n_pix_local) {
     if (n_paths > c->prim_pid_entries) {
         c->primary_key.valid = false;
-        free_dev(c->d_prim_pid);
-        c->prim_pid_entries = 0;
+        c->prim_pid_entries = 0;  // (a growing ensure releases before it allocates, and a failed one leaves nothing)
         const uint64_t n = std::max<uint64_t>(n_paths, 256);
-        HIPCHECK(c, hipMalloc((void**)&c->d_prim_pid, n * sizeof(uint32_t)));
+        HIPCHECK(c, c->prim.pid.ensure(n * sizeof(uint32_t)));
         c->prim_pid_entries = n;
     }
     if (n_pix_local > c->prim_pix_entries) {
         c->primary_key.valid = false;
-        free_dev(c->d_prim_list);
-        free_dev(c->d_prim_hit);
         c->prim_pix_entries = 0;
         const uint32_t n = std::max<uint32_t>(n_pix_local, 256u);
-        HIPCHECK(c, hipMalloc((void**)&c->d_prim_list, (size_t)n * sizeof(uint32_t)));
-        HIPCHECK(c, hipMalloc((void**)&c->d_prim_hit, (size_t)n * sizeof(uint32_t)));
+        HIPCHECK(c, c->prim.list.ensure((size_t)n * sizeof(uint32_t)));
+        HIPCHECK(c, c->prim.hit.ensure((size_t)n * sizeof(uint32_t)));
         c->prim_pix_entries = n;
     }
     return PRT_OK;
 }
 
-void free_light_state(PrtContext* c) {
-    free_dev(c->lb.sh.o);
-    free_dev(c->lb.sh.d);
-    free_dev(c->lb.sh.t);
-    free_dev(c->lb.sh.hit);
-    free_dev(c->lb.sh.hd2);
-    free_dev(c->lb.pdf_b);
-    free_dev(c->lb.lrad);
-    c->cap_light = 0;
-}
-
 // the lighting pipeline's per-path buffers (sized with the path state; the statistics words once)
 int ensure_light_state(PrtContext* c, uint64_t n_paths) {
-    if (!c->d_light_stats) {
-        HIPCHECK(c, hipMalloc((void**)&c->d_light_stats, kLightStatWords * sizeof(unsigned long long)));
+    if (!c->wk.light_stats.p) {
+        HIPCHECK(c, c->wk.light_stats.ensure(kLightStatWords * sizeof(unsigned long long)));
         // on the context's stream: a hipMemset of device memory on the null stream may return before it has run and is not
         // ordered against the (non-blocking) render stream, so the first batch's counts could be zeroed after they were
         // added (seen with the three contexts of a group on one GPU: one rank's first sample missing from the shadow rays)
-        HIPCHECK(c, hipMemsetAsync(c->d_light_stats, 0, kLightStatWords * sizeof(unsigned long long), c->stream));
+        HIPCHECK(c, hipMemsetAsync(c->wk.light_stats.p, 0, kLightStatWords * sizeof(unsigned long long), c->stream));
     }
-    c->lb.stats = c->d_light_stats;
+    c->lb.stats = c->wk.light_stats.as<unsigned long long>();
     if (n_paths <= c->cap_light) return PRT_OK;
-    free_light_state(c);
+    c->light = LightMem();
+    c->cap_light = 0;
     const uint64_t n = std::max<uint64_t>(n_paths, 256);
-    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.o, n * sizeof(float4)));
-    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.d, n * sizeof(float4)));
-    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.t, n * sizeof(float4)));
-    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.hit, n * sizeof(uint32_t)));
-    HIPCHECK(c, hipMalloc((void**)&c->lb.sh.hd2, n * sizeof(float)));
-    HIPCHECK(c, hipMalloc((void**)&c->lb.pdf_b, n * sizeof(float)));
-    HIPCHECK(c, hipMalloc((void**)&c->lb.lrad, n * sizeof(float4)));
+    int e = c->light.sh.alloc(n);
+    if (!e) e = c->light.pdf_b.ensure(n * sizeof(float));
+    if (!e) e = c->light.lrad.ensure(n * sizeof(float4));
+    c->lb.sh = c->light.sh.view();
+    c->lb.pdf_b = c->light.pdf_b.as<float>();
+    c->lb.lrad = c->light.lrad.as<float4>();
+    HIPCHECK(c, e);
     c->cap_light = n;
     return PRT_OK;
 }
@@ -497,22 +477,22 @@ bool mesh_lights_on(const PrtContext* c) { return (c->light_sources & PRT_LIGHT_
 // with the MESH bit: the candidate table, n_lights = the candidates the search can return (0: nothing to sample)
 DevLights dev_lights(const PrtContext* c) {
     const uint32_t mode = c->lighting == PRT_LIGHTING_NEE ? (uint32_t)PRT_LIGHTING_NEE : (uint32_t)PRT_LIGHTING_NEE_MIS;
-    if (mesh_lights_on(c)) return DevLights{(const float4*)c->d_ml_records, (const uint32_t*)c->d_prim_light, c->hs.ml.n_search, mode};
-    return DevLights{(const float4*)c->d_lights, (const uint32_t*)c->d_prim_light,
-                     (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4)), mode};
+    if (mesh_lights_on(c)) return DevLights{c->ml.records.as<float4>(), c->scene.prim_light.as<uint32_t>(), c->hs.ml.n_search, mode};
+    return DevLights{c->scene.lights.as<float4>(), c->scene.prim_light.as<uint32_t>(), (uint32_t)(c->hs.lights.size() / (4 * PRT_LIGHT_F4)), mode};
 }
 
 DevMeshLights dev_mesh_lights(const PrtContext* c) {
-    return DevMeshLights{(const uint32_t*)c->d_ml_thr, c->light_buckets ? (const uint32_t*)c->d_ml_bucket : nullptr,
-                         (const DevLightRun*)c->d_ml_runs, c->hs.ml.bucket_shift, (uint32_t)c->hs.ml.runs.size()};
+    return DevMeshLights{c->ml.thr.as<uint32_t>(), c->light_buckets ? c->ml.bucket.as<uint32_t>() : nullptr,
+                         c->ml.runs.as<DevLightRun>(), c->hs.ml.bucket_shift, (uint32_t)c->hs.ml.runs.size()};
 }
 
 // clustered selection takes effect only while the integer rule selects lights
 bool clusters_on(const PrtContext* c) { return mesh_lights_on(c) && c->light_selection == (uint32_t)PRT_LIGHT_SELECTION_CLUSTERED; }
 
 DevLightClusters dev_light_clusters(const PrtContext* c) {
-    return DevLightClusters{(const float4*)c->d_lc_boxes, (const uint4*)c->d_lc_range, (const uint32_t*)c->d_lc_members,
-                            (const uint32_t*)c->d_lc_thr, (const uint32_t*)c->d_lc_cand, (const float*)c->d_lc_pmf, c->hs.lc.n_clusters()};
+    const MeshLightMem& m = c->ml;
+    return DevLightClusters{m.lc_boxes.as<float4>(), m.lc_range.as<uint4>(), m.lc_members.as<uint32_t>(),
+                            m.lc_thr.as<uint32_t>(), m.lc_cand.as<uint32_t>(), m.lc_pmf.as<float>(), c->hs.lc.n_clusters()};
 }
 
 uint32_t light_set_size(const PrtContext* c) {
@@ -526,33 +506,21 @@ uint64_t env_threshold(const PrtContext* c) { return prt_environment_threshold(c
 
 DevEnv dev_env(const PrtContext* c) {
     const uint64_t te = env_threshold(c);
-    return DevEnv{(const float4*)c->d_env_texels, (const uint32_t*)c->d_env_row, (const uint32_t*)c->d_env_col,
-                  (const uint32_t*)c->d_env_last, c->env.W, c->env.H, c->env.row_last, (uint32_t)te, te == 4294967296ull ? 1u : 0u,
+    return DevEnv{c->envm.texels.as<float4>(), c->envm.row.as<uint32_t>(), c->envm.col.as<uint32_t>(),
+                  c->envm.last.as<uint32_t>(), c->env.W, c->env.H, c->env.row_last, (uint32_t)te, te == 4294967296ull ? 1u : 0u,
                   (float)((double)te / 4294967296.0)};
-}
-
-void free_env(PrtContext* c) {
-    free_dev(c->d_env_texels);
-    free_dev(c->d_env_row);
-    free_dev(c->d_env_col);
-    free_dev(c->d_env_last);
 }
 
 // c->env onto the device (prt_set_environment, prt_clone_scene)
 int upload_env(PrtContext* c) {
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    free_env(c);
+    c->envm = EnvMem();
     if (!env_on(c)) return PRT_OK;
-    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
-    HIPCHECK(c, up(&c->d_env_texels, c->env.texels.data(), c->env.texels.size() * 4));
-    HIPCHECK(c, up(&c->d_env_row, c->env.row_thr.data(), c->env.row_thr.size() * 4));
-    HIPCHECK(c, up(&c->d_env_col, c->env.col_thr.data(), c->env.col_thr.size() * 4));
-    HIPCHECK(c, up(&c->d_env_last, c->env.col_last.data(), c->env.col_last.size() * 4));
+    HIPCHECK(c, c->envm.texels.alloc_copy(c->env.texels.data(), c->env.texels.size() * 4));
+    HIPCHECK(c, c->envm.row.alloc_copy(c->env.row_thr.data(), c->env.row_thr.size() * 4));
+    HIPCHECK(c, c->envm.col.alloc_copy(c->env.col_thr.data(), c->env.col_thr.size() * 4));
+    HIPCHECK(c, c->envm.last.alloc_copy(c->env.col_last.data(), c->env.col_last.size() * 4));
     return PRT_OK;
 }
 
@@ -561,16 +529,12 @@ int upload_env(PrtContext* c) {
 bool tex_on(const PrtContext* c) { return c->tex.is_set && c->tex.n_textured_materials != 0u; }
 
 DevTex dev_tex(const PrtContext* c) {
-    return DevTex{(const float4*)c->d_tex_texels, (const uint4*)c->d_tex_desc, (const uint32_t*)c->d_tex_mat, (const float2*)c->d_tex_uvs,
-                  (const uint32_t*)c->d_tex_inst, c->tex.n_textures};
+    return DevTex{c->texm.texels.as<float4>(), c->texm.desc.as<uint4>(), c->texm.mat.as<uint32_t>(), c->texm.uvs.as<float2>(),
+                  c->texm.inst.as<uint32_t>(), c->tex.n_textures};
 }
 
 void free_tex(PrtContext* c) {
-    free_dev(c->d_tex_texels);
-    free_dev(c->d_tex_desc);
-    free_dev(c->d_tex_mat);
-    free_dev(c->d_tex_uvs);
-    free_dev(c->d_tex_inst);
+    c->texm = TexMem();
     c->tex_bytes = 0;
 }
 
@@ -580,24 +544,23 @@ int upload_tex(PrtContext* c) {
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     free_tex(c);
     if (!c->tex.is_set) return PRT_OK;
-    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) c->tex_bytes += bytes;
+    auto up = [&](DevBuf& dst, const auto& src) {  // (every table has 4-byte elements)
+        const int e = dst.alloc_copy(src.data(), src.size() * 4);
+        if (!e) c->tex_bytes += src.size() * 4;
         return e;
     };
     const PrtTexTables& t = c->tex;
-    HIPCHECK(c, up(&c->d_tex_texels, t.texels.data(), t.texels.size() * 4));
-    HIPCHECK(c, up(&c->d_tex_desc, t.desc.data(), t.desc.size() * 4));
-    HIPCHECK(c, up(&c->d_tex_mat, t.mat_tex.data(), t.mat_tex.size() * 4));
-    HIPCHECK(c, up(&c->d_tex_uvs, t.uvs.data(), t.uvs.size() * 4));
-    HIPCHECK(c, up(&c->d_tex_inst, t.inst_uv_base.data(), t.inst_uv_base.size() * 4));
+    HIPCHECK(c, up(c->texm.texels, t.texels));
+    HIPCHECK(c, up(c->texm.desc, t.desc));
+    HIPCHECK(c, up(c->texm.mat, t.mat_tex));
+    HIPCHECK(c, up(c->texm.uvs, t.uvs));
+    HIPCHECK(c, up(c->texm.inst, t.inst_uv_base));
     return PRT_OK;
 }
 
 // prt_set_scene: the binding goes with the scene it was made for
 void drop_tex(PrtContext* c) {
-    if (c->has_device && c->d_tex_texels) {
+    if (c->has_device && c->texm.texels.p) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         free_tex(c);
@@ -611,34 +574,21 @@ int sync_light_tables(PrtContext* c) {
     const uint64_t te = env_threshold(c);
     if (te == c->t_env_dev || !c->has_device) return PRT_OK;
     std::vector<float> a, b;
-    const bool ml = mesh_lights_on(c) && c->d_ml_records;
+    const bool ml = mesh_lights_on(c) && c->ml.records.p;
     prt_scaled_light_tables(c->hs, te, &a, ml ? &b : nullptr);
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    if (!a.empty() && c->d_lights) HIPCHECK(c, hipMemcpy(c->d_lights, a.data(), a.size() * 4, hipMemcpyHostToDevice));
-    if (!a.empty() && c->d_lights && c->tally) c->tally->h2d += a.size() * 4;
-    if (ml && !b.empty()) HIPCHECK(c, hipMemcpy(c->d_ml_records, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+    if (!a.empty() && c->scene.lights.p) HIPCHECK(c, hipMemcpy(c->scene.lights.p, a.data(), a.size() * 4, hipMemcpyHostToDevice));
+    if (!a.empty() && c->scene.lights.p && c->tally) c->tally->h2d += a.size() * 4;
+    if (ml && !b.empty()) HIPCHECK(c, hipMemcpy(c->ml.records.p, b.data(), b.size() * 4, hipMemcpyHostToDevice));
     if (ml && !b.empty() && c->tally) c->tally->h2d += b.size() * 4;
-    if (ml && c->d_lc_pmf) {
+    if (ml && c->ml.lc_pmf.p) {
         prt_cluster_pmf_in(c->hs, te, &a);
-        if (!a.empty()) HIPCHECK(c, hipMemcpy(c->d_lc_pmf, a.data(), a.size() * 4, hipMemcpyHostToDevice));
+        if (!a.empty()) HIPCHECK(c, hipMemcpy(c->ml.lc_pmf.p, a.data(), a.size() * 4, hipMemcpyHostToDevice));
         if (!a.empty() && c->tally) c->tally->h2d += a.size() * 4;
     }
     c->t_env_dev = te;
     return PRT_OK;
-}
-
-void free_mesh_lights(PrtContext* c) {
-    free_dev(c->d_ml_records);
-    free_dev(c->d_ml_thr);
-    free_dev(c->d_ml_bucket);
-    free_dev(c->d_ml_runs);
-    free_dev(c->d_lc_boxes);
-    free_dev(c->d_lc_range);
-    free_dev(c->d_lc_members);
-    free_dev(c->d_lc_thr);
-    free_dev(c->d_lc_cand);
-    free_dev(c->d_lc_pmf);
 }
 
 // the candidate table of the current scene onto the device (prt_set_light_sources, upload_scene, prt_refit_meshes)
@@ -646,55 +596,55 @@ int upload_mesh_lights(PrtContext* c) {
     static_assert(sizeof(DevLightRun) == sizeof(PrtLightRun), "DevLightRun is PrtLightRun");
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    free_mesh_lights(c);
+    c->ml = MeshLightMem();
     const PrtMeshLights& ml = c->hs.ml;
-    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && c->tally) c->tally->h2d += bytes;
+    auto up = [&](DevBuf& dst, const void* src, size_t bytes) {
+        const int e = dst.alloc_copy(src, bytes);
+        if (!e && c->tally) c->tally->h2d += bytes;
         return e;
     };
-    HIPCHECK(c, up(&c->d_ml_records, ml.records.data(), ml.records.size() * 4));
-    HIPCHECK(c, up(&c->d_ml_thr, ml.thr.data(), ml.thr.size() * 4));
-    HIPCHECK(c, up(&c->d_ml_bucket, ml.bucket.data(), ml.bucket.size() * 4));
-    HIPCHECK(c, up(&c->d_ml_runs, ml.runs.data(), ml.runs.size() * sizeof(PrtLightRun)));
+    HIPCHECK(c, up(c->ml.records, ml.records.data(), ml.records.size() * 4));
+    HIPCHECK(c, up(c->ml.thr, ml.thr.data(), ml.thr.size() * 4));
+    HIPCHECK(c, up(c->ml.bucket, ml.bucket.data(), ml.bucket.size() * 4));
+    HIPCHECK(c, up(c->ml.runs, ml.runs.data(), ml.runs.size() * sizeof(PrtLightRun)));
     const PrtLightClusters& lc = c->hs.lc;  // (12 bytes per candidate more; they go up whatever the selection mode)
     std::vector<float> pmf_in;
     prt_cluster_pmf_in(c->hs, 0u, &pmf_in);
-    HIPCHECK(c, up(&c->d_lc_boxes, lc.boxes.data(), lc.boxes.size() * 4));
-    HIPCHECK(c, up(&c->d_lc_range, lc.range.data(), lc.range.size() * 4));
-    HIPCHECK(c, up(&c->d_lc_members, lc.members.data(), lc.members.size() * 4));
-    HIPCHECK(c, up(&c->d_lc_thr, lc.thr.data(), lc.thr.size() * 4));
-    HIPCHECK(c, up(&c->d_lc_cand, lc.cand_cluster.data(), lc.cand_cluster.size() * 4));
-    HIPCHECK(c, up(&c->d_lc_pmf, pmf_in.data(), pmf_in.size() * 4));
+    HIPCHECK(c, up(c->ml.lc_boxes, lc.boxes.data(), lc.boxes.size() * 4));
+    HIPCHECK(c, up(c->ml.lc_range, lc.range.data(), lc.range.size() * 4));
+    HIPCHECK(c, up(c->ml.lc_members, lc.members.data(), lc.members.size() * 4));
+    HIPCHECK(c, up(c->ml.lc_thr, lc.thr.data(), lc.thr.size() * 4));
+    HIPCHECK(c, up(c->ml.lc_cand, lc.cand_cluster.data(), lc.cand_cluster.size() * 4));
+    HIPCHECK(c, up(c->ml.lc_pmf, pmf_in.data(), pmf_in.size() * 4));
     c->t_env_dev = c->t_env_dev ? ~0ull : 0ull;  // (the records went up unscaled: a scaled default table is rewritten with them)
     return sync_light_tables(c);
 }
 
 int ensure_counters(PrtContext* c) {
-    if (c->d_counts) return PRT_OK;
-    HIPCHECK(c, hipMalloc((void**)&c->d_counts, (PRT_MAX_DEPTH + 2) * PRT_CNT_STRIDE * sizeof(uint32_t)));
-    HIPCHECK(c, hipMalloc((void**)&c->d_ray_stats, kRayStatWords * 2 * sizeof(unsigned long long)));
-    c->ray_stats_target = c->d_ray_stats;
-    HIPCHECK(c, hipMalloc((void**)&c->d_trav_stats, kTravStatsWords * sizeof(unsigned long long)));
-    HIPCHECK(c, hipMemset(c->d_counts, 0, (PRT_MAX_DEPTH + 2) * PRT_CNT_STRIDE * sizeof(uint32_t)));
-    HIPCHECK(c, hipMemset(c->d_ray_stats, 0, kRayStatWords * 2 * sizeof(unsigned long long)));
-    HIPCHECK(c, hipMemset(c->d_trav_stats, 0, kTravStatsWords * sizeof(unsigned long long)));
+    WorkMem& w = c->wk;
+    if (w.counts.p) return PRT_OK;
+    HIPCHECK(c, w.counts.ensure((PRT_MAX_DEPTH + 2) * PRT_CNT_STRIDE * sizeof(uint32_t)));
+    HIPCHECK(c, w.ray_stats.ensure(kRayStatWords * 2 * sizeof(unsigned long long)));
+    c->ray_stats_target = w.ray_stats.as<unsigned long long>();
+    HIPCHECK(c, w.trav_stats.ensure(kTravStatsWords * sizeof(unsigned long long)));
+    HIPCHECK(c, hipMemset(w.counts.p, 0, w.counts.bytes));
+    HIPCHECK(c, hipMemset(w.ray_stats.p, 0, w.ray_stats.bytes));
+    HIPCHECK(c, hipMemset(w.trav_stats.p, 0, w.trav_stats.bytes));
     // [0..255] chunk cursors (one 128-B line per XCD), [256] watchdog flag, [512] overflow count, [513..] overflow list
-    HIPCHECK(c, hipMalloc((void**)&c->d_work, (513 + (1u << 20)) * sizeof(uint32_t)));
-    HIPCHECK(c, hipMemset(c->d_work, 0, (513 + (1u << 20)) * sizeof(uint32_t)));
+    HIPCHECK(c, w.work.ensure((513 + (1u << 20)) * sizeof(uint32_t)));
+    HIPCHECK(c, hipMemset(w.work.p, 0, w.work.bytes));
     return PRT_OK;
 }
 
 // global spill area of the traversal stacks: [prt_spill_rows of the scene's trees][grid threads]
 int ensure_spill(PrtContext* c) {
     const size_t need = (size_t)c->tune.grid_blocks * 256u * prt_spill_rows(c->hs.bvh.max_stack4, c->hs.bvh.max_depth);
-    return c->spill.ensure(c, need * sizeof(uint32_t));
+    return ensure(c, c->spill, need * sizeof(uint32_t));
 }
 
 // What prt_refit_meshes_device keeps with a scene goes with it
 void drop_refit_keep(PrtContext* c) {
-    c->rk_buf.release();
+    c->scene.refit_keep = DevBuf();
     c->rk = PrtContext::RefitKeep();
     c->host_copies_stale = false;
     c->rinfo = PrtRefitInfo{};
@@ -708,30 +658,17 @@ int refresh_host_copies(PrtContext* c) {
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     PrtHostScene& hs = c->hs;
     const size_t n_nodes = hs.bvh.nodes8.size() / 20, n_tris = c->dsc.n_tris;
-    if (n_nodes) HIPCHECK(c, hipMemcpy2D(hs.bvh.nodes8.data(), 80, c->d_nodes8, (size_t)c->dsc.node_stride * 16, 80, n_nodes, hipMemcpyDeviceToHost));
-    if (hs.tri_records.size() == 12 * n_tris) HIPCHECK(c, hipMemcpy(hs.tri_records.data(), c->d_tris, 48 * n_tris, hipMemcpyDeviceToHost));
-    if (hs.nrm_records.size() == 12 * n_tris) HIPCHECK(c, hipMemcpy(hs.nrm_records.data(), c->d_nrms, 48 * n_tris, hipMemcpyDeviceToHost));
+    if (n_nodes) HIPCHECK(c, hipMemcpy2D(hs.bvh.nodes8.data(), 80, c->scene.nodes8.p, (size_t)c->dsc.node_stride * 16, 80, n_nodes, hipMemcpyDeviceToHost));
+    if (hs.tri_records.size() == 12 * n_tris) HIPCHECK(c, hipMemcpy(hs.tri_records.data(), c->scene.tris.p, 48 * n_tris, hipMemcpyDeviceToHost));
+    if (hs.nrm_records.size() == 12 * n_tris) HIPCHECK(c, hipMemcpy(hs.nrm_records.data(), c->scene.nrms.p, 48 * n_tris, hipMemcpyDeviceToHost));
     c->host_copies_stale = false;
     return PRT_OK;
 }
 
 void free_scene(PrtContext* c) {
     drop_refit_keep(c);
-    free_dev(c->d_prims);
-    free_dev(c->d_mat_rgbs);
-    free_dev(c->d_mat_type);
-    free_dev(c->d_nodes);
-    free_dev(c->d_nodes4);
-    free_dev(c->d_nodes8);
-    free_dev(c->d_insts);
-    free_dev(c->d_tlas_inst);
-    free_dev(c->d_abvh_nodes);
-    free_dev(c->d_abvh_order);
-    free_dev(c->d_tris);
-    free_dev(c->d_nrms);
-    free_dev(c->d_lights);
-    free_dev(c->d_prim_light);
-    free_mesh_lights(c);
+    c->scene = SceneMem();
+    c->ml = MeshLightMem();
     c->has_scene = false;
 }
 
@@ -750,27 +687,27 @@ int read_ray_stats(PrtContext* c, const unsigned long long* d_set, unsigned long
 int begin_event(PrtContext* c, int kind, EventPair* ep) {
     if (!c->timing) return PRT_OK;
     if (!c->event_pool.empty()) {
-        *ep = c->event_pool.back();
+        *ep = std::move(c->event_pool.back());
         c->event_pool.pop_back();
     } else {
-        HIPCHECK(c, hipEventCreate(&ep->a));
-        HIPCHECK(c, hipEventCreate(&ep->b));
+        HIPCHECK(c, ep->a.create(true));
+        HIPCHECK(c, ep->b.create(true));
     }
     ep->kind = kind;
-    HIPCHECK(c, hipEventRecord(ep->a, c->stream));
+    HIPCHECK(c, hipEventRecord(ev(ep->a), c->stream));
     return PRT_OK;
 }
 int end_event(PrtContext* c, EventPair* ep) {
     if (!c->timing) return PRT_OK;
-    HIPCHECK(c, hipEventRecord(ep->b, c->stream));
-    c->events.push_back(*ep);
+    HIPCHECK(c, hipEventRecord(ev(ep->b), c->stream));
+    c->events.push_back(std::move(*ep));
     return PRT_OK;
 }
 int drain_events(PrtContext* c) {
     for (EventPair& ep : c->events) {
         float ms = 0.0f;
-        HIPCHECK(c, hipEventSynchronize(ep.b));
-        HIPCHECK(c, hipEventElapsedTime(&ms, ep.a, ep.b));
+        HIPCHECK(c, hipEventSynchronize(ev(ep.b)));
+        HIPCHECK(c, hipEventElapsedTime(&ms, ev(ep.a), ev(ep.b)));
         switch (ep.kind) {
             case 0: c->stats.raygen_ms += ms; break;
             case 1: c->stats.intersect_ms += ms; break;
@@ -778,7 +715,7 @@ int drain_events(PrtContext* c) {
             case 4: c->stats.scan_ms += ms; break;
             default: c->stats.accumulate_ms += ms; break;
         }
-        c->event_pool.push_back(ep);
+        c->event_pool.push_back(std::move(ep));
     }
     c->events.clear();
     return PRT_OK;
@@ -817,7 +754,7 @@ void walk_rays(PrtContext* c, const PrtRayBuf& rays, const uint32_t* count, uint
                unsigned long long* stats, const PrtPrimary* primary, bool seeded = false) {
     const PrtWalkRequest request = !any ? PRT_WALK_CLOSEST : seeded ? PRT_WALK_SEEDED : PRT_WALK_ANY;
     const PrtWalkPlan plan = prt_plan_walk(walk_facts(c, tune, request, max_rays, stats != nullptr, primary != nullptr));
-    prt_launch_walk(c->stream, plan, PrtWalkArgs{&c->dsc, rays, count, c->d_work, (uint32_t*)c->spill.p, stats, primary, &tune});
+    prt_launch_walk(c->stream, plan, PrtWalkArgs{&c->dsc, rays, count, c->wk.work.as<uint32_t>(), c->spill.as<uint32_t>(), stats, primary, &tune});
 }
 
 // Measurement aid (sort_rays, tools/sort_ab.py): the front rays of `in` in sorted order through tune->perm.  The host needs
@@ -829,20 +766,20 @@ int sort_front_rays(PrtContext* c, const PrtRayBuf& in, const uint32_t* front_co
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     if (n_front <= 1u) return PRT_OK;
     if (c->sort_entries < n_paths) {
-        free_dev(c->d_sort);
+        c->wk.sort = DevBuf();
         c->sort_entries = 0;
         c->sort_temp = prt_sort_rays_temp_bytes(n_paths);
-        HIPCHECK(c, hipMalloc((void**)&c->d_sort, 4 * (size_t)n_paths * sizeof(uint32_t) + c->sort_temp));
+        HIPCHECK(c, c->wk.sort.ensure(4 * (size_t)n_paths * sizeof(uint32_t) + c->sort_temp));
         c->sort_entries = n_paths;
     }
     EventPair es{};
     if ((rc = begin_event(c, 4, &es))) return rc;
-    uint32_t* q = c->d_sort;
+    uint32_t* q = c->wk.sort.as<uint32_t>();
     if (prt_sort_rays(c->stream, in.o, in.d, n_front, c->dsc.root_min, c->dsc.root_max, c->sort_rays, q, q + n_paths,
                       q + 2 * (size_t)n_paths, q + 3 * (size_t)n_paths, q + 4 * (size_t)n_paths, c->sort_temp))
         return fail(c, PRT_ERR_HIP, "ray sort failed");
     if ((rc = end_event(c, &es))) return rc;
-    if (c->timing) HIPCHECK(c, hipEventRecord(ep->a, c->stream));  // the traversal's own time starts after the sort
+    if (c->timing) HIPCHECK(c, hipEventRecord(ev(ep->a), c->stream));  // the traversal's own time starts after the sort
     tune->perm = q + 3 * (size_t)n_paths;
     return PRT_OK;
 }
@@ -854,7 +791,7 @@ int sort_front_rays(PrtContext* c, const PrtRayBuf& in, const uint32_t* front_co
 int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t max_depth, uint32_t seed, uint32_t first_sample,
               bool accumulate, unsigned long long* trav_stats) {
     const PrtTileMap& tm = view.tm;
-    if (view.list && !c->d_film_stat) return fail(c, PRT_ERR_INVALID, "a tile list needs film statistics");
+    if (view.list && !c->film.stat.p) return fail(c, PRT_ERR_INVALID, "a tile list needs film statistics");
     const uint64_t n_paths64 = (uint64_t)S_cur * tm.n_pix_local;
     c->batch_walked = false;
     c->primary_reuse_active = 0u;
@@ -906,28 +843,33 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     // the producer that wrote them, the host waits for it after enqueueing the traversal): the GPU never waits for the
     // host, k_shade gets an exact grid, and a batch stops at the first bounce without rays.
     const bool exact = c->dsc.n_nodes != 0u && c->tune.exact_grids != 0u && (n_paths > (16384u * 512u) || c->tune.exact_grids == 2u);  // 2: always (tests)
-    if (exact && !c->h_counts) {
-        HIPCHECK(c, hipHostMalloc((void**)&c->h_counts, (PRT_MAX_DEPTH + 2) * 64 * sizeof(uint32_t), hipHostMallocDefault));
-        for (hipEvent_t& e : c->ev_counts) HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t& e : c->ev_prod) HIPCHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (exact && !c->wk.counts_host.p) {
+        HIPCHECK(c, c->wk.counts_host.alloc((PRT_MAX_DEPTH + 2) * 64 * sizeof(uint32_t)));
+        for (DevEvent& e : c->wk.ev_counts) HIPCHECK(c, e.create(false));
+        for (DevEvent& e : c->wk.ev_prod) HIPCHECK(c, e.create(false));
         HIPCHECK(c, hipStreamCreateWithFlags(&c->count_stream, hipStreamNonBlocking));
     }
+    // the work arrays as the kernels take them (allocated with the scene and the film: ensure_counters)
+    uint32_t* const d_counts = c->wk.counts.as<uint32_t>();
+    uint32_t* const d_work = c->wk.work.as<uint32_t>();
+    uint32_t* const h_counts = c->wk.counts_host.as<uint32_t>();
+    float4* const d_rad = c->path.rad.as<float4>();
     auto read_back = [&](uint32_t d) -> hipError_t {  // counts of bounce d: words 0 (front) and 32 (back) of its stride
         // (on a stream of its own behind an event: in the render stream the 4-us copy kernel and the gaps around it were
         // 10-20 us per bounce, 1 % of a step of a rank of eight)
-        hipError_t e = hipEventRecord(c->ev_prod[d], c->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(c->count_stream, c->ev_prod[d], 0);
+        hipError_t e = hipEventRecord(ev(c->wk.ev_prod[d]), c->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c->count_stream, ev(c->wk.ev_prod[d]), 0);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(c->h_counts + 64 * (size_t)d, c->d_counts + (size_t)d * PRT_CNT_STRIDE, 33 * sizeof(uint32_t),
+            e = hipMemcpyAsync(h_counts + 64 * (size_t)d, d_counts + (size_t)d * PRT_CNT_STRIDE, 33 * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, c->count_stream);
-        return e != hipSuccess ? e : hipEventRecord(c->ev_counts[d], c->count_stream);
+        return e != hipSuccess ? e : hipEventRecord(ev(c->wk.ev_counts[d]), c->count_stream);
     };
     EventPair ep{};
     // film += the batch's samples (unless this is a measurement run) and per-depth ray counts from the paths' last segment indices
     auto accumulate_batch = [&]() -> int {
         if ((rc = begin_event(c, 3, &ep))) return rc;
-        const PrtAccumulateArgs aa{c->d_rad, lit ? c->lb.lrad : nullptr, c->d_film_local, c->d_film_stat, tm, S_cur, max_depth,
-                                   accumulate, c->ray_stats_target, compact ? c->d_pix + tm.n_pix_local : nullptr, view.list};
+        const PrtAccumulateArgs aa{d_rad, lit ? c->lb.lrad : nullptr, c->film.local.as<float4>(), c->film.stat.as<float2>(), tm, S_cur, max_depth,
+                                   accumulate, c->ray_stats_target, compact ? c->wk.pix.as<float4>() + tm.n_pix_local : nullptr, view.list};
         if (!prt_launch_accumulate(c->stream, plan.accumulate, aa)) return fail(c, PRT_ERR_INVALID, "no such accumulate instance");
         c->batch_instance[PRT_STAGE_ACCUMULATE] = prt_accumulate_name(plan.accumulate);
         if ((rc = end_event(c, &ep))) return rc;
@@ -946,19 +888,18 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     // the pipeline up to ~250 k paths per call and loses above (profiles/r3_path_kernel.txt, TUNING.md): both are bound
     // by a path's chain of dependent node fetches, and the pipeline shades with full waves.
     if (plan.path) {
-        HIPCHECK(c, hipMemsetAsync(c->d_work, 0, 256 * sizeof(uint32_t), c->stream));  // the cursors; the error flags in [256] stay for prt_synchronize
-        PrtPathArgs pa{c->cam, tm, c->sampling, c->d_rad, first_sample, seed, max_depth, n_paths};
+        HIPCHECK(c, hipMemsetAsync(d_work, 0, 256 * sizeof(uint32_t), c->stream));  // the cursors; the error flags in [256] stay for prt_synchronize
+        PrtPathArgs pa{c->cam, tm, c->sampling, d_rad, first_sample, seed, max_depth, n_paths};
         if ((rc = begin_event(c, 1, &ep))) return rc;
-        prt_launch_path(c->stream, prt_plan_walk(wf), c->dsc, pa, c->d_work, c->tune);
+        prt_launch_path(c->stream, prt_plan_walk(wf), c->dsc, pa, d_work, c->tune);
         if ((rc = end_event(c, &ep))) return rc;
         ++c->stats.intersect_launches;
         return accumulate_batch();
     }
     if (compact && c->pix_entries < tm.n_pix_local) {
-        free_dev(c->d_pix);
         c->pix_entries = 0;
         c->primary_key.valid = false;
-        HIPCHECK(c, hipMalloc((void**)&c->d_pix, 4 * (size_t)tm.n_pix_local * sizeof(float4)));
+        HIPCHECK(c, c->wk.pix.ensure(4 * (size_t)tm.n_pix_local * sizeof(float4)));
         c->pix_entries = tm.n_pix_local;
         c->pix_records_blank = false;
     }
@@ -972,8 +913,9 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     const bool instrumented = trav_stats != nullptr || c->d_shade_div != nullptr;
     const bool persistent = compact && (walk || S_cur == 1u);
     if (persistent && (rc = ensure_primary_state(c, n_paths, tm.n_pix_local))) return rc;
+    float4* const d_pix = c->wk.pix.as<float4>();
     PrtRayBuf rb0 = c->rb[0];
-    if (persistent) rb0.t = (float4*)c->d_prim_pid, rb0.hd2 = (float*)c->d_prim_list, rb0.hit = c->d_prim_hit;
+    if (persistent) rb0.t = c->prim.pid.as<float4>(), rb0.hd2 = c->prim.list.as<float>(), rb0.hit = c->prim.hit.as<uint32_t>();
     PrtPrimaryKey now{};
     now.valid = persistent && c->primary_reuse != 0 && !instrumented;  // eligible (compact: no jitter, no lens, no tile list)
     if (now.valid) {
@@ -994,8 +936,8 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     // Bounce 0's words are written by k_raygen alone (front, back, finished, list; k_shade of bounce d adds to bounce d + 1's,
     // and word 48, the shadow rays, belongs to the lighting modes, which are never compact) and read by the bounce-0 walk,
     // k_primary_hit and the first k_shade: they stand as the refresh left them.
-    if (reuse) HIPCHECK(c, hipMemsetAsync(c->d_counts + PRT_CNT_STRIDE, 0, (size_t)max_depth * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
-    else HIPCHECK(c, hipMemsetAsync(c->d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
+    if (reuse) HIPCHECK(c, hipMemsetAsync(d_counts + PRT_CNT_STRIDE, 0, (size_t)max_depth * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
+    else HIPCHECK(c, hipMemsetAsync(d_counts, 0, (size_t)(max_depth + 1) * PRT_CNT_STRIDE * sizeof(uint32_t), c->stream));
     const DevLights lt = dev_lights(c);
     const DevMeshLights mlt = dev_mesh_lights(c);
     const DevLightClusters lct = dev_light_clusters(c);
@@ -1008,7 +950,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     // slot.  A batch of ONE sample keeps its path slots: they ARE that list (one path per pixel, in the same order), and
     // k_raygen saves the second store and atomic.
     c->batch_walked = walk;
-    const PrtPrimary primary{(const uint32_t*)rb0.t, c->d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, tm.n_pix_local,
+    const PrtPrimary primary{(const uint32_t*)rb0.t, d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, tm.n_pix_local,
                              1.0f / (float)tm.n_pix_local, first_sample, seed, walk ? 1u : 0u};
     PrtPrimary primary_list = primary;  // what the traversal sees: list slots in place of path slots
     if (walk) primary_list.pid = (const uint32_t*)rb0.hd2;
@@ -1017,8 +959,8 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     if (!reuse) {
         c->primary_key.valid = false;  // k_raygen overwrites d_pix and bounce 0's counters: set again below, once the stage stands
         if ((rc = begin_event(c, 0, &ep))) return rc;
-        const PrtRaygenArgs ra{&c->dsc, c->cam, tm, n_paths, first_sample, seed, max_depth, rb0, c->d_rad, c->d_counts, c->d_work, c->sampling,
-                               compact ? c->d_pix : nullptr, walk, f.env ? &denv : nullptr, f.lens ? &dlens : nullptr, view.list};
+        const PrtRaygenArgs ra{&c->dsc, c->cam, tm, n_paths, first_sample, seed, max_depth, rb0, d_rad, d_counts, d_work, c->sampling,
+                               compact ? d_pix : nullptr, walk, f.env ? &denv : nullptr, f.lens ? &dlens : nullptr, view.list};
         if (!prt_launch_raygen(c->stream, plan.raygen, ra)) return fail(c, PRT_ERR_INVALID, "no such raygen instance");
         if ((rc = end_event(c, &ep))) return rc;
         if (exact) HIPCHECK(c, read_back(0));
@@ -1026,7 +968,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     for (uint32_t d = 0; d < max_depth; ++d) {
         const PrtRayBuf& in = d == 0 ? rb0 : c->rb[d & 1];
         const PrtRayBuf& out = c->rb[(d + 1) & 1];
-        const uint32_t* front_count = c->d_counts + (size_t)d * PRT_CNT_STRIDE;
+        const uint32_t* front_count = d_counts + (size_t)d * PRT_CNT_STRIDE;
         const PrtPrimary* prim_d = (compact && d == 0) ? &primary : nullptr;
         const bool held = reuse && d == 0;  // bounce 0's hits and the pixels' hit records stand
         // (REUSE starts at the first k_shade: the cursors and the overflow counter k_raygen zeroes are the bounce-0 walk's, and
@@ -1039,7 +981,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
             if (plan.walk8 && c->sort_rays && !prim_d && (d > 0 || c->sampling.jitter || f.lens))
                 if ((rc = sort_front_rays(c, in, front_count, n_paths, &ep, &tune))) return rc;
             if (walk && d == 0)
-                walk_rays(c, in, c->d_counts + PRT_CNT_LIST, tm.n_pix_local, false, tune, trav_stats, &primary_list);
+                walk_rays(c, in, d_counts + PRT_CNT_LIST, tm.n_pix_local, false, tune, trav_stats, &primary_list);
             else if (plan.last_segment == 2u && d + 1u == max_depth && !trav_stats)
                 // the last segment's stored rays only ask whether a triangle lies in front of their seed: the seeded any-hit walk
                 // (instrumented batches keep the closest-hit walk, which answers the same question)
@@ -1052,11 +994,11 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
                 // (a batch of ONE sample has nothing to share: k_shade rebuilds the hit itself, one launch less)
                 if (plan.primary_hit) {  // (timed with the shade stage)
                     if ((rc = begin_event(c, 2, &ep))) return rc;
-                    prt_launch_primary_hit(c->stream, c->dsc, primary, in.hit, c->d_pix, c->d_counts);
+                    prt_launch_primary_hit(c->stream, c->dsc, primary, in.hit, d_pix, d_counts);
                     if ((rc = end_event(c, &ep))) return rc;
                     c->pix_records_blank = false;
                 } else if (!c->pix_records_blank) {  // "no record" for every pixel (hit id 0xFFFFFFFF never equals a hit k_shade looks up); stays so until k_primary_hit runs again
-                    HIPCHECK(c, hipMemsetAsync(c->d_pix + 2 * (size_t)tm.n_pix_local, 0xFF, 2 * (size_t)tm.n_pix_local * sizeof(float4), c->stream));
+                    HIPCHECK(c, hipMemsetAsync(d_pix + 2 * (size_t)tm.n_pix_local, 0xFF, 2 * (size_t)tm.n_pix_local * sizeof(float4), c->stream));
                     c->pix_records_blank = true;
                 }
             }
@@ -1065,16 +1007,16 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         if (exact && held) {  // bounce 0's counts as the refresh read them: no copy, no wait
             n_rays_known = c->primary_counts[0] + c->primary_counts[1];
         } else if (exact) {
-            HIPCHECK(c, hipEventSynchronize(c->ev_counts[d]));
-            n_rays_known = c->h_counts[64 * (size_t)d] + c->h_counts[64 * (size_t)d + 32];
-            if (d == 0) c->primary_counts[0] = c->h_counts[0], c->primary_counts[1] = c->h_counts[32];
+            HIPCHECK(c, hipEventSynchronize(ev(c->wk.ev_counts[d])));
+            n_rays_known = h_counts[64 * (size_t)d] + h_counts[64 * (size_t)d + 32];
+            if (d == 0) c->primary_counts[0] = h_counts[0], c->primary_counts[1] = h_counts[32];
         }
         if (n_rays_known == 0u) break;  // every path has ended: the later bounces have nothing to do
         if (d == 0 && !reuse && now.valid) c->primary_key = now;  // the stage stands: what the next batch may start from
-        if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, c->d_counts, d, n_paths, c->d_shade_div, prim_d);
+        if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, d_counts, d, n_paths, c->d_shade_div, prim_d);
         if ((rc = begin_event(c, 2, &ep))) return rc;
         const PrtShadeInst shade = d == 0 ? plan.shade0 : plan.shade;
-        const PrtShadeArgs sa{&c->dsc, in, out, c->d_rad, c->d_counts, c->d_work, d, max_depth, n_paths, c->sampling, n_rays_known, prim_d, plan.last_segment,
+        const PrtShadeArgs sa{&c->dsc, in, out, d_rad, d_counts, d_work, d, max_depth, n_paths, c->sampling, n_rays_known, prim_d, plan.last_segment,
                               f.env ? &denv : nullptr, f.tex ? &dtex : nullptr, lit ? &lt : nullptr, (lit && f.mesh_lights) ? &mlt : nullptr,
                               lit ? &c->lb : nullptr, (lit && f.light_clusters) ? &lct : nullptr};
         if (!prt_launch_shade(c->stream, shade, sa)) return fail(c, PRT_ERR_INVALID, "no such shade instance");
@@ -1084,11 +1026,11 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         if (lit && (lt.n_lights || (f.env && (denv.t_all | denv.t_env)))) {
             // the bounce's shadow rays: prt_occluded's pipeline on the device-side count (at most one per ray of the
             // bounce), then their contributions into the paths' light radiance (timed with the shade stage)
-            const uint32_t* scount = c->d_counts + (size_t)d * PRT_CNT_STRIDE + 48u;
+            const uint32_t* scount = d_counts + (size_t)d * PRT_CNT_STRIDE + 48u;
             const uint32_t nmax = n_rays_known == 0xFFFFFFFFu ? n_paths : n_rays_known;
-            prt_launch_scan_prims_bounded(c->stream, c->dsc, c->lb.sh, scount, c->d_work, nmax);
+            prt_launch_scan_prims_bounded(c->stream, c->dsc, c->lb.sh, scount, d_work, nmax);
             if (c->dsc.n_nodes) walk_rays(c, c->lb.sh, scount, nmax, true, c->tune, nullptr, nullptr);
-            prt_launch_light_accum(c->stream, c->dsc, c->lb, scount, c->d_work, nmax);
+            prt_launch_light_accum(c->stream, c->dsc, c->lb, scount, d_work, nmax);
         }
         if ((rc = end_event(c, &ep))) return rc;
         if (exact && d + 1 < max_depth) HIPCHECK(c, read_back(d + 1));
@@ -1101,18 +1043,19 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
 void fill_dev_scene(PrtContext* c, uint32_t node_stride, uint32_t depth8) {
     const PrtSceneScalars& k = c->hs.sc;
     DevScene d{};
-    d.prims = (const DevPrim*)c->d_prims;
-    d.mat_rgbs = (const float4*)c->d_mat_rgbs;
-    d.mat_type = (const uint32_t*)c->d_mat_type;
-    d.nodes = (const float4*)c->d_nodes;
-    d.nodes4 = (const float4*)c->d_nodes4;
-    d.nodes8 = (const uint4*)c->d_nodes8;  // null when the tree has no compressed 8-wide form: the 4-wide kernel runs
-    d.tris = (const float4*)c->d_tris;
-    d.tri_normals = (const float4*)c->d_nrms;
-    d.abvh_nodes = (const float4*)c->d_abvh_nodes;
-    d.abvh_order = (const uint32_t*)c->d_abvh_order;
-    d.insts = (const DevInstance*)c->d_insts;
-    d.tlas_inst = (const uint32_t*)c->d_tlas_inst;
+    const SceneMem& m = c->scene;
+    d.prims = m.prims.as<DevPrim>();
+    d.mat_rgbs = m.mat_rgbs.as<float4>();
+    d.mat_type = m.mat_type.as<uint32_t>();
+    d.nodes = m.nodes.as<float4>();
+    d.nodes4 = m.nodes4.as<float4>();
+    d.nodes8 = m.nodes8.as<uint4>();  // null when the tree has no compressed 8-wide form: the 4-wide kernel runs
+    d.tris = m.tris.as<float4>();
+    d.tri_normals = m.nrms.as<float4>();
+    d.abvh_nodes = m.abvh_nodes.as<float4>();
+    d.abvh_order = m.abvh_order.as<uint32_t>();
+    d.insts = m.insts.as<DevInstance>();
+    d.tlas_inst = m.tlas_inst.as<uint32_t>();
     d.n_insts = k.n_insts;
     d.node_stride = node_stride;
     d.depth8 = depth8;
@@ -1132,14 +1075,15 @@ void fill_dev_scene(PrtContext* c, uint32_t node_stride, uint32_t depth8) {
 // Second half of prt_set_scene / prt_clone_scene: the context's host copies -> its device.  `gb` (device-side build):
 // the builder's arrays on this device become the scene's arrays; otherwise trees and triangle records are uploaded from
 // the host copies (a scene built on ANOTHER device arrives that way too: its 8-wide tree and records were read back).
-int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
+int upload_scene(PrtContext* c, BuiltTree* gb) {
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     free_scene(c);
-    if (gb) {  // owned by the context from here on (free_scene)
-        c->d_nodes8 = gb->d_nodes8;
-        c->d_tris = gb->d_tris;
-        c->d_nrms = gb->d_nrms;
+    SceneMem& m = c->scene;
+    if (gb) {  // the scene's from here on
+        m.nodes8 = std::move(gb->nodes8);
+        m.tris = std::move(gb->tris);
+        m.nrms = std::move(gb->nrms);
     }
     // Node slots.  An 80-B node at a 16-B aligned address lies across two 128-B lines half of the time, so a visit that
     // misses the caches moves 1.5 lines = 192 B (tools/gather_calib.hip).  Trees far beyond the L2s (C5: 1.6 M nodes =
@@ -1149,26 +1093,16 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
     const size_t n_nodes8 = gb ? (size_t)gb->n_nodes : n8.size() / 20;
     const uint32_t node_stride = c->node_stride ? (uint32_t)c->node_stride : (n_nodes8 * 80 > ((size_t)64 << 20) ? 8u : 5u);
     if (node_stride == 8u && n_nodes8) {
-        void* wide = nullptr;
-        HIPCHECK(c, hipMalloc(&wide, 128 * n_nodes8));
-        hipError_t e = hipMemset(wide, 0, 128 * n_nodes8);
+        DevBuf wide;
+        HIPCHECK(c, wide.ensure(128 * n_nodes8));
+        hipError_t e = hipMemset(wide.p, 0, 128 * n_nodes8);
         if (e == hipSuccess)
-            e = gb ? hipMemcpy2D(wide, 128, c->d_nodes8, 80, 80, n_nodes8, hipMemcpyDeviceToDevice)
-                   : hipMemcpy2D(wide, 128, n8.data(), 80, 80, n_nodes8, hipMemcpyHostToDevice);
+            e = gb ? hipMemcpy2D(wide.p, 128, m.nodes8.p, 80, 80, n_nodes8, hipMemcpyDeviceToDevice)
+                   : hipMemcpy2D(wide.p, 128, n8.data(), 80, 80, n_nodes8, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipDeviceSynchronize();  // (device-to-device copies on the null stream return early; renders use c->stream)
-        if (e != hipSuccess) {
-            (void)hipFree(wide);
-            HIPCHECK(c, e);
-        }
-        free_dev(c->d_nodes8);
-        c->d_nodes8 = wide;
+        HIPCHECK(c, e);
+        m.nodes8 = std::move(wide);
     }
-    auto upload = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
-        if (e != hipSuccess) return e;
-        if (bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
     std::vector<float> rgbs(4 * c->hs.materials.size());
     std::vector<uint32_t> mtype(c->hs.materials.size());
     for (size_t i = 0; i < c->hs.materials.size(); ++i) {
@@ -1178,27 +1112,27 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
         rgbs[4 * i + 3] = c->hs.materials[i].scalar;
         mtype[i] = c->hs.materials[i].type;
     }
-    HIPCHECK(c, upload(&c->d_prims, c->hs.prims.data(), c->hs.prims.size() * sizeof(DevPrim)));
-    HIPCHECK(c, upload(&c->d_mat_rgbs, rgbs.data(), rgbs.size() * 4));
-    HIPCHECK(c, upload(&c->d_mat_type, mtype.data(), mtype.size() * 4));
+    HIPCHECK(c, m.prims.alloc_copy(c->hs.prims.data(), c->hs.prims.size() * sizeof(DevPrim)));
+    HIPCHECK(c, m.mat_rgbs.alloc_copy(rgbs.data(), rgbs.size() * 4));
+    HIPCHECK(c, m.mat_type.alloc_copy(mtype.data(), mtype.size() * 4));
     if (!c->hs.scene_device_built) {  // (device-built scenes have no binary / 4-wide tree: null pointers select the 8-wide kernel)
-        HIPCHECK(c, upload(&c->d_nodes, c->hs.bvh.nodes.data(), c->hs.bvh.nodes.size() * 4));
-        HIPCHECK(c, upload(&c->d_nodes4, c->hs.bvh.nodes4.data(), c->hs.bvh.nodes4.size() * 4));
+        HIPCHECK(c, m.nodes.alloc_copy(c->hs.bvh.nodes.data(), c->hs.bvh.nodes.size() * 4));
+        HIPCHECK(c, m.nodes4.alloc_copy(c->hs.bvh.nodes4.data(), c->hs.bvh.nodes4.size() * 4));
     }
-    if (!gb && !n8.empty() && node_stride != 8u) HIPCHECK(c, upload(&c->d_nodes8, n8.data(), n8.size() * 4));
+    if (!gb && !n8.empty() && node_stride != 8u) HIPCHECK(c, m.nodes8.alloc_copy(n8.data(), n8.size() * 4));
     if (!c->hs.abvh.nodes4.empty()) {
-        HIPCHECK(c, upload(&c->d_abvh_nodes, c->hs.abvh.nodes4.data(), c->hs.abvh.nodes4.size() * 4));
-        HIPCHECK(c, upload(&c->d_abvh_order, c->hs.abvh.order.data(), c->hs.abvh.order.size() * 4));
+        HIPCHECK(c, m.abvh_nodes.alloc_copy(c->hs.abvh.nodes4.data(), c->hs.abvh.nodes4.size() * 4));
+        HIPCHECK(c, m.abvh_order.alloc_copy(c->hs.abvh.order.data(), c->hs.abvh.order.size() * 4));
     }
     if (!c->hs.dev_insts.empty()) {
-        HIPCHECK(c, upload(&c->d_insts, c->hs.dev_insts.data(), c->hs.dev_insts.size() * sizeof(DevInstance)));
-        HIPCHECK(c, upload(&c->d_tlas_inst, c->hs.tlas_inst.data(), c->hs.tlas_inst.size() * 4));
+        HIPCHECK(c, m.insts.alloc_copy(c->hs.dev_insts.data(), c->hs.dev_insts.size() * sizeof(DevInstance)));
+        HIPCHECK(c, m.tlas_inst.alloc_copy(c->hs.tlas_inst.data(), c->hs.tlas_inst.size() * 4));
     }
-    HIPCHECK(c, upload(&c->d_lights, c->hs.lights.data(), c->hs.lights.size() * 4));
-    HIPCHECK(c, upload(&c->d_prim_light, c->hs.prim_light.data(), c->hs.prim_light.size() * 4));
+    HIPCHECK(c, m.lights.alloc_copy(c->hs.lights.data(), c->hs.lights.size() * 4));
+    HIPCHECK(c, m.prim_light.alloc_copy(c->hs.prim_light.data(), c->hs.prim_light.size() * 4));
     if (!gb) {
-        HIPCHECK(c, upload(&c->d_tris, c->hs.tri_records.data(), c->hs.tri_records.size() * 4));
-        HIPCHECK(c, upload(&c->d_nrms, c->hs.nrm_records.data(), c->hs.nrm_records.size() * 4));
+        HIPCHECK(c, m.tris.alloc_copy(c->hs.tri_records.data(), c->hs.tri_records.size() * 4));
+        HIPCHECK(c, m.nrms.alloc_copy(c->hs.nrm_records.data(), c->hs.nrm_records.size() * 4));
     }
     if (mesh_lights_on(c)) {
         const int rc_ml = upload_mesh_lights(c);
@@ -1217,7 +1151,7 @@ int upload_scene(PrtContext* c, PrtGpuBvh* gb) {
 // scene compiler works with (prt_scene.h PrtDeviceBuilder); with `keep` the device arrays stay allocated and are handed
 // to the caller.  The builder's time is added to *ms.
 int device_build(PrtContext* c, const float* verts, const float* norms, const uint32_t* tri_mat, uint32_t n, uint32_t n_prims,
-                 std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, PrtGpuBvh* keep, float leaf_cost, double* ms,
+                 std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, BuiltTree* keep, float leaf_cost, double* ms,
                  int builder) {
     float cmin[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, cmax[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (size_t t = 0; t < (size_t)n; ++t)
@@ -1230,49 +1164,41 @@ int device_build(PrtContext* c, const float* verts, const float* norms, const ui
         }
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    void *dv = nullptr, *dn = nullptr, *dm = nullptr;
-    auto drop = [&]() {
-        (void)hipFree(dv);
-        (void)hipFree(dn);
-        (void)hipFree(dm);
-    };
-    hipError_t e = hipMalloc(&dv, 36 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&dn, 36 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&dm, 4 * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpy(dv, verts, 36 * (size_t)n, hipMemcpyHostToDevice);
-    // (fills on the stream the builder's kernels run on: c->stream is non-blocking, nothing orders it after the null stream)
-    if (e == hipSuccess) e = norms ? hipMemcpy(dn, norms, 36 * (size_t)n, hipMemcpyHostToDevice) : hipMemsetAsync(dn, 0, 36 * (size_t)n, c->stream);
-    if (e == hipSuccess) e = tri_mat ? hipMemcpy(dm, tri_mat, 4 * (size_t)n, hipMemcpyHostToDevice) : hipMemsetAsync(dm, 0, 4 * (size_t)n, c->stream);
-    if (e != hipSuccess) {
-        drop();
-        return fail(c, PRT_ERR_HIP, "device-side BVH build: %s", hipGetErrorString(e));
-    }
     PrtGpuBvh gb{};
-    const auto t0 = std::chrono::steady_clock::now();
-    // gpu_build 1: the quality builder (PLOC + optimal collapse); 2: the Morton octree (fastest build, slower to traverse)
-    const int brc = builder == 2
-                        ? prt_gpu_bvh8_build(c->stream, (const float*)dv, (const float*)dn, (const uint32_t*)dm, n, n_prims, cmin, cmax, &gb)
-                        : prt_gpu_bvh8_build_ploc(c->stream, (const float*)dv, (const float*)dn, (const uint32_t*)dm, n, n_prims, cmin, cmax, &gb, leaf_cost);
-    *ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    drop();
+    int brc = 0;
+    {  // the builder's inputs: gone before anything is read back
+        DevBuf dv, dn, dm;
+        hipError_t e = (hipError_t)dv.ensure(36 * (size_t)n);
+        if (e == hipSuccess) e = (hipError_t)dn.ensure(36 * (size_t)n);
+        if (e == hipSuccess) e = (hipError_t)dm.ensure(4 * (size_t)n);
+        if (e == hipSuccess) e = hipMemcpy(dv.p, verts, 36 * (size_t)n, hipMemcpyHostToDevice);
+        // (fills on the stream the builder's kernels run on: c->stream is non-blocking, nothing orders it after the null stream)
+        if (e == hipSuccess) e = norms ? hipMemcpy(dn.p, norms, 36 * (size_t)n, hipMemcpyHostToDevice) : hipMemsetAsync(dn.p, 0, 36 * (size_t)n, c->stream);
+        if (e == hipSuccess) e = tri_mat ? hipMemcpy(dm.p, tri_mat, 4 * (size_t)n, hipMemcpyHostToDevice) : hipMemsetAsync(dm.p, 0, 4 * (size_t)n, c->stream);
+        if (e != hipSuccess) return fail(c, PRT_ERR_HIP, "device-side BVH build: %s", hipGetErrorString(e));
+        const auto t0 = std::chrono::steady_clock::now();
+        // gpu_build 1: the quality builder (PLOC + optimal collapse); 2: the Morton octree (fastest build, slower to traverse)
+        brc = builder == 2 ? prt_gpu_bvh8_build(c->stream, dv.as<float>(), dn.as<float>(), dm.as<uint32_t>(), n, n_prims, cmin, cmax, &gb)
+                           : prt_gpu_bvh8_build_ploc(c->stream, dv.as<float>(), dn.as<float>(), dm.as<uint32_t>(), n, n_prims, cmin, cmax, &gb, leaf_cost);
+        *ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
     if (brc < 0) {  // the builder itself gave up (too many passes / levels for this input): the caller may take the host builder
         (void)fail(c, PRT_ERR_INVALID, "device-side BVH build gave up (%d)", brc);
         return kPrtDeviceBuildGaveUp;
     }
     if (brc) return fail(c, PRT_ERR_HIP, "device-side BVH build failed (%d)", brc);
+    BuiltTree bt;  // the builder's arrays are ours from here on
+    bt.nodes8.adopt(gb.d_nodes8, 80 * (size_t)gb.n_nodes);
+    bt.tris.adopt(gb.d_tris, 48 * (size_t)n);
+    bt.nrms.adopt(gb.d_nrms, 48 * (size_t)n);
+    bt.n_nodes = gb.n_nodes;
     nodes8.resize(20 * (size_t)gb.n_nodes);
     depth = gb.depth;
-    e = hipMemcpy(nodes8.data(), gb.d_nodes8, nodes8.size() * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(tri_rec, gb.d_tris, 48 * (size_t)n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && nrm_rec) e = hipMemcpy(nrm_rec, gb.d_nrms, 48 * (size_t)n, hipMemcpyDeviceToHost);
-    if (keep && e == hipSuccess) {
-        *keep = gb;
-    } else {
-        (void)hipFree(gb.d_nodes8);
-        (void)hipFree(gb.d_tris);
-        (void)hipFree(gb.d_nrms);
-    }
+    hipError_t e = hipMemcpy(nodes8.data(), bt.nodes8.p, nodes8.size() * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(tri_rec, bt.tris.p, 48 * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && nrm_rec) e = hipMemcpy(nrm_rec, bt.nrms.p, 48 * (size_t)n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, PRT_ERR_HIP, "device-side BVH build: %s", hipGetErrorString(e));
+    if (keep) *keep = std::move(bt);
     return PRT_OK;
 }
 
@@ -1290,16 +1216,16 @@ int read_local_moments(PrtContext* c, std::vector<float>* film, std::vector<floa
     int rc = need_device(c);
     if (rc) return rc;
     if (!c->has_film) return fail(c, PRT_ERR_INVALID, "prt_set_film has not been called");
-    if (!c->film_stats || !c->d_film_stat) return fail(c, PRT_ERR_INVALID, "film statistics are off (prt_set_film_statistics)");
+    if (!c->film_stats || !c->film.stat.p) return fail(c, PRT_ERR_INVALID, "film statistics are off (prt_set_film_statistics)");
     const size_t n = c->tm.n_pix_local;
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     if (film) {
         film->assign(4 * n, 0.0f);
-        if (n) HIPCHECK(c, hipMemcpy(film->data(), c->d_film_local, n * sizeof(float4), hipMemcpyDeviceToHost));
+        if (n) HIPCHECK(c, hipMemcpy(film->data(), c->film.local.as<float4>(), n * sizeof(float4), hipMemcpyDeviceToHost));
     }
     stat->assign(2 * n, 0.0f);
-    if (n) HIPCHECK(c, hipMemcpy(stat->data(), c->d_film_stat, n * sizeof(float2), hipMemcpyDeviceToHost));
+    if (n) HIPCHECK(c, hipMemcpy(stat->data(), c->film.stat.as<float2>(), n * sizeof(float2), hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 
@@ -1342,45 +1268,18 @@ int prt_create(int device_id, PrtContext** out) {
 
 void prt_destroy(PrtContext* c) {
     if (!c) return;
-    if (c->has_device) {
+    if (c->has_device) {  // (a host-only context owns nothing on a device: its destructor makes no HIP call)
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
-        free_scene(c);
-        free_env(c);
-        free_tex(c);
-        free_path_state(c);
-        free_primary_state(c);
-        free_light_state(c);
-        free_dev(c->d_light_stats);
-        free_dev(c->d_film_local);
-        free_dev(c->d_film_stat);
-        free_dev(c->d_tile_sel);
-        if (c->h_tile_count) (void)hipHostFree(c->h_tile_count);
-        free_dev(c->d_counts);
-        free_dev(c->d_ray_stats);
-        if (c->h_flag) (void)hipHostFree(c->h_flag);
-        free_dev(c->d_trav_stats);
-        if (c->h_counts) {
-            (void)hipHostFree(c->h_counts);
-            for (hipEvent_t& e : c->ev_counts) (void)hipEventDestroy(e);
-            for (hipEvent_t& e : c->ev_prod) (void)hipEventDestroy(e);
-            if (c->count_stream) (void)hipStreamDestroy(c->count_stream);
-        }
-        free_dev(c->d_work);
-        free_dev(c->d_pix);
-        free_dev(c->d_sort);
-        for (DevBuf* b : {&c->spill, &c->scratch, &c->feat, &c->guide, &c->samp, &c->dn, &c->tp, &c->tp_mt, &c->tpa, &c->bake}) b->release();
-        for (EventPair& ep : c->events) {
-            (void)hipEventDestroy(ep.a);
-            (void)hipEventDestroy(ep.b);
-        }
-        for (EventPair& ep : c->event_pool) {
-            (void)hipEventDestroy(ep.a);
-            (void)hipEventDestroy(ep.b);
-        }
+        if (c->count_stream) (void)hipStreamDestroy(c->count_stream);
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     }
-    delete c;
+    delete c;  // every allocation, pinned word and event goes with its owner (prt_devmem.h)
+}
+
+void prt_device_memory_info(uint64_t* live_bytes, uint64_t* alloc_calls) {
+    if (live_bytes) *live_bytes = g_live_bytes.load();
+    if (alloc_calls) *alloc_calls = g_alloc_calls.load();
 }
 
 const char* prt_last_error(const PrtContext* c) { return c ? c->err.c_str() : "null context"; }
@@ -1424,7 +1323,7 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
     // device-side build (prt_set_param("gpu_build", 1 | 2)) on a context with a device: world meshes, placed copies and the
     // top-level tree.  The world meshes' device arrays (`keep`) stay with this layer: they become the scene's arrays below,
     // or go if the compiler did not take that tree after all (deeper than the kernels' stacks: the host builder's stands)
-    PrtGpuBvh gb{};
+    BuiltTree gb;
     if (c->gpu_build && c->has_device)
         opt.device_build = [&](const float* verts, const float* norms, const uint32_t* tri_mat, uint32_t n, uint32_t n_prims, float leaf_cost,
                                bool keep, std::vector<uint32_t>& nodes8, uint32_t& depth, float* tri_rec, float* nrm_rec, double* ms, std::string* err) {
@@ -1434,12 +1333,8 @@ int prt_set_scene(PrtContext* c, const PrtSceneDesc* s) {
             return brc;
         };
     rc = prt_compile_scene(s, opt, &hs, &c->err);
-    const bool use_gb = !rc && gb.d_nodes8 && hs.scene_device_built;
-    if (!use_gb) {
-        free_dev(gb.d_nodes8);
-        free_dev(gb.d_tris);
-        free_dev(gb.d_nrms);
-    }
+    const bool use_gb = !rc && gb.nodes8.p && hs.scene_device_built;
+    if (!use_gb) gb = BuiltTree();
     if (rc) return rc;
     c->hs = std::move(hs);
     c->hs.builder = opt.device_build ? (uint32_t)c->gpu_build : 0u;
@@ -1489,8 +1384,8 @@ int prt_clone_scene(PrtContext* dst, const PrtContext* src) {
 static void commit_refit(PrtContext* c, const float root_box[6], float extent) {
     // the binary and 4-wide trees (A/B kernels, overflow fallback of deep host-built trees) still describe the OLD
     // geometry: they go, and the instance selection falls to the 8-wide kernels that need neither (prt_plan_walk)
-    free_dev(c->d_nodes);
-    free_dev(c->d_nodes4);
+    c->scene.nodes = DevBuf();
+    c->scene.nodes4 = DevBuf();
     c->dsc.nodes = nullptr;
     c->dsc.nodes4 = nullptr;
     c->hs.bvh.nodes.clear();
@@ -1572,36 +1467,38 @@ int prt_refit_meshes(PrtContext* c, const PrtMesh* meshes, uint32_t n_meshes) {
         return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: malformed tree (node %u)", bad - 1u);
     if (level_nodes.size() != n_nodes) return fail(c, PRT_ERR_INVALID, "prt_refit_meshes: %zu of %u nodes reachable from the root", level_nodes.size(), n_nodes);
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    void *dv = nullptr, *dn = nullptr;
-    hipError_t e = hipMalloc(&dv, 36 * (size_t)n_tris);
-    if (e == hipSuccess) e = hipMalloc(&dn, 36 * (size_t)n_tris);
-    if (e == hipSuccess) e = hipMemcpy(dv, verts.data(), 36 * (size_t)n_tris, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dn, norms.data(), 36 * (size_t)n_tris, hipMemcpyHostToDevice);
-    tally.h2d += 72 * (uint64_t)n_tris;
+    const SceneMem& m = c->scene;
     float root_box[6] = {0, 0, 0, 0, 0, 0};
     int brc = 0;
-    if (e == hipSuccess) {
-        const auto t0 = std::chrono::steady_clock::now();
-        brc = prt_gpu_bvh8_refit(c->stream, (uint32_t*)c->d_nodes8, c->dsc.node_stride * 4u, n_nodes, level_nodes.data(), level_start.data(),
-                                 (uint32_t)level_start.size() - 1u, (const float*)dv, (const float*)dn, (uint32_t)n_tris, c->dsc.n_prims,
-                                 (float4*)c->d_tris, (float4*)c->d_nrms, root_box, &tally);
-        c->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    hipError_t e;
+    {  // the new vertices and normals on the device: gone before the host copies are read back
+        DevBuf dv, dn;
+        e = (hipError_t)dv.ensure(36 * (size_t)n_tris);
+        if (e == hipSuccess) e = (hipError_t)dn.ensure(36 * (size_t)n_tris);
+        if (e == hipSuccess) e = hipMemcpy(dv.p, verts.data(), 36 * (size_t)n_tris, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dn.p, norms.data(), 36 * (size_t)n_tris, hipMemcpyHostToDevice);
+        tally.h2d += 72 * (uint64_t)n_tris;
+        if (e == hipSuccess) {
+            const auto t0 = std::chrono::steady_clock::now();
+            brc = prt_gpu_bvh8_refit(c->stream, m.nodes8.as<uint32_t>(), c->dsc.node_stride * 4u, n_nodes, level_nodes.data(), level_start.data(),
+                                     (uint32_t)level_start.size() - 1u, dv.as<float>(), dn.as<float>(), (uint32_t)n_tris, c->dsc.n_prims,
+                                     m.tris.as<float4>(), m.nrms.as<float4>(), root_box, &tally);
+            c->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
     }
-    (void)hipFree(dv);
-    (void)hipFree(dn);
     if (e != hipSuccess || brc) {
         c->has_scene = false;  // the device arrays may be half rewritten
         return fail(c, PRT_ERR_HIP, "prt_refit_meshes: %s (%d)", e != hipSuccess ? hipGetErrorString(e) : "refit failed", brc);
     }
     // host copies (prt_bvh_read8 / prt_bvh_read, prt_clone_scene) follow the device
-    e = hipMemcpy2D(c->hs.bvh.nodes8.data(), 80, c->d_nodes8, (size_t)c->dsc.node_stride * 16, 80, n_nodes, hipMemcpyDeviceToHost);
+    e = hipMemcpy2D(c->hs.bvh.nodes8.data(), 80, c->scene.nodes8.p, (size_t)c->dsc.node_stride * 16, 80, n_nodes, hipMemcpyDeviceToHost);
     tally.d2h += 80 * (uint64_t)n_nodes;
     if (e == hipSuccess && c->hs.tri_records.size() == 12 * (size_t)n_tris) {
-        e = hipMemcpy(c->hs.tri_records.data(), c->d_tris, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
+        e = hipMemcpy(c->hs.tri_records.data(), c->scene.tris.p, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
         tally.d2h += 48 * (uint64_t)n_tris;
     }
     if (e == hipSuccess && c->hs.nrm_records.size() == 12 * (size_t)n_tris) {
-        e = hipMemcpy(c->hs.nrm_records.data(), c->d_nrms, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
+        e = hipMemcpy(c->hs.nrm_records.data(), c->scene.nrms.p, 48 * (size_t)n_tris, hipMemcpyDeviceToHost);
         tally.d2h += 48 * (uint64_t)n_tris;
     }
     HIPCHECK(c, e);
@@ -1626,7 +1523,7 @@ static int ensure_refit_keep(PrtContext* c, PrtCopyTally* tally) {
     ws.add(&rk.d_corner, n_corner).add(&rk.d_csr_start, n_vert + 1).add(&rk.d_csr_corner, n_corner).add(&rk.d_light_tris, n_light);
     ws.add(&rk.d_valid, 4).add(&rk.d_normals, 3 * n_vert).add(&rk.d_light_verts, 9 * n_light);
     ws.add(&rk.scratch.cbox, 48 * n_nodes).add(&rk.scratch.nbox, 6 * n_nodes).add(&rk.scratch.counters, 4).add(&rk.scratch.level_nodes, n_nodes);
-    if ((rc = commit(c, ws, c->rk_buf))) {
+    if ((rc = commit(c, ws, c->scene.refit_keep))) {
         rk = PrtContext::RefitKeep();
         return rc;
     }
@@ -1714,9 +1611,9 @@ int prt_refit_meshes_device(PrtContext* c, const PrtMeshDeviceArrays* meshes, ui
     int brc = n_computed ? prt_gpu_mesh_normals(c->stream, in, nout.data(), rk.d_corner, rk.d_csr_start, rk.d_csr_corner) : 0;
     if (!brc) brc = prt_gpu_light_gather(c->stream, in, rk.d_corner, rk.d_light_tris, rk.n_light_tris, rk.d_light_verts);
     if (!brc)
-        brc = prt_gpu_bvh8_refit_indexed(c->stream, (uint32_t*)c->d_nodes8, c->dsc.node_stride * 4u, rk.n_nodes, rk.level_start.data(),
+        brc = prt_gpu_bvh8_refit_indexed(c->stream, c->scene.nodes8.as<uint32_t>(), c->dsc.node_stride * 4u, rk.n_nodes, rk.level_start.data(),
                                          (uint32_t)rk.level_start.size() - 1u, in, nrm.data(), rk.d_corner, (uint32_t)n_tris, c->dsc.n_prims,
-                                         (float4*)c->d_tris, (float4*)c->d_nrms, rk.scratch, root_box, &tally);
+                                         c->scene.tris.as<float4>(), c->scene.nrms.as<float4>(), rk.scratch, root_box, &tally);
     c->refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     std::vector<float> packed(9 * (size_t)rk.n_light_tris);
     if (!brc && !packed.empty()) {
@@ -1815,29 +1712,14 @@ int prt_set_instance_transforms(PrtContext* c, const PrtInstance* instances, uin
         memcpy(&mesh_box[6 * (size_t)m + 3], hs.placed_meshes[m].mx, 12);
     }
     memcpy(&mesh_box[6 * (size_t)n_meshes], hs.world_box.data(), 24);
-    void *d_xf = nullptr, *d_box = nullptr, *d_im = nullptr, *d_recs = nullptr, *d_new = nullptr;
-    auto drop = [&]() {
-        (void)hipFree(d_xf);
-        (void)hipFree(d_box);
-        (void)hipFree(d_im);
-        (void)hipFree(d_recs);
-    };
-    auto up_to = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess && src && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
-    hipError_t e = up_to(&d_xf, xf.data(), xf.size() * 4);
-    if (e == hipSuccess) e = up_to(&d_box, mesh_box.data(), mesh_box.size() * 4);
-    if (e == hipSuccess) e = up_to(&d_im, inst_mesh.data(), inst_mesh.size() * 4);
-    if (e == hipSuccess) e = up_to(&d_recs, nullptr, 48 * (size_t)n_total);
-    if (e != hipSuccess) {  // (nothing of the scene written yet)
-        drop();
-        return fail(c, PRT_ERR_HIP, "prt_set_instance_transforms: %s", hipGetErrorString(e));
-    }
+    SceneMem& m = c->scene;
+    DevBuf d_xf, d_box, d_im, d_recs, d_new;  // (freed when the function returns)
+    hipError_t e = (hipError_t)d_xf.alloc_copy(xf.data(), xf.size() * 4);
+    if (e == hipSuccess) e = (hipError_t)d_box.alloc_copy(mesh_box.data(), mesh_box.size() * 4);
+    if (e == hipSuccess) e = (hipError_t)d_im.alloc_copy(inst_mesh.data(), inst_mesh.size() * 4);
+    if (e == hipSuccess) e = (hipError_t)d_recs.ensure(std::max<size_t>(48 * (size_t)n_total, 16));
+    if (e != hipSuccess) return fail(c, PRT_ERR_HIP, "prt_set_instance_transforms: %s", hipGetErrorString(e));  // (nothing of the scene written yet)
     auto broken = [&](hipError_t he, int brc) {
-        drop();
-        (void)hipFree(d_new);
         c->has_scene = false;  // the device arrays may be half rewritten
         return fail(c, PRT_ERR_HIP, "prt_set_instance_transforms: %s (%d)", he != hipSuccess ? hipGetErrorString(he) : "device pass failed", brc);
     };
@@ -1846,23 +1728,21 @@ int prt_set_instance_transforms(PrtContext* c, const PrtInstance* instances, uin
     if (mode == (uint32_t)PRT_INSTANCES_REFIT) {
         std::vector<uint32_t> level_nodes, level_start;
         if (prt_tree_levels(hs.nodes8_all, old_top, level_nodes, level_start) || level_nodes.size() != old_top) {
-            drop();
             return fail(c, PRT_ERR_INVALID, "prt_set_instance_transforms: malformed top-level tree");
         }
-        int brc = prt_gpu_place_copies(c->stream, (const float*)d_xf, (const float*)d_box, (const uint32_t*)d_im, (const uint32_t*)c->d_tlas_inst,
-                                       n_total, n_world, c->d_insts, (float4*)d_recs);
+        int brc = prt_gpu_place_copies(c->stream, d_xf.as<float>(), d_box.as<float>(), d_im.as<uint32_t>(), m.tlas_inst.as<uint32_t>(),
+                                       n_total, n_world, m.insts.p, d_recs.as<float4>());
         float root_box[6];
         if (!brc)
-            brc = prt_gpu_bvh8_refit_top(c->stream, (uint32_t*)c->d_nodes8, stride * 4u, old_top, level_nodes.data(), level_start.data(),
-                                         (uint32_t)level_start.size() - 1u, (const float4*)d_recs, root_box);
+            brc = prt_gpu_bvh8_refit_top(c->stream, m.nodes8.as<uint32_t>(), stride * 4u, old_top, level_nodes.data(), level_start.data(),
+                                         (uint32_t)level_start.size() - 1u, d_recs.as<float4>(), root_box);
         if (brc && brc != -6) return broken(hipSuccess, brc);
         if (!brc) {
             prt_commit_instances(&hs, up, instances);
             // the host copies follow the device: the re-quantized top level and the instance table
-            e = hipMemcpy2D(hs.nodes8_all.data(), 80, c->d_nodes8, node_bytes, 80, old_top, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(hs.dev_insts.data(), c->d_insts, (size_t)n_total * sizeof(DevInstance), hipMemcpyDeviceToHost);
+            e = hipMemcpy2D(hs.nodes8_all.data(), 80, c->scene.nodes8.p, node_bytes, 80, old_top, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(hs.dev_insts.data(), c->scene.insts.p, (size_t)n_total * sizeof(DevInstance), hipMemcpyDeviceToHost);
             if (e != hipSuccess) return broken(e, 0);
-            drop();
             fill_dev_scene(c, stride, hs.bvh_info.depth8);
             if (mesh_lights_on(c) && (rc = upload_mesh_lights(c))) return rc;
             return done(PRT_INSTANCES_REFIT);
@@ -1872,48 +1752,40 @@ int prt_set_instance_transforms(PrtContext* c, const PrtInstance* instances, uin
     rc = prt_build_top_level(opt, hs, &up, &hs.gpu_build_ms, &c->err);
     if (rc) {
         if (top_dirty) {  // the scene stays what it was: the refit's half-written top level and instances go back
-            e = hipMemcpy2D(c->d_nodes8, node_bytes, hs.nodes8_all.data(), 80, 80, old_top, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(c->d_insts, hs.dev_insts.data(), (size_t)n_total * sizeof(DevInstance), hipMemcpyHostToDevice);
+            e = hipMemcpy2D(c->scene.nodes8.p, node_bytes, hs.nodes8_all.data(), 80, 80, old_top, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(c->scene.insts.p, hs.dev_insts.data(), (size_t)n_total * sizeof(DevInstance), hipMemcpyHostToDevice);
             if (e != hipSuccess) return broken(e, 0);
         }
-        drop();
         return rc;
     }
     const uint32_t new_top = (uint32_t)(up.top_nodes8.size() / 20), delta = new_top - old_top, new_all = n_all - old_top + new_top;
-    uint32_t* d_n8 = (uint32_t*)c->d_nodes8;
+    uint32_t* d_n8 = m.nodes8.as<uint32_t>();
     if (delta) {  // the mesh trees move behind the new top level, device to device
-        e = hipMalloc(&d_new, node_bytes * new_all);
-        if (e == hipSuccess && stride != 5u) e = hipMemset(d_new, 0, node_bytes * new_top);
+        e = (hipError_t)d_new.ensure(node_bytes * new_all);
+        if (e == hipSuccess && stride != 5u) e = hipMemset(d_new.p, 0, node_bytes * new_top);
         if (e == hipSuccess)
-            e = hipMemcpy((char*)d_new + node_bytes * new_top, (const char*)c->d_nodes8 + node_bytes * old_top, node_bytes * (n_all - old_top),
+            e = hipMemcpy(d_new.as<char>() + node_bytes * new_top, m.nodes8.as<char>() + node_bytes * old_top, node_bytes * (n_all - old_top),
                           hipMemcpyDeviceToDevice);
         if (e != hipSuccess) {  // (the scene is still whole unless the refit wrote to it)
             if (top_dirty) return broken(e, 0);
-            drop();
-            (void)hipFree(d_new);
             return fail(c, PRT_ERR_HIP, "prt_set_instance_transforms: %s", hipGetErrorString(e));
         }
-        d_n8 = (uint32_t*)d_new;
+        d_n8 = d_new.as<uint32_t>();
     }
     e = hipMemcpy2D(d_n8, node_bytes, up.top_nodes8.data(), 80, 80, new_top, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->d_tlas_inst, up.top_order.data(), (size_t)n_total * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->scene.tlas_inst.p, up.top_order.data(), (size_t)n_total * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();  // (copies on the null stream return early; the kernels run on c->stream)
     if (e != hipSuccess) return broken(e, 0);
-    int brc = prt_gpu_place_copies(c->stream, (const float*)d_xf, (const float*)d_box, (const uint32_t*)d_im, (const uint32_t*)c->d_tlas_inst, n_total,
-                                   n_world, c->d_insts, (float4*)d_recs);
-    if (!brc && delta) brc = prt_gpu_rebase(c->stream, d_n8, stride * 4u, new_top, new_all, c->d_insts, n_total, delta);
+    int brc = prt_gpu_place_copies(c->stream, d_xf.as<float>(), d_box.as<float>(), d_im.as<uint32_t>(), m.tlas_inst.as<uint32_t>(), n_total,
+                                   n_world, m.insts.p, d_recs.as<float4>());
+    if (!brc && delta) brc = prt_gpu_rebase(c->stream, d_n8, stride * 4u, new_top, new_all, m.insts.p, n_total, delta);
     e = hipStreamSynchronize(c->stream);
     if (brc || e != hipSuccess) return broken(e, brc);
-    if (delta) {
-        (void)hipFree(c->d_nodes8);
-        c->d_nodes8 = d_new;
-        d_new = nullptr;
-    }
+    if (delta) m.nodes8 = std::move(d_new);
     prt_commit_top_level(&hs, up);
     prt_commit_instances(&hs, up, instances);
-    e = hipMemcpy(hs.dev_insts.data(), c->d_insts, (size_t)n_total * sizeof(DevInstance), hipMemcpyDeviceToHost);
+    e = hipMemcpy(hs.dev_insts.data(), c->scene.insts.p, (size_t)n_total * sizeof(DevInstance), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return broken(e, 0);
-    drop();
     fill_dev_scene(c, stride, hs.bvh_info.depth8);
     if (mesh_lights_on(c) && (rc = upload_mesh_lights(c))) return rc;
     return done(PRT_INSTANCES_REBUILD);
@@ -2012,14 +1884,14 @@ int prt_set_film(PrtContext* c, uint32_t width, uint32_t height, uint32_t rank, 
     }
     c->valid_local = valid;
     c->has_film = true;
-    c->pix_records_blank = false;  // (the records' place in d_pix depends on the pixel count)
+    c->pix_records_blank = false;  // (the records' place in wk.pix depends on the pixel count)
     if (!c->has_device) return PRT_OK;
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    free_dev(c->d_film_local);
-    free_dev(c->d_film_stat);
-    HIPCHECK(c, hipMalloc((void**)&c->d_film_local, std::max<size_t>((size_t)tm.stride, 64) * sizeof(float4)));
-    if (c->film_stats) HIPCHECK(c, hipMalloc((void**)&c->d_film_stat, std::max<size_t>((size_t)tm.stride, 64) * sizeof(float2)));
+    c->film.local = DevBuf();
+    c->film.stat = DevBuf();
+    HIPCHECK(c, c->film.local.ensure(std::max<size_t>((size_t)tm.stride, 64) * sizeof(float4)));
+    if (c->film_stats) HIPCHECK(c, c->film.stat.ensure(std::max<size_t>((size_t)tm.stride, 64) * sizeof(float2)));
     int rc = ensure_counters(c);
     if (rc) return rc;
     return prt_film_clear(c);
@@ -2029,9 +1901,9 @@ int prt_film_clear(PrtContext* c) {
     int rc = need_device(c);
     if (rc) return rc;
     if (!c->has_film) return fail(c, PRT_ERR_INVALID, "prt_set_film has not been called");
-    HIPCHECK(c, hipMemsetAsync(c->d_film_local, 0, std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float4), c->stream));
-    if (c->d_film_stat)
-        HIPCHECK(c, hipMemsetAsync(c->d_film_stat, 0, std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float2), c->stream));
+    HIPCHECK(c, hipMemsetAsync(c->film.local.p, 0, std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float4), c->stream));
+    if (c->film.stat.p)
+        HIPCHECK(c, hipMemsetAsync(c->film.stat.p, 0, std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float2), c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return PRT_OK;
 }
@@ -2046,9 +1918,9 @@ int prt_set_film_statistics(PrtContext* c, int on) {
     if (!c->has_device) return PRT_OK;  // host-only: the setting is all there is
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    free_dev(c->d_film_stat);
+    c->film.stat = DevBuf();
     if (!c->has_film) return PRT_OK;  // (prt_set_film allocates the moments with the film)
-    if (want) HIPCHECK(c, hipMalloc((void**)&c->d_film_stat, std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float2)));
+    if (want) HIPCHECK(c, c->film.stat.ensure(std::max<size_t>((size_t)c->tm.stride, 64) * sizeof(float2)));
     return prt_film_clear(c);
 }
 
@@ -2091,7 +1963,7 @@ int prt_set_light_sources(PrtContext* c, uint32_t mask) {
     if (mesh_lights_on(c)) return upload_mesh_lights(c);
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    free_mesh_lights(c);
+    c->ml = MeshLightMem();
     return PRT_OK;
 }
 
@@ -2351,12 +2223,12 @@ int prt_get_light_stats(PrtContext* c, PrtLightStats* out) {
     out->n_lights = light_set_size(c);
     out->n_emitters_unsampled = mesh_lights_on(c) ? c->hs.ml.n_emitters_unsampled : c->hs.n_emitters_unsampled;
     if (clusters_on(c)) out->n_emitters_unsampled += c->hs.lc.n_empty_inner;
-    if (!c->has_device || !c->d_light_stats) return PRT_OK;
+    if (!c->has_device || !c->wk.light_stats.p) return PRT_OK;
     int rc = need_device(c);
     if (rc) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     std::vector<unsigned long long> h(kLightStatWords);
-    HIPCHECK(c, hipMemcpy(h.data(), c->d_light_stats, kLightStatWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHECK(c, hipMemcpy(h.data(), c->wk.light_stats.p, kLightStatWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (size_t sl = 0; sl < PRT_RAY_STAT_SLOTS; ++sl) {
         out->shadow_rays += h[2 * sl];
         out->shadow_occluded += h[2 * sl + 1];
@@ -2384,16 +2256,16 @@ int prt_synchronize(PrtContext* c) {
     if (rc) return rc;
     // (the flag's copy is enqueued behind the kernels and ONE wait covers both: a blocking copy after the wait was a second
     // host round trip, ~30 us of a 0.9 ms one-sample call)
-    if (c->d_work && !c->h_flag) {
-        HIPCHECK(c, hipHostMalloc((void**)&c->h_flag, 64, hipHostMallocDefault));
-        *c->h_flag = 0u;
+    if (c->wk.work.p && !c->wk.flag.p) {
+        HIPCHECK(c, c->wk.flag.alloc(64));
+        *c->wk.flag.as<uint32_t>() = 0u;
     }
-    if (c->d_work) HIPCHECK(c, hipMemcpyAsync(c->h_flag, c->d_work + 256, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (c->wk.work.p) HIPCHECK(c, hipMemcpyAsync(c->wk.flag.p, c->wk.work.as<uint32_t>() + 256, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    if (c->d_work) {  // watchdog flag of the persistent traversal kernel
-        const uint32_t w = *c->h_flag;
+    if (c->wk.work.p) {  // watchdog flag of the persistent traversal kernel
+        const uint32_t w = *c->wk.flag.as<uint32_t>();
         if (w) {
-            HIPCHECK(c, hipMemset(c->d_work, 0, 2052));
+            HIPCHECK(c, hipMemset(c->wk.work.p, 0, 2052));
             return fail(c, PRT_ERR_HIP, w & 2u ? "traversal stack-overflow list full" : "traversal watchdog tripped: a wave exceeded its iteration cap");
         }
     }
@@ -2410,7 +2282,7 @@ int prt_film_local(PrtContext* c, void** d_ptr, uint64_t* n_floats) {
     int rc = need_device(c);
     if (rc) return rc;
     if (!c->has_film) return fail(c, PRT_ERR_INVALID, "prt_set_film has not been called");
-    if (d_ptr) *d_ptr = c->d_film_local;
+    if (d_ptr) *d_ptr = c->film.local.as<float4>();
     if (n_floats) *n_floats = (uint64_t)c->tm.stride * 4;
     return PRT_OK;
 }
@@ -2449,11 +2321,11 @@ static int resolve_own(PrtContext* c, float** d_rgb, float** d_w, uint8_t** d_rg
     const size_t off_rgb = (gathered + 255) & ~(size_t)255;
     const size_t off_w = off_rgb + ((npix * 12 + 255) & ~(size_t)255);
     const size_t off_b = off_w + ((npix * 4 + 255) & ~(size_t)255);
-    int rc = c->scratch.ensure(c, off_b + npix * 4);
+    int rc = ensure(c, c->scratch, off_b + npix * 4);
     if (rc) return rc;
     char* base = (char*)c->scratch.p;
     HIPCHECK(c, hipMemsetAsync(base, 0, gathered, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(base + (size_t)tm.rank * tm.stride * sizeof(float4), c->d_film_local,
+    HIPCHECK(c, hipMemcpyAsync(base + (size_t)tm.rank * tm.stride * sizeof(float4), c->film.local.as<float4>(),
                                (size_t)tm.stride * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     *d_rgb = (float*)(base + off_rgb);
     *d_w = (float*)(base + off_w);
@@ -2533,15 +2405,14 @@ int prt_render_adaptive(PrtContext* c, const PrtAdaptive* cfg, uint32_t max_dept
     info.tiles_local = n_tiles;
     if (out) *out = info;
     // count words, flags and two lists of n_tiles entries each; the pinned words the count is read into
-    if (c->tile_sel_entries < n_tiles || !c->d_tile_sel) {
-        free_dev(c->d_tile_sel);
+    if (c->tile_sel_entries < n_tiles || !c->film.tile_sel.p) {
         c->tile_sel_entries = 0;
-        HIPCHECK(c, hipMalloc((void**)&c->d_tile_sel, (16 + 3 * (size_t)std::max(n_tiles, 1u)) * sizeof(uint32_t)));
+        HIPCHECK(c, c->film.tile_sel.ensure((16 + 3 * (size_t)std::max(n_tiles, 1u)) * sizeof(uint32_t)));
         c->tile_sel_entries = std::max(n_tiles, 1u);
     }
-    if (!c->h_tile_count) HIPCHECK(c, hipHostMalloc((void**)&c->h_tile_count, 64, hipHostMallocDefault));
-    uint32_t* d_count = c->d_tile_sel;
-    uint32_t* d_flags = c->d_tile_sel + 16;
+    if (!c->film.tile_count.p) HIPCHECK(c, c->film.tile_count.alloc(64));
+    uint32_t* d_count = c->film.tile_sel.as<uint32_t>();
+    uint32_t* d_flags = c->film.tile_sel.as<uint32_t>() + 16;
     uint32_t* d_list[2] = {d_flags + c->tile_sel_entries, d_flags + 2 * (size_t)c->tile_sel_entries};
     uint32_t added = 0;
     if (cfg->min_spp) {  // pass 0: every tile, the ordinary route
@@ -2559,12 +2430,12 @@ int prt_render_adaptive(PrtContext* c, const PrtAdaptive* cfg, uint32_t max_dept
     };
     while (n_prev) {
         // which of the tiles that were active until now still are; ONE small wait per pass for their number
-        prt_launch_tile_select(c->stream, c->d_film_local, c->d_film_stat, c->tm, prev, n_prev, cfg->threshold, cfg->noise_floor,
+        prt_launch_tile_select(c->stream, c->film.local.as<float4>(), c->film.stat.as<float2>(), c->tm, prev, n_prev, cfg->threshold, cfg->noise_floor,
                                d_flags, d_list[cur], d_count);
         HIPCHECK(c, hipGetLastError());
-        HIPCHECK(c, hipMemcpyAsync(c->h_tile_count, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(c->film.tile_count.p, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(c, hipStreamSynchronize(c->stream));
-        const uint32_t n_act = c->h_tile_count[0], pix_act = c->h_tile_count[1];
+        const uint32_t n_act = c->film.tile_count.as<uint32_t>()[0], pix_act = c->film.tile_count.as<uint32_t>()[1];
         if (n_act > n_prev) return fail(c, PRT_ERR_HIP, "tile selection returned %u of %u tiles", n_act, n_prev);
         if (n_act < n_prev) {
             info.tiles_converged += n_prev - n_act;
@@ -2661,15 +2532,15 @@ static int enqueue_query(PrtContext* c, uint32_t n, const float* d_o, const floa
     if ((rc = ensure_path_state(c, n))) return rc;
     if ((rc = ensure_counters(c))) return rc;
     if ((rc = ensure_spill(c))) return rc;
-    uint32_t* cnt = c->d_counts + (size_t)(PRT_MAX_DEPTH + 1) * PRT_CNT_STRIDE;  // a counter slot the render loop never uses
+    uint32_t* cnt = c->wk.counts.as<uint32_t>() + (size_t)(PRT_MAX_DEPTH + 1) * PRT_CNT_STRIDE;  // a counter slot the render loop never uses
     if (d_tmax) {
         // occlusion: every ray seeded with "miss at d2 = tmax^2", the analytic scan from that bound, the any-hit walk
         // (or, with another traversal variant forced, the closest hit, which k_occlusion_bytes compares with the bound)
         prt_launch_pack_occlusion_rays(c->stream, n, d_o, d_d, d_tmax, c->rb[0], cnt);
-        prt_launch_scan_prims_bounded(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n);
+        prt_launch_scan_prims_bounded(c->stream, c->dsc, c->rb[0], cnt, c->wk.work.as<uint32_t>(), n);
     } else {
         prt_launch_pack_rays(c->stream, n, d_o, d_d, c->rb[0], cnt);
-        prt_launch_scan_prims(c->stream, c->dsc, c->rb[0], cnt, c->d_work, n, nullptr);
+        prt_launch_scan_prims(c->stream, c->dsc, c->rb[0], cnt, c->wk.work.as<uint32_t>(), n, nullptr);
     }
     if (c->dsc.n_nodes) walk_rays(c, c->rb[0], cnt, n, d_tmax != nullptr, c->tune, nullptr, nullptr);
     if (d_tmax) prt_launch_occlusion_bytes(c->stream, c->dsc, n, c->rb[0], d_tmax, d_occ);
@@ -2807,7 +2678,7 @@ static int enqueue_feature_samples(PrtContext* c, uint32_t n) {
     int rc;
     const uint32_t K = c->fsamp.samples;
     const bool follow = c->ftrace.max_specular > 0u;
-    if ((rc = c->samp.ensure(c, 3 * (size_t)n * sizeof(float4)))) return rc;
+    if ((rc = ensure(c, c->samp, 3 * (size_t)n * sizeof(float4)))) return rc;
     const PrtFeatureBufs samp = feature_view(c->samp.p, n);
     if (c->sampling.jitter == 0u && !(c->lens.aperture > 0.0f)) {
         const PrtFeatureBufs src = feature_view(follow ? c->guide.p : c->feat.p, n);
@@ -2864,8 +2735,8 @@ int prt_render_features(PrtContext* c) {
     const uint32_t n = (uint32_t)n64;
     const bool follow = c->ftrace.max_specular > 0u;
     const size_t n1 = n;
-    if (follow && (rc = c->guide.ensure(c, 3 * n1 * sizeof(float4)))) return rc;
-    if ((rc = c->feat.ensure(c, 3 * n1 * sizeof(float4)))) return rc;
+    if (follow && (rc = ensure(c, c->guide, 3 * n1 * sizeof(float4)))) return rc;
+    if ((rc = ensure(c, c->feat, 3 * n1 * sizeof(float4)))) return rc;
     // one pinhole ray through every pixel centre (k_camera_rays: fov_y honoured, no lens, no draw), the ray-query pipeline
     // of prt_closest_hit_device, the textured albedo of prt_hit_uv while a binding textures something, then the records
     float *d_px, *d_py, *d_o, *d_d, *d_a;
@@ -3068,7 +2939,7 @@ int prt_film_denoise(PrtContext* c, const PrtDenoise* cfg, float* rgb_out, float
                     c->tm.rank, c->tm.world);
     int rc = check_ready(c);
     if (rc) return rc;
-    if (!c->d_film_stat) return fail(c, PRT_ERR_INVALID, "prt_film_denoise: film statistics are off (prt_set_film_statistics)");
+    if (!c->film.stat.p) return fail(c, PRT_ERR_INVALID, "prt_film_denoise: film statistics are off (prt_set_film_statistics)");
     const PrtTileMap& tm = c->tm;
     if ((uint64_t)tm.W * tm.H > (uint64_t)PRT_DENOISE_MAX_PIXELS) return fail(c, PRT_ERR_INVALID, "denoise: more than 2^28 pixels");
     if (!c->feat_valid && (rc = prt_render_features(c))) return rc;
@@ -3077,7 +2948,7 @@ int prt_film_denoise(PrtContext* c, const PrtDenoise* cfg, float* rgb_out, float
     FilterScratch s;
     if ((rc = s.commit_film(c, n))) return rc;
     const PrtFeatureBufs gf = filter_features(c);
-    prt_launch_dn_film_prepare(c->stream, tm, c->d_film_local, c->d_film_stat, gf, k.demodulate, s.cv0);
+    prt_launch_dn_film_prepare(c->stream, tm, c->film.local.as<float4>(), c->film.stat.as<float2>(), gf, k.demodulate, s.cv0);
     if ((rc = enqueue_filter(c, k, tm.W, tm.H, gf, s.cv0, s.cv1, s.out, var_out ? s.var : nullptr))) return rc;
     if ((rc = download(c, rgb_out, s.out, 3 * n))) return rc;
     if (var_out && (rc = download(c, var_out, s.var, n))) return rc;
@@ -3238,7 +3109,7 @@ int prt_film_temporal(PrtContext* c, const PrtTemporal* cfg, const PrtDenoise* d
                     c->tm.rank, c->tm.world);
     int rc = check_ready(c);
     if (rc) return rc;
-    if (!c->d_film_stat) return fail(c, PRT_ERR_INVALID, "prt_film_temporal: film statistics are off (prt_set_film_statistics)");
+    if (!c->film.stat.p) return fail(c, PRT_ERR_INVALID, "prt_film_temporal: film statistics are off (prt_set_film_statistics)");
     const PrtTileMap& tm = c->tm;
     if ((bad = prt_temporal_check(cfg, tm.W, tm.H, nullptr, true))) return fail(c, PRT_ERR_INVALID, "%s", bad);
     if (!c->feat_valid && (rc = prt_render_features(c))) return rc;
@@ -3277,14 +3148,14 @@ int prt_film_temporal(PrtContext* c, const PrtTemporal* cfg, const PrtDenoise* d
             memcpy(&h[r_words + 24 * (size_t)i], I.inv, 48);
             memcpy(&h[r_words + 24 * (size_t)i + 12], &c->tp_mats[12 * (size_t)i], 48);
         }
-        if ((rc = c->tp_mt.ensure(c, h.size() * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure(c, c->tp_mt, h.size() * sizeof(uint32_t)))) return rc;
         uint32_t* d_mt = (uint32_t*)c->tp_mt.p;
         if ((rc = upload(c, d_mt, h.data(), h.size()))) return rc;
         mt = PrtMotionTable{d_mt, (const float4*)(d_mt + r_words), n_copies};
     }
     HIPCHECK(c, hipMemsetAsync(d_counts, 0, 16, c->stream));
     const PrtFeatureBufs first = current_set(c, c->feat);
-    prt_launch_tp_reproject_film(c->stream, tm, k, c->tp_K, c->d_film_local, c->d_film_stat, first.nrm, first.pos, mt, prev, next, d_mean, d_var,
+    prt_launch_tp_reproject_film(c->stream, tm, k, c->tp_K, c->film.local.as<float4>(), c->film.stat.as<float2>(), first.nrm, first.pos, mt, prev, next, d_mean, d_var,
                                  d_status, d_counts);
     HIPCHECK(c, hipGetLastError());
     if (history_out) prt_launch_tp_unpack(c->stream, (uint32_t)n, next, d_hist, d_m1, d_m2);
@@ -3642,15 +3513,6 @@ struct BakeBufs {
     uint8_t* cov2 = nullptr;
 };
 
-// Two events around a call's device work (PrtBakeInfo.device_ms)
-struct BakeTimer {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~BakeTimer() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-
 // The refusals, in the order of the header; everything here is decided without a device.  q: null for the entry points
 // that trace nothing.
 static int check_bake(PrtContext* c, const PrtBakeTarget* t, const PrtRadianceQuery* q, bool with_query, BakeTarget* b) {
@@ -3857,11 +3719,11 @@ static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const Prt
     if (rc) return rc;
     if (!out_rgb) return fail(c, PRT_ERR_INVALID, "prt_bake_irradiance: null rgb_sum");
     if ((rc = need_device(c))) return rc;
-    BakeTimer tm;
+    EventPair tm;  // around the call's device work (PrtBakeInfo.device_ms)
     if (info) {
-        HIPCHECK(c, hipEventCreate(&tm.a));
-        HIPCHECK(c, hipEventCreate(&tm.b));
-        HIPCHECK(c, hipEventRecord(tm.a, c->stream));
+        HIPCHECK(c, tm.a.create(true));
+        HIPCHECK(c, tm.b.create(true));
+        HIPCHECK(c, hipEventRecord(ev(tm.a), c->stream));
     }
     BakeBufs x;
     uint32_t counts[PRT_BAKE_COUNTERS] = {};
@@ -3947,10 +3809,10 @@ static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const Prt
     if (out_cov) HIPCHECK(c, hipMemcpyAsync(out_cov, cov[cur], n, kind, c->stream));
     if (info) {
         if ((rc = download(c, counts, x.counts, (size_t)PRT_BAKE_COUNTERS))) return rc;
-        HIPCHECK(c, hipEventRecord(tm.b, c->stream));
+        HIPCHECK(c, hipEventRecord(ev(tm.b), c->stream));
         HIPCHECK(c, hipStreamSynchronize(c->stream));
         float ms = 0.0f;
-        HIPCHECK(c, hipEventElapsedTime(&ms, tm.a, tm.b));
+        HIPCHECK(c, hipEventElapsedTime(&ms, ev(tm.a), ev(tm.b)));
         info->n_filled = counts[PRT_BAKE_CNT_FILLED];
         info->rays = (uint64_t)n_cov * q->samples;
         info->segments = (uint64_t)counts[PRT_BAKE_CNT_SEGMENTS] | ((uint64_t)counts[PRT_BAKE_CNT_SEGMENTS + 1u] << 32);
@@ -4123,9 +3985,9 @@ int prt_get_stats(PrtContext* c, PrtStats* out) {
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     if ((rc = drain_events(c))) return rc;
     PrtStats s = c->stats;
-    if (c->d_ray_stats) {
+    if (c->wk.ray_stats.p) {
         unsigned long long h[PRT_MAX_DEPTH];
-        if ((rc = read_ray_stats(c, c->d_ray_stats, h))) return rc;
+        if ((rc = read_ray_stats(c, c->wk.ray_stats.as<unsigned long long>(), h))) return rc;
         s.rays_total = 0;
         for (int d = 0; d < PRT_MAX_DEPTH; ++d) {
             s.rays_per_depth[d] = h[d];
@@ -4144,8 +4006,8 @@ int prt_reset_stats(PrtContext* c) {
     memset(&c->stats, 0, sizeof(c->stats));
     c->dead_paths = 0;
     // (stream-ordered, like the counting kernels that follow: see ensure_light_state)
-    if (c->d_ray_stats) HIPCHECK(c, hipMemsetAsync(c->d_ray_stats, 0, kRayStatWords * sizeof(unsigned long long), c->stream));
-    if (c->d_light_stats) HIPCHECK(c, hipMemsetAsync(c->d_light_stats, 0, kLightStatWords * sizeof(unsigned long long), c->stream));
+    if (c->wk.ray_stats.p) HIPCHECK(c, hipMemsetAsync(c->wk.ray_stats.p, 0, kRayStatWords * sizeof(unsigned long long), c->stream));
+    if (c->wk.light_stats.p) HIPCHECK(c, hipMemsetAsync(c->wk.light_stats.p, 0, kLightStatWords * sizeof(unsigned long long), c->stream));
     return PRT_OK;
 }
 
@@ -4157,27 +4019,27 @@ int prt_measure_traversal(PrtContext* c, uint32_t max_depth, uint32_t seed, uint
     {
         std::vector<unsigned long long> init(kTravStatsWords, 0ull);
         for (uint32_t d = 0; d <= PRT_MAX_DEPTH; ++d) init[16 + PRT_TIMELINE_WORDS * d] = init[16 + PRT_TIMELINE_WORDS * d + 2] = ~0ull;  // minima
-        HIPCHECK(c, hipMemcpy(c->d_trav_stats, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        HIPCHECK(c, hipMemcpy(c->wk.trav_stats.p, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
     }
     const bool timing = c->timing;
     const uint64_t launches = c->stats.intersect_launches;
     c->timing = false;
     // the per-depth ray counters are cumulative: this run counts into the scratch set
     unsigned long long before[PRT_MAX_DEPTH] = {}, after[PRT_MAX_DEPTH];
-    HIPCHECK(c, hipMemsetAsync(c->d_ray_stats + kRayStatWords, 0, kRayStatWords * sizeof(unsigned long long), c->stream));
-    c->ray_stats_target = c->d_ray_stats + kRayStatWords;
+    HIPCHECK(c, hipMemsetAsync(c->wk.ray_stats.as<unsigned long long>() + kRayStatWords, 0, kRayStatWords * sizeof(unsigned long long), c->stream));
+    c->ray_stats_target = c->wk.ray_stats.as<unsigned long long>() + kRayStatWords;
     // measure_spp (prt_set_param) samples in one batch: the counters scale, the per-phase cycle split becomes that of a
     // loaded kernel
-    rc = run_batch(c, whole_film(c), (uint32_t)std::max(1, c->measure_spp), max_depth, seed, sample, false, c->d_trav_stats);
-    c->ray_stats_target = c->d_ray_stats;
+    rc = run_batch(c, whole_film(c), (uint32_t)std::max(1, c->measure_spp), max_depth, seed, sample, false, c->wk.trav_stats.as<unsigned long long>());
+    c->ray_stats_target = c->wk.ray_stats.as<unsigned long long>();
     c->timing = timing;
     c->stats.intersect_launches = launches;
     if (rc) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    if ((rc = read_ray_stats(c, c->d_ray_stats + kRayStatWords, after))) return rc;
+    if ((rc = read_ray_stats(c, c->wk.ray_stats.as<unsigned long long>() + kRayStatWords, after))) return rc;
     unsigned long long t[kTravStatsWords];
     std::vector<uint32_t> cnt((size_t)(PRT_MAX_DEPTH + 2) * PRT_CNT_STRIDE);
-    HIPCHECK(c, hipMemcpy(t, c->d_trav_stats, sizeof(t), hipMemcpyDeviceToHost));
+    HIPCHECK(c, hipMemcpy(t, c->wk.trav_stats.as<unsigned long long>(), sizeof(t), hipMemcpyDeviceToHost));
     if (getenv("PRT_TAIL_PROBE")) {  // diagnostic: where a launch of the 8-wide kernel spends its wall time (100 MHz ticks -> us)
         for (uint32_t d = 0; d < max_depth; ++d) {
             const unsigned long long* tl = t + 16 + PRT_TIMELINE_WORDS * d;
@@ -4189,7 +4051,7 @@ int prt_measure_traversal(PrtContext* c, uint32_t max_depth, uint32_t seed, uint
                     tl[5] * 0.01 / tl[6], tl[4] * 0.01 / tl[6], tl[6], tl[7]);
         }
     }
-    HIPCHECK(c, hipMemcpy(cnt.data(), c->d_counts, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(c, hipMemcpy(cnt.data(), c->wk.counts.p, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     memset(out, 0, sizeof(*out));
     uint64_t front = 0;
     for (uint32_t d = 0; d < max_depth; ++d) {
@@ -4219,12 +4081,12 @@ int prt_measure_shade_divergence(PrtContext* c, uint32_t max_depth, uint32_t see
     if (!out || max_depth == 0 || max_depth > PRT_MAX_DEPTH) return PRT_ERR_INVALID;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     const size_t bytes = 16 * (size_t)PRT_MAX_DEPTH * sizeof(unsigned long long);
-    unsigned long long* buf = nullptr;
-    HIPCHECK(c, hipMalloc((void**)&buf, bytes));
-    hipError_t e = hipMemsetAsync(buf, 0, bytes, c->stream);
+    DevBuf buf;  // (freed when the function returns)
+    HIPCHECK(c, buf.ensure(bytes));
+    hipError_t e = hipMemsetAsync(buf.p, 0, bytes, c->stream);
     if (e == hipSuccess) {
-        c->d_shade_div = buf;
-        c->ray_stats_target = c->d_ray_stats + kRayStatWords;  // (the run's rays are not the context's)
+        c->d_shade_div = buf.as<unsigned long long>();
+        c->ray_stats_target = c->wk.ray_stats.as<unsigned long long>() + kRayStatWords;  // (the run's rays are not the context's)
         const bool timing = c->timing;
         const uint64_t launches = c->stats.intersect_launches;
         c->timing = false;
@@ -4232,11 +4094,10 @@ int prt_measure_shade_divergence(PrtContext* c, uint32_t max_depth, uint32_t see
         c->timing = timing;
         c->stats.intersect_launches = launches;
         c->d_shade_div = nullptr;
-        c->ray_stats_target = c->d_ray_stats;
+        c->ray_stats_target = c->wk.ray_stats.as<unsigned long long>();
         if (!rc) e = hipStreamSynchronize(c->stream);
-        if (!rc && e == hipSuccess) e = hipMemcpy(out, buf, 16 * (size_t)max_depth * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        if (!rc && e == hipSuccess) e = hipMemcpy(out, buf.p, 16 * (size_t)max_depth * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     }
-    (void)hipFree(buf);
     if (rc) return rc;
     HIPCHECK(c, e);
     return PRT_OK;
@@ -4297,10 +4158,10 @@ int prt_last_segment(PrtContext* c, uint32_t* active, uint32_t* front_rays) {
     *active = c->last_segment_active;
     if (front_rays) {
         *front_rays = 0u;
-        if (c->last_batch_depth != 0u && c->d_counts) {
+        if (c->last_batch_depth != 0u && c->wk.counts.p) {
             HIPCHECK(c, hipSetDevice(c->device));
             HIPCHECK(c, hipStreamSynchronize(c->stream));
-            HIPCHECK(c, hipMemcpy(front_rays, c->d_counts + (size_t)(c->last_batch_depth - 1u) * PRT_CNT_STRIDE, sizeof(uint32_t),
+            HIPCHECK(c, hipMemcpy(front_rays, c->wk.counts.as<uint32_t>() + (size_t)(c->last_batch_depth - 1u) * PRT_CNT_STRIDE, sizeof(uint32_t),
                                   hipMemcpyDeviceToHost));
         }
     }

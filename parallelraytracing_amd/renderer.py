@@ -373,6 +373,13 @@ class Film:
         return np.where(self.weights[..., None] > 0, self.accum / w, 0.0).astype(np.float32)
 
 
+def device_memory_info() -> Tuple[int, int]:
+    """(live_bytes, alloc_calls) of prt_device_memory_info: device bytes the library's contexts own now, allocation calls so far."""
+    live, calls = C.c_uint64(0), C.c_uint64(0)
+    capi.lib().prt_device_memory_info(C.byref(live), C.byref(calls))
+    return int(live.value), int(calls.value)
+
+
 def hits_to_numpy(t) -> np.ndarray:
     """The [n, 10] int32 tensor of HipWavefrontRenderer.closest_hit_device as PrtHit records (capi.HIT_DTYPE)."""
     a = np.ascontiguousarray(t.cpu().numpy(), dtype=np.int32).reshape(-1, 10)
