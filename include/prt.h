@@ -1422,7 +1422,10 @@ int prt_set_variant(PrtContext* ctx, int variant);
  * triangles, prt_last_segment: 0 = walked and shaded like any other; 1 = it ends in the shade launch that produces it where
  * the analytic scan alone decides what the film gets; 2, default = 1, and the rays still walked get the any-hit walk seeded
  * with their analytic hit), "primary_reuse" (1, default: a still camera's primary stage is kept across batches and calls,
- * prt_primary_reuse; 0 = every batch rebuilds it; setting ANY tunable makes the next batch rebuild it), "denoise_lds" (which iterations of the denoiser stage their block's footprint in LDS: 0 = none, 1, default = step 1,
+ * prt_primary_reuse; 0 = every batch rebuilds it; setting ANY tunable makes the next batch rebuild it), "path_id_order" (how a
+ * batch of compact primary rays with at least 8 samples numbers its paths: 1, default = pixel * samples + sample, so the waves
+ * of the shade launches, which hold runs of one pixel's samples, store their path results next to each other; 0 = sample *
+ * pixels + pixel, as every other batch; A/B), "denoise_lds" (which iterations of the denoiser stage their block's footprint in LDS: 0 = none, 1, default = step 1,
  * 2 = steps 1 and 2; A/B), "feature_chunk" / "radiance_chunk" (samples per chunk of the sampled feature pass / of prt_radiance; 0, default = by
  * the ray budget).  Results never depend on a tunable.  Unknown names / bad values
  * return PRT_ERR_INVALID. */

@@ -208,6 +208,7 @@ struct PrtContext {
     float pad_coeff = kPadCoeff;  // prt_set_param("pad_log2", n): culling pad = 2^-n of the coordinates' magnitude (A/B; before prt_set_scene)
     int node_stride = 0;      // prt_set_param("node_stride", 5 | 8): uint4 per 8-wide node slot, 0 = by tree size (upload_scene); before prt_set_scene
     int compact_primary = 1;  // prt_set_param("compact_primary", 0): k_raygen stores full ray records (A/B)
+    int path_id_order = 1;    // prt_set_param("path_id_order", 0): every batch numbers its paths sample-major (prt_path_id.h; A/B)
     int primary_walk = 1;     // prt_set_param("primary_walk", 0): compact primary rays are walked once per sample, not once per pixel (A/B)
     const char* shade_instance = "";  // the shade kernel instance the last run_batch launched, as its launch macro spelled it (prt_shade_instance)
     const char* batch_instance[4] = {"", "", "", ""};  // what the last run_batch launched, by PRT_STAGE_* (prt_batch_instance)
@@ -233,7 +234,7 @@ struct PrtContext {
     PrimaryMem prim;
     uint64_t prim_pid_entries = 0;
     uint32_t prim_pix_entries = 0;
-    PrtPrimaryKey primary_key{};        // what the buffers hold (valid = false: nothing)
+    PrtPrimaryStageKey primary_key{};   // what the buffers hold (batch.valid = false: nothing)
     uint64_t camera_gen = 1, scene_gen = 1;  // PrtPrimaryKey: bumped by every setter that can change what the stage computes
     uint32_t primary_counts[2] = {0u, 0u};   // bounce 0's front / back ray counts as the host read them at the refresh (exact grids)
     int primary_reuse = 1;              // prt_set_param("primary_reuse", 0): every batch rebuilds its primary stage (A/B)
@@ -430,14 +431,14 @@ void touch_camera(PrtContext* c) { ++c->camera_gen; }
 // The persistent primary buffers of the compact route (sized with the path state; they only grow, and growing drops what they held)
 int ensure_primary_state(PrtContext* c, uint64_t n_paths, uint32_t n_pix_local) {
     if (n_paths > c->prim_pid_entries) {
-        c->primary_key.valid = false;
+        c->primary_key.batch.valid = false;
         c->prim_pid_entries = 0;  // (a growing ensure releases before it allocates, and a failed one leaves nothing)
         const uint64_t n = std::max<uint64_t>(n_paths, 256);
         HIPCHECK(c, c->prim.pid.ensure(n * sizeof(uint32_t)));
         c->prim_pid_entries = n;
     }
     if (n_pix_local > c->prim_pix_entries) {
-        c->primary_key.valid = false;
+        c->primary_key.batch.valid = false;
         c->prim_pix_entries = 0;
         const uint32_t n = std::max<uint32_t>(n_pix_local, 256u);
         HIPCHECK(c, c->prim.list.ensure((size_t)n * sizeof(uint32_t)));
@@ -834,6 +835,8 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     f.last_segment = c->last_segment;
     const PrtRoutePlan plan = prt_plan_route(f);
     const bool lit = f.lit, compact = plan.compact, walk = plan.walk;
+    // how this batch numbers its paths (prt_path_id.h): a function of the plan, the batch's sample count and the tunable
+    const bool pixel_major_ids = prt_path_id_pixel_major(compact, S_cur, c->path_id_order);
     const DevEnv denv = dev_env(c);
     const DevTex dtex = dev_tex(c);
     const DevLens dlens{c->lens.aperture, c->lens.focus_distance};
@@ -869,7 +872,8 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     auto accumulate_batch = [&]() -> int {
         if ((rc = begin_event(c, 3, &ep))) return rc;
         const PrtAccumulateArgs aa{d_rad, lit ? c->lb.lrad : nullptr, c->film.local.as<float4>(), c->film.stat.as<float2>(), tm, S_cur, max_depth,
-                                   accumulate, c->ray_stats_target, compact ? c->wk.pix.as<float4>() + tm.n_pix_local : nullptr, view.list};
+                                   accumulate, c->ray_stats_target, compact ? c->wk.pix.as<float4>() + tm.n_pix_local : nullptr, view.list,
+                                   pixel_major_ids};
         if (!prt_launch_accumulate(c->stream, plan.accumulate, aa)) return fail(c, PRT_ERR_INVALID, "no such accumulate instance");
         c->batch_instance[PRT_STAGE_ACCUMULATE] = prt_accumulate_name(plan.accumulate);
         if ((rc = end_event(c, &ep))) return rc;
@@ -898,7 +902,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     }
     if (compact && c->pix_entries < tm.n_pix_local) {
         c->pix_entries = 0;
-        c->primary_key.valid = false;
+        c->primary_key.batch.valid = false;
         HIPCHECK(c, c->wk.pix.ensure(4 * (size_t)tm.n_pix_local * sizeof(float4)));
         c->pix_entries = tm.n_pix_local;
         c->pix_records_blank = false;
@@ -916,7 +920,8 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     float4* const d_pix = c->wk.pix.as<float4>();
     PrtRayBuf rb0 = c->rb[0];
     if (persistent) rb0.t = c->prim.pid.as<float4>(), rb0.hd2 = c->prim.list.as<float>(), rb0.hit = c->prim.hit.as<uint32_t>();
-    PrtPrimaryKey now{};
+    PrtPrimaryStageKey now_stage{};
+    PrtPrimaryKey& now = now_stage.batch;
     now.valid = persistent && c->primary_reuse != 0 && !instrumented;  // eligible (compact: no jitter, no lens, no tile list)
     if (now.valid) {
         const PrtWalkPlan wp0 = prt_plan_walk(walk_facts(c, c->tune, PRT_WALK_CLOSEST, walk ? tm.n_pix_local : n_paths, false, true));
@@ -929,7 +934,8 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
         now.rr_depth = c->sampling.rr_depth, now.clamp = c->sampling.clamp;
         now.listed = view.list != nullptr, now.instrumented = instrumented, now.exact = exact;
     }
-    const bool reuse = prt_primary_reusable(c->primary_key, now);
+    now_stage.id_order = pixel_major_ids ? 1u : 0u, now_stage.id_S = pixel_major_ids ? S_cur : 0u;
+    const bool reuse = prt_primary_stage_reusable(c->primary_key, now_stage);
     c->primary_reuse_active = reuse ? 1u : 0u;
     if (reuse) ++c->primary_reused_batches;
     // front/back counters of every bounce start at zero (the producers add to them atomically).  REUSE: from bounce 1's stride.
@@ -950,17 +956,18 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
     // slot.  A batch of ONE sample keeps its path slots: they ARE that list (one path per pixel, in the same order), and
     // k_raygen saves the second store and atomic.
     c->batch_walked = walk;
-    const PrtPrimary primary{(const uint32_t*)rb0.t, d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z}, tm.n_pix_local,
-                             1.0f / (float)tm.n_pix_local, first_sample, seed, walk ? 1u : 0u};
-    PrtPrimary primary_list = primary;  // what the traversal sees: list slots in place of path slots
-    if (walk) primary_list.pid = (const uint32_t*)rb0.hd2;
+    const PrtPrimary primary{(const uint32_t*)rb0.t, d_pix, {c->cam.pos.x, c->cam.pos.y, c->cam.pos.z},
+                             prt_path_id_order(tm.n_pix_local, S_cur, pixel_major_ids), first_sample, seed, walk ? 1u : 0u};
+    PrtPrimary primary_list = primary;  // what the traversal sees: list slots in place of path slots, each entry a local pixel,
+                                        // which is the sample-major id of the pixel's sample 0 whatever the batch's order
+    if (walk) primary_list.pid = (const uint32_t*)rb0.hd2, primary_list.ids = prt_path_id_order(tm.n_pix_local, S_cur, false);
     // (REUSE: the name of the instance whose output the batch uses)
     c->batch_instance[PRT_STAGE_RAYGEN] = prt_raygen_name(plan.raygen);
     if (!reuse) {
-        c->primary_key.valid = false;  // k_raygen overwrites d_pix and bounce 0's counters: set again below, once the stage stands
+        c->primary_key.batch.valid = false;  // k_raygen overwrites d_pix and bounce 0's counters: set again below, once the stage stands
         if ((rc = begin_event(c, 0, &ep))) return rc;
         const PrtRaygenArgs ra{&c->dsc, c->cam, tm, n_paths, first_sample, seed, max_depth, rb0, d_rad, d_counts, d_work, c->sampling,
-                               compact ? d_pix : nullptr, walk, f.env ? &denv : nullptr, f.lens ? &dlens : nullptr, view.list};
+                               compact ? d_pix : nullptr, walk, pixel_major_ids, f.env ? &denv : nullptr, f.lens ? &dlens : nullptr, view.list};
         if (!prt_launch_raygen(c->stream, plan.raygen, ra)) return fail(c, PRT_ERR_INVALID, "no such raygen instance");
         if ((rc = end_event(c, &ep))) return rc;
         if (exact) HIPCHECK(c, read_back(0));
@@ -1012,7 +1019,7 @@ int run_batch(PrtContext* c, const PrtBatchView& view, uint32_t S_cur, uint32_t 
             if (d == 0) c->primary_counts[0] = h_counts[0], c->primary_counts[1] = h_counts[32];
         }
         if (n_rays_known == 0u) break;  // every path has ended: the later bounces have nothing to do
-        if (d == 0 && !reuse && now.valid) c->primary_key = now;  // the stage stands: what the next batch may start from
+        if (d == 0 && !reuse && now.valid) c->primary_key = now_stage;  // the stage stands: what the next batch may start from
         if (c->d_shade_div) prt_launch_shade_divstats(c->stream, c->dsc, in, d_counts, d, n_paths, c->d_shade_div, prim_d);
         if ((rc = begin_event(c, 2, &ep))) return rc;
         const PrtShadeInst shade = d == 0 ? plan.shade0 : plan.shade;
@@ -4227,6 +4234,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "last_segment" && value >= 0 && value <= 2) c->last_segment = (uint32_t)value;
     else if (n == "compact_primary" && (value == 0 || value == 1)) c->compact_primary = value;
     else if (n == "primary_walk" && (value == 0 || value == 1)) c->primary_walk = value;
+    else if (n == "path_id_order" && (value == 0 || value == 1)) c->path_id_order = value;
     else if (n == "node_stride" && (value == 0 || value == 5 || value == 8)) c->node_stride = value;
     else if (n == "pad_log2" && value >= 8 && value <= 22) c->pad_coeff = std::ldexp(1.0f, -value);
     else if (n == "tail" && value >= 0 && value <= 64) c->tune.tail = (uint32_t)value;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/prt.h"
+#include "prt_path_id.h"    // how a batch numbers its paths: (local pixel, sample) <-> path id
 #include "prt_route.h"      // the instance lists and the plan of a batch
 #include "prt_walk.h"       // PrtTravTuning; the walk kernels' instance lists and the plan of a tree walk
 #include "prt_scene_pod.h"  // DevPrim, DevInstance
@@ -118,8 +119,8 @@ struct PrtPrimary {
                           // 2 x n_pix_local more: the primary hit's surface interaction (k_primary_hit): {position, hit id},
                           // {normal, material | front << 31}
     float origin[3];      // camera position
-    uint32_t n_pix_local;
-    float inv_n;          // 1 / n_pix_local (first guess of path id / n_pix_local, corrected exactly)
+    PrtPathIdOrder ids;   // the batch's path ids (prt_path_id.h; n_pix_local is in there).  The traversal's copy with walk = 1:
+                          // always sample-major, a list entry is a local pixel = the sample-major id of its sample 0
     uint32_t first_sample, seed;
     uint32_t walk;        // 1: the first traversal walked one ray per front pixel (hit[] is indexed by list slot), 0: one per path slot
 };
@@ -238,6 +239,7 @@ struct PrtRaygenArgs {
     PrtSampling sp;
     float4* compact_pix;   // the compact instance: the pixel records (PrtPrimary.pix)
     bool primary_walk;     // the compact instance: write the front-pixel list into out.hd2 (PrtPrimary)
+    bool pixel_major_ids;  // the compact instance: path id = pixel * S + sample (prt_path_id.h)
     const DevEnv* env;     // the instances with an environment image
     const DevLens* lens;   // the instances with a thin lens (one full record per sample)
     const uint32_t* list;  // k_raygen_list: the tiles of a PrtBatchView
@@ -304,6 +306,7 @@ struct PrtAccumulateArgs {
     unsigned long long* ray_stats;
     const float4* pix_end;  // compact primary rays: what a pixel's paths deliver if they end with their primary ray
     const uint32_t* list;
+    bool pixel_major_ids;   // compact primary rays: rad[] is indexed pixel * S + sample (prt_path_id.h)
 };
 bool prt_launch_accumulate(hipStream_t st, PrtAccumulateInst inst, const PrtAccumulateArgs& a);
 void prt_launch_resolve(hipStream_t st, const float4* gathered, uint32_t world, uint32_t stride, uint32_t W,

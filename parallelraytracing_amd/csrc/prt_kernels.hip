@@ -157,19 +157,10 @@ PRT_DEV bool tile_pixel(const PrtTileMap& tm, uint32_t pl, uint32_t& x, uint32_t
 }
 
 // The primary ray of path i (no jitter: the pixel centre, cpu/renderer.cpp:45) as k_raygen computed it for the path's
-// pixel (PrtPrimary, prt_kernels.h): path id -> (sample, local pixel) -> the pixel's record.
+// pixel (PrtPrimary, prt_kernels.h): path id -> (sample, local pixel) in the batch's id order (prt_path_id.h) -> the pixel's record.
 PRT_DEV void primary_ray(const PrtPrimary& pr, uint32_t i, f3& o, f3& d, uint32_t& pixel, uint32_t& sample, uint32_t* local_pixel = nullptr) {
-    uint32_t q = (uint32_t)((float)i * pr.inv_n);  // within one of i / n_pix_local
-    uint32_t r = i - q * pr.n_pix_local;
-    if ((int32_t)r < 0) {
-        --q;
-        r += pr.n_pix_local;
-    }
-    if (r >= pr.n_pix_local) {
-        ++q;
-        r -= pr.n_pix_local;
-    }
-    sample = q;
+    uint32_t r;
+    prt_path_id_decode(pr.ids, i, r, sample);
     if (local_pixel) *local_pixel = r;
     const float4 P = pr.pix[r];
     o = mk3(pr.origin[0], pr.origin[1], pr.origin[2]);
@@ -327,8 +318,12 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
                          float4* __restrict__ ro, float4* __restrict__ rd, float4* __restrict__ rt, uint32_t* __restrict__ hit,
                          float* __restrict__ hd2, float4* __restrict__ rad, uint32_t* __restrict__ counts,
                          uint32_t* __restrict__ work, uint32_t max_depth, PrtSampling sp_arg, float4* __restrict__ pix,
-                         const DevEnv* env, const DevLens* lens = nullptr, const uint32_t* __restrict__ list = nullptr) {
+                         const DevEnv* env, const DevLens* lens = nullptr, const uint32_t* __restrict__ list = nullptr,
+                         uint32_t pixel_major_ids = 0u) {
     const PrtSampling sp = SAMPLING ? sp_arg : PrtSampling{0u, 0u, 0.0f};
+    // the batch's path ids (prt_path_id.h; encode only: no decode fields).  Pixel-major on the compact instance alone, where the
+    // host asks for it: everywhere else S = 0 is a compile-time constant and the id is sample * n_pix_local + pixel as ever
+    const PrtPathIdOrder ids{tm.n_pix_local, 0.0f, (COMPACT && pixel_major_ids) ? S : 0u, 0u, 0u};
     const uint32_t pl = blockIdx.x * (uint32_t)PRODUCER_BLOCK + threadIdx.x;
     if (blockIdx.y == 0 && pl < 8u) work[32u * pl] = 0u;  // chunk cursors of the traversal kernel that follows
     if (blockIdx.y == 0 && pl == 8u) work[512] = 0u;      // its overflow-list counter
@@ -375,7 +370,8 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
         uint32_t first_slot = slot0;  // slot of this pixel's sample s0
         // One walk per pixel (PrtPrimary, walk = 1; hd2 is then the list, else null): the block's front pixels go on the
         // dense list the first traversal runs over, in the order block_alloc2 ranked them (its ballots; one more atomic
-        // per block).  Entry = the local pixel index = the path id of the pixel's sample 0.
+        // per block).  Entry = the local pixel index = the sample-major path id of the pixel's sample 0, which is how the walk
+        // decodes it whatever the batch's own id order (PrtPrimary.ids).
         const bool walk = COMPACT && hd2 != nullptr;
         uint32_t list_slot = 0xFFFFFFFFu;  // (what a stored back pixel's record carries)
         if (walk && blockIdx.y == 0) {  // block-uniform
@@ -387,12 +383,12 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
                 ((uint32_t*)hd2)[list_slot] = pl;
             }
         }
-        if (s1 - s0 < 8u) {
+        if (s1 - s0 < PRT_PATH_ID_MIN_SAMPLES) {
             // few samples per pixel in this batch (interactive use: ProgressiveRender adds ONE sample per call): SAMPLE-major
             // slots, every thread stores its own pixel's copies, coalesced across the pixels of a wave
             if (in_range && slot0 != 0xFFFFFFFFu) {
                 for (uint32_t sl = s0; sl < s1; ++sl) {
-                    const uint32_t i = sl * tm.n_pix_local + pl;  // path id
+                    const uint32_t i = prt_path_id_encode(ids, pl, sl);  // path id
                     const uint32_t slot = front ? slot0 + (sl - s0) * stride : slot0 - (sl - s0) * stride;
                     if (COMPACT) {
                         ((uint32_t*)rt)[slot] = i;
@@ -440,7 +436,7 @@ PRT_DEV void raygen_step(DevScene sc, DevCamera cam, PrtTileMap tm, uint32_t S, 
                 }
                 if (lane < mult) {
                     const uint32_t slot = fr ? f + lane : f - lane;
-                    const uint32_t i = (s0 + lane) * tm.n_pix_local + plp;  // path id
+                    const uint32_t i = prt_path_id_encode(ids, plp, s0 + lane);  // path id
                     if (COMPACT) {  // 12 B per path: bounce 0 rebuilds the rest from the path id (PrtPrimary)
                         ((uint32_t*)rt)[slot] = i;
                     } else {
@@ -546,9 +542,11 @@ __global__ void __launch_bounds__(PRODUCER_BLOCK) k_raygen(DevScene sc, DevCamer
                                                             float4* __restrict__ rt, uint32_t* __restrict__ hit,
                                                             float* __restrict__ hd2, float4* __restrict__ rad,
                                                             uint32_t* __restrict__ counts, uint32_t* __restrict__ work,
-                                                            uint32_t max_depth, PrtSampling sp_arg, float4* __restrict__ pix) {
+                                                            uint32_t max_depth, PrtSampling sp_arg, float4* __restrict__ pix,
+                                                            uint32_t pixel_major_ids) {
+    // (pixel_major_ids: read by the COMPACT instance only)
     raygen_step<JITTER, SAMPLING, ABVH, COMPACT, false>(sc, cam, tm, S, first_sample, seed, ro, rd, rt, hit, hd2, rad, counts, work,
-                                                        max_depth, sp_arg, pix, nullptr);
+                                                        max_depth, sp_arg, pix, nullptr, nullptr, nullptr, COMPACT ? pixel_major_ids : 0u);
 }
 
 // k_raygen under an environment image (prt_set_environment): full ray records always, sampling options compiled in
@@ -2200,7 +2198,7 @@ __device__ __forceinline__ void traverse8_body(DevScene sc, const float4* __rest
                             f3 po, pd;
                             uint32_t pixel, sample, lp;
                             primary_ray(pr, ld_stream(&pr.pid[qi]), po, pd, pixel, sample, &lp);
-                            const float4 E = pr.pix[pr.n_pix_local + lp];  // the pixel's analytic hit (k_raygen)
+                            const float4 E = pr.pix[pr.ids.n_pix_local + lp];  // the pixel's analytic hit (k_raygen)
                             hid = __float_as_uint(E.y);
                             hd2_0 = E.z;
                             // every primary ray starts at the camera, a kernel argument: left visible, the compiler hoists
@@ -2599,13 +2597,13 @@ PRT_DEV void shade_step(DevScene sc, const float4* __restrict__ ro, const float4
             // a back-side primary ray was never walked: its closest hit is the analytic scan's, kept per pixel (k_raygen);
             // a front-side one was walked once for its pixel (walk = 1): the hit sits at the pixel's list slot (in big
             // batches a wave holds the samples of one pixel: both loads are wave-uniform)
-            if (k >= nA) id = __float_as_uint(pr.pix[pr.n_pix_local + lp].y);
-            else if (pr.walk) id = hit[__float_as_uint(pr.pix[pr.n_pix_local + lp].x)];
+            if (k >= nA) id = __float_as_uint(pr.pix[pr.ids.n_pix_local + lp].y);
+            else if (pr.walk) id = hit[__float_as_uint(pr.pix[pr.ids.n_pix_local + lp].x)];
             rng = path_seed(pixel, pr.first_sample + sample, pr.seed);
             depth = 0u;
             thr = mk3(1.f, 1.f, 1.f);
-            pre_a = pr.pix[2u * pr.n_pix_local + lp];
-            pre_b = pr.pix[3u * pr.n_pix_local + lp];
+            pre_a = pr.pix[2u * pr.ids.n_pix_local + lp];
+            pre_b = pr.pix[3u * pr.ids.n_pix_local + lp];
         } else {
             const float4 O = ld_stream(&ro[src]);
             const float4 D = ld_stream(&rd[src]);
@@ -2685,8 +2683,8 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_tex(DevScene sc, DevTex t
 __global__ void __launch_bounds__(256) k_primary_hit(DevScene sc, PrtPrimary pr, const uint32_t* __restrict__ hit,
                                                      float4* __restrict__ pix, const uint32_t* __restrict__ counts) {
     const uint32_t pl = blockIdx.x * 256u + threadIdx.x;
-    if (pl >= pr.n_pix_local) return;
-    const float4 E = pix[pr.n_pix_local + pl];
+    if (pl >= pr.ids.n_pix_local) return;
+    const float4 E = pix[pr.ids.n_pix_local + pl];
     float4 a = make_float4(0.f, 0.f, 0.f, __uint_as_float(HIT_DEAD)), b = make_float4(0.f, 0.f, 0.f, 0.f);  // no record
     if (__float_as_uint(E.w) == 0xFFFFFFFEu) {  // the pixel's paths were stored
         // front pixels (a list slot, not the sentinel; one walk per sample: a ray slot below the front count) were walked:
@@ -2704,8 +2702,8 @@ __global__ void __launch_bounds__(256) k_primary_hit(DevScene sc, PrtPrimary pr,
             }
         }
     }
-    pix[2u * pr.n_pix_local + pl] = a;
-    pix[3u * pr.n_pix_local + pl] = b;
+    pix[2u * pr.ids.n_pix_local + pl] = a;
+    pix[3u * pr.ids.n_pix_local + pl] = b;
 }
 
 // Diagnostic (prt_measure_shade_divergence, tools/shade_divergence.py; SURVEY 8f-4 "material-coherent work queues",
@@ -2729,7 +2727,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK) k_shade_divstats(DevScene sc, con
             f3 o_, d_;
             uint32_t pixel, sample, lp;
             primary_ray(pr, pr.pid[src], o_, d_, pixel, sample, &lp);
-            const float4 E = pr.pix[pr.n_pix_local + lp];
+            const float4 E = pr.pix[pr.ids.n_pix_local + lp];
             id = k >= nA ? __float_as_uint(E.y) : hit[__float_as_uint(E.x)];
         } else {
             id = hit[src];
@@ -2979,6 +2977,123 @@ __global__ void __launch_bounds__(256) k_accumulate_stat(const float4* __restric
     if (valid && update_film) {
         film_local[fl] = f;
         stat[fl] = m2;
+    }
+    }
+    __syncthreads();
+    if (threadIdx.x < max_depth) {
+        unsigned long long n = 0;
+        for (uint32_t e = threadIdx.x; e < max_depth; ++e) n += s_ends[e];
+        if (n) atomicAdd(&ray_stats[(blockIdx.x & (PRT_RAY_STAT_SLOTS - 1u)) * PRT_MAX_DEPTH + threadIdx.x], n);
+    }
+}
+
+// Pixel-major path ids (prt_path_id.h; compact primary rays, batches of at least 8 samples): k_accumulate (STAT = false) and
+// k_accumulate_stat<false, false> (STAT = true) for rad[pixel * S + sample].  Still one thread per pixel, the same additions in
+// the same order (s = 0 .. S - 1: that fixes the fp32 sums) and the same per-depth histogram; what differs is who loads.  The
+// samples of a pixel are adjacent now, so a lane that loaded its own pixel's next eight samples would touch a 128-B line of
+// its own per load instruction, 64 lines per instruction instead of 8 (measured: 4.42 ms instead of 1.25 ms on C3).  Instead a
+// wave loads the next eight samples of its 64 pixels COOPERATIVELY, eight lanes per pixel (one full line per pixel where S is
+// a multiple of 8), eight pixels per load instruction, eight instructions in flight, and transposes them through LDS: lane p
+// then reads pixel p's eight samples.  Rows are padded to nine float4 (stride 36 dwords: the 16 lanes of a ds_read_b128 pass
+// fall on distinct banks).  Pixels outside the image or ended by their primary ray (pix_end) are not loaded.
+#ifndef PRT_ACC_PM_CHUNK
+#define PRT_ACC_PM_CHUNK 8  // samples per chunk: 8, or 16 (A/B: 128-thread blocks, two waves per SIMD, 2.39 ms on C3)
+#endif
+#define PRT_ACC_PM_BLOCK (PRT_ACC_PM_CHUNK == 8 ? 256 : 128)
+template <bool STAT>
+__global__ void __launch_bounds__(PRT_ACC_PM_BLOCK) k_accumulate_pixel_major(const float4* __restrict__ rad, float4* __restrict__ film_local,
+                                                                float2* __restrict__ stat, PrtTileMap tm, uint32_t S, uint32_t max_depth,
+                                                                int update_film, unsigned long long* __restrict__ ray_stats,
+                                                                const float4* __restrict__ pix_end) {
+    __shared__ uint32_t s_ends[PRT_MAX_DEPTH];  // per-depth ray counts: see k_accumulate
+    constexpr uint32_t C = PRT_ACC_PM_CHUNK, ROW = C + 1u, BLOCK = PRT_ACC_PM_BLOCK;
+    __shared__ float4 s_t[BLOCK / 64u][64u * ROW];  // per wave: [pixel of the wave][sample of the chunk], rows padded by one
+    if (threadIdx.x < PRT_MAX_DEPTH) s_ends[threadIdx.x] = 0u;
+    __syncthreads();
+    const PrtPathIdOrder ids{tm.n_pix_local, 0.0f, S, 0u, 0u};  // (encode only)
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+    float4* const t = s_t[wave];
+    for (uint32_t pl0 = blockIdx.x * BLOCK; pl0 < tm.n_pix_local; pl0 += gridDim.x * BLOCK) {  // block-uniform trip count
+    const uint32_t pl = pl0 + threadIdx.x;
+    const uint32_t wave_pl = pl0 + 64u * wave;  // the wave's first pixel
+    uint32_t x, y;
+    const bool valid = pl < tm.n_pix_local && tile_pixel(tm, pl, x, y);
+    float4 f = valid ? film_local[pl] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float2 m2 = make_float2(0.f, 0.f);
+    if (STAT && valid) m2 = stat[pl];
+    float4 E = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xFFFFFFFEu));
+    if (valid && pix_end) E = pix_end[pl];
+    const bool ended = __float_as_uint(E.w) != 0xFFFFFFFEu;
+    const unsigned long long need = __ballot(valid && !ended);  // the wave's pixels whose samples are in rad[]
+    const float weight = 1.0f;
+    // The per-depth histogram of the last segment indices.  k_accumulate's wave ballot per sample and depth is most of its
+    // instructions (40 of ~55 per eight samples at max_depth 5), and with the transposition's LDS this kernel has half its
+    // occupancy to hide them behind.  Up to eight depths each lane counts its own pixel's indices in the bytes of one 64-bit
+    // register instead (index e adds 1 << 8 e) and adds the bytes to the block's counters every 31 chunks (248 samples: a byte
+    // cannot overflow) and after the last one; counts do not depend on the order.  Deeper paths keep the ballots.
+    const bool packed = max_depth <= 8u;
+    unsigned long long h = 0ull;
+    // load instruction j of a chunk: C lanes per pixel, pixel (64 / C) j + lane / C of the wave, sample s0 + lane % C
+    const uint32_t cs = lane % C, cq = lane / C;
+    float4 v[C];
+    auto load_chunk = [&](uint32_t s0) {
+#pragma unroll
+        for (uint32_t j = 0; j < C; ++j) {
+            const uint32_t q = (64u / C) * j + cq;
+            v[j] = (((need >> q) & 1ull) != 0ull && s0 + cs < S) ? ld_stream(&rad[prt_path_id_encode(ids, wave_pl + q, s0 + cs)]) : E;
+        }
+    };
+    load_chunk(0u);
+    for (uint32_t s0 = 0; s0 < S; s0 += C) {  // block-uniform trip counts
+        // The rows belong to this wave alone and a wave's LDS instructions execute in order, so what orders the writes of the
+        // eight loaders of a row against its reader (and the reads against the next chunk's writes) is the order of the
+        // instructions: wave-level fences keep the compiler from moving them, no other wave has to wait.
+#pragma unroll
+        for (uint32_t j = 0; j < C; ++j) t[((64u / C) * j + cq) * ROW + cs] = v[j];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (s0 + C < S) load_chunk(s0 + C);  // the next chunk's loads fly while this one is summed
+#pragma unroll
+        for (uint32_t j = 0; j < C; ++j) {
+            if (s0 + j >= S) break;
+            uint32_t e = 0xFFFFFFFFu;
+            if (valid) {
+                const float4 r = ended ? E : t[lane * ROW + j];
+                f.x += r.x * weight;
+                f.y += r.y * weight;
+                f.z += r.z * weight;
+                f.w += weight;
+                if (STAT) {  // (k_accumulate_stat's single fp32 operations)
+                    const float lum = __fadd_rn(__fadd_rn(__fmul_rn(0.2126f, r.x), __fmul_rn(0.7152f, r.y)), __fmul_rn(0.0722f, r.z));
+                    m2.x = __fadd_rn(m2.x, lum);
+                    m2.y = __fadd_rn(m2.y, __fmul_rn(lum, lum));
+                }
+                e = __float_as_uint(r.w);
+            }
+            if (packed) {
+                if (e < 8u) h += 1ull << (8u * e);
+            } else {
+                for (uint32_t dd = 0; dd < max_depth; ++dd) {
+                    const unsigned long long mk = __ballot(e == dd);
+                    if (mk != 0ull && lane == 0) atomicAdd(&s_ends[dd], (uint32_t)__popcll(mk));
+                }
+            }
+        }
+        if (packed && ((s0 / C) % 31u == 30u || s0 + C >= S)) {
+            for (uint32_t dd = 0; dd < max_depth; ++dd) {
+                const uint32_t n = (uint32_t)(h >> (8u * dd)) & 0xFFu;
+                if (n) atomicAdd(&s_ends[dd], n);
+            }
+            h = 0ull;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (the next chunk overwrites the rows)
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (valid && update_film) {
+        film_local[pl] = f;
+        if (STAT) stat[pl] = m2;
     }
     }
     __syncthreads();
@@ -3788,9 +3903,9 @@ bool prt_launch_raygen(hipStream_t st, PrtRaygenInst inst, const PrtRaygenArgs& 
     const DevLens& l = or_empty(a.lens);
 #define PRT_RAYGEN_HEAD a.cam, a.tm, S, a.first_sample, a.seed, a.out.o, a.out.d, a.out.t, a.out.hit
 #define PRT_RAYGEN_TAIL a.rad, a.counts, a.work, a.max_depth, a.sp
-#define PRT_RAYGEN_ARGS_PLAIN sc, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL, nullptr
+#define PRT_RAYGEN_ARGS_PLAIN sc, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL, nullptr, 0u
     // (the compact instance stores nothing in hit / hd2 per ray slot: its hd2 argument is the front-pixel list, or null)
-#define PRT_RAYGEN_ARGS_COMPACT sc, PRT_RAYGEN_HEAD, a.primary_walk ? a.out.hd2 : nullptr, PRT_RAYGEN_TAIL, a.compact_pix
+#define PRT_RAYGEN_ARGS_COMPACT sc, PRT_RAYGEN_HEAD, a.primary_walk ? a.out.hd2 : nullptr, PRT_RAYGEN_TAIL, a.compact_pix, a.pixel_major_ids ? 1u : 0u
 #define PRT_RAYGEN_ARGS_ENV sc, e, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL
 #define PRT_RAYGEN_ARGS_LENS sc, l, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL
 #define PRT_RAYGEN_ARGS_LENS_ENV sc, e, l, PRT_RAYGEN_HEAD, a.out.hd2, PRT_RAYGEN_TAIL
@@ -3994,13 +4109,28 @@ void prt_launch_shade_divstats(hipStream_t st, const DevScene& sc, const PrtRayB
 
 void prt_launch_primary_hit(hipStream_t st, const DevScene& sc, const PrtPrimary& pr, const uint32_t* hit, float4* pix,
                             const uint32_t* counts) {
-    hipLaunchKernelGGL(k_primary_hit, dim3(blocks_for(pr.n_pix_local)), dim3(256), 0, st, sc, pr, hit, pix, counts);
+    hipLaunchKernelGGL(k_primary_hit, dim3(blocks_for(pr.ids.n_pix_local)), dim3(256), 0, st, sc, pr, hit, pix, counts);
 }
 
 bool prt_launch_accumulate(hipStream_t st, PrtAccumulateInst inst, const PrtAccumulateArgs& a) {
     const uint32_t nb = blocks_for(a.tm.n_pix_local ? a.tm.n_pix_local : 1);
     const dim3 grid(nb < 8192u ? nb : 8192u);
     const int upd = a.update_film ? 1 : 0;
+    if (a.pixel_major_ids) {
+        // Pixel-major path ids come with compact primary rays, whose plan names k_accumulate or, with film statistics,
+        // k_accumulate_stat<false, false>: the same sums from the other layout of rad[] (k_accumulate_pixel_major), launched
+        // under the plan's instance, which is what prt_batch_instance goes on reporting
+        if (inst != PRT_I_k_accumulate && inst != PRT_INST(k_accumulate_stat, ff)) return false;
+        const uint32_t nbp = (a.tm.n_pix_local + PRT_ACC_PM_BLOCK - 1u) / PRT_ACC_PM_BLOCK;
+        const dim3 grid_pm(nbp < 8192u ? (nbp ? nbp : 1u) : 8192u);
+        if (inst == PRT_I_k_accumulate)
+            hipLaunchKernelGGL((k_accumulate_pixel_major<false>), grid_pm, dim3(PRT_ACC_PM_BLOCK), 0, st, a.rad, a.film_local, a.stat, a.tm, a.S, a.max_depth, upd,
+                               a.ray_stats, a.pix_end);
+        else
+            hipLaunchKernelGGL((k_accumulate_pixel_major<true>), grid_pm, dim3(PRT_ACC_PM_BLOCK), 0, st, a.rad, a.film_local, a.stat, a.tm, a.S, a.max_depth, upd,
+                               a.ray_stats, a.pix_end);
+        return true;
+    }
 #define PRT_ACC_ARGS_PLAIN a.rad, a.film_local, a.tm, a.S, a.max_depth, upd, a.ray_stats, a.pix_end
 #define PRT_ACC_ARGS_LIT a.rad, a.lrad, a.film_local, a.tm, a.S, a.max_depth, upd, a.ray_stats
 #define PRT_ACC_ARGS_STAT a.rad, a.lrad, a.film_local, a.stat, a.tm, a.S, a.max_depth, upd, a.ray_stats, a.pix_end, a.list

@@ -52,3 +52,18 @@ inline bool prt_primary_reusable(const PrtPrimaryKey& held, const PrtPrimaryKey&
            held.lens == now.lens && held.jitter == now.jitter && held.rr_depth == now.rr_depth && held.clamp == now.clamp &&
            held.listed == now.listed && held.instrumented == now.instrumented && held.exact == now.exact;
 }
+
+// What a context holds: the key above, and how the kept stage numbers its paths (prt_path_id.h).  The stage stores a path-id
+// list per ray slot, so a batch may only start from ids of its own order and, pixel-major, of its own sample count: id_S is
+// the divisor the ids were built for (0 with sample-major ids).  (The batch size is in the key above as S_cur and setting the
+// path_id_order tunable bumps scene_gen, so these repeat what the key implies: spelled out all the same, a stale id is a
+// sample added to the wrong pixel.)
+struct PrtPrimaryStageKey {
+    PrtPrimaryKey batch;
+    uint32_t id_order;  // 0 sample-major, 1 pixel-major
+    uint32_t id_S;
+};
+
+inline bool prt_primary_stage_reusable(const PrtPrimaryStageKey& held, const PrtPrimaryStageKey& now) {
+    return prt_primary_reusable(held.batch, now.batch) && held.id_order == now.id_order && held.id_S == now.id_S;
+}
