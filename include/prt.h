@@ -1238,8 +1238,12 @@ int prt_radiance_lit_pb_device(PrtContext* ctx, const PrtRadianceQuery* q, uint3
  *  Coverage: face f with UVs a, b, c (fp32 widened to double; every operation below rounded once, no contraction):
  *      A2 = (bx-ax)(cy-ay) - (by-ay)(cx-ax)
  *      E0 = (bx-px)(cy-py) - (by-py)(cx-px)   E1 = (cx-px)(ay-py) - (cy-py)(ax-px)   E2 = (ax-px)(by-py) - (ay-py)(bx-px)
- *    covers the texel iff its UVs are finite, A2 != 0, and E0, E1, E2 are all >= 0 (A2 > 0) or all <= 0 (A2 < 0): edges are
- *    inclusive, so a shared edge leaves no crack.  The owner is the lowest covering face index, whatever the launch order.
+ *    covers the texel iff its UVs are finite, A2 != 0, E0, E1, E2 are all >= 0 (A2 > 0) or all <= 0 (A2 < 0), and the centre
+ *    lies in the face's closed UV box: min(ax,bx,cx) <= px <= max(ax,bx,cx) and min(ay,by,cy) <= py <= max(ay,by,cy),
+ *    plain double comparisons.  Edges are inclusive, so a shared edge leaves no crack.  In exact arithmetic the box follows
+ *    from the edge functions; it is part of the rule because the rounded edge functions of a near-collinear face can all be
+ *    exactly zero along its whole line, far from the face: the box bounds what rounding can claim.  The owner is the lowest
+ *    covering face index, whatever the launch order.
  *  Surface: b1 = (float)(E1 / A2), b2 = (float)(E2 / A2), w0 = 1.0f - b1 - b2; then in fp32 per component
  *    x = (w0 * X0 + b1 * X1) + b2 * X2, for the position from the face's vertices and for ns from its vertex normals (the
  *    hit reconstruction's order).  l2 = dot(ns, ns), (x*x + y*y) + z*z: a texel with !(l2 > 0 && l2 < inf) is degenerate:

@@ -41,16 +41,21 @@ __device__ inline void bk_centre(uint32_t i, uint32_t j, uint32_t W, uint32_t H,
     py = 1.0 - ((double)i + 0.5) / (double)H;
 }
 
-// The edge functions of a face with area at (px, py); true: the face covers the point, edges included.
+// The edge functions of a face with area at (px, py); true: the face covers the point, edges included: the signs agree
+// with the area's and the point lies in the face's closed UV box.  (In exact arithmetic the box follows from the signs; in
+// rounded arithmetic it bounds what a sliver, whose edge functions round to zero all along its line, can claim.)
 __device__ inline bool bk_covers(const BkFace& e, double px, double py, double& E1, double& E2) {
     const double E0 = (e.bx - px) * (e.cy - py) - (e.by - py) * (e.cx - px);
     E1 = (e.cx - px) * (e.ay - py) - (e.cy - py) * (e.ax - px);
     E2 = (e.ax - px) * (e.by - py) - (e.ay - py) * (e.bx - px);
-    return e.A2 > 0.0 ? (E0 >= 0.0 && E1 >= 0.0 && E2 >= 0.0) : (E0 <= 0.0 && E1 <= 0.0 && E2 <= 0.0);
+    const bool in_box = fmin(e.ax, fmin(e.bx, e.cx)) <= px && px <= fmax(e.ax, fmax(e.bx, e.cx)) &&
+                        fmin(e.ay, fmin(e.by, e.cy)) <= py && py <= fmax(e.ay, fmax(e.by, e.cy));
+    const bool signs = e.A2 > 0.0 ? (E0 >= 0.0 && E1 >= 0.0 && E2 >= 0.0) : (E0 <= 0.0 && E1 <= 0.0 && E2 <= 0.0);
+    return signs && in_box;
 }
 
 // One wave per face: its 64 lanes stride the texels of the face's bounding box, clipped to the map and widened by a texel
-// on every side (the box only bounds the work: the edge functions decide).  The owner is the lowest covering face, by an
+// on every side (the widened box only bounds the work: bk_covers decides, closed box included).  The owner is the lowest covering face, by an
 // integer atomicMin: the result does not depend on the order the waves run in.
 __global__ __launch_bounds__(256) void k_bk_cover(PrtBakeFaces fc, PrtBakeMap m, uint32_t* __restrict__ counts) {
     const uint64_t f64 = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);

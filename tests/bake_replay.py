@@ -7,6 +7,9 @@ RNG (pcg_hash, path_seed, Random, the rejection sampler of RandomUnitVector) in 
   * dilate(coverage, rgb, passes): the gutter fill.
   * the shapes the tests bake (square, cube with the PLY's overlapping UVs, cube with an atlas that leaves gutters), the
     map sizes, and the emitter of the form-factor test.
+  * the shapes beyond toy maps (BIG_SHAPES: a grid whose vertices are texel centres, a 2,003-face soup, faces of magnitude
+    2^20, near-collinear slivers, a 20 k-face scan and a placed copy under planar projections) with the maps they are baked
+    on, and exact_owner: the owner in exact rational arithmetic.
 
 No kernel code and no GPU is involved."""
 from __future__ import annotations
@@ -117,26 +120,48 @@ def _edges(uv, px, py):
     return A2, E0, E1, E2
 
 
+def centres(W, H):
+    """(px, py) of the W * H texels in map order, in double"""
+    t = np.arange(W * H)
+    return ((t % W).astype(np.float64) + 0.5) / float(W), 1.0 - ((t // W).astype(np.float64) + 0.5) / float(H)
+
+
+def in_box(uv, px, py):
+    """The centre lies in the face's closed UV box: double comparisons of the widened fp32 UVs with the centre"""
+    x, y = uv[:, 0].astype(np.float64), uv[:, 1].astype(np.float64)
+    return (x.min() <= px) & (px <= x.max()) & (y.min() <= py) & (py <= y.max())
+
+
+def covers(uv, px, py):
+    """The coverage rule of one face at the points -> (bool per point, or None: the face is skipped; A2, E1, E2)"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        A2, E0, E1, E2 = _edges(uv, px, py)
+        if not np.isfinite(uv).all() or A2 == 0.0:
+            return None, A2, E1, E2
+        signs = ((E0 >= 0) & (E1 >= 0) & (E2 >= 0)) if A2 > 0 else ((E0 <= 0) & (E1 <= 0) & (E2 <= 0))
+        return signs & in_box(uv, px, py), A2, E1, E2
+
+
 def surface(faces, W, H, mat16=None, inv16=None):
     """faces = (uv, position, normal) as mesh_faces gives them; mat16 / inv16: a placed copy's column-major Mat and Inv.
     -> dict(owner [H, W] uint32, coverage [H, W] uint8, bary [H, W, 2], position, normal [H, W, 3], n_covered,
-    n_degenerate, n_faces_skipped)."""
+    n_degenerate, n_faces_skipped; coverers [H, W]: how many faces' rule covers the texel, face_texels [F]: how many texels
+    each face's rule covers)."""
     uv, pos, nrm = (np.asarray(a, F) for a in faces)
     n = W * H
-    t = np.arange(n)
-    i, j = t // W, t % W
-    px = (j.astype(np.float64) + 0.5) / float(W)
-    py = 1.0 - (i.astype(np.float64) + 0.5) / float(H)
+    px, py = centres(W, H)
     owner = np.full(n, NONE, np.uint32)
     b1, b2 = np.zeros(n, F), np.zeros(n, F)
     skipped = 0
+    coverers, face_texels = np.zeros(n, np.int32), np.zeros(len(uv), np.int64)     # (of the rule alone: for the tests' conditions)
     with np.errstate(invalid="ignore", over="ignore"):
         for f in range(len(uv)):
-            A2, E0, E1, E2 = _edges(uv[f], px, py)
-            if not np.isfinite(uv[f]).all() or A2 == 0.0:
+            cov, A2, E1, E2 = covers(uv[f], px, py)
+            if cov is None:
                 skipped += 1
                 continue
-            cov = ((E0 >= 0) & (E1 >= 0) & (E2 >= 0)) if A2 > 0 else ((E0 <= 0) & (E1 <= 0) & (E2 <= 0))
+            coverers += cov
+            face_texels[f] = cov.sum()
             new = cov & (owner == NONE)          # faces in ascending order: the first to cover a texel is the lowest
             owner[new] = f
             b1[new] = (E1[new] / A2).astype(F)
@@ -163,7 +188,7 @@ def surface(faces, W, H, mat16=None, inv16=None):
     bary[at[good], 1] = b2[own][good]
     return dict(owner=owner.reshape(H, W), coverage=(owner != NONE).astype(np.uint8).reshape(H, W), bary=bary.reshape(H, W, 2),
                 position=position.reshape(H, W, 3), normal=normal.reshape(H, W, 3), n_covered=int(good.sum()),
-                n_degenerate=int((~good).sum()), n_faces_skipped=skipped)
+                n_degenerate=int((~good).sum()), n_faces_skipped=skipped, coverers=coverers.reshape(H, W), face_texels=face_texels)
 
 
 def interior(surf, margin=0.05):
@@ -250,13 +275,144 @@ COPY_SRT = (1.7, (20.0, 35.0, -10.0), (0.4, 1.1, -0.3))   # the placed copy: sca
 SHAPES = ("square", "cube", "cube_atlas", "copy", "copy_atlas")
 
 
+# ---- shapes beyond toy maps: many faces, maps of several compaction trips (1024 texels each) ----------------------------------
+BIG_SIZES = ((80, 96), (33, 129), (128, 128))       # (H, W): 7.5 trips, 4.2 trips, 16 whole trips
+STRIPS = ((1, 2049), (2049, 1))
+DYADIC = ((16, 16), (32, 32), (16, 64))             # the grid's rule is exact on these
+SLIVER_SIZES = ((16, 16), (17, 17), (12, 12))
+BIG_SHAPES = ("grid", "soup", "huge", "slivers", "bunny", "ico_copy")
+SHAPE_SIZES = dict(grid=BIG_SIZES + STRIPS + DYADIC, soup=BIG_SIZES + STRIPS, huge=BIG_SIZES, slivers=BIG_SIZES + SLIVER_SIZES,
+                   bunny=BIG_SIZES, ico_copy=BIG_SIZES)
+SOUP_FACES = 2003
+SOUP_TWINS = (700, 1500)                            # two faces of the soup with identical UVs
+SLIVER_0 = ((0.0, 0.0), (0.5, 0.5), (1e-30, 2e-30))   # rounded E0 = E1 = E2 = 0 at every point of the diagonal of the map
+
+
+def soup_mesh(uv, seed):
+    """Three vertices of their own per face [F, 3, 2]: small random triangles in [-1, 1]^3, random unit vertex normals"""
+    rng = np.random.default_rng(seed)
+    n = len(uv)
+    pos = (rng.uniform(-1.0, 1.0, (n, 1, 3)) + rng.uniform(-0.1, 0.1, (n, 3, 3))).astype(F)
+    nrm = rng.normal(size=(n, 3, 3))
+    nrm = (nrm / np.linalg.norm(nrm, axis=2, keepdims=True)).astype(F)
+    return prt.Mesh(vertices=pos.reshape(-1, 3), normals=nrm.reshape(-1, 3), indices=np.arange(3 * n, dtype=np.uint32).reshape(n, 3),
+                    uvs=np.asarray(uv, F).reshape(-1, 2))
+
+
+def grid_mesh():
+    """An 8 x 8 vertex grid, 98 faces: UV vertices at (4k + 1) / 32, texel centres of a 16-wide map; the diagonal alternates
+    per cell; about a third of the faces are wound clockwise.  Positions and normals are the square's."""
+    rng = np.random.default_rng(21)
+    k = (4.0 * np.arange(8) + 1.0) / 32.0
+    uv = np.array([[k[c], k[r]] for r in range(8) for c in range(8)], F)
+    idx = []
+    for r in range(7):
+        for c in range(7):
+            v00, v10, v01, v11 = r * 8 + c, r * 8 + c + 1, (r + 1) * 8 + c, (r + 1) * 8 + c + 1
+            idx += [[v00, v10, v11], [v00, v11, v01]] if (r + c) % 2 == 0 else [[v00, v10, v01], [v10, v11, v01]]
+    idx = np.array(idx, np.uint32)
+    flip = rng.random(len(idx)) < 1.0 / 3.0
+    idx[flip] = idx[flip][:, [0, 2, 1]]
+    pos = np.stack([2.0 * uv[:, 0] - 1.0, np.zeros(64), 1.0 - 2.0 * uv[:, 1]], 1).astype(F)
+    return prt.Mesh(vertices=pos, normals=np.tile(np.array([[0.0, 1.0, 0.0]], F), (64, 1)), indices=idx, uvs=uv)
+
+
+def soup_uvs():
+    """SOUP_FACES random triangles: centres uniform in [-0.1, 1.1]^2, vertices within +-size of the centre, size log-uniform
+    in 2e-3 .. 0.12 (from well below a texel of every map used to a dozen texels across; the upper end is what brings the
+    covered share of 2,003 faces above 30 % on every map, the strips included), random winding, one pair of identical faces"""
+    rng = np.random.default_rng(31)
+    n = SOUP_FACES
+    centre = rng.uniform(-0.1, 1.1, (n, 1, 2))
+    size = np.exp(rng.uniform(np.log(2e-3), np.log(0.12), (n, 1, 1)))
+    uv = (centre + size * rng.uniform(-1.0, 1.0, (n, 3, 2))).astype(F)
+    uv[SOUP_TWINS[1]] = uv[SOUP_TWINS[0]]
+    return uv
+
+
+def huge_uvs():
+    """Three small faces first, which keep their texels; then a face over the whole map, one of magnitude 2^20 over it too,
+    and one of magnitude 2^20 wholly outside"""
+    B = 2.0 ** 20
+    return np.array([[[0.1, 0.1], [0.4, 0.15], [0.2, 0.45]], [[0.9, 0.9], [0.6, 0.8], [0.85, 0.55]], [[0.3, 0.7], [0.5, 0.6], [0.45, 0.95]],
+                     [[-1, -1], [3, -1], [-1, 3]], [[-B, -B], [B, -B], [0, B]], [[B, B], [B / 2, B], [B, B / 2]]], F)
+
+
+def sliver_uvs():
+    """A few dozen near-collinear faces with area (A2 != 0): SLIVER_0; along diagonals and anti-diagonals, short, so that
+    their lines cross texel centres far outside their boxes; along axis-aligned lines, c one fp32 ulp off the line a-b;
+    along arbitrary directions, c the fp32 rounding of a point of a-b, or an ulp from it; third vertices down to 1e-30 and
+    to subnormals."""
+    rng = np.random.default_rng(41)
+    up = lambda v: np.nextafter(F(v), F(np.inf))
+    f = [SLIVER_0]
+    for tiny in (1e-30, 3e-39, 1.4e-45):                 # (the last two are subnormal in fp32)
+        f.append(((0.0, 0.0), (0.25, 0.25), (tiny, 2 * tiny)))
+        f.append(((0.0, 0.0), (2 * tiny, tiny), (0.3125, 0.3125)))
+        f.append(((0.0, 0.0), (0.375, 0.0), (0.1, tiny)))            # along v = 0
+        f.append(((0.0, 0.0), (tiny, 0.2), (0.0, 0.625)))            # along u = 0
+    for lo, hi in ((0.125, 0.375), (0.53125, 0.59375), (0.25, 0.28125)):
+        f.append(((lo, lo), (hi, hi), (up(lo), lo)))                                  # diagonal, an ulp off at a
+        f.append(((lo, 1.0 - lo), (hi, 1.0 - hi), (up((lo + hi) / 2), 1.0 - (lo + hi) / 2)))      # anti-diagonal
+    for v in (0.3, 0.53125, 0.96875):
+        f.append(((0.1, v), (0.9, v), (0.5, up(v))))                                  # horizontal, c an ulp above
+        f.append(((v, 0.2), (up(v), 0.55), (v, 0.7)))                                 # vertical, b an ulp right
+    while len(f) < 40:                                   # arbitrary directions
+        a, b = rng.uniform(0.0, 1.0, 2).astype(F), rng.uniform(0.0, 1.0, 2).astype(F)
+        s = rng.uniform(0.2, 0.8)
+        c = (a.astype(np.float64) * (1.0 - s) + b.astype(np.float64) * s).astype(F)
+        if len(f) % 2:
+            c[0] = up(c[0])
+        f.append((a, b, c))
+    return np.array(f, F)
+
+
 @functools.lru_cache(maxsize=None)
 def shape(name):
     """dict(mesh, uvs (per call, or None: the mesh's own), placed) of a shape; computed once, shared"""
     if name == "square":
         return dict(mesh=square_mesh(), uvs=None, placed=False)
+    if name == "grid":
+        return dict(mesh=grid_mesh(), uvs=None, placed=False)
+    if name in ("soup", "huge", "slivers"):
+        uv, seed = dict(soup=(soup_uvs, 32), huge=(huge_uvs, 33), slivers=(sliver_uvs, 34))[name]
+        return dict(mesh=soup_mesh(uv(), seed), uvs=None, placed=False)
+    if name in ("bunny", "ico_copy"):
+        m = prt.scenes.refined("bunny.ply", 20_000) if name == "bunny" else prt.scenes.refined("icosahedron.ply", 2000)
+        return dict(mesh=m, uvs=prt.scenes.planar_uvs(m, axes=(0, 1)), placed=name == "ico_copy")
     m = cube_mesh()
     return dict(mesh=m, uvs=cube_atlas_uvs(m) if name.endswith("atlas") else None, placed=name.startswith("copy"))
+
+
+def exact_owner(uv, W, H):
+    """The lowest face whose closed triangle holds the texel centre, in exact rational arithmetic -> (owner [H, W] uint32,
+    number of exact coverers [H, W]).  fractions.Fraction turns the fp32 UVs and the centres (2j + 1) / (2W),
+    1 - (2i + 1) / (2H) into integers over one common denominator; the edge functions are then integer arithmetic."""
+    from fractions import Fraction
+    from math import lcm
+    q = [[Fraction(float(v)) for v in face.ravel()] for face in np.asarray(uv, F)]
+    cx = [Fraction(2 * j + 1, 2 * W) for j in range(W)]
+    cy = [1 - Fraction(2 * i + 1, 2 * H) for i in range(H)]
+    D = lcm(*(v.denominator for face in q for v in face), *(v.denominator for v in cx + cy))
+    whole = lambda v: int(v * D)
+    assert all((v * D).denominator == 1 for face in q for v in face)
+    px = np.tile(np.array([whole(v) for v in cx], object), H)
+    py = np.repeat(np.array([whole(v) for v in cy], object), W)
+    owner = np.full(W * H, NONE, np.uint32)
+    count = np.zeros(W * H, np.int64)
+    for f, face in enumerate(q):
+        ax, ay, bx, by, cx_, cy_ = (whole(v) for v in face)
+        A2 = (bx - ax) * (cy_ - ay) - (by - ay) * (cx_ - ax)
+        if A2 == 0:
+            continue
+        s = 1 if A2 > 0 else -1
+        E0 = ((bx - px) * (cy_ - py) - (by - py) * (cx_ - px)) * s
+        E1 = ((cx_ - px) * (ay - py) - (cy_ - py) * (ax - px)) * s
+        E2 = ((ax - px) * (by - py) - (ay - py) * (bx - px)) * s
+        cov = ((E0 >= 0) & (E1 >= 0) & (E2 >= 0)).astype(bool)
+        owner[cov & (owner == NONE)] = f
+        count += cov
+    return owner.reshape(H, W), count.reshape(H, W)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,6 +1,8 @@
 """The numpy restatement of surface baking (tests/bake_replay.py) against what the header promises, without a GPU: the
-coverage rule on small layouts whose answer is known by hand, and the conditions the GPU tests (tests/test_gpu_bake.py)
-rely on, shown from the reference alone."""
+coverage rule on small layouts whose answer is known by hand, and the conditions the GPU tests (tests/test_gpu_bake.py,
+tests/test_gpu_bake_shapes.py) rely on, shown from the reference alone: for the shapes beyond toy maps, the grid's owners
+against exact rational arithmetic and its no-crack law, the soup's shares, and the slivers under the rule with and without
+the box condition."""
 import numpy as np
 import pytest
 
@@ -186,3 +188,197 @@ def test_form_factor_case_keeps_every_texel_between_5_and_95_percent():
     n = s["normal"].reshape(-1, 3).astype(np.float64)
     Fq = cf.form_factor(p, n, cf.quad_corners(mat, br.FF_QUAD["width"], br.FF_QUAD["height"]))
     assert Fq.min() >= 0.05 and Fq.max() <= 0.95, (Fq.min(), Fq.max())
+
+
+# ---- shapes beyond toy maps (br.BIG_SHAPES): what makes each of them a test, shown from the replay alone ------------------------
+def _uv(name):
+    s = br.shape(name)
+    return br.mesh_faces(s["mesh"], s["uvs"])[0]
+
+
+def _boxes(uv):
+    """[F, 4]: min u, max u, min v, max v of every face, in double"""
+    u, v = uv[..., 0].astype(np.float64), uv[..., 1].astype(np.float64)
+    return np.stack([u.min(1), u.max(1), v.min(1), v.max(1)], 1)
+
+
+def _sane(s):
+    """What the bit-for-bit comparisons on the GPU need of a reference: no NaN anywhere (a NaN has no one bit pattern)"""
+    return not (np.isnan(s["position"]).any() or np.isnan(s["normal"]).any() or np.isnan(s["bary"]).any())
+
+
+def _old_rule(uv, px, py):
+    """The rule before the box condition: the signs of the rounded edge functions alone"""
+    A2, E0, E1, E2 = br._edges(uv, px, py)
+    return ((E0 >= 0) & (E1 >= 0) & (E2 >= 0)) if A2 > 0 else ((E0 <= 0) & (E1 <= 0) & (E2 <= 0))
+
+
+def test_big_shapes_use_maps_of_several_compaction_trips():
+    assert all(H * W > 4 * 1024 for H, W in br.BIG_SIZES) and (128 * 128) % 1024 == 0 and (80 * 96) % 1024 == 512
+    for name in br.BIG_SHAPES:
+        assert set(br.BIG_SIZES) <= set(br.SHAPE_SIZES[name])
+    assert set(br.STRIPS) <= set(br.SHAPE_SIZES["soup"]) and set(br.STRIPS + br.DYADIC) <= set(br.SHAPE_SIZES["grid"])
+    assert set(br.SLIVER_SIZES) <= set(br.SHAPE_SIZES["slivers"])
+
+
+def test_grid_is_98_faces_a_third_of_them_clockwise():
+    uv = _uv("grid")
+    a, b, c = (uv[:, k].astype(np.float64) for k in range(3))
+    A2 = (b[:, 0] - a[:, 0]) * (c[:, 1] - a[:, 1]) - (b[:, 1] - a[:, 1]) * (c[:, 0] - a[:, 0])
+    assert len(uv) == 98 and len(uv) % 4 != 0 and (np.abs(A2) == 1.0 / 64.0).all()
+    assert 0.25 <= (A2 < 0).mean() <= 0.42, (A2 < 0).mean()
+    assert np.array_equal(np.unique(uv), ((4.0 * np.arange(8) + 1.0) / 32.0).astype(F))
+
+
+@pytest.mark.parametrize("H,W", br.DYADIC)
+def test_grid_owner_is_the_lowest_exact_coverer_on_dyadic_maps(H, W):
+    uv = _uv("grid")
+    s = br.reference("grid", H, W)
+    owner, count = br.exact_owner(uv, W, H)
+    tied = int((count > 1).sum())
+    print(f"grid {H} x {W}: covered {(count > 0).sum()}, tied {tied}, most coverers {count.max()}")
+    assert np.array_equal(s["owner"], owner) and np.array_equal(s["coverers"], count) and s["n_degenerate"] == 0
+    assert tied > 0
+    if (H, W) == (16, 16):      # vertices are texel centres: ties on vertices, axis-aligned edges and diagonals
+        assert ((count > 0).sum(), tied, count.max()) == (225, 195, 8)
+
+
+@pytest.mark.parametrize("H,W", [(24, 24), (17, 33), (80, 96), (100, 100)])
+def test_grid_leaves_no_crack_and_claims_nothing_outside(H, W):
+    s = br.reference("grid", H, W) if (H, W) in br.SHAPE_SIZES["grid"] else br.surface(br.mesh_faces(br.shape("grid")["mesh"]), W, H)
+    px, py = (a.reshape(H, W) for a in br.centres(W, H))
+    lo, hi = 1.0 / 32.0, 29.0 / 32.0
+    inside = (lo < px) & (px < hi) & (lo < py) & (py < hi)
+    outside = (px < lo) | (px > hi) | (py < lo) | (py > hi)
+    assert inside.sum() > 100 and outside.sum() > 10
+    assert (s["coverage"][inside] == 1).all() and (s["coverage"][outside] == 0).all() and s["n_degenerate"] == 0 and _sane(s)
+
+
+@pytest.mark.parametrize("H,W", br.SHAPE_SIZES["grid"])
+def test_grid_strips_and_large_maps_are_covered_and_uncovered(H, W):
+    s = br.reference("grid", H, W)
+    assert 0 < s["n_covered"] < H * W and s["n_faces_skipped"] == 0 and _sane(s)
+
+
+@pytest.mark.parametrize("H,W", br.SHAPE_SIZES["soup"])
+def test_soup_conditions(H, W):
+    uv = _uv("soup")
+    s = br.reference("soup", H, W)
+    cov = s["coverage"].ravel() != 0
+    share, multi, nothing = cov.mean(), (s["coverers"].ravel()[cov] > 1).mean(), (s["face_texels"] == 0).mean()
+    print(f"soup {H} x {W}: covered {share:.3f}, of them with two or more coverers {multi:.3f}, faces covering nothing {nothing:.3f}")
+    assert len(uv) == br.SOUP_FACES == 2003 and len(uv) % 4 != 0 and s["n_faces_skipped"] == 0 and s["n_degenerate"] == 0 and _sane(s)
+    assert np.array_equal(cov, s["coverers"].ravel() > 0)
+    assert 0.30 <= share <= 0.80
+    # every 1024-texel stretch of the compaction holds covered and uncovered texels (the strips' last stretch is one texel)
+    for start in range(0, H * W, 1024):
+        part = cov[start:start + 1024]
+        assert len(part) == 1 or (part.any() and not part.all()), start
+    assert multi >= 0.10 and nothing >= 0.25
+    a, b = br.SOUP_TWINS
+    assert np.array_equal(uv[a], uv[b]) and a < b and not (s["owner"] == b).any()
+    box = _boxes(uv)
+    assert ((box[:, 1] < 0) | (box[:, 0] > 1) | (box[:, 3] < 0) | (box[:, 2] > 1)).any()         # wholly outside the map
+    for lo, hi, edge in ((0, 1, 0.0), (0, 1, 1.0), (2, 3, 0.0), (2, 3, 1.0)):                       # across each border
+        assert ((box[:, lo] < edge) & (box[:, hi] > edge)).any()
+    size = np.maximum(box[:, 1] - box[:, 0], box[:, 3] - box[:, 2])
+    assert size.min() < 0.5 / 128 and size.max() > 4.0 / 80      # from below a texel to several across, on the square maps
+
+
+def test_soup_twins_cover_texels_on_the_square_maps():
+    a, b = br.SOUP_TWINS
+    s = br.reference("soup", 128, 128)
+    assert s["face_texels"][a] == s["face_texels"][b] > 0 and (s["owner"] == a).any()
+
+
+@pytest.mark.parametrize("H,W", br.SHAPE_SIZES["huge"])
+def test_huge_faces_cover_the_map_and_small_faces_keep_their_texels(H, W):
+    uv = _uv("huge")
+    s = br.reference("huge", H, W)
+    assert len(uv) == 6 and np.abs(uv[4:]).max() == 2.0 ** 20 and s["n_faces_skipped"] == 0 and _sane(s)
+    n = H * W
+    assert s["face_texels"][3] == n and s["face_texels"][4] == n and s["face_texels"][5] == 0
+    assert s["n_covered"] == n and s["n_degenerate"] == 0
+    alone = br.surface(tuple(a[:3] for a in br.mesh_faces(br.shape("huge")["mesh"])), W, H)
+    for f in range(3):
+        assert (alone["owner"] == f).sum() > 8 and np.array_equal(s["owner"] == f, alone["owner"] == f)
+    assert np.array_equal(s["owner"] == 3, alone["owner"] == br.NONE) and not (s["owner"] >= 4).any()
+
+
+@pytest.mark.parametrize("H,W", br.SHAPE_SIZES["slivers"])
+def test_slivers_own_nothing_outside_their_boxes(H, W):
+    uv = _uv("slivers")
+    s = br.reference("slivers", H, W)
+    box = _boxes(uv)
+    px, py = (a.reshape(H, W) for a in br.centres(W, H))
+    own = s["owner"] != br.NONE
+    b = box[s["owner"][own].astype(np.int64)]
+    assert ((b[:, 0] <= px[own]) & (px[own] <= b[:, 1]) & (b[:, 2] <= py[own]) & (py[own] <= b[:, 3])).all()
+    assert 24 <= len(uv) <= 60 and _sane(s) and np.isfinite(s["position"]).all()
+    assert (np.abs(uv)[uv != 0].min() < 1.2e-38) and (uv == F(1e-30)).any()      # subnormal and 1e-30 third vertices
+    # without the box condition some face claims a texel outside its box
+    stray = 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        for f in range(len(uv)):
+            new = br.covers(uv[f], px.ravel(), py.ravel())[0]
+            if new is None:
+                continue
+            old = _old_rule(uv[f], px.ravel(), py.ravel())
+            assert not (new & ~old).any()
+            stray += int((old & ~new).sum())
+    print(f"slivers {H} x {W}: covered {s['n_covered']}, texels the rule without the box would add: {stray}")
+    if (H, W) in br.SLIVER_SIZES:
+        assert stray > 0 and s["n_covered"] > 0
+
+
+def test_sliver_0_covers_8_3_and_2_texels_where_the_signs_alone_give_the_whole_diagonal():
+    uv = _uv("slivers")[0]
+    assert np.array_equal(uv, np.array(br.SLIVER_0, F))
+    want = {(16, 16): 8, (17, 17): 3, (12, 12): 2}
+    for (H, W), n in want.items():
+        px, py = br.centres(W, H)
+        new, A2, _, _ = br.covers(uv, px, py)
+        old = _old_rule(uv, px, py)
+        assert A2 != 0.0 and new.sum() == n and old.sum() > n, (H, W, new.sum(), old.sum())
+        assert (px[new] <= 0.5).all() and (py[new] <= 0.5).all() and (px[old].max() > 0.9)
+    px, py = br.centres(16, 16)
+    old = _old_rule(uv, px, py)
+    assert old.sum() == 16 and np.array_equal(old, px == py)        # all 16 texels of the diagonal; 8 lie on the face's edge
+
+
+@pytest.mark.parametrize("name", ["bunny", "ico_copy"])
+def test_scanned_meshes_under_a_planar_projection_overlap_front_and_back(name):
+    mesh = br.shape(name)["mesh"]
+    assert mesh.n_triangles >= (20_000 if name == "bunny" else 2000) and br.shape(name)["placed"] == (name == "ico_copy")
+    for H, W in br.SHAPE_SIZES[name]:
+        s = br.reference(name, H, W)
+        cov = s["coverage"].ravel() != 0
+        multi = (s["coverers"].ravel()[cov] > 1).mean()
+        print(f"{name} {H} x {W}: covered {cov.mean():.3f}, two or more coverers {multi:.3f}, faces covering nothing {(s['face_texels'] == 0).mean():.3f}")
+        assert 0.3 <= cov.mean() < 1.0 and multi >= 0.9 and s["n_degenerate"] == 0 and s["n_faces_skipped"] == 0 and _sane(s)
+        assert (s["face_texels"] == 0).mean() >= (0.25 if name == "bunny" else 0.0)      # sub-texel faces
+        n = s["normal"].reshape(-1, 3)[cov].astype(np.float64)
+        assert np.allclose((n ** 2).sum(1), 1.0, atol=1e-6)
+
+
+def test_soup_has_gutters_that_one_pass_does_not_fill():
+    cov = br.reference("soup", 80, 96)["coverage"]
+    ones = np.ones((80, 96, 3), F)
+    c1, _, n1 = br.dilate(cov, ones, 1)
+    c2, _, n2 = br.dilate(cov, ones, 2)
+    _, _, n4 = br.dilate(cov, ones, 4)
+    second = (c2 == 2) & (c1 == 0)        # filled by pass 2: none of their neighbours is owned, all they see was filled by pass 1
+    padded = np.pad(cov, 1)
+    owned_near = sum(padded[1 + di:81 + di, 1 + dj:97 + dj] for di, dj in br.NEIGHBOURS)
+    assert 0 < n1 < n2 < n4 and second.sum() == n2 - n1 and not owned_near[second].any()
+
+
+@pytest.mark.parametrize("name,H,W", [("grid", 24, 24), ("grid", 17, 33), ("grid", 7, 5), ("grid", 100, 100), ("soup", 80, 96), ("soup", 1, 2049),
+                                      ("huge", 33, 129)])
+def test_box_condition_changes_nothing_for_well_conditioned_faces(name, H, W):
+    uv = _uv(name)
+    px, py = br.centres(W, H)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for f in range(len(uv)):
+            new = br.covers(uv[f], px, py)[0]
+            assert new is not None and np.array_equal(new, _old_rule(uv[f], px, py)), f

@@ -16,6 +16,7 @@ world-space mesh, because the interface refits only scenes without placed copies
    identical closest_hit calls of 65 rays.
 4. The film of cycle 1's render equals the film of cycle 3's bit for bit."""
 import ctypes as C
+import gc
 
 import numpy as np
 import pytest
@@ -102,10 +103,18 @@ def _destroy(r):
     r._ctx = None
 
 
+def _baseline():
+    """live_bytes before a check begins.  Contexts that earlier tests of the process left in reference cycles (a refused call's
+    traceback holds its frame, and the frame its renderer) are destroyed by whichever collection comes next; collected here,
+    so that none of them is destroyed between two readings of a check and counted as this context's bytes."""
+    gc.collect()
+    return prt.device_memory_info()[0]
+
+
 def _lifecycle():
     """One context through the whole interface; returns the frame of its first render.  Asserts check 1 for this cycle."""
     import torch
-    base = prt.device_memory_info()[0]
+    base = _baseline()
     scene = _scene()
     r, film = _create(scene)
     frame = _frame(r, film)
@@ -184,7 +193,7 @@ def _refusals(r, scene, flat):
 
 @pytest.mark.parametrize("flat", [False, True], ids=["placed_copy", "world_mesh"])
 def test_refused_calls_allocate_nothing_and_steady_state_allocates_nothing(flat):
-    base = prt.device_memory_info()[0]
+    base = _baseline()
     scene = _scene(flat=flat)
     r, film = _create(scene)
     frame = _frame(r, film)
