@@ -1350,6 +1350,66 @@ int prt_bake_irradiance_opt_device(PrtContext* ctx, const PrtBakeTarget* target,
 int prt_bake_light_samples(PrtContext* ctx, const PrtBakeTarget* target, uint32_t seed, uint32_t sample, float* dirs, float* tmax,
                            uint32_t* light, float* contrib, float* ray_pb);
 
+/* ---- SH probes: radiance at points projected on spherical harmonics ------------------------------
+ * For n_probes points: `samples` uniformly distributed directions per point are followed by the radiance query and the
+ * results are projected, on the device and in a fixed order, onto the real spherical harmonics up to order 2: what a grid of
+ * irradiance probes stores to light objects a lightmap cannot.  All arithmetic is fp32, one rounding per written
+ * operation, no contraction.
+ *  Ray (p, s) of probe p with position x_p: key = path_seed(p, first_sample + s, seed): the probe index stands where the
+ *    pixel index stands in a render.  d = RandomUnitVector(key): the shade kernels' own rejection sampler (draws x, y, z in
+ *    that order, accepted when 1e-8f < l2 <= 1, p / sqrt(l2)): uniform on the sphere, pdf 1 / (4 pi); d is used as
+ *    returned, not normalised again.  o = x_p.  The state is the advanced one.
+ *  Path: prt_radiance's path for (o, d, rng_state) with q.max_depth segments, bit for bit.  lighting != 0: prt_radiance_lit's
+ *    path under the context's lighting settings, pb = -1 on segment 0.  The sample value L (rgb) is what the query returns
+ *    for one sample: clamp, roulette, textures and environment apply as there.
+ *  Basis, with (x, y, z) = d and k = 0 .. 8:
+ *      Y0 = 0.282094792f                 Y1 = 0.488602512f*y               Y2 = 0.488602512f*z
+ *      Y3 = 0.488602512f*x               Y4 = 1.092548431f*(x*y)           Y5 = 1.092548431f*(y*z)
+ *      Y6 = 0.315391565f*(3.0f*(z*z) - 1.0f)    Y7 = 1.092548431f*(x*z)    Y8 = 0.546274215f*((x*x) - (y*y))
+ *    `order` in {0, 1, 2} keeps the first (order + 1)^2 of them, so a lower order is a prefix of a higher one.  This is the
+ *    usual real-SH ordering with z as the polar axis.  It has no relation to the environment image's +Y pole: the basis is
+ *    a function of the world-space direction alone, and a caller who wants another frame rotates the direction.
+ *  Coefficient sums: sh_sum[p][k][c] = the fp32 sum, from 0.0f in ascending sample order, of fl(L_c * Y_k(d)), whatever
+ *    the chunking (prt_set_param("probe_chunk", samples per chunk; 0 = by the ray budget of "radiance_chunk")).  A sum, as
+ *    in the film and the bake: the radiance coefficient is (4 pi / samples) * sum.  No floating-point atomics are used.
+ *  Irradiance from coefficients (prt_sh_irradiance; a pure host function, no context): E_c(n) = the fp32 sum, from 0.0f
+ *    over k ascending, of fl(fl(A_k * Y_k(n)) * coeff[k][c]) with A = 3.14159274f for k = 0, 2.09439516f for k = 1 .. 3 and
+ *    0.785398185f for k = 4 .. 8.  Not clamped.
+ *  Refusals (PRT_ERR_INVALID), decided without a device and in this order: no scene; null options, or null positions
+ *    or output with n_probes != 0 (prt_radiance's rule for its arrays); reserved != 0; order > 2; a position that is not finite (the host form only: the device form takes positions as they
+ *    are); n_probes * samples > 2^32 - 1; prt_radiance's own refusals for q.  Then PRT_ERR_NO_DEVICE on a host-only context.
+ *    n_probes == 0 is OK and does nothing.  max_depth == 0 gives zeros.
+ *  Side effects: prt_radiance's: none.  Film, statistics, feature sets, temporal history, light statistics and batch
+ *    instance names are untouched; the next render is bit for bit what it would have been.
+ *  Cost: per chunk of whole samples one ray kernel, the query's rounds over n_probes x chunk rays, and one projection kernel.
+ *    No host wait beyond the query's own; with info one more per call.  From the second identical call on nothing is
+ *    allocated.
+ * Not offered: the group (prt_group_*); orders above 2; interpolation in a grid, which callers do on the coefficients. */
+typedef struct PrtProbeShOptions {
+    uint32_t order;        /* 0, 1 or 2: (order + 1)^2 coefficients per channel */
+    uint32_t lighting;     /* != 0: prt_radiance_lit's paths */
+    uint32_t reserved[2];  /* must be 0 */
+} PrtProbeShOptions;
+typedef struct PrtProbeShInfo {
+    uint64_t n_probes, rays, segments, shadow_rays, shadow_occluded;
+    double device_ms;
+} PrtProbeShInfo;
+/* Host arrays: positions [3*n_probes], sh_sum [n_probes][(order+1)^2][3].  Synchronous.  info may be NULL. */
+int prt_probe_sh(PrtContext* ctx, const PrtProbeShOptions* options, const PrtRadianceQuery* q, uint32_t n_probes, const float* positions,
+                 float* sh_sum, PrtProbeShInfo* info);
+/* The same with positions and sh_sum as DEVICE pointers: enqueued on the context's stream, with the waits the query has;
+ * complete in stream order on return.  The positions are taken as they are: a position that is not finite is not refused. */
+int prt_probe_sh_device(PrtContext* ctx, const PrtProbeShOptions* options, const PrtRadianceQuery* q, uint32_t n_probes,
+                        const void* d_positions, void* d_sh_sum, PrtProbeShInfo* info);
+/* The rays of sample `sample` of every probe (host, [3*n_probes], [3*n_probes], [n_probes]): the function-level view of the
+ * ray kernel, as prt_bake_rays is.  Refusals: no scene, a null array, a position that is not finite. */
+int prt_probe_sh_rays(PrtContext* ctx, uint32_t n_probes, const float* positions, uint32_t seed, uint32_t sample, float* origins,
+                      float* dirs, uint32_t* rng_state);
+/* Host only, no context.  Y [n][(order+1)^2] = the basis at dirs [n][3], directions used as given.  E [n][3] from
+ * coeffs [n][(order+1)^2][3] and normals [n][3] by the rule above.  PRT_ERR_INVALID: order > 2, or a null array with n != 0. */
+int prt_sh_eval(uint32_t n, const float* dirs, uint32_t order, float* Y);
+int prt_sh_irradiance(uint32_t n, const float* coeffs, const float* normals, uint32_t order, float* E);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 int prt_enable_timing(PrtContext* ctx, int on); /* HIP events around every kernel launch */
 int prt_get_stats(PrtContext* ctx, PrtStats* out);

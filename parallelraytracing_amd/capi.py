@@ -129,6 +129,20 @@ class PrtBakeOptions(C.Structure):
     _fields_ = [("lighting", C.c_uint32), ("texel_light", C.c_uint32), ("dilate", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+SH_MAX_ORDER = 2  # PRT_SH_MAX_ORDER
+
+
+class PrtProbeShOptions(C.Structure):
+    """The options of prt_probe_sh (include/prt.h "SH probes"); reserved must be 0."""
+    _fields_ = [("order", C.c_uint32), ("lighting", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class PrtProbeShInfo(C.Structure):
+    """The counts of one prt_probe_sh call (include/prt.h "SH probes")."""
+    _fields_ = [("n_probes", C.c_uint64), ("rays", C.c_uint64), ("segments", C.c_uint64), ("shadow_rays", C.c_uint64),
+                ("shadow_occluded", C.c_uint64), ("device_ms", C.c_double)]
+
+
 class PrtAdaptive(C.Structure):
     """Settings of prt_render_adaptive (include/prt.h "Film statistics and adaptive sampling")."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
@@ -408,6 +422,13 @@ SIGNATURES = {
     "prt_bake_irradiance_opt_device": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.POINTER(PrtBakeOptions),
                                                  _vp, _vp, C.POINTER(PrtBakeInfo)]),
     "prt_bake_light_samples": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.c_uint32, C.c_uint32, _fp, _fp, _u32p, _fp, _fp]),
+    "prt_probe_sh": (C.c_int, [_vp, C.POINTER(PrtProbeShOptions), C.POINTER(PrtRadianceQuery), C.c_uint32, _fp, _fp,
+                               C.POINTER(PrtProbeShInfo)]),
+    "prt_probe_sh_device": (C.c_int, [_vp, C.POINTER(PrtProbeShOptions), C.POINTER(PrtRadianceQuery), C.c_uint32, _vp, _vp,
+                                      C.POINTER(PrtProbeShInfo)]),
+    "prt_probe_sh_rays": (C.c_int, [_vp, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _fp, _fp, _u32p]),
+    "prt_sh_eval": (C.c_int, [C.c_uint32, _fp, C.c_uint32, _fp]),
+    "prt_sh_irradiance": (C.c_int, [C.c_uint32, _fp, _fp, C.c_uint32, _fp]),
     "prt_enable_timing": (C.c_int, [_vp, C.c_int]),
     "prt_get_stats": (C.c_int, [_vp, C.POINTER(PrtStats)]),
     "prt_reset_stats": (C.c_int, [_vp]),

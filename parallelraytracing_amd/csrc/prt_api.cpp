@@ -36,6 +36,8 @@
 #include "prt_radiance_lit.h"
 #include "prt_bake.h"
 #include "prt_bake_light.h"
+#include "prt_probe_sh.h"
+#include "prt_sh_contract.h"
 #include "prt_scene.h"
 #include "prt_temporal.h"
 #include "prt_temporal_contract.h"
@@ -281,6 +283,7 @@ struct PrtContext {
     int feature_chunk = 0;  // prt_set_param("feature_chunk", n): samples per chunk of the sampled pass, 0 = by the ray budget
     int radiance_chunk = 0;  // prt_set_param("radiance_chunk", n): samples per chunk of the radiance query, 0 = by the ray budget
     int bake_chunk = 0;      // prt_set_param("bake_chunk", n): samples per chunk of a bake, 0 = by the ray budget of radiance_chunk
+    int probe_chunk = 0;     // prt_set_param("probe_chunk", n): samples per chunk of prt_probe_sh, 0 = by the ray budget of radiance_chunk
     DevBuf bake;             // the faces and the map of a bake (prt_bake.h); its rays and the query's lists are in scratch
     DevBuf dn;
     // ---- temporal reprojection (include/prt.h): two history sets that ping-pong, the blended planar frame, status and
@@ -3888,6 +3891,143 @@ int prt_bake_light_samples(PrtContext* c, const PrtBakeTarget* target, uint32_t 
     return PRT_OK;
 }
 
+// ---- SH probes (include/prt.h "SH probes") -----------------------------------------------------------------
+// The refusals of both forms, in the order of the header; everything here is decided without a device.
+static int check_probe_sh(PrtContext* c, const PrtProbeShOptions* opt, const PrtRadianceQuery* q, uint32_t n, const void* positions,
+                          const void* sh_sum, bool host_positions) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (!opt) return fail(c, PRT_ERR_INVALID, "prt_probe_sh: null options");
+    if (n != 0u && (!positions || !sh_sum)) return fail(c, PRT_ERR_INVALID, "prt_probe_sh: null array");
+    if (opt->reserved[0] != 0u || opt->reserved[1] != 0u)
+        return fail(c, PRT_ERR_INVALID, "prt_probe_sh: reserved = %u, %u, expected 0", opt->reserved[0], opt->reserved[1]);
+    if (opt->order > PRT_SH_MAX_ORDER) return fail(c, PRT_ERR_INVALID, "prt_probe_sh: order = %u, expected 0 .. %u", opt->order, PRT_SH_MAX_ORDER);
+    if (host_positions) {
+        const float* x = (const float*)positions;
+        for (size_t i = 0; i < 3 * (size_t)n; ++i)
+            if (!std::isfinite(x[i])) return fail(c, PRT_ERR_INVALID, "prt_probe_sh: the position of probe %zu is not finite", i / 3);
+    }
+    if (q && (uint64_t)n * q->samples > 0xFFFFFFFFull)
+        return fail(c, PRT_ERR_INVALID, "prt_probe_sh: %u probes x %u samples exceed 2^32 - 1 paths", n, q->samples);
+    return check_radiance(c, q, n, positions, positions, nullptr, sh_sum);
+}
+
+// Both forms of prt_probe_sh.  The rays of a chunk of whole samples go through the radiance query's own rounds
+// (enqueue_radiance / enqueue_radiance_lit with the states given, one sample per ray), sample-major over the probes, and
+// k_sh_project adds a probe's projected values in ascending sample order: nothing depends on the chunk.
+static int probe_sh(PrtContext* c, const PrtProbeShOptions* opt, const PrtRadianceQuery* q, uint32_t n, const void* positions, void* out,
+                    bool device_form, PrtProbeShInfo* info) {
+    int rc = check_probe_sh(c, opt, q, n, positions, out, !device_form);
+    if (info) *info = PrtProbeShInfo{};
+    if (rc || n == 0u) return rc;
+    if ((rc = need_device(c))) return rc;
+    EventPair tm;  // around the call's device work (PrtProbeShInfo.device_ms)
+    if (info) {
+        HIPCHECK(c, tm.a.create(true));
+        HIPCHECK(c, tm.b.create(true));
+        HIPCHECK(c, hipEventRecord(ev(tm.a), c->stream));
+    }
+    const uint32_t K = prt_sh_count(opt->order);
+    const bool lit = opt->lighting != 0u && c->lighting != (uint32_t)PRT_LIGHTING_OFF;
+    const uint32_t cs = c->probe_chunk > 0 ? std::min((uint32_t)c->probe_chunk, q->samples) : radiance_chunk(c, *q, n);
+    const size_t n1 = n, m = (size_t)cs * n1;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (as prt_radiance: the scratch may be reallocated)
+    float *d_pos = nullptr, *d_sh = nullptr, *d_o, *d_d, *d_rgb;
+    uint32_t *d_rng, *d_seg, *d_counts;
+    RadianceScratch xs;
+    RadianceLitScratch xl;
+    PrtWorkspace ws;
+    if (!device_form) ws.add(&d_pos, 3 * n1).add(&d_sh, 3 * n1 * K);
+    ws.add(&d_counts, (size_t)PRT_PROBE_SH_COUNTERS).add(&d_o, 3 * m).add(&d_d, 3 * m).add(&d_rng, m).add(&d_rgb, 3 * m).add(&d_seg, m);
+    if (lit) xl.declare(ws, m, tex_on(c));
+    else xs.declare(ws, m, tex_on(c));
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if (device_form) {
+        d_pos = (float*)const_cast<void*>(positions);
+        d_sh = (float*)out;
+    } else if ((rc = upload(c, d_pos, (const float*)positions, 3 * n1))) {
+        return rc;
+    }
+    HIPCHECK(c, hipMemsetAsync(d_counts, 0, PRT_PROBE_SH_COUNTERS * sizeof(uint32_t), c->stream));
+    uint64_t shadow[2] = {0u, 0u};
+    const PrtRadianceQuery q1{q->max_depth, 1u, q->seed, q->first_sample};  // (one sample per ray: the states are given)
+    for (uint32_t s0 = 0; s0 < q->samples; s0 += cs) {
+        const uint32_t ccs = std::min(cs, q->samples - s0);
+        const uint32_t mm = ccs * n;
+        prt_launch_sh_rays(c->stream, n, ccs, q->first_sample + s0, q->seed, d_pos, d_o, d_d, d_rng);
+        HIPCHECK(c, hipGetLastError());
+        if (lit) {
+            PrtRadianceLitInfo li{0u, 0u};
+            if ((rc = enqueue_radiance_lit(c, q1, mm, 1u, d_o, d_d, d_rng, nullptr, d_rgb, d_seg, xl, info ? &li : nullptr))) return rc;
+            shadow[0] += li.shadow_rays;
+            shadow[1] += li.shadow_occluded;
+        } else if ((rc = enqueue_radiance(c, q1, mm, 1u, d_o, d_d, d_rng, d_rgb, d_seg, xs))) {
+            return rc;
+        }
+        prt_launch_sh_project(c->stream, n, ccs, K, s0 == 0u, d_d, d_rgb, d_seg, d_sh, d_counts);
+        HIPCHECK(c, hipGetLastError());
+    }
+    if (!device_form && (rc = download(c, (float*)out, d_sh, 3 * n1 * K))) return rc;
+    if (info) {
+        uint32_t counts[PRT_PROBE_SH_COUNTERS] = {};
+        if ((rc = download(c, counts, d_counts, (size_t)PRT_PROBE_SH_COUNTERS))) return rc;
+        HIPCHECK(c, hipEventRecord(ev(tm.b), c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        HIPCHECK(c, hipEventElapsedTime(&ms, ev(tm.a), ev(tm.b)));
+        info->n_probes = n;
+        info->rays = (uint64_t)n * q->samples;
+        info->segments = (uint64_t)counts[PRT_PROBE_SH_CNT_SEGMENTS] | ((uint64_t)counts[PRT_PROBE_SH_CNT_SEGMENTS + 1u] << 32);
+        info->shadow_rays = shadow[0];
+        info->shadow_occluded = shadow[1];
+        info->device_ms = (double)ms;
+    }
+    return device_form ? PRT_OK : prt_synchronize(c);  // (host form: waits for the stream and reports a ray a walk had to give up)
+}
+
+int prt_probe_sh(PrtContext* c, const PrtProbeShOptions* options, const PrtRadianceQuery* q, uint32_t n_probes, const float* positions,
+                 float* sh_sum, PrtProbeShInfo* info) {
+    return probe_sh(c, options, q, n_probes, positions, sh_sum, false, info);
+}
+
+int prt_probe_sh_device(PrtContext* c, const PrtProbeShOptions* options, const PrtRadianceQuery* q, uint32_t n_probes, const void* d_positions,
+                        void* d_sh_sum, PrtProbeShInfo* info) {
+    return probe_sh(c, options, q, n_probes, d_positions, d_sh_sum, true, info);
+}
+
+int prt_probe_sh_rays(PrtContext* c, uint32_t n, const float* positions, uint32_t seed, uint32_t sample, float* origins, float* dirs,
+                      uint32_t* rng_state) {
+    if (!c) return PRT_ERR_INVALID;
+    if (!c->has_scene) return fail(c, PRT_ERR_INVALID, "prt_set_scene has not been called");
+    if (n != 0u && (!positions || !origins || !dirs || !rng_state)) return fail(c, PRT_ERR_INVALID, "prt_probe_sh_rays: null array");
+    for (size_t i = 0; i < 3 * (size_t)n; ++i)
+        if (!std::isfinite(positions[i])) return fail(c, PRT_ERR_INVALID, "prt_probe_sh_rays: the position of probe %zu is not finite", i / 3);
+    if (n == 0u) return PRT_OK;
+    int rc = need_device(c);
+    if (rc) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (the scratch may be reallocated)
+    const size_t n1 = n;
+    float *d_pos, *d_o, *d_d;
+    uint32_t* d_rng;
+    PrtWorkspace ws;
+    ws.add(&d_pos, 3 * n1).add(&d_o, 3 * n1).add(&d_d, 3 * n1).add(&d_rng, n1);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_pos, positions, 3 * n1))) return rc;
+    prt_launch_sh_rays(c->stream, n, 1u, sample, seed, d_pos, d_o, d_d, d_rng);
+    HIPCHECK(c, hipGetLastError());
+    if ((rc = download(c, origins, d_o, 3 * n1)) || (rc = download(c, dirs, d_d, 3 * n1)) || (rc = download(c, rng_state, d_rng, n1))) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return PRT_OK;
+}
+
+int prt_sh_eval(uint32_t n, const float* dirs, uint32_t order, float* Y) {
+    return prt_sh_eval_rule(n, dirs, order, Y) ? PRT_OK : PRT_ERR_INVALID;
+}
+
+int prt_sh_irradiance(uint32_t n, const float* coeffs, const float* normals, uint32_t order, float* E) {
+    return prt_sh_irradiance_rule(n, coeffs, normals, order, E) ? PRT_OK : PRT_ERR_INVALID;
+}
+
 int prt_sample_light(PrtContext* c, uint32_t n, const float* in_dirs, const PrtHit* hits, const uint32_t* keys,
                      float* shadow_dirs, float* tmax, uint32_t* light, float* contrib, float* pdf_light, float* pdf_bsdf,
                      float* w_light, float* w_bsdf) {
@@ -4254,6 +4394,7 @@ int prt_set_param(PrtContext* c, const char* name, int value) {
     else if (n == "feature_chunk" && value >= 0 && value <= (int)PRT_FEATURE_MAX_SAMPLES) c->feature_chunk = value;
     else if (n == "radiance_chunk" && value >= 0 && value <= (int)PRT_RADIANCE_MAX_SAMPLES) c->radiance_chunk = value;
     else if (n == "bake_chunk" && value >= 0 && value <= (int)PRT_RADIANCE_MAX_SAMPLES) c->bake_chunk = value;
+    else if (n == "probe_chunk" && value >= 0 && value <= (int)PRT_RADIANCE_MAX_SAMPLES) c->probe_chunk = value;
     else if (n == "exit_max" && value >= 0 && value < 64) c->tune.exit_max = (uint32_t)value;
     else return fail(c, PRT_ERR_INVALID, "unknown parameter or bad value: %s = %d", name, value);
     return PRT_OK;

@@ -14,6 +14,11 @@
 //              [--frames N --orbit-deg D [--temporal [--temporal-max-history H]]]
 //              [--probe X,Y,Z --probe-size WxH --probe-lighting]
 //              [--bake WxH --bake-dilate N --bake-texel-light]
+//              [--probe-grid NXxNYxNZ --probe-box x0,y0,z0,x1,y1,z1 [--probe-order N] [--probe-lighting]]
+// --probe-grid NXxNYxNZ with --probe-box renders no frame: it writes PREFIX.pfm, the light probes of a cell-centred grid over
+// the box (x fastest; the Python package's probe_grid) as real spherical-harmonic coefficients (prt_probe_sh): one row per
+// probe, (order + 1)^2 texels wide (--probe-order 0 | 1 | 2, default 2), each texel the rgb coefficient 4 pi * sum / spp of
+// --spp uniformly distributed paths of up to --depth segments.  The first GPU; --probe-lighting as for --probe.
 // --bake WxH (with --ply) renders no frame: it writes PREFIX.pfm, the irradiance map of the mesh over the PLY's own UVs
 // (prt_bake_irradiance): --spp paths of up to --depth segments per covered texel, pi * sum / spp, top row first;
 // --bake-dilate N fills the gutters with N passes.  The first GPU; --lighting applies as it would to a frame.
@@ -95,6 +100,9 @@ int main(int argc, char** argv) {
     bool probe = false, probe_lighting = false;
     float probe_pos[3] = {0.0f, 0.0f, 0.0f};
     uint32_t probe_w = 64, probe_h = 32;
+    bool probe_grid = false, probe_box_set = false;
+    uint32_t grid_n[3] = {0, 0, 0}, probe_order = 2;
+    double probe_box[6] = {0, 0, 0, 0, 0, 0};
     bool bake = false;
     uint32_t bake_w = 0, bake_h = 0, bake_dilate = 0;
     bool bake_texel_light = false;
@@ -174,6 +182,15 @@ int main(int argc, char** argv) {
             probe = true;
         }
         else if (a == "--probe-lighting") probe_lighting = true;
+        else if (a == "--probe-grid") {
+            if (sscanf(next(), "%ux%ux%u", &grid_n[0], &grid_n[1], &grid_n[2]) != 3 || !grid_n[0] || !grid_n[1] || !grid_n[2]) { fprintf(stderr, "--probe-grid takes NXxNYxNZ\n"); return 2; }
+            probe_grid = true;
+        }
+        else if (a == "--probe-box") {
+            if (sscanf(next(), "%lf,%lf,%lf,%lf,%lf,%lf", &probe_box[0], &probe_box[1], &probe_box[2], &probe_box[3], &probe_box[4], &probe_box[5]) != 6) { fprintf(stderr, "--probe-box takes x0,y0,z0,x1,y1,z1\n"); return 2; }
+            probe_box_set = true;
+        }
+        else if (a == "--probe-order") probe_order = (uint32_t)atoi(next());
         else if (a == "--bake") {
             if (sscanf(next(), "%ux%u", &bake_w, &bake_h) != 2 || !bake_w || !bake_h) { fprintf(stderr, "--bake takes WxH\n"); return 2; }
             bake = true;
@@ -222,8 +239,16 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--bake-texel-light goes with --bake and --lighting nee or mis\n");
         return 2;
     }
-    if (probe_lighting && !probe) {
-        fprintf(stderr, "--probe-lighting goes with --probe\n");
+    if (probe_lighting && !probe && !probe_grid) {
+        fprintf(stderr, "--probe-lighting goes with --probe or --probe-grid\n");
+        return 2;
+    }
+    if (probe_grid != probe_box_set || (probe_grid && (probe || bake || orbit || adaptive || denoise || temporal || !features_out.empty()))) {
+        fprintf(stderr, "--probe-grid goes with --probe-box and renders no frame: it does not go with --probe, --bake, --orbit-deg, --adaptive, --denoise, --temporal or --features-out\n");
+        return 2;
+    }
+    if (probe_order > 2u || (uint64_t)grid_n[0] * grid_n[1] * grid_n[2] > 0xFFFFFFFFull) {
+        fprintf(stderr, "--probe-order takes 0, 1 or 2, and --probe-grid at most 2^32 - 1 probes\n");
         return 2;
     }
     if (temporal && devices.size() != 1) {
@@ -275,6 +300,23 @@ int main(int argc, char** argv) {
             if (prt_write_pfm((out + ".pfm").c_str(), rgb.data(), probe_w, probe_h)) { fprintf(stderr, "cannot write %s.pfm\n", out.c_str()); return 1; }
             printf("probe at (%g, %g, %g): %ux%u texels, %u spp, max_depth %u -> %s.pfm\n", probe_pos[0], probe_pos[1], probe_pos[2], probe_w, probe_h, spp,
                    depth, out.c_str());
+            return 0;
+        }
+        if (probe_grid) {  // cell centres in double, rounded once, x fastest: the Python package's probe_grid
+            const uint32_t n_probes = grid_n[0] * grid_n[1] * grid_n[2], K = (probe_order + 1u) * (probe_order + 1u);
+            std::vector<float> pos(3 * (size_t)n_probes), coeffs;
+            for (uint32_t k = 0, p = 0; k < grid_n[2]; ++k)
+                for (uint32_t j = 0; j < grid_n[1]; ++j)
+                    for (uint32_t i = 0; i < grid_n[0]; ++i, ++p) {
+                        const uint32_t cell[3] = {i, j, k};
+                        for (int a = 0; a < 3; ++a)
+                            pos[3 * (size_t)p + a] = (float)(probe_box[a] + ((double)cell[a] + 0.5) * ((probe_box[3 + a] - probe_box[a]) / (double)grid_n[a]));
+                    }
+            PrtProbeShInfo pi{};
+            r.ProbeSH(n_probes, pos.data(), probe_order, spp, coeffs, probe_lighting, &pi);
+            if (prt_write_pfm((out + ".pfm").c_str(), coeffs.data(), K, n_probes)) { fprintf(stderr, "cannot write %s.pfm\n", out.c_str()); return 1; }
+            printf("probes: %ux%ux%u grid, order %u, %u spp, max_depth %u, %llu segments, %.3f ms on the device -> %s.pfm (%u x %u)\n", grid_n[0], grid_n[1],
+                   grid_n[2], probe_order, spp, depth, (unsigned long long)pi.segments, pi.device_ms, out.c_str(), K, n_probes);
             return 0;
         }
         if (bake) {

@@ -517,6 +517,18 @@ public:
             throw Error(std::string("prt_bake_irradiance: ") + prt_last_error(c));
         for (float& v : irradiance) v = v * 3.14159274f / (float)samples;
     }
+    // Light probes on the first GPU's context (prt_probe_sh, include/prt.h "SH probes"): the radiance arriving at n_probes
+    // points (positions: 3 floats each) as real spherical-harmonic coefficients, n_probes x (order + 1)^2 x 3 floats,
+    // 4 pi * sum / samples.  lighting: Radiance's.  info (may be null): the counts of the call.
+    void ProbeSH(uint32_t n_probes, const float* positions, uint32_t order, uint32_t samples, std::vector<float>& coeffs, bool lighting = false,
+                 PrtProbeShInfo* info = nullptr, uint32_t first_sample = 0) {
+        PrtContext* c = prt_group_context(grp_, 0);
+        const PrtProbeShOptions opt{order, lighting ? 1u : 0u, {0u, 0u}};
+        const PrtRadianceQuery q{max_depth_, samples, seed_, first_sample};
+        coeffs.assign((size_t)n_probes * (order <= 2u ? (order + 1u) * (order + 1u) : 1u) * 3u, 0.0f);
+        if (prt_probe_sh(c, &opt, &q, n_probes, positions, coeffs.data(), info)) throw Error(std::string("prt_probe_sh: ") + prt_last_error(c));
+        for (float& v : coeffs) v = v * (4.0f * 3.14159274f) / (float)samples;
+    }
 
 private:
     void check(int rc) {

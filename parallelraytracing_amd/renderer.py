@@ -1253,6 +1253,73 @@ class HipWavefrontRenderer:
         return self.radiance(o, d, samples=samples, seed=seed, first_sample=first_sample, max_depth=max_depth,
                              lighting=lighting).reshape(H, W, 3)
 
+    # ---- SH probes (include/prt.h "SH probes") --------------------------------------------------------------------
+    def probe_sh_rays(self, positions, sample: int = 0, seed=None) -> dict:
+        """The ray of sample `sample` of every probe (prt_probe_sh_rays): {"o", "d" [P, 3], "rng_state" [P] uint32}.
+        radiance(o, d, rng_state=...) follows the paths probe_sh follows."""
+        x = np.ascontiguousarray(_f32(positions).reshape(-1, 3))
+        P = x.shape[0]
+        o, d = np.zeros((P, 3), np.float32), np.zeros((P, 3), np.float32)
+        rng = np.zeros(P, np.uint32)
+        self._check(capi.lib().prt_probe_sh_rays(self._ctx, P, x.ctypes.data_as(_fp), int(self.seed if seed is None else seed) & 0xFFFFFFFF,
+                                                 int(sample) & 0xFFFFFFFF, o.ctypes.data_as(_fp), d.ctypes.data_as(_fp), rng.ctypes.data_as(_u32p)))
+        return {"o": o, "d": d, "rng_state": rng}
+
+    def probe_sh(self, positions, order: int = 2, samples: int = 64, seed=None, first_sample: int = 0, max_depth=None,
+                 lighting: bool = False, out: str = "numpy", return_info: bool = False):
+        """Light probes (prt_probe_sh): the radiance arriving at P points as real spherical-harmonic coefficients
+        [P, (order + 1)^2, 3]: `samples` uniformly distributed directions per point, followed by the radiance query
+        (lighting: radiance()'s) and projected on the device in a fixed order.  The value is
+        sum * float32(4 pi) / float32(samples); sh_irradiance(coeffs, n) turns it into the irradiance on a surface of normal
+        n.  positions [P, 3]: a numpy array (the host form) or a torch tensor on the renderer's device (the device form,
+        ordered after torch's current stream; positions are taken as they are).  out = "torch": a tensor on the renderer's
+        device through the device form.  return_info: also {"sum": the raw fp32 sums, "info": the counts of the call}."""
+        if out not in ("numpy", "torch"):
+            raise ValueError(f"out: {out!r}, expected 'numpy' or 'torch'")
+        if int(order) < 0 or int(order) > 0xFFFFFFFF:
+            raise ValueError(f"order: {order}")
+        opt = capi.PrtProbeShOptions(int(order), int(bool(lighting)), (C.c_uint32 * 2)(0, 0))
+        q = capi.PrtRadianceQuery(int(self.max_depth if max_depth is None else max_depth), int(samples),
+                                  int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample) & 0xFFFFFFFF)
+        K = (int(order) + 1) ** 2 if int(order) <= capi.SH_MAX_ORDER else 1      # (the library refuses the order; the array is a placeholder)
+        info = capi.PrtProbeShInfo()
+        try:
+            import torch
+            is_t = isinstance(positions, torch.Tensor)
+        except ImportError:
+            is_t = False
+        if is_t or out == "torch":
+            import torch
+            dev = self._torch_device()
+            if is_t:
+                P = int(positions.shape[0]) if positions.dim() == 2 else -1
+                self._check_tensor("positions", positions, (P, 3))
+                x = positions
+            else:
+                x = torch.from_numpy(np.ascontiguousarray(_f32(positions).reshape(-1, 3))).to(dev)
+                P = int(x.shape[0])
+            total = torch.zeros((P, K, 3), dtype=torch.float32, device=dev)
+            self._on_context_stream(lambda: capi.lib().prt_probe_sh_device(
+                self._ctx, C.byref(opt), C.byref(q), P, C.c_void_p(x.data_ptr()), C.c_void_p(total.data_ptr()),
+                C.byref(info) if return_info else None))
+            if out == "torch":
+                # (tensor operands: torch turns a division by a Python number into a multiplication by its reciprocal)
+                coeffs = total * torch.full((1, 1, 1), float(np.float32(4.0 * np.pi)), dtype=torch.float32, device=dev) \
+                    / torch.full((1, 1, 1), float(q.samples), dtype=torch.float32, device=dev)
+            else:
+                total = total.cpu().numpy()
+                coeffs = total * np.float32(4.0 * np.pi) / np.float32(q.samples)
+        else:
+            x = np.ascontiguousarray(_f32(positions).reshape(-1, 3))
+            P = x.shape[0]
+            total = np.zeros((P, K, 3), np.float32)
+            self._check(capi.lib().prt_probe_sh(self._ctx, C.byref(opt), C.byref(q), P, x.ctypes.data_as(_fp), total.ctypes.data_as(_fp),
+                                                C.byref(info) if return_info else None))
+            coeffs = total * np.float32(4.0 * np.pi) / np.float32(q.samples)
+        if return_info:
+            return coeffs, {"sum": total, "info": {name: getattr(info, name) for name, _ in capi.PrtProbeShInfo._fields_}}
+        return coeffs
+
     # ---- surface baking (include/prt.h "Surface baking") ---------------------------------------------------------
     def _bake_target(self, mesh, instance, size, uvs):
         """The PrtBakeTarget of world-space mesh `mesh` or placed copy `instance` on a size = (H, W) map, and what keeps
@@ -1878,6 +1945,54 @@ def probe_directions(H: int, W: int) -> np.ndarray:
     x, y, z = st * cp, np.broadcast_to(ct, (H, W)), st * sp
     inv = 1.0 / np.sqrt((x * x + y * y) + z * z)
     return np.stack([x * inv, y * inv, z * inv], axis=-1).astype(np.float32)
+
+
+def sh_basis(d, order: int = 2) -> np.ndarray:
+    """The real spherical harmonics of include/prt.h "SH probes" at directions d [..., 3] (used as given, not normalised):
+    [..., (order + 1)^2] float32, through the library's own lines (prt_sh_eval; no context, no device)."""
+    a = _f32(d)
+    if a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError(f"sh_basis: d must be [..., 3], got {a.shape}")
+    if not 0 <= int(order) <= capi.SH_MAX_ORDER:
+        raise ValueError(f"sh_basis: order {order}, expected 0 .. {capi.SH_MAX_ORDER}")
+    K = (int(order) + 1) ** 2
+    flat = np.ascontiguousarray(a.reshape(-1, 3))
+    Y = np.zeros((flat.shape[0], K), np.float32)
+    if capi.lib().prt_sh_eval(flat.shape[0], flat.ctypes.data_as(_fp), int(order), Y.ctypes.data_as(_fp)):
+        raise PrtError("prt_sh_eval failed")
+    return Y.reshape(a.shape[:-1] + (K,))
+
+
+def sh_irradiance(coeffs, normals) -> np.ndarray:
+    """The irradiance E [..., 3] float32 that radiance coefficients [..., K, 3] (K = 1, 4 or 9: what probe_sh returns) give
+    on a surface of normal `normals` [..., 3] (prt_sh_irradiance; a pure host function).  The leading shapes broadcast: one
+    set of coefficients under many normals, or one normal for many probes.  Not clamped."""
+    c, n = _f32(coeffs), _f32(normals)
+    if c.ndim < 2 or c.shape[-1] != 3 or c.shape[-2] not in (1, 4, 9):
+        raise ValueError(f"sh_irradiance: coeffs must be [..., 1 | 4 | 9, 3], got {c.shape}")
+    if n.ndim < 1 or n.shape[-1] != 3:
+        raise ValueError(f"sh_irradiance: normals must be [..., 3], got {n.shape}")
+    K = c.shape[-2]
+    lead = np.broadcast_shapes(c.shape[:-2], n.shape[:-1])
+    cf = np.ascontiguousarray(np.broadcast_to(c, lead + (K, 3)).reshape(-1, K, 3))
+    nf = np.ascontiguousarray(np.broadcast_to(n, lead + (3,)).reshape(-1, 3))
+    E = np.zeros((cf.shape[0], 3), np.float32)
+    if capi.lib().prt_sh_irradiance(cf.shape[0], cf.ctypes.data_as(_fp), nf.ctypes.data_as(_fp), {1: 0, 4: 1, 9: 2}[K], E.ctypes.data_as(_fp)):
+        raise PrtError("prt_sh_irradiance failed")
+    return E.reshape(lead + (3,))
+
+
+def probe_grid(lo, hi, counts) -> np.ndarray:
+    """Cell-centred probe positions [nx * ny * nz, 3] float32 of an nx x ny x nz grid over the box lo .. hi, x fastest:
+    probe (i, j, k) has index (k * ny + j) * nx + i and lies at lo + (index + 1/2) * (hi - lo) / count per axis (float64,
+    rounded once)."""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    nx, ny, nz = (int(v) for v in counts)
+    if min(nx, ny, nz) < 1:
+        raise ValueError(f"probe_grid: counts {counts}, expected at least 1 each way")
+    ax = [lo[a] + (np.arange(n) + 0.5) * ((hi[a] - lo[a]) / n) for a, n in enumerate((nx, ny, nz))]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return np.stack([x.ravel(), y.ravel(), z.ravel()], axis=1).astype(np.float32)
 
 
 def read_pfm(path: str) -> np.ndarray:
