@@ -1350,6 +1350,101 @@ int prt_bake_irradiance_opt_device(PrtContext* ctx, const PrtBakeTarget* target,
 int prt_bake_light_samples(PrtContext* ctx, const PrtBakeTarget* target, uint32_t seed, uint32_t sample, float* dirs, float* tmax,
                            uint32_t* light, float* contrib, float* ray_pb);
 
+/* ---- Bake statistics and adaptive sampling ---------------------------------------------------------
+ * What "Film statistics and adaptive sampling" gives the film, for the lightmap: per-texel moments of the samples'
+ * luminance, and a bake that goes on sampling only where the map is unconverged.  Every fp32 operation below is a single
+ * one, rounded once, never contracted.
+ *  Moments: for every sample value (r, g, b) the bake adds to texel t (under texel_light the value fl(q + e)), in ascending
+ *    sample order:
+ *        y = fl(fl(fl(0.2126f r) + fl(0.7152f g)) + fl(0.0722f b));   A = fl(A + y);   Q = fl(Q + fl(y y))
+ *    from A = Q = 0.0f: the film's luminance and the film's moments.  count[t] (fp32, an exact integer) is the number of
+ *    samples added.  rgb_sum[t] is prt_bake_irradiance's sum: from 0.0f in ascending sample order, whatever the chunking.
+ *  Rule: prt_adaptive_unconverged(count, A, Q, threshold, noise_floor), the film's rule (csrc/prt_adaptive.h, written once
+ *    and compiled for the device and for the host).  A texel is COVERED iff its coverage byte is 1; a texel that is not
+ *    (coverage 0, or 2 in a map that went through the gutter fill) is converged.  The comparisons of the rule are false on
+ *    a NaN, so a texel whose moments are NaN (count >= 2) is converged.
+ *  Blocks: the map is cut into aligned 8 x 8 blocks of texels, block (by, bx) = rows 8 by .. 8 by + 7 and columns 8 bx ..
+ *    8 bx + 7 clipped to the map, numbered row-major: block index by * ceil(W / 8) + bx.  A block is ACTIVE while any covered
+ *    texel in it is unconverged: one wave per block, a ballot, no floating-point reduction, so the decision cannot depend on
+ *    an order.  A block without covered texels is never active.
+ *  Loop (prt_bake_irradiance_adaptive; prt_render_adaptive's).  Pass 0 gives every covered texel min_spp samples, indices
+ *    q.first_sample .. q.first_sample + min_spp - 1, exactly as prt_bake_irradiance_opt would.  min_spp = 0 is refused: unlike
+ *    the film, the call keeps no state between calls.  If max_spp == min_spp the call ends there: the uniform bake with
+ *    statistics, without a selection and without a host wait beyond the bake's (that is how a caller gets the variance for
+ *    the denoiser without adapting; blocks_converged and blocks_capped are then 0).  Otherwise, with added = min_spp:
+ *      1. select: of the blocks active so far (at first: all blocks) those that are active by the rule now;
+ *      2. list the covered texels of those blocks in ascending texel order and read both lengths back (one small wait);
+ *      3. stop if the list is empty, or if added >= max_spp;
+ *      4. add k = min(step_spp, max_spp - added) samples, indices q.first_sample + added .. + k - 1, to the listed texels
+ *         only, by the bake's own per-chunk sequence over that list (the ray kernel, the radiance query unlit or lit, under
+ *         texel_light the light sample, the occlusion pass and the add); added += k.
+ *    A block that drops out never returns.  A texel that ends with count n therefore holds samples q.first_sample ..
+ *    q.first_sample + n - 1, and since the bake is keyed by (texel, sample, seed) and sums in sample order, its rgb_sum
+ *    equals that texel of prt_bake_irradiance_opt with samples = n, bit for bit: lit or unlit, with or without texel_light,
+ *    whatever bake_chunk / radiance_chunk, tree builder or tunable.  q.samples is ignored: cfg decides, and every bound on
+ *    the sample count is checked with max_spp in its place.  The chunk of a pass is bake_chunk, or else what radiance_chunk
+ *    gives for the pass's sample count and list length.
+ *  Outputs: rgb_sum [3*H*W], count, sum_y (A), sum_y2 (Q) [H*W], rgb_mean [3*H*W], coverage [H*W] bytes; each but rgb_sum
+ *    may be NULL.  rgb_mean[t] = rgb_sum[t] / count[t] per component, one fp32 division; 0 where count is 0.  The
+ *    options.dilate passes of the gutter fill run on the pair (coverage, rgb_mean) only, and `coverage` is the pair's
+ *    (0 / 1 / 2).  The mean and not the sum is filled because neighbouring texels have different counts: a mean of sums
+ *    over texels of 16 and of 256 samples is no quantity at all, while their means estimate the same kind of thing.  Sums,
+ *    counts and moments are never dilated: a filled texel has count 0.  Irradiance on the +n side is pi * rgb_mean.
+ *  Info: PrtBakeInfo as prt_bake_irradiance fills it, with rays = the sum of all counts.  PrtBakeAdaptiveInfo: below.
+ *  Refusals (PRT_ERR_INVALID, decided before the device is touched, in this order): null options; options.reserved != 0;
+ *    prt_bake_surface's for the target (no scene, null target, kind, index, size, UVs); null q; null cfg; a cfg.reserved
+ *    word != 0; min_spp == 0; threshold or noise_floor negative or NaN; both 0; max_spp < min_spp; step_spp == 0 with max_spp
+ *    > min_spp; max_spp > PRT_RADIANCE_MAX_SAMPLES; width * height * max_spp > 2^32 - 1; null rgb_sum.  After those a
+ *    host-only context returns PRT_ERR_NO_DEVICE.  Side effects: the bake's: none.
+ *  Cost: the bake's, plus per later pass one wave per previously active block, one block compacting the block list in its
+ *    order, one block compacting the `active` bytes of the map, and the wait for two words; one division per texel at the
+ *    end.  With info != NULL under texel_light each pass also waits once for its shadow-ray counters.
+ *  Memory: the maps of a call lie behind the bake's own arrays in the context's bake buffer, the rays and the query's lists
+ *    of a pass in scratch; from the second identical call on nothing is allocated (prt_device_memory_info).
+ * Not offered: the group (prt_group_*); per-texel (rather than per-block) stopping; carrying moments across calls. */
+typedef struct PrtBakeAdaptive {
+    uint32_t min_spp, step_spp, max_spp;
+    float threshold, noise_floor;
+    uint32_t reserved[3];  /* must be 0 */
+} PrtBakeAdaptive;
+typedef struct PrtBakeAdaptiveInfo {
+    uint32_t passes;           /* passes over a texel list that sampled (pass 0 is not one) */
+    uint32_t blocks;           /* ceil(W / 8) * ceil(H / 8) */
+    uint32_t blocks_converged; /* blocks the rule stopped (at any count, max_spp included; blocks without covered texels too) */
+    uint32_t blocks_capped;    /* blocks still active when max_spp was reached */
+    uint32_t min_texel_spp;    /* fewest / most samples a covered texel ends with (0 / 0 for a map without one) */
+    uint32_t max_texel_spp;
+    uint64_t texel_samples;    /* the sum of all counts */
+} PrtBakeAdaptiveInfo;
+/* Host outputs.  Synchronous. */
+int prt_bake_irradiance_adaptive(PrtContext* ctx, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* options,
+                                 const PrtBakeAdaptive* cfg, float* rgb_sum, float* count, float* sum_y, float* sum_y2, float* rgb_mean,
+                                 uint8_t* coverage, PrtBakeInfo* info /* may be NULL */, PrtBakeAdaptiveInfo* adaptive_info /* may be NULL */);
+/* The same with the six outputs as DEVICE pointers, as prt_bake_irradiance_opt_device has its two: enqueued on the
+ * context's stream with the waits above; complete in stream order on return. */
+int prt_bake_irradiance_adaptive_device(PrtContext* ctx, const PrtBakeTarget* target, const PrtRadianceQuery* q,
+                                        const PrtBakeOptions* options, const PrtBakeAdaptive* cfg, void* d_rgb_sum, void* d_count,
+                                        void* d_sum_y, void* d_sum_y2, void* d_rgb_mean, void* d_coverage, PrtBakeInfo* info,
+                                        PrtBakeAdaptiveInfo* adaptive_info);
+/* Function level, in the manner of prt_tile_select: steps 1 and 2 of the loop on caller-supplied host arrays, through the
+ * kernels the loop launches.  coverage [H*W] bytes, count, sum_y, sum_y2 [H*W] floats.  prev: n_prev distinct block indices,
+ * or NULL for blocks 0 .. n_prev - 1.  block_list (room for n_prev entries) receives the entries of prev that are active,
+ * in prev's order, and 0xFFFFFFFF in the entries past them; texel_list (room for H*W entries) the covered texels of those
+ * blocks in ascending order, and 0xFFFFFFFF past them; counts[0], counts[1] = the two lengths.  Needs a device and a
+ * context, no scene; of the context only scratch memory is read or written.  Synchronous on return.
+ * PRT_ERR_INVALID (checked on the host, in this order): a bad size; a null array (prev aside); n_prev above the block
+ * count; a prev[i] >= the block count; threshold or noise_floor negative or NaN; both 0. */
+int prt_bake_block_select(PrtContext* ctx, uint32_t W, uint32_t H, const uint8_t* coverage, const float* count, const float* sum_y,
+                          const float* sum_y2, const uint32_t* prev /* may be NULL */, uint32_t n_prev, float threshold, float noise_floor,
+                          uint32_t* block_list, uint32_t* texel_list, uint32_t* counts /* [2] */);
+/* Pure host function, no context: per texel t < n, evaluated in double and rounded once,
+ *     count[t] == 0: 0 (a texel without samples is an uncovered one: every covered texel of an adaptive bake has min_spp >= 1);
+ *     else count[t] < 2 (or NaN): +inf;
+ *     else sqrt(V / (count - 1)) / (m + noise_floor) with m = A / count, V = max(0, Q / count - m m): prt_film_noise_read's
+ *     formula, IEEE 0 / 0 = NaN where a black texel meets noise_floor = 0.
+ * PRT_ERR_INVALID: noise_floor negative or NaN; a null array with n != 0. */
+int prt_bake_noise(uint64_t n, const float* count, const float* sum_y, const float* sum_y2, float noise_floor, float* rel_err);
+
 /* ---- SH probes: radiance at points projected on spherical harmonics ------------------------------
  * For n_probes points: `samples` uniformly distributed directions per point are followed by the radiance query and the
  * results are projected, on the device and in a fixed order, onto the real spherical harmonics up to order 2: what a grid of

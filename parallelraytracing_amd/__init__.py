@@ -8,12 +8,12 @@ from . import capi
 
 capi.lib()  # fail loudly if the HIP extension is missing
 
-from .renderer import (Camera, Film, HipWavefrontGroupRenderer, HipWavefrontRenderer, Mesh, PrtError, Scene,  # noqa: E402
+from .renderer import (Camera, Film, bake_noise, HipWavefrontGroupRenderer, HipWavefrontRenderer, Mesh, PrtError, Scene,  # noqa: E402
                        device_memory_info, glm_normalize, hits_to_numpy, instance_names, make_transform, probe_directions, probe_grid, read_pfm, sh_basis, sh_irradiance, write_pfm,
                        write_ppm)
 from . import dist, scenes  # noqa: E402
 
-__all__ = ["Camera", "Film", "HipWavefrontGroupRenderer", "HipWavefrontRenderer", "Mesh", "PrtError", "Scene", "capi", "device_memory_info", "dist",
+__all__ = ["Camera", "Film", "HipWavefrontGroupRenderer", "HipWavefrontRenderer", "Mesh", "PrtError", "Scene", "bake_noise", "capi", "device_memory_info", "dist",
            "glm_normalize",
            "hits_to_numpy", "instance_names", "make_transform", "probe_directions", "probe_grid", "read_pfm", "scenes", "sh_basis", "sh_irradiance",
            "write_pfm", "write_ppm"]

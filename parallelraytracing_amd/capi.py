@@ -129,6 +129,18 @@ class PrtBakeOptions(C.Structure):
     _fields_ = [("lighting", C.c_uint32), ("texel_light", C.c_uint32), ("dilate", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PrtBakeAdaptive(C.Structure):
+    """Settings of prt_bake_irradiance_adaptive (include/prt.h "Bake statistics and adaptive sampling"); reserved must be 0."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
+                ("noise_floor", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class PrtBakeAdaptiveInfo(C.Structure):
+    """What one prt_bake_irradiance_adaptive call did (include/prt.h "Bake statistics and adaptive sampling")."""
+    _fields_ = [("passes", C.c_uint32), ("blocks", C.c_uint32), ("blocks_converged", C.c_uint32), ("blocks_capped", C.c_uint32),
+                ("min_texel_spp", C.c_uint32), ("max_texel_spp", C.c_uint32), ("texel_samples", C.c_uint64)]
+
+
 SH_MAX_ORDER = 2  # PRT_SH_MAX_ORDER
 
 
@@ -422,6 +434,15 @@ SIGNATURES = {
     "prt_bake_irradiance_opt_device": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.POINTER(PrtBakeOptions),
                                                  _vp, _vp, C.POINTER(PrtBakeInfo)]),
     "prt_bake_light_samples": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.c_uint32, C.c_uint32, _fp, _fp, _u32p, _fp, _fp]),
+    "prt_bake_irradiance_adaptive": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.POINTER(PrtBakeOptions),
+                                               C.POINTER(PrtBakeAdaptive), _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_uint8),
+                                               C.POINTER(PrtBakeInfo), C.POINTER(PrtBakeAdaptiveInfo)]),
+    "prt_bake_irradiance_adaptive_device": (C.c_int, [_vp, C.POINTER(PrtBakeTarget), C.POINTER(PrtRadianceQuery), C.POINTER(PrtBakeOptions),
+                                                      C.POINTER(PrtBakeAdaptive), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PrtBakeInfo),
+                                                      C.POINTER(PrtBakeAdaptiveInfo)]),
+    "prt_bake_block_select": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), _fp, _fp, _fp, _u32p, C.c_uint32, C.c_float,
+                                        C.c_float, _u32p, _u32p, _u32p]),
+    "prt_bake_noise": (C.c_int, [C.c_uint64, _fp, _fp, _fp, C.c_float, _fp]),
     "prt_probe_sh": (C.c_int, [_vp, C.POINTER(PrtProbeShOptions), C.POINTER(PrtRadianceQuery), C.c_uint32, _fp, _fp,
                                C.POINTER(PrtProbeShInfo)]),
     "prt_probe_sh_device": (C.c_int, [_vp, C.POINTER(PrtProbeShOptions), C.POINTER(PrtRadianceQuery), C.c_uint32, _vp, _vp,

@@ -36,6 +36,8 @@
 #include "prt_radiance_lit.h"
 #include "prt_bake.h"
 #include "prt_bake_light.h"
+#include "prt_bake_adaptive.h"
+#include "prt_bake_adaptive_contract.h"
 #include "prt_probe_sh.h"
 #include "prt_sh_contract.h"
 #include "prt_scene.h"
@@ -3523,6 +3525,15 @@ struct BakeBufs {
     uint8_t* cov2 = nullptr;
 };
 
+// What an adaptive bake keeps beside them for the length of a call, in c->bake too (c->scratch is laid out anew by every
+// pass): the count and the moments, the second buffer of the mean's gutter fill, the `active` bytes, the texel list of a
+// pass, the flags and the two block lists that ping-pong, and the selection's counters.
+struct BakeAdaptiveBufs {
+    float *count = nullptr, *sum_y = nullptr, *sum_y2 = nullptr, *mean2 = nullptr;
+    uint8_t* active = nullptr;
+    uint32_t *tlist = nullptr, *flags = nullptr, *blist[2] = {nullptr, nullptr}, *sel = nullptr;
+};
+
 // The refusals, in the order of the header; everything here is decided without a device.  q: null for the entry points
 // that trace nothing.
 static int check_bake(PrtContext* c, const PrtBakeTarget* t, const PrtRadianceQuery* q, bool with_query, BakeTarget* b) {
@@ -3623,7 +3634,7 @@ static int bake_geometry(PrtContext* c, BakeTarget* b) {
 
 // Coverage, surface and the texel list of a checked target on the context's stream; counts (host) as of the list.  The
 // arrays are in c->bake; with_rgb: the two value buffers and the second coverage buffer of the gutter fill too.
-static int enqueue_bake_surface(PrtContext* c, BakeTarget* b, bool with_rgb, BakeBufs* x, uint32_t* counts) {
+static int enqueue_bake_surface(PrtContext* c, BakeTarget* b, bool with_rgb, BakeBufs* x, uint32_t* counts, BakeAdaptiveBufs* ax = nullptr) {
     int rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));  // (c->bake may be reallocated: nothing enqueued before may still be using it)
     if ((rc = bake_geometry(c, b))) return rc;
@@ -3634,6 +3645,11 @@ static int enqueue_bake_surface(PrtContext* c, BakeTarget* b, bool with_rgb, Bak
     ws.add(&x->map.owner, n).add(&x->map.cov, n).add(&x->map.bary, 2 * n).add(&x->map.position, 3 * n).add(&x->map.normal, 3 * n);
     ws.add(&x->list, n).add(&x->counts, (size_t)PRT_BAKE_COUNTERS);
     if (with_rgb) ws.add(&x->rgb[0], 3 * n).add(&x->rgb[1], 3 * n).add(&x->cov2, n);
+    if (ax) {  // (behind the bake's own arrays, which lie where they lie without these)
+        const size_t nb = prt_bake_block_count(b->W, b->H);
+        ws.add(&ax->count, n).add(&ax->sum_y, n).add(&ax->sum_y2, n).add(&ax->mean2, 3 * n).add(&ax->active, n).add(&ax->tlist, n);
+        ws.add(&ax->flags, nb).add(&ax->blist[0], nb).add(&ax->blist[1], nb).add(&ax->sel, (size_t)PRT_BKA_COUNTERS);
+    }
     if ((rc = commit(c, ws, c->bake))) return rc;
     if ((rc = upload(c, d_uv, b->uv6.data(), 6 * F)) || (rc = upload(c, d_pos, b->pos9.data(), 9 * F)) || (rc = upload(c, d_nrm, b->nrm9.data(), 9 * F)))
         return rc;
@@ -3711,13 +3727,90 @@ int prt_bake_rays(PrtContext* c, const PrtBakeTarget* target, uint32_t seed, uin
     return PRT_OK;
 }
 
-// Both forms of prt_bake_irradiance.  The rays of a chunk of whole samples go through the radiance query's own rounds
-// (enqueue_radiance / enqueue_radiance_lit with the states given, one sample per ray), sample-major over the covered texels,
-// and k_bk_sum adds a texel's values in ascending sample order: nothing depends on the chunk.
-// With the texel's light sample (opt.texel_light under a lit bake with max_depth >= 1): per chunk k_bkl_sample takes the
+// Where the ordered sum of a chunk goes: moments.count == null: k_bk_sum into rgb_sum alone; else k_bka_sum into all four maps.
+struct BakeSums {
+    PrtBakeMoments moments{};
+    uint32_t* counts = nullptr;
+};
+
+// q.samples samples, indices q.first_sample .., of the n_list texels of d_list (ascending texel indices of the map) into
+// `out`.  The rays of a chunk of whole samples go through the radiance query's own rounds (enqueue_radiance /
+// enqueue_radiance_lit with the states given, one sample per ray), sample-major over the list, and the sum kernel adds a
+// texel's values in ascending sample order: nothing depends on the chunk.
+// With the texel's light sample (texel): per chunk k_bkl_sample takes the
 // samples and the pdfs of the texels' rays, the lit query starts its paths from those pdfs, one pass of the occlusion
 // pipeline resolves the texels' shadow rays (dense: a ray that is not cast has tmax = 0 and never occludes, so there is no
 // count to wait for) and k_bkl_add adds what arrives to the query's values before the ordered sum.
+// first: the maps of `out` hold nothing yet (the first chunk starts from 0.0f).  shadow += the shadow rays cast / occluded,
+// where want_info.  The rays and the query's lists are in c->scratch.
+static int enqueue_bake_samples(PrtContext* c, const PrtRadianceQuery& q, bool lit, bool texel, const uint32_t* d_list, uint32_t n_list,
+                                const PrtBakeMap& map, bool first, const BakeSums& out, bool want_info, uint64_t shadow[2]) {
+    int rc;
+    const uint32_t cs = c->bake_chunk > 0 ? std::min((uint32_t)c->bake_chunk, q.samples) : radiance_chunk(c, q, n_list);
+    const size_t m = (size_t)cs * n_list;
+    float *d_o, *d_d, *d_rgb;
+    uint32_t *d_rng, *d_seg;
+    RadianceScratch xs;
+    RadianceLitScratch xl;
+    PrtBakeLightRays tl{};
+    uint8_t* d_tocc = nullptr;
+    unsigned long long* d_tstats = nullptr;
+    PrtWorkspace ws;
+    ws.add(&d_o, 3 * m).add(&d_d, 3 * m).add(&d_rng, m).add(&d_rgb, 3 * m).add(&d_seg, m);
+    if (lit) xl.declare(ws, m, tex_on(c));
+    else xs.declare(ws, m, tex_on(c));
+    if (texel)
+        ws.add(&tl.x, 3 * m).add(&tl.w, 3 * m).add(&tl.tmax, m).add(&tl.contrib, 3 * m).add(&tl.ray_pb, m).add(&d_tocc, m).add(
+            &d_tstats, (size_t)2 * PRT_BKL_STAT_SLOTS);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    PrtBakeLightArgs la{};
+    if (texel) {
+        if ((rc = sync_light_tables(c))) return rc;
+        la = PrtBakeLightArgs{dev_lights(c), dev_mesh_lights(c), dev_light_clusters(c), env_on(c) ? dev_env(c) : DevEnv{}, c->sampling.clamp};
+        HIPCHECK(c, hipMemsetAsync(d_tstats, 0, 2 * PRT_BKL_STAT_SLOTS * sizeof(unsigned long long), c->stream));
+    }
+    const PrtRadianceQuery q1{q.max_depth, 1u, q.seed, q.first_sample};  // (one sample per ray: the states are given)
+    for (uint32_t s0 = 0; s0 < q.samples; s0 += cs) {
+        const uint32_t ccs = std::min(cs, q.samples - s0);
+        const uint32_t mm = ccs * n_list;
+        prt_launch_bk_rays(c->stream, n_list, ccs, q.first_sample + s0, q.seed, d_list, map, d_o, d_d, d_rng);
+        HIPCHECK(c, hipGetLastError());
+        if (texel) {
+            prt_launch_bkl_sample(c->stream, mesh_lights_on(c), env_on(c), clusters_on(c), n_list, ccs, q.first_sample + s0, q.seed, d_list, map,
+                                  d_d, la, tl);
+            HIPCHECK(c, hipGetLastError());
+        }
+        if (lit) {
+            PrtRadianceLitInfo li{0u, 0u};
+            if ((rc = enqueue_radiance_lit(c, q1, mm, 1u, d_o, d_d, d_rng, texel ? tl.ray_pb : nullptr, d_rgb, d_seg, xl, want_info ? &li : nullptr)))
+                return rc;
+            shadow[0] += li.shadow_rays;
+            shadow[1] += li.shadow_occluded;
+        } else if ((rc = enqueue_radiance(c, q1, mm, 1u, d_o, d_d, d_rng, d_rgb, d_seg, xs))) {
+            return rc;
+        }
+        if (texel) {  // the texels' shadow rays: prt_occluded's pipeline, then e onto the query's values
+            if ((rc = enqueue_query(c, mm, tl.x, tl.w, tl.tmax, nullptr, d_tocc))) return rc;
+            prt_launch_bkl_add(c->stream, mm, tl, d_tocc, d_rgb, d_tstats);
+            HIPCHECK(c, hipGetLastError());
+        }
+        if (out.moments.count) prt_launch_bka_sum(c->stream, n_list, ccs, first && s0 == 0u, d_list, d_rgb, d_seg, out.moments, out.counts);
+        else prt_launch_bk_sum(c->stream, n_list, ccs, first && s0 == 0u, d_list, d_rgb, d_seg, out.moments.rgb_sum, out.counts);
+        HIPCHECK(c, hipGetLastError());
+    }
+    if (texel && want_info) {  // (once per call of this function, and only where info is given)
+        unsigned long long st[2 * PRT_BKL_STAT_SLOTS];
+        HIPCHECK(c, hipMemcpyAsync(st, d_tstats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t k = 0; k < PRT_BKL_STAT_SLOTS; ++k) {
+            shadow[0] += st[2 * k];
+            shadow[1] += st[2 * k + 1];
+        }
+    }
+    return PRT_OK;
+}
+
+// Both forms of prt_bake_irradiance: the surface, q.samples samples of every covered texel, the gutter fill.
 static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* opt, void* out_rgb,
                            void* out_cov, bool device_out, PrtBakeInfo* info) {
     if (!c) return PRT_ERR_INVALID;
@@ -3746,66 +3839,10 @@ static int bake_irradiance(PrtContext* c, const PrtBakeTarget* target, const Prt
     const bool texel = lit && opt->texel_light != 0u && q->max_depth != 0u;
     uint64_t shadow[2] = {0u, 0u};
     if (n_cov != 0u) {
-        uint32_t cs = c->bake_chunk > 0 ? std::min((uint32_t)c->bake_chunk, q->samples) : radiance_chunk(c, *q, n_cov);
-        const size_t m = (size_t)cs * n_cov;
-        float *d_o, *d_d, *d_rgb;
-        uint32_t *d_rng, *d_seg;
-        RadianceScratch xs;
-        RadianceLitScratch xl;
-        PrtBakeLightRays tl{};
-        uint8_t* d_tocc = nullptr;
-        unsigned long long* d_tstats = nullptr;
-        PrtWorkspace ws;
-        ws.add(&d_o, 3 * m).add(&d_d, 3 * m).add(&d_rng, m).add(&d_rgb, 3 * m).add(&d_seg, m);
-        if (lit) xl.declare(ws, m, tex_on(c));
-        else xs.declare(ws, m, tex_on(c));
-        if (texel)
-            ws.add(&tl.x, 3 * m).add(&tl.w, 3 * m).add(&tl.tmax, m).add(&tl.contrib, 3 * m).add(&tl.ray_pb, m).add(&d_tocc, m).add(
-                &d_tstats, (size_t)2 * PRT_BKL_STAT_SLOTS);
-        if ((rc = commit(c, ws, c->scratch))) return rc;
-        PrtBakeLightArgs la{};
-        if (texel) {
-            if ((rc = sync_light_tables(c))) return rc;
-            la = PrtBakeLightArgs{dev_lights(c), dev_mesh_lights(c), dev_light_clusters(c), env_on(c) ? dev_env(c) : DevEnv{}, c->sampling.clamp};
-            HIPCHECK(c, hipMemsetAsync(d_tstats, 0, 2 * PRT_BKL_STAT_SLOTS * sizeof(unsigned long long), c->stream));
-        }
-        const PrtRadianceQuery q1{q->max_depth, 1u, q->seed, q->first_sample};  // (one sample per ray: the states are given)
-        for (uint32_t s0 = 0; s0 < q->samples; s0 += cs) {
-            const uint32_t ccs = std::min(cs, q->samples - s0);
-            const uint32_t mm = ccs * n_cov;
-            prt_launch_bk_rays(c->stream, n_cov, ccs, q->first_sample + s0, q->seed, x.list, x.map, d_o, d_d, d_rng);
-            HIPCHECK(c, hipGetLastError());
-            if (texel) {
-                prt_launch_bkl_sample(c->stream, mesh_lights_on(c), env_on(c), clusters_on(c), n_cov, ccs, q->first_sample + s0, q->seed, x.list,
-                                      x.map, d_d, la, tl);
-                HIPCHECK(c, hipGetLastError());
-            }
-            if (lit) {
-                PrtRadianceLitInfo li{0u, 0u};
-                if ((rc = enqueue_radiance_lit(c, q1, mm, 1u, d_o, d_d, d_rng, texel ? tl.ray_pb : nullptr, d_rgb, d_seg, xl, info ? &li : nullptr)))
-                    return rc;
-                shadow[0] += li.shadow_rays;
-                shadow[1] += li.shadow_occluded;
-            } else if ((rc = enqueue_radiance(c, q1, mm, 1u, d_o, d_d, d_rng, d_rgb, d_seg, xs))) {
-                return rc;
-            }
-            if (texel) {  // the texels' shadow rays: prt_occluded's pipeline, then e onto the query's values
-                if ((rc = enqueue_query(c, mm, tl.x, tl.w, tl.tmax, nullptr, d_tocc))) return rc;
-                prt_launch_bkl_add(c->stream, mm, tl, d_tocc, d_rgb, d_tstats);
-                HIPCHECK(c, hipGetLastError());
-            }
-            prt_launch_bk_sum(c->stream, n_cov, ccs, s0 == 0u, x.list, d_rgb, d_seg, x.rgb[0], x.counts);
-            HIPCHECK(c, hipGetLastError());
-        }
-        if (texel && info) {  // (once per call, and only where info is given)
-            unsigned long long st[2 * PRT_BKL_STAT_SLOTS];
-            HIPCHECK(c, hipMemcpyAsync(st, d_tstats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
-            HIPCHECK(c, hipStreamSynchronize(c->stream));
-            for (uint32_t k = 0; k < PRT_BKL_STAT_SLOTS; ++k) {
-                shadow[0] += st[2 * k];
-                shadow[1] += st[2 * k + 1];
-            }
-        }
+        BakeSums out;
+        out.moments.rgb_sum = x.rgb[0];
+        out.counts = x.counts;
+        if ((rc = enqueue_bake_samples(c, *q, lit, texel, x.list, n_cov, x.map, true, out, info != nullptr, shadow))) return rc;
     }
     int cur = 0;
     uint8_t* cov[2] = {x.map.cov, x.cov2};
@@ -3889,6 +3926,211 @@ int prt_bake_light_samples(PrtContext* c, const PrtBakeTarget* target, uint32_t 
     for (size_t i = 0; light && i < n; ++i)
         light[i] = (mesh_lights_on(c) && cand[i] != 0xFFFFFFFFu && cand[i] != PRT_LIGHT_ENVIRONMENT) ? c->hs.ml.cand_visible[cand[i]] : cand[i];
     return PRT_OK;
+}
+
+// ---- bake statistics and adaptive sampling (include/prt.h "Bake statistics and adaptive sampling") -----------
+struct BakeAdaptiveOut {
+    void *rgb_sum, *count, *sum_y, *sum_y2, *rgb_mean, *coverage;
+};
+
+// Both forms of prt_bake_irradiance_adaptive: prt_render_adaptive's loop over 8 x 8 blocks of texels.  Pass 0 is the bake's
+// own sequence over the covered texels; every later pass selects (k_bka_select, k_bka_blocks), lists the covered texels of the
+// active blocks in ascending order (k_bk_compact over the `active` bytes), reads the two lengths back and runs the same
+// sequence over that list.  k_bka_sum stands where k_bk_sum stands.
+static int bake_irradiance_adaptive(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* opt,
+                                    const PrtBakeAdaptive* cfg, const BakeAdaptiveOut& o, bool device_out, PrtBakeInfo* info,
+                                    PrtBakeAdaptiveInfo* ainfo) {
+    if (!c) return PRT_ERR_INVALID;
+    const char* who = "prt_bake_irradiance_adaptive";
+    if (!opt) return fail(c, PRT_ERR_INVALID, "%s: null options", who);
+    if (opt->reserved != 0u) return fail(c, PRT_ERR_INVALID, "%s: options.reserved = %u, expected 0", who, opt->reserved);
+    BakeTarget b;
+    int rc = check_bake(c, target, nullptr, false, &b);
+    if (rc) return rc;
+    if (!q) return fail(c, PRT_ERR_INVALID, "%s: null query", who);
+    if (const char* why = prt_bake_adaptive_refusal(cfg, b.W, b.H)) return fail(c, PRT_ERR_INVALID, "%s: %s", who, why);
+    if (!o.rgb_sum) return fail(c, PRT_ERR_INVALID, "%s: null rgb_sum", who);
+    if ((rc = need_device(c))) return rc;
+    EventPair tm;  // around the call's device work (PrtBakeInfo.device_ms)
+    if (info) {
+        HIPCHECK(c, tm.a.create(true));
+        HIPCHECK(c, tm.b.create(true));
+        HIPCHECK(c, hipEventRecord(ev(tm.a), c->stream));
+    }
+    BakeBufs x;
+    BakeAdaptiveBufs ax;
+    uint32_t counts[PRT_BAKE_COUNTERS] = {};
+    if ((rc = enqueue_bake_surface(c, &b, true, &x, counts, &ax))) return rc;
+    bake_info_surface(info, b, counts);
+    const size_t n = (size_t)b.W * b.H;
+    const uint32_t n_cov = counts[PRT_BAKE_CNT_COVERED], n_blocks = prt_bake_block_count(b.W, b.H);
+    HIPCHECK(c, hipMemsetAsync(x.rgb[0], 0, 3 * n * sizeof(float), c->stream));
+    HIPCHECK(c, hipMemsetAsync(ax.count, 0, n * sizeof(float), c->stream));
+    HIPCHECK(c, hipMemsetAsync(ax.sum_y, 0, n * sizeof(float), c->stream));
+    HIPCHECK(c, hipMemsetAsync(ax.sum_y2, 0, n * sizeof(float), c->stream));
+    const bool lit = opt->lighting != 0u && c->lighting != (uint32_t)PRT_LIGHTING_OFF;
+    const bool texel = lit && opt->texel_light != 0u && q->max_depth != 0u;
+    uint64_t shadow[2] = {0u, 0u};
+    BakeSums out;
+    out.moments = PrtBakeMoments{x.rgb[0], ax.count, ax.sum_y, ax.sum_y2};
+    out.counts = x.counts;
+    PrtBakeAdaptiveInfo ai{};
+    ai.blocks = n_blocks;
+    uint32_t added = cfg->min_spp;
+    if (n_cov != 0u) {  // pass 0: every covered texel, as prt_bake_irradiance_opt has it
+        const PrtRadianceQuery q0{q->max_depth, cfg->min_spp, q->seed, q->first_sample};
+        if ((rc = enqueue_bake_samples(c, q0, lit, texel, x.list, n_cov, x.map, true, out, info != nullptr, shadow))) return rc;
+        ai.texel_samples = (uint64_t)cfg->min_spp * n_cov;
+        ai.min_texel_spp = ai.max_texel_spp = cfg->min_spp;
+    }
+    if (cfg->max_spp > cfg->min_spp) {
+        bool any = false;
+        auto stopped_at = [&](uint32_t spp) {  // some covered texels end with this count
+            ai.min_texel_spp = any ? std::min(ai.min_texel_spp, spp) : spp;
+            ai.max_texel_spp = any ? std::max(ai.max_texel_spp, spp) : spp;
+            any = true;
+        };
+        HIPCHECK(c, hipMemsetAsync(ax.active, 0, n, c->stream));
+        const uint32_t* prev = nullptr;
+        uint32_t n_prev = n_blocks, len_prev = n_cov, cur = 0;
+        while (n_prev) {
+            // which of the blocks that were active until now still are, and their covered texels; ONE small wait per pass
+            const bool at_cap = added >= cfg->max_spp;
+            HIPCHECK(c, hipMemsetAsync(ax.sel, 0, PRT_BKA_COUNTERS * sizeof(uint32_t), c->stream));
+            prt_launch_bka_select(c->stream, b.W, b.H, x.map.cov, out.moments, prev, n_prev, cfg->threshold, cfg->noise_floor, at_cap, ax.flags,
+                                  ax.active, ax.sel);
+            HIPCHECK(c, hipGetLastError());
+            prt_launch_bka_blocks(c->stream, n_prev, prev, ax.flags, ax.blist[cur], ax.sel);
+            HIPCHECK(c, hipGetLastError());
+            prt_launch_bk_compact(c->stream, (uint32_t)n, ax.active, ax.tlist, ax.sel);
+            HIPCHECK(c, hipGetLastError());
+            uint32_t sel[PRT_BKA_COUNTERS] = {};
+            if ((rc = download(c, sel, ax.sel, (size_t)PRT_BKA_COUNTERS))) return rc;
+            HIPCHECK(c, hipStreamSynchronize(c->stream));
+            const uint32_t n_act = sel[PRT_BKA_CNT_ACTIVE], len = sel[PRT_BAKE_CNT_COVERED];
+            if (n_act > n_prev || len > len_prev || sel[PRT_BKA_CNT_CONVERGED] != n_prev - n_act)
+                return fail(c, PRT_ERR_HIP, "%s: the selection returned %u of %u blocks, %u of %u texels", who, n_act, n_prev, len, len_prev);
+            ai.blocks_converged += n_prev - n_act;
+            if (len < len_prev) stopped_at(added);
+            if (n_act == 0u) break;
+            if (at_cap) {
+                ai.blocks_capped = sel[PRT_BKA_CNT_CAPPED];
+                stopped_at(added);
+                break;
+            }
+            const uint32_t k = std::min(cfg->step_spp, cfg->max_spp - added);
+            const PrtRadianceQuery qk{q->max_depth, k, q->seed, q->first_sample + added};
+            if ((rc = enqueue_bake_samples(c, qk, lit, texel, ax.tlist, len, x.map, false, out, info != nullptr, shadow))) return rc;
+            added += k;
+            ai.texel_samples += (uint64_t)k * len;
+            ++ai.passes;
+            prev = ax.blist[cur];
+            n_prev = n_act;
+            len_prev = len;
+            cur ^= 1u;
+        }
+    }
+    // the mean, and the gutter fill on (coverage, mean) only: x.rgb[1] and ax.mean2 ping-pong
+    float* mean[2] = {x.rgb[1], ax.mean2};
+    uint8_t* cov[2] = {x.map.cov, x.cov2};
+    int cur = 0;
+    const bool want_mean = o.rgb_mean != nullptr || opt->dilate != 0u;
+    if (want_mean) {
+        prt_launch_bka_mean(c->stream, (uint32_t)n, x.rgb[0], ax.count, mean[0]);
+        HIPCHECK(c, hipGetLastError());
+        for (uint32_t p = 0; p < opt->dilate; ++p) {
+            prt_launch_bk_dilate(c->stream, b.W, b.H, cov[cur], mean[cur], cov[cur ^ 1], mean[cur ^ 1], x.counts);
+            HIPCHECK(c, hipGetLastError());
+            cur ^= 1;
+        }
+    }
+    const hipMemcpyKind kind = device_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIPCHECK(c, hipMemcpyAsync(o.rgb_sum, x.rgb[0], 3 * n * sizeof(float), kind, c->stream));
+    if (o.count) HIPCHECK(c, hipMemcpyAsync(o.count, ax.count, n * sizeof(float), kind, c->stream));
+    if (o.sum_y) HIPCHECK(c, hipMemcpyAsync(o.sum_y, ax.sum_y, n * sizeof(float), kind, c->stream));
+    if (o.sum_y2) HIPCHECK(c, hipMemcpyAsync(o.sum_y2, ax.sum_y2, n * sizeof(float), kind, c->stream));
+    if (o.rgb_mean) HIPCHECK(c, hipMemcpyAsync(o.rgb_mean, mean[cur], 3 * n * sizeof(float), kind, c->stream));
+    if (o.coverage) HIPCHECK(c, hipMemcpyAsync(o.coverage, cov[cur], n, kind, c->stream));
+    if (info) {
+        if ((rc = download(c, counts, x.counts, (size_t)PRT_BAKE_COUNTERS))) return rc;
+        HIPCHECK(c, hipEventRecord(ev(tm.b), c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        HIPCHECK(c, hipEventElapsedTime(&ms, ev(tm.a), ev(tm.b)));
+        info->n_filled = counts[PRT_BAKE_CNT_FILLED];
+        info->rays = ai.texel_samples;
+        info->segments = (uint64_t)counts[PRT_BAKE_CNT_SEGMENTS] | ((uint64_t)counts[PRT_BAKE_CNT_SEGMENTS + 1u] << 32);
+        info->shadow_rays = shadow[0];
+        info->shadow_occluded = shadow[1];
+        info->device_ms = (double)ms;
+    }
+    if (ainfo) *ainfo = ai;
+    return device_out ? PRT_OK : prt_synchronize(c);  // (host form: waits for the stream and reports a ray a walk had to give up)
+}
+
+int prt_bake_irradiance_adaptive(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* options,
+                                 const PrtBakeAdaptive* cfg, float* rgb_sum, float* count, float* sum_y, float* sum_y2, float* rgb_mean,
+                                 uint8_t* coverage, PrtBakeInfo* info, PrtBakeAdaptiveInfo* adaptive_info) {
+    return bake_irradiance_adaptive(c, target, q, options, cfg, BakeAdaptiveOut{rgb_sum, count, sum_y, sum_y2, rgb_mean, coverage}, false, info,
+                                    adaptive_info);
+}
+
+int prt_bake_irradiance_adaptive_device(PrtContext* c, const PrtBakeTarget* target, const PrtRadianceQuery* q, const PrtBakeOptions* options,
+                                        const PrtBakeAdaptive* cfg, void* d_rgb_sum, void* d_count, void* d_sum_y, void* d_sum_y2,
+                                        void* d_rgb_mean, void* d_coverage, PrtBakeInfo* info, PrtBakeAdaptiveInfo* adaptive_info) {
+    return bake_irradiance_adaptive(c, target, q, options, cfg, BakeAdaptiveOut{d_rgb_sum, d_count, d_sum_y, d_sum_y2, d_rgb_mean, d_coverage},
+                                    true, info, adaptive_info);
+}
+
+int prt_bake_block_select(PrtContext* c, uint32_t W, uint32_t H, const uint8_t* coverage, const float* count, const float* sum_y,
+                          const float* sum_y2, const uint32_t* prev, uint32_t n_prev, float threshold, float noise_floor, uint32_t* block_list,
+                          uint32_t* texel_list, uint32_t* counts) {
+    if (!c) return PRT_ERR_INVALID;
+    const char* who = "prt_bake_block_select";
+    if (W == 0u || H == 0u || W > PRT_TEX_MAX_SIZE || H > PRT_TEX_MAX_SIZE)
+        return fail(c, PRT_ERR_INVALID, "%s: a %u x %u map, expected 1 .. %u each way", who, W, H, PRT_TEX_MAX_SIZE);
+    if (!coverage || !count || !sum_y || !sum_y2 || !block_list || !texel_list || !counts) return fail(c, PRT_ERR_INVALID, "%s: null array", who);
+    const uint32_t n_blocks = prt_bake_block_count(W, H);
+    if (n_prev > n_blocks) return fail(c, PRT_ERR_INVALID, "%s: n_prev %u above the map's %u blocks", who, n_prev, n_blocks);
+    for (uint32_t i = 0; prev && i < n_prev; ++i)
+        if (prev[i] >= n_blocks) return fail(c, PRT_ERR_INVALID, "%s: prev[%u] = %u is not one of the %u blocks", who, i, prev[i], n_blocks);
+    if (const char* why = prt_bake_rule_refusal(threshold, noise_floor)) return fail(c, PRT_ERR_INVALID, "%s: %s", who, why);
+    int rc = need_device(c);
+    if (rc) return rc;
+    const size_t n = (size_t)W * H, n_ent = std::max(n_prev, 1u);
+    PrtBakeMoments m{};
+    uint8_t *d_cov, *d_active;
+    uint32_t *d_prev, *d_flags, *d_blist, *d_tlist, *d_sel;
+    PrtWorkspace ws;
+    ws.add(&d_cov, n).add(&m.count, n).add(&m.sum_y, n).add(&m.sum_y2, n).add(&d_active, n).add(&d_tlist, n);
+    ws.add(&d_prev, n_ent).add(&d_flags, n_ent).add(&d_blist, n_ent).add(&d_sel, (size_t)PRT_BKA_COUNTERS);
+    if ((rc = commit(c, ws, c->scratch))) return rc;
+    if ((rc = upload(c, d_cov, coverage, n)) || (rc = upload(c, m.count, count, n)) || (rc = upload(c, m.sum_y, sum_y, n)) ||
+        (rc = upload(c, m.sum_y2, sum_y2, n)))
+        return rc;
+    if (prev && n_prev && (rc = upload(c, d_prev, prev, n_prev))) return rc;
+    HIPCHECK(c, hipMemsetAsync(d_active, 0, n, c->stream));  // (the texels of blocks outside prev)
+    HIPCHECK(c, hipMemsetAsync(d_tlist, 0xFF, n * sizeof(uint32_t), c->stream));
+    HIPCHECK(c, hipMemsetAsync(d_blist, 0xFF, n_ent * sizeof(uint32_t), c->stream));
+    HIPCHECK(c, hipMemsetAsync(d_sel, 0, PRT_BKA_COUNTERS * sizeof(uint32_t), c->stream));
+    prt_launch_bka_select(c->stream, W, H, d_cov, m, prev ? d_prev : nullptr, n_prev, threshold, noise_floor, false, d_flags, d_active, d_sel);
+    HIPCHECK(c, hipGetLastError());
+    prt_launch_bka_blocks(c->stream, n_prev, prev ? d_prev : nullptr, d_flags, d_blist, d_sel);
+    HIPCHECK(c, hipGetLastError());
+    prt_launch_bk_compact(c->stream, (uint32_t)n, d_active, d_tlist, d_sel);
+    HIPCHECK(c, hipGetLastError());
+    uint32_t sel[PRT_BKA_COUNTERS] = {};
+    if ((rc = download(c, sel, d_sel, (size_t)PRT_BKA_COUNTERS))) return rc;
+    if (n_prev && (rc = download(c, block_list, d_blist, n_prev))) return rc;
+    if ((rc = download(c, texel_list, d_tlist, n))) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    counts[0] = sel[PRT_BKA_CNT_ACTIVE];
+    counts[1] = sel[PRT_BAKE_CNT_COVERED];
+    return PRT_OK;
+}
+
+int prt_bake_noise(uint64_t n, const float* count, const float* sum_y, const float* sum_y2, float noise_floor, float* rel_err) {
+    return prt_bake_noise_rule(n, count, sum_y, sum_y2, noise_floor, rel_err) ? PRT_OK : PRT_ERR_INVALID;
 }
 
 // ---- SH probes (include/prt.h "SH probes") -----------------------------------------------------------------

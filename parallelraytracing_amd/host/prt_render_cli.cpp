@@ -14,6 +14,7 @@
 //              [--frames N --orbit-deg D [--temporal [--temporal-max-history H]]]
 //              [--probe X,Y,Z --probe-size WxH --probe-lighting]
 //              [--bake WxH --bake-dilate N --bake-texel-light]
+//              [--bake WxH --bake-adaptive T [--min-spp N --spp-step N --max-spp N --noise-floor F] [--samples-out S.pfm] [--noise-out N.pfm]]
 //              [--probe-grid NXxNYxNZ --probe-box x0,y0,z0,x1,y1,z1 [--probe-order N] [--probe-lighting]]
 // --probe-grid NXxNYxNZ with --probe-box renders no frame: it writes PREFIX.pfm, the light probes of a cell-centred grid over
 // the box (x fastest; the Python package's probe_grid) as real spherical-harmonic coefficients (prt_probe_sh): one row per
@@ -23,6 +24,11 @@
 // (prt_bake_irradiance): --spp paths of up to --depth segments per covered texel, pi * sum / spp, top row first;
 // --bake-dilate N fills the gutters with N passes.  The first GPU; --lighting applies as it would to a frame.
 // --bake-texel-light (with --lighting nee|mis) also samples the lights at the texel itself (prt_bake_irradiance_opt).
+// --bake-adaptive T (with --bake) bakes with block-adaptive sampling (prt_bake_irradiance_adaptive) instead of --spp samples for
+// every texel: --min-spp (default 8) samples for every covered texel, then --spp-step (8) at a time for the 8x8 blocks of texels
+// that still hold one whose standard error exceeds T times (its mean luminance + --noise-floor), up to --max-spp (64);
+// PREFIX.pfm is pi * the mean.  --samples-out and --noise-out write the per-texel sample counts and the relative standard
+// errors (prt_bake_noise) as grey PFMs of the map's size.
 // --probe X,Y,Z renders no frame: it writes PREFIX.pfm, a lat-long radiance probe of --probe-size WxH texels (default 64x32)
 // at that point, --spp paths of up to --depth segments per texel along the texel centre's direction (prt_radiance), in the
 // layout --env reads (top row = the +Y pole): a probe of one scene can light another.  The first GPU; the estimator is the
@@ -105,7 +111,7 @@ int main(int argc, char** argv) {
     double probe_box[6] = {0, 0, 0, 0, 0, 0};
     bool bake = false;
     uint32_t bake_w = 0, bake_h = 0, bake_dilate = 0;
-    bool bake_texel_light = false;
+    bool bake_texel_light = false, bake_adaptive = false;
     std::vector<int> devices{0};
     float cam[3] = {5.0f, 5.0f, 8.0f};
     bool cam_set = false;
@@ -197,6 +203,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--bake-dilate") bake_dilate = (uint32_t)atoi(next());
         else if (a == "--bake-texel-light") bake_texel_light = true;
+        else if (a == "--bake-adaptive") { ad.threshold = (float)atof(next()); bake_adaptive = true; }
         else if (a == "--probe-size") {
             if (sscanf(next(), "%ux%u", &probe_w, &probe_h) != 2 || !probe_w || !probe_h) { fprintf(stderr, "--probe-size takes WxH\n"); return 2; }
         }
@@ -211,8 +218,12 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--ground-texture and --mesh-texture go with --ply (the presets have no ground quad or mesh of their own)\n");
         return 2;
     }
-    if (!adaptive && (!samples_out.empty() || !noise_out.empty())) {
-        fprintf(stderr, "--samples-out and --noise-out go with --adaptive\n");
+    if (!adaptive && !bake_adaptive && (!samples_out.empty() || !noise_out.empty())) {
+        fprintf(stderr, "--samples-out and --noise-out go with --adaptive or --bake-adaptive\n");
+        return 2;
+    }
+    if (bake_adaptive && !bake) {
+        fprintf(stderr, "--bake-adaptive goes with --bake\n");
         return 2;
     }
     if (feature_samples && !denoise && features_out.empty()) {
@@ -323,6 +334,31 @@ int main(int argc, char** argv) {
             if (!scene->MeshHasUVs(0)) { fprintf(stderr, "error: --bake: %s has no per-vertex UVs\n", ply.c_str()); return 1; }
             std::vector<float> irr;
             PrtBakeInfo bi{};
+            if (bake_adaptive) {
+                const PrtBakeAdaptive cfg{ad.min_spp, ad.step_spp, ad.max_spp, ad.threshold, ad.noise_floor, {0u, 0u, 0u}};
+                PrtBakeAdaptiveInfo ai{};
+                std::vector<float> count, sum_y, sum_y2;
+                r.BakeIrradianceAdaptive(0u, scene->mesh_uvs.at(0), bake_w, bake_h, cfg, irr, &count, &sum_y, &sum_y2, bake_dilate,
+                                         lighting != PRT_LIGHTING_OFF, nullptr, &bi, &ai, PRT_BAKE_MESH, 0u, bake_texel_light);
+                auto write_grey = [&](const std::string& path, const std::vector<float>& v) {
+                    std::vector<float> rgb(3 * v.size());
+                    for (size_t i = 0; i < v.size(); ++i) rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = v[i];
+                    return prt_write_pfm(path.c_str(), rgb.data(), bake_w, bake_h);
+                };
+                if (prt_write_pfm((out + ".pfm").c_str(), irr.data(), bake_w, bake_h)) { fprintf(stderr, "cannot write %s.pfm\n", out.c_str()); return 1; }
+                if (!samples_out.empty() && write_grey(samples_out, count)) { fprintf(stderr, "cannot write %s\n", samples_out.c_str()); return 1; }
+                if (!noise_out.empty()) {
+                    std::vector<float> noise(count.size());
+                    if (prt_bake_noise(count.size(), count.data(), sum_y.data(), sum_y2.data(), cfg.noise_floor, noise.data()) ||
+                        write_grey(noise_out, noise)) { fprintf(stderr, "cannot write %s\n", noise_out.c_str()); return 1; }
+                }
+                printf("adaptive bake: %ux%u texels, %llu covered, %llu filled, threshold %g, %u..%u spp in steps of %u: %u passes, %llu texel-samples, "
+                       "%u blocks: %u converged, %u at the cap, %u..%u spp per texel, max_depth %u, %llu segments, %.3f ms on the device -> %s.pfm\n",
+                       bake_w, bake_h, (unsigned long long)bi.n_covered, (unsigned long long)bi.n_filled, cfg.threshold, cfg.min_spp, cfg.max_spp,
+                       cfg.step_spp, ai.passes, (unsigned long long)ai.texel_samples, ai.blocks, ai.blocks_converged, ai.blocks_capped, ai.min_texel_spp,
+                       ai.max_texel_spp, depth, (unsigned long long)bi.segments, bi.device_ms, out.c_str());
+                return 0;
+            }
             r.BakeIrradiance(0u, scene->mesh_uvs.at(0), bake_w, bake_h, spp, irr, bake_dilate, lighting != PRT_LIGHTING_OFF, nullptr, &bi, PRT_BAKE_MESH, 0u,
                              bake_texel_light);
             if (prt_write_pfm((out + ".pfm").c_str(), irr.data(), bake_w, bake_h)) { fprintf(stderr, "cannot write %s.pfm\n", out.c_str()); return 1; }

@@ -517,6 +517,33 @@ public:
             throw Error(std::string("prt_bake_irradiance: ") + prt_last_error(c));
         for (float& v : irradiance) v = v * 3.14159274f / (float)samples;
     }
+    // The bake with per-texel statistics and block-adaptive sampling (prt_bake_irradiance_adaptive, include/prt.h "Bake
+    // statistics and adaptive sampling"): cfg.min_spp samples for every covered texel, then cfg.step_spp at a time for the
+    // covered texels of the 8x8 blocks that still hold an unconverged one, up to cfg.max_spp.  irradiance: pi * the mean
+    // (after `dilate` passes of the gutter fill, which touch the mean alone).  count / sum_y / sum_y2 / coverage (each may be
+    // null): the per-texel sample counts, the luminance moments and the coverage bytes.  The other arguments: BakeIrradiance's.
+    void BakeIrradianceAdaptive(uint32_t index, const float* uvs, uint32_t width, uint32_t height, const PrtBakeAdaptive& cfg,
+                                std::vector<float>& irradiance, std::vector<float>* count = nullptr, std::vector<float>* sum_y = nullptr,
+                                std::vector<float>* sum_y2 = nullptr, uint32_t dilate = 0, bool lighting = false,
+                                std::vector<uint8_t>* coverage = nullptr, PrtBakeInfo* info = nullptr, PrtBakeAdaptiveInfo* adaptive_info = nullptr,
+                                uint32_t kind = PRT_BAKE_MESH, uint32_t first_sample = 0, bool texel_light = false) {
+        PrtContext* c = prt_group_context(grp_, 0);
+        const PrtBakeTarget t{kind, index, uvs, width, height};
+        const PrtRadianceQuery q{max_depth_, 0u, seed_, first_sample};
+        const size_t n = (size_t)width * height;
+        std::vector<float> sum(3 * n, 0.0f);
+        irradiance.assign(3 * n, 0.0f);
+        for (std::vector<float>* v : {count, sum_y, sum_y2})
+            if (v) v->assign(n, 0.0f);
+        if (coverage) coverage->assign(n, 0);
+        if (texel_light && !lighting) throw Error("BakeIrradianceAdaptive: texel_light belongs to a light-sampled bake: pass lighting = true");
+        const PrtBakeOptions opt{lighting ? 1u : 0u, texel_light ? 1u : 0u, dilate, 0u};
+        if (prt_bake_irradiance_adaptive(c, &t, &q, &opt, &cfg, sum.data(), count ? count->data() : nullptr, sum_y ? sum_y->data() : nullptr,
+                                         sum_y2 ? sum_y2->data() : nullptr, irradiance.data(), coverage ? coverage->data() : nullptr, info,
+                                         adaptive_info))
+            throw Error(std::string("prt_bake_irradiance_adaptive: ") + prt_last_error(c));
+        for (float& v : irradiance) v = v * 3.14159274f;
+    }
     // Light probes on the first GPU's context (prt_probe_sh, include/prt.h "SH probes"): the radiance arriving at n_probes
     // points (positions: 3 floats each) as real spherical-harmonic coefficients, n_probes x (order + 1)^2 x 3 floats,
     // 4 pi * sum / samples.  lighting: Radiance's.  info (may be null): the counts of the call.

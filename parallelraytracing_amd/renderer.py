@@ -1421,6 +1421,95 @@ class HipWavefrontRenderer:
             return irr, {"sum": total, "coverage": cov, "info": self._bake_info(info)}
         return irr
 
+    # ---- bake statistics and adaptive sampling (include/prt.h "Bake statistics and adaptive sampling") -----------------
+    def bake_irradiance_adaptive(self, mesh=None, instance=None, size=(64, 64), uvs=None, threshold: float = 0.05, min_spp: int = 16,
+                                 step_spp: int = 16, max_spp: int = 256, noise_floor: float = 0.01, lighting: bool = False,
+                                 texel_light: bool = False, dilate: int = 0, seed=None, first_sample: int = 0, max_depth=None,
+                                 out: str = "numpy", return_info: bool = True) -> dict:
+        """A bake with per-texel statistics that goes on sampling only where the map is unconverged
+        (prt_bake_irradiance_adaptive): min_spp samples to every covered texel, then step_spp at a time to the covered texels
+        of the 8x8 blocks that still hold an unconverged one (the film's rule on the texel's luminance moments), up to max_spp.
+        A texel that ends with count n equals that texel of bake_irradiance(samples=n) bit for bit.  max_spp == min_spp: the
+        uniform bake with statistics.  Returns {"irradiance" [H, W, 3] = float32(pi) * the mean (after `dilate` passes of the
+        gutter fill, which touch the mean alone), "sum" [H, W, 3], "count", "sum_y", "sum_y2" [H, W] float32, "coverage"
+        [H, W] uint8 (0 none, 1 owned, 2 filled), and with return_info "info": the PrtBakeInfo fields and "adaptive": the
+        PrtBakeAdaptiveInfo fields}.  out = "torch": tensors on the renderer's device through the device form.
+
+        Denoising a lightmap is a composition of what exists, no new filter:
+
+            r = R.bake_irradiance_adaptive(mesh=0, size=(H, W), threshold=0.05, lighting=True, texel_light=True)
+            n = np.maximum(r["count"], 2.0)
+            m = r["sum_y"] / n
+            V = np.maximum(r["sum_y2"] / n - m * m, 0.0)            # per-sample variance of the luminance
+            var = (V / n).astype(np.float32)                         # variance of the mean: what the filter weighs
+            g = R.bake_surface(mesh=0, size=(H, W))                  # the guides
+            prim = np.where(g["coverage"] != 0, g["owner"], -1).astype(np.int32)
+            mean = r["sum"] / np.maximum(r["count"], 1.0)[..., None]
+            smooth = R.denoise_arrays(mean, var, np.ones_like(mean), g["normal"], g["position"], prim)"""
+        if out not in ("numpy", "torch"):
+            raise ValueError(f"out: {out!r}, expected 'numpy' or 'torch'")
+        if texel_light and not lighting:
+            raise ValueError("texel_light: the texel's light sample belongs to a light-sampled bake: pass lighting=True")
+        if int(dilate) < 0 or int(dilate) > 0xFFFFFFFF:
+            raise ValueError(f"dilate: {dilate}")
+        for name, v in (("min_spp", min_spp), ("step_spp", step_spp), ("max_spp", max_spp)):
+            if int(v) < 0 or int(v) > 0xFFFFFFFF:
+                raise ValueError(f"{name}: {v}")
+        opt = capi.PrtBakeOptions(int(bool(lighting)), int(bool(texel_light)), int(dilate), 0)
+        cfg = capi.PrtBakeAdaptive(int(min_spp), int(step_spp), int(max_spp), float(threshold), float(noise_floor))
+        t, keep, H, W = self._bake_target(mesh, instance, size, uvs)
+        q = capi.PrtRadianceQuery(int(self.max_depth if max_depth is None else max_depth), 0,
+                                  int(self.seed if seed is None else seed) & 0xFFFFFFFF, int(first_sample) & 0xFFFFFFFF)
+        info, ainfo = capi.PrtBakeInfo(), capi.PrtBakeAdaptiveInfo()
+        if out == "torch":
+            import torch
+            dev = self._torch_device()
+            total, mean = (torch.zeros((H, W, 3), dtype=torch.float32, device=dev) for _ in range(2))
+            cnt, sy, sy2 = (torch.zeros((H, W), dtype=torch.float32, device=dev) for _ in range(3))
+            cov = torch.zeros((H, W), dtype=torch.uint8, device=dev)
+            self._on_context_stream(lambda: capi.lib().prt_bake_irradiance_adaptive_device(
+                self._ctx, C.byref(t), C.byref(q), C.byref(opt), C.byref(cfg), *[C.c_void_p(a.data_ptr()) for a in (total, cnt, sy, sy2, mean, cov)],
+                C.byref(info) if return_info else None, C.byref(ainfo)))
+            irr = mean * torch.full((1, 1, 1), float(np.float32(np.pi)), dtype=torch.float32, device=dev)
+        else:
+            total, mean = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.float32)
+            cnt, sy, sy2 = (np.zeros((H, W), np.float32) for _ in range(3))
+            cov = np.zeros((H, W), np.uint8)
+            self._check(capi.lib().prt_bake_irradiance_adaptive(
+                self._ctx, C.byref(t), C.byref(q), C.byref(opt), C.byref(cfg), *[a.ctypes.data_as(_fp) for a in (total, cnt, sy, sy2, mean)],
+                cov.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info) if return_info else None, C.byref(ainfo)))
+            irr = mean * np.float32(np.pi)
+        r = {"irradiance": irr, "mean": mean, "sum": total, "count": cnt, "sum_y": sy, "sum_y2": sy2, "coverage": cov}
+        if return_info:
+            r["info"] = self._bake_info(info)
+            r["adaptive"] = {name: getattr(ainfo, name) for name, _ in capi.PrtBakeAdaptiveInfo._fields_}
+        return r
+
+    def bake_block_select(self, coverage, count, sum_y, sum_y2, threshold: float, noise_floor: float = 0.01, prev=None):
+        """prt_bake_block_select: the adaptive bake's selection on [H, W] arrays of coverage bytes, counts and moments.  prev:
+        block indices (None: every block, row-major).  Returns (block_list, texel_list): the entries of prev that are active,
+        in prev's order, and the covered texels of those blocks in ascending order."""
+        cov = np.ascontiguousarray(coverage, np.uint8)
+        imgs = [np.ascontiguousarray(a, np.float32) for a in (count, sum_y, sum_y2)]
+        if cov.ndim != 2 or any(a.shape != cov.shape for a in imgs):
+            raise ValueError("coverage, count, sum_y and sum_y2 must be [H, W]")
+        H, W = cov.shape
+        if prev is None:
+            n_prev, p_prev = ((W + 7) // 8) * ((H + 7) // 8), None
+        else:
+            prev = np.ascontiguousarray(prev, np.uint32).reshape(-1)
+            n_prev, p_prev = prev.size, prev.ctypes.data_as(_u32p)
+        blist = np.zeros(max(n_prev, 1), np.uint32)
+        tlist = np.zeros(max(H * W, 1), np.uint32)
+        counts = np.zeros(2, np.uint32)
+        self._check(capi.lib().prt_bake_block_select(self._ctx, W, H, cov.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                     *[a.ctypes.data_as(_fp) for a in imgs], p_prev, n_prev, float(threshold),
+                                                     float(noise_floor), blist.ctypes.data_as(_u32p), tlist.ctypes.data_as(_u32p),
+                                                     counts.ctypes.data_as(_u32p)))
+        if np.any(blist[int(counts[0]):n_prev] != 0xFFFFFFFF) or np.any(tlist[int(counts[1]):H * W] != 0xFFFFFFFF):
+            raise PrtError("prt_bake_block_select: an entry past a list's length is not 0xFFFFFFFF")
+        return blist[:int(counts[0])].copy(), tlist[:int(counts[1])].copy()
+
     def enable_timing(self, on: bool = True):
         self._check(capi.lib().prt_enable_timing(self._ctx, int(on)))
 
@@ -1961,6 +2050,20 @@ def sh_basis(d, order: int = 2) -> np.ndarray:
     if capi.lib().prt_sh_eval(flat.shape[0], flat.ctypes.data_as(_fp), int(order), Y.ctypes.data_as(_fp)):
         raise PrtError("prt_sh_eval failed")
     return Y.reshape(a.shape[:-1] + (K,))
+
+
+def bake_noise(count, sum_y, sum_y2, noise_floor: float = 0.01):
+    """The relative standard error of every texel's mean luminance from an adaptive bake's count and moments (prt_bake_noise;
+    a pure host function): 0 where count == 0 (an uncovered texel), +inf where count < 2, else sqrt(V / (count - 1)) /
+    (m + noise_floor) with m = sum_y / count, V = max(0, sum_y2 / count - m^2).  The arrays' shape is kept."""
+    c, a, q = (np.ascontiguousarray(x, np.float32) for x in (count, sum_y, sum_y2))
+    if a.shape != c.shape or q.shape != c.shape:
+        raise ValueError("count, sum_y and sum_y2 must have one shape")
+    out = np.zeros(c.shape, np.float32)
+    if capi.lib().prt_bake_noise(c.size, c.ctypes.data_as(_fp), a.ctypes.data_as(_fp), q.ctypes.data_as(_fp), float(noise_floor),
+                                 out.ctypes.data_as(_fp)):
+        raise PrtError("prt_bake_noise failed")
+    return out
 
 
 def sh_irradiance(coeffs, normals) -> np.ndarray:
